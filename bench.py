@@ -56,6 +56,9 @@ def parse():
     ap.add_argument("--cpu-seconds", type=float, default=10.0)
     ap.add_argument("--settle-seconds", type=float, default=0.5,
                     help="untimed steps run for this long before the --warmup steps so that the timed region reads settled clocks (reported as settle_ms)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (merged-cloud offsets, per-tick sums over every vertex, "
+                         "a fixed seeded sample of the vertices) as DIR/<name>.npy, float32 / float64, < 64 MB in all")
     args = ap.parse_args()
     if args.core_only:
         args.no_icp = args.no_cpu = args.no_host_path = args.no_mesh = args.no_tick_parallel = True
@@ -64,6 +67,50 @@ def parse():
 
 from bench_support.common import HBM_PEAK_GBS, leg, pmc_traffic, settle   # noqa: E402  (no torch, no HIP: safe before the ranks exist)
 from bench_support.launch import launch_probe, self_launch               # noqa: E402
+
+
+DUMP_SAMPLE_VERTICES = 1 << 20     # in all ticks together: 36 B each on disk (index f64 + XYZ f32 + RGBA f32)
+DUMP_SEED = 20251015
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(torch, vertices, offsets, out_dir):
+    """--dump-outputs: the merged clouds of the last timed step, as a caller of the timed path receives them (vertices u8 [T, capacity, 16]
+    = VertexC4ubV3f, offsets i32 [T, N + 1]), written as float32 / float64 .npy files:
+      offsets.npy              f64 [T, N + 1]  first vertex of every sensor's block, last column = vertices in the tick (exact)
+      tick_sums.npy            f64 [T, 7]      per tick, sums over EVERY vertex of X, Y, Z, R, G, B, A
+      vertex_sample_index.npy  f64 [T, M]      a fixed seeded sample of vertex positions: floor(u * n_tick), u ~ U[0, 1) sorted
+      vertex_sample_xyz.npy    f32 [T, M, 3]   X, Y, Z of the sampled vertices (NaN where the tick is empty)
+      vertex_sample_rgba.npy   f32 [T, M, 4]   R, G, B, A of the sampled vertices (byte values)
+    The sample positions depend on the seed and the tick's vertex count only, so two builds that agree on offsets sample the same vertices."""
+    os.makedirs(out_dir, exist_ok=True)
+    T = vertices.shape[0]
+    off = offsets.to(torch.int64)
+    n = off[:, -1]
+    M = max(1, min(DUMP_SAMPLE_VERTICES // max(T, 1), vertices.shape[1]))
+    u = np.sort(np.random.default_rng(DUMP_SEED).random((T, M)), axis=1)
+    idx = torch.from_numpy(u).to(vertices.device).mul_(n.to(torch.float64).unsqueeze(1)).floor_().to(torch.int64)
+    idx = torch.minimum(idx, (n - 1).clamp_min(0).unsqueeze(1))
+    raw = vertices[torch.arange(T, device=vertices.device).unsqueeze(1), idx].cpu().numpy()       # [T, M, 16] u8
+    xyz = np.ascontiguousarray(raw[..., 4:16]).view("<f4").reshape(T, M, 3).astype(np.float32)
+    rgba = raw[..., 0:4].astype(np.float32)
+    empty = (n == 0).cpu().numpy()
+    xyz[empty] = np.nan
+    rgba[empty] = np.nan
+    # sums over the whole cloud of every tick: the part of the output the sample does not show
+    sums = np.zeros((T, 7), dtype=np.float64)
+    for k, n_k in enumerate(n.cpu().tolist()):
+        v = vertices[k, :n_k]
+        sums[k, 0:3] = v[:, 4:16].contiguous().view(torch.float32).to(torch.float64).sum(dim=0).cpu().numpy()
+        sums[k, 3:7] = v[:, 0:4].to(torch.float64).sum(dim=0).cpu().numpy()
+    arrays = {"offsets": off.cpu().numpy().astype(np.float64), "tick_sums": sums,
+              "vertex_sample_index": idx.cpu().numpy().astype(np.float64), "vertex_sample_xyz": xyz, "vertex_sample_rgba": rgba}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f"--dump-outputs: {total} bytes exceed the {DUMP_LIMIT_BYTES}-byte budget")
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return sorted(arrays)
 
 
 def main():
@@ -199,6 +246,10 @@ def main():
     kstats = prof_plan.kernel_stats(reset=True)
     prof_plan.profile(False)
     thr_table, thr_build_ms = fus.plan.thresholds(copy=False)   # already built by the second warm-up run; reports its build time
+    # --dump-outputs: the last timed step's merged clouds, before anything else runs on the fusion buffers (N > 1: the whole rig's, rank 0)
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        dumped = dump_outputs(torch, *(ex.merged_cloud() if ex else (fus.vertices, fus.offsets)), args.dump_outputs)
 
     # run-to-run spread of the number above: the same K steps four more times, outside the region `value` comes from
     repeats = [B * args.steps / elapsed]
@@ -278,6 +329,7 @@ def main():
             "dtype": "f32",
             "data": "synthetic",
             **({"value_verified": verified} if verified is not None else {}),
+            **({"outputs_dumped": {"dir": args.dump_outputs, "files": [f + ".npy" for f in dumped]}} if dumped is not None else {}),
             **({"value_repeats": repeats, "value_spread_pct": 100.0 * (max(repeats) - min(repeats)) / float(np.median(repeats)),
                 "value_spread_note": "the same K steps timed four more times right after the region `value` comes from (value_repeats[0] = value); "
                                      "across fresh boxes the driver command has read 210-220 k (+-2 %)"} if len(repeats) > 1 else {}),

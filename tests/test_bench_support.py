@@ -102,3 +102,46 @@ def test_value_verification_catches_a_corrupted_cloud(orc):
     assert not compare_mesh(orc, *args, good[0], good[1], good[2], good[3], t2, toff)[0]
     d2 = good[0].copy(); d2[1234] ^= 1
     assert not compare_mesh(orc, *args, d2, *good[1:])[0]
+
+
+def test_dump_outputs_is_deterministic_small_and_faithful(tmp_path):
+    """bench.py --dump-outputs: float32 / float64 files within the budget, identical from run to run, and the samples and per-tick sums are
+    those of the clouds handed in (CPU tensors stand in for the HBM buffers)."""
+    import numpy as np
+    import torch
+    import bench
+    from livescan3d_amd import native
+
+    T, cap, N = 6, 5000, 3
+    rng = np.random.default_rng(7)
+    v = np.zeros((T, cap), native.VERTEX_DTYPE)
+    for f in "XYZ":
+        v[f] = rng.standard_normal((T, cap)).astype(np.float32)
+    for f in "RGBA":
+        v[f] = rng.integers(0, 256, (T, cap))
+    counts = rng.integers(0, cap // N, (T, N))
+    counts[2] = 0                                       # an empty tick
+    off = np.zeros((T, N + 1), np.int32)
+    off[:, 1:] = np.cumsum(counts, axis=1)
+    vt, ot = torch.from_numpy(v.view(np.uint8).reshape(T, cap, 16).copy()), torch.from_numpy(off)
+    names = bench.dump_outputs(torch, vt, ot, str(tmp_path / "a"))
+    assert names == bench.dump_outputs(torch, vt, ot, str(tmp_path / "b"))
+    got = {}
+    for n in names:
+        a, b = np.load(tmp_path / "a" / f"{n}.npy"), np.load(tmp_path / "b" / f"{n}.npy")
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, b, equal_nan=True), n
+        got[n] = a
+    assert sum(a.nbytes for a in got.values()) <= bench.DUMP_LIMIT_BYTES
+    assert np.array_equal(got["offsets"], off)
+    idx = got["vertex_sample_index"].astype(np.int64)
+    for k in range(T):
+        n = off[k, -1]
+        if n == 0:
+            assert np.isnan(got["vertex_sample_xyz"][k]).all() and not got["tick_sums"][k].any()
+            continue
+        assert 0 <= idx[k].min() and idx[k].max() < n
+        s = v[k, idx[k]]
+        assert np.array_equal(got["vertex_sample_xyz"][k], np.stack([s[c] for c in "XYZ"], axis=1))
+        assert np.array_equal(got["vertex_sample_rgba"][k], np.stack([s[c] for c in "RGBA"], axis=1).astype(np.float32))
+        want = [v[k, :n][c].astype(np.float64).sum() for c in "XYZRGBA"]
+        assert np.allclose(got["tick_sums"][k], want, rtol=1e-12, atol=1e-9)
