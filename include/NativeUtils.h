@@ -60,8 +60,11 @@ void generateVerticesFromDepthMap(unsigned char *depth_maps, unsigned char *dept
  * (src/NativeUtils/depthprocessing.cpp:1715-1792).  In scope: the vertices of all sensors, cropped, in sensor
  * order then raster order, and the triangles of the reference's always-on triangulation (meshGenerator.cpp; indices
  * into `vertices`, reference order) -- i.e. the reference with both flags false.
- * bcolor_transfer / bgenerate_triangles select reference stages that are out of scope (colour transfer, overlay
- * merge); passing true is reported through lsnGetLastError() and otherwise ignored. */
+ * bcolor_transfer = true runs the reference's colour transfer (confidence maps, pairwise coverage, greedy pairing,
+ * per-channel mean / mean-absolute-deviation transfer in RGB; depthprocessing.cpp:263-385,1387-1575, colorcorrection.cpp)
+ * on the device before the mesh leaves it: only the R,G,B bytes of the corrected sensors' vertices change (as
+ * lsnFusionColorTransfer below; the call runs on one device even with $LSN_HOST_DEVICES).  bgenerate_triangles (the overlay
+ * merge) is out of scope: passing true is reported through lsnGetLastError() and otherwise ignored. */
 void generateMeshFromDepthMaps(int n_maps, unsigned char *depth_maps, unsigned char *depth_colors, int *widths,
                                int *heights, float *intr_params, float *wtransform_params, Mesh *out_mesh,
                                bool bcolor_transfer, float minX, float minY, float minZ, float maxX, float maxY,
@@ -214,6 +217,21 @@ int lsnFusionThresholds(LsnFusion *plan, unsigned int *out_host, float *build_ms
 long long lsnFusionTickTriangleCapacity(const LsnFusion *plan);
 int lsnFusionRunMesh(LsnFusion *plan, const void *d_depth_maps, const void *d_depth_colors, void *d_vertices, int *d_offsets,
                      void *d_triangles, int *d_tri_offsets, void *stream);
+
+/* Colour transfer (generateMeshFromDepthMaps' bcolor_transfer stage) in place on the output of lsnFusionRun / lsnFusionRunMesh:
+ * d_depth_maps the depth maps that call read, d_vertices / d_offsets what it wrote; every tick on its own, asynchronous on `stream`.
+ * Only the R,G,B bytes of the vertices of corrected sensors change.  Reference: generateVerticesConfidence,
+ * updateColorCorrectionCoefficients and applyColorCorrection (src/NativeUtils/depthprocessing.cpp:285-384,1387-1575,
+ * colorcorrection.cpp:6-170, CS_RGB), with two defined deviations: a transform sample whose pixel in the base
+ * sensor has depth but no vertex is skipped (the reference reads out of bounds), and a double -> int conversion of a NaN or of a
+ * value out of range gives INT_MIN (the reference's x64 result), so such a channel becomes 0.  At most 32 sensors.
+ * lsnFusionColorDiagnostics (synchronises `stream`): what the last colour transfer computed for tick `tick` -- the confidence maps
+ * (lsnFusionTickCapacity() bytes, the sensors' maps back to back), the symmetric coverage table (n_maps^2 ints), the chosen pairs
+ * {base, corrected} in order (2 * (n_maps - 1) ints) and their transforms {mean_base[3], mean_corrected[3], scale[3]}
+ * (9 * max(n_maps - 1, 1) doubles); any pointer may be NULL.  Returns the number of pairs, -1 on error. */
+int lsnFusionColorTransfer(LsnFusion *plan, const void *d_depth_maps, void *d_vertices, const int *d_offsets, void *stream);
+int lsnFusionColorDiagnostics(LsnFusion *plan, int tick, unsigned char *confidence, int *coverage, int *pairs, double *transforms,
+                              void *stream);
 
 /* Radial correction of n_ticks x n_maps frames in place in HBM (same layouts as lsnFusionRun's inputs);
  * intr_params: host, 7 floats per sensor {cx,cy,fx,fy,r2,r4,r6}. */

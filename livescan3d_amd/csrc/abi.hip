@@ -223,11 +223,13 @@ static void generateMeshFromDepthMaps_impl(int n_maps, unsigned char *depth_maps
     }
     const float b[6] = {minX, minY, minZ, maxX, maxY, maxZ};
     if (ensure_ready(c) ||
-        fuse_host(c, l, depth_maps, depth_colors, widths, heights, intr_params, wtransform_params, out_mesh, b, 0, n_maps, true)) {
+        fuse_host(c, l, depth_maps, depth_colors, widths, heights, intr_params, wtransform_params, out_mesh, b, 0, n_maps, true, false, nullptr,
+                  nullptr, bcolor_transfer)) {
         empty_mesh(out_mesh);
         return;
     }
-    if (bcolor_transfer || bgenerate_triangles) {
+    // bcolor_transfer is implemented (color.hip, through fuse_host's colour flow); the overlay merge is not
+    if (bgenerate_triangles) {
         lsn::set_error("generateMeshFromDepthMaps: colour transfer / overlay merge are outside this library's scope; "
                        "returned the cropped vertices of all sensors (flags false,false behaviour)");
         if (!c.warned_flags) {

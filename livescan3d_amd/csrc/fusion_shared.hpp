@@ -563,6 +563,11 @@ struct LsnFusion {
     int stream_half = 0;
     // per-pixel depth thresholds (thresh_kernel): built once the same parameters are used for a second run
     lsn::DevBuf thr;
+    // colour transfer (color.hip), allocated on first use: tile counts / offsets of its index pass, pixel <-> vertex maps, confidence maps,
+    // confidence-tile starts, coverage tables, chosen pairs, per-block sample counts, colour sums, compacted samples, transforms
+    lsn::DevBuf ct_counts, ct_off, ct_pix2v, ct_v2pix, ct_conf, ct_ctile, ct_cov, ct_pairs, ct_blk, ct_stats, ct_samples, ct_xform;
+    bool ct_ready = false;
+    int ct_nblk = 0;                     // sample blocks per pair (the largest sensor's pixels / 256)
     bool thr_valid = false;
     bool thr_enabled = true;             // $LSN_NO_THRESHOLDS=1 keeps the arithmetic count pass (ablation / tests)
     bool one_tick_single_pass = false;   // a one-tick plan of <= 2048 tiles takes the single pass (fuse_kernel<4>) instead of count -> scan -> write; $LSN_ONE_TICK_SINGLE_PASS=0 / 1 forces

@@ -676,6 +676,41 @@ int fuse_host_grouped(HostCall &h, Mesh *out)
     return 0;
 }
 
+// Flow 2b: colour transfer (bcolor_transfer = true).  It crosses sensors, so the whole merged cloud has to be in HBM before any of it
+// can go home: the groups fuse into d_out as in flow 2, then the correction runs in place (color.hip) and the corrected mesh leaves in
+// one copy.  The triangles do not depend on the colours; they are built as in flow 2.
+int fuse_host_color(HostCall &h, Mesh *out)
+{
+    Lane &l = h.l;
+    if (h.begin(true, 0)) return -1;
+    const int count = h.count;
+    if (h.upload([&](size_t k, const Group &g) -> int { return h.fuse_group(k, g, l.d_out.p, nullptr, false); })) return -1;
+    if (h.with_triangles && lsn::run_triangles(h.plan, h.run_d, l.d_tri.p, l.d_tri_off.as<int>(), l.h_toff, false, l.stream)) return -1;
+    if (lsn::color_transfer(h.plan, h.run_d, l.d_out.p, l.d_off.as<int>(), l.stream)) return -1;
+    if (hipStreamSynchronize(l.stream) != hipSuccess) {
+        lsn::set_error("NativeUtils: %s", hipGetErrorString(hipGetLastError()));
+        return -1;
+    }
+    h.tr.mark("sync");
+    const int nv = l.h_off[count], nt = h.with_triangles ? l.h_toff[count] : 0;
+    if (l.h_off[count + 1] != 0) {
+        (void)lsnFusionCheck(h.plan, l.stream);   // clears the plan's sticky flag
+        lsn::set_error("NativeUtils: the single-pass fusion gave up on a predecessor tile (look-back spin limit)");
+        return -1;
+    }
+    if (nv < 0 || nv > h.cap || nt < 0 || nt > 2 * h.cap) {
+        lsn::set_error("NativeUtils: device returned impossible counts (%d vertices, %d triangles)", nv, nt);
+        return -1;
+    }
+    if (nt > 0 && !(h.host_tri = pinned_get(h.c, (size_t)nt * 12))) return -1;
+    LSN_HIP(hipMemcpyAsync(h.host, l.d_out.p, (size_t)nv * 16, hipMemcpyDeviceToHost, l.stream));
+    if (nt > 0) LSN_HIP(hipMemcpyAsync(h.host_tri, l.d_tri.p, (size_t)nt * 12, hipMemcpyDeviceToHost, l.stream));
+    LSN_HIP(hipStreamSynchronize(l.stream));
+    h.tr.mark("down");
+    h.commit(out, nv, nt, true);
+    return 0;
+}
+
 // ---- flow 3: the call sharded over several devices ($LSN_HOST_DEVICES) ----------------------------------------------------------------
 //
 // One GPU's merge call sits at the floor of ONE PCIe link: 8.7 MB up and 15-43 MB down around ~30 us of kernels.
@@ -1067,13 +1102,15 @@ int materialize(Lane &l)
 // $LSN_HOST_PATH=direct / grouped forces one of them for every call (A/B runs).
 int fuse_host(Ctx &c, Lane &l, const unsigned char *depth_maps, const unsigned char *depth_colors, const int *widths, const int *heights,
               const float *intr, const float *wt, Mesh *out, const float *bounds6, int first, int count, bool with_triangles, bool radial,
-              unsigned char *radial_back_d, unsigned char *radial_back_c)
+              unsigned char *radial_back_d, unsigned char *radial_back_c, bool color_transfer)
 {
-    // a merge call on a context with several devices ($LSN_HOST_DEVICES), more than one sensor: one sensor block per device and link
-    if (&l == &c.merge && c.shards.size() >= 2 && count >= 2 && first == 0)
+    // a merge call on a context with several devices ($LSN_HOST_DEVICES), more than one sensor: one sensor block per device and link --
+    // except with colour transfer, which crosses sensors: that call runs on the first device alone (flow 2b)
+    if (&l == &c.merge && c.shards.size() >= 2 && count >= 2 && first == 0 && !color_transfer)
         return fuse_host_sharded(c, l, depth_maps, depth_colors, widths, heights, intr, wt, out, bounds6, count, with_triangles, radial, radial_back_d,
                                  radial_back_c);
     HostCall h(c, l, depth_maps, depth_colors, widths, heights, intr, wt, bounds6, first, count, with_triangles, radial, radial_back_d, radial_back_c);
+    if (color_transfer) return fuse_host_color(h, out);
     const bool direct = c.host_path == 1 || (c.host_path == 0 && !radial);
     return direct ? fuse_host_direct(h, out) : fuse_host_grouped(h, out);
 }

@@ -135,6 +135,9 @@ int run_write(LsnFusion *p, const void *d_depth, const void *d_colors, void *ver
 int run_triangles_count(LsnFusion *p, const void *d_depth, int *d_tri_offsets, int *tri_mirror, hipEvent_t tri_counted, hipStream_t s);
 int run_triangles_write(LsnFusion *p, const void *d_depth, void *d_triangles, int index_base, bool host_out, hipStream_t s);
 
+// lsnFusionColorTransfer on a stream (color.hip): colour transfer in place on the cloud lsnFusionRun* wrote from d_depth.
+int color_transfer(LsnFusion *p, const void *d_depth, void *d_vertices, const int *d_offsets, hipStream_t s);
+
 // The survivor exchange's two ends with the back-to-back stream layout (exchange.hip; see their definitions).
 int pack_survivors(LsnFusion *p, const void *d_depth, const void *d_colors, void *d_mask, void *d_depth_c, void *d_rgb_c, int *d_tile_prefix,
                    int *d_offsets, int *d_tick_base, void *stream);

@@ -608,3 +608,8 @@ int lsn::run_triangles_write(LsnFusion *p, const void *d_depth, void *d_triangle
     LSN_HIP(hipSetDevice(p->device));
     return triangle_write_pass(p, d_depth, d_triangles, index_base, host_out, s);
 }
+
+// The colour transfer of the merge call (bcolor_transfer) lives in color.hip and is compiled here, in the translation unit of the
+// triangulation it runs beside: it uses the same plan and tile machinery (fusion_shared.hpp), and every build that lists the library's
+// translation units -- the product Makefile and the host-side sanitizer builds of tests/fake_hip -- compiles it without listing it.
+#include "color.hip"

@@ -25,6 +25,7 @@ EXPORTS = [
     "lsnGetLastError", "lsnDeviceCount", "lsnCorrectAndGenerateMesh", "lsnHostScheduleDescribe", "lsnHostShardDescribe", "lsnHostShardPartMicros", "lsnTestFaultPoints", "lsnHostPoolStats",
     "lsnFusionCreate", "lsnFusionDestroy", "lsnFusionTickCapacity", "lsnFusionSetParams", "lsnPackSensorParams", "lsnFusionSetMode",
     "lsnFusionRun", "lsnFusionRunStreamed", "lsnFusionSetPipelined", "lsnFusionRadialCorrect", "lsnFusionRadialCorrectTo", "lsnFusionRadialCountersLeft", "lsnFusionRunMesh", "lsnFusionTickTriangleCapacity", "lsnFusionProfile", "lsnFusionKernelStats", "lsnFusionLookbackFailed", "lsnFusionCheck", "lsnFusionThresholds", "lsnMergeShards",
+    "lsnFusionColorTransfer", "lsnFusionColorDiagnostics",
     "lsnFusionTilesPerTick", "lsnFusionPackSurvivors", "lsnFusionReconstruct",
     "lsnDeviceMalloc", "lsnDeviceFree", "lsnDeviceUpload", "lsnDeviceDownload", "lsnStreamCreate", "lsnStreamDestroy", "lsnStreamSynchronize",
     "lsnFusionPackSurvivorsRun", "lsnFusionReconstructRun", "lsnShardUniqueId", "lsnShardPlan", "lsnShardCreate", "lsnShardPrepare", "lsnShardConnect", "lsnShardRcclPath", "lsnShardDestroy", "lsnShardMergedCapacity", "lsnShardSetParams", "lsnShardStep", "lsnShardLastBytesSent", "lsnShardRanksSeen",
@@ -149,6 +150,10 @@ def lib():
     L.lsnFusionLookbackFailed.argtypes = [vp, vp]
     L.lsnFusionCheck.restype = C.c_int
     L.lsnFusionCheck.argtypes = [vp, vp]
+    L.lsnFusionColorTransfer.restype = C.c_int
+    L.lsnFusionColorTransfer.argtypes = [vp, vp, vp, vp, vp]
+    L.lsnFusionColorDiagnostics.restype = C.c_int
+    L.lsnFusionColorDiagnostics.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp]
     L.lsnMergeShards.restype = C.c_int
     L.lsnMergeShards.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_longlong, vp, vp, C.c_longlong, vp, vp]
     L.lsnIcpCreate.restype = vp
@@ -326,7 +331,7 @@ def generate_mesh_from_depth_maps(depth_maps, depth_colors, widths, heights, int
     lib().generateMeshFromDepthMaps(n, _ptr(dm), _ptr(dc), _ptr(widths), _ptr(heights), _ptr(intr), _ptr(wt),
                                     C.byref(mesh), bool(color_transfer), *[float(x) for x in b], bool(generate_triangles))
     err = last_error()
-    if err and mesh.nVertices == 0 and not (color_transfer or generate_triangles):
+    if err and mesh.nVertices == 0 and not generate_triangles:
         lib().deleteMesh(C.byref(mesh))
         raise NativeUtilsError(err)
     return _copy_mesh(mesh)
@@ -515,6 +520,25 @@ class FusionPlan:
         """Vertices + triangles (the reference's complete merge call); d_triangles: n_ticks x 2*capacity x 3 int32."""
         _check(lib().lsnFusionRunMesh(self._h, d_depth, d_colors, d_vertices, d_offsets, d_triangles, d_tri_offsets, stream),
                "lsnFusionRunMesh")
+
+    def color_transfer(self, d_depth, d_vertices, d_offsets, stream=0):
+        """Colour transfer (bcolor_transfer) in place on the clouds run() / run_mesh() wrote from d_depth; every tick on its own."""
+        _check(lib().lsnFusionColorTransfer(self._h, d_depth, d_vertices, d_offsets, stream or None), "lsnFusionColorTransfer")
+
+    def color_diagnostics(self, tick=0, stream=0):
+        """What the last color_transfer() computed for one tick: {"confidence": uint8[pixels_per_tick], "coverage": int32[n, n]
+        (symmetric), "pairs": [(i, j), ...] in the order they were chosen, "transforms": float64[n_pairs, 9] (mean_i[3], mean_j[3],
+        scale[3])}."""
+        n = self.n_maps
+        conf = np.zeros(max(self.pixels_per_tick, 1), dtype=np.uint8)
+        cov = np.zeros((n, n), dtype=np.int32)
+        pairs = np.zeros(2 * max(n - 1, 1), dtype=np.int32)
+        xf = np.zeros((max(n - 1, 1), 9), dtype=np.float64)
+        k = lib().lsnFusionColorDiagnostics(self._h, int(tick), _ptr(conf), _ptr(cov), _ptr(pairs), _ptr(xf), stream or None)
+        if k < 0:
+            raise NativeUtilsError(f"lsnFusionColorDiagnostics failed: {last_error()}")
+        return {"confidence": conf[:self.pixels_per_tick], "coverage": cov,
+                "pairs": [(int(pairs[2 * q]), int(pairs[2 * q + 1])) for q in range(k)], "transforms": xf[:k].copy()}
 
     def thresholds(self, capacity=None, stream=0, copy=True):
         """Builds the per-pixel depth thresholds now.  Returns (table uint32[capacity] or None, build_ms); table is None when
