@@ -63,8 +63,10 @@ void generateVerticesFromDepthMap(unsigned char *depth_maps, unsigned char *dept
  * bcolor_transfer = true runs the reference's colour transfer (confidence maps, pairwise coverage, greedy pairing,
  * per-channel mean / mean-absolute-deviation transfer in RGB; depthprocessing.cpp:263-385,1387-1575, colorcorrection.cpp)
  * on the device before the mesh leaves it: only the R,G,B bytes of the corrected sensors' vertices change (as
- * lsnFusionColorTransfer below; the call runs on one device even with $LSN_HOST_DEVICES).  bgenerate_triangles (the overlay
- * merge) is out of scope: passing true is reported through lsnGetLastError() and otherwise ignored. */
+ * lsnFusionColorTransfer below; the call runs on one device even with $LSN_HOST_DEVICES).  bgenerate_triangles = true (the
+ * cross-view overlay merge) is an opt-in, see lsnSetOverlayMerge: while the switch is off (the default) the call returns the
+ * unmerged mesh and reports the flag through lsnGetLastError(); while it is on it returns the merged mesh (as lsnFusionOverlayMerge
+ * below: same vertices, other triangles; one device; every sensor of the same size, else the unmerged mesh and a message). */
 void generateMeshFromDepthMaps(int n_maps, unsigned char *depth_maps, unsigned char *depth_colors, int *widths,
                                int *heights, float *intr_params, float *wtransform_params, Mesh *out_mesh,
                                bool bcolor_transfer, float minX, float minY, float minZ, float maxX, float maxY,
@@ -232,6 +234,23 @@ int lsnFusionRunMesh(LsnFusion *plan, const void *d_depth_maps, const void *d_de
 int lsnFusionColorTransfer(LsnFusion *plan, const void *d_depth_maps, void *d_vertices, const int *d_offsets, void *stream);
 int lsnFusionColorDiagnostics(LsnFusion *plan, int tick, unsigned char *confidence, int *coverage, int *pairs, double *transforms,
                               void *stream);
+
+/* Cross-view overlay merge (generateMeshFromDepthMaps' bgenerate_triangles stage) on the output of lsnFusionRun / lsnFusionRunMesh:
+ * d_depth_maps the raw depth maps that call read (for the confidence maps), d_vertices / d_offsets what it wrote (read only); every tick
+ * on its own, asynchronous on `stream`.  Rewrites d_triangles / d_tri_offsets in lsnFusionRunMesh's layout and capacity: the triangles
+ * of every sensor's reprojected depth map after the base / overlay schedule of mergeVerticesForViews (src/NativeUtils/depthprocessing.cpp
+ * :598-1099,1227-1313,1659-1691).  Independent of lsnFusionColorTransfer (neither reads what the other writes).  Every sensor must have
+ * the same size; at most 32 sensors.  Returns 0, -1 on error.
+ * lsnFusionOverlayDiagnostics (synchronises `stream`): for the last merge of tick `tick`, the reprojected maps as first built and as
+ * the merge left them (lsnFusionTickCapacity() u16 each, the sensors' maps back to back) and the point_assigned flag of every vertex
+ * (nVertices bytes); any pointer may be NULL.  Returns the number of assigned vertices, -1 on error.
+ * lsnSetOverlayMerge: the process-wide switch of generateMeshFromDepthMaps' merge (initially $LSN_OVERLAY_MERGE == "1"); returns the
+ * previous value. */
+int lsnFusionOverlayMerge(LsnFusion *plan, const void *d_depth_maps, const void *d_vertices, const int *d_offsets, void *d_triangles,
+                          int *d_tri_offsets, void *stream);
+int lsnFusionOverlayDiagnostics(LsnFusion *plan, int tick, unsigned short *reprojected, unsigned short *merged, unsigned char *assigned,
+                                void *stream);
+int lsnSetOverlayMerge(int enable);
 
 /* Radial correction of n_ticks x n_maps frames in place in HBM (same layouts as lsnFusionRun's inputs);
  * intr_params: host, 7 floats per sensor {cx,cy,fx,fy,r2,r4,r6}. */

@@ -207,6 +207,18 @@ extern "C" void generateVerticesFromDepthMap(unsigned char *depth_maps, unsigned
     if (!done && out_mesh) empty_mesh(out_mesh);   // nothing reaches the caller but an empty mesh and the message
 }
 
+// lsnSetOverlayMerge: whether generateMeshFromDepthMaps(..., bgenerate_triangles = true) runs the overlay merge; read once from $LSN_OVERLAY_MERGE
+static std::atomic<int> &overlay_merge_switch()
+{
+    static std::atomic<int> on{[] {
+        const char *e = getenv("LSN_OVERLAY_MERGE");
+        return e && strcmp(e, "1") == 0 ? 1 : 0;
+    }()};
+    return on;
+}
+
+extern "C" int lsnSetOverlayMerge(int enable) { return overlay_merge_switch().exchange(enable ? 1 : 0); }
+
 static void generateMeshFromDepthMaps_impl(int n_maps, unsigned char *depth_maps, unsigned char *depth_colors, int *widths, int *heights,
                                           float *intr_params, float *wtransform_params, Mesh *out_mesh, bool bcolor_transfer, float minX,
                                           float minY, float minZ, float maxX, float maxY, float maxZ, bool bgenerate_triangles)
@@ -222,10 +234,21 @@ static void generateMeshFromDepthMaps_impl(int n_maps, unsigned char *depth_maps
         return;
     }
     const float b[6] = {minX, minY, minZ, maxX, maxY, maxZ};
+    // the overlay merge runs when the caller asks for it and the process opted in (lsnSetOverlayMerge / $LSN_OVERLAY_MERGE); it needs
+    // every sensor of the same size (merge.hip): otherwise the unmerged mesh goes back, with a message
+    bool merge = bgenerate_triangles && overlay_merge_switch().load();
+    bool mixed = false;
+    for (int i = 1; merge && i < n_maps; i++) mixed |= widths[i] != widths[0] || heights[i] != heights[0];
+    merge &= !mixed;
     if (ensure_ready(c) ||
         fuse_host(c, l, depth_maps, depth_colors, widths, heights, intr_params, wtransform_params, out_mesh, b, 0, n_maps, true, false, nullptr,
-                  nullptr, bcolor_transfer)) {
+                  nullptr, bcolor_transfer, merge)) {
         empty_mesh(out_mesh);
+        return;
+    }
+    if (merge) return;
+    if (mixed) {
+        lsn::set_error("generateMeshFromDepthMaps: the overlay merge needs every sensor of the same size; returned the unmerged mesh");
         return;
     }
     // bcolor_transfer is implemented (color.hip, through fuse_host's colour flow); the overlay merge is not

@@ -568,6 +568,12 @@ struct LsnFusion {
     lsn::DevBuf ct_counts, ct_off, ct_pix2v, ct_v2pix, ct_conf, ct_ctile, ct_cov, ct_pairs, ct_blk, ct_stats, ct_samples, ct_xform;
     bool ct_ready = false;
     int ct_nblk = 0;                     // sample blocks per pair (the largest sensor's pixels / 256)
+    // overlay merge (merge.hip), allocated on its first call: index-pass counts, vertex / intermediate triangle offsets, confidence-tile
+    // starts, pixel <-> vertex maps and confidence maps of the raw maps, the reprojected maps (as first built / as modified) and their
+    // pixel -> vertex maps, point_assigned, per-vertex confidence and projection, raster scratch, mapped depth / tag maps, eroded mask
+    lsn::DevBuf mg_counts, mg_voff, mg_toff, mg_ctile, mg_pix2v, mg_v2pix, mg_conf, mg_depth0, mg_depth, mg_d2v, mg_assigned, mg_vconf, mg_proj,
+        mg_zmax, mg_key, mg_mdepth, mg_mtag, mg_ero;
+    bool mg_ready = false;
     bool thr_valid = false;
     bool thr_enabled = true;             // $LSN_NO_THRESHOLDS=1 keeps the arithmetic count pass (ablation / tests)
     bool one_tick_single_pass = false;   // a one-tick plan of <= 2048 tiles takes the single pass (fuse_kernel<4>) instead of count -> scan -> write; $LSN_ONE_TICK_SINGLE_PASS=0 / 1 forces

@@ -167,7 +167,8 @@ int parse_device_list(const char *text, int n_visible, std::vector<int> &out);
 // The calls.  The lane's lock is held by the caller; `out` is left untouched on failure (the export then returns an empty mesh).
 int fuse_host(Ctx &c, Lane &l, const unsigned char *depth_maps, const unsigned char *depth_colors, const int *widths, const int *heights,
               const float *intr, const float *wt, Mesh *out, const float *bounds6, int first, int count, bool with_triangles, bool radial = false,
-              unsigned char *radial_back_d = nullptr, unsigned char *radial_back_c = nullptr, bool color_transfer = false);
+              unsigned char *radial_back_d = nullptr, unsigned char *radial_back_c = nullptr, bool color_transfer = false,
+              bool overlay_merge = false);
 void radial_host(Ctx &c, Lane &l, int n_maps, unsigned char *depth_maps, unsigned char *depth_colors, const int *widths, const int *heights,
                  const float *intr_params);
 int materialize(Lane &l);                  // lsnLastMesh*: the mesh of the lane's last call in d_out / d_tri

@@ -676,17 +676,24 @@ int fuse_host_grouped(HostCall &h, Mesh *out)
     return 0;
 }
 
-// Flow 2b: colour transfer (bcolor_transfer = true).  It crosses sensors, so the whole merged cloud has to be in HBM before any of it
-// can go home: the groups fuse into d_out as in flow 2, then the correction runs in place (color.hip) and the corrected mesh leaves in
-// one copy.  The triangles do not depend on the colours; they are built as in flow 2.
-int fuse_host_color(HostCall &h, Mesh *out)
+// Flow 2b: colour transfer (bcolor_transfer = true) and / or the overlay merge (bgenerate_triangles = true with the merge switched on).
+// Both cross sensors, so the whole merged cloud has to be in HBM before any of it can go home: the groups fuse into d_out as in flow 2,
+// then the correction runs in place (color.hip), the merge rebuilds the triangles (merge.hip), and the mesh leaves in one copy.  Without
+// the merge the triangles do not depend on the colours; they are built as in flow 2.  The merge reads the positions alone, so the two
+// commute.
+int fuse_host_color(HostCall &h, Mesh *out, bool color_transfer, bool overlay_merge)
 {
     Lane &l = h.l;
     if (h.begin(true, 0)) return -1;
     const int count = h.count;
     if (h.upload([&](size_t k, const Group &g) -> int { return h.fuse_group(k, g, l.d_out.p, nullptr, false); })) return -1;
-    if (h.with_triangles && lsn::run_triangles(h.plan, h.run_d, l.d_tri.p, l.d_tri_off.as<int>(), l.h_toff, false, l.stream)) return -1;
-    if (lsn::color_transfer(h.plan, h.run_d, l.d_out.p, l.d_off.as<int>(), l.stream)) return -1;
+    if (h.with_triangles && !overlay_merge && lsn::run_triangles(h.plan, h.run_d, l.d_tri.p, l.d_tri_off.as<int>(), l.h_toff, false, l.stream))
+        return -1;
+    if (color_transfer && lsn::color_transfer(h.plan, h.run_d, l.d_out.p, l.d_off.as<int>(), l.stream)) return -1;
+    if (h.with_triangles && overlay_merge) {
+        if (lsn::overlay_merge(h.plan, h.run_d, l.d_out.p, l.d_off.as<int>(), l.d_tri.p, l.d_tri_off.as<int>(), l.stream)) return -1;
+        LSN_HIP(hipMemcpyAsync(l.h_toff, l.d_tri_off.as<int>(), sizeof(int) * (size_t)(count + 1), hipMemcpyDeviceToHost, l.stream));
+    }
     if (hipStreamSynchronize(l.stream) != hipSuccess) {
         lsn::set_error("NativeUtils: %s", hipGetErrorString(hipGetLastError()));
         return -1;
@@ -1102,15 +1109,15 @@ int materialize(Lane &l)
 // $LSN_HOST_PATH=direct / grouped forces one of them for every call (A/B runs).
 int fuse_host(Ctx &c, Lane &l, const unsigned char *depth_maps, const unsigned char *depth_colors, const int *widths, const int *heights,
               const float *intr, const float *wt, Mesh *out, const float *bounds6, int first, int count, bool with_triangles, bool radial,
-              unsigned char *radial_back_d, unsigned char *radial_back_c, bool color_transfer)
+              unsigned char *radial_back_d, unsigned char *radial_back_c, bool color_transfer, bool overlay_merge)
 {
     // a merge call on a context with several devices ($LSN_HOST_DEVICES), more than one sensor: one sensor block per device and link --
-    // except with colour transfer, which crosses sensors: that call runs on the first device alone (flow 2b)
-    if (&l == &c.merge && c.shards.size() >= 2 && count >= 2 && first == 0 && !color_transfer)
+    // except with colour transfer or the overlay merge, which cross sensors: that call runs on the first device alone (flow 2b)
+    if (&l == &c.merge && c.shards.size() >= 2 && count >= 2 && first == 0 && !color_transfer && !overlay_merge)
         return fuse_host_sharded(c, l, depth_maps, depth_colors, widths, heights, intr, wt, out, bounds6, count, with_triangles, radial, radial_back_d,
                                  radial_back_c);
     HostCall h(c, l, depth_maps, depth_colors, widths, heights, intr, wt, bounds6, first, count, with_triangles, radial, radial_back_d, radial_back_c);
-    if (color_transfer) return fuse_host_color(h, out);
+    if (color_transfer || overlay_merge) return fuse_host_color(h, out, color_transfer, overlay_merge);
     const bool direct = c.host_path == 1 || (c.host_path == 0 && !radial);
     return direct ? fuse_host_direct(h, out) : fuse_host_grouped(h, out);
 }

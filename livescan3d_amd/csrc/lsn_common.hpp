@@ -137,6 +137,9 @@ int run_triangles_write(LsnFusion *p, const void *d_depth, void *d_triangles, in
 
 // lsnFusionColorTransfer on a stream (color.hip): colour transfer in place on the cloud lsnFusionRun* wrote from d_depth.
 int color_transfer(LsnFusion *p, const void *d_depth, void *d_vertices, const int *d_offsets, hipStream_t s);
+// lsnFusionOverlayMerge on a stream (merge.hip): rewrites the triangles of the cloud lsnFusionRun* wrote from d_depth.
+int overlay_merge(LsnFusion *p, const void *d_depth, const void *d_vertices, const int *d_offsets, void *d_triangles, int *d_tri_offsets,
+                  hipStream_t s);
 
 // The survivor exchange's two ends with the back-to-back stream layout (exchange.hip; see their definitions).
 int pack_survivors(LsnFusion *p, const void *d_depth, const void *d_colors, void *d_mask, void *d_depth_c, void *d_rgb_c, int *d_tile_prefix,

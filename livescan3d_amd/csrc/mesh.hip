@@ -455,7 +455,9 @@ __global__ __launch_bounds__(kThreads, MODE == 0 ? LSN_TRI_MIN_WAVES : 1) void t
 }  // namespace
 
 // The triangle passes of a tick whose pixel -> vertex map is filled, in two halves (count -> scan | write); p->mu held.
-static bool tri_args(LsnFusion *p, const void *d_depth, void *d_triangles, TriArgs &t)
+// `pixmap`: another full pixel -> vertex map of the plan's layout (one int per pixel, -1 = none) to triangulate instead of the one the
+// vertex pass wrote (merge.hip: the reprojected maps of the overlay merge); the general-width form of the passes reads it.
+static bool tri_args(LsnFusion *p, const void *d_depth, void *d_triangles, TriArgs &t, const int *pixmap = nullptr)
 {
     t.frames = p->frames.as<FrameDesc>();
     t.tiles = p->tile_frame.as<TileDesc>();
@@ -473,13 +475,18 @@ static bool tri_args(LsnFusion *p, const void *d_depth, void *d_triangles, TriAr
     t.index_base = 0;
     t.tick_pix_stride = p->cap;
     t.tick_tri_stride = 2 * p->cap;
+    if (pixmap) {
+        t.pixmap = pixmap;
+        return false;
+    }
     return p->pixmap_compact && ((uintptr_t)d_depth & 15) == 0;   // the vertex pass wrote the compact map iff it ran its wide-load form
 }
 
-static int triangle_count_passes(LsnFusion *p, const void *d_depth, int *d_tri_offsets, hipStream_t s, const lsn::RunHooks *hooks)
+static int triangle_count_passes(LsnFusion *p, const void *d_depth, int *d_tri_offsets, hipStream_t s, const lsn::RunHooks *hooks,
+                                 const int *pixmap = nullptr)
 {
     TriArgs t;
-    const bool vec = tri_args(p, d_depth, nullptr, t);
+    const bool vec = tri_args(p, d_depth, nullptr, t, pixmap);
     const int grid = p->tiles_per_tick * p->n_ticks;
     if (vec) hipLaunchKernelGGL((tri_kernel<0, true>), dim3(grid), dim3(kThreads), 0, s, t);
     else     hipLaunchKernelGGL((tri_kernel<0, false>), dim3(grid), dim3(kThreads), 0, s, t);
@@ -493,10 +500,11 @@ static int triangle_count_passes(LsnFusion *p, const void *d_depth, int *d_tri_o
     return 0;
 }
 
-static int triangle_write_pass(LsnFusion *p, const void *d_depth, void *d_triangles, int index_base, bool host_out, hipStream_t s)
+static int triangle_write_pass(LsnFusion *p, const void *d_depth, void *d_triangles, int index_base, bool host_out, hipStream_t s,
+                               const int *pixmap = nullptr)
 {
     TriArgs t;
-    const bool vec = tri_args(p, d_depth, d_triangles, t);
+    const bool vec = tri_args(p, d_depth, d_triangles, t, pixmap);
     t.host_out = host_out;
     t.index_base = index_base;
     const size_t stage_bytes = sizeof(int) * (size_t)(stage_ints(t.win) + 3 * 64);
@@ -613,3 +621,6 @@ int lsn::run_triangles_write(LsnFusion *p, const void *d_depth, void *d_triangle
 // triangulation it runs beside: it uses the same plan and tile machinery (fusion_shared.hpp), and every build that lists the library's
 // translation units -- the product Makefile and the host-side sanitizer builds of tests/fake_hip -- compiles it without listing it.
 #include "color.hip"
+// The overlay merge (bgenerate_triangles) likewise: it re-runs these triangle passes on its reprojected maps and shares color.hip's
+// projection, index pass and confidence maps.
+#include "merge.hip"

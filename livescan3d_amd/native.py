@@ -25,7 +25,7 @@ EXPORTS = [
     "lsnGetLastError", "lsnDeviceCount", "lsnCorrectAndGenerateMesh", "lsnHostScheduleDescribe", "lsnHostShardDescribe", "lsnHostShardPartMicros", "lsnTestFaultPoints", "lsnHostPoolStats",
     "lsnFusionCreate", "lsnFusionDestroy", "lsnFusionTickCapacity", "lsnFusionSetParams", "lsnPackSensorParams", "lsnFusionSetMode",
     "lsnFusionRun", "lsnFusionRunStreamed", "lsnFusionSetPipelined", "lsnFusionRadialCorrect", "lsnFusionRadialCorrectTo", "lsnFusionRadialCountersLeft", "lsnFusionRunMesh", "lsnFusionTickTriangleCapacity", "lsnFusionProfile", "lsnFusionKernelStats", "lsnFusionLookbackFailed", "lsnFusionCheck", "lsnFusionThresholds", "lsnMergeShards",
-    "lsnFusionColorTransfer", "lsnFusionColorDiagnostics",
+    "lsnFusionColorTransfer", "lsnFusionColorDiagnostics", "lsnFusionOverlayMerge", "lsnFusionOverlayDiagnostics", "lsnSetOverlayMerge",
     "lsnFusionTilesPerTick", "lsnFusionPackSurvivors", "lsnFusionReconstruct",
     "lsnDeviceMalloc", "lsnDeviceFree", "lsnDeviceUpload", "lsnDeviceDownload", "lsnStreamCreate", "lsnStreamDestroy", "lsnStreamSynchronize",
     "lsnFusionPackSurvivorsRun", "lsnFusionReconstructRun", "lsnShardUniqueId", "lsnShardPlan", "lsnShardCreate", "lsnShardPrepare", "lsnShardConnect", "lsnShardRcclPath", "lsnShardDestroy", "lsnShardMergedCapacity", "lsnShardSetParams", "lsnShardStep", "lsnShardLastBytesSent", "lsnShardRanksSeen",
@@ -154,6 +154,12 @@ def lib():
     L.lsnFusionColorTransfer.argtypes = [vp, vp, vp, vp, vp]
     L.lsnFusionColorDiagnostics.restype = C.c_int
     L.lsnFusionColorDiagnostics.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp]
+    L.lsnFusionOverlayMerge.restype = C.c_int
+    L.lsnFusionOverlayMerge.argtypes = [vp, vp, vp, vp, vp, vp, vp]
+    L.lsnFusionOverlayDiagnostics.restype = C.c_int
+    L.lsnFusionOverlayDiagnostics.argtypes = [vp, C.c_int, vp, vp, vp, vp]
+    L.lsnSetOverlayMerge.restype = C.c_int
+    L.lsnSetOverlayMerge.argtypes = [C.c_int]
     L.lsnMergeShards.restype = C.c_int
     L.lsnMergeShards.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_longlong, vp, vp, C.c_longlong, vp, vp]
     L.lsnIcpCreate.restype = vp
@@ -317,9 +323,22 @@ def _copy_mesh(mesh):
     return verts, tris
 
 
+def set_overlay_merge(enable):
+    """lsnSetOverlayMerge: the process-wide switch of generateMeshFromDepthMaps' overlay merge.  Returns the previous value (bool)."""
+    return bool(lib().lsnSetOverlayMerge(1 if enable else 0))
+
+
 def generate_mesh_from_depth_maps(depth_maps, depth_colors, widths, heights, intr, wt, bounds,
-                                  color_transfer=False, generate_triangles=False):
-    """KinectServer.GenerateMesh (KinectServer.cs:354-374).  Returns (vertices[VERTEX_DTYPE], triangles int32)."""
+                                  color_transfer=False, generate_triangles=False, overlay_merge=None):
+    """KinectServer.GenerateMesh (KinectServer.cs:354-374).  Returns (vertices[VERTEX_DTYPE], triangles int32).
+    overlay_merge: None leaves the process-wide switch (lsnSetOverlayMerge) as it is; True / False sets it for this call alone."""
+    if overlay_merge is not None:
+        prev = set_overlay_merge(overlay_merge)
+        try:
+            return generate_mesh_from_depth_maps(depth_maps, depth_colors, widths, heights, intr, wt, bounds, color_transfer,
+                                                 generate_triangles)
+        finally:
+            set_overlay_merge(prev)
     require_gpu()
     widths, heights = _as(widths, np.int32), _as(heights, np.int32)
     n = len(widths)
@@ -539,6 +558,24 @@ class FusionPlan:
             raise NativeUtilsError(f"lsnFusionColorDiagnostics failed: {last_error()}")
         return {"confidence": conf[:self.pixels_per_tick], "coverage": cov,
                 "pairs": [(int(pairs[2 * q]), int(pairs[2 * q + 1])) for q in range(k)], "transforms": xf[:k].copy()}
+
+    def overlay_merge(self, d_depth, d_vertices, d_offsets, d_triangles, d_tri_offsets, stream=0):
+        """Overlay merge (bgenerate_triangles) on the clouds run() / run_mesh() wrote from d_depth: rewrites the triangles and their
+        offsets (run_mesh's layout); every tick on its own."""
+        _check(lib().lsnFusionOverlayMerge(self._h, d_depth, d_vertices, d_offsets, d_triangles, d_tri_offsets, stream or None),
+               "lsnFusionOverlayMerge")
+
+    def overlay_diagnostics(self, tick=0, n_vertices=None, stream=0):
+        """What the last overlay_merge() left for one tick: {"reprojected": uint16[pixels_per_tick] (step 1), "merged": uint16
+        [pixels_per_tick] (the final maps), "assigned": uint8[n_vertices] (point_assigned), "n_assigned": int}."""
+        rep = np.zeros(max(self.pixels_per_tick, 1), dtype=np.uint16)
+        mer = np.zeros(max(self.pixels_per_tick, 1), dtype=np.uint16)
+        asg = np.zeros(max(int(self.capacity), 1), dtype=np.uint8)
+        k = lib().lsnFusionOverlayDiagnostics(self._h, int(tick), _ptr(rep), _ptr(mer), _ptr(asg), stream or None)
+        if k < 0:
+            raise NativeUtilsError(f"lsnFusionOverlayDiagnostics failed: {last_error()}")
+        nv = int(self.capacity) if n_vertices is None else int(n_vertices)
+        return {"reprojected": rep[:self.pixels_per_tick], "merged": mer[:self.pixels_per_tick], "assigned": asg[:nv].copy(), "n_assigned": k}
 
     def thresholds(self, capacity=None, stream=0, copy=True):
         """Builds the per-pixel depth thresholds now.  Returns (table uint32[capacity] or None, build_ms); table is None when
