@@ -239,13 +239,6 @@ constexpr int kSpinLimit = 1 << 20;
 // Mode 2 (single pass, one look-back per TILE) tags its words instead of clearing them: bits 63..34 = the launch's epoch,
 // 33..32 = flag, low 32 bits = value; a word of another epoch reads as "empty".
 constexpr int kEpochShift = 34;
-#ifndef LSN_LOOK_SLOTS
-#define LSN_LOOK_SLOTS 1
-#endif
-#ifndef LSN_LOOK_AGENT_ONLY
-#define LSN_LOOK_AGENT_ONLY 0
-#endif
-constexpr int kLookSlots = LSN_LOOK_SLOTS;   // predecessor words per lane and round trip of the look-back (x 64 lanes); build-time for A/B runs
 constexpr unsigned long long kTileAggregate = 1ull << 32, kTilePrefix = 2ull << 32;
 
 // Exclusive prefix of this tile inside its tick, by decoupled look-back (wave 0 of the workgroup; 64 predecessors per poll).
@@ -263,56 +256,42 @@ __device__ __forceinline__ int tile_lookback(const FuseArgs &a, int tick, int ti
     int pos = tile - 1 - lane;  // lane 0 looks at the nearest predecessor
     bool done = tile == 0;
     int spins = 0;
-    static_assert(kLookSlots >= 1 && kLookSlots <= 16, "LSN_LOOK_SLOTS");
-    const bool near_polls = a.n_ticks > 1 && !LSN_LOOK_AGENT_ONLY;
+    const bool near_polls = a.n_ticks > 1;
     while (!done) {
-        // kLookSlots x 64 predecessors per round trip: the words of all slots are in flight together, then slot after slot is evaluated like
-        // one 64-wide poll.  Built for one-tick launches, where every tile is resident, publishes its aggregate at about the same time and a
-        // tile far down the tick sums hundreds of aggregates in dependent rounds of 64 -- and measured SLOWER the wider the window (8 x 512x424,
-        // one tick: 16.1 us with 1 slot, 16.0 with 4, 18.1 with 8, 19.0 with 16; 16 x 1024x1024: 85 / 104 / 128 / 143 us; 64 ticks: 359 / 370 /
-        // 416 / 507 us -- profiles/r05_ab_lookback.txt): the polls are uncached 8-byte loads and their number, not the depth of the chain, is
-        // what costs.  The default stays 1 slot; -DLSN_LOOK_SLOTS=n rebuilds the A/B.
-        unsigned long long ws[kLookSlots];
-#pragma unroll
-        for (int j = 0; j < kLookSlots; j++) {
-            const int q = pos - 64 * j;
-            ws[j] = tag | kTilePrefix;  // before the first tile: prefix 0
-            if (q >= 0) {
-                // most polls take the short way (sc0: past the CU's L1 only; the word is in this XCD's L2 when the producer ran on
-                // this XCD); every fourth goes to memory (agent scope), so a producer on another XCD is seen as well -- a stale L2
-                // line can only read as "empty" (epoch tag).  A one-tick launch spreads the tick's tiles over all XCDs: every poll goes to memory
-                if (near_polls && (spins & 3) != 3) ws[j] = __hip_atomic_load(&st[q], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                else ws[j] = __hip_atomic_load(&st[q], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
+        // One 64-wide poll per round trip.  Windows of 1 / 4 / 8 / 16 x 64 predecessors in flight per round trip (for one-tick launches,
+        // where a tile far down the tick sums hundreds of aggregates in dependent rounds) measured slower the wider they were (8 x 512x424,
+        // one tick: 16.1 / 16.0 / 18.1 / 19.0 us; 16 x 1024x1024: 85 / 104 / 128 / 143 us; 64 ticks: 359 / 370 / 416 / 507 us --
+        // profiles/r05_ab_lookback.txt): the polls are uncached 8-byte loads and their number, not the depth of the chain, is what costs.
+        unsigned long long w = tag | kTilePrefix;  // before the first tile: prefix 0
+        if (pos >= 0) {
+            // most polls take the short way (sc0: past the CU's L1 only; the word is in this XCD's L2 when the producer ran on
+            // this XCD); every fourth goes to memory (agent scope), so a producer on another XCD is seen as well -- a stale L2
+            // line can only read as "empty" (epoch tag).  A one-tick launch spreads the tick's tiles over all XCDs: every poll goes to memory
+            if (near_polls && (spins & 3) != 3) w = __hip_atomic_load(&st[pos], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            else w = __hip_atomic_load(&st[pos], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
         bool again = false;
-#pragma unroll
-        for (int j = 0; j < kLookSlots; j++) {
-            if (done || again) break;
-            const unsigned long long w = ws[j];
-            const unsigned int flag = (w >> kEpochShift) == a.epoch ? (unsigned int)(w >> 32) & 3u : 0u;
-            const unsigned long long pref = __ballot(flag == 2);
-            const int first = pref ? __ffsll((long long)pref) - 1 : 63;
-            const unsigned long long relevant = first >= 63 ? ~0ull : ((2ull << first) - 1ull);
-            const bool poisoned = (__ballot(flag == 3) & relevant) != 0;
-            if (poisoned || (__ballot(flag == 0) & relevant) != 0) {
-                if (poisoned || ++spins > kSpinLimit) {
-                    if (lane == 0) {
-                        atomicExch(a.error_flag, 1);
-                        if (a.offsets_mirror) a.offsets_mirror[a.n_frames + 1] = 1;
-                        __hip_atomic_store(&st[tile], tag | (3ull << 32), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    }
-                    return -1;
+        const unsigned int flag = (w >> kEpochShift) == a.epoch ? (unsigned int)(w >> 32) & 3u : 0u;
+        const unsigned long long pref = __ballot(flag == 2);
+        const int first = pref ? __ffsll((long long)pref) - 1 : 63;
+        const unsigned long long relevant = first >= 63 ? ~0ull : ((2ull << first) - 1ull);
+        const bool poisoned = (__ballot(flag == 3) & relevant) != 0;
+        if (poisoned || (__ballot(flag == 0) & relevant) != 0) {
+            if (poisoned || ++spins > kSpinLimit) {
+                if (lane == 0) {
+                    atomicExch(a.error_flag, 1);
+                    if (a.offsets_mirror) a.offsets_mirror[a.n_frames + 1] = 1;
+                    __hip_atomic_store(&st[tile], tag | (3ull << 32), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 }
-                __builtin_amdgcn_s_sleep(1);
-                pos -= 64 * j;   // the slots before this one are summed: the next round starts here
-                again = true;
-                break;
+                return -1;
             }
+            __builtin_amdgcn_s_sleep(1);
+            again = true;   // the same 64 predecessors again
+        } else {
             acc += wave_sum(lane <= first ? (int)(unsigned int)w : 0);
             if (pref) done = true;
         }
-        if (!done && !again) pos -= 64 * kLookSlots;
+        if (!done && !again) pos -= 64;
     }
     if (lane == 0 && tile != 0)
         __hip_atomic_store(&st[tile], tag | kTilePrefix | (unsigned int)(acc + tile_tot), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -356,8 +335,7 @@ __global__ __launch_bounds__(kThreads) void fuse_kernel(const FuseArgs a)
     tile += a.tile0;   // a launch over a group of sensors of a one-tick plan (run_frames); 0 everywhere else
     // The write pass takes the ticks last to first: what the count pass read last is still in the Infinity Cache (64 ticks of depth are
     // 222 MB against 256 MB of cache, and in the forward order the colours streaming through evict exactly the depth that is needed
-    // next).  Worth 0-2 % of the step, never less than nothing (A/B/B/A on three boxes: 0.3007 -> 0.2951 / 0.2966 ms, 0.2946 -> 0.2921, 0.2976 against 0.2973;
-    // $LSN_WRITE_FORWARD=1 undoes it).
+    // next).  Worth 0-2 % of the step, never less than nothing (A/B/B/A on three boxes: 0.3007 -> 0.2951 / 0.2966 ms, 0.2946 -> 0.2921, 0.2976 against 0.2973).
     if (MODE == 1 && a.reverse_ticks) tick = a.n_ticks - 1 - tick;
     const int lin = tick * a.tiles_per_tick + tile;
 
@@ -681,7 +659,6 @@ static LsnFusion * lsnFusionCreate_impl(int device, int n_ticks, int n_maps, con
     LsnFusion *p = new (std::nothrow) LsnFusion();
     if (!p) return nullptr;
     p->device = device;
-    if (const char *env = getenv("LSN_TILES_PER_RUN")) p->tiles_per_run_override = atoi(env);
     if (const char *env = getenv("LSN_NO_THRESHOLDS")) p->thr_enabled = atoi(env) == 0;
     if (const char *env = getenv("LSN_LAZY_RGB")) p->lazy_rgb = atoi(env) != 0;
 
@@ -994,9 +971,8 @@ void lsn::fill_args(LsnFusion *p, FuseArgs &a, const void *d_depth, const void *
     {
         const long long total = (long long)p->tiles_per_tick * p->n_ticks;
         long long tpr = total / (6ll * 7 * 256);
-        if (p->tiles_per_run_override > 0) tpr = p->tiles_per_run_override;
         if (tpr < 1) tpr = 1;
-        if (tpr > 8 && p->tiles_per_run_override <= 0) tpr = 8;
+        if (tpr > 8) tpr = 8;
         if (tpr > p->tiles_per_tick) tpr = p->tiles_per_tick;
         a.tiles_per_run = (int)tpr;
         a.runs_per_tick = (p->tiles_per_tick + a.tiles_per_run - 1) / a.tiles_per_run;
@@ -1011,10 +987,7 @@ void lsn::fill_args(LsnFusion *p, FuseArgs &a, const void *d_depth, const void *
     a.tile_counts_next = nullptr;
     a.thr = p->thr_valid ? p->thr.as<unsigned int>() : nullptr;
     a.tile0 = 0;
-    {
-        static const int fwd = getenv("LSN_WRITE_FORWARD") ? atoi(getenv("LSN_WRITE_FORWARD")) : 0;
-        a.reverse_ticks = fwd ? 0 : 1;
-    }
+    a.reverse_ticks = 1;   // always (see fuse_kernel)
     a.host_out = 0;
     a.offsets_mirror = nullptr;
     a.group_end_mirror = nullptr;
@@ -1048,19 +1021,15 @@ int lsn::ensure_thresholds(LsnFusion *p, hipStream_t s)
 void lsn::launch_count(LsnFusion *p, bool vec, hipStream_t s, const FuseArgs &a)
 {
     if (a.thr) {
-        static const int tune = getenv("LSN_TICK_GROUP") ? atoi(getenv("LSN_TICK_GROUP")) : 0;
-        int G = tune ? tune : (a.n_ticks >= 8 ? 8 : (a.n_ticks >= 4 ? 4 : 1));
-        if (G != 16 && G != 8 && G != 4 && G != 2) G = 1;
+        const int G = a.n_ticks >= 8 ? 8 : (a.n_ticks >= 4 ? 4 : 1);
         const int grid = p->tiles_per_tick * ((a.n_ticks + G - 1) / G);
 #define LSN_COUNT_THR(GG)                                                                                         \
     do {                                                                                                          \
         if (vec) hipLaunchKernelGGL((count_thr_kernel<true, GG>), dim3(grid), dim3(kThreads), 0, s, a);           \
         else     hipLaunchKernelGGL((count_thr_kernel<false, GG>), dim3(grid), dim3(kThreads), 0, s, a);          \
     } while (0)
-        if (G == 16) LSN_COUNT_THR(16);
-        else if (G == 8) LSN_COUNT_THR(8);
+        if (G == 8) LSN_COUNT_THR(8);
         else if (G == 4) LSN_COUNT_THR(4);
-        else if (G == 2) LSN_COUNT_THR(2);
         else LSN_COUNT_THR(1);
 #undef LSN_COUNT_THR
     } else {
@@ -1215,8 +1184,8 @@ int lsn::run_locked(LsnFusion *p, const void *d_depth, const void *d_colors, voi
         // block order: chunks of 16 consecutive tiles, every tick's chunk before the next chunk -- the ~2000 resident workgroups
         // then belong to as many look-back chains as there are ticks (measured, 64 ticks x 848 tiles: tick-major 0.54 ms, ticks
         // fastest 0.40, chunks of 4 / 16 / 64 tiles 0.335 / 0.328 / 0.41)
-        static const int chunk = getenv("LSN_FUSE_CHUNK") ? atoi(getenv("LSN_FUSE_CHUNK")) : 16;
-        a.chunk = std::max(0, chunk);
+        constexpr int kFuseChunk = 16;
+        a.chunk = kFuseChunk;
         if (e0) LSN_HIP(hipEventRecord(e0, s));
         launch<4>(vec, grid, s, a, p->lazy_rgb);
         if (e1) LSN_HIP(hipEventRecord(e1, s));

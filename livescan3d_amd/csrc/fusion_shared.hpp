@@ -57,7 +57,7 @@ struct FuseArgs {
     int tiles_per_run;               // mode 1
     unsigned int epoch;              // mode 2: tag of this launch's look-back words (run_state is never cleared)
     int chunk;                       // write pass block order: 0 = tick-major; C > 0 = chunks of C consecutive tiles, all ticks of a chunk before the next chunk
-    int reverse_ticks;               // the write pass takes the ticks last to first (what the count pass read last is nearest in cache); $LSN_WRITE_FORWARD=1: first to last
+    int reverse_ticks;               // the write pass takes the ticks last to first (what the count pass read last is nearest in cache); always 1
     int tile0;                       // one-tick plans only: the launch covers tiles [tile0, tile0 + gridDim.x) of the tick (a group of sensors, run_frames)
     int host_out;                    // mode 2: `out` is pinned host memory (plain, destination-aligned stores; see stage_and_store)
     int *group_end_mirror;           // mode 2, optional (pinned host memory): where this launch's vertices end inside the tick, stored by its last tile
@@ -387,13 +387,11 @@ __device__ __forceinline__ void compute_tile(const FuseArgs &a, const Tile &t, c
     compute_pixels<WRITE>(a, P, in, xf, yf, keep, vert);
 }
 
-// Where rank q of a staged window lives: q + q / 8 (one 16-byte pad per 8 ranks).  LSN_STAGE_PAD_SHIFT (build-time, A/B only):
-// 4 = one pad per 16 ranks, 31 = no padding.
-#ifndef LSN_STAGE_PAD_SHIFT
-#define LSN_STAGE_PAD_SHIFT 3
-#endif
-__device__ __forceinline__ int stage_slot16(int q) { return q + (q >> LSN_STAGE_PAD_SHIFT); }
-constexpr int kStageSlots = kWin + (kWin >> LSN_STAGE_PAD_SHIFT) + 1;
+// Where rank q of a staged window lives: q + q / 8 (one 16-byte pad per 8 ranks; one per 16 ranks or none measured 0.2958 / 0.2951 /
+// 0.3005 ms per step: profiles/r04_ab_pad.txt).
+constexpr int kStagePadShift = 3;
+__device__ __forceinline__ int stage_slot16(int q) { return q + (q >> kStagePadShift); }
+constexpr int kStageSlots = kWin + (kWin >> kStagePadShift) + 1;
 
 // Stages a tile's survivors in LDS in rank order, window by window, and copies them out with consecutive lanes writing
 // consecutive 16-B vertices.  Rank q of a window lives at slot q + q/8: a lane's 8 consecutive ranks then start 9 slots
@@ -531,7 +529,6 @@ struct LsnFusion {
     bool params_set = false;
     int mode = 0;
     unsigned int epoch = 0;          // mode 2: launches so far (tags the look-back words)
-    int tiles_per_run_override = 0;  // $LSN_TILES_PER_RUN (tuning / tests)
     bool want_pixmap = false;        // the run in progress also fills the pixel -> vertex map (set and cleared under mu by run_locked)
     float bounds[6] = {0, 0, 0, 0, 0, 0};
     lsn::DevBuf frames, tile_frame, params, tile_counts, tile_state, misc;  // misc: error flag (word 0) + tickets

@@ -275,12 +275,10 @@ void plan_schedule(std::vector<Group> &groups, std::vector<Copy> &copies, const 
         // small_first: the FIRST group of a call that starts with the radial correction AND goes on to the fusion is a little smaller (>= 1.9 MB of colours: three 512x424 sensors):
         // nothing leaves for the host before the first group is up, corrected and fused, and the groups behind it hide their ~100 us of closing
         // rounds behind its download anyway (8 x 512x424, tick as one call: 3 | 5 sensors 1.025-1.034 ms against 4 | 4 1.041-1.050; 2 | 4 | 2
-        // 1.08, 1 | 4 | 3 1.14 -- $LSN_HOST_FIRST_GROUP=n forces n sensors for the A/B).  The radial export ALONE keeps equal groups: nothing
+        // 1.08, 1 | 4 | 3 1.14).  The radial export ALONE keeps equal groups: nothing
         // leaves before a group is corrected there either, but its way home is as long as its way up (0.445 ms with 4 | 4, 0.454 with 3 | 5)
-        static const int first_n = getenv("LSN_HOST_FIRST_GROUP") ? atoi(getenv("LSN_HOST_FIRST_GROUP")) : 0;
-        const int cut = (radial && small_first && first_n > 0 && groups.empty()) ? first_n : 0;
         const size_t want = (radial && small_first && groups.empty()) ? kRadialFirstGroup : full;
-        while (i < end && (cut > 0 ? g.count < cut : per > 0 ? g.count < per : (g.count == 0 || weight(g) < want))) {
+        while (i < end && (per > 0 ? g.count < per : (g.count == 0 || weight(g) < want))) {
             g.dbytes += dsz(i);
             g.cbytes += csz(i);
             g.count++;

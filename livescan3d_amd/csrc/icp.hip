@@ -227,7 +227,7 @@ __global__ __launch_bounds__(kThreads) void bbox_partial_kernel(const float *pts
     }
 }
 
-__global__ __launch_bounds__(64) void grid_setup_kernel(const float *part, int n_parts, int n_points, float cell_override, GridParams *gp)
+__global__ __launch_bounds__(64) void grid_setup_kernel(const float *part, int n_parts, int n_points, GridParams *gp)
 {
     float mn[3] = {INFINITY, INFINITY, INFINITY}, mx[3] = {-INFINITY, -INFINITY, -INFINITY};
     for (int b = threadIdx.x; b < n_parts; b += 64)
@@ -251,7 +251,6 @@ __global__ __launch_bounds__(64) void grid_setup_kernel(const float *part, int n
     float area = ext[0] * ext[1] + ext[1] * ext[2] + ext[0] * ext[2];
     float h = 2.0f * sqrtf(fmaxf(area, 1e-12f) / (float)(n_points > 0 ? n_points : 1));
     h = fminf(fmaxf(h, L / 512.0f), L / 4.0f);
-    if (cell_override > 0.0f) h = cell_override;
     int nsx = 1, nsy = 1, nsz = 1;
     for (int guard = 0; guard < 2000; guard++) {
         // cells needed per axis, rounded up to whole super-blocks
@@ -801,13 +800,6 @@ constexpr int kChunkPts = 8;                 // points per chunk = loads in flig
 constexpr int kNearCapMax = 128;             // largest candidate cap per query
 constexpr int kMaxChunks = 64 * (kNearCapMax / kChunkPts + kNearRuns);   // a run of n points is ceil(n / 8) chunks
 
-#ifdef LSN_CULL_STAMPS   // dev aid: per-workgroup clock stamps of nn_cull_kernel<true> (tools/cull_stamps.py)
-__device__ long long g_cull_stamps[8 * 8192];
-#define LSN_STAMP(i) do { if (APPLY && threadIdx.x == 0 && blockIdx.x < 8192) g_cull_stamps[8 * blockIdx.x + (i)] = wall_clock64(); } while (0)
-#else
-#define LSN_STAMP(i) do { } while (0)
-#endif
-
 struct NearBox {   // a query's box of cells (inclusive), filled by lane = query, read by its team
     int xl, xh, yl, yh, zl, zh;
     int want;      // the query takes the near path (after near_enqueue: and its box held <= the cap)
@@ -1060,7 +1052,6 @@ __global__ __launch_bounds__(kCullThreads) __attribute__((amdgpu_waves_per_eu(7,
     const int g = blockIdx.x;
     if (g * 64 >= n2) return;  // workgroup-uniform
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    LSN_STAMP(0);
     const GridParams grid = *gp;
     if (wave == 0) {
         const int j = g * 64 + lane;
@@ -1101,17 +1092,13 @@ __global__ __launch_bounds__(kCullThreads) __attribute__((amdgpu_waves_per_eu(7,
         sh.box[lane] = near_ball_box(grid, seed_targets && near_pts > 0 && part && B < INFINITY, qx, qy, qz, B);
         sh.flag[lane] = settled;
         if (lane == 0) sh.n_chunks = 0;
-        LSN_STAMP(1);
     }
     __syncthreads();
-    LSN_STAMP(2);
     if (seed_targets && near_pts > 0) {
         near_enqueue<false>(sh, grid, cell_start, near_pts, threadIdx.x / kTeam, threadIdx.x % kTeam);
         __syncthreads();
-        LSN_STAMP(3);
         near_consume(sh, sorted);
         __syncthreads();
-        LSN_STAMP(4);
         if (wave == 0 && sh.box[lane].want) {   // the walk covered the ball of the bound: the key is final
             sh.q[lane].w = -1.0f;
             sh.flag[lane] = 1;
@@ -1128,7 +1115,6 @@ __global__ __launch_bounds__(kCullThreads) __attribute__((amdgpu_waves_per_eu(7,
     gi.pad = 0;
     gi.resolved = __ballot(sh.flag[lane] != 0);
     if (threadIdx.x == 0) groups[g] = gi;
-    LSN_STAMP(5);
     if (!(gi.rmax >= 0.0f)) return;
     const int n_supers = grid.ncells / 4096;
     int *cnt = wk.counters + kBankInts * bank;
@@ -1180,7 +1166,6 @@ __global__ __launch_bounds__(kCullThreads) __attribute__((amdgpu_waves_per_eu(7,
             out += __popcll(mask);
         }
     }
-    LSN_STAMP(6);
 }
 
 // One wave per (group, super-block) item: the super-block's 64 blocks, one per lane, against the group's box, then each
@@ -1695,13 +1680,11 @@ struct GridBufs {
 struct LsnIcp {
     int device = 0;
     int max_n1 = 0, max_n2 = 0;
-    float cell_override = 0.0f;
     GridBufs tgt, src;    // tgt: cell-sorted target + boxes; src.sorted: the spatially sorted working copy of the source
     lsn::DevBuf bbox_part, block_sums;
     lsn::DevBuf idx, dist, keys, counters, part1, part3, state, trace;
     lsn::DevBuf best_key, groups, list_a, list_b, idx_sorted;   // the NN step's per-query keys, per-group boxes and work lists
     int seg_a = 0, seg_b = 0;   // capacity of one list segment
-    int item_points = 128;      // points per scan item; $LSN_ICP_ITEM (tuning): 64, 128, 192 or 256.  128 instead of 256: 0.094 -> 0.089 ms/iteration (configs[1])
     // optional phase timing of lsnIcpRun (lsnIcpSetProfiling): HIP events on the caller's stream around
     // [0] grid build + source sort, [1] the NN steps (incl. the fused apply), [2] statistics + Kabsch sums + solve, [3] final apply
     bool profiling = false;
@@ -1709,7 +1692,6 @@ struct LsnIcp {
     std::vector<int> event_phase;   // phase that ENDS at event k (event 0 opens the run)
     size_t n_events = 0;
     int trace_iters = 0;
-    bool seed_nn = true;   // $LSN_ICP_NO_SEED=1 turns the previous-neighbour seeding off (ablation)
     int near_mode = 1;     // $LSN_ICP_NEAR: 0 = no near path, 1 = the probe always, seeded steps when the previous step's distances say it pays, 2 = always
     int near_pts = 128;    // the near path's candidate cap per query (<= kNearCapMax); $LSN_ICP_NEAR=0 turns the path off (A/B, tests), $LSN_ICP_NEAR_PTS sets the cap
     int last_groups = 0;   // query groups of the last grid NN step (lsnIcpNearResolved)
@@ -1731,11 +1713,8 @@ static LsnIcp * lsnIcpCreate_impl(int device, int max_n1, int max_n2)
     w->device = device;
     w->max_n1 = max_n1;
     w->max_n2 = max_n2;
-    if (const char *e2 = getenv("LSN_ICP_NO_SEED")) w->seed_nn = atoi(e2) == 0;
     if (const char *e3 = getenv("LSN_ICP_NEAR_PTS")) w->near_pts = std::max(1, std::min(kNearCapMax, atoi(e3)));
     if (const char *e4 = getenv("LSN_ICP_NEAR")) w->near_mode = std::max(0, std::min(2, atoi(e4)));
-    const char *env = getenv("LSN_ICP_CELL");
-    if (env) w->cell_override = (float)atof(env);
     bool bad = false;
     bad |= w->tgt.reserve(max_n1, true) != 0;
     bad |= w->src.reserve(max_n2, false) != 0;
@@ -1749,10 +1728,6 @@ static LsnIcp * lsnIcpCreate_impl(int device, int max_n1, int max_n2)
         const int n_groups = (max_n2 + 63) / 64;
         // generous: a seeded group needs ~5 super-blocks and ~10 point ranges; $LSN_ICP_TINY_LISTS=1 forces the overflow path (tests)
         const bool tiny = getenv("LSN_ICP_TINY_LISTS") && atoi(getenv("LSN_ICP_TINY_LISTS")) != 0;
-        if (const char *e = getenv("LSN_ICP_ITEM")) {
-            const int v = atoi(e);
-            if (v == 64 || v == 128 || v == 192 || v == 256) w->item_points = v;
-        }
         w->seg_a = tiny ? 2 : 1024 + n_groups / 4;   // x 64 segments: 64 k + 16 per group
         w->seg_b = tiny ? 2 : 8192 + 2 * n_groups;   // x 64 segments: 512 k + 128 per group
         bad |= w->best_key.reserve(sizeof(unsigned long long) * (size_t)max_n2) != 0;
@@ -1850,7 +1825,7 @@ static int build_grid(LsnIcp *w, GridBufs &g, const float *d_pts, int n, bool wi
     const int nb = capped_blocks(n);
     GridParams *gp = g.gp.as<GridParams>();
     hipLaunchKernelGGL(bbox_partial_kernel, dim3(nb), dim3(kThreads), 0, s, d_pts, n, w->bbox_part.as<float>());
-    hipLaunchKernelGGL(grid_setup_kernel, dim3(1), dim3(64), 0, s, w->bbox_part.as<float>(), nb, n, w->cell_override, gp);
+    hipLaunchKernelGGL(grid_setup_kernel, dim3(1), dim3(64), 0, s, w->bbox_part.as<float>(), nb, n, gp);
     if (!g.counts_clear) LSN_HIP(hipMemsetAsync(g.cell_cnt.p, 0, sizeof(int) * (size_t)kMaxCells, s));
     g.counts_clear = false;   // dirty until the scatter below has been enqueued
     const int nall = std::max(1, blocks_for(n));   // one point per thread: a capped grid makes every thread a chain of dependent rounds
@@ -1874,6 +1849,8 @@ static int build_grid(LsnIcp *w, GridBufs &g, const float *d_pts, int n, bool wi
     return 0;
 }
 
+constexpr int kItemPoints = 128;   // points per scan item (NnWork::item_points).  128 instead of 256: 0.094 -> 0.089 ms/iteration (configs[1])
+
 static NnWork work_of(LsnIcp *w)
 {
     NnWork wk;
@@ -1881,7 +1858,7 @@ static NnWork work_of(LsnIcp *w)
     wk.list_b = w->list_b.as<int4>();
     wk.seg_a = w->seg_a;
     wk.seg_b = w->seg_b;
-    wk.item_points = w->item_points;
+    wk.item_points = kItemPoints;
     wk.counters = w->counters.as<int>();
     return wk;
 }
@@ -1898,9 +1875,9 @@ static int run_nn(LsnIcp *w, const float *d_verts1, int n1, float *d_verts2, int
     if (nn_mode == 0) {
         // slices of the target cloud: ~32 k workgroups of a few hundred to a few thousand points each (measured best at configs[1]
         // and [2]: 2 k workgroups 2.13 ms, 8 k 1.80, 16-32 k 1.77, 64 k 1.83)
-        static const int want_wgs = getenv("LSN_ICP_BRUTE_WGS") ? std::max(1, atoi(getenv("LSN_ICP_BRUTE_WGS"))) : 32768;
+        constexpr int kBruteWorkgroups = 32768;
         const int qblocks = blocks_for(n2);
-        int slices = std::max(1, std::min(65535, (want_wgs + qblocks - 1) / qblocks));
+        int slices = std::max(1, std::min(65535, (kBruteWorkgroups + qblocks - 1) / qblocks));
         const int slice_points = std::max(64, (((n1 + slices - 1) / slices) + 7) & ~7);
         slices = std::max(1, (n1 + slice_points - 1) / slice_points);
         unsigned long long *best_key = w->best_key.as<unsigned long long>();
@@ -1924,9 +1901,8 @@ static int run_nn(LsnIcp *w, const float *d_verts1, int n1, float *d_verts2, int
     // point ranges; longer lists are served by looping.  Waves without an item leave after one load.
     // waves per query group of the two list consumers.  The scan list of a seeded step holds ~6 (configs[1]) to ~11 (configs[2]) items
     // per group, unevenly over the 64 segments: with fewer waves than the fullest segment has items, some waves serve a second item
-    // behind their first -- a second chain of dependent round trips that sets the launch time ($LSN_ICP_SCAN_WAVES, A/B in EXPERIMENTS.md)
-    static const int scan_waves = getenv("LSN_ICP_SCAN_WAVES") ? std::max(1, atoi(getenv("LSN_ICP_SCAN_WAVES"))) : 12;
-    static const int block_waves = getenv("LSN_ICP_BLOCK_WAVES") ? std::max(1, atoi(getenv("LSN_ICP_BLOCK_WAVES"))) : 8;
+    // behind their first -- a second chain of dependent round trips that sets the launch time (A/B in EXPERIMENTS.md, profiles/r04_ab_icp.txt)
+    constexpr int scan_waves = 12, block_waves = 8;
     const dim3 blocks_grid(64 * ((block_waves * n_groups + 63) / 64)), scan_grid(64 * ((scan_waves * n_groups + 63) / 64));
     if (seeded) {
         hipLaunchKernelGGL(nn_cull_kernel<true>, dim3(n_groups), dim3(kCullThreads), 0, s, src, d_verts2, n2, st, keys, n1, gp, supers, d_verts1, n1,
@@ -2034,13 +2010,13 @@ static int lsnIcpRun_impl(LsnIcp *w, const float *d_verts1, int n1, float *d_ver
     IcpState *st = w->state.as<IcpState>();
     // one launch instead of three fills (each a kernel of its own, ~4.5 us): the match keys, the NN step's list counters, and
     // v_valid -- the first iteration's SVD starts cold
-    const bool seeded0 = d_seeds && w->seed_nn && nn_mode != 0;
+    const bool seeded0 = d_seeds && nn_mode != 0;
     hipLaunchKernelGGL(run_init_kernel, dim3(blocks_for(std::max(std::max(n1, n2), 2 * kBankInts))), dim3(kThreads), 0, s, keys, n1, w->counters.as<int>(),
                        2 * kBankInts, st, seeded0 ? d_seeds : (const int *)nullptr, (const float4 *)w->src.sorted.as<float4>(), n2, w->idx_sorted.as<int>());
     for (int iter = 0; iter < maxIter; iter++) {
         // from the second iteration on idx[] still holds every query's previous neighbour: the search is seeded with it, and
         // its first launch also carries out the previous iteration's motion and clears the match keys
-        const bool fused = (iter > 0 || seeded0) && w->seed_nn && nn_mode != 0;
+        const bool fused = (iter > 0 || seeded0) && nn_mode != 0;
         if (iter > 0 && !fused)
             hipLaunchKernelGGL(apply_kernel, dim3(blocks_for(n2 > n1 ? n2 : n1)), dim3(kThreads), 0, s, w->src.sorted.as<float4>(), d_verts2, n2,
                                (const IcpState *)st, keys, n1);
@@ -2087,14 +2063,6 @@ extern "C" int lsnIcpNearResolved(LsnIcp *w, void *stream)
 {
     return lsn::guarded<int>("lsnIcpNearResolved", static_cast<int>(-1), [&]() { return lsnIcpNearResolved_impl(w, stream); });
 }
-
-#ifdef LSN_CULL_STAMPS
-extern "C" int lsnDevCullStamps(long long *out, int n_blocks)
-{
-    (void)hipDeviceSynchronize();
-    return hipMemcpyFromSymbol(out, HIP_SYMBOL(g_cull_stamps), sizeof(long long) * 8 * (size_t)(n_blocks < 8192 ? n_blocks : 8192)) == hipSuccess ? 0 : -1;
-}
-#endif
 
 static int lsnIcpTrace_impl(LsnIcp *w, float *out, int max_iters, void *stream)
 {
@@ -2185,7 +2153,6 @@ static int lsnRefine_impl(int device, int n_sensors, float *const *clouds, const
         lsn::DevBuf &d_all = rs->d_all, &d_others = rs->d_others, &d_Rt = rs->d_Rt, &d_seeds = rs->d_seeds;
         if (!rc) rc = d_all.reserve(sizeof(float) * 3 * (size_t)total) || d_others.reserve(sizeof(float) * 3 * (size_t)(total - min_n)) ||
                       d_Rt.reserve(sizeof(float) * Rt.size()) || d_seeds.reserve(sizeof(int) * (size_t)total);
-        static const bool carry_seeds = !(getenv("LSN_REFINE_SEEDS") && atoi(getenv("LSN_REFINE_SEEDS")) == 0);   // A/B
         std::vector<long long> off(n_sensors + 1, 0);
         for (int i = 0; i < n_sensors; i++) off[i + 1] = off[i] + counts[i];
         for (int i = 0; i < n_sensors && !rc; i++)
@@ -2202,14 +2169,15 @@ static int lsnRefine_impl(int device, int n_sensors, float *const *clouds, const
                                         hipMemcpyDeviceToDevice, s) != hipSuccess;
                 // From the second pass on the first NN step of a call is seeded with the neighbours the sensor's call of the previous pass ended
                 // with ("all other sensors" is the same concatenation in every pass, so the indices still name real points; the others have moved a
-                // little, which only makes the seeds a little less tight): ~65 us instead of ~150 for that step, same result.
+                // little, which only makes the seeds a little less tight): ~65 us instead of ~150 for that step, same result (14.23-14.38 ->
+                // 13.98-14.07 ms per call, same digest).
                 if (!rc)
                     rc = lsn::guarded<int>("lsnRefine", -1, [&]() {
                         return lsnIcpRun_impl(ws, d_others.as<float>(), (int)pos, d_all.as<float>() + 3 * off[i], counts[i], d_Rt.as<float>() + 12 * i,
                                               d_Rt.as<float>() + 12 * i + 9, n_icp_iters, 1, s,
-                                              carry_seeds && it > 0 ? d_seeds.as<int>() + off[i] : (const int *)nullptr);     // :370
+                                              it > 0 ? d_seeds.as<int>() + off[i] : (const int *)nullptr);     // :370
                     });
-                if (!rc && carry_seeds && it + 1 < n_refine_iters)
+                if (!rc && it + 1 < n_refine_iters)
                     rc = hipMemcpyAsync(d_seeds.as<int>() + off[i], ws->idx.p, sizeof(int) * (size_t)counts[i], hipMemcpyDeviceToDevice, s) != hipSuccess;
             }
         }

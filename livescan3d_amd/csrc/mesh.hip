@@ -15,7 +15,7 @@ namespace {
 
 // (TriArgs, the kernel argument block, is declared in fusion_shared.hpp next to FuseArgs)
 
-constexpr int kTriWinDefault = 1536;  // triangles staged per LDS round (18 KB); a multiple of 16 (LSN_TRI_WINDOW: 256 .. 4096)
+constexpr int kTriWinDefault = 1536;  // triangles staged per LDS round (18 KB); a multiple of 16 (1024-2048 within 2 %, 4096 20 % slower: occupancy)
 // The staged window is padded by one int per 16 triangles: a lane of 8 pixels on a closed surface holds 16 triangles, so the k-th
 // triangles of the lanes of a wave lie 48 ints apart -- 4 banks for 64 lanes (SQ_LDS_BANK_CONFLICT: 77 % of the LDS cycles of the
 // write pass, which made it LDS-bound); 49 ints apart they take 64 different banks.
@@ -214,15 +214,15 @@ __device__ __forceinline__ unsigned int lane_triangles(const DepthRow (&rows)[4]
     return spread_to_nibbles(V0) | (spread_to_nibbles(V1) << 1) | (spread_to_nibbles(V2) << 2) | (spread_to_nibbles(V3) << 3);
 }
 
-#ifndef LSN_TRI_MIN_WAVES
-#define LSN_TRI_MIN_WAVES 5   // waves per SIMD the count pass is compiled for (build-time, A/B: 5 = 102 VGPRs allowed, 7 = 73; it needs 71)
-#endif
+// Waves per SIMD the count pass is compiled for: 5 = 102 VGPRs allowed (it needs 71); 7 and 8 measured inside the noise
+// (277.7 / 269.8 us against 276.6 / 278.5 and 266.2: profiles/r05_ab_tri_occupancy.txt).
+constexpr int kTriMinWaves = 5;
 // MODE 0 = count triangles per tile, 1 = write them at the scanned offsets.
 // HOST (write pass): `tri` is pinned host memory -- plain stores, rounds aligned to the destination (stage_and_store's note).  A template
 // parameter, not a run-time flag: a run-time choice between a streaming and a plain store of the same value to the same address is
 // folded into ONE plain store by the compiler, and the device-resident path loses its streaming stores (65.8 against 71.7 k ticks/s).
 template <int MODE, bool VEC, bool HOST = false>
-__global__ __launch_bounds__(kThreads, MODE == 0 ? LSN_TRI_MIN_WAVES : 1) void tri_kernel(const TriArgs a)
+__global__ __launch_bounds__(kThreads, MODE == 0 ? kTriMinWaves : 1) void tri_kernel(const TriArgs a)
 {
     extern __shared__ int stage[];   // write pass: stage_ints(a.win) + 3 * 64 ints
     const int kTriWin = a.win;
@@ -469,8 +469,7 @@ static bool tri_args(LsnFusion *p, const void *d_depth, void *d_triangles, TriAr
     t.tile_counts = p->tri_counts.as<int>();
     t.codes = p->tri_codes.as<unsigned int>();
     t.tiles_per_tick = p->tiles_per_tick;
-    static const int win_env = getenv("LSN_TRI_WINDOW") ? atoi(getenv("LSN_TRI_WINDOW")) : kTriWinDefault;
-    t.win = std::min(4096, std::max(256, win_env)) & ~15;
+    t.win = kTriWinDefault;
     t.host_out = 0;
     t.index_base = 0;
     t.tick_pix_stride = p->cap;

@@ -190,8 +190,7 @@ struct WarpSrc {
 
 
 // Warped value of K destination pixels p[k] of one frame (fb = first pixel of the frame in the batch, doff = in its tick): a
-// chain of dependent loads per pixel -- table, the candidates' depths (both at once; with SPEC the first candidate's colour too),
-// the winner's colour -- issued for all K pixels level by level.  Every load is unconditional (a pixel that needs none reads its own
+// chain of dependent loads per pixel -- table, the candidates' depths (both at once), the winner's colour -- issued for all K pixels level by level.  Every load is unconditional (a pixel that needs none reads its own
 // position and drops the value): no exec-mask branches, so the K loads of a level really are in flight together.  pv: any valid
 // pixel of the frame (stands in for p[k] where in[k] is false).
 // (buffer addressing: a 128-bit resource in SGPRs + one 32-bit byte offset per lane -- no 64-bit vector arithmetic per load, and an
@@ -199,7 +198,7 @@ struct WarpSrc {
 constexpr unsigned int kRsrcWord3 = 0x00027000u;   // gfx9 raw buffer, 32-bit elements
 constexpr unsigned int kNowhere = 0xFFFFFFF0u;     // a byte offset outside every frame
 
-template <int K, bool SPEC = false>
+template <int K>
 __device__ __forceinline__ void gather_batch(const WarpSrc &S, long long fb, long long doff, int npix, int pv, const int (&p)[K], const bool (&in)[K],
                                              unsigned int (&d)[K], unsigned int (&rgb)[K])
 {
@@ -216,7 +215,7 @@ __device__ __forceinline__ void gather_batch(const WarpSrc &S, long long fb, lon
     unsigned int e[K];
 #pragma unroll
     for (int k = 0; k < K; k++) e[k] = __builtin_amdgcn_raw_buffer_load_b32(tab, in[k] ? 4u * (unsigned int)p[k] : kNowhere, 0, 0);
-    unsigned int s0[K], s1[K], d0[K], d1[K], c0[K];
+    unsigned int s0[K], s1[K], d0[K], d1[K];
     bool any_wide = false;
 #pragma unroll
     for (int k = 0; k < K; k++) {
@@ -228,27 +227,12 @@ __device__ __forceinline__ void gather_batch(const WarpSrc &S, long long fb, lon
         s1[k] = (unsigned int)p[k] + a1 - 32768u;
         d0[k] = __builtin_amdgcn_raw_buffer_load_b16(dep, v0 ? 2u * s0[k] : kNowhere, 0, 0);
         d1[k] = __builtin_amdgcn_raw_buffer_load_b16(dep, v1 ? 2u * s1[k] : kNowhere, 0, 0);
-        if (SPEC) c0[k] = colour(s0[k], v0);               // the first candidate's colour rides with the depths
     }
-    bool second = false;
 #pragma unroll
     for (int k = 0; k < K; k++) {
         const unsigned int src = d0[k] ? s0[k] : s1[k];     // the highest valid source wins (:200-218: the last one in raster order)
         d[k] = d0[k] ? d0[k] : d1[k];
-        if (SPEC) {
-            rgb[k] = d0[k] ? c0[k] : 0u;
-            second |= !d0[k] && d1[k];
-        } else {
-            rgb[k] = colour(src, d[k] != 0);
-        }
-    }
-    if (SPEC && __any(second)) {                            // a zero-depth first candidate in front of a valid second one
-#pragma unroll
-        for (int k = 0; k < K; k++) {
-            const bool need = !d0[k] && d1[k];
-            const unsigned int v = colour(s1[k], need);
-            if (need) rgb[k] = v;
-        }
+        rgb[k] = colour(src, d[k] != 0);
     }
     if (__any(any_wide)) {                                  // three or four sources, or a far one: the full table (a few pixels per frame)
         const unsigned short *gdep = S.depth + fb;
@@ -609,10 +593,7 @@ __device__ __forceinline__ int wave_reserve(int *counter, int mine)
 }
 
 constexpr int kCntStride = 32;   // ints between two frames' counters: one 128-byte line each (atomics on one line serialise in its L2 channel)
-#ifndef LSN_BAND_THREADS
-#define LSN_BAND_THREADS 256
-#endif
-constexpr int kBandThreads = LSN_BAND_THREADS;   // (A/B knob: tools/ab_band.sh)
+constexpr int kBandThreads = 256;   // threads per band workgroup (512 x 12 rows: 462-467 us, 256 x 6: 378-391; see the launch)
 
 struct BandDesc { int frame, y0; };
 
@@ -703,10 +684,7 @@ __global__ __launch_bounds__(kBandThreads) void radial_band_kernel(const BandArg
 
     // ---- 1. the un-closed band into LDS ----
     if (GATHER) {
-#ifndef LSN_BAND_FLY
-#define LSN_BAND_FLY 8
-#endif
-        constexpr int kFly = LSN_BAND_FLY;
+        constexpr int kFly = 8;   // pixels in flight per thread: 3 / 4 / 6 / 8 / 12 / 16 -> 514 / 424 / 416 / 378-391 / 438 / 468 us (profiles/r06_ab_band.txt)
         for (int i0 = lo + tid; i0 < hi; i0 += kFly * kBandThreads) {
             int p[kFly];
             bool in[kFly];
@@ -716,10 +694,7 @@ __global__ __launch_bounds__(kBandThreads) void radial_band_kernel(const BandArg
                 in[k] = i0 + k * kBandThreads < hi;
             }
             unsigned int d[kFly], c[kFly];
-#ifndef LSN_BAND_SPEC
-#define LSN_BAND_SPEC false
-#endif
-            gather_batch<kFly, LSN_BAND_SPEC>(a.src, fb, fd.depth_off, fd.npix, pl0 + lo, p, in, d, c);
+            gather_batch<kFly>(a.src, fb, fd.depth_off, fd.npix, pl0 + lo, p, in, d, c);
 #pragma unroll
             for (int k = 0; k < kFly; k++) {
                 if (!in[k]) continue;
@@ -897,10 +872,7 @@ __global__ __launch_bounds__(kBandThreads) void radial_band_kernel(const BandArg
     }
 }
 
-#ifndef LSN_FIX_THREADS
-#define LSN_FIX_THREADS 256
-#endif
-constexpr int kFixThreads = LSN_FIX_THREADS;   // measured on 512 scene frames: 1024 threads 377 us, 512: 274, 256: 245 -- the rounds are short, idle waves only add barrier time
+constexpr int kFixThreads = 256;   // measured on 512 scene frames: 1024 threads 377 us, 512: 274, 256: 245 -- the rounds are short, idle waves only add barrier time
 constexpr int kFixList = 8192;   // entries per round list (LDS, two lists: 64 KB)
 
 struct FixArgs {
@@ -1227,10 +1199,6 @@ static int radial_correct_on(LsnFusion *p, const float *intr_params, const void 
         // One band per frame is the shortest chain of steps, but (rows + 2) x 192 B of LDS per workgroup then allows a single
         // frame per CU.  With more frames than CUs, 256-row bands (49.5 KB: three frames per CU) win.
         if ((long long)n_tf > 256 && rows > 256) rows = 256;
-        if (const char *env = getenv("LSN_RADIAL_ROWS")) {  // tuning: rows per band (multiple of 64, <= 768)
-            const int v = atoi(env);
-            if (v >= 64 && v <= 768 && v % 64 == 0) rows = v;
-        }
         const size_t ring_bytes = (sizeof(unsigned int) + sizeof(unsigned short)) * kRing * (rows + 2);
         hipLaunchKernelGGL(radial_close_kernel, dim3((unsigned)n_tf), dim3(rows), ring_bytes, s, p->frames.as<FrameDesc>(), p->n_maps,
                            p->map_copy.as<unsigned short>(), p->colors_copy.as<unsigned char>(), p->cap);

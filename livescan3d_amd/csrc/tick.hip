@@ -23,7 +23,6 @@ struct LsnTick {
     std::vector<float> intr;             // the radial correction's intrinsics (lsnTickSetParams)
     hipStream_t side = nullptr;
     hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_band = nullptr;
-    bool stagger = true;                 // $LSN_TICK_STAGGER=0: both halves start together
     std::mutex mu;
 };
 
@@ -66,10 +65,6 @@ static LsnTick *lsnTickCreate_impl(int device, int n_ticks, int n_maps, const in
     t->parts = parts;
     t->first[0] = 0;
     t->first[1] = parts == 2 ? (n_ticks + 1) / 2 : n_ticks;
-    if (const char *e = getenv("LSN_TICK_FIRST")) {   // tuning: ticks in the first half
-        const int v = atoi(e);
-        if (parts == 2 && v >= 1 && v < n_ticks) t->first[1] = v;
-    }
     t->first[2] = n_ticks;
     bool bad = false;
     for (int k = 0; k < parts && !bad; k++) {
@@ -85,7 +80,6 @@ static LsnTick *lsnTickCreate_impl(int device, int n_ticks, int n_maps, const in
                   hipEventCreateWithFlags(&t->ev_fork, hipEventDisableTiming) != hipSuccess ||
                   hipEventCreateWithFlags(&t->ev_join, hipEventDisableTiming) != hipSuccess ||
                   hipEventCreateWithFlags(&t->ev_band, hipEventDisableTiming) != hipSuccess;
-        if (const char *e = getenv("LSN_TICK_STAGGER")) t->stagger = atoi(e) != 0;
         if (bad && !lsn::has_error()) lsn::set_error("lsnTickCreate: %s", hipGetErrorString(hipGetLastError()));
     }
     if (bad) {
@@ -149,18 +143,18 @@ static int lsnTickRun_impl(LsnTick *t, const void *d_depth_in, const void *d_col
                                 static_cast<unsigned char *>(d_triangles) + 12 * (size_t)t->tri_cap * t0, d_tri_offsets + nm * t0, st);
     };
     if (t->parts == 1) return part(0, s);
-    // fork: the side stream starts where the caller's stream stands -- and, staggered, only when the first half's band kernel is through: two
+    // fork: the side stream starts where the caller's stream stands -- and only when the first half's band kernel is through (staggered): two
     // halves that start together march in step (band beside band, closing beside closing) and gain nothing; half a stage apart, one half's
     // closing rounds run beside the other half's band kernel, then beside its count / write / triangle passes.  join: the caller's stream
     // continues behind both halves.
     LSN_HIP(hipEventRecord(t->ev_fork, s));
     LSN_HIP(hipStreamWaitEvent(t->side, t->ev_fork, 0));
-    t->plan[0]->after_band = t->stagger ? t->ev_band : nullptr;
+    t->plan[0]->after_band = t->ev_band;
     const int rc_a = part(0, s);
     t->plan[0]->after_band = nullptr;
     char err_a[lsn::kErrorLen];
     snprintf(err_a, sizeof(err_a), "%s", lsn::error_buffer());   // (every export clears the channel on entry: the second half's calls would wipe the first half's text)
-    if (t->stagger) (void)hipStreamWaitEvent(t->side, t->ev_band, 0);   // (a closing route without a band kernel records nothing new: no wait, the halves start together)
+    (void)hipStreamWaitEvent(t->side, t->ev_band, 0);   // (a closing route without a band kernel records nothing new: no wait, the halves start together)
     const int rc_b = part(1, t->side);
     if (rc_a) lsn::set_error("%s", err_a);
     // (the join is enqueued whatever happened: nothing of a failed half may still be running unobserved when the caller's stream goes on)

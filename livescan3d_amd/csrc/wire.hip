@@ -956,8 +956,7 @@ static long long lsnTransferPack_impl(LsnTransfer *t, const void *d_vertices, in
     const int *src_t = d_triangles;
     int n_send = n_vertices, n_chunks = 0, host_chunks = 1;
     bool linked = false;
-    static const bool no_links = getenv("LSN_TRANSFER_WINDOW_WALK") != nullptr;       // ablation: the chunk-by-chunk walk only
-    if (n_triangles > 0 && !no_links && 3ll * n_triangles / kChunkLimit + 2 <= kLinkChunksLds &&
+    if (n_triangles > 0 && 3ll * n_triangles / kChunkLimit + 2 <= kLinkChunksLds &&
         (n_triangles + kScanPerBlock - 1) / kScanPerBlock <= kLinkTotalsLds && t->max_chunks <= kLinkChunksLds) {
         const int n_pos = 3 * n_triangles;
         LinkState *st = t->l_state.as<LinkState>();

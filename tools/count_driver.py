@@ -1,4 +1,4 @@
-"""Times the count pass variants: python3 tools/count_driver.py [ticks sensors width height]  (reads $LSN_TICK_GROUP / $LSN_NO_THRESHOLDS)."""
+"""Times the count pass variants: python3 tools/count_driver.py [ticks sensors width height]  (reads $LSN_NO_THRESHOLDS)."""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
@@ -17,4 +17,4 @@ t0 = time.perf_counter()
 for _ in range(50):
     fus.run(depth, rgb)
 torch.cuda.synchronize()
-print("shape", T, S, w, h, "G", os.environ.get("LSN_TICK_GROUP"), "nothr", os.environ.get("LSN_NO_THRESHOLDS"), "ms/step", round((time.perf_counter() - t0) / 50 * 1e3, 4))
+print("shape", T, S, w, h, "nothr", os.environ.get("LSN_NO_THRESHOLDS"), "ms/step", round((time.perf_counter() - t0) / 50 * 1e3, 4))

@@ -1,5 +1,5 @@
 """lsnTransferPack on one tick's merged mesh (8 x 512x424 scene frames), `reps` times: wall time per call, path taken.
-LSN_TRANSFER_WINDOW_WALK=1 selects the chunk-after-chunk walk.  Usage: python3 tools/wire_driver.py [reps]"""
+Usage: python3 tools/wire_driver.py [reps]"""
 import os
 import sys
 import time
