@@ -10,11 +10,17 @@ compaction (+ for N > 1 the RCCL all-gather of the per-GPU sensor shards and the
 value = merged clouds per second = ticks * K / wall time (max over ranks).  Sensors are sharded in contiguous blocks
 over the ranks (fixed total work: "strong" scaling).  Prints ONE JSON line on rank 0.
 
-Extra objects in the line: "roofline" (dominant kernel: algorithmic bytes 2P + 19V per sensor-frame / HIP-event
-kernel time vs 8 TB/s), "cpu_baseline" (the CPU oracle = port of the reference path, timed on this host's cores on
-a bounded sample, rank 0 at N = 1 only), "icp" (configs[1]: 2 sensors x 512x424, ICP(maxIter=10) ms per iteration, with
-a roofline per kernel group from the library's own HIP events), "icp_config2" (configs[2]: 8 sensors, target = 7 sensors'
-clouds: voxel-grid NN vs brute-force NN).
+A plain run does only what `value` needs: set-up, settling, --warmup, the K timed steps, --dump-outputs, and the line, whose
+"roofline" (dominant kernel: algorithmic bytes 2P + 19V per sensor-frame / HIP-event kernel time vs 8 TB/s) comes from the
+timed steps themselves.
+
+--full adds everything else, after the headline: "value_repeats" (the K steps four more times), "value_verified" (the
+outputs behind `value` against the CPU oracle), "cpu_baseline" (the CPU oracle = port of the reference path, timed on this
+host's cores on a bounded sample, rank 0 at N = 1 only), "icp" (configs[1]: 2 sensors x 512x424, ICP(maxIter=10) ms per
+iteration, with a roofline per kernel group from the library's own HIP events), "icp_config2" (configs[2]: 8 sensors,
+target = 7 sensors' clouds: voxel-grid NN vs brute-force NN), the other shapes, the chained tick, the host exports and
+the ablations; N > 1: the tick-parallel leg and the exchange comparisons.  --no-icp, --no-cpu, --no-mesh, --no-host-path
+and --no-tick-parallel leave parts of it out.
 """
 import argparse
 import json
@@ -47,9 +53,13 @@ def parse():
                          "lsnShard* exports; survivors-python: the same protocol driven over torch.distributed; vertices: 16 B)")
     ap.add_argument("--compare-exchanges", action="store_true",
                     help="N > 1: also time the vertex exchange and the Python-driven survivor exchange (more collectives through "
-                         "torch.distributed after the headline; always on under LSN_BENCH_FORCE_DIST=1)")
+                         "torch.distributed after the headline; needs --full, under which LSN_BENCH_FORCE_DIST=1 turns it on by itself)")
     ap.add_argument("--no-mesh", action="store_true")
-    ap.add_argument("--core-only", action="store_true", help="only the timed region behind `value` (for rocprofv3 summaries): no extra legs")
+    scope = ap.add_mutually_exclusive_group()
+    scope.add_argument("--full", action="store_true",
+                       help="after the headline, also run the repeats, the oracle check of `value`, the CPU baselines, the ICP, mesh, "
+                            "host-path and other-shape legs and the ablations (N > 1: the tick-parallel leg and the exchange comparisons)")
+    scope.add_argument("--core-only", action="store_true", help="only the timed region behind `value`: what a run without --full does")
     ap.add_argument("--padded-exchange", action="store_true", help="N > 1: all-gather full-capacity slabs (no host sync)")
     ap.add_argument("--no-tick-parallel", action="store_true", help="N > 1: skip the extra tick-parallel (no-exchange) leg")
     ap.add_argument("--icp-reps", type=int, default=5)
@@ -60,6 +70,8 @@ def parse():
                     help="after the timed steps, write what the last timed step computed (merged-cloud offsets, per-tick sums over every vertex, "
                          "a fixed seeded sample of the vertices) as DIR/<name>.npy, float32 / float64, < 64 MB in all")
     args = ap.parse_args()
+    if not args.full:     # a plain run: the timed region behind `value` and nothing after it
+        args.core_only = True
     if args.core_only:
         args.no_icp = args.no_cpu = args.no_host_path = args.no_mesh = args.no_tick_parallel = True
     return args
@@ -335,7 +347,7 @@ def main():
                                      "across fresh boxes the driver command has read 210-220 k (+-2 %)"} if len(repeats) > 1 else {}),
             "config": {
                 "workload": f"{S} synthetic {w}x{h} Kinect streams per tick (BASELINE configs[2]/[3], the north-star target shape), "
-                            f"{B} ticks fused per step; ICP: configs[1] (2 sensors x 512x424, 10 iterations) reported under 'icp'",
+                            f"{B} ticks fused per step; ICP: configs[1] (2 sensors x 512x424, 10 iterations) reported under 'icp' (--full)",
                 "sensors": S, "width": w, "height": h, "ticks_per_step": B,
                 "sensors_per_gpu": S_loc,
                 "survivor_fraction": V_total / float(B * S * P),

@@ -4,6 +4,7 @@ go unnoticed until somebody reads the line)."""
 import importlib
 import os
 import re
+import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -68,6 +69,29 @@ def test_bench_line_carries_value_verified_and_fails_on_a_mismatch():
     from bench_support.verify import checked
     assert checked(lambda: 1 / 0)() == {"bitexact": None, "not_checked": "ZeroDivisionError: division by zero"}
     assert checked(lambda x: {"bitexact": True, "x": x})(3) == {"bitexact": True, "x": 3}
+
+
+def test_a_plain_run_times_the_headline_and_full_adds_the_rest(monkeypatch):
+    """`bench.py --gpus 1 --steps K --warmup W` runs only what `value` needs; --full brings back every leg, the repeats and the oracle check,
+    and the --no-* switches still leave single parts of it out."""
+    import pytest
+    import bench
+    extras = ("no_icp", "no_cpu", "no_host_path", "no_mesh", "no_tick_parallel")
+
+    def parsed(*argv):
+        monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "20", "--warmup", "5", *argv])
+        return bench.parse()
+    plain = parsed()
+    assert not plain.full and plain.core_only and all(getattr(plain, k) for k in extras)
+    assert (plain.steps, plain.warmup, plain.settle_seconds, plain.mode, plain.dump_outputs) == (20, 5, 0.5, 0, None)
+    full = parsed("--full")
+    assert full.full and not full.core_only and not any(getattr(full, k) for k in extras)
+    assert (full.steps, full.warmup, full.settle_seconds, full.mode) == (20, 5, 0.5, 0)
+    some = parsed("--full", "--no-icp", "--no-cpu")
+    assert some.no_icp and some.no_cpu and not (some.no_mesh or some.no_host_path or some.core_only)
+    assert parsed("--core-only").core_only
+    with pytest.raises(SystemExit):
+        parsed("--full", "--core-only")
 
 
 def test_value_verification_catches_a_corrupted_cloud(orc):
