@@ -15,7 +15,10 @@ and the two places where the behaviour is defined rather than copied (DESIGN.md 
   * (int) of a double that is NaN or out of range gives INT_MIN (x64 cvttsd2si), so the clamp gives 0.
 
 tests/color_ref_py.py restates steps 1-5 again in plain Python loops; tests/golden/color_transfer_ref.npz pins steps 4-5 to the
-reference's own colorcorrection.cpp (tests/golden/make_color_golden.py)."""
+reference's own colorcorrection.cpp (tests/golden/make_color_golden.py), and tests/golden/export_ref.npz / export_ref_digests.json
+pin steps 1-5 together to the reference's own generateMeshFromDepthMaps(bcolor_transfer = true) (tests/golden/make_export_golden.py,
+tests/test_export_pin.py).  The first defined place above (a crop box through the overlap) is not in those fixtures: there the
+reference reads out of bounds, so this restatement is the definition."""
 import numpy as np
 
 ET_LIMIT = 20          # :392

@@ -17,8 +17,12 @@ smallest (val, index) among those after the last covering triangle whose val is 
 draw_sequential restates the loop literally (tests/test_merge_ref.py checks the two against each other and against the reference's
 own drawTriangle through tests/golden/overlay_merge_ref.npz).
 
+Pinned as a whole: tests/golden/export_ref.npz / export_ref_digests.json hold the reference's own
+generateMeshFromDepthMaps(bgenerate_triangles = true), alone and after colour transfer, on wall, twins, ring and edge rigs
+(tests/golden/make_export_golden.py); tests/test_export_pin.py holds overlay_merge() to them.
+
 Defined where the reference is not: float -> unsigned short is x64's (cvttss2si to int32, INT_MIN for NaN and
-out of range, then the low 16 bits); every sensor must have the same size."""
+out of range, then the low 16 bits); every sensor must have the same size (mixed sizes are not in the export fixtures)."""
 import numpy as np
 
 from tests import color_ref

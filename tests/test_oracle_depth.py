@@ -1,10 +1,10 @@
 """The CPU oracle's depth -> cloud path against an independent numpy-float32 op-by-op restatement of
 createVertices (src/NativeUtils/depthprocessing.cpp:122-187) and against committed digests.
 
-Status: PARITY UNPINNED for this path -- the reference ships no golden vectors for it (ref.bin absent,
-src/NativeUtils/main.cpp:159-252) and depthprocessing.cpp cannot be compiled here without stand-ins for <windows.h>.
-What these tests do pin: two independently written restatements (C and numpy) agree bit for bit, and the C one
-does not drift (sha256 of its output on seeded inputs, tests/golden/digests.json)."""
+Status: pinned.  The reference's own exports, compiled with stand-ins (tests/golden/make_export_golden.py), are recorded in
+tests/golden/export_ref.npz / export_ref_digests.json; tests/test_export_pin.py holds the C oracle and numpy_create_vertices below
+to them.  Here: the two independently written restatements (C and numpy) agree bit for bit, and the C one does not drift (sha256 of
+its output on seeded inputs, tests/golden/digests.json)."""
 import json
 import os
 

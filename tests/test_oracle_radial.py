@@ -1,6 +1,7 @@
 """The oracle's radial correction (oracle/lsn_oracle.c::orc_radial_correction) against an independent pure-Python /
 numpy-float32 restatement of depthMapAndColorRadialCorrection (src/NativeUtils/depthprocessing.cpp:191-261).
-PARITY UNPINNED (no reference build / fixtures): two independent restatements must agree bit for bit."""
+Pinned: tests/test_export_pin.py holds both restatements to the reference's own depthMapAndColorSetRadialCorrection
+(tests/golden/export_ref.npz, export_ref_digests.json); here the two must agree bit for bit on further frames."""
 import numpy as np
 import pytest
 
