@@ -252,6 +252,27 @@ int lsnFusionOverlayDiagnostics(LsnFusion *plan, int tick, unsigned short *repro
                                 void *stream);
 int lsnSetOverlayMerge(int enable);
 
+/* Outlier filter (LiveScanClient's filter(), src/LiveScanClient/filter.cpp:36-81, with the server's bFilter / nFilterNeighbors /
+ * fFilterThreshold, LiveScanServer/KinectSettings.cs:30-32) on the output of lsnFusionRun / lsnFusionRunMesh: d_depth_maps the depth maps
+ * that call read, d_vertices / d_offsets what it wrote (read only).  Every sensor's block of every tick is filtered on its own: a vertex is
+ * removed iff fewer than k vertices of its block (itself included) lie at a squared distance <= max_dist * max_dist in float, evaluated as
+ * PointCloud::kdtree_distance does (= the reference's k-th nearest distance > pow(maxDist, 2); a block of fewer than k vertices is kept iff
+ * that threshold is >= FLT_MAX).  Writes the maps with depth 0 at the pixels of removed vertices to d_depth_out (may equal d_depth_maps);
+ * the caller then runs lsnFusionRun / lsnFusionRunMesh on d_depth_out, and colour transfer / the overlay merge after that if wanted.
+ * k <= 0, max_dist <= 0 or NaN: the maps are copied unchanged.  Asynchronous on `stream`; returns 0, -1 on error.
+ * lsnFusionOutlierDiagnostics (synchronises `stream`): for tick `tick` of the last filter, the removed vertices per sensor (n_maps ints),
+ * the removed flag of every vertex (nVertices bytes) and the vertices the grid pass decided per sensor (n_maps ints; 0 for a block of fewer
+ * than k vertices, decided by its size); any pointer may be NULL.  Returns the number of removed vertices, -1 on error.
+ * lsnSetOutlierFilter: the process-wide switch of the filter in generateMeshFromDepthMaps, generateVerticesFromDepthMap and
+ * lsnCorrectAndGenerateMesh (which writes back the unmasked corrected maps): they return the mesh of the masked maps.  Initially
+ * $LSN_OUTLIER_FILTER="k,max_dist" (e.g. "10,0.1"; unset or malformed: off); every call reads the current value.  The previous pair goes to
+ * prev_k / prev_max_dist (either may be NULL); returns 0. */
+int lsnFusionOutlierFilter(LsnFusion *plan, int k, float max_dist, const void *d_depth_maps, const void *d_vertices, const int *d_offsets,
+                           void *d_depth_out, void *stream);
+int lsnFusionOutlierDiagnostics(LsnFusion *plan, int tick, int *removed_per_sensor, unsigned char *removed_per_vertex, int *exact_per_sensor,
+                                void *stream);
+int lsnSetOutlierFilter(int k, float max_dist, int *prev_k, float *prev_max_dist);
+
 /* Radial correction of n_ticks x n_maps frames in place in HBM (same layouts as lsnFusionRun's inputs);
  * intr_params: host, 7 floats per sensor {cx,cy,fx,fy,r2,r4,r6}. */
 int lsnFusionRadialCorrect(LsnFusion *plan, const float *intr_params, void *d_depth_maps, void *d_depth_colors, void *stream);

@@ -179,6 +179,9 @@ extern "C" int lsnStreamSynchronize(int device, void *stream)
 }
 
 
+// the outlier filter's current (k, max_dist) (lsnSetOutlierFilter, below)
+static void outlier_current(int &k, float &max_dist);
+
 static void generateVerticesFromDepthMap_impl(unsigned char *depth_maps, unsigned char *depth_colors, int *widths, int *heights,
                                              float *intr_params, float *wtransform_params, Mesh *out_mesh, float minX, float minY,
                                              float minZ, float maxX, float maxY, float maxZ, int depth_map_index)
@@ -194,8 +197,11 @@ static void generateVerticesFromDepthMap_impl(unsigned char *depth_maps, unsigne
         return;
     }
     const float b[6] = {minX, minY, minZ, maxX, maxY, maxZ};
+    int ok_k = 0;
+    float ok_d = 0.0f;
+    outlier_current(ok_k, ok_d);
     if (ensure_ready(c) || fuse_host(c, l, depth_maps, depth_colors, widths, heights, intr_params, wtransform_params,
-                                     out_mesh, b, depth_map_index, 1, false))
+                                     out_mesh, b, depth_map_index, 1, false, false, nullptr, nullptr, false, false, ok_k, ok_d))
         empty_mesh(out_mesh);
 }
 
@@ -219,6 +225,55 @@ static std::atomic<int> &overlay_merge_switch()
 
 extern "C" int lsnSetOverlayMerge(int enable) { return overlay_merge_switch().exchange(enable ? 1 : 0); }
 
+// lsnSetOutlierFilter: (k, max_dist) of the exports' outlier filter.  Its first value comes from $LSN_OUTLIER_FILTER="k,max_dist" (unset:
+// off; malformed: off, with a message); from then on it is what the last lsnSetOutlierFilter set, and every export reads it when called.
+struct OutlierSetting {
+    std::mutex mu;
+    int k = 0;
+    float max_dist = 0.0f;
+};
+
+static OutlierSetting &outlier_setting()
+{
+    static OutlierSetting *s = [] {
+        OutlierSetting *o = new OutlierSetting();
+        const char *e = getenv("LSN_OUTLIER_FILTER");
+        if (e && *e) {
+            int k = 0, used = 0;
+            float d = 0.0f;
+            if (sscanf(e, " %d , %f %n", &k, &d, &used) == 2 && e[used] == '\0') {
+                o->k = k;
+                o->max_dist = d;
+            } else {
+                fprintf(stderr, "[NativeUtils] $LSN_OUTLIER_FILTER=\"%s\" is not \"k,max_dist\" (e.g. \"10,0.1\"): the outlier filter stays off\n", e);
+            }
+        }
+        return o;
+    }();
+    return *s;
+}
+
+static void outlier_current(int &k, float &max_dist)
+{
+    OutlierSetting &o = outlier_setting();
+    std::lock_guard<std::mutex> g(o.mu);
+    k = o.k;
+    max_dist = o.max_dist;
+}
+
+extern "C" int lsnSetOutlierFilter(int k, float max_dist, int *prev_k, float *prev_max_dist)
+{
+    return lsn::guarded<int>("lsnSetOutlierFilter", static_cast<int>(-1), [&]() {
+        OutlierSetting &o = outlier_setting();
+        std::lock_guard<std::mutex> g(o.mu);
+        if (prev_k) *prev_k = o.k;
+        if (prev_max_dist) *prev_max_dist = o.max_dist;
+        o.k = k;
+        o.max_dist = max_dist;
+        return 0;
+    });
+}
+
 static void generateMeshFromDepthMaps_impl(int n_maps, unsigned char *depth_maps, unsigned char *depth_colors, int *widths, int *heights,
                                           float *intr_params, float *wtransform_params, Mesh *out_mesh, bool bcolor_transfer, float minX,
                                           float minY, float minZ, float maxX, float maxY, float maxZ, bool bgenerate_triangles)
@@ -240,9 +295,12 @@ static void generateMeshFromDepthMaps_impl(int n_maps, unsigned char *depth_maps
     bool mixed = false;
     for (int i = 1; merge && i < n_maps; i++) mixed |= widths[i] != widths[0] || heights[i] != heights[0];
     merge &= !mixed;
+    int ok_k = 0;
+    float ok_d = 0.0f;
+    outlier_current(ok_k, ok_d);
     if (ensure_ready(c) ||
         fuse_host(c, l, depth_maps, depth_colors, widths, heights, intr_params, wtransform_params, out_mesh, b, 0, n_maps, true, false, nullptr,
-                  nullptr, bcolor_transfer, merge)) {
+                  nullptr, bcolor_transfer, merge, ok_k, ok_d)) {
         empty_mesh(out_mesh);
         return;
     }
@@ -290,8 +348,12 @@ static void lsnCorrectAndGenerateMesh_impl(int n_maps, unsigned char *depth_maps
         return;
     }
     const float b[6] = {minX, minY, minZ, maxX, maxY, maxZ};
+    int ok_k = 0;
+    float ok_d = 0.0f;
+    outlier_current(ok_k, ok_d);
     if (ensure_ready(c) || fuse_host(c, l, depth_maps, depth_colors, widths, heights, intr_params, wtransform_params, out_mesh, b, 0, n_maps,
-                                     true, true, write_back_corrected ? depth_maps : nullptr, write_back_corrected ? depth_colors : nullptr))
+                                     true, true, write_back_corrected ? depth_maps : nullptr, write_back_corrected ? depth_colors : nullptr, false,
+                                     false, ok_k, ok_d))
         empty_mesh(out_mesh);
 }
 

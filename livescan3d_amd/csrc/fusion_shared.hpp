@@ -571,6 +571,13 @@ struct LsnFusion {
     lsn::DevBuf mg_counts, mg_voff, mg_toff, mg_ctile, mg_pix2v, mg_v2pix, mg_conf, mg_depth0, mg_depth, mg_d2v, mg_assigned, mg_vconf, mg_proj,
         mg_zmax, mg_key, mg_mdepth, mg_mtag, mg_ero;
     bool mg_ready = false;
+    // outlier filter (outlier.hip), allocated on its first call: index-pass counts / offsets / pixel <-> vertex maps, each vertex's bucket,
+    // the bucket tables and their chunk sums, the points in bucket order, removed flags, per-sensor counts, the caller's offsets, the
+    // sensors' bucket bases and masks, the blocks' bounding boxes and grid frames
+    lsn::DevBuf ol_counts, ol_off, ol_pix2v, ol_v2pix, ol_key, ol_bucket, ol_chunk, ol_pts, ol_removed, ol_stats, ol_offs, ol_tab, ol_box,
+        ol_frame;
+    bool ol_ready = false;
+    int ol_nb = 0, ol_nchunk = 0;        // buckets per tick, scan chunks per tick
     bool thr_valid = false;
     bool thr_enabled = true;             // $LSN_NO_THRESHOLDS=1 keeps the arithmetic count pass (ablation / tests)
     bool one_tick_single_pass = false;   // a one-tick plan of <= 2048 tiles takes the single pass (fuse_kernel<4>) instead of count -> scan -> write; $LSN_ONE_TICK_SINGLE_PASS=0 / 1 forces

@@ -49,6 +49,7 @@ struct Lane {
     int *h_off = nullptr, *h_toff = nullptr;   // pinned: the offset tables of the call in progress
     int h_off_cap = 0;
     lsn::DevBuf d_depth, d_colors, d_depth2, d_colors2, d_out, d_off, d_tri, d_tri_off;
+    lsn::DevBuf d_masked;     // a call with the outlier filter on: its depth maps with the removed vertices' pixels at 0 (allocated by the first such call)
     // the lane's plans: key = n sensors, first sensor, widths..., heights...  Owned by the lane and only touched under its lock, so a
     // plan never runs on two lanes' streams at once and an eviction cannot pull a plan from under the other lane's call
     std::map<std::vector<int>, LsnFusion *> plans;
@@ -165,10 +166,11 @@ void plan_shards(int count, int n_devices, int *first, int &D);
 int parse_device_list(const char *text, int n_visible, std::vector<int> &out);
 
 // The calls.  The lane's lock is held by the caller; `out` is left untouched on failure (the export then returns an empty mesh).
+// outlier_k / outlier_max_dist: the outlier filter (lsnSetOutlierFilter); it runs when outlier_k > 0 and outlier_max_dist > 0.
 int fuse_host(Ctx &c, Lane &l, const unsigned char *depth_maps, const unsigned char *depth_colors, const int *widths, const int *heights,
               const float *intr, const float *wt, Mesh *out, const float *bounds6, int first, int count, bool with_triangles, bool radial = false,
               unsigned char *radial_back_d = nullptr, unsigned char *radial_back_c = nullptr, bool color_transfer = false,
-              bool overlay_merge = false);
+              bool overlay_merge = false, int outlier_k = 0, float outlier_max_dist = 0.0f);
 void radial_host(Ctx &c, Lane &l, int n_maps, unsigned char *depth_maps, unsigned char *depth_colors, const int *widths, const int *heights,
                  const float *intr_params);
 int materialize(Lane &l);                  // lsnLastMesh*: the mesh of the lane's last call in d_out / d_tri

@@ -679,12 +679,33 @@ int fuse_host_grouped(HostCall &h, Mesh *out)
 // then the correction runs in place (color.hip), the merge rebuilds the triangles (merge.hip), and the mesh leaves in one copy.  Without
 // the merge the triangles do not depend on the colours; they are built as in flow 2.  The merge reads the positions alone, so the two
 // commute.
-int fuse_host_color(HostCall &h, Mesh *out, bool color_transfer, bool overlay_merge)
+// With the outlier filter on (outlier_k > 0) the tick's cloud is filtered per sensor where it lies (outlier.hip), the removed vertices'
+// pixels become depth 0 in a copy of the maps, and the groups fuse again from that copy: everything after -- triangles, colour transfer,
+// overlay merge -- is the call on the masked maps.  The corrected maps a call that starts with the radial correction
+// writes back are the unmasked ones.
+int fuse_host_color(HostCall &h, Mesh *out, bool color_transfer, bool overlay_merge, int outlier_k = 0, float outlier_max_dist = 0.0f)
 {
     Lane &l = h.l;
     if (h.begin(true, 0)) return -1;
     const int count = h.count;
     if (h.upload([&](size_t k, const Group &g) -> int { return h.fuse_group(k, g, l.d_out.p, nullptr, false); })) return -1;
+    if (outlier_k > 0) {
+        size_t dbytes = 0;
+        for (const Group &g : l.groups) dbytes += g.dbytes;
+        if (l.d_masked.reserve(dbytes + 16) ||
+            lsn::outlier_filter(h.plan, outlier_k, outlier_max_dist, h.run_d, l.d_out.p, l.d_off.as<int>(), l.d_masked.p, l.stream))
+            return -1;
+        if (h.back) {
+            LSN_HIP(hipStreamSynchronize(l.stream));   // every group's corrected maps are final
+            for (size_t k = 0; k < h.G; k++)
+                if (write_back_runs(l, k, h.back_d, h.back_c)) return -1;
+            LSN_HIP(hipStreamSynchronize(l.back));
+            h.back = false;
+        }
+        h.run_d = l.d_masked.as<char>();
+        for (size_t k = 0; k < h.G; k++)
+            if (h.fuse_group(k, l.groups[k], l.d_out.p, nullptr, false)) return -1;
+    }
     if (h.with_triangles && !overlay_merge && lsn::run_triangles(h.plan, h.run_d, l.d_tri.p, l.d_tri_off.as<int>(), l.h_toff, false, l.stream))
         return -1;
     if (color_transfer && lsn::color_transfer(h.plan, h.run_d, l.d_out.p, l.d_off.as<int>(), l.stream)) return -1;
@@ -1107,14 +1128,20 @@ int materialize(Lane &l)
 // $LSN_HOST_PATH=direct / grouped forces one of them for every call (A/B runs).
 int fuse_host(Ctx &c, Lane &l, const unsigned char *depth_maps, const unsigned char *depth_colors, const int *widths, const int *heights,
               const float *intr, const float *wt, Mesh *out, const float *bounds6, int first, int count, bool with_triangles, bool radial,
-              unsigned char *radial_back_d, unsigned char *radial_back_c, bool color_transfer, bool overlay_merge)
+              unsigned char *radial_back_d, unsigned char *radial_back_c, bool color_transfer, bool overlay_merge, int outlier_k,
+              float outlier_max_dist)
 {
+    // the outlier filter runs for k > 0 and max_dist > 0; k <= 0, max_dist <= 0 and a NaN max_dist change nothing (outlier.hip), so
+    // those calls take the flows of a call without it
+    const bool filter = outlier_k > 0 && outlier_max_dist > 0.0f;
     // a merge call on a context with several devices ($LSN_HOST_DEVICES), more than one sensor: one sensor block per device and link --
-    // except with colour transfer or the overlay merge, which cross sensors: that call runs on the first device alone (flow 2b)
-    if (&l == &c.merge && c.shards.size() >= 2 && count >= 2 && first == 0 && !color_transfer && !overlay_merge)
+    // except with colour transfer, the overlay merge or the outlier filter, which need the whole cloud in HBM: that call runs on the first
+    // device alone (flow 2b)
+    if (&l == &c.merge && c.shards.size() >= 2 && count >= 2 && first == 0 && !color_transfer && !overlay_merge && !filter)
         return fuse_host_sharded(c, l, depth_maps, depth_colors, widths, heights, intr, wt, out, bounds6, count, with_triangles, radial, radial_back_d,
                                  radial_back_c);
     HostCall h(c, l, depth_maps, depth_colors, widths, heights, intr, wt, bounds6, first, count, with_triangles, radial, radial_back_d, radial_back_c);
+    if (filter) return fuse_host_color(h, out, color_transfer, overlay_merge, outlier_k, outlier_max_dist);
     if (color_transfer || overlay_merge) return fuse_host_color(h, out, color_transfer, overlay_merge);
     const bool direct = c.host_path == 1 || (c.host_path == 0 && !radial);
     return direct ? fuse_host_direct(h, out) : fuse_host_grouped(h, out);

@@ -140,6 +140,9 @@ int color_transfer(LsnFusion *p, const void *d_depth, void *d_vertices, const in
 // lsnFusionOverlayMerge on a stream (merge.hip): rewrites the triangles of the cloud lsnFusionRun* wrote from d_depth.
 int overlay_merge(LsnFusion *p, const void *d_depth, const void *d_vertices, const int *d_offsets, void *d_triangles, int *d_tri_offsets,
                   hipStream_t s);
+// lsnFusionOutlierFilter on a stream (outlier.hip): d_depth with depth 0 at the pixels of removed vertices into d_depth_out.
+int outlier_filter(LsnFusion *p, int k, float max_dist, const void *d_depth, const void *d_vertices, const int *d_offsets, void *d_depth_out,
+                   hipStream_t s);
 
 // The survivor exchange's two ends with the back-to-back stream layout (exchange.hip; see their definitions).
 int pack_survivors(LsnFusion *p, const void *d_depth, const void *d_colors, void *d_mask, void *d_depth_c, void *d_rgb_c, int *d_tile_prefix,

@@ -623,3 +623,5 @@ int lsn::run_triangles_write(LsnFusion *p, const void *d_depth, void *d_triangle
 // The overlay merge (bgenerate_triangles) likewise: it re-runs these triangle passes on its reprojected maps and shares color.hip's
 // projection, index pass and confidence maps.
 #include "merge.hip"
+// The outlier filter likewise: it reuses color.hip's index pass and block scan.
+#include "outlier.hip"

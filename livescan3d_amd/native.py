@@ -26,6 +26,7 @@ EXPORTS = [
     "lsnFusionCreate", "lsnFusionDestroy", "lsnFusionTickCapacity", "lsnFusionSetParams", "lsnPackSensorParams", "lsnFusionSetMode",
     "lsnFusionRun", "lsnFusionRunStreamed", "lsnFusionSetPipelined", "lsnFusionRadialCorrect", "lsnFusionRadialCorrectTo", "lsnFusionRadialCountersLeft", "lsnFusionRunMesh", "lsnFusionTickTriangleCapacity", "lsnFusionProfile", "lsnFusionKernelStats", "lsnFusionLookbackFailed", "lsnFusionCheck", "lsnFusionThresholds", "lsnMergeShards",
     "lsnFusionColorTransfer", "lsnFusionColorDiagnostics", "lsnFusionOverlayMerge", "lsnFusionOverlayDiagnostics", "lsnSetOverlayMerge",
+    "lsnFusionOutlierFilter", "lsnFusionOutlierDiagnostics", "lsnSetOutlierFilter",
     "lsnFusionTilesPerTick", "lsnFusionPackSurvivors", "lsnFusionReconstruct",
     "lsnDeviceMalloc", "lsnDeviceFree", "lsnDeviceUpload", "lsnDeviceDownload", "lsnStreamCreate", "lsnStreamDestroy", "lsnStreamSynchronize",
     "lsnFusionPackSurvivorsRun", "lsnFusionReconstructRun", "lsnShardUniqueId", "lsnShardPlan", "lsnShardCreate", "lsnShardPrepare", "lsnShardConnect", "lsnShardRcclPath", "lsnShardDestroy", "lsnShardMergedCapacity", "lsnShardSetParams", "lsnShardStep", "lsnShardLastBytesSent", "lsnShardRanksSeen",
@@ -160,6 +161,13 @@ def lib():
     L.lsnFusionOverlayDiagnostics.argtypes = [vp, C.c_int, vp, vp, vp, vp]
     L.lsnSetOverlayMerge.restype = C.c_int
     L.lsnSetOverlayMerge.argtypes = [C.c_int]
+    if hasattr(L, "lsnSetOutlierFilter"):   # (absent from an older build loaded through $LSN_NATIVE_LIB)
+        L.lsnFusionOutlierFilter.restype = C.c_int
+        L.lsnFusionOutlierFilter.argtypes = [vp, C.c_int, C.c_float, vp, vp, vp, vp, vp]
+        L.lsnFusionOutlierDiagnostics.restype = C.c_int
+        L.lsnFusionOutlierDiagnostics.argtypes = [vp, C.c_int, vp, vp, vp, vp]
+        L.lsnSetOutlierFilter.restype = C.c_int
+        L.lsnSetOutlierFilter.argtypes = [C.c_int, C.c_float, vp, vp]
     L.lsnMergeShards.restype = C.c_int
     L.lsnMergeShards.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_longlong, vp, vp, C.c_longlong, vp, vp]
     L.lsnIcpCreate.restype = vp
@@ -328,10 +336,38 @@ def set_overlay_merge(enable):
     return bool(lib().lsnSetOverlayMerge(1 if enable else 0))
 
 
+def set_outlier_filter(k, max_dist):
+    """lsnSetOutlierFilter: the process-wide (k, max_dist) of the exports' outlier filter (k <= 0 or max_dist <= 0: off).
+    Returns the previous pair."""
+    pk, pd = C.c_int(0), C.c_float(0)
+    _check(lib().lsnSetOutlierFilter(int(k), float(max_dist), C.byref(pk), C.byref(pd)), "lsnSetOutlierFilter")
+    return pk.value, pd.value
+
+
+class _OutlierFilter:
+    """Sets the process-wide outlier filter for the body of a with-statement (None: leaves it as it is)."""
+
+    def __init__(self, setting):
+        self.setting, self.prev = setting, None
+
+    def __enter__(self):
+        if self.setting is not None:
+            self.prev = set_outlier_filter(*self.setting)
+
+    def __exit__(self, *exc):
+        if self.prev is not None:
+            set_outlier_filter(*self.prev)
+
+
 def generate_mesh_from_depth_maps(depth_maps, depth_colors, widths, heights, intr, wt, bounds,
-                                  color_transfer=False, generate_triangles=False, overlay_merge=None):
+                                  color_transfer=False, generate_triangles=False, overlay_merge=None, outlier_filter=None):
     """KinectServer.GenerateMesh (KinectServer.cs:354-374).  Returns (vertices[VERTEX_DTYPE], triangles int32).
-    overlay_merge: None leaves the process-wide switch (lsnSetOverlayMerge) as it is; True / False sets it for this call alone."""
+    overlay_merge: None leaves the process-wide switch (lsnSetOverlayMerge) as it is; True / False sets it for this call alone.
+    outlier_filter: None leaves the process-wide outlier filter (lsnSetOutlierFilter) as it is; (k, max_dist) sets it for this call alone."""
+    if outlier_filter is not None:
+        with _OutlierFilter(outlier_filter):
+            return generate_mesh_from_depth_maps(depth_maps, depth_colors, widths, heights, intr, wt, bounds, color_transfer,
+                                                 generate_triangles, overlay_merge)
     if overlay_merge is not None:
         prev = set_overlay_merge(overlay_merge)
         try:
@@ -411,9 +447,13 @@ def radial_correction(depth_maps, depth_colors, widths, heights, intr):
     return dm, dc
 
 
-def correct_and_generate_mesh(depth_maps, depth_colors, widths, heights, intr, wt, bounds, write_back=True):
+def correct_and_generate_mesh(depth_maps, depth_colors, widths, heights, intr, wt, bounds, write_back=True, outlier_filter=None):
     """One call per tick (extension): radial correction + merge call with a single upload.  Returns (vertices, triangles,
-    corrected depth as uint8, corrected colours); with write_back=False the last two are the untouched inputs."""
+    corrected depth as uint8, corrected colours); with write_back=False the last two are the untouched inputs.
+    outlier_filter: as for generate_mesh_from_depth_maps (the corrected maps written back are the unmasked ones)."""
+    if outlier_filter is not None:
+        with _OutlierFilter(outlier_filter):
+            return correct_and_generate_mesh(depth_maps, depth_colors, widths, heights, intr, wt, bounds, write_back)
     require_gpu()
     widths, heights = _as(widths, np.int32), _as(heights, np.int32)
     n = len(widths)
@@ -432,8 +472,12 @@ def correct_and_generate_mesh(depth_maps, depth_colors, widths, heights, intr, w
     return v, t, dm, dc
 
 
-def generate_vertices_from_depth_map(depth_maps, depth_colors, widths, heights, intr, wt, bounds, index):
-    """One sensor's cropped cloud, as KinectServer.GetLatestFrameVerticesOnly calls it (KinectServer.cs:527-554)."""
+def generate_vertices_from_depth_map(depth_maps, depth_colors, widths, heights, intr, wt, bounds, index, outlier_filter=None):
+    """One sensor's cropped cloud, as KinectServer.GetLatestFrameVerticesOnly calls it (KinectServer.cs:527-554).
+    outlier_filter: as for generate_mesh_from_depth_maps."""
+    if outlier_filter is not None:
+        with _OutlierFilter(outlier_filter):
+            return generate_vertices_from_depth_map(depth_maps, depth_colors, widths, heights, intr, wt, bounds, index)
     require_gpu()
     widths, heights = _as(widths, np.int32), _as(heights, np.int32)
     n = len(widths)
@@ -576,6 +620,25 @@ class FusionPlan:
             raise NativeUtilsError(f"lsnFusionOverlayDiagnostics failed: {last_error()}")
         nv = int(self.capacity) if n_vertices is None else int(n_vertices)
         return {"reprojected": rep[:self.pixels_per_tick], "merged": mer[:self.pixels_per_tick], "assigned": asg[:nv].copy(), "n_assigned": k}
+
+    def outlier_filter(self, k, max_dist, d_depth, d_vertices, d_offsets, d_depth_out, stream=0):
+        """Outlier filter on the clouds run() / run_mesh() wrote from d_depth: d_depth_out (may be d_depth) receives the maps with depth 0
+        at the pixels of removed vertices; every sensor of every tick on its own.  Run run() / run_mesh() on d_depth_out next."""
+        _check(lib().lsnFusionOutlierFilter(self._h, int(k), float(max_dist), d_depth, d_vertices, d_offsets, d_depth_out, stream or None),
+               "lsnFusionOutlierFilter")
+
+    def outlier_diagnostics(self, tick=0, n_vertices=None, stream=0):
+        """What the last outlier_filter() decided for one tick: {"removed_per_sensor": int32[n], "removed": uint8[n_vertices] (flag per
+        vertex of the filtered cloud), "exact_per_sensor": int32[n] (vertices the grid pass decided), "total": int}."""
+        rps = np.zeros(max(self.n_maps, 1), dtype=np.int32)
+        eps = np.zeros(max(self.n_maps, 1), dtype=np.int32)
+        rem = np.zeros(max(int(self.capacity), 1), dtype=np.uint8)
+        k = lib().lsnFusionOutlierDiagnostics(self._h, int(tick), _ptr(rps), _ptr(rem), _ptr(eps), stream or None)
+        if k < 0:
+            raise NativeUtilsError(f"lsnFusionOutlierDiagnostics failed: {last_error()}")
+        nv = int(self.capacity) if n_vertices is None else int(n_vertices)
+        return {"removed_per_sensor": rps[:self.n_maps].copy(), "removed": rem[:nv].copy(), "exact_per_sensor": eps[:self.n_maps].copy(),
+                "total": k}
 
     def thresholds(self, capacity=None, stream=0, copy=True):
         """Builds the per-pixel depth thresholds now.  Returns (table uint32[capacity] or None, build_ms); table is None when
