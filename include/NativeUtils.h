@@ -230,7 +230,9 @@ int lsnFusionRunMesh(LsnFusion *plan, const void *d_depth_maps, const void *d_de
  * lsnFusionColorDiagnostics (synchronises `stream`): what the last colour transfer computed for tick `tick` -- the confidence maps
  * (lsnFusionTickCapacity() bytes, the sensors' maps back to back), the symmetric coverage table (n_maps^2 ints), the chosen pairs
  * {base, corrected} in order (2 * (n_maps - 1) ints) and their transforms {mean_base[3], mean_corrected[3], scale[3]}
- * (9 * max(n_maps - 1, 1) doubles); any pointer may be NULL.  Returns the number of pairs, -1 on error. */
+ * (9 * max(n_maps - 1, 1) doubles); any pointer may be NULL.  Returns the number of pairs, -1 on error.  The confidence maps live in
+ * the index the plan's three stages share (colour transfer, overlay merge, outlier filter): they are valid until another of the three
+ * stages runs on the plan; everything else is the last colour transfer's until the next one. */
 int lsnFusionColorTransfer(LsnFusion *plan, const void *d_depth_maps, void *d_vertices, const int *d_offsets, void *stream);
 int lsnFusionColorDiagnostics(LsnFusion *plan, int tick, unsigned char *confidence, int *coverage, int *pairs, double *transforms,
                               void *stream);
@@ -243,7 +245,9 @@ int lsnFusionColorDiagnostics(LsnFusion *plan, int tick, unsigned char *confiden
  * the same size; at most 32 sensors.  Returns 0, -1 on error.
  * lsnFusionOverlayDiagnostics (synchronises `stream`): for the last merge of tick `tick`, the reprojected maps as first built and as
  * the merge left them (lsnFusionTickCapacity() u16 each, the sensors' maps back to back) and the point_assigned flag of every vertex
- * (nVertices bytes); any pointer may be NULL.  Returns the number of assigned vertices, -1 on error.
+ * (nVertices bytes); any pointer may be NULL.  Returns the number of assigned vertices, -1 on error.  nVertices comes from the index the
+ * plan's three stages share: the flags and the return value are valid until another of the three stages runs on the plan (the maps are
+ * the last merge's until the next one).
  * lsnSetOverlayMerge: the process-wide switch of generateMeshFromDepthMaps' merge (initially $LSN_OVERLAY_MERGE == "1"); returns the
  * previous value. */
 int lsnFusionOverlayMerge(LsnFusion *plan, const void *d_depth_maps, const void *d_vertices, const int *d_offsets, void *d_triangles,
@@ -262,7 +266,8 @@ int lsnSetOverlayMerge(int enable);
  * k <= 0, max_dist <= 0 or NaN: the maps are copied unchanged.  Asynchronous on `stream`; returns 0, -1 on error.
  * lsnFusionOutlierDiagnostics (synchronises `stream`): for tick `tick` of the last filter, the removed vertices per sensor (n_maps ints),
  * the removed flag of every vertex (nVertices bytes) and the vertices the grid pass decided per sensor (n_maps ints; 0 for a block of fewer
- * than k vertices, decided by its size); any pointer may be NULL.  Returns the number of removed vertices, -1 on error.
+ * than k vertices, decided by its size); any pointer may be NULL.  Returns the number of removed vertices, -1 on error.  (All of it is
+ * the filter's own: it stays until the next filter, whatever other stage runs on the plan.)
  * lsnSetOutlierFilter: the process-wide switch of the filter in generateMeshFromDepthMaps, generateVerticesFromDepthMap and
  * lsnCorrectAndGenerateMesh (which writes back the unmasked corrected maps): they return the mesh of the masked maps.  Initially
  * $LSN_OUTLIER_FILTER="k,max_dist" (e.g. "10,0.1"; unset or malformed: off); every call reads the current value.  The previous pair goes to

@@ -182,27 +182,44 @@ extern "C" int lsnStreamSynchronize(int device, void *stream)
 // the outlier filter's current (k, max_dist) (lsnSetOutlierFilter, below)
 static void outlier_current(int &k, float &max_dist);
 
+// What the three mesh exports share: `call` as `name` filled it (everything but the outlier filter's setting, which is read here) runs on
+// lane `l` of the context.  0: *out_mesh is the call's mesh; -1: the call was refused or failed, *out_mesh (if there is one) is empty and,
+// unless the caller merely passed no sensors, the message is set.
+static int mesh_export(const char *name, Lane &l, MeshCall &call, Mesh *out_mesh)
+{
+    lsn::clear_error();
+    if (!out_mesh) return -1;
+    std::lock_guard<std::mutex> g(l.mu);
+    if (call.count <= 0 || call.first < 0 || !call.depth_maps || !call.depth_colors || !call.widths || !call.heights || !call.intr || !call.wt) {
+        if (call.count != 0) lsn::set_error("%s: bad arguments", name);
+        empty_mesh(out_mesh);
+        return -1;
+    }
+    outlier_current(call.outlier_k, call.outlier_max_dist);
+    Ctx &c = ctx();
+    if (ensure_ready(c) || fuse_host(c, l, call, out_mesh)) {
+        empty_mesh(out_mesh);
+        return -1;
+    }
+    return 0;
+}
+
 static void generateVerticesFromDepthMap_impl(unsigned char *depth_maps, unsigned char *depth_colors, int *widths, int *heights,
                                              float *intr_params, float *wtransform_params, Mesh *out_mesh, float minX, float minY,
                                              float minZ, float maxX, float maxY, float maxZ, int depth_map_index)
 {
-    lsn::clear_error();
-    if (!out_mesh) return;
-    Ctx &c = ctx();
-    Lane &l = c.single;
-    std::lock_guard<std::mutex> g(l.mu);
-    if (!depth_maps || !depth_colors || !widths || !heights || !intr_params || !wtransform_params || depth_map_index < 0) {
-        lsn::set_error("generateVerticesFromDepthMap: bad arguments");
-        empty_mesh(out_mesh);
-        return;
-    }
     const float b[6] = {minX, minY, minZ, maxX, maxY, maxZ};
-    int ok_k = 0;
-    float ok_d = 0.0f;
-    outlier_current(ok_k, ok_d);
-    if (ensure_ready(c) || fuse_host(c, l, depth_maps, depth_colors, widths, heights, intr_params, wtransform_params,
-                                     out_mesh, b, depth_map_index, 1, false, false, nullptr, nullptr, false, false, ok_k, ok_d))
-        empty_mesh(out_mesh);
+    MeshCall call;
+    call.depth_maps = depth_maps;
+    call.depth_colors = depth_colors;
+    call.widths = widths;
+    call.heights = heights;
+    call.intr = intr_params;
+    call.wt = wtransform_params;
+    call.bounds6 = b;
+    call.first = depth_map_index;
+    call.count = 1;
+    (void)mesh_export("generateVerticesFromDepthMap", ctx().single, call, out_mesh);
 }
 
 extern "C" void generateVerticesFromDepthMap(unsigned char *depth_maps, unsigned char *depth_colors, int *widths, int *heights,
@@ -278,32 +295,27 @@ static void generateMeshFromDepthMaps_impl(int n_maps, unsigned char *depth_maps
                                           float *intr_params, float *wtransform_params, Mesh *out_mesh, bool bcolor_transfer, float minX,
                                           float minY, float minZ, float maxX, float maxY, float maxZ, bool bgenerate_triangles)
 {
-    lsn::clear_error();
-    if (!out_mesh) return;
-    Ctx &c = ctx();
-    Lane &l = c.merge;
-    std::lock_guard<std::mutex> g(l.mu);
-    if (n_maps <= 0 || !depth_maps || !depth_colors || !widths || !heights || !intr_params || !wtransform_params) {
-        if (n_maps != 0) lsn::set_error("generateMeshFromDepthMaps: bad arguments");
-        empty_mesh(out_mesh);
-        return;
-    }
     const float b[6] = {minX, minY, minZ, maxX, maxY, maxZ};
     // the overlay merge runs when the caller asks for it and the process opted in (lsnSetOverlayMerge / $LSN_OVERLAY_MERGE); it needs
     // every sensor of the same size (merge.hip): otherwise the unmerged mesh goes back, with a message
     bool merge = bgenerate_triangles && overlay_merge_switch().load();
     bool mixed = false;
-    for (int i = 1; merge && i < n_maps; i++) mixed |= widths[i] != widths[0] || heights[i] != heights[0];
+    for (int i = 1; merge && widths && heights && i < n_maps; i++) mixed |= widths[i] != widths[0] || heights[i] != heights[0];
     merge &= !mixed;
-    int ok_k = 0;
-    float ok_d = 0.0f;
-    outlier_current(ok_k, ok_d);
-    if (ensure_ready(c) ||
-        fuse_host(c, l, depth_maps, depth_colors, widths, heights, intr_params, wtransform_params, out_mesh, b, 0, n_maps, true, false, nullptr,
-                  nullptr, bcolor_transfer, merge, ok_k, ok_d)) {
-        empty_mesh(out_mesh);
-        return;
-    }
+    MeshCall call;
+    call.depth_maps = depth_maps;
+    call.depth_colors = depth_colors;
+    call.widths = widths;
+    call.heights = heights;
+    call.intr = intr_params;
+    call.wt = wtransform_params;
+    call.bounds6 = b;
+    call.count = n_maps;
+    call.with_triangles = true;
+    call.color_transfer = bcolor_transfer;
+    call.overlay_merge = merge;
+    Ctx &c = ctx();
+    if (mesh_export("generateMeshFromDepthMaps", c.merge, call, out_mesh)) return;
     if (merge) return;
     if (mixed) {
         lsn::set_error("generateMeshFromDepthMaps: the overlay merge needs every sensor of the same size; returned the unmerged mesh");
@@ -337,24 +349,21 @@ static void lsnCorrectAndGenerateMesh_impl(int n_maps, unsigned char *depth_maps
                                           float *intr_params, float *wtransform_params, Mesh *out_mesh, float minX, float minY, float minZ,
                                           float maxX, float maxY, float maxZ, int write_back_corrected)
 {
-    lsn::clear_error();
-    if (!out_mesh) return;
-    Ctx &c = ctx();
-    Lane &l = c.merge;
-    std::lock_guard<std::mutex> g(l.mu);
-    if (n_maps <= 0 || !depth_maps || !depth_colors || !widths || !heights || !intr_params || !wtransform_params) {
-        if (n_maps != 0) lsn::set_error("lsnCorrectAndGenerateMesh: bad arguments");
-        empty_mesh(out_mesh);
-        return;
-    }
     const float b[6] = {minX, minY, minZ, maxX, maxY, maxZ};
-    int ok_k = 0;
-    float ok_d = 0.0f;
-    outlier_current(ok_k, ok_d);
-    if (ensure_ready(c) || fuse_host(c, l, depth_maps, depth_colors, widths, heights, intr_params, wtransform_params, out_mesh, b, 0, n_maps,
-                                     true, true, write_back_corrected ? depth_maps : nullptr, write_back_corrected ? depth_colors : nullptr, false,
-                                     false, ok_k, ok_d))
-        empty_mesh(out_mesh);
+    MeshCall call;
+    call.depth_maps = depth_maps;
+    call.depth_colors = depth_colors;
+    call.widths = widths;
+    call.heights = heights;
+    call.intr = intr_params;
+    call.wt = wtransform_params;
+    call.bounds6 = b;
+    call.count = n_maps;
+    call.with_triangles = true;
+    call.radial = true;
+    call.back_d = write_back_corrected ? depth_maps : nullptr;
+    call.back_c = write_back_corrected ? depth_colors : nullptr;
+    (void)mesh_export("lsnCorrectAndGenerateMesh", ctx().merge, call, out_mesh);
 }
 
 extern "C" void lsnCorrectAndGenerateMesh(int n_maps, unsigned char *depth_maps, unsigned char *depth_colors, int *widths, int *heights,

@@ -560,22 +560,25 @@ struct LsnFusion {
     int stream_half = 0;
     // per-pixel depth thresholds (thresh_kernel): built once the same parameters are used for a second run
     lsn::DevBuf thr;
-    // colour transfer (color.hip), allocated on first use: tile counts / offsets of its index pass, pixel <-> vertex maps, confidence maps,
-    // confidence-tile starts, coverage tables, chosen pairs, per-block sample counts, colour sums, compacted samples, transforms
-    lsn::DevBuf ct_counts, ct_off, ct_pix2v, ct_v2pix, ct_conf, ct_ctile, ct_cov, ct_pairs, ct_blk, ct_stats, ct_samples, ct_xform;
+    // the cloud index the three stages below start from (cloud_index.hip), allocated on first use and rebuilt by every stage from its own
+    // input: tile counts / offsets of the index pass, pixel <-> vertex maps; confidence maps and confidence-tile starts (allocated by the
+    // first stage that asks for them)
+    lsn::DevBuf ix_counts, ix_off, ix_pix2v, ix_v2pix, ix_conf, ix_ctile;
+    bool ix_conf_ready = false;
+    // colour transfer (color.hip), allocated on first use: coverage tables, chosen pairs, per-block sample counts, colour sums, compacted
+    // samples, transforms
+    lsn::DevBuf ct_cov, ct_pairs, ct_blk, ct_stats, ct_samples, ct_xform;
     bool ct_ready = false;
     int ct_nblk = 0;                     // sample blocks per pair (the largest sensor's pixels / 256)
-    // overlay merge (merge.hip), allocated on its first call: index-pass counts, vertex / intermediate triangle offsets, confidence-tile
-    // starts, pixel <-> vertex maps and confidence maps of the raw maps, the reprojected maps (as first built / as modified) and their
-    // pixel -> vertex maps, point_assigned, per-vertex confidence and projection, raster scratch, mapped depth / tag maps, eroded mask
-    lsn::DevBuf mg_counts, mg_voff, mg_toff, mg_ctile, mg_pix2v, mg_v2pix, mg_conf, mg_depth0, mg_depth, mg_d2v, mg_assigned, mg_vconf, mg_proj,
-        mg_zmax, mg_key, mg_mdepth, mg_mtag, mg_ero;
+    // overlay merge (merge.hip), allocated on its first call: intermediate triangle offsets, the reprojected maps (as first built / as
+    // modified) and their pixel -> vertex maps, point_assigned, per-vertex confidence and projection, raster scratch, mapped depth / tag
+    // maps, eroded mask
+    lsn::DevBuf mg_toff, mg_depth0, mg_depth, mg_d2v, mg_assigned, mg_vconf, mg_proj, mg_zmax, mg_key, mg_mdepth, mg_mtag, mg_ero;
     bool mg_ready = false;
-    // outlier filter (outlier.hip), allocated on its first call: index-pass counts / offsets / pixel <-> vertex maps, each vertex's bucket,
-    // the bucket tables and their chunk sums, the points in bucket order, removed flags, per-sensor counts, the caller's offsets, the
-    // sensors' bucket bases and masks, the blocks' bounding boxes and grid frames
-    lsn::DevBuf ol_counts, ol_off, ol_pix2v, ol_v2pix, ol_key, ol_bucket, ol_chunk, ol_pts, ol_removed, ol_stats, ol_offs, ol_tab, ol_box,
-        ol_frame;
+    // outlier filter (outlier.hip), allocated on its first call: each vertex's bucket, the bucket tables and their chunk sums, the points in
+    // bucket order, removed flags, per-sensor counts, the caller's offsets, the sensors' bucket bases and masks, the blocks' bounding boxes
+    // and grid frames
+    lsn::DevBuf ol_key, ol_bucket, ol_chunk, ol_pts, ol_removed, ol_stats, ol_offs, ol_tab, ol_box, ol_frame;
     bool ol_ready = false;
     int ol_nb = 0, ol_nchunk = 0;        // buckets per tick, scan chunks per tick
     bool thr_valid = false;

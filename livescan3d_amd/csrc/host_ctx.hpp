@@ -37,6 +37,8 @@ struct Copy {
 
 constexpr int kMaxGroups = 16;
 
+struct Ctx;
+
 // What one call in flight needs: streams, events, device buffers, plans.  LiveScanServer runs its merge calls (updateWorker: radial
 // correction, generateMeshFromDepthMaps) and its refine calls (refineWorker: generateVerticesFromDepthMap per sensor, then ICP) on two
 // threads (MainWindowForm.cs:238,304); each of the three families has its own lane, so they only meet at the pool of pinned blocks.
@@ -66,6 +68,15 @@ struct Lane {
     std::vector<float> last_intr, last_wt, last_bounds;
     std::vector<Group> groups;
     std::vector<Copy> copies;
+    // the lane's buffers are about to be reused: until a call publishes its mesh, lsnLastMesh* have nothing to read
+    void forget_last()
+    {
+        last_nv = -1;
+        last_plan = nullptr;
+        last_sharded = false;
+    }
+    // the mesh of the call that just ended is the lane's last, and the lane the last of its thread and of the process (host_flows.hip)
+    void publish_last(Ctx &c, int nv, int nt, bool in_hbm, bool sharded, bool radial, bool with_triangles);
 };
 
 // A thread that runs one job at a time for the thread that hands it over.  A pageable upload keeps the thread that issues it until the
@@ -165,12 +176,23 @@ void plan_schedule(std::vector<Group> &groups, std::vector<Copy> &copies, const 
 void plan_shards(int count, int n_devices, int *first, int &D);
 int parse_device_list(const char *text, int n_visible, std::vector<int> &out);
 
+// What one mesh call is, as its export received it.  A record that the export fills by name and the flows read: nothing is decided in it.
+struct MeshCall {
+    const unsigned char *depth_maps = nullptr, *depth_colors = nullptr;   // the caller's packed frames of ALL its sensors ...
+    const int *widths = nullptr, *heights = nullptr;
+    const float *intr = nullptr, *wt = nullptr;                           // ... their intrinsics [7] and world transforms [12] ...
+    const float *bounds6 = nullptr;                                       // ... and the crop box
+    int first = 0, count = 0;                // the sensors of the call: [first, first + count) (generateVerticesFromDepthMap uses one)
+    bool with_triangles = false;
+    bool radial = false;                     // the call starts with the radial correction of the frames, on the device
+    unsigned char *back_d = nullptr, *back_c = nullptr;   // optional: the corrected maps are also copied to these host arrays, like the separate export does
+    bool color_transfer = false, overlay_merge = false;   // the stages on the fused cloud (color.hip, merge.hip) ...
+    int outlier_k = 0;                       // ... and the outlier filter (outlier.hip, lsnSetOutlierFilter): it runs when outlier_k > 0
+    float outlier_max_dist = 0.0f;           //     and outlier_max_dist > 0
+};
+
 // The calls.  The lane's lock is held by the caller; `out` is left untouched on failure (the export then returns an empty mesh).
-// outlier_k / outlier_max_dist: the outlier filter (lsnSetOutlierFilter); it runs when outlier_k > 0 and outlier_max_dist > 0.
-int fuse_host(Ctx &c, Lane &l, const unsigned char *depth_maps, const unsigned char *depth_colors, const int *widths, const int *heights,
-              const float *intr, const float *wt, Mesh *out, const float *bounds6, int first, int count, bool with_triangles, bool radial = false,
-              unsigned char *radial_back_d = nullptr, unsigned char *radial_back_c = nullptr, bool color_transfer = false,
-              bool overlay_merge = false, int outlier_k = 0, float outlier_max_dist = 0.0f);
+int fuse_host(Ctx &c, Lane &l, const MeshCall &call, Mesh *out);
 void radial_host(Ctx &c, Lane &l, int n_maps, unsigned char *depth_maps, unsigned char *depth_colors, const int *widths, const int *heights,
                  const float *intr_params);
 int materialize(Lane &l);                  // lsnLastMesh*: the mesh of the lane's last call in d_out / d_tri

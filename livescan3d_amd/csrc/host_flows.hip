@@ -37,6 +37,18 @@ namespace host {
 // the lane of the calling thread's own last mesh call (lsnLastMesh* read that lane's mesh; include/NativeUtils.h)
 thread_local Lane *t_last_lane = nullptr;
 
+void Lane::publish_last(Ctx &c, int nv, int nt, bool in_hbm, bool sharded, bool radial, bool with_triangles)
+{
+    last_nv = nv;
+    last_nt = nt;
+    last_in_hbm = in_hbm;
+    last_sharded = sharded;
+    last_radial = radial;
+    last_tri = with_triangles;
+    c.last_lane.store(this);
+    t_last_lane = this;
+}
+
 Ctx &ctx()
 {
     static Ctx *c = new Ctx();   // never destroyed: its HIP objects must not be released from a static destructor after the runtime is gone
@@ -383,12 +395,7 @@ struct PhaseTrace {
 struct HostCall {
     Ctx &c;
     Lane &l;
-    const unsigned char *depth_maps, *depth_colors;
-    const int *widths, *heights;
-    const float *intr, *wt, *bounds6;
-    int first, count;                       // the sensors of the call (generateVerticesFromDepthMap uses one)
-    bool with_triangles, radial;            // radial: the call starts with the radial correction of the frames, on the device
-    unsigned char *back_d, *back_c;         // optional: the corrected maps are also copied to these host arrays, like the separate export does
+    const MeshCall &call;
     LsnFusion *plan = nullptr;
     size_t G = 0;
     long long cap = 0;
@@ -397,12 +404,7 @@ struct HostCall {
     const char *run_d = nullptr, *run_c = nullptr;   // what the fusion and triangle launches read: the raw frames, or the corrected ones
     PhaseTrace tr;
 
-    HostCall(Ctx &c_, Lane &l_, const unsigned char *dm, const unsigned char *dc, const int *w, const int *h, const float *in, const float *wtp,
-             const float *b6, int first_, int count_, bool tri, bool rad, unsigned char *bd, unsigned char *bc)
-        : c(c_), l(l_), depth_maps(dm), depth_colors(dc), widths(w), heights(h), intr(in), wt(wtp), bounds6(b6), first(first_), count(count_),
-          with_triangles(tri), radial(rad), back_d(bd), back_c(bc)
-    {
-    }
+    HostCall(Ctx &c_, Lane &l_, const MeshCall &call_) : c(c_), l(l_), call(call_) {}
     HostCall(const HostCall &) = delete;
     HostCall &operator=(const HostCall &) = delete;
     ~HostCall()
@@ -418,9 +420,7 @@ struct HostCall {
     // offsets [count + 1] and the give-up flag.
     int begin(bool in_hbm, int extra_tab)
     {
-        l.last_nv = -1;
-        l.last_plan = nullptr;
-        l.last_sharded = false;
+        l.forget_last();
         static const bool trace_env = getenv("LSN_HOST_TRACE") && atoi(getenv("LSN_HOST_TRACE")) != 0;
         static std::atomic<int> trace_calls{0};
         if (trace_env) {
@@ -429,10 +429,12 @@ struct HostCall {
         }
         tr.mark("enter");
         l.groups.clear();
-        plan = get_plan(c, l, widths, heights, first, count);
+        const int count = call.count;
+        const bool radial = call.radial, with_triangles = call.with_triangles;
+        plan = get_plan(c, l, call.widths, call.heights, call.first, count);
         if (!plan) return -1;
         l.last_plan = plan;
-        if (make_schedule(c, l, widths, heights, first, count, radial, radial)) return -1;
+        if (make_schedule(c, l, call.widths, call.heights, call.first, count, radial, radial)) return -1;
         G = l.groups.size();
         size_t dbytes = 0, cbytes = 0;
         for (const Group &g : l.groups) {
@@ -445,7 +447,7 @@ struct HostCall {
             return -1;
         if (radial && (l.d_depth2.reserve(dbytes + 16) || l.d_colors2.reserve(cbytes + 16))) return -1;
         if (in_hbm && (l.d_out.reserve((size_t)cap * 16) || (with_triangles && l.d_tri.reserve((size_t)cap * 2 * 12)))) return -1;
-        back = radial && back_d && back_c;
+        back = radial && call.back_d && call.back_c;
         // the mesh's host blocks, sized for the most the frames can give (recycled through the pool: the same blocks tick after tick);
         // capacity-sized because the first vertices leave before the count is known
         host = pinned_get(c, (size_t)cap * sizeof(VertexC4ubV3f));
@@ -454,7 +456,7 @@ struct HostCall {
         l.h_off[count] = -1;       // the total: stored by the last tile of the last group
         l.h_off[count + 1] = 0;    // the look-back's give-up flag
         l.h_toff[count] = 0;
-        if (lsnFusionSetParams(plan, intr + 7 * first, wt + 12 * first, bounds6, l.stream)) return -1;
+        if (lsnFusionSetParams(plan, call.intr + 7 * call.first, call.wt + 12 * call.first, call.bounds6, l.stream)) return -1;
         run_d = radial ? l.d_depth2.as<char>() : l.d_depth.as<char>();
         run_c = radial ? l.d_colors2.as<char>() : l.d_colors.as<char>();
         tr.mark("setup");
@@ -472,7 +474,7 @@ struct HostCall {
         for (size_t i = 0; i < l.copies.size(); i++) {
             const Copy &cp = l.copies[i];
             char *dst = (cp.colours ? l.d_colors.as<char>() : l.d_depth.as<char>()) + cp.dev_off;
-            const unsigned char *src = (cp.colours ? depth_colors : depth_maps) + cp.src_off;
+            const unsigned char *src = (cp.colours ? call.depth_colors : call.depth_maps) + cp.src_off;
             const hipError_t e = G == 1 ? hipMemcpyAsync(dst, src, cp.bytes, hipMemcpyHostToDevice, l.stream)
                                         : hipMemcpyWithStream(dst, src, cp.bytes, hipMemcpyHostToDevice, l.up);
             if (e != hipSuccess) {
@@ -483,7 +485,7 @@ struct HostCall {
             for (; next_group < G && l.groups[next_group].ready_after == (int)i + 1; next_group++) {
                 const Group &g = l.groups[next_group];
                 // out of place: raw frames in d_depth / d_colors, corrected ones in the second pair, which the launches read
-                if (radial && lsnFusionRadialCorrectTo(g.radial_plan, intr + 7 * g.first, l.d_depth.as<char>() + g.d_off, l.d_colors.as<char>() + g.c_off,
+                if (call.radial && lsnFusionRadialCorrectTo(g.radial_plan, call.intr + 7 * g.first, l.d_depth.as<char>() + g.d_off, l.d_colors.as<char>() + g.c_off,
                                                        l.d_depth2.as<char>() + g.d_off, l.d_colors2.as<char>() + g.c_off, l.stream))
                     return -1;
                 if (on_group(next_group, g)) return -1;
@@ -496,8 +498,26 @@ struct HostCall {
     // One launch, single pass, over group k's sensors, continuing where group k - 1 stopped (fusion.hip: run_frames).
     int fuse_group(size_t k, const Group &g, void *vertices, int *group_end_mirror, bool host_out)
     {
-        return lsn::run_frames(plan, run_d, run_c, vertices, l.d_off.as<int>(), g.first - first, g.first - first + g.count, k == 0, with_triangles, l.h_off,
-                               group_end_mirror, host_out, l.stream);
+        return lsn::run_frames(plan, run_d, run_c, vertices, l.d_off.as<int>(), g.first - call.first, g.first - call.first + g.count, k == 0,
+                               call.with_triangles, l.h_off, group_end_mirror, host_out, l.stream);
+    }
+
+    // The counts the kernels left in the lane's pinned tables, read once the kernels' stream has drained; refused when the look-back gave
+    // up or when they cannot be.
+    int final_counts(int &nv, int &nt)
+    {
+        nv = l.h_off[call.count];
+        nt = call.with_triangles ? l.h_toff[call.count] : 0;
+        if (l.h_off[call.count + 1] != 0) {
+            (void)lsnFusionCheck(plan, l.stream);   // clears the plan's sticky flag
+            lsn::set_error("NativeUtils: the single-pass fusion gave up on a predecessor tile (look-back spin limit)");
+            return -1;
+        }
+        if (nv < 0 || nv > cap || nt < 0 || nt > 2 * cap) {
+            lsn::set_error("NativeUtils: device returned impossible counts (%d vertices, %d triangles)", nv, nt);
+            return -1;
+        }
+        return 0;
     }
 
     // The mesh is the caller's from here on (deleteMesh returns its blocks to the pool).
@@ -507,18 +527,12 @@ struct HostCall {
             pinned_put(c, host_tri);
             host_tri = nullptr;
         }
-        l.last_nv = nv;
-        l.last_nt = nt;
-        l.last_in_hbm = in_hbm;
-        l.last_radial = radial;
-        l.last_tri = with_triangles;
+        l.publish_last(c, nv, nt, in_hbm, false, call.radial, call.with_triangles);
         out->nVertices = nv;
         out->vertices = static_cast<VertexC4ubV3f *>(host);
         out->nTriangles = nt;
         out->triangles = nt > 0 ? static_cast<int *>(host_tri) : g_no_triangles;
         committed = true;
-        c.last_lane.store(&l);
-        t_last_lane = &l;
         tr.mark("done");
         tr.print();
     }
@@ -551,14 +565,14 @@ int fuse_host_direct(HostCall &h, Mesh *out)
             return h.fuse_group(k, g, h.host, nullptr, true);
         }))
         return -1;
-    if (h.with_triangles && lsn::run_triangles(h.plan, h.run_d, h.host_tri, l.d_tri_off.as<int>(), l.h_toff, true, l.stream)) return -1;
+    if (h.call.with_triangles && lsn::run_triangles(h.plan, h.run_d, h.host_tri, l.d_tri_off.as<int>(), l.h_toff, true, l.stream)) return -1;
     if (h.back) {
         // the corrected maps go home group by group (copy engine, pageable destination: each copy blocks) while the launches run
         for (size_t k = 0; k < h.G; k++) {
             const Group &b = l.groups[k];
             if (hipStreamWaitEvent(l.down, l.ev_group[k], 0) != hipSuccess ||
-                hipMemcpyWithStream(h.back_d + b.d_src, l.d_depth2.as<char>() + b.d_off, b.dbytes, hipMemcpyDeviceToHost, l.down) != hipSuccess ||
-                hipMemcpyWithStream(h.back_c + b.c_src, l.d_colors2.as<char>() + b.c_off, b.cbytes, hipMemcpyDeviceToHost, l.down) != hipSuccess) {
+                hipMemcpyWithStream(h.call.back_d + b.d_src, l.d_depth2.as<char>() + b.d_off, b.dbytes, hipMemcpyDeviceToHost, l.down) != hipSuccess ||
+                hipMemcpyWithStream(h.call.back_c + b.c_src, l.d_colors2.as<char>() + b.c_off, b.cbytes, hipMemcpyDeviceToHost, l.down) != hipSuccess) {
                 lsn::set_error("NativeUtils: write-back of the corrected maps failed: %s", hipGetErrorString(hipGetLastError()));
                 return -1;
             }
@@ -571,17 +585,8 @@ int fuse_host_direct(HostCall &h, Mesh *out)
         return -1;
     }
     h.tr.mark("sync");
-    // the kernels left the counts in the pinned tables
-    const int nv = l.h_off[h.count], nt = h.with_triangles ? l.h_toff[h.count] : 0;
-    if (l.h_off[h.count + 1] != 0) {
-        (void)lsnFusionCheck(h.plan, l.stream);   // clears the plan's sticky flag
-        lsn::set_error("NativeUtils: the single-pass fusion gave up on a predecessor tile (look-back spin limit)");
-        return -1;
-    }
-    if (nv < 0 || nv > h.cap || nt < 0 || nt > 2 * h.cap) {
-        lsn::set_error("NativeUtils: device returned impossible counts (%d vertices, %d triangles)", nv, nt);
-        return -1;
-    }
+    int nv, nt;
+    if (h.final_counts(nv, nt)) return -1;
     h.commit(out, nv, nt, false);
     return 0;
 }
@@ -596,7 +601,7 @@ int fuse_host_grouped(HostCall &h, Mesh *out)
 {
     Lane &l = h.l;
     if (h.begin(true, (int)kMaxGroups)) return -1;   // table: offsets [count + 1], give-up flag, then the groups' end offsets
-    const int count = h.count;
+    const int count = h.call.count;
     int *h_end = l.h_off + count + 2;
     int sent = 0;   // vertices already on their way home
     // group k's launches have been enqueued: when its event has fired, its vertices go home
@@ -618,7 +623,7 @@ int fuse_host_grouped(HostCall &h, Mesh *out)
     };
     // the corrected maps only start home once every upload and launch of the call has been issued (their copies keep the thread)
     auto write_back = [&](size_t k) -> int {
-        const int rc = write_back_runs(l, k, h.back_d, h.back_c);
+        const int rc = write_back_runs(l, k, h.call.back_d, h.call.back_c);
         h.tr.mark("back");
         return rc;
     };
@@ -631,7 +636,7 @@ int fuse_host_grouped(HostCall &h, Mesh *out)
     // the triangle passes over the whole tick, behind the last group (they only read what the groups left in HBM); ev_tri fires when the
     // triangle COUNTS are in the pinned table -- behind the scan, before the write pass -- so the block for the triangles is there and
     // its download queued while the write pass still runs
-    if (h.with_triangles && lsn::run_triangles(h.plan, h.run_d, l.d_tri.p, l.d_tri_off.as<int>(), l.h_toff, false, l.stream, l.ev_tri)) return -1;
+    if (h.call.with_triangles && lsn::run_triangles(h.plan, h.run_d, l.d_tri.p, l.d_tri_off.as<int>(), l.h_toff, false, l.stream, l.ev_tri)) return -1;
     // the corrected maps of all groups but the last (their events fired long ago), the last group's vertices, then the triangles
     // (asynchronous) BEFORE the last group's maps, so that the thread-keeping copies share the link with the triangle download
     if (h.back)
@@ -640,7 +645,7 @@ int fuse_host_grouped(HostCall &h, Mesh *out)
     if (service(h.G - 1)) return -1;
     const int nv = sent;
     int nt = 0;
-    if (h.with_triangles) {
+    if (h.call.with_triangles) {
         if (hipEventSynchronize(l.ev_tri) != hipSuccess) {
             lsn::set_error("NativeUtils: %s", hipGetErrorString(hipGetLastError()));
             return -1;
@@ -679,26 +684,27 @@ int fuse_host_grouped(HostCall &h, Mesh *out)
 // then the correction runs in place (color.hip), the merge rebuilds the triangles (merge.hip), and the mesh leaves in one copy.  Without
 // the merge the triangles do not depend on the colours; they are built as in flow 2.  The merge reads the positions alone, so the two
 // commute.
-// With the outlier filter on (outlier_k > 0) the tick's cloud is filtered per sensor where it lies (outlier.hip), the removed vertices'
+// With the outlier filter on (`filter`: fuse_host decides) the tick's cloud is filtered per sensor where it lies (outlier.hip), the removed vertices'
 // pixels become depth 0 in a copy of the maps, and the groups fuse again from that copy: everything after -- triangles, colour transfer,
 // overlay merge -- is the call on the masked maps.  The corrected maps a call that starts with the radial correction
 // writes back are the unmasked ones.
-int fuse_host_color(HostCall &h, Mesh *out, bool color_transfer, bool overlay_merge, int outlier_k = 0, float outlier_max_dist = 0.0f)
+int fuse_host_color(HostCall &h, Mesh *out, bool filter)
 {
     Lane &l = h.l;
+    const MeshCall &call = h.call;
     if (h.begin(true, 0)) return -1;
-    const int count = h.count;
+    const int count = call.count;
     if (h.upload([&](size_t k, const Group &g) -> int { return h.fuse_group(k, g, l.d_out.p, nullptr, false); })) return -1;
-    if (outlier_k > 0) {
+    if (filter) {
         size_t dbytes = 0;
         for (const Group &g : l.groups) dbytes += g.dbytes;
         if (l.d_masked.reserve(dbytes + 16) ||
-            lsn::outlier_filter(h.plan, outlier_k, outlier_max_dist, h.run_d, l.d_out.p, l.d_off.as<int>(), l.d_masked.p, l.stream))
+            lsn::outlier_filter(h.plan, call.outlier_k, call.outlier_max_dist, h.run_d, l.d_out.p, l.d_off.as<int>(), l.d_masked.p, l.stream))
             return -1;
         if (h.back) {
             LSN_HIP(hipStreamSynchronize(l.stream));   // every group's corrected maps are final
             for (size_t k = 0; k < h.G; k++)
-                if (write_back_runs(l, k, h.back_d, h.back_c)) return -1;
+                if (write_back_runs(l, k, call.back_d, call.back_c)) return -1;
             LSN_HIP(hipStreamSynchronize(l.back));
             h.back = false;
         }
@@ -706,10 +712,10 @@ int fuse_host_color(HostCall &h, Mesh *out, bool color_transfer, bool overlay_me
         for (size_t k = 0; k < h.G; k++)
             if (h.fuse_group(k, l.groups[k], l.d_out.p, nullptr, false)) return -1;
     }
-    if (h.with_triangles && !overlay_merge && lsn::run_triangles(h.plan, h.run_d, l.d_tri.p, l.d_tri_off.as<int>(), l.h_toff, false, l.stream))
+    if (call.with_triangles && !call.overlay_merge && lsn::run_triangles(h.plan, h.run_d, l.d_tri.p, l.d_tri_off.as<int>(), l.h_toff, false, l.stream))
         return -1;
-    if (color_transfer && lsn::color_transfer(h.plan, h.run_d, l.d_out.p, l.d_off.as<int>(), l.stream)) return -1;
-    if (h.with_triangles && overlay_merge) {
+    if (call.color_transfer && lsn::color_transfer(h.plan, h.run_d, l.d_out.p, l.d_off.as<int>(), l.stream)) return -1;
+    if (call.with_triangles && call.overlay_merge) {
         if (lsn::overlay_merge(h.plan, h.run_d, l.d_out.p, l.d_off.as<int>(), l.d_tri.p, l.d_tri_off.as<int>(), l.stream)) return -1;
         LSN_HIP(hipMemcpyAsync(l.h_toff, l.d_tri_off.as<int>(), sizeof(int) * (size_t)(count + 1), hipMemcpyDeviceToHost, l.stream));
     }
@@ -718,16 +724,8 @@ int fuse_host_color(HostCall &h, Mesh *out, bool color_transfer, bool overlay_me
         return -1;
     }
     h.tr.mark("sync");
-    const int nv = l.h_off[count], nt = h.with_triangles ? l.h_toff[count] : 0;
-    if (l.h_off[count + 1] != 0) {
-        (void)lsnFusionCheck(h.plan, l.stream);   // clears the plan's sticky flag
-        lsn::set_error("NativeUtils: the single-pass fusion gave up on a predecessor tile (look-back spin limit)");
-        return -1;
-    }
-    if (nv < 0 || nv > h.cap || nt < 0 || nt > 2 * h.cap) {
-        lsn::set_error("NativeUtils: device returned impossible counts (%d vertices, %d triangles)", nv, nt);
-        return -1;
-    }
+    int nv, nt;
+    if (h.final_counts(nv, nt)) return -1;
     if (nt > 0 && !(h.host_tri = pinned_get(h.c, (size_t)nt * 12))) return -1;
     LSN_HIP(hipMemcpyAsync(h.host, l.d_out.p, (size_t)nv * 16, hipMemcpyDeviceToHost, l.stream));
     if (nt > 0) LSN_HIP(hipMemcpyAsync(h.host_tri, l.d_tri.p, (size_t)nt * 12, hipMemcpyDeviceToHost, l.stream));
@@ -752,13 +750,10 @@ int fuse_host_color(HostCall &h, Mesh *out, bool color_transfer, bool overlay_me
 // One thread per device, because a pageable upload keeps the thread that issues it.
 struct ShardedCall {
     Ctx &c;
-    const unsigned char *depth_maps, *depth_colors;
-    const int *widths, *heights;
-    const float *intr, *wt, *bounds6;
-    int count = 0, D = 0;
-    bool with_triangles = false, radial = false, back = false;
+    const MeshCall &call;                              // first = 0: every sensor of the caller's arrays
+    int D = 0;
+    bool back = false;                                 // the corrected maps go home as well
     bool only_radial = false;                          // depthMapAndColorSetRadialCorrection: correct and write back, no mesh
-    unsigned char *back_d = nullptr, *back_c = nullptr;
     int first[kMaxShards + 1] = {};                    // device d owns sensors [first[d], first[d + 1])
     void *host = nullptr, *host_tri = nullptr;
     std::atomic<int> nv[kMaxShards], nt[kMaxShards];   // -1 = not known yet
@@ -766,7 +761,7 @@ struct ShardedCall {
     std::mutex err_mu;
     char error[lsn::kErrorLen] = {0};
 
-    explicit ShardedCall(Ctx &c_) : c(c_)
+    ShardedCall(Ctx &c_, const MeshCall &call_) : c(c_), call(call_)
     {
         for (int d = 0; d < kMaxShards; d++) {
             nv[d].store(-1);
@@ -808,47 +803,48 @@ void plan_shards(int count, int n_devices, int *first, int &D)
 int shard_part(ShardedCall &sc, int d)
 {
     Ctx &c = sc.c;
+    const MeshCall &call = sc.call;
     Lane &l = c.shards[d]->lane;
     LSN_HIP(hipSetDevice(l.device));
     const int f0 = sc.first[d], n = sc.first[d + 1] - f0;
     size_t d_src = 0, c_src = 0, dbytes = 0, cbytes = 0;
     for (int i = 0; i < f0 + n; i++) {
-        const size_t px = (size_t)sc.widths[i] * sc.heights[i];
+        const size_t px = (size_t)call.widths[i] * call.heights[i];
         (i < f0 ? d_src : dbytes) += px * 2;
         (i < f0 ? c_src : cbytes) += px * 3;
     }
     l.groups.clear();
-    LsnFusion *plan = get_plan(c, l, sc.widths, sc.heights, f0, n);
+    LsnFusion *plan = get_plan(c, l, call.widths, call.heights, f0, n);
     if (!plan) return -1;
     if (sc.only_radial) {
         // the radial export alone: this block up over this device's link, corrected out of place, home again (both ways pageable copies
         // that keep this thread -- which is why every device has one)
         if (l.d_depth.reserve(dbytes + 16) || l.d_colors.reserve(cbytes + 16) || l.d_depth2.reserve(dbytes + 16) || l.d_colors2.reserve(cbytes + 16)) return -1;
-        LSN_HIP(hipMemcpyWithStream(l.d_depth.p, sc.depth_maps + d_src, dbytes, hipMemcpyHostToDevice, l.up));
-        LSN_HIP(hipMemcpyWithStream(l.d_colors.p, sc.depth_colors + c_src, cbytes, hipMemcpyHostToDevice, l.up));
-        if (lsnFusionRadialCorrectTo(plan, sc.intr + 7 * f0, l.d_depth.p, l.d_colors.p, l.d_depth2.p, l.d_colors2.p, l.stream)) return -1;
+        LSN_HIP(hipMemcpyWithStream(l.d_depth.p, call.depth_maps + d_src, dbytes, hipMemcpyHostToDevice, l.up));
+        LSN_HIP(hipMemcpyWithStream(l.d_colors.p, call.depth_colors + c_src, cbytes, hipMemcpyHostToDevice, l.up));
+        if (lsnFusionRadialCorrectTo(plan, call.intr + 7 * f0, l.d_depth.p, l.d_colors.p, l.d_depth2.p, l.d_colors2.p, l.stream)) return -1;
         LSN_HIP(hipStreamSynchronize(l.stream));
-        LSN_HIP(hipMemcpyWithStream(sc.back_d + d_src, l.d_depth2.p, dbytes, hipMemcpyDeviceToHost, l.back));
-        LSN_HIP(hipMemcpyWithStream(sc.back_c + c_src, l.d_colors2.p, cbytes, hipMemcpyDeviceToHost, l.back));
+        LSN_HIP(hipMemcpyWithStream(call.back_d + d_src, l.d_depth2.p, dbytes, hipMemcpyDeviceToHost, l.back));
+        LSN_HIP(hipMemcpyWithStream(call.back_c + c_src, l.d_colors2.p, cbytes, hipMemcpyDeviceToHost, l.back));
         return 0;
     }
     const long long cap = lsnFusionTickCapacity(plan);
     if (l.d_depth.reserve(dbytes + 16) || l.d_colors.reserve(cbytes + 16) || l.d_off.reserve(sizeof(int) * (size_t)(n + 1)) ||
         l.d_tri_off.reserve(sizeof(int) * (size_t)(n + 1)) || ensure_tables(l, n + 2))
         return -1;
-    if (sc.radial && (l.d_depth2.reserve(dbytes + 16) || l.d_colors2.reserve(cbytes + 16))) return -1;
-    if (lsnFusionSetParams(plan, sc.intr + 7 * f0, sc.wt + 12 * f0, sc.bounds6, l.stream)) return -1;
-    const char *run_d = sc.radial ? l.d_depth2.as<char>() : l.d_depth.as<char>();
-    const char *run_c = sc.radial ? l.d_colors2.as<char>() : l.d_colors.as<char>();
+    if (call.radial && (l.d_depth2.reserve(dbytes + 16) || l.d_colors2.reserve(cbytes + 16))) return -1;
+    if (lsnFusionSetParams(plan, call.intr + 7 * f0, call.wt + 12 * f0, call.bounds6, l.stream)) return -1;
+    const char *run_d = call.radial ? l.d_depth2.as<char>() : l.d_depth.as<char>();
+    const char *run_c = call.radial ? l.d_colors2.as<char>() : l.d_colors.as<char>();
     l.h_off[n] = -1;
     l.h_toff[n] = -1;
     hipEvent_t ev_counted = l.ev_group[0], ev_corrected = l.ev_group[1];
     // depth up; the count pass (depth only) runs while the colours follow -- unless the call starts with the correction, which needs both
-    LSN_HIP(hipMemcpyWithStream(l.d_depth.p, sc.depth_maps + d_src, dbytes, hipMemcpyHostToDevice, l.up));
-    if (!sc.radial && lsn::run_count(plan, run_d, run_c, l.d_off.as<int>(), l.h_off, ev_counted, l.stream)) return -1;
-    LSN_HIP(hipMemcpyWithStream(l.d_colors.p, sc.depth_colors + c_src, cbytes, hipMemcpyHostToDevice, l.up));
-    if (sc.radial) {
-        if (lsnFusionRadialCorrectTo(plan, sc.intr + 7 * f0, l.d_depth.p, l.d_colors.p, l.d_depth2.p, l.d_colors2.p, l.stream)) return -1;
+    LSN_HIP(hipMemcpyWithStream(l.d_depth.p, call.depth_maps + d_src, dbytes, hipMemcpyHostToDevice, l.up));
+    if (!call.radial && lsn::run_count(plan, run_d, run_c, l.d_off.as<int>(), l.h_off, ev_counted, l.stream)) return -1;
+    LSN_HIP(hipMemcpyWithStream(l.d_colors.p, call.depth_colors + c_src, cbytes, hipMemcpyHostToDevice, l.up));
+    if (call.radial) {
+        if (lsnFusionRadialCorrectTo(plan, call.intr + 7 * f0, l.d_depth.p, l.d_colors.p, l.d_depth2.p, l.d_colors2.p, l.stream)) return -1;
         LSN_HIP(hipEventRecord(ev_corrected, l.stream));
         if (lsn::run_count(plan, run_d, run_c, l.d_off.as<int>(), l.h_off, ev_counted, l.stream)) return -1;
     }
@@ -865,16 +861,16 @@ int shard_part(ShardedCall &sc, int d)
         lsn::set_error("NativeUtils: the merged cloud exceeds 2^31-1 vertices");
         return -1;
     }
-    if (lsn::run_write(plan, run_d, run_c, static_cast<char *>(sc.host) + (size_t)base * 16, l.d_off.as<int>(), sc.with_triangles, true, l.stream)) return -1;
-    if (sc.with_triangles && lsn::run_triangles_count(plan, run_d, l.d_tri_off.as<int>(), l.h_toff, l.ev_tri, l.stream)) return -1;
+    if (lsn::run_write(plan, run_d, run_c, static_cast<char *>(sc.host) + (size_t)base * 16, l.d_off.as<int>(), call.with_triangles, true, l.stream)) return -1;
+    if (call.with_triangles && lsn::run_triangles_count(plan, run_d, l.d_tri_off.as<int>(), l.h_toff, l.ev_tri, l.stream)) return -1;
     if (sc.back) {
         // the corrected maps of this block go home (pageable destination: the copies keep this thread) while the write pass stores and the
         // triangle count pass, already queued, runs behind it
         LSN_HIP(hipStreamWaitEvent(l.back, ev_corrected, 0));
-        LSN_HIP(hipMemcpyWithStream(sc.back_d + d_src, l.d_depth2.p, dbytes, hipMemcpyDeviceToHost, l.back));
-        LSN_HIP(hipMemcpyWithStream(sc.back_c + c_src, l.d_colors2.p, cbytes, hipMemcpyDeviceToHost, l.back));
+        LSN_HIP(hipMemcpyWithStream(call.back_d + d_src, l.d_depth2.p, dbytes, hipMemcpyDeviceToHost, l.back));
+        LSN_HIP(hipMemcpyWithStream(call.back_c + c_src, l.d_colors2.p, cbytes, hipMemcpyDeviceToHost, l.back));
     }
-    if (sc.with_triangles) {
+    if (call.with_triangles) {
         LSN_HIP(hipEventSynchronize(l.ev_tri));
         const int nt = l.h_toff[n];
         if (nt < 0 || nt > 2 * cap) {
@@ -977,40 +973,33 @@ int run_parts(Ctx &c, ShardedCall &sc)
 int radial_sharded(Ctx &c, Lane &ml, int n_maps, unsigned char *depth_maps, unsigned char *depth_colors, const int *widths, const int *heights,
                    const float *intr)
 {
-    ml.last_nv = -1;
-    ml.last_plan = nullptr;
-    ml.last_sharded = false;
-    ShardedCall sc(c);
-    sc.depth_maps = depth_maps; sc.depth_colors = depth_colors;
-    sc.widths = widths; sc.heights = heights;
-    sc.intr = intr;
-    sc.count = n_maps;
+    ml.forget_last();
+    MeshCall call;
+    call.depth_maps = depth_maps;
+    call.depth_colors = depth_colors;
+    call.widths = widths;
+    call.heights = heights;
+    call.intr = intr;
+    call.count = n_maps;
+    call.radial = true;
+    call.back_d = depth_maps;
+    call.back_c = depth_colors;
+    ShardedCall sc(c, call);
     sc.only_radial = true;
-    sc.back_d = depth_maps; sc.back_c = depth_colors;
     plan_shards(n_maps, (int)c.shards.size(), sc.first, sc.D);
     return run_parts(c, sc);
 }
 
 // The merge lane's lock is held (it serialises the calls; the shards' lanes are only ever used under it).
-int fuse_host_sharded(Ctx &c, Lane &ml, const unsigned char *depth_maps, const unsigned char *depth_colors, const int *widths, const int *heights,
-                      const float *intr, const float *wt, Mesh *out, const float *bounds6, int count, bool with_triangles, bool radial,
-                      unsigned char *radial_back_d, unsigned char *radial_back_c)
+int fuse_host_sharded(Ctx &c, Lane &ml, const MeshCall &call, Mesh *out)
 {
-    ml.last_nv = -1;
-    ml.last_plan = nullptr;
-    ml.last_sharded = false;
-    ShardedCall sc(c);
-    sc.depth_maps = depth_maps; sc.depth_colors = depth_colors;
-    sc.widths = widths; sc.heights = heights;
-    sc.intr = intr; sc.wt = wt; sc.bounds6 = bounds6;
-    sc.count = count;
-    sc.with_triangles = with_triangles;
-    sc.radial = radial;
-    sc.back = radial && radial_back_d && radial_back_c;
-    sc.back_d = radial_back_d; sc.back_c = radial_back_c;
+    ml.forget_last();
+    const int count = call.count;
+    ShardedCall sc(c, call);
+    sc.back = call.radial && call.back_d && call.back_c;
     plan_shards(count, (int)c.shards.size(), sc.first, sc.D);
     long long cap = 0;
-    for (int i = 0; i < count; i++) cap += (long long)widths[i] * heights[i];
+    for (int i = 0; i < count; i++) cap += (long long)call.widths[i] * call.heights[i];
     if (cap > 0x7FFFFFFFll) {
         lsn::set_error("NativeUtils: a tick may not exceed 2^31-1 pixels (Mesh.nVertices is an int)");
         return -1;
@@ -1029,7 +1018,7 @@ int fuse_host_sharded(Ctx &c, Lane &ml, const unsigned char *depth_maps, const u
     } blocks(c);
     blocks.host = pinned_get(c, (size_t)cap * sizeof(VertexC4ubV3f));
     if (!blocks.host) return -1;
-    if (with_triangles && !(blocks.host_tri = pinned_get(c, (size_t)cap * 2 * 12))) return -1;
+    if (call.with_triangles && !(blocks.host_tri = pinned_get(c, (size_t)cap * 2 * 12))) return -1;
     sc.host = blocks.host;
     sc.host_tri = blocks.host_tri;
     if (run_parts(c, sc)) return -1;
@@ -1043,24 +1032,17 @@ int fuse_host_sharded(Ctx &c, Lane &ml, const unsigned char *depth_maps, const u
         blocks.host_tri = nullptr;
     }
     // what lsnLastMesh* would need to rebuild this mesh on one device (materialize)
-    ml.last_w.assign(widths, widths + count);
-    ml.last_h.assign(heights, heights + count);
-    ml.last_intr.assign(intr, intr + 7 * (size_t)count);
-    ml.last_wt.assign(wt, wt + 12 * (size_t)count);
-    ml.last_bounds.assign(bounds6, bounds6 + 6);
-    ml.last_nv = (int)nv;
-    ml.last_nt = (int)nt;
-    ml.last_in_hbm = false;
-    ml.last_sharded = true;
-    ml.last_radial = radial;
-    ml.last_tri = with_triangles;
+    ml.last_w.assign(call.widths, call.widths + count);
+    ml.last_h.assign(call.heights, call.heights + count);
+    ml.last_intr.assign(call.intr, call.intr + 7 * (size_t)count);
+    ml.last_wt.assign(call.wt, call.wt + 12 * (size_t)count);
+    ml.last_bounds.assign(call.bounds6, call.bounds6 + 6);
+    ml.publish_last(c, (int)nv, (int)nt, false, true, call.radial, call.with_triangles);
     out->nVertices = (int)nv;
     out->vertices = static_cast<VertexC4ubV3f *>(blocks.host);
     out->nTriangles = (int)nt;
     out->triangles = nt > 0 ? static_cast<int *>(blocks.host_tri) : g_no_triangles;
     blocks.committed = true;
-    c.last_lane.store(&ml);
-    t_last_lane = &ml;
     return 0;
 }
 
@@ -1126,24 +1108,19 @@ int materialize(Lane &l)
 //   calls that start with the radial correction: mesh in HBM, asynchronous copies home group by group (1.1 against 1.26 ms: the ~100 us
 //       of latency-bound closing rounds per group cannot hide behind a storing kernel, but they do hide behind a DMA).
 // $LSN_HOST_PATH=direct / grouped forces one of them for every call (A/B runs).
-int fuse_host(Ctx &c, Lane &l, const unsigned char *depth_maps, const unsigned char *depth_colors, const int *widths, const int *heights,
-              const float *intr, const float *wt, Mesh *out, const float *bounds6, int first, int count, bool with_triangles, bool radial,
-              unsigned char *radial_back_d, unsigned char *radial_back_c, bool color_transfer, bool overlay_merge, int outlier_k,
-              float outlier_max_dist)
+int fuse_host(Ctx &c, Lane &l, const MeshCall &call, Mesh *out)
 {
     // the outlier filter runs for k > 0 and max_dist > 0; k <= 0, max_dist <= 0 and a NaN max_dist change nothing (outlier.hip), so
     // those calls take the flows of a call without it
-    const bool filter = outlier_k > 0 && outlier_max_dist > 0.0f;
+    const bool filter = call.outlier_k > 0 && call.outlier_max_dist > 0.0f;
+    const bool whole_cloud = call.color_transfer || call.overlay_merge || filter;
     // a merge call on a context with several devices ($LSN_HOST_DEVICES), more than one sensor: one sensor block per device and link --
     // except with colour transfer, the overlay merge or the outlier filter, which need the whole cloud in HBM: that call runs on the first
     // device alone (flow 2b)
-    if (&l == &c.merge && c.shards.size() >= 2 && count >= 2 && first == 0 && !color_transfer && !overlay_merge && !filter)
-        return fuse_host_sharded(c, l, depth_maps, depth_colors, widths, heights, intr, wt, out, bounds6, count, with_triangles, radial, radial_back_d,
-                                 radial_back_c);
-    HostCall h(c, l, depth_maps, depth_colors, widths, heights, intr, wt, bounds6, first, count, with_triangles, radial, radial_back_d, radial_back_c);
-    if (filter) return fuse_host_color(h, out, color_transfer, overlay_merge, outlier_k, outlier_max_dist);
-    if (color_transfer || overlay_merge) return fuse_host_color(h, out, color_transfer, overlay_merge);
-    const bool direct = c.host_path == 1 || (c.host_path == 0 && !radial);
+    if (&l == &c.merge && c.shards.size() >= 2 && call.count >= 2 && call.first == 0 && !whole_cloud) return fuse_host_sharded(c, l, call, out);
+    HostCall h(c, l, call);
+    if (whole_cloud) return fuse_host_color(h, out, filter);
+    const bool direct = c.host_path == 1 || (c.host_path == 0 && !call.radial);
     return direct ? fuse_host_direct(h, out) : fuse_host_grouped(h, out);
 }
 

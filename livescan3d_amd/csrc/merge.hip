@@ -5,8 +5,8 @@
 // generateTriangles (:1659-1691) on every sensor's MODIFIED depth_map / depth_to_vertices_map and formMesh (:1578-1629).  The merge
 // removes, adds or reorders no vertex and touches no colour: only the triangle list changes.  On the device, over every tick of the plan:
 //
-//   0. pixel <-> vertex maps and confidence maps of the raw depth maps: color.hip's ct_index_kernel / ct_conf_kernel, into the merge's own
-//      buffers (vertices_to_depth_map and confidence_map of the reference).
+//   0. pixel <-> vertex maps and confidence maps of the raw depth maps: the plan's cloud index (cloud_index.hip; vertices_to_depth_map
+//      and confidence_map of the reference).
 //   1. reprojection (mg_reproject_kernel, :1241-1248, projectVerticesIntoDepthMap :749-782 with includeAssigned = false): every vertex
 //      projected with the inverse of its own pose; the last vertex that lands on a pixel wins (an atomicMax of the vertex index, then
 //      the winner writes its depth).  No d == 0 test here.
@@ -24,7 +24,7 @@
 //
 // Defined here where the reference is not: float -> unsigned short as x64 code converts (cvttss2si, then the low 16
 // bits); every sensor must have the same size (the reference strides an overlay with the base's width); no debug images or timings.
-// Compiled as part of mesh.hip's translation unit (after color.hip, whose project / cvt_i32_x64 / index and confidence kernels it uses).
+// Compiled as part of mesh.hip's translation unit (after cloud_index.hip, whose project / cvt_i32_x64 and cloud index it uses).
 #include "fusion_shared.hpp"
 
 namespace {
@@ -260,13 +260,9 @@ static int overlay_merge_locked(LsnFusion *p, const void *d_depth, const void *d
             return -1;
         }
     LSN_HIP(hipSetDevice(p->device));
-    std::vector<int> ctile(n + 1, 0);
-    for (int i = 0; i < n; i++) ctile[i + 1] = ctile[i] + ((p->w[i] + kConfTile - 1) / kConfTile) * ((p->h[i] + kConfTile - 1) / kConfTile);
     const size_t px = (size_t)p->cap * T;
     if (!p->mg_ready) {
-        if (p->mg_counts.reserve(sizeof(int) * (size_t)p->tiles_per_tick * T) || p->mg_voff.reserve(sizeof(int) * (size_t)(n + 1) * T) ||
-            p->mg_toff.reserve(sizeof(int) * (size_t)(n + 1) * T) || p->mg_ctile.reserve(sizeof(int) * (size_t)(n + 1)) ||
-            p->mg_pix2v.reserve(sizeof(int) * px) || p->mg_v2pix.reserve(sizeof(int) * px) || p->mg_conf.reserve(px) ||
+        if (p->mg_toff.reserve(sizeof(int) * (size_t)(n + 1) * T) ||
             p->mg_depth0.reserve(sizeof(unsigned short) * px) || p->mg_depth.reserve(sizeof(unsigned short) * px) ||
             p->mg_d2v.reserve(sizeof(int) * px) || p->mg_assigned.reserve(px) || p->mg_vconf.reserve(px) ||
             p->mg_proj.reserve(sizeof(int2) * px) || p->mg_zmax.reserve(sizeof(int) * px) ||
@@ -275,28 +271,17 @@ static int overlay_merge_locked(LsnFusion *p, const void *d_depth, const void *d
             p->tri_counts.reserve(sizeof(int) * (size_t)p->tiles_per_tick * T) ||
             p->tri_codes.reserve(sizeof(unsigned int) * (size_t)p->tiles_per_tick * T * kThreads))
             return -1;
-        LSN_HIP(hipMemcpy(p->mg_ctile.p, ctile.data(), sizeof(int) * (size_t)(n + 1), hipMemcpyHostToDevice));
         p->mg_ready = true;
     }
-    // 0. pixel <-> vertex maps and confidence maps of the raw depth maps (color.hip)
-    FuseArgs fa;
-    fill_args(p, fa, d_depth, d_depth, const_cast<void *>(d_vertices), p->mg_voff.as<int>());
-    fa.thr = nullptr;
-    hipLaunchKernelGGL(ct_index_kernel<0>, dim3(p->tiles_per_tick, T), dim3(kThreads), 0, s, fa, p->mg_counts.as<int>(), p->mg_pix2v.as<int>(),
-                       p->mg_v2pix.as<int>());
-    hipLaunchKernelGGL(scan_kernel, dim3(T), dim3(kScanThreads), 0, s, p->mg_counts.as<int>(), p->tiles_per_tick, fa.frames, n,
-                       p->mg_voff.as<int>(), (int *)nullptr);
-    hipLaunchKernelGGL(ct_index_kernel<1>, dim3(p->tiles_per_tick, T), dim3(kThreads), 0, s, fa, p->mg_counts.as<int>(), p->mg_pix2v.as<int>(),
-                       p->mg_v2pix.as<int>());
-    hipLaunchKernelGGL(ct_conf_kernel, dim3(ctile[n], T), dim3(256), 0, s, fa.frames, p->mg_ctile.as<int>(), n,
-                       static_cast<const unsigned short *>(d_depth), p->tick_depth_elems, p->mg_conf.as<unsigned char>());
+    // 0. pixel <-> vertex maps and confidence maps of the raw depth maps
+    if (cloud_index_locked(p, d_depth, const_cast<void *>(d_vertices), true, s)) return -1;
     MgArgs a;
-    a.frames = fa.frames;
-    a.params = fa.params;
+    a.frames = p->frames.as<FrameDesc>();
+    a.params = p->params.as<SensorParams>();
     a.verts = static_cast<const uint4 *>(d_vertices);
     a.voff = d_offsets;
-    a.v2pix = p->mg_v2pix.as<int>();
-    a.conf = p->mg_conf.as<unsigned char>();
+    a.v2pix = p->ix_v2pix.as<int>();
+    a.conf = p->ix_conf.as<unsigned char>();
     a.depth = p->mg_depth.as<unsigned short>();
     a.d2v = p->mg_d2v.as<int>();
     a.assigned = p->mg_assigned.as<unsigned char>();
@@ -388,7 +373,7 @@ static int lsnFusionOverlayDiagnostics_impl(LsnFusion *p, int tick, unsigned sho
     hipStream_t s = lsn::as_stream(stream);
     const int n = p->n_maps;
     std::vector<int> off((size_t)n + 1);
-    LSN_HIP(hipMemcpyAsync(off.data(), p->mg_voff.as<int>() + (size_t)tick * (n + 1), sizeof(int) * (n + 1), hipMemcpyDeviceToHost, s));
+    LSN_HIP(hipMemcpyAsync(off.data(), p->ix_off.as<int>() + (size_t)tick * (n + 1), sizeof(int) * (n + 1), hipMemcpyDeviceToHost, s));
     const size_t pix = (size_t)p->tick_depth_elems;
     if (reprojected)
         LSN_HIP(hipMemcpyAsync(reprojected, p->mg_depth0.as<unsigned short>() + (size_t)tick * pix, sizeof(unsigned short) * pix, hipMemcpyDeviceToHost, s));

@@ -616,12 +616,14 @@ int lsn::run_triangles_write(LsnFusion *p, const void *d_depth, void *d_triangle
     return triangle_write_pass(p, d_depth, d_triangles, index_base, host_out, s);
 }
 
-// The colour transfer of the merge call (bcolor_transfer) lives in color.hip and is compiled here, in the translation unit of the
-// triangulation it runs beside: it uses the same plan and tile machinery (fusion_shared.hpp), and every build that lists the library's
-// translation units -- the product Makefile and the host-side sanitizer builds of tests/fake_hip -- compiles it without listing it.
+// The three stages that work on the fused cloud live in files of their own and are compiled here, in the translation unit of the
+// triangulation they run beside: they use the same plan and tile machinery (fusion_shared.hpp), and every build that lists the library's
+// translation units -- the product Makefile and the host-side sanitizer builds of tests/fake_hip -- compiles them without listing them.
+// What more than one of them uses (the plan's cloud index, the projection, the block scan):
+#include "cloud_index.hip"
+// The colour transfer of the merge call (bcolor_transfer):
 #include "color.hip"
-// The overlay merge (bgenerate_triangles) likewise: it re-runs these triangle passes on its reprojected maps and shares color.hip's
-// projection, index pass and confidence maps.
+// The overlay merge (bgenerate_triangles): it re-runs these triangle passes on its reprojected maps.
 #include "merge.hip"
-// The outlier filter likewise: it reuses color.hip's index pass and block scan.
+// The outlier filter (lsnSetOutlierFilter):
 #include "outlier.hip"

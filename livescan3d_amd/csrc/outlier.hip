@@ -14,7 +14,7 @@
 // Scope (DESIGN.md sections 2 and 11): every sensor's block of every tick on its own -- the cloud generateVerticesFromDepthMap returns
 // for that sensor; a removed vertex becomes depth 0 at its pixel, and the caller fuses the masked maps again.  Stages, each ONE launch over
 // all ticks and sensors of the plan:
-//   1. index pass (color.hip's ct_index_kernel<0>, scan_kernel, ct_index_kernel<1>): the pixel of every vertex.
+//   1. index pass (the plan's cloud index without the confidence maps, cloud_index.hip): the pixel of every vertex.
 //   2. grid (ol_box_kernel, ol_frame_kernel, ol_key_kernel, ol_chunk_kernel<0>, ct_block_scan_kernel, ol_chunk_kernel<1>,
 //      ol_scatter_kernel): the bounding box of every (tick, sensor) block; every vertex's cell of a uniform grid anchored at the box's
 //      corner whose edge is at least maxDist and at least 2^-20 of the box's extent (ol_cell below), hashed into its sensor's table of
@@ -29,7 +29,7 @@
 //      stops at k.  Duplicates or a radius larger than the cloud do not make this quadratic: every candidate then counts, and the walk
 //      stops after k of them.
 //   4. mask (ol_mask_kernel): depth 0 at the pixels of removed vertices, in d_depth_out (a copy of the input maps unless in place).
-// Compiled as part of mesh.hip's translation unit (the include at its end), not on its own.
+// Compiled as part of mesh.hip's translation unit (after cloud_index.hip, whose cloud index, sensor_of and block scan it uses).
 #include "fusion_shared.hpp"
 
 #include <cfloat>
@@ -374,8 +374,7 @@ static int outlier_filter_locked(LsnFusion *p, int k, float max_dist, const void
         }
         const int nchunk = (int)((nb + kOlChunk - 1) / kOlChunk);
         const size_t px = (size_t)p->cap * T;
-        if (p->ol_counts.reserve(sizeof(int) * (size_t)p->tiles_per_tick * T) || p->ol_off.reserve(sizeof(int) * (size_t)(n + 1) * T) ||
-            p->ol_pix2v.reserve(sizeof(int) * px) || p->ol_v2pix.reserve(sizeof(int) * px) || p->ol_key.reserve(sizeof(int) * px) ||
+        if (p->ol_key.reserve(sizeof(int) * px) ||
             p->ol_bucket.reserve(sizeof(int) * (size_t)nb * T) || p->ol_chunk.reserve(sizeof(int) * (size_t)nchunk * T) ||
             p->ol_pts.reserve(sizeof(float4) * px) || p->ol_removed.reserve(px + 1) || p->ol_stats.reserve(sizeof(int) * 2 * (size_t)n * T) ||
             p->ol_offs.reserve(sizeof(int) * (size_t)(n + 1) * T) || p->ol_tab.reserve(sizeof(int) * 2 * (size_t)n) ||
@@ -395,21 +394,13 @@ static int outlier_filter_locked(LsnFusion *p, int k, float max_dist, const void
         LSN_HIP(hipMemsetAsync(p->ol_removed.p, 0, (size_t)p->cap * T, s));
         return 0;
     }
-    // 1. vertex -> pixel (the fusion's keep predicate, arithmetic form)
-    FuseArgs fa;
-    fill_args(p, fa, d_depth, d_depth, const_cast<void *>(d_vertices), p->ol_off.as<int>());
-    fa.thr = nullptr;
-    hipLaunchKernelGGL(ct_index_kernel<0>, dim3(p->tiles_per_tick, T), dim3(kThreads), 0, s, fa, p->ol_counts.as<int>(), p->ol_pix2v.as<int>(),
-                       p->ol_v2pix.as<int>());
-    hipLaunchKernelGGL(scan_kernel, dim3(T), dim3(kScanThreads), 0, s, p->ol_counts.as<int>(), p->tiles_per_tick, fa.frames, n,
-                       p->ol_off.as<int>(), (int *)nullptr);
-    hipLaunchKernelGGL(ct_index_kernel<1>, dim3(p->tiles_per_tick, T), dim3(kThreads), 0, s, fa, p->ol_counts.as<int>(), p->ol_pix2v.as<int>(),
-                       p->ol_v2pix.as<int>());
+    // 1. vertex -> pixel
+    if (cloud_index_locked(p, d_depth, const_cast<void *>(d_vertices), false, s)) return -1;
     OlArgs a;
-    a.frames = fa.frames;
+    a.frames = p->frames.as<FrameDesc>();
     a.offsets = d_offsets;
     a.verts = static_cast<const uint4 *>(d_vertices);
-    a.v2pix = p->ol_v2pix.as<int>();
+    a.v2pix = p->ix_v2pix.as<int>();
     a.bbase = p->ol_tab.as<int>();
     a.bmask = p->ol_tab.as<int>() + n;
     a.key = p->ol_key.as<int>();

@@ -145,6 +145,12 @@ void merge_thread(int iters)
             (void)lsnLastMeshTransferFrame(frame.data(), bound);
         }
         release(m);
+        // the same rig with bcolor_transfer: the flow that keeps the whole cloud in HBM, and the colour transfer's scratch on the plan (its
+        // kernels are no-ops on the double and it only changes colour bytes on a device, so the same mesh is expected)
+        generateMeshFromDepthMaps(small.n, small.depth.data(), small.colours.data(), small.widths.data(), small.heights.data(), small.intr.data(),
+                                  small.wt.data(), &m, true, small.b[0], small.b[1], small.b[2], small.b[3], small.b[4], small.b[5], false);
+        check_mesh(m, small.total(), true, "merge 3x250x121, colour transfer");
+        release(m);
         // the tick as one call: the radial kernels are not emulated, the corrected maps read as zeros -> an empty cloud, through every copy
         // and event of the flow; the caller's arrays are overwritten with the (zero) corrected maps, so they are copies
         std::vector<unsigned char> d2 = rig.depth, c2 = rig.colours;

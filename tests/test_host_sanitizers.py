@@ -43,27 +43,46 @@ def _run(binary, iters, **env):
     return summary[0]
 
 
-@pytest.mark.parametrize("kind", ["asan", "tsan"])
+def _filtered(case):
+    """A parameter that ends in "+filter" runs its case with the outlier filter on ($LSN_OUTLIER_FILTER, which the library reads itself):
+    every merge, single-sensor and tick-as-one-call of the soak then takes the flow that keeps the whole cloud in HBM.  Returns the
+    parameter without the suffix and the environment to add."""
+    value, plus, _ = case.partition("+filter")
+    return value, ({"LSN_OUTLIER_FILTER": "10,0.1"} if plus else {})
+
+
+@pytest.mark.parametrize("kind", ["asan", "tsan", "asan+filter", "tsan+filter"])
 def test_call_mix_from_four_threads(soaks, kind):
-    line = _run(soaks[kind], 3)
+    kind, env = _filtered(kind)
+    line = _run(soaks[kind], 3, **env)
     assert "over 1 device part(s)" in line
 
 
 @pytest.mark.parametrize("kind", ["asan", "tsan"])
-@pytest.mark.parametrize("devices,parts", [("0,1", 2), ("1,0", 2), ("0,1,1", 3), ("1,0,1,0,1,0,1,0", 8)])
+@pytest.mark.parametrize("devices,parts", [("0,1", 2), ("1,0", 2), ("0,1,1", 3), ("1,0,1,0,1,0,1,0", 8), ("0,1+filter", 2)])
 def test_merge_calls_sharded_over_devices(soaks, kind, devices, parts):
     """The sharded flow ($LSN_HOST_DEVICES): one worker thread per device part, counts exchanged through atomics, every part storing into
-    the same pinned block at its base -- the double's two devices listed in any order and more than once."""
-    line = _run(soaks[kind], 3, LSN_HOST_DEVICES=devices)
+    the same pinned block at its base -- the double's two devices listed in any order and more than once.  With the outlier filter on, a
+    mesh call runs on the first device alone while the radial export stays sharded."""
+    devices, env = _filtered(devices)
+    line = _run(soaks[kind], 3, LSN_HOST_DEVICES=devices, **env)
     assert f"over {parts} device part(s)" in line
 
 
-@pytest.mark.parametrize("devices", ["", "0,1,0"])
+@pytest.mark.parametrize("devices", ["", "0,1,0", "+filter", "0,1,0+filter"])
 def test_failed_allocations_leave_nothing_behind(soaks, devices):
     """$LSN_TEST_FAIL_ALLOC=n for a spread of n (first calls, steady state, inside the sharded flow's worker threads): the call that is hit
-    returns an empty mesh, everything after it works, the pool ends empty, and neither sanitizer has anything to say."""
-    env = {"LSN_HOST_DEVICES": devices} if devices else {}
-    for n in (1, 2, 5, 9, 14, 23, 37, 38, 39, 40, 41, 55, 77, 120, 160, 200):
+    returns an empty mesh, everything after it works, the pool ends empty, and neither sanitizer has anything to say.  With the outlier
+    filter on, the masked maps and the stages' scratch are reserved behind everything the plain flow reserves (a two-iteration soak passes
+    ~500 allocations with the filter off and ~800 with it on), so the spread reaches further: a failure there must drain the lane and return
+    the pinned blocks."""
+    devices, env = _filtered(devices)
+    if devices:
+        env["LSN_HOST_DEVICES"] = devices
+    spread = (1, 2, 5, 9, 14, 23, 37, 38, 39, 40, 41, 55, 77, 120, 160, 200)
+    if env.get("LSN_OUTLIER_FILTER"):
+        spread += (300, 450, 505, 600, 750, 800)
+    for n in spread:
         _run(soaks["asan"], 2, LSN_TEST_FAIL_ALLOC=str(n), **env)
     for n in (3, 40, 90):
         _run(soaks["tsan"], 2, LSN_TEST_FAIL_ALLOC=str(n), **env)
