@@ -234,7 +234,7 @@ static int cloud_index_locked(LsnFusion *p, const void *d_depth, void *d_vertice
     }
     // the fusion's keep predicate, arithmetic form
     FuseArgs fa;
-    fill_args(p, fa, d_depth, d_depth, d_vertices, p->ix_off.as<int>());
+    fill_args(p, fa, d_depth, d_depth, d_vertices, p->ix_off.as<int>(), false);
     fa.thr = nullptr;
     hipLaunchKernelGGL(ct_index_kernel<0>, dim3(p->tiles_per_tick, T), dim3(kThreads), 0, s, fa, p->ix_counts.as<int>(), p->ix_pix2v.as<int>(),
                        p->ix_v2pix.as<int>());

@@ -320,16 +320,14 @@ int lsn::pack_survivors(LsnFusion *p, const void *d_depth, const void *d_colors,
     std::lock_guard<std::mutex> g(p->mu);
     LSN_HIP(hipSetDevice(p->device));
     hipStream_t s = lsn::as_stream(stream);
-    const bool vec = p->vec_ok && ((uintptr_t)d_depth & 15) == 0 && ((uintptr_t)d_colors & 7) == 0 && (p->tick_depth_elems % 8) == 0;
-    if (!vec) {
+    if (!wide_loads(p, d_depth, d_colors)) {
         lsn::set_error("lsnFusionPackSurvivors: needs frame widths that are multiples of 8 and 16-byte aligned buffers (exchange vertices instead)");
         return -1;
     }
     if (ensure_thresholds(p, s)) return -1;
     FuseArgs a;
-    fill_args(p, a, d_depth, d_colors, nullptr, d_offsets);
-    launch_count(p, true, s, a);
-    hipLaunchKernelGGL(scan_kernel, dim3((unsigned)p->n_ticks), dim3(kScanThreads), 0, s, a.tile_counts, a.tiles_per_tick, a.frames, a.n_frames, a.offsets, nullptr);
+    fill_args(p, a, d_depth, d_colors, nullptr, d_offsets, false);
+    count_and_scan(p, true, s, a);
     PackArgs pk;
     pk.mask = static_cast<unsigned char *>(d_mask);
     pk.depth_c = static_cast<unsigned short *>(d_depth_c);
@@ -429,7 +427,7 @@ int lsn::reconstruct(LsnFusion *all, int n_shards, int maps_per_shard, const voi
     }
     LSN_HIP(hipSetDevice(all->device));
     FuseArgs a;
-    fill_args(all, a, nullptr, nullptr, d_merged, d_merged_offsets);
+    fill_args(all, a, nullptr, nullptr, d_merged, d_merged_offsets, false);
     a.thr = nullptr;
     ReconArgs r;
     r.mask = static_cast<const unsigned char *>(d_masks);
@@ -951,7 +949,7 @@ static int shard_step(LsnShard *sh, const void *d_depth_local, const void *d_col
     const size_t T = (size_t)sh->n_ticks, W = (size_t)sh->world, cap = (size_t)sh->cap_loc;
     const size_t off_ints = T * (sh->mpr + 1);
     if (sh->vertex_mode) {
-        if (lsn::run_hooked(sh->local, d_depth_local, d_colors_local, sh->v_local.p, sh->offsets.as<int>(), s, nullptr)) return -1;
+        if (lsn::run_vertices(sh->local, d_depth_local, d_colors_local, sh->v_local.p, sh->offsets.as<int>(), s)) return -1;
         LSN_NCCL(r->AllGather(sh->offsets.p, sh->g_off.p, off_ints, ncclInt32, sh->comm, s));
         long long slab = (long long)cap;
         if (!sh->padded) {

@@ -236,7 +236,7 @@ constexpr unsigned long long kFlagAggregate = 1ull << 62;
 constexpr unsigned long long kFlagPrefix = 2ull << 62;
 constexpr int kSpinLimit = 1 << 20;
 
-// Mode 2 (single pass, one look-back per TILE) tags its words instead of clearing them: bits 63..34 = the launch's epoch,
+// The single pass (fuse_kernel<4>: one look-back per TILE; a plan in mode 2, one-tick plans, run_frames) tags its words instead of clearing them: bits 63..34 = the launch's epoch,
 // 33..32 = flag, low 32 bits = value; a word of another epoch reads as "empty".
 constexpr int kEpochShift = 34;
 constexpr unsigned long long kTileAggregate = 1ull << 32, kTilePrefix = 2ull << 32;
@@ -300,9 +300,11 @@ __device__ __forceinline__ int tile_lookback(const FuseArgs &a, int tick, int ti
 
 // ---- mode 0: count kernel, scan kernel, write kernel ------------------------------------------------------------
 
-// MODE 0 = count only (writes tile_counts), 1 = write with offsets from tile_counts (exclusive prefixes by then),
-// 3 = streamed: mode 1 for this batch AND the count of the same tile of the NEXT batch (depth_next) in one workgroup --
-// the count pass is VALU-bound, the write pass HBM-bound, and inside one kernel they share every CU all the time.
+// MODE is the kernel pass (fusion_shared.hpp: kPassCount / kPassWrite / kPassWriteCountNext / kPassSingle), not the plan's mode:
+// 0 = count only (writes tile_counts), 1 = write with offsets from tile_counts (exclusive prefixes by then),
+// 3 = streamed: pass 1 for this batch AND the count of the same tile of the NEXT batch (depth_next) in one workgroup --
+// the count pass is VALU-bound, the write pass HBM-bound, and inside one kernel they share every CU all the time;
+// 4 = single pass: the tile resolves its offset by look-back (tile_lookback) -- what a plan in mode 2 and the one-tick forms launch.
 // LAZY (write pass only): the colours are loaded after the keep predicates are known, by the lanes that kept a pixel --
 // spatially coherent frames (real scenes: background beyond the crop box, invalid regions) then never fetch the colour
 // lines of rejected areas; the price is that the colour load no longer flies together with the depth load.
@@ -711,7 +713,7 @@ static LsnFusion * lsnFusionCreate_impl(int device, int n_ticks, int n_maps, con
     p->tick_depth_elems = doff;
     p->tick_rgb_bytes = coff;
     p->tiles_per_tick = tiles;
-    // one-tick plans of up to 2048 tiles take the single pass (run_locked); $LSN_ONE_TICK_SINGLE_PASS=0 / 1 forces the three launches / the single pass
+    // one-tick plans of up to 2048 tiles take the single pass (run_form); $LSN_ONE_TICK_SINGLE_PASS=0 / 1 forces the three launches / the single pass
     p->one_tick_single_pass = n_ticks == 1 && tiles <= 2048;
     if (const char *env = getenv("LSN_ONE_TICK_SINGLE_PASS")) p->one_tick_single_pass = atoi(env) != 0;
     p->tile_start.push_back(tiles);
@@ -853,7 +855,7 @@ extern "C" int lsnFusionSetParams(LsnFusion *p, const float *intr, const float *
 
 static int lsnFusionSetMode_impl(LsnFusion *p, int mode)
 {
-    if (!p || mode < 0 || mode > 2) {
+    if (!p || mode < lsn::kPlanThreeLaunches || mode > lsn::kPlanSinglePass) {
         lsn::set_error("lsnFusionSetMode: mode must be 0 (count/scan/write launches), 1 (single launch, runs + look-back) or 2 (single pass, look-back per tile)");
         return -1;
     }
@@ -929,7 +931,7 @@ static int lsnFusionKernelStats_impl(LsnFusion *p, double *avg_ms, long long *la
     if (avg_ms) *avg_ms = p->launches ? p->acc_ms / (double)p->launches : 0.0;
     if (launches) *launches = p->launches;
     if (name && name_len > 0)
-        snprintf(name, (size_t)name_len, "%s", p->timed_kernel ? p->timed_kernel : (p->mode == 0 ? "fuse_kernel<1>" : p->mode == 2 ? "fuse_kernel<4>" : "run_kernel"));
+        snprintf(name, (size_t)name_len, "%s", p->timed_kernel ? p->timed_kernel : (p->mode == lsn::kPlanThreeLaunches ? "fuse_kernel<1>" : p->mode == lsn::kPlanSinglePass ? "fuse_kernel<4>" : "run_kernel"));
     if (reset) {
         p->acc_ms = 0;
         p->launches = 0;
@@ -942,8 +944,8 @@ extern "C" int lsnFusionKernelStats(LsnFusion *p, double *avg_ms, long long *lau
     return lsn::guarded<int>("lsnFusionKernelStats", static_cast<int>(-1), [&]() { return lsnFusionKernelStats_impl(p, avg_ms, launches, name, name_len, reset); });
 }
 
-// Kernel arguments of one call (everything but the per-mode scratch selection).
-void lsn::fill_args(LsnFusion *p, FuseArgs &a, const void *d_depth, const void *d_colors, void *d_vertices, int *d_offsets)
+// Kernel arguments of one call (everything but the scratch selection of the launch form).
+void lsn::fill_args(LsnFusion *p, FuseArgs &a, const void *d_depth, const void *d_colors, void *d_vertices, int *d_offsets, bool with_pixmap)
 {
     a.epoch = 0;
     a.chunk = 0;
@@ -960,13 +962,13 @@ void lsn::fill_args(LsnFusion *p, FuseArgs &a, const void *d_depth, const void *
     a.error_flag = p->misc.as<int>();
     a.ticket = p->misc.as<unsigned int>() + 32;
     a.offsets = d_offsets;
-    a.pixmap = p->want_pixmap ? p->pixmap.as<int>() : nullptr;
-    a.pm_first = p->want_pixmap ? p->pm_first.as<int>() : nullptr;
-    a.pm_mask = p->want_pixmap ? p->pm_mask.as<unsigned char>() : nullptr;
+    a.pixmap = with_pixmap ? p->pixmap.as<int>() : nullptr;
+    a.pm_first = with_pixmap ? p->pm_first.as<int>() : nullptr;
+    a.pm_mask = with_pixmap ? p->pm_mask.as<unsigned char>() : nullptr;
     a.n_frames = p->n_maps;
     a.tiles_per_tick = p->tiles_per_tick;
     a.n_ticks = p->n_ticks;
-    // mode 1: runs of consecutive tiles.  Long runs amortise the look-back and the second (cached) depth read, short
+    // run_kernel: runs of consecutive tiles.  Long runs amortise the look-back and the second (cached) depth read, short
     // runs balance the load: aim at >= ~6 runs per workgroup slot (7 per CU x 256 CUs), at most 8 tiles per run.
     {
         const long long total = (long long)p->tiles_per_tick * p->n_ticks;
@@ -1017,26 +1019,48 @@ int lsn::ensure_thresholds(LsnFusion *p, hipStream_t s)
     return 0;
 }
 
-// The count pass of one batch into a.tile_counts: from the thresholds when they exist, else arithmetically.
-void lsn::launch_count(LsnFusion *p, bool vec, hipStream_t s, const FuseArgs &a)
+// The one place a fuse_kernel launch is spelled.  (pass, wide loads, lazy colours, pinned output) -> instantiation; only the
+// combinations a caller can ask for exist in the code object: kPassCount and kPassWriteCountNext have neither a LAZY nor a HOST form,
+// kPassSingle no HOST form (it has the run-time a.host_out), and the HOST form of kPassWrite is always LAZY.
+template <int MODE, bool LAZY, bool HOST>
+static void launch_fuse_as(bool vec, int grid, hipStream_t s, const FuseArgs &a)
+{
+    if (vec) hipLaunchKernelGGL((fuse_kernel<MODE, true, LAZY, HOST>), dim3(grid), dim3(kThreads), 0, s, a);
+    else     hipLaunchKernelGGL((fuse_kernel<MODE, false, LAZY, HOST>), dim3(grid), dim3(kThreads), 0, s, a);
+}
+
+template <int MODE>
+static void launch_fuse(bool vec, int grid, hipStream_t s, const FuseArgs &a, bool lazy_rgb = false, bool host_out = false)
+{
+    if constexpr (MODE == lsn::kPassWrite) {
+        if (host_out) return launch_fuse_as<MODE, true, true>(vec, grid, s, a);
+    }
+    if constexpr (MODE == lsn::kPassWrite || MODE == lsn::kPassSingle) {
+        if (lazy_rgb) return launch_fuse_as<MODE, true, false>(vec, grid, s, a);
+    }
+    launch_fuse_as<MODE, false, false>(vec, grid, s, a);
+}
+
+template <int kTickGroup>
+static void launch_count_thr(bool vec, int grid, hipStream_t s, const FuseArgs &a)
+{
+    if (vec) hipLaunchKernelGGL((count_thr_kernel<true, kTickGroup>), dim3(grid), dim3(kThreads), 0, s, a);
+    else     hipLaunchKernelGGL((count_thr_kernel<false, kTickGroup>), dim3(grid), dim3(kThreads), 0, s, a);
+}
+
+// The count pass of one batch into a.tile_counts (from the thresholds when they exist, else arithmetically), then the scan.
+void lsn::count_and_scan(LsnFusion *p, bool vec, hipStream_t s, const FuseArgs &a, int *mirror)
 {
     if (a.thr) {
         const int G = a.n_ticks >= 8 ? 8 : (a.n_ticks >= 4 ? 4 : 1);
         const int grid = p->tiles_per_tick * ((a.n_ticks + G - 1) / G);
-#define LSN_COUNT_THR(GG)                                                                                         \
-    do {                                                                                                          \
-        if (vec) hipLaunchKernelGGL((count_thr_kernel<true, GG>), dim3(grid), dim3(kThreads), 0, s, a);           \
-        else     hipLaunchKernelGGL((count_thr_kernel<false, GG>), dim3(grid), dim3(kThreads), 0, s, a);          \
-    } while (0)
-        if (G == 8) LSN_COUNT_THR(8);
-        else if (G == 4) LSN_COUNT_THR(4);
-        else LSN_COUNT_THR(1);
-#undef LSN_COUNT_THR
+        if (G == 8) launch_count_thr<8>(vec, grid, s, a);
+        else if (G == 4) launch_count_thr<4>(vec, grid, s, a);
+        else launch_count_thr<1>(vec, grid, s, a);
     } else {
-        const int grid = p->tiles_per_tick * a.n_ticks;
-        if (vec) hipLaunchKernelGGL((fuse_kernel<0, true>), dim3(grid), dim3(kThreads), 0, s, a);
-        else     hipLaunchKernelGGL((fuse_kernel<0, false>), dim3(grid), dim3(kThreads), 0, s, a);
+        launch_fuse<lsn::kPassCount>(vec, p->tiles_per_tick * a.n_ticks, s, a);
     }
+    hipLaunchKernelGGL(scan_kernel, dim3((unsigned)a.n_ticks), dim3(kScanThreads), 0, s, a.tile_counts, a.tiles_per_tick, a.frames, a.n_frames, a.offsets, mirror);
 }
 
 // Next HIP-event pair of the dominant-kernel timer (profiling on).
@@ -1058,28 +1082,11 @@ int lsn::next_event_pair(LsnFusion *p, hipEvent_t &e0, hipEvent_t &e1)
     return 0;
 }
 
-template <int MODE>
-static void launch(bool vec, int grid, hipStream_t s, const FuseArgs &a, bool lazy_rgb = false)
-{
-    if ((MODE == 1 || MODE == 4) && lazy_rgb) {
-        if (vec) hipLaunchKernelGGL((fuse_kernel<MODE, true, true>), dim3(grid), dim3(kThreads), 0, s, a);
-        else     hipLaunchKernelGGL((fuse_kernel<MODE, false, true>), dim3(grid), dim3(kThreads), 0, s, a);
-        return;
-    }
-    if (vec) hipLaunchKernelGGL((fuse_kernel<MODE, true>), dim3(grid), dim3(kThreads), 0, s, a);
-    else     hipLaunchKernelGGL((fuse_kernel<MODE, false>), dim3(grid), dim3(kThreads), 0, s, a);
-}
-
 static int lsnFusionRun_impl(LsnFusion *p, const void *d_depth, const void *d_colors, void *d_vertices, int *d_offsets,
                             void *stream)
 {
     lsn::clear_error();
-    if (!p || !d_depth || !d_colors || !d_vertices || !d_offsets) {
-        lsn::set_error("lsnFusionRun: null argument");
-        return -1;
-    }
-    std::lock_guard<std::mutex> g(p->mu);
-    return lsn::run_locked(p, d_depth, d_colors, d_vertices, d_offsets, lsn::as_stream(stream), false, nullptr);
+    return lsn::run_vertices(p, d_depth, d_colors, d_vertices, d_offsets, lsn::as_stream(stream));
 }
 
 extern "C" int lsnFusionRun(LsnFusion *p, const void *d_depth, const void *d_colors, void *d_vertices, int *d_offsets,
@@ -1088,18 +1095,116 @@ extern "C" int lsnFusionRun(LsnFusion *p, const void *d_depth, const void *d_col
     return lsn::guarded<int>("lsnFusionRun", static_cast<int>(-1), [&]() { return lsnFusionRun_impl(p, d_depth, d_colors, d_vertices, d_offsets, stream); });
 }
 
-int lsn::run_hooked(LsnFusion *p, const void *d_depth, const void *d_colors, void *d_vertices, int *d_offsets, hipStream_t s, const RunHooks *hooks)
+int lsn::run_vertices(LsnFusion *p, const void *d_depth, const void *d_colors, void *d_vertices, int *d_offsets, hipStream_t s)
 {
     if (!p || !d_depth || !d_colors || !d_vertices || !d_offsets) {
         lsn::set_error("lsnFusionRun: null argument");
         return -1;
     }
     std::lock_guard<std::mutex> g(p->mu);
-    return lsn::run_locked(p, d_depth, d_colors, d_vertices, d_offsets, s, false, hooks);
+    return lsn::run_locked(p, d_depth, d_colors, d_vertices, d_offsets, s, false);
 }
 
-int lsn::run_locked(LsnFusion *p, const void *d_depth, const void *d_colors, void *d_vertices, int *d_offsets, hipStream_t s, bool with_pixmap,
-                    const RunHooks *hooks)
+// A single-pass launch tags its look-back words with an epoch (30 bits) instead of clearing them; they are cleared when it wraps.
+static int next_epoch(LsnFusion *p, hipStream_t s)
+{
+    if (p->epoch == 0 || p->epoch >= (1u << 30) - 1) {
+        LSN_HIP(hipMemsetAsync(p->tile_state.p, 0, sizeof(unsigned long long) * (size_t)p->tiles_per_tick * p->n_ticks, s));
+        p->epoch = 0;
+    }
+    ++p->epoch;
+    return 0;
+}
+
+// ---- the four launch forms of a whole-plan run (run_locked); e0 / e1: the event pair around the dominant kernel, or null --------------
+
+// count -> scan -> write on the caller's stream
+static int run_three_launches(LsnFusion *p, FuseArgs &a, bool vec, hipStream_t s, hipEvent_t e0, hipEvent_t e1)
+{
+    count_and_scan(p, vec, s, a);
+    if (e0) LSN_HIP(hipEventRecord(e0, s));
+    a.chunk = 0;   // tick-major block order (walking the ticks fastest was measured slower: DESIGN.md section 4, mode 2)
+    launch_fuse<lsn::kPassWrite>(vec, p->tiles_per_tick * p->n_ticks, s, a, p->lazy_rgb);
+    if (e1) LSN_HIP(hipEventRecord(e1, s));
+    return 0;
+}
+
+// Count + scan of THIS call go to the side stream: they only read the inputs (promised resident by lsnFusionSetPipelined) and write
+// this call's half of the double-buffered scratch, so they overlap with the previous call's write kernel, which is still running on
+// the caller's stream (a VALU-bound kernel beside an HBM-bound one).  The caller's stream then waits for them and runs the write kernel.
+static int run_pipelined(LsnFusion *p, FuseArgs &a, bool vec, hipStream_t s, hipEvent_t e0, hipEvent_t e1)
+{
+    const int b = (int)(p->calls & 1);
+    const size_t off_elems = (size_t)p->n_ticks * (p->n_maps + 1);
+    int *d_offsets = a.offsets, *off_int = p->offs_int.as<int>() + b * off_elems;
+    a.tile_counts = b ? p->tile_counts_b.as<int>() : p->tile_counts.as<int>();
+    if (p->calls >= 2) LSN_HIP(hipStreamWaitEvent(p->side, p->ev_written[b], 0));  // the write that last read this half
+    a.offsets = off_int;
+    count_and_scan(p, vec, p->side, a);
+    a.offsets = d_offsets;
+    LSN_HIP(hipEventRecord(p->ev_counted, p->side));
+    LSN_HIP(hipStreamWaitEvent(s, p->ev_counted, 0));
+    LSN_HIP(hipMemcpyAsync(d_offsets, off_int, sizeof(int) * off_elems, hipMemcpyDeviceToDevice, s));
+    if (e0) LSN_HIP(hipEventRecord(e0, s));
+    launch_fuse<lsn::kPassWrite>(vec, p->tiles_per_tick * p->n_ticks, s, a);
+    if (e1) LSN_HIP(hipEventRecord(e1, s));
+    LSN_HIP(hipEventRecord(p->ev_written[b], s));
+    p->calls++;
+    return 0;
+}
+
+static int run_single_pass(LsnFusion *p, FuseArgs &a, bool vec, hipStream_t s, hipEvent_t e0, hipEvent_t e1)
+{
+    if (next_epoch(p, s)) return -1;
+    a.epoch = p->epoch;
+    // block order: chunks of 16 consecutive tiles, every tick's chunk before the next chunk -- the ~2000 resident workgroups
+    // then belong to as many look-back chains as there are ticks (measured, 64 ticks x 848 tiles: tick-major 0.54 ms, ticks
+    // fastest 0.40, chunks of 4 / 16 / 64 tiles 0.335 / 0.328 / 0.41)
+    constexpr int kFuseChunk = 16;
+    a.chunk = kFuseChunk;
+    if (e0) LSN_HIP(hipEventRecord(e0, s));
+    launch_fuse<lsn::kPassSingle>(vec, p->tiles_per_tick * p->n_ticks, s, a, p->lazy_rgb);
+    if (e1) LSN_HIP(hipEventRecord(e1, s));
+    return 0;
+}
+
+// one launch of run_kernel: a look-back per run of tiles
+static int run_lookback_runs(LsnFusion *p, FuseArgs &a, bool vec, hipStream_t s, hipEvent_t e0, hipEvent_t e1)
+{
+    LSN_HIP(hipMemsetAsync(p->tile_state.p, 0, sizeof(unsigned long long) * (size_t)p->tiles_per_tick * p->n_ticks, s));
+    LSN_HIP(hipMemsetAsync(p->misc.as<char>() + 128, 0, 128 * (size_t)p->n_ticks, s));  // tickets; the error flag is sticky
+    if (e0) LSN_HIP(hipEventRecord(e0, s));
+    const int rgrid = a.runs_per_tick * p->n_ticks;
+    if (vec) hipLaunchKernelGGL((run_kernel<true>), dim3(rgrid), dim3(kThreads), 0, s, a);
+    else     hipLaunchKernelGGL((run_kernel<false>), dim3(rgrid), dim3(kThreads), 0, s, a);
+    if (e1) LSN_HIP(hipEventRecord(e1, s));
+    return 0;
+}
+
+// Which form a whole-plan run takes.  The pixel -> vertex map (lsnFusionRunMesh) is filled by the write pass of the three launches or,
+// for a one-tick plan, by the single pass; neither the look-back per run nor the pipelined form fills it.
+//
+// One-tick plans (what a live device-resident caller holds: one merge per call): count -> scan -> write is three dependent launches
+// around ~5 us of work -- 13.4-15.8 us per call whatever the rig, the launches' own latency -- the single pass one launch whose
+// look-back chain grows with the tick's tiles: 1 x 512x424 (106 tiles) 7.6-8.0 us, 8 x 512x424 (848) 13.5-13.6, 2 x 1024x1024 (2048)
+// 14.2, 16 x 1024x1024 (16384) 82 against 55 (tools/one_tick_driver.py; measured WITHOUT the kernel-timing events, whose two
+// records per call had hidden the difference: 21.4 against 20.0-21.6, profiles/r05_ab_lookback.txt).  So a one-tick plan of up to
+// 2048 tiles takes the single pass (lsnFusionCreate), a bigger one the three launches; $LSN_ONE_TICK_SINGLE_PASS=0 / 1 forces either.
+enum class RunForm { ThreeLaunches, Pipelined, SinglePass, LookbackRuns };
+static RunForm run_form(const LsnFusion *p, bool with_pixmap)
+{
+    switch (p->mode) {
+    case lsn::kPlanThreeLaunches:
+        if (p->pipelined) return with_pixmap ? RunForm::ThreeLaunches : RunForm::Pipelined;
+        return p->n_ticks == 1 && p->one_tick_single_pass ? RunForm::SinglePass : RunForm::ThreeLaunches;
+    case lsn::kPlanLookbackRuns:
+        return with_pixmap ? RunForm::ThreeLaunches : RunForm::LookbackRuns;
+    default:   // kPlanSinglePass
+        return with_pixmap ? RunForm::ThreeLaunches : RunForm::SinglePass;
+    }
+}
+
+int lsn::run_locked(LsnFusion *p, const void *d_depth, const void *d_colors, void *d_vertices, int *d_offsets, hipStream_t s, bool with_pixmap)
 {
     if (!p->params_set) {
         lsn::set_error("lsnFusionRun: lsnFusionSetParams has not been called");
@@ -1110,100 +1215,30 @@ int lsn::run_locked(LsnFusion *p, const void *d_depth, const void *d_colors, voi
         return -1;
     }
     LSN_HIP(hipSetDevice(p->device));
-    struct PixmapScope {   // a.pixmap follows p->want_pixmap (fill_args); never left set behind an early return
-        LsnFusion *p;
-        PixmapScope(LsnFusion *q, bool on) : p(q) { p->want_pixmap = on; }
-        ~PixmapScope() { p->want_pixmap = false; }
-    } scope(p, with_pixmap);
-
     if (ensure_thresholds(p, s)) return -1;
     FuseArgs a;
-    fill_args(p, a, d_depth, d_colors, d_vertices, d_offsets);
-
-    // the wide-load path also needs 16-B aligned buffers and every tick to start 16-B / 8-B aligned
-    const bool vec = p->vec_ok && ((uintptr_t)d_depth & 15) == 0 && ((uintptr_t)d_colors & 7) == 0 &&
-                     (p->tick_depth_elems % 8) == 0;
-    if (with_pixmap) p->pixmap_compact = vec;   // the triangulation reads the form this run writes
-    const int grid = p->tiles_per_tick * p->n_ticks;
-    const size_t off_bytes = sizeof(int) * (size_t)p->n_ticks * (p->n_maps + 1);
+    fill_args(p, a, d_depth, d_colors, d_vertices, d_offsets, with_pixmap);
+    const bool vec = wide_loads(p, d_depth, d_colors);
 
     hipEvent_t e0 = nullptr, e1 = nullptr;
     if (timed_launch(p) && next_event_pair(p, e0, e1)) return -1;
 
-    // One-tick plans (what a live device-resident caller holds: one merge per call): count -> scan -> write is three dependent launches
-    // around ~5 us of work -- 13.4-15.8 us per call whatever the rig, the launches' own latency -- the single pass one launch whose
-    // look-back chain grows with the tick's tiles: 1 x 512x424 (106 tiles) 7.6-8.0 us, 8 x 512x424 (848) 13.5-13.6, 2 x 1024x1024 (2048)
-    // 14.2, 16 x 1024x1024 (16384) 82 against 55 (tools/one_tick_driver.py; measured WITHOUT the kernel-timing events, whose two
-    // records per call had hidden the difference: 21.4 against 20.0-21.6, profiles/r05_ab_lookback.txt).  So a one-tick plan of up to
-    // 2048 tiles takes the single pass (lsnFusionCreate), a bigger one the three launches; $LSN_ONE_TICK_SINGLE_PASS=0 / 1 forces either.
-    const bool single_pass = (p->mode == 2 && !with_pixmap && !hooks) || (p->mode == 0 && p->n_ticks == 1 && !hooks && !p->pipelined && p->one_tick_single_pass);
-    if (p->mode == 0) p->timed_kernel = single_pass ? "fuse_kernel<4>" : nullptr;   // what the event pair below brackets
-
-    if (p->pipelined && p->mode == 0 && !with_pixmap && !hooks) {
-        // Count + scan of THIS call go to the side stream: they only read the inputs (promised resident by
-        // lsnFusionSetPipelined) and write this call's half of the double-buffered scratch, so they overlap with the
-        // previous call's write kernel, which is still running on the caller's stream (a VALU-bound kernel beside an
-        // HBM-bound one).  The caller's stream then waits for them and runs the write kernel.
-        const int b = (int)(p->calls & 1);
-        const size_t off_elems = (size_t)p->n_ticks * (p->n_maps + 1);
-        a.tile_counts = b ? p->tile_counts_b.as<int>() : p->tile_counts.as<int>();
-        int *off_int = p->offs_int.as<int>() + b * off_elems;
-        if (p->calls >= 2) LSN_HIP(hipStreamWaitEvent(p->side, p->ev_written[b], 0));  // the write that last read this half
-        FuseArgs ac = a;
-        ac.offsets = off_int;
-        launch_count(p, vec, p->side, ac);
-        hipLaunchKernelGGL(scan_kernel, dim3((unsigned)p->n_ticks), dim3(kScanThreads), 0, p->side, ac.tile_counts, ac.tiles_per_tick, ac.frames,
-                           ac.n_frames, off_int, nullptr);
-        LSN_HIP(hipEventRecord(p->ev_counted, p->side));
-        LSN_HIP(hipStreamWaitEvent(s, p->ev_counted, 0));
-        LSN_HIP(hipMemcpyAsync(d_offsets, off_int, sizeof(int) * off_elems, hipMemcpyDeviceToDevice, s));
-        if (e0) LSN_HIP(hipEventRecord(e0, s));
-        launch<1>(vec, grid, s, a);
-        if (e1) LSN_HIP(hipEventRecord(e1, s));
-        LSN_HIP(hipEventRecord(p->ev_written[b], s));
-        p->calls++;
-    } else if (!single_pass && (p->mode == 0 || with_pixmap || hooks)) {
-        launch_count(p, vec, s, a);
-        hipLaunchKernelGGL(scan_kernel, dim3((unsigned)p->n_ticks), dim3(kScanThreads), 0, s, a.tile_counts, a.tiles_per_tick, a.frames, a.n_frames,
-                           a.offsets, nullptr);
-        if (hooks && hooks->h_offsets) LSN_HIP(hipMemcpyAsync(hooks->h_offsets, d_offsets, off_bytes, hipMemcpyDeviceToHost, s));
-        if (hooks && hooks->counted) LSN_HIP(hipEventRecord(hooks->counted, s));
-        if (hooks && hooks->colours_ready) LSN_HIP(hipStreamWaitEvent(s, hooks->colours_ready, 0));
-        if (e0) LSN_HIP(hipEventRecord(e0, s));
-        a.chunk = 0;   // tick-major block order (walking the ticks fastest was measured slower: DESIGN.md section 4, mode 2)
-        launch<1>(vec, grid, s, a, p->lazy_rgb);
-        if (e1) LSN_HIP(hipEventRecord(e1, s));
-        if (hooks && hooks->written) LSN_HIP(hipEventRecord(hooks->written, s));
-    } else if (single_pass) {
-        // single pass: per-tile look-back words tagged with the launch's epoch (30 bits; the words are cleared when it wraps)
-        if (p->epoch == 0 || p->epoch >= (1u << 30) - 1) {
-            LSN_HIP(hipMemsetAsync(p->tile_state.p, 0, sizeof(unsigned long long) * (size_t)grid, s));
-            p->epoch = 0;
-        }
-        a.epoch = ++p->epoch;
-        // block order: chunks of 16 consecutive tiles, every tick's chunk before the next chunk -- the ~2000 resident workgroups
-        // then belong to as many look-back chains as there are ticks (measured, 64 ticks x 848 tiles: tick-major 0.54 ms, ticks
-        // fastest 0.40, chunks of 4 / 16 / 64 tiles 0.335 / 0.328 / 0.41)
-        constexpr int kFuseChunk = 16;
-        a.chunk = kFuseChunk;
-        if (e0) LSN_HIP(hipEventRecord(e0, s));
-        launch<4>(vec, grid, s, a, p->lazy_rgb);
-        if (e1) LSN_HIP(hipEventRecord(e1, s));
-    } else {
-        LSN_HIP(hipMemsetAsync(p->tile_state.p, 0, sizeof(unsigned long long) * (size_t)grid, s));
-        LSN_HIP(hipMemsetAsync(p->misc.as<char>() + 128, 0, 128 * (size_t)p->n_ticks, s));  // tickets; the error flag is sticky
-        if (e0) LSN_HIP(hipEventRecord(e0, s));
-        const int rgrid = a.runs_per_tick * p->n_ticks;
-        if (vec) hipLaunchKernelGGL((run_kernel<true>), dim3(rgrid), dim3(kThreads), 0, s, a);
-        else     hipLaunchKernelGGL((run_kernel<false>), dim3(rgrid), dim3(kThreads), 0, s, a);
-        if (e1) LSN_HIP(hipEventRecord(e1, s));
+    const RunForm form = run_form(p, with_pixmap);
+    if (p->mode == lsn::kPlanThreeLaunches) p->timed_kernel = form == RunForm::SinglePass ? "fuse_kernel<4>" : nullptr;   // what the event pair brackets
+    int rc = -1;
+    switch (form) {
+    case RunForm::ThreeLaunches: rc = run_three_launches(p, a, vec, s, e0, e1); break;
+    case RunForm::Pipelined:     rc = run_pipelined(p, a, vec, s, e0, e1); break;
+    case RunForm::SinglePass:    rc = run_single_pass(p, a, vec, s, e0, e1); break;
+    case RunForm::LookbackRuns:  rc = run_lookback_runs(p, a, vec, s, e0, e1); break;
     }
+    if (rc) return -1;
     LSN_HIP(hipGetLastError());
     return 0;
 }
 
 // A one-tick plan fused group by group: frames [f0, f1) in ONE launch, single pass (a tile computes its vertices once, publishes
-// its count and resolves its offset by look-back over the tiles before it -- fuse_kernel<4>, the mode-2 kernel), so the groups of
+// its count and resolves its offset by look-back over the tiles before it -- fuse_kernel<kPassSingle>), so the groups of
 // a tick can be launched one after the other as their frames arrive, each continuing where the previous one stopped: the tiles of
 // a later launch find the inclusive prefixes of the earlier launches' tiles in place (same epoch).  This is the form the host
 // exports use (host_flows.hip): their output block is pinned host memory, the launch is bound by the PCIe link, and any further kernel
@@ -1223,34 +1258,18 @@ int lsn::run_frames(LsnFusion *p, const void *d_depth, const void *d_colors, voi
     }
     std::lock_guard<std::mutex> g(p->mu);
     LSN_HIP(hipSetDevice(p->device));
-    const bool vec = p->vec_ok && ((uintptr_t)d_depth & 15) == 0 && ((uintptr_t)d_colors & 7) == 0 && (p->tick_depth_elems % 8) == 0;
-    if (with_pixmap) {
-        if (vec ? (p->pm_first.reserve(sizeof(int) * ((size_t)p->cap / 8 + 2)) || p->pm_mask.reserve((size_t)p->cap / 8 + 2))
-                : p->pixmap.reserve(sizeof(int) * (size_t)p->cap))
-            return -1;
-        p->pixmap_compact = vec;
-    }
-    struct PixmapScope {
-        LsnFusion *p;
-        PixmapScope(LsnFusion *q, bool on) : p(q) { p->want_pixmap = on; }
-        ~PixmapScope() { p->want_pixmap = false; }
-    } scope(p, with_pixmap);
+    const bool vec = wide_loads(p, d_depth, d_colors);
+    if (with_pixmap && reserve_pixmap(p, vec)) return -1;
     FuseArgs a;
-    fill_args(p, a, d_depth, d_colors, d_vertices, d_offsets);
-    if (first_of_tick) {
-        if (p->epoch == 0 || p->epoch >= (1u << 30) - 1) {
-            LSN_HIP(hipMemsetAsync(p->tile_state.p, 0, sizeof(unsigned long long) * (size_t)p->tiles_per_tick, s));
-            p->epoch = 0;
-        }
-        ++p->epoch;
-    }
+    fill_args(p, a, d_depth, d_colors, d_vertices, d_offsets, with_pixmap);
+    if (first_of_tick && next_epoch(p, s)) return -1;
     a.epoch = p->epoch;
     a.chunk = 0;
     a.tile0 = p->tile_start[f0];
     a.offsets_mirror = offsets_mirror;
     a.group_end_mirror = group_end_mirror;
     a.host_out = host_out ? 1 : 0;
-    launch<4>(vec, p->tile_start[f1] - p->tile_start[f0], s, a, p->lazy_rgb);
+    launch_fuse<lsn::kPassSingle>(vec, p->tile_start[f1] - p->tile_start[f0], s, a, p->lazy_rgb);
     LSN_HIP(hipGetLastError());
     return 0;
 }
@@ -1276,10 +1295,8 @@ int lsn::run_count(LsnFusion *p, const void *d_depth, const void *d_colors, int 
     LSN_HIP(hipSetDevice(p->device));
     if (ensure_thresholds(p, s)) return -1;
     FuseArgs a;
-    fill_args(p, a, d_depth, d_colors, nullptr, d_offsets);
-    const bool vec = p->vec_ok && ((uintptr_t)d_depth & 15) == 0 && ((uintptr_t)d_colors & 7) == 0 && (p->tick_depth_elems % 8) == 0;
-    launch_count(p, vec, s, a);
-    hipLaunchKernelGGL(scan_kernel, dim3(1), dim3(kScanThreads), 0, s, a.tile_counts, a.tiles_per_tick, a.frames, a.n_frames, a.offsets, offsets_mirror);
+    fill_args(p, a, d_depth, d_colors, nullptr, d_offsets, false);
+    count_and_scan(p, wide_loads(p, d_depth, d_colors), s, a, offsets_mirror);
     LSN_HIP(hipGetLastError());
     if (counted) LSN_HIP(hipEventRecord(counted, s));
     return 0;
@@ -1293,27 +1310,11 @@ int lsn::run_write(LsnFusion *p, const void *d_depth, const void *d_colors, void
     }
     std::lock_guard<std::mutex> g(p->mu);
     LSN_HIP(hipSetDevice(p->device));
-    const bool vec = p->vec_ok && ((uintptr_t)d_depth & 15) == 0 && ((uintptr_t)d_colors & 7) == 0 && (p->tick_depth_elems % 8) == 0;
-    if (with_pixmap) {
-        if (vec ? (p->pm_first.reserve(sizeof(int) * ((size_t)p->cap / 8 + 2)) || p->pm_mask.reserve((size_t)p->cap / 8 + 2))
-                : p->pixmap.reserve(sizeof(int) * (size_t)p->cap))
-            return -1;
-        p->pixmap_compact = vec;
-    }
-    struct PixmapScope {
-        LsnFusion *p;
-        PixmapScope(LsnFusion *q, bool on) : p(q) { p->want_pixmap = on; }
-        ~PixmapScope() { p->want_pixmap = false; }
-    } scope(p, with_pixmap);
+    const bool vec = wide_loads(p, d_depth, d_colors);
+    if (with_pixmap && reserve_pixmap(p, vec)) return -1;
     FuseArgs a;
-    fill_args(p, a, d_depth, d_colors, vertices, d_offsets);
-    const int grid = p->tiles_per_tick;
-    if (host_out) {
-        if (vec) hipLaunchKernelGGL((fuse_kernel<1, true, true, true>), dim3(grid), dim3(kThreads), 0, s, a);
-        else     hipLaunchKernelGGL((fuse_kernel<1, false, true, true>), dim3(grid), dim3(kThreads), 0, s, a);
-    } else {
-        launch<1>(vec, grid, s, a, p->lazy_rgb);
-    }
+    fill_args(p, a, d_depth, d_colors, vertices, d_offsets, with_pixmap);
+    launch_fuse<lsn::kPassWrite>(vec, p->tiles_per_tick, s, a, p->lazy_rgb, host_out);   // (the pinned-output form loads its colours lazily whatever lazy_rgb says)
     LSN_HIP(hipGetLastError());
     return 0;
 }
@@ -1340,9 +1341,8 @@ static int lsnFusionRunStreamed_impl(LsnFusion *p, const void *d_depth, const vo
 
     if (ensure_thresholds(p, s)) return -1;
     FuseArgs a;
-    fill_args(p, a, d_depth, d_colors, d_vertices, d_offsets);
-    const bool vec = p->vec_ok && ((uintptr_t)d_depth & 15) == 0 && ((uintptr_t)d_colors & 7) == 0 && (p->tick_depth_elems % 8) == 0 &&
-                     (!d_next_depth || ((uintptr_t)d_next_depth & 15) == 0);
+    fill_args(p, a, d_depth, d_colors, d_vertices, d_offsets, false);
+    const bool vec = wide_loads(p, d_depth, d_colors) && (!d_next_depth || ((uintptr_t)d_next_depth & 15) == 0);
     const int grid = (int)n_tiles;
     int *cur = p->stream_half ? p->tile_counts_b.as<int>() : p->tile_counts.as<int>();
     int *nxt = p->stream_half ? p->tile_counts.as<int>() : p->tile_counts_b.as<int>();
@@ -1350,10 +1350,9 @@ static int lsnFusionRunStreamed_impl(LsnFusion *p, const void *d_depth, const vo
     int *off_nxt = p->offs_int.as<int>() + (p->stream_half ? 0 : off_elems);
     a.tile_counts = cur;
     if (p->counted_for != d_depth || p->counted_gen != p->params_gen) {
-        // nothing (valid) was counted ahead for this batch: do it now, like mode 0
+        // nothing (valid) was counted ahead for this batch: do it now, like the three launches
         a.offsets = off_cur;
-        launch_count(p, vec, s, a);
-        hipLaunchKernelGGL(scan_kernel, dim3((unsigned)p->n_ticks), dim3(kScanThreads), 0, s, cur, a.tiles_per_tick, a.frames, a.n_frames, off_cur, nullptr);
+        count_and_scan(p, vec, s, a);
     }
     LSN_HIP(hipMemcpyAsync(d_offsets, off_cur, sizeof(int) * off_elems, hipMemcpyDeviceToDevice, s));
     a.offsets = d_offsets;
@@ -1363,9 +1362,9 @@ static int lsnFusionRunStreamed_impl(LsnFusion *p, const void *d_depth, const vo
     if (d_next_depth) {
         a.depth_next = static_cast<const unsigned short *>(d_next_depth);
         a.tile_counts_next = nxt;
-        launch<3>(vec, grid, s, a);
+        launch_fuse<lsn::kPassWriteCountNext>(vec, grid, s, a);
     } else {
-        launch<1>(vec, grid, s, a);
+        launch_fuse<lsn::kPassWrite>(vec, grid, s, a);
     }
     if (e1) LSN_HIP(hipEventRecord(e1, s));
     if (d_next_depth) {

@@ -5,10 +5,22 @@
 
 #include "lsn_common.hpp"
 
+#include <cstdint>
 #include <mutex>
 #include <vector>
 
 namespace lsn {
+
+// Two numberings are called "mode" in this library.  The PLAN's mode is what lsnFusionSetMode takes (LsnFusion::mode) and says how a
+// call resolves the tiles' offsets; the kernel PASS is fuse_kernel's MODE template parameter and says what one launch does.  Plain ints,
+// not an enum type: the value is part of the kernels' mangled names, which the profiles and lsnFusionKernelStats report.
+constexpr int kPlanThreeLaunches = 0;   // count -> scan -> write
+constexpr int kPlanLookbackRuns = 1;    // one launch of run_kernel: runs of tiles, one look-back per run
+constexpr int kPlanSinglePass = 2;      // one launch of fuse_kernel<kPassSingle>: one look-back per tile
+constexpr int kPassCount = 0;           // counts into tile_counts
+constexpr int kPassWrite = 1;           // writes at the scanned tile_counts
+constexpr int kPassWriteCountNext = 3;  // kPassWrite + the count of the NEXT batch (lsnFusionRunStreamed)
+constexpr int kPassSingle = 4;          // computes once, resolves its offset by look-back over the tiles before it
 
 struct FrameDesc {
     int w, h, npix, tile_start;  // tile_start: first tile of this frame inside its tick
@@ -40,29 +52,29 @@ struct FuseArgs {
     const unsigned short *depth;
     const unsigned char *rgb;
     uint4 *out;
-    int *tile_counts;                // mode 0: [n_ticks * tiles_per_tick] counts, then exclusive prefixes
-    unsigned long long *run_state;   // mode 1: [n_ticks * tiles_per_tick] {flag:2 | value}, indexed by run
-    unsigned int *ticket;            // mode 1: per-tick run tickets, 32 words apart
+    int *tile_counts;                // count and write passes: [n_ticks * tiles_per_tick] counts, then exclusive prefixes (scan_kernel)
+    unsigned long long *run_state;   // [n_ticks * tiles_per_tick] look-back words: run_kernel {flag:2 | value}, indexed by run; kPassSingle {epoch | flag:2 | value}, by tile
+    unsigned int *ticket;            // run_kernel: per-tick run tickets, 32 words apart
     int *offsets;                    // [n_ticks][n_frames + 1]
     int *pixmap;                     // optional [n_ticks][pixels per tick]: vertex index inside the tick's cloud, -1 = none (rigs the 8-pixel lanes do not fit)
     int *pm_first;                   // ... or its compact form, per lane of 8 pixels: index of the lane's first vertex ...
     unsigned char *pm_mask;          // ... and which of the 8 pixels have one (0.625 instead of 4 bytes per pixel)
-    const unsigned short *depth_next;  // streamed mode (MODE 3): the NEXT batch's depth, counted in the shadow of this write
+    const unsigned short *depth_next;  // kPassWriteCountNext: the NEXT batch's depth, counted in the shadow of this write
     int *tile_counts_next;             // ... and where its per-tile counts go
-    int *error_flag;                 // mode 1: set when a bounded spin gives up (sticky until read)
+    int *error_flag;                 // run_kernel, kPassSingle: set when a bounded look-back spin gives up; write passes: a tile's count differs from the scanned one (sticky until read)
     const unsigned int *thr;         // optional [pixels per tick]: the depth interval each pixel survives in (thresh_kernel), null = none
     int n_frames;
     int tiles_per_tick;
     int n_ticks;
-    int tiles_per_run;               // mode 1
-    unsigned int epoch;              // mode 2: tag of this launch's look-back words (run_state is never cleared)
+    int tiles_per_run;               // run_kernel
+    unsigned int epoch;              // kPassSingle: tag of this launch's look-back words (run_state is cleared only when it wraps)
     int chunk;                       // write pass block order: 0 = tick-major; C > 0 = chunks of C consecutive tiles, all ticks of a chunk before the next chunk
     int reverse_ticks;               // the write pass takes the ticks last to first (what the count pass read last is nearest in cache); always 1
     int tile0;                       // one-tick plans only: the launch covers tiles [tile0, tile0 + gridDim.x) of the tick (a group of sensors, run_frames)
-    int host_out;                    // mode 2: `out` is pinned host memory (plain, destination-aligned stores; see stage_and_store)
-    int *group_end_mirror;           // mode 2, optional (pinned host memory): where this launch's vertices end inside the tick, stored by its last tile
-    int *offsets_mirror;             // mode 2, optional: the offset table entries are also stored here (pinned host memory), [n_frames + 1] = give-up flag
-    int runs_per_tick;               // mode 1
+    int host_out;                    // kPassSingle: `out` is pinned host memory (plain, destination-aligned stores; see stage_and_store)
+    int *group_end_mirror;           // kPassSingle, optional (pinned host memory): where this launch's vertices end inside the tick, stored by its last tile
+    int *offsets_mirror;             // kPassSingle, optional: the offset table entries are also stored here (pinned host memory), [n_frames + 1] = give-up flag
+    int runs_per_tick;               // run_kernel
     long long tick_depth_stride;  // u16 elements
     long long tick_rgb_stride;    // bytes
     long long tick_vert_stride;   // vertices
@@ -527,9 +539,8 @@ struct LsnFusion {
     int tiles_per_tick = 0;
     bool vec_ok = false;
     bool params_set = false;
-    int mode = 0;
-    unsigned int epoch = 0;          // mode 2: launches so far (tags the look-back words)
-    bool want_pixmap = false;        // the run in progress also fills the pixel -> vertex map (set and cleared under mu by run_locked)
+    int mode = lsn::kPlanThreeLaunches;   // lsnFusionSetMode
+    unsigned int epoch = 0;          // single-pass launches so far (tags the look-back words)
     float bounds[6] = {0, 0, 0, 0, 0, 0};
     lsn::DevBuf frames, tile_frame, params, tile_counts, tile_state, misc;  // misc: error flag (word 0) + tickets
     lsn::DevBuf xtab, ytab;
@@ -601,12 +612,29 @@ struct LsnFusion {
 };
 
 namespace lsn {
-// Kernel arguments of one call (everything but the per-mode scratch selection).
-void fill_args(LsnFusion *p, FuseArgs &a, const void *d_depth, const void *d_colors, void *d_vertices, int *d_offsets);
+// Whether a call on these buffers takes the wide-load kernels (16-B depth / 8-B colour loads): the rig allows it (vec_ok), the buffers
+// are aligned and so is every tick's start inside them.  Every pass of a call, and the triangulation that reads the map its vertex
+// pass wrote, must agree on it: this is the one place it is decided.
+inline bool wide_loads(const LsnFusion *p, const void *d_depth, const void *d_colors)
+{
+    return p->vec_ok && ((uintptr_t)d_depth & 15) == 0 && ((uintptr_t)d_colors & 7) == 0 && (p->tick_depth_elems % 8) == 0;
+}
+// The pixel -> vertex map the next vertex pass fills (p->mu held): 5 bytes per 8 pixels when it runs its wide-load form, else one int per pixel.
+inline int reserve_pixmap(LsnFusion *p, bool vec)
+{
+    const size_t px = (size_t)p->cap * p->n_ticks;
+    if (vec ? (p->pm_first.reserve(sizeof(int) * (px / 8 + 2)) || p->pm_mask.reserve(px / 8 + 2)) : p->pixmap.reserve(sizeof(int) * px)) return -1;
+    p->pixmap_compact = vec;   // the triangulation reads the form that pass writes
+    return 0;
+}
+// Kernel arguments of one call (everything but the scratch selection of the launch form); with_pixmap: the write pass also fills the
+// pixel -> vertex map (reserve_pixmap).
+void fill_args(LsnFusion *p, FuseArgs &a, const void *d_depth, const void *d_colors, void *d_vertices, int *d_offsets, bool with_pixmap);
 // Called at the top of every run (p->mu held): builds the per-pixel depth thresholds on the second run with unchanged parameters.
 int ensure_thresholds(LsnFusion *p, hipStream_t s);
-// The count pass of one batch into a.tile_counts: from the thresholds when they exist, else arithmetically.
-void launch_count(LsnFusion *p, bool vec, hipStream_t s, const FuseArgs &a);
+// The count pass of one batch into a.tile_counts (from the thresholds when they exist, else arithmetically), then the scan: exclusive
+// prefixes in place, the offset table to a.offsets and, when given, to `mirror` (pinned host memory).
+void count_and_scan(LsnFusion *p, bool vec, hipStream_t s, const FuseArgs &a, int *mirror = nullptr);
 // Next HIP-event pair of the dominant-kernel timer (profiling on).
 int next_event_pair(LsnFusion *p, hipEvent_t &e0, hipEvent_t &e1);
 // whether the dominant kernel of the launch sequence being queued is timed (profiling on, and this launch's turn)
@@ -614,6 +642,8 @@ inline bool timed_launch(LsnFusion *p) { return p->profile && (p->profile_every 
 }  // namespace lsn
 using lsn::ensure_thresholds;
 using lsn::fill_args;
-using lsn::launch_count;
+using lsn::count_and_scan;
+using lsn::reserve_pixmap;
+using lsn::wide_loads;
 using lsn::next_event_pair;
 using lsn::timed_launch;

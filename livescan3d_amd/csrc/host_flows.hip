@@ -1074,8 +1074,8 @@ int materialize_sharded(Ctx &c, Lane &l)
         d_off += px * 2;
         c_off += px * 3;
     }
-    if (l.last_tri ? lsn::run_mesh(plan, l.d_depth.p, l.d_colors.p, l.d_out.p, l.d_off.as<int>(), l.d_tri.p, l.d_tri_off.as<int>(), l.stream, nullptr)
-                   : lsn::run_hooked(plan, l.d_depth.p, l.d_colors.p, l.d_out.p, l.d_off.as<int>(), l.stream, nullptr))
+    if (l.last_tri ? lsn::run_mesh(plan, l.d_depth.p, l.d_colors.p, l.d_out.p, l.d_off.as<int>(), l.d_tri.p, l.d_tri_off.as<int>(), l.stream)
+                   : lsn::run_vertices(plan, l.d_depth.p, l.d_colors.p, l.d_out.p, l.d_off.as<int>(), l.stream))
         return -1;
     LSN_HIP(hipStreamSynchronize(l.stream));
     l.last_in_hbm = true;
@@ -1093,8 +1093,8 @@ int materialize(Lane &l)
     const long long cap = lsnFusionTickCapacity(plan);
     if (l.d_out.reserve((size_t)cap * 16) || (l.last_tri && l.d_tri.reserve((size_t)cap * 2 * 12))) return -1;
     const void *run_d = l.last_radial ? l.d_depth2.p : l.d_depth.p, *run_c = l.last_radial ? l.d_colors2.p : l.d_colors.p;
-    if (l.last_tri ? lsn::run_mesh(plan, run_d, run_c, l.d_out.p, l.d_off.as<int>(), l.d_tri.p, l.d_tri_off.as<int>(), l.stream, nullptr)
-                   : lsn::run_hooked(plan, run_d, run_c, l.d_out.p, l.d_off.as<int>(), l.stream, nullptr))
+    if (l.last_tri ? lsn::run_mesh(plan, run_d, run_c, l.d_out.p, l.d_off.as<int>(), l.d_tri.p, l.d_tri_off.as<int>(), l.stream)
+                   : lsn::run_vertices(plan, run_d, run_c, l.d_out.p, l.d_off.as<int>(), l.stream))
         return -1;
     LSN_HIP(hipStreamSynchronize(l.stream));
     l.last_in_hbm = true;

@@ -99,29 +99,19 @@ struct DevBuf {
 
 inline hipStream_t as_stream(void *s) { return static_cast<hipStream_t>(s); }
 
-// Optional extras of one run, for hosts that overlap copies with the passes (host_flows.hip): all members may be null.
-struct RunHooks {
-    hipEvent_t colours_ready = nullptr;   // the write pass waits for it (the count pass only reads depth)
-    int *h_offsets = nullptr;             // pinned host copy of the offset table, issued right after the scan ...
-    hipEvent_t counted = nullptr;         // ... and this event recorded behind it (the vertex count is known before the write pass ends)
-    hipEvent_t written = nullptr;         // recorded after the write pass (the vertices may leave while the triangulation runs)
-    int *h_tri_offsets = nullptr;         // lsnFusionRunMesh: pinned host copy of the triangle offset table ...
-    hipEvent_t tri_counted = nullptr;     // ... and the event behind it
-    bool mirror = false;                  // h_tri_offsets is pinned, device-visible memory and the scan kernel stores the table there itself: no copy
-    bool host_out = false;                // the triangle write pass's output is pinned host memory (its HOST form)
-};
-// lsnFusionRun with the plan's mutex already held; with_pixmap also fills the pixel -> vertex map the triangulation reads.
-int run_locked(LsnFusion *p, const void *d_depth, const void *d_colors, void *d_vertices, int *d_offsets, hipStream_t s, bool with_pixmap,
-               const RunHooks *hooks);
-// lsnFusionRun with hooks (takes the mutex).
-int run_hooked(LsnFusion *p, const void *d_depth, const void *d_colors, void *d_vertices, int *d_offsets, hipStream_t s, const RunHooks *hooks);
-// lsnFusionRunMesh with hooks (takes the mutex once for the vertex and the triangle passes).
+// lsnFusionRun on a stream, for the library's own flows (takes the plan's mutex; leaves the error text as it is unless it fails).
+int run_vertices(LsnFusion *p, const void *d_depth, const void *d_colors, void *d_vertices, int *d_offsets, hipStream_t s);
+// The same with the mutex already held; with_pixmap also fills the pixel -> vertex map the triangulation reads, which the caller has
+// reserved (reserve_pixmap, fusion_shared.hpp).  Picks the launch form from the plan's mode (fusion.hip run_form).
+int run_locked(LsnFusion *p, const void *d_depth, const void *d_colors, void *d_vertices, int *d_offsets, hipStream_t s, bool with_pixmap);
+// lsnFusionRunMesh on a stream (takes the mutex once for the vertex and the triangle passes).
 int run_mesh(LsnFusion *p, const void *d_depth, const void *d_colors, void *d_vertices, int *d_offsets, void *d_triangles, int *d_tri_offsets,
-             hipStream_t s, const RunHooks *hooks);
+             hipStream_t s);
 
 // One launch, single pass, over frames [f0, f1) of a one-tick plan (fusion.hip); and the triangle passes alone over the whole tick, for
-// a pixel -> vertex map that run_frames(with_pixmap) launches have filled (mesh.hip).  tri_mirror: optional pinned copy of the table;
-// tri_counted: optional event recorded behind the scan (the counts are in the mirror), before the triangle write pass.
+// a pixel -> vertex map that run_frames(with_pixmap) launches have filled (mesh.hip).  tri_mirror: optional pinned, device-visible copy of
+// the table, stored by the scan kernel itself; tri_counted: optional event recorded behind the scan (the counts are in the mirror), before
+// the triangle write pass; host_out: d_triangles is pinned host memory (the write pass's HOST form).
 int run_frames(LsnFusion *p, const void *d_depth, const void *d_colors, void *d_vertices, int *d_offsets, int f0, int f1, bool first_of_tick,
                bool with_pixmap, int *offsets_mirror, int *group_end_mirror, bool host_out, hipStream_t s);
 int run_triangles(LsnFusion *p, const void *d_depth, void *d_triangles, int *d_tri_offsets, int *tri_mirror, bool host_out, hipStream_t s,

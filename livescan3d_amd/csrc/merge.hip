@@ -310,7 +310,7 @@ static int overlay_merge_locked(LsnFusion *p, const void *d_depth, const void *d
     LSN_HIP(hipMemcpyAsync(p->mg_depth0.p, a.depth, sizeof(unsigned short) * px, hipMemcpyDeviceToDevice, s));
     // 2. bases in turn
     for (int b = 0; b < n && n > 1; b++) {
-        if (triangle_count_passes(p, a.depth, p->mg_toff.as<int>(), s, nullptr, a.d2v) ||
+        if (triangle_count_passes(p, a.depth, p->mg_toff.as<int>(), nullptr, nullptr, s, a.d2v) ||
             triangle_write_pass(p, a.depth, d_triangles, 0, false, s, a.d2v))
             return -1;
         hipLaunchKernelGGL(mg_project_kernel, dim3(vblocks, T), dim3(256), 0, s, a, b);
@@ -324,7 +324,7 @@ static int overlay_merge_locked(LsnFusion *p, const void *d_depth, const void *d
         }
     }
     // 3. the final maps triangulated into the caller's buffers
-    if (triangle_count_passes(p, a.depth, d_tri_offsets, s, nullptr, a.d2v) || triangle_write_pass(p, a.depth, d_triangles, 0, false, s, a.d2v))
+    if (triangle_count_passes(p, a.depth, d_tri_offsets, nullptr, nullptr, s, a.d2v) || triangle_write_pass(p, a.depth, d_triangles, 0, false, s, a.d2v))
         return -1;
     LSN_HIP(hipGetLastError());
     return 0;

@@ -481,7 +481,9 @@ static bool tri_args(LsnFusion *p, const void *d_depth, void *d_triangles, TriAr
     return p->pixmap_compact && ((uintptr_t)d_depth & 15) == 0;   // the vertex pass wrote the compact map iff it ran its wide-load form
 }
 
-static int triangle_count_passes(LsnFusion *p, const void *d_depth, int *d_tri_offsets, hipStream_t s, const lsn::RunHooks *hooks,
+// tri_mirror (optional, pinned and device-visible): the scan kernel stores the offset table there as well; tri_counted (optional): recorded
+// behind the scan.
+static int triangle_count_passes(LsnFusion *p, const void *d_depth, int *d_tri_offsets, int *tri_mirror, hipEvent_t tri_counted, hipStream_t s,
                                  const int *pixmap = nullptr)
 {
     TriArgs t;
@@ -489,12 +491,9 @@ static int triangle_count_passes(LsnFusion *p, const void *d_depth, int *d_tri_o
     const int grid = p->tiles_per_tick * p->n_ticks;
     if (vec) hipLaunchKernelGGL((tri_kernel<0, true>), dim3(grid), dim3(kThreads), 0, s, t);
     else     hipLaunchKernelGGL((tri_kernel<0, false>), dim3(grid), dim3(kThreads), 0, s, t);
-    const bool mirror = hooks && hooks->mirror && hooks->h_tri_offsets;
     hipLaunchKernelGGL(scan_kernel, dim3((unsigned)p->n_ticks), dim3(kScanThreads), 0, s, t.tile_counts, t.tiles_per_tick, t.frames, p->n_maps,
-                       d_tri_offsets, mirror ? hooks->h_tri_offsets : nullptr);
-    if (hooks && hooks->h_tri_offsets && !mirror)
-        LSN_HIP(hipMemcpyAsync(hooks->h_tri_offsets, d_tri_offsets, sizeof(int) * (size_t)p->n_ticks * (p->n_maps + 1), hipMemcpyDeviceToHost, s));
-    if (hooks && hooks->tri_counted) LSN_HIP(hipEventRecord(hooks->tri_counted, s));
+                       d_tri_offsets, tri_mirror);
+    if (tri_counted) LSN_HIP(hipEventRecord(tri_counted, s));
     LSN_HIP(hipGetLastError());
     return 0;
 }
@@ -519,10 +518,18 @@ static int triangle_write_pass(LsnFusion *p, const void *d_depth, void *d_triang
     return 0;
 }
 
-static int triangle_passes(LsnFusion *p, const void *d_depth, void *d_triangles, int *d_tri_offsets, hipStream_t s, const lsn::RunHooks *hooks)
+static int triangle_passes(LsnFusion *p, const void *d_depth, void *d_triangles, int *d_tri_offsets, int *tri_mirror, hipEvent_t tri_counted,
+                           bool host_out, hipStream_t s)
 {
-    if (triangle_count_passes(p, d_depth, d_tri_offsets, s, hooks)) return -1;
-    return triangle_write_pass(p, d_depth, d_triangles, 0, hooks && hooks->host_out, s);
+    if (triangle_count_passes(p, d_depth, d_tri_offsets, tri_mirror, tri_counted, s)) return -1;
+    return triangle_write_pass(p, d_depth, d_triangles, 0, host_out, s);
+}
+
+// The triangle passes' scratch (p->mu held): per-tile counts and the per-lane codes the count pass leaves for the write pass.
+static int reserve_tri_scratch(LsnFusion *p)
+{
+    const size_t n_tiles = (size_t)p->tiles_per_tick * p->n_ticks;
+    return p->tri_counts.reserve(sizeof(int) * n_tiles) || p->tri_codes.reserve(sizeof(unsigned int) * n_tiles * kThreads) ? -1 : 0;
 }
 
 extern "C" long long lsnFusionTickTriangleCapacity(const LsnFusion *p) { return p ? 2 * p->cap : 0; }
@@ -531,7 +538,7 @@ static int lsnFusionRunMesh_impl(LsnFusion *p, const void *d_depth, const void *
                                 void *d_triangles, int *d_tri_offsets, void *stream)
 {
     lsn::clear_error();
-    return lsn::run_mesh(p, d_depth, d_colors, d_vertices, d_offsets, d_triangles, d_tri_offsets, lsn::as_stream(stream), nullptr);
+    return lsn::run_mesh(p, d_depth, d_colors, d_vertices, d_offsets, d_triangles, d_tri_offsets, lsn::as_stream(stream));
 }
 
 extern "C" int lsnFusionRunMesh(LsnFusion *p, const void *d_depth, const void *d_colors, void *d_vertices, int *d_offsets,
@@ -541,7 +548,7 @@ extern "C" int lsnFusionRunMesh(LsnFusion *p, const void *d_depth, const void *d
 }
 
 int lsn::run_mesh(LsnFusion *p, const void *d_depth, const void *d_colors, void *d_vertices, int *d_offsets, void *d_triangles,
-                  int *d_tri_offsets, hipStream_t s, const RunHooks *hooks)
+                  int *d_tri_offsets, hipStream_t s)
 {
     if (!p || !d_depth || !d_colors || !d_vertices || !d_offsets || !d_triangles || !d_tri_offsets) {
         lsn::set_error("lsnFusionRunMesh: null argument");
@@ -551,17 +558,10 @@ int lsn::run_mesh(LsnFusion *p, const void *d_depth, const void *d_colors, void 
     // two threads sharing a plan cannot interleave between them
     std::lock_guard<std::mutex> g(p->mu);
     LSN_HIP(hipSetDevice(p->device));
-    // the pixel -> vertex map: 5 bytes per 8 pixels when the vertex pass runs its wide-load form (the same test as in run_locked),
-    // else one int per pixel
-    const bool wide = p->vec_ok && ((uintptr_t)d_depth & 15) == 0 && ((uintptr_t)d_colors & 7) == 0 && (p->tick_depth_elems % 8) == 0;
-    if ((wide ? (p->pm_first.reserve(sizeof(int) * ((size_t)p->cap * p->n_ticks / 8 + 2)) || p->pm_mask.reserve((size_t)p->cap * p->n_ticks / 8 + 2))
-              : p->pixmap.reserve(sizeof(int) * (size_t)p->cap * p->n_ticks)) ||
-        p->tri_counts.reserve(sizeof(int) * (size_t)p->tiles_per_tick * p->n_ticks) ||
-        p->tri_codes.reserve(sizeof(unsigned int) * (size_t)p->tiles_per_tick * p->n_ticks * kThreads))
-        return -1;
-    // vertices + depth_to_vertices_map (count / scan / write launches)
-    if (lsn::run_locked(p, d_depth, d_colors, d_vertices, d_offsets, s, true, hooks)) return -1;
-    return triangle_passes(p, d_depth, d_triangles, d_tri_offsets, s, hooks);
+    if (reserve_pixmap(p, wide_loads(p, d_depth, d_colors)) || reserve_tri_scratch(p)) return -1;
+    // vertices + depth_to_vertices_map (count / scan / write launches, or the single pass of a one-tick plan)
+    if (lsn::run_locked(p, d_depth, d_colors, d_vertices, d_offsets, s, true)) return -1;
+    return triangle_passes(p, d_depth, d_triangles, d_tri_offsets, nullptr, nullptr, false, s);
 }
 
 int lsn::run_triangles(LsnFusion *p, const void *d_depth, void *d_triangles, int *d_tri_offsets, int *tri_mirror, bool host_out, hipStream_t s,
@@ -573,15 +573,8 @@ int lsn::run_triangles(LsnFusion *p, const void *d_depth, void *d_triangles, int
     }
     std::lock_guard<std::mutex> g(p->mu);
     LSN_HIP(hipSetDevice(p->device));
-    if (p->tri_counts.reserve(sizeof(int) * (size_t)p->tiles_per_tick * p->n_ticks) ||
-        p->tri_codes.reserve(sizeof(unsigned int) * (size_t)p->tiles_per_tick * p->n_ticks * kThreads))
-        return -1;
-    lsn::RunHooks hooks;
-    hooks.mirror = tri_mirror != nullptr;
-    hooks.host_out = host_out;
-    hooks.h_tri_offsets = tri_mirror;
-    hooks.tri_counted = tri_counted;
-    return triangle_passes(p, d_depth, d_triangles, d_tri_offsets, s, &hooks);
+    if (reserve_tri_scratch(p)) return -1;
+    return triangle_passes(p, d_depth, d_triangles, d_tri_offsets, tri_mirror, tri_counted, host_out, s);
 }
 
 
@@ -595,14 +588,8 @@ int lsn::run_triangles_count(LsnFusion *p, const void *d_depth, int *d_tri_offse
     }
     std::lock_guard<std::mutex> g(p->mu);
     LSN_HIP(hipSetDevice(p->device));
-    if (p->tri_counts.reserve(sizeof(int) * (size_t)p->tiles_per_tick * p->n_ticks) ||
-        p->tri_codes.reserve(sizeof(unsigned int) * (size_t)p->tiles_per_tick * p->n_ticks * kThreads))
-        return -1;
-    lsn::RunHooks hooks;
-    hooks.mirror = tri_mirror != nullptr;
-    hooks.h_tri_offsets = tri_mirror;
-    hooks.tri_counted = tri_counted;
-    return triangle_count_passes(p, d_depth, d_tri_offsets, s, &hooks);
+    if (reserve_tri_scratch(p)) return -1;
+    return triangle_count_passes(p, d_depth, d_tri_offsets, tri_mirror, tri_counted, s);
 }
 
 int lsn::run_triangles_write(LsnFusion *p, const void *d_depth, void *d_triangles, int index_base, bool host_out, hipStream_t s)

@@ -399,12 +399,93 @@ void parser_fuzz(int rounds)
     }
 }
 
+// The device-resident exports of the fused pass on the double, one call after the other on this thread: every launch form a plan can take
+// (lsnFusionSetMode 0 / 1 / 2, with and without the triangulation, pipelined, streamed) on a multi-tick plan of 8-pixel-aligned sensors
+// and on a one-tick plan with a ragged one (the general-width kernels and map).  The double emulates the count, scan, write and
+// single-pass kernels, so where only those run the vertex totals are checked; the look-back-per-run kernel and the streamed write +
+// count are no-ops there and only have to be enqueued without an error.
+void fusion_forms(int T, const int *w, const int *h)
+{
+    const int n = 2;
+    char what[64];
+    snprintf(what, sizeof(what), "fusion forms (%d tick(s), %dx%d + %dx%d)", T, w[0], h[0], w[1], h[1]);
+    LsnFusion *p = lsnFusionCreate(0, T, n, w, h);
+    CHECK(g_faults || p != nullptr, "%s: lsnFusionCreate", what);
+    if (!p) return;
+    const long long cap = lsnFusionTickCapacity(p), tcap = lsnFusionTickTriangleCapacity(p);
+    CHECK(cap == (long long)w[0] * h[0] + (long long)w[1] * h[1] && tcap == 2 * cap, "%s: capacities", what);
+    float intr[14], wt[24], bounds[6] = {-2, -2, -2, 2, 2, 2};
+    for (int i = 0; i < n; i++) {
+        const float k[7] = {w[i] / 2.0f, h[i] / 2.0f, 365.0f * w[i] / 512.0f, 365.0f * w[i] / 512.0f, 0.09f, -0.05f, 0.01f};
+        memcpy(intr + 7 * i, k, sizeof(k));
+        const float q[12] = {0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0, 1};
+        memcpy(wt + 12 * i, q, sizeof(q));
+    }
+    void *d[3] = {nullptr, nullptr, nullptr}, *c = nullptr, *v = nullptr, *tr = nullptr;
+    int *o = nullptr, *to = nullptr;
+    bool ok = fakeDevMalloc(&d[0], 2 * cap * T) == 0 && fakeDevMalloc(&d[1], 2 * cap * T) == 0 && fakeDevMalloc(&d[2], 2 * cap * T) == 0 &&
+              fakeDevMalloc(&c, 3 * cap * T) == 0 && fakeDevMalloc(&v, 16 * cap * T) == 0 && fakeDevMalloc(&tr, 12 * tcap * T) == 0 &&
+              fakeDevMalloc((void **)&o, sizeof(int) * (n + 1) * T) == 0 && fakeDevMalloc((void **)&to, sizeof(int) * (n + 1) * T) == 0;
+    CHECK(g_faults || ok, "%s: device buffers", what);
+    CHECK(!ok || lsnFusionRun(p, d[0], c, v, o, nullptr) == -1, "%s: lsnFusionRun before lsnFusionSetParams", what);
+    const bool set = lsnFusionSetParams(p, intr, wt, bounds, nullptr) == 0;
+    CHECK(g_faults || set, "%s: lsnFusionSetParams", what);
+    if (ok && set) {
+        // the double's "device" memory is the host's: three batches of depth, every seventh pixel without a measurement
+        std::vector<int> want(T, 0);
+        for (int b = 0; b < 3; b++) {
+            unsigned short *dep = static_cast<unsigned short *>(d[b]);
+            for (long long i = 0; i < cap * T; i++) dep[i] = (i + b) % 7 == 0 ? 0 : (unsigned short)(600 + i % 900);
+        }
+        for (int t = 0; t < T; t++)
+            for (long long i = cap * t; i < cap * (t + 1); i++) want[t] += i % 7 != 0;
+        auto call = [&](int rc, bool counted, const char *which) {
+            char why[256] = "";
+            if (rc) (void)lsnGetLastError(why, sizeof(why));
+            CHECK(g_faults || rc == 0, "%s: %s: %s", what, which, why);
+            if (rc || !counted) return;
+            for (int t = 0; t < T; t++) CHECK(o[t * (n + 1) + n] == want[t], "%s: %s: tick %d has %d vertices, expected %d", what, which, t, o[t * (n + 1) + n], want[t]);
+        };
+        for (int mode = 0; mode < 3; mode++) {
+            CHECK(lsnFusionSetMode(p, mode) == 0 || g_faults, "%s: lsnFusionSetMode(%d)", what, mode);
+            for (int rep = 0; rep < 2; rep++) {   // (the second run with unchanged parameters builds the depth thresholds)
+                call(lsnFusionRun(p, d[0], c, v, o, nullptr), mode != 1, "lsnFusionRun");
+                call(lsnFusionRunMesh(p, d[0], c, v, o, tr, to, nullptr), true, "lsnFusionRunMesh");
+                for (int t = 0; t < T && !g_faults; t++)
+                    CHECK(to[t * (n + 1) + n] == want[t], "%s: lsnFusionRunMesh: tick %d has %d triangles, expected %d", what, t, to[t * (n + 1) + n], want[t]);
+            }
+        }
+        CHECK(lsnFusionSetMode(p, 3) == -1, "%s: lsnFusionSetMode(3)", what);
+        CHECK(lsnFusionSetMode(p, 0) == 0 || g_faults, "%s: lsnFusionSetMode(0)", what);
+        const bool piped = lsnFusionSetPipelined(p, 1) == 0;
+        CHECK(g_faults || piped, "%s: lsnFusionSetPipelined(1)", what);
+        if (piped)
+            for (int rep = 0; rep < 3; rep++) call(lsnFusionRun(p, d[0], c, v, o, nullptr), true, "lsnFusionRun, pipelined");
+        CHECK(lsnFusionSetPipelined(p, 0) == 0 || g_faults, "%s: lsnFusionSetPipelined(0)", what);
+        call(lsnFusionRun(p, d[0], c, v, o, nullptr), true, "lsnFusionRun after the pipelined calls");
+        // streamed: batch 0 counted now and batch 1 ahead, batch 1 from the counts made ahead (the double makes none: nothing to check),
+        // then batch 2, which nobody counted ahead
+        call(lsnFusionRunStreamed(p, d[0], c, v, o, d[1], nullptr), true, "lsnFusionRunStreamed with a next batch");
+        call(lsnFusionRunStreamed(p, d[1], c, v, o, nullptr, nullptr), false, "lsnFusionRunStreamed without one");
+        call(lsnFusionRunStreamed(p, d[2], c, v, o, nullptr, nullptr), false, "lsnFusionRunStreamed, not counted ahead");
+        CHECK(lsnFusionRunStreamed(p, nullptr, c, v, o, nullptr, nullptr) == -1, "%s: lsnFusionRunStreamed(null)", what);
+    }
+    for (void *q : {d[0], d[1], d[2], c, v, tr, (void *)o, (void *)to}) (void)fakeDevFree(q);
+    lsnFusionDestroy(p);
+}
+
 int main(int argc, char **argv)
 {
     const int iters = argc > 1 ? atoi(argv[1]) : 4;
     null_sweep();
     ragged_rigs(3 * iters);
     parser_fuzz(20 * iters);
+    {
+        // (behind everything else this thread does alone: the fault hooks count allocations and guarded entries from the start)
+        const int w_even[2] = {64, 24}, h_even[2] = {48, 16}, w_ragged[2] = {64, 20}, h_ragged[2] = {48, 16};
+        fusion_forms(3, w_even, h_even);
+        fusion_forms(1, w_ragged, h_ragged);
+    }
     {
         std::vector<std::thread> th;
         th.emplace_back(merge_thread, iters);
