@@ -278,6 +278,28 @@ int lsnFusionOutlierDiagnostics(LsnFusion *plan, int tick, int *removed_per_sens
                                 void *stream);
 int lsnSetOutlierFilter(int k, float max_dist, int *prev_k, float *prev_max_dist);
 
+/* Flying-pixel filter (LiveScanClient's KinectCapture::filterFlyingPixels, src/LiveScanClient/kinectCapture.cpp:132-174, with the server's
+ * bFilterFlyingPixels / nFPNeighbourhoodSize / nFPThreshold, LiveScanServer/KinectSettings.cs:34-37) on all n_ticks x n_maps depth maps of
+ * the plan, in front of the radial correction: a pixel with `neighbourhood` <= x < w - neighbourhood and the same for y (value 0 included)
+ * becomes 0 iff MORE than N / 2 of the N = (2 neighbourhood + 1)^2 - 1 pixels of its window differ from it by MORE than `threshold`
+ * (integer comparison; a neighbour of depth 0 counts like any other value); every decision reads the unmodified map, the border band
+ * is copied through, a frame smaller than the window is copied.  The reference's nFPMaxNonFittingNeighbours is overwritten with N / 2
+ * before it is read, so it is no parameter.  neighbourhood <= 0: the maps are copied unchanged.  Any neighbourhood >= 1 is right; up to 3
+ * the window comes from on-chip memory, above that from cached global loads (slow).  Out of place: a d_depth_out that overlaps
+ * d_depth_in (equal pointers included) is refused.  Asynchronous on `stream`; returns 0, -1 on error.
+ * lsnFusionFlyingDiagnostics (synchronises `stream`): for tick `tick` of the plan's last filter, the pixels of depth != 0 it set to 0, per
+ * sensor (n_maps ints; may be NULL; all 0 after a call with neighbourhood <= 0).  Returns their sum, -1 on error or before any filter call.
+ * lsnSetFlyingPixelFilter: the process-wide switch of the filter in the exports that START AT RAW FRAMES, i.e. with the radial correction:
+ * depthMapAndColorSetRadialCorrection and lsnCorrectAndGenerateMesh filter every sensor's map before correcting it, on every device of
+ * $LSN_HOST_DEVICES, and what they write back is the filtered, corrected maps.  generateMeshFromDepthMaps and
+ * generateVerticesFromDepthMap never filter: LiveScanServer calls them on the maps the radial export has just returned
+ * (KinectServer.cs:518-525, :354-374), and the filter is not idempotent -- there it would run twice per tick.  It runs for
+ * neighbourhood >= 1.  Initially $LSN_FLYING_PIXELS="neighbourhood,threshold" (e.g. "1,20", the client's defaults; unset or malformed:
+ * off); every call reads the current value.  The previous pair goes to prev_neighbourhood / prev_threshold (either may be NULL); returns 0. */
+int lsnFusionFlyingPixels(LsnFusion *plan, int neighbourhood, int threshold, const void *d_depth_in, void *d_depth_out, void *stream);
+int lsnFusionFlyingDiagnostics(LsnFusion *plan, int tick, int *removed_per_sensor, void *stream);
+int lsnSetFlyingPixelFilter(int neighbourhood, int threshold, int *prev_neighbourhood, int *prev_threshold);
+
 /* Radial correction of n_ticks x n_maps frames in place in HBM (same layouts as lsnFusionRun's inputs);
  * intr_params: host, 7 floats per sensor {cx,cy,fx,fy,r2,r4,r6}. */
 int lsnFusionRadialCorrect(LsnFusion *plan, const float *intr_params, void *d_depth_maps, void *d_depth_colors, void *stream);
@@ -449,6 +471,11 @@ int lsnTickSetParams(LsnTick *tick, const float *intr_params, const float *wtran
 long long lsnTickCapacity(const LsnTick *tick);
 long long lsnTickTriangleCapacity(const LsnTick *tick);
 int lsnTickParts(const LsnTick *tick);   /* 1 or 2 */
+/* The flying-pixel filter as the tick's first stage: lsnTickRun then runs filter -> radial correction -> vertices -> triangles, on both
+ * halves of a two-part tick.  d_depth_in stays untouched; d_depth_corrected receives the filtered AND corrected maps.  The filtered maps
+ * pass through scratch of the tick object (2 bytes per pixel per tick), reserved by the first lsnTickRun that filters: a tick object
+ * that never filters allocates nothing for it.  neighbourhood <= 0: off (the default).  Returns 0, -1 on error. */
+int lsnTickSetFlyingPixels(LsnTick *tick, int neighbourhood, int threshold);
 int lsnTickRun(LsnTick *tick, const void *d_depth_in, const void *d_colors_in, void *d_depth_corrected, void *d_colors_corrected,
                void *d_vertices, int *d_offsets, void *d_triangles, int *d_tri_offsets, void *stream);
 

@@ -181,6 +181,8 @@ extern "C" int lsnStreamSynchronize(int device, void *stream)
 
 // the outlier filter's current (k, max_dist) (lsnSetOutlierFilter, below)
 static void outlier_current(int &k, float &max_dist);
+// the flying-pixel filter's current (neighbourhood, threshold) (lsnSetFlyingPixelFilter, below)
+static void flying_current(int &neighbourhood, int &threshold);
 
 // What the three mesh exports share: `call` as `name` filled it (everything but the outlier filter's setting, which is read here) runs on
 // lane `l` of the context.  0: *out_mesh is the call's mesh; -1: the call was refused or failed, *out_mesh (if there is one) is empty and,
@@ -291,6 +293,57 @@ extern "C" int lsnSetOutlierFilter(int k, float max_dist, int *prev_k, float *pr
     });
 }
 
+// lsnSetFlyingPixelFilter: (neighbourhood, threshold) of the flying-pixel filter of the exports that start at raw frames, i.e. with the
+// radial correction: depthMapAndColorSetRadialCorrection and lsnCorrectAndGenerateMesh.  generateMeshFromDepthMaps and
+// generateVerticesFromDepthMap never read it: LiveScanServer calls them on the maps the radial export has just returned
+// (KinectServer.cs:518-525, :354-374), and the filter is not idempotent -- there it would run twice per tick.  Its first value comes from
+// $LSN_FLYING_PIXELS="neighbourhood,threshold" (unset: off; malformed: off, with a message); from then on it is what the last
+// lsnSetFlyingPixelFilter set, and the two exports read it when called.
+struct FlyingSetting {
+    std::mutex mu;
+    int neighbourhood = 0, threshold = 0;
+};
+
+static FlyingSetting &flying_setting()
+{
+    static FlyingSetting *s = [] {
+        FlyingSetting *o = new FlyingSetting();
+        const char *e = getenv("LSN_FLYING_PIXELS");
+        if (e && *e) {
+            int n = 0, t = 0, used = 0;
+            if (sscanf(e, " %d , %d %n", &n, &t, &used) == 2 && e[used] == '\0') {
+                o->neighbourhood = n;
+                o->threshold = t;
+            } else {
+                fprintf(stderr, "[NativeUtils] $LSN_FLYING_PIXELS=\"%s\" is not \"neighbourhood,threshold\" (e.g. \"1,20\"): the flying-pixel filter stays off\n", e);
+            }
+        }
+        return o;
+    }();
+    return *s;
+}
+
+static void flying_current(int &neighbourhood, int &threshold)
+{
+    FlyingSetting &o = flying_setting();
+    std::lock_guard<std::mutex> g(o.mu);
+    neighbourhood = o.neighbourhood;
+    threshold = o.threshold;
+}
+
+extern "C" int lsnSetFlyingPixelFilter(int neighbourhood, int threshold, int *prev_neighbourhood, int *prev_threshold)
+{
+    return lsn::guarded<int>("lsnSetFlyingPixelFilter", static_cast<int>(-1), [&]() {
+        FlyingSetting &o = flying_setting();
+        std::lock_guard<std::mutex> g(o.mu);
+        if (prev_neighbourhood) *prev_neighbourhood = o.neighbourhood;
+        if (prev_threshold) *prev_threshold = o.threshold;
+        o.neighbourhood = neighbourhood;
+        o.threshold = threshold;
+        return 0;
+    });
+}
+
 static void generateMeshFromDepthMaps_impl(int n_maps, unsigned char *depth_maps, unsigned char *depth_colors, int *widths, int *heights,
                                           float *intr_params, float *wtransform_params, Mesh *out_mesh, bool bcolor_transfer, float minX,
                                           float minY, float minZ, float maxX, float maxY, float maxZ, bool bgenerate_triangles)
@@ -363,6 +416,7 @@ static void lsnCorrectAndGenerateMesh_impl(int n_maps, unsigned char *depth_maps
     call.radial = true;
     call.back_d = write_back_corrected ? depth_maps : nullptr;
     call.back_c = write_back_corrected ? depth_colors : nullptr;
+    flying_current(call.fp_neighbourhood, call.fp_threshold);
     (void)mesh_export("lsnCorrectAndGenerateMesh", ctx().merge, call, out_mesh);
 }
 
@@ -386,7 +440,9 @@ static void depthMapAndColorSetRadialCorrection_impl(int n_maps, unsigned char *
     Lane &l = c.merge;
     std::lock_guard<std::mutex> g(l.mu);
     if (ensure_ready(c)) return;
-    radial_host(c, l, n_maps, depth_maps, depth_colors, widths, heights, intr_params);
+    int fp_n = 0, fp_t = 0;
+    flying_current(fp_n, fp_t);
+    radial_host(c, l, n_maps, depth_maps, depth_colors, widths, heights, intr_params, fp_n, fp_t);
 }
 
 extern "C" void depthMapAndColorSetRadialCorrection(int n_maps, unsigned char *depth_maps, unsigned char *depth_colors, int *widths,

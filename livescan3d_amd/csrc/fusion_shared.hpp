@@ -592,6 +592,14 @@ struct LsnFusion {
     lsn::DevBuf ol_key, ol_bucket, ol_chunk, ol_pts, ol_removed, ol_stats, ol_offs, ol_tab, ol_box, ol_frame;
     bool ol_ready = false;
     int ol_nb = 0, ol_nchunk = 0;        // buckets per tick, scan chunks per tick
+    // flying-pixel filter (flying.hip), allocated on its first call: the 128 x 16 tiles of one tick, the removed pixels of depth != 0 per
+    // tile of every tick (lsnFusionFlyingDiagnostics adds them up per sensor through fl_tile_frame)
+    lsn::DevBuf fl_tiles, fl_counts;
+    std::vector<int> fl_tile_frame;
+    bool fl_ready = false;
+    int fl_tiles_per_tick = 0;
+    int fl_last = 0;                     // what the last call was: 0 = none yet, 1 = a copy (neighbourhood <= 0), 2 = the filter
+    hipStream_t fl_stream = nullptr;     // ... and its stream
     bool thr_valid = false;
     bool thr_enabled = true;             // $LSN_NO_THRESHOLDS=1 keeps the arithmetic count pass (ablation / tests)
     bool one_tick_single_pass = false;   // a one-tick plan of <= 2048 tiles takes the single pass (fuse_kernel<4>) instead of count -> scan -> write; $LSN_ONE_TICK_SINGLE_PASS=0 / 1 forces

@@ -52,6 +52,7 @@ struct Lane {
     int h_off_cap = 0;
     lsn::DevBuf d_depth, d_colors, d_depth2, d_colors2, d_out, d_off, d_tri, d_tri_off;
     lsn::DevBuf d_masked;     // a call with the outlier filter on: its depth maps with the removed vertices' pixels at 0 (allocated by the first such call)
+    lsn::DevBuf d_flying;     // a call with the flying-pixel filter on: its raw depth maps filtered, what the radial correction then reads (allocated by the first such call)
     // the lane's plans: key = n sensors, first sensor, widths..., heights...  Owned by the lane and only touched under its lock, so a
     // plan never runs on two lanes' streams at once and an eviction cannot pull a plan from under the other lane's call
     std::map<std::vector<int>, LsnFusion *> plans;
@@ -189,12 +190,17 @@ struct MeshCall {
     bool color_transfer = false, overlay_merge = false;   // the stages on the fused cloud (color.hip, merge.hip) ...
     int outlier_k = 0;                       // ... and the outlier filter (outlier.hip, lsnSetOutlierFilter): it runs when outlier_k > 0
     float outlier_max_dist = 0.0f;           //     and outlier_max_dist > 0
+    int fp_neighbourhood = 0, fp_threshold = 0;   // the flying-pixel filter (flying.hip, lsnSetFlyingPixelFilter) in front of the radial correction
+                                                  //     of a call that starts with it (`radial`): it runs when flying_on(fp_neighbourhood)
 };
+
+// The one place that decides whether a call filters flying pixels: a neighbourhood of at least one pixel (0 and below mean off).
+inline bool flying_on(int neighbourhood) { return neighbourhood >= 1; }
 
 // The calls.  The lane's lock is held by the caller; `out` is left untouched on failure (the export then returns an empty mesh).
 int fuse_host(Ctx &c, Lane &l, const MeshCall &call, Mesh *out);
 void radial_host(Ctx &c, Lane &l, int n_maps, unsigned char *depth_maps, unsigned char *depth_colors, const int *widths, const int *heights,
-                 const float *intr_params);
+                 const float *intr_params, int fp_neighbourhood = 0, int fp_threshold = 0);
 int materialize(Lane &l);                  // lsnLastMesh*: the mesh of the lane's last call in d_out / d_tri
 
 }  // namespace host

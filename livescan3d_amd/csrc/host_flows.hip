@@ -446,6 +446,7 @@ struct HostCall {
             l.d_tri_off.reserve(sizeof(int) * (size_t)(count + 1)) || ensure_tables(l, count + 2 + extra_tab))
             return -1;
         if (radial && (l.d_depth2.reserve(dbytes + 16) || l.d_colors2.reserve(cbytes + 16))) return -1;
+        if (radial && flying_on(call.fp_neighbourhood) && l.d_flying.reserve(dbytes + 16)) return -1;
         if (in_hbm && (l.d_out.reserve((size_t)cap * 16) || (with_triangles && l.d_tri.reserve((size_t)cap * 2 * 12)))) return -1;
         back = radial && call.back_d && call.back_c;
         // the mesh's host blocks, sized for the most the frames can give (recycled through the pool: the same blocks tick after tick);
@@ -484,8 +485,14 @@ struct HostCall {
             tr.mark(cp.colours ? "upC" : "upD");
             for (; next_group < G && l.groups[next_group].ready_after == (int)i + 1; next_group++) {
                 const Group &g = l.groups[next_group];
-                // out of place: raw frames in d_depth / d_colors, corrected ones in the second pair, which the launches read
-                if (call.radial && lsnFusionRadialCorrectTo(g.radial_plan, call.intr + 7 * g.first, l.d_depth.as<char>() + g.d_off, l.d_colors.as<char>() + g.c_off,
+                // out of place: raw frames in d_depth / d_colors, corrected ones in the second pair, which the launches read; with the
+                // flying-pixel filter on, the group's raw maps are filtered into d_flying first and the correction reads those
+                const char *raw_d = l.d_depth.as<char>() + g.d_off;
+                if (call.radial && flying_on(call.fp_neighbourhood)) {
+                    if (lsn::flying_pixels(g.radial_plan, call.fp_neighbourhood, call.fp_threshold, raw_d, l.d_flying.as<char>() + g.d_off, l.stream)) return -1;
+                    raw_d = l.d_flying.as<char>() + g.d_off;
+                }
+                if (call.radial && lsnFusionRadialCorrectTo(g.radial_plan, call.intr + 7 * g.first, raw_d, l.d_colors.as<char>() + g.c_off,
                                                        l.d_depth2.as<char>() + g.d_off, l.d_colors2.as<char>() + g.c_off, l.stream))
                     return -1;
                 if (on_group(next_group, g)) return -1;
@@ -816,13 +823,18 @@ int shard_part(ShardedCall &sc, int d)
     l.groups.clear();
     LsnFusion *plan = get_plan(c, l, call.widths, call.heights, f0, n);
     if (!plan) return -1;
+    // the flying-pixel filter of a call that starts with the correction: this device filters its own block into d_flying, which the
+    // correction then reads
+    const bool flying = call.radial && flying_on(call.fp_neighbourhood);
+    if (flying && l.d_flying.reserve(dbytes + 16)) return -1;
     if (sc.only_radial) {
         // the radial export alone: this block up over this device's link, corrected out of place, home again (both ways pageable copies
         // that keep this thread -- which is why every device has one)
         if (l.d_depth.reserve(dbytes + 16) || l.d_colors.reserve(cbytes + 16) || l.d_depth2.reserve(dbytes + 16) || l.d_colors2.reserve(cbytes + 16)) return -1;
         LSN_HIP(hipMemcpyWithStream(l.d_depth.p, call.depth_maps + d_src, dbytes, hipMemcpyHostToDevice, l.up));
         LSN_HIP(hipMemcpyWithStream(l.d_colors.p, call.depth_colors + c_src, cbytes, hipMemcpyHostToDevice, l.up));
-        if (lsnFusionRadialCorrectTo(plan, call.intr + 7 * f0, l.d_depth.p, l.d_colors.p, l.d_depth2.p, l.d_colors2.p, l.stream)) return -1;
+        if (flying && lsn::flying_pixels(plan, call.fp_neighbourhood, call.fp_threshold, l.d_depth.p, l.d_flying.p, l.stream)) return -1;
+        if (lsnFusionRadialCorrectTo(plan, call.intr + 7 * f0, flying ? l.d_flying.p : l.d_depth.p, l.d_colors.p, l.d_depth2.p, l.d_colors2.p, l.stream)) return -1;
         LSN_HIP(hipStreamSynchronize(l.stream));
         LSN_HIP(hipMemcpyWithStream(call.back_d + d_src, l.d_depth2.p, dbytes, hipMemcpyDeviceToHost, l.back));
         LSN_HIP(hipMemcpyWithStream(call.back_c + c_src, l.d_colors2.p, cbytes, hipMemcpyDeviceToHost, l.back));
@@ -844,7 +856,8 @@ int shard_part(ShardedCall &sc, int d)
     if (!call.radial && lsn::run_count(plan, run_d, run_c, l.d_off.as<int>(), l.h_off, ev_counted, l.stream)) return -1;
     LSN_HIP(hipMemcpyWithStream(l.d_colors.p, call.depth_colors + c_src, cbytes, hipMemcpyHostToDevice, l.up));
     if (call.radial) {
-        if (lsnFusionRadialCorrectTo(plan, call.intr + 7 * f0, l.d_depth.p, l.d_colors.p, l.d_depth2.p, l.d_colors2.p, l.stream)) return -1;
+        if (flying && lsn::flying_pixels(plan, call.fp_neighbourhood, call.fp_threshold, l.d_depth.p, l.d_flying.p, l.stream)) return -1;
+        if (lsnFusionRadialCorrectTo(plan, call.intr + 7 * f0, flying ? l.d_flying.p : l.d_depth.p, l.d_colors.p, l.d_depth2.p, l.d_colors2.p, l.stream)) return -1;
         LSN_HIP(hipEventRecord(ev_corrected, l.stream));
         if (lsn::run_count(plan, run_d, run_c, l.d_off.as<int>(), l.h_off, ev_counted, l.stream)) return -1;
     }
@@ -971,7 +984,7 @@ int run_parts(Ctx &c, ShardedCall &sc)
 // depthMapAndColorSetRadialCorrection over the devices of $LSN_HOST_DEVICES: every device corrects its block of sensors and writes it back
 // into the caller's arrays.  The merge lane's lock is held.
 int radial_sharded(Ctx &c, Lane &ml, int n_maps, unsigned char *depth_maps, unsigned char *depth_colors, const int *widths, const int *heights,
-                   const float *intr)
+                   const float *intr, int fp_neighbourhood, int fp_threshold)
 {
     ml.forget_last();
     MeshCall call;
@@ -984,6 +997,8 @@ int radial_sharded(Ctx &c, Lane &ml, int n_maps, unsigned char *depth_maps, unsi
     call.radial = true;
     call.back_d = depth_maps;
     call.back_c = depth_colors;
+    call.fp_neighbourhood = fp_neighbourhood;
+    call.fp_threshold = fp_threshold;
     ShardedCall sc(c, call);
     sc.only_radial = true;
     plan_shards(n_maps, (int)c.shards.size(), sc.first, sc.D);
@@ -1126,12 +1141,13 @@ int fuse_host(Ctx &c, Lane &l, const MeshCall &call, Mesh *out)
 
 // depthMapAndColorSetRadialCorrection on the lane (one device) or over the devices of $LSN_HOST_DEVICES.  The lane's lock is held.
 void radial_host(Ctx &c, Lane &l, int n_maps, unsigned char *depth_maps, unsigned char *depth_colors, const int *widths, const int *heights,
-                 const float *intr_params)
+                 const float *intr_params, int fp_neighbourhood, int fp_threshold)
 {
     if (c.shards.size() >= 2 && n_maps >= 2) {
-        (void)radial_sharded(c, l, n_maps, depth_maps, depth_colors, widths, heights, intr_params);
+        (void)radial_sharded(c, l, n_maps, depth_maps, depth_colors, widths, heights, intr_params, fp_neighbourhood, fp_threshold);
         return;
     }
+    const bool flying = flying_on(fp_neighbourhood);   // every group's raw maps are filtered into d_flying, which its correction reads
     l.last_nv = -1;   // the lane's buffers are about to be reused
     l.last_plan = nullptr;
     l.groups.clear();
@@ -1144,6 +1160,7 @@ void radial_host(Ctx &c, Lane &l, int n_maps, unsigned char *depth_maps, unsigne
         cbytes += q.cbytes;
     }
     if (l.d_depth.reserve(dbytes + 16) || l.d_colors.reserve(cbytes + 16) || l.d_depth2.reserve(dbytes + 16) || l.d_colors2.reserve(cbytes + 16)) return;
+    if (flying && l.d_flying.reserve(dbytes + 16)) return;
     // Both directions are pageable copies that keep the thread; what overlaps is the correction itself (~100 us per group, latency
     // bound) with the next group's upload and the previous group's way home.  Out of place on the device (the warped, un-closed
     // maps stay in LDS); a group's slice of the caller's arrays is overwritten once ITS kernels have run -- a call that fails
@@ -1168,7 +1185,12 @@ void radial_host(Ctx &c, Lane &l, int n_maps, unsigned char *depth_maps, unsigne
         }
         for (; ok && next_group < G && l.groups[next_group].ready_after == (int)i + 1; next_group++) {
             const Group &q = l.groups[next_group];
-            ok = lsnFusionRadialCorrectTo(q.radial_plan, intr_params + 7 * q.first, l.d_depth.as<char>() + q.d_off, l.d_colors.as<char>() + q.c_off,
+            const char *raw_d = l.d_depth.as<char>() + q.d_off;
+            if (flying) {
+                ok = lsn::flying_pixels(q.radial_plan, fp_neighbourhood, fp_threshold, raw_d, l.d_flying.as<char>() + q.d_off, l.stream) == 0;
+                raw_d = l.d_flying.as<char>() + q.d_off;
+            }
+            ok = ok && lsnFusionRadialCorrectTo(q.radial_plan, intr_params + 7 * q.first, raw_d, l.d_colors.as<char>() + q.c_off,
                                           l.d_depth2.as<char>() + q.d_off, l.d_colors2.as<char>() + q.c_off, l.stream) == 0 &&
                  hipEventRecord(l.ev_group[next_group], l.stream) == hipSuccess;
             // the group before goes home while this one is being corrected -- but never before every upload run it shares with a later

@@ -134,6 +134,10 @@ int overlay_merge(LsnFusion *p, const void *d_depth, const void *d_vertices, con
 int outlier_filter(LsnFusion *p, int k, float max_dist, const void *d_depth, const void *d_vertices, const int *d_offsets, void *d_depth_out,
                    hipStream_t s);
 
+// lsnFusionFlyingPixels on a stream (flying.hip): the flying-pixel filter on every map of the plan, d_depth_in into d_depth_out (out of
+// place; neighbourhood <= 0 copies).  Takes the plan's mutex.
+int flying_pixels(LsnFusion *p, int neighbourhood, int threshold, const void *d_depth_in, void *d_depth_out, hipStream_t s);
+
 // The survivor exchange's two ends with the back-to-back stream layout (exchange.hip; see their definitions).
 int pack_survivors(LsnFusion *p, const void *d_depth, const void *d_colors, void *d_mask, void *d_depth_c, void *d_rgb_c, int *d_tile_prefix,
                    int *d_offsets, int *d_tick_base, void *stream);

@@ -1371,3 +1371,6 @@ extern "C" int lsnFusionRadialCorrectTo(LsnFusion *p, const float *intr_params, 
 {
     return lsn::guarded<int>("lsnFusionRadialCorrectTo", static_cast<int>(-1), [&]() { return lsnFusionRadialCorrectTo_impl(p, intr_params, d_depth_in, d_colors_in, d_depth_out, d_colors_out, stream); });
 }
+
+// The flying-pixel filter, the per-sensor depth stage in front of this one, is compiled as part of this translation unit.
+#include "flying.hip"

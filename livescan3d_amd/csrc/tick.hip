@@ -21,6 +21,8 @@ struct LsnTick {
     int first[3] = {0, 0, 0};            // part k covers ticks [first[k], first[k + 1])
     long long cap = 0, tri_cap = 0;      // vertices / triangles per tick
     std::vector<float> intr;             // the radial correction's intrinsics (lsnTickSetParams)
+    int fp_neighbourhood = 0, fp_threshold = 0;   // the flying-pixel filter in front of the correction (lsnTickSetFlyingPixels; <= 0: off)
+    lsn::DevBuf d_filtered;              // ... and its output, [n_ticks][pixels per tick] u16: reserved by the first run that filters
     hipStream_t side = nullptr;
     hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_band = nullptr;
     std::mutex mu;
@@ -117,6 +119,24 @@ extern "C" int lsnTickSetParams(LsnTick *t, const float *intr, const float *wt, 
     return lsn::guarded<int>("lsnTickSetParams", static_cast<int>(-1), [&]() { return lsnTickSetParams_impl(t, intr, wt, bounds6, stream); });
 }
 
+static int lsnTickSetFlyingPixels_impl(LsnTick *t, int neighbourhood, int threshold)
+{
+    lsn::clear_error();
+    if (!t) {
+        lsn::set_error("lsnTickSetFlyingPixels: null argument");
+        return -1;
+    }
+    std::lock_guard<std::mutex> g(t->mu);
+    t->fp_neighbourhood = neighbourhood;
+    t->fp_threshold = threshold;
+    return 0;
+}
+
+extern "C" int lsnTickSetFlyingPixels(LsnTick *t, int neighbourhood, int threshold)
+{
+    return lsn::guarded<int>("lsnTickSetFlyingPixels", static_cast<int>(-1), [&]() { return lsnTickSetFlyingPixels_impl(t, neighbourhood, threshold); });
+}
+
 static int lsnTickRun_impl(LsnTick *t, const void *d_depth_in, const void *d_colors_in, void *d_depth_corr, void *d_colors_corr, void *d_vertices,
                            int *d_offsets, void *d_triangles, int *d_tri_offsets, void *stream)
 {
@@ -132,12 +152,23 @@ static int lsnTickRun_impl(LsnTick *t, const void *d_depth_in, const void *d_col
     std::lock_guard<std::mutex> g(t->mu);
     LSN_HIP(hipSetDevice(t->device));
     hipStream_t s = lsn::as_stream(stream);
+    const bool filter = t->fp_neighbourhood >= 1;
+    if (filter && t->d_filtered.reserve(2 * (size_t)t->cap * t->n_ticks + 16)) return -1;
     // part k's slices of the caller's arrays: [tick][pixels], [tick][pixels][3], [tick][capacity] vertices, [tick][n_maps + 1], ...
     auto part = [&](int k, hipStream_t st) -> int {
         const size_t t0 = (size_t)t->first[k];
         const size_t px = (size_t)t->cap, nm = (size_t)t->n_maps + 1;
         const unsigned char *din = static_cast<const unsigned char *>(d_depth_in) + 2 * px * t0, *cin = static_cast<const unsigned char *>(d_colors_in) + 3 * px * t0;
         unsigned char *dco = static_cast<unsigned char *>(d_depth_corr) + 2 * px * t0, *cco = static_cast<unsigned char *>(d_colors_corr) + 3 * px * t0;
+        if (filter) {   // filter -> correction: the filtered maps go through the tick's scratch, the caller's input stays as it is
+            unsigned char *dfl = t->d_filtered.as<unsigned char>() + 2 * px * t0;
+            // the scratch is shared by all runs of the tick object: a run on another stream than the previous one's waits until that
+            // run's correction has read it (the event radial.hip records behind every chain)
+            LsnFusion *pl = t->plan[k];
+            if (pl->radial_chain_open && pl->work_cnt_stream != st) LSN_HIP(hipStreamWaitEvent(st, pl->radial_done, 0));
+            if (lsn::flying_pixels(t->plan[k], t->fp_neighbourhood, t->fp_threshold, din, dfl, st)) return -1;
+            din = dfl;
+        }
         if (lsnFusionRadialCorrectTo(t->plan[k], t->intr.data(), din, cin, dco, cco, st)) return -1;
         return lsnFusionRunMesh(t->plan[k], dco, cco, static_cast<unsigned char *>(d_vertices) + 16 * px * t0, d_offsets + nm * t0,
                                 static_cast<unsigned char *>(d_triangles) + 12 * (size_t)t->tri_cap * t0, d_tri_offsets + nm * t0, st);

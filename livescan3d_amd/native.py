@@ -27,6 +27,7 @@ EXPORTS = [
     "lsnFusionRun", "lsnFusionRunStreamed", "lsnFusionSetPipelined", "lsnFusionRadialCorrect", "lsnFusionRadialCorrectTo", "lsnFusionRadialCountersLeft", "lsnFusionRunMesh", "lsnFusionTickTriangleCapacity", "lsnFusionProfile", "lsnFusionKernelStats", "lsnFusionLookbackFailed", "lsnFusionCheck", "lsnFusionThresholds", "lsnMergeShards",
     "lsnFusionColorTransfer", "lsnFusionColorDiagnostics", "lsnFusionOverlayMerge", "lsnFusionOverlayDiagnostics", "lsnSetOverlayMerge",
     "lsnFusionOutlierFilter", "lsnFusionOutlierDiagnostics", "lsnSetOutlierFilter",
+    "lsnFusionFlyingPixels", "lsnFusionFlyingDiagnostics", "lsnSetFlyingPixelFilter", "lsnTickSetFlyingPixels",
     "lsnFusionTilesPerTick", "lsnFusionPackSurvivors", "lsnFusionReconstruct",
     "lsnDeviceMalloc", "lsnDeviceFree", "lsnDeviceUpload", "lsnDeviceDownload", "lsnStreamCreate", "lsnStreamDestroy", "lsnStreamSynchronize",
     "lsnFusionPackSurvivorsRun", "lsnFusionReconstructRun", "lsnShardUniqueId", "lsnShardPlan", "lsnShardCreate", "lsnShardPrepare", "lsnShardConnect", "lsnShardRcclPath", "lsnShardDestroy", "lsnShardMergedCapacity", "lsnShardSetParams", "lsnShardStep", "lsnShardLastBytesSent", "lsnShardRanksSeen",
@@ -168,6 +169,15 @@ def lib():
         L.lsnFusionOutlierDiagnostics.argtypes = [vp, C.c_int, vp, vp, vp, vp]
         L.lsnSetOutlierFilter.restype = C.c_int
         L.lsnSetOutlierFilter.argtypes = [C.c_int, C.c_float, vp, vp]
+    if hasattr(L, "lsnSetFlyingPixelFilter"):   # (absent from an older build loaded through $LSN_NATIVE_LIB)
+        L.lsnFusionFlyingPixels.restype = C.c_int
+        L.lsnFusionFlyingPixels.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp]
+        L.lsnFusionFlyingDiagnostics.restype = C.c_int
+        L.lsnFusionFlyingDiagnostics.argtypes = [vp, C.c_int, vp, vp]
+        L.lsnSetFlyingPixelFilter.restype = C.c_int
+        L.lsnSetFlyingPixelFilter.argtypes = [C.c_int, C.c_int, vp, vp]
+        L.lsnTickSetFlyingPixels.restype = C.c_int
+        L.lsnTickSetFlyingPixels.argtypes = [vp, C.c_int, C.c_int]
     L.lsnMergeShards.restype = C.c_int
     L.lsnMergeShards.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_longlong, vp, vp, C.c_longlong, vp, vp]
     L.lsnIcpCreate.restype = vp
@@ -359,6 +369,29 @@ class _OutlierFilter:
             set_outlier_filter(*self.prev)
 
 
+def set_flying_pixel_filter(neighbourhood, threshold):
+    """lsnSetFlyingPixelFilter: the process-wide (neighbourhood, threshold) of the flying-pixel filter in the exports that start with the
+    radial correction (radial_correction, correct_and_generate_mesh); neighbourhood <= 0: off.  Returns the previous pair."""
+    pn, pt = C.c_int(0), C.c_int(0)
+    _check(lib().lsnSetFlyingPixelFilter(int(neighbourhood), int(threshold), C.byref(pn), C.byref(pt)), "lsnSetFlyingPixelFilter")
+    return pn.value, pt.value
+
+
+class _FlyingPixels:
+    """Sets the process-wide flying-pixel filter for the body of a with-statement (None: leaves it as it is)."""
+
+    def __init__(self, setting):
+        self.setting, self.prev = setting, None
+
+    def __enter__(self):
+        if self.setting is not None:
+            self.prev = set_flying_pixel_filter(*self.setting)
+
+    def __exit__(self, *exc):
+        if self.prev is not None:
+            set_flying_pixel_filter(*self.prev)
+
+
 def generate_mesh_from_depth_maps(depth_maps, depth_colors, widths, heights, intr, wt, bounds,
                                   color_transfer=False, generate_triangles=False, overlay_merge=None, outlier_filter=None):
     """KinectServer.GenerateMesh (KinectServer.cs:354-374).  Returns (vertices[VERTEX_DTYPE], triangles int32).
@@ -430,9 +463,14 @@ def host_schedule(widths, heights, first=0, count=None, radial=False, sensors_pe
     return g, buf.value.decode()
 
 
-def radial_correction(depth_maps, depth_colors, widths, heights, intr):
+def radial_correction(depth_maps, depth_colors, widths, heights, intr, flying_pixels=None):
     """KinectServer.CorrectRadialDistortionsForDepthMaps (KinectServer.cs:518-525): returns corrected copies
-    (depth as a uint8 view of the u16 maps, colours); the export itself works in place on the arrays it is given."""
+    (depth as a uint8 view of the u16 maps, colours); the export itself works in place on the arrays it is given.
+    flying_pixels: None leaves the process-wide flying-pixel filter (lsnSetFlyingPixelFilter) as it is; (neighbourhood, threshold) sets
+    it for this call alone (the maps are filtered, then corrected)."""
+    if flying_pixels is not None:
+        with _FlyingPixels(flying_pixels):
+            return radial_correction(depth_maps, depth_colors, widths, heights, intr)
     require_gpu()
     widths, heights = _as(widths, np.int32), _as(heights, np.int32)
     n = len(widths)
@@ -447,10 +485,15 @@ def radial_correction(depth_maps, depth_colors, widths, heights, intr):
     return dm, dc
 
 
-def correct_and_generate_mesh(depth_maps, depth_colors, widths, heights, intr, wt, bounds, write_back=True, outlier_filter=None):
+def correct_and_generate_mesh(depth_maps, depth_colors, widths, heights, intr, wt, bounds, write_back=True, outlier_filter=None,
+                              flying_pixels=None):
     """One call per tick (extension): radial correction + merge call with a single upload.  Returns (vertices, triangles,
     corrected depth as uint8, corrected colours); with write_back=False the last two are the untouched inputs.
-    outlier_filter: as for generate_mesh_from_depth_maps (the corrected maps written back are the unmasked ones)."""
+    outlier_filter: as for generate_mesh_from_depth_maps (the corrected maps written back are the unmasked ones).
+    flying_pixels: as for radial_correction (the corrected maps written back are the filtered, corrected ones)."""
+    if flying_pixels is not None:
+        with _FlyingPixels(flying_pixels):
+            return correct_and_generate_mesh(depth_maps, depth_colors, widths, heights, intr, wt, bounds, write_back, outlier_filter)
     if outlier_filter is not None:
         with _OutlierFilter(outlier_filter):
             return correct_and_generate_mesh(depth_maps, depth_colors, widths, heights, intr, wt, bounds, write_back)
@@ -640,6 +683,20 @@ class FusionPlan:
         return {"removed_per_sensor": rps[:self.n_maps].copy(), "removed": rem[:nv].copy(), "exact_per_sensor": eps[:self.n_maps].copy(),
                 "total": k}
 
+    def flying_pixels(self, neighbourhood, threshold, d_depth_in, d_depth_out, stream=0):
+        """Flying-pixel filter on every map of the plan, d_depth_in into d_depth_out (out of place: overlapping buffers are refused;
+        neighbourhood <= 0 copies).  Run radial_correct_to() / run() on d_depth_out next."""
+        _check(lib().lsnFusionFlyingPixels(self._h, int(neighbourhood), int(threshold), d_depth_in, d_depth_out, stream or None),
+               "lsnFusionFlyingPixels")
+
+    def flying_diagnostics(self, tick=0, stream=0):
+        """What the last flying_pixels() removed in one tick: (pixels of depth != 0 set to 0 per sensor int32[n], their sum)."""
+        rps = np.zeros(max(self.n_maps, 1), dtype=np.int32)
+        k = lib().lsnFusionFlyingDiagnostics(self._h, int(tick), _ptr(rps), stream or None)
+        if k < 0:
+            raise NativeUtilsError(f"lsnFusionFlyingDiagnostics failed: {last_error()}")
+        return rps[:self.n_maps].copy(), k
+
     def thresholds(self, capacity=None, stream=0, copy=True):
         """Builds the per-pixel depth thresholds now.  Returns (table uint32[capacity] or None, build_ms); table is None when
         the plan does not use thresholds ($LSN_NO_THRESHOLDS=1)."""
@@ -812,6 +869,11 @@ class TickPipeline:
         intr, wt, bounds = _as(intr, np.float32).ravel(), _as(wt, np.float32).ravel(), _as(bounds, np.float32).ravel()
         assert intr.size == 7 * self.n_maps and wt.size == 12 * self.n_maps and bounds.size == 6
         _check(lib().lsnTickSetParams(self._h, _ptr(intr), _ptr(wt), _ptr(bounds), stream), "lsnTickSetParams")
+
+    def set_flying_pixels(self, neighbourhood, threshold):
+        """The flying-pixel filter as the first stage of run() (neighbourhood <= 0: off): filter -> radial correction -> vertices ->
+        triangles; d_depth_corr then receives the filtered and corrected maps."""
+        _check(lib().lsnTickSetFlyingPixels(self._h, int(neighbourhood), int(threshold)), "lsnTickSetFlyingPixels")
 
     def run(self, d_depth_in, d_colors_in, d_depth_corr, d_colors_corr, d_vertices, d_offsets, d_triangles, d_tri_offsets, stream=0):
         _check(lib().lsnTickRun(self._h, d_depth_in, d_colors_in, d_depth_corr, d_colors_corr, d_vertices, d_offsets, d_triangles, d_tri_offsets, stream),

@@ -1,0 +1,176 @@
+#!/usr/bin/env python3
+"""Timing of the flying-pixel filter (flying.hip).  Three modes, one JSON line each:
+
+  --kernel   lsnFusionFlyingPixels alone on batches in HBM, r = 1, 2, 3 (HIP events, median of `reps`): 64 scene ticks x 8 x 512x424 and
+             8 ticks x 16 x 1024x1024; algorithmic bytes = 4 B per pixel, reported as GB/s and as a share of 8 TB/s.  The same process
+             also runs lsnFusionRun on the first batch, so that a `rocprofv3 --kernel-trace --stats` run of this mode shows
+             count_thr_kernel and fuse_kernel<1> beside flying_kernel<R, true>.
+  --flows    lsnTickRun on 64 scene ticks x 8 x 512x424 (ticks/s, median of `reps` timed runs of `calls` calls) and one
+             lsnCorrectAndGenerateMesh host call on 8 x 512x424 (ms, median of `host_calls` calls), with the switch off and -- when the
+             loaded library has it -- at (1, 20).
+  --ab LIB   "switch off costs nothing": runs `--flows --off-only` in fresh child processes, alternating between this tree's library and
+             LIB (the parent commit's libNativeUtils.so, through $LSN_NATIVE_LIB), `pairs` times each, and reports both medians, the
+             parent's own run-to-run spread (max - min) and whether the difference of the medians lies within it.
+
+    python tools/flying_timing.py --kernel [reps]
+    python tools/flying_timing.py --flows [reps] [calls] [host_calls]
+    python tools/flying_timing.py --ab path/to/parent/libNativeUtils.so [pairs]
+
+The 64-tick batches are 8 distinct scene ticks repeated 8 times (the timing does not care, the ray casting on the CPU does)."""
+import json
+import os
+import statistics
+import subprocess
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+from livescan3d_amd import native, synth  # noqa: E402
+
+HBM_PEAK = 8.0e12
+
+
+def _scene_batch(n_ticks, n, w, h, distinct=8):
+    rigs = [synth.make_rig("scene", n, w, h, seed=1, tick=t) for t in range(min(distinct, n_ticks))]
+    return rigs[0], np.stack([rigs[t % len(rigs)].depth_maps.view(np.int16) for t in range(n_ticks)]), \
+        np.stack([rigs[t % len(rigs)].depth_colors for t in range(n_ticks)])
+
+
+def _events(torch, fn, reps):
+    ms = []
+    for _ in range(reps + 2):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        fn()
+        e1.record()
+        torch.cuda.synchronize()
+        ms.append(e0.elapsed_time(e1))
+    return statistics.median(ms[2:])
+
+
+def kernel(reps):
+    import torch
+    res = {"mode": "kernel", "reps": reps}
+    for name, (T, n, w, h) in {"64x8x512x424": (64, 8, 512, 424), "8x16x1024x1024": (8, 16, 1024, 1024)}.items():
+        rig, depth, rgb = _scene_batch(T, n, w, h, distinct=8 if w == 512 else 2)
+        plan = native.FusionPlan(0, T, rig.widths, rig.heights)
+        plan.set_params(rig.intr, rig.wt, rig.bounds)
+        d_in, c_in = torch.from_numpy(depth).cuda(), torch.from_numpy(rgb).cuda()
+        d_out = torch.empty_like(d_in)
+        st = int(torch.cuda.current_stream().cuda_stream)
+        nbytes = 4.0 * d_in.numel()
+        res[f"{name}_MB"] = round(nbytes / 1e6, 1)
+        for r in (1, 2, 3):
+            ms = _events(torch, lambda: plan.flying_pixels(r, 20, d_in.data_ptr(), d_out.data_ptr(), st), reps)
+            res[f"{name}_r{r}_ms"] = round(ms, 4)
+            res[f"{name}_r{r}_GBps"] = round(nbytes / ms / 1e6, 1)
+            res[f"{name}_r{r}_share_of_8TBps"] = round(nbytes / (ms * 1e-3) / HBM_PEAK, 3)
+        res[f"{name}_removed_tick0_r3"] = int(plan.flying_diagnostics(0)[1])
+        if w == 512:   # the project's own streaming kernels in the same run (count_thr_kernel from the third run on, fuse_kernel<1>)
+            verts = torch.zeros((T, plan.capacity, 16), dtype=torch.uint8, device="cuda")
+            off = torch.zeros((T, n + 1), dtype=torch.int32, device="cuda")
+            res[f"{name}_fusion_run_ms"] = round(_events(torch, lambda: plan.run(d_in.data_ptr(), c_in.data_ptr(), verts.data_ptr(), off.data_ptr(), st), reps + 2), 4)
+        plan.close()
+        del d_in, c_in, d_out
+    print(json.dumps(res))
+
+
+def flows(reps, calls, host_calls, off_only):
+    import ctypes as C
+    import torch
+    L = native.lib()
+    has = hasattr(L, "lsnSetFlyingPixelFilter")
+    res = {"mode": "flows", "library": os.environ.get("LSN_NATIVE_LIB", "in-tree"), "has_filter": has, "reps": reps, "calls": calls}
+    T, n, w, h = 64, 8, 512, 424
+    rig, depth, rgb = _scene_batch(T, n, w, h)
+    tp = native.TickPipeline(0, T, rig.widths, rig.heights)
+    tp.set_params(rig.intr, rig.wt, rig.bounds)
+    d_in, c_in = torch.from_numpy(depth).cuda(), torch.from_numpy(rgb).cuda()
+    d_co, c_co = torch.empty_like(d_in), torch.empty_like(c_in)
+    verts = torch.zeros((T, tp.capacity, 16), dtype=torch.uint8, device="cuda")
+    off = torch.zeros((T, n + 1), dtype=torch.int32, device="cuda")
+    tri = torch.zeros((T, tp.tri_capacity, 3), dtype=torch.int32, device="cuda")
+    toff = torch.zeros((T, n + 1), dtype=torch.int32, device="cuda")
+    st = int(torch.cuda.current_stream().cuda_stream)
+
+    def tick_rate():
+        rates = []
+        for i in range(reps + 1):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(calls):
+                tp.run(d_in.data_ptr(), c_in.data_ptr(), d_co.data_ptr(), c_co.data_ptr(), verts.data_ptr(), off.data_ptr(), tri.data_ptr(), toff.data_ptr(), st)
+            torch.cuda.synchronize()
+            rates.append(T * calls / (time.perf_counter() - t0))
+        return rates[1:]
+
+    def host_ms():
+        p = lambda a: a.ctypes.data_as(C.c_void_p)
+        b = [float(x) for x in rig.bounds]
+        t = []
+        for _ in range(host_calls + 3):
+            dm, dc = rig.depth_maps.copy(), rig.depth_colors.copy()
+            m = native.Mesh()
+            t0 = time.perf_counter()
+            L.lsnCorrectAndGenerateMesh(rig.n, p(dm), p(dc), p(rig.widths), p(rig.heights), p(rig.intr), p(rig.wt), C.byref(m), *b, 1)
+            L.deleteMesh(C.byref(m))
+            t.append((time.perf_counter() - t0) * 1e3)
+        assert native.last_error() == ""
+        return t[3:]
+
+    for label, setting in [("off", None)] + ([("on_1_20", (1, 20))] if has and not off_only else []):
+        if setting:
+            tp.set_flying_pixels(*setting)
+            prev = native.set_flying_pixel_filter(*setting)
+        r = tick_rate()
+        res[f"tick_run_ticks_per_s_{label}"] = round(statistics.median(r), 1)
+        res[f"tick_run_ticks_per_s_{label}_min_max"] = [round(min(r), 1), round(max(r), 1)]
+        res[f"tick_run_vertices_tick0_{label}"] = int(off[0, -1].item())
+        hm = host_ms()
+        res[f"host_call_ms_{label}"] = round(statistics.median(hm), 4)
+        res[f"host_call_ms_{label}_min_max"] = [round(min(hm), 4), round(max(hm), 4)]
+        if setting:
+            native.set_flying_pixel_filter(*prev)
+    tp.close()
+    print(json.dumps(res))
+
+
+def ab(parent_lib, pairs):
+    runs = {"this": [], "parent": []}
+    for i in range(pairs):
+        for who in ("parent", "this") if i % 2 else ("this", "parent"):
+            env = {k: v for k, v in os.environ.items() if k not in ("LSN_NATIVE_LIB", "LSN_FLYING_PIXELS")}
+            if who == "parent":
+                env["LSN_NATIVE_LIB"] = os.path.abspath(parent_lib)
+            r = subprocess.run([sys.executable, os.path.abspath(__file__), "--flows", "--off-only", "5", "20", "30"], env=env, cwd=ROOT,
+                               capture_output=True, text=True, timeout=600)
+            if r.returncode != 0:
+                sys.exit(f"child ({who}) failed with {r.returncode}: {r.stderr[-1500:]}")
+            runs[who].append(json.loads(r.stdout.strip().splitlines()[-1]))
+    res = {"mode": "ab", "pairs": pairs, "parent_has_filter": runs["parent"][0]["has_filter"], "this_has_filter": runs["this"][0]["has_filter"]}
+    for key in ("tick_run_ticks_per_s_off", "host_call_ms_off"):
+        a, b = [x[key] for x in runs["this"]], [x[key] for x in runs["parent"]]
+        spread = max(b) - min(b)
+        diff = statistics.median(a) - statistics.median(b)
+        res[key] = {"this": a, "parent": b, "median_this": statistics.median(a), "median_parent": statistics.median(b),
+                    "difference_of_medians": round(diff, 4), "parent_spread": round(spread, 4), "within_parent_spread": abs(diff) <= spread}
+    print(json.dumps(res))
+
+
+def main():
+    args = [a for a in sys.argv[1:] if not a.startswith("--")]
+    if "--ab" in sys.argv:
+        return ab(args[0], int(args[1]) if len(args) > 1 else 5)
+    native.require_gpu()
+    if "--kernel" in sys.argv:
+        return kernel(int(args[0]) if args else 10)
+    reps, calls, host_calls = (int(args[i]) if len(args) > i else d for i, d in enumerate((5, 20, 30)))
+    return flows(reps, calls, host_calls, "--off-only" in sys.argv)
+
+
+if __name__ == "__main__":
+    main()
