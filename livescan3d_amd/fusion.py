@@ -4,56 +4,159 @@ import torch
 
 from . import native
 
+SENTINEL = -7   # prefill of both offset tables: no legal offset, so an entry that was never written shows
+
 
 def _stream_handle(stream=None):
     s = stream if stream is not None else torch.cuda.current_stream()
     return int(s.cuda_stream)
 
 
+def _device(device=None):
+    return torch.device("cuda", torch.cuda.current_device() if device is None else device)
+
+
 class DeviceFusion:
-    """T ticks x N sensors -> T merged clouds, inputs and outputs resident in HBM.
+    """T ticks x N sensors -> T merged clouds (and meshes), inputs and outputs resident in HBM: the one device batch of the tests and tools.
 
     depth: torch.int16 / uint16-bit-pattern tensor [T, sum(w*h)] (or any shape with that many u16 per tick),
-    rgb:   torch.uint8 tensor [T, sum(w*h)*3].  Outputs: vertices torch.uint8 [T, capacity, 16] viewed as
-    VertexC4ubV3f, offsets torch.int32 [T, N+1] (offsets[k, i] = first vertex of sensor i, offsets[k, N] = nVertices).
-    """
+    rgb:   torch.uint8 tensor [T, sum(w*h)*3]; from_rigs() uploads them, and every launch takes another pair in their place.
+    Outputs, owned by the object: vertices torch.uint8 [T, capacity, 16] viewed as VertexC4ubV3f, offsets torch.int32 [T, N+1]
+    (offsets[k, i] = first vertex of sensor i, offsets[k, N] = nVertices); triangles torch.int32 [T, 2*capacity, 3] and tri_offsets
+    [T, N+1], allocated when first needed.  Both offset tables are prefilled with SENTINEL.  The methods launch on the current stream (or
+    `stream`, a torch stream) and return at once; the host views at the end synchronise.  Nothing here checks a result."""
 
     def __init__(self, n_ticks, widths, heights, device=None, mode=0):
         if not torch.cuda.is_available():
             raise native.NativeUtilsError("DeviceFusion needs a HIP device (no CPU path)")
-        self.device = torch.device("cuda", torch.cuda.current_device() if device is None else device)
+        self.device = _device(device)
         self.plan = native.FusionPlan(self.device.index, n_ticks, widths, heights)
         self.plan.set_mode(mode)
         self.n_ticks, self.n_maps = n_ticks, self.plan.n_maps
         self.capacity = self.plan.capacity
+        # (not cleared here: the benchmark and the drivers construct their plans this way; from_rigs() clears them)
         self.vertices = torch.empty((n_ticks, self.capacity, 16), dtype=torch.uint8, device=self.device)
-        self.offsets = torch.zeros((n_ticks, self.n_maps + 1), dtype=torch.int32, device=self.device)
+        self.offsets = torch.full((n_ticks, self.n_maps + 1), SENTINEL, dtype=torch.int32, device=self.device)
+        self.depth = self.rgb = self.intr = self._triangles = self._tri_offsets = None
+
+    @classmethod
+    def from_rigs(cls, rigs, n_ticks=None, device=None, mode=0):
+        """A plan of n_ticks (default len(rigs)) ticks of rigs[0]'s sizes with rigs[k % len(rigs)] uploaded as tick k and the vertices
+        cleared.  One calibration for the plan: intr, wt and bounds are rigs[0]'s, whatever the other rigs carry."""
+        self = cls(len(rigs) if n_ticks is None else n_ticks, rigs[0].widths, rigs[0].heights, device, mode)
+        self.set_params(rigs[0].intr, rigs[0].wt, rigs[0].bounds)
+        self.depth, self.rgb = upload_rigs(rigs, self.n_ticks, self.device.index)
+        self.vertices.zero_()
+        return self
 
     @property
     def tiles_per_tick(self):
         return self.plan.tiles_per_tick
 
+    def _mesh(self):
+        if self._triangles is None:
+            self._triangles = torch.zeros((self.n_ticks, 2 * self.capacity, 3), dtype=torch.int32, device=self.device)
+            self._tri_offsets = torch.full((self.n_ticks, self.n_maps + 1), SENTINEL, dtype=torch.int32, device=self.device)
+        return self._triangles, self._tri_offsets
+
+    @property
+    def triangles(self):
+        return self._mesh()[0]
+
+    @property
+    def tri_offsets(self):
+        return self._mesh()[1]
+
     def set_params(self, intr, wt, bounds):
+        self.intr = intr
         self.plan.set_params(intr, wt, bounds, _stream_handle())
 
-    def run(self, depth, rgb, stream=None):
+    def _in(self, depth, rgb=None):
+        """The data pointers of the inputs of a launch: the tensors handed in, else the uploaded ticks."""
+        return (self.depth if depth is None else depth).data_ptr(), (self.rgb if rgb is None else rgb).data_ptr()
+
+    def run(self, depth=None, rgb=None, stream=None):
+        depth, rgb = self.depth if depth is None else depth, self.rgb if rgb is None else rgb
         assert depth.is_cuda and rgb.is_cuda and depth.is_contiguous() and rgb.is_contiguous()
         assert depth.element_size() == 2 and depth.numel() == self.n_ticks * self.plan.pixels_per_tick, depth.shape
         assert rgb.dtype == torch.uint8 and rgb.numel() == self.n_ticks * self.plan.pixels_per_tick * 3, rgb.shape
         self.plan.run(depth.data_ptr(), rgb.data_ptr(), self.vertices.data_ptr(), self.offsets.data_ptr(), _stream_handle(stream))
         return self.vertices, self.offsets
 
+    def run_mesh(self, depth=None, rgb=None, stream=None):
+        self.plan.run_mesh(*self._in(depth, rgb), self.vertices.data_ptr(), self.offsets.data_ptr(), self.triangles.data_ptr(),
+                           self.tri_offsets.data_ptr(), _stream_handle(stream))
+
+    def radial_correct(self, depth=None, rgb=None, stream=None, intr=None):
+        """In place, on the uploaded ticks unless another pair is handed in; intr: the plan's unless given."""
+        self.plan.radial_correct(self.intr if intr is None else intr, *self._in(depth, rgb), _stream_handle(stream))
+
+    def radial_correct_to(self, depth_out, rgb_out, depth=None, rgb=None, stream=None, intr=None):
+        self.plan.radial_correct_to(self.intr if intr is None else intr, *self._in(depth, rgb), depth_out.data_ptr(), rgb_out.data_ptr(),
+                                    _stream_handle(stream))
+
+    def color_transfer(self, depth=None, stream=None):
+        self.plan.color_transfer(self._in(depth)[0], self.vertices.data_ptr(), self.offsets.data_ptr(), _stream_handle(stream))
+
+    def overlay_merge(self, depth=None, stream=None):
+        self.plan.overlay_merge(self._in(depth)[0], self.vertices.data_ptr(), self.offsets.data_ptr(), self.triangles.data_ptr(),
+                                self.tri_offsets.data_ptr(), _stream_handle(stream))
+
+    def outlier_filter(self, k, max_dist, depth_out, depth=None, stream=None):
+        self.plan.outlier_filter(k, max_dist, self._in(depth)[0], self.vertices.data_ptr(), self.offsets.data_ptr(), depth_out.data_ptr(),
+                                 _stream_handle(stream))
+
+    def flying_pixels(self, neighbourhood, threshold, depth_out, depth=None, stream=None):
+        self.plan.flying_pixels(neighbourhood, threshold, self._in(depth)[0], depth_out.data_ptr(), _stream_handle(stream))
+
+    # ---- host views (each synchronises the device first) ----
+
+    def host_offsets(self):
+        """offsets [T, N+1] as a numpy array."""
+        torch.cuda.synchronize(self.device)
+        return self.offsets.cpu().numpy()
+
+    def host_tri_offsets(self):
+        torch.cuda.synchronize(self.device)
+        return self.tri_offsets.cpu().numpy()
+
+    def tick_bytes(self, k):
+        """Host copy of tick k's merged cloud as uint8 [nVertices, 16]."""
+        torch.cuda.synchronize(self.device)
+        return self.vertices[k, :int(self.offsets[k, -1])].cpu().numpy()
+
     def tick_cloud(self, k):
-        """Host copy of tick k's merged cloud as a VERTEX_DTYPE array (synchronises)."""
-        off = self.offsets[k].cpu().numpy()
-        n = int(off[-1])
-        raw = self.vertices[k, :n].cpu().numpy()
-        return raw.view(native.VERTEX_DTYPE).reshape(-1), off
+        """Host copy of tick k's merged cloud as a VERTEX_DTYPE array, and its offsets."""
+        return self.tick_bytes(k).view(native.VERTEX_DTYPE).reshape(-1), self.offsets[k].cpu().numpy()
+
+    def tick_triangles(self, k):
+        """Host copy of tick k's triangles int32 [nTriangles, 3], cut at tri_offsets[k, -1]."""
+        torch.cuda.synchronize(self.device)
+        return self.triangles[k, :int(self.tri_offsets[k, -1])].cpu().numpy()
+
+    def close(self):
+        self.plan.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+def stack_rigs(rigs, n_ticks=None):
+    """Rigs (synth.Rig) -> (depth int16 [T, P], rgb uint8 [T, 3P]) as numpy arrays; tick k is rigs[k % len(rigs)], T = len(rigs) unless given."""
+    T = len(rigs) if n_ticks is None else n_ticks
+    return (np.stack([np.ascontiguousarray(rigs[k % len(rigs)].depth_maps).view(np.int16) for k in range(T)]),
+            np.stack([np.ascontiguousarray(rigs[k % len(rigs)].depth_colors) for k in range(T)]))
+
+
+def upload_rigs(rigs, n_ticks=None, device=None):
+    """stack_rigs() on the GPU."""
+    d, c = stack_rigs(rigs, n_ticks)
+    return torch.from_numpy(d).to(_device(device)), torch.from_numpy(c).to(_device(device))
 
 
 def upload_rig(rig, n_ticks=1, device=None):
-    """Rig (synth.Rig) -> (depth int16 [T, P], rgb uint8 [T, 3P]) on the GPU, the same tick replicated T times."""
-    dev = torch.device("cuda", torch.cuda.current_device() if device is None else device)
-    d = torch.from_numpy(rig.depth_maps.view(np.int16).copy()).to(dev)
-    c = torch.from_numpy(rig.depth_colors.copy()).to(dev)
-    return d.unsqueeze(0).repeat(n_ticks, 1).contiguous(), c.unsqueeze(0).repeat(n_ticks, 1).contiguous()
+    """One rig, the same tick replicated n_ticks times."""
+    return upload_rigs([rig], n_ticks, device)

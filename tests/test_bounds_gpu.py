@@ -10,32 +10,12 @@ import numpy as np
 import pytest
 
 from livescan3d_amd import native, synth
+from tests.support import Guarded
 
 pytestmark = pytest.mark.gpu
 
-GUARD = 4096
-PATTERN = 0xA5
-
 UNIFORM = [(512, 424)] * 3
 RAGGED = [(61, 37), (512, 424), (100, 3), (7, 5), (2049, 1), (64, 48), (129, 65)]
-
-
-class Guarded:
-    """`nbytes` of device memory with GUARD pattern bytes either side."""
-
-    def __init__(self, torch, nbytes, dev):
-        self.torch, self.n = torch, int(nbytes)
-        self.buf = torch.full((GUARD + self.n + GUARD,), PATTERN, dtype=torch.uint8, device=dev)
-
-    @property
-    def ptr(self):
-        return self.buf.data_ptr() + GUARD
-
-    def body(self):
-        return self.buf[GUARD:GUARD + self.n]
-
-    def intact(self):
-        return bool((self.buf[:GUARD] == PATTERN).all().item()) and bool((self.buf[GUARD + self.n:] == PATTERN).all().item())
 
 
 def _rig(sizes, seed, kind):
@@ -58,14 +38,14 @@ def torch_dev(gpu):
 @pytest.mark.parametrize("sizes,kind,ticks", [(UNIFORM, "scene", 1), (UNIFORM, "noise", 3), (RAGGED, "scene", 1), (RAGGED, "noise", 2)],
                          ids=["uniform-scene-1", "uniform-noise-3", "ragged-scene-1", "ragged-noise-2"])
 def test_fusion_mesh_and_radial_stay_inside_their_buffers(torch_dev, orc, sizes, kind, ticks):
+    from livescan3d_amd.fusion import upload_rig
     torch, dev = torch_dev
     rig = _rig(sizes, 21, kind)
     S = len(sizes)
     plan = native.FusionPlan(0, ticks, rig.widths, rig.heights)
     cap, P = plan.capacity, plan.pixels_per_tick
     plan.set_params(rig.intr, rig.wt, rig.bounds)
-    depth = torch.from_numpy(rig.depth_maps.view(np.int16).copy()).to(dev).unsqueeze(0).repeat(ticks, 1).contiguous()
-    rgb = torch.from_numpy(rig.depth_colors.copy()).to(dev).unsqueeze(0).repeat(ticks, 1).contiguous()
+    depth, rgb = upload_rig(rig, ticks, 0)
     want_v, _, want_t = orc.generate_mesh(rig.depth_maps, rig.depth_colors, rig.widths, rig.heights, rig.intr, rig.wt, rig.bounds)
 
     # ---- lsnFusionRun ----

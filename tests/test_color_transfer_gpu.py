@@ -7,16 +7,9 @@ import pytest
 
 from livescan3d_amd import native, synth
 from tests import color_cases, color_ref
+from tests.support import CUT_BOUNDS, export
 
 pytestmark = pytest.mark.gpu
-
-CUT_BOUNDS = np.array([-0.3, -1.0, -1.5, 1.5, 1.5, 1.5], dtype=np.float32)   # through the sphere, inside the views' overlap
-
-
-def _export(rig, color, tri=False):
-    v, t = native.generate_mesh_from_depth_maps(rig.depth_maps, rig.depth_colors, rig.widths, rig.heights, rig.intr, rig.wt, rig.bounds,
-                                                color_transfer=color, generate_triangles=tri)
-    return v, t, native.last_error()
 
 
 def _xyz(v):
@@ -24,8 +17,8 @@ def _xyz(v):
 
 
 def _check_export(rig, orc, expect_change):
-    plain, t0, e0 = _export(rig, False)
-    got, t1, e1 = _export(rig, True)
+    plain, t0, e0 = export(rig)
+    got, t1, e1 = export(rig, color_transfer=True)
     want, diag = color_ref.color_transfer(rig, orc)
     assert e0 == "" and e1 == "", (e0, e1)
     assert len(got) == len(plain) == len(want)
@@ -102,30 +95,20 @@ def test_tiny_and_odd_frames(gpu, orc):
         _check_export(color_cases.ring(len(sizes), sizes=sizes, of=8), orc, None)
 
 
-def _device_run(rigs, color=True):
+def _device_run(rigs):
+    """run_mesh over a batch of ticks, then the colour transfer; synchronised."""
     import torch
-    T = len(rigs)
-    plan = native.FusionPlan(0, T, rigs[0].widths, rigs[0].heights)
-    plan.set_params(rigs[0].intr, rigs[0].wt, rigs[0].bounds)
-    depth = torch.from_numpy(np.stack([r.depth_maps.view(np.int16) for r in rigs])).cuda()
-    rgb = torch.from_numpy(np.stack([r.depth_colors for r in rigs])).cuda()
-    N, cap = rigs[0].n, plan.capacity
-    verts = torch.zeros((T, cap, 16), dtype=torch.uint8, device="cuda")
-    off = torch.zeros((T, N + 1), dtype=torch.int32, device="cuda")
-    tri = torch.zeros((T, 2 * cap, 3), dtype=torch.int32, device="cuda")
-    toff = torch.zeros((T, N + 1), dtype=torch.int32, device="cuda")
-    st = int(torch.cuda.current_stream().cuda_stream)
-    plan.run_mesh(depth.data_ptr(), rgb.data_ptr(), verts.data_ptr(), off.data_ptr(), tri.data_ptr(), toff.data_ptr(), st)
-    if color:
-        plan.color_transfer(depth.data_ptr(), verts.data_ptr(), off.data_ptr(), st)
+    from livescan3d_amd.fusion import DeviceFusion
+    fus = DeviceFusion.from_rigs(rigs)
+    fus.run_mesh()
+    fus.color_transfer()
     torch.cuda.synchronize()
-    return plan, verts.cpu().numpy(), off.cpu().numpy()
+    return fus
 
 
 def test_diagnostics_match_reference(gpu, orc):
     rig = color_cases.ring(8)
-    plan, _, _ = _device_run([rig])
-    d = plan.color_diagnostics(0)
+    d = _device_run([rig]).plan.color_diagnostics(0)
     _, want = color_ref.color_transfer(rig, orc)
     assert np.array_equal(d["confidence"], want["confidence"])
     assert np.array_equal(d["coverage"], want["coverage"])
@@ -139,8 +122,7 @@ def test_confidence_shift_x_frames(gpu):
     intr = np.concatenate([synth.kinect_intrinsics(64, 48)] * 2)
     wt = np.concatenate([synth.pack_pose(*synth.ring_pose(0, 8))] * 2)
     rig = synth.Rig([a, b], [np.zeros((48, 64, 3), np.uint8)] * 2, intr, wt, synth.DEFAULT_BOUNDS)
-    plan, _, _ = _device_run([rig])
-    conf = plan.color_diagnostics(0)["confidence"]
+    conf = _device_run([rig]).plan.color_diagnostics(0)["confidence"]
     assert np.array_equal(conf[:64 * 48].reshape(48, 64), color_ref.confidence_map(a))
     assert np.array_equal(conf[64 * 48:].reshape(48, 64), color_ref.confidence_map(b))
 
@@ -149,22 +131,23 @@ def test_device_batch_equals_export_calls(gpu):
     """lsnFusionColorTransfer over a 16-tick batch: every tick equals its own export call."""
     T = 16
     rigs = [color_cases.ring(8, tick=k, seed=1 + k % 3, sizes=[(256, 212)] * 8) for k in range(T)]
-    for r in rigs[1:]:   # one calibration for the plan
+    for r in rigs[1:]:   # the export calls below: with the plan's calibration (rigs[0]'s)
         r.intr, r.wt, r.bounds = rigs[0].intr, rigs[0].wt, rigs[0].bounds
-    _, verts, off = _device_run(rigs)
-    for k in range(T):
-        want, _, err = _export(rigs[k], True)
-        nv = int(off[k, -1])
-        assert err == "" and nv == len(want)
-        assert verts[k, :nv].tobytes() == want.tobytes(), k
+    with _device_run(rigs) as fus:
+        off = fus.host_offsets()
+        for k in range(T):
+            want, _, err = export(rigs[k], color_transfer=True)
+            nv = int(off[k, -1])
+            assert err == "" and nv == len(want)
+            assert fus.tick_bytes(k).tobytes() == want.tobytes(), k
 
 
 def test_overlay_merge_flag_still_reports(gpu, orc):
     """bgenerate_triangles = true: the message stays as it was; the colour transfer is applied when its own flag is set."""
     rig = color_cases.ring(4, sizes=[(256, 212)] * 4, of=8)
-    v0, t0, e0 = _export(rig, False, tri=True)
+    v0, t0, e0 = export(rig, generate_triangles=True)
     assert "overlay merge are outside this library's scope" in e0
-    v1, t1, e1 = _export(rig, True, tri=True)
+    v1, t1, e1 = export(rig, color_transfer=True, generate_triangles=True)
     assert e1 == e0
     want, diag = color_ref.color_transfer(rig, orc)
     assert diag["pairs"] and v1.tobytes() == want.tobytes() and t1.tobytes() == t0.tobytes()

@@ -19,8 +19,7 @@ import pytest
 
 from livescan3d_amd import synth
 from tests import color_ref, export_cases, merge_ref
-from tests.test_oracle_depth import numpy_create_vertices
-from tests.test_oracle_radial import py_radial
+from tests.depth_ref import numpy_create_vertices, py_radial
 
 GOLDEN = export_cases.GOLDEN
 NPZ = os.path.join(GOLDEN, "export_ref.npz")

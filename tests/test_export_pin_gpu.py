@@ -100,52 +100,27 @@ def test_host_radial_export_matches_the_reference(gpu, name):
     same(name, "radial_colors", c, want)
 
 
-def _stack(rigs):
-    import torch
-    depth = torch.from_numpy(np.stack([np.ascontiguousarray(r.depth_maps).view(np.int16) for r in rigs])).cuda()
-    rgb = torch.from_numpy(np.stack([np.ascontiguousarray(r.depth_colors) for r in rigs])).cuda()
-    return depth, rgb
-
-
 def _plan_mesh(rigs, ct, tri):
     """run_mesh over the stacked ticks, then colour transfer and the overlay merge in the reference's order.
     Returns per tick (vertex bytes, offsets, triangles)."""
-    import torch
-    T, N = len(rigs), rigs[0].n
-    plan = native.FusionPlan(0, T, rigs[0].widths, rigs[0].heights)
-    plan.set_params(rigs[0].intr, rigs[0].wt, rigs[0].bounds)
-    depth, rgb = _stack(rigs)
-    cap = plan.capacity
-    verts = torch.zeros((T, cap, 16), dtype=torch.uint8, device="cuda")
-    off = torch.full((T, N + 1), -7, dtype=torch.int32, device="cuda")
-    tris = torch.zeros((T, 2 * cap, 3), dtype=torch.int32, device="cuda")
-    toff = torch.full((T, N + 1), -7, dtype=torch.int32, device="cuda")
-    st = int(torch.cuda.current_stream().cuda_stream)
-    plan.run_mesh(depth.data_ptr(), rgb.data_ptr(), verts.data_ptr(), off.data_ptr(), tris.data_ptr(), toff.data_ptr(), st)
-    if ct:
-        plan.color_transfer(depth.data_ptr(), verts.data_ptr(), off.data_ptr(), st)
-    if tri:
-        plan.overlay_merge(depth.data_ptr(), verts.data_ptr(), off.data_ptr(), tris.data_ptr(), toff.data_ptr(), st)
-    torch.cuda.synchronize()
-    o, to, v, t = off.cpu().numpy(), toff.cpu().numpy(), verts.cpu().numpy(), tris.cpu().numpy()
-    plan.close()
-    return [(v[k, :o[k, -1]], o[k], t[k, :to[k, -1]]) for k in range(T)]
+    from livescan3d_amd.fusion import DeviceFusion
+    with DeviceFusion.from_rigs(rigs) as fus:
+        fus.run_mesh()
+        if ct:
+            fus.color_transfer()
+        if tri:
+            fus.overlay_merge()
+        o = fus.host_offsets()
+        return [(fus.tick_bytes(k), o[k], fus.tick_triangles(k)) for k in range(len(rigs))]
 
 
 def _plan_run(rigs):
     """run (no triangles): the single pass for one tick, count -> scan -> write for more.  Returns per tick (vertex bytes, offsets)."""
-    import torch
-    T, N = len(rigs), rigs[0].n
-    plan = native.FusionPlan(0, T, rigs[0].widths, rigs[0].heights)
-    plan.set_params(rigs[0].intr, rigs[0].wt, rigs[0].bounds)
-    depth, rgb = _stack(rigs)
-    verts = torch.zeros((T, plan.capacity, 16), dtype=torch.uint8, device="cuda")
-    off = torch.full((T, N + 1), -7, dtype=torch.int32, device="cuda")
-    plan.run(depth.data_ptr(), rgb.data_ptr(), verts.data_ptr(), off.data_ptr(), int(torch.cuda.current_stream().cuda_stream))
-    torch.cuda.synchronize()
-    o, v = off.cpu().numpy(), verts.cpu().numpy()
-    plan.close()
-    return [(v[k, :o[k, -1]], o[k]) for k in range(T)]
+    from livescan3d_amd.fusion import DeviceFusion
+    with DeviceFusion.from_rigs(rigs) as fus:
+        fus.run()
+        o = fus.host_offsets()
+        return [(fus.tick_bytes(k), o[k]) for k in range(len(rigs))]
 
 
 def _check_counts(name, o, counts):
@@ -185,30 +160,29 @@ def test_fusion_plan_tick_sequence_matches_the_reference(gpu):
 @pytest.mark.parametrize("name", RADIAL)
 def test_fusion_plan_radial_matches_the_reference(gpu, name):
     import torch
+    from livescan3d_amd.fusion import DeviceFusion
     rig, _, _, want, _ = case(name)
-    plan = native.FusionPlan(0, 1, rig.widths, rig.heights)
-    depth, rgb = _stack([rig])
-    st = int(torch.cuda.current_stream().cuda_stream)
-    d2, c2 = torch.zeros_like(depth), torch.zeros_like(rgb)
-    plan.radial_correct_to(rig.intr, depth.data_ptr(), rgb.data_ptr(), d2.data_ptr(), c2.data_ptr(), st)
-    plan.radial_correct(rig.intr, depth.data_ptr(), rgb.data_ptr(), st)
-    torch.cuda.synchronize()
-    for tag, d, c in (("out of place", d2, c2), ("in place", depth, rgb)):
-        same(f"{name} {tag}", "radial_depth", d.cpu().numpy(), want)
-        same(f"{name} {tag}", "radial_colors", c.cpu().numpy(), want)
-    plan.close()
+    with DeviceFusion.from_rigs([rig]) as fus:
+        d2, c2 = torch.zeros_like(fus.depth), torch.zeros_like(fus.rgb)
+        fus.radial_correct_to(d2, c2)
+        fus.radial_correct()
+        torch.cuda.synchronize()
+        for tag, d, c in (("out of place", d2, c2), ("in place", fus.depth, fus.rgb)):
+            same(f"{name} {tag}", "radial_depth", d.cpu().numpy(), want)
+            same(f"{name} {tag}", "radial_colors", c.cpu().numpy(), want)
 
 
 @pytest.mark.parametrize("name", RADIAL_MESH)
 def test_tick_pipeline_matches_the_reference(gpu, name):
     """lsnTickRun: radial correction out of place -> vertices -> triangulation, one tick and two."""
     import torch
+    from livescan3d_amd.fusion import upload_rig
     rig, _, _, want, counts = case(name)
     for T in (1, 2):
         N = rig.n
         tp = native.TickPipeline(0, T, rig.widths, rig.heights)
         tp.set_params(rig.intr, rig.wt, rig.bounds)
-        depth, rgb = _stack([rig] * T)
+        depth, rgb = upload_rig(rig, T)
         cd, cc = torch.zeros_like(depth), torch.zeros_like(rgb)
         v = torch.zeros((T, tp.capacity, 16), dtype=torch.uint8, device="cuda")
         o = torch.full((T, N + 1), -7, dtype=torch.int32, device="cuda")

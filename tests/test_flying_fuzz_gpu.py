@@ -11,7 +11,7 @@ import pytest
 
 from livescan3d_amd import native, synth
 from tests import flying_ref
-from tests.test_bounds_gpu import Guarded
+from tests.support import Guarded
 
 pytestmark = pytest.mark.gpu
 
@@ -64,6 +64,7 @@ def _random_rig(rng):
 @pytest.mark.parametrize("seed", range(N_CASES))
 def test_random_rig_through_every_entry(gpu, orc, seed):
     import torch
+    from livescan3d_amd.fusion import upload_rig
     rng = np.random.default_rng(7000 + seed)
     rig, r, thr = _random_rig(rng)
     what = f"seed {seed}: sizes {list(zip(rig.widths.tolist(), rig.heights.tolist()))} r {r} thr {thr}"
@@ -100,8 +101,7 @@ def test_random_rig_through_every_entry(gpu, orc, seed):
     tp = native.TickPipeline(0, T, rig.widths, rig.heights)
     tp.set_params(rig.intr, rig.wt, rig.bounds)
     tp.set_flying_pixels(r, thr)
-    d_in = torch.from_numpy(np.stack([rig.depth_maps] * T)).to(dev)
-    c_in = torch.from_numpy(np.stack([rig.depth_colors] * T)).to(dev)
+    d_in, c_in = upload_rig(rig, T, 0)
     n = rig.n
     outs = {"depth": Guarded(torch, T * 2 * npix, dev), "colors": Guarded(torch, T * 3 * npix, dev), "verts": Guarded(torch, T * 16 * tp.capacity, dev),
             "off": Guarded(torch, T * 4 * (n + 1), dev), "tri": Guarded(torch, T * 12 * tp.tri_capacity, dev), "toff": Guarded(torch, T * 4 * (n + 1), dev)}

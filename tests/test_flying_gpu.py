@@ -9,18 +9,16 @@ Every test here fails on a library without the feature (the exports do not exist
 import hashlib
 import json
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 from livescan3d_amd import native, synth
 from tests import color_cases, color_ref, flying_cases, flying_ref, merge_ref, outlier_ref
+from tests.support import ROOT, child
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden", "flying_pixels_ref.npz")
 DIGESTS = os.path.join(ROOT, "tests", "golden", "flying_pixels_digests.json")
 
@@ -151,12 +149,11 @@ def _scene_rig(n=4, w=256, h=212):
 def _assert_not_vacuous(rig, r=1, thr=20):
     """From the device's own diagnostics: every sensor of the scene rig loses more than 0 and less than half of its valid pixels."""
     import torch
-    plan = native.FusionPlan(0, 1, rig.widths, rig.heights)
-    d_in = torch.from_numpy(rig.depth_maps.view(np.int16).copy()).cuda()
-    d_out = torch.empty_like(d_in)
-    plan.flying_pixels(r, thr, d_in.data_ptr(), d_out.data_ptr())
-    per, total = plan.flying_diagnostics(0)
-    plan.close()
+    from livescan3d_amd.fusion import DeviceFusion
+    with DeviceFusion.from_rigs([rig]) as fus:
+        d_out = torch.empty_like(fus.depth)
+        fus.flying_pixels(r, thr, d_out)
+        per, total = fus.plan.flying_diagnostics(0)
     dm, p = rig.depth_maps.view("<u2"), 0
     for i in range(rig.n):
         n = int(rig.widths[i]) * int(rig.heights[i])
@@ -241,14 +238,7 @@ print(H(np.asarray(gd).view(np.uint8), gc), H(v, np.asarray(t, np.int32), np.asa
 """
 
 
-def _child(env_extra, n, w, h):
-    env = dict(os.environ)
-    for k in ("LSN_FLYING_PIXELS", "LSN_OUTLIER_FILTER", "LSN_HOST_PATH", "LSN_HOST_GROUP", "LSN_HOST_DEVICES"):
-        env.pop(k, None)
-    env.update(env_extra)
-    r = subprocess.run([sys.executable, "-c", CHILD, str(n), str(w), str(h)], cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stderr[-2000:]
-    return r.stdout.strip().splitlines()[-1].split()
+DROP = ("LSN_FLYING_PIXELS", "LSN_OUTLIER_FILTER", "LSN_HOST_PATH", "LSN_HOST_GROUP", "LSN_HOST_DEVICES")
 
 
 def _H(*a):
@@ -269,9 +259,9 @@ def test_every_host_flow_with_the_environment_switch(gpu, orc, flow):
     allv, counts = orc.generate_mesh_vertices(rig.depth_maps, rig.depth_colors, rig.widths, rig.heights, rig.intr, rig.wt, rig.bounds)
     sv = allv[counts[0]:counts[0] + counts[1]]
     want = [_H(cd, cc), _H(v, np.asarray(t, np.int32), cd, cc), _H(orc.transfer_frame(v, t), orc.ply_binary(v, t)), _H(mv, np.asarray(mt, np.int32), sv)]
-    got = _child(dict(flow, LSN_FLYING_PIXELS="1,20"), n, w, h)
+    got = child(CHILD, dict(flow, LSN_FLYING_PIXELS="1,20"), n, w, h, drop=DROP, timeout=600)[0].split()
     assert got == want, flow
-    off = _child(flow, n, w, h)
+    off = child(CHILD, flow, n, w, h, drop=DROP, timeout=600)[0].split()
     assert off[0] != want[0] and off[1] != want[1] and off[3] == want[3]       # the switch changes the raw-frame exports only
 
 
@@ -314,6 +304,7 @@ def test_composes_with_the_outlier_filter(gpu, orc):
 @pytest.mark.parametrize("n_ticks,parts", [(1, 1), (8, 1), (8, 2), (64, 1), (64, 2)])
 def test_tick_run_filters_first(gpu, orc, n_ticks, parts):
     import torch
+    from livescan3d_amd.fusion import upload_rigs
     n, w, h = 4, 256, 212   # (smaller scene frames lose more than half of their pixels: see _assert_not_vacuous)
     rigs = [color_cases.ring(n, sizes=[(w, h)] * n, of=8, tick=t) for t in range(n_ticks)]
     _assert_not_vacuous(rigs[0])
@@ -328,9 +319,8 @@ def test_tick_run_filters_first(gpu, orc, n_ticks, parts):
             os.environ["LSN_TICK_PARTS"] = old
     assert tp.parts == (parts if n_ticks >= 2 else 1)
     tp.set_params(rigs[0].intr, rigs[0].wt, rigs[0].bounds)
-    src = np.stack([r.depth_maps.view(np.int16) for r in rigs])
-    d_in = torch.from_numpy(src).cuda()
-    c_in = torch.from_numpy(np.stack([r.depth_colors for r in rigs])).cuda()
+    d_in, c_in = upload_rigs(rigs)
+    src = b"".join(r.depth_maps.tobytes() for r in rigs)
     d_co, c_co = torch.zeros_like(d_in), torch.zeros_like(c_in)
     cap, tcap = tp.capacity, tp.tri_capacity
     verts = torch.zeros((n_ticks, cap, 16), dtype=torch.uint8, device="cuda")
@@ -348,7 +338,7 @@ def test_tick_run_filters_first(gpu, orc, n_ticks, parts):
     tp.set_flying_pixels(1, 20)
     for _ in range(2):                                    # twice: the second run finds the scratch reserved
         gd, gc, gv, go, gt, gto = run()
-        assert d_in.cpu().numpy().tobytes() == src.tobytes()      # d_depth_in stays untouched
+        assert d_in.cpu().numpy().tobytes() == src      # d_depth_in stays untouched
         for k in ([0] if n_ticks == 1 else [0, n_ticks // 2 - 1, n_ticks // 2, n_ticks - 1] + list(range(1, n_ticks, 9))):
             _, cd, cc, v, t = _want_tick(rigs[k], orc, 1, 20)
             assert gd[k].view(np.uint8).tobytes() == cd.tobytes() and gc[k].tobytes() == cc.tobytes(), k
@@ -365,6 +355,7 @@ def test_device_chain_filter_radial_mesh_colour_merge(gpu, orc):
     """On the device API the caller chains the stages freely: filter -> radial -> lsnFusionRunMesh -> colour transfer -> overlay merge on
     a ring rig equals the restatements of those stages on the filtered, corrected maps."""
     import torch
+    from livescan3d_amd.fusion import DeviceFusion
     rig = _scene_rig()
     _assert_not_vacuous(rig)
     _, cd, cc, _, _ = _want_tick(rig, orc, 1, 20)
@@ -372,25 +363,15 @@ def test_device_chain_filter_radial_mesh_colour_merge(gpu, orc):
     crig.depth_colors = cc
     want_tri, _ = merge_ref.overlay_merge(crig, orc)
     want_v, _ = color_ref.color_transfer(crig, orc)
-    plan = native.FusionPlan(0, 1, rig.widths, rig.heights)
-    plan.set_params(rig.intr, rig.wt, rig.bounds)
-    d_in = torch.from_numpy(rig.depth_maps.view(np.int16).copy()).cuda()
-    c_in = torch.from_numpy(rig.depth_colors.copy()).cuda()
-    d_f, d_c, c_c = torch.empty_like(d_in), torch.empty_like(d_in), torch.empty_like(c_in)
-    cap = plan.capacity
-    verts = torch.zeros((cap, 16), dtype=torch.uint8, device="cuda")
-    off = torch.zeros(rig.n + 1, dtype=torch.int32, device="cuda")
-    tri = torch.zeros((2 * cap, 3), dtype=torch.int32, device="cuda")
-    toff = torch.zeros(rig.n + 1, dtype=torch.int32, device="cuda")
-    st = int(torch.cuda.current_stream().cuda_stream)
-    plan.flying_pixels(1, 20, d_in.data_ptr(), d_f.data_ptr(), st)
-    plan.radial_correct_to(rig.intr, d_f.data_ptr(), c_in.data_ptr(), d_c.data_ptr(), c_c.data_ptr(), st)
-    plan.run_mesh(d_c.data_ptr(), c_c.data_ptr(), verts.data_ptr(), off.data_ptr(), tri.data_ptr(), toff.data_ptr(), st)
-    plan.color_transfer(d_c.data_ptr(), verts.data_ptr(), off.data_ptr(), st)
-    plan.overlay_merge(d_c.data_ptr(), verts.data_ptr(), off.data_ptr(), tri.data_ptr(), toff.data_ptr(), st)
+    fus = DeviceFusion.from_rigs([rig])
+    d_f, d_c, c_c = torch.empty_like(fus.depth), torch.empty_like(fus.depth), torch.empty_like(fus.rgb)
+    fus.flying_pixels(1, 20, d_f)
+    fus.radial_correct_to(d_c, c_c, depth=d_f)
+    fus.run_mesh(d_c, c_c)
+    fus.color_transfer(d_c)
+    fus.overlay_merge(d_c)
     torch.cuda.synchronize()
     assert d_c.cpu().numpy().view(np.uint8).tobytes() == cd.tobytes() and c_c.cpu().numpy().tobytes() == cc.tobytes()
-    nv, nt = int(off.cpu().numpy()[-1]), int(toff.cpu().numpy()[-1])
-    assert nv == len(want_v) and verts.cpu().numpy()[:nv].tobytes() == want_v.tobytes()
-    assert np.array_equal(tri.cpu().numpy()[:nt], want_tri)
-    plan.close()
+    assert len(fus.tick_bytes(0)) == len(want_v) and fus.tick_bytes(0).tobytes() == want_v.tobytes()
+    assert np.array_equal(fus.tick_triangles(0), want_tri)
+    fus.close()

@@ -8,15 +8,13 @@ import ctypes as C
 import hashlib
 import json
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 from tests import flying_cases, flying_ref as ref
+from tests.support import ROOT, child
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden", "flying_pixels_ref.npz")
 DIGESTS = os.path.join(ROOT, "tests", "golden", "flying_pixels_digests.json")
 
@@ -142,24 +140,19 @@ def test_not_idempotent_and_off():
 
 # ---- host state of the library: no device needed --------------------------------------------------------------------------------------
 
-def _child(code, env_extra):
-    env = {k: v for k, v in os.environ.items() if k != "LSN_FLYING_PIXELS"}
-    env.update(env_extra)
-    r = subprocess.run([sys.executable, "-c", code], cwd=ROOT, env=env, capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stderr[-2000:]
-    return r.stdout.strip().splitlines()[-1], r.stderr
+DROP = ("LSN_FLYING_PIXELS",)   # the children start without the switch of this shell
 
 
 def test_environment_switch_parsing():
     # the child reads the switch by setting it and setting it back: nothing else runs in that process
     code = "from livescan3d_amd import native; p = native.set_flying_pixel_filter(0, 0); native.set_flying_pixel_filter(*p); print(p)"
-    assert _child(code, {})[0] == "(0, 0)"
-    assert _child(code, {"LSN_FLYING_PIXELS": "1,20"})[0] == "(1, 20)"
-    assert _child(code, {"LSN_FLYING_PIXELS": " 3 , -1 "})[0] == "(3, -1)"
+    assert child(code, {}, drop=DROP)[0] == "(0, 0)"
+    assert child(code, {"LSN_FLYING_PIXELS": "1,20"}, drop=DROP)[0] == "(1, 20)"
+    assert child(code, {"LSN_FLYING_PIXELS": " 3 , -1 "}, drop=DROP)[0] == "(3, -1)"
     for bad in ("one", "1", "1,20x", "1;20", "1,2.5", ","):
-        out, err = _child(code, {"LSN_FLYING_PIXELS": bad})
+        out, err = child(code, {"LSN_FLYING_PIXELS": bad}, drop=DROP)
         assert out == "(0, 0)" and "LSN_FLYING_PIXELS" in err, bad
-    assert _child(code, {"LSN_FLYING_PIXELS": ""})[0] == "(0, 0)"
+    assert child(code, {"LSN_FLYING_PIXELS": ""}, drop=DROP)[0] == "(0, 0)"
 
 
 def test_switch_round_trip():

@@ -116,11 +116,8 @@ def test_device_resident_batch_matches_oracle(gpu, orc, mode):
     from livescan3d_amd.fusion import DeviceFusion
     T, N, w, h = 5, 3, 512, 424
     rigs = [synth.make_rig("scene" if k % 2 else "noise", N, w, h, seed=7, tick=k, bounds=synth.CROP_BOUNDS) for k in range(T)]
-    fus = DeviceFusion(T, rigs[0].widths, rigs[0].heights, mode=mode)
-    fus.set_params(rigs[0].intr, rigs[0].wt, rigs[0].bounds)
-    depth = torch.from_numpy(np.stack([r.depth_maps.view(np.int16) for r in rigs])).cuda()
-    rgb = torch.from_numpy(np.stack([r.depth_colors for r in rigs])).cuda()
-    fus.run(depth, rgb)
+    fus = DeviceFusion.from_rigs(rigs, mode=mode)
+    fus.run()
     torch.cuda.synchronize()
     for k in range(T):
         rk = rigs[k]
@@ -226,42 +223,32 @@ def test_triangulation_on_smooth_and_stepped_surfaces(gpu, orc):
 
 def test_device_resident_mesh_batch(gpu, orc):
     """lsnFusionRunMesh on T ticks x N sensors resident in HBM: vertices, triangles and both offset tables."""
-    import torch
+    from livescan3d_amd.fusion import DeviceFusion
     T, N, w, h = 3, 3, 512, 424
     rigs = [synth.make_rig("scene", N, w, h, seed=8, tick=k, bounds=synth.CROP_BOUNDS) for k in range(T)]
-    plan = native.FusionPlan(0, T, rigs[0].widths, rigs[0].heights)
-    plan.set_params(rigs[0].intr, rigs[0].wt, rigs[0].bounds)
-    depth = torch.from_numpy(np.stack([r.depth_maps.view(np.int16) for r in rigs])).cuda()
-    rgb = torch.from_numpy(np.stack([r.depth_colors for r in rigs])).cuda()
-    cap = plan.capacity
-    verts = torch.zeros((T, cap, 16), dtype=torch.uint8, device="cuda")
-    off = torch.zeros((T, N + 1), dtype=torch.int32, device="cuda")
-    tri = torch.zeros((T, 2 * cap, 3), dtype=torch.int32, device="cuda")
-    toff = torch.zeros((T, N + 1), dtype=torch.int32, device="cuda")
-    plan.run_mesh(depth.data_ptr(), rgb.data_ptr(), verts.data_ptr(), off.data_ptr(), tri.data_ptr(), toff.data_ptr(),
-                  int(torch.cuda.current_stream().cuda_stream))
-    torch.cuda.synchronize()
-    off_h, toff_h = off.cpu().numpy(), toff.cpu().numpy()
+    fus = DeviceFusion.from_rigs(rigs)
+    fus.run_mesh()
+    off_h, toff_h = fus.host_offsets(), fus.host_tri_offsets()
     for k in range(T):
         want, counts, want_tri = orc.generate_mesh(rigs[k].depth_maps, rigs[k].depth_colors, rigs[k].widths, rigs[k].heights,
                                                    rigs[0].intr, rigs[0].wt, rigs[0].bounds)
         nv, nt = int(off_h[k, -1]), int(toff_h[k, -1])
         assert nv == len(want) and nt == len(want_tri)
-        assert verts[k, :nv].cpu().numpy().tobytes() == want.tobytes()
-        assert np.array_equal(tri[k, :nt].cpu().numpy(), want_tri)
+        assert fus.tick_bytes(k).tobytes() == want.tobytes()
+        assert np.array_equal(fus.tick_triangles(k), want_tri)
         assert (np.diff(toff_h[k]) >= 0).all() and toff_h[k, 0] == 0
+    fus.close()
 
 
 def test_pipelined_calls_match(gpu, orc):
     """lsnFusionSetPipelined: count/scan of call k+1 on a side stream beside write(k); results identical, call after call."""
     import torch
-    from livescan3d_amd.fusion import DeviceFusion
+    from livescan3d_amd.fusion import DeviceFusion, upload_rigs
     T, N, w, h = 4, 2, 512, 424
     batches = []
     for b in range(3):
         rigs = [synth.make_rig("noise", N, w, h, seed=30 + b, tick=k, bounds=synth.CROP_BOUNDS) for k in range(T)]
-        batches.append((rigs, torch.from_numpy(np.stack([r.depth_maps.view(np.int16) for r in rigs])).cuda(),
-                        torch.from_numpy(np.stack([r.depth_colors for r in rigs])).cuda()))
+        batches.append((rigs, *upload_rigs(rigs)))
     fus = DeviceFusion(T, [w] * N, [h] * N)
     fus.set_params(batches[0][0][0].intr, batches[0][0][0].wt, synth.CROP_BOUNDS)
     fus.plan.set_pipelined(True)
@@ -286,12 +273,12 @@ def test_streamed_calls_match(gpu, orc):
     """lsnFusionRunStreamed: batch k is written while batch k+1 is counted inside the same kernel; a changed parameter set
     or an unexpected next batch falls back to counting on the spot.  Results identical to the oracle, call after call."""
     import torch
+    from livescan3d_amd.fusion import upload_rigs
     T, N, w, h = 3, 2, 512, 424
     batches = []
     for b in range(4):
         rigs = [synth.make_rig("noise" if b % 2 else "scene", N, w, h, seed=40 + b, tick=k, bounds=synth.CROP_BOUNDS) for k in range(T)]
-        batches.append((rigs, torch.from_numpy(np.stack([r.depth_maps.view(np.int16) for r in rigs])).cuda(),
-                        torch.from_numpy(np.stack([r.depth_colors for r in rigs])).cuda()))
+        batches.append((rigs, *upload_rigs(rigs)))
     plan = native.FusionPlan(0, T, [w] * N, [h] * N)
     intr, wt = batches[0][0][0].intr, batches[0][0][0].wt
     plan.set_params(intr, wt, synth.CROP_BOUNDS)
@@ -325,14 +312,13 @@ def test_streamed_refilled_next_buffer_is_a_clean_error(gpu, orc):
     mistake) must get an error flag, not overlapping tiles and writes past the tick's slab: the write pass compares every tile's
     survivors with what the count pass had seen and writes nothing where they differ."""
     import torch
+    from livescan3d_amd.fusion import upload_rigs
     T, N, w, h = 2, 2, 512, 424
     mk = lambda seed, kind: [synth.make_rig(kind, N, w, h, seed=seed, tick=k, bounds=synth.CROP_BOUNDS) for k in range(T)]
-    up = lambda rigs: (torch.from_numpy(np.stack([r.depth_maps.view(np.int16) for r in rigs])).cuda(),
-                       torch.from_numpy(np.stack([r.depth_colors for r in rigs])).cuda())
     ra, rb, rc = mk(70, "scene"), mk(71, "scene"), mk(72, "noise")        # rc: many more survivors than rb
-    da, ca = up(ra)
-    db, cb = up(rb)
-    dc, cc = up(rc)
+    da, ca = upload_rigs(ra)
+    db, cb = upload_rigs(rb)
+    dc, cc = upload_rigs(rc)
     plan = native.FusionPlan(0, T, [w] * N, [h] * N)
     plan.set_params(ra[0].intr, ra[0].wt, synth.CROP_BOUNDS)
     st = int(torch.cuda.current_stream().cuda_stream)
@@ -689,6 +675,7 @@ def test_tick_pipeline_gives_the_two_calls_bytes(gpu, orc, monkeypatch, T, sizes
     halves side by side on two streams.  Corrected maps, clouds, offsets, triangles: the oracle's, byte for byte, for every tick -- odd
     tick counts, ragged rigs (the second half's slices then start unaligned), both settings of the split; twice, on a side stream."""
     import torch
+    from livescan3d_amd.fusion import upload_rigs
     if parts_env:
         monkeypatch.setenv("LSN_TICK_PARTS", parts_env)
     N = len(sizes)
@@ -707,8 +694,7 @@ def test_tick_pipeline_gives_the_two_calls_bytes(gpu, orc, monkeypatch, T, sizes
     assert tp.parts == (int(parts_env) if parts_env else (2 if T >= 8 else 1))
     tp.set_params(r0.intr, r0.wt, r0.bounds)
     cap, tcap = tp.capacity, tp.tri_capacity
-    depth = torch.from_numpy(np.stack([r.depth_maps.view(np.int16) for r in rigs])).cuda().contiguous()
-    rgb = torch.from_numpy(np.stack([r.depth_colors for r in rigs])).cuda().contiguous()
+    depth, rgb = upload_rigs(rigs)
     st = torch.cuda.Stream()
     for rep in range(2):
         cd, cc = torch.zeros_like(depth), torch.zeros_like(rgb)

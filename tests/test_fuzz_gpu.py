@@ -140,6 +140,7 @@ def test_random_ticks_device_resident(gpu, orc, seed):
     """lsnFusionRadialCorrectTo -> lsnFusionRunMesh on 1-5 DIFFERENT ticks of a random rig (the host exports above run one tick per
     call): every tick's corrected maps, cloud, offsets and triangles against the oracle."""
     import torch
+    from livescan3d_amd.fusion import SENTINEL, DeviceFusion
     rng = np.random.default_rng(5000 + seed)
     T = int(rng.integers(1, 6))                                 # (one tick: the plan takes the single pass by itself)
     rigs = [_random_rig(np.random.default_rng(7000 + seed))]
@@ -154,21 +155,13 @@ def test_random_ticks_device_resident(gpu, orc, seed):
                 d[rng.random((h, w)) < 0.08] = 0
             depths.append(d); rgbs.append(c)
         rigs.append(synth.Rig(depths, rgbs, rigs[0].intr, rigs[0].wt, rigs[0].bounds))
-    r0, S = rigs[0], len(sizes)
-    plan = native.FusionPlan(0, T, r0.widths, r0.heights)
-    cap, P = plan.capacity, plan.pixels_per_tick
-    plan.set_params(r0.intr, r0.wt, r0.bounds)
-    dev = torch.device("cuda", 0)
-    depth = torch.from_numpy(np.stack([r.depth_maps.view(np.int16) for r in rigs])).to(dev).contiguous()
-    rgb = torch.from_numpy(np.stack([r.depth_colors for r in rigs])).to(dev).contiguous()
-    cd, cc = torch.empty_like(depth), torch.empty_like(rgb)
-    verts = torch.zeros((T, cap, 16), dtype=torch.uint8, device=dev)
-    offs = torch.zeros((T, S + 1), dtype=torch.int32, device=dev)
-    tris = torch.zeros((T, 2 * cap, 3), dtype=torch.int32, device=dev)
-    toffs = torch.zeros((T, S + 1), dtype=torch.int32, device=dev)
-    plan.radial_correct_to(r0.intr, depth.data_ptr(), rgb.data_ptr(), cd.data_ptr(), cc.data_ptr())
-    plan.run_mesh(cd.data_ptr(), cc.data_ptr(), verts.data_ptr(), offs.data_ptr(), tris.data_ptr(), toffs.data_ptr())
+    S = len(sizes)
+    fus = DeviceFusion.from_rigs(rigs)
+    cd, cc = torch.empty_like(fus.depth), torch.empty_like(fus.rgb)
+    fus.radial_correct_to(cd, cc)
+    fus.run_mesh(cd, cc)
     torch.cuda.synchronize()
+    verts, offs, tris, toffs = fus.vertices, fus.offsets, fus.triangles, fus.tri_offsets
     for k, r in enumerate(rigs):
         what = f"seed {seed} tick {k} of {T}: sizes {sizes}"
         wd, wc = orc.radial_correction(r.depth_maps, r.depth_colors, r.widths, r.heights, r.intr)
@@ -185,19 +178,20 @@ def test_random_ticks_device_resident(gpu, orc, seed):
         assert np.array_equal(tris[k, :len(want_t)].cpu().numpy(), np.asarray(want_t).reshape(-1, 3)), what + " [triangles]"
     # the cloud again through every way the compaction can get its offsets (lsnFusionSetMode), twice each: the second run of a mode counts
     # from the per-pixel depth thresholds the first one left
+    verts, offs = verts.clone(), offs.clone()
     for mode in (0, 1, 2, 0):
-        plan.set_mode(mode)
+        fus.plan.set_mode(mode)
         for rep in range(2):
-            v2 = torch.zeros_like(verts)
-            o2 = torch.zeros_like(offs)
-            plan.run(cd.data_ptr(), cc.data_ptr(), v2.data_ptr(), o2.data_ptr())
+            fus.vertices.zero_()
+            fus.offsets.fill_(SENTINEL)
+            v2, o2 = fus.run(cd, cc)
             torch.cuda.synchronize()
-            assert plan.check() == 0, f"seed {seed}: device-side flag after mode {mode}, run {rep}"
+            assert fus.plan.check() == 0, f"seed {seed}: device-side flag after mode {mode}, run {rep}"
             assert torch.equal(o2, offs), f"seed {seed}: offsets of mode {mode}, run {rep}"
             for k in range(T):
                 n = int(offs[k, -1].item())
                 assert torch.equal(v2[k, :n], verts[k, :n]), f"seed {seed}: cloud of tick {k}, mode {mode}, run {rep}"
-    plan.close()
+    fus.close()
 
 
 @pytest.mark.parametrize("seed", range(24 * SCALE))

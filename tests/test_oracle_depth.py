@@ -2,8 +2,8 @@
 createVertices (src/NativeUtils/depthprocessing.cpp:122-187) and against committed digests.
 
 Status: pinned.  The reference's own exports, compiled with stand-ins (tests/golden/make_export_golden.py), are recorded in
-tests/golden/export_ref.npz / export_ref_digests.json; tests/test_export_pin.py holds the C oracle and numpy_create_vertices below
-to them.  Here: the two independently written restatements (C and numpy) agree bit for bit, and the C one does not drift (sha256 of
+tests/golden/export_ref.npz / export_ref_digests.json; tests/test_export_pin.py holds the C oracle and numpy_create_vertices
+(tests/depth_ref.py) to them.  Here: the two independently written restatements (C and numpy) agree bit for bit, and the C one does not drift (sha256 of
 its output on seeded inputs, tests/golden/digests.json)."""
 import json
 import os
@@ -12,38 +12,7 @@ import numpy as np
 import pytest
 
 from livescan3d_amd import synth
-
-VDT = [("R", "u1"), ("G", "u1"), ("B", "u1"), ("A", "u1"), ("X", "<f4"), ("Y", "<f4"), ("Z", "<f4")]
-
-
-def numpy_create_vertices(depth, rgb, intr, wt, bounds):
-    """numpy float32, one rounding per operation, same order as depthprocessing.cpp:149-163."""
-    f = np.float32
-    h, w = depth.shape
-    cx, cy, fx, fy = [f(v) for v in intr[:4]]
-    t = [f(v) for v in wt[:3]]
-    R = np.asarray(wt[3:12], dtype=np.float32).reshape(3, 3)
-    y, x = np.meshgrid(np.arange(h), np.arange(w), indexing="ij")
-    with np.errstate(all="ignore"):
-        Z = depth.astype(np.float32) / f(1000.0)
-        X = (x.astype(np.float32) - cx) / fx
-        Y = (cy - y.astype(np.float32)) / fy
-        X = X * Z
-        Y = Y * Z
-        X = X + t[0]
-        Y = Y + t[1]
-        Z = Z + t[2]
-        ox = (X * R[0, 0] + Y * R[0, 1]) + Z * R[0, 2]
-        oy = (X * R[1, 0] + Y * R[1, 1]) + Z * R[1, 2]
-        oz = (X * R[2, 0] + Y * R[2, 1]) + Z * R[2, 2]
-        b = np.asarray(bounds, dtype=np.float32)
-        rejected = (ox < b[0]) | (ox > b[3]) | (oy < b[1]) | (oy > b[4]) | (oz < b[2]) | (oz > b[5])
-    keep = (depth != 0) & ~rejected
-    out = np.zeros(int(keep.sum()), dtype=VDT)
-    out["R"], out["G"], out["B"] = rgb[keep][:, 0], rgb[keep][:, 1], rgb[keep][:, 2]
-    out["A"] = 255
-    out["X"], out["Y"], out["Z"] = ox[keep], oy[keep], oz[keep]
-    return out
+from tests.depth_ref import numpy_create_vertices
 
 
 def _frames(rig):

@@ -6,58 +6,7 @@ import numpy as np
 import pytest
 
 from livescan3d_amd import synth
-
-
-def py_radial(depth2d, rgb3, intr):
-    f = np.float32
-    h, w = depth2d.shape
-    cx, cy, fx, fy, r2, r4, r6 = [f(v) for v in intr]
-    depth = depth2d.ravel()
-    colors = rgb3.reshape(-1, 3)
-    map_copy = np.zeros(w * h, np.uint16)
-    colors_copy = np.zeros((w * h, 3), np.uint8)
-
-    def f2i(v):
-        if not (v > f(-2147483904.0) and v < f(2147483648.0)):   # NaN / out of range: cvttss2si -> INT_MIN
-            return -2147483648
-        return int(np.trunc(v))
-
-    with np.errstate(all="ignore"):
-        for y in range(h):
-            for x in range(w):
-                if depth[x + y * w] == 0:
-                    continue
-                u = (f(x) - cx) / fx
-                v = (f(y) - cy) / fy
-                r = u * u + v * v
-                d = f(1) - r2 * r - r4 * r * r - r6 * r * r * r
-                xc = f2i(u * d * fx + cx)
-                yc = f2i(v * d * fy + cy)
-                if 0 <= xc < w and 0 <= yc < h:
-                    map_copy[xc + yc * w] = depth[x + y * w]
-                    colors_copy[xc + yc * w] = colors[x + y * w]
-    shifts = [-w - 1, -w, -w + 1, -1, 1, w - 1, w, w + 1]
-    for y in range(1, h - 1):
-        for x in range(1, w - 1):
-            pos = x + y * w
-            if map_copy[pos] != 0:
-                continue
-            n = s = 0
-            sc = [0, 0, 0]
-            prev = -1
-            for sh in shifts:
-                mv = int(map_copy[pos + sh])
-                if mv > 0 and (prev == -1 or abs(mv - prev) < 30):
-                    prev = mv
-                    n += 1
-                    s += mv
-                    for c in range(3):
-                        sc[c] += int(colors_copy[pos + sh, c])
-            if n > 4:
-                map_copy[pos] = s // n
-                for c in range(3):
-                    colors_copy[pos, c] = sc[c] // n
-    return map_copy.reshape(h, w), colors_copy.reshape(h, w, 3)
+from tests.depth_ref import py_radial
 
 
 @pytest.mark.parametrize("w,h,dist", [(40, 30, (0.09, -0.27, 0.09)), (33, 21, (0.5, 0.0, 0.0)), (24, 16, (0.0, 0.0, 0.0)),

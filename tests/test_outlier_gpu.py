@@ -3,18 +3,15 @@
 Bar: bit-exact -- a filtered single-sensor call equals filter() applied to the unfiltered cloud; a filtered merge call equals the same call
 without the filter on the restatement's masked maps; the device-resident batch equals the exports."""
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 from livescan3d_amd import native, synth
 from tests import color_cases, merge_cases, outlier_ref
+from tests.support import ROOT, child
 
 pytestmark = pytest.mark.gpu
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def _rigs_small():
@@ -123,29 +120,16 @@ def test_correct_and_generate_mesh(gpu):
 
 def _device_batch(rigs, k, d, in_place):
     import torch
-    T = len(rigs)
-    plan = native.FusionPlan(0, T, rigs[0].widths, rigs[0].heights)
-    plan.set_params(rigs[0].intr, rigs[0].wt, rigs[0].bounds)
-    depth = torch.from_numpy(np.stack([r.depth_maps.view(np.int16) for r in rigs])).cuda()
-    rgb = torch.from_numpy(np.stack([r.depth_colors for r in rigs])).cuda()
-    N, cap = rigs[0].n, plan.capacity
-    verts = torch.zeros((T, cap, 16), dtype=torch.uint8, device="cuda")
-    off = torch.zeros((T, N + 1), dtype=torch.int32, device="cuda")
-    tri = torch.zeros((T, 2 * cap, 3), dtype=torch.int32, device="cuda")
-    toff = torch.zeros((T, N + 1), dtype=torch.int32, device="cuda")
-    out = depth if in_place else torch.empty_like(depth)
-    st = int(torch.cuda.current_stream().cuda_stream)
-    plan.run(depth.data_ptr(), rgb.data_ptr(), verts.data_ptr(), off.data_ptr(), st)
-    plan.outlier_filter(k, d, depth.data_ptr(), verts.data_ptr(), off.data_ptr(), out.data_ptr(), st)
-    torch.cuda.synchronize()
-    o = off.cpu().numpy()
-    diags = [plan.outlier_diagnostics(t, int(o[t, -1]), st) for t in range(T)]
-    plan.run_mesh(out.data_ptr(), rgb.data_ptr(), verts.data_ptr(), off.data_ptr(), tri.data_ptr(), toff.data_ptr(), st)
-    torch.cuda.synchronize()
-    o2, to, tr, vv = off.cpu().numpy(), toff.cpu().numpy(), tri.cpu().numpy(), verts.cpu().numpy()
-    res = [(vv[t, :o2[t, -1]].copy().view(native.VERTEX_DTYPE).ravel(), tr[t, :to[t, -1]]) for t in range(T)]
-    plan.close()
-    return res, diags, o, out.cpu().numpy()
+    from livescan3d_amd.fusion import DeviceFusion
+    with DeviceFusion.from_rigs(rigs) as fus:
+        out = fus.depth if in_place else torch.empty_like(fus.depth)
+        fus.run()
+        fus.outlier_filter(k, d, out)
+        o = fus.host_offsets()
+        diags = [fus.plan.outlier_diagnostics(t, int(o[t, -1])) for t in range(len(rigs))]
+        fus.run_mesh(out)
+        res = [(fus.tick_cloud(t)[0], fus.tick_triangles(t)) for t in range(len(rigs))]
+        return res, diags, o, out.cpu().numpy()
 
 
 def test_device_batch_equals_exports(gpu, orc):
@@ -185,22 +169,16 @@ def test_full_size_exhaustive(gpu):
     """8 x 512x424 scene tick at (10, 0.01) and (10, 0.1): every removed vertex and 2000 random kept ones checked against their whole
     sensor block."""
     import torch
+    from livescan3d_amd.fusion import DeviceFusion
     rig = synth.make_rig("scene", 8, 512, 424, seed=7)
-    plan = native.FusionPlan(0, 1, rig.widths, rig.heights)
-    plan.set_params(rig.intr, rig.wt, rig.bounds)
-    depth = torch.from_numpy(rig.depth_maps.view(np.int16).copy()).cuda()
-    rgb = torch.from_numpy(rig.depth_colors.copy()).cuda()
-    verts = torch.zeros((plan.capacity, 16), dtype=torch.uint8, device="cuda")
-    off = torch.zeros(rig.n + 1, dtype=torch.int32, device="cuda")
-    out = torch.empty_like(depth)
-    plan.run(depth.data_ptr(), rgb.data_ptr(), verts.data_ptr(), off.data_ptr())
-    torch.cuda.synchronize()
-    o = off.cpu().numpy()
-    v = verts.cpu().numpy()[:o[-1]].copy().view(native.VERTEX_DTYPE).ravel()
+    fus = DeviceFusion.from_rigs([rig])
+    out = torch.empty_like(fus.depth)
+    fus.run()
+    v, o = fus.tick_cloud(0)
     rng = np.random.default_rng(3)
     for k, d in [(10, 0.01), (10, 0.1)]:
-        plan.outlier_filter(k, d, depth.data_ptr(), verts.data_ptr(), off.data_ptr(), out.data_ptr())
-        dg = plan.outlier_diagnostics(0, int(o[-1]))
+        fus.outlier_filter(k, d, out)
+        dg = fus.plan.outlier_diagnostics(0, int(o[-1]))
         rem = dg["removed"].astype(bool)
         thr = outlier_ref.threshold(d)
         for s in range(rig.n):
@@ -212,26 +190,20 @@ def test_full_size_exhaustive(gpu):
             sample = rng.choice(kept, size=min(2000, len(kept)), replace=False)
             assert (outlier_ref.neighbour_counts(blk, thr, sample) >= k).all(), (k, d, s)
         assert dg["total"] > 0 and dg["total"] < o[-1]
-    plan.close()
+    fus.close()
 
 
-def _child(code, env_extra):
-    env = dict(os.environ)
-    env.pop("LSN_OUTLIER_FILTER", None)
-    env.update(env_extra)
-    r = subprocess.run([sys.executable, "-c", code], cwd=ROOT, env=env, capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stderr[-2000:]
-    return r.stdout.strip().splitlines()[-1]
+DROP = ("LSN_OUTLIER_FILTER",)   # the children start without the switch of this shell
 
 
 def test_environment_switch():
     # the child reads the switch by setting it and setting it back: nothing else runs in that process
     code = "from livescan3d_amd import native; p = native.set_outlier_filter(0, 0.0); native.set_outlier_filter(*p); print(p)"
-    assert _child(code, {}) == "(0, 0.0)"
-    k, d = eval(_child(code, {"LSN_OUTLIER_FILTER": "10,0.1"}))
+    assert child(code, {}, drop=DROP)[0] == "(0, 0.0)"
+    k, d = eval(child(code, {"LSN_OUTLIER_FILTER": "10,0.1"}, drop=DROP)[0])
     assert k == 10 and np.float32(d) == np.float32(0.1)
-    assert _child(code, {"LSN_OUTLIER_FILTER": "ten"}) == "(0, 0.0)"
-    assert _child(code, {"LSN_OUTLIER_FILTER": "10,0.1x"}) == "(0, 0.0)"
+    assert child(code, {"LSN_OUTLIER_FILTER": "ten"}, drop=DROP)[0] == "(0, 0.0)"
+    assert child(code, {"LSN_OUTLIER_FILTER": "10,0.1x"}, drop=DROP)[0] == "(0, 0.0)"
 
 
 def test_environment_filters_the_exports_and_host_devices(gpu):
@@ -245,9 +217,9 @@ def test_environment_filters_the_exports_and_host_devices(gpu):
                                                 outlier_filter=(10, 0.02))
     import hashlib
     want = f"{len(v)} {hashlib.sha256(v.tobytes() + t.tobytes()).hexdigest()}"
-    assert _child(code, {"LSN_OUTLIER_FILTER": "10,0.02"}) == want
-    assert _child(code, {"LSN_OUTLIER_FILTER": "10,0.02", "LSN_HOST_DEVICES": "0,0,0"}) == want
-    plain = _child(code, {"LSN_HOST_DEVICES": "0,0,0"})
+    assert child(code, {"LSN_OUTLIER_FILTER": "10,0.02"}, drop=DROP)[0] == want
+    assert child(code, {"LSN_OUTLIER_FILTER": "10,0.02", "LSN_HOST_DEVICES": "0,0,0"}, drop=DROP)[0] == want
+    plain = child(code, {"LSN_HOST_DEVICES": "0,0,0"}, drop=DROP)[0]
     assert plain != want and int(plain.split()[0]) > len(v)
 
 

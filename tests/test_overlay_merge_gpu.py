@@ -3,70 +3,50 @@ against the CPU reference (tests/merge_ref.py).
 
 Bar: bit-exact -- the triangles equal the reference's; the vertices are byte-identical to the call without the merge; the
 diagnostics (reprojected maps, final maps, point_assigned) equal the reference's."""
-import os
-import subprocess
-import sys
-
 import numpy as np
 import pytest
 
 from livescan3d_amd import native
 from tests import color_cases, color_ref, merge_cases, merge_ref
+from tests.support import CUT_BOUNDS, ROOT, child, export
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CUT_BOUNDS = np.array([-0.3, -1.0, -1.5, 1.5, 1.5, 1.5], dtype=np.float32)   # through the sphere, inside the views' overlap
-
-
-def _export(rig, color=False, tri=True, merge=True):
-    v, t = native.generate_mesh_from_depth_maps(rig.depth_maps, rig.depth_colors, rig.widths, rig.heights, rig.intr, rig.wt, rig.bounds,
-                                                color_transfer=color, generate_triangles=tri, overlay_merge=merge)
-    return v, t, native.last_error()
+MERGED = dict(generate_triangles=True, overlay_merge=True)
+PLAIN = dict(overlay_merge=False)
 
 
 def _device(rigs, order=("merge",)):
-    """run_mesh over a batch of ticks, then the stages of `order` ("merge", "color").  Returns (plan, verts, off, tris per tick)."""
+    """run_mesh over a batch of ticks, then the stages of `order` ("merge", "color"); synchronised."""
     import torch
-    T = len(rigs)
-    plan = native.FusionPlan(0, T, rigs[0].widths, rigs[0].heights)
-    plan.set_params(rigs[0].intr, rigs[0].wt, rigs[0].bounds)
-    depth = torch.from_numpy(np.stack([r.depth_maps.view(np.int16) for r in rigs])).cuda()
-    rgb = torch.from_numpy(np.stack([r.depth_colors for r in rigs])).cuda()
-    N, cap = rigs[0].n, plan.capacity
-    verts = torch.zeros((T, cap, 16), dtype=torch.uint8, device="cuda")
-    off = torch.zeros((T, N + 1), dtype=torch.int32, device="cuda")
-    tri = torch.zeros((T, 2 * cap, 3), dtype=torch.int32, device="cuda")
-    toff = torch.zeros((T, N + 1), dtype=torch.int32, device="cuda")
-    st = int(torch.cuda.current_stream().cuda_stream)
-    plan.run_mesh(depth.data_ptr(), rgb.data_ptr(), verts.data_ptr(), off.data_ptr(), tri.data_ptr(), toff.data_ptr(), st)
+    from livescan3d_amd.fusion import DeviceFusion
+    fus = DeviceFusion.from_rigs(rigs)
+    fus.run_mesh()
     for stage in order:
-        if stage == "merge":
-            plan.overlay_merge(depth.data_ptr(), verts.data_ptr(), off.data_ptr(), tri.data_ptr(), toff.data_ptr(), st)
-        else:
-            plan.color_transfer(depth.data_ptr(), verts.data_ptr(), off.data_ptr(), st)
+        {"merge": fus.overlay_merge, "color": fus.color_transfer}[stage]()
     torch.cuda.synchronize()
-    o, to, tr = off.cpu().numpy(), toff.cpu().numpy(), tri.cpu().numpy()
-    return plan, verts.cpu().numpy(), o, [tr[k, :int(to[k, -1])] for k in range(T)]
+    return fus
 
 
 def _check_device(rig, orc, expect_assigned=None):
-    plan, verts, off, tris = _device([rig])
+    fus = _device([rig])
+    tris = fus.tick_triangles(0)
     want, diag = merge_ref.overlay_merge(rig, orc)
-    assert tris[0].shape == want.shape and np.array_equal(tris[0], want), (tris[0].shape, want.shape)
-    nv = int(off[0, -1])
-    d = plan.overlay_diagnostics(0, nv)
+    assert tris.shape == want.shape and np.array_equal(tris, want), (tris.shape, want.shape)
+    nv = int(fus.host_offsets()[0, -1])
+    d = fus.plan.overlay_diagnostics(0, nv)
     assert np.array_equal(d["reprojected"], diag["reprojected"])
     assert np.array_equal(d["merged"], diag["merged"])
     assert np.array_equal(d["assigned"], diag["assigned"]) and d["n_assigned"] == int(diag["assigned"].sum())
     if expect_assigned is not None:
         assert (d["n_assigned"] > 0) == expect_assigned, d["n_assigned"]
+    fus.close()
     return want, diag
 
 
 def _check_export(rig, orc):
-    plain, t0, e0 = _export(rig, merge=False, tri=False)
-    got, t1, e1 = _export(rig)
+    plain, t0, e0 = export(rig, **PLAIN)
+    got, t1, e1 = export(rig, **MERGED)
     want, _ = merge_ref.overlay_merge(rig, orc)
     assert e0 == "" and e1 == "", (e0, e1)
     assert got.tobytes() == plain.tobytes()                       # the merge touches no vertex
@@ -79,7 +59,7 @@ def test_wall_export_is_merged(gpu, orc):
     rig = merge_cases.wall(4)
     got, tris = _check_export(rig, orc)
     assert native.last_mesh_ply() == orc.ply_binary(got, tris)   # lsnLastMesh* serves the merged mesh
-    _, plain_tris, _ = _export(rig, merge=False, tri=False)
+    _, plain_tris, _ = export(rig, **PLAIN)
     assert len(tris) < len(plain_tris)
 
 
@@ -98,7 +78,7 @@ def test_one_sensor_is_the_reprojection(gpu, orc):
     want, diag = _check_device(rig, orc, False)
     assert np.array_equal(diag["reprojected"], diag["merged"])
     # the triangles differ from the plain call only through the reprojection's rounding
-    _, plain, _ = _export(rig, merge=False, tri=False)
+    _, plain, _ = export(rig, **PLAIN)
     assert abs(len(want) - len(plain)) < 0.05 * len(plain)
 
 
@@ -124,23 +104,25 @@ def test_batch_equals_ticks_one_by_one(gpu, orc):
     rigs = [merge_cases.wall(4, 128, 106, tick=k) for k in range(T)]
     for r in rigs[1:]:   # one calibration for the plan
         r.intr, r.wt, r.bounds = rigs[0].intr, rigs[0].wt, rigs[0].bounds
-    _, _, _, tris = _device(rigs)
+    with _device(rigs) as fus:
+        tris = [fus.tick_triangles(k) for k in range(T)]
     for k in range(T):
-        _, _, _, one = _device([rigs[k]])
-        assert np.array_equal(tris[k], one[0]), k
+        with _device([rigs[k]]) as one:
+            assert np.array_equal(tris[k], one.tick_triangles(0)), k
     want, _ = merge_ref.overlay_merge(rigs[5], orc)
     assert np.array_equal(tris[5], want)
 
 
 def test_merge_and_colour_in_both_orders(gpu, orc):
     rig = merge_cases.wall(4)
-    _, v1, _, t1 = _device([rig], ("merge", "color"))
-    _, v2, _, t2 = _device([rig], ("color", "merge"))
+    with _device([rig], ("merge", "color")) as f1, _device([rig], ("color", "merge")) as f2:
+        v1, v2 = f1.vertices.cpu().numpy(), f2.vertices.cpu().numpy()
+        t1, t2 = f1.tick_triangles(0), f2.tick_triangles(0)
     want, _ = merge_ref.overlay_merge(rig, orc)
     cwant, _ = color_ref.color_transfer(rig, orc)
-    assert np.array_equal(t1[0], want) and np.array_equal(t2[0], want)
+    assert np.array_equal(t1, want) and np.array_equal(t2, want)
     assert v1.tobytes() == v2.tobytes() and v1[0, :len(cwant)].tobytes() == cwant.tobytes()
-    got, tris, err = _export(rig, color=True)
+    got, tris, err = export(rig, color_transfer=True, **MERGED)
     assert err == "" and got.tobytes() == cwant.tobytes() and np.array_equal(tris, want)
 
 
@@ -154,8 +136,8 @@ def test_mixed_sizes_rejected(gpu):
     with pytest.raises(native.NativeUtilsError, match="same size"):
         plan.overlay_merge(buf.data_ptr(), buf.data_ptr(), buf.data_ptr(), buf.data_ptr(), buf.data_ptr(), 0)
     # the export: the unmerged mesh and a message
-    plain, t0, _ = _export(rig, merge=False)
-    got, t1, err = _export(rig)
+    plain, t0, _ = export(rig, generate_triangles=True, **PLAIN)
+    got, t1, err = export(rig, **MERGED)
     assert "same size" in err and got.tobytes() == plain.tobytes() and np.array_equal(t0, t1)
 
 
@@ -163,9 +145,9 @@ def test_switch_off_behaves_as_before(gpu):
     rig = color_cases.ring(4, sizes=[(256, 212)] * 4, of=8)
     prev = native.set_overlay_merge(False)
     try:
-        v0, t0, e0 = _export(rig, merge=None)
+        v0, t0, e0 = export(rig, generate_triangles=True)
         assert "overlay merge are outside this library's scope" in e0
-        plain, tp, _ = _export(rig, merge=None, tri=False)
+        plain, tp, _ = export(rig)
         assert v0.tobytes() == plain.tobytes() and np.array_equal(t0, tp)
     finally:
         native.set_overlay_merge(prev)
@@ -174,7 +156,7 @@ def test_switch_off_behaves_as_before(gpu):
 def test_switch_is_restored_and_silent(gpu, capfd):
     prev = native.set_overlay_merge(False)
     try:
-        _export(merge_cases.wall(2), merge=True)
+        export(merge_cases.wall(2), **MERGED)
         assert native.set_overlay_merge(False) is False     # the per-call switch was put back
         assert "NativeUtils" not in capfd.readouterr().err
     finally:
@@ -198,9 +180,7 @@ print("RESULT", int(on), len(t), repr(err))
 
 def test_env_switch_in_child_process(gpu, orc):
     """$LSN_OVERLAY_MERGE=1 switches the merge on for a fresh process (one child, under a time limit)."""
-    env = dict(os.environ, LSN_OVERLAY_MERGE="1")
-    r = subprocess.run([sys.executable, "-c", CHILD, ROOT], env=env, capture_output=True, text=True, timeout=300, cwd=ROOT)
-    assert r.returncode == 0, r.stderr[-2000:]
-    line = [x for x in r.stdout.splitlines() if x.startswith("RESULT")][-1].split(" ", 3)
+    line = child(CHILD, {"LSN_OVERLAY_MERGE": "1"}, ROOT)[0].split(" ", 3)
+    assert line[0] == "RESULT"
     want, _ = merge_ref.overlay_merge(merge_cases.wall(3), orc)
     assert line[1] == "1" and int(line[2]) == len(want) and line[3] == "''"

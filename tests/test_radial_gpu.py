@@ -84,25 +84,20 @@ def test_device_resident_batch_then_fusion(gpu, orc):
     """The per-tick order of LiveScanServer (KinectServer.cs:518-525 then :354-374): radial correction, then the merge
     call, all on HBM-resident ticks."""
     import torch
+    from livescan3d_amd.fusion import DeviceFusion
     T, N, w, h = 3, 2, 512, 424
     rigs = [synth.make_rig("scene", N, w, h, seed=9, tick=k, bounds=synth.CROP_BOUNDS) for k in range(T)]
-    plan = native.FusionPlan(0, T, rigs[0].widths, rigs[0].heights)
-    plan.set_params(rigs[0].intr, rigs[0].wt, rigs[0].bounds)
-    depth = torch.from_numpy(np.stack([r.depth_maps.view(np.int16) for r in rigs])).cuda()
-    rgb = torch.from_numpy(np.stack([r.depth_colors for r in rigs])).cuda()
-    st = int(torch.cuda.current_stream().cuda_stream)
-    plan.radial_correct(rigs[0].intr, depth.data_ptr(), rgb.data_ptr(), st)
-    verts = torch.zeros((T, plan.capacity, 16), dtype=torch.uint8, device="cuda")
-    off = torch.zeros((T, N + 1), dtype=torch.int32, device="cuda")
-    plan.run(depth.data_ptr(), rgb.data_ptr(), verts.data_ptr(), off.data_ptr(), st)
+    fus = DeviceFusion.from_rigs(rigs)
+    fus.radial_correct()
+    fus.run()
     torch.cuda.synchronize()
     for k in range(T):
         want_d, want_c = orc.radial_correction(rigs[k].depth_maps, rigs[k].depth_colors, rigs[k].widths, rigs[k].heights, rigs[0].intr)
-        assert np.array_equal(depth[k].cpu().numpy().view(np.uint8), want_d)
-        assert np.array_equal(rgb[k].cpu().numpy(), want_c)
+        assert np.array_equal(fus.depth[k].cpu().numpy().view(np.uint8), want_d)
+        assert np.array_equal(fus.rgb[k].cpu().numpy(), want_c)
         want_v, _ = orc.generate_mesh_vertices(want_d, want_c, rigs[k].widths, rigs[k].heights, rigs[0].intr, rigs[0].wt, rigs[0].bounds)
-        n = int(off[k, -1])
-        assert verts[k, :n].cpu().numpy().tobytes() == want_v.tobytes()
+        assert fus.tick_bytes(k).tobytes() == want_v.tobytes()
+    fus.close()
 
 
 def test_both_warp_paths_agree_with_the_oracle(gpu, orc, monkeypatch):
@@ -125,6 +120,7 @@ def test_hole_closing_paths_agree_with_the_oracle(gpu, orc, monkeypatch, env):
     the wavefront kernel alone: scene frames (thousands of fills, chains of fills feeding fills), a ragged rig (the pixel-by-pixel
     path) and a batch through the device-resident entry points, in place and out of place."""
     import torch
+    from livescan3d_amd.fusion import DeviceFusion
     for k, v in env.items():
         monkeypatch.setenv(k, v)
     for rig in (synth.make_rig("scene", 3, 512, 424, seed=21), synth.make_rig("scene", 2, 250, 120, seed=22), synth.make_rig("noise", 2, 128, 96, seed=23)):
@@ -134,18 +130,15 @@ def test_hole_closing_paths_agree_with_the_oracle(gpu, orc, monkeypatch, env):
         assert np.array_equal(np.asarray(got_c).ravel(), np.asarray(want_c).ravel())
     T, N, w, h = 5, 4, 256, 212
     rigs = [synth.make_rig("scene", N, w, h, seed=24, tick=k) for k in range(T)]
-    plan = native.FusionPlan(0, T, rigs[0].widths, rigs[0].heights)
-    depth = torch.from_numpy(np.stack([r.depth_maps.view(np.int16) for r in rigs])).cuda()
-    rgb = torch.from_numpy(np.stack([r.depth_colors for r in rigs])).cuda()
-    plan.radial_correct(rigs[0].intr, depth.data_ptr(), rgb.data_ptr(), int(torch.cuda.current_stream().cuda_stream))
+    fus = DeviceFusion.from_rigs(rigs)
+    depth2, rgb2 = fus.depth.clone(), fus.rgb.clone()
+    fus.radial_correct()
     torch.cuda.synchronize()
-    got_d, got_c = depth.cpu().numpy().view(np.uint8), rgb.cpu().numpy()
-    depth2 = torch.from_numpy(np.stack([r.depth_maps.view(np.int16) for r in rigs])).cuda()
-    rgb2 = torch.from_numpy(np.stack([r.depth_colors for r in rigs])).cuda()
+    got_d, got_c = fus.depth.cpu().numpy().view(np.uint8), fus.rgb.cpu().numpy()
     out_d, out_c = torch.zeros_like(depth2), torch.zeros_like(rgb2)
-    plan.radial_correct_to(rigs[0].intr, depth2.data_ptr(), rgb2.data_ptr(), out_d.data_ptr(), out_c.data_ptr(), int(torch.cuda.current_stream().cuda_stream))
+    fus.radial_correct_to(out_d, out_c, depth2, rgb2)
     torch.cuda.synchronize()
-    assert np.array_equal(depth2.cpu().numpy(), np.stack([r.depth_maps.view(np.int16) for r in rigs])), "out of place: the input was touched"
+    assert depth2.cpu().numpy().tobytes() == b"".join(r.depth_maps.tobytes() for r in rigs), "out of place: the input was touched"
     got2_d, got2_c = out_d.cpu().numpy().view(np.uint8), out_c.cpu().numpy()
     for k in range(T):
         want_d, want_c = orc.radial_correction(rigs[k].depth_maps, rigs[k].depth_colors, rigs[k].widths, rigs[k].heights, rigs[0].intr)
@@ -159,14 +152,13 @@ def test_more_frames_than_compute_units(gpu, orc):
     """A batch with more sensor-frames than the GPU has compute units (the second pass runs one workgroup per frame), and a
     1024-wide frame (eight-row bands).  Every frame against the oracle."""
     import torch
+    from livescan3d_amd.fusion import DeviceFusion
     T, N, w, h = 33, 8, 512, 424                                 # 264 frames
     rigs = [synth.make_rig("noise" if k % 3 else "scene", N, w, h, seed=14, tick=k) for k in range(T)]
-    plan = native.FusionPlan(0, T, rigs[0].widths, rigs[0].heights)
-    depth = torch.from_numpy(np.stack([r.depth_maps.view(np.int16) for r in rigs])).cuda()
-    rgb = torch.from_numpy(np.stack([r.depth_colors for r in rigs])).cuda()
-    plan.radial_correct(rigs[0].intr, depth.data_ptr(), rgb.data_ptr(), int(torch.cuda.current_stream().cuda_stream))
+    fus = DeviceFusion.from_rigs(rigs)
+    fus.radial_correct()
     torch.cuda.synchronize()
-    got_d, got_c = depth.cpu().numpy().view(np.uint8), rgb.cpu().numpy()
+    got_d, got_c = fus.depth.cpu().numpy().view(np.uint8), fus.rgb.cpu().numpy()
     for k in range(T):
         want_d, want_c = orc.radial_correction(rigs[k].depth_maps, rigs[k].depth_colors, rigs[k].widths, rigs[k].heights, rigs[0].intr)
         assert np.array_equal(got_d[k], want_d), f"tick {k}: depth"
@@ -199,6 +191,7 @@ def test_partly_overlapping_buffers_are_refused_and_route_switches_leave_no_stal
     while another still reads it, so the entry point refuses it (identical pointers = in place, disjoint = out of place).  And a call that
     takes the wavefront closing after the band kernel must not leave work-list counts behind for the next two-pass call."""
     import torch
+    from livescan3d_amd.fusion import upload_rigs
     T, N, w, h = 2, 2, 256, 212
     rigs = [synth.make_rig("scene", N, w, h, seed=31, tick=k) for k in range(T)]
     plan = native.FusionPlan(0, T, rigs[0].widths, rigs[0].heights)
@@ -206,8 +199,8 @@ def test_partly_overlapping_buffers_are_refused_and_route_switches_leave_no_stal
     npix = T * N * w * h
     big_d = torch.zeros(2 * npix, dtype=torch.int16, device="cuda")
     big_c = torch.zeros(6 * npix, dtype=torch.uint8, device="cuda")
-    big_d[:npix] = torch.from_numpy(np.stack([r.depth_maps.view(np.int16) for r in rigs]).ravel()).cuda()
-    big_c[:3 * npix] = torch.from_numpy(np.stack([r.depth_colors for r in rigs]).ravel()).cuda()
+    depth, rgb = upload_rigs(rigs)
+    big_d[:npix], big_c[:3 * npix] = depth.ravel(), rgb.ravel()
     with pytest.raises(native.NativeUtilsError, match="overlap"):
         plan.radial_correct_to(rigs[0].intr, big_d.data_ptr(), big_c.data_ptr(), big_d.data_ptr() + 2 * (npix // 2), big_c.data_ptr() + 3 * npix, st)
     with pytest.raises(native.NativeUtilsError, match="overlap"):
@@ -238,21 +231,19 @@ def test_closing_chain_leaves_its_counters_cleared(gpu, orc, monkeypatch, ticks,
     call, the second call -- which skipped the memset -- is as right as the first, and a call on ANOTHER stream (which clears the counters
     again: they might still be counting behind the first stream) is right as well."""
     import torch
+    from livescan3d_amd.fusion import DeviceFusion
     for k, v in env.items():
         monkeypatch.setenv(k, v)
     N, w, h = 2, 128, 96
     rigs = [synth.make_rig("scene", N, w, h, seed=13, tick=k % 4) for k in range(ticks)]
-    plan = native.FusionPlan(0, ticks, rigs[0].widths, rigs[0].heights)
-    src_d = torch.from_numpy(np.stack([r.depth_maps.view(np.int16) for r in rigs])).cuda()
-    src_c = torch.from_numpy(np.stack([r.depth_colors for r in rigs])).cuda()
+    fus = DeviceFusion.from_rigs(rigs)
     want = [orc.radial_correction(r.depth_maps, r.depth_colors, r.widths, r.heights, rigs[0].intr) for r in rigs[:4]]
-    other = torch.cuda.Stream()
-    st0 = int(torch.cuda.current_stream().cuda_stream)
-    for rep, st in enumerate((st0, st0, int(other.cuda_stream), st0)):
-        d, c = src_d.clone(), src_c.clone()
+    st0, other = torch.cuda.current_stream(), torch.cuda.Stream()
+    for rep, st in enumerate((st0, st0, other, st0)):
+        d, c = fus.depth.clone(), fus.rgb.clone()
         torch.cuda.synchronize()
-        plan.radial_correct(rigs[0].intr, d.data_ptr(), c.data_ptr(), st)
-        assert plan.radial_counters_left(st) == 0, f"call {rep}: the chain left counters behind"
+        fus.radial_correct(d, c, st)
+        assert fus.plan.radial_counters_left(int(st.cuda_stream)) == 0, f"call {rep}: the chain left counters behind"
         for k in (0, 1, ticks - 1):
             assert np.array_equal(d[k].cpu().numpy().view(np.uint8), np.asarray(want[k % 4][0]).view(np.uint8).ravel()), f"call {rep}: tick {k} depth"
             assert np.array_equal(c[k].cpu().numpy(), np.asarray(want[k % 4][1]).ravel()), f"call {rep}: tick {k} colours"
@@ -264,22 +255,21 @@ def test_calls_on_two_streams_back_to_back_share_the_plans_scratch_safely(gpu, o
     behind every chain).  Both calls, and a third one back on the first stream, must be right; a batch big enough that the first chain is
     still running when the second call is issued."""
     import torch
+    from livescan3d_amd.fusion import DeviceFusion
     N, w, h, ticks = 4, 256, 212, 48
     rigs = [synth.make_rig("scene", N, w, h, seed=17, tick=k % 3) for k in range(ticks)]
-    plan = native.FusionPlan(0, ticks, rigs[0].widths, rigs[0].heights)
-    src_d = torch.from_numpy(np.stack([r.depth_maps.view(np.int16) for r in rigs])).cuda()
-    src_c = torch.from_numpy(np.stack([r.depth_colors for r in rigs])).cuda()
+    fus = DeviceFusion.from_rigs(rigs)
     want = [orc.radial_correction(r.depth_maps, r.depth_colors, r.widths, r.heights, rigs[0].intr) for r in rigs[:3]]
     s1, s2 = torch.cuda.Stream(), torch.cuda.Stream()
     for rep in range(3):
-        outs = [(src_d.clone(), src_c.clone()) for _ in range(3)]
+        outs = [(fus.depth.clone(), fus.rgb.clone()) for _ in range(3)]
         torch.cuda.synchronize()
         for (d, c), st in zip(outs, (s1, s2, s1)):
-            plan.radial_correct(rigs[0].intr, d.data_ptr(), c.data_ptr(), int(st.cuda_stream))
+            fus.radial_correct(d, c, st)
         torch.cuda.synchronize()
-        assert plan.radial_counters_left(int(s1.cuda_stream)) == 0
+        assert fus.plan.radial_counters_left(int(s1.cuda_stream)) == 0
         for i, (d, c) in enumerate(outs):
             for k in (0, 1, 2, ticks - 1):
                 assert np.array_equal(d[k].cpu().numpy().view(np.uint8), np.asarray(want[k % 3][0]).view(np.uint8).ravel()), f"round {rep} call {i}: tick {k} depth"
                 assert np.array_equal(c[k].cpu().numpy(), np.asarray(want[k % 3][1]).ravel()), f"round {rep} call {i}: tick {k} colours"
-    plan.close()
+    fus.close()

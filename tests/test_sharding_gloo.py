@@ -123,6 +123,7 @@ def _survivor_worker(rank, world, port, S, T, w, h, out_dir):
     dist.init_process_group("gloo", rank=rank, world_size=world)
     from types import SimpleNamespace
     from livescan3d_amd import synth
+    from livescan3d_amd.fusion import stack_rigs
     from livescan3d_amd.sharding import sensor_block
     from bench_support.exchange import SurvivorExchange
     from oracle import orc
@@ -180,8 +181,8 @@ def _survivor_worker(rank, world, port, S, T, w, h, out_dir):
 
     local = SimpleNamespace(n_ticks=T, n_maps=mpr, capacity=mpr * P, tiles_per_tick=mpr * tiles_per_frame, device="cpu", plan=None)
     whole = SimpleNamespace(capacity=S * P, plan=None)
-    depth = torch.from_numpy(np.stack([r.depth_maps.view(np.int16)[s0 * P:s1 * P] for r in rigs]))
-    rgb = torch.from_numpy(np.stack([r.depth_colors[3 * s0 * P:3 * s1 * P] for r in rigs]))
+    depth, rgb = stack_rigs(rigs)
+    depth, rgb = torch.from_numpy(depth[:, s0 * P:s1 * P].copy()), torch.from_numpy(rgb[:, 3 * s0 * P:3 * s1 * P].copy())
     xch = SurvivorExchange(world, local, whole, pack_fn=pack_fn, recon_fn=recon_fn)
     merged, merged_off = xch.exchange(depth, rgb)
     assert xch.last_slab < mpr * P

@@ -76,13 +76,12 @@ def test_survivor_exchange_kernels_on_one_gpu(gpu, S, G, w, h):
     import numpy as np
     import torch
     from livescan3d_amd import synth
-    from livescan3d_amd.fusion import DeviceFusion
+    from livescan3d_amd.fusion import DeviceFusion, upload_rigs
     from oracle import orc
     T, mpr, P = 3, S // G, w * h
     rigs = [synth.make_rig("noise" if k % 2 else "scene", S, w, h, seed=23, tick=k, bounds=synth.CROP_BOUNDS) for k in range(T)]
     intr, wt, bounds = rigs[0].intr, rigs[0].wt, rigs[0].bounds
-    depth_all = torch.from_numpy(np.stack([r.depth_maps.view(np.int16) for r in rigs])).cuda()          # [T, S*P]
-    rgb_all = torch.from_numpy(np.stack([r.depth_colors for r in rigs])).cuda()                          # [T, S*P*3]
+    depth_all, rgb_all = upload_rigs(rigs)          # [T, S*P]
     st = int(torch.cuda.current_stream().cuda_stream)
     whole = DeviceFusion(T, [w] * S, [h] * S)
     whole.set_params(intr, wt, bounds)
@@ -208,7 +207,7 @@ def _shard_worker(rank, padded, chunks, out):
     import numpy as np
     import torch
     from livescan3d_amd import synth
-    from livescan3d_amd.fusion import DeviceFusion
+    from livescan3d_amd.fusion import DeviceFusion, upload_rigs
     from livescan3d_amd.sharding import ShardedFusion
     from oracle import orc
     torch.cuda.set_device(0)
@@ -216,8 +215,7 @@ def _shard_worker(rank, padded, chunks, out):
     T, S, w, h = 3, 4, 256, 212
     rigs = [synth.make_rig("noise" if k % 2 else "scene", S, w, h, seed=31, tick=k, bounds=synth.CROP_BOUNDS) for k in range(T)]
     intr, wt, bounds = rigs[0].intr, rigs[0].wt, rigs[0].bounds
-    depth = torch.from_numpy(np.stack([r.depth_maps.view(np.int16) for r in rigs])).to(dev)
-    rgb = torch.from_numpy(np.stack([r.depth_colors for r in rigs])).to(dev)
+    depth, rgb = upload_rigs(rigs, device=0)
     sf = ShardedFusion(0, 1, T, [w] * S, [h] * S, dev)             # lsnShardUniqueId / lsnShardCreate: RCCL communicator of one rank
     sf.set_params(intr, wt, bounds)
     ok = True
@@ -261,6 +259,7 @@ def _shard_worker_ragged(rank, padded, out):
         os.environ["LSN_SHARD_PADDED"] = "1"
     import numpy as np
     import torch
+    from livescan3d_amd.fusion import upload_rigs
     from livescan3d_amd import synth
     from livescan3d_amd.sharding import ShardedFusion
     from oracle import orc
@@ -277,8 +276,7 @@ def _shard_worker_ragged(rank, padded, out):
             intr.append(synth.kinect_intrinsics(w, h))
             wt.append(synth.pack_pose(*synth.ring_pose(s, len(sizes))))
         rigs.append(synth.Rig(depths, rgbs, np.concatenate(intr), np.concatenate(wt), [-1.0, -1.2, -1.5, 1.3, 1.1, 1.6]))
-    depth = torch.from_numpy(np.stack([r.depth_maps.view(np.int16) for r in rigs])).to(dev)
-    rgb = torch.from_numpy(np.stack([r.depth_colors for r in rigs])).to(dev)
+    depth, rgb = upload_rigs(rigs, device=0)
     sf = ShardedFusion(0, 1, T, [w for w, _ in sizes], [h for _, h in sizes], dev)
     sf.set_params(rigs[0].intr, rigs[0].wt, rigs[0].bounds)
     ok = True
@@ -324,7 +322,7 @@ def _shard_worker_multi(rank, world, port, sizes, chunks, padded, out):
     import torch
     import torch.distributed as dist
     from livescan3d_amd import synth
-    from livescan3d_amd.fusion import DeviceFusion
+    from livescan3d_amd.fusion import DeviceFusion, upload_rigs
     from livescan3d_amd.sharding import ShardedFusion
     dist.init_process_group("gloo", rank=rank, world_size=world)    # carries the 128-byte id only
     torch.cuda.set_device(0)
@@ -342,8 +340,7 @@ def _shard_worker_multi(rank, world, port, sizes, chunks, padded, out):
         rigs.append(synth.Rig(depths, rgbs, np.concatenate(intr), np.concatenate(wt), synth.CROP_BOUNDS))
     pix = [w * h for w, h in sizes]
     p0, p1 = sum(pix[:rank * mpr]), sum(pix[:(rank + 1) * mpr])
-    depth = torch.from_numpy(np.stack([r.depth_maps.view(np.int16) for r in rigs])).to(dev)
-    rgb = torch.from_numpy(np.stack([r.depth_colors for r in rigs])).to(dev)
+    depth, rgb = upload_rigs(rigs, device=0)
     mine_d = depth[:, p0:p1].contiguous()
     mine_c = rgb[:, 3 * p0:3 * p1].contiguous()
     widths, heights = [w for w, _ in sizes], [h for _, h in sizes]
@@ -428,6 +425,7 @@ def _shard_worker_world8(proc, n_procs, port, out, S=8, w=512, h=424, T=2):
     import numpy as np
     import torch
     import torch.distributed as dist
+    from livescan3d_amd.fusion import upload_rigs
     from livescan3d_amd import native, synth
     from oracle import orc
     dist.init_process_group("gloo", rank=proc, world_size=n_procs)   # carries the 128-byte id and the verdicts only
@@ -437,8 +435,7 @@ def _shard_worker_world8(proc, n_procs, port, out, S=8, w=512, h=424, T=2):
     per_proc = world // n_procs
     P, mpr = w * h, S // world
     rigs = [synth.make_rig("scene" if k else "noise", S, w, h, seed=31, tick=k, bounds=synth.CROP_BOUNDS) for k in range(T)]
-    depth = torch.from_numpy(np.stack([r.depth_maps.view(np.int16) for r in rigs])).to(dev)     # [T, S * P]
-    rgb = torch.from_numpy(np.stack([r.depth_colors for r in rigs])).to(dev)
+    depth, rgb = upload_rigs(rigs, device=0)     # [T, S * P]
     want = [orc.generate_mesh_vertices(r.depth_maps, r.depth_colors, r.widths, r.heights, rigs[0].intr, rigs[0].wt, rigs[0].bounds) for r in rigs]
     # 1. every rank prepares on its own; the processes agree that all 8 are ready before anybody enters the blocking rendezvous
     shards, errs = {}, []

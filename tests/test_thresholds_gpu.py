@@ -84,9 +84,9 @@ def _oracle(orc, rig):
 
 def _run_and_compare(orc, fus, rigs, what, streamed=False):
     import torch
+    from livescan3d_amd.fusion import upload_rigs
     T = len(rigs)
-    depth = torch.from_numpy(np.stack([r.depth_maps.view(np.int16) for r in rigs])).cuda()
-    rgb = torch.from_numpy(np.stack([r.depth_colors for r in rigs])).cuda()
+    depth, rgb = upload_rigs(rigs)
     if streamed:
         st = int(torch.cuda.current_stream().cuda_stream)
         fus.plan.run_streamed(depth.data_ptr(), rgb.data_ptr(), fus.vertices.data_ptr(), fus.offsets.data_ptr(), depth.data_ptr(), st)

@@ -24,72 +24,51 @@ import subprocess
 import sys
 import time
 
-import numpy as np
-
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 from livescan3d_amd import native, synth  # noqa: E402
+from tools import timing  # noqa: E402
 
 HBM_PEAK = 8.0e12
 
 
-def _scene_batch(n_ticks, n, w, h, distinct=8):
-    rigs = [synth.make_rig("scene", n, w, h, seed=1, tick=t) for t in range(min(distinct, n_ticks))]
-    return rigs[0], np.stack([rigs[t % len(rigs)].depth_maps.view(np.int16) for t in range(n_ticks)]), \
-        np.stack([rigs[t % len(rigs)].depth_colors for t in range(n_ticks)])
-
-
-def _events(torch, fn, reps):
-    ms = []
-    for _ in range(reps + 2):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        fn()
-        e1.record()
-        torch.cuda.synchronize()
-        ms.append(e0.elapsed_time(e1))
-    return statistics.median(ms[2:])
+def _scene_rigs(n_ticks, n, w, h, distinct=8):
+    return [synth.make_rig("scene", n, w, h, seed=1, tick=t) for t in range(min(distinct, n_ticks))]
 
 
 def kernel(reps):
     import torch
+    from livescan3d_amd.fusion import DeviceFusion
     res = {"mode": "kernel", "reps": reps}
     for name, (T, n, w, h) in {"64x8x512x424": (64, 8, 512, 424), "8x16x1024x1024": (8, 16, 1024, 1024)}.items():
-        rig, depth, rgb = _scene_batch(T, n, w, h, distinct=8 if w == 512 else 2)
-        plan = native.FusionPlan(0, T, rig.widths, rig.heights)
-        plan.set_params(rig.intr, rig.wt, rig.bounds)
-        d_in, c_in = torch.from_numpy(depth).cuda(), torch.from_numpy(rgb).cuda()
-        d_out = torch.empty_like(d_in)
-        st = int(torch.cuda.current_stream().cuda_stream)
-        nbytes = 4.0 * d_in.numel()
-        res[f"{name}_MB"] = round(nbytes / 1e6, 1)
-        for r in (1, 2, 3):
-            ms = _events(torch, lambda: plan.flying_pixels(r, 20, d_in.data_ptr(), d_out.data_ptr(), st), reps)
-            res[f"{name}_r{r}_ms"] = round(ms, 4)
-            res[f"{name}_r{r}_GBps"] = round(nbytes / ms / 1e6, 1)
-            res[f"{name}_r{r}_share_of_8TBps"] = round(nbytes / (ms * 1e-3) / HBM_PEAK, 3)
-        res[f"{name}_removed_tick0_r3"] = int(plan.flying_diagnostics(0)[1])
-        if w == 512:   # the project's own streaming kernels in the same run (count_thr_kernel from the third run on, fuse_kernel<1>)
-            verts = torch.zeros((T, plan.capacity, 16), dtype=torch.uint8, device="cuda")
-            off = torch.zeros((T, n + 1), dtype=torch.int32, device="cuda")
-            res[f"{name}_fusion_run_ms"] = round(_events(torch, lambda: plan.run(d_in.data_ptr(), c_in.data_ptr(), verts.data_ptr(), off.data_ptr(), st), reps + 2), 4)
-        plan.close()
-        del d_in, c_in, d_out
+        with DeviceFusion.from_rigs(_scene_rigs(T, n, w, h, distinct=8 if w == 512 else 2), T) as fus:
+            d_out = torch.empty_like(fus.depth)
+            nbytes = 4.0 * fus.depth.numel()
+            res[f"{name}_MB"] = round(nbytes / 1e6, 1)
+            for r in (1, 2, 3):
+                ms = timing.event_ms(lambda: fus.flying_pixels(r, 20, d_out), reps, 2)
+                res[f"{name}_r{r}_ms"] = round(ms, 4)
+                res[f"{name}_r{r}_GBps"] = round(nbytes / ms / 1e6, 1)
+                res[f"{name}_r{r}_share_of_8TBps"] = round(nbytes / (ms * 1e-3) / HBM_PEAK, 3)
+            res[f"{name}_removed_tick0_r3"] = int(fus.plan.flying_diagnostics(0)[1])
+            if w == 512:   # the project's own streaming kernels in the same run (count_thr_kernel from the third run on, fuse_kernel<1>)
+                res[f"{name}_fusion_run_ms"] = round(timing.event_ms(fus.run, reps + 2, 2), 4)
     print(json.dumps(res))
 
 
 def flows(reps, calls, host_calls, off_only):
-    import ctypes as C
     import torch
+    from livescan3d_amd.fusion import upload_rigs
     L = native.lib()
     has = hasattr(L, "lsnSetFlyingPixelFilter")
     res = {"mode": "flows", "library": os.environ.get("LSN_NATIVE_LIB", "in-tree"), "has_filter": has, "reps": reps, "calls": calls}
     T, n, w, h = 64, 8, 512, 424
-    rig, depth, rgb = _scene_batch(T, n, w, h)
+    rigs = _scene_rigs(T, n, w, h)
+    rig = rigs[0]
     tp = native.TickPipeline(0, T, rig.widths, rig.heights)
     tp.set_params(rig.intr, rig.wt, rig.bounds)
-    d_in, c_in = torch.from_numpy(depth).cuda(), torch.from_numpy(rgb).cuda()
+    d_in, c_in = upload_rigs(rigs, T)
     d_co, c_co = torch.empty_like(d_in), torch.empty_like(c_in)
     verts = torch.zeros((T, tp.capacity, 16), dtype=torch.uint8, device="cuda")
     off = torch.zeros((T, n + 1), dtype=torch.int32, device="cuda")
@@ -109,18 +88,11 @@ def flows(reps, calls, host_calls, off_only):
         return rates[1:]
 
     def host_ms():
-        p = lambda a: a.ctypes.data_as(C.c_void_p)
         b = [float(x) for x in rig.bounds]
-        t = []
-        for _ in range(host_calls + 3):
-            dm, dc = rig.depth_maps.copy(), rig.depth_colors.copy()
-            m = native.Mesh()
-            t0 = time.perf_counter()
-            L.lsnCorrectAndGenerateMesh(rig.n, p(dm), p(dc), p(rig.widths), p(rig.heights), p(rig.intr), p(rig.wt), C.byref(m), *b, 1)
-            L.deleteMesh(C.byref(m))
-            t.append((time.perf_counter() - t0) * 1e3)
+        t = timing.export_call_ms(lambda m, dm, dc: L.lsnCorrectAndGenerateMesh(*timing.rig_pointers(rig, dm, dc)[0], m, *b, 1), host_calls, 3,
+                                  frames=lambda: (rig.depth_maps.copy(), rig.depth_colors.copy()))   # the call corrects them in place
         assert native.last_error() == ""
-        return t[3:]
+        return t
 
     for label, setting in [("off", None)] + ([("on_1_20", (1, 20))] if has and not off_only else []):
         if setting:

@@ -2,10 +2,10 @@
 """Dev helper: minimal ICP driver for profiling (configs[1]-sized clouds, few dispatches)."""
 import sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-import numpy as np
 import torch
 from livescan3d_amd import native, synth
 from livescan3d_amd.fusion import DeviceFusion, upload_rig
+from tools import timing
 
 n_sens = int(os.environ.get("ICP_SENSORS", "2"))
 rig = synth.make_rig("scene", n_sens, 512, 424, seed=4, perturb=True)
@@ -23,12 +23,8 @@ ws = native.IcpWorkspace(0, n1, n2)
 for rep in range(int(os.environ.get("ICP_REPS", "3"))):
     src = src0.clone()
     Rt = torch.tensor([1, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0], dtype=torch.float32, device="cuda")
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    ws.run(tgt.data_ptr(), n1, src.data_ptr(), n2, Rt.data_ptr(), Rt.data_ptr() + 36, 10, native.NN_BRUTE if os.environ.get("ICP_BRUTE") == "1" else native.NN_GRID, int(torch.cuda.current_stream().cuda_stream))
-    e1.record()
-    torch.cuda.synchronize()
-    print("n1", n1, "n2", n2, "ms/iter", e0.elapsed_time(e1) / 10)
+    ms = timing.event_ms(lambda: ws.run(tgt.data_ptr(), n1, src.data_ptr(), n2, Rt.data_ptr(), Rt.data_ptr() + 36, 10, native.NN_BRUTE if os.environ.get("ICP_BRUTE") == "1" else native.NN_GRID, int(torch.cuda.current_stream().cuda_stream)), 1, 0)
+    print("n1", n1, "n2", n2, "ms/iter", ms / 10)
 if hasattr(native.lib(), "lsnIcpNearResolved"):
     print("near path settled", ws.near_resolved(int(torch.cuda.current_stream().cuda_stream)), "of", n2, "queries in the last step")
 tr = ws.trace(10)

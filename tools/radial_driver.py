@@ -3,7 +3,7 @@ import sys, os, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
 from livescan3d_amd import synth
-from livescan3d_amd.fusion import DeviceFusion
+from livescan3d_amd.fusion import DeviceFusion, upload_rigs
 kind = sys.argv[1] if len(sys.argv) > 1 else "noise"
 T = int(sys.argv[2]) if len(sys.argv) > 2 else 16
 reps = int(sys.argv[3]) if len(sys.argv) > 3 else 3
@@ -14,8 +14,7 @@ if kind == "noise":
     depth, rgb = depth.view(T, -1), rgb.view(T, -1)
 else:
     rigs = [synth.make_rig("scene", S, w, h, seed=3, tick=k) for k in range(min(T, 8))]
-    depth = torch.from_numpy(np.stack([rigs[k % len(rigs)].depth_maps.view(np.int16) for k in range(T)])).to(dev)
-    rgb = torch.from_numpy(np.stack([rigs[k % len(rigs)].depth_colors for k in range(T)])).to(dev)
+    depth, rgb = upload_rigs(rigs, T, 0)
 fus = DeviceFusion(T, [w] * S, [h] * S, device=0)
 intr = np.concatenate([synth.kinect_intrinsics(w, h)] * S)
 st = int(torch.cuda.current_stream().cuda_stream)

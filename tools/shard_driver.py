@@ -6,19 +6,17 @@ import os
 import sys
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-import numpy as np
 import torch
 
 from livescan3d_amd import synth
-from livescan3d_amd.fusion import DeviceFusion
+from livescan3d_amd.fusion import DeviceFusion, upload_rigs
 
 T, S, w, h = 64, 8, 512, 424
 P = w * h
 dev = torch.device("cuda", 0)
 # numpy-generated frames, few dispatches (the torch generator's thousands of small launches do not survive a --pmc pass)
 rigs = [synth.make_rig("noise", S, w, h, seed=1, tick=k, bounds=synth.CROP_BOUNDS) for k in range(8)]
-depth = torch.from_numpy(np.stack([rigs[k % 8].depth_maps.view(np.int16) for k in range(T)])).to(dev)
-rgb = torch.from_numpy(np.stack([rigs[k % 8].depth_colors for k in range(T)])).to(dev)
+depth, rgb = upload_rigs(rigs, T, 0)
 plan = DeviceFusion(T, [w] * S, [h] * S)
 plan.set_params(rigs[0].intr, rigs[0].wt, rigs[0].bounds)
 cap = S * P
