@@ -54,135 +54,167 @@ extern "C" int lsnGetLastError(char *buf, int len)
     return (int)strlen(s);
 }
 
-static int lsnDeviceCount_impl(void)
-{
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess) {
-        (void)hipGetLastError();
-        return 0;
-    }
-    return n;
-}
-
 extern "C" int lsnDeviceCount(void)
 {
-    return lsn::guarded<int>("lsnDeviceCount", static_cast<int>(-1), [&]() { return lsnDeviceCount_impl(); });
+    return lsn::guarded("lsnDeviceCount", -1, [&]() {
+        int n = 0;
+        if (hipGetDeviceCount(&n) != hipSuccess) {
+            (void)hipGetLastError();
+            return 0;
+        }
+        return n;
+    });
 }
 
 // ---- device memory / streams for hosts without a HIP of their own ------------------------------------------------------------
 
-static void * lsnDeviceMalloc_impl(int device, long long bytes)
-{
-    lsn::clear_error();
-    if (bytes <= 0) {
-        lsn::set_error("lsnDeviceMalloc: bad size %lld", bytes);
-        return nullptr;
-    }
-    LSN_HIP_NULL(hipSetDevice(device));
-    void *p = nullptr;
-    LSN_HIP_NULL(hipMalloc(&p, (size_t)bytes));
-    return p;
-}
-
 extern "C" void * lsnDeviceMalloc(int device, long long bytes)
 {
-    return lsn::guarded<void *>("lsnDeviceMalloc", static_cast<void *>(nullptr), [&]() { return lsnDeviceMalloc_impl(device, bytes); });
-}
-
-static int lsnDeviceFree_impl(int device, void *d_ptr)
-{
-    lsn::clear_error();
-    if (!d_ptr) return 0;
-    LSN_HIP(hipSetDevice(device));
-    LSN_HIP(hipFree(d_ptr));
-    return 0;
+    return lsn::guarded("lsnDeviceMalloc", static_cast<void *>(nullptr), [&]() -> void * {
+        lsn::clear_error();
+        if (bytes <= 0) {
+            lsn::set_error("lsnDeviceMalloc: bad size %lld", bytes);
+            return nullptr;
+        }
+        LSN_HIP_NULL(hipSetDevice(device));
+        void *p = nullptr;
+        LSN_HIP_NULL(hipMalloc(&p, (size_t)bytes));
+        return p;
+    });
 }
 
 extern "C" int lsnDeviceFree(int device, void *d_ptr)
 {
-    return lsn::guarded<int>("lsnDeviceFree", static_cast<int>(-1), [&]() { return lsnDeviceFree_impl(device, d_ptr); });
-}
-
-static int lsnDeviceUpload_impl(int device, void *d_dst, const void *h_src, long long bytes, void *stream)
-{
-    lsn::clear_error();
-    if (!d_dst || !h_src || bytes < 0) {
-        lsn::set_error("lsnDeviceUpload: bad arguments");
-        return -1;
-    }
-    LSN_HIP(hipSetDevice(device));
-    if (bytes > 0) LSN_HIP(hipMemcpyAsync(d_dst, h_src, (size_t)bytes, hipMemcpyHostToDevice, lsn::as_stream(stream)));
-    return 0;
+    return lsn::guarded("lsnDeviceFree", -1, [&]() {
+        lsn::clear_error();
+        if (!d_ptr) return 0;
+        LSN_HIP(hipSetDevice(device));
+        LSN_HIP(hipFree(d_ptr));
+        return 0;
+    });
 }
 
 extern "C" int lsnDeviceUpload(int device, void *d_dst, const void *h_src, long long bytes, void *stream)
 {
-    return lsn::guarded<int>("lsnDeviceUpload", static_cast<int>(-1), [&]() { return lsnDeviceUpload_impl(device, d_dst, h_src, bytes, stream); });
-}
-
-static int lsnDeviceDownload_impl(int device, void *h_dst, const void *d_src, long long bytes, void *stream)
-{
-    lsn::clear_error();
-    if (!h_dst || !d_src || bytes < 0) {
-        lsn::set_error("lsnDeviceDownload: bad arguments");
-        return -1;
-    }
-    LSN_HIP(hipSetDevice(device));
-    if (bytes > 0) LSN_HIP(hipMemcpyAsync(h_dst, d_src, (size_t)bytes, hipMemcpyDeviceToHost, lsn::as_stream(stream)));
-    return 0;
+    return lsn::guarded("lsnDeviceUpload", -1, [&]() {
+        lsn::clear_error();
+        if (!d_dst || !h_src || bytes < 0) {
+            lsn::set_error("lsnDeviceUpload: bad arguments");
+            return -1;
+        }
+        LSN_HIP(hipSetDevice(device));
+        if (bytes > 0) LSN_HIP(hipMemcpyAsync(d_dst, h_src, (size_t)bytes, hipMemcpyHostToDevice, lsn::as_stream(stream)));
+        return 0;
+    });
 }
 
 extern "C" int lsnDeviceDownload(int device, void *h_dst, const void *d_src, long long bytes, void *stream)
 {
-    return lsn::guarded<int>("lsnDeviceDownload", static_cast<int>(-1), [&]() { return lsnDeviceDownload_impl(device, h_dst, d_src, bytes, stream); });
-}
-
-static void * lsnStreamCreate_impl(int device)
-{
-    lsn::clear_error();
-    LSN_HIP_NULL(hipSetDevice(device));
-    hipStream_t s = nullptr;
-    LSN_HIP_NULL(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-    return s;
+    return lsn::guarded("lsnDeviceDownload", -1, [&]() {
+        lsn::clear_error();
+        if (!h_dst || !d_src || bytes < 0) {
+            lsn::set_error("lsnDeviceDownload: bad arguments");
+            return -1;
+        }
+        LSN_HIP(hipSetDevice(device));
+        if (bytes > 0) LSN_HIP(hipMemcpyAsync(h_dst, d_src, (size_t)bytes, hipMemcpyDeviceToHost, lsn::as_stream(stream)));
+        return 0;
+    });
 }
 
 extern "C" void * lsnStreamCreate(int device)
 {
-    return lsn::guarded<void *>("lsnStreamCreate", static_cast<void *>(nullptr), [&]() { return lsnStreamCreate_impl(device); });
-}
-
-static int lsnStreamDestroy_impl(int device, void *stream)
-{
-    lsn::clear_error();
-    if (!stream) return 0;
-    LSN_HIP(hipSetDevice(device));
-    LSN_HIP(hipStreamDestroy(lsn::as_stream(stream)));
-    return 0;
+    return lsn::guarded("lsnStreamCreate", static_cast<void *>(nullptr), [&]() -> void * {
+        lsn::clear_error();
+        LSN_HIP_NULL(hipSetDevice(device));
+        hipStream_t s = nullptr;
+        LSN_HIP_NULL(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+        return s;
+    });
 }
 
 extern "C" int lsnStreamDestroy(int device, void *stream)
 {
-    return lsn::guarded<int>("lsnStreamDestroy", static_cast<int>(-1), [&]() { return lsnStreamDestroy_impl(device, stream); });
-}
-
-static int lsnStreamSynchronize_impl(int device, void *stream)
-{
-    lsn::clear_error();
-    LSN_HIP(hipSetDevice(device));
-    LSN_HIP(hipStreamSynchronize(lsn::as_stream(stream)));
-    return 0;
+    return lsn::guarded("lsnStreamDestroy", -1, [&]() {
+        lsn::clear_error();
+        if (!stream) return 0;
+        LSN_HIP(hipSetDevice(device));
+        LSN_HIP(hipStreamDestroy(lsn::as_stream(stream)));
+        return 0;
+    });
 }
 
 extern "C" int lsnStreamSynchronize(int device, void *stream)
 {
-    return lsn::guarded<int>("lsnStreamSynchronize", static_cast<int>(-1), [&]() { return lsnStreamSynchronize_impl(device, stream); });
+    return lsn::guarded("lsnStreamSynchronize", -1, [&]() {
+        lsn::clear_error();
+        LSN_HIP(hipSetDevice(device));
+        LSN_HIP(hipStreamSynchronize(lsn::as_stream(stream)));
+        return 0;
+    });
 }
 
+// A process-wide pair of numbers that switches a filter of the exports: its first value comes from $env, written as `format` reads it
+// (unset: off; malformed: off, with the message `malformed`); from then on it is what the last lsnSet* call set, and every export reads
+// it when called.
+namespace {
+template <class A, class B>
+struct PairSetting {
+    std::mutex mu;
+    A a{};
+    B b{};
+    PairSetting(const char *env, const char *format, const char *malformed)
+    {
+        const char *e = getenv(env);
+        if (!e || !*e) return;
+        A x{};
+        B y{};
+        int used = 0;
+        if (sscanf(e, format, &x, &y, &used) == 2 && e[used] == '\0') {
+            a = x;
+            b = y;
+        } else {
+            fprintf(stderr, malformed, e);
+        }
+    }
+    void current(A &x, B &y)
+    {
+        std::lock_guard<std::mutex> g(mu);
+        x = a;
+        y = b;
+    }
+    // lsnSet*: the previous pair goes to prev_* (either may be null)
+    void exchange(A x, B y, A *prev_a, B *prev_b)
+    {
+        std::lock_guard<std::mutex> g(mu);
+        if (prev_a) *prev_a = a;
+        if (prev_b) *prev_b = b;
+        a = x;
+        b = y;
+    }
+};
+}  // namespace
 
-// the outlier filter's current (k, max_dist) (lsnSetOutlierFilter, below)
-static void outlier_current(int &k, float &max_dist);
-// the flying-pixel filter's current (neighbourhood, threshold) (lsnSetFlyingPixelFilter, below)
-static void flying_current(int &neighbourhood, int &threshold);
+// (k, max_dist) of the exports' outlier filter (lsnSetOutlierFilter); never destroyed: an export may run while the process exits
+static PairSetting<int, float> &outlier_setting()
+{
+    static auto *s = new PairSetting<int, float>(
+        "LSN_OUTLIER_FILTER", " %d , %f %n",
+        "[NativeUtils] $LSN_OUTLIER_FILTER=\"%s\" is not \"k,max_dist\" (e.g. \"10,0.1\"): the outlier filter stays off\n");
+    return *s;
+}
+
+// (neighbourhood, threshold) of the flying-pixel filter of the exports that start at raw frames, i.e. with the radial correction:
+// depthMapAndColorSetRadialCorrection and lsnCorrectAndGenerateMesh (lsnSetFlyingPixelFilter).  generateMeshFromDepthMaps and
+// generateVerticesFromDepthMap never read it: LiveScanServer calls them on the maps the radial export has just returned
+// (KinectServer.cs:518-525, :354-374), and the filter is not idempotent -- there it would run twice per tick.
+static PairSetting<int, int> &flying_setting()
+{
+    static auto *s = new PairSetting<int, int>(
+        "LSN_FLYING_PIXELS", " %d , %d %n",
+        "[NativeUtils] $LSN_FLYING_PIXELS=\"%s\" is not \"neighbourhood,threshold\" (e.g. \"1,20\"): the flying-pixel filter stays off\n");
+    return *s;
+}
 
 // What the three mesh exports share: `call` as `name` filled it (everything but the outlier filter's setting, which is read here) runs on
 // lane `l` of the context.  0: *out_mesh is the call's mesh; -1: the call was refused or failed, *out_mesh (if there is one) is empty and,
@@ -197,7 +229,7 @@ static int mesh_export(const char *name, Lane &l, MeshCall &call, Mesh *out_mesh
         empty_mesh(out_mesh);
         return -1;
     }
-    outlier_current(call.outlier_k, call.outlier_max_dist);
+    outlier_setting().current(call.outlier_k, call.outlier_max_dist);
     Ctx &c = ctx();
     if (ensure_ready(c) || fuse_host(c, l, call, out_mesh)) {
         empty_mesh(out_mesh);
@@ -206,29 +238,25 @@ static int mesh_export(const char *name, Lane &l, MeshCall &call, Mesh *out_mesh
     return 0;
 }
 
-static void generateVerticesFromDepthMap_impl(unsigned char *depth_maps, unsigned char *depth_colors, int *widths, int *heights,
-                                             float *intr_params, float *wtransform_params, Mesh *out_mesh, float minX, float minY,
-                                             float minZ, float maxX, float maxY, float maxZ, int depth_map_index)
-{
-    const float b[6] = {minX, minY, minZ, maxX, maxY, maxZ};
-    MeshCall call;
-    call.depth_maps = depth_maps;
-    call.depth_colors = depth_colors;
-    call.widths = widths;
-    call.heights = heights;
-    call.intr = intr_params;
-    call.wt = wtransform_params;
-    call.bounds6 = b;
-    call.first = depth_map_index;
-    call.count = 1;
-    (void)mesh_export("generateVerticesFromDepthMap", ctx().single, call, out_mesh);
-}
-
 extern "C" void generateVerticesFromDepthMap(unsigned char *depth_maps, unsigned char *depth_colors, int *widths, int *heights,
                                              float *intr_params, float *wtransform_params, Mesh *out_mesh, float minX, float minY,
                                              float minZ, float maxX, float maxY, float maxZ, int depth_map_index)
 {
-    const bool done = lsn::guarded<bool>("generateVerticesFromDepthMap", false, [&]() { generateVerticesFromDepthMap_impl(depth_maps, depth_colors, widths, heights, intr_params, wtransform_params, out_mesh, minX, minY, minZ, maxX, maxY, maxZ, depth_map_index); return true; });
+    const bool done = lsn::guarded("generateVerticesFromDepthMap", false, [&]() {
+        const float b[6] = {minX, minY, minZ, maxX, maxY, maxZ};
+        MeshCall call;
+        call.depth_maps = depth_maps;
+        call.depth_colors = depth_colors;
+        call.widths = widths;
+        call.heights = heights;
+        call.intr = intr_params;
+        call.wt = wtransform_params;
+        call.bounds6 = b;
+        call.first = depth_map_index;
+        call.count = 1;
+        (void)mesh_export("generateVerticesFromDepthMap", ctx().single, call, out_mesh);
+        return true;
+    });
     if (!done && out_mesh) empty_mesh(out_mesh);   // nothing reaches the caller but an empty mesh and the message
 }
 
@@ -244,300 +272,195 @@ static std::atomic<int> &overlay_merge_switch()
 
 extern "C" int lsnSetOverlayMerge(int enable) { return overlay_merge_switch().exchange(enable ? 1 : 0); }
 
-// lsnSetOutlierFilter: (k, max_dist) of the exports' outlier filter.  Its first value comes from $LSN_OUTLIER_FILTER="k,max_dist" (unset:
-// off; malformed: off, with a message); from then on it is what the last lsnSetOutlierFilter set, and every export reads it when called.
-struct OutlierSetting {
-    std::mutex mu;
-    int k = 0;
-    float max_dist = 0.0f;
-};
-
-static OutlierSetting &outlier_setting()
-{
-    static OutlierSetting *s = [] {
-        OutlierSetting *o = new OutlierSetting();
-        const char *e = getenv("LSN_OUTLIER_FILTER");
-        if (e && *e) {
-            int k = 0, used = 0;
-            float d = 0.0f;
-            if (sscanf(e, " %d , %f %n", &k, &d, &used) == 2 && e[used] == '\0') {
-                o->k = k;
-                o->max_dist = d;
-            } else {
-                fprintf(stderr, "[NativeUtils] $LSN_OUTLIER_FILTER=\"%s\" is not \"k,max_dist\" (e.g. \"10,0.1\"): the outlier filter stays off\n", e);
-            }
-        }
-        return o;
-    }();
-    return *s;
-}
-
-static void outlier_current(int &k, float &max_dist)
-{
-    OutlierSetting &o = outlier_setting();
-    std::lock_guard<std::mutex> g(o.mu);
-    k = o.k;
-    max_dist = o.max_dist;
-}
-
 extern "C" int lsnSetOutlierFilter(int k, float max_dist, int *prev_k, float *prev_max_dist)
 {
-    return lsn::guarded<int>("lsnSetOutlierFilter", static_cast<int>(-1), [&]() {
-        OutlierSetting &o = outlier_setting();
-        std::lock_guard<std::mutex> g(o.mu);
-        if (prev_k) *prev_k = o.k;
-        if (prev_max_dist) *prev_max_dist = o.max_dist;
-        o.k = k;
-        o.max_dist = max_dist;
+    return lsn::guarded("lsnSetOutlierFilter", -1, [&]() {
+        outlier_setting().exchange(k, max_dist, prev_k, prev_max_dist);
         return 0;
     });
-}
-
-// lsnSetFlyingPixelFilter: (neighbourhood, threshold) of the flying-pixel filter of the exports that start at raw frames, i.e. with the
-// radial correction: depthMapAndColorSetRadialCorrection and lsnCorrectAndGenerateMesh.  generateMeshFromDepthMaps and
-// generateVerticesFromDepthMap never read it: LiveScanServer calls them on the maps the radial export has just returned
-// (KinectServer.cs:518-525, :354-374), and the filter is not idempotent -- there it would run twice per tick.  Its first value comes from
-// $LSN_FLYING_PIXELS="neighbourhood,threshold" (unset: off; malformed: off, with a message); from then on it is what the last
-// lsnSetFlyingPixelFilter set, and the two exports read it when called.
-struct FlyingSetting {
-    std::mutex mu;
-    int neighbourhood = 0, threshold = 0;
-};
-
-static FlyingSetting &flying_setting()
-{
-    static FlyingSetting *s = [] {
-        FlyingSetting *o = new FlyingSetting();
-        const char *e = getenv("LSN_FLYING_PIXELS");
-        if (e && *e) {
-            int n = 0, t = 0, used = 0;
-            if (sscanf(e, " %d , %d %n", &n, &t, &used) == 2 && e[used] == '\0') {
-                o->neighbourhood = n;
-                o->threshold = t;
-            } else {
-                fprintf(stderr, "[NativeUtils] $LSN_FLYING_PIXELS=\"%s\" is not \"neighbourhood,threshold\" (e.g. \"1,20\"): the flying-pixel filter stays off\n", e);
-            }
-        }
-        return o;
-    }();
-    return *s;
-}
-
-static void flying_current(int &neighbourhood, int &threshold)
-{
-    FlyingSetting &o = flying_setting();
-    std::lock_guard<std::mutex> g(o.mu);
-    neighbourhood = o.neighbourhood;
-    threshold = o.threshold;
 }
 
 extern "C" int lsnSetFlyingPixelFilter(int neighbourhood, int threshold, int *prev_neighbourhood, int *prev_threshold)
 {
-    return lsn::guarded<int>("lsnSetFlyingPixelFilter", static_cast<int>(-1), [&]() {
-        FlyingSetting &o = flying_setting();
-        std::lock_guard<std::mutex> g(o.mu);
-        if (prev_neighbourhood) *prev_neighbourhood = o.neighbourhood;
-        if (prev_threshold) *prev_threshold = o.threshold;
-        o.neighbourhood = neighbourhood;
-        o.threshold = threshold;
+    return lsn::guarded("lsnSetFlyingPixelFilter", -1, [&]() {
+        flying_setting().exchange(neighbourhood, threshold, prev_neighbourhood, prev_threshold);
         return 0;
     });
-}
-
-static void generateMeshFromDepthMaps_impl(int n_maps, unsigned char *depth_maps, unsigned char *depth_colors, int *widths, int *heights,
-                                          float *intr_params, float *wtransform_params, Mesh *out_mesh, bool bcolor_transfer, float minX,
-                                          float minY, float minZ, float maxX, float maxY, float maxZ, bool bgenerate_triangles)
-{
-    const float b[6] = {minX, minY, minZ, maxX, maxY, maxZ};
-    // the overlay merge runs when the caller asks for it and the process opted in (lsnSetOverlayMerge / $LSN_OVERLAY_MERGE); it needs
-    // every sensor of the same size (merge.hip): otherwise the unmerged mesh goes back, with a message
-    bool merge = bgenerate_triangles && overlay_merge_switch().load();
-    bool mixed = false;
-    for (int i = 1; merge && widths && heights && i < n_maps; i++) mixed |= widths[i] != widths[0] || heights[i] != heights[0];
-    merge &= !mixed;
-    MeshCall call;
-    call.depth_maps = depth_maps;
-    call.depth_colors = depth_colors;
-    call.widths = widths;
-    call.heights = heights;
-    call.intr = intr_params;
-    call.wt = wtransform_params;
-    call.bounds6 = b;
-    call.count = n_maps;
-    call.with_triangles = true;
-    call.color_transfer = bcolor_transfer;
-    call.overlay_merge = merge;
-    Ctx &c = ctx();
-    if (mesh_export("generateMeshFromDepthMaps", c.merge, call, out_mesh)) return;
-    if (merge) return;
-    if (mixed) {
-        lsn::set_error("generateMeshFromDepthMaps: the overlay merge needs every sensor of the same size; returned the unmerged mesh");
-        return;
-    }
-    // bcolor_transfer is implemented (color.hip, through fuse_host's colour flow); the overlay merge is not
-    if (bgenerate_triangles) {
-        lsn::set_error("generateMeshFromDepthMaps: colour transfer / overlay merge are outside this library's scope; "
-                       "returned the cropped vertices of all sensors (flags false,false behaviour)");
-        if (!c.warned_flags) {
-            // nobody on the C# side reads lsnGetLastError, and bGenerateTriangles = true is LiveScanServer's default
-            // (KinectSettings.cs:50): say it once per process where an operator can see it
-            c.warned_flags = true;
-            fprintf(stderr, "[NativeUtils] generateMeshFromDepthMaps was called with bcolor_transfer=%d bgenerate_triangles=%d: this library "
-                            "implements the (false, false) behaviour only (no cross-view overlay merge, no colour transfer); the mesh "
-                            "returned is the unmerged one. Set bGenerateTriangles / bColorTransfer to false in LiveScanServer's settings.\n",
-                    (int)bcolor_transfer, (int)bgenerate_triangles);
-        }
-    }
 }
 
 extern "C" void generateMeshFromDepthMaps(int n_maps, unsigned char *depth_maps, unsigned char *depth_colors, int *widths, int *heights,
                                           float *intr_params, float *wtransform_params, Mesh *out_mesh, bool bcolor_transfer, float minX,
                                           float minY, float minZ, float maxX, float maxY, float maxZ, bool bgenerate_triangles)
 {
-    const bool done = lsn::guarded<bool>("generateMeshFromDepthMaps", false, [&]() { generateMeshFromDepthMaps_impl(n_maps, depth_maps, depth_colors, widths, heights, intr_params, wtransform_params, out_mesh, bcolor_transfer, minX, minY, minZ, maxX, maxY, maxZ, bgenerate_triangles); return true; });
+    const bool done = lsn::guarded("generateMeshFromDepthMaps", false, [&]() {
+        const float b[6] = {minX, minY, minZ, maxX, maxY, maxZ};
+        // the overlay merge runs when the caller asks for it and the process opted in (lsnSetOverlayMerge / $LSN_OVERLAY_MERGE); it needs
+        // every sensor of the same size (merge.hip): otherwise the unmerged mesh goes back, with a message
+        bool merge = bgenerate_triangles && overlay_merge_switch().load();
+        bool mixed = false;
+        for (int i = 1; merge && widths && heights && i < n_maps; i++) mixed |= widths[i] != widths[0] || heights[i] != heights[0];
+        merge &= !mixed;
+        MeshCall call;
+        call.depth_maps = depth_maps;
+        call.depth_colors = depth_colors;
+        call.widths = widths;
+        call.heights = heights;
+        call.intr = intr_params;
+        call.wt = wtransform_params;
+        call.bounds6 = b;
+        call.count = n_maps;
+        call.with_triangles = true;
+        call.color_transfer = bcolor_transfer;
+        call.overlay_merge = merge;
+        Ctx &c = ctx();
+        if (mesh_export("generateMeshFromDepthMaps", c.merge, call, out_mesh)) return true;
+        if (merge) return true;
+        if (mixed) {
+            lsn::set_error("generateMeshFromDepthMaps: the overlay merge needs every sensor of the same size; returned the unmerged mesh");
+            return true;
+        }
+        // bcolor_transfer is implemented (color.hip, through fuse_host's colour flow); the overlay merge is not
+        if (bgenerate_triangles) {
+            lsn::set_error("generateMeshFromDepthMaps: colour transfer / overlay merge are outside this library's scope; "
+                           "returned the cropped vertices of all sensors (flags false,false behaviour)");
+            if (!c.warned_flags) {
+                // nobody on the C# side reads lsnGetLastError, and bGenerateTriangles = true is LiveScanServer's default
+                // (KinectSettings.cs:50): say it once per process where an operator can see it
+                c.warned_flags = true;
+                fprintf(stderr, "[NativeUtils] generateMeshFromDepthMaps was called with bcolor_transfer=%d bgenerate_triangles=%d: this library "
+                                "implements the (false, false) behaviour only (no cross-view overlay merge, no colour transfer); the mesh "
+                                "returned is the unmerged one. Set bGenerateTriangles / bColorTransfer to false in LiveScanServer's settings.\n",
+                        (int)bcolor_transfer, (int)bgenerate_triangles);
+            }
+        }
+        return true;
+    });
     if (!done && out_mesh) empty_mesh(out_mesh);   // nothing reaches the caller but an empty mesh and the message
-}
-
-static void lsnCorrectAndGenerateMesh_impl(int n_maps, unsigned char *depth_maps, unsigned char *depth_colors, int *widths, int *heights,
-                                          float *intr_params, float *wtransform_params, Mesh *out_mesh, float minX, float minY, float minZ,
-                                          float maxX, float maxY, float maxZ, int write_back_corrected)
-{
-    const float b[6] = {minX, minY, minZ, maxX, maxY, maxZ};
-    MeshCall call;
-    call.depth_maps = depth_maps;
-    call.depth_colors = depth_colors;
-    call.widths = widths;
-    call.heights = heights;
-    call.intr = intr_params;
-    call.wt = wtransform_params;
-    call.bounds6 = b;
-    call.count = n_maps;
-    call.with_triangles = true;
-    call.radial = true;
-    call.back_d = write_back_corrected ? depth_maps : nullptr;
-    call.back_c = write_back_corrected ? depth_colors : nullptr;
-    flying_current(call.fp_neighbourhood, call.fp_threshold);
-    (void)mesh_export("lsnCorrectAndGenerateMesh", ctx().merge, call, out_mesh);
 }
 
 extern "C" void lsnCorrectAndGenerateMesh(int n_maps, unsigned char *depth_maps, unsigned char *depth_colors, int *widths, int *heights,
                                           float *intr_params, float *wtransform_params, Mesh *out_mesh, float minX, float minY, float minZ,
                                           float maxX, float maxY, float maxZ, int write_back_corrected)
 {
-    const bool done = lsn::guarded<bool>("lsnCorrectAndGenerateMesh", false, [&]() { lsnCorrectAndGenerateMesh_impl(n_maps, depth_maps, depth_colors, widths, heights, intr_params, wtransform_params, out_mesh, minX, minY, minZ, maxX, maxY, maxZ, write_back_corrected); return true; });
+    const bool done = lsn::guarded("lsnCorrectAndGenerateMesh", false, [&]() {
+        const float b[6] = {minX, minY, minZ, maxX, maxY, maxZ};
+        MeshCall call;
+        call.depth_maps = depth_maps;
+        call.depth_colors = depth_colors;
+        call.widths = widths;
+        call.heights = heights;
+        call.intr = intr_params;
+        call.wt = wtransform_params;
+        call.bounds6 = b;
+        call.count = n_maps;
+        call.with_triangles = true;
+        call.radial = true;
+        call.back_d = write_back_corrected ? depth_maps : nullptr;
+        call.back_c = write_back_corrected ? depth_colors : nullptr;
+        flying_setting().current(call.fp_neighbourhood, call.fp_threshold);
+        (void)mesh_export("lsnCorrectAndGenerateMesh", ctx().merge, call, out_mesh);
+        return true;
+    });
     if (!done && out_mesh) empty_mesh(out_mesh);   // nothing reaches the caller but an empty mesh and the message
-}
-
-static void depthMapAndColorSetRadialCorrection_impl(int n_maps, unsigned char *depth_maps, unsigned char *depth_colors, int *widths,
-                                                    int *heights, float *intr_params)
-{
-    lsn::clear_error();
-    if (n_maps <= 0 || !depth_maps || !depth_colors || !widths || !heights || !intr_params) {
-        if (n_maps != 0) lsn::set_error("depthMapAndColorSetRadialCorrection: bad arguments");
-        return;
-    }
-    Ctx &c = ctx();
-    Lane &l = c.merge;
-    std::lock_guard<std::mutex> g(l.mu);
-    if (ensure_ready(c)) return;
-    int fp_n = 0, fp_t = 0;
-    flying_current(fp_n, fp_t);
-    radial_host(c, l, n_maps, depth_maps, depth_colors, widths, heights, intr_params, fp_n, fp_t);
 }
 
 extern "C" void depthMapAndColorSetRadialCorrection(int n_maps, unsigned char *depth_maps, unsigned char *depth_colors, int *widths,
                                                     int *heights, float *intr_params)
 {
-    lsn::guarded_void("depthMapAndColorSetRadialCorrection", [&]() { depthMapAndColorSetRadialCorrection_impl(n_maps, depth_maps, depth_colors, widths, heights, intr_params); });
-}
-
-static Mesh * createMesh_impl(void)
-{
-    Mesh *m = (Mesh *)calloc(1, sizeof(Mesh));  // zeroed like depthprocessing.cpp:1820-1825
-    return m;
+    lsn::guarded_void("depthMapAndColorSetRadialCorrection", [&]() {
+        lsn::clear_error();
+        if (n_maps <= 0 || !depth_maps || !depth_colors || !widths || !heights || !intr_params) {
+            if (n_maps != 0) lsn::set_error("depthMapAndColorSetRadialCorrection: bad arguments");
+            return;
+        }
+        Ctx &c = ctx();
+        Lane &l = c.merge;
+        std::lock_guard<std::mutex> g(l.mu);
+        if (ensure_ready(c)) return;
+        int fp_n = 0, fp_t = 0;
+        flying_setting().current(fp_n, fp_t);
+        radial_host(c, l, n_maps, depth_maps, depth_colors, widths, heights, intr_params, fp_n, fp_t);
+    });
 }
 
 extern "C" Mesh * createMesh(void)
 {
-    return lsn::guarded<Mesh *>("createMesh", static_cast<Mesh *>(nullptr), [&]() { return createMesh_impl(); });
-}
-
-static void deleteMesh_impl(Mesh *mesh)
-{
-    if (!mesh) return;
-    Ctx &c = ctx();
-    if (mesh->triangles) pinned_put(c, mesh->triangles);   // a pinned block of ours; the static empty array or a foreign pointer is left alone
-    if (mesh->vertices) pinned_put(c, mesh->vertices);
-    mesh->triangles = nullptr;
-    mesh->vertices = nullptr;
+    return lsn::guarded("createMesh", static_cast<Mesh *>(nullptr), [&]() -> Mesh * {
+        Mesh *m = (Mesh *)calloc(1, sizeof(Mesh));  // zeroed like depthprocessing.cpp:1820-1825
+        return m;
+    });
 }
 
 extern "C" void deleteMesh(Mesh *mesh)
 {
-    lsn::guarded_void("deleteMesh", [&]() { deleteMesh_impl(mesh); });
-}
-
-static float ICP_impl(Point3f *verts1, Point3f *verts2, int nVerts1, int nVerts2, float *R, float *t, int maxIter)
-{
-    lsn::clear_error();
-    const float error = 1.0f;  // icp.cpp:85,176
-    if (!verts1 || !verts2 || !R || !t || nVerts1 <= 0 || nVerts2 <= 0 || maxIter <= 0) {
-        // the reference would throw out of nanoflann on an empty cloud (include/nanoflann.h:904); callers guard
-        if (nVerts1 <= 0 || nVerts2 <= 0) lsn::set_error("ICP: empty cloud (nVerts1=%d nVerts2=%d)", nVerts1, nVerts2);
-        return error;
-    }
-    Ctx &c = ctx();
-    std::lock_guard<std::mutex> g(c.icp_mu);   // not c.mu: merge calls go on while a refine call runs
-    if (ensure_ready(c)) return error;
-    if (!c.icp || nVerts1 > c.icp_n1 || nVerts2 > c.icp_n2) {
-        if (c.icp) lsnIcpDestroy(c.icp);
-        c.icp_n1 = nVerts1 > c.icp_n1 ? nVerts1 : c.icp_n1;
-        c.icp_n2 = nVerts2 > c.icp_n2 ? nVerts2 : c.icp_n2;
-        c.icp = lsnIcpCreate(c.device, c.icp_n1, c.icp_n2);
-        if (!c.icp) {
-            c.icp_n1 = c.icp_n2 = 0;
-            return error;
-        }
-    }
-    if (c.d_v1.reserve(sizeof(float) * 3 * (size_t)nVerts1) || c.d_v2.reserve(sizeof(float) * 3 * (size_t)nVerts2) || c.d_Rt.reserve(64))
-        return error;
-    const char *env = getenv("LSN_NN");
-    const int nn_mode = (env && strcmp(env, "brute") == 0) ? 0 : 1;
-    auto fail = [&]() { return error; };
-    if (hipMemcpyAsync(c.d_v1.p, verts1, sizeof(float) * 3 * (size_t)nVerts1, hipMemcpyHostToDevice, c.icp_stream) != hipSuccess ||
-        hipMemcpyAsync(c.d_v2.p, verts2, sizeof(float) * 3 * (size_t)nVerts2, hipMemcpyHostToDevice, c.icp_stream) != hipSuccess ||
-        hipMemcpyAsync(c.d_Rt.p, R, sizeof(float) * 9, hipMemcpyHostToDevice, c.icp_stream) != hipSuccess ||
-        hipMemcpyAsync(c.d_Rt.as<float>() + 9, t, sizeof(float) * 3, hipMemcpyHostToDevice, c.icp_stream) != hipSuccess) {
-        lsn::set_error("ICP: upload failed: %s", hipGetErrorString(hipGetLastError()));
-        return fail();
-    }
-    if (lsnIcpRun(c.icp, c.d_v1.as<float>(), nVerts1, c.d_v2.as<float>(), nVerts2, c.d_Rt.as<float>(), c.d_Rt.as<float>() + 9, maxIter,
-                  nn_mode, c.icp_stream))
-        return fail();
-    // results go to a scratch first so that the caller's buffers stay untouched when anything fails: a pinned block of the pool
-    // (recycled call after call; the download runs as DMA into it)
-    const size_t v2_bytes = sizeof(float) * 3 * (size_t)nVerts2;
-    float *v2 = static_cast<float *>(pinned_get(c, v2_bytes + sizeof(float) * 12));
-    if (!v2) return fail();
-    float *Rt = v2 + (size_t)nVerts2 * 3;
-    if (hipMemcpyAsync(v2, c.d_v2.p, v2_bytes, hipMemcpyDeviceToHost, c.icp_stream) != hipSuccess ||
-        hipMemcpyAsync(Rt, c.d_Rt.p, sizeof(float) * 12, hipMemcpyDeviceToHost, c.icp_stream) != hipSuccess ||
-        hipStreamSynchronize(c.icp_stream) != hipSuccess) {
-        lsn::set_error("ICP: download failed: %s", hipGetErrorString(hipGetLastError()));
-        (void)hipStreamSynchronize(c.icp_stream);
-        pinned_put(c, v2);
-        return fail();
-    }
-    memcpy(verts2, v2, v2_bytes);
-    memcpy(R, Rt, sizeof(float) * 9);
-    memcpy(t, Rt + 9, sizeof(float) * 3);
-    pinned_put(c, v2);
-    return error;
+    lsn::guarded_void("deleteMesh", [&]() {
+        if (!mesh) return;
+        Ctx &c = ctx();
+        if (mesh->triangles) pinned_put(c, mesh->triangles);   // a pinned block of ours; the static empty array or a foreign pointer is left alone
+        if (mesh->vertices) pinned_put(c, mesh->vertices);
+        mesh->triangles = nullptr;
+        mesh->vertices = nullptr;
+    });
 }
 
 extern "C" float ICP(Point3f *verts1, Point3f *verts2, int nVerts1, int nVerts2, float *R, float *t, int maxIter)
 {
-    return lsn::guarded<float>("ICP", 1.0f, [&]() { return ICP_impl(verts1, verts2, nVerts1, nVerts2, R, t, maxIter); });
+    return lsn::guarded("ICP", 1.0f, [&]() {
+        lsn::clear_error();
+        const float error = 1.0f;  // icp.cpp:85,176
+        if (!verts1 || !verts2 || !R || !t || nVerts1 <= 0 || nVerts2 <= 0 || maxIter <= 0) {
+            // the reference would throw out of nanoflann on an empty cloud (include/nanoflann.h:904); callers guard
+            if (nVerts1 <= 0 || nVerts2 <= 0) lsn::set_error("ICP: empty cloud (nVerts1=%d nVerts2=%d)", nVerts1, nVerts2);
+            return error;
+        }
+        Ctx &c = ctx();
+        std::lock_guard<std::mutex> g(c.icp_mu);   // not c.mu: merge calls go on while a refine call runs
+        if (ensure_ready(c)) return error;
+        if (!c.icp || nVerts1 > c.icp_n1 || nVerts2 > c.icp_n2) {
+            if (c.icp) lsnIcpDestroy(c.icp);
+            c.icp_n1 = nVerts1 > c.icp_n1 ? nVerts1 : c.icp_n1;
+            c.icp_n2 = nVerts2 > c.icp_n2 ? nVerts2 : c.icp_n2;
+            c.icp = lsnIcpCreate(c.device, c.icp_n1, c.icp_n2);
+            if (!c.icp) {
+                c.icp_n1 = c.icp_n2 = 0;
+                return error;
+            }
+        }
+        if (c.d_v1.reserve(sizeof(float) * 3 * (size_t)nVerts1) || c.d_v2.reserve(sizeof(float) * 3 * (size_t)nVerts2) || c.d_Rt.reserve(64))
+            return error;
+        const char *env = getenv("LSN_NN");
+        const int nn_mode = (env && strcmp(env, "brute") == 0) ? 0 : 1;
+        auto fail = [&]() { return error; };
+        if (hipMemcpyAsync(c.d_v1.p, verts1, sizeof(float) * 3 * (size_t)nVerts1, hipMemcpyHostToDevice, c.icp_stream) != hipSuccess ||
+            hipMemcpyAsync(c.d_v2.p, verts2, sizeof(float) * 3 * (size_t)nVerts2, hipMemcpyHostToDevice, c.icp_stream) != hipSuccess ||
+            hipMemcpyAsync(c.d_Rt.p, R, sizeof(float) * 9, hipMemcpyHostToDevice, c.icp_stream) != hipSuccess ||
+            hipMemcpyAsync(c.d_Rt.as<float>() + 9, t, sizeof(float) * 3, hipMemcpyHostToDevice, c.icp_stream) != hipSuccess) {
+            lsn::set_error("ICP: upload failed: %s", hipGetErrorString(hipGetLastError()));
+            return fail();
+        }
+        if (lsnIcpRun(c.icp, c.d_v1.as<float>(), nVerts1, c.d_v2.as<float>(), nVerts2, c.d_Rt.as<float>(), c.d_Rt.as<float>() + 9, maxIter,
+                      nn_mode, c.icp_stream))
+            return fail();
+        // results go to a scratch first so that the caller's buffers stay untouched when anything fails: a pinned block of the pool
+        // (recycled call after call; the download runs as DMA into it)
+        const size_t v2_bytes = sizeof(float) * 3 * (size_t)nVerts2;
+        float *v2 = static_cast<float *>(pinned_get(c, v2_bytes + sizeof(float) * 12));
+        if (!v2) return fail();
+        float *Rt = v2 + (size_t)nVerts2 * 3;
+        if (hipMemcpyAsync(v2, c.d_v2.p, v2_bytes, hipMemcpyDeviceToHost, c.icp_stream) != hipSuccess ||
+            hipMemcpyAsync(Rt, c.d_Rt.p, sizeof(float) * 12, hipMemcpyDeviceToHost, c.icp_stream) != hipSuccess ||
+            hipStreamSynchronize(c.icp_stream) != hipSuccess) {
+            lsn::set_error("ICP: download failed: %s", hipGetErrorString(hipGetLastError()));
+            (void)hipStreamSynchronize(c.icp_stream);
+            pinned_put(c, v2);
+            return fail();
+        }
+        memcpy(verts2, v2, v2_bytes);
+        memcpy(R, Rt, sizeof(float) * 9);
+        memcpy(t, Rt + 9, sizeof(float) * 3);
+        pinned_put(c, v2);
+        return error;
+    });
 }
 
 // ---- the outbound formats of the mesh the last merge call left in HBM (include/NativeUtils.h part 3) ----------------------------
@@ -585,32 +508,26 @@ long long last_mesh_bytes(Ctx &c, Lane &l, int kind, unsigned char *out, long lo
 }
 }  // namespace
 
-static long long lsnLastMeshTransferFrame_impl(unsigned char *out, long long out_cap)
-{
-    lsn::clear_error();
-    Ctx &c = ctx();
-    Lane *l = t_last_lane ? t_last_lane : c.last_lane.load();   // this thread's own last mesh call, else the process's
-    if (!l) l = &c.merge;
-    std::lock_guard<std::mutex> g(l->mu);
-    return last_mesh_bytes(c, *l, 0, out, out_cap);
-}
-
 extern "C" long long lsnLastMeshTransferFrame(unsigned char *out, long long out_cap)
 {
-    return lsn::guarded<long long>("lsnLastMeshTransferFrame", static_cast<long long>(-1), [&]() { return lsnLastMeshTransferFrame_impl(out, out_cap); });
-}
-
-static long long lsnLastMeshPly_impl(unsigned char *out, long long out_cap)
-{
-    lsn::clear_error();
-    Ctx &c = ctx();
-    Lane *l = t_last_lane ? t_last_lane : c.last_lane.load();   // this thread's own last mesh call, else the process's
-    if (!l) l = &c.merge;
-    std::lock_guard<std::mutex> g(l->mu);
-    return last_mesh_bytes(c, *l, 1, out, out_cap);
+    return lsn::guarded("lsnLastMeshTransferFrame", -1LL, [&]() -> long long {
+        lsn::clear_error();
+        Ctx &c = ctx();
+        Lane *l = t_last_lane ? t_last_lane : c.last_lane.load();   // this thread's own last mesh call, else the process's
+        if (!l) l = &c.merge;
+        std::lock_guard<std::mutex> g(l->mu);
+        return last_mesh_bytes(c, *l, 0, out, out_cap);
+    });
 }
 
 extern "C" long long lsnLastMeshPly(unsigned char *out, long long out_cap)
 {
-    return lsn::guarded<long long>("lsnLastMeshPly", static_cast<long long>(-1), [&]() { return lsnLastMeshPly_impl(out, out_cap); });
+    return lsn::guarded("lsnLastMeshPly", -1LL, [&]() -> long long {
+        lsn::clear_error();
+        Ctx &c = ctx();
+        Lane *l = t_last_lane ? t_last_lane : c.last_lane.load();   // this thread's own last mesh call, else the process's
+        if (!l) l = &c.merge;
+        std::lock_guard<std::mutex> g(l->mu);
+        return last_mesh_bytes(c, *l, 1, out, out_cap);
+    });
 }

@@ -365,42 +365,38 @@ int color_transfer(LsnFusion *p, const void *d_depth, void *d_vertices, const in
 
 extern "C" int lsnFusionColorTransfer(LsnFusion *p, const void *d_depth_maps, void *d_vertices, const int *d_offsets, void *stream)
 {
-    return lsn::guarded<int>("lsnFusionColorTransfer", static_cast<int>(-1), [&]() {
+    return lsn::guarded("lsnFusionColorTransfer", -1, [&]() {
         lsn::clear_error();
         return lsn::color_transfer(p, d_depth_maps, d_vertices, d_offsets, lsn::as_stream(stream));
     });
 }
 
-static int lsnFusionColorDiagnostics_impl(LsnFusion *p, int tick, unsigned char *conf, int *coverage, int *pairs, double *xform, void *stream)
-{
-    lsn::clear_error();
-    if (!p || tick < 0 || tick >= p->n_ticks) {
-        lsn::set_error("lsnFusionColorDiagnostics: bad arguments");
-        return -1;
-    }
-    std::lock_guard<std::mutex> g(p->mu);
-    if (!p->ct_ready) {
-        lsn::set_error("lsnFusionColorDiagnostics: no colour transfer has run on this plan");
-        return -1;
-    }
-    LSN_HIP(hipSetDevice(p->device));
-    hipStream_t s = lsn::as_stream(stream);
-    const int n = p->n_maps, np = n > 1 ? n - 1 : 1, words = 1 + 2 * np + n;
-    std::vector<int> pr((size_t)words);
-    LSN_HIP(hipMemcpyAsync(pr.data(), p->ct_pairs.as<int>() + (size_t)tick * words, sizeof(int) * words, hipMemcpyDeviceToHost, s));
-    if (conf) LSN_HIP(hipMemcpyAsync(conf, p->ix_conf.as<unsigned char>() + (size_t)tick * p->cap, (size_t)p->cap, hipMemcpyDeviceToHost, s));
-    if (coverage)
-        LSN_HIP(hipMemcpyAsync(coverage, p->ct_cov.as<int>() + (size_t)tick * n * n, sizeof(int) * n * n, hipMemcpyDeviceToHost, s));
-    if (xform) LSN_HIP(hipMemcpyAsync(xform, p->ct_xform.as<double>() + (size_t)tick * np * 9, sizeof(double) * 9 * np, hipMemcpyDeviceToHost, s));
-    LSN_HIP(hipStreamSynchronize(s));
-    const int n_pairs = pr[0] >= 0 && pr[0] <= np ? pr[0] : 0;
-    if (pairs)
-        for (int k = 0; k < 2 * n_pairs; k++) pairs[k] = pr[1 + k];
-    return n_pairs;
-}
-
 extern "C" int lsnFusionColorDiagnostics(LsnFusion *p, int tick, unsigned char *conf, int *coverage, int *pairs, double *xform, void *stream)
 {
-    return lsn::guarded<int>("lsnFusionColorDiagnostics", static_cast<int>(-1),
-                             [&]() { return lsnFusionColorDiagnostics_impl(p, tick, conf, coverage, pairs, xform, stream); });
+    return lsn::guarded("lsnFusionColorDiagnostics", -1, [&]() {
+        lsn::clear_error();
+        if (!p || tick < 0 || tick >= p->n_ticks) {
+            lsn::set_error("lsnFusionColorDiagnostics: bad arguments");
+            return -1;
+        }
+        std::lock_guard<std::mutex> g(p->mu);
+        if (!p->ct_ready) {
+            lsn::set_error("lsnFusionColorDiagnostics: no colour transfer has run on this plan");
+            return -1;
+        }
+        LSN_HIP(hipSetDevice(p->device));
+        hipStream_t s = lsn::as_stream(stream);
+        const int n = p->n_maps, np = n > 1 ? n - 1 : 1, words = 1 + 2 * np + n;
+        std::vector<int> pr((size_t)words);
+        LSN_HIP(hipMemcpyAsync(pr.data(), p->ct_pairs.as<int>() + (size_t)tick * words, sizeof(int) * words, hipMemcpyDeviceToHost, s));
+        if (conf) LSN_HIP(hipMemcpyAsync(conf, p->ix_conf.as<unsigned char>() + (size_t)tick * p->cap, (size_t)p->cap, hipMemcpyDeviceToHost, s));
+        if (coverage)
+            LSN_HIP(hipMemcpyAsync(coverage, p->ct_cov.as<int>() + (size_t)tick * n * n, sizeof(int) * n * n, hipMemcpyDeviceToHost, s));
+        if (xform) LSN_HIP(hipMemcpyAsync(xform, p->ct_xform.as<double>() + (size_t)tick * np * 9, sizeof(double) * 9 * np, hipMemcpyDeviceToHost, s));
+        LSN_HIP(hipStreamSynchronize(s));
+        const int n_pairs = pr[0] >= 0 && pr[0] <= np ? pr[0] : 0;
+        if (pairs)
+            for (int k = 0; k < 2 * n_pairs; k++) pairs[k] = pr[1 + k];
+        return n_pairs;
+    });
 }

@@ -291,17 +291,13 @@ __global__ __launch_bounds__(kThreads, 8) void recon_kernel(const FuseArgs a, co
 
 extern "C" int lsnFusionTilesPerTick(const LsnFusion *p) { return p ? p->tiles_per_tick : 0; }
 
-static int lsnFusionPackSurvivors_impl(LsnFusion *p, const void *d_depth, const void *d_colors, void *d_mask, void *d_depth_c, void *d_rgb_c,
-                                      int *d_tile_prefix, int *d_offsets, void *stream)
-{
-    lsn::clear_error();
-    return lsn::pack_survivors(p, d_depth, d_colors, d_mask, d_depth_c, d_rgb_c, d_tile_prefix, d_offsets, nullptr, stream);
-}
-
 extern "C" int lsnFusionPackSurvivors(LsnFusion *p, const void *d_depth, const void *d_colors, void *d_mask, void *d_depth_c, void *d_rgb_c,
                                       int *d_tile_prefix, int *d_offsets, void *stream)
 {
-    return lsn::guarded<int>("lsnFusionPackSurvivors", static_cast<int>(-1), [&]() { return lsnFusionPackSurvivors_impl(p, d_depth, d_colors, d_mask, d_depth_c, d_rgb_c, d_tile_prefix, d_offsets, stream); });
+    return lsn::guarded("lsnFusionPackSurvivors", -1, [&]() {
+        lsn::clear_error();
+        return lsn::pack_survivors(p, d_depth, d_colors, d_mask, d_depth_c, d_rgb_c, d_tile_prefix, d_offsets, nullptr, stream);
+    });
 }
 
 // Survivor exchange, sender side: count + scan as in lsnFusionRun, then the compact streams instead of vertices.
@@ -344,57 +340,43 @@ int lsn::pack_survivors(LsnFusion *p, const void *d_depth, const void *d_colors,
 
 // Survivor exchange, receiver side: `all` is a plan over the WHOLE rig (every sensor, lsnFusionSetParams called with all
 // parameters, same n_ticks); the gathered arrays hold n_shards equally shaped shards of maps_per_shard sensors each.
-static int lsnFusionReconstruct_impl(LsnFusion *all, int n_shards, int maps_per_shard, const void *d_masks, const void *d_depth_c,
-                                    const void *d_rgb_c, long long slab, const int *d_tile_prefix, const int *d_shard_offsets,
-                                    void *d_merged, int *d_merged_offsets, void *stream)
-{
-    lsn::clear_error();
-    return lsn::reconstruct(all, n_shards, maps_per_shard, d_masks, d_depth_c, d_rgb_c, slab, d_tile_prefix, d_shard_offsets, d_merged,
-                            d_merged_offsets, nullptr, stream);
-}
-
 extern "C" int lsnFusionReconstruct(LsnFusion *all, int n_shards, int maps_per_shard, const void *d_masks, const void *d_depth_c,
                                     const void *d_rgb_c, long long slab, const int *d_tile_prefix, const int *d_shard_offsets,
                                     void *d_merged, int *d_merged_offsets, void *stream)
 {
-    return lsn::guarded<int>("lsnFusionReconstruct", static_cast<int>(-1), [&]() { return lsnFusionReconstruct_impl(all, n_shards, maps_per_shard, d_masks, d_depth_c, d_rgb_c, slab, d_tile_prefix, d_shard_offsets, d_merged, d_merged_offsets, stream); });
-}
-
-static int lsnFusionPackSurvivorsRun_impl(LsnFusion *p, const void *d_depth, const void *d_colors, void *d_mask, void *d_depth_c, void *d_rgb_c,
-                                         int *d_tile_prefix, int *d_offsets, int *d_tick_base, void *stream)
-{
-    lsn::clear_error();
-    if (!d_tick_base || !d_tile_prefix) {
-        lsn::set_error("lsnFusionPackSurvivorsRun: null argument");
-        return -1;
-    }
-    return lsn::pack_survivors(p, d_depth, d_colors, d_mask, d_depth_c, d_rgb_c, d_tile_prefix, d_offsets, d_tick_base, stream);
+    return lsn::guarded("lsnFusionReconstruct", -1, [&]() {
+        lsn::clear_error();
+        return lsn::reconstruct(all, n_shards, maps_per_shard, d_masks, d_depth_c, d_rgb_c, slab, d_tile_prefix, d_shard_offsets, d_merged,
+                                d_merged_offsets, nullptr, stream);
+    });
 }
 
 extern "C" int lsnFusionPackSurvivorsRun(LsnFusion *p, const void *d_depth, const void *d_colors, void *d_mask, void *d_depth_c, void *d_rgb_c,
                                          int *d_tile_prefix, int *d_offsets, int *d_tick_base, void *stream)
 {
-    return lsn::guarded<int>("lsnFusionPackSurvivorsRun", static_cast<int>(-1), [&]() { return lsnFusionPackSurvivorsRun_impl(p, d_depth, d_colors, d_mask, d_depth_c, d_rgb_c, d_tile_prefix, d_offsets, d_tick_base, stream); });
-}
-
-static int lsnFusionReconstructRun_impl(LsnFusion *all, int n_shards, int maps_per_shard, const void *d_masks, const void *d_depth_c,
-                                       const void *d_rgb_c, long long run_len, const int *d_tile_prefix, const int *d_shard_offsets,
-                                       void *d_merged, int *d_merged_offsets, int *d_tick_base_scratch, void *stream)
-{
-    lsn::clear_error();
-    if (!d_tick_base_scratch) {
-        lsn::set_error("lsnFusionReconstructRun: null argument");
-        return -1;
-    }
-    return lsn::reconstruct(all, n_shards, maps_per_shard, d_masks, d_depth_c, d_rgb_c, run_len, d_tile_prefix, d_shard_offsets, d_merged,
-                            d_merged_offsets, d_tick_base_scratch, stream);
+    return lsn::guarded("lsnFusionPackSurvivorsRun", -1, [&]() {
+        lsn::clear_error();
+        if (!d_tick_base || !d_tile_prefix) {
+            lsn::set_error("lsnFusionPackSurvivorsRun: null argument");
+            return -1;
+        }
+        return lsn::pack_survivors(p, d_depth, d_colors, d_mask, d_depth_c, d_rgb_c, d_tile_prefix, d_offsets, d_tick_base, stream);
+    });
 }
 
 extern "C" int lsnFusionReconstructRun(LsnFusion *all, int n_shards, int maps_per_shard, const void *d_masks, const void *d_depth_c,
                                        const void *d_rgb_c, long long run_len, const int *d_tile_prefix, const int *d_shard_offsets,
                                        void *d_merged, int *d_merged_offsets, int *d_tick_base_scratch, void *stream)
 {
-    return lsn::guarded<int>("lsnFusionReconstructRun", static_cast<int>(-1), [&]() { return lsnFusionReconstructRun_impl(all, n_shards, maps_per_shard, d_masks, d_depth_c, d_rgb_c, run_len, d_tile_prefix, d_shard_offsets, d_merged, d_merged_offsets, d_tick_base_scratch, stream); });
+    return lsn::guarded("lsnFusionReconstructRun", -1, [&]() {
+        lsn::clear_error();
+        if (!d_tick_base_scratch) {
+            lsn::set_error("lsnFusionReconstructRun: null argument");
+            return -1;
+        }
+        return lsn::reconstruct(all, n_shards, maps_per_shard, d_masks, d_depth_c, d_rgb_c, run_len, d_tile_prefix, d_shard_offsets, d_merged,
+                                d_merged_offsets, d_tick_base_scratch, stream);
+    });
 }
 
 // d_tick_base (nullable, scratch [n_shards][n_ticks]): the gathered streams are one back-to-back run of `slab` entries per shard
@@ -463,18 +445,14 @@ int lsn::reconstruct(LsnFusion *all, int n_shards, int maps_per_shard, const voi
     return 0;
 }
 
-static int lsnMergeShards_impl(int device, int n_shards, int n_ticks, int maps_per_shard, const void *d_shards, long long shard_cap,
-                              const int *d_shard_offsets, void *d_merged, long long merged_cap, int *d_merged_offsets, void *stream)
-{
-    lsn::clear_error();
-    return lsn::merge_shards(device, n_shards, n_ticks, maps_per_shard, d_shards, shard_cap, d_shard_offsets, d_merged, merged_cap, d_merged_offsets,
-                             false, stream);
-}
-
 extern "C" int lsnMergeShards(int device, int n_shards, int n_ticks, int maps_per_shard, const void *d_shards, long long shard_cap,
                               const int *d_shard_offsets, void *d_merged, long long merged_cap, int *d_merged_offsets, void *stream)
 {
-    return lsn::guarded<int>("lsnMergeShards", static_cast<int>(-1), [&]() { return lsnMergeShards_impl(device, n_shards, n_ticks, maps_per_shard, d_shards, shard_cap, d_shard_offsets, d_merged, merged_cap, d_merged_offsets, stream); });
+    return lsn::guarded("lsnMergeShards", -1, [&]() {
+        lsn::clear_error();
+        return lsn::merge_shards(device, n_shards, n_ticks, maps_per_shard, d_shards, shard_cap, d_shard_offsets, d_merged, merged_cap, d_merged_offsets,
+                                 false, stream);
+    });
 }
 
 int lsn::merge_shards(int device, int n_shards, int n_ticks, int maps_per_shard, const void *d_shards, long long shard_cap,
@@ -660,284 +638,255 @@ struct LsnShard {
     std::mutex mu;
 };
 
-static int lsnShardUniqueId_impl(unsigned char *id128)
-{
-    lsn::clear_error();
-    if (!id128) return -1;
-    Rccl *r = rccl();
-    if (!r) return -1;
-    static_assert(sizeof(ncclUniqueId) == 128, "ncclUniqueId is 128 bytes");
-    ncclUniqueId id;
-    LSN_NCCL(r->GetUniqueId(&id));
-    memcpy(id128, &id, 128);
-    return 0;
-}
-
 extern "C" int lsnShardUniqueId(unsigned char *id128)
 {
-    return lsn::guarded<int>("lsnShardUniqueId", static_cast<int>(-1), [&]() { return lsnShardUniqueId_impl(id128); });
-}
-
-static void lsnShardDestroy_impl(LsnShard *sh)
-{
-    if (!sh) return;
-    (void)hipSetDevice(sh->device);
-    if (sh->comm && rccl()) (void)rccl()->CommDestroy(sh->comm);
-    if (sh->local) lsnFusionDestroy(sh->local);
-    if (sh->whole) lsnFusionDestroy(sh->whole);
-    if (sh->h_goff) (void)hipHostFree(sh->h_goff);
-    if (sh->ev_off) (void)hipEventDestroy(sh->ev_off);
-    if (sh->ev_pre) (void)hipEventDestroy(sh->ev_pre);
-    for (hipEvent_t e : sh->ev_chunk) (void)hipEventDestroy(e);
-    if (sh->comm_stream) (void)hipStreamDestroy(sh->comm_stream);
-    delete sh;
+    return lsn::guarded("lsnShardUniqueId", -1, [&]() {
+        lsn::clear_error();
+        if (!id128) return -1;
+        Rccl *r = rccl();
+        if (!r) return -1;
+        static_assert(sizeof(ncclUniqueId) == 128, "ncclUniqueId is 128 bytes");
+        ncclUniqueId id;
+        LSN_NCCL(r->GetUniqueId(&id));
+        memcpy(id128, &id, 128);
+        return 0;
+    });
 }
 
 extern "C" void lsnShardDestroy(LsnShard *sh)
 {
-    lsn::guarded_void("lsnShardDestroy", [&]() { lsnShardDestroy_impl(sh); });
-}
-
-static LsnShard * lsnShardPrepare_impl(int device, int rank, int world, int n_ticks, int n_maps, const int *widths, const int *heights)
-{
-    lsn::clear_error();
-    if (world <= 0 || rank < 0 || rank >= world || n_ticks <= 0 || n_maps <= 0 || !widths || !heights || n_maps % world != 0) {
-        lsn::set_error("lsnShardPrepare: bad arguments (rank %d of %d, %d sensors must split evenly)", rank, world, n_maps);
-        return nullptr;
-    }
-    bool uniform = true;
-    for (int i = 0; i < n_maps; i++) uniform = uniform && widths[i] == widths[0] && heights[i] == heights[0] && widths[i] % 8 == 0;
-    const int per_rank = n_maps / world;
-    // the vertex exchange needs equally shaped shards as well (an all-gather moves equal blocks): every rank's block must have
-    // the same pixel capacity
-    long long cap0 = 0;
-    for (int q = 0; q < world; q++) {
-        long long capq = 0;
-        for (int i = 0; i < per_rank; i++) capq += (long long)widths[q * per_rank + i] * heights[q * per_rank + i];
-        if (q == 0) cap0 = capq;
-        if (capq != cap0) {
-            lsn::set_error("lsnShardPrepare: the ranks' sensor blocks must hold the same number of pixels (%lld vs %lld)", cap0, capq);
-            return nullptr;
-        }
-    }
-    Rccl *r = rccl();
-    if (!r) return nullptr;
-    LSN_HIP_NULL(hipSetDevice(device));
-    LsnShard *sh = new (std::nothrow) LsnShard();
-    if (!sh) return nullptr;
-    sh->device = device;
-    sh->rank = rank;
-    sh->world = world;
-    sh->n_ticks = n_ticks;
-    sh->n_maps = n_maps;
-    sh->mpr = n_maps / world;
-    sh->vertex_mode = !uniform || (getenv("LSN_SHARD_VERTICES") && atoi(getenv("LSN_SHARD_VERTICES")) != 0);
-    if (const char *e = getenv("LSN_SHARD_PADDED")) sh->padded = atoi(e) != 0;
-    // One shot on the caller's stream unless $LSN_SHARD_CHUNKS asks for the pipelined form (collectives on a second stream beside the
-    // reconstruction): that form has only ever run with the shared-memory test double and with one real rank -- it stays opt-in until
-    // a run on a multi-GPU node has verified it.
-    sh->chunks = 1;
-    if (const char *e = getenv("LSN_SHARD_CHUNKS")) sh->chunks = atoi(e);
-    if (sh->chunks < 1) sh->chunks = 1;
-    if (sh->chunks > 16) sh->chunks = 16;
-    if (sh->chunks > n_ticks) sh->chunks = n_ticks;
-    sh->local = lsnFusionCreate(device, n_ticks, sh->mpr, widths + rank * sh->mpr, heights + rank * sh->mpr);
-    sh->whole = lsnFusionCreate(device, n_ticks, n_maps, widths, heights);
-    bool bad = !sh->local || !sh->whole;
-    if (!bad) {
-        sh->cap_loc = sh->local->cap;
-        sh->tiles_loc = sh->local->tiles_per_tick;
-        const size_t T = (size_t)n_ticks, W = (size_t)world, cap = (size_t)sh->cap_loc;
-        if (sh->vertex_mode) {
-            bad |= sh->v_local.reserve(T * cap * 16) != 0;
-            bad |= sh->v_gathered.reserve(W * T * cap * 16) != 0;
-        }
-        bad |= sh->mask.reserve(T * cap / 8) != 0;
-        // a chunk's send starts at the rank's own tick start and is as long as the LONGEST rank's chunk: room to read past the end
-        const size_t chunk_cap = ((T + sh->chunks - 1) / sh->chunks) * cap + 64;
-        bad |= sh->depth_c.reserve((T * cap + chunk_cap) * 2 + 64) != 0;
-        bad |= sh->rgb_c.reserve((T * cap + chunk_cap) * 3 + 64) != 0;
-        bad |= sh->offsets.reserve(sizeof(int) * T * (sh->mpr + 1)) != 0;
-        bad |= sh->tick_base.reserve(sizeof(int) * T) != 0;
-        bad |= sh->g_off.reserve(sizeof(int) * W * T * (sh->mpr + 1)) != 0;
-        bad |= sh->g_tp.reserve(sizeof(int) * W * T * sh->tiles_loc) != 0;
-        bad |= sh->g_mask.reserve(W * T * cap / 8) != 0;
-        bad |= sh->g_dc.reserve(W * (T * cap + 8 * 16 + 64) * 2) != 0;
-        bad |= sh->g_cc.reserve(W * (T * cap + 8 * 16 + 64) * 3) != 0;
-        bad |= sh->g_tick_base.reserve(sizeof(int) * W * T) != 0;
-        bad |= sh->merged.reserve((size_t)sh->whole->cap * 16 * T) != 0;
-        bad |= sh->merged_off.reserve(sizeof(int) * T * (n_maps + 1)) != 0;
-        bad |= hipHostMalloc((void **)&sh->h_goff, sizeof(int) * W * T * (sh->mpr + 1), hipHostMallocDefault) != hipSuccess;
-        bad |= hipEventCreateWithFlags(&sh->ev_off, hipEventDisableTiming) != hipSuccess;
-        bad |= hipEventCreateWithFlags(&sh->ev_pre, hipEventDisableTiming) != hipSuccess;
-        bad |= hipStreamCreateWithFlags(&sh->comm_stream, hipStreamNonBlocking) != hipSuccess;
-        for (int c = 0; c < sh->chunks && !bad; c++) {
-            hipEvent_t e = nullptr;
-            bad |= hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess;
-            if (e) sh->ev_chunk.push_back(e);
-        }
-    }
-    if (bad) {
-        if (!lsn::has_error()) lsn::set_error("lsnShardPrepare: allocation failed: %s", hipGetErrorString(hipGetLastError()));
-        lsnShardDestroy(sh);
-        return nullptr;
-    }
-    return sh;
+    lsn::guarded_void("lsnShardDestroy", [&]() {
+        if (!sh) return;
+        (void)hipSetDevice(sh->device);
+        if (sh->comm && rccl()) (void)rccl()->CommDestroy(sh->comm);
+        if (sh->local) lsnFusionDestroy(sh->local);
+        if (sh->whole) lsnFusionDestroy(sh->whole);
+        if (sh->h_goff) (void)hipHostFree(sh->h_goff);
+        if (sh->ev_off) (void)hipEventDestroy(sh->ev_off);
+        if (sh->ev_pre) (void)hipEventDestroy(sh->ev_pre);
+        for (hipEvent_t e : sh->ev_chunk) (void)hipEventDestroy(e);
+        if (sh->comm_stream) (void)hipStreamDestroy(sh->comm_stream);
+        delete sh;
+    });
 }
 
 extern "C" LsnShard * lsnShardPrepare(int device, int rank, int world, int n_ticks, int n_maps, const int *widths, const int *heights)
 {
-    return lsn::guarded<LsnShard *>("lsnShardPrepare", static_cast<LsnShard *>(nullptr), [&]() { return lsnShardPrepare_impl(device, rank, world, n_ticks, n_maps, widths, heights); });
-}
-
-static int lsnShardConnect_impl(LsnShard *sh, const unsigned char *id128)
-{
-    lsn::clear_error();
-    if (!sh || !id128) {
-        lsn::set_error("lsnShardConnect: null argument");
-        return -1;
-    }
-    Rccl *r = rccl();
-    if (!r) return -1;
-    std::lock_guard<std::mutex> g(sh->mu);
-    if (sh->comm) {
-        lsn::set_error("lsnShardConnect: already connected");
-        return -1;
-    }
-    LSN_HIP(hipSetDevice(sh->device));
-    ncclUniqueId id;
-    memcpy(&id, id128, 128);
-    const ncclResult_t rc = r->CommInitRank(&sh->comm, sh->world, id, sh->rank);   // blocks until every rank of the world has called it
-    if (rc != ncclSuccess) {
-        lsn::set_error("lsnShardConnect: ncclCommInitRank failed: %s", r->GetErrorString(rc));
-        sh->comm = nullptr;
-        return -1;
-    }
-    return 0;
+    return lsn::guarded("lsnShardPrepare", static_cast<LsnShard *>(nullptr), [&]() -> LsnShard * {
+        lsn::clear_error();
+        if (world <= 0 || rank < 0 || rank >= world || n_ticks <= 0 || n_maps <= 0 || !widths || !heights || n_maps % world != 0) {
+            lsn::set_error("lsnShardPrepare: bad arguments (rank %d of %d, %d sensors must split evenly)", rank, world, n_maps);
+            return nullptr;
+        }
+        bool uniform = true;
+        for (int i = 0; i < n_maps; i++) uniform = uniform && widths[i] == widths[0] && heights[i] == heights[0] && widths[i] % 8 == 0;
+        const int per_rank = n_maps / world;
+        // the vertex exchange needs equally shaped shards as well (an all-gather moves equal blocks): every rank's block must have
+        // the same pixel capacity
+        long long cap0 = 0;
+        for (int q = 0; q < world; q++) {
+            long long capq = 0;
+            for (int i = 0; i < per_rank; i++) capq += (long long)widths[q * per_rank + i] * heights[q * per_rank + i];
+            if (q == 0) cap0 = capq;
+            if (capq != cap0) {
+                lsn::set_error("lsnShardPrepare: the ranks' sensor blocks must hold the same number of pixels (%lld vs %lld)", cap0, capq);
+                return nullptr;
+            }
+        }
+        Rccl *r = rccl();
+        if (!r) return nullptr;
+        LSN_HIP_NULL(hipSetDevice(device));
+        LsnShard *sh = new (std::nothrow) LsnShard();
+        if (!sh) return nullptr;
+        sh->device = device;
+        sh->rank = rank;
+        sh->world = world;
+        sh->n_ticks = n_ticks;
+        sh->n_maps = n_maps;
+        sh->mpr = n_maps / world;
+        sh->vertex_mode = !uniform || (getenv("LSN_SHARD_VERTICES") && atoi(getenv("LSN_SHARD_VERTICES")) != 0);
+        if (const char *e = getenv("LSN_SHARD_PADDED")) sh->padded = atoi(e) != 0;
+        // One shot on the caller's stream unless $LSN_SHARD_CHUNKS asks for the pipelined form (collectives on a second stream beside the
+        // reconstruction): that form has only ever run with the shared-memory test double and with one real rank -- it stays opt-in until
+        // a run on a multi-GPU node has verified it.
+        sh->chunks = 1;
+        if (const char *e = getenv("LSN_SHARD_CHUNKS")) sh->chunks = atoi(e);
+        if (sh->chunks < 1) sh->chunks = 1;
+        if (sh->chunks > 16) sh->chunks = 16;
+        if (sh->chunks > n_ticks) sh->chunks = n_ticks;
+        sh->local = lsnFusionCreate(device, n_ticks, sh->mpr, widths + rank * sh->mpr, heights + rank * sh->mpr);
+        sh->whole = lsnFusionCreate(device, n_ticks, n_maps, widths, heights);
+        bool bad = !sh->local || !sh->whole;
+        if (!bad) {
+            sh->cap_loc = sh->local->cap;
+            sh->tiles_loc = sh->local->tiles_per_tick;
+            const size_t T = (size_t)n_ticks, W = (size_t)world, cap = (size_t)sh->cap_loc;
+            if (sh->vertex_mode) {
+                bad |= sh->v_local.reserve(T * cap * 16) != 0;
+                bad |= sh->v_gathered.reserve(W * T * cap * 16) != 0;
+            }
+            bad |= sh->mask.reserve(T * cap / 8) != 0;
+            // a chunk's send starts at the rank's own tick start and is as long as the LONGEST rank's chunk: room to read past the end
+            const size_t chunk_cap = ((T + sh->chunks - 1) / sh->chunks) * cap + 64;
+            bad |= sh->depth_c.reserve((T * cap + chunk_cap) * 2 + 64) != 0;
+            bad |= sh->rgb_c.reserve((T * cap + chunk_cap) * 3 + 64) != 0;
+            bad |= sh->offsets.reserve(sizeof(int) * T * (sh->mpr + 1)) != 0;
+            bad |= sh->tick_base.reserve(sizeof(int) * T) != 0;
+            bad |= sh->g_off.reserve(sizeof(int) * W * T * (sh->mpr + 1)) != 0;
+            bad |= sh->g_tp.reserve(sizeof(int) * W * T * sh->tiles_loc) != 0;
+            bad |= sh->g_mask.reserve(W * T * cap / 8) != 0;
+            bad |= sh->g_dc.reserve(W * (T * cap + 8 * 16 + 64) * 2) != 0;
+            bad |= sh->g_cc.reserve(W * (T * cap + 8 * 16 + 64) * 3) != 0;
+            bad |= sh->g_tick_base.reserve(sizeof(int) * W * T) != 0;
+            bad |= sh->merged.reserve((size_t)sh->whole->cap * 16 * T) != 0;
+            bad |= sh->merged_off.reserve(sizeof(int) * T * (n_maps + 1)) != 0;
+            bad |= hipHostMalloc((void **)&sh->h_goff, sizeof(int) * W * T * (sh->mpr + 1), hipHostMallocDefault) != hipSuccess;
+            bad |= hipEventCreateWithFlags(&sh->ev_off, hipEventDisableTiming) != hipSuccess;
+            bad |= hipEventCreateWithFlags(&sh->ev_pre, hipEventDisableTiming) != hipSuccess;
+            bad |= hipStreamCreateWithFlags(&sh->comm_stream, hipStreamNonBlocking) != hipSuccess;
+            for (int c = 0; c < sh->chunks && !bad; c++) {
+                hipEvent_t e = nullptr;
+                bad |= hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess;
+                if (e) sh->ev_chunk.push_back(e);
+            }
+        }
+        if (bad) {
+            if (!lsn::has_error()) lsn::set_error("lsnShardPrepare: allocation failed: %s", hipGetErrorString(hipGetLastError()));
+            lsnShardDestroy(sh);
+            return nullptr;
+        }
+        return sh;
+    });
 }
 
 extern "C" int lsnShardConnect(LsnShard *sh, const unsigned char *id128)
 {
-    return lsn::guarded<int>("lsnShardConnect", static_cast<int>(-1), [&]() { return lsnShardConnect_impl(sh, id128); });
-}
-
-static LsnShard * lsnShardCreate_impl(int device, int rank, int world, const unsigned char *id128, int n_ticks, int n_maps, const int *widths,
-                                    const int *heights)
-{
-    if (!id128) {
+    return lsn::guarded("lsnShardConnect", -1, [&]() {
         lsn::clear_error();
-        lsn::set_error("lsnShardCreate: null id");
-        return nullptr;
-    }
-    LsnShard *sh = lsnShardPrepare(device, rank, world, n_ticks, n_maps, widths, heights);
-    if (!sh) return nullptr;
-    if (lsnShardConnect(sh, id128)) {
-        const std::string why = lsn::error_buffer();
-        lsnShardDestroy(sh);
-        lsn::set_error("%s", why.c_str());
-        return nullptr;
-    }
-    return sh;
+        if (!sh || !id128) {
+            lsn::set_error("lsnShardConnect: null argument");
+            return -1;
+        }
+        Rccl *r = rccl();
+        if (!r) return -1;
+        std::lock_guard<std::mutex> g(sh->mu);
+        if (sh->comm) {
+            lsn::set_error("lsnShardConnect: already connected");
+            return -1;
+        }
+        LSN_HIP(hipSetDevice(sh->device));
+        ncclUniqueId id;
+        memcpy(&id, id128, 128);
+        const ncclResult_t rc = r->CommInitRank(&sh->comm, sh->world, id, sh->rank);   // blocks until every rank of the world has called it
+        if (rc != ncclSuccess) {
+            lsn::set_error("lsnShardConnect: ncclCommInitRank failed: %s", r->GetErrorString(rc));
+            sh->comm = nullptr;
+            return -1;
+        }
+        return 0;
+    });
 }
 
 extern "C" LsnShard * lsnShardCreate(int device, int rank, int world, const unsigned char *id128, int n_ticks, int n_maps, const int *widths,
                                     const int *heights)
 {
-    return lsn::guarded<LsnShard *>("lsnShardCreate", static_cast<LsnShard *>(nullptr), [&]() { return lsnShardCreate_impl(device, rank, world, id128, n_ticks, n_maps, widths, heights); });
-}
-
-static int lsnShardRcclPath_impl(char *buf, int len)
-{
-    Rccl *r = rccl();
-    if (!r) return -1;
-    if (buf && len > 0) snprintf(buf, (size_t)len, "%s", r->path.c_str());
-    return (int)r->path.size();
+    return lsn::guarded("lsnShardCreate", static_cast<LsnShard *>(nullptr), [&]() -> LsnShard * {
+        if (!id128) {
+            lsn::clear_error();
+            lsn::set_error("lsnShardCreate: null id");
+            return nullptr;
+        }
+        LsnShard *sh = lsnShardPrepare(device, rank, world, n_ticks, n_maps, widths, heights);
+        if (!sh) return nullptr;
+        if (lsnShardConnect(sh, id128)) {
+            const std::string why = lsn::error_buffer();
+            lsnShardDestroy(sh);
+            lsn::set_error("%s", why.c_str());
+            return nullptr;
+        }
+        return sh;
+    });
 }
 
 extern "C" int lsnShardRcclPath(char *buf, int len)
 {
-    return lsn::guarded<int>("lsnShardRcclPath", static_cast<int>(-1), [&]() { return lsnShardRcclPath_impl(buf, len); });
+    return lsn::guarded("lsnShardRcclPath", -1, [&]() {
+        Rccl *r = rccl();
+        if (!r) return -1;
+        if (buf && len > 0) snprintf(buf, (size_t)len, "%s", r->path.c_str());
+        return (int)r->path.size();
+    });
 }
 
 // What the connected communicator itself reports: its rank count, or -1 (not connected / the RCCL in use lacks ncclCommCount / the
 // communicator's own rank differs from the handle's).  bench.py puts it into the N > 1 line as n_ranks_seen.
-static int lsnShardRanksSeen_impl(LsnShard *sh)
-{
-    lsn::clear_error();
-    Rccl *r = rccl();
-    if (!sh || !r) return -1;
-    std::lock_guard<std::mutex> g(sh->mu);
-    if (!sh->comm || !r->CommCount) {
-        lsn::set_error("lsnShardRanksSeen: %s", !sh->comm ? "the handle is not connected" : "this RCCL has no ncclCommCount");
-        return -1;
-    }
-    int n = -1, me = sh->rank;
-    LSN_NCCL(r->CommCount(sh->comm, &n));
-    if (r->CommUserRank) LSN_NCCL(r->CommUserRank(sh->comm, &me));
-    if (me != sh->rank) {
-        lsn::set_error("lsnShardRanksSeen: the communicator says rank %d, the handle %d", me, sh->rank);
-        return -1;
-    }
-    return n;
-}
-
 extern "C" int lsnShardRanksSeen(LsnShard *sh)
 {
-    return lsn::guarded<int>("lsnShardRanksSeen", static_cast<int>(-1), [&]() { return lsnShardRanksSeen_impl(sh); });
+    return lsn::guarded("lsnShardRanksSeen", -1, [&]() {
+        lsn::clear_error();
+        Rccl *r = rccl();
+        if (!sh || !r) return -1;
+        std::lock_guard<std::mutex> g(sh->mu);
+        if (!sh->comm || !r->CommCount) {
+            lsn::set_error("lsnShardRanksSeen: %s", !sh->comm ? "the handle is not connected" : "this RCCL has no ncclCommCount");
+            return -1;
+        }
+        int n = -1, me = sh->rank;
+        LSN_NCCL(r->CommCount(sh->comm, &n));
+        if (r->CommUserRank) LSN_NCCL(r->CommUserRank(sh->comm, &me));
+        if (me != sh->rank) {
+            lsn::set_error("lsnShardRanksSeen: the communicator says rank %d, the handle %d", me, sh->rank);
+            return -1;
+        }
+        return n;
+    });
 }
 
 extern "C" LsnFusion *lsnShardPlan(LsnShard *sh, int whole) { return sh ? (whole ? sh->whole : sh->local) : nullptr; }
 extern "C" long long lsnShardMergedCapacity(const LsnShard *sh) { return sh && sh->whole ? sh->whole->cap : 0; }
 extern "C" long long lsnShardLastBytesSent(const LsnShard *sh) { return sh ? sh->last_bytes_per_rank : 0; }
 
-static int lsnShardSetParams_impl(LsnShard *sh, const float *intr_all, const float *wt_all, const float *bounds6, void *stream)
-{
-    lsn::clear_error();
-    if (!sh || !intr_all || !wt_all || !bounds6) {
-        lsn::set_error("lsnShardSetParams: null argument");
-        return -1;
-    }
-    if (lsnFusionSetParams(sh->whole, intr_all, wt_all, bounds6, stream)) return -1;
-    return lsnFusionSetParams(sh->local, intr_all + 7 * (size_t)sh->rank * sh->mpr, wt_all + 12 * (size_t)sh->rank * sh->mpr, bounds6, stream);
-}
-
 extern "C" int lsnShardSetParams(LsnShard *sh, const float *intr_all, const float *wt_all, const float *bounds6, void *stream)
 {
-    return lsn::guarded<int>("lsnShardSetParams", static_cast<int>(-1), [&]() { return lsnShardSetParams_impl(sh, intr_all, wt_all, bounds6, stream); });
+    return lsn::guarded("lsnShardSetParams", -1, [&]() {
+        lsn::clear_error();
+        if (!sh || !intr_all || !wt_all || !bounds6) {
+            lsn::set_error("lsnShardSetParams: null argument");
+            return -1;
+        }
+        if (lsnFusionSetParams(sh->whole, intr_all, wt_all, bounds6, stream)) return -1;
+        return lsnFusionSetParams(sh->local, intr_all + 7 * (size_t)sh->rank * sh->mpr, wt_all + 12 * (size_t)sh->rank * sh->mpr, bounds6, stream);
+    });
 }
 
 static int shard_step(LsnShard *sh, const void *d_depth_local, const void *d_colors_local, void **d_merged, int **d_merged_offsets, void *stream);
 
-static int lsnShardStep_impl(LsnShard *sh, const void *d_depth_local, const void *d_colors_local, void **d_merged, int **d_merged_offsets,
-                            void *stream)
-{
-    lsn::clear_error();
-    if (!sh || !d_depth_local || !d_colors_local) {
-        lsn::set_error("lsnShardStep: null argument");
-        return -1;
-    }
-    std::lock_guard<std::mutex> g(sh->mu);
-    if (!sh->comm) {
-        lsn::set_error("lsnShardStep: the handle is not connected (lsnShardConnect)");
-        return -1;
-    }
-    if (sh->failed) {
-        // a collective of an earlier step failed: the ranks' communicators are no longer in step, nothing further may be queued on them
-        lsn::set_error("lsnShardStep: an earlier step failed (%s); destroy the handle", sh->failure.c_str());
-        return -1;
-    }
-    const int rc = shard_step(sh, d_depth_local, d_colors_local, d_merged, d_merged_offsets, stream);
-    if (rc) {
-        sh->failed = true;
-        sh->failure = lsn::error_buffer();
-    }
-    return rc;
-}
-
 extern "C" int lsnShardStep(LsnShard *sh, const void *d_depth_local, const void *d_colors_local, void **d_merged, int **d_merged_offsets,
                             void *stream)
 {
-    return lsn::guarded<int>("lsnShardStep", static_cast<int>(-1), [&]() { return lsnShardStep_impl(sh, d_depth_local, d_colors_local, d_merged, d_merged_offsets, stream); });
+    return lsn::guarded("lsnShardStep", -1, [&]() {
+        lsn::clear_error();
+        if (!sh || !d_depth_local || !d_colors_local) {
+            lsn::set_error("lsnShardStep: null argument");
+            return -1;
+        }
+        std::lock_guard<std::mutex> g(sh->mu);
+        if (!sh->comm) {
+            lsn::set_error("lsnShardStep: the handle is not connected (lsnShardConnect)");
+            return -1;
+        }
+        if (sh->failed) {
+            // a collective of an earlier step failed: the ranks' communicators are no longer in step, nothing further may be queued on them
+            lsn::set_error("lsnShardStep: an earlier step failed (%s); destroy the handle", sh->failure.c_str());
+            return -1;
+        }
+        const int rc = shard_step(sh, d_depth_local, d_colors_local, d_merged, d_merged_offsets, stream);
+        if (rc) {
+            sh->failed = true;
+            sh->failure = lsn::error_buffer();
+        }
+        return rc;
+    });
 }
 
 static int shard_step(LsnShard *sh, const void *d_depth_local, const void *d_colors_local, void **d_merged, int **d_merged_offsets, void *stream)

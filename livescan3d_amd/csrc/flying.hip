@@ -227,53 +227,45 @@ int lsn::flying_pixels(LsnFusion *p, int neighbourhood, int threshold, const voi
     return 0;
 }
 
-static int lsnFusionFlyingPixels_impl(LsnFusion *p, int neighbourhood, int threshold, const void *d_depth_in, void *d_depth_out, void *stream)
-{
-    lsn::clear_error();
-    if (!p || !d_depth_in || !d_depth_out) {
-        lsn::set_error("lsnFusionFlyingPixels: null argument");
-        return -1;
-    }
-    return lsn::flying_pixels(p, neighbourhood, threshold, d_depth_in, d_depth_out, lsn::as_stream(stream));
-}
-
 extern "C" int lsnFusionFlyingPixels(LsnFusion *p, int neighbourhood, int threshold, const void *d_depth_in, void *d_depth_out, void *stream)
 {
-    return lsn::guarded<int>("lsnFusionFlyingPixels", static_cast<int>(-1),
-                             [&]() { return lsnFusionFlyingPixels_impl(p, neighbourhood, threshold, d_depth_in, d_depth_out, stream); });
-}
-
-static int lsnFusionFlyingDiagnostics_impl(LsnFusion *p, int tick, int *removed_per_sensor, void *stream)
-{
-    lsn::clear_error();
-    if (!p || tick < 0 || tick >= p->n_ticks) {
-        lsn::set_error("lsnFusionFlyingDiagnostics: bad arguments");
-        return -1;
-    }
-    std::lock_guard<std::mutex> g(p->mu);
-    if (p->fl_last == 0) {
-        lsn::set_error("lsnFusionFlyingDiagnostics: the plan has not run the filter");
-        return -1;
-    }
-    LSN_HIP(hipSetDevice(p->device));
-    std::vector<int> per(p->n_maps, 0);
-    if (p->fl_last == 2) {
-        std::vector<int> counts((size_t)p->fl_tiles_per_tick);
-        LSN_HIP(hipStreamSynchronize(lsn::as_stream(stream)));
-        if (p->fl_stream != lsn::as_stream(stream)) LSN_HIP(hipStreamSynchronize(p->fl_stream));
-        LSN_HIP(hipMemcpy(counts.data(), p->fl_counts.as<int>() + (size_t)tick * p->fl_tiles_per_tick, sizeof(int) * counts.size(), hipMemcpyDeviceToHost));
-        for (size_t t = 0; t < counts.size(); t++) per[p->fl_tile_frame[t]] += counts[t];
-    }
-    long long total = 0;
-    for (int f = 0; f < p->n_maps; f++) {
-        if (removed_per_sensor) removed_per_sensor[f] = per[f];
-        total += per[f];
-    }
-    return (int)total;
+    return lsn::guarded("lsnFusionFlyingPixels", -1, [&]() {
+        lsn::clear_error();
+        if (!p || !d_depth_in || !d_depth_out) {
+            lsn::set_error("lsnFusionFlyingPixels: null argument");
+            return -1;
+        }
+        return lsn::flying_pixels(p, neighbourhood, threshold, d_depth_in, d_depth_out, lsn::as_stream(stream));
+    });
 }
 
 extern "C" int lsnFusionFlyingDiagnostics(LsnFusion *p, int tick, int *removed_per_sensor, void *stream)
 {
-    return lsn::guarded<int>("lsnFusionFlyingDiagnostics", static_cast<int>(-1),
-                             [&]() { return lsnFusionFlyingDiagnostics_impl(p, tick, removed_per_sensor, stream); });
+    return lsn::guarded("lsnFusionFlyingDiagnostics", -1, [&]() {
+        lsn::clear_error();
+        if (!p || tick < 0 || tick >= p->n_ticks) {
+            lsn::set_error("lsnFusionFlyingDiagnostics: bad arguments");
+            return -1;
+        }
+        std::lock_guard<std::mutex> g(p->mu);
+        if (p->fl_last == 0) {
+            lsn::set_error("lsnFusionFlyingDiagnostics: the plan has not run the filter");
+            return -1;
+        }
+        LSN_HIP(hipSetDevice(p->device));
+        std::vector<int> per(p->n_maps, 0);
+        if (p->fl_last == 2) {
+            std::vector<int> counts((size_t)p->fl_tiles_per_tick);
+            LSN_HIP(hipStreamSynchronize(lsn::as_stream(stream)));
+            if (p->fl_stream != lsn::as_stream(stream)) LSN_HIP(hipStreamSynchronize(p->fl_stream));
+            LSN_HIP(hipMemcpy(counts.data(), p->fl_counts.as<int>() + (size_t)tick * p->fl_tiles_per_tick, sizeof(int) * counts.size(), hipMemcpyDeviceToHost));
+            for (size_t t = 0; t < counts.size(); t++) per[p->fl_tile_frame[t]] += counts[t];
+        }
+        long long total = 0;
+        for (int f = 0; f < p->n_maps; f++) {
+            if (removed_per_sensor) removed_per_sensor[f] = per[f];
+            total += per[f];
+        }
+        return (int)total;
+    });
 }

@@ -650,133 +650,127 @@ __global__ __launch_bounds__(kThreads) void table_kernel(const FrameDesc *frames
 // host side
 // -------------------------------------------------------------------------------------------------------------
 
-static LsnFusion * lsnFusionCreate_impl(int device, int n_ticks, int n_maps, const int *widths, const int *heights)
+extern "C" LsnFusion * lsnFusionCreate(int device, int n_ticks, int n_maps, const int *widths, const int *heights)
 {
-    lsn::clear_error();
-    if (n_ticks <= 0 || n_maps <= 0 || !widths || !heights) {
-        lsn::set_error("lsnFusionCreate: bad arguments (n_ticks=%d n_maps=%d)", n_ticks, n_maps);
-        return nullptr;
-    }
-    LSN_HIP_NULL(hipSetDevice(device));
-    LsnFusion *p = new (std::nothrow) LsnFusion();
-    if (!p) return nullptr;
-    p->device = device;
-    if (const char *env = getenv("LSN_NO_THRESHOLDS")) p->thr_enabled = atoi(env) == 0;
-    if (const char *env = getenv("LSN_LAZY_RGB")) p->lazy_rgb = atoi(env) != 0;
+    return lsn::guarded("lsnFusionCreate", static_cast<LsnFusion *>(nullptr), [&]() -> LsnFusion * {
+        lsn::clear_error();
+        if (n_ticks <= 0 || n_maps <= 0 || !widths || !heights) {
+            lsn::set_error("lsnFusionCreate: bad arguments (n_ticks=%d n_maps=%d)", n_ticks, n_maps);
+            return nullptr;
+        }
+        LSN_HIP_NULL(hipSetDevice(device));
+        LsnFusion *p = new (std::nothrow) LsnFusion();
+        if (!p) return nullptr;
+        p->device = device;
+        if (const char *env = getenv("LSN_NO_THRESHOLDS")) p->thr_enabled = atoi(env) == 0;
+        if (const char *env = getenv("LSN_LAZY_RGB")) p->lazy_rgb = atoi(env) != 0;
 
-    p->n_ticks = n_ticks;
-    p->n_maps = n_maps;
-    std::vector<FrameDesc> fr(n_maps);
-    std::vector<TileDesc> tf;
-    long long doff = 0, coff = 0;
-    int tiles = 0, xoff = 0, yoff = 0;
-    bool vec = true;
-    for (int i = 0; i < n_maps; i++) {
-        if (widths[i] <= 0 || heights[i] <= 0 || (long long)widths[i] * heights[i] > (1ll << 30)) {
-            lsn::set_error("lsnFusionCreate: bad frame size %dx%d", widths[i], heights[i]);
+        p->n_ticks = n_ticks;
+        p->n_maps = n_maps;
+        std::vector<FrameDesc> fr(n_maps);
+        std::vector<TileDesc> tf;
+        long long doff = 0, coff = 0;
+        int tiles = 0, xoff = 0, yoff = 0;
+        bool vec = true;
+        for (int i = 0; i < n_maps; i++) {
+            if (widths[i] <= 0 || heights[i] <= 0 || (long long)widths[i] * heights[i] > (1ll << 30)) {
+                lsn::set_error("lsnFusionCreate: bad frame size %dx%d", widths[i], heights[i]);
+                delete p;
+                return nullptr;
+            }
+            p->w.push_back(widths[i]);
+            p->h.push_back(heights[i]);
+            const int npix = widths[i] * heights[i];
+            fr[i].w = widths[i];
+            fr[i].h = heights[i];
+            fr[i].npix = npix;
+            fr[i].tile_start = tiles;
+            p->tile_start.push_back(tiles);
+            fr[i].depth_off = doff;
+            fr[i].rgb_off = coff;
+            fr[i].xtab_off = xoff;
+            fr[i].ytab_off = yoff;
+            fr[i].pad1 = 0;
+            xoff += (widths[i] + 7) & ~7;  // keeps every sensor's row 32-B aligned for the float4 loads
+            yoff += heights[i];
+            const int nt = (npix + kTile - 1) / kTile;
+            fr[i].inv_w = 1.0f / (float)widths[i];
+            for (int t = 0; t < nt; t++) {
+                const long long px = (long long)t * kTile;
+                TileDesc td;
+                td.frame = i;
+                td.y0 = (int)(px / widths[i]);
+                td.x0 = (int)(px % widths[i]);
+                td.pad = 0;
+                tf.push_back(td);
+            }
+            tiles += nt;
+            doff += npix;
+            coff += 3ll * npix;
+            // 16-B depth loads / 8-B colour loads need every frame to start 8-pixel aligned and rows not to split a lane
+            if (widths[i] % 8 != 0) vec = false;
+        }
+        p->cap = doff;
+        p->tick_depth_elems = doff;
+        p->tick_rgb_bytes = coff;
+        p->tiles_per_tick = tiles;
+        // one-tick plans of up to 2048 tiles take the single pass (run_form); $LSN_ONE_TICK_SINGLE_PASS=0 / 1 forces the three launches / the single pass
+        p->one_tick_single_pass = n_ticks == 1 && tiles <= 2048;
+        if (const char *env = getenv("LSN_ONE_TICK_SINGLE_PASS")) p->one_tick_single_pass = atoi(env) != 0;
+        p->tile_start.push_back(tiles);
+        p->vec_ok = vec;
+        if (doff > 0x7FFFFFFFll) {
+            lsn::set_error("lsnFusionCreate: a tick may not exceed 2^31-1 pixels (Mesh.nVertices is an int)");
             delete p;
             return nullptr;
         }
-        p->w.push_back(widths[i]);
-        p->h.push_back(heights[i]);
-        const int npix = widths[i] * heights[i];
-        fr[i].w = widths[i];
-        fr[i].h = heights[i];
-        fr[i].npix = npix;
-        fr[i].tile_start = tiles;
-        p->tile_start.push_back(tiles);
-        fr[i].depth_off = doff;
-        fr[i].rgb_off = coff;
-        fr[i].xtab_off = xoff;
-        fr[i].ytab_off = yoff;
-        fr[i].pad1 = 0;
-        xoff += (widths[i] + 7) & ~7;  // keeps every sensor's row 32-B aligned for the float4 loads
-        yoff += heights[i];
-        const int nt = (npix + kTile - 1) / kTile;
-        fr[i].inv_w = 1.0f / (float)widths[i];
-        for (int t = 0; t < nt; t++) {
-            const long long px = (long long)t * kTile;
-            TileDesc td;
-            td.frame = i;
-            td.y0 = (int)(px / widths[i]);
-            td.x0 = (int)(px % widths[i]);
-            td.pad = 0;
-            tf.push_back(td);
+        if ((long long)tiles * n_ticks > 0x7FFFFFFFll) {
+            lsn::set_error("lsnFusionCreate: too many tiles");
+            delete p;
+            return nullptr;
         }
-        tiles += nt;
-        doff += npix;
-        coff += 3ll * npix;
-        // 16-B depth loads / 8-B colour loads need every frame to start 8-pixel aligned and rows not to split a lane
-        if (widths[i] % 8 != 0) vec = false;
-    }
-    p->cap = doff;
-    p->tick_depth_elems = doff;
-    p->tick_rgb_bytes = coff;
-    p->tiles_per_tick = tiles;
-    // one-tick plans of up to 2048 tiles take the single pass (run_form); $LSN_ONE_TICK_SINGLE_PASS=0 / 1 forces the three launches / the single pass
-    p->one_tick_single_pass = n_ticks == 1 && tiles <= 2048;
-    if (const char *env = getenv("LSN_ONE_TICK_SINGLE_PASS")) p->one_tick_single_pass = atoi(env) != 0;
-    p->tile_start.push_back(tiles);
-    p->vec_ok = vec;
-    if (doff > 0x7FFFFFFFll) {
-        lsn::set_error("lsnFusionCreate: a tick may not exceed 2^31-1 pixels (Mesh.nVertices is an int)");
-        delete p;
-        return nullptr;
-    }
-    if ((long long)tiles * n_ticks > 0x7FFFFFFFll) {
-        lsn::set_error("lsnFusionCreate: too many tiles");
-        delete p;
-        return nullptr;
-    }
-    const size_t n_tiles_total = (size_t)tiles * n_ticks;
-    if (p->frames.reserve(sizeof(FrameDesc) * n_maps) || p->tile_frame.reserve(sizeof(TileDesc) * tf.size()) ||
-        p->params.reserve(sizeof(SensorParams) * n_maps) || p->tile_counts.reserve(sizeof(int) * n_tiles_total) ||
-        p->tile_state.reserve(sizeof(unsigned long long) * n_tiles_total) || p->misc.reserve(128 * ((size_t)n_ticks + 1)) ||
-        p->xtab.reserve(sizeof(float) * (size_t)(xoff + 8)) || p->ytab.reserve(sizeof(float) * (size_t)(yoff + 8))) {
-        delete p;
-        return nullptr;
-    }
-    if (hipMemset(p->misc.p, 0, 128 * ((size_t)n_ticks + 1)) != hipSuccess) {
-        lsn::set_error("lsnFusionCreate: scratch initialisation failed");
-        delete p;
-        return nullptr;
-    }
-    if (hipMemcpy(p->frames.p, fr.data(), sizeof(FrameDesc) * n_maps, hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(p->tile_frame.p, tf.data(), sizeof(TileDesc) * tf.size(), hipMemcpyHostToDevice) != hipSuccess) {
-        lsn::set_error("lsnFusionCreate: geometry upload failed");
-        delete p;
-        return nullptr;
-    }
-    return p;
-}
-
-extern "C" LsnFusion * lsnFusionCreate(int device, int n_ticks, int n_maps, const int *widths, const int *heights)
-{
-    return lsn::guarded<LsnFusion *>("lsnFusionCreate", static_cast<LsnFusion *>(nullptr), [&]() { return lsnFusionCreate_impl(device, n_ticks, n_maps, widths, heights); });
-}
-
-static void lsnFusionDestroy_impl(LsnFusion *p)
-{
-    if (!p) return;
-    (void)hipSetDevice(p->device);
-    for (auto &e : p->events) {
-        (void)hipEventDestroy(e.first);
-        (void)hipEventDestroy(e.second);
-    }
-    if (p->radial_done) (void)hipEventDestroy(p->radial_done);
-    if (p->side) {
-        (void)hipStreamSynchronize(p->side);
-        (void)hipStreamDestroy(p->side);
-        (void)hipEventDestroy(p->ev_counted);
-        (void)hipEventDestroy(p->ev_written[0]);
-        (void)hipEventDestroy(p->ev_written[1]);
-    }
-    delete p;
+        const size_t n_tiles_total = (size_t)tiles * n_ticks;
+        if (p->frames.reserve(sizeof(FrameDesc) * n_maps) || p->tile_frame.reserve(sizeof(TileDesc) * tf.size()) ||
+            p->params.reserve(sizeof(SensorParams) * n_maps) || p->tile_counts.reserve(sizeof(int) * n_tiles_total) ||
+            p->tile_state.reserve(sizeof(unsigned long long) * n_tiles_total) || p->misc.reserve(128 * ((size_t)n_ticks + 1)) ||
+            p->xtab.reserve(sizeof(float) * (size_t)(xoff + 8)) || p->ytab.reserve(sizeof(float) * (size_t)(yoff + 8))) {
+            delete p;
+            return nullptr;
+        }
+        if (hipMemset(p->misc.p, 0, 128 * ((size_t)n_ticks + 1)) != hipSuccess) {
+            lsn::set_error("lsnFusionCreate: scratch initialisation failed");
+            delete p;
+            return nullptr;
+        }
+        if (hipMemcpy(p->frames.p, fr.data(), sizeof(FrameDesc) * n_maps, hipMemcpyHostToDevice) != hipSuccess ||
+            hipMemcpy(p->tile_frame.p, tf.data(), sizeof(TileDesc) * tf.size(), hipMemcpyHostToDevice) != hipSuccess) {
+            lsn::set_error("lsnFusionCreate: geometry upload failed");
+            delete p;
+            return nullptr;
+        }
+        return p;
+    });
 }
 
 extern "C" void lsnFusionDestroy(LsnFusion *p)
 {
-    lsn::guarded_void("lsnFusionDestroy", [&]() { lsnFusionDestroy_impl(p); });
+    lsn::guarded_void("lsnFusionDestroy", [&]() {
+        if (!p) return;
+        (void)hipSetDevice(p->device);
+        for (auto &e : p->events) {
+            (void)hipEventDestroy(e.first);
+            (void)hipEventDestroy(e.second);
+        }
+        if (p->radial_done) (void)hipEventDestroy(p->radial_done);
+        if (p->side) {
+            (void)hipStreamSynchronize(p->side);
+            (void)hipStreamDestroy(p->side);
+            (void)hipEventDestroy(p->ev_counted);
+            (void)hipEventDestroy(p->ev_written[0]);
+            (void)hipEventDestroy(p->ev_written[1]);
+        }
+        delete p;
+    });
 }
 
 extern "C" long long lsnFusionTickCapacity(const LsnFusion *p) { return p ? p->cap : 0; }
@@ -793,119 +787,104 @@ static void pack_sensor_params(const float *ip, const float *tp, SensorParams &s
     s.r20 = tp[9]; s.r21 = tp[10]; s.r22 = tp[11];
 }
 
-static int lsnPackSensorParams_impl(const float *intr7, const float *wt12, float *out16)
-{
-    lsn::clear_error();
-    if (!intr7 || !wt12 || !out16) {
-        lsn::set_error("lsnPackSensorParams: null argument");
-        return -1;
-    }
-    SensorParams s;
-    pack_sensor_params(intr7, wt12, s);
-    static_assert(sizeof(SensorParams) == 16 * sizeof(float), "SensorParams is 16 floats");
-    memcpy(out16, &s, sizeof(s));
-    return 0;
-}
-
 extern "C" int lsnPackSensorParams(const float *intr7, const float *wt12, float *out16)
 {
-    return lsn::guarded<int>("lsnPackSensorParams", static_cast<int>(-1), [&]() { return lsnPackSensorParams_impl(intr7, wt12, out16); });
-}
-
-static int lsnFusionSetParams_impl(LsnFusion *p, const float *intr, const float *wt, const float *bounds6, void *stream)
-{
-    lsn::clear_error();
-    if (!p || !intr || !wt || !bounds6) {
-        lsn::set_error("lsnFusionSetParams: null argument");
-        return -1;
-    }
-    LSN_HIP(hipSetDevice(p->device));
-    {
-        // LiveScanServer passes the same calibration with every call (KinectServer.cs:470-490): nothing to do then
-        std::lock_guard<std::mutex> g(p->mu);
-        if (p->params_set && p->last_intr.size() == 7 * (size_t)p->n_maps &&
-            memcmp(p->last_intr.data(), intr, sizeof(float) * 7 * p->n_maps) == 0 &&
-            memcmp(p->last_wt.data(), wt, sizeof(float) * 12 * p->n_maps) == 0 && memcmp(p->bounds, bounds6, sizeof(p->bounds)) == 0)
-            return 0;
-    }
-    std::vector<SensorParams> sp(p->n_maps);
-    for (int i = 0; i < p->n_maps; i++) pack_sensor_params(intr + 7 * i, wt + 12 * i, sp[i]);
-    // pageable source: hipMemcpyAsync copies it out before returning, so the local vector may die
-    LSN_HIP(hipMemcpyAsync(p->params.p, sp.data(), sizeof(SensorParams) * p->n_maps, hipMemcpyHostToDevice,
-                           lsn::as_stream(stream)));
-    hipLaunchKernelGGL(table_kernel, dim3(8, (unsigned)p->n_maps), dim3(kThreads), 0, lsn::as_stream(stream), p->frames.as<FrameDesc>(),
-                       p->params.as<SensorParams>(), p->n_maps, p->xtab.as<float>(), p->ytab.as<float>());
-    LSN_HIP(hipGetLastError());
-    LSN_HIP(hipStreamSynchronize(lsn::as_stream(stream)));
-    std::lock_guard<std::mutex> g(p->mu);
-    memcpy(p->bounds, bounds6, sizeof(p->bounds));
-    p->last_intr.assign(intr, intr + 7 * (size_t)p->n_maps);
-    p->last_wt.assign(wt, wt + 12 * (size_t)p->n_maps);
-    p->params_set = true;
-    p->params_gen++;  // counts made ahead with the old parameters are void
-    p->thr_valid = false;
-    p->runs_with_params = 0;
-    return 0;
+    return lsn::guarded("lsnPackSensorParams", -1, [&]() {
+        lsn::clear_error();
+        if (!intr7 || !wt12 || !out16) {
+            lsn::set_error("lsnPackSensorParams: null argument");
+            return -1;
+        }
+        SensorParams s;
+        pack_sensor_params(intr7, wt12, s);
+        static_assert(sizeof(SensorParams) == 16 * sizeof(float), "SensorParams is 16 floats");
+        memcpy(out16, &s, sizeof(s));
+        return 0;
+    });
 }
 
 extern "C" int lsnFusionSetParams(LsnFusion *p, const float *intr, const float *wt, const float *bounds6, void *stream)
 {
-    return lsn::guarded<int>("lsnFusionSetParams", static_cast<int>(-1), [&]() { return lsnFusionSetParams_impl(p, intr, wt, bounds6, stream); });
-}
-
-static int lsnFusionSetMode_impl(LsnFusion *p, int mode)
-{
-    if (!p || mode < lsn::kPlanThreeLaunches || mode > lsn::kPlanSinglePass) {
-        lsn::set_error("lsnFusionSetMode: mode must be 0 (count/scan/write launches), 1 (single launch, runs + look-back) or 2 (single pass, look-back per tile)");
-        return -1;
-    }
-    p->mode = mode;
-    return 0;
+    return lsn::guarded("lsnFusionSetParams", -1, [&]() {
+        lsn::clear_error();
+        if (!p || !intr || !wt || !bounds6) {
+            lsn::set_error("lsnFusionSetParams: null argument");
+            return -1;
+        }
+        LSN_HIP(hipSetDevice(p->device));
+        {
+            // LiveScanServer passes the same calibration with every call (KinectServer.cs:470-490): nothing to do then
+            std::lock_guard<std::mutex> g(p->mu);
+            if (p->params_set && p->last_intr.size() == 7 * (size_t)p->n_maps &&
+                memcmp(p->last_intr.data(), intr, sizeof(float) * 7 * p->n_maps) == 0 &&
+                memcmp(p->last_wt.data(), wt, sizeof(float) * 12 * p->n_maps) == 0 && memcmp(p->bounds, bounds6, sizeof(p->bounds)) == 0)
+                return 0;
+        }
+        std::vector<SensorParams> sp(p->n_maps);
+        for (int i = 0; i < p->n_maps; i++) pack_sensor_params(intr + 7 * i, wt + 12 * i, sp[i]);
+        // pageable source: hipMemcpyAsync copies it out before returning, so the local vector may die
+        LSN_HIP(hipMemcpyAsync(p->params.p, sp.data(), sizeof(SensorParams) * p->n_maps, hipMemcpyHostToDevice,
+                               lsn::as_stream(stream)));
+        hipLaunchKernelGGL(table_kernel, dim3(8, (unsigned)p->n_maps), dim3(kThreads), 0, lsn::as_stream(stream), p->frames.as<FrameDesc>(),
+                           p->params.as<SensorParams>(), p->n_maps, p->xtab.as<float>(), p->ytab.as<float>());
+        LSN_HIP(hipGetLastError());
+        LSN_HIP(hipStreamSynchronize(lsn::as_stream(stream)));
+        std::lock_guard<std::mutex> g(p->mu);
+        memcpy(p->bounds, bounds6, sizeof(p->bounds));
+        p->last_intr.assign(intr, intr + 7 * (size_t)p->n_maps);
+        p->last_wt.assign(wt, wt + 12 * (size_t)p->n_maps);
+        p->params_set = true;
+        p->params_gen++;  // counts made ahead with the old parameters are void
+        p->thr_valid = false;
+        p->runs_with_params = 0;
+        return 0;
+    });
 }
 
 extern "C" int lsnFusionSetMode(LsnFusion *p, int mode)
 {
-    return lsn::guarded<int>("lsnFusionSetMode", static_cast<int>(-1), [&]() { return lsnFusionSetMode_impl(p, mode); });
-}
-
-static int lsnFusionSetPipelined_impl(LsnFusion *p, int enable)
-{
-    lsn::clear_error();
-    if (!p) return -1;
-    std::lock_guard<std::mutex> g(p->mu);
-    LSN_HIP(hipSetDevice(p->device));
-    if (enable && !p->side) {
-        if (p->tile_counts_b.reserve(sizeof(int) * (size_t)p->tiles_per_tick * p->n_ticks) ||
-            p->offs_int.reserve(sizeof(int) * 2 * (size_t)p->n_ticks * (p->n_maps + 1)))
+    return lsn::guarded("lsnFusionSetMode", -1, [&]() {
+        if (!p || mode < lsn::kPlanThreeLaunches || mode > lsn::kPlanSinglePass) {
+            lsn::set_error("lsnFusionSetMode: mode must be 0 (count/scan/write launches), 1 (single launch, runs + look-back) or 2 (single pass, look-back per tile)");
             return -1;
-        LSN_HIP(hipStreamCreateWithFlags(&p->side, hipStreamNonBlocking));
-        LSN_HIP(hipEventCreateWithFlags(&p->ev_counted, hipEventDisableTiming));
-        LSN_HIP(hipEventCreateWithFlags(&p->ev_written[0], hipEventDisableTiming));
-        LSN_HIP(hipEventCreateWithFlags(&p->ev_written[1], hipEventDisableTiming));
-    }
-    if (!enable && p->side) LSN_HIP(hipStreamSynchronize(p->side));
-    p->pipelined = enable != 0;
-    p->calls = 0;
-    return 0;
+        }
+        p->mode = mode;
+        return 0;
+    });
 }
 
 extern "C" int lsnFusionSetPipelined(LsnFusion *p, int enable)
 {
-    return lsn::guarded<int>("lsnFusionSetPipelined", static_cast<int>(-1), [&]() { return lsnFusionSetPipelined_impl(p, enable); });
-}
-
-static int lsnFusionProfile_impl(LsnFusion *p, int enable)
-{
-    if (!p) return -1;
-    p->profile = enable != 0;
-    p->profile_every = enable > 1 ? enable : 1;
-    p->profile_seq = 0;
-    return 0;
+    return lsn::guarded("lsnFusionSetPipelined", -1, [&]() {
+        lsn::clear_error();
+        if (!p) return -1;
+        std::lock_guard<std::mutex> g(p->mu);
+        LSN_HIP(hipSetDevice(p->device));
+        if (enable && !p->side) {
+            if (p->tile_counts_b.reserve(sizeof(int) * (size_t)p->tiles_per_tick * p->n_ticks) ||
+                p->offs_int.reserve(sizeof(int) * 2 * (size_t)p->n_ticks * (p->n_maps + 1)))
+                return -1;
+            LSN_HIP(hipStreamCreateWithFlags(&p->side, hipStreamNonBlocking));
+            LSN_HIP(hipEventCreateWithFlags(&p->ev_counted, hipEventDisableTiming));
+            LSN_HIP(hipEventCreateWithFlags(&p->ev_written[0], hipEventDisableTiming));
+            LSN_HIP(hipEventCreateWithFlags(&p->ev_written[1], hipEventDisableTiming));
+        }
+        if (!enable && p->side) LSN_HIP(hipStreamSynchronize(p->side));
+        p->pipelined = enable != 0;
+        p->calls = 0;
+        return 0;
+    });
 }
 
 extern "C" int lsnFusionProfile(LsnFusion *p, int enable)
 {
-    return lsn::guarded<int>("lsnFusionProfile", static_cast<int>(-1), [&]() { return lsnFusionProfile_impl(p, enable); });
+    return lsn::guarded("lsnFusionProfile", -1, [&]() {
+        if (!p) return -1;
+        p->profile = enable != 0;
+        p->profile_every = enable > 1 ? enable : 1;
+        p->profile_seq = 0;
+        return 0;
+    });
 }
 
 static int drain_events(LsnFusion *p)
@@ -921,27 +900,24 @@ static int drain_events(LsnFusion *p)
     return 0;
 }
 
-static int lsnFusionKernelStats_impl(LsnFusion *p, double *avg_ms, long long *launches, char *name, int name_len, int reset)
-{
-    lsn::clear_error();
-    if (!p) return -1;
-    std::lock_guard<std::mutex> g(p->mu);
-    LSN_HIP(hipSetDevice(p->device));
-    if (drain_events(p)) return -1;
-    if (avg_ms) *avg_ms = p->launches ? p->acc_ms / (double)p->launches : 0.0;
-    if (launches) *launches = p->launches;
-    if (name && name_len > 0)
-        snprintf(name, (size_t)name_len, "%s", p->timed_kernel ? p->timed_kernel : (p->mode == lsn::kPlanThreeLaunches ? "fuse_kernel<1>" : p->mode == lsn::kPlanSinglePass ? "fuse_kernel<4>" : "run_kernel"));
-    if (reset) {
-        p->acc_ms = 0;
-        p->launches = 0;
-    }
-    return 0;
-}
-
 extern "C" int lsnFusionKernelStats(LsnFusion *p, double *avg_ms, long long *launches, char *name, int name_len, int reset)
 {
-    return lsn::guarded<int>("lsnFusionKernelStats", static_cast<int>(-1), [&]() { return lsnFusionKernelStats_impl(p, avg_ms, launches, name, name_len, reset); });
+    return lsn::guarded("lsnFusionKernelStats", -1, [&]() {
+        lsn::clear_error();
+        if (!p) return -1;
+        std::lock_guard<std::mutex> g(p->mu);
+        LSN_HIP(hipSetDevice(p->device));
+        if (drain_events(p)) return -1;
+        if (avg_ms) *avg_ms = p->launches ? p->acc_ms / (double)p->launches : 0.0;
+        if (launches) *launches = p->launches;
+        if (name && name_len > 0)
+            snprintf(name, (size_t)name_len, "%s", p->timed_kernel ? p->timed_kernel : (p->mode == lsn::kPlanThreeLaunches ? "fuse_kernel<1>" : p->mode == lsn::kPlanSinglePass ? "fuse_kernel<4>" : "run_kernel"));
+        if (reset) {
+            p->acc_ms = 0;
+            p->launches = 0;
+        }
+        return 0;
+    });
 }
 
 // Kernel arguments of one call (everything but the scratch selection of the launch form).
@@ -1082,17 +1058,13 @@ int lsn::next_event_pair(LsnFusion *p, hipEvent_t &e0, hipEvent_t &e1)
     return 0;
 }
 
-static int lsnFusionRun_impl(LsnFusion *p, const void *d_depth, const void *d_colors, void *d_vertices, int *d_offsets,
-                            void *stream)
-{
-    lsn::clear_error();
-    return lsn::run_vertices(p, d_depth, d_colors, d_vertices, d_offsets, lsn::as_stream(stream));
-}
-
 extern "C" int lsnFusionRun(LsnFusion *p, const void *d_depth, const void *d_colors, void *d_vertices, int *d_offsets,
                             void *stream)
 {
-    return lsn::guarded<int>("lsnFusionRun", static_cast<int>(-1), [&]() { return lsnFusionRun_impl(p, d_depth, d_colors, d_vertices, d_offsets, stream); });
+    return lsn::guarded("lsnFusionRun", -1, [&]() {
+        lsn::clear_error();
+        return lsn::run_vertices(p, d_depth, d_colors, d_vertices, d_offsets, lsn::as_stream(stream));
+    });
 }
 
 int lsn::run_vertices(LsnFusion *p, const void *d_depth, const void *d_colors, void *d_vertices, int *d_offsets, hipStream_t s)
@@ -1320,116 +1292,106 @@ int lsn::run_write(LsnFusion *p, const void *d_depth, const void *d_colors, void
 }
 
 // Streamed calls: this batch is written while the NEXT batch (already resident) is counted by the same kernel.
-static int lsnFusionRunStreamed_impl(LsnFusion *p, const void *d_depth, const void *d_colors, void *d_vertices, int *d_offsets,
-                                    const void *d_next_depth, void *stream)
-{
-    lsn::clear_error();
-    if (!p || !d_depth || !d_colors || !d_vertices || !d_offsets) {
-        lsn::set_error("lsnFusionRunStreamed: null argument");
-        return -1;
-    }
-    if (!p->params_set) {
-        lsn::set_error("lsnFusionRunStreamed: lsnFusionSetParams has not been called");
-        return -1;
-    }
-    std::lock_guard<std::mutex> g(p->mu);
-    LSN_HIP(hipSetDevice(p->device));
-    hipStream_t s = lsn::as_stream(stream);
-    const size_t n_tiles = (size_t)p->tiles_per_tick * p->n_ticks;
-    const size_t off_elems = (size_t)p->n_ticks * (p->n_maps + 1);
-    if (p->tile_counts_b.reserve(sizeof(int) * n_tiles) || p->offs_int.reserve(sizeof(int) * 2 * off_elems)) return -1;
-
-    if (ensure_thresholds(p, s)) return -1;
-    FuseArgs a;
-    fill_args(p, a, d_depth, d_colors, d_vertices, d_offsets, false);
-    const bool vec = wide_loads(p, d_depth, d_colors) && (!d_next_depth || ((uintptr_t)d_next_depth & 15) == 0);
-    const int grid = (int)n_tiles;
-    int *cur = p->stream_half ? p->tile_counts_b.as<int>() : p->tile_counts.as<int>();
-    int *nxt = p->stream_half ? p->tile_counts.as<int>() : p->tile_counts_b.as<int>();
-    int *off_cur = p->offs_int.as<int>() + (p->stream_half ? off_elems : 0);
-    int *off_nxt = p->offs_int.as<int>() + (p->stream_half ? 0 : off_elems);
-    a.tile_counts = cur;
-    if (p->counted_for != d_depth || p->counted_gen != p->params_gen) {
-        // nothing (valid) was counted ahead for this batch: do it now, like the three launches
-        a.offsets = off_cur;
-        count_and_scan(p, vec, s, a);
-    }
-    LSN_HIP(hipMemcpyAsync(d_offsets, off_cur, sizeof(int) * off_elems, hipMemcpyDeviceToDevice, s));
-    a.offsets = d_offsets;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (timed_launch(p) && next_event_pair(p, e0, e1)) return -1;
-    if (e0) LSN_HIP(hipEventRecord(e0, s));
-    if (d_next_depth) {
-        a.depth_next = static_cast<const unsigned short *>(d_next_depth);
-        a.tile_counts_next = nxt;
-        launch_fuse<lsn::kPassWriteCountNext>(vec, grid, s, a);
-    } else {
-        launch_fuse<lsn::kPassWrite>(vec, grid, s, a);
-    }
-    if (e1) LSN_HIP(hipEventRecord(e1, s));
-    if (d_next_depth) {
-        hipLaunchKernelGGL(scan_kernel, dim3((unsigned)p->n_ticks), dim3(kScanThreads), 0, s, nxt, a.tiles_per_tick, a.frames, a.n_frames, off_nxt, nullptr);
-        p->counted_for = d_next_depth;
-        p->counted_gen = p->params_gen;
-        p->stream_half ^= 1;
-    } else {
-        p->counted_for = nullptr;
-    }
-    LSN_HIP(hipGetLastError());
-    return 0;
-}
-
 extern "C" int lsnFusionRunStreamed(LsnFusion *p, const void *d_depth, const void *d_colors, void *d_vertices, int *d_offsets,
                                     const void *d_next_depth, void *stream)
 {
-    return lsn::guarded<int>("lsnFusionRunStreamed", static_cast<int>(-1), [&]() { return lsnFusionRunStreamed_impl(p, d_depth, d_colors, d_vertices, d_offsets, d_next_depth, stream); });
+    return lsn::guarded("lsnFusionRunStreamed", -1, [&]() {
+        lsn::clear_error();
+        if (!p || !d_depth || !d_colors || !d_vertices || !d_offsets) {
+            lsn::set_error("lsnFusionRunStreamed: null argument");
+            return -1;
+        }
+        if (!p->params_set) {
+            lsn::set_error("lsnFusionRunStreamed: lsnFusionSetParams has not been called");
+            return -1;
+        }
+        std::lock_guard<std::mutex> g(p->mu);
+        LSN_HIP(hipSetDevice(p->device));
+        hipStream_t s = lsn::as_stream(stream);
+        const size_t n_tiles = (size_t)p->tiles_per_tick * p->n_ticks;
+        const size_t off_elems = (size_t)p->n_ticks * (p->n_maps + 1);
+        if (p->tile_counts_b.reserve(sizeof(int) * n_tiles) || p->offs_int.reserve(sizeof(int) * 2 * off_elems)) return -1;
+
+        if (ensure_thresholds(p, s)) return -1;
+        FuseArgs a;
+        fill_args(p, a, d_depth, d_colors, d_vertices, d_offsets, false);
+        const bool vec = wide_loads(p, d_depth, d_colors) && (!d_next_depth || ((uintptr_t)d_next_depth & 15) == 0);
+        const int grid = (int)n_tiles;
+        int *cur = p->stream_half ? p->tile_counts_b.as<int>() : p->tile_counts.as<int>();
+        int *nxt = p->stream_half ? p->tile_counts.as<int>() : p->tile_counts_b.as<int>();
+        int *off_cur = p->offs_int.as<int>() + (p->stream_half ? off_elems : 0);
+        int *off_nxt = p->offs_int.as<int>() + (p->stream_half ? 0 : off_elems);
+        a.tile_counts = cur;
+        if (p->counted_for != d_depth || p->counted_gen != p->params_gen) {
+            // nothing (valid) was counted ahead for this batch: do it now, like the three launches
+            a.offsets = off_cur;
+            count_and_scan(p, vec, s, a);
+        }
+        LSN_HIP(hipMemcpyAsync(d_offsets, off_cur, sizeof(int) * off_elems, hipMemcpyDeviceToDevice, s));
+        a.offsets = d_offsets;
+        hipEvent_t e0 = nullptr, e1 = nullptr;
+        if (timed_launch(p) && next_event_pair(p, e0, e1)) return -1;
+        if (e0) LSN_HIP(hipEventRecord(e0, s));
+        if (d_next_depth) {
+            a.depth_next = static_cast<const unsigned short *>(d_next_depth);
+            a.tile_counts_next = nxt;
+            launch_fuse<lsn::kPassWriteCountNext>(vec, grid, s, a);
+        } else {
+            launch_fuse<lsn::kPassWrite>(vec, grid, s, a);
+        }
+        if (e1) LSN_HIP(hipEventRecord(e1, s));
+        if (d_next_depth) {
+            hipLaunchKernelGGL(scan_kernel, dim3((unsigned)p->n_ticks), dim3(kScanThreads), 0, s, nxt, a.tiles_per_tick, a.frames, a.n_frames, off_nxt, nullptr);
+            p->counted_for = d_next_depth;
+            p->counted_gen = p->params_gen;
+            p->stream_half ^= 1;
+        } else {
+            p->counted_for = nullptr;
+        }
+        LSN_HIP(hipGetLastError());
+        return 0;
+    });
 }
 
 // Diagnostics / tests: builds the per-pixel depth thresholds now (if the plan uses them) and copies them out.
-static int lsnFusionThresholds_impl(LsnFusion *p, unsigned int *out_host, float *build_ms, void *stream)
-{
-    lsn::clear_error();
-    if (!p || !p->params_set) {
-        lsn::set_error("lsnFusionThresholds: no plan / lsnFusionSetParams has not been called");
-        return -1;
-    }
-    std::lock_guard<std::mutex> g(p->mu);
-    LSN_HIP(hipSetDevice(p->device));
-    if (!p->thr_enabled) return 1;
-    hipStream_t s = lsn::as_stream(stream);
-    if (!p->thr_valid) {
-        p->runs_with_params = 1;
-        if (ensure_thresholds(p, s)) return -1;
-    }
-    if (build_ms) *build_ms = p->thr_build_ms;
-    if (out_host) {
-        LSN_HIP(hipMemcpyAsync(out_host, p->thr.p, sizeof(unsigned int) * (size_t)p->cap, hipMemcpyDeviceToHost, s));
-        LSN_HIP(hipStreamSynchronize(s));
-    }
-    return 0;
-}
-
 extern "C" int lsnFusionThresholds(LsnFusion *p, unsigned int *out_host, float *build_ms, void *stream)
 {
-    return lsn::guarded<int>("lsnFusionThresholds", static_cast<int>(-1), [&]() { return lsnFusionThresholds_impl(p, out_host, build_ms, stream); });
+    return lsn::guarded("lsnFusionThresholds", -1, [&]() {
+        lsn::clear_error();
+        if (!p || !p->params_set) {
+            lsn::set_error("lsnFusionThresholds: no plan / lsnFusionSetParams has not been called");
+            return -1;
+        }
+        std::lock_guard<std::mutex> g(p->mu);
+        LSN_HIP(hipSetDevice(p->device));
+        if (!p->thr_enabled) return 1;
+        hipStream_t s = lsn::as_stream(stream);
+        if (!p->thr_valid) {
+            p->runs_with_params = 1;
+            if (ensure_thresholds(p, s)) return -1;
+        }
+        if (build_ms) *build_ms = p->thr_build_ms;
+        if (out_host) {
+            LSN_HIP(hipMemcpyAsync(out_host, p->thr.p, sizeof(unsigned int) * (size_t)p->cap, hipMemcpyDeviceToHost, s));
+            LSN_HIP(hipStreamSynchronize(s));
+        }
+        return 0;
+    });
 }
 
 // Reads back the look-back error flag (diagnostics for tests); synchronises the stream.
 extern "C" int lsnFusionCheck(LsnFusion *p, void *stream) { return lsnFusionLookbackFailed(p, stream); }
 
-static int lsnFusionLookbackFailed_impl(LsnFusion *p, void *stream)
-{
-    if (!p) return -1;
-    int flag = 0;
-    LSN_HIP(hipSetDevice(p->device));
-    LSN_HIP(hipStreamSynchronize(lsn::as_stream(stream)));
-    LSN_HIP(hipMemcpy(&flag, p->misc.p, sizeof(int), hipMemcpyDeviceToHost));
-    if (flag) LSN_HIP(hipMemset(p->misc.p, 0, sizeof(int)));
-    return flag;
-}
-
 extern "C" int lsnFusionLookbackFailed(LsnFusion *p, void *stream)
 {
-    return lsn::guarded<int>("lsnFusionLookbackFailed", static_cast<int>(-1), [&]() { return lsnFusionLookbackFailed_impl(p, stream); });
+    return lsn::guarded("lsnFusionLookbackFailed", -1, [&]() {
+        if (!p) return -1;
+        int flag = 0;
+        LSN_HIP(hipSetDevice(p->device));
+        LSN_HIP(hipStreamSynchronize(lsn::as_stream(stream)));
+        LSN_HIP(hipMemcpy(&flag, p->misc.p, sizeof(int), hipMemcpyDeviceToHost));
+        if (flag) LSN_HIP(hipMemset(p->misc.p, 0, sizeof(int)));
+        return flag;
+    });
 }
 

@@ -1214,37 +1214,34 @@ using namespace lsn::host;
 // "0:[0-3] 1:[4-7]": shard:[first-last sensor], blocks contiguous and in sensor order (the order their vertices take in the Mesh) -- and,
 // when first_out is given, the block bounds themselves (n_devices + 1 ints are enough).  Returns the number of shards used
 // (min(n_devices, n_maps), at most 16), -1 on bad arguments.  n_devices = 0: the devices this process was configured with.
-static int lsnHostShardDescribe_impl(int n_maps, int n_devices, int *first_out, char *buf, int len)
-{
-    lsn::clear_error();
-    if (n_devices == 0) {
-        std::vector<int> devs;
-        const char *e = getenv("LSN_HOST_DEVICES");
-        if (e && parse_device_list(e, 1 << 30, devs)) return -1;
-        n_devices = devs.size() >= 2 ? (int)devs.size() : 1;
-    }
-    if (n_maps <= 0 || n_devices < 0) {
-        lsn::set_error("lsnHostShardDescribe: bad arguments");
-        return -1;
-    }
-    int first[kMaxShards + 1], D = 0;
-    plan_shards(n_maps, n_devices, first, D);
-    std::string out;
-    for (int d = 0; d < D; d++) {
-        char item[64];
-        if (first[d + 1] - first[d] == 1) snprintf(item, sizeof(item), "%s%d:[%d]", d ? " " : "", d, first[d]);
-        else snprintf(item, sizeof(item), "%s%d:[%d-%d]", d ? " " : "", d, first[d], first[d + 1] - 1);
-        out += item;
-    }
-    if (buf && len > 0) snprintf(buf, (size_t)len, "%s", out.c_str());
-    if (first_out)
-        for (int d = 0; d <= D; d++) first_out[d] = first[d];
-    return D;
-}
-
 extern "C" int lsnHostShardDescribe(int n_maps, int n_devices, int *first_out, char *buf, int len)
 {
-    return lsn::guarded<int>("lsnHostShardDescribe", static_cast<int>(-1), [&]() { return lsnHostShardDescribe_impl(n_maps, n_devices, first_out, buf, len); });
+    return lsn::guarded("lsnHostShardDescribe", -1, [&]() {
+        lsn::clear_error();
+        if (n_devices == 0) {
+            std::vector<int> devs;
+            const char *e = getenv("LSN_HOST_DEVICES");
+            if (e && parse_device_list(e, 1 << 30, devs)) return -1;
+            n_devices = devs.size() >= 2 ? (int)devs.size() : 1;
+        }
+        if (n_maps <= 0 || n_devices < 0) {
+            lsn::set_error("lsnHostShardDescribe: bad arguments");
+            return -1;
+        }
+        int first[kMaxShards + 1], D = 0;
+        plan_shards(n_maps, n_devices, first, D);
+        std::string out;
+        for (int d = 0; d < D; d++) {
+            char item[64];
+            if (first[d + 1] - first[d] == 1) snprintf(item, sizeof(item), "%s%d:[%d]", d ? " " : "", d, first[d]);
+            else snprintf(item, sizeof(item), "%s%d:[%d-%d]", d ? " " : "", d, first[d], first[d + 1] - 1);
+            out += item;
+        }
+        if (buf && len > 0) snprintf(buf, (size_t)len, "%s", out.c_str());
+        if (first_out)
+            for (int d = 0; d <= D; d++) first_out[d] = first[d];
+        return D;
+    });
 }
 
 // Measurement aid: the wall time (microseconds) every part of the LAST sharded call took when the parts ran one after the other
@@ -1263,7 +1260,7 @@ extern "C" long long lsnTestFaultPoints(int kind) { return lsn::test_fault_point
 
 extern "C" int lsnHostPoolStats(int *live_blocks, int *pooled_blocks, long long *live_bytes)
 {
-    return lsn::guarded<int>("lsnHostPoolStats", static_cast<int>(-1), [&]() {
+    return lsn::guarded("lsnHostPoolStats", -1, [&]() {
         Ctx &c = ctx();
         std::lock_guard<std::mutex> tg(c.tab_mu);
         long long bytes = 0;
@@ -1278,46 +1275,42 @@ extern "C" int lsnHostPoolStats(int *live_blocks, int *pooled_blocks, long long 
 // Host-only (no device needed): the upload schedule a call with these frames would follow, as text -- "D[0-2] C[0-2] | D[3-7] C[3-5] |
 // C[6-7]": runs of the depth / colour arrays in upload order, `|` where a group of sensors becomes ready and is launched.  Exists
 // so that the scheduling logic can be tested without a GPU (tests/test_abi.py).
-static int lsnHostScheduleDescribe_impl(int n_maps, const int *widths, const int *heights, int first, int count, int radial, int sensors_per_group,
-                                       char *buf, int len)
-{
-    lsn::clear_error();
-    if (n_maps <= 0 || !widths || !heights || first < 0 || count <= 0 || first + count > n_maps || !buf || len <= 0) {
-        lsn::set_error("lsnHostScheduleDescribe: bad arguments");
-        return -1;
-    }
-    std::vector<Group> groups;
-    std::vector<Copy> copies;
-    plan_schedule(groups, copies, widths, heights, first, count, radial != 0, sensors_per_group, radial == 1);
-    auto sensor_at = [&](bool colours, size_t off) {   // which sensor starts at byte `off` of the lane's (packed) buffer
-        size_t at = 0;
-        for (int i = first; i < first + count; i++) {
-            if (at == off) return i;
-            at += (size_t)widths[i] * heights[i] * (colours ? 3 : 2);
-        }
-        return first + count;
-    };
-    std::string out;
-    size_t next_group = 0;
-    for (size_t i = 0; i < copies.size(); i++) {
-        const Copy &cp = copies[i];
-        const int a = sensor_at(cp.colours, cp.dev_off), b = sensor_at(cp.colours, cp.dev_off + cp.bytes) - 1;
-        char item[64];
-        if (a == b) snprintf(item, sizeof(item), "%c[%d]", cp.colours ? 'C' : 'D', a);
-        else snprintf(item, sizeof(item), "%c[%d-%d]", cp.colours ? 'C' : 'D', a, b);
-        if (!out.empty()) out += " ";
-        out += item;
-        bool ready = false;
-        for (; next_group < groups.size() && groups[next_group].ready_after == (int)i + 1; next_group++) ready = true;
-        if (ready && i + 1 < copies.size()) out += " |";
-    }
-    snprintf(buf, (size_t)len, "%s", out.c_str());
-    return (int)groups.size();
-}
-
 extern "C" int lsnHostScheduleDescribe(int n_maps, const int *widths, const int *heights, int first, int count, int radial, int sensors_per_group,
                                        char *buf, int len)
 {
-    return lsn::guarded<int>("lsnHostScheduleDescribe", static_cast<int>(-1), [&]() { return lsnHostScheduleDescribe_impl(n_maps, widths, heights, first, count, radial, sensors_per_group, buf, len); });
+    return lsn::guarded("lsnHostScheduleDescribe", -1, [&]() {
+        lsn::clear_error();
+        if (n_maps <= 0 || !widths || !heights || first < 0 || count <= 0 || first + count > n_maps || !buf || len <= 0) {
+            lsn::set_error("lsnHostScheduleDescribe: bad arguments");
+            return -1;
+        }
+        std::vector<Group> groups;
+        std::vector<Copy> copies;
+        plan_schedule(groups, copies, widths, heights, first, count, radial != 0, sensors_per_group, radial == 1);
+        auto sensor_at = [&](bool colours, size_t off) {   // which sensor starts at byte `off` of the lane's (packed) buffer
+            size_t at = 0;
+            for (int i = first; i < first + count; i++) {
+                if (at == off) return i;
+                at += (size_t)widths[i] * heights[i] * (colours ? 3 : 2);
+            }
+            return first + count;
+        };
+        std::string out;
+        size_t next_group = 0;
+        for (size_t i = 0; i < copies.size(); i++) {
+            const Copy &cp = copies[i];
+            const int a = sensor_at(cp.colours, cp.dev_off), b = sensor_at(cp.colours, cp.dev_off + cp.bytes) - 1;
+            char item[64];
+            if (a == b) snprintf(item, sizeof(item), "%c[%d]", cp.colours ? 'C' : 'D', a);
+            else snprintf(item, sizeof(item), "%c[%d-%d]", cp.colours ? 'C' : 'D', a, b);
+            if (!out.empty()) out += " ";
+            out += item;
+            bool ready = false;
+            for (; next_group < groups.size() && groups[next_group].ready_after == (int)i + 1; next_group++) ready = true;
+            if (ready && i + 1 < copies.size()) out += " |";
+        }
+        snprintf(buf, (size_t)len, "%s", out.c_str());
+        return (int)groups.size();
+    });
 }
 

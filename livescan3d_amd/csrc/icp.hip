@@ -1700,84 +1700,75 @@ struct LsnIcp {
 
 static constexpr int kTraceCap = 1024;
 
-static LsnIcp * lsnIcpCreate_impl(int device, int max_n1, int max_n2)
-{
-    lsn::clear_error();
-    if (max_n1 <= 0 || max_n2 <= 0) {
-        lsn::set_error("lsnIcpCreate: bad capacities (%d, %d)", max_n1, max_n2);
-        return nullptr;
-    }
-    LSN_HIP_NULL(hipSetDevice(device));
-    LsnIcp *w = new (std::nothrow) LsnIcp();
-    if (!w) return nullptr;
-    w->device = device;
-    w->max_n1 = max_n1;
-    w->max_n2 = max_n2;
-    if (const char *e3 = getenv("LSN_ICP_NEAR_PTS")) w->near_pts = std::max(1, std::min(kNearCapMax, atoi(e3)));
-    if (const char *e4 = getenv("LSN_ICP_NEAR")) w->near_mode = std::max(0, std::min(2, atoi(e4)));
-    bool bad = false;
-    bad |= w->tgt.reserve(max_n1, true) != 0;
-    bad |= w->src.reserve(max_n2, false) != 0;
-    bad |= w->bbox_part.reserve(sizeof(float) * 6 * kMaxBlocks) != 0;
-    bad |= w->block_sums.reserve(sizeof(int) * 2048) != 0;
-    bad |= w->idx.reserve(sizeof(int) * (size_t)max_n2) != 0;
-    bad |= w->dist.reserve(sizeof(float) * (size_t)max_n2) != 0;
-    bad |= w->keys.reserve(sizeof(unsigned long long) * (size_t)max_n1) != 0;
-    bad |= w->counters.reserve(sizeof(int) * 2 * kBankInts) != 0;
-    {
-        const int n_groups = (max_n2 + 63) / 64;
-        // generous: a seeded group needs ~5 super-blocks and ~10 point ranges; $LSN_ICP_TINY_LISTS=1 forces the overflow path (tests)
-        const bool tiny = getenv("LSN_ICP_TINY_LISTS") && atoi(getenv("LSN_ICP_TINY_LISTS")) != 0;
-        w->seg_a = tiny ? 2 : 1024 + n_groups / 4;   // x 64 segments: 64 k + 16 per group
-        w->seg_b = tiny ? 2 : 8192 + 2 * n_groups;   // x 64 segments: 512 k + 128 per group
-        bad |= w->best_key.reserve(sizeof(unsigned long long) * (size_t)max_n2) != 0;
-        bad |= w->idx_sorted.reserve(sizeof(int) * (size_t)max_n2) != 0;
-        bad |= w->groups.reserve(sizeof(GroupInfo) * (size_t)n_groups) != 0;
-        bad |= w->list_a.reserve(sizeof(uint2) * (size_t)w->seg_a * kSegs) != 0;
-        bad |= w->list_b.reserve(sizeof(int4) * (size_t)w->seg_b * kSegs) != 0;
-    }
-    bad |= w->part1.reserve(sizeof(double) * 4 * kMaxBlocks) != 0;
-    bad |= w->part3.reserve(sizeof(double) * 16 * kMaxBlocks) != 0;
-    bad |= w->state.reserve(sizeof(IcpState)) != 0;
-    bad |= w->trace.reserve(sizeof(float) * 16 * kTraceCap) != 0;
-    if (bad) {
-        delete w;
-        return nullptr;
-    }
-    return w;
-}
-
 extern "C" LsnIcp * lsnIcpCreate(int device, int max_n1, int max_n2)
 {
-    return lsn::guarded<LsnIcp *>("lsnIcpCreate", static_cast<LsnIcp *>(nullptr), [&]() { return lsnIcpCreate_impl(device, max_n1, max_n2); });
-}
-
-static void lsnIcpDestroy_impl(LsnIcp *w)
-{
-    if (!w) return;
-    (void)hipSetDevice(w->device);
-    for (hipEvent_t e : w->events) (void)hipEventDestroy(e);
-    delete w;
+    return lsn::guarded("lsnIcpCreate", static_cast<LsnIcp *>(nullptr), [&]() -> LsnIcp * {
+        lsn::clear_error();
+        if (max_n1 <= 0 || max_n2 <= 0) {
+            lsn::set_error("lsnIcpCreate: bad capacities (%d, %d)", max_n1, max_n2);
+            return nullptr;
+        }
+        LSN_HIP_NULL(hipSetDevice(device));
+        LsnIcp *w = new (std::nothrow) LsnIcp();
+        if (!w) return nullptr;
+        w->device = device;
+        w->max_n1 = max_n1;
+        w->max_n2 = max_n2;
+        if (const char *e3 = getenv("LSN_ICP_NEAR_PTS")) w->near_pts = std::max(1, std::min(kNearCapMax, atoi(e3)));
+        if (const char *e4 = getenv("LSN_ICP_NEAR")) w->near_mode = std::max(0, std::min(2, atoi(e4)));
+        bool bad = false;
+        bad |= w->tgt.reserve(max_n1, true) != 0;
+        bad |= w->src.reserve(max_n2, false) != 0;
+        bad |= w->bbox_part.reserve(sizeof(float) * 6 * kMaxBlocks) != 0;
+        bad |= w->block_sums.reserve(sizeof(int) * 2048) != 0;
+        bad |= w->idx.reserve(sizeof(int) * (size_t)max_n2) != 0;
+        bad |= w->dist.reserve(sizeof(float) * (size_t)max_n2) != 0;
+        bad |= w->keys.reserve(sizeof(unsigned long long) * (size_t)max_n1) != 0;
+        bad |= w->counters.reserve(sizeof(int) * 2 * kBankInts) != 0;
+        {
+            const int n_groups = (max_n2 + 63) / 64;
+            // generous: a seeded group needs ~5 super-blocks and ~10 point ranges; $LSN_ICP_TINY_LISTS=1 forces the overflow path (tests)
+            const bool tiny = getenv("LSN_ICP_TINY_LISTS") && atoi(getenv("LSN_ICP_TINY_LISTS")) != 0;
+            w->seg_a = tiny ? 2 : 1024 + n_groups / 4;   // x 64 segments: 64 k + 16 per group
+            w->seg_b = tiny ? 2 : 8192 + 2 * n_groups;   // x 64 segments: 512 k + 128 per group
+            bad |= w->best_key.reserve(sizeof(unsigned long long) * (size_t)max_n2) != 0;
+            bad |= w->idx_sorted.reserve(sizeof(int) * (size_t)max_n2) != 0;
+            bad |= w->groups.reserve(sizeof(GroupInfo) * (size_t)n_groups) != 0;
+            bad |= w->list_a.reserve(sizeof(uint2) * (size_t)w->seg_a * kSegs) != 0;
+            bad |= w->list_b.reserve(sizeof(int4) * (size_t)w->seg_b * kSegs) != 0;
+        }
+        bad |= w->part1.reserve(sizeof(double) * 4 * kMaxBlocks) != 0;
+        bad |= w->part3.reserve(sizeof(double) * 16 * kMaxBlocks) != 0;
+        bad |= w->state.reserve(sizeof(IcpState)) != 0;
+        bad |= w->trace.reserve(sizeof(float) * 16 * kTraceCap) != 0;
+        if (bad) {
+            delete w;
+            return nullptr;
+        }
+        return w;
+    });
 }
 
 extern "C" void lsnIcpDestroy(LsnIcp *w)
 {
-    lsn::guarded_void("lsnIcpDestroy", [&]() { lsnIcpDestroy_impl(w); });
-}
-
-static int lsnIcpSetProfiling_impl(LsnIcp *w, int on)
-{
-    lsn::clear_error();
-    if (!w) return -1;
-    std::lock_guard<std::mutex> g(w->mu);
-    w->profiling = on != 0;
-    w->n_events = 0;
-    return 0;
+    lsn::guarded_void("lsnIcpDestroy", [&]() {
+        if (!w) return;
+        (void)hipSetDevice(w->device);
+        for (hipEvent_t e : w->events) (void)hipEventDestroy(e);
+        delete w;
+    });
 }
 
 extern "C" int lsnIcpSetProfiling(LsnIcp *w, int on)
 {
-    return lsn::guarded<int>("lsnIcpSetProfiling", static_cast<int>(-1), [&]() { return lsnIcpSetProfiling_impl(w, on); });
+    return lsn::guarded("lsnIcpSetProfiling", -1, [&]() {
+        lsn::clear_error();
+        if (!w) return -1;
+        std::lock_guard<std::mutex> g(w->mu);
+        w->profiling = on != 0;
+        w->n_events = 0;
+        return 0;
+    });
 }
 
 // records the end of `phase` on the stream (profiling only)
@@ -1794,25 +1785,22 @@ static void mark(LsnIcp *w, int phase, hipStream_t s)
     (void)hipEventRecord(w->events[w->n_events++], s);
 }
 
-static int lsnIcpProfile_impl(LsnIcp *w, float *ms4, void *stream)
-{
-    lsn::clear_error();
-    if (!w || !ms4) return -1;
-    std::lock_guard<std::mutex> g(w->mu);
-    LSN_HIP(hipSetDevice(w->device));
-    LSN_HIP(hipStreamSynchronize(lsn::as_stream(stream)));
-    for (int k = 0; k < 4; k++) ms4[k] = 0.0f;
-    for (size_t k = 1; k < w->n_events; k++) {
-        float ms = 0.0f;
-        LSN_HIP(hipEventElapsedTime(&ms, w->events[k - 1], w->events[k]));
-        ms4[w->event_phase[k] & 3] += ms;
-    }
-    return (int)w->n_events;
-}
-
 extern "C" int lsnIcpProfile(LsnIcp *w, float *ms4, void *stream)
 {
-    return lsn::guarded<int>("lsnIcpProfile", static_cast<int>(-1), [&]() { return lsnIcpProfile_impl(w, ms4, stream); });
+    return lsn::guarded("lsnIcpProfile", -1, [&]() {
+        lsn::clear_error();
+        if (!w || !ms4) return -1;
+        std::lock_guard<std::mutex> g(w->mu);
+        LSN_HIP(hipSetDevice(w->device));
+        LSN_HIP(hipStreamSynchronize(lsn::as_stream(stream)));
+        for (int k = 0; k < 4; k++) ms4[k] = 0.0f;
+        for (size_t k = 1; k < w->n_events; k++) {
+            float ms = 0.0f;
+            LSN_HIP(hipEventElapsedTime(&ms, w->events[k - 1], w->events[k]));
+            ms4[w->event_phase[k] & 3] += ms;
+        }
+        return (int)w->n_events;
+    });
 }
 
 static inline int blocks_for(int n) { return (n + kThreads - 1) / kThreads; }
@@ -1958,34 +1946,31 @@ static int check_sizes(LsnIcp *w, int n1, int n2, const char *who)
     return 0;
 }
 
-static int lsnIcpNearest_impl(LsnIcp *w, const float *d_verts1, int n1, const float *d_verts2, int n2, int *d_idx, float *d_dist2,
-                             int nn_mode, void *stream)
-{
-    lsn::clear_error();
-    if (check_sizes(w, n1, n2, "lsnIcpNearest")) return -1;
-    if (!d_verts1 || !d_verts2 || !d_idx || !d_dist2) {
-        lsn::set_error("lsnIcpNearest: null argument");
-        return -1;
-    }
-    std::lock_guard<std::mutex> g(w->mu);
-    LSN_HIP(hipSetDevice(w->device));
-    hipStream_t s = lsn::as_stream(stream);
-    if (nn_mode != 0 && build_grid(w, w->tgt, d_verts1, n1, true, s)) return -1;
-    if (build_grid(w, w->src, d_verts2, n2, false, s)) return -1;
-    LSN_HIP(hipMemsetAsync(w->counters.p, 0, sizeof(int) * 2 * kBankInts, s));
-    return run_nn(w, d_verts1, n1, nullptr, n2, d_idx, d_dist2, nullptr, nn_mode, s, false, nullptr, 0);
-}
-
 extern "C" int lsnIcpNearest(LsnIcp *w, const float *d_verts1, int n1, const float *d_verts2, int n2, int *d_idx, float *d_dist2,
                              int nn_mode, void *stream)
 {
-    return lsn::guarded<int>("lsnIcpNearest", static_cast<int>(-1), [&]() { return lsnIcpNearest_impl(w, d_verts1, n1, d_verts2, n2, d_idx, d_dist2, nn_mode, stream); });
+    return lsn::guarded("lsnIcpNearest", -1, [&]() {
+        lsn::clear_error();
+        if (check_sizes(w, n1, n2, "lsnIcpNearest")) return -1;
+        if (!d_verts1 || !d_verts2 || !d_idx || !d_dist2) {
+            lsn::set_error("lsnIcpNearest: null argument");
+            return -1;
+        }
+        std::lock_guard<std::mutex> g(w->mu);
+        LSN_HIP(hipSetDevice(w->device));
+        hipStream_t s = lsn::as_stream(stream);
+        if (nn_mode != 0 && build_grid(w, w->tgt, d_verts1, n1, true, s)) return -1;
+        if (build_grid(w, w->src, d_verts2, n2, false, s)) return -1;
+        LSN_HIP(hipMemsetAsync(w->counters.p, 0, sizeof(int) * 2 * kBankInts, s));
+        return run_nn(w, d_verts1, n1, nullptr, n2, d_idx, d_dist2, nullptr, nn_mode, s, false, nullptr, 0);
+    });
 }
 
 // d_seeds (nullable, lsnRefine): n2 target indices by the queries' original index -- any index < n1 is a valid seed (a real point bounds the
 // search; the result never depends on it), good ones make the first step as cheap as the later ones.
-static int lsnIcpRun_impl(LsnIcp *w, const float *d_verts1, int n1, float *d_verts2, int n2, float *d_R, float *d_t, int maxIter,
-                         int nn_mode, void *stream, const int *d_seeds = nullptr)
+// The body of lsnIcpRun under a name of its own: lsnRefine (below) calls it too, with seeds, inside a guarded entry it makes itself.
+static int icp_run(LsnIcp *w, const float *d_verts1, int n1, float *d_verts2, int n2, float *d_R, float *d_t, int maxIter, int nn_mode,
+                   void *stream, const int *d_seeds = nullptr)
 {
     lsn::clear_error();
     if (check_sizes(w, n1, n2, "lsnIcpRun")) return -1;
@@ -2041,43 +2026,37 @@ static int lsnIcpRun_impl(LsnIcp *w, const float *d_verts1, int n1, float *d_ver
 extern "C" int lsnIcpRun(LsnIcp *w, const float *d_verts1, int n1, float *d_verts2, int n2, float *d_R, float *d_t, int maxIter,
                          int nn_mode, void *stream)
 {
-    return lsn::guarded<int>("lsnIcpRun", static_cast<int>(-1), [&]() { return lsnIcpRun_impl(w, d_verts1, n1, d_verts2, n2, d_R, d_t, maxIter, nn_mode, stream); });
+    return lsn::guarded("lsnIcpRun", -1, [&]() { return icp_run(w, d_verts1, n1, d_verts2, n2, d_R, d_t, maxIter, nn_mode, stream); });
 }
 
 // How many queries of the last voxel-grid NN step the near path settled (diagnostic: synchronises `stream`, reads the groups' masks back).
-static int lsnIcpNearResolved_impl(LsnIcp *w, void *stream)
-{
-    lsn::clear_error();
-    if (!w) return -1;
-    std::lock_guard<std::mutex> g(w->mu);
-    LSN_HIP(hipSetDevice(w->device));
-    LSN_HIP(hipStreamSynchronize(lsn::as_stream(stream)));
-    std::vector<GroupInfo> gi((size_t)w->last_groups);
-    if (w->last_groups > 0) LSN_HIP(hipMemcpy(gi.data(), w->groups.p, sizeof(GroupInfo) * gi.size(), hipMemcpyDeviceToHost));
-    long long n = 0;
-    for (const GroupInfo &x : gi) n += __builtin_popcountll(x.resolved);
-    return (int)n;
-}
-
 extern "C" int lsnIcpNearResolved(LsnIcp *w, void *stream)
 {
-    return lsn::guarded<int>("lsnIcpNearResolved", static_cast<int>(-1), [&]() { return lsnIcpNearResolved_impl(w, stream); });
-}
-
-static int lsnIcpTrace_impl(LsnIcp *w, float *out, int max_iters, void *stream)
-{
-    lsn::clear_error();
-    if (!w || !out) return -1;
-    LSN_HIP(hipSetDevice(w->device));
-    LSN_HIP(hipStreamSynchronize(lsn::as_stream(stream)));
-    int n = w->trace_iters < max_iters ? w->trace_iters : max_iters;
-    if (n > 0) LSN_HIP(hipMemcpy(out, w->trace.p, sizeof(float) * 16 * (size_t)n, hipMemcpyDeviceToHost));
-    return n;
+    return lsn::guarded("lsnIcpNearResolved", -1, [&]() {
+        lsn::clear_error();
+        if (!w) return -1;
+        std::lock_guard<std::mutex> g(w->mu);
+        LSN_HIP(hipSetDevice(w->device));
+        LSN_HIP(hipStreamSynchronize(lsn::as_stream(stream)));
+        std::vector<GroupInfo> gi((size_t)w->last_groups);
+        if (w->last_groups > 0) LSN_HIP(hipMemcpy(gi.data(), w->groups.p, sizeof(GroupInfo) * gi.size(), hipMemcpyDeviceToHost));
+        long long n = 0;
+        for (const GroupInfo &x : gi) n += __builtin_popcountll(x.resolved);
+        return (int)n;
+    });
 }
 
 extern "C" int lsnIcpTrace(LsnIcp *w, float *out, int max_iters, void *stream)
 {
-    return lsn::guarded<int>("lsnIcpTrace", static_cast<int>(-1), [&]() { return lsnIcpTrace_impl(w, out, max_iters, stream); });
+    return lsn::guarded("lsnIcpTrace", -1, [&]() {
+        lsn::clear_error();
+        if (!w || !out) return -1;
+        LSN_HIP(hipSetDevice(w->device));
+        LSN_HIP(hipStreamSynchronize(lsn::as_stream(stream)));
+        int n = w->trace_iters < max_iters ? w->trace_iters : max_iters;
+        if (n > 0) LSN_HIP(hipMemcpy(out, w->trace.p, sizeof(float) * 16 * (size_t)n, hipMemcpyDeviceToHost));
+        return n;
+    });
 }
 
 // refineWorker_DoWork (LiveScanServer/MainWindowForm.cs:330-410) with every cloud resident in HBM for the whole
@@ -2109,118 +2088,114 @@ static RefineState &refine_state()
     return *st;
 }
 
-static int lsnRefine_impl(int device, int n_sensors, float *const *clouds, const int *counts, int n_refine_iters, int n_icp_iters,
-                         float *world_R, float *world_t, float *Rs_out, float *Ts_out)
-{
-    lsn::clear_error();
-    if (n_sensors <= 0 || !clouds || !counts) {
-        lsn::set_error("lsnRefine: bad arguments");
-        return -1;
-    }
-    long long total = 0;
-    int max_n = 0, min_n = 0x7FFFFFFF;
-    for (int i = 0; i < n_sensors; i++) {
-        if (counts[i] < 0 || (counts[i] > 0 && !clouds[i])) {
-            lsn::set_error("lsnRefine: bad cloud %d", i);
-            return -1;
-        }
-        total += counts[i];
-        max_n = counts[i] > max_n ? counts[i] : max_n;
-        min_n = counts[i] < min_n ? counts[i] : min_n;
-    }
-    std::vector<float> Rt((size_t)n_sensors * 12, 0.0f);
-    for (int i = 0; i < n_sensors; i++)
-        for (int j = 0; j < 3; j++) Rt[(size_t)i * 12 + j + j * 3] = 1.0f;   // Rs[i] = I, Ts[i] = 0 (:330-344)
-    const bool runnable = n_sensors >= 2 && min_n > 0 && total - min_n <= 0x7FFFFFFFll && n_refine_iters > 0 && n_icp_iters > 0;
-    if (runnable) {
-        LSN_HIP(hipSetDevice(device));
-        // the pass's device state (workspace, cloud buffers, stream) is kept between calls: allocating it was 2-3 ms of a 20 ms pass.
-        // A second pass running at the same time gets a state of its own.
-        RefineState *rs = &refine_state();
-        std::unique_lock<std::mutex> hold(rs->mu, std::try_to_lock);
-        RefineState own;
-        if (!hold.owns_lock()) rs = &own;
-        const int need1 = (int)(total - min_n), need2 = max_n;
-        if (rs->ws && (rs->device != device || rs->ws->max_n1 < need1 || rs->ws->max_n2 < need2)) rs->drop();
-        if (!rs->ws) {
-            rs->device = device;
-            rs->ws = lsnIcpCreate(device, need1, need2);
-        }
-        int rc = rs->ws ? 0 : -1;
-        if (!rc && !rs->s) rc = hipStreamCreateWithFlags(&rs->s, hipStreamNonBlocking) != hipSuccess;
-        hipStream_t s = rs->s;
-        LsnIcp *ws = rs->ws;
-        lsn::DevBuf &d_all = rs->d_all, &d_others = rs->d_others, &d_Rt = rs->d_Rt, &d_seeds = rs->d_seeds;
-        if (!rc) rc = d_all.reserve(sizeof(float) * 3 * (size_t)total) || d_others.reserve(sizeof(float) * 3 * (size_t)(total - min_n)) ||
-                      d_Rt.reserve(sizeof(float) * Rt.size()) || d_seeds.reserve(sizeof(int) * (size_t)total);
-        std::vector<long long> off(n_sensors + 1, 0);
-        for (int i = 0; i < n_sensors; i++) off[i + 1] = off[i] + counts[i];
-        for (int i = 0; i < n_sensors && !rc; i++)
-            rc = hipMemcpyAsync(d_all.as<float>() + 3 * off[i], clouds[i], sizeof(float) * 3 * (size_t)counts[i], hipMemcpyHostToDevice, s) != hipSuccess;
-        if (!rc) rc = hipMemcpyAsync(d_Rt.p, Rt.data(), sizeof(float) * Rt.size(), hipMemcpyHostToDevice, s) != hipSuccess;
-        for (int it = 0; it < n_refine_iters && !rc; it++) {                  // :347
-            for (int i = 0; i < n_sensors && !rc; i++) {                      // :349
-                // :352-357 all other sensors' current clouds, in sensor order = everything before sensor i's block and everything behind it: two copies
-                const long long pos = total - counts[i];
-                if (off[i] > 0)
-                    rc = hipMemcpyAsync(d_others.as<float>(), d_all.as<float>(), sizeof(float) * 3 * (size_t)off[i], hipMemcpyDeviceToDevice, s) != hipSuccess;
-                if (!rc && off[i + 1] < total)
-                    rc = hipMemcpyAsync(d_others.as<float>() + 3 * off[i], d_all.as<float>() + 3 * off[i + 1], sizeof(float) * 3 * (size_t)(total - off[i + 1]),
-                                        hipMemcpyDeviceToDevice, s) != hipSuccess;
-                // From the second pass on the first NN step of a call is seeded with the neighbours the sensor's call of the previous pass ended
-                // with ("all other sensors" is the same concatenation in every pass, so the indices still name real points; the others have moved a
-                // little, which only makes the seeds a little less tight): ~65 us instead of ~150 for that step, same result (14.23-14.38 ->
-                // 13.98-14.07 ms per call, same digest).
-                if (!rc)
-                    rc = lsn::guarded<int>("lsnRefine", -1, [&]() {
-                        return lsnIcpRun_impl(ws, d_others.as<float>(), (int)pos, d_all.as<float>() + 3 * off[i], counts[i], d_Rt.as<float>() + 12 * i,
-                                              d_Rt.as<float>() + 12 * i + 9, n_icp_iters, 1, s,
-                                              it > 0 ? d_seeds.as<int>() + off[i] : (const int *)nullptr);     // :370
-                    });
-                if (!rc && it + 1 < n_refine_iters)
-                    rc = hipMemcpyAsync(d_seeds.as<int>() + off[i], ws->idx.p, sizeof(int) * (size_t)counts[i], hipMemcpyDeviceToDevice, s) != hipSuccess;
-            }
-        }
-        // results land in scratch first: the caller's arrays are only touched when everything worked
-        std::vector<float> back((size_t)total * 3);
-        if (!rc) rc = hipMemcpyAsync(back.data(), d_all.p, sizeof(float) * 3 * (size_t)total, hipMemcpyDeviceToHost, s) != hipSuccess;
-        if (!rc) rc = hipMemcpyAsync(Rt.data(), d_Rt.p, sizeof(float) * Rt.size(), hipMemcpyDeviceToHost, s) != hipSuccess;
-        if (!rc && s) rc = hipStreamSynchronize(s) != hipSuccess;
-        if (rc) {
-            if (!lsn::has_error()) lsn::set_error("lsnRefine: %s", hipGetErrorString(hipGetLastError()));
-            if (s) (void)hipStreamSynchronize(s);
-            rs->drop();   // nothing of a failed pass is kept
-            return -1;
-        }
-        for (int i = 0; i < n_sensors; i++) memcpy(clouds[i], back.data() + 3 * off[i], sizeof(float) * 3 * (size_t)counts[i]);
-    }
-    // :382-410 pose composition, the C# loops as written
-    if (world_R && world_t) {
-        for (int i = 0; i < n_sensors; i++) {
-            float *WR = world_R + 9 * i, *Wt = world_t + 3 * i;
-            const float *Ri = Rt.data() + 12 * (size_t)i, *Ti = Ri + 9;
-            float tempT[3] = {0, 0, 0};
-            float tempR[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-            for (int j = 0; j < 3; j++) {
-                for (int k = 0; k < 3; k++) tempT[j] += Ti[k] * WR[3 * k + j];
-                Wt[j] += tempT[j];
-            }
-            for (int j = 0; j < 3; j++)
-                for (int k = 0; k < 3; k++) {
-                    for (int l = 0; l < 3; l++) tempR[3 * j + k] += Ri[l * 3 + j] * WR[3 * l + k];
-                    WR[3 * j + k] = tempR[3 * j + k];
-                }
-        }
-    }
-    for (int i = 0; i < n_sensors; i++) {
-        if (Rs_out) memcpy(Rs_out + 9 * i, Rt.data() + 12 * (size_t)i, 9 * sizeof(float));
-        if (Ts_out) memcpy(Ts_out + 3 * i, Rt.data() + 12 * (size_t)i + 9, 3 * sizeof(float));
-    }
-    return 0;
-}
-
 extern "C" int lsnRefine(int device, int n_sensors, float *const *clouds, const int *counts, int n_refine_iters, int n_icp_iters,
                          float *world_R, float *world_t, float *Rs_out, float *Ts_out)
 {
-    return lsn::guarded<int>("lsnRefine", static_cast<int>(-1), [&]() { return lsnRefine_impl(device, n_sensors, clouds, counts, n_refine_iters, n_icp_iters, world_R, world_t, Rs_out, Ts_out); });
+    return lsn::guarded("lsnRefine", -1, [&]() {
+        lsn::clear_error();
+        if (n_sensors <= 0 || !clouds || !counts) {
+            lsn::set_error("lsnRefine: bad arguments");
+            return -1;
+        }
+        long long total = 0;
+        int max_n = 0, min_n = 0x7FFFFFFF;
+        for (int i = 0; i < n_sensors; i++) {
+            if (counts[i] < 0 || (counts[i] > 0 && !clouds[i])) {
+                lsn::set_error("lsnRefine: bad cloud %d", i);
+                return -1;
+            }
+            total += counts[i];
+            max_n = counts[i] > max_n ? counts[i] : max_n;
+            min_n = counts[i] < min_n ? counts[i] : min_n;
+        }
+        std::vector<float> Rt((size_t)n_sensors * 12, 0.0f);
+        for (int i = 0; i < n_sensors; i++)
+            for (int j = 0; j < 3; j++) Rt[(size_t)i * 12 + j + j * 3] = 1.0f;   // Rs[i] = I, Ts[i] = 0 (:330-344)
+        const bool runnable = n_sensors >= 2 && min_n > 0 && total - min_n <= 0x7FFFFFFFll && n_refine_iters > 0 && n_icp_iters > 0;
+        if (runnable) {
+            LSN_HIP(hipSetDevice(device));
+            // the pass's device state (workspace, cloud buffers, stream) is kept between calls: allocating it was 2-3 ms of a 20 ms pass.
+            // A second pass running at the same time gets a state of its own.
+            RefineState *rs = &refine_state();
+            std::unique_lock<std::mutex> hold(rs->mu, std::try_to_lock);
+            RefineState own;
+            if (!hold.owns_lock()) rs = &own;
+            const int need1 = (int)(total - min_n), need2 = max_n;
+            if (rs->ws && (rs->device != device || rs->ws->max_n1 < need1 || rs->ws->max_n2 < need2)) rs->drop();
+            if (!rs->ws) {
+                rs->device = device;
+                rs->ws = lsnIcpCreate(device, need1, need2);
+            }
+            int rc = rs->ws ? 0 : -1;
+            if (!rc && !rs->s) rc = hipStreamCreateWithFlags(&rs->s, hipStreamNonBlocking) != hipSuccess;
+            hipStream_t s = rs->s;
+            LsnIcp *ws = rs->ws;
+            lsn::DevBuf &d_all = rs->d_all, &d_others = rs->d_others, &d_Rt = rs->d_Rt, &d_seeds = rs->d_seeds;
+            if (!rc) rc = d_all.reserve(sizeof(float) * 3 * (size_t)total) || d_others.reserve(sizeof(float) * 3 * (size_t)(total - min_n)) ||
+                          d_Rt.reserve(sizeof(float) * Rt.size()) || d_seeds.reserve(sizeof(int) * (size_t)total);
+            std::vector<long long> off(n_sensors + 1, 0);
+            for (int i = 0; i < n_sensors; i++) off[i + 1] = off[i] + counts[i];
+            for (int i = 0; i < n_sensors && !rc; i++)
+                rc = hipMemcpyAsync(d_all.as<float>() + 3 * off[i], clouds[i], sizeof(float) * 3 * (size_t)counts[i], hipMemcpyHostToDevice, s) != hipSuccess;
+            if (!rc) rc = hipMemcpyAsync(d_Rt.p, Rt.data(), sizeof(float) * Rt.size(), hipMemcpyHostToDevice, s) != hipSuccess;
+            for (int it = 0; it < n_refine_iters && !rc; it++) {                  // :347
+                for (int i = 0; i < n_sensors && !rc; i++) {                      // :349
+                    // :352-357 all other sensors' current clouds, in sensor order = everything before sensor i's block and everything behind it: two copies
+                    const long long pos = total - counts[i];
+                    if (off[i] > 0)
+                        rc = hipMemcpyAsync(d_others.as<float>(), d_all.as<float>(), sizeof(float) * 3 * (size_t)off[i], hipMemcpyDeviceToDevice, s) != hipSuccess;
+                    if (!rc && off[i + 1] < total)
+                        rc = hipMemcpyAsync(d_others.as<float>() + 3 * off[i], d_all.as<float>() + 3 * off[i + 1], sizeof(float) * 3 * (size_t)(total - off[i + 1]),
+                                            hipMemcpyDeviceToDevice, s) != hipSuccess;
+                    // From the second pass on the first NN step of a call is seeded with the neighbours the sensor's call of the previous pass ended
+                    // with ("all other sensors" is the same concatenation in every pass, so the indices still name real points; the others have moved a
+                    // little, which only makes the seeds a little less tight): ~65 us instead of ~150 for that step, same result (14.23-14.38 ->
+                    // 13.98-14.07 ms per call, same digest).
+                    if (!rc)
+                        rc = lsn::guarded("lsnRefine", -1, [&]() {
+                            return icp_run(ws, d_others.as<float>(), (int)pos, d_all.as<float>() + 3 * off[i], counts[i], d_Rt.as<float>() + 12 * i,
+                                           d_Rt.as<float>() + 12 * i + 9, n_icp_iters, 1, s,
+                                           it > 0 ? d_seeds.as<int>() + off[i] : (const int *)nullptr);     // :370
+                        });
+                    if (!rc && it + 1 < n_refine_iters)
+                        rc = hipMemcpyAsync(d_seeds.as<int>() + off[i], ws->idx.p, sizeof(int) * (size_t)counts[i], hipMemcpyDeviceToDevice, s) != hipSuccess;
+                }
+            }
+            // results land in scratch first: the caller's arrays are only touched when everything worked
+            std::vector<float> back((size_t)total * 3);
+            if (!rc) rc = hipMemcpyAsync(back.data(), d_all.p, sizeof(float) * 3 * (size_t)total, hipMemcpyDeviceToHost, s) != hipSuccess;
+            if (!rc) rc = hipMemcpyAsync(Rt.data(), d_Rt.p, sizeof(float) * Rt.size(), hipMemcpyDeviceToHost, s) != hipSuccess;
+            if (!rc && s) rc = hipStreamSynchronize(s) != hipSuccess;
+            if (rc) {
+                if (!lsn::has_error()) lsn::set_error("lsnRefine: %s", hipGetErrorString(hipGetLastError()));
+                if (s) (void)hipStreamSynchronize(s);
+                rs->drop();   // nothing of a failed pass is kept
+                return -1;
+            }
+            for (int i = 0; i < n_sensors; i++) memcpy(clouds[i], back.data() + 3 * off[i], sizeof(float) * 3 * (size_t)counts[i]);
+        }
+        // :382-410 pose composition, the C# loops as written
+        if (world_R && world_t) {
+            for (int i = 0; i < n_sensors; i++) {
+                float *WR = world_R + 9 * i, *Wt = world_t + 3 * i;
+                const float *Ri = Rt.data() + 12 * (size_t)i, *Ti = Ri + 9;
+                float tempT[3] = {0, 0, 0};
+                float tempR[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+                for (int j = 0; j < 3; j++) {
+                    for (int k = 0; k < 3; k++) tempT[j] += Ti[k] * WR[3 * k + j];
+                    Wt[j] += tempT[j];
+                }
+                for (int j = 0; j < 3; j++)
+                    for (int k = 0; k < 3; k++) {
+                        for (int l = 0; l < 3; l++) tempR[3 * j + k] += Ri[l * 3 + j] * WR[3 * l + k];
+                        WR[3 * j + k] = tempR[3 * j + k];
+                    }
+            }
+        }
+        for (int i = 0; i < n_sensors; i++) {
+            if (Rs_out) memcpy(Rs_out + 9 * i, Rt.data() + 12 * (size_t)i, 9 * sizeof(float));
+            if (Ts_out) memcpy(Ts_out + 3 * i, Rt.data() + 12 * (size_t)i + 9, 3 * sizeof(float));
+        }
+        return 0;
+    });
 }

@@ -27,6 +27,7 @@ void test_fault_point(int kind);                       // 0 = guarded entry, 1 =
 
 // Every extern "C" entry point runs its body through this: no exception may cross the C-ABI into a P/Invoke frame
 // (SURVEY 8b "exceptions must not escape"; the reference itself lets nanoflann throw, include/nanoflann.h:904).
+// R is the type of `fail`, what the export returns when its body threw; a body whose returns are not all of that type names it (-> R).
 template <class R, class F>
 inline R guarded(const char *name, R fail, F &&body) noexcept
 {
@@ -40,18 +41,14 @@ inline R guarded(const char *name, R fail, F &&body) noexcept
     }
     return fail;
 }
+// The same for an export that returns nothing.
 template <class F>
 inline void guarded_void(const char *name, F &&body) noexcept
 {
-    try {
-        test_fault_point(0);
+    (void)guarded(name, false, [&]() {
         body();
-        return;
-    } catch (const std::exception &e) {
-        set_error("%s: %s", name, e.what());
-    } catch (...) {
-        set_error("%s: unknown exception", name);
-    }
+        return true;
+    });
 }
 
 #define LSN_HIP(expr)                                                                                    \

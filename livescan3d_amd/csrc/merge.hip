@@ -350,47 +350,42 @@ int overlay_merge(LsnFusion *p, const void *d_depth, const void *d_vertices, con
 extern "C" int lsnFusionOverlayMerge(LsnFusion *p, const void *d_depth_maps, const void *d_vertices, const int *d_offsets, void *d_triangles,
                                      int *d_tri_offsets, void *stream)
 {
-    return lsn::guarded<int>("lsnFusionOverlayMerge", static_cast<int>(-1), [&]() {
+    return lsn::guarded("lsnFusionOverlayMerge", -1, [&]() {
         lsn::clear_error();
         return lsn::overlay_merge(p, d_depth_maps, d_vertices, d_offsets, d_triangles, d_tri_offsets, lsn::as_stream(stream));
     });
 }
 
-static int lsnFusionOverlayDiagnostics_impl(LsnFusion *p, int tick, unsigned short *reprojected, unsigned short *merged, unsigned char *assigned,
-                                            void *stream)
-{
-    lsn::clear_error();
-    if (!p || tick < 0 || tick >= p->n_ticks) {
-        lsn::set_error("lsnFusionOverlayDiagnostics: bad arguments");
-        return -1;
-    }
-    std::lock_guard<std::mutex> g(p->mu);
-    if (!p->mg_ready) {
-        lsn::set_error("lsnFusionOverlayDiagnostics: no overlay merge has run on this plan");
-        return -1;
-    }
-    LSN_HIP(hipSetDevice(p->device));
-    hipStream_t s = lsn::as_stream(stream);
-    const int n = p->n_maps;
-    std::vector<int> off((size_t)n + 1);
-    LSN_HIP(hipMemcpyAsync(off.data(), p->ix_off.as<int>() + (size_t)tick * (n + 1), sizeof(int) * (n + 1), hipMemcpyDeviceToHost, s));
-    const size_t pix = (size_t)p->tick_depth_elems;
-    if (reprojected)
-        LSN_HIP(hipMemcpyAsync(reprojected, p->mg_depth0.as<unsigned short>() + (size_t)tick * pix, sizeof(unsigned short) * pix, hipMemcpyDeviceToHost, s));
-    if (merged) LSN_HIP(hipMemcpyAsync(merged, p->mg_depth.as<unsigned short>() + (size_t)tick * pix, sizeof(unsigned short) * pix, hipMemcpyDeviceToHost, s));
-    std::vector<unsigned char> asg((size_t)p->cap);
-    LSN_HIP(hipMemcpyAsync(asg.data(), p->mg_assigned.as<unsigned char>() + (size_t)tick * p->cap, (size_t)p->cap, hipMemcpyDeviceToHost, s));
-    LSN_HIP(hipStreamSynchronize(s));
-    const int nv = std::min<long long>(std::max(off[n], 0), p->cap);
-    int count = 0;
-    for (int v = 0; v < nv; v++) count += asg[v] != 0;
-    if (assigned) memcpy(assigned, asg.data(), (size_t)nv);
-    return count;
-}
-
 extern "C" int lsnFusionOverlayDiagnostics(LsnFusion *p, int tick, unsigned short *reprojected, unsigned short *merged, unsigned char *assigned,
                                            void *stream)
 {
-    return lsn::guarded<int>("lsnFusionOverlayDiagnostics", static_cast<int>(-1),
-                             [&]() { return lsnFusionOverlayDiagnostics_impl(p, tick, reprojected, merged, assigned, stream); });
+    return lsn::guarded("lsnFusionOverlayDiagnostics", -1, [&]() {
+        lsn::clear_error();
+        if (!p || tick < 0 || tick >= p->n_ticks) {
+            lsn::set_error("lsnFusionOverlayDiagnostics: bad arguments");
+            return -1;
+        }
+        std::lock_guard<std::mutex> g(p->mu);
+        if (!p->mg_ready) {
+            lsn::set_error("lsnFusionOverlayDiagnostics: no overlay merge has run on this plan");
+            return -1;
+        }
+        LSN_HIP(hipSetDevice(p->device));
+        hipStream_t s = lsn::as_stream(stream);
+        const int n = p->n_maps;
+        std::vector<int> off((size_t)n + 1);
+        LSN_HIP(hipMemcpyAsync(off.data(), p->ix_off.as<int>() + (size_t)tick * (n + 1), sizeof(int) * (n + 1), hipMemcpyDeviceToHost, s));
+        const size_t pix = (size_t)p->tick_depth_elems;
+        if (reprojected)
+            LSN_HIP(hipMemcpyAsync(reprojected, p->mg_depth0.as<unsigned short>() + (size_t)tick * pix, sizeof(unsigned short) * pix, hipMemcpyDeviceToHost, s));
+        if (merged) LSN_HIP(hipMemcpyAsync(merged, p->mg_depth.as<unsigned short>() + (size_t)tick * pix, sizeof(unsigned short) * pix, hipMemcpyDeviceToHost, s));
+        std::vector<unsigned char> asg((size_t)p->cap);
+        LSN_HIP(hipMemcpyAsync(asg.data(), p->mg_assigned.as<unsigned char>() + (size_t)tick * p->cap, (size_t)p->cap, hipMemcpyDeviceToHost, s));
+        LSN_HIP(hipStreamSynchronize(s));
+        const int nv = std::min<long long>(std::max(off[n], 0), p->cap);
+        int count = 0;
+        for (int v = 0; v < nv; v++) count += asg[v] != 0;
+        if (assigned) memcpy(assigned, asg.data(), (size_t)nv);
+        return count;
+    });
 }

@@ -534,17 +534,13 @@ static int reserve_tri_scratch(LsnFusion *p)
 
 extern "C" long long lsnFusionTickTriangleCapacity(const LsnFusion *p) { return p ? 2 * p->cap : 0; }
 
-static int lsnFusionRunMesh_impl(LsnFusion *p, const void *d_depth, const void *d_colors, void *d_vertices, int *d_offsets,
-                                void *d_triangles, int *d_tri_offsets, void *stream)
-{
-    lsn::clear_error();
-    return lsn::run_mesh(p, d_depth, d_colors, d_vertices, d_offsets, d_triangles, d_tri_offsets, lsn::as_stream(stream));
-}
-
 extern "C" int lsnFusionRunMesh(LsnFusion *p, const void *d_depth, const void *d_colors, void *d_vertices, int *d_offsets,
                                 void *d_triangles, int *d_tri_offsets, void *stream)
 {
-    return lsn::guarded<int>("lsnFusionRunMesh", static_cast<int>(-1), [&]() { return lsnFusionRunMesh_impl(p, d_depth, d_colors, d_vertices, d_offsets, d_triangles, d_tri_offsets, stream); });
+    return lsn::guarded("lsnFusionRunMesh", -1, [&]() {
+        lsn::clear_error();
+        return lsn::run_mesh(p, d_depth, d_colors, d_vertices, d_offsets, d_triangles, d_tri_offsets, lsn::as_stream(stream));
+    });
 }
 
 int lsn::run_mesh(LsnFusion *p, const void *d_depth, const void *d_colors, void *d_vertices, int *d_offsets, void *d_triangles,

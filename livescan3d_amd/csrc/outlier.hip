@@ -460,48 +460,42 @@ int outlier_filter(LsnFusion *p, int k, float max_dist, const void *d_depth, con
 extern "C" int lsnFusionOutlierFilter(LsnFusion *p, int k, float max_dist, const void *d_depth_maps, const void *d_vertices, const int *d_offsets,
                                       void *d_depth_out, void *stream)
 {
-    return lsn::guarded<int>("lsnFusionOutlierFilter", static_cast<int>(-1), [&]() {
+    return lsn::guarded("lsnFusionOutlierFilter", -1, [&]() {
         lsn::clear_error();
         return lsn::outlier_filter(p, k, max_dist, d_depth_maps, d_vertices, d_offsets, d_depth_out, lsn::as_stream(stream));
     });
 }
 
-static int lsnFusionOutlierDiagnostics_impl(LsnFusion *p, int tick, int *removed_per_sensor, unsigned char *removed_per_vertex,
-                                            int *exact_per_sensor, void *stream)
-{
-    lsn::clear_error();
-    if (!p || tick < 0 || tick >= p->n_ticks) {
-        lsn::set_error("lsnFusionOutlierDiagnostics: bad arguments");
-        return -1;
-    }
-    std::lock_guard<std::mutex> g(p->mu);
-    if (!p->ol_ready) {
-        lsn::set_error("lsnFusionOutlierDiagnostics: no outlier filter has run on this plan");
-        return -1;
-    }
-    LSN_HIP(hipSetDevice(p->device));
-    hipStream_t s = lsn::as_stream(stream);
-    const int n = p->n_maps;
-    std::vector<int> off((size_t)n + 1), st(2 * (size_t)n);
-    LSN_HIP(hipMemcpyAsync(off.data(), p->ol_offs.as<int>() + (size_t)tick * (n + 1), sizeof(int) * (n + 1), hipMemcpyDeviceToHost, s));
-    LSN_HIP(hipMemcpyAsync(st.data(), p->ol_stats.as<int>() + (size_t)tick * 2 * n, sizeof(int) * 2 * n, hipMemcpyDeviceToHost, s));
-    LSN_HIP(hipStreamSynchronize(s));
-    const int nv = (int)std::min<long long>(std::max(off[n], 0), p->cap);
-    if (removed_per_vertex && nv > 0)
-        LSN_HIP(hipMemcpy(removed_per_vertex, p->ol_removed.as<unsigned char>() + (size_t)tick * p->cap, (size_t)nv, hipMemcpyDeviceToHost));
-    int total = 0;
-    for (int i = 0; i < n; i++) {
-        total += st[i];
-        if (removed_per_sensor) removed_per_sensor[i] = st[i];
-        if (exact_per_sensor) exact_per_sensor[i] = st[n + i];
-    }
-    return total;
-}
-
 extern "C" int lsnFusionOutlierDiagnostics(LsnFusion *p, int tick, int *removed_per_sensor, unsigned char *removed_per_vertex, int *exact_per_sensor,
                                            void *stream)
 {
-    return lsn::guarded<int>("lsnFusionOutlierDiagnostics", static_cast<int>(-1), [&]() {
-        return lsnFusionOutlierDiagnostics_impl(p, tick, removed_per_sensor, removed_per_vertex, exact_per_sensor, stream);
+    return lsn::guarded("lsnFusionOutlierDiagnostics", -1, [&]() {
+        lsn::clear_error();
+        if (!p || tick < 0 || tick >= p->n_ticks) {
+            lsn::set_error("lsnFusionOutlierDiagnostics: bad arguments");
+            return -1;
+        }
+        std::lock_guard<std::mutex> g(p->mu);
+        if (!p->ol_ready) {
+            lsn::set_error("lsnFusionOutlierDiagnostics: no outlier filter has run on this plan");
+            return -1;
+        }
+        LSN_HIP(hipSetDevice(p->device));
+        hipStream_t s = lsn::as_stream(stream);
+        const int n = p->n_maps;
+        std::vector<int> off((size_t)n + 1), st(2 * (size_t)n);
+        LSN_HIP(hipMemcpyAsync(off.data(), p->ol_offs.as<int>() + (size_t)tick * (n + 1), sizeof(int) * (n + 1), hipMemcpyDeviceToHost, s));
+        LSN_HIP(hipMemcpyAsync(st.data(), p->ol_stats.as<int>() + (size_t)tick * 2 * n, sizeof(int) * 2 * n, hipMemcpyDeviceToHost, s));
+        LSN_HIP(hipStreamSynchronize(s));
+        const int nv = (int)std::min<long long>(std::max(off[n], 0), p->cap);
+        if (removed_per_vertex && nv > 0)
+            LSN_HIP(hipMemcpy(removed_per_vertex, p->ol_removed.as<unsigned char>() + (size_t)tick * p->cap, (size_t)nv, hipMemcpyDeviceToHost));
+        int total = 0;
+        for (int i = 0; i < n; i++) {
+            total += st[i];
+            if (removed_per_sensor) removed_per_sensor[i] = st[i];
+            if (exact_per_sensor) exact_per_sensor[i] = st[n + i];
+        }
+        return total;
     });
 }

@@ -1318,58 +1318,48 @@ static int radial_correct_on(LsnFusion *p, const float *intr_params, const void 
 
 // Test hook: how many of the closing chain's work counters are not zero once `stream` has drained.  The chain leaves them all cleared when
 // it has run to its end (that is what lets the next call skip its memset); tests/test_radial_gpu.py holds it to that on every closing route.
-static int lsnFusionRadialCountersLeft_impl(LsnFusion *p, void *stream)
-{
-    lsn::clear_error();
-    if (!p) return -1;
-    std::lock_guard<std::mutex> g(p->mu);
-    LSN_HIP(hipSetDevice(p->device));
-    LSN_HIP(hipStreamSynchronize(lsn::as_stream(stream)));
-    if (!p->work_cnt.p || p->work_cnt.bytes == 0) return 0;
-    std::vector<int> host(p->work_cnt.bytes / sizeof(int));
-    LSN_HIP(hipMemcpy(host.data(), p->work_cnt.p, host.size() * sizeof(int), hipMemcpyDeviceToHost));
-    int left = 0;
-    for (int v : host) left += v != 0;
-    return left;
-}
-
 extern "C" int lsnFusionRadialCountersLeft(LsnFusion *p, void *stream)
 {
-    return lsn::guarded<int>("lsnFusionRadialCountersLeft", static_cast<int>(-1), [&]() { return lsnFusionRadialCountersLeft_impl(p, stream); });
-}
-
-static int lsnFusionRadialCorrect_impl(LsnFusion *p, const float *intr_params, void *d_depth, void *d_colors, void *stream)
-{
-    lsn::clear_error();
-    if (!p || !intr_params || !d_depth || !d_colors) {
-        lsn::set_error("lsnFusionRadialCorrect: null argument");
-        return -1;
-    }
-    std::lock_guard<std::mutex> g(p->mu);
-    return radial_correct(p, intr_params, d_depth, d_colors, d_depth, d_colors, lsn::as_stream(stream));
+    return lsn::guarded("lsnFusionRadialCountersLeft", -1, [&]() {
+        lsn::clear_error();
+        if (!p) return -1;
+        std::lock_guard<std::mutex> g(p->mu);
+        LSN_HIP(hipSetDevice(p->device));
+        LSN_HIP(hipStreamSynchronize(lsn::as_stream(stream)));
+        if (!p->work_cnt.p || p->work_cnt.bytes == 0) return 0;
+        std::vector<int> host(p->work_cnt.bytes / sizeof(int));
+        LSN_HIP(hipMemcpy(host.data(), p->work_cnt.p, host.size() * sizeof(int), hipMemcpyDeviceToHost));
+        int left = 0;
+        for (int v : host) left += v != 0;
+        return left;
+    });
 }
 
 extern "C" int lsnFusionRadialCorrect(LsnFusion *p, const float *intr_params, void *d_depth, void *d_colors, void *stream)
 {
-    return lsn::guarded<int>("lsnFusionRadialCorrect", static_cast<int>(-1), [&]() { return lsnFusionRadialCorrect_impl(p, intr_params, d_depth, d_colors, stream); });
-}
-
-static int lsnFusionRadialCorrectTo_impl(LsnFusion *p, const float *intr_params, const void *d_depth_in, const void *d_colors_in, void *d_depth_out,
-                                        void *d_colors_out, void *stream)
-{
-    lsn::clear_error();
-    if (!p || !intr_params || !d_depth_in || !d_colors_in || !d_depth_out || !d_colors_out) {
-        lsn::set_error("lsnFusionRadialCorrectTo: null argument");
-        return -1;
-    }
-    std::lock_guard<std::mutex> g(p->mu);
-    return radial_correct(p, intr_params, d_depth_in, d_colors_in, d_depth_out, d_colors_out, lsn::as_stream(stream));
+    return lsn::guarded("lsnFusionRadialCorrect", -1, [&]() {
+        lsn::clear_error();
+        if (!p || !intr_params || !d_depth || !d_colors) {
+            lsn::set_error("lsnFusionRadialCorrect: null argument");
+            return -1;
+        }
+        std::lock_guard<std::mutex> g(p->mu);
+        return radial_correct(p, intr_params, d_depth, d_colors, d_depth, d_colors, lsn::as_stream(stream));
+    });
 }
 
 extern "C" int lsnFusionRadialCorrectTo(LsnFusion *p, const float *intr_params, const void *d_depth_in, const void *d_colors_in, void *d_depth_out,
                                         void *d_colors_out, void *stream)
 {
-    return lsn::guarded<int>("lsnFusionRadialCorrectTo", static_cast<int>(-1), [&]() { return lsnFusionRadialCorrectTo_impl(p, intr_params, d_depth_in, d_colors_in, d_depth_out, d_colors_out, stream); });
+    return lsn::guarded("lsnFusionRadialCorrectTo", -1, [&]() {
+        lsn::clear_error();
+        if (!p || !intr_params || !d_depth_in || !d_colors_in || !d_depth_out || !d_colors_out) {
+            lsn::set_error("lsnFusionRadialCorrectTo: null argument");
+            return -1;
+        }
+        std::lock_guard<std::mutex> g(p->mu);
+        return radial_correct(p, intr_params, d_depth_in, d_colors_in, d_depth_out, d_colors_out, lsn::as_stream(stream));
+    });
 }
 
 // The flying-pixel filter, the per-sensor depth stage in front of this one, is compiled as part of this translation unit.

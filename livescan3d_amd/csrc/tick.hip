@@ -28,7 +28,8 @@ struct LsnTick {
     std::mutex mu;
 };
 
-static void lsnTickDestroy_impl(LsnTick *t)
+// The body of lsnTickDestroy under a name of its own: lsnTickCreate calls it too, on a tick object it could not finish.
+static void tick_destroy(LsnTick *t)
 {
     if (!t) return;
     (void)hipSetDevice(t->device);
@@ -46,158 +47,143 @@ static void lsnTickDestroy_impl(LsnTick *t)
 
 extern "C" void lsnTickDestroy(LsnTick *t)
 {
-    lsn::guarded_void("lsnTickDestroy", [&]() { lsnTickDestroy_impl(t); });
-}
-
-static LsnTick *lsnTickCreate_impl(int device, int n_ticks, int n_maps, const int *widths, const int *heights)
-{
-    lsn::clear_error();
-    if (n_ticks <= 0 || n_maps <= 0 || !widths || !heights) {
-        lsn::set_error("lsnTickCreate: bad arguments");
-        return nullptr;
-    }
-    LsnTick *t = new (std::nothrow) LsnTick();
-    if (!t) return nullptr;
-    t->device = device;
-    t->n_ticks = n_ticks;
-    t->n_maps = n_maps;
-    // two halves from 8 ticks up ($LSN_TICK_PARTS=1: one plan, one stream -- the two calls as they are)
-    int parts = n_ticks >= 8 ? 2 : 1;
-    if (const char *e = getenv("LSN_TICK_PARTS")) parts = atoi(e) >= 2 && n_ticks >= 2 ? 2 : 1;
-    t->parts = parts;
-    t->first[0] = 0;
-    t->first[1] = parts == 2 ? (n_ticks + 1) / 2 : n_ticks;
-    t->first[2] = n_ticks;
-    bool bad = false;
-    for (int k = 0; k < parts && !bad; k++) {
-        t->plan[k] = lsnFusionCreate(device, t->first[k + 1] - t->first[k], n_maps, widths, heights);
-        bad = !t->plan[k];
-    }
-    if (!bad) {
-        t->cap = lsnFusionTickCapacity(t->plan[0]);
-        t->tri_cap = lsnFusionTickTriangleCapacity(t->plan[0]);
-        bad = hipSetDevice(device) != hipSuccess;
-        if (!bad && parts == 2)
-            bad = hipStreamCreateWithFlags(&t->side, hipStreamNonBlocking) != hipSuccess ||
-                  hipEventCreateWithFlags(&t->ev_fork, hipEventDisableTiming) != hipSuccess ||
-                  hipEventCreateWithFlags(&t->ev_join, hipEventDisableTiming) != hipSuccess ||
-                  hipEventCreateWithFlags(&t->ev_band, hipEventDisableTiming) != hipSuccess;
-        if (bad && !lsn::has_error()) lsn::set_error("lsnTickCreate: %s", hipGetErrorString(hipGetLastError()));
-    }
-    if (bad) {
-        lsnTickDestroy_impl(t);
-        return nullptr;
-    }
-    return t;
+    lsn::guarded_void("lsnTickDestroy", [&]() { tick_destroy(t); });
 }
 
 extern "C" LsnTick *lsnTickCreate(int device, int n_ticks, int n_maps, const int *widths, const int *heights)
 {
-    return lsn::guarded<LsnTick *>("lsnTickCreate", static_cast<LsnTick *>(nullptr), [&]() { return lsnTickCreate_impl(device, n_ticks, n_maps, widths, heights); });
+    return lsn::guarded("lsnTickCreate", static_cast<LsnTick *>(nullptr), [&]() -> LsnTick * {
+        lsn::clear_error();
+        if (n_ticks <= 0 || n_maps <= 0 || !widths || !heights) {
+            lsn::set_error("lsnTickCreate: bad arguments");
+            return nullptr;
+        }
+        LsnTick *t = new (std::nothrow) LsnTick();
+        if (!t) return nullptr;
+        t->device = device;
+        t->n_ticks = n_ticks;
+        t->n_maps = n_maps;
+        // two halves from 8 ticks up ($LSN_TICK_PARTS=1: one plan, one stream -- the two calls as they are)
+        int parts = n_ticks >= 8 ? 2 : 1;
+        if (const char *e = getenv("LSN_TICK_PARTS")) parts = atoi(e) >= 2 && n_ticks >= 2 ? 2 : 1;
+        t->parts = parts;
+        t->first[0] = 0;
+        t->first[1] = parts == 2 ? (n_ticks + 1) / 2 : n_ticks;
+        t->first[2] = n_ticks;
+        bool bad = false;
+        for (int k = 0; k < parts && !bad; k++) {
+            t->plan[k] = lsnFusionCreate(device, t->first[k + 1] - t->first[k], n_maps, widths, heights);
+            bad = !t->plan[k];
+        }
+        if (!bad) {
+            t->cap = lsnFusionTickCapacity(t->plan[0]);
+            t->tri_cap = lsnFusionTickTriangleCapacity(t->plan[0]);
+            bad = hipSetDevice(device) != hipSuccess;
+            if (!bad && parts == 2)
+                bad = hipStreamCreateWithFlags(&t->side, hipStreamNonBlocking) != hipSuccess ||
+                      hipEventCreateWithFlags(&t->ev_fork, hipEventDisableTiming) != hipSuccess ||
+                      hipEventCreateWithFlags(&t->ev_join, hipEventDisableTiming) != hipSuccess ||
+                      hipEventCreateWithFlags(&t->ev_band, hipEventDisableTiming) != hipSuccess;
+            if (bad && !lsn::has_error()) lsn::set_error("lsnTickCreate: %s", hipGetErrorString(hipGetLastError()));
+        }
+        if (bad) {
+            tick_destroy(t);
+            return nullptr;
+        }
+        return t;
+    });
 }
 
 extern "C" long long lsnTickCapacity(const LsnTick *t) { return t ? t->cap : 0; }
 extern "C" long long lsnTickTriangleCapacity(const LsnTick *t) { return t ? t->tri_cap : 0; }
 extern "C" int lsnTickParts(const LsnTick *t) { return t ? t->parts : 0; }
 
-static int lsnTickSetParams_impl(LsnTick *t, const float *intr, const float *wt, const float *bounds6, void *stream)
-{
-    lsn::clear_error();
-    if (!t || !intr || !wt || !bounds6) {
-        lsn::set_error("lsnTickSetParams: null argument");
-        return -1;
-    }
-    std::lock_guard<std::mutex> g(t->mu);
-    t->intr.assign(intr, intr + 7 * (size_t)t->n_maps);
-    for (int k = 0; k < t->parts; k++)
-        if (lsnFusionSetParams(t->plan[k], intr, wt, bounds6, stream)) return -1;
-    return 0;
-}
-
 extern "C" int lsnTickSetParams(LsnTick *t, const float *intr, const float *wt, const float *bounds6, void *stream)
 {
-    return lsn::guarded<int>("lsnTickSetParams", static_cast<int>(-1), [&]() { return lsnTickSetParams_impl(t, intr, wt, bounds6, stream); });
-}
-
-static int lsnTickSetFlyingPixels_impl(LsnTick *t, int neighbourhood, int threshold)
-{
-    lsn::clear_error();
-    if (!t) {
-        lsn::set_error("lsnTickSetFlyingPixels: null argument");
-        return -1;
-    }
-    std::lock_guard<std::mutex> g(t->mu);
-    t->fp_neighbourhood = neighbourhood;
-    t->fp_threshold = threshold;
-    return 0;
+    return lsn::guarded("lsnTickSetParams", -1, [&]() {
+        lsn::clear_error();
+        if (!t || !intr || !wt || !bounds6) {
+            lsn::set_error("lsnTickSetParams: null argument");
+            return -1;
+        }
+        std::lock_guard<std::mutex> g(t->mu);
+        t->intr.assign(intr, intr + 7 * (size_t)t->n_maps);
+        for (int k = 0; k < t->parts; k++)
+            if (lsnFusionSetParams(t->plan[k], intr, wt, bounds6, stream)) return -1;
+        return 0;
+    });
 }
 
 extern "C" int lsnTickSetFlyingPixels(LsnTick *t, int neighbourhood, int threshold)
 {
-    return lsn::guarded<int>("lsnTickSetFlyingPixels", static_cast<int>(-1), [&]() { return lsnTickSetFlyingPixels_impl(t, neighbourhood, threshold); });
-}
-
-static int lsnTickRun_impl(LsnTick *t, const void *d_depth_in, const void *d_colors_in, void *d_depth_corr, void *d_colors_corr, void *d_vertices,
-                           int *d_offsets, void *d_triangles, int *d_tri_offsets, void *stream)
-{
-    lsn::clear_error();
-    if (!t || !d_depth_in || !d_colors_in || !d_depth_corr || !d_colors_corr || !d_vertices || !d_offsets || !d_triangles || !d_tri_offsets) {
-        lsn::set_error("lsnTickRun: null argument");
-        return -1;
-    }
-    if (t->intr.empty()) {
-        lsn::set_error("lsnTickRun: lsnTickSetParams has not been called");
-        return -1;
-    }
-    std::lock_guard<std::mutex> g(t->mu);
-    LSN_HIP(hipSetDevice(t->device));
-    hipStream_t s = lsn::as_stream(stream);
-    const bool filter = t->fp_neighbourhood >= 1;
-    if (filter && t->d_filtered.reserve(2 * (size_t)t->cap * t->n_ticks + 16)) return -1;
-    // part k's slices of the caller's arrays: [tick][pixels], [tick][pixels][3], [tick][capacity] vertices, [tick][n_maps + 1], ...
-    auto part = [&](int k, hipStream_t st) -> int {
-        const size_t t0 = (size_t)t->first[k];
-        const size_t px = (size_t)t->cap, nm = (size_t)t->n_maps + 1;
-        const unsigned char *din = static_cast<const unsigned char *>(d_depth_in) + 2 * px * t0, *cin = static_cast<const unsigned char *>(d_colors_in) + 3 * px * t0;
-        unsigned char *dco = static_cast<unsigned char *>(d_depth_corr) + 2 * px * t0, *cco = static_cast<unsigned char *>(d_colors_corr) + 3 * px * t0;
-        if (filter) {   // filter -> correction: the filtered maps go through the tick's scratch, the caller's input stays as it is
-            unsigned char *dfl = t->d_filtered.as<unsigned char>() + 2 * px * t0;
-            // the scratch is shared by all runs of the tick object: a run on another stream than the previous one's waits until that
-            // run's correction has read it (the event radial.hip records behind every chain)
-            LsnFusion *pl = t->plan[k];
-            if (pl->radial_chain_open && pl->work_cnt_stream != st) LSN_HIP(hipStreamWaitEvent(st, pl->radial_done, 0));
-            if (lsn::flying_pixels(t->plan[k], t->fp_neighbourhood, t->fp_threshold, din, dfl, st)) return -1;
-            din = dfl;
+    return lsn::guarded("lsnTickSetFlyingPixels", -1, [&]() {
+        lsn::clear_error();
+        if (!t) {
+            lsn::set_error("lsnTickSetFlyingPixels: null argument");
+            return -1;
         }
-        if (lsnFusionRadialCorrectTo(t->plan[k], t->intr.data(), din, cin, dco, cco, st)) return -1;
-        return lsnFusionRunMesh(t->plan[k], dco, cco, static_cast<unsigned char *>(d_vertices) + 16 * px * t0, d_offsets + nm * t0,
-                                static_cast<unsigned char *>(d_triangles) + 12 * (size_t)t->tri_cap * t0, d_tri_offsets + nm * t0, st);
-    };
-    if (t->parts == 1) return part(0, s);
-    // fork: the side stream starts where the caller's stream stands -- and only when the first half's band kernel is through (staggered): two
-    // halves that start together march in step (band beside band, closing beside closing) and gain nothing; half a stage apart, one half's
-    // closing rounds run beside the other half's band kernel, then beside its count / write / triangle passes.  join: the caller's stream
-    // continues behind both halves.
-    LSN_HIP(hipEventRecord(t->ev_fork, s));
-    LSN_HIP(hipStreamWaitEvent(t->side, t->ev_fork, 0));
-    t->plan[0]->after_band = t->ev_band;
-    const int rc_a = part(0, s);
-    t->plan[0]->after_band = nullptr;
-    char err_a[lsn::kErrorLen];
-    snprintf(err_a, sizeof(err_a), "%s", lsn::error_buffer());   // (every export clears the channel on entry: the second half's calls would wipe the first half's text)
-    (void)hipStreamWaitEvent(t->side, t->ev_band, 0);   // (a closing route without a band kernel records nothing new: no wait, the halves start together)
-    const int rc_b = part(1, t->side);
-    if (rc_a) lsn::set_error("%s", err_a);
-    // (the join is enqueued whatever happened: nothing of a failed half may still be running unobserved when the caller's stream goes on)
-    if (hipEventRecord(t->ev_join, t->side) == hipSuccess) (void)hipStreamWaitEvent(s, t->ev_join, 0);
-    else (void)hipGetLastError();
-    return rc_a || rc_b ? -1 : 0;
+        std::lock_guard<std::mutex> g(t->mu);
+        t->fp_neighbourhood = neighbourhood;
+        t->fp_threshold = threshold;
+        return 0;
+    });
 }
 
 extern "C" int lsnTickRun(LsnTick *t, const void *d_depth_in, const void *d_colors_in, void *d_depth_corr, void *d_colors_corr, void *d_vertices,
                           int *d_offsets, void *d_triangles, int *d_tri_offsets, void *stream)
 {
-    return lsn::guarded<int>("lsnTickRun", static_cast<int>(-1), [&]() {
-        return lsnTickRun_impl(t, d_depth_in, d_colors_in, d_depth_corr, d_colors_corr, d_vertices, d_offsets, d_triangles, d_tri_offsets, stream);
+    return lsn::guarded("lsnTickRun", -1, [&]() {
+        lsn::clear_error();
+        if (!t || !d_depth_in || !d_colors_in || !d_depth_corr || !d_colors_corr || !d_vertices || !d_offsets || !d_triangles || !d_tri_offsets) {
+            lsn::set_error("lsnTickRun: null argument");
+            return -1;
+        }
+        if (t->intr.empty()) {
+            lsn::set_error("lsnTickRun: lsnTickSetParams has not been called");
+            return -1;
+        }
+        std::lock_guard<std::mutex> g(t->mu);
+        LSN_HIP(hipSetDevice(t->device));
+        hipStream_t s = lsn::as_stream(stream);
+        const bool filter = t->fp_neighbourhood >= 1;
+        if (filter && t->d_filtered.reserve(2 * (size_t)t->cap * t->n_ticks + 16)) return -1;
+        // part k's slices of the caller's arrays: [tick][pixels], [tick][pixels][3], [tick][capacity] vertices, [tick][n_maps + 1], ...
+        auto part = [&](int k, hipStream_t st) -> int {
+            const size_t t0 = (size_t)t->first[k];
+            const size_t px = (size_t)t->cap, nm = (size_t)t->n_maps + 1;
+            const unsigned char *din = static_cast<const unsigned char *>(d_depth_in) + 2 * px * t0, *cin = static_cast<const unsigned char *>(d_colors_in) + 3 * px * t0;
+            unsigned char *dco = static_cast<unsigned char *>(d_depth_corr) + 2 * px * t0, *cco = static_cast<unsigned char *>(d_colors_corr) + 3 * px * t0;
+            if (filter) {   // filter -> correction: the filtered maps go through the tick's scratch, the caller's input stays as it is
+                unsigned char *dfl = t->d_filtered.as<unsigned char>() + 2 * px * t0;
+                // the scratch is shared by all runs of the tick object: a run on another stream than the previous one's waits until that
+                // run's correction has read it (the event radial.hip records behind every chain)
+                LsnFusion *pl = t->plan[k];
+                if (pl->radial_chain_open && pl->work_cnt_stream != st) LSN_HIP(hipStreamWaitEvent(st, pl->radial_done, 0));
+                if (lsn::flying_pixels(t->plan[k], t->fp_neighbourhood, t->fp_threshold, din, dfl, st)) return -1;
+                din = dfl;
+            }
+            if (lsnFusionRadialCorrectTo(t->plan[k], t->intr.data(), din, cin, dco, cco, st)) return -1;
+            return lsnFusionRunMesh(t->plan[k], dco, cco, static_cast<unsigned char *>(d_vertices) + 16 * px * t0, d_offsets + nm * t0,
+                                    static_cast<unsigned char *>(d_triangles) + 12 * (size_t)t->tri_cap * t0, d_tri_offsets + nm * t0, st);
+        };
+        if (t->parts == 1) return part(0, s);
+        // fork: the side stream starts where the caller's stream stands -- and only when the first half's band kernel is through (staggered): two
+        // halves that start together march in step (band beside band, closing beside closing) and gain nothing; half a stage apart, one half's
+        // closing rounds run beside the other half's band kernel, then beside its count / write / triangle passes.  join: the caller's stream
+        // continues behind both halves.
+        LSN_HIP(hipEventRecord(t->ev_fork, s));
+        LSN_HIP(hipStreamWaitEvent(t->side, t->ev_fork, 0));
+        t->plan[0]->after_band = t->ev_band;
+        const int rc_a = part(0, s);
+        t->plan[0]->after_band = nullptr;
+        char err_a[lsn::kErrorLen];
+        snprintf(err_a, sizeof(err_a), "%s", lsn::error_buffer());   // (every export clears the channel on entry: the second half's calls would wipe the first half's text)
+        (void)hipStreamWaitEvent(t->side, t->ev_band, 0);   // (a closing route without a band kernel records nothing new: no wait, the halves start together)
+        const int rc_b = part(1, t->side);
+        if (rc_a) lsn::set_error("%s", err_a);
+        // (the join is enqueued whatever happened: nothing of a failed half may still be running unobserved when the caller's stream goes on)
+        if (hipEventRecord(t->ev_join, t->side) == hipSuccess) (void)hipStreamWaitEvent(s, t->ev_join, 0);
+        else (void)hipGetLastError();
+        return rc_a || rc_b ? -1 : 0;
     });
 }

@@ -858,207 +858,191 @@ struct LsnTransfer {
 
 extern "C" {
 
-static LsnTransfer *lsnTransferCreate_impl(int device, int max_vertices, int max_triangles)
-{
-    lsn::clear_error();
-    if (max_vertices < 0 || max_triangles < 0) { lsn::set_error("lsnTransferCreate: negative capacity"); return nullptr; }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) {
-        lsn::set_error("lsnTransferCreate: no HIP device %d (this library has no CPU path)", device);
-        return nullptr;
-    }
-    LSN_HIP_NULL(hipSetDevice(device));
-    auto *t = new LsnTransfer;
-    t->device = device;
-    t->max_v = max_vertices;
-    t->max_t = max_triangles;
-    t->max_chunks = (int)(3ll * max_triangles / kChunkLimit + max_vertices / kChunkLimit + 2);
-    const size_t nv = (size_t)(max_vertices > 0 ? max_vertices : 1), nt3 = (size_t)(max_triangles > 0 ? 3ll * max_triangles : 1);
-    if (t->tag.reserve(nv * 8) || t->lidx.reserve(nv * 4) || t->new_v.reserve(nt3 * 16) || t->new_tri.reserve(nt3 * 4) ||
-        t->bsum.reserve(kWindowBlocks * 4) || t->boff.reserve(kWindowBlocks * 4) || t->v_chunks.reserve((size_t)t->max_chunks * 4) ||
-        t->t_chunks.reserve((size_t)t->max_chunks * 4) || t->state.reserve(sizeof(ChunkState)) ||
-        t->l_cnt.reserve(nv * 4) || t->l_uses.reserve(nv * 4 * kMaxUses) || t->l_prev.reserve(nt3 * 4 + 32) || t->l_pack.reserve((nt3 / 3 + 8) * 8) ||
-        t->l_totals.reserve((nt3 / kScanPerBlock + 2) * 8) || t->l_rank.reserve(nt3 * 4 + 32) || t->l_start.reserve(((size_t)t->max_chunks + 1) * 4) ||
-        t->l_vbase.reserve(((size_t)t->max_chunks + 1) * 4) || t->l_state.reserve(sizeof(LinkState))) {
-        delete t;
-        return nullptr;
-    }
-    if (hipHostMalloc(reinterpret_cast<void **>(&t->h_link), sizeof(LinkState), hipHostMallocDefault) != hipSuccess) {
-        lsn::set_error("lsnTransferCreate: hipHostMalloc failed");
-        delete t;
-        return nullptr;
-    }
-    if (hipHostMalloc(reinterpret_cast<void **>(&t->h_state), sizeof(ChunkState), hipHostMallocDefault) != hipSuccess) {
-        lsn::set_error("lsnTransferCreate: hipHostMalloc failed");
-        delete t;
-        return nullptr;
-    }
-    return t;
-}
-
 LsnTransfer *lsnTransferCreate(int device, int max_vertices, int max_triangles)
 {
-    return lsn::guarded<LsnTransfer *>("lsnTransferCreate", static_cast<LsnTransfer *>(nullptr), [&]() { return lsnTransferCreate_impl(device, max_vertices, max_triangles); });
-}
-
-static void lsnTransferDestroy_impl(LsnTransfer *t)
-{
-    if (!t) return;
-    (void)hipSetDevice(t->device);
-    delete t;
+    return lsn::guarded("lsnTransferCreate", static_cast<LsnTransfer *>(nullptr), [&]() -> LsnTransfer * {
+        lsn::clear_error();
+        if (max_vertices < 0 || max_triangles < 0) { lsn::set_error("lsnTransferCreate: negative capacity"); return nullptr; }
+        int ndev = 0;
+        if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) {
+            lsn::set_error("lsnTransferCreate: no HIP device %d (this library has no CPU path)", device);
+            return nullptr;
+        }
+        LSN_HIP_NULL(hipSetDevice(device));
+        auto *t = new LsnTransfer;
+        t->device = device;
+        t->max_v = max_vertices;
+        t->max_t = max_triangles;
+        t->max_chunks = (int)(3ll * max_triangles / kChunkLimit + max_vertices / kChunkLimit + 2);
+        const size_t nv = (size_t)(max_vertices > 0 ? max_vertices : 1), nt3 = (size_t)(max_triangles > 0 ? 3ll * max_triangles : 1);
+        if (t->tag.reserve(nv * 8) || t->lidx.reserve(nv * 4) || t->new_v.reserve(nt3 * 16) || t->new_tri.reserve(nt3 * 4) ||
+            t->bsum.reserve(kWindowBlocks * 4) || t->boff.reserve(kWindowBlocks * 4) || t->v_chunks.reserve((size_t)t->max_chunks * 4) ||
+            t->t_chunks.reserve((size_t)t->max_chunks * 4) || t->state.reserve(sizeof(ChunkState)) ||
+            t->l_cnt.reserve(nv * 4) || t->l_uses.reserve(nv * 4 * kMaxUses) || t->l_prev.reserve(nt3 * 4 + 32) || t->l_pack.reserve((nt3 / 3 + 8) * 8) ||
+            t->l_totals.reserve((nt3 / kScanPerBlock + 2) * 8) || t->l_rank.reserve(nt3 * 4 + 32) || t->l_start.reserve(((size_t)t->max_chunks + 1) * 4) ||
+            t->l_vbase.reserve(((size_t)t->max_chunks + 1) * 4) || t->l_state.reserve(sizeof(LinkState))) {
+            delete t;
+            return nullptr;
+        }
+        if (hipHostMalloc(reinterpret_cast<void **>(&t->h_link), sizeof(LinkState), hipHostMallocDefault) != hipSuccess) {
+            lsn::set_error("lsnTransferCreate: hipHostMalloc failed");
+            delete t;
+            return nullptr;
+        }
+        if (hipHostMalloc(reinterpret_cast<void **>(&t->h_state), sizeof(ChunkState), hipHostMallocDefault) != hipSuccess) {
+            lsn::set_error("lsnTransferCreate: hipHostMalloc failed");
+            delete t;
+            return nullptr;
+        }
+        return t;
+    });
 }
 
 void lsnTransferDestroy(LsnTransfer *t)
 {
-    lsn::guarded_void("lsnTransferDestroy", [&]() { lsnTransferDestroy_impl(t); });
-}
-
-static int lsnTransferLastPath_impl(LsnTransfer *t)
-{
-    if (!t) return -1;
-    std::lock_guard<std::mutex> guard(t->mu);
-    return t->last_path;
+    lsn::guarded_void("lsnTransferDestroy", [&]() {
+        if (!t) return;
+        (void)hipSetDevice(t->device);
+        delete t;
+    });
 }
 
 int lsnTransferLastPath(LsnTransfer *t)
 {
-    return lsn::guarded<int>("lsnTransferLastPath", static_cast<int>(-1), [&]() { return lsnTransferLastPath_impl(t); });
-}
-
-static long long lsnTransferFrameBound_impl(int n_vertices, int n_triangles)
-{
-    const long long nt = n_triangles > 0 ? n_triangles : 0, nv = n_vertices > 0 ? n_vertices : 0;
-    const long long send = nt > 0 ? 3 * nt : nv;
-    const long long chunks = 3 * nt / kChunkLimit + nv / kChunkLimit + 2;
-    return 12 + 8 * chunks + 15 * send + 12 * nt;
+    return lsn::guarded("lsnTransferLastPath", -1, [&]() {
+        if (!t) return -1;
+        std::lock_guard<std::mutex> guard(t->mu);
+        return t->last_path;
+    });
 }
 
 long long lsnTransferFrameBound(int n_vertices, int n_triangles)
 {
-    return lsn::guarded<long long>("lsnTransferFrameBound", static_cast<long long>(-1), [&]() { return lsnTransferFrameBound_impl(n_vertices, n_triangles); });
-}
-
-static long long lsnTransferPack_impl(LsnTransfer *t, const void *d_vertices, int n_vertices, const int *d_triangles, int n_triangles,
-                          void *d_out, long long out_cap, void *stream)
-{
-    lsn::clear_error();
-    if (!t) { lsn::set_error("lsnTransferPack: null handle"); return -1; }
-    if (n_vertices < 0 || n_triangles < 0 || n_vertices > t->max_v || n_triangles > t->max_t) {
-        lsn::set_error("lsnTransferPack: %d vertices / %d triangles exceed the handle's capacity (%d / %d)", n_vertices, n_triangles, t->max_v, t->max_t);
-        return -1;
-    }
-    if ((n_vertices && !d_vertices) || (n_triangles && !d_triangles) || !d_out) { lsn::set_error("lsnTransferPack: null buffer"); return -1; }
-    if (n_triangles > 0 && n_vertices == 0) { lsn::set_error("lsnTransferPack: triangles without vertices"); return -1; }
-    std::lock_guard<std::mutex> guard(t->mu);
-    LSN_HIP(hipSetDevice(t->device));
-    hipStream_t s = lsn::as_stream(stream);
-    const uint4 *src_v = static_cast<const uint4 *>(d_vertices);
-    const int *src_t = d_triangles;
-    int n_send = n_vertices, n_chunks = 0, host_chunks = 1;
-    bool linked = false;
-    if (n_triangles > 0 && 3ll * n_triangles / kChunkLimit + 2 <= kLinkChunksLds &&
-        (n_triangles + kScanPerBlock - 1) / kScanPerBlock <= kLinkTotalsLds && t->max_chunks <= kLinkChunksLds) {
-        const int n_pos = 3 * n_triangles;
-        LinkState *st = t->l_state.as<LinkState>();
-        int *cnt = t->l_cnt.as<int>(), *rank = t->l_rank.as<int>();
-        unsigned *prev = t->l_prev.as<unsigned>();
-        auto *pack = t->l_pack.as<unsigned long long>();
-        auto *totals64 = t->l_totals.as<unsigned long long>();
-        int *totals32 = t->l_totals.as<int>();
-        LSN_HIP(hipMemsetAsync(st, 0, sizeof(LinkState), s));
-        LSN_HIP(hipMemsetAsync(cnt, 0, (size_t)n_vertices * 4, s));
-        link_uses_kernel<<<(n_pos + kUsesThreads * kUsesPer - 1) / (kUsesThreads * kUsesPer), kUsesThreads, 0, s>>>(src_t, n_pos, n_vertices, cnt,
-                                                                                                                 t->l_uses.as<int>(), st);
-        link_prev_kernel<<<(n_vertices + 255) / 256, 256, 0, s>>>(cnt, t->l_uses.as<int>(), n_vertices, prev, st);
-        link_pack_kernel<<<(n_triangles + 255) / 256, 256, 0, s>>>(prev, n_triangles, pack, st);
-        const int pb = (n_triangles + kScanPerBlock - 1) / kScanPerBlock;
-        scan_totals_kernel<unsigned long long><<<pb, 256, 0, s>>>(pack, n_triangles, totals64);
-        scan_top_kernel<unsigned long long><<<1, 1024, 0, s>>>(totals64, pb);
-        scan_apply_kernel<unsigned long long><<<pb, 256, 0, s>>>(pack, n_triangles, totals64);
-        link_chunks_kernel<<<1, 64, 0, s>>>(pack, totals64, n_triangles, t->max_chunks, t->l_start.as<int>(), t->l_vbase.as<int>(),
-                                            t->v_chunks.as<int>(), t->t_chunks.as<int>(), st);
-        const int rb = (n_pos + kScanPerBlock - 1) / kScanPerBlock;
-        rank_totals_kernel<<<rb, 256, 0, s>>>(prev, n_pos, t->l_start.as<int>(), st, totals32);
-        scan_top_kernel<int><<<1, 1024, 0, s>>>(totals32, rb);
-        rank_apply_kernel<<<rb, 256, 0, s>>>(prev, n_pos, t->l_start.as<int>(), st, totals32, rank);
-        link_emit_kernel<<<(n_pos + 255) / 256, 256, 0, s>>>(src_t, prev, n_pos, src_v, t->l_start.as<int>(), t->l_vbase.as<int>(), st, rank,
-                                                             t->new_v.as<uint4>(), t->new_tri.as<int>());
-        LSN_HIP(hipGetLastError());
-        LSN_HIP(hipMemcpyAsync(t->h_link, st, sizeof(LinkState), hipMemcpyDeviceToHost, s));
-        LSN_HIP(hipStreamSynchronize(s));
-        if (t->h_link->bad) {
-            lsn::set_error("lsnTransferPack: a triangle index lies outside [0, %d)", n_vertices);
-            return -1;
-        }
-        if (!t->h_link->fallback) {
-            linked = true;
-            host_chunks = 0;
-            n_send = t->h_link->n_send;
-            n_chunks = t->h_link->n_chunks;
-            src_v = t->new_v.as<uint4>();
-            src_t = t->new_tri.as<int>();
-            t->last_path = 1;
-        }
-    }
-    if (linked) {
-    } else if (n_triangles > 0) {
-        t->last_path = 2;
-        host_chunks = 0;
-        ChunkState init{};
-        init.p_first = init.p_last = -1;
-        *t->h_state = init;
-        LSN_HIP(hipMemcpyAsync(t->state.p, t->h_state, sizeof(ChunkState), hipMemcpyHostToDevice, s));
-        LSN_HIP(hipMemsetAsync(t->tag.p, 0xff, (size_t)n_vertices * 8, s));
-        ChunkState *st = t->state.as<ChunkState>();
-        auto *tag = t->tag.as<unsigned long long>();
-        const long long max_iter = n_triangles / kWindowTri + 3ll * n_triangles / kChunkLimit + 4;
-        long long it = 0;
-        bool done = false;
-        while (!done) {
-            for (int r = 0; r < 4; r++, it++) {
-                chunk_tag_kernel<<<kWindowBlocks, kTriPerBlock, 0, s>>>(st, src_t, n_triangles, n_vertices, tag, t->lidx.as<int>(), t->new_tri.as<int>());
-                chunk_count_kernel<<<kWindowBlocks, kTriPerBlock, 0, s>>>(st, src_t, n_triangles, n_vertices, tag, t->bsum.as<int>(), t->boff.as<int>());
-                chunk_emit_kernel<<<kWindowBlocks, kTriPerBlock, 0, s>>>(st, src_t, n_triangles, n_vertices, src_v, tag, t->boff.as<int>(),
-                                                                         t->lidx.as<int>(), t->new_v.as<uint4>(), t->v_chunks.as<int>(), t->t_chunks.as<int>());
-            }
-            LSN_HIP(hipMemcpyAsync(t->h_state, t->state.p, sizeof(ChunkState), hipMemcpyDeviceToHost, s));
-            LSN_HIP(hipStreamSynchronize(s));
-            done = t->h_state->done != 0;
-            if (!done && it > max_iter) { lsn::set_error("lsnTransferPack: chunk search did not terminate"); return -1; }
-        }
-        // the new indices of the last window (idempotent when a pass after the last emit already wrote them)
-        chunk_tag_kernel<<<kWindowBlocks, kTriPerBlock, 0, s>>>(st, src_t, n_triangles, n_vertices, tag, t->lidx.as<int>(), t->new_tri.as<int>());
-        if (t->h_state->bad) {
-            (void)hipStreamSynchronize(s);
-            lsn::set_error("lsnTransferPack: a triangle index lies outside [0, %d)", n_vertices);
-            return -1;
-        }
-        n_send = t->h_state->vbase;
-        n_chunks = t->h_state->c;
-        src_v = t->new_v.as<uint4>();
-        src_t = t->new_tri.as<int>();
-    } else {
-        t->last_path = 0;
-        n_chunks = (n_vertices + kChunkLimit - 1) / kChunkLimit;          // formVerticesChunks (:177-201)
-    }
-    const long long need = 12 + 8ll * n_chunks + 15ll * n_send + 12ll * n_triangles;
-    if (need > out_cap) { lsn::set_error("lsnTransferPack: the stream needs %lld bytes, the buffer holds %lld", need, out_cap); return -1; }
-    if (((size_t)d_out & 3) != 0) { lsn::set_error("lsnTransferPack: d_out must be 4-byte aligned"); return -1; }
-    const int xb = (n_send + kItemsPerBlock - 1) / kItemsPerBlock, cb = xb;
-    const int tb = (int)((3ll * n_triangles + kItemsPerBlock * 3 - 1) / (kItemsPerBlock * 3));
-    transfer_assemble_kernel<<<xb + cb + tb + 1, 256, 0, s>>>(src_v, n_send, src_t, n_triangles, n_chunks, t->v_chunks.as<int>(), t->t_chunks.as<int>(),
-                                                               host_chunks, static_cast<unsigned char *>(d_out), xb, cb, tb);
-    LSN_HIP(hipGetLastError());
-    LSN_HIP(hipStreamSynchronize(s));
-    t->last_chunks = n_chunks;
-    t->last_send = n_send;
-    return need;
+    return lsn::guarded("lsnTransferFrameBound", -1LL, [&]() -> long long {
+        const long long nt = n_triangles > 0 ? n_triangles : 0, nv = n_vertices > 0 ? n_vertices : 0;
+        const long long send = nt > 0 ? 3 * nt : nv;
+        const long long chunks = 3 * nt / kChunkLimit + nv / kChunkLimit + 2;
+        return 12 + 8 * chunks + 15 * send + 12 * nt;
+    });
 }
 
 long long lsnTransferPack(LsnTransfer *t, const void *d_vertices, int n_vertices, const int *d_triangles, int n_triangles,
                           void *d_out, long long out_cap, void *stream)
 {
-    return lsn::guarded<long long>("lsnTransferPack", static_cast<long long>(-1), [&]() { return lsnTransferPack_impl(t, d_vertices, n_vertices, d_triangles, n_triangles, d_out, out_cap, stream); });
+    return lsn::guarded("lsnTransferPack", -1LL, [&]() -> long long {
+        lsn::clear_error();
+        if (!t) { lsn::set_error("lsnTransferPack: null handle"); return -1; }
+        if (n_vertices < 0 || n_triangles < 0 || n_vertices > t->max_v || n_triangles > t->max_t) {
+            lsn::set_error("lsnTransferPack: %d vertices / %d triangles exceed the handle's capacity (%d / %d)", n_vertices, n_triangles, t->max_v, t->max_t);
+            return -1;
+        }
+        if ((n_vertices && !d_vertices) || (n_triangles && !d_triangles) || !d_out) { lsn::set_error("lsnTransferPack: null buffer"); return -1; }
+        if (n_triangles > 0 && n_vertices == 0) { lsn::set_error("lsnTransferPack: triangles without vertices"); return -1; }
+        std::lock_guard<std::mutex> guard(t->mu);
+        LSN_HIP(hipSetDevice(t->device));
+        hipStream_t s = lsn::as_stream(stream);
+        const uint4 *src_v = static_cast<const uint4 *>(d_vertices);
+        const int *src_t = d_triangles;
+        int n_send = n_vertices, n_chunks = 0, host_chunks = 1;
+        bool linked = false;
+        if (n_triangles > 0 && 3ll * n_triangles / kChunkLimit + 2 <= kLinkChunksLds &&
+            (n_triangles + kScanPerBlock - 1) / kScanPerBlock <= kLinkTotalsLds && t->max_chunks <= kLinkChunksLds) {
+            const int n_pos = 3 * n_triangles;
+            LinkState *st = t->l_state.as<LinkState>();
+            int *cnt = t->l_cnt.as<int>(), *rank = t->l_rank.as<int>();
+            unsigned *prev = t->l_prev.as<unsigned>();
+            auto *pack = t->l_pack.as<unsigned long long>();
+            auto *totals64 = t->l_totals.as<unsigned long long>();
+            int *totals32 = t->l_totals.as<int>();
+            LSN_HIP(hipMemsetAsync(st, 0, sizeof(LinkState), s));
+            LSN_HIP(hipMemsetAsync(cnt, 0, (size_t)n_vertices * 4, s));
+            link_uses_kernel<<<(n_pos + kUsesThreads * kUsesPer - 1) / (kUsesThreads * kUsesPer), kUsesThreads, 0, s>>>(src_t, n_pos, n_vertices, cnt,
+                                                                                                                     t->l_uses.as<int>(), st);
+            link_prev_kernel<<<(n_vertices + 255) / 256, 256, 0, s>>>(cnt, t->l_uses.as<int>(), n_vertices, prev, st);
+            link_pack_kernel<<<(n_triangles + 255) / 256, 256, 0, s>>>(prev, n_triangles, pack, st);
+            const int pb = (n_triangles + kScanPerBlock - 1) / kScanPerBlock;
+            scan_totals_kernel<unsigned long long><<<pb, 256, 0, s>>>(pack, n_triangles, totals64);
+            scan_top_kernel<unsigned long long><<<1, 1024, 0, s>>>(totals64, pb);
+            scan_apply_kernel<unsigned long long><<<pb, 256, 0, s>>>(pack, n_triangles, totals64);
+            link_chunks_kernel<<<1, 64, 0, s>>>(pack, totals64, n_triangles, t->max_chunks, t->l_start.as<int>(), t->l_vbase.as<int>(),
+                                                t->v_chunks.as<int>(), t->t_chunks.as<int>(), st);
+            const int rb = (n_pos + kScanPerBlock - 1) / kScanPerBlock;
+            rank_totals_kernel<<<rb, 256, 0, s>>>(prev, n_pos, t->l_start.as<int>(), st, totals32);
+            scan_top_kernel<int><<<1, 1024, 0, s>>>(totals32, rb);
+            rank_apply_kernel<<<rb, 256, 0, s>>>(prev, n_pos, t->l_start.as<int>(), st, totals32, rank);
+            link_emit_kernel<<<(n_pos + 255) / 256, 256, 0, s>>>(src_t, prev, n_pos, src_v, t->l_start.as<int>(), t->l_vbase.as<int>(), st, rank,
+                                                                 t->new_v.as<uint4>(), t->new_tri.as<int>());
+            LSN_HIP(hipGetLastError());
+            LSN_HIP(hipMemcpyAsync(t->h_link, st, sizeof(LinkState), hipMemcpyDeviceToHost, s));
+            LSN_HIP(hipStreamSynchronize(s));
+            if (t->h_link->bad) {
+                lsn::set_error("lsnTransferPack: a triangle index lies outside [0, %d)", n_vertices);
+                return -1;
+            }
+            if (!t->h_link->fallback) {
+                linked = true;
+                host_chunks = 0;
+                n_send = t->h_link->n_send;
+                n_chunks = t->h_link->n_chunks;
+                src_v = t->new_v.as<uint4>();
+                src_t = t->new_tri.as<int>();
+                t->last_path = 1;
+            }
+        }
+        if (linked) {
+        } else if (n_triangles > 0) {
+            t->last_path = 2;
+            host_chunks = 0;
+            ChunkState init{};
+            init.p_first = init.p_last = -1;
+            *t->h_state = init;
+            LSN_HIP(hipMemcpyAsync(t->state.p, t->h_state, sizeof(ChunkState), hipMemcpyHostToDevice, s));
+            LSN_HIP(hipMemsetAsync(t->tag.p, 0xff, (size_t)n_vertices * 8, s));
+            ChunkState *st = t->state.as<ChunkState>();
+            auto *tag = t->tag.as<unsigned long long>();
+            const long long max_iter = n_triangles / kWindowTri + 3ll * n_triangles / kChunkLimit + 4;
+            long long it = 0;
+            bool done = false;
+            while (!done) {
+                for (int r = 0; r < 4; r++, it++) {
+                    chunk_tag_kernel<<<kWindowBlocks, kTriPerBlock, 0, s>>>(st, src_t, n_triangles, n_vertices, tag, t->lidx.as<int>(), t->new_tri.as<int>());
+                    chunk_count_kernel<<<kWindowBlocks, kTriPerBlock, 0, s>>>(st, src_t, n_triangles, n_vertices, tag, t->bsum.as<int>(), t->boff.as<int>());
+                    chunk_emit_kernel<<<kWindowBlocks, kTriPerBlock, 0, s>>>(st, src_t, n_triangles, n_vertices, src_v, tag, t->boff.as<int>(),
+                                                                             t->lidx.as<int>(), t->new_v.as<uint4>(), t->v_chunks.as<int>(), t->t_chunks.as<int>());
+                }
+                LSN_HIP(hipMemcpyAsync(t->h_state, t->state.p, sizeof(ChunkState), hipMemcpyDeviceToHost, s));
+                LSN_HIP(hipStreamSynchronize(s));
+                done = t->h_state->done != 0;
+                if (!done && it > max_iter) { lsn::set_error("lsnTransferPack: chunk search did not terminate"); return -1; }
+            }
+            // the new indices of the last window (idempotent when a pass after the last emit already wrote them)
+            chunk_tag_kernel<<<kWindowBlocks, kTriPerBlock, 0, s>>>(st, src_t, n_triangles, n_vertices, tag, t->lidx.as<int>(), t->new_tri.as<int>());
+            if (t->h_state->bad) {
+                (void)hipStreamSynchronize(s);
+                lsn::set_error("lsnTransferPack: a triangle index lies outside [0, %d)", n_vertices);
+                return -1;
+            }
+            n_send = t->h_state->vbase;
+            n_chunks = t->h_state->c;
+            src_v = t->new_v.as<uint4>();
+            src_t = t->new_tri.as<int>();
+        } else {
+            t->last_path = 0;
+            n_chunks = (n_vertices + kChunkLimit - 1) / kChunkLimit;          // formVerticesChunks (:177-201)
+        }
+        const long long need = 12 + 8ll * n_chunks + 15ll * n_send + 12ll * n_triangles;
+        if (need > out_cap) { lsn::set_error("lsnTransferPack: the stream needs %lld bytes, the buffer holds %lld", need, out_cap); return -1; }
+        if (((size_t)d_out & 3) != 0) { lsn::set_error("lsnTransferPack: d_out must be 4-byte aligned"); return -1; }
+        const int xb = (n_send + kItemsPerBlock - 1) / kItemsPerBlock, cb = xb;
+        const int tb = (int)((3ll * n_triangles + kItemsPerBlock * 3 - 1) / (kItemsPerBlock * 3));
+        transfer_assemble_kernel<<<xb + cb + tb + 1, 256, 0, s>>>(src_v, n_send, src_t, n_triangles, n_chunks, t->v_chunks.as<int>(), t->t_chunks.as<int>(),
+                                                                   host_chunks, static_cast<unsigned char *>(d_out), xb, cb, tb);
+        LSN_HIP(hipGetLastError());
+        LSN_HIP(hipStreamSynchronize(s));
+        t->last_chunks = n_chunks;
+        t->last_send = n_send;
+        return need;
+    });
 }
 
 static int ply_header(PlyHeader *h, int nV, int nT)
@@ -1073,44 +1057,37 @@ static int ply_header(PlyHeader *h, int nV, int nT)
     return h->len > 0 && h->len < (int)sizeof h->text ? 0 : -1;
 }
 
-static long long lsnPlyBinaryBytes_impl(int n_vertices, int n_triangles)
-{
-    PlyHeader h;
-    if (n_vertices < 0 || n_triangles < 0 || ply_header(&h, n_vertices, n_triangles)) return -1;
-    return h.len + 15ll * n_vertices + 13ll * n_triangles;
-}
-
 long long lsnPlyBinaryBytes(int n_vertices, int n_triangles)
 {
-    return lsn::guarded<long long>("lsnPlyBinaryBytes", static_cast<long long>(-1), [&]() { return lsnPlyBinaryBytes_impl(n_vertices, n_triangles); });
-}
-
-static long long lsnPlyPack_impl(int device, const void *d_vertices, int n_vertices, const int *d_triangles, int n_triangles, void *d_out,
-                     long long out_cap, void *stream)
-{
-    lsn::clear_error();
-    PlyHeader h;
-    if (n_vertices < 0 || n_triangles < 0 || ply_header(&h, n_vertices, n_triangles)) { lsn::set_error("lsnPlyPack: bad counts"); return -1; }
-    if ((n_vertices && !d_vertices) || (n_triangles && !d_triangles) || !d_out) { lsn::set_error("lsnPlyPack: null buffer"); return -1; }
-    const long long need = h.len + 15ll * n_vertices + 13ll * n_triangles;
-    if (need > out_cap) { lsn::set_error("lsnPlyPack: the file needs %lld bytes, the buffer holds %lld", need, out_cap); return -1; }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) {
-        lsn::set_error("lsnPlyPack: no HIP device %d (this library has no CPU path)", device);
-        return -1;
-    }
-    LSN_HIP(hipSetDevice(device));
-    const int vb = (n_vertices + kItemsPerBlock - 1) / kItemsPerBlock, fb = (n_triangles + kItemsPerBlock - 1) / kItemsPerBlock;
-    ply_pack_kernel<<<vb + fb + 1, 256, 0, lsn::as_stream(stream)>>>(static_cast<const uint4 *>(d_vertices), n_vertices, d_triangles, n_triangles,
-                                                                     static_cast<unsigned char *>(d_out), h, vb, fb);
-    LSN_HIP(hipGetLastError());
-    return need;
+    return lsn::guarded("lsnPlyBinaryBytes", -1LL, [&]() -> long long {
+        PlyHeader h;
+        if (n_vertices < 0 || n_triangles < 0 || ply_header(&h, n_vertices, n_triangles)) return -1;
+        return h.len + 15ll * n_vertices + 13ll * n_triangles;
+    });
 }
 
 long long lsnPlyPack(int device, const void *d_vertices, int n_vertices, const int *d_triangles, int n_triangles, void *d_out,
                      long long out_cap, void *stream)
 {
-    return lsn::guarded<long long>("lsnPlyPack", static_cast<long long>(-1), [&]() { return lsnPlyPack_impl(device, d_vertices, n_vertices, d_triangles, n_triangles, d_out, out_cap, stream); });
+    return lsn::guarded("lsnPlyPack", -1LL, [&]() -> long long {
+        lsn::clear_error();
+        PlyHeader h;
+        if (n_vertices < 0 || n_triangles < 0 || ply_header(&h, n_vertices, n_triangles)) { lsn::set_error("lsnPlyPack: bad counts"); return -1; }
+        if ((n_vertices && !d_vertices) || (n_triangles && !d_triangles) || !d_out) { lsn::set_error("lsnPlyPack: null buffer"); return -1; }
+        const long long need = h.len + 15ll * n_vertices + 13ll * n_triangles;
+        if (need > out_cap) { lsn::set_error("lsnPlyPack: the file needs %lld bytes, the buffer holds %lld", need, out_cap); return -1; }
+        int ndev = 0;
+        if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) {
+            lsn::set_error("lsnPlyPack: no HIP device %d (this library has no CPU path)", device);
+            return -1;
+        }
+        LSN_HIP(hipSetDevice(device));
+        const int vb = (n_vertices + kItemsPerBlock - 1) / kItemsPerBlock, fb = (n_triangles + kItemsPerBlock - 1) / kItemsPerBlock;
+        ply_pack_kernel<<<vb + fb + 1, 256, 0, lsn::as_stream(stream)>>>(static_cast<const uint4 *>(d_vertices), n_vertices, d_triangles, n_triangles,
+                                                                         static_cast<unsigned char *>(d_out), h, vb, fb);
+        LSN_HIP(hipGetLastError());
+        return need;
+    });
 }
 
 }  // extern "C"
@@ -1177,131 +1154,116 @@ extern "C" {
 
 int lsnZstdAvailable(void) { return zstd().ok ? 1 : 0; }
 
-static int lsnFrameParseHeader_impl(const unsigned char *header16, LsnFrameInfo *info)
-{
-    lsn::clear_error();
-    if (!header16 || !info) { lsn::set_error("lsnFrameParseHeader: null argument"); return -1; }
-    info->payload_bytes = rd_i32(header16);                     // KinectSocket.cs:229
-    info->compressed = rd_i32(header16 + 4);                    // :237
-    info->width = rd_i32(header16 + 8);                         // :238
-    info->height = rd_i32(header16 + 12);                       // :239
-    if (info->payload_bytes <= 0) return 1;                     // :231-235: "no more stored frames"
-    if (info->width < 0 || info->height < 0 || (long long)info->width * info->height > (1ll << 26)) {
-        lsn::set_error("lsnFrameParseHeader: implausible frame size %d x %d", info->width, info->height);
-        return -1;
-    }
-    return 0;
-}
-
 int lsnFrameParseHeader(const unsigned char *header16, LsnFrameInfo *info)
 {
-    return lsn::guarded<int>("lsnFrameParseHeader", static_cast<int>(-1), [&]() { return lsnFrameParseHeader_impl(header16, info); });
-}
-
-static long long lsnFrameDecode_impl(const unsigned char *payload, int payload_bytes, int compressed, int width, int height,
-                         unsigned char *depth_out, unsigned char *rgb_out, unsigned char *bodies_out, int bodies_cap,
-                         int *n_bodies)
-{
-    lsn::clear_error();
-    if (!payload || payload_bytes <= 0 || width < 0 || height < 0) { lsn::set_error("lsnFrameDecode: bad arguments"); return -1; }
-    const long long P = (long long)width * height;
-    const unsigned char *raw = payload;
-    long long raw_len = payload_bytes;
-    std::vector<unsigned char> tmp;
-    if (compressed == 1) {                                      // KinectSocket.cs:247-248
-        Zstd &z = zstd();
-        if (!z.ok) { lsn::set_error("lsnFrameDecode: compressed frame but libzstd.so.1 could not be loaded"); return -1; }
-        const unsigned long long out = z.decompressed_size(payload, (size_t)payload_bytes);     // ZSTDDecompressor.cs:28
-        // a frame is w*h*5 bytes plus a few KB of body joints: anything else is a corrupted length field, not worth allocating
-        if (out < (unsigned long long)(5 * P + 4) || out > (unsigned long long)(5 * P) + (1ull << 20)) {
-            lsn::set_error("lsnFrameDecode: the zstd frame announces %llu bytes, a %d x %d frame has %lld + bodies", out, width, height, 5 * P);
+    return lsn::guarded("lsnFrameParseHeader", -1, [&]() {
+        lsn::clear_error();
+        if (!header16 || !info) { lsn::set_error("lsnFrameParseHeader: null argument"); return -1; }
+        info->payload_bytes = rd_i32(header16);                     // KinectSocket.cs:229
+        info->compressed = rd_i32(header16 + 4);                    // :237
+        info->width = rd_i32(header16 + 8);                         // :238
+        info->height = rd_i32(header16 + 12);                       // :239
+        if (info->payload_bytes <= 0) return 1;                     // :231-235: "no more stored frames"
+        if (info->width < 0 || info->height < 0 || (long long)info->width * info->height > (1ll << 26)) {
+            lsn::set_error("lsnFrameParseHeader: implausible frame size %d x %d", info->width, info->height);
             return -1;
         }
-        tmp.resize((size_t)out);
-        const size_t got = z.decompress(tmp.data(), tmp.size(), payload, (size_t)payload_bytes);
-        if (z.is_error(got) || got != out) { lsn::set_error("lsnFrameDecode: zstd decompression failed"); return -1; }
-        raw = tmp.data();
-        raw_len = (long long)out;
-    }
-    if (raw_len < 5 * P + 4) { lsn::set_error("lsnFrameDecode: payload of %lld bytes is shorter than %d x %d x 5 + 4", raw_len, width, height); return -1; }
-    int nb = 0;
-    const long long bl = body_block_length(raw + 5 * P, raw_len - 5 * P, &nb);
-    if (bl < 0) { lsn::set_error("lsnFrameDecode: inconsistent body block"); return -1; }
-    if (depth_out) memcpy(depth_out, raw, (size_t)(2 * P));                              // KinectSocket.cs:256
-    if (rgb_out) memcpy(rgb_out, raw + 2 * P, (size_t)(3 * P));                          // :257
-    if (bodies_out) {
-        if (bl > bodies_cap) { lsn::set_error("lsnFrameDecode: body block of %lld bytes exceeds the buffer (%d)", bl, bodies_cap); return -1; }
-        memcpy(bodies_out, raw + 5 * P, (size_t)bl);
-    }
-    if (n_bodies) *n_bodies = nb;
-    return bl;
+        return 0;
+    });
 }
 
 long long lsnFrameDecode(const unsigned char *payload, int payload_bytes, int compressed, int width, int height,
                          unsigned char *depth_out, unsigned char *rgb_out, unsigned char *bodies_out, int bodies_cap,
                          int *n_bodies)
 {
-    return lsn::guarded<long long>("lsnFrameDecode", static_cast<long long>(-1), [&]() { return lsnFrameDecode_impl(payload, payload_bytes, compressed, width, height, depth_out, rgb_out, bodies_out, bodies_cap, n_bodies); });
-}
-
-static long long lsnFrameEncode_impl(const unsigned char *depth, const unsigned char *rgb, int width, int height, const unsigned char *bodies,
-                         int bodies_bytes, int compression_level, unsigned char *out, long long out_cap)
-{
-    lsn::clear_error();
-    if (!depth || !rgb || !out || width < 0 || height < 0) { lsn::set_error("lsnFrameEncode: bad arguments"); return -1; }
-    static const unsigned char no_bodies[4] = {0, 0, 0, 0};
-    if (!bodies || bodies_bytes < 4) { bodies = no_bodies; bodies_bytes = 4; }
-    const long long P = (long long)width * height, size = 5 * P + bodies_bytes;
-    if (size > 0x7fffffffll) { lsn::set_error("lsnFrameEncode: frame too large"); return -1; }
-    int isize = (int)size, comp = compression_level > 0 ? 1 : 0;
-    if (!comp) {
-        if (16 + size > out_cap) { lsn::set_error("lsnFrameEncode: needs %lld bytes", 16 + size); return -1; }
-        memcpy(out + 16, depth, (size_t)(2 * P));
-        memcpy(out + 16 + 2 * P, rgb, (size_t)(3 * P));
-        memcpy(out + 16 + 5 * P, bodies, (size_t)bodies_bytes);
-    } else {                                                    // liveScanClient.cpp:270-281
-        Zstd &z = zstd();
-        if (!z.ok) { lsn::set_error("lsnFrameEncode: compression requested but libzstd.so.1 could not be loaded"); return -1; }
-        std::vector<unsigned char> raw((size_t)size);
-        memcpy(raw.data(), depth, (size_t)(2 * P));
-        memcpy(raw.data() + 2 * P, rgb, (size_t)(3 * P));
-        memcpy(raw.data() + 5 * P, bodies, (size_t)bodies_bytes);
-        std::vector<unsigned char> packed(z.bound((size_t)size));
-        const size_t c = z.compress(packed.data(), packed.size(), raw.data(), raw.size(), compression_level);
-        if (z.is_error(c)) { lsn::set_error("lsnFrameEncode: zstd compression failed"); return -1; }
-        if (16 + (long long)c > out_cap) { lsn::set_error("lsnFrameEncode: needs %lld bytes", 16 + (long long)c); return -1; }
-        memcpy(out + 16, packed.data(), c);
-        isize = (int)c;
-    }
-    memcpy(out, &isize, 4);                                     // liveScanClient.cpp:284-288
-    memcpy(out + 4, &comp, 4);
-    memcpy(out + 8, &width, 4);
-    memcpy(out + 12, &height, 4);
-    return 16 + (long long)isize;
+    return lsn::guarded("lsnFrameDecode", -1LL, [&]() -> long long {
+        lsn::clear_error();
+        if (!payload || payload_bytes <= 0 || width < 0 || height < 0) { lsn::set_error("lsnFrameDecode: bad arguments"); return -1; }
+        const long long P = (long long)width * height;
+        const unsigned char *raw = payload;
+        long long raw_len = payload_bytes;
+        std::vector<unsigned char> tmp;
+        if (compressed == 1) {                                      // KinectSocket.cs:247-248
+            Zstd &z = zstd();
+            if (!z.ok) { lsn::set_error("lsnFrameDecode: compressed frame but libzstd.so.1 could not be loaded"); return -1; }
+            const unsigned long long out = z.decompressed_size(payload, (size_t)payload_bytes);     // ZSTDDecompressor.cs:28
+            // a frame is w*h*5 bytes plus a few KB of body joints: anything else is a corrupted length field, not worth allocating
+            if (out < (unsigned long long)(5 * P + 4) || out > (unsigned long long)(5 * P) + (1ull << 20)) {
+                lsn::set_error("lsnFrameDecode: the zstd frame announces %llu bytes, a %d x %d frame has %lld + bodies", out, width, height, 5 * P);
+                return -1;
+            }
+            tmp.resize((size_t)out);
+            const size_t got = z.decompress(tmp.data(), tmp.size(), payload, (size_t)payload_bytes);
+            if (z.is_error(got) || got != out) { lsn::set_error("lsnFrameDecode: zstd decompression failed"); return -1; }
+            raw = tmp.data();
+            raw_len = (long long)out;
+        }
+        if (raw_len < 5 * P + 4) { lsn::set_error("lsnFrameDecode: payload of %lld bytes is shorter than %d x %d x 5 + 4", raw_len, width, height); return -1; }
+        int nb = 0;
+        const long long bl = body_block_length(raw + 5 * P, raw_len - 5 * P, &nb);
+        if (bl < 0) { lsn::set_error("lsnFrameDecode: inconsistent body block"); return -1; }
+        if (depth_out) memcpy(depth_out, raw, (size_t)(2 * P));                              // KinectSocket.cs:256
+        if (rgb_out) memcpy(rgb_out, raw + 2 * P, (size_t)(3 * P));                          // :257
+        if (bodies_out) {
+            if (bl > bodies_cap) { lsn::set_error("lsnFrameDecode: body block of %lld bytes exceeds the buffer (%d)", bl, bodies_cap); return -1; }
+            memcpy(bodies_out, raw + 5 * P, (size_t)bl);
+        }
+        if (n_bodies) *n_bodies = nb;
+        return bl;
+    });
 }
 
 long long lsnFrameEncode(const unsigned char *depth, const unsigned char *rgb, int width, int height, const unsigned char *bodies,
                          int bodies_bytes, int compression_level, unsigned char *out, long long out_cap)
 {
-    return lsn::guarded<long long>("lsnFrameEncode", static_cast<long long>(-1), [&]() { return lsnFrameEncode_impl(depth, rgb, width, height, bodies, bodies_bytes, compression_level, out, out_cap); });
-}
-
-static long long lsnRecordingAppend_impl(unsigned char *out, long long cap, const unsigned char *frame, int len, int timestamp_ms)
-{
-    lsn::clear_error();
-    char hdr[96];
-    const int hl = snprintf(hdr, sizeof hdr, "bufferSize= %d\nframe_timestamp= %d\n", len, timestamp_ms);   // frameFileWriterReader.cpp:123
-    const long long need = hl + (long long)len + 1;
-    if (!out || len < 0 || need > cap) { lsn::set_error("lsnRecordingAppend: needs %lld bytes", need); return -1; }
-    memcpy(out, hdr, (size_t)hl);
-    if (len > 0) memcpy(out + hl, frame, (size_t)len);
-    out[hl + len] = '\n';                                       // :127
-    return need;
+    return lsn::guarded("lsnFrameEncode", -1LL, [&]() -> long long {
+        lsn::clear_error();
+        if (!depth || !rgb || !out || width < 0 || height < 0) { lsn::set_error("lsnFrameEncode: bad arguments"); return -1; }
+        static const unsigned char no_bodies[4] = {0, 0, 0, 0};
+        if (!bodies || bodies_bytes < 4) { bodies = no_bodies; bodies_bytes = 4; }
+        const long long P = (long long)width * height, size = 5 * P + bodies_bytes;
+        if (size > 0x7fffffffll) { lsn::set_error("lsnFrameEncode: frame too large"); return -1; }
+        int isize = (int)size, comp = compression_level > 0 ? 1 : 0;
+        if (!comp) {
+            if (16 + size > out_cap) { lsn::set_error("lsnFrameEncode: needs %lld bytes", 16 + size); return -1; }
+            memcpy(out + 16, depth, (size_t)(2 * P));
+            memcpy(out + 16 + 2 * P, rgb, (size_t)(3 * P));
+            memcpy(out + 16 + 5 * P, bodies, (size_t)bodies_bytes);
+        } else {                                                    // liveScanClient.cpp:270-281
+            Zstd &z = zstd();
+            if (!z.ok) { lsn::set_error("lsnFrameEncode: compression requested but libzstd.so.1 could not be loaded"); return -1; }
+            std::vector<unsigned char> raw((size_t)size);
+            memcpy(raw.data(), depth, (size_t)(2 * P));
+            memcpy(raw.data() + 2 * P, rgb, (size_t)(3 * P));
+            memcpy(raw.data() + 5 * P, bodies, (size_t)bodies_bytes);
+            std::vector<unsigned char> packed(z.bound((size_t)size));
+            const size_t c = z.compress(packed.data(), packed.size(), raw.data(), raw.size(), compression_level);
+            if (z.is_error(c)) { lsn::set_error("lsnFrameEncode: zstd compression failed"); return -1; }
+            if (16 + (long long)c > out_cap) { lsn::set_error("lsnFrameEncode: needs %lld bytes", 16 + (long long)c); return -1; }
+            memcpy(out + 16, packed.data(), c);
+            isize = (int)c;
+        }
+        memcpy(out, &isize, 4);                                     // liveScanClient.cpp:284-288
+        memcpy(out + 4, &comp, 4);
+        memcpy(out + 8, &width, 4);
+        memcpy(out + 12, &height, 4);
+        return 16 + (long long)isize;
+    });
 }
 
 long long lsnRecordingAppend(unsigned char *out, long long cap, const unsigned char *frame, int len, int timestamp_ms)
 {
-    return lsn::guarded<long long>("lsnRecordingAppend", static_cast<long long>(-1), [&]() { return lsnRecordingAppend_impl(out, cap, frame, len, timestamp_ms); });
+    return lsn::guarded("lsnRecordingAppend", -1LL, [&]() -> long long {
+        lsn::clear_error();
+        char hdr[96];
+        const int hl = snprintf(hdr, sizeof hdr, "bufferSize= %d\nframe_timestamp= %d\n", len, timestamp_ms);   // frameFileWriterReader.cpp:123
+        const long long need = hl + (long long)len + 1;
+        if (!out || len < 0 || need > cap) { lsn::set_error("lsnRecordingAppend: needs %lld bytes", need); return -1; }
+        memcpy(out, hdr, (size_t)hl);
+        if (len > 0) memcpy(out + hl, frame, (size_t)len);
+        out[hl + len] = '\n';                                       // :127
+        return need;
+    });
 }
 
 }  // extern "C"
@@ -1339,33 +1301,29 @@ bool next_int(const unsigned char *f, long long len, long long *pos, int *out)
 
 extern "C" {
 
-static long long lsnRecordingNext_impl(const unsigned char *file, long long len, long long pos, long long *frame_off, int *frame_len,
-                           int *timestamp_ms)
-{
-    lsn::clear_error();
-    if (!file || pos < 0 || !frame_off || !frame_len || !timestamp_ms) { lsn::set_error("lsnRecordingNext: bad arguments"); return -1; }
-    long long b, e;
-    int size = 0, ts = 0;
-    if (!next_token(file, len, &pos, &b, &e)) return -1;        // end of file: not an error
-    if (!next_int(file, len, &pos, &size) || !next_token(file, len, &pos, &b, &e) || !next_int(file, len, &pos, &ts) || size < 0) {
-        lsn::set_error("lsnRecordingNext: malformed record header at byte %lld", b);
-        return -1;
-    }
-    *frame_len = size;
-    *timestamp_ms = ts;
-    if (size == 0) { *frame_off = pos; return pos; }            // :72-73
-    pos += 1;                                                   // fgetc '\n' (:75)
-    if (pos + size > len) { lsn::set_error("lsnRecordingNext: record of %d bytes runs past the end of the file", size); return -1; }
-    *frame_off = pos;
-    pos += size;
-    if (pos < len) pos += 1;                                    // fgetc '\n' (:78)
-    return pos;
-}
-
 long long lsnRecordingNext(const unsigned char *file, long long len, long long pos, long long *frame_off, int *frame_len,
                            int *timestamp_ms)
 {
-    return lsn::guarded<long long>("lsnRecordingNext", static_cast<long long>(-1), [&]() { return lsnRecordingNext_impl(file, len, pos, frame_off, frame_len, timestamp_ms); });
+    return lsn::guarded("lsnRecordingNext", -1LL, [&]() -> long long {
+        lsn::clear_error();
+        if (!file || pos < 0 || !frame_off || !frame_len || !timestamp_ms) { lsn::set_error("lsnRecordingNext: bad arguments"); return -1; }
+        long long b, e;
+        int size = 0, ts = 0;
+        if (!next_token(file, len, &pos, &b, &e)) return -1;        // end of file: not an error
+        if (!next_int(file, len, &pos, &size) || !next_token(file, len, &pos, &b, &e) || !next_int(file, len, &pos, &ts) || size < 0) {
+            lsn::set_error("lsnRecordingNext: malformed record header at byte %lld", b);
+            return -1;
+        }
+        *frame_len = size;
+        *timestamp_ms = ts;
+        if (size == 0) { *frame_off = pos; return pos; }            // :72-73
+        pos += 1;                                                   // fgetc '\n' (:75)
+        if (pos + size > len) { lsn::set_error("lsnRecordingNext: record of %d bytes runs past the end of the file", size); return -1; }
+        *frame_off = pos;
+        pos += size;
+        if (pos < len) pos += 1;                                    // fgetc '\n' (:78)
+        return pos;
+    });
 }
 
 }  // extern "C"

@@ -19,26 +19,6 @@ LIB_PATH = os.environ.get("LSN_NATIVE_LIB") or os.path.join(_HERE, "lib", "libNa
 VERTEX_DTYPE = np.dtype([("R", "u1"), ("G", "u1"), ("B", "u1"), ("A", "u1"),
                          ("X", "<f4"), ("Y", "<f4"), ("Z", "<f4")])  # VertexC4ubV3f, 16 bytes
 
-# every symbol include/NativeUtils.h declares
-EXPORTS = [
-    "generateVerticesFromDepthMap", "generateMeshFromDepthMaps", "depthMapAndColorSetRadialCorrection", "createMesh", "deleteMesh", "ICP",
-    "lsnGetLastError", "lsnDeviceCount", "lsnCorrectAndGenerateMesh", "lsnHostScheduleDescribe", "lsnHostShardDescribe", "lsnHostShardPartMicros", "lsnTestFaultPoints", "lsnHostPoolStats",
-    "lsnFusionCreate", "lsnFusionDestroy", "lsnFusionTickCapacity", "lsnFusionSetParams", "lsnPackSensorParams", "lsnFusionSetMode",
-    "lsnFusionRun", "lsnFusionRunStreamed", "lsnFusionSetPipelined", "lsnFusionRadialCorrect", "lsnFusionRadialCorrectTo", "lsnFusionRadialCountersLeft", "lsnFusionRunMesh", "lsnFusionTickTriangleCapacity", "lsnFusionProfile", "lsnFusionKernelStats", "lsnFusionLookbackFailed", "lsnFusionCheck", "lsnFusionThresholds", "lsnMergeShards",
-    "lsnFusionColorTransfer", "lsnFusionColorDiagnostics", "lsnFusionOverlayMerge", "lsnFusionOverlayDiagnostics", "lsnSetOverlayMerge",
-    "lsnFusionOutlierFilter", "lsnFusionOutlierDiagnostics", "lsnSetOutlierFilter",
-    "lsnFusionFlyingPixels", "lsnFusionFlyingDiagnostics", "lsnSetFlyingPixelFilter", "lsnTickSetFlyingPixels",
-    "lsnFusionTilesPerTick", "lsnFusionPackSurvivors", "lsnFusionReconstruct",
-    "lsnDeviceMalloc", "lsnDeviceFree", "lsnDeviceUpload", "lsnDeviceDownload", "lsnStreamCreate", "lsnStreamDestroy", "lsnStreamSynchronize",
-    "lsnFusionPackSurvivorsRun", "lsnFusionReconstructRun", "lsnShardUniqueId", "lsnShardPlan", "lsnShardCreate", "lsnShardPrepare", "lsnShardConnect", "lsnShardRcclPath", "lsnShardDestroy", "lsnShardMergedCapacity", "lsnShardSetParams", "lsnShardStep", "lsnShardLastBytesSent", "lsnShardRanksSeen",
-    "lsnIcpCreate", "lsnIcpDestroy", "lsnIcpRun", "lsnIcpNearest", "lsnIcpTrace", "lsnIcpSetProfiling", "lsnIcpProfile", "lsnIcpNearResolved", "lsnRefine",
-    "lsnTickCreate", "lsnTickDestroy", "lsnTickSetParams", "lsnTickCapacity", "lsnTickTriangleCapacity", "lsnTickParts", "lsnTickRun",
-    "lsnTransferCreate", "lsnTransferDestroy", "lsnTransferFrameBound", "lsnTransferPack", "lsnTransferLastPath", "lsnPlyBinaryBytes", "lsnPlyPack",
-    "lsnLastMeshTransferFrame", "lsnLastMeshPly",
-    "lsnZstdAvailable", "lsnFrameParseHeader", "lsnFrameDecode", "lsnFrameEncode", "lsnRecordingNext", "lsnRecordingAppend",
-]
-
-
 class NativeUtilsError(RuntimeError):
     pass
 
@@ -54,6 +34,120 @@ assert C.sizeof(Mesh) == 32
 class FrameInfo(C.Structure):
     """LsnFrameInfo: the 16-byte header of a frame message (KinectSocket.cs:229-239)."""
     _fields_ = [("payload_bytes", C.c_int), ("compressed", C.c_int), ("width", C.c_int), ("height", C.c_int)]
+
+
+_vp, _i, _ll, _f, _b, _s = C.c_void_p, C.c_int, C.c_longlong, C.c_float, C.c_bool, C.c_char_p
+_mesh = C.POINTER(Mesh)
+
+# Every function include/NativeUtils.h declares: name -> (restype, argtypes).  This is the one place the header's types are restated
+# (tests/test_abi.py holds every entry against the header); lib() declares them all in one loop.
+_PROTOTYPES = {
+    # part 1: the reference's exports and what belongs to them
+    "generateVerticesFromDepthMap": (None, [_vp, _vp, _vp, _vp, _vp, _vp, _mesh, _f, _f, _f, _f, _f, _f, _i]),
+    "generateMeshFromDepthMaps": (None, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _mesh, _b, _f, _f, _f, _f, _f, _f, _b]),
+    "depthMapAndColorSetRadialCorrection": (None, [_i, _vp, _vp, _vp, _vp, _vp]),
+    "createMesh": (_mesh, []),
+    "deleteMesh": (None, [_mesh]),
+    "ICP": (_f, [_vp, _vp, _i, _i, _vp, _vp, _i]),
+    "lsnGetLastError": (_i, [_s, _i]),
+    "lsnDeviceCount": (_i, []),
+    "lsnCorrectAndGenerateMesh": (None, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _mesh, _f, _f, _f, _f, _f, _f, _i]),
+    "lsnHostScheduleDescribe": (_i, [_i, _vp, _vp, _i, _i, _i, _i, _s, _i]),
+    "lsnHostShardDescribe": (_i, [_i, _i, _vp, _s, _i]),
+    "lsnHostShardPartMicros": (_i, [_vp, _i]),
+    "lsnTestFaultPoints": (_ll, [_i]),
+    "lsnHostPoolStats": (_i, [_vp, _vp, _vp]),
+    "lsnSetOverlayMerge": (_i, [_i]),
+    "lsnSetOutlierFilter": (_i, [_i, _f, _vp, _vp]),
+    "lsnSetFlyingPixelFilter": (_i, [_i, _i, _vp, _vp]),
+    # part 2: the device-resident API
+    "lsnFusionCreate": (_vp, [_i, _i, _i, _vp, _vp]),
+    "lsnFusionDestroy": (None, [_vp]),
+    "lsnFusionTickCapacity": (_ll, [_vp]),
+    "lsnFusionSetParams": (_i, [_vp, _vp, _vp, _vp, _vp]),
+    "lsnPackSensorParams": (_i, [_vp, _vp, _vp]),
+    "lsnFusionSetMode": (_i, [_vp, _i]),
+    "lsnFusionRun": (_i, [_vp] * 6),
+    "lsnFusionRunStreamed": (_i, [_vp] * 7),
+    "lsnFusionSetPipelined": (_i, [_vp, _i]),
+    "lsnFusionRadialCorrect": (_i, [_vp] * 5),
+    "lsnFusionRadialCorrectTo": (_i, [_vp] * 7),
+    "lsnFusionRadialCountersLeft": (_i, [_vp, _vp]),
+    "lsnFusionRunMesh": (_i, [_vp] * 8),
+    "lsnFusionTickTriangleCapacity": (_ll, [_vp]),
+    "lsnFusionProfile": (_i, [_vp, _i]),
+    "lsnFusionKernelStats": (_i, [_vp, C.POINTER(C.c_double), C.POINTER(_ll), _s, _i, _i]),
+    "lsnFusionLookbackFailed": (_i, [_vp, _vp]),
+    "lsnFusionCheck": (_i, [_vp, _vp]),
+    "lsnFusionThresholds": (_i, [_vp, _vp, C.POINTER(_f), _vp]),
+    "lsnMergeShards": (_i, [_i, _i, _i, _i, _vp, _ll, _vp, _vp, _ll, _vp, _vp]),
+    "lsnFusionColorTransfer": (_i, [_vp] * 5),
+    "lsnFusionColorDiagnostics": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp]),
+    "lsnFusionOverlayMerge": (_i, [_vp] * 7),
+    "lsnFusionOverlayDiagnostics": (_i, [_vp, _i, _vp, _vp, _vp, _vp]),
+    "lsnFusionOutlierFilter": (_i, [_vp, _i, _f, _vp, _vp, _vp, _vp, _vp]),
+    "lsnFusionOutlierDiagnostics": (_i, [_vp, _i, _vp, _vp, _vp, _vp]),
+    "lsnFusionFlyingPixels": (_i, [_vp, _i, _i, _vp, _vp, _vp]),
+    "lsnFusionFlyingDiagnostics": (_i, [_vp, _i, _vp, _vp]),
+    "lsnFusionTilesPerTick": (_i, [_vp]),
+    "lsnFusionPackSurvivors": (_i, [_vp] * 9),
+    "lsnFusionReconstruct": (_i, [_vp, _i, _i, _vp, _vp, _vp, _ll, _vp, _vp, _vp, _vp, _vp]),
+    "lsnFusionPackSurvivorsRun": (_i, [_vp] * 10),
+    "lsnFusionReconstructRun": (_i, [_vp, _i, _i, _vp, _vp, _vp, _ll, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "lsnDeviceMalloc": (_vp, [_i, _ll]),
+    "lsnDeviceFree": (_i, [_i, _vp]),
+    "lsnDeviceUpload": (_i, [_i, _vp, _vp, _ll, _vp]),
+    "lsnDeviceDownload": (_i, [_i, _vp, _vp, _ll, _vp]),
+    "lsnStreamCreate": (_vp, [_i]),
+    "lsnStreamDestroy": (_i, [_i, _vp]),
+    "lsnStreamSynchronize": (_i, [_i, _vp]),
+    "lsnShardUniqueId": (_i, [_vp]),
+    "lsnShardCreate": (_vp, [_i, _i, _i, _vp, _i, _i, _vp, _vp]),
+    "lsnShardPrepare": (_vp, [_i, _i, _i, _i, _i, _vp, _vp]),
+    "lsnShardConnect": (_i, [_vp, _vp]),
+    "lsnShardRcclPath": (_i, [_s, _i]),
+    "lsnShardPlan": (_vp, [_vp, _i]),
+    "lsnShardDestroy": (None, [_vp]),
+    "lsnShardMergedCapacity": (_ll, [_vp]),
+    "lsnShardSetParams": (_i, [_vp] * 5),
+    "lsnShardStep": (_i, [_vp] * 6),
+    "lsnShardLastBytesSent": (_ll, [_vp]),
+    "lsnShardRanksSeen": (_i, [_vp]),
+    "lsnIcpCreate": (_vp, [_i, _i, _i]),
+    "lsnIcpDestroy": (None, [_vp]),
+    "lsnIcpRun": (_i, [_vp, _vp, _i, _vp, _i, _vp, _vp, _i, _i, _vp]),
+    "lsnIcpNearest": (_i, [_vp, _vp, _i, _vp, _i, _vp, _vp, _i, _vp]),
+    "lsnIcpTrace": (_i, [_vp, _vp, _i, _vp]),
+    "lsnIcpSetProfiling": (_i, [_vp, _i]),
+    "lsnIcpProfile": (_i, [_vp, _vp, _vp]),
+    "lsnIcpNearResolved": (_i, [_vp, _vp]),
+    "lsnRefine": (_i, [_i, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp]),
+    "lsnTickCreate": (_vp, [_i, _i, _i, _vp, _vp]),
+    "lsnTickDestroy": (None, [_vp]),
+    "lsnTickSetParams": (_i, [_vp] * 5),
+    "lsnTickSetFlyingPixels": (_i, [_vp, _i, _i]),
+    "lsnTickCapacity": (_ll, [_vp]),
+    "lsnTickTriangleCapacity": (_ll, [_vp]),
+    "lsnTickParts": (_i, [_vp]),
+    "lsnTickRun": (_i, [_vp] * 10),
+    # part 3: wire / disk formats
+    "lsnTransferCreate": (_vp, [_i, _i, _i]),
+    "lsnTransferDestroy": (None, [_vp]),
+    "lsnTransferFrameBound": (_ll, [_i, _i]),
+    "lsnTransferPack": (_ll, [_vp, _vp, _i, _vp, _i, _vp, _ll, _vp]),
+    "lsnTransferLastPath": (_i, [_vp]),
+    "lsnPlyBinaryBytes": (_ll, [_i, _i]),
+    "lsnPlyPack": (_ll, [_i, _vp, _i, _vp, _i, _vp, _ll, _vp]),
+    "lsnLastMeshTransferFrame": (_ll, [_vp, _ll]),
+    "lsnLastMeshPly": (_ll, [_vp, _ll]),
+    "lsnZstdAvailable": (_i, []),
+    "lsnFrameParseHeader": (_i, [_vp, C.POINTER(FrameInfo)]),
+    "lsnFrameDecode": (_ll, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _i, C.POINTER(_i)]),
+    "lsnFrameEncode": (_ll, [_vp, _vp, _i, _i, _vp, _i, _i, _vp, _ll]),
+    "lsnRecordingNext": (_ll, [_vp, _ll, _ll, C.POINTER(_ll), C.POINTER(_i), C.POINTER(_i)]),
+    "lsnRecordingAppend": (_ll, [_vp, _ll, _vp, _i, _i]),
+}
+EXPORTS = list(_PROTOTYPES)
 
 _lib = None
 
@@ -77,216 +171,10 @@ def lib():
         L = C.CDLL(LIB_PATH)
     except OSError as e:  # pragma: no cover
         raise NativeUtilsError(f"cannot load {LIB_PATH}: {e}") from e
-    vp, fp, ip = C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_int)
-    f = C.c_float
-    L.generateVerticesFromDepthMap.restype = None
-    L.generateVerticesFromDepthMap.argtypes = [vp, vp, vp, vp, vp, vp, C.POINTER(Mesh), f, f, f, f, f, f, C.c_int]
-    L.generateMeshFromDepthMaps.restype = None
-    L.generateMeshFromDepthMaps.argtypes = [C.c_int, vp, vp, vp, vp, vp, vp, C.POINTER(Mesh), C.c_bool,
-                                            f, f, f, f, f, f, C.c_bool]
-    L.lsnCorrectAndGenerateMesh.restype = None
-    L.lsnCorrectAndGenerateMesh.argtypes = [C.c_int, vp, vp, vp, vp, vp, vp, C.POINTER(Mesh), f, f, f, f, f, f, C.c_int]
-    L.depthMapAndColorSetRadialCorrection.restype = None
-    L.depthMapAndColorSetRadialCorrection.argtypes = [C.c_int, vp, vp, vp, vp, vp]
-    L.lsnFusionRadialCorrect.restype = C.c_int
-    L.lsnFusionRadialCorrect.argtypes = [vp, vp, vp, vp, vp]
-    L.lsnFusionRadialCountersLeft.restype = C.c_int
-    L.lsnFusionRadialCountersLeft.argtypes = [vp, vp]
-    L.lsnFusionRadialCorrectTo.restype = C.c_int
-    L.lsnFusionRadialCorrectTo.argtypes = [vp, vp, vp, vp, vp, vp, vp]
-    L.createMesh.restype = C.POINTER(Mesh)
-    L.createMesh.argtypes = []
-    L.deleteMesh.restype = None
-    L.deleteMesh.argtypes = [C.POINTER(Mesh)]
-    L.ICP.restype = C.c_float
-    L.ICP.argtypes = [vp, vp, C.c_int, C.c_int, vp, vp, C.c_int]
-    L.lsnGetLastError.restype = C.c_int
-    L.lsnGetLastError.argtypes = [C.c_char_p, C.c_int]
-    L.lsnDeviceCount.restype = C.c_int
-    L.lsnDeviceCount.argtypes = []
-    L.lsnFusionCreate.restype = vp
-    L.lsnFusionCreate.argtypes = [C.c_int, C.c_int, C.c_int, vp, vp]
-    L.lsnFusionDestroy.restype = None
-    L.lsnFusionDestroy.argtypes = [vp]
-    L.lsnFusionTickCapacity.restype = C.c_longlong
-    L.lsnFusionTickCapacity.argtypes = [vp]
-    L.lsnFusionSetParams.restype = C.c_int
-    L.lsnFusionSetParams.argtypes = [vp, vp, vp, vp, vp]
-    L.lsnPackSensorParams.restype = C.c_int
-    L.lsnPackSensorParams.argtypes = [vp, vp, vp]
-    L.lsnHostShardDescribe.restype = C.c_int
-    L.lsnHostShardDescribe.argtypes = [C.c_int, C.c_int, vp, C.c_char_p, C.c_int]
-    L.lsnHostShardPartMicros.restype = C.c_int
-    L.lsnHostShardPartMicros.argtypes = [vp, C.c_int]
-    L.lsnTestFaultPoints.restype = C.c_longlong
-    L.lsnTestFaultPoints.argtypes = [C.c_int]
-    L.lsnHostPoolStats.restype = C.c_int
-    L.lsnHostPoolStats.argtypes = [vp, vp, vp]
-    L.lsnHostScheduleDescribe.restype = C.c_int
-    L.lsnHostScheduleDescribe.argtypes = [C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_int]
-    L.lsnFusionSetMode.restype = C.c_int
-    L.lsnFusionSetMode.argtypes = [vp, C.c_int]
-    L.lsnFusionRunStreamed.restype = C.c_int
-    L.lsnFusionRunStreamed.argtypes = [vp, vp, vp, vp, vp, vp, vp]
-    L.lsnFusionSetPipelined.restype = C.c_int
-    L.lsnFusionSetPipelined.argtypes = [vp, C.c_int]
-    L.lsnFusionRun.restype = C.c_int
-    L.lsnFusionRun.argtypes = [vp, vp, vp, vp, vp, vp]
-    L.lsnFusionRunMesh.restype = C.c_int
-    L.lsnFusionRunMesh.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp]
-    L.lsnFusionTickTriangleCapacity.restype = C.c_longlong
-    L.lsnFusionTickTriangleCapacity.argtypes = [vp]
-    L.lsnFusionProfile.restype = C.c_int
-    L.lsnFusionProfile.argtypes = [vp, C.c_int]
-    L.lsnFusionKernelStats.restype = C.c_int
-    L.lsnFusionKernelStats.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_longlong), C.c_char_p, C.c_int, C.c_int]
-    L.lsnFusionThresholds.restype = C.c_int
-    L.lsnFusionThresholds.argtypes = [vp, vp, C.POINTER(C.c_float), vp]
-    L.lsnFusionTilesPerTick.restype = C.c_int
-    L.lsnFusionTilesPerTick.argtypes = [vp]
-    L.lsnFusionPackSurvivors.restype = C.c_int
-    L.lsnFusionPackSurvivors.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp]
-    L.lsnFusionReconstruct.restype = C.c_int
-    L.lsnFusionReconstruct.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp, C.c_longlong, vp, vp, vp, vp, vp]
-    L.lsnFusionLookbackFailed.restype = C.c_int
-    L.lsnFusionLookbackFailed.argtypes = [vp, vp]
-    L.lsnFusionCheck.restype = C.c_int
-    L.lsnFusionCheck.argtypes = [vp, vp]
-    L.lsnFusionColorTransfer.restype = C.c_int
-    L.lsnFusionColorTransfer.argtypes = [vp, vp, vp, vp, vp]
-    L.lsnFusionColorDiagnostics.restype = C.c_int
-    L.lsnFusionColorDiagnostics.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp]
-    L.lsnFusionOverlayMerge.restype = C.c_int
-    L.lsnFusionOverlayMerge.argtypes = [vp, vp, vp, vp, vp, vp, vp]
-    L.lsnFusionOverlayDiagnostics.restype = C.c_int
-    L.lsnFusionOverlayDiagnostics.argtypes = [vp, C.c_int, vp, vp, vp, vp]
-    L.lsnSetOverlayMerge.restype = C.c_int
-    L.lsnSetOverlayMerge.argtypes = [C.c_int]
-    if hasattr(L, "lsnSetOutlierFilter"):   # (absent from an older build loaded through $LSN_NATIVE_LIB)
-        L.lsnFusionOutlierFilter.restype = C.c_int
-        L.lsnFusionOutlierFilter.argtypes = [vp, C.c_int, C.c_float, vp, vp, vp, vp, vp]
-        L.lsnFusionOutlierDiagnostics.restype = C.c_int
-        L.lsnFusionOutlierDiagnostics.argtypes = [vp, C.c_int, vp, vp, vp, vp]
-        L.lsnSetOutlierFilter.restype = C.c_int
-        L.lsnSetOutlierFilter.argtypes = [C.c_int, C.c_float, vp, vp]
-    if hasattr(L, "lsnSetFlyingPixelFilter"):   # (absent from an older build loaded through $LSN_NATIVE_LIB)
-        L.lsnFusionFlyingPixels.restype = C.c_int
-        L.lsnFusionFlyingPixels.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp]
-        L.lsnFusionFlyingDiagnostics.restype = C.c_int
-        L.lsnFusionFlyingDiagnostics.argtypes = [vp, C.c_int, vp, vp]
-        L.lsnSetFlyingPixelFilter.restype = C.c_int
-        L.lsnSetFlyingPixelFilter.argtypes = [C.c_int, C.c_int, vp, vp]
-        L.lsnTickSetFlyingPixels.restype = C.c_int
-        L.lsnTickSetFlyingPixels.argtypes = [vp, C.c_int, C.c_int]
-    L.lsnMergeShards.restype = C.c_int
-    L.lsnMergeShards.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_longlong, vp, vp, C.c_longlong, vp, vp]
-    L.lsnIcpCreate.restype = vp
-    L.lsnIcpCreate.argtypes = [C.c_int, C.c_int, C.c_int]
-    L.lsnIcpDestroy.restype = None
-    L.lsnIcpDestroy.argtypes = [vp]
-    L.lsnIcpRun.restype = C.c_int
-    L.lsnIcpRun.argtypes = [vp, vp, C.c_int, vp, C.c_int, vp, vp, C.c_int, C.c_int, vp]
-    L.lsnIcpNearest.restype = C.c_int
-    L.lsnIcpNearest.argtypes = [vp, vp, C.c_int, vp, C.c_int, vp, vp, C.c_int, vp]
-    L.lsnRefine.restype = C.c_int
-    L.lsnRefine.argtypes = [C.c_int, C.c_int, vp, vp, C.c_int, C.c_int, vp, vp, vp, vp]
-    L.lsnDeviceMalloc.restype = vp
-    L.lsnDeviceMalloc.argtypes = [C.c_int, C.c_longlong]
-    L.lsnDeviceFree.restype = C.c_int
-    L.lsnDeviceFree.argtypes = [C.c_int, vp]
-    L.lsnDeviceUpload.restype = C.c_int
-    L.lsnDeviceUpload.argtypes = [C.c_int, vp, vp, C.c_longlong, vp]
-    L.lsnDeviceDownload.restype = C.c_int
-    L.lsnDeviceDownload.argtypes = [C.c_int, vp, vp, C.c_longlong, vp]
-    L.lsnStreamCreate.restype = vp
-    L.lsnStreamCreate.argtypes = [C.c_int]
-    L.lsnStreamDestroy.restype = C.c_int
-    L.lsnStreamDestroy.argtypes = [C.c_int, vp]
-    L.lsnStreamSynchronize.restype = C.c_int
-    L.lsnStreamSynchronize.argtypes = [C.c_int, vp]
-    L.lsnFusionPackSurvivorsRun.restype = C.c_int
-    L.lsnFusionPackSurvivorsRun.argtypes = [vp] * 10
-    L.lsnFusionReconstructRun.restype = C.c_int
-    L.lsnFusionReconstructRun.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp, C.c_longlong, vp, vp, vp, vp, vp, vp]
-    L.lsnShardUniqueId.restype = C.c_int
-    L.lsnShardUniqueId.argtypes = [vp]
-    L.lsnShardCreate.restype = vp
-    L.lsnShardCreate.argtypes = [C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int, vp, vp]
-    L.lsnShardPrepare.restype = vp
-    L.lsnShardPrepare.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]
-    L.lsnShardConnect.restype = C.c_int
-    L.lsnShardConnect.argtypes = [vp, vp]
-    L.lsnShardRcclPath.restype = C.c_int
-    L.lsnShardRcclPath.argtypes = [C.c_char_p, C.c_int]
-    L.lsnShardPlan.restype = vp
-    L.lsnShardPlan.argtypes = [vp, C.c_int]
-    L.lsnShardDestroy.restype = None
-    L.lsnShardDestroy.argtypes = [vp]
-    L.lsnShardMergedCapacity.restype = C.c_longlong
-    L.lsnShardMergedCapacity.argtypes = [vp]
-    L.lsnShardLastBytesSent.restype = C.c_longlong
-    L.lsnShardLastBytesSent.argtypes = [vp]
-    L.lsnShardRanksSeen.restype = C.c_int
-    L.lsnShardRanksSeen.argtypes = [vp]
-    L.lsnShardSetParams.restype = C.c_int
-    L.lsnShardSetParams.argtypes = [vp, vp, vp, vp, vp]
-    L.lsnShardStep.restype = C.c_int
-    L.lsnShardStep.argtypes = [vp, vp, vp, vp, vp, vp]
-    L.lsnIcpTrace.restype = C.c_int
-    L.lsnIcpTrace.argtypes = [vp, vp, C.c_int, vp]
-    L.lsnIcpSetProfiling.restype = C.c_int
-    L.lsnIcpSetProfiling.argtypes = [vp, C.c_int]
-    L.lsnIcpProfile.restype = C.c_int
-    L.lsnIcpProfile.argtypes = [vp, vp, vp]
-    if hasattr(L, "lsnTickCreate"):
-        L.lsnTickCreate.restype = vp
-        L.lsnTickCreate.argtypes = [C.c_int, C.c_int, C.c_int, vp, vp]
-        L.lsnTickDestroy.restype = None
-        L.lsnTickDestroy.argtypes = [vp]
-        L.lsnTickSetParams.restype = C.c_int
-        L.lsnTickSetParams.argtypes = [vp, vp, vp, vp, vp]
-        L.lsnTickCapacity.restype = C.c_longlong
-        L.lsnTickCapacity.argtypes = [vp]
-        L.lsnTickTriangleCapacity.restype = C.c_longlong
-        L.lsnTickTriangleCapacity.argtypes = [vp]
-        L.lsnTickParts.restype = C.c_int
-        L.lsnTickParts.argtypes = [vp]
-        L.lsnTickRun.restype = C.c_int
-        L.lsnTickRun.argtypes = [vp] + [vp] * 9
-    if hasattr(L, "lsnIcpNearResolved"):   # (absent from an older build loaded through $LSN_NATIVE_LIB)
-        L.lsnIcpNearResolved.restype = C.c_int
-        L.lsnIcpNearResolved.argtypes = [vp, vp]
-    ll = C.c_longlong
-    L.lsnTransferCreate.restype = vp
-    L.lsnTransferCreate.argtypes = [C.c_int, C.c_int, C.c_int]
-    L.lsnTransferDestroy.restype = None
-    L.lsnTransferDestroy.argtypes = [vp]
-    L.lsnTransferLastPath.restype = C.c_int
-    L.lsnTransferLastPath.argtypes = [C.c_void_p]
-    L.lsnTransferFrameBound.restype = ll
-    L.lsnTransferFrameBound.argtypes = [C.c_int, C.c_int]
-    L.lsnTransferPack.restype = ll
-    L.lsnTransferPack.argtypes = [vp, vp, C.c_int, vp, C.c_int, vp, ll, vp]
-    L.lsnPlyBinaryBytes.restype = ll
-    L.lsnPlyBinaryBytes.argtypes = [C.c_int, C.c_int]
-    L.lsnPlyPack.restype = ll
-    L.lsnPlyPack.argtypes = [C.c_int, vp, C.c_int, vp, C.c_int, vp, ll, vp]
-    L.lsnLastMeshTransferFrame.restype = ll
-    L.lsnLastMeshTransferFrame.argtypes = [vp, ll]
-    L.lsnLastMeshPly.restype = ll
-    L.lsnLastMeshPly.argtypes = [vp, ll]
-    L.lsnZstdAvailable.restype = C.c_int
-    L.lsnZstdAvailable.argtypes = []
-    L.lsnFrameParseHeader.restype = C.c_int
-    L.lsnFrameParseHeader.argtypes = [vp, C.POINTER(FrameInfo)]
-    L.lsnFrameDecode.restype = ll
-    L.lsnFrameDecode.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, C.c_int, C.POINTER(C.c_int)]
-    L.lsnFrameEncode.restype = ll
-    L.lsnFrameEncode.argtypes = [vp, vp, C.c_int, C.c_int, vp, C.c_int, C.c_int, vp, ll]
-    L.lsnRecordingNext.restype = ll
-    L.lsnRecordingNext.argtypes = [vp, ll, ll, C.POINTER(ll), C.POINTER(C.c_int), C.POINTER(C.c_int)]
-    L.lsnRecordingAppend.restype = ll
-    L.lsnRecordingAppend.argtypes = [vp, ll, vp, C.c_int, C.c_int]
+    for name, (restype, argtypes) in _PROTOTYPES.items():
+        fn = getattr(L, name, None)   # a foreign build ($LSN_NATIVE_LIB) may lack an export: it stays undeclared, and calling it raises
+        if fn is not None:
+            fn.restype, fn.argtypes = restype, argtypes
     _lib = L
     return L
 
@@ -300,6 +188,20 @@ def last_error():
 def _check(rc, what):
     if rc != 0:
         raise NativeUtilsError(f"{what} failed: {last_error()}")
+
+
+def _nonneg(n, what):
+    """A count / size / code an export returns: negative means it failed."""
+    if n < 0:
+        raise NativeUtilsError(f"{what} failed: {last_error()}")
+    return n
+
+
+def _handle(h, what):
+    """The handle an lsn*Create export returns: null means it failed."""
+    if not h:
+        raise NativeUtilsError(f"{what} failed: {last_error()}")
+    return h
 
 
 def device_count():
@@ -354,21 +256,6 @@ def set_outlier_filter(k, max_dist):
     return pk.value, pd.value
 
 
-class _OutlierFilter:
-    """Sets the process-wide outlier filter for the body of a with-statement (None: leaves it as it is)."""
-
-    def __init__(self, setting):
-        self.setting, self.prev = setting, None
-
-    def __enter__(self):
-        if self.setting is not None:
-            self.prev = set_outlier_filter(*self.setting)
-
-    def __exit__(self, *exc):
-        if self.prev is not None:
-            set_outlier_filter(*self.prev)
-
-
 def set_flying_pixel_filter(neighbourhood, threshold):
     """lsnSetFlyingPixelFilter: the process-wide (neighbourhood, threshold) of the flying-pixel filter in the exports that start with the
     radial correction (radial_correction, correct_and_generate_mesh); neighbourhood <= 0: off.  Returns the previous pair."""
@@ -377,19 +264,47 @@ def set_flying_pixel_filter(neighbourhood, threshold):
     return pn.value, pt.value
 
 
-class _FlyingPixels:
-    """Sets the process-wide flying-pixel filter for the body of a with-statement (None: leaves it as it is)."""
+class _Scoped:
+    """Sets a process-wide setting for the body of a with-statement: setter(*setting) returns the previous one, which goes back in on the
+    way out (None: leaves the setting as it is)."""
 
-    def __init__(self, setting):
-        self.setting, self.prev = setting, None
+    def __init__(self, setter, setting):
+        self.setter, self.setting, self.prev = setter, setting, None
 
     def __enter__(self):
         if self.setting is not None:
-            self.prev = set_flying_pixel_filter(*self.setting)
+            self.prev = self.setter(*self.setting)
 
     def __exit__(self, *exc):
         if self.prev is not None:
-            set_flying_pixel_filter(*self.prev)
+            self.setter(*self.prev)
+
+
+def _host_args(depth_maps, depth_colors, widths, heights, intr, wt=None, bounds=None, copy=False):
+    """The host arrays of a part 1 export as it reads them, their sizes checked: (n, depth bytes, colour bytes, widths, heights, intr, wt,
+    bounds as six floats); wt / bounds stay None for the export without them.  copy: the depth and colour bytes are private copies (for
+    an export that works in place)."""
+    widths, heights = _as(widths, np.int32), _as(heights, np.int32)
+    n = len(widths)
+    dm = np.ascontiguousarray(depth_maps).view(np.uint8).ravel()
+    dc = _as(depth_colors, np.uint8).ravel()
+    if copy:
+        dm, dc = dm.copy(), dc.copy()
+    intr = _as(intr, np.float32).ravel()
+    assert intr.size == 7 * n
+    if wt is not None:
+        wt, bounds = _as(wt, np.float32).ravel(), _as(bounds, np.float32).ravel()
+        assert wt.size == 12 * n and bounds.size == 6
+        bounds = [float(x) for x in bounds]
+    return n, dm, dc, widths, heights, intr, wt, bounds
+
+
+def _raise_if_empty(mesh):
+    """A mesh export left a message and an empty mesh: the mesh goes back to the library and the message is raised."""
+    err = last_error()
+    if err and mesh.nVertices == 0:
+        lib().deleteMesh(C.byref(mesh))
+        raise NativeUtilsError(err)
 
 
 def generate_mesh_from_depth_maps(depth_maps, depth_colors, widths, heights, intr, wt, bounds,
@@ -397,32 +312,16 @@ def generate_mesh_from_depth_maps(depth_maps, depth_colors, widths, heights, int
     """KinectServer.GenerateMesh (KinectServer.cs:354-374).  Returns (vertices[VERTEX_DTYPE], triangles int32).
     overlay_merge: None leaves the process-wide switch (lsnSetOverlayMerge) as it is; True / False sets it for this call alone.
     outlier_filter: None leaves the process-wide outlier filter (lsnSetOutlierFilter) as it is; (k, max_dist) sets it for this call alone."""
-    if outlier_filter is not None:
-        with _OutlierFilter(outlier_filter):
-            return generate_mesh_from_depth_maps(depth_maps, depth_colors, widths, heights, intr, wt, bounds, color_transfer,
-                                                 generate_triangles, overlay_merge)
-    if overlay_merge is not None:
-        prev = set_overlay_merge(overlay_merge)
-        try:
-            return generate_mesh_from_depth_maps(depth_maps, depth_colors, widths, heights, intr, wt, bounds, color_transfer,
-                                                 generate_triangles)
-        finally:
-            set_overlay_merge(prev)
-    require_gpu()
-    widths, heights = _as(widths, np.int32), _as(heights, np.int32)
-    n = len(widths)
-    dm = np.ascontiguousarray(depth_maps).view(np.uint8).ravel()
-    dc = _as(depth_colors, np.uint8).ravel()
-    intr, wt, b = _as(intr, np.float32).ravel(), _as(wt, np.float32).ravel(), _as(bounds, np.float32).ravel()
-    assert intr.size == 7 * n and wt.size == 12 * n and b.size == 6
-    mesh = Mesh()
-    lib().generateMeshFromDepthMaps(n, _ptr(dm), _ptr(dc), _ptr(widths), _ptr(heights), _ptr(intr), _ptr(wt),
-                                    C.byref(mesh), bool(color_transfer), *[float(x) for x in b], bool(generate_triangles))
-    err = last_error()
-    if err and mesh.nVertices == 0 and not generate_triangles:
-        lib().deleteMesh(C.byref(mesh))
-        raise NativeUtilsError(err)
-    return _copy_mesh(mesh)
+    with _Scoped(set_outlier_filter, outlier_filter), \
+            _Scoped(lambda on: (set_overlay_merge(on),), None if overlay_merge is None else (overlay_merge,)):
+        require_gpu()
+        n, dm, dc, widths, heights, intr, wt, b = _host_args(depth_maps, depth_colors, widths, heights, intr, wt, bounds)
+        mesh = Mesh()
+        lib().generateMeshFromDepthMaps(n, _ptr(dm), _ptr(dc), _ptr(widths), _ptr(heights), _ptr(intr), _ptr(wt),
+                                        C.byref(mesh), bool(color_transfer), *b, bool(generate_triangles))
+        if not generate_triangles:   # (with triangles the message may be the notice that goes with the unmerged mesh)
+            _raise_if_empty(mesh)
+        return _copy_mesh(mesh)
 
 
 def host_shards(n_maps, n_devices=0):
@@ -468,21 +367,14 @@ def radial_correction(depth_maps, depth_colors, widths, heights, intr, flying_pi
     (depth as a uint8 view of the u16 maps, colours); the export itself works in place on the arrays it is given.
     flying_pixels: None leaves the process-wide flying-pixel filter (lsnSetFlyingPixelFilter) as it is; (neighbourhood, threshold) sets
     it for this call alone (the maps are filtered, then corrected)."""
-    if flying_pixels is not None:
-        with _FlyingPixels(flying_pixels):
-            return radial_correction(depth_maps, depth_colors, widths, heights, intr)
-    require_gpu()
-    widths, heights = _as(widths, np.int32), _as(heights, np.int32)
-    n = len(widths)
-    dm = np.ascontiguousarray(depth_maps).view(np.uint8).ravel().copy()
-    dc = _as(depth_colors, np.uint8).ravel().copy()
-    intr = _as(intr, np.float32).ravel()
-    assert intr.size == 7 * n
-    lib().depthMapAndColorSetRadialCorrection(n, _ptr(dm), _ptr(dc), _ptr(widths), _ptr(heights), _ptr(intr))
-    err = last_error()
-    if err:
-        raise NativeUtilsError(err)
-    return dm, dc
+    with _Scoped(set_flying_pixel_filter, flying_pixels):
+        require_gpu()
+        n, dm, dc, widths, heights, intr, _, _ = _host_args(depth_maps, depth_colors, widths, heights, intr, copy=True)
+        lib().depthMapAndColorSetRadialCorrection(n, _ptr(dm), _ptr(dc), _ptr(widths), _ptr(heights), _ptr(intr))
+        err = last_error()
+        if err:
+            raise NativeUtilsError(err)
+        return dm, dc
 
 
 def correct_and_generate_mesh(depth_maps, depth_colors, widths, heights, intr, wt, bounds, write_back=True, outlier_filter=None,
@@ -491,51 +383,28 @@ def correct_and_generate_mesh(depth_maps, depth_colors, widths, heights, intr, w
     corrected depth as uint8, corrected colours); with write_back=False the last two are the untouched inputs.
     outlier_filter: as for generate_mesh_from_depth_maps (the corrected maps written back are the unmasked ones).
     flying_pixels: as for radial_correction (the corrected maps written back are the filtered, corrected ones)."""
-    if flying_pixels is not None:
-        with _FlyingPixels(flying_pixels):
-            return correct_and_generate_mesh(depth_maps, depth_colors, widths, heights, intr, wt, bounds, write_back, outlier_filter)
-    if outlier_filter is not None:
-        with _OutlierFilter(outlier_filter):
-            return correct_and_generate_mesh(depth_maps, depth_colors, widths, heights, intr, wt, bounds, write_back)
-    require_gpu()
-    widths, heights = _as(widths, np.int32), _as(heights, np.int32)
-    n = len(widths)
-    dm = np.ascontiguousarray(depth_maps).view(np.uint8).ravel().copy()
-    dc = _as(depth_colors, np.uint8).ravel().copy()
-    intr, wt, b = _as(intr, np.float32).ravel(), _as(wt, np.float32).ravel(), _as(bounds, np.float32).ravel()
-    assert intr.size == 7 * n and wt.size == 12 * n and b.size == 6
-    mesh = Mesh()
-    lib().lsnCorrectAndGenerateMesh(n, _ptr(dm), _ptr(dc), _ptr(widths), _ptr(heights), _ptr(intr), _ptr(wt), C.byref(mesh),
-                                    *[float(x) for x in b], 1 if write_back else 0)
-    err = last_error()
-    if err and mesh.nVertices == 0:
-        lib().deleteMesh(C.byref(mesh))
-        raise NativeUtilsError(err)
-    v, t = _copy_mesh(mesh)
-    return v, t, dm, dc
+    with _Scoped(set_flying_pixel_filter, flying_pixels), _Scoped(set_outlier_filter, outlier_filter):
+        require_gpu()
+        n, dm, dc, widths, heights, intr, wt, b = _host_args(depth_maps, depth_colors, widths, heights, intr, wt, bounds, copy=True)
+        mesh = Mesh()
+        lib().lsnCorrectAndGenerateMesh(n, _ptr(dm), _ptr(dc), _ptr(widths), _ptr(heights), _ptr(intr), _ptr(wt), C.byref(mesh),
+                                        *b, 1 if write_back else 0)
+        _raise_if_empty(mesh)
+        v, t = _copy_mesh(mesh)
+        return v, t, dm, dc
 
 
 def generate_vertices_from_depth_map(depth_maps, depth_colors, widths, heights, intr, wt, bounds, index, outlier_filter=None):
     """One sensor's cropped cloud, as KinectServer.GetLatestFrameVerticesOnly calls it (KinectServer.cs:527-554).
     outlier_filter: as for generate_mesh_from_depth_maps."""
-    if outlier_filter is not None:
-        with _OutlierFilter(outlier_filter):
-            return generate_vertices_from_depth_map(depth_maps, depth_colors, widths, heights, intr, wt, bounds, index)
-    require_gpu()
-    widths, heights = _as(widths, np.int32), _as(heights, np.int32)
-    n = len(widths)
-    dm = np.ascontiguousarray(depth_maps).view(np.uint8).ravel()
-    dc = _as(depth_colors, np.uint8).ravel()
-    intr, wt, b = _as(intr, np.float32).ravel(), _as(wt, np.float32).ravel(), _as(bounds, np.float32).ravel()
-    assert intr.size == 7 * n and wt.size == 12 * n and b.size == 6
-    mesh = Mesh()
-    lib().generateVerticesFromDepthMap(_ptr(dm), _ptr(dc), _ptr(widths), _ptr(heights), _ptr(intr), _ptr(wt),
-                                       C.byref(mesh), *[float(x) for x in b], int(index))
-    err = last_error()
-    if err and mesh.nVertices == 0:
-        lib().deleteMesh(C.byref(mesh))
-        raise NativeUtilsError(err)
-    return _copy_mesh(mesh)[0]
+    with _Scoped(set_outlier_filter, outlier_filter):
+        require_gpu()
+        _, dm, dc, widths, heights, intr, wt, b = _host_args(depth_maps, depth_colors, widths, heights, intr, wt, bounds)
+        mesh = Mesh()
+        lib().generateVerticesFromDepthMap(_ptr(dm), _ptr(dc), _ptr(widths), _ptr(heights), _ptr(intr), _ptr(wt),
+                                           C.byref(mesh), *b, int(index))
+        _raise_if_empty(mesh)
+        return _copy_mesh(mesh)[0]
 
 
 def icp(verts1, verts2, R=None, t=None, max_iter=10):
@@ -573,23 +442,45 @@ def refine(clouds, world_R, world_t, n_refine_iters=2, n_icp_iters=10, device=0)
 # Part 2: device-resident API
 # ----------------------------------------------------------------------------------------------------------
 
-class FusionPlan:
+class _Handle:
+    """What the classes around an lsn*Create'd handle share: close() destroys the handle once, through the export the class names; a
+    collected object closes itself and never raises."""
+    _destroy = None   # the export that destroys the handle
+    _h = None
+
+    def close(self):
+        if self._h:
+            getattr(lib(), self._destroy)(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _set_params(what, h, n_maps, intr, wt, bounds, stream):
+    """lsnFusionSetParams / lsnShardSetParams / lsnTickSetParams: the calibration of n_maps sensors and the bounding box."""
+    intr, wt, b = _as(intr, np.float32).ravel(), _as(wt, np.float32).ravel(), _as(bounds, np.float32).ravel()
+    assert intr.size == 7 * n_maps and wt.size == 12 * n_maps and b.size == 6
+    _check(getattr(lib(), what)(h, _ptr(intr), _ptr(wt), _ptr(b), stream), what)
+
+
+class FusionPlan(_Handle):
     """lsnFusion*: T ticks x N sensors fused per call on HBM-resident inputs."""
+    _destroy = "lsnFusionDestroy"
 
     def __init__(self, device, n_ticks, widths, heights):
         require_gpu()
         self.widths, self.heights = _as(widths, np.int32), _as(heights, np.int32)
         self.n_maps, self.n_ticks, self.device = len(self.widths), int(n_ticks), int(device)
-        self._h = lib().lsnFusionCreate(self.device, self.n_ticks, self.n_maps, _ptr(self.widths), _ptr(self.heights))
-        if not self._h:
-            raise NativeUtilsError(f"lsnFusionCreate failed: {last_error()}")
+        self._h = _handle(lib().lsnFusionCreate(self.device, self.n_ticks, self.n_maps, _ptr(self.widths), _ptr(self.heights)), "lsnFusionCreate")
         self.capacity = int(lib().lsnFusionTickCapacity(self._h))
         self.pixels_per_tick = int(np.sum(self.widths.astype(np.int64) * self.heights))
 
     def set_params(self, intr, wt, bounds, stream=0):
-        intr, wt, b = _as(intr, np.float32).ravel(), _as(wt, np.float32).ravel(), _as(bounds, np.float32).ravel()
-        assert intr.size == 7 * self.n_maps and wt.size == 12 * self.n_maps and b.size == 6
-        _check(lib().lsnFusionSetParams(self._h, _ptr(intr), _ptr(wt), _ptr(b), stream), "lsnFusionSetParams")
+        _set_params("lsnFusionSetParams", self._h, self.n_maps, intr, wt, bounds, stream)
 
     def set_pipelined(self, enable=True):
         """Overlap the count pass of the next call with the write kernel of the current one (inputs must be resident)."""
@@ -617,9 +508,7 @@ class FusionPlan:
 
     def radial_counters_left(self, stream=0):
         """Work counters of the hole-closing chain that are not zero once `stream` has drained (test hook; 0 after a complete chain)."""
-        n = lib().lsnFusionRadialCountersLeft(self._h, stream)
-        if n < 0:
-            raise NativeUtilsError(f"lsnFusionRadialCountersLeft failed: {last_error()}")
+        n = _nonneg(lib().lsnFusionRadialCountersLeft(self._h, stream), "lsnFusionRadialCountersLeft")
         return n
 
     def run_mesh(self, d_depth, d_colors, d_vertices, d_offsets, d_triangles, d_tri_offsets, stream=0):
@@ -640,9 +529,7 @@ class FusionPlan:
         cov = np.zeros((n, n), dtype=np.int32)
         pairs = np.zeros(2 * max(n - 1, 1), dtype=np.int32)
         xf = np.zeros((max(n - 1, 1), 9), dtype=np.float64)
-        k = lib().lsnFusionColorDiagnostics(self._h, int(tick), _ptr(conf), _ptr(cov), _ptr(pairs), _ptr(xf), stream or None)
-        if k < 0:
-            raise NativeUtilsError(f"lsnFusionColorDiagnostics failed: {last_error()}")
+        k = _nonneg(lib().lsnFusionColorDiagnostics(self._h, int(tick), _ptr(conf), _ptr(cov), _ptr(pairs), _ptr(xf), stream or None), "lsnFusionColorDiagnostics")
         return {"confidence": conf[:self.pixels_per_tick], "coverage": cov,
                 "pairs": [(int(pairs[2 * q]), int(pairs[2 * q + 1])) for q in range(k)], "transforms": xf[:k].copy()}
 
@@ -658,9 +545,7 @@ class FusionPlan:
         rep = np.zeros(max(self.pixels_per_tick, 1), dtype=np.uint16)
         mer = np.zeros(max(self.pixels_per_tick, 1), dtype=np.uint16)
         asg = np.zeros(max(int(self.capacity), 1), dtype=np.uint8)
-        k = lib().lsnFusionOverlayDiagnostics(self._h, int(tick), _ptr(rep), _ptr(mer), _ptr(asg), stream or None)
-        if k < 0:
-            raise NativeUtilsError(f"lsnFusionOverlayDiagnostics failed: {last_error()}")
+        k = _nonneg(lib().lsnFusionOverlayDiagnostics(self._h, int(tick), _ptr(rep), _ptr(mer), _ptr(asg), stream or None), "lsnFusionOverlayDiagnostics")
         nv = int(self.capacity) if n_vertices is None else int(n_vertices)
         return {"reprojected": rep[:self.pixels_per_tick], "merged": mer[:self.pixels_per_tick], "assigned": asg[:nv].copy(), "n_assigned": k}
 
@@ -676,9 +561,7 @@ class FusionPlan:
         rps = np.zeros(max(self.n_maps, 1), dtype=np.int32)
         eps = np.zeros(max(self.n_maps, 1), dtype=np.int32)
         rem = np.zeros(max(int(self.capacity), 1), dtype=np.uint8)
-        k = lib().lsnFusionOutlierDiagnostics(self._h, int(tick), _ptr(rps), _ptr(rem), _ptr(eps), stream or None)
-        if k < 0:
-            raise NativeUtilsError(f"lsnFusionOutlierDiagnostics failed: {last_error()}")
+        k = _nonneg(lib().lsnFusionOutlierDiagnostics(self._h, int(tick), _ptr(rps), _ptr(rem), _ptr(eps), stream or None), "lsnFusionOutlierDiagnostics")
         nv = int(self.capacity) if n_vertices is None else int(n_vertices)
         return {"removed_per_sensor": rps[:self.n_maps].copy(), "removed": rem[:nv].copy(), "exact_per_sensor": eps[:self.n_maps].copy(),
                 "total": k}
@@ -692,9 +575,7 @@ class FusionPlan:
     def flying_diagnostics(self, tick=0, stream=0):
         """What the last flying_pixels() removed in one tick: (pixels of depth != 0 set to 0 per sensor int32[n], their sum)."""
         rps = np.zeros(max(self.n_maps, 1), dtype=np.int32)
-        k = lib().lsnFusionFlyingDiagnostics(self._h, int(tick), _ptr(rps), stream or None)
-        if k < 0:
-            raise NativeUtilsError(f"lsnFusionFlyingDiagnostics failed: {last_error()}")
+        k = _nonneg(lib().lsnFusionFlyingDiagnostics(self._h, int(tick), _ptr(rps), stream or None), "lsnFusionFlyingDiagnostics")
         return rps[:self.n_maps].copy(), k
 
     def thresholds(self, capacity=None, stream=0, copy=True):
@@ -702,9 +583,7 @@ class FusionPlan:
         the plan does not use thresholds ($LSN_NO_THRESHOLDS=1)."""
         out = np.zeros(int(capacity or self.capacity), dtype=np.uint32) if copy else None
         ms = C.c_float(0)
-        rc = lib().lsnFusionThresholds(self._h, _ptr(out) if copy else None, C.byref(ms), stream or None)
-        if rc < 0:
-            raise NativeUtilsError(f"lsnFusionThresholds failed: {last_error()}")
+        rc = _nonneg(lib().lsnFusionThresholds(self._h, _ptr(out) if copy else None, C.byref(ms), stream or None), "lsnFusionThresholds")
         return (None if rc == 1 else out), ms.value
 
     @property
@@ -754,17 +633,6 @@ class FusionPlan:
                "lsnFusionKernelStats")
         return {"kernel": name.value.decode(), "avg_ms": avg.value, "launches": n.value}
 
-    def close(self):
-        if self._h:
-            lib().lsnFusionDestroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 def merge_shards(device, n_shards, n_ticks, maps_per_shard, d_shards, shard_cap, d_shard_offsets, d_merged, merged_cap,
                  d_merged_offsets, stream=0):
@@ -787,8 +655,9 @@ def shard_unique_id():
     return bytes(buf)
 
 
-class Shard:
+class Shard(_Handle):
     """lsnShard*: this rank's block of sensors in, the merged cloud of all sensors out (RCCL all-gathers inside the library)."""
+    _destroy = "lsnShardDestroy"
 
     def __init__(self, device, rank, world, unique_id, n_ticks, widths, heights):
         """unique_id: rank 0's 128 bytes -> prepare + connect at once (lsnShardCreate); None -> lsnShardPrepare only, the caller
@@ -797,14 +666,11 @@ class Shard:
         w, h = _as(widths, np.int32), _as(heights, np.int32)
         self.n_ticks, self.n_maps, self.world, self.rank = int(n_ticks), len(w), int(world), int(rank)
         if unique_id is None:
-            self._h = lib().lsnShardPrepare(int(device), self.rank, self.world, self.n_ticks, self.n_maps, _ptr(w), _ptr(h))
-            what = "lsnShardPrepare"
+            self._h = _handle(lib().lsnShardPrepare(int(device), self.rank, self.world, self.n_ticks, self.n_maps, _ptr(w), _ptr(h)), "lsnShardPrepare")
         else:
             idb = (C.c_ubyte * 128).from_buffer_copy(bytes(unique_id))
-            self._h = lib().lsnShardCreate(int(device), self.rank, self.world, idb, self.n_ticks, self.n_maps, _ptr(w), _ptr(h))
-            what = "lsnShardCreate"
-        if not self._h:
-            raise NativeUtilsError(f"{what} failed: {last_error()}")
+            self._h = _handle(lib().lsnShardCreate(int(device), self.rank, self.world, idb, self.n_ticks, self.n_maps, _ptr(w), _ptr(h)),
+                              "lsnShardCreate")
         self.capacity = int(lib().lsnShardMergedCapacity(self._h))
 
     def connect(self, unique_id):
@@ -812,9 +678,7 @@ class Shard:
         _check(lib().lsnShardConnect(self._h, idb), "lsnShardConnect")
 
     def set_params(self, intr_all, wt_all, bounds, stream=0):
-        intr, wt, b = _as(intr_all, np.float32).ravel(), _as(wt_all, np.float32).ravel(), _as(bounds, np.float32).ravel()
-        assert intr.size == 7 * self.n_maps and wt.size == 12 * self.n_maps and b.size == 6
-        _check(lib().lsnShardSetParams(self._h, _ptr(intr), _ptr(wt), _ptr(b), stream), "lsnShardSetParams")
+        _set_params("lsnShardSetParams", self._h, self.n_maps, intr_all, wt_all, bounds, stream)
 
     def step(self, d_depth_local, d_colors_local, stream=0):
         """Returns (device pointer of the merged cloud [n_ticks][capacity] vertices, device pointer of its offsets [n_ticks][n_maps + 1])."""
@@ -833,42 +697,28 @@ class Shard:
         """A non-owning FusionPlan view of one of the handle's plans (profile / kernel_stats / check only)."""
         v = object.__new__(FusionPlan)
         v._h = lib().lsnShardPlan(self._h, 1 if whole else 0)
-        v.close = lambda: None
+        v.close = lambda: None   # (also what the view's __del__ calls: the handle stays the Shard's)
         return v
-
-    def close(self):
-        if self._h:
-            lib().lsnShardDestroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 NN_BRUTE, NN_GRID = 0, 1
 
 
-class TickPipeline:
+class TickPipeline(_Handle):
     """lsnTick*: the chained tick (radial correction out of place -> vertices -> triangulation) of n_ticks x n_maps frames in HBM as one call."""
+    _destroy = "lsnTickDestroy"
 
     def __init__(self, device, n_ticks, widths, heights):
         require_gpu()
         self.widths, self.heights = _as(widths, np.int32), _as(heights, np.int32)
         self.n_ticks, self.n_maps = int(n_ticks), len(self.widths)
-        self._h = lib().lsnTickCreate(int(device), self.n_ticks, self.n_maps, _ptr(self.widths), _ptr(self.heights))
-        if not self._h:
-            raise NativeUtilsError(f"lsnTickCreate failed: {last_error()}")
+        self._h = _handle(lib().lsnTickCreate(int(device), self.n_ticks, self.n_maps, _ptr(self.widths), _ptr(self.heights)), "lsnTickCreate")
         self.capacity = int(lib().lsnTickCapacity(self._h))
         self.tri_capacity = int(lib().lsnTickTriangleCapacity(self._h))
         self.parts = int(lib().lsnTickParts(self._h))
 
     def set_params(self, intr, wt, bounds, stream=0):
-        intr, wt, bounds = _as(intr, np.float32).ravel(), _as(wt, np.float32).ravel(), _as(bounds, np.float32).ravel()
-        assert intr.size == 7 * self.n_maps and wt.size == 12 * self.n_maps and bounds.size == 6
-        _check(lib().lsnTickSetParams(self._h, _ptr(intr), _ptr(wt), _ptr(bounds), stream), "lsnTickSetParams")
+        _set_params("lsnTickSetParams", self._h, self.n_maps, intr, wt, bounds, stream)
 
     def set_flying_pixels(self, neighbourhood, threshold):
         """The flying-pixel filter as the first stage of run() (neighbourhood <= 0: off): filter -> radial correction -> vertices ->
@@ -879,27 +729,15 @@ class TickPipeline:
         _check(lib().lsnTickRun(self._h, d_depth_in, d_colors_in, d_depth_corr, d_colors_corr, d_vertices, d_offsets, d_triangles, d_tri_offsets, stream),
                "lsnTickRun")
 
-    def close(self):
-        if self._h:
-            lib().lsnTickDestroy(self._h)
-            self._h = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class IcpWorkspace:
+class IcpWorkspace(_Handle):
     """lsnIcp*: device-resident ICP for clouds up to (max_n1, max_n2)."""
+    _destroy = "lsnIcpDestroy"
 
     def __init__(self, device, max_n1, max_n2):
         require_gpu()
         self.device = int(device)
-        self._h = lib().lsnIcpCreate(self.device, int(max_n1), int(max_n2))
-        if not self._h:
-            raise NativeUtilsError(f"lsnIcpCreate failed: {last_error()}")
+        self._h = _handle(lib().lsnIcpCreate(self.device, int(max_n1), int(max_n2)), "lsnIcpCreate")
 
     def run(self, d_verts1, n1, d_verts2, n2, d_R, d_t, max_iter=10, nn_mode=NN_GRID, stream=0):
         _check(lib().lsnIcpRun(self._h, d_verts1, int(n1), d_verts2, int(n2), d_R, d_t, int(max_iter), int(nn_mode), stream),
@@ -915,70 +753,41 @@ class IcpWorkspace:
     def profile(self, stream=0):
         """Milliseconds of the last profiled run(): {build, nn, match_reduce_solve, final_apply} (synchronises the stream)."""
         ms = np.zeros(4, dtype=np.float32)
-        if lib().lsnIcpProfile(self._h, _ptr(ms), stream) < 0:
-            raise NativeUtilsError(f"lsnIcpProfile failed: {last_error()}")
+        _nonneg(lib().lsnIcpProfile(self._h, _ptr(ms), stream), "lsnIcpProfile")
         return {"build": float(ms[0]), "nn": float(ms[1]), "match_reduce_solve": float(ms[2]), "final_apply": float(ms[3])}
 
     def near_resolved(self, stream=0):
         """Queries of the last voxel-grid NN step that the near path settled (diagnostic; synchronises the stream)."""
-        n = lib().lsnIcpNearResolved(self._h, stream)
-        if n < 0:
-            raise NativeUtilsError(f"lsnIcpNearResolved failed: {last_error()}")
+        n = _nonneg(lib().lsnIcpNearResolved(self._h, stream), "lsnIcpNearResolved")
         return int(n)
 
     def trace(self, max_iters, stream=0):
         out = np.zeros((max(max_iters, 1), 16), dtype=np.float32)
-        n = lib().lsnIcpTrace(self._h, _ptr(out), int(max_iters), stream)
-        if n < 0:
-            raise NativeUtilsError(f"lsnIcpTrace failed: {last_error()}")
+        n = _nonneg(lib().lsnIcpTrace(self._h, _ptr(out), int(max_iters), stream), "lsnIcpTrace")
         return out[:n]
-
-    def close(self):
-        if self._h:
-            lib().lsnIcpDestroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 # ----------------------------------------------------------------------------------------------------------
 # Part 3: wire / disk formats either side of the path
 # ----------------------------------------------------------------------------------------------------------
 
-class TransferPacker:
+class TransferPacker(_Handle):
     """LsnTransfer: builds the TransferSocket.SendFrame byte stream (TransferSocket.cs:50-104; chunks as
     TransferServer.cs:177-270) on the device."""
+    _destroy = "lsnTransferDestroy"
+    h = property(lambda self: self._h, doc="the LsnTransfer handle (None once closed)")
 
     def __init__(self, device, max_vertices, max_triangles):
         require_gpu()
-        self.h = lib().lsnTransferCreate(int(device), int(max_vertices), int(max_triangles))
-        if not self.h:
-            raise NativeUtilsError(f"lsnTransferCreate failed: {last_error()}")
+        self._h = _handle(lib().lsnTransferCreate(int(device), int(max_vertices), int(max_triangles)), "lsnTransferCreate")
 
     def pack(self, d_vertices, n_vertices, d_triangles, n_triangles, d_out, out_cap, stream=0):
-        n = lib().lsnTransferPack(self.h, d_vertices, int(n_vertices), d_triangles or None, int(n_triangles), d_out, int(out_cap), stream or None)
-        if n < 0:
-            raise NativeUtilsError(f"lsnTransferPack failed: {last_error()}")
+        n = _nonneg(lib().lsnTransferPack(self._h, d_vertices, int(n_vertices), d_triangles or None, int(n_triangles), d_out, int(out_cap), stream or None), "lsnTransferPack")
         return int(n)
 
     def last_path(self):
         """0 vertices only, 1 all chunks from one prefix sum, 2 chunk after chunk (lsnTransferLastPath)."""
-        return int(lib().lsnTransferLastPath(self.h))
-
-    def close(self):
-        if getattr(self, "h", None):
-            lib().lsnTransferDestroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        return int(lib().lsnTransferLastPath(self._h))
 
 
 def transfer_frame_bound(n_vertices, n_triangles):
@@ -991,22 +800,15 @@ def ply_binary_bytes(n_vertices, n_triangles):
 
 def ply_pack(device, d_vertices, n_vertices, d_triangles, n_triangles, d_out, out_cap, stream=0):
     require_gpu()
-    n = lib().lsnPlyPack(int(device), d_vertices, int(n_vertices), d_triangles or None, int(n_triangles), d_out, int(out_cap), stream or None)
-    if n < 0:
-        raise NativeUtilsError(f"lsnPlyPack failed: {last_error()}")
+    n = _nonneg(lib().lsnPlyPack(int(device), d_vertices, int(n_vertices), d_triangles or None, int(n_triangles), d_out, int(out_cap), stream or None), "lsnPlyPack")
     return int(n)
 
 
 def _last_mesh(fn, what):
     require_gpu()
-    cap = fn(None, 0)
-    if cap < 0:
-        raise NativeUtilsError(f"{what} failed: {last_error()}")
+    cap = _nonneg(fn(None, 0), what)
     out = np.zeros(cap, dtype=np.uint8)
-    n = fn(_ptr(out), cap)
-    if n < 0:
-        raise NativeUtilsError(f"{what} failed: {last_error()}")
-    return out[:n].tobytes()
+    return out[:_nonneg(fn(_ptr(out), cap), what)].tobytes()
 
 
 def last_mesh_transfer_frame():
@@ -1029,9 +831,7 @@ def frame_parse_header(header16):
     if buf.size != 16:
         raise NativeUtilsError("a frame header is 16 bytes")
     info = FrameInfo()
-    rc = lib().lsnFrameParseHeader(_ptr(buf), C.byref(info))
-    if rc < 0:
-        raise NativeUtilsError(f"lsnFrameParseHeader failed: {last_error()}")
+    rc = _nonneg(lib().lsnFrameParseHeader(_ptr(buf), C.byref(info)), "lsnFrameParseHeader")
     return None if rc == 1 else info
 
 
@@ -1049,9 +849,7 @@ def frame_decode(message):
     bodies = np.zeros(1 << 16, dtype=np.uint8)
     nb = C.c_int(0)
     payload = np.ascontiguousarray(msg[16:16 + info.payload_bytes])
-    bl = lib().lsnFrameDecode(_ptr(payload), info.payload_bytes, info.compressed, w, h, _ptr(depth), _ptr(rgb), _ptr(bodies), bodies.size, C.byref(nb))
-    if bl < 0:
-        raise NativeUtilsError(f"lsnFrameDecode failed: {last_error()}")
+    bl = _nonneg(lib().lsnFrameDecode(_ptr(payload), info.payload_bytes, info.compressed, w, h, _ptr(depth), _ptr(rgb), _ptr(bodies), bodies.size, C.byref(nb)), "lsnFrameDecode")
     return depth, rgb, bodies[:bl].tobytes(), nb.value
 
 
@@ -1061,10 +859,8 @@ def frame_encode(depth, rgb, bodies=None, compression_level=0):
     rgb = _as(rgb, np.uint8).reshape(h, w, 3)
     b = np.frombuffer(bodies, dtype=np.uint8) if bodies else None
     out = np.zeros(16 + 5 * w * h + (b.size if b is not None else 4) + 1024 + (w * h * 5) // 64, dtype=np.uint8)
-    n = lib().lsnFrameEncode(_ptr(depth), _ptr(rgb), w, h, _ptr(b) if b is not None else None, b.size if b is not None else 0,
-                             int(compression_level), _ptr(out), out.size)
-    if n < 0:
-        raise NativeUtilsError(f"lsnFrameEncode failed: {last_error()}")
+    n = _nonneg(lib().lsnFrameEncode(_ptr(depth), _ptr(rgb), w, h, _ptr(b) if b is not None else None, b.size if b is not None else 0,
+                                     int(compression_level), _ptr(out), out.size), "lsnFrameEncode")
     return out[:n].tobytes()
 
 
@@ -1087,7 +883,5 @@ def recording_frames(file_bytes):
 def recording_append(frame, timestamp_ms):
     f = np.frombuffer(bytes(frame), dtype=np.uint8)
     out = np.zeros(f.size + 96, dtype=np.uint8)
-    n = lib().lsnRecordingAppend(_ptr(out), out.size, _ptr(f) if f.size else None, f.size, int(timestamp_ms))
-    if n < 0:
-        raise NativeUtilsError(f"lsnRecordingAppend failed: {last_error()}")
+    n = _nonneg(lib().lsnRecordingAppend(_ptr(out), out.size, _ptr(f) if f.size else None, f.size, int(timestamp_ms)), "lsnRecordingAppend")
     return out[:n].tobytes()

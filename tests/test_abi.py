@@ -12,10 +12,61 @@ from livescan3d_amd import native, synth
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
+HEADER = os.path.join(ROOT, "include", "NativeUtils.h")
+
+
+def _kind(c_type):
+    """The kind of one C type as the header spells it (a parameter with its name, or a return type): p pointer, f float, q long long,
+    b bool, v void, i int."""
+    if "*" in c_type:
+        return "p"
+    for word, kind in (("float", "f"), ("long long", "q"), ("bool", "b"), ("void", "v")):
+        if re.search(rf"\b{word}\b", c_type):
+            return kind
+    assert re.search(r"\bint\b", c_type), c_type
+    return "i"
+
+
+def _header_prototypes(path=HEADER):
+    """The one parser of include/NativeUtils.h: {function name: (kind of the return value, [kind of every parameter])}."""
+    text = re.sub(r"/\*.*?\*/", "", open(path).read(), flags=re.S)
+    text = re.sub(r"//[^\n]*", "", text)
+    out = {}
+    for ret, name, params in re.findall(r"\b([A-Za-z_][A-Za-z0-9_ \*]*?)\b([A-Za-z_][A-Za-z0-9_]*)\s*\(([^;{}]*)\)\s*;", text):
+        ps = [p.strip() for p in params.replace("\n", " ").split(",") if p.strip()]
+        assert name not in out, name
+        out[name] = (_kind(ret), [] if ps == ["void"] else [_kind(p) for p in ps])
+    return out
+
+
 def _declared_functions():
-    text = open(os.path.join(ROOT, "include", "NativeUtils.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    return sorted(set(re.findall(r"\b([A-Za-z_][A-Za-z0-9_]*)\s*\([^;{}]*\)\s*;", text)))
+    return sorted(_header_prototypes())
+
+
+def _ctypes_kind(t):
+    """The kind (as _kind names them) of one entry of native's prototype table."""
+    if t is None:
+        return "v"
+    if t in (C.c_void_p, C.c_char_p) or issubclass(t, C._Pointer):
+        return "p"
+    return {C.c_float: "f", C.c_longlong: "q", C.c_bool: "b", C.c_int: "i"}[t]
+
+
+def test_prototype_table_agrees_with_the_header():
+    """native's prototype table is the one place the header's types are restated: for every function include/NativeUtils.h declares, the
+    kind (pointer, float, long long, bool, int, void) of the return value and of every parameter must be the table's -- a wrong one is a
+    crash inside the caller, not an error.  The table is also what lib() declares on the loaded library."""
+    header = _header_prototypes()
+    assert len(header) > 90 and header["ICP"] == ("f", ["p", "p", "i", "i", "p", "p", "i"])    # the parser reads what it should
+    assert header["generateMeshFromDepthMaps"] == ("v", ["i"] + ["p"] * 7 + ["b"] + ["f"] * 6 + ["b"])
+    assert set(native._PROTOTYPES) == set(header) == set(native.EXPORTS)
+    wrong = {name: (header[name], (_ctypes_kind(res), [_ctypes_kind(a) for a in args]))
+             for name, (res, args) in native._PROTOTYPES.items() if (_ctypes_kind(res), [_ctypes_kind(a) for a in args]) != header[name]}
+    assert not wrong, wrong
+    L = native.lib()
+    for name, (res, args) in native._PROTOTYPES.items():
+        f = getattr(L, name)
+        assert f.restype == res and list(f.argtypes) == list(args), name
 
 
 def test_library_exports_every_declared_symbol():
@@ -411,23 +462,15 @@ def test_host_upload_schedule_properties():
 
 
 _NULL_ARGS_SCRIPT = r"""
-import ctypes as C, re, sys
-sys.path.insert(0, {root!r})
+import sys
+sys.path[:0] = [{root!r}, {tests!r}]
 from livescan3d_amd import native
+from test_abi import _header_prototypes
 L = native.lib()
-text = re.sub(r"/\*.*?\*/", "", open({header!r}).read(), flags=re.S)
 n = 0
-for ret, name, params in re.findall(r"\b([A-Za-z_][A-Za-z0-9_ \*]*?)\b([A-Za-z_][A-Za-z0-9_]*)\s*\(([^;{{}}]*)\)\s*;", text):
-    ps = [p.strip() for p in params.replace("\n", " ").split(",") if p.strip()]
-    if ps == ["void"]:
-        ps = []
-    kinds = ["p" if "*" in p else "f" if re.search(r"\bfloat\b", p) else "q" if re.search(r"\blong long\b", p) else "b" if re.search(r"\bbool\b", p) else "i" for p in ps]
-    f = getattr(L, name)
-    f.argtypes = [dict(p=C.c_void_p, f=C.c_float, q=C.c_longlong, b=C.c_bool, i=C.c_int)[k] for k in kinds]
-    ret = ret.strip()
-    f.restype = C.c_void_p if "*" in ret else C.c_float if "float" in ret else C.c_longlong if "long long" in ret else None if ret == "void" else C.c_int
+for name, (_, kinds) in _header_prototypes().items():
     print(name, flush=True)
-    f(*[None if k == "p" else 0.0 if k == "f" else 0 for k in kinds])
+    getattr(L, name)(*[None if k == "p" else 0.0 if k == "f" else 0 for k in kinds])     # through native's own prototypes
     n += 1
 print("ALL", n)
 """
@@ -438,7 +481,7 @@ def test_every_export_survives_null_and_zero_arguments():
     none may crash the process -- a P/Invoke caller that passes a wrong handle gets an error, not an access violation."""
     import subprocess
     import sys as _sys
-    r = subprocess.run([_sys.executable, "-c", _NULL_ARGS_SCRIPT.format(root=ROOT, header=os.path.join(ROOT, "include", "NativeUtils.h"))],
+    r = subprocess.run([_sys.executable, "-c", _NULL_ARGS_SCRIPT.format(root=ROOT, tests=os.path.join(ROOT, "tests"))],
                        capture_output=True, text=True, timeout=300)
     lines = r.stdout.strip().splitlines()
     assert r.returncode == 0 and lines and lines[-1].startswith("ALL"), f"crashed in {lines[-1] if lines else '?'} (rc {r.returncode})\n{r.stderr[-1500:]}"
