@@ -88,6 +88,32 @@ void lsnCorrectAndGenerateMesh(int n_maps, unsigned char *depth_maps, unsigned c
                                float *intr_params, float *wtransform_params, Mesh *out_mesh, float minX, float minY, float minZ,
                                float maxX, float maxY, float maxZ, int write_back_corrected);
 
+/* Extension: LiveScanServer's "Refine calibration" (refineWorker_DoWork, LiveScanServer/MainWindowForm.cs:304-416, fed by
+ * KinectServer.GetLatestFrameVerticesOnly, KinectServer.cs:527-554) as ONE call.  Through the reference's exports that path is the radial
+ * export, n x generateVerticesFromDepthMap, a host loop that strips X, Y, Z out of the vertices (:318-327) and the ICP loop: every point
+ * crosses PCIe three times.  Here the frames (the arrays of generateMeshFromDepthMaps) go up once and the clouds never leave the device:
+ * all sensors are fused with the crop box, vertices only, into one merged cloud in HBM -- sensor i's block is byte for byte what
+ * generateVerticesFromDepthMap(..., i) returns at that moment, the outlier filter (lsnSetOutlierFilter) included -- the blocks are stripped
+ * to packed XYZ on the device and refined by lsnRefine's Gauss-Seidel loop.  Runs on the lane of the single-sensor calls and on ONE device,
+ * also under $LSN_HOST_DEVICES.
+ *   correct_radial  0: the frames are already corrected (the reference's order: CorrectRadialDistortionsForDepthMaps, then the vertices);
+ *                   != 0: the flying-pixel filter (lsnSetFlyingPixelFilter) and the radial correction run on the device first, as in
+ *                   lsnCorrectAndGenerateMesh.  The caller's frames are never written.
+ *   wtransform_refined (12 floats per sensor, packed as wtransform_params; may be wtransform_params itself; nullable) receives the world
+ *                   transforms after the pose composition of MainWindowForm.cs:382-410; camera_R (n x 9) / camera_t (n x 3), in/out,
+ *                   nullable, are updated like cameraPoses[i] (:394, :407); Rs_out / Ts_out as in lsnRefine.
+ *   clouds_out (room for sum(w * h) x 3 floats, nullable) / counts_out (n_maps ints, nullable) receive the refined clouds, sensor blocks in
+ *                   sensor order, and their point counts: they exist so that the call can be checked; LiveScanServer needs neither.
+ * Returns 0, also when there is nothing to refine (lsnRefine's rule: fewer than two sensors, a sensor with no vertex inside the crop box,
+ * n_refine_iters <= 0 or n_icp_iters <= 0): then Rs = I, Ts = 0, the poses are composed with those and the clouds come back unrefined.
+ * Returns -1 with the message set and NO output array touched on failure; without a HIP device that is what happens (no CPU path).
+ * It is NOT a mesh call: it returns no Mesh and leaves its lane without a "last mesh" -- lsnLastMesh* on a thread whose last call was this
+ * one report that no mesh is resident. */
+int lsnRefineFromDepthMaps(int n_maps, unsigned char *depth_maps, unsigned char *depth_colors, int *widths, int *heights,
+                           float *intr_params, float *wtransform_params, float minX, float minY, float minZ, float maxX, float maxY,
+                           float maxZ, int correct_radial, int n_refine_iters, int n_icp_iters, float *wtransform_refined,
+                           float *camera_R, float *camera_t, float *Rs_out, float *Ts_out, float *clouds_out, int *counts_out);
+
 /* Host-only (no device needed), for tests and for operators who want to see it: the upload schedule a merge call (radial = 0), a
  * call that starts with the radial correction and goes on to the fusion (radial = 1: lsnCorrectAndGenerateMesh) or the radial export alone
  * (radial = 2: depthMapAndColorSetRadialCorrection) follows for sensors [first, first + count) of these frames, written to buf
@@ -432,10 +458,40 @@ int lsnIcpNearest(LsnIcp *icp, const float *d_verts1, int n1, const float *d_ver
  * cloud, Rs[i], Ts[i], n_icp_iters), with every cloud resident in HBM for the whole pass.  clouds[i] = counts[i] x 3 floats
  * on the HOST, moved in place; world_R (n x 9) / world_t (n x 3), nullable, are updated like worldTransforms[i]
  * (:382-410, the C# loops as written); Rs_out (n x 9) / Ts_out (n x 3), nullable, receive the accumulated ICP poses.
- * The pass's device state (ICP workspace, cloud buffers, stream) is kept for the next call on the same device (grown when a
- * rig needs more); a pass that runs while another is in flight allocates its own and frees it again. */
+ * The pass's device state (ICP workspace, cloud buffers, stream) is kept for the next call on the same device, one state per device
+ * (grown when a rig needs more; lsnRefineRelease frees it); a pass that runs while another is in flight on the device allocates its own
+ * and frees it again.
+ * What stays on the device between passes, per device: the clouds (12 bytes per point), "all other sensors" (12 bytes per point less the
+ * smallest cloud), the seeds (4 bytes per point), the poses, and an ICP workspace for (all points but the smallest cloud, the largest
+ * cloud) -- 134.7 MB for 8 x 512x424 scene frames (858 708 points) and 86.0 MB for 3 x 96x80 (11 074 points), as lsnRefineRelease
+ * reported them: the workspace's grids' cell tables do not depend on the rig.
+ * There is no switch on this path: $LSN_REFINE_SEEDS, the A/B switch of the seeding between passes that the round 6 records mention, was
+ * retired with the other settled switches -- the seeds are always on; $LSN_ICP_NEAR / $LSN_ICP_NEAR_PTS (below) still apply. */
 int lsnRefine(int device, int n_sensors, float *const *clouds, const int *counts, int n_refine_iters, int n_icp_iters,
               float *world_R, float *world_t, float *Rs_out, float *Ts_out);
+
+/* The same pass for a cloud that is ALREADY resident: d_vertices / d_offsets are ONE tick's merged cloud (VertexC4ubV3f, 16-byte aligned) and
+ * its row of n_sensors + 1 offsets as lsnFusionRun wrote them -- for tick k of a plan pass d_vertices + k * capacity * 16 bytes and
+ * d_offsets + k * (n_sensors + 1).  Both are read only.  The call is ordered behind the work queued on `stream`, reads the offsets row
+ * back (one small copy that SYNCHRONISES `stream`) and is complete on return: its results are host arrays.  world_R / world_t in/out as in
+ * lsnRefine, camera_R / camera_t as in lsnRefineFromDepthMaps, all nullable; d_clouds_out (device, offsets[n_sensors] x 3 floats, nullable)
+ * receives the refined points, sensor blocks in sensor order.  Nothing to refine: as lsnRefineFromDepthMaps.  Returns 0, -1 on error. */
+int lsnRefineVertices(int device, int n_sensors, const void *d_vertices, const int *d_offsets, int n_refine_iters, int n_icp_iters,
+                      float *world_R, float *world_t, float *camera_R, float *camera_t, float *Rs_out, float *Ts_out, float *d_clouds_out,
+                      void *stream);
+
+/* Host-only (no device needed): the pose composition at the end of refineWorker_DoWork (MainWindowForm.cs:382-410) in f32, the C# loops
+ * as written -- including their in-place update of worldTransforms[i].R while later rows still read it.  Rs (n x 9) / Ts (n x 3) are the
+ * accumulated ICP poses; world_R (n x 9) / world_t (n x 3) and camera_R / camera_t are updated in place; either pair may be NULL (without
+ * the world pair the camera rotations stay as they are: :407 copies what :403 computed from the world rotation).  The one place the
+ * composition lives: lsnRefine, lsnRefineVertices and lsnRefineFromDepthMaps end with it.  Returns 0, -1 on bad arguments. */
+int lsnRefineComposePoses(int n, const float *Rs, const float *Ts, float *world_R, float *world_t, float *camera_R, float *camera_t);
+
+/* Frees what the refine passes keep on `device` (every device: device < 0); a pass in flight on that state ends first.  Returns the bytes
+ * of device memory released, 0 if nothing was held (no device is touched then), -1 on error.  The next pass allocates afresh.  Like
+ * every export that takes a device it makes that device the calling thread's current one (hipSetDevice) and does not switch back: after
+ * lsnRefineRelease(-1) the thread is on the last device whose state it freed. */
+long long lsnRefineRelease(int device);
 
 /* How many queries of the workspace's last voxel-grid NN step were settled by the near path (the walk over the cells around
  * a query whose bound is small; diagnostic, synchronises `stream`; -1 on error).  $LSN_ICP_NEAR (read by lsnIcpCreate):

@@ -383,6 +383,70 @@ extern "C" void depthMapAndColorSetRadialCorrection(int n_maps, unsigned char *d
     });
 }
 
+// LiveScanServer's "Refine calibration" as one call: the frames go up once, the clouds never leave the device.  The fusion runs on the
+// single-sensor lane -- the refine worker's lane, so the update worker's merge calls go on beside it -- and on that lane's device alone,
+// whatever $LSN_HOST_DEVICES says; the pass itself is icp.hip's (lsn::refine_cloud).  Every result is computed into scratch first: a call
+// that fails has touched none of the caller's arrays.
+extern "C" int lsnRefineFromDepthMaps(int n_maps, unsigned char *depth_maps, unsigned char *depth_colors, int *widths, int *heights,
+                                      float *intr_params, float *wtransform_params, float minX, float minY, float minZ, float maxX, float maxY,
+                                      float maxZ, int correct_radial, int n_refine_iters, int n_icp_iters, float *wtransform_refined,
+                                      float *camera_R, float *camera_t, float *Rs_out, float *Ts_out, float *clouds_out, int *counts_out)
+{
+    return lsn::guarded("lsnRefineFromDepthMaps", -1, [&]() {
+        lsn::clear_error();
+        if (n_maps <= 0 || !depth_maps || !depth_colors || !widths || !heights || !intr_params || !wtransform_params) {
+            lsn::set_error("lsnRefineFromDepthMaps: bad arguments");
+            return -1;
+        }
+        const float b[6] = {minX, minY, minZ, maxX, maxY, maxZ};
+        MeshCall call;
+        call.depth_maps = depth_maps;
+        call.depth_colors = depth_colors;
+        call.widths = widths;
+        call.heights = heights;
+        call.intr = intr_params;
+        call.wt = wtransform_params;
+        call.bounds6 = b;
+        call.count = n_maps;
+        call.radial = correct_radial != 0;
+        if (call.radial) flying_setting().current(call.fp_neighbourhood, call.fp_threshold);
+        outlier_setting().current(call.outlier_k, call.outlier_max_dist);
+        Ctx &c = ctx();
+        Lane &l = c.single;
+        std::lock_guard<std::mutex> g(l.mu);
+        if (ensure_ready(c)) return -1;
+        std::vector<int> offsets((size_t)n_maps + 1);
+        if (fuse_resident(c, l, call, offsets.data())) return -1;
+        const size_t cloud_bytes = sizeof(float) * 3 * (size_t)offsets[n_maps];
+        // the refined points come home through a pinned block of the pool (recycled call after call; the download runs as DMA into it)
+        struct Block {
+            Ctx &c;
+            void *p = nullptr;
+            explicit Block(Ctx &c_) : c(c_) {}
+            ~Block() { if (p) pinned_put(c, p); }
+        } home(c);
+        if (clouds_out && cloud_bytes > 0 && !(home.p = pinned_get(c, cloud_bytes))) return -1;
+        std::vector<float> Rt((size_t)n_maps * 12);
+        if (lsn::refine_cloud("lsnRefineFromDepthMaps", l.device, n_maps, l.d_out.p, offsets.data(), n_refine_iters, n_icp_iters, Rt.data(),
+                              static_cast<float *>(home.p), nullptr))
+            return -1;
+        // worldTransforms[i] = {t[3], R[3][3]} of wtransform_params: unpacked, composed, packed again
+        std::vector<float> world_R((size_t)n_maps * 9), world_t((size_t)n_maps * 3);
+        for (int i = 0; i < n_maps; i++) {
+            memcpy(world_t.data() + 3 * (size_t)i, wtransform_params + 12 * (size_t)i, 3 * sizeof(float));
+            memcpy(world_R.data() + 9 * (size_t)i, wtransform_params + 12 * (size_t)i + 3, 9 * sizeof(float));
+        }
+        lsn::refine_compose(n_maps, Rt.data(), world_R.data(), world_t.data(), camera_R, camera_t, Rs_out, Ts_out);
+        for (int i = 0; wtransform_refined && i < n_maps; i++) {
+            memcpy(wtransform_refined + 12 * (size_t)i, world_t.data() + 3 * (size_t)i, 3 * sizeof(float));
+            memcpy(wtransform_refined + 12 * (size_t)i + 3, world_R.data() + 9 * (size_t)i, 9 * sizeof(float));
+        }
+        if (home.p) memcpy(clouds_out, home.p, cloud_bytes);
+        for (int i = 0; counts_out && i < n_maps; i++) counts_out[i] = offsets[i + 1] - offsets[i];
+        return 0;
+    });
+}
+
 extern "C" Mesh * createMesh(void)
 {
     return lsn::guarded("createMesh", static_cast<Mesh *>(nullptr), [&]() -> Mesh * {

@@ -201,7 +201,10 @@ inline bool flying_on(int neighbourhood) { return neighbourhood >= 1; }
 int fuse_host(Ctx &c, Lane &l, const MeshCall &call, Mesh *out);
 void radial_host(Ctx &c, Lane &l, int n_maps, unsigned char *depth_maps, unsigned char *depth_colors, const int *widths, const int *heights,
                  const float *intr_params, int fp_neighbourhood = 0, int fp_threshold = 0);
-int materialize(Lane &l);                  // lsnLastMesh*: the mesh of the lane's last call in d_out / d_tri
+// The fusion of a call whose cloud stays on the device: vertices only (with the outlier filter if the call has it on) into l.d_out, final on
+// return, the tick's offset row (call.count + 1 ints) into `offsets`.  No mesh: the lane is left without a last one.
+int fuse_resident(Ctx &c, Lane &l, const MeshCall &call, int *offsets);
+int materialize(Lane &l);                // lsnLastMesh*: the mesh of the lane's last call in d_out / d_tri
 
 }  // namespace host
 }  // namespace lsn

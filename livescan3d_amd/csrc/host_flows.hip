@@ -385,6 +385,23 @@ struct PhaseTrace {
     }
 };
 
+// The corrected maps of group k go home in the runs of the upload schedule (>= 1 MiB each: a smaller pageable copy is staged through
+// a bounce buffer): every run whose last group is k.  Pageable destination: these copies keep the thread; on their own stream.
+int write_back_runs(Lane &l, size_t k, unsigned char *back_d, unsigned char *back_c)
+{
+    const size_t G = l.groups.size();
+    for (const Copy &cp : l.copies) {
+        size_t last = 0;   // the last group this run covers
+        for (size_t q = 0; q < G; q++)
+            if ((cp.colours ? l.groups[q].c_off : l.groups[q].d_off) < cp.dev_off + cp.bytes) last = q;
+        if (last != k) continue;
+        unsigned char *dst = (cp.colours ? back_c : back_d) + cp.src_off;
+        const char *src = (cp.colours ? l.d_colors2.as<char>() : l.d_depth2.as<char>()) + cp.dev_off;
+        LSN_HIP(hipMemcpyWithStream(dst, src, cp.bytes, hipMemcpyDeviceToHost, l.back));
+    }
+    return 0;
+}
+
 // Everything one merge / single-sensor / correct-and-merge call holds while it runs, and the steps its two flows share: the plan and
 // the upload schedule, the lane's device buffers, the pinned blocks that become Mesh::vertices / Mesh::triangles, the upload loop that
 // hands every group of sensors to the flow the moment its frames are on the device, the hand-over to the caller.
@@ -401,6 +418,7 @@ struct HostCall {
     long long cap = 0;
     void *host = nullptr, *host_tri = nullptr;
     bool back = false, committed = false;
+    bool goes_home = true;   // false: the cloud stays in the lane's HBM (fuse_resident) -- no vertex block is taken
     const char *run_d = nullptr, *run_c = nullptr;   // what the fusion and triangle launches read: the raw frames, or the corrected ones
     PhaseTrace tr;
 
@@ -451,8 +469,7 @@ struct HostCall {
         back = radial && call.back_d && call.back_c;
         // the mesh's host blocks, sized for the most the frames can give (recycled through the pool: the same blocks tick after tick);
         // capacity-sized because the first vertices leave before the count is known
-        host = pinned_get(c, (size_t)cap * sizeof(VertexC4ubV3f));
-        if (!host) return -1;
+        if (goes_home && !(host = pinned_get(c, (size_t)cap * sizeof(VertexC4ubV3f)))) return -1;
         if (!in_hbm && with_triangles && !(host_tri = pinned_get(c, (size_t)cap * 2 * 12))) return -1;
         l.h_off[count] = -1;       // the total: stored by the last tile of the last group
         l.h_off[count + 1] = 0;    // the look-back's give-up flag
@@ -509,6 +526,29 @@ struct HostCall {
                                call.with_triangles, l.h_off, group_end_mirror, host_out, l.stream);
     }
 
+    // The outlier filter on the tick's cloud in l.d_out, behind the groups' launches: the cloud is filtered per sensor where it lies
+    // (outlier.hip), the removed vertices' pixels become depth 0 in a copy of the maps, and the groups fuse again from that copy, which
+    // every later launch of the call reads.  The corrected maps a call writes back are the unmasked ones: they go home first.
+    int outlier_pass()
+    {
+        size_t dbytes = 0;
+        for (const Group &g : l.groups) dbytes += g.dbytes;
+        if (l.d_masked.reserve(dbytes + 16) ||
+            lsn::outlier_filter(plan, call.outlier_k, call.outlier_max_dist, run_d, l.d_out.p, l.d_off.as<int>(), l.d_masked.p, l.stream))
+            return -1;
+        if (back) {
+            LSN_HIP(hipStreamSynchronize(l.stream));   // every group's corrected maps are final
+            for (size_t k = 0; k < G; k++)
+                if (write_back_runs(l, k, call.back_d, call.back_c)) return -1;
+            LSN_HIP(hipStreamSynchronize(l.back));
+            back = false;
+        }
+        run_d = l.d_masked.as<char>();
+        for (size_t k = 0; k < G; k++)
+            if (fuse_group(k, l.groups[k], l.d_out.p, nullptr, false)) return -1;
+        return 0;
+    }
+
     // The counts the kernels left in the lane's pinned tables, read once the kernels' stream has drained; refused when the look-back gave
     // up or when they cannot be.
     int final_counts(int &nv, int &nt)
@@ -544,23 +584,6 @@ struct HostCall {
         tr.print();
     }
 };
-
-// The corrected maps of group k go home in the runs of the upload schedule (>= 1 MiB each: a smaller pageable copy is staged through
-// a bounce buffer): every run whose last group is k.  Pageable destination: these copies keep the thread; on their own stream.
-int write_back_runs(Lane &l, size_t k, unsigned char *back_d, unsigned char *back_c)
-{
-    const size_t G = l.groups.size();
-    for (const Copy &cp : l.copies) {
-        size_t last = 0;   // the last group this run covers
-        for (size_t q = 0; q < G; q++)
-            if ((cp.colours ? l.groups[q].c_off : l.groups[q].d_off) < cp.dev_off + cp.bytes) last = q;
-        if (last != k) continue;
-        unsigned char *dst = (cp.colours ? back_c : back_d) + cp.src_off;
-        const char *src = (cp.colours ? l.d_colors2.as<char>() : l.d_depth2.as<char>()) + cp.dev_off;
-        LSN_HIP(hipMemcpyWithStream(dst, src, cp.bytes, hipMemcpyDeviceToHost, l.back));
-    }
-    return 0;
-}
 
 // Flow 1: the kernels store the vertices and the triangles straight into the mesh's host blocks (file comment).
 int fuse_host_direct(HostCall &h, Mesh *out)
@@ -691,10 +714,8 @@ int fuse_host_grouped(HostCall &h, Mesh *out)
 // then the correction runs in place (color.hip), the merge rebuilds the triangles (merge.hip), and the mesh leaves in one copy.  Without
 // the merge the triangles do not depend on the colours; they are built as in flow 2.  The merge reads the positions alone, so the two
 // commute.
-// With the outlier filter on (`filter`: fuse_host decides) the tick's cloud is filtered per sensor where it lies (outlier.hip), the removed vertices'
-// pixels become depth 0 in a copy of the maps, and the groups fuse again from that copy: everything after -- triangles, colour transfer,
-// overlay merge -- is the call on the masked maps.  The corrected maps a call that starts with the radial correction
-// writes back are the unmasked ones.
+// With the outlier filter on (`filter`: fuse_host decides) the cloud is filtered first (HostCall::outlier_pass): everything after -- triangles,
+// colour transfer, overlay merge -- is the call on the masked maps.
 int fuse_host_color(HostCall &h, Mesh *out, bool filter)
 {
     Lane &l = h.l;
@@ -702,23 +723,7 @@ int fuse_host_color(HostCall &h, Mesh *out, bool filter)
     if (h.begin(true, 0)) return -1;
     const int count = call.count;
     if (h.upload([&](size_t k, const Group &g) -> int { return h.fuse_group(k, g, l.d_out.p, nullptr, false); })) return -1;
-    if (filter) {
-        size_t dbytes = 0;
-        for (const Group &g : l.groups) dbytes += g.dbytes;
-        if (l.d_masked.reserve(dbytes + 16) ||
-            lsn::outlier_filter(h.plan, call.outlier_k, call.outlier_max_dist, h.run_d, l.d_out.p, l.d_off.as<int>(), l.d_masked.p, l.stream))
-            return -1;
-        if (h.back) {
-            LSN_HIP(hipStreamSynchronize(l.stream));   // every group's corrected maps are final
-            for (size_t k = 0; k < h.G; k++)
-                if (write_back_runs(l, k, call.back_d, call.back_c)) return -1;
-            LSN_HIP(hipStreamSynchronize(l.back));
-            h.back = false;
-        }
-        h.run_d = l.d_masked.as<char>();
-        for (size_t k = 0; k < h.G; k++)
-            if (h.fuse_group(k, l.groups[k], l.d_out.p, nullptr, false)) return -1;
-    }
+    if (filter && h.outlier_pass()) return -1;
     if (call.with_triangles && !call.overlay_merge && lsn::run_triangles(h.plan, h.run_d, l.d_tri.p, l.d_tri_off.as<int>(), l.h_toff, false, l.stream))
         return -1;
     if (call.color_transfer && lsn::color_transfer(h.plan, h.run_d, l.d_out.p, l.d_off.as<int>(), l.stream)) return -1;
@@ -739,6 +744,28 @@ int fuse_host_color(HostCall &h, Mesh *out, bool filter)
     LSN_HIP(hipStreamSynchronize(l.stream));
     h.tr.mark("down");
     h.commit(out, nv, nt, true);
+    return 0;
+}
+
+// Flow 2c: the cloud stays in HBM (lsnRefineFromDepthMaps).  Vertices only; the groups fuse into d_out as in flow 2, the outlier filter
+// runs if the call has it on, and nothing goes home: no pinned block is taken, no download queued.  offsets (count + 1 ints) receives the
+// tick's offset row; on return the cloud in l.d_out is final.  It is no mesh call: the lane is left without a last mesh.
+int fuse_resident(Ctx &c, Lane &l, const MeshCall &call, int *offsets)
+{
+    HostCall h(c, l, call);
+    h.goes_home = false;
+    if (h.begin(true, 0)) return -1;
+    if (h.upload([&](size_t k, const Group &g) -> int { return h.fuse_group(k, g, l.d_out.p, nullptr, false); })) return -1;
+    if (call.outlier_k > 0 && call.outlier_max_dist > 0.0f && h.outlier_pass()) return -1;
+    if (hipStreamSynchronize(l.stream) != hipSuccess) {
+        lsn::set_error("NativeUtils: %s", hipGetErrorString(hipGetLastError()));
+        return -1;
+    }
+    int nv, nt;
+    if (h.final_counts(nv, nt)) return -1;
+    for (int i = 0; i <= call.count; i++) offsets[i] = l.h_off[i];
+    l.forget_last();
+    h.committed = true;   // nothing is in flight and no block was taken
     return 0;
 }
 

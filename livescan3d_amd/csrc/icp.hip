@@ -36,6 +36,8 @@
 #include "lsn_common.hpp"
 
 #include <algorithm>
+#include <cstdint>
+#include <map>
 #include <mutex>
 #include <vector>
 
@@ -1675,6 +1677,7 @@ struct GridBufs {
         }
         return bad;
     }
+    size_t bytes() const { return gp.bytes + cell_of.bytes + rank_of.bytes + cell_cnt.bytes + cell_start.bytes + sorted.bytes + boxes.bytes + supers.bytes; }
 };
 
 struct LsnIcp {
@@ -1696,6 +1699,11 @@ struct LsnIcp {
     int near_pts = 128;    // the near path's candidate cap per query (<= kNearCapMax); $LSN_ICP_NEAR=0 turns the path off (A/B, tests), $LSN_ICP_NEAR_PTS sets the cap
     int last_groups = 0;   // query groups of the last grid NN step (lsnIcpNearResolved)
     std::mutex mu;
+    size_t bytes() const   // device memory the workspace holds (lsnRefineRelease reports it)
+    {
+        return tgt.bytes() + src.bytes() + bbox_part.bytes + block_sums.bytes + idx.bytes + dist.bytes + keys.bytes + counters.bytes + part1.bytes +
+               part3.bytes + state.bytes + trace.bytes + best_key.bytes + groups.bytes + list_a.bytes + list_b.bytes + idx_sorted.bytes;
+    }
 };
 
 static constexpr int kTraceCap = 1024;
@@ -2059,17 +2067,20 @@ extern "C" int lsnIcpTrace(LsnIcp *w, float *out, int max_iters, void *stream)
     });
 }
 
+#include "refine_xyz.hip"   // xyz_of_vertices: a merged cloud's vertices as the packed points the pass below works on
+
 // refineWorker_DoWork (LiveScanServer/MainWindowForm.cs:330-410) with every cloud resident in HBM for the whole
 // Gauss-Seidel loop: the reference re-uploads "all other sensors" and the sensor's own cloud for each of the
-// n_sensors x n_refine_iters ICP calls; here each cloud goes up once and comes back once.  The pose composition at the
-// end repeats the C# loops literally, including their in-place update of worldTransforms[i].R while later rows still
-// read it (:398-406).
+// n_sensors x n_refine_iters ICP calls; here each cloud goes up once and comes back once -- or never leaves the device at all
+// (lsnRefineVertices, lsnRefineFromDepthMaps).  The pose composition at the end repeats the C# loops literally, including
+// their in-place update of worldTransforms[i].R while later rows still read it (:398-406).
 struct RefineState {   // what a refine pass keeps on the device between calls
     std::mutex mu;
     int device = -1;
     LsnIcp *ws = nullptr;
     hipStream_t s = nullptr;
     lsn::DevBuf d_all, d_others, d_Rt, d_seeds;
+    long long bytes() const { return (long long)(d_all.bytes + d_others.bytes + d_Rt.bytes + d_seeds.bytes + (ws ? ws->bytes() : 0)); }
     void drop()
     {
         if (device >= 0) (void)hipSetDevice(device);
@@ -2082,10 +2093,196 @@ struct RefineState {   // what a refine pass keeps on the device between calls
     ~RefineState() { drop(); }
 };
 
-static RefineState &refine_state()
+// The kept states, one per device (lsnRefineRelease frees them).  Never destroyed: no HIP calls from static destructors at process exit.
+struct RefineStates {
+    std::mutex mu;
+    std::map<int, RefineState *> of_device;
+};
+
+static RefineStates &refine_states()
 {
-    static RefineState *st = new RefineState();   // never destroyed: no HIP calls from static destructors at process exit
+    static RefineStates *all = new RefineStates();
+    return *all;
+}
+
+static RefineState &refine_state(int device)
+{
+    RefineStates &all = refine_states();
+    std::lock_guard<std::mutex> g(all.mu);
+    RefineState *&st = all.of_device[device];
+    if (!st) st = new RefineState();
     return *st;
+}
+
+// The Gauss-Seidel loop (:347-376) on clouds that are resident: rs.d_all holds every sensor's current cloud, sensor i's counts[i] points at
+// 3 * off[i] floats, and rs.d_Rt its accumulated pose {R[9], t[3]} at 12 * i.  Everything is queued on rs.s; nothing is waited for.
+// 0, or non-zero with the message set or a HIP error pending.
+static int refine_gauss_seidel(const char *who, RefineState &rs, int n_sensors, const int *counts, const long long *off, int n_refine_iters,
+                               int n_icp_iters)
+{
+    hipStream_t s = rs.s;
+    LsnIcp *ws = rs.ws;
+    lsn::DevBuf &d_all = rs.d_all, &d_others = rs.d_others, &d_Rt = rs.d_Rt, &d_seeds = rs.d_seeds;
+    const long long total = off[n_sensors];
+    int rc = 0;
+    for (int it = 0; it < n_refine_iters && !rc; it++) {                  // :347
+        for (int i = 0; i < n_sensors && !rc; i++) {                      // :349
+            // :352-357 all other sensors' current clouds, in sensor order = everything before sensor i's block and everything behind it: two copies
+            const long long pos = total - counts[i];
+            if (off[i] > 0)
+                rc = hipMemcpyAsync(d_others.as<float>(), d_all.as<float>(), sizeof(float) * 3 * (size_t)off[i], hipMemcpyDeviceToDevice, s) != hipSuccess;
+            if (!rc && off[i + 1] < total)
+                rc = hipMemcpyAsync(d_others.as<float>() + 3 * off[i], d_all.as<float>() + 3 * off[i + 1], sizeof(float) * 3 * (size_t)(total - off[i + 1]),
+                                    hipMemcpyDeviceToDevice, s) != hipSuccess;
+            // From the second pass on the first NN step of a call is seeded with the neighbours the sensor's call of the previous pass ended
+            // with ("all other sensors" is the same concatenation in every pass, so the indices still name real points; the others have moved a
+            // little, which only makes the seeds a little less tight): ~65 us instead of ~150 for that step, same result (14.23-14.38 ->
+            // 13.98-14.07 ms per call, same digest).
+            if (!rc)
+                rc = lsn::guarded(who, -1, [&]() {
+                    return icp_run(ws, d_others.as<float>(), (int)pos, d_all.as<float>() + 3 * off[i], counts[i], d_Rt.as<float>() + 12 * i,
+                                   d_Rt.as<float>() + 12 * i + 9, n_icp_iters, 1, s,
+                                   it > 0 ? d_seeds.as<int>() + off[i] : (const int *)nullptr);     // :370
+                });
+            if (!rc && it + 1 < n_refine_iters)
+                rc = hipMemcpyAsync(d_seeds.as<int>() + off[i], ws->idx.p, sizeof(int) * (size_t)counts[i], hipMemcpyDeviceToDevice, s) != hipSuccess;
+        }
+    }
+    return rc;
+}
+
+// What a pass is, by its clouds' sizes: off[i] = first point of sensor i, off[n_sensors] = all points.  `runnable` is the rule of every refine
+// export: at least two sensors, none of them empty, at least one pass of at least one ICP iteration (MainWindowForm.cs:469-473 guards the
+// same way; ICP on an empty cloud would throw out of nanoflann in the reference).
+struct RefineShape {
+    std::vector<long long> off;
+    long long total = 0;
+    int max_n = 0, min_n = 0x7FFFFFFF;
+    bool runnable = false;
+    RefineShape(int n_sensors, const int *counts, int n_refine_iters, int n_icp_iters) : off((size_t)n_sensors + 1, 0)
+    {
+        for (int i = 0; i < n_sensors; i++) {
+            off[i + 1] = off[i] + counts[i];
+            max_n = counts[i] > max_n ? counts[i] : max_n;
+            min_n = counts[i] < min_n ? counts[i] : min_n;
+        }
+        total = off[n_sensors];
+        runnable = n_sensors >= 2 && min_n > 0 && total - min_n <= 0x7FFFFFFFll && n_refine_iters > 0 && n_icp_iters > 0;
+    }
+};
+
+// One pass on `device`, on the device's kept state: fill(rs, off) queues on rs.s whatever brings the clouds into rs.d_all; the Gauss-Seidel
+// loop runs if the shape is runnable; drain(rs) queues the copies that take the clouds wherever the caller wants them; Rt (n_sensors x 12,
+// handed in as {I, 0}) receives the accumulated poses.  Complete on return.  -1: the message is set and nothing of the pass is kept.
+template <class Fill, class Drain>
+static int refine_pass(const char *who, int device, int n_sensors, const int *counts, const RefineShape &shape, int n_refine_iters, int n_icp_iters,
+                       float *Rt, Fill &&fill, Drain &&drain)
+{
+    const long long total = shape.total;
+    const size_t rt_bytes = sizeof(float) * 12 * (size_t)n_sensors;
+    LSN_HIP(hipSetDevice(device));
+    // the pass's device state (workspace, cloud buffers, stream) is kept between calls: allocating it was 2-3 ms of a 20 ms pass.
+    // A second pass running at the same time on the device gets a state of its own.
+    RefineState *rs = &refine_state(device);
+    std::unique_lock<std::mutex> hold(rs->mu, std::try_to_lock);
+    RefineState own;
+    if (!hold.owns_lock()) rs = &own;
+    int rc = 0;
+    if (shape.runnable) {
+        const int need1 = (int)(total - shape.min_n), need2 = shape.max_n;
+        if (rs->ws && (rs->ws->max_n1 < need1 || rs->ws->max_n2 < need2)) rs->drop();
+        if (!rs->ws) rs->ws = lsnIcpCreate(device, need1, need2);
+        rc = rs->ws ? 0 : -1;
+    }
+    rs->device = device;
+    if (!rc && !rs->s) rc = hipStreamCreateWithFlags(&rs->s, hipStreamNonBlocking) != hipSuccess;
+    hipStream_t s = rs->s;
+    if (!rc) rc = rs->d_all.reserve(sizeof(float) * 3 * (size_t)total);
+    if (!rc && shape.runnable)
+        rc = rs->d_others.reserve(sizeof(float) * 3 * (size_t)(total - shape.min_n)) || rs->d_Rt.reserve(rt_bytes) ||
+             rs->d_seeds.reserve(sizeof(int) * (size_t)total);
+    // (allocated before anything is queued: once a copy into host memory is in flight nothing below may throw before the synchronise)
+    std::vector<float> Rt_back(shape.runnable ? 12 * (size_t)n_sensors : 0);
+    if (!rc) rc = fill(*rs, shape.off.data());
+    if (!rc && shape.runnable) {
+        rc = hipMemcpyAsync(rs->d_Rt.p, Rt, rt_bytes, hipMemcpyHostToDevice, s) != hipSuccess;
+        if (!rc) rc = refine_gauss_seidel(who, *rs, n_sensors, counts, shape.off.data(), n_refine_iters, n_icp_iters);
+    }
+    // results land in scratch first: the caller's arrays are only touched when everything worked
+    if (!rc) rc = drain(*rs);
+    if (!rc && shape.runnable) rc = hipMemcpyAsync(Rt_back.data(), rs->d_Rt.p, rt_bytes, hipMemcpyDeviceToHost, s) != hipSuccess;
+    if (!rc && s) rc = hipStreamSynchronize(s) != hipSuccess;
+    if (rc) {
+        if (!lsn::has_error()) lsn::set_error("%s: %s", who, hipGetErrorString(hipGetLastError()));
+        if (s) (void)hipStreamSynchronize(s);
+        rs->drop();   // nothing of a failed pass is kept
+        return -1;
+    }
+    if (shape.runnable) memcpy(Rt, Rt_back.data(), rt_bytes);
+    return 0;
+}
+
+static void identity_poses(std::vector<float> &Rt, int n_sensors)
+{
+    Rt.assign((size_t)n_sensors * 12, 0.0f);
+    for (int i = 0; i < n_sensors; i++)
+        for (int j = 0; j < 3; j++) Rt[(size_t)i * 12 + j + j * 3] = 1.0f;   // Rs[i] = I, Ts[i] = 0 (:330-344)
+}
+
+// :382-410 pose composition, the C# loops as written (f32, every product rounded before it is added: the build keeps contraction off).
+// The rows of worldTransforms[i].R are overwritten while later rows still read it (:398-406), so the result is not Rs^T * R unless R is
+// orthogonal to the last bit -- the reference's behaviour, kept.  Rs / Ts: pose i at Rs + stride_R * i / Ts + stride_T * i.
+// A null world pair leaves the camera rotations alone (:407 copies what :403 computed from the world rotation); the camera translations
+// (:394) need the ICP translations only.
+static void compose_poses(int n, const float *Rs, int stride_R, const float *Ts, int stride_T, float *world_R, float *world_t, float *camera_R,
+                          float *camera_t)
+{
+    const bool world = world_R && world_t, camera = camera_R && camera_t;
+    for (int i = 0; i < n; i++) {
+        const float *Ri = Rs + (size_t)stride_R * i, *Ti = Ts + (size_t)stride_T * i;
+        if (world) {
+            float *WR = world_R + 9 * i, *Wt = world_t + 3 * i;
+            float tempT[3] = {0, 0, 0};
+            for (int j = 0; j < 3; j++) {
+                for (int k = 0; k < 3; k++) tempT[j] += Ti[k] * WR[3 * k + j];
+                Wt[j] += tempT[j];
+            }
+        }
+        if (camera)
+            for (int j = 0; j < 3; j++) camera_t[3 * i + j] += Ti[j];   // :394
+        if (world) {
+            float *WR = world_R + 9 * i;
+            float tempR[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+            for (int j = 0; j < 3; j++)
+                for (int k = 0; k < 3; k++) {
+                    for (int l = 0; l < 3; l++) tempR[3 * j + k] += Ri[l * 3 + j] * WR[3 * l + k];
+                    WR[3 * j + k] = tempR[3 * j + k];
+                    if (camera) camera_R[9 * i + 3 * j + k] = tempR[3 * j + k];   // :407
+                }
+        }
+    }
+}
+
+void lsn::refine_compose(int n, const float *Rt, float *world_R, float *world_t, float *camera_R, float *camera_t, float *Rs_out, float *Ts_out)
+{
+    compose_poses(n, Rt, 12, Rt + 9, 12, world_R, world_t, camera_R, camera_t);
+    for (int i = 0; i < n; i++) {
+        if (Rs_out) memcpy(Rs_out + 9 * i, Rt + 12 * (size_t)i, 9 * sizeof(float));
+        if (Ts_out) memcpy(Ts_out + 3 * i, Rt + 12 * (size_t)i + 9, 3 * sizeof(float));
+    }
+}
+
+extern "C" int lsnRefineComposePoses(int n, const float *Rs, const float *Ts, float *world_R, float *world_t, float *camera_R, float *camera_t)
+{
+    return lsn::guarded("lsnRefineComposePoses", -1, [&]() {
+        lsn::clear_error();
+        if (n <= 0 || !Rs || !Ts) {
+            lsn::set_error("lsnRefineComposePoses: bad arguments");
+            return -1;
+        }
+        compose_poses(n, Rs, 9, Ts, 3, world_R, world_t, camera_R, camera_t);
+        return 0;
+    });
 }
 
 extern "C" int lsnRefine(int device, int n_sensors, float *const *clouds, const int *counts, int n_refine_iters, int n_icp_iters,
@@ -2097,105 +2294,116 @@ extern "C" int lsnRefine(int device, int n_sensors, float *const *clouds, const 
             lsn::set_error("lsnRefine: bad arguments");
             return -1;
         }
-        long long total = 0;
-        int max_n = 0, min_n = 0x7FFFFFFF;
         for (int i = 0; i < n_sensors; i++) {
             if (counts[i] < 0 || (counts[i] > 0 && !clouds[i])) {
                 lsn::set_error("lsnRefine: bad cloud %d", i);
                 return -1;
             }
-            total += counts[i];
-            max_n = counts[i] > max_n ? counts[i] : max_n;
-            min_n = counts[i] < min_n ? counts[i] : min_n;
         }
-        std::vector<float> Rt((size_t)n_sensors * 12, 0.0f);
-        for (int i = 0; i < n_sensors; i++)
-            for (int j = 0; j < 3; j++) Rt[(size_t)i * 12 + j + j * 3] = 1.0f;   // Rs[i] = I, Ts[i] = 0 (:330-344)
-        const bool runnable = n_sensors >= 2 && min_n > 0 && total - min_n <= 0x7FFFFFFFll && n_refine_iters > 0 && n_icp_iters > 0;
-        if (runnable) {
-            LSN_HIP(hipSetDevice(device));
-            // the pass's device state (workspace, cloud buffers, stream) is kept between calls: allocating it was 2-3 ms of a 20 ms pass.
-            // A second pass running at the same time gets a state of its own.
-            RefineState *rs = &refine_state();
-            std::unique_lock<std::mutex> hold(rs->mu, std::try_to_lock);
-            RefineState own;
-            if (!hold.owns_lock()) rs = &own;
-            const int need1 = (int)(total - min_n), need2 = max_n;
-            if (rs->ws && (rs->device != device || rs->ws->max_n1 < need1 || rs->ws->max_n2 < need2)) rs->drop();
-            if (!rs->ws) {
-                rs->device = device;
-                rs->ws = lsnIcpCreate(device, need1, need2);
-            }
-            int rc = rs->ws ? 0 : -1;
-            if (!rc && !rs->s) rc = hipStreamCreateWithFlags(&rs->s, hipStreamNonBlocking) != hipSuccess;
-            hipStream_t s = rs->s;
-            LsnIcp *ws = rs->ws;
-            lsn::DevBuf &d_all = rs->d_all, &d_others = rs->d_others, &d_Rt = rs->d_Rt, &d_seeds = rs->d_seeds;
-            if (!rc) rc = d_all.reserve(sizeof(float) * 3 * (size_t)total) || d_others.reserve(sizeof(float) * 3 * (size_t)(total - min_n)) ||
-                          d_Rt.reserve(sizeof(float) * Rt.size()) || d_seeds.reserve(sizeof(int) * (size_t)total);
-            std::vector<long long> off(n_sensors + 1, 0);
-            for (int i = 0; i < n_sensors; i++) off[i + 1] = off[i] + counts[i];
-            for (int i = 0; i < n_sensors && !rc; i++)
-                rc = hipMemcpyAsync(d_all.as<float>() + 3 * off[i], clouds[i], sizeof(float) * 3 * (size_t)counts[i], hipMemcpyHostToDevice, s) != hipSuccess;
-            if (!rc) rc = hipMemcpyAsync(d_Rt.p, Rt.data(), sizeof(float) * Rt.size(), hipMemcpyHostToDevice, s) != hipSuccess;
-            for (int it = 0; it < n_refine_iters && !rc; it++) {                  // :347
-                for (int i = 0; i < n_sensors && !rc; i++) {                      // :349
-                    // :352-357 all other sensors' current clouds, in sensor order = everything before sensor i's block and everything behind it: two copies
-                    const long long pos = total - counts[i];
-                    if (off[i] > 0)
-                        rc = hipMemcpyAsync(d_others.as<float>(), d_all.as<float>(), sizeof(float) * 3 * (size_t)off[i], hipMemcpyDeviceToDevice, s) != hipSuccess;
-                    if (!rc && off[i + 1] < total)
-                        rc = hipMemcpyAsync(d_others.as<float>() + 3 * off[i], d_all.as<float>() + 3 * off[i + 1], sizeof(float) * 3 * (size_t)(total - off[i + 1]),
-                                            hipMemcpyDeviceToDevice, s) != hipSuccess;
-                    // From the second pass on the first NN step of a call is seeded with the neighbours the sensor's call of the previous pass ended
-                    // with ("all other sensors" is the same concatenation in every pass, so the indices still name real points; the others have moved a
-                    // little, which only makes the seeds a little less tight): ~65 us instead of ~150 for that step, same result (14.23-14.38 ->
-                    // 13.98-14.07 ms per call, same digest).
-                    if (!rc)
-                        rc = lsn::guarded("lsnRefine", -1, [&]() {
-                            return icp_run(ws, d_others.as<float>(), (int)pos, d_all.as<float>() + 3 * off[i], counts[i], d_Rt.as<float>() + 12 * i,
-                                           d_Rt.as<float>() + 12 * i + 9, n_icp_iters, 1, s,
-                                           it > 0 ? d_seeds.as<int>() + off[i] : (const int *)nullptr);     // :370
-                        });
-                    if (!rc && it + 1 < n_refine_iters)
-                        rc = hipMemcpyAsync(d_seeds.as<int>() + off[i], ws->idx.p, sizeof(int) * (size_t)counts[i], hipMemcpyDeviceToDevice, s) != hipSuccess;
-                }
-            }
-            // results land in scratch first: the caller's arrays are only touched when everything worked
-            std::vector<float> back((size_t)total * 3);
-            if (!rc) rc = hipMemcpyAsync(back.data(), d_all.p, sizeof(float) * 3 * (size_t)total, hipMemcpyDeviceToHost, s) != hipSuccess;
-            if (!rc) rc = hipMemcpyAsync(Rt.data(), d_Rt.p, sizeof(float) * Rt.size(), hipMemcpyDeviceToHost, s) != hipSuccess;
-            if (!rc && s) rc = hipStreamSynchronize(s) != hipSuccess;
-            if (rc) {
-                if (!lsn::has_error()) lsn::set_error("lsnRefine: %s", hipGetErrorString(hipGetLastError()));
-                if (s) (void)hipStreamSynchronize(s);
-                rs->drop();   // nothing of a failed pass is kept
-                return -1;
-            }
-            for (int i = 0; i < n_sensors; i++) memcpy(clouds[i], back.data() + 3 * off[i], sizeof(float) * 3 * (size_t)counts[i]);
+        const RefineShape shape(n_sensors, counts, n_refine_iters, n_icp_iters);
+        std::vector<float> Rt;
+        identity_poses(Rt, n_sensors);
+        if (shape.runnable) {
+            std::vector<float> back((size_t)shape.total * 3);   // before the pass: nothing may throw between the queued download and its synchronise
+            const int rc = refine_pass(
+                "lsnRefine", device, n_sensors, counts, shape, n_refine_iters, n_icp_iters, Rt.data(),
+                [&](RefineState &rs, const long long *off) -> int {
+                    int bad = 0;
+                    for (int i = 0; i < n_sensors && !bad; i++)
+                        bad = hipMemcpyAsync(rs.d_all.as<float>() + 3 * off[i], clouds[i], sizeof(float) * 3 * (size_t)counts[i], hipMemcpyHostToDevice, rs.s) != hipSuccess;
+                    return bad;
+                },
+                [&](RefineState &rs) -> int {
+                    return hipMemcpyAsync(back.data(), rs.d_all.p, sizeof(float) * 3 * (size_t)shape.total, hipMemcpyDeviceToHost, rs.s) != hipSuccess;
+                });
+            if (rc) return -1;
+            for (int i = 0; i < n_sensors; i++) memcpy(clouds[i], back.data() + 3 * shape.off[i], sizeof(float) * 3 * (size_t)counts[i]);
         }
-        // :382-410 pose composition, the C# loops as written
-        if (world_R && world_t) {
-            for (int i = 0; i < n_sensors; i++) {
-                float *WR = world_R + 9 * i, *Wt = world_t + 3 * i;
-                const float *Ri = Rt.data() + 12 * (size_t)i, *Ti = Ri + 9;
-                float tempT[3] = {0, 0, 0};
-                float tempR[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-                for (int j = 0; j < 3; j++) {
-                    for (int k = 0; k < 3; k++) tempT[j] += Ti[k] * WR[3 * k + j];
-                    Wt[j] += tempT[j];
-                }
-                for (int j = 0; j < 3; j++)
-                    for (int k = 0; k < 3; k++) {
-                        for (int l = 0; l < 3; l++) tempR[3 * j + k] += Ri[l * 3 + j] * WR[3 * l + k];
-                        WR[3 * j + k] = tempR[3 * j + k];
-                    }
-            }
-        }
-        for (int i = 0; i < n_sensors; i++) {
-            if (Rs_out) memcpy(Rs_out + 9 * i, Rt.data() + 12 * (size_t)i, 9 * sizeof(float));
-            if (Ts_out) memcpy(Ts_out + 3 * i, Rt.data() + 12 * (size_t)i + 9, 3 * sizeof(float));
-        }
+        lsn::refine_compose(n_sensors, Rt.data(), world_R, world_t, nullptr, nullptr, Rs_out, Ts_out);
         return 0;
+    });
+}
+
+// The pass on ONE tick's merged cloud that is resident on `device` and final (nothing that writes it is still in flight): the vertices are
+// stripped to points (refine_xyz.hip), refined where they lie, and leave as the caller asks -- h_clouds (host, nullable) and d_clouds
+// (device, nullable) each receive offsets[n_sensors] - offsets[0] points, sensor blocks in sensor order.  offsets: the tick's row on the
+// HOST.  Rt: n_sensors x 12, receives {Rs[i], Ts[i]} ({I, 0} when the shape is not runnable: then the clouds leave as they came).
+int lsn::refine_cloud(const char *who, int device, int n_sensors, const void *d_vertices, const int *offsets, int n_refine_iters, int n_icp_iters,
+                      float *Rt, float *h_clouds, float *d_clouds)
+{
+    std::vector<int> counts((size_t)n_sensors);
+    bool bad = offsets[0] < 0;
+    for (int i = 0; i < n_sensors; i++) {
+        bad |= offsets[i + 1] < offsets[i];
+        counts[i] = offsets[i + 1] - offsets[i];
+    }
+    if (bad) {
+        lsn::set_error("%s: the offsets row is not one a fusion wrote (it must start at >= 0 and never decrease)", who);
+        return -1;
+    }
+    const RefineShape shape(n_sensors, counts.data(), n_refine_iters, n_icp_iters);
+    std::vector<float> poses;
+    identity_poses(poses, n_sensors);
+    const size_t cloud_bytes = sizeof(float) * 3 * (size_t)shape.total;
+    const int rc = refine_pass(
+        who, device, n_sensors, counts.data(), shape, n_refine_iters, n_icp_iters, poses.data(),
+        [&](RefineState &rs, const long long *) -> int {
+            return xyz_of_vertices(static_cast<const char *>(d_vertices) + (size_t)offsets[0] * sizeof(VertexC4ubV3f), rs.d_all.as<float>(), (int)shape.total, rs.s);
+        },
+        [&](RefineState &rs) -> int {
+            if (cloud_bytes == 0) return 0;
+            if (h_clouds && hipMemcpyAsync(h_clouds, rs.d_all.p, cloud_bytes, hipMemcpyDeviceToHost, rs.s) != hipSuccess) return 1;
+            if (d_clouds && hipMemcpyAsync(d_clouds, rs.d_all.p, cloud_bytes, hipMemcpyDeviceToDevice, rs.s) != hipSuccess) return 1;
+            return 0;
+        });
+    if (rc) return -1;
+    memcpy(Rt, poses.data(), sizeof(float) * poses.size());
+    return 0;
+}
+
+extern "C" int lsnRefineVertices(int device, int n_sensors, const void *d_vertices, const int *d_offsets, int n_refine_iters, int n_icp_iters,
+                                 float *world_R, float *world_t, float *camera_R, float *camera_t, float *Rs_out, float *Ts_out,
+                                 float *d_clouds_out, void *stream)
+{
+    return lsn::guarded("lsnRefineVertices", -1, [&]() {
+        lsn::clear_error();
+        // (the strip kernel loads a vertex as one 16-byte word)
+        if (n_sensors <= 0 || !d_vertices || !d_offsets || (reinterpret_cast<uintptr_t>(d_vertices) & 15) != 0) {
+            lsn::set_error("lsnRefineVertices: bad arguments");
+            return -1;
+        }
+        LSN_HIP(hipSetDevice(device));
+        // behind everything queued on the caller's stream: once the row is here, the cloud it describes is final
+        std::vector<int> offsets((size_t)n_sensors + 1);
+        LSN_HIP(hipMemcpyAsync(offsets.data(), d_offsets, sizeof(int) * offsets.size(), hipMemcpyDeviceToHost, lsn::as_stream(stream)));
+        LSN_HIP(hipStreamSynchronize(lsn::as_stream(stream)));
+        std::vector<float> Rt((size_t)n_sensors * 12);
+        if (lsn::refine_cloud("lsnRefineVertices", device, n_sensors, d_vertices, offsets.data(), n_refine_iters, n_icp_iters, Rt.data(), nullptr, d_clouds_out))
+            return -1;
+        lsn::refine_compose(n_sensors, Rt.data(), world_R, world_t, camera_R, camera_t, Rs_out, Ts_out);
+        return 0;
+    });
+}
+
+extern "C" long long lsnRefineRelease(int device)
+{
+    return lsn::guarded("lsnRefineRelease", -1LL, [&]() -> long long {
+        lsn::clear_error();
+        std::vector<RefineState *> states;
+        {
+            RefineStates &all = refine_states();
+            std::lock_guard<std::mutex> g(all.mu);
+            for (const auto &kv : all.of_device)
+                if (device < 0 || kv.first == device) states.push_back(kv.second);
+        }
+        long long released = 0;
+        for (RefineState *st : states) {
+            std::lock_guard<std::mutex> g(st->mu);   // a pass in flight on this state ends first
+            const long long held = st->bytes();
+            if (held == 0 && !st->s) continue;       // never used, or released already: no device is touched
+            st->drop();
+            released += held;
+        }
+        return released;
     });
 }

@@ -135,6 +135,14 @@ int outlier_filter(LsnFusion *p, int k, float max_dist, const void *d_depth, con
 // place; neighbourhood <= 0 copies).  Takes the plan's mutex.
 int flying_pixels(LsnFusion *p, int neighbourhood, int threshold, const void *d_depth_in, void *d_depth_out, hipStream_t s);
 
+// The refine pass (icp.hip) on ONE tick's merged cloud, resident on `device` and final: vertices -> packed points -> Gauss-Seidel loop.
+// offsets: the tick's n_sensors + 1 row on the HOST; Rt: n_sensors x 12 floats, receives {Rs[i][9], Ts[i][3]}; h_clouds (host) / d_clouds
+// (device), both nullable, receive the refined points.  Complete on return.  refine_compose: the pose composition of the reference's refine
+// worker for those poses (world and camera pairs nullable), and the poses themselves into Rs_out / Ts_out (nullable).
+int refine_cloud(const char *who, int device, int n_sensors, const void *d_vertices, const int *offsets, int n_refine_iters, int n_icp_iters,
+                 float *Rt, float *h_clouds, float *d_clouds);
+void refine_compose(int n, const float *Rt, float *world_R, float *world_t, float *camera_R, float *camera_t, float *Rs_out, float *Ts_out);
+
 // The survivor exchange's two ends with the back-to-back stream layout (exchange.hip; see their definitions).
 int pack_survivors(LsnFusion *p, const void *d_depth, const void *d_colors, void *d_mask, void *d_depth_c, void *d_rgb_c, int *d_tile_prefix,
                    int *d_offsets, int *d_tick_base, void *stream);

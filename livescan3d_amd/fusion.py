@@ -109,6 +109,14 @@ class DeviceFusion:
     def flying_pixels(self, neighbourhood, threshold, depth_out, depth=None, stream=None):
         self.plan.flying_pixels(neighbourhood, threshold, self._in(depth)[0], depth_out.data_ptr(), _stream_handle(stream))
 
+    def refine(self, tick, n_refine_iters=2, n_icp_iters=10, world_R=None, world_t=None, camera_R=None, camera_t=None, clouds_out=None,
+               stream=None):
+        """The refine pass (native.refine_vertices) on tick `tick`'s merged cloud where it lies; clouds_out: a float32 tensor with room for
+        the tick's nVertices x 3 refined points.  Synchronises the stream; returns what native.refine_vertices returns."""
+        return native.refine_vertices(self.device.index, self.n_maps, self.vertices[tick].data_ptr(), self.offsets[tick].data_ptr(),
+                                      n_refine_iters, n_icp_iters, world_R, world_t, camera_R, camera_t,
+                                      None if clouds_out is None else clouds_out.data_ptr(), _stream_handle(stream))
+
     # ---- host views (each synchronises the device first) ----
 
     def host_offsets(self):

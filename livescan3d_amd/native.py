@@ -52,6 +52,7 @@ _PROTOTYPES = {
     "lsnGetLastError": (_i, [_s, _i]),
     "lsnDeviceCount": (_i, []),
     "lsnCorrectAndGenerateMesh": (None, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _mesh, _f, _f, _f, _f, _f, _f, _i]),
+    "lsnRefineFromDepthMaps": (_i, [_i] + [_vp] * 6 + [_f] * 6 + [_i] * 3 + [_vp] * 7),
     "lsnHostScheduleDescribe": (_i, [_i, _vp, _vp, _i, _i, _i, _i, _s, _i]),
     "lsnHostShardDescribe": (_i, [_i, _i, _vp, _s, _i]),
     "lsnHostShardPartMicros": (_i, [_vp, _i]),
@@ -122,6 +123,9 @@ _PROTOTYPES = {
     "lsnIcpProfile": (_i, [_vp, _vp, _vp]),
     "lsnIcpNearResolved": (_i, [_vp, _vp]),
     "lsnRefine": (_i, [_i, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp]),
+    "lsnRefineVertices": (_i, [_i, _i, _vp, _vp, _i, _i] + [_vp] * 8),
+    "lsnRefineComposePoses": (_i, [_i] + [_vp] * 6),
+    "lsnRefineRelease": (_ll, [_i]),
     "lsnTickCreate": (_vp, [_i, _i, _i, _vp, _vp]),
     "lsnTickDestroy": (None, [_vp]),
     "lsnTickSetParams": (_i, [_vp] * 5),
@@ -436,6 +440,77 @@ def refine(clouds, world_R, world_t, n_refine_iters=2, n_icp_iters=10, device=0)
     _check(lib().lsnRefine(int(device), len(cl), C.cast(ptrs, C.c_void_p), _ptr(n), int(n_refine_iters), int(n_icp_iters),
                            _ptr(wR), _ptr(wt), _ptr(Rs), _ptr(Ts)), "lsnRefine")
     return cl, wR.reshape(-1, 3, 3), wt.reshape(-1, 3), Rs.reshape(-1, 3, 3), Ts.reshape(-1, 3)
+
+
+def _pose_pair(R, t, n):
+    """An in/out pose pair of a refine export as private flat f32 copies, or (None, None)."""
+    if R is None or t is None:
+        return None, None
+    R, t = _as(R, np.float32).reshape(-1).copy(), _as(t, np.float32).reshape(-1).copy()
+    assert R.size == 9 * n and t.size == 3 * n
+    return R, t
+
+
+def _opt(a):
+    return None if a is None else _ptr(a)
+
+
+def _shaped(a, *shape):
+    return None if a is None else a.reshape(*shape)
+
+
+def compose_poses(Rs, Ts, world_R=None, world_t=None, camera_R=None, camera_t=None):
+    """lsnRefineComposePoses (needs no GPU): the pose composition at the end of refineWorker_DoWork (MainWindowForm.cs:382-410), the C#
+    loops as written.  Returns (world_R [n,3,3], world_t [n,3], camera_R, camera_t), None for a pair that was not given; inputs are
+    not modified."""
+    Rs, Ts = _as(Rs, np.float32).reshape(-1), _as(Ts, np.float32).reshape(-1)
+    n = Ts.size // 3
+    assert Rs.size == 9 * n and Ts.size == 3 * n
+    wR, wt = _pose_pair(world_R, world_t, n)
+    cR, ct = _pose_pair(camera_R, camera_t, n)
+    _check(lib().lsnRefineComposePoses(n, _ptr(Rs), _ptr(Ts), _opt(wR), _opt(wt), _opt(cR), _opt(ct)), "lsnRefineComposePoses")
+    return _shaped(wR, -1, 3, 3), _shaped(wt, -1, 3), _shaped(cR, -1, 3, 3), _shaped(ct, -1, 3)
+
+
+def refine_frames(depth_maps, depth_colors, widths, heights, intr, wt, bounds, n_refine_iters=2, n_icp_iters=10, correct_radial=False,
+                  camera_R=None, camera_t=None, outlier_filter=None, flying_pixels=None):
+    """lsnRefineFromDepthMaps: LiveScanServer's "Refine calibration" in one call -- frames up once, vertices, XYZ and the Gauss-Seidel loop
+    on the device.  Returns a dict: clouds (list of [n_i, 3] f32, refined), counts, Rs [n,3,3], Ts [n,3], wt (the refined world
+    transforms, packed like the input), camera_R / camera_t (None unless given); inputs are not modified.
+    outlier_filter / flying_pixels: as for correct_and_generate_mesh (the latter only matters with correct_radial)."""
+    with _Scoped(set_flying_pixel_filter, flying_pixels), _Scoped(set_outlier_filter, outlier_filter):
+        n, dm, dc, widths, heights, intr, wt, b = _host_args(depth_maps, depth_colors, widths, heights, intr, wt, bounds)
+        cR, ct = _pose_pair(camera_R, camera_t, n)
+        Rs, Ts = np.zeros(9 * n, dtype=np.float32), np.zeros(3 * n, dtype=np.float32)
+        wt_out = np.zeros(12 * n, dtype=np.float32)
+        clouds = np.zeros(max(1, int(np.sum(widths.astype(np.int64) * heights))) * 3, dtype=np.float32)
+        counts = np.zeros(n, dtype=np.int32)
+        _check(lib().lsnRefineFromDepthMaps(n, _ptr(dm), _ptr(dc), _ptr(widths), _ptr(heights), _ptr(intr), _ptr(wt), *b,
+                                            1 if correct_radial else 0, int(n_refine_iters), int(n_icp_iters), _ptr(wt_out), _opt(cR), _opt(ct),
+                                            _ptr(Rs), _ptr(Ts), _ptr(clouds), _ptr(counts)), "lsnRefineFromDepthMaps")
+        off = np.concatenate([[0], np.cumsum(counts)])
+        return {"clouds": [clouds[3 * off[i]:3 * off[i + 1]].reshape(-1, 3).copy() for i in range(n)], "counts": counts,
+                "Rs": Rs.reshape(-1, 3, 3), "Ts": Ts.reshape(-1, 3), "wt": wt_out,
+                "camera_R": _shaped(cR, -1, 3, 3), "camera_t": _shaped(ct, -1, 3)}
+
+
+def refine_vertices(device, n_sensors, d_vertices, d_offsets, n_refine_iters=2, n_icp_iters=10, world_R=None, world_t=None, camera_R=None,
+                    camera_t=None, d_clouds_out=None, stream=0):
+    """lsnRefineVertices: the refine pass on ONE tick's merged cloud that is resident on `device` (d_vertices / d_offsets / d_clouds_out:
+    device pointers as integers).  Synchronises `stream`; complete on return.  Returns (world_R, world_t, camera_R, camera_t, Rs, Ts),
+    None for a pair that was not given; inputs are not modified."""
+    n = int(n_sensors)
+    wR, wt = _pose_pair(world_R, world_t, n)
+    cR, ct = _pose_pair(camera_R, camera_t, n)
+    Rs, Ts = np.zeros(9 * n, dtype=np.float32), np.zeros(3 * n, dtype=np.float32)
+    _check(lib().lsnRefineVertices(int(device), n, d_vertices, d_offsets, int(n_refine_iters), int(n_icp_iters), _opt(wR), _opt(wt), _opt(cR),
+                                   _opt(ct), _ptr(Rs), _ptr(Ts), d_clouds_out, stream), "lsnRefineVertices")
+    return _shaped(wR, -1, 3, 3), _shaped(wt, -1, 3), _shaped(cR, -1, 3, 3), _shaped(ct, -1, 3), Rs.reshape(-1, 3, 3), Ts.reshape(-1, 3)
+
+
+def refine_release(device=-1):
+    """lsnRefineRelease: frees what the refine passes keep on `device` (default: every device).  Returns the bytes released."""
+    return int(_nonneg(lib().lsnRefineRelease(int(device)), "lsnRefineRelease"))
 
 
 # ----------------------------------------------------------------------------------------------------------
