@@ -304,6 +304,37 @@ int lsnFusionOutlierDiagnostics(LsnFusion *plan, int tick, int *removed_per_sens
                                 void *stream);
 int lsnSetOutlierFilter(int k, float max_dist, int *prev_k, float *prev_max_dist);
 
+/* Render view: the merged mesh of every tick (what lsnFusionRun / lsnFusionRunMesh and the stages above left in d_vertices / d_offsets /
+ * d_triangles / d_tri_offsets, read only) drawn from n_views <= 16 virtual pinhole cameras into frames with a sensor's layout: d_depth_out
+ * [n_ticks][n_views][height][width] u16 millimetres, 0 = nothing drawn; d_colors_out [n_ticks][n_views][height][width][3] RGB8, 0,0,0 where
+ * the depth is 0.  They can go into lsnFrameEncode, a PPM, or back into a fusion plan as a synthetic sensor.  A view is described like a
+ * sensor: intr_params 7 floats per view (cx, cy, fx, fy; the three distortion terms are ignored), wtransform_params 12 floats per view
+ * (p_world = R (p_cam + t)), both on the host; every view is width x height, 1 <= width, height <= 1024.  The reference shows the mesh in
+ * an OpenGL window (LiveScanServer's OpenGLWindow) and has no renderer of its own to copy: the stage is defined here
+ * from the reference's pointProjection and drawTriangle (src/NativeUtils/depthprocessing.cpp:735-747, :598-706), both pinned bit for bit.
+ * A vertex is projected with the view's inverted pose to integer (x, y) and depth d in mm, clamped to [0, 65535]; it is drawable iff it
+ * lands inside the image and d != 0 (which drops what is behind the camera, closer than 1 mm or not finite).  d_triangles given: a
+ * triangle is drawn iff its three indices are below the tick's nVertices and all three vertices are drawable -- there is NO CLIPPING, a
+ * triangle that leaves the image or crosses the camera plane is dropped whole -- over the pixels drawTriangle covers, with its depth
+ * value; a plain z-buffer: per pixel the candidate of smallest (depth value, triangle index) wins, candidates of value 0 are skipped; the
+ * colour is the winner's vertex colours under drawTriangle's weights, per channel trunc(c1 w1 + c2 w2 + c3 w3 + 0.5f) in float, clamped
+ * to [0, 255].  d_triangles == NULL (then d_tri_offsets is not read): points, every drawable vertex a candidate (d, vertex index) at its
+ * pixel, with its own colour.  The image does not depend on the order in which the device takes the primitives.  Triangle counts are
+ * clipped to lsnFusionTickTriangleCapacity().  Asynchronous on `stream`; returns 0, -1 with a message on a null argument, more than 16
+ * views or a bad size -- then no output is touched.
+ * Scratch, the plan's own, reserved by the first call, grown when a later call needs more, freed with the plan (a plan that never renders
+ * has none): 8 bytes x n_ticks x n_views x width x height of pixel keys and, with triangles, 8 bytes x n_ticks x lsnFusionTickCapacity() of
+ * projected vertices + 4 bytes x n_ticks x lsnFusionTickTriangleCapacity() of work list (the views of a call take turns on these two):
+ * 8 x 512x424 sensors, one tick, four 512x424 views = 6.9 + 13.9 + 13.9 MB.
+ * lsnFusionRenderDiagnostics (synchronises `stream`): for (tick, view) of the plan's last render, the primitives drawn (triangles with
+ * three drawable vertices / drawable vertices), the triangles whose bounding box was large enough to be drawn by a whole wave instead of
+ * one lane (a measurement aid: the image does not depend on it; 0 for points), and the pixels with depth != 0; any pointer may be NULL.
+ * Returns 0, -1 on error or before any render. */
+int lsnFusionRenderViews(LsnFusion *plan, int n_views, const float *intr_params, const float *wtransform_params, int width, int height,
+                         const void *d_vertices, const int *d_offsets, const void *d_triangles, const int *d_tri_offsets, void *d_depth_out,
+                         void *d_colors_out, void *stream);
+int lsnFusionRenderDiagnostics(LsnFusion *plan, int tick, int view, int *n_drawn, int *n_large, int *n_pixels, void *stream);
+
 /* Flying-pixel filter (LiveScanClient's KinectCapture::filterFlyingPixels, src/LiveScanClient/kinectCapture.cpp:132-174, with the server's
  * bFilterFlyingPixels / nFPNeighbourhoodSize / nFPThreshold, LiveScanServer/KinectSettings.cs:34-37) on all n_ticks x n_maps depth maps of
  * the plan, in front of the radial correction: a pixel with `neighbourhood` <= x < w - neighbourhood and the same for y (value 0 included)
@@ -588,6 +619,12 @@ long long lsnPlyPack(int device, const void *d_vertices, int n_vertices, const i
  * replaces the mesh -- one thread per family, as in LiveScanServer. */
 long long lsnLastMeshTransferFrame(unsigned char *out, long long out_cap);
 long long lsnLastMeshPly(unsigned char *out, long long out_cap);
+/* The same mesh (found and, where needed, rebuilt in HBM the same way) drawn from ONE virtual camera as lsnFusionRenderViews draws it, into
+ * host arrays: depth_out width x height u16 (as bytes), colors_out width x height x 3; points_only != 0, or a mesh without triangles: its
+ * vertices as points.  The preview of a server that has no OpenGLWindow.  Returns the number of pixels with depth != 0, -1 on error (no
+ * mesh, a bad size); complete on return. */
+long long lsnLastMeshRenderView(const float *intr7, const float *wt12, int width, int height, int points_only, unsigned char *depth_out,
+                                unsigned char *colors_out);
 
 /* Inbound (host-side parsing, no device work): the client's frame message -- LiveScanClient::SerializeFrame
  * (src/LiveScanClient/liveScanClient.cpp:185-290) as KinectSocket.ReceiveFrame reads it

@@ -595,3 +595,44 @@ extern "C" long long lsnLastMeshPly(unsigned char *out, long long out_cap)
         return last_mesh_bytes(c, *l, 1, out, out_cap);
     });
 }
+
+// One view of the calling thread's last mesh (render.hip) into host arrays: the mesh is one tick of one "sensor" whose offset rows are its
+// two counts.
+extern "C" long long lsnLastMeshRenderView(const float *intr7, const float *wt12, int width, int height, int points_only, unsigned char *depth_out,
+                                           unsigned char *colors_out)
+{
+    return lsn::guarded("lsnLastMeshRenderView", -1LL, [&]() -> long long {
+        lsn::clear_error();
+        if (!intr7 || !wt12 || !depth_out || !colors_out) {
+            lsn::set_error("lsnLastMeshRenderView: null argument");
+            return -1;
+        }
+        Ctx &c = ctx();
+        Lane *l = t_last_lane ? t_last_lane : c.last_lane.load();   // this thread's own last mesh call, else the process's
+        if (!l) l = &c.merge;
+        std::lock_guard<std::mutex> g(l->mu);
+        if (ensure_ready(c)) return -1;
+        if (l->last_nv < 0) {
+            lsn::set_error("lsnLastMesh*: no mesh is resident (call generateMeshFromDepthMaps / generateVerticesFromDepthMap first)");
+            return -1;
+        }
+        if (materialize(*l)) return -1;
+        const int nv = l->last_nv, nt = l->last_nt;
+        const bool points = points_only != 0 || nt <= 0;
+        std::lock_guard<std::mutex> wg(c.wire_mu);
+        LSN_HIP(hipSetDevice(l->device));
+        const size_t npix = (size_t)(width > 0 ? width : 0) * (size_t)(height > 0 ? height : 0);
+        if (c.d_rv_off.reserve(sizeof(int) * 4) || c.d_rv_img.reserve(5 * npix + 16)) return -1;
+        c.rv_rows[0] = 0; c.rv_rows[1] = nv; c.rv_rows[2] = 0; c.rv_rows[3] = nt;   // {first vertex, nVertices}, {first triangle, nTriangles}
+        LSN_HIP(hipMemcpyAsync(c.d_rv_off.p, c.rv_rows, sizeof(c.rv_rows), hipMemcpyHostToDevice, l->stream));
+        unsigned char *d_depth = c.d_rv_img.as<unsigned char>(), *d_col = d_depth + 2 * npix;
+        if (lsn::render_views(c.rv, "lsnLastMeshRenderView", 1, 1, nv, nt, 1, intr7, wt12, width, height, l->d_out.p, c.d_rv_off.as<int>(),
+                              points ? nullptr : l->d_tri.p, points ? nullptr : c.d_rv_off.as<int>() + 2, d_depth, d_col, l->stream))
+            return -1;
+        LSN_HIP(hipMemcpyAsync(depth_out, d_depth, 2 * npix, hipMemcpyDeviceToHost, l->stream));
+        LSN_HIP(hipMemcpyAsync(colors_out, d_col, 3 * npix, hipMemcpyDeviceToHost, l->stream));
+        int n_pixels = 0;
+        if (lsn::render_counts(c.rv, "lsnLastMeshRenderView", 0, 0, nullptr, nullptr, &n_pixels, l->stream)) return -1;   // synchronises
+        return n_pixels;
+    });
+}

@@ -775,18 +775,8 @@ extern "C" void lsnFusionDestroy(LsnFusion *p)
 
 extern "C" long long lsnFusionTickCapacity(const LsnFusion *p) { return p ? p->cap : 0; }
 
-// IntrinsicCameraParameters(float*) / WorldTranformation(float*), include/NativeUtils/depthprocessing.h:56-63,96-97: the caller's 7 and 12
-// floats of one sensor as the kernels read them.  The one place the unpack order is written down (tests/test_abi.py holds it against
-// the reference's own constructors through lsnPackSensorParams).
-static void pack_sensor_params(const float *ip, const float *tp, SensorParams &s)
-{
-    s.cx = ip[0]; s.cy = ip[1]; s.fx = ip[2]; s.fy = ip[3];
-    s.t0 = tp[0]; s.t1 = tp[1]; s.t2 = tp[2];
-    s.r00 = tp[3]; s.r01 = tp[4]; s.r02 = tp[5];
-    s.r10 = tp[6]; s.r11 = tp[7]; s.r12 = tp[8];
-    s.r20 = tp[9]; s.r21 = tp[10]; s.r22 = tp[11];
-}
-
+// (pack_sensor_params, the one place the unpack order of a sensor's 7 + 12 floats is written down, is in fusion_shared.hpp: the render
+// stage packs its views with it)
 extern "C" int lsnPackSensorParams(const float *intr7, const float *wt12, float *out16)
 {
     return lsn::guarded("lsnPackSensorParams", -1, [&]() {

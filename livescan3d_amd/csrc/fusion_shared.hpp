@@ -43,6 +43,18 @@ struct SensorParams {  // 16 floats, wave-uniform -> scalar loads
     float r00, r01, r02, r10, r11, r12, r20, r21, r22;
 };
 
+// IntrinsicCameraParameters(float*) / WorldTranformation(float*), include/NativeUtils/depthprocessing.h:56-63,96-97: the caller's 7 and 12
+// floats of one sensor as the kernels read them.  The one place the unpack order is written down (tests/test_abi.py holds it against
+// the reference's own constructors through lsnPackSensorParams).
+inline void pack_sensor_params(const float *ip, const float *tp, SensorParams &s)
+{
+    s.cx = ip[0]; s.cy = ip[1]; s.fx = ip[2]; s.fy = ip[3];
+    s.t0 = tp[0]; s.t1 = tp[1]; s.t2 = tp[2];
+    s.r00 = tp[3]; s.r01 = tp[4]; s.r02 = tp[5];
+    s.r10 = tp[6]; s.r11 = tp[7]; s.r12 = tp[8];
+    s.r20 = tp[9]; s.r21 = tp[10]; s.r22 = tp[11];
+}
+
 struct FuseArgs {
     const FrameDesc *frames;
     const TileDesc *tiles;             // tile (within tick) -> frame and first-pixel coordinates
@@ -106,6 +118,7 @@ using lsn::FrameDesc;
 using lsn::FuseArgs;
 using lsn::TriArgs;
 using lsn::SensorParams;
+using lsn::pack_sensor_params;
 using lsn::TileDesc;
 
 namespace {
@@ -600,6 +613,8 @@ struct LsnFusion {
     int fl_tiles_per_tick = 0;
     int fl_last = 0;                     // what the last call was: 0 = none yet, 1 = a copy (neighbourhood <= 0), 2 = the filter
     hipStream_t fl_stream = nullptr;     // ... and its stream
+    // render view (render.hip), allocated on its first call: keys, projections, work list, counters
+    lsn::RenderScratch rv;
     bool thr_valid = false;
     bool thr_enabled = true;             // $LSN_NO_THRESHOLDS=1 keeps the arithmetic count pass (ablation / tests)
     bool one_tick_single_pass = false;   // a one-tick plan of <= 2048 tiles takes the single pass (fuse_kernel<4>) instead of count -> scan -> write; $LSN_ONE_TICK_SINGLE_PASS=0 / 1 forces

@@ -157,6 +157,9 @@ struct Ctx {
     LsnTransfer *xfer = nullptr;
     int xfer_v = 0, xfer_t = 0;
     lsn::DevBuf d_wire;
+    lsn::RenderScratch rv;    // lsnLastMeshRenderView (under wire_mu too): the renderer's scratch, the mesh's two counts as offset rows, the image
+    lsn::DevBuf d_rv_off, d_rv_img;
+    int rv_rows[4] = {0, 0, 0, 0};
     bool warned_flags = false;
 };
 

@@ -135,6 +135,22 @@ int outlier_filter(LsnFusion *p, int k, float max_dist, const void *d_depth, con
 // place; neighbourhood <= 0 copies).  Takes the plan's mutex.
 int flying_pixels(LsnFusion *p, int neighbourhood, int threshold, const void *d_depth_in, void *d_depth_out, hipStream_t s);
 
+// The render stage (render.hip): what one renderer keeps between calls -- the per-pixel keys [n_ticks][n_views][w * h] u64, one view's
+// projected vertices [n_ticks][vertices per tick] and work list [n_ticks][triangles per tick] (the views of a call take turns on them;
+// mesh mode only), the counters behind lsnFusionRenderDiagnostics.  Reserved by the first call, grown by a call that needs more.
+struct RenderScratch {
+    DevBuf key, proj, list, cnt;
+    bool keys_clean = false;          // every key is "none": the resolve passes of the last call were all queued
+    int last_ticks = 0, last_views = 0;   // the shape of the last render (0: none yet)
+};
+// lsnFusionRenderViews on any batch of clouds in lsnFusionRunMesh's layout (n sensors per offset row, tick_vert vertices and tick_tri
+// triangles per tick), and the counters of one (tick, view) of the last call with `rs` (synchronises `s`).  The caller holds the lock that
+// guards `rs` and has made its device current; `who` names the export in messages.
+int render_views(RenderScratch &rs, const char *who, int n_ticks, int n, long long tick_vert, long long tick_tri, int n_views,
+                 const float *intr_params, const float *wtransform_params, int width, int height, const void *d_vertices, const int *d_offsets,
+                 const void *d_triangles, const int *d_tri_offsets, void *d_depth_out, void *d_colors_out, hipStream_t s);
+int render_counts(RenderScratch &rs, const char *who, int tick, int view, int *n_drawn, int *n_large, int *n_pixels, hipStream_t s);
+
 // The refine pass (icp.hip) on ONE tick's merged cloud, resident on `device` and final: vertices -> packed points -> Gauss-Seidel loop.
 // offsets: the tick's n_sensors + 1 row on the HOST; Rt: n_sensors x 12 floats, receives {Rs[i][9], Ts[i][3]}; h_clouds (host) / d_clouds
 // (device), both nullable, receive the refined points.  Complete on return.  refine_compose: the pose composition of the reference's refine

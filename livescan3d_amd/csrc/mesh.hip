@@ -602,7 +602,8 @@ int lsn::run_triangles_write(LsnFusion *p, const void *d_depth, void *d_triangle
 // The three stages that work on the fused cloud live in files of their own and are compiled here, in the translation unit of the
 // triangulation they run beside: they use the same plan and tile machinery (fusion_shared.hpp), and every build that lists the library's
 // translation units -- the product Makefile and the host-side sanitizer builds of tests/fake_hip -- compiles them without listing them.
-// What more than one of them uses (the plan's cloud index, the projection, the block scan):
+// (So does the render stage, which draws what they leave.)  What more than one of them uses (the plan's cloud index, the projection, the
+// block scan):
 #include "cloud_index.hip"
 // The colour transfer of the merge call (bcolor_transfer):
 #include "color.hip"
@@ -610,3 +611,5 @@ int lsn::run_triangles_write(LsnFusion *p, const void *d_depth, void *d_triangle
 #include "merge.hip"
 // The outlier filter (lsnSetOutlierFilter):
 #include "outlier.hip"
+// Render view (lsnFusionRenderViews): the merged mesh drawn from virtual cameras, with the merge's projection and coverage.
+#include "render.hip"

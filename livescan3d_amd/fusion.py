@@ -109,6 +109,17 @@ class DeviceFusion:
     def flying_pixels(self, neighbourhood, threshold, depth_out, depth=None, stream=None):
         self.plan.flying_pixels(neighbourhood, threshold, self._in(depth)[0], depth_out.data_ptr(), _stream_handle(stream))
 
+    def render_views(self, intr, wt, width, height, points=False, stream=None):
+        """The ticks' meshes (points: their vertices alone) drawn from the virtual cameras intr / wt (7 / 12 floats per view), each
+        width x height.  Returns (depth int16-bit-pattern [T, V, h, w], rgb uint8 [T, V, h, w, 3]), both prefilled with SENTINEL."""
+        n_views = np.asarray(intr).size // 7
+        depth = torch.full((self.n_ticks, n_views, height, width), SENTINEL, dtype=torch.int16, device=self.device)
+        rgb = torch.full((self.n_ticks, n_views, height, width, 3), SENTINEL % 256, dtype=torch.uint8, device=self.device)
+        self.plan.render_views(intr, wt, width, height, self.vertices.data_ptr(), self.offsets.data_ptr(),
+                               0 if points else self.triangles.data_ptr(), 0 if points else self.tri_offsets.data_ptr(), depth.data_ptr(),
+                               rgb.data_ptr(), _stream_handle(stream))
+        return depth, rgb
+
     def refine(self, tick, n_refine_iters=2, n_icp_iters=10, world_R=None, world_t=None, camera_R=None, camera_t=None, clouds_out=None,
                stream=None):
         """The refine pass (native.refine_vertices) on tick `tick`'s merged cloud where it lies; clouds_out: a float32 tensor with room for

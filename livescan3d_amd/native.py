@@ -90,6 +90,8 @@ _PROTOTYPES = {
     "lsnFusionOutlierDiagnostics": (_i, [_vp, _i, _vp, _vp, _vp, _vp]),
     "lsnFusionFlyingPixels": (_i, [_vp, _i, _i, _vp, _vp, _vp]),
     "lsnFusionFlyingDiagnostics": (_i, [_vp, _i, _vp, _vp]),
+    "lsnFusionRenderViews": (_i, [_vp, _i, _vp, _vp, _i, _i] + [_vp] * 7),
+    "lsnFusionRenderDiagnostics": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp]),
     "lsnFusionTilesPerTick": (_i, [_vp]),
     "lsnFusionPackSurvivors": (_i, [_vp] * 9),
     "lsnFusionReconstruct": (_i, [_vp, _i, _i, _vp, _vp, _vp, _ll, _vp, _vp, _vp, _vp, _vp]),
@@ -144,6 +146,7 @@ _PROTOTYPES = {
     "lsnPlyPack": (_ll, [_i, _vp, _i, _vp, _i, _vp, _ll, _vp]),
     "lsnLastMeshTransferFrame": (_ll, [_vp, _ll]),
     "lsnLastMeshPly": (_ll, [_vp, _ll]),
+    "lsnLastMeshRenderView": (_ll, [_vp, _vp, _i, _i, _i, _vp, _vp]),
     "lsnZstdAvailable": (_i, []),
     "lsnFrameParseHeader": (_i, [_vp, C.POINTER(FrameInfo)]),
     "lsnFrameDecode": (_ll, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _i, C.POINTER(_i)]),
@@ -653,6 +656,26 @@ class FusionPlan(_Handle):
         k = _nonneg(lib().lsnFusionFlyingDiagnostics(self._h, int(tick), _ptr(rps), stream or None), "lsnFusionFlyingDiagnostics")
         return rps[:self.n_maps].copy(), k
 
+    def render_views(self, intr, wt, width, height, d_vertices, d_offsets, d_triangles, d_tri_offsets, d_depth_out, d_colors_out, stream=0):
+        """Render view: every tick's merged mesh (d_triangles None / 0: its vertices as points) drawn from the virtual cameras of intr
+        (7 floats per view) / wt (12 per view), each width x height, into d_depth_out [n_ticks][n_views][h][w] u16 and d_colors_out
+        [...][3] u8 (device pointers).  Returns the number of views."""
+        intr, wt = _as(intr, np.float32).ravel(), _as(wt, np.float32).ravel()
+        n_views = intr.size // 7
+        assert intr.size == 7 * n_views and wt.size == 12 * n_views
+        _check(lib().lsnFusionRenderViews(self._h, n_views, _ptr(intr), _ptr(wt), int(width), int(height), d_vertices, d_offsets,
+                                          d_triangles or None, d_tri_offsets or None, d_depth_out, d_colors_out, stream or None),
+               "lsnFusionRenderViews")
+        return n_views
+
+    def render_diagnostics(self, tick=0, view=0, stream=0):
+        """The last render_views() of (tick, view): {"drawn": primitives drawn, "large": triangles that took the work-list path, "pixels":
+        pixels with depth != 0}."""
+        d, l, p = C.c_int(0), C.c_int(0), C.c_int(0)
+        _check(lib().lsnFusionRenderDiagnostics(self._h, int(tick), int(view), C.byref(d), C.byref(l), C.byref(p), stream or None),
+               "lsnFusionRenderDiagnostics")
+        return {"drawn": d.value, "large": l.value, "pixels": p.value}
+
     def thresholds(self, capacity=None, stream=0, copy=True):
         """Builds the per-pixel depth thresholds now.  Returns (table uint32[capacity] or None, build_ms); table is None when
         the plan does not use thresholds ($LSN_NO_THRESHOLDS=1)."""
@@ -894,6 +917,19 @@ def last_mesh_transfer_frame():
 def last_mesh_ply():
     """Binary PLY file image (Utils.cs:222-262) of the mesh the last merge call returned, built in HBM."""
     return _last_mesh(lib().lsnLastMeshPly, "lsnLastMeshPly")
+
+
+def last_mesh_render_view(intr7, wt12, width, height, points_only=False):
+    """lsnLastMeshRenderView: one view of the mesh the calling thread's last mesh call returned, rendered in HBM.  Returns (depth uint16
+    [h, w], rgb uint8 [h, w, 3], pixels with depth != 0)."""
+    require_gpu()
+    intr, wt = _as(intr7, np.float32).ravel(), _as(wt12, np.float32).ravel()
+    assert intr.size == 7 and wt.size == 12
+    w, h = int(width), int(height)
+    depth = np.zeros((max(h, 0), max(w, 0)), dtype=np.uint16)
+    rgb = np.zeros((max(h, 0), max(w, 0), 3), dtype=np.uint8)
+    n = _nonneg(lib().lsnLastMeshRenderView(_ptr(intr), _ptr(wt), w, h, 1 if points_only else 0, _ptr(depth), _ptr(rgb)), "lsnLastMeshRenderView")
+    return depth, rgb, int(n)
 
 
 def zstd_available():
