@@ -335,6 +335,40 @@ int lsnFusionRenderViews(LsnFusion *plan, int n_views, const float *intr_params,
                          void *d_colors_out, void *stream);
 int lsnFusionRenderDiagnostics(LsnFusion *plan, int tick, int view, int *n_drawn, int *n_large, int *n_pixels, void *stream);
 
+/* Mesh level of detail: vertex clustering of the merged mesh of every tick (what lsnFusionRun / lsnFusionRunMesh and the stages above left
+ * in d_vertices / d_offsets / d_triangles / d_tri_offsets, read only) on a uniform grid of edge `cell` metres, after the stages and in
+ * front of lsnTransferPack / lsnPlyPack / lsnFusionRenderViews / lsnRefineVertices, which take the outputs as they are.  The reference
+ * has no decimation to copy: the stage is defined here (tests/simplify_ref.py restates it).  Per tick, on its own:
+ * nVertices = d_offsets[n_maps] clipped to [0, lsnFusionTickCapacity()], nTriangles = d_tri_offsets[n_maps] clipped to [0,
+ * lsnFusionTickTriangleCapacity()].  inv = 1.0f / cell, once, in float.  Per axis of a vertex q = floorf(c * inv) (one float multiply,
+ * not fused with anything); the axis is in range iff q is finite and -2^20 <= q < 2^20, compared in float.  A vertex with three axes in
+ * range has the 63-bit key (qx + 2^20) | (qy + 2^20) << 21 | (qz + 2^20) << 42 and shares its cell with every vertex of that key; any
+ * other vertex (a NaN or infinite coordinate, q out of range) is unclustered: a cell of its own, always kept.  The vertex of LOWEST INDEX
+ * of a cell represents it and keeps its own 16 bytes: nothing is averaged, the result does not depend on the order in which the device
+ * takes the vertices.  d_vertices_out: the representatives in ascending input index (sensor order and raster order survive);
+ * d_offsets_out[i] = the kept vertices whose input index is below d_offsets[i], i = 0..n_maps, so d_offsets_out[n_maps] is the new
+ * nVertices; d_remap_out (nullable; lsnFusionTickCapacity() ints per tick): the output index of every input vertex's representative.
+ * d_triangles given: a triangle whose three indices are in [0, nVertices) is remapped; it is dropped if two of its new indices are equal
+ * or an index was out of range; the survivors keep their input order, d_tri_offsets_out[i] = the survivors whose input position is below
+ * d_tri_offsets[i].  DUPLICATE TRIANGLES ARE NOT REMOVED: two input triangles that become the same triple are both kept.  d_triangles ==
+ * NULL: points only, d_tri_offsets, d_triangles_out and d_tri_offsets_out are neither read nor written.  cell <= 0 or NaN: off -- the
+ * counted vertices, the counted triangles (out-of-range and degenerate ones too) and both offset rows are copied as they are, the remap
+ * is the identity.  cell = +inf (inv = 0: everything finite in one cell) and a denormal cell (inv = inf: everything unclustered) follow
+ * the arithmetic.  Simplifying the output again with the same cell returns the same bytes.  Outputs have lsnFusionRunMesh's layouts and
+ * per-tick strides; nothing behind a tick's new counts is written.  Out of place: an output that overlaps an input is refused.
+ * Asynchronous on `stream`; returns 0, -1 with a message (null argument, overlap) -- then no output is touched.
+ * Scratch, the plan's own, reserved by the first call, grown when a later call needs more, freed with the plan (a plan that never
+ * simplifies has none): per tick a hash table of 12 bytes x the power of two at or above 2 x lsnFusionTickCapacity() (cleared by every
+ * call, on `stream`; not reserved while cell <= 0), 8 bytes x lsnFusionTickCapacity() of representative / remap and output index, and
+ * 4 bytes per 256 vertices and per 256 triangles: 8 x 512x424 sensors, one tick = 50.3 + 13.9 + 0.1 MB.
+ * lsnFusionSimplifyDiagnostics (synchronises `stream`): for one tick of the plan's last call the occupied cells (= the new nVertices),
+ * the unclustered vertices (0 after cell <= 0) and the dropped triangles; any pointer may be NULL.  Returns 0, -1 on error or before any
+ * call. */
+int lsnFusionSimplify(LsnFusion *plan, float cell, const void *d_vertices, const int *d_offsets, const void *d_triangles,
+                      const int *d_tri_offsets, void *d_vertices_out, int *d_offsets_out, void *d_triangles_out, int *d_tri_offsets_out,
+                      int *d_remap_out, void *stream);
+int lsnFusionSimplifyDiagnostics(LsnFusion *plan, int tick, int *n_cells, int *n_unclustered, int *n_dropped_triangles, void *stream);
+
 /* Flying-pixel filter (LiveScanClient's KinectCapture::filterFlyingPixels, src/LiveScanClient/kinectCapture.cpp:132-174, with the server's
  * bFilterFlyingPixels / nFPNeighbourhoodSize / nFPThreshold, LiveScanServer/KinectSettings.cs:34-37) on all n_ticks x n_maps depth maps of
  * the plan, in front of the radial correction: a pixel with `neighbourhood` <= x < w - neighbourhood and the same for y (value 0 included)
@@ -625,6 +659,12 @@ long long lsnLastMeshPly(unsigned char *out, long long out_cap);
  * mesh, a bad size); complete on return. */
 long long lsnLastMeshRenderView(const float *intr7, const float *wt12, int width, int height, int points_only, unsigned char *depth_out,
                                 unsigned char *colors_out);
+/* lsnLastMeshTransferFrame / lsnLastMeshPly at a level of detail: the same mesh goes through lsnFusionSimplify's stage with `cell` (as one
+ * tick of one sensor, in HBM) and is packed from there.  out == NULL: an UPPER BOUND of the length, the one of the unsimplified mesh.
+ * cell <= 0 or NaN: byte for byte what the plain calls return.  The resident mesh is not changed: the plain calls still return all of it.
+ * A simplified mesh uses some vertices many times, so lsnTransferPack forms its chunks one after the other; only the bytes matter. */
+long long lsnLastMeshTransferFrameLod(float cell, unsigned char *out, long long out_cap);
+long long lsnLastMeshPlyLod(float cell, unsigned char *out, long long out_cap);
 
 /* Inbound (host-side parsing, no device work): the client's frame message -- LiveScanClient::SerializeFrame
  * (src/LiveScanClient/liveScanClient.cpp:185-290) as KinectSocket.ReceiveFrame reads it

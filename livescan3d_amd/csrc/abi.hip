@@ -530,20 +530,43 @@ extern "C" float ICP(Point3f *verts1, Point3f *verts2, int nVerts1, int nVerts2,
 // ---- the outbound formats of the mesh the last merge call left in HBM (include/NativeUtils.h part 3) ----------------------------
 
 namespace {
-// requires the lane's lock; kind 0 = TransferSocket.SendFrame stream, 1 = binary PLY file image
-long long last_mesh_bytes(Ctx &c, Lane &l, int kind, unsigned char *out, long long out_cap)
+// requires the lane's lock; kind 0 = TransferSocket.SendFrame stream, 1 = binary PLY file image; cell: null = the mesh as it is, else it
+// goes through the level-of-detail stage first (simplify.hip; the mesh is one tick of one "sensor" whose offset rows are its two counts),
+// in HBM, and the packers read what that left
+long long last_mesh_bytes(Ctx &c, Lane &l, int kind, const float *cell, unsigned char *out, long long out_cap)
 {
     if (ensure_ready(c)) return -1;
     if (l.last_nv < 0) {
         lsn::set_error("lsnLastMesh*: no mesh is resident (call generateMeshFromDepthMaps / generateVerticesFromDepthMap first)");
         return -1;
     }
-    const int nv = l.last_nv, nt = l.last_nt;
-    const long long bound = kind == 0 ? lsnTransferFrameBound(nv, nt) : lsnPlyBinaryBytes(nv, nt);
+    int nv = l.last_nv, nt = l.last_nt;
+    long long bound = kind == 0 ? lsnTransferFrameBound(nv, nt) : lsnPlyBinaryBytes(nv, nt);
+    // with cell an upper bound: fewer vertices and triangles are never longer, except that a mesh that loses every triangle leaves as points
+    if (cell && kind == 0) bound = std::max(bound, lsnTransferFrameBound(nv, 0));
     if (!out) return bound;
     if (materialize(l)) return -1;
     std::lock_guard<std::mutex> wg(c.wire_mu);
     if (c.d_wire.reserve((size_t)bound + 16)) return -1;
+    const void *d_v = l.d_out.p;
+    const int *d_t = l.d_tri.as<int>();
+    if (cell && nv > 0) {
+        const char *who = kind == 0 ? "lsnLastMeshTransferFrameLod" : "lsnLastMeshPlyLod";
+        LSN_HIP(hipSetDevice(l.device));
+        if (c.d_lod_v.reserve(16 * (size_t)nv) || c.d_lod_t.reserve(12 * (size_t)(nt > 0 ? nt : 1)) || c.d_lod_off.reserve(sizeof(c.lod_rows))) return -1;
+        int *rows = c.d_lod_off.as<int>();   // {0, nVertices}, {0, nTriangles} in; the same two rows out
+        c.lod_rows[0] = 0; c.lod_rows[1] = nv; c.lod_rows[2] = 0; c.lod_rows[3] = nt;
+        LSN_HIP(hipMemcpyAsync(rows, c.lod_rows, 4 * sizeof(int), hipMemcpyHostToDevice, l.stream));
+        if (lsn::simplify(c.sp, who, 1, 1, nv, nt > 0 ? nt : 0, *cell, d_v, rows, nt > 0 ? d_t : nullptr, rows + 2, c.d_lod_v.p, rows + 4,
+                          c.d_lod_t.p, rows + 6, nullptr, l.stream))
+            return -1;
+        LSN_HIP(hipMemcpyAsync(c.lod_rows + 4, rows + 4, 4 * sizeof(int), hipMemcpyDeviceToHost, l.stream));
+        LSN_HIP(hipStreamSynchronize(l.stream));
+        nv = c.lod_rows[5];
+        if (nt > 0) nt = c.lod_rows[7];
+        d_v = c.d_lod_v.p;
+        d_t = c.d_lod_t.as<int>();
+    }
     long long n = -1;
     if (kind == 0) {
         if (!c.xfer || nv > c.xfer_v || nt > c.xfer_t) {
@@ -556,9 +579,9 @@ long long last_mesh_bytes(Ctx &c, Lane &l, int kind, unsigned char *out, long lo
                 return -1;
             }
         }
-        n = lsnTransferPack(c.xfer, l.d_out.p, nv, nt > 0 ? l.d_tri.as<int>() : nullptr, nt, c.d_wire.p, bound, l.stream);
+        n = lsnTransferPack(c.xfer, d_v, nv, nt > 0 ? d_t : nullptr, nt, c.d_wire.p, bound, l.stream);
     } else {
-        n = lsnPlyPack(c.device, l.d_out.p, nv, nt > 0 ? l.d_tri.as<int>() : nullptr, nt, c.d_wire.p, bound, l.stream);
+        n = lsnPlyPack(c.device, d_v, nv, nt > 0 ? d_t : nullptr, nt, c.d_wire.p, bound, l.stream);
     }
     if (n < 0) return -1;
     if (n > out_cap) {
@@ -580,7 +603,7 @@ extern "C" long long lsnLastMeshTransferFrame(unsigned char *out, long long out_
         Lane *l = t_last_lane ? t_last_lane : c.last_lane.load();   // this thread's own last mesh call, else the process's
         if (!l) l = &c.merge;
         std::lock_guard<std::mutex> g(l->mu);
-        return last_mesh_bytes(c, *l, 0, out, out_cap);
+        return last_mesh_bytes(c, *l, 0, nullptr, out, out_cap);
     });
 }
 
@@ -592,7 +615,32 @@ extern "C" long long lsnLastMeshPly(unsigned char *out, long long out_cap)
         Lane *l = t_last_lane ? t_last_lane : c.last_lane.load();   // this thread's own last mesh call, else the process's
         if (!l) l = &c.merge;
         std::lock_guard<std::mutex> g(l->mu);
-        return last_mesh_bytes(c, *l, 1, out, out_cap);
+        return last_mesh_bytes(c, *l, 1, nullptr, out, out_cap);
+    });
+}
+
+// The same two through the level-of-detail stage (simplify.hip) with cell size `cell`; out == NULL: the length for the unsimplified mesh.
+extern "C" long long lsnLastMeshTransferFrameLod(float cell, unsigned char *out, long long out_cap)
+{
+    return lsn::guarded("lsnLastMeshTransferFrameLod", -1LL, [&]() -> long long {
+        lsn::clear_error();
+        Ctx &c = ctx();
+        Lane *l = t_last_lane ? t_last_lane : c.last_lane.load();   // this thread's own last mesh call, else the process's
+        if (!l) l = &c.merge;
+        std::lock_guard<std::mutex> g(l->mu);
+        return last_mesh_bytes(c, *l, 0, &cell, out, out_cap);
+    });
+}
+
+extern "C" long long lsnLastMeshPlyLod(float cell, unsigned char *out, long long out_cap)
+{
+    return lsn::guarded("lsnLastMeshPlyLod", -1LL, [&]() -> long long {
+        lsn::clear_error();
+        Ctx &c = ctx();
+        Lane *l = t_last_lane ? t_last_lane : c.last_lane.load();   // this thread's own last mesh call, else the process's
+        if (!l) l = &c.merge;
+        std::lock_guard<std::mutex> g(l->mu);
+        return last_mesh_bytes(c, *l, 1, &cell, out, out_cap);
     });
 }
 

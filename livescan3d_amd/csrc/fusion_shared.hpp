@@ -615,6 +615,8 @@ struct LsnFusion {
     hipStream_t fl_stream = nullptr;     // ... and its stream
     // render view (render.hip), allocated on its first call: keys, projections, work list, counters
     lsn::RenderScratch rv;
+    // mesh level of detail (simplify.hip), allocated on its first call: hash table, remap, tile counts, counters
+    lsn::SimplifyScratch sp;
     bool thr_valid = false;
     bool thr_enabled = true;             // $LSN_NO_THRESHOLDS=1 keeps the arithmetic count pass (ablation / tests)
     bool one_tick_single_pass = false;   // a one-tick plan of <= 2048 tiles takes the single pass (fuse_kernel<4>) instead of count -> scan -> write; $LSN_ONE_TICK_SINGLE_PASS=0 / 1 forces

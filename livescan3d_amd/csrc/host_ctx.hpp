@@ -160,6 +160,9 @@ struct Ctx {
     lsn::RenderScratch rv;    // lsnLastMeshRenderView (under wire_mu too): the renderer's scratch, the mesh's two counts as offset rows, the image
     lsn::DevBuf d_rv_off, d_rv_img;
     int rv_rows[4] = {0, 0, 0, 0};
+    lsn::SimplifyScratch sp;  // lsnLastMesh*Lod (under wire_mu too): the simplifier's scratch, the simplified mesh, the offset rows in and out
+    lsn::DevBuf d_lod_v, d_lod_t, d_lod_off;
+    int lod_rows[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     bool warned_flags = false;
 };
 

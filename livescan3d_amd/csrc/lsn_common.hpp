@@ -151,6 +151,22 @@ int render_views(RenderScratch &rs, const char *who, int n_ticks, int n, long lo
                  const void *d_triangles, const int *d_tri_offsets, void *d_depth_out, void *d_colors_out, hipStream_t s);
 int render_counts(RenderScratch &rs, const char *who, int tick, int view, int *n_drawn, int *n_large, int *n_pixels, hipStream_t s);
 
+// Mesh level of detail (simplify.hip): what one simplifier keeps between calls -- the hash table [n_ticks][slots] of u64 keys and, behind
+// them, u32 values (slots: the power of two at or above 2 x the vertices per tick), representative / remap and output index per vertex,
+// the per-256 counts of kept vertices and triangles, the counters behind lsnFusionSimplifyDiagnostics.  Reserved by the first call, grown
+// by a call that needs more; cell <= 0 never reserves the table.
+struct SimplifyScratch {
+    DevBuf table, rep, newidx, tiles, cnt;
+    int last_ticks = 0;   // the ticks of the last call (0: none yet)
+};
+// lsnFusionSimplify on any batch of clouds in lsnFusionRunMesh's layout (n sensors per offset row, tick_vert vertices and tick_tri
+// triangles per tick), and the counters of one tick of the last call with `ss` (synchronises `s`).  The caller holds the lock that guards
+// `ss` and has made its device current; `who` names the export in messages.
+int simplify(SimplifyScratch &ss, const char *who, int n_ticks, int n, long long tick_vert, long long tick_tri, float cell, const void *d_vertices,
+             const int *d_offsets, const void *d_triangles, const int *d_tri_offsets, void *d_vertices_out, int *d_offsets_out,
+             void *d_triangles_out, int *d_tri_offsets_out, int *d_remap_out, hipStream_t s);
+int simplify_counts(SimplifyScratch &ss, const char *who, int tick, int *n_cells, int *n_unclustered, int *n_dropped_triangles, hipStream_t s);
+
 // The refine pass (icp.hip) on ONE tick's merged cloud, resident on `device` and final: vertices -> packed points -> Gauss-Seidel loop.
 // offsets: the tick's n_sensors + 1 row on the HOST; Rt: n_sensors x 12 floats, receives {Rs[i][9], Ts[i][3]}; h_clouds (host) / d_clouds
 // (device), both nullable, receive the refined points.  Complete on return.  refine_compose: the pose composition of the reference's refine

@@ -613,3 +613,5 @@ int lsn::run_triangles_write(LsnFusion *p, const void *d_depth, void *d_triangle
 #include "outlier.hip"
 // Render view (lsnFusionRenderViews): the merged mesh drawn from virtual cameras, with the merge's projection and coverage.
 #include "render.hip"
+// Mesh level of detail (lsnFusionSimplify): vertex clustering of the merged mesh, in front of the packers and the renderer.
+#include "simplify.hip"

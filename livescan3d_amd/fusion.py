@@ -120,6 +120,21 @@ class DeviceFusion:
                                rgb.data_ptr(), _stream_handle(stream))
         return depth, rgb
 
+    def simplify(self, cell, points=False, stream=None):
+        """Mesh level of detail: the ticks' meshes (points: their vertices alone) clustered on a grid of edge `cell`.  Returns fresh tensors
+        (vertices uint8 [T, capacity, 16], offsets int32 [T, N+1], triangles int32 [T, 2*capacity, 3] or None, tri_offsets or None, remap
+        int32 [T, capacity]); the offset tables are prefilled with SENTINEL."""
+        vertices = torch.zeros_like(self.vertices)
+        offsets = torch.full_like(self.offsets, SENTINEL)
+        triangles = None if points else torch.zeros_like(self.triangles)
+        tri_offsets = None if points else torch.full_like(self.tri_offsets, SENTINEL)
+        remap = torch.zeros((self.n_ticks, self.capacity), dtype=torch.int32, device=self.device)
+        self.plan.simplify(cell, self.vertices.data_ptr(), self.offsets.data_ptr(), 0 if points else self.triangles.data_ptr(),
+                           0 if points else self.tri_offsets.data_ptr(), vertices.data_ptr(), offsets.data_ptr(),
+                           0 if points else triangles.data_ptr(), 0 if points else tri_offsets.data_ptr(), remap.data_ptr(),
+                           _stream_handle(stream))
+        return vertices, offsets, triangles, tri_offsets, remap
+
     def refine(self, tick, n_refine_iters=2, n_icp_iters=10, world_R=None, world_t=None, camera_R=None, camera_t=None, clouds_out=None,
                stream=None):
         """The refine pass (native.refine_vertices) on tick `tick`'s merged cloud where it lies; clouds_out: a float32 tensor with room for

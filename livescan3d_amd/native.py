@@ -92,6 +92,8 @@ _PROTOTYPES = {
     "lsnFusionFlyingDiagnostics": (_i, [_vp, _i, _vp, _vp]),
     "lsnFusionRenderViews": (_i, [_vp, _i, _vp, _vp, _i, _i] + [_vp] * 7),
     "lsnFusionRenderDiagnostics": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp]),
+    "lsnFusionSimplify": (_i, [_vp, _f] + [_vp] * 10),
+    "lsnFusionSimplifyDiagnostics": (_i, [_vp, _i, _vp, _vp, _vp, _vp]),
     "lsnFusionTilesPerTick": (_i, [_vp]),
     "lsnFusionPackSurvivors": (_i, [_vp] * 9),
     "lsnFusionReconstruct": (_i, [_vp, _i, _i, _vp, _vp, _vp, _ll, _vp, _vp, _vp, _vp, _vp]),
@@ -147,6 +149,8 @@ _PROTOTYPES = {
     "lsnLastMeshTransferFrame": (_ll, [_vp, _ll]),
     "lsnLastMeshPly": (_ll, [_vp, _ll]),
     "lsnLastMeshRenderView": (_ll, [_vp, _vp, _i, _i, _i, _vp, _vp]),
+    "lsnLastMeshTransferFrameLod": (_ll, [_f, _vp, _ll]),
+    "lsnLastMeshPlyLod": (_ll, [_f, _vp, _ll]),
     "lsnZstdAvailable": (_i, []),
     "lsnFrameParseHeader": (_i, [_vp, C.POINTER(FrameInfo)]),
     "lsnFrameDecode": (_ll, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _i, C.POINTER(_i)]),
@@ -676,6 +680,22 @@ class FusionPlan(_Handle):
                "lsnFusionRenderDiagnostics")
         return {"drawn": d.value, "large": l.value, "pixels": p.value}
 
+    def simplify(self, cell, d_vertices, d_offsets, d_triangles, d_tri_offsets, d_vertices_out, d_offsets_out, d_triangles_out,
+                 d_tri_offsets_out, d_remap_out=0, stream=0):
+        """Mesh level of detail: every tick's merged mesh (d_triangles None / 0: its vertices alone) clustered on a grid of edge `cell`
+        into the out buffers (run_mesh's layouts; d_remap_out: capacity ints per tick, optional).  Out of place; cell <= 0 copies."""
+        _check(lib().lsnFusionSimplify(self._h, float(cell), d_vertices, d_offsets, d_triangles or None, d_tri_offsets or None, d_vertices_out,
+                                       d_offsets_out, d_triangles_out or None, d_tri_offsets_out or None, d_remap_out or None, stream or None),
+               "lsnFusionSimplify")
+
+    def simplify_diagnostics(self, tick=0, stream=0):
+        """The last simplify() of one tick: {"cells": occupied cells = vertices out, "unclustered": vertices that are a cell of their own,
+        "dropped_triangles": triangles that collapsed or named a vertex out of range}."""
+        c, u, d = C.c_int(0), C.c_int(0), C.c_int(0)
+        _check(lib().lsnFusionSimplifyDiagnostics(self._h, int(tick), C.byref(c), C.byref(u), C.byref(d), stream or None),
+               "lsnFusionSimplifyDiagnostics")
+        return {"cells": c.value, "unclustered": u.value, "dropped_triangles": d.value}
+
     def thresholds(self, capacity=None, stream=0, copy=True):
         """Builds the per-pixel depth thresholds now.  Returns (table uint32[capacity] or None, build_ms); table is None when
         the plan does not use thresholds ($LSN_NO_THRESHOLDS=1)."""
@@ -917,6 +937,18 @@ def last_mesh_transfer_frame():
 def last_mesh_ply():
     """Binary PLY file image (Utils.cs:222-262) of the mesh the last merge call returned, built in HBM."""
     return _last_mesh(lib().lsnLastMeshPly, "lsnLastMeshPly")
+
+
+def last_mesh_transfer_frame_lod(cell):
+    """lsnLastMeshTransferFrameLod: the SendFrame stream of that mesh after vertex clustering with cell size `cell` (<= 0: as it is)."""
+    fn = lib().lsnLastMeshTransferFrameLod
+    return _last_mesh(lambda out, cap: fn(float(cell), out, cap), "lsnLastMeshTransferFrameLod")
+
+
+def last_mesh_ply_lod(cell):
+    """lsnLastMeshPlyLod: the binary PLY file image of that mesh after vertex clustering with cell size `cell` (<= 0: as it is)."""
+    fn = lib().lsnLastMeshPlyLod
+    return _last_mesh(lambda out, cap: fn(float(cell), out, cap), "lsnLastMeshPlyLod")
 
 
 def last_mesh_render_view(intr7, wt12, width, height, points_only=False):
