@@ -7,9 +7,10 @@
 //             = lsnLastMeshTransferFrame, appended tick after tick to --frames-out; the last tick's mesh as a binary PLY
 //             (Utils.saveToPly, LiveScanServer/Utils.cs:222-262) = lsnLastMeshPly, written to --ply.  With --lod CELL both go
 //             through the level-of-detail stage first (vertex clustering on a grid of CELL metres: lsnLastMeshTransferFrameLod,
-//             lsnLastMeshPlyLod); without it the output is what it always was.
+//             lsnLastMeshPlyLod); without it the output is what it always was.  With --normals the PLY carries vertex normals
+//             (nx, ny, nz between z and red; lsnLastMeshPlyNormals, which takes --lod's CELL as its own argument).
 //
-//   stream --calib calib.bin [--bounds 6 floats] [--lod CELL] [--frames-out f.bin] [--ply mesh.ply] rec0.bin rec1.bin ...
+//   stream --calib calib.bin [--bounds 6 floats] [--lod CELL] [--normals] [--frames-out f.bin] [--ply mesh.ply] rec0.bin rec1.bin ...
 //   calib.bin: per sensor 7 f32 intrinsics + 12 f32 pose (the arrays KinectServer passes, KinectServer.cs:470-490)
 //
 // Build: make -C examples stream   (links -lNativeUtils only)
@@ -46,7 +47,7 @@ int main(int argc, char **argv)
 {
     float b[6] = {-5, -5, -5, 5, 5, 5};   // KinectSettings.cs:54-60
     const char *calib = nullptr, *frames_out = nullptr, *ply = nullptr;
-    bool lod = false;
+    bool lod = false, normals = false;
     float cell = 0.0f;
     std::vector<const char *> recs;
     for (int i = 1; i < argc; i++) {
@@ -54,11 +55,12 @@ int main(int argc, char **argv)
         else if (!strcmp(argv[i], "--frames-out") && i + 1 < argc) frames_out = argv[++i];
         else if (!strcmp(argv[i], "--ply") && i + 1 < argc) ply = argv[++i];
         else if (!strcmp(argv[i], "--lod") && i + 1 < argc) { lod = true; cell = (float)atof(argv[++i]); }
+        else if (!strcmp(argv[i], "--normals")) normals = true;
         else if (!strcmp(argv[i], "--bounds") && i + 6 < argc) { for (int k = 0; k < 6; k++) b[k] = (float)atof(argv[++i]); }
         else recs.push_back(argv[i]);
     }
     const int n = (int)recs.size();
-    if (!calib || n == 0) { fprintf(stderr, "usage: %s --calib calib.bin [--bounds 6 floats] [--lod CELL] [--frames-out f.bin] [--ply mesh.ply] rec0.bin ...\n", argv[0]); return 2; }
+    if (!calib || n == 0) { fprintf(stderr, "usage: %s --calib calib.bin [--bounds 6 floats] [--lod CELL] [--normals] [--frames-out f.bin] [--ply mesh.ply] rec0.bin ...\n", argv[0]); return 2; }
     std::vector<unsigned char> cal;
     if (!read_all(calib, cal) || cal.size() != (size_t)n * 19 * 4) { fprintf(stderr, "calib: expected %d x 19 floats\n", n); return 1; }
     std::vector<float> intr(7 * (size_t)n), wt(12 * (size_t)n);
@@ -117,10 +119,12 @@ int main(int argc, char **argv)
     }
     if (fo) fclose(fo);
     if (ply && ticks > 0) {
-        long long need = lod ? lsnLastMeshPlyLod(cell, nullptr, 0) : lsnLastMeshPly(nullptr, 0);
-        if (need < 0) return fail("lsnLastMeshPly");
+        long long need = normals ? lsnLastMeshPlyNormals(cell, nullptr, 0) : lod ? lsnLastMeshPlyLod(cell, nullptr, 0) : lsnLastMeshPly(nullptr, 0);
+        if (need < 0) return fail(normals ? "lsnLastMeshPlyNormals" : "lsnLastMeshPly");
         wire.resize((size_t)need);
-        if (lod) {
+        if (normals) {
+            if ((need = lsnLastMeshPlyNormals(cell, wire.data(), need)) < 0) return fail("lsnLastMeshPlyNormals");
+        } else if (lod) {
             if ((need = lsnLastMeshPlyLod(cell, wire.data(), need)) < 0) return fail("lsnLastMeshPlyLod");
         } else if (lsnLastMeshPly(wire.data(), need) != need) {
             return fail("lsnLastMeshPly");

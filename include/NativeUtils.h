@@ -369,6 +369,36 @@ int lsnFusionSimplify(LsnFusion *plan, float cell, const void *d_vertices, const
                       int *d_remap_out, void *stream);
 int lsnFusionSimplifyDiagnostics(LsnFusion *plan, int tick, int *n_cells, int *n_unclustered, int *n_dropped_triangles, void *stream);
 
+/* Vertex normals of the merged mesh of every tick (what lsnFusionRunMesh and the stages above -- overlay merge, outlier filter, level of
+ * detail -- left in d_vertices / d_offsets / d_triangles / d_tri_offsets, read only): area weighted, bit-exact whatever order the device
+ * takes the triangles in.  The reference computes no normals: the stage is defined here (tests/normals_ref.py
+ * restates it).  Per tick, on its own: nVertices = d_offsets[n_maps] clipped to [0, lsnFusionTickCapacity()], nTriangles =
+ * d_tri_offsets[n_maps] clipped to [0, lsnFusionTickTriangleCapacity()].  Face vector of the triangle (i0, i1, i2) with positions p0, p1,
+ * p2, all in float, every operation rounded on its own, nothing fused: u = p2 - p0, v = p1 - p0; fx = u.y * v.z - u.z * v.y, fy = u.z * v.x
+ * - u.x * v.z, fz = u.x * v.y - u.y * v.x, that is (p2 - p0) x (p1 - p0): twice the area long, and for the triples lsnFusionRunMesh emits
+ * it points towards the sensor that saw the triangle.  A triangle is USED iff its three indices are in [0, nVertices) and fx, fy, fz are
+ * all finite with |c| < 4096.0f (compared in float, before any conversion); any other triangle contributes nothing and is counted as
+ * skipped.  A degenerate triangle (a repeated index, collinear points) is used and contributes zeros.  Fixed point: q_c = (int64)
+ * trunc(c * 2^40); the float multiply is exact for |c| < 4096, the product is below 2^52, so the conversion is exact; a component below
+ * 2^-40 becomes 0, so the result does not depend on whether the device flushes float denormals.  Sum: S[i] += q for i = i0, i1, i2 --
+ * three signed 64-bit sums per vertex, two's complement with wrap-around (more than 2048 triangles of 4096 m^2 on one vertex).  Integer
+ * addition is associative: the sums do not depend on the order of the triangles.  Normal: S[i] == (0, 0, 0) (a vertex of no used
+ * triangle, or one whose contributions cancel) gives (+0, +0, +0); otherwise s_c = (float) S_c, one round-to-nearest-even conversion from
+ * int64 each, len = sqrtf((s.x * s.x + s.y * s.y) + s.z * s.z), n_c = s_c / len: float throughout, in that order, sqrtf and the divisions
+ * correctly rounded.  Nothing overflows (3 x 2^126 < FLT_MAX) and len >= 1.
+ * d_normals_out: [n_ticks][lsnFusionTickCapacity()][3] floats, 12 bytes per vertex at the vertex's own index; nothing behind a tick's
+ * nVertices is written.  Out of place: an output that overlaps an input is refused.  d_triangles == NULL is refused: the normals of a
+ * bare point cloud are not defined here.  Asynchronous on `stream`; returns 0, -1 with a message (null argument, overlap) -- then no
+ * output is touched.
+ * Scratch, the plan's own, reserved by the first call, grown when a later call needs more, freed with the plan (a plan that never asks
+ * for normals has none): the sums as three planes [n_ticks][3][lsnFusionTickCapacity()] of int64 (24 bytes per vertex; 8 x 512x424
+ * sensors, one tick = 41.7 MB; the counted vertices are cleared by every call, on `stream`) and 16 bytes of counters per tick.
+ * lsnFusionNormalsDiagnostics (synchronises `stream`): for one tick of the plan's last call the used triangles, the skipped triangles and
+ * the vertices whose normal is (0, 0, 0); any pointer may be NULL.  Returns 0, -1 on error or before any call. */
+int lsnFusionNormals(LsnFusion *plan, const void *d_vertices, const int *d_offsets, const void *d_triangles, const int *d_tri_offsets,
+                     void *d_normals_out, void *stream);
+int lsnFusionNormalsDiagnostics(LsnFusion *plan, int tick, int *n_used, int *n_skipped, int *n_zero_normals, void *stream);
+
 /* Flying-pixel filter (LiveScanClient's KinectCapture::filterFlyingPixels, src/LiveScanClient/kinectCapture.cpp:132-174, with the server's
  * bFilterFlyingPixels / nFPNeighbourhoodSize / nFPThreshold, LiveScanServer/KinectSettings.cs:34-37) on all n_ticks x n_maps depth maps of
  * the plan, in front of the radial correction: a pixel with `neighbourhood` <= x < w - neighbourhood and the same for y (value 0 included)
@@ -641,6 +671,12 @@ int lsnTransferLastPath(LsnTransfer *t);
 long long lsnPlyBinaryBytes(int n_vertices, int n_triangles);
 long long lsnPlyPack(int device, const void *d_vertices, int n_vertices, const int *d_triangles, int n_triangles, void *d_out,
                      long long out_cap, void *stream);
+/* The same file with vertex normals: the header has "property float nx\nproperty float ny\nproperty float nz\n" between z and red (the
+ * "\r\n" behind the format line is kept), the vertex records are the 27 bytes {f32 x,y,z; f32 nx,ny,nz; u8 r,g,b}, the face records the
+ * same 13.  d_normals: 3 floats per vertex (one tick of lsnFusionNormals' output).  lsnPlyNormalsBytes is the exact length. */
+long long lsnPlyNormalsBytes(int n_vertices, int n_triangles);
+long long lsnPlyPackNormals(int device, const void *d_vertices, const void *d_normals, int n_vertices, const int *d_triangles, int n_triangles,
+                            void *d_out, long long out_cap, void *stream);
 
 /* Host callers (LiveScanServer): the mesh the last generateMeshFromDepthMaps / generateVerticesFromDepthMap /
  * lsnCorrectAndGenerateMesh call OF THE CALLING THREAD returned is still in HBM -- or its frames are, and it is rebuilt there on demand
@@ -665,6 +701,11 @@ long long lsnLastMeshRenderView(const float *intr7, const float *wt12, int width
  * A simplified mesh uses some vertices many times, so lsnTransferPack forms its chunks one after the other; only the bytes matter. */
 long long lsnLastMeshTransferFrameLod(float cell, unsigned char *out, long long out_cap);
 long long lsnLastMeshPlyLod(float cell, unsigned char *out, long long out_cap);
+/* lsnLastMeshPly with vertex normals (lsnPlyPackNormals' file): the same mesh goes through the level-of-detail stage with `cell` (<= 0 or
+ * NaN: the mesh as it is), then through lsnFusionNormals' stage on what that left, both as one tick of one sensor, in HBM, and is packed
+ * from there.  out == NULL: the length for the unsimplified mesh, an upper bound.  A mesh without triangles: -1 with a message.  The
+ * resident mesh is not changed. */
+long long lsnLastMeshPlyNormals(float cell, unsigned char *out, long long out_cap);
 
 /* Inbound (host-side parsing, no device work): the client's frame message -- LiveScanClient::SerializeFrame
  * (src/LiveScanClient/liveScanClient.cpp:185-290) as KinectSocket.ReceiveFrame reads it

@@ -530,9 +530,10 @@ extern "C" float ICP(Point3f *verts1, Point3f *verts2, int nVerts1, int nVerts2,
 // ---- the outbound formats of the mesh the last merge call left in HBM (include/NativeUtils.h part 3) ----------------------------
 
 namespace {
-// requires the lane's lock; kind 0 = TransferSocket.SendFrame stream, 1 = binary PLY file image; cell: null = the mesh as it is, else it
-// goes through the level-of-detail stage first (simplify.hip; the mesh is one tick of one "sensor" whose offset rows are its two counts),
-// in HBM, and the packers read what that left
+// requires the lane's lock; kind 0 = TransferSocket.SendFrame stream, 1 = binary PLY file image, 2 = that file with vertex normals; cell:
+// null = the mesh as it is, else it goes through the level-of-detail stage first (simplify.hip; the mesh is one tick of one "sensor" whose
+// offset rows are its two counts), in HBM, and the packers read what that left.  Kind 2 (cell given; <= 0 or NaN skips the level of detail)
+// then runs the normals stage (normals.hip) on the same one tick.
 long long last_mesh_bytes(Ctx &c, Lane &l, int kind, const float *cell, unsigned char *out, long long out_cap)
 {
     if (ensure_ready(c)) return -1;
@@ -541,7 +542,11 @@ long long last_mesh_bytes(Ctx &c, Lane &l, int kind, const float *cell, unsigned
         return -1;
     }
     int nv = l.last_nv, nt = l.last_nt;
-    long long bound = kind == 0 ? lsnTransferFrameBound(nv, nt) : lsnPlyBinaryBytes(nv, nt);
+    if (kind == 2 && nt <= 0) {
+        lsn::set_error("lsnLastMeshPlyNormals: the resident mesh has no triangles (the normals of a bare point cloud are not defined)");
+        return -1;
+    }
+    long long bound = kind == 0 ? lsnTransferFrameBound(nv, nt) : kind == 1 ? lsnPlyBinaryBytes(nv, nt) : lsnPlyNormalsBytes(nv, nt);
     // with cell an upper bound: fewer vertices and triangles are never longer, except that a mesh that loses every triangle leaves as points
     if (cell && kind == 0) bound = std::max(bound, lsnTransferFrameBound(nv, 0));
     if (!out) return bound;
@@ -550,8 +555,17 @@ long long last_mesh_bytes(Ctx &c, Lane &l, int kind, const float *cell, unsigned
     if (c.d_wire.reserve((size_t)bound + 16)) return -1;
     const void *d_v = l.d_out.p;
     const int *d_t = l.d_tri.as<int>();
-    if (cell && nv > 0) {
-        const char *who = kind == 0 ? "lsnLastMeshTransferFrameLod" : "lsnLastMeshPlyLod";
+    const int *d_rows = nullptr;            // kind 2: the offset rows {0, nVertices}, {0, nTriangles} of what the packer will read
+    const int nv0 = nv, nt0 = nt;           // ... and its strides
+    if (kind == 2) {
+        LSN_HIP(hipSetDevice(l.device));
+        if (c.d_lod_off.reserve(sizeof(c.lod_rows))) return -1;
+        c.lod_rows[0] = 0; c.lod_rows[1] = nv; c.lod_rows[2] = 0; c.lod_rows[3] = nt;
+        LSN_HIP(hipMemcpyAsync(c.d_lod_off.p, c.lod_rows, 4 * sizeof(int), hipMemcpyHostToDevice, l.stream));
+        d_rows = c.d_lod_off.as<int>();
+    }
+    if (cell && nv > 0 && (kind != 2 || *cell > 0.0f)) {
+        const char *who = kind == 0 ? "lsnLastMeshTransferFrameLod" : kind == 1 ? "lsnLastMeshPlyLod" : "lsnLastMeshPlyNormals";
         LSN_HIP(hipSetDevice(l.device));
         if (c.d_lod_v.reserve(16 * (size_t)nv) || c.d_lod_t.reserve(12 * (size_t)(nt > 0 ? nt : 1)) || c.d_lod_off.reserve(sizeof(c.lod_rows))) return -1;
         int *rows = c.d_lod_off.as<int>();   // {0, nVertices}, {0, nTriangles} in; the same two rows out
@@ -566,6 +580,11 @@ long long last_mesh_bytes(Ctx &c, Lane &l, int kind, const float *cell, unsigned
         if (nt > 0) nt = c.lod_rows[7];
         d_v = c.d_lod_v.p;
         d_t = c.d_lod_t.as<int>();
+        d_rows = rows + 4;
+    }
+    if (kind == 2) {   // (the simplified mesh keeps the strides nv0 / nt0; one tick, so only the clipping sees them)
+        if (c.d_nm.reserve(12 * (size_t)(nv0 > 0 ? nv0 : 1))) return -1;
+        if (lsn::normals(c.nm, "lsnLastMeshPlyNormals", 1, 1, nv0, nt0, d_v, d_rows, d_t, d_rows + 2, c.d_nm.p, nullptr, l.stream)) return -1;
     }
     long long n = -1;
     if (kind == 0) {
@@ -580,8 +599,10 @@ long long last_mesh_bytes(Ctx &c, Lane &l, int kind, const float *cell, unsigned
             }
         }
         n = lsnTransferPack(c.xfer, d_v, nv, nt > 0 ? d_t : nullptr, nt, c.d_wire.p, bound, l.stream);
-    } else {
+    } else if (kind == 1) {
         n = lsnPlyPack(c.device, d_v, nv, nt > 0 ? d_t : nullptr, nt, c.d_wire.p, bound, l.stream);
+    } else {
+        n = lsnPlyPackNormals(c.device, d_v, c.d_nm.p, nv, nt > 0 ? d_t : nullptr, nt, c.d_wire.p, bound, l.stream);
     }
     if (n < 0) return -1;
     if (n > out_cap) {
@@ -641,6 +662,19 @@ extern "C" long long lsnLastMeshPlyLod(float cell, unsigned char *out, long long
         if (!l) l = &c.merge;
         std::lock_guard<std::mutex> g(l->mu);
         return last_mesh_bytes(c, *l, 1, &cell, out, out_cap);
+    });
+}
+
+// The PLY file of that mesh with vertex normals (normals.hip), after the level-of-detail stage with `cell` (<= 0 or NaN: the mesh as it is).
+extern "C" long long lsnLastMeshPlyNormals(float cell, unsigned char *out, long long out_cap)
+{
+    return lsn::guarded("lsnLastMeshPlyNormals", -1LL, [&]() -> long long {
+        lsn::clear_error();
+        Ctx &c = ctx();
+        Lane *l = t_last_lane ? t_last_lane : c.last_lane.load();   // this thread's own last mesh call, else the process's
+        if (!l) l = &c.merge;
+        std::lock_guard<std::mutex> g(l->mu);
+        return last_mesh_bytes(c, *l, 2, &cell, out, out_cap);
     });
 }
 

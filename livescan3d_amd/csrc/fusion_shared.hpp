@@ -617,6 +617,8 @@ struct LsnFusion {
     lsn::RenderScratch rv;
     // mesh level of detail (simplify.hip), allocated on its first call: hash table, remap, tile counts, counters
     lsn::SimplifyScratch sp;
+    // vertex normals (normals.hip), allocated on its first call: the integer sums, counters
+    lsn::NormalsScratch nm;
     bool thr_valid = false;
     bool thr_enabled = true;             // $LSN_NO_THRESHOLDS=1 keeps the arithmetic count pass (ablation / tests)
     bool one_tick_single_pass = false;   // a one-tick plan of <= 2048 tiles takes the single pass (fuse_kernel<4>) instead of count -> scan -> write; $LSN_ONE_TICK_SINGLE_PASS=0 / 1 forces

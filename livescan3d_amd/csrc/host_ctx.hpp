@@ -163,6 +163,8 @@ struct Ctx {
     lsn::SimplifyScratch sp;  // lsnLastMesh*Lod (under wire_mu too): the simplifier's scratch, the simplified mesh, the offset rows in and out
     lsn::DevBuf d_lod_v, d_lod_t, d_lod_off;
     int lod_rows[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    lsn::NormalsScratch nm;   // lsnLastMeshPlyNormals (under wire_mu too): the normals stage's scratch and the normals of the mesh it packs
+    lsn::DevBuf d_nm;
     bool warned_flags = false;
 };
 

@@ -167,6 +167,21 @@ int simplify(SimplifyScratch &ss, const char *who, int n_ticks, int n, long long
              void *d_triangles_out, int *d_tri_offsets_out, int *d_remap_out, hipStream_t s);
 int simplify_counts(SimplifyScratch &ss, const char *who, int tick, int *n_cells, int *n_unclustered, int *n_dropped_triangles, hipStream_t s);
 
+// Vertex normals (normals.hip): what one stage keeps between calls -- the sums, three planes [n_ticks][3][vertices per tick] of i64 (24 B
+// per vertex; the counted vertices are cleared by every call), and the counters behind lsnFusionNormalsDiagnostics, 16 B per tick.
+// Reserved by the first call, grown by a call that needs more.
+struct NormalsScratch {
+    DevBuf acc, cnt;
+    int last_ticks = 0;   // the ticks of the last call (0: none yet)
+};
+// lsnFusionNormals on any batch of meshes in lsnFusionRunMesh's layout (n sensors per offset row, tick_vert vertices and tick_tri
+// triangles per tick; d_normals_out: tick_vert x 3 floats per tick), and the counters of one tick of the last call with `ns`
+// (synchronises `s`).  The caller holds the lock that guards `ns` and has made its device current; `who` names the export in messages;
+// prof (nullable): the plan whose lsnFusionProfile brackets the face pass.
+int normals(NormalsScratch &ns, const char *who, int n_ticks, int n, long long tick_vert, long long tick_tri, const void *d_vertices,
+            const int *d_offsets, const void *d_triangles, const int *d_tri_offsets, void *d_normals_out, LsnFusion *prof, hipStream_t s);
+int normals_counts(NormalsScratch &ns, const char *who, int tick, int *n_used, int *n_skipped, int *n_zero_normals, hipStream_t s);
+
 // The refine pass (icp.hip) on ONE tick's merged cloud, resident on `device` and final: vertices -> packed points -> Gauss-Seidel loop.
 // offsets: the tick's n_sensors + 1 row on the HOST; Rt: n_sensors x 12 floats, receives {Rs[i][9], Ts[i][3]}; h_clouds (host) / d_clouds
 // (device), both nullable, receive the refined points.  Complete on return.  refine_compose: the pose composition of the reference's refine

@@ -722,6 +722,20 @@ template <int I> __device__ __forceinline__ void ply_vertex(unsigned *w, const u
     put8<15 * I + 14>(w, v.x >> 16);
 }
 
+template <int I> __device__ __forceinline__ void ply_vertex_normal(unsigned *w, const uint4 v, const float *n)
+{
+    // {X, Y, Z, nx, ny, nz, R, G, B} = 27 bytes (lsnPlyPackNormals; n: the vertex's three floats, null behind the last vertex)
+    put32<27 * I + 0>(w, v.y);
+    put32<27 * I + 4>(w, v.z);
+    put32<27 * I + 8>(w, v.w);
+    put32<27 * I + 12>(w, n ? __float_as_uint(n[0]) : 0u);
+    put32<27 * I + 16>(w, n ? __float_as_uint(n[1]) : 0u);
+    put32<27 * I + 20>(w, n ? __float_as_uint(n[2]) : 0u);
+    put8<27 * I + 24>(w, v.x);
+    put8<27 * I + 25>(w, v.x >> 8);
+    put8<27 * I + 26>(w, v.x >> 16);
+}
+
 template <int I> __device__ __forceinline__ void ply_face(unsigned *w, int a, int b, int c)
 {
     put8<13 * I + 0>(w, 3u);                                  // (byte)3, then the three indices (Utils.cs:259-262)
@@ -735,27 +749,38 @@ struct PlyHeader {
     char text[316];
 };
 
-// blocks [0, vb) : vertex records, [vb, vb+fb) : face records, last block: the header text
-__global__ __launch_bounds__(256) void ply_pack_kernel(const uint4 *__restrict__ verts, int nV, const int *__restrict__ tri, int nT,
-                                                        unsigned char *__restrict__ out, PlyHeader hdr, int vb, int fb)
+// blocks [0, vb) : vertex records, [vb, vb+fb) : face records, last block: the header text.  NORMALS: the vertex records carry the three
+// floats of `normals` between position and colour (27 bytes instead of 15); the face records and everything else are the same.
+template <bool NORMALS>
+__global__ __launch_bounds__(256) void ply_pack_kernel(const uint4 *__restrict__ verts, const float *__restrict__ normals, int nV,
+                                                        const int *__restrict__ tri, int nT, unsigned char *__restrict__ out, PlyHeader hdr,
+                                                        int vb, int fb)
 {
-    __shared__ unsigned lds[kItemsPerBlock * 15 / 4 + 1];
+    constexpr int VB = NORMALS ? 27 : 15;                      // bytes per vertex record; a lane's four are VB words
+    __shared__ unsigned lds[kItemsPerBlock * VB / 4 + 1];
     const int b = blockIdx.x;
     if (b < vb) {
         const int first = b * kItemsPerBlock, n = min(kItemsPerBlock, nV - first);
         const int i0 = first + 4 * threadIdx.x;
-        unsigned w[16];
+        unsigned w[VB + 1];
 #pragma unroll
-        for (int q = 0; q < 16; q++) w[q] = 0;
+        for (int q = 0; q < VB + 1; q++) w[q] = 0;
         const uint4 z = make_uint4(0, 0, 0, 0);
-        ply_vertex<0>(w, i0 + 0 < nV ? verts[i0 + 0] : z);
-        ply_vertex<1>(w, i0 + 1 < nV ? verts[i0 + 1] : z);
-        ply_vertex<2>(w, i0 + 2 < nV ? verts[i0 + 2] : z);
-        ply_vertex<3>(w, i0 + 3 < nV ? verts[i0 + 3] : z);
+        if constexpr (NORMALS) {
+            ply_vertex_normal<0>(w, i0 + 0 < nV ? verts[i0 + 0] : z, i0 + 0 < nV ? normals + 3 * (size_t)(i0 + 0) : nullptr);
+            ply_vertex_normal<1>(w, i0 + 1 < nV ? verts[i0 + 1] : z, i0 + 1 < nV ? normals + 3 * (size_t)(i0 + 1) : nullptr);
+            ply_vertex_normal<2>(w, i0 + 2 < nV ? verts[i0 + 2] : z, i0 + 2 < nV ? normals + 3 * (size_t)(i0 + 2) : nullptr);
+            ply_vertex_normal<3>(w, i0 + 3 < nV ? verts[i0 + 3] : z, i0 + 3 < nV ? normals + 3 * (size_t)(i0 + 3) : nullptr);
+        } else {
+            ply_vertex<0>(w, i0 + 0 < nV ? verts[i0 + 0] : z);
+            ply_vertex<1>(w, i0 + 1 < nV ? verts[i0 + 1] : z);
+            ply_vertex<2>(w, i0 + 2 < nV ? verts[i0 + 2] : z);
+            ply_vertex<3>(w, i0 + 3 < nV ? verts[i0 + 3] : z);
+        }
 #pragma unroll
-        for (int q = 0; q < 15; q++) lds[15 * threadIdx.x + q] = w[q];
+        for (int q = 0; q < VB; q++) lds[VB * threadIdx.x + q] = w[q];
         __syncthreads();
-        block_stream_store(out + hdr.len + 15ll * first, lds, 15 * n);
+        block_stream_store(out + hdr.len + (long long)VB * first, lds, VB * n);
     } else if (b < vb + fb) {
         const int first = (b - vb) * kItemsPerBlock, n = min(kItemsPerBlock, nT - first);
         const int i0 = first + 4 * threadIdx.x;
@@ -772,7 +797,7 @@ __global__ __launch_bounds__(256) void ply_pack_kernel(const uint4 *__restrict__
 #pragma unroll
         for (int q = 0; q < 13; q++) lds[13 * threadIdx.x + q] = w[q];
         __syncthreads();
-        block_stream_store(out + hdr.len + 15ll * nV + 13ll * first, lds, 13 * n);
+        block_stream_store(out + hdr.len + (long long)VB * nV + 13ll * first, lds, 13 * n);
     } else {
         for (int i = threadIdx.x; i < hdr.len; i += blockDim.x) out[i] = (unsigned char)hdr.text[i];
     }
@@ -1045,48 +1070,75 @@ long long lsnTransferPack(LsnTransfer *t, const void *d_vertices, int n_vertices
     });
 }
 
-static int ply_header(PlyHeader *h, int nV, int nT)
+static int ply_header(PlyHeader *h, int nV, int nT, bool normals)
 {
     h->len = snprintf(h->text, sizeof h->text,
                       "ply\nformat binary_little_endian 1.0\r\n"          // StreamWriter.WriteLine on Windows (Utils.cs:234)
                       "element vertex %d\n"
-                      "property float x\nproperty float y\nproperty float z\nproperty uchar red\nproperty uchar green\nproperty uchar blue\n"
+                      "property float x\nproperty float y\nproperty float z\n%sproperty uchar red\nproperty uchar green\nproperty uchar blue\n"
                       "element face %d\n"
                       "property list uchar int vertex_index\n"
-                      "end_header\n", nV, nT);
+                      "end_header\n", nV, normals ? "property float nx\nproperty float ny\nproperty float nz\n" : "", nT);
     return h->len > 0 && h->len < (int)sizeof h->text ? 0 : -1;
+}
+
+// lsnPlyBinaryBytes / lsnPlyNormalsBytes and lsnPlyPack / lsnPlyPackNormals: the same file with 15- or 27-byte vertex records.
+static long long ply_bytes(int n_vertices, int n_triangles, bool normals)
+{
+    PlyHeader h;
+    if (n_vertices < 0 || n_triangles < 0 || ply_header(&h, n_vertices, n_triangles, normals)) return -1;
+    return h.len + (normals ? 27ll : 15ll) * n_vertices + 13ll * n_triangles;
+}
+
+static long long ply_pack(const char *who, int device, const void *d_vertices, const void *d_normals, bool normals, int n_vertices,
+                          const int *d_triangles, int n_triangles, void *d_out, long long out_cap, void *stream)
+{
+    lsn::clear_error();
+    PlyHeader h;
+    if (n_vertices < 0 || n_triangles < 0 || ply_header(&h, n_vertices, n_triangles, normals)) { lsn::set_error("%s: bad counts", who); return -1; }
+    if ((n_vertices && (!d_vertices || (normals && !d_normals))) || (n_triangles && !d_triangles) || !d_out) { lsn::set_error("%s: null buffer", who); return -1; }
+    const long long need = h.len + (normals ? 27ll : 15ll) * n_vertices + 13ll * n_triangles;
+    if (need > out_cap) { lsn::set_error("%s: the file needs %lld bytes, the buffer holds %lld", who, need, out_cap); return -1; }
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) {
+        lsn::set_error("%s: no HIP device %d (this library has no CPU path)", who, device);
+        return -1;
+    }
+    LSN_HIP(hipSetDevice(device));
+    const int vb = (n_vertices + kItemsPerBlock - 1) / kItemsPerBlock, fb = (n_triangles + kItemsPerBlock - 1) / kItemsPerBlock;
+    if (normals)
+        ply_pack_kernel<true><<<vb + fb + 1, 256, 0, lsn::as_stream(stream)>>>(static_cast<const uint4 *>(d_vertices), static_cast<const float *>(d_normals),
+                                                                               n_vertices, d_triangles, n_triangles, static_cast<unsigned char *>(d_out), h, vb, fb);
+    else
+        ply_pack_kernel<false><<<vb + fb + 1, 256, 0, lsn::as_stream(stream)>>>(static_cast<const uint4 *>(d_vertices), nullptr, n_vertices, d_triangles,
+                                                                                n_triangles, static_cast<unsigned char *>(d_out), h, vb, fb);
+    LSN_HIP(hipGetLastError());
+    return need;
 }
 
 long long lsnPlyBinaryBytes(int n_vertices, int n_triangles)
 {
-    return lsn::guarded("lsnPlyBinaryBytes", -1LL, [&]() -> long long {
-        PlyHeader h;
-        if (n_vertices < 0 || n_triangles < 0 || ply_header(&h, n_vertices, n_triangles)) return -1;
-        return h.len + 15ll * n_vertices + 13ll * n_triangles;
-    });
+    return lsn::guarded("lsnPlyBinaryBytes", -1LL, [&]() -> long long { return ply_bytes(n_vertices, n_triangles, false); });
 }
 
 long long lsnPlyPack(int device, const void *d_vertices, int n_vertices, const int *d_triangles, int n_triangles, void *d_out,
                      long long out_cap, void *stream)
 {
     return lsn::guarded("lsnPlyPack", -1LL, [&]() -> long long {
-        lsn::clear_error();
-        PlyHeader h;
-        if (n_vertices < 0 || n_triangles < 0 || ply_header(&h, n_vertices, n_triangles)) { lsn::set_error("lsnPlyPack: bad counts"); return -1; }
-        if ((n_vertices && !d_vertices) || (n_triangles && !d_triangles) || !d_out) { lsn::set_error("lsnPlyPack: null buffer"); return -1; }
-        const long long need = h.len + 15ll * n_vertices + 13ll * n_triangles;
-        if (need > out_cap) { lsn::set_error("lsnPlyPack: the file needs %lld bytes, the buffer holds %lld", need, out_cap); return -1; }
-        int ndev = 0;
-        if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) {
-            lsn::set_error("lsnPlyPack: no HIP device %d (this library has no CPU path)", device);
-            return -1;
-        }
-        LSN_HIP(hipSetDevice(device));
-        const int vb = (n_vertices + kItemsPerBlock - 1) / kItemsPerBlock, fb = (n_triangles + kItemsPerBlock - 1) / kItemsPerBlock;
-        ply_pack_kernel<<<vb + fb + 1, 256, 0, lsn::as_stream(stream)>>>(static_cast<const uint4 *>(d_vertices), n_vertices, d_triangles, n_triangles,
-                                                                         static_cast<unsigned char *>(d_out), h, vb, fb);
-        LSN_HIP(hipGetLastError());
-        return need;
+        return ply_pack("lsnPlyPack", device, d_vertices, nullptr, false, n_vertices, d_triangles, n_triangles, d_out, out_cap, stream);
+    });
+}
+
+long long lsnPlyNormalsBytes(int n_vertices, int n_triangles)
+{
+    return lsn::guarded("lsnPlyNormalsBytes", -1LL, [&]() -> long long { return ply_bytes(n_vertices, n_triangles, true); });
+}
+
+long long lsnPlyPackNormals(int device, const void *d_vertices, const void *d_normals, int n_vertices, const int *d_triangles, int n_triangles,
+                            void *d_out, long long out_cap, void *stream)
+{
+    return lsn::guarded("lsnPlyPackNormals", -1LL, [&]() -> long long {
+        return ply_pack("lsnPlyPackNormals", device, d_vertices, d_normals, true, n_vertices, d_triangles, n_triangles, d_out, out_cap, stream);
     });
 }
 

@@ -37,7 +37,7 @@ class DeviceFusion:
         # (not cleared here: the benchmark and the drivers construct their plans this way; from_rigs() clears them)
         self.vertices = torch.empty((n_ticks, self.capacity, 16), dtype=torch.uint8, device=self.device)
         self.offsets = torch.full((n_ticks, self.n_maps + 1), SENTINEL, dtype=torch.int32, device=self.device)
-        self.depth = self.rgb = self.intr = self._triangles = self._tri_offsets = None
+        self.depth = self.rgb = self.intr = self._triangles = self._tri_offsets = self._normals = None
 
     @classmethod
     def from_rigs(cls, rigs, n_ticks=None, device=None, mode=0):
@@ -134,6 +134,17 @@ class DeviceFusion:
                            0 if points else triangles.data_ptr(), 0 if points else tri_offsets.data_ptr(), remap.data_ptr(),
                            _stream_handle(stream))
         return vertices, offsets, triangles, tri_offsets, remap
+
+    def normals(self, vertices=None, offsets=None, triangles=None, tri_offsets=None, stream=None):
+        """Vertex normals of the ticks' meshes -- the batch's own, or the four tensors handed in (simplify()'s first four outputs, say).
+        Returns float32 [T, capacity, 3], the batch's own tensor (allocated by the first call with every byte SENTINEL % 256, written again
+        by every call): a tick's normals lie at its vertices' indices, nothing behind its nVertices is written."""
+        if self._normals is None:
+            self._normals = torch.full((self.n_ticks, self.capacity, 12), SENTINEL % 256, dtype=torch.uint8, device=self.device).view(torch.float32)
+        self.plan.normals((self.vertices if vertices is None else vertices).data_ptr(), (self.offsets if offsets is None else offsets).data_ptr(),
+                          (self.triangles if triangles is None else triangles).data_ptr(),
+                          (self.tri_offsets if tri_offsets is None else tri_offsets).data_ptr(), self._normals.data_ptr(), _stream_handle(stream))
+        return self._normals
 
     def refine(self, tick, n_refine_iters=2, n_icp_iters=10, world_R=None, world_t=None, camera_R=None, camera_t=None, clouds_out=None,
                stream=None):

@@ -94,6 +94,8 @@ _PROTOTYPES = {
     "lsnFusionRenderDiagnostics": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp]),
     "lsnFusionSimplify": (_i, [_vp, _f] + [_vp] * 10),
     "lsnFusionSimplifyDiagnostics": (_i, [_vp, _i, _vp, _vp, _vp, _vp]),
+    "lsnFusionNormals": (_i, [_vp] * 7),
+    "lsnFusionNormalsDiagnostics": (_i, [_vp, _i, _vp, _vp, _vp, _vp]),
     "lsnFusionTilesPerTick": (_i, [_vp]),
     "lsnFusionPackSurvivors": (_i, [_vp] * 9),
     "lsnFusionReconstruct": (_i, [_vp, _i, _i, _vp, _vp, _vp, _ll, _vp, _vp, _vp, _vp, _vp]),
@@ -146,11 +148,14 @@ _PROTOTYPES = {
     "lsnTransferLastPath": (_i, [_vp]),
     "lsnPlyBinaryBytes": (_ll, [_i, _i]),
     "lsnPlyPack": (_ll, [_i, _vp, _i, _vp, _i, _vp, _ll, _vp]),
+    "lsnPlyNormalsBytes": (_ll, [_i, _i]),
+    "lsnPlyPackNormals": (_ll, [_i, _vp, _vp, _i, _vp, _i, _vp, _ll, _vp]),
     "lsnLastMeshTransferFrame": (_ll, [_vp, _ll]),
     "lsnLastMeshPly": (_ll, [_vp, _ll]),
     "lsnLastMeshRenderView": (_ll, [_vp, _vp, _i, _i, _i, _vp, _vp]),
     "lsnLastMeshTransferFrameLod": (_ll, [_f, _vp, _ll]),
     "lsnLastMeshPlyLod": (_ll, [_f, _vp, _ll]),
+    "lsnLastMeshPlyNormals": (_ll, [_f, _vp, _ll]),
     "lsnZstdAvailable": (_i, []),
     "lsnFrameParseHeader": (_i, [_vp, C.POINTER(FrameInfo)]),
     "lsnFrameDecode": (_ll, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _i, C.POINTER(_i)]),
@@ -696,6 +701,20 @@ class FusionPlan(_Handle):
                "lsnFusionSimplifyDiagnostics")
         return {"cells": c.value, "unclustered": u.value, "dropped_triangles": d.value}
 
+    def normals(self, d_vertices, d_offsets, d_triangles, d_tri_offsets, d_normals_out, stream=0):
+        """Vertex normals of every tick's merged mesh (run_mesh's layouts) into d_normals_out, float32 [n_ticks, capacity, 3]: area
+        weighted, summed as 64-bit integers, so bit-exact in any order.  Out of place; a mesh without triangles (d_triangles 0) is refused."""
+        _check(lib().lsnFusionNormals(self._h, d_vertices, d_offsets, d_triangles or None, d_tri_offsets or None, d_normals_out, stream or None),
+               "lsnFusionNormals")
+
+    def normals_diagnostics(self, tick=0, stream=0):
+        """The last normals() of one tick: {"used": triangles that were summed, "skipped": triangles with an index out of range or a face
+        component that is not finite and below 4096, "zero_normals": vertices whose normal is (0, 0, 0)}."""
+        u, k, z = C.c_int(0), C.c_int(0), C.c_int(0)
+        _check(lib().lsnFusionNormalsDiagnostics(self._h, int(tick), C.byref(u), C.byref(k), C.byref(z), stream or None),
+               "lsnFusionNormalsDiagnostics")
+        return {"used": u.value, "skipped": k.value, "zero_normals": z.value}
+
     def thresholds(self, capacity=None, stream=0, copy=True):
         """Builds the per-pixel depth thresholds now.  Returns (table uint32[capacity] or None, build_ms); table is None when
         the plan does not use thresholds ($LSN_NO_THRESHOLDS=1)."""
@@ -922,6 +941,18 @@ def ply_pack(device, d_vertices, n_vertices, d_triangles, n_triangles, d_out, ou
     return int(n)
 
 
+def ply_normals_bytes(n_vertices, n_triangles):
+    """The exact length of lsnPlyPackNormals' file: lsnPlyPack's with nx, ny, nz in the header and 27-byte vertex records."""
+    return int(lib().lsnPlyNormalsBytes(int(n_vertices), int(n_triangles)))
+
+
+def ply_pack_normals(device, d_vertices, d_normals, n_vertices, d_triangles, n_triangles, d_out, out_cap, stream=0):
+    require_gpu()
+    n = _nonneg(lib().lsnPlyPackNormals(int(device), d_vertices, d_normals, int(n_vertices), d_triangles or None, int(n_triangles), d_out,
+                                        int(out_cap), stream or None), "lsnPlyPackNormals")
+    return int(n)
+
+
 def _last_mesh(fn, what):
     require_gpu()
     cap = _nonneg(fn(None, 0), what)
@@ -949,6 +980,13 @@ def last_mesh_ply_lod(cell):
     """lsnLastMeshPlyLod: the binary PLY file image of that mesh after vertex clustering with cell size `cell` (<= 0: as it is)."""
     fn = lib().lsnLastMeshPlyLod
     return _last_mesh(lambda out, cap: fn(float(cell), out, cap), "lsnLastMeshPlyLod")
+
+
+def last_mesh_ply_normals(cell=0.0):
+    """lsnLastMeshPlyNormals: the binary PLY file image of that mesh with vertex normals, after vertex clustering with cell size `cell`
+    (<= 0: as it is).  A mesh without triangles is an error."""
+    fn = lib().lsnLastMeshPlyNormals
+    return _last_mesh(lambda out, cap: fn(float(cell), out, cap), "lsnLastMeshPlyNormals")
 
 
 def last_mesh_render_view(intr7, wt12, width, height, points_only=False):

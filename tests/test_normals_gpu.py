@@ -1,0 +1,319 @@
+"""lsnFusionNormals / lsnFusionNormalsDiagnostics / lsnPlyPackNormals / lsnLastMeshPlyNormals on the GPU against the CPU restatement
+(tests/normals_ref.py).
+
+Bar: bit-exact -- the normals of every tick equal the restatement's byte for byte and the diagnostics' three counts are equal; the output
+lies between guard bands in a buffer prefilled with 249, and nothing behind a tick's nVertices is written (tests/normals_cases.py
+check_device).  Every test fails without the feature (the exports are missing)."""
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+from livescan3d_amd import native, synth
+from tests import color_cases, merge_cases
+from tests.normals_cases import PREFILL, Clouds, check_device, cloud, tick, wrap_mesh
+from tests.support import ROOT, Guarded, child
+
+pytestmark = pytest.mark.gpu
+
+HAND_MADE = ("one_triangle", "reversed", "skipped_and_degenerate", "cancelling_pair", "rounding", "fan")
+
+
+def _check(c, **kw):
+    return check_device(c.torch, c.plan, c.v, c.off, c.t, c.toff, **kw)
+
+
+def _random_tick(rng, nv=64, nt=128, off=None, toff=None):
+    """A full tick of the 8 x 8 plan: random positions, random triples (a few out of range, a few degenerate)."""
+    tri = rng.integers(0, nv, (nt, 3)).astype(np.int32)
+    tri[rng.integers(0, nt, 4), rng.integers(0, 3, 4)] = [-1, nv, 2 ** 30, -2 ** 31]
+    tri[5] = tri[5, 0]
+    return cloud(rng.uniform(-2, 2, (nv, 3))), np.array(off or [0, nv], np.int32), tri, np.array(toff or [0, nt], np.int32)
+
+
+def test_hand_made_meshes(gpu):
+    """One 8 x 8 sensor (capacity 64 vertices / 128 triangles), a case per tick in one plan; what lies behind each tick's counts is
+    garbage (0x5A vertices, -3 indices) and must not be read.  The fan puts the adds of 126 triangles on one vertex."""
+    import torch
+    c = Clouds(torch, [tick(k) for k in HAND_MADE])
+    _, refs = _check(c)
+    by = dict(zip(HAND_MADE, refs))
+    assert by["one_triangle"]["normals"].tolist() == [[0, 0, -1]] * 3 and by["reversed"]["normals"].tolist() == [[0, 0, 1]] * 3
+    assert (by["skipped_and_degenerate"]["used"], by["skipped_and_degenerate"]["skipped"]) == (5, 7)
+    assert by["cancelling_pair"]["zero_normals"] == 3 and by["rounding"]["used"] == len(tick("rounding")[2])
+    assert by["fan"]["used"] == 126 and by["fan"]["zero_normals"] == 0
+    c.close()
+
+
+def test_wrap_around(gpu):
+    """2100 triangles of the largest face vector below 4096 on one vertex of a 48 x 48 sensor's plan (capacity 2304 / 4608): the sum
+    passes 2^63, and the normal follows the wrapped sum."""
+    import torch
+    xyz, tri = wrap_mesh()
+    c = Clouds(torch, [(cloud(xyz), np.array([0, len(xyz)], np.int32), tri, np.array([0, len(tri)], np.int32))], sizes=((48, 48),))
+    assert c.plan.capacity == 2304
+    _, refs = _check(c)
+    assert refs[0]["sums"][0, 2] < 0 and refs[0]["normals"][0, 2] == -1 and refs[0]["used"] == 2101
+    c.close()
+
+
+def test_full_capacity_empty_and_clipped_ticks(gpu):
+    """64 vertices and 128 triangles, the whole capacity: the last lanes of the last wave and workgroup.  An empty tick between two full
+    ones; a tick whose d_offsets[n_maps] and d_tri_offsets[n_maps] exceed the capacities (clipped); negative counts."""
+    import torch
+    rng = np.random.default_rng(5)
+    ticks = [_random_tick(rng), (cloud(np.zeros((0, 3))), np.array([0, 0], np.int32), np.zeros((0, 3), np.int32), np.array([0, 0], np.int32)),
+             _random_tick(rng), _random_tick(rng, off=[0, 64 + 5], toff=[0, 128 + 77]), _random_tick(rng, off=[0, -4], toff=[0, 128]),
+             _random_tick(rng, off=[0, 64], toff=[3, -1]), _random_tick(rng, 61, 127)]
+    c = Clouds(torch, ticks)
+    _, refs = _check(c)
+    assert [len(r["normals"]) for r in refs] == [64, 0, 64, 64, 0, 64, 61]
+    assert [r["used"] + r["skipped"] for r in refs] == [128, 0, 128, 128, 128, 0, 127] and refs[4]["used"] == 0 and refs[5]["zero_normals"] == 64
+    assert refs[0]["skipped"] >= 3 and refs[0]["used"] > 100
+    c.close()
+
+
+@pytest.fixture(scope="module")
+def ring_fusion(gpu):
+    from livescan3d_amd.fusion import DeviceFusion
+    rig = color_cases.ring(3, sizes=[(96, 80)] * 3)
+    fus = DeviceFusion.from_rigs([rig])
+    fus.run_mesh()
+    yield rig, fus
+    fus.close()
+
+
+def test_ring_plain_thin_method_and_twice_into_the_same_buffer(ring_fusion):
+    """The 3 x 96x80 ring through run_mesh -> normals; a second call into the same buffer gives the same bytes (the sums are cleared by
+    every call: nothing accumulates); DeviceFusion.normals returns the same normals in the batch's own prefilled tensor."""
+    import torch
+    _, fus = ring_fusion
+    out, refs = check_device(torch, fus.plan, fus.vertices, fus.offsets, fus.triangles, fus.tri_offsets)
+    assert fus.plan.normals_diagnostics(0) == {"used": 16924, "skipped": 0, "zero_normals": 1458}
+    first = out.body().clone()
+    check_device(torch, fus.plan, fus.vertices, fus.offsets, fus.triangles, fus.tri_offsets, out=out, refs=refs)
+    assert torch.equal(first, out.body())
+    n = fus.normals()
+    torch.cuda.synchronize()
+    nv = len(refs[0]["normals"])
+    assert n.dtype == torch.float32 and tuple(n.shape) == (1, fus.capacity, 3) and fus.normals() is n
+    assert n[0, :nv].cpu().numpy().tobytes() == refs[0]["normals"].tobytes()
+    assert (n[0, nv:].cpu().numpy().view(np.uint8) == PREFILL).all()
+
+
+def test_ring_after_simplify(ring_fusion):
+    """The outputs of simplify(0.05): the triangles are no grid triangles any more, and the vertices are used many times."""
+    import torch
+    _, fus = ring_fusion
+    v, off, t, toff, _ = fus.simplify(0.05)
+    _, refs = check_device(torch, fus.plan, v, off, t, toff)
+    assert len(refs[0]["normals"]) == 5040 and refs[0]["skipped"] == 0 and 0 < refs[0]["used"] < 16924
+    n = fus.normals(*fus.simplify(0.05)[:4])
+    torch.cuda.synchronize()
+    assert n[0, :5040].cpu().numpy().tobytes() == refs[0]["normals"].tobytes()
+
+
+def test_after_overlay_merge(gpu):
+    """The merge rewrites the triangles (the set-up of tests/test_simplify_gpu.py::test_after_overlay_merge)."""
+    import torch
+    from livescan3d_amd.fusion import DeviceFusion
+    rig = merge_cases.wall(4, 96, 80)
+    with DeviceFusion.from_rigs([rig]) as fus:
+        fus.run_mesh()
+        n_before = len(fus.tick_triangles(0))
+        _, before = check_device(torch, fus.plan, fus.vertices, fus.offsets, fus.triangles, fus.tri_offsets)
+        fus.overlay_merge()
+        torch.cuda.synchronize()
+        assert 0 < len(fus.tick_triangles(0)) < n_before
+        _, after = check_device(torch, fus.plan, fus.vertices, fus.offsets, fus.triangles, fus.tri_offsets)
+        assert 0 < after[0]["used"] and after[0]["used"] + after[0]["skipped"] == len(fus.tick_triangles(0))
+        assert after[0]["normals"].tobytes() != before[0]["normals"].tobytes()
+
+
+def test_a_second_plan_with_more_ticks(ring_fusion):
+    """Three ticks of different frames, the middle one without valid depth, after the one-tick plan has run."""
+    import copy
+    import torch
+    from livescan3d_amd.fusion import DeviceFusion
+    rigs = [color_cases.ring(3, sizes=[(96, 80)] * 3, tick=k) for k in range(3)]
+    rigs[1] = copy.copy(rigs[1])
+    rigs[1].depth_maps = np.zeros_like(rigs[1].depth_maps)
+    with DeviceFusion.from_rigs(rigs) as fus:
+        fus.run_mesh()
+        _, refs = check_device(torch, fus.plan, fus.vertices, fus.offsets, fus.triangles, fus.tri_offsets)
+        assert [len(r["normals"]) > 10000 for r in refs] == [True, False, True] and len(refs[1]["normals"]) == 0
+        assert refs[0]["normals"].tobytes() != refs[2]["normals"].tobytes()
+    _, fus1 = ring_fusion
+    check_device(torch, fus1.plan, fus1.vertices, fus1.offsets, fus1.triangles, fus1.tri_offsets)      # and the first plan still works
+
+
+def test_refusals(ring_fusion):
+    """A null argument, d_triangles == NULL and an output that overlaps an input: -1, a message, and no output byte touched."""
+    import torch
+    _, fus = ring_fusion
+    plan, cap = fus.plan, fus.capacity
+    out = Guarded(torch, cap * 12, "cuda")
+    out.body().fill_(PREFILL)
+    before = fus.vertices.clone()
+    good = {"v": fus.vertices.data_ptr(), "off": fus.offsets.data_ptr(), "t": fus.triangles.data_ptr(), "toff": fus.tri_offsets.data_ptr(), "out": out.ptr}
+
+    def refused(msg, **ptrs):
+        a = dict(good, **ptrs)
+        with pytest.raises(native.NativeUtilsError, match=msg):
+            plan.normals(a["v"], a["off"], a["t"], a["toff"], a["out"])
+
+    refused("null", v=0)
+    refused("null", off=0)
+    refused("null", toff=0)
+    refused("null", out=0)
+    refused("d_triangles", t=0)
+    refused("overlaps d_vertices", out=fus.vertices.data_ptr())
+    refused("overlaps d_vertices", out=fus.vertices.data_ptr() + 16 * cap - 4)         # the last input bytes under the first output ones
+    refused("overlaps d_vertices", v=out.ptr + 12 * cap - 4)
+    refused("overlaps d_triangles", out=fus.triangles.data_ptr() + 12)
+    refused("overlaps", out=fus.offsets.data_ptr())
+    torch.cuda.synchronize()
+    assert out.intact() and bool((out.body() == PREFILL).all().item()) and torch.equal(before, fus.vertices)
+    L = native.lib()
+    assert L.lsnFusionNormals(None, good["v"], good["off"], good["t"], good["toff"], good["out"], None) == -1 and "null" in native.last_error()
+    assert L.lsnFusionNormalsDiagnostics(None, 0, None, None, None, None) == -1
+    fresh = native.FusionPlan(0, 1, [8], [8])
+    with pytest.raises(native.NativeUtilsError, match="no normals have been computed"):
+        fresh.normals_diagnostics(0)
+    fresh.close()
+    check_device(torch, plan, fus.vertices, fus.offsets, fus.triangles, fus.tri_offsets)
+    with pytest.raises(native.NativeUtilsError, match="last call had 1 ticks"):
+        plan.normals_diagnostics(1)
+    assert L.lsnFusionNormalsDiagnostics(plan._h, 0, None, None, None, None) == 0         # any pointer may be NULL
+
+
+def ply_with_normals(v, n, t):
+    """The numpy packer: lsnPlyPack's header with nx, ny, nz between z and red, 27-byte vertex records, 13-byte face records."""
+    header = (f"ply\nformat binary_little_endian 1.0\r\nelement vertex {len(v)}\nproperty float x\nproperty float y\nproperty float z\n"
+              "property float nx\nproperty float ny\nproperty float nz\nproperty uchar red\nproperty uchar green\nproperty uchar blue\n"
+              f"element face {len(t)}\nproperty list uchar int vertex_index\nend_header\n").encode()
+    vr = np.zeros(len(v), np.dtype([("p", "<f4", 3), ("n", "<f4", 3), ("c", "u1", 3)]))
+    assert vr.dtype.itemsize == 27
+    vr["p"] = np.stack([v["X"], v["Y"], v["Z"]], axis=1)
+    vr["n"] = np.asarray(n, np.float32).reshape(-1, 3)
+    vr["c"] = np.stack([v["R"], v["G"], v["B"]], axis=1)
+    fr = np.zeros(len(t), np.dtype([("k", "u1"), ("i", "<i4", 3)]))
+    assert fr.dtype.itemsize == 13
+    fr["k"], fr["i"] = 3, np.asarray(t, np.int32).reshape(-1, 3)
+    return header + vr.tobytes() + fr.tobytes()
+
+
+def test_ply_pack_normals(ring_fusion, orc):
+    """lsnPlyPackNormals against the numpy packer, byte for byte, at every alignment of the output; the plain lsnPlyPack of the same mesh
+    is what it was."""
+    import torch
+    _, fus = ring_fusion
+    n = fus.normals()
+    torch.cuda.synchronize()
+    v, _ = fus.tick_cloud(0)
+    t = fus.tick_triangles(0)
+    hn = n[0, :len(v)].cpu().numpy()
+    for nv, nt in ((len(v), len(t)), (1025, 1023), (3, 1), (0, 0)):
+        want = ply_with_normals(v[:nv], hn[:nv], t[:nt])
+        need = native.ply_normals_bytes(nv, nt)
+        assert need == len(want)
+        for shift in (0, 1, 3):
+            buf = Guarded(torch, need + shift, "cuda")
+            buf.body().fill_(PREFILL)
+            assert native.ply_pack_normals(0, fus.vertices.data_ptr(), n.data_ptr(), nv, fus.triangles.data_ptr(), nt, buf.ptr + shift, need) == need
+            torch.cuda.synchronize()
+            assert buf.intact() and buf.body()[shift:].cpu().numpy().tobytes() == want, (nv, nt, shift)
+    need = native.ply_binary_bytes(len(v), len(t))
+    plain = torch.zeros(need, dtype=torch.uint8, device="cuda")
+    assert native.ply_pack(0, fus.vertices.data_ptr(), len(v), fus.triangles.data_ptr(), len(t), plain.data_ptr(), need) == need
+    torch.cuda.synchronize()
+    assert plain.cpu().numpy().tobytes() == orc.ply_binary(v, t)
+    small = torch.zeros(64, dtype=torch.uint8, device="cuda")
+    with pytest.raises(native.NativeUtilsError, match="buffer holds"):
+        native.ply_pack_normals(0, fus.vertices.data_ptr(), n.data_ptr(), 3, fus.triangles.data_ptr(), 1, small.data_ptr(), 64)
+    with pytest.raises(native.NativeUtilsError, match="null"):
+        native.ply_pack_normals(0, fus.vertices.data_ptr(), 0, 3, fus.triangles.data_ptr(), 1, small.data_ptr(), 4096)
+
+
+CHILD = r"""
+import sys
+sys.path.insert(0, sys.argv[1])
+import numpy as np
+from livescan3d_amd import native
+from tests import color_cases, normals_ref, simplify_ref
+from tests.test_normals_gpu import ply_with_normals
+rig = color_cases.ring(3, sizes=[(96, 80)] * 3)
+try:
+    native.last_mesh_ply_normals(0.0)
+    first = "packed"
+except native.NativeUtilsError as ex:
+    first = str(ex)
+v, t = native.generate_mesh_from_depth_maps(rig.depth_maps, rig.depth_colors, rig.widths, rig.heights, rig.intr, rig.wt, rig.bounds)
+plain = native.last_mesh_ply()
+n = normals_ref.normals(v, [0, len(v)], t, [0, len(t)])["normals"]
+got = native.last_mesh_ply_normals(0.0)
+ok = [got == ply_with_normals(v, n, t), native.last_mesh_ply_normals(float("nan")) == got, native.last_mesh_ply_normals(-1.0) == got]
+r = simplify_ref.simplify(v, [0, len(v)], t, [0, len(t)], 0.05)
+rn = normals_ref.normals(r["vertices"], [0, len(r["vertices"])], r["triangles"], [0, len(r["triangles"])])["normals"]
+lod = native.last_mesh_ply_normals(0.05)
+ok += [lod == ply_with_normals(r["vertices"], rn, r["triangles"]), len(lod) < len(got)]
+L = native.lib()
+ok += [L.lsnLastMeshPlyNormals(0.05, None, 0) == len(got) == native.ply_normals_bytes(len(v), len(t))]
+ok += [native.last_mesh_ply() == plain, native.last_mesh_ply_normals(0.0) == got]          # the resident mesh is as it was
+small = np.zeros(100, np.uint8)
+ok += [L.lsnLastMeshPlyNormals(0.0, small.ctypes.data, 100) == -1 and "buffer holds" in native.last_error()]
+native.generate_vertices_from_depth_map(rig.depth_maps, rig.depth_colors, rig.widths, rig.heights, rig.intr, rig.wt, rig.bounds, 0)
+try:
+    native.last_mesh_ply_normals(0.0)
+    last = "packed"
+except native.NativeUtilsError as ex:
+    last = str(ex)
+print("RESULT", "".join(str(int(x)) for x in ok), len(v), repr(first), "|", repr(last))
+"""
+
+
+def test_last_mesh_ply_normals(gpu):
+    """A fresh process: no mesh yet -> -1; after generateMeshFromDepthMaps on the ring, cell = 0 (and NaN, and -1): positions, colours and
+    faces are lsnLastMeshPly's, the normals the restatement's; cell = 0.05: the restatement of simplify followed by normals; out == NULL:
+    the bound; the resident mesh unchanged; after a vertices-only call -1 with a message."""
+    line = child(CHILD, {}, ROOT)[0]
+    head, _, tail = line.partition(" | ")
+    parts = head.split(" ", 3)
+    assert parts[0] == "RESULT" and parts[1] == "1" * 9 and parts[2] == "11087", line
+    assert "no mesh is resident" in parts[3] and "no triangles" in tail, line
+
+
+def test_stream_example_writes_a_ply_with_normals(gpu, tmp_path):
+    """examples/stream --normals [--lod CELL]: the PLY's header declares nx, ny, nz, its length is the header's counts' and its normals
+    are unit vectors or zero."""
+    subprocess.check_call(["make", "-C", os.path.join(ROOT, "examples"), "stream"], stdout=subprocess.DEVNULL)
+    n, w, h = 2, 96, 80
+    rig = synth.make_rig("scene", n, w, h, seed=21, bounds=synth.CROP_BOUNDS)
+    recs = []
+    for i in range(n):
+        depth = rig.depth_maps.view(np.uint16)[i * w * h:(i + 1) * w * h].reshape(h, w)
+        rgb = rig.depth_colors[3 * i * w * h:3 * (i + 1) * w * h].reshape(h, w, 3)
+        path = tmp_path / f"rec{i}.bin"
+        path.write_bytes(native.recording_append(native.frame_encode(depth, rgb, None, 0), 0))
+        recs.append(str(path))
+    calib = np.concatenate([np.concatenate([rig.intr[7 * i:7 * i + 7], rig.wt[12 * i:12 * i + 12]]) for i in range(n)]).astype(np.float32)
+    (tmp_path / "calib.bin").write_bytes(calib.tobytes())
+    sizes = []
+    for extra in ([], ["--lod", "0.05"]):
+        out = subprocess.run([os.path.join(ROOT, "examples", "stream"), "--calib", str(tmp_path / "calib.bin"), "--bounds",
+                              *[str(float(x)) for x in synth.CROP_BOUNDS], "--normals", *extra, "--ply", str(tmp_path / "mesh.ply"), *recs],
+                             capture_output=True, text=True, timeout=120)
+        assert out.returncode == 0 and "1 ticks" in out.stdout, out.stdout + out.stderr
+        blob = (tmp_path / "mesh.ply").read_bytes()
+        end = blob.index(b"end_header\n") + len(b"end_header\n")
+        lines = blob[:end].decode().split("\n")
+        assert lines[1] == "format binary_little_endian 1.0\r" and lines[3:12] == [f"property {k}" for k in (
+            "float x", "float y", "float z", "float nx", "float ny", "float nz", "uchar red", "uchar green", "uchar blue")]
+        nv, nt = int(lines[2].split()[-1]), int(lines[12].split()[-1])
+        assert nv > 100 and nt > 100 and len(blob) == end + 27 * nv + 13 * nt == native.ply_normals_bytes(nv, nt)
+        rec = np.frombuffer(blob, np.dtype([("p", "<f4", 3), ("n", "<f4", 3), ("c", "u1", 3)]), nv, end)
+        length = np.sqrt((rec["n"].astype(np.float64) ** 2).sum(axis=1))
+        assert ((np.abs(length - 1) < 1e-6) | (length == 0)).all() and (length > 0).sum() > nv // 2
+        sizes.append(nv)
+    assert sizes[1] < sizes[0]
