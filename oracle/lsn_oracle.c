@@ -630,7 +630,17 @@ float orc_icp(const float *verts1, float *verts2, int n1, int n2,
             mk++;
         }
 
-        if (mk == 0) break;   /* cv::reduce on an empty matrix would throw across the ABI; stop instead */
+        if (mk == 0) {        /* cv::reduce on an empty matrix would throw across the ABI; stop instead */
+            if (trace) {      /* what was counted before stopping, and "no motion" as the kernels' trace states it: T = 0, Rn = I */
+                trace[iter].n_matched = m;
+                trace[iter].n_kept = 0;
+                trace[iter].mean = mean;
+                trace[iter].stddev = sd;
+                for (int c = 0; c < 3; c++) trace[iter].T[c] = 0;
+                for (int k = 0; k < 9; k++) trace[iter].Rn[k] = (k % 4 == 0) ? 1.0f : 0.0f;
+            }
+            break;
+        }
 
         /* :141 cv::reduce(matched1 - matched2, tempT, 0, CV_REDUCE_AVG): f32 element-wise difference,
          * f32 column sums top to bottom, then scaled by (float)(1.0/rows). */
