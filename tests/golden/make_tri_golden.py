@@ -16,6 +16,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)
 sys.path.insert(0, ROOT)
 from livescan3d_amd import synth  # noqa: E402
 from oracle import orc  # noqa: E402
+from tests import tri_cases  # noqa: E402
 
 OUT = os.path.dirname(os.path.abspath(__file__))
 
@@ -53,8 +54,25 @@ def cases():
     return out
 
 
+def boundary():
+    """tri_boundary_ref.npz: the boundary frames of tests/tri_cases.py (the general frame with both backgrounds, the hand-made and
+    vertex-less stencils, the write-pass frames), their pixel -> vertex maps from the oracle's createVertices under each frame's box, and
+    what the reference's generateTrianglesGradients returns for them."""
+    blob, names = {}, []
+    for f in tri_cases.fixture_frames():
+        p2v = tri_cases.p2v_of(orc, f).astype(np.int32)
+        tri = orc.ref_triangles(f.depth, p2v)
+        blob[f.name + "_depth"], blob[f.name + "_p2v"], blob[f.name + "_tri"] = f.depth, p2v, tri
+        names.append(f.name)
+        print(f"{f.name}: {len(tri)} triangles")
+    blob["names"] = np.array(names)
+    np.savez_compressed(os.path.join(OUT, "tri_boundary_ref.npz"), **blob)
+    print("wrote tri_boundary_ref.npz", os.path.getsize(os.path.join(OUT, "tri_boundary_ref.npz")), "bytes")
+
+
 def main():
     assert orc.have_ref_tri(), "oracle/_ref/libref_tri.so missing: run `make -C oracle` where /root/reference exists"
+    boundary()
     blob = {}
     names = []
     for name, depth, p2v in cases():

@@ -1,6 +1,6 @@
 """The oracle's triangulation (oracle/lsn_oracle.c::orc_generate_triangles) against an independent pure-Python
-restatement of MeshGenerator::generateTrianglesGradients (src/NativeUtils/meshGenerator.cpp:14-181), including the
-4-thread row-band split the reference uses (:147-181), on small frames -- and, the pin proper, against the REFERENCE's
+restatement of MeshGenerator::generateTrianglesGradients (tests/tri_ref.py: src/NativeUtils/meshGenerator.cpp:14-181, including the
+4-thread row-band split the reference uses, :147-181), on small frames -- and, the pin proper, against the REFERENCE's
 own meshGenerator.cpp: committed fixtures made by tests/golden/make_tri_golden.py from oracle/_ref/libref_tri.so, plus
 a wider live sweep (up to 512x424) whenever that compiled reference is present."""
 import os
@@ -9,60 +9,7 @@ import numpy as np
 import pytest
 
 from livescan3d_amd import synth
-
-
-def py_check(depth, p1, p2, p3):
-    vals = [int(depth[p1]), int(depth[p2]), int(depth[p3])]
-    ptrs = [p1, p2, p3]
-    if 0 in vals:
-        return False
-    thr = int((vals[0] + vals[1] + vals[2]) / 3.0 * 0.00272 + 7.273)
-    for a, b in ((0, 1), (1, 2), (2, 0)):
-        v1, v2 = vals[a], vals[b]
-        if abs(v1 - v2) < thr:
-            continue
-        shift = ptrs[b] - ptrs[a]
-        vf = int(depth[ptrs[b] + shift])
-        if vf != 0 and abs(v2 - v1 - (vf - v2)) < thr:
-            continue
-        vb = int(depth[ptrs[a] - shift])
-        if vb != 0 and abs(v2 - v1 - (v1 - vb)) < thr:
-            continue
-        return False
-    return True
-
-
-def py_region(depth, p2v, w, h, min_y, max_y, out):
-    min_x, max_x = 1, w - 2
-    min_y, max_y = max(min_y, 2), min(max_y, h - 2)
-    up, upright, right = -w, -w + 1, 1
-    tshift = [(right, up, 0), (right, upright, up), (0, upright, up), (0, right, upright)]
-    for y in range(min_y, max_y):
-        for x in range(min_x, max_x):
-            p = y * w + x
-            if p2v[p] == -1:
-                continue
-            tr = [py_check(depth, p, p + up, p + right), py_check(depth, p + right, p + up, p + upright), False, False]
-            if not tr[0] and not tr[1]:
-                tr[2] = py_check(depth, p, p + up, p + upright)
-                tr[3] = py_check(depth, p, p + upright, p + right)
-            for i in range(4):
-                if tr[i]:
-                    m = [int(p2v[p + s]) for s in tshift[i]]
-                    if -1 not in m:
-                        out.append(m)
-
-
-def py_triangles(depth2d, p2v):
-    h, w = depth2d.shape
-    depth = depth2d.ravel()
-    out = []
-    step, pos = h // 4 + 1, 0                       # generateTrianglesGradients :147-181: 4 bands, concatenated in order
-    for _ in range(4):
-        size = min(step, h - pos)
-        py_region(depth, p2v, w, h, pos, pos + size, out)
-        pos += size
-    return np.array(out, dtype=np.int32).reshape(-1, 3)
+from tests.tri_ref import py_triangles
 
 
 @pytest.mark.parametrize("w,h", [(40, 30), (33, 21), (64, 9), (5, 5), (8, 4)])
