@@ -530,64 +530,95 @@ extern "C" float ICP(Point3f *verts1, Point3f *verts2, int nVerts1, int nVerts2,
 // ---- the outbound formats of the mesh the last merge call left in HBM (include/NativeUtils.h part 3) ----------------------------
 
 namespace {
-// requires the lane's lock; kind 0 = TransferSocket.SendFrame stream, 1 = binary PLY file image, 2 = that file with vertex normals; cell:
-// null = the mesh as it is, else it goes through the level-of-detail stage first (simplify.hip; the mesh is one tick of one "sensor" whose
-// offset rows are its two counts), in HBM, and the packers read what that left.  Kind 2 (cell given; <= 0 or NaN skips the level of detail)
-// then runs the normals stage (normals.hip) on the same one tick.
-long long last_mesh_bytes(Ctx &c, Lane &l, int kind, const float *cell, unsigned char *out, long long out_cap)
-{
-    if (ensure_ready(c)) return -1;
-    if (l.last_nv < 0) {
-        lsn::set_error("lsnLastMesh*: no mesh is resident (call generateMeshFromDepthMaps / generateVerticesFromDepthMap first)");
-        return -1;
+// The exports below as steps on the mesh the calling thread's last mesh call left: the lane is picked and locked here; `resident` says
+// whether there is a mesh (from then on nv / nt are its counts, and a call that only asks for a length is answered); `open` puts it into
+// HBM and makes it a batch of one tick of one "sensor" whose offset rows are its two counts; `lod` and `normals` run their stage on what
+// the step before left, `render`, `frame` and `ply` bring the result home.  Locks: the lane's, then c.wire_mu from `open` on.
+struct LastMesh {
+    Ctx &c;
+    Lane &l;
+    std::lock_guard<std::mutex> lane_lock;
+    std::unique_lock<std::mutex> wire_lock;
+    int nv = 0, nt = 0;              // the mesh the next step sees ...
+    int nv0 = 0, nt0 = 0;            // ... and its strides: the resident mesh's counts (the simplified mesh keeps them)
+    const void *d_v = nullptr;
+    const int *d_t = nullptr, *d_rows = nullptr;   // d_rows: {0, nv}, {0, nt} on the device
+
+    static Lane &pick(Ctx &c)
+    {
+        Lane *l = t_last_lane ? t_last_lane : c.last_lane.load();   // this thread's own last mesh call, else the process's
+        return l ? *l : c.merge;
     }
-    int nv = l.last_nv, nt = l.last_nt;
-    if (kind == 2 && nt <= 0) {
-        lsn::set_error("lsnLastMeshPlyNormals: the resident mesh has no triangles (the normals of a bare point cloud are not defined)");
-        return -1;
-    }
-    long long bound = kind == 0 ? lsnTransferFrameBound(nv, nt) : kind == 1 ? lsnPlyBinaryBytes(nv, nt) : lsnPlyNormalsBytes(nv, nt);
-    // with cell an upper bound: fewer vertices and triangles are never longer, except that a mesh that loses every triangle leaves as points
-    if (cell && kind == 0) bound = std::max(bound, lsnTransferFrameBound(nv, 0));
-    if (!out) return bound;
-    if (materialize(l)) return -1;
-    std::lock_guard<std::mutex> wg(c.wire_mu);
-    if (c.d_wire.reserve((size_t)bound + 16)) return -1;
-    const void *d_v = l.d_out.p;
-    const int *d_t = l.d_tri.as<int>();
-    const int *d_rows = nullptr;            // kind 2: the offset rows {0, nVertices}, {0, nTriangles} of what the packer will read
-    const int nv0 = nv, nt0 = nt;           // ... and its strides
-    if (kind == 2) {
-        LSN_HIP(hipSetDevice(l.device));
-        if (c.d_lod_off.reserve(sizeof(c.lod_rows))) return -1;
-        c.lod_rows[0] = 0; c.lod_rows[1] = nv; c.lod_rows[2] = 0; c.lod_rows[3] = nt;
-        LSN_HIP(hipMemcpyAsync(c.d_lod_off.p, c.lod_rows, 4 * sizeof(int), hipMemcpyHostToDevice, l.stream));
-        d_rows = c.d_lod_off.as<int>();
-    }
-    if (cell && nv > 0 && (kind != 2 || *cell > 0.0f)) {
-        const char *who = kind == 0 ? "lsnLastMeshTransferFrameLod" : kind == 1 ? "lsnLastMeshPlyLod" : "lsnLastMeshPlyNormals";
-        LSN_HIP(hipSetDevice(l.device));
-        if (c.d_lod_v.reserve(16 * (size_t)nv) || c.d_lod_t.reserve(12 * (size_t)(nt > 0 ? nt : 1)) || c.d_lod_off.reserve(sizeof(c.lod_rows))) return -1;
-        int *rows = c.d_lod_off.as<int>();   // {0, nVertices}, {0, nTriangles} in; the same two rows out
-        c.lod_rows[0] = 0; c.lod_rows[1] = nv; c.lod_rows[2] = 0; c.lod_rows[3] = nt;
-        LSN_HIP(hipMemcpyAsync(rows, c.lod_rows, 4 * sizeof(int), hipMemcpyHostToDevice, l.stream));
-        if (lsn::simplify(c.sp, who, 1, 1, nv, nt > 0 ? nt : 0, *cell, d_v, rows, nt > 0 ? d_t : nullptr, rows + 2, c.d_lod_v.p, rows + 4,
-                          c.d_lod_t.p, rows + 6, nullptr, l.stream))
+    LastMesh() : c(ctx()), l(pick(c)), lane_lock(l.mu) {}
+
+    int resident()
+    {
+        if (ensure_ready(c)) return -1;
+        if (l.last_nv < 0) {
+            lsn::set_error("lsnLastMesh*: no mesh is resident (call generateMeshFromDepthMaps / generateVerticesFromDepthMap first)");
             return -1;
-        LSN_HIP(hipMemcpyAsync(c.lod_rows + 4, rows + 4, 4 * sizeof(int), hipMemcpyDeviceToHost, l.stream));
+        }
+        nv = nv0 = l.last_nv;
+        nt = nt0 = l.last_nt;
+        return 0;
+    }
+    int open(long long wire_bytes = 0)   // wire_bytes: what a packer may write
+    {
+        if (materialize(l)) return -1;
+        wire_lock = std::unique_lock<std::mutex>(c.wire_mu);
+        if (wire_bytes > 0 && c.d_wire.reserve((size_t)wire_bytes + 16)) return -1;
+        LSN_HIP(hipSetDevice(l.device));
+        if (c.d_mesh_rows.reserve(sizeof(c.mesh_rows))) return -1;
+        c.mesh_rows[0] = 0; c.mesh_rows[1] = nv; c.mesh_rows[2] = 0; c.mesh_rows[3] = nt;
+        LSN_HIP(hipMemcpyAsync(c.d_mesh_rows.p, c.mesh_rows, 4 * sizeof(int), hipMemcpyHostToDevice, l.stream));
+        d_v = l.d_out.p;
+        d_t = l.d_tri.as<int>();
+        d_rows = c.d_mesh_rows.as<int>();
+        return 0;
+    }
+    lsn::MeshBatch batch(bool points_only = false) const
+    {
+        return {static_cast<const uint4 *>(d_v), d_rows, nt0 > 0 && !points_only ? d_t : nullptr, d_rows + 2, nv0, nt0 > 0 ? nt0 : 0, 1, 1};
+    }
+    // the level of detail (simplify.hip), in HBM: the later steps see the simplified mesh and the rows the stage wrote
+    int lod(const char *who, float cell)
+    {
+        if (nv <= 0) return 0;
+        if (c.d_lod_v.reserve(16 * (size_t)nv) || c.d_lod_t.reserve(12 * (size_t)(nt > 0 ? nt : 1))) return -1;
+        int *out_rows = c.d_mesh_rows.as<int>() + 4;
+        if (lsn::simplify(c.sp, who, batch(), cell, c.d_lod_v.p, out_rows, c.d_lod_t.p, out_rows + 2, nullptr, l.stream)) return -1;
+        LSN_HIP(hipMemcpyAsync(c.mesh_rows + 4, out_rows, 4 * sizeof(int), hipMemcpyDeviceToHost, l.stream));
         LSN_HIP(hipStreamSynchronize(l.stream));
-        nv = c.lod_rows[5];
-        if (nt > 0) nt = c.lod_rows[7];
+        nv = c.mesh_rows[5];
+        if (nt > 0) nt = c.mesh_rows[7];
         d_v = c.d_lod_v.p;
         d_t = c.d_lod_t.as<int>();
-        d_rows = rows + 4;
+        d_rows = out_rows;
+        return 0;
     }
-    if (kind == 2) {   // (the simplified mesh keeps the strides nv0 / nt0; one tick, so only the clipping sees them)
+    // the vertex normals (normals.hip) of that mesh into c.d_nm
+    int normals(const char *who)
+    {
         if (c.d_nm.reserve(12 * (size_t)(nv0 > 0 ? nv0 : 1))) return -1;
-        if (lsn::normals(c.nm, "lsnLastMeshPlyNormals", 1, 1, nv0, nt0, d_v, d_rows, d_t, d_rows + 2, c.d_nm.p, nullptr, l.stream)) return -1;
+        return lsn::normals(c.nm, who, batch(), c.d_nm.p, nullptr, l.stream);
     }
-    long long n = -1;
-    if (kind == 0) {
+    // one view of it (render.hip) into the host arrays; the pixels with depth != 0
+    long long render(const char *who, const float *intr7, const float *wt12, int width, int height, bool points_only, unsigned char *depth_out,
+                     unsigned char *colors_out)
+    {
+        const size_t npix = (size_t)(width > 0 ? width : 0) * (size_t)(height > 0 ? height : 0);
+        if (c.d_rv_img.reserve(5 * npix + 16)) return -1;
+        unsigned char *d_depth = c.d_rv_img.as<unsigned char>(), *d_col = d_depth + 2 * npix;
+        if (lsn::render_views(c.rv, who, batch(points_only), 1, intr7, wt12, width, height, d_depth, d_col, l.stream)) return -1;
+        LSN_HIP(hipMemcpyAsync(depth_out, d_depth, 2 * npix, hipMemcpyDeviceToHost, l.stream));
+        LSN_HIP(hipMemcpyAsync(colors_out, d_col, 3 * npix, hipMemcpyDeviceToHost, l.stream));
+        int n_pixels = 0;
+        if (lsn::render_counts(c.rv, who, 0, 0, nullptr, nullptr, &n_pixels, l.stream)) return -1;   // synchronises
+        return n_pixels;
+    }
+    // the TransferSocket.SendFrame stream of it, at most `bound` bytes, into out
+    long long frame(long long bound, unsigned char *out, long long out_cap)
+    {
         if (!c.xfer || nv > c.xfer_v || nt > c.xfer_t) {
             if (c.xfer) lsnTransferDestroy(c.xfer);
             c.xfer_v = nv > c.xfer_v ? nv : c.xfer_v;
@@ -598,33 +629,42 @@ long long last_mesh_bytes(Ctx &c, Lane &l, int kind, const float *cell, unsigned
                 return -1;
             }
         }
-        n = lsnTransferPack(c.xfer, d_v, nv, nt > 0 ? d_t : nullptr, nt, c.d_wire.p, bound, l.stream);
-    } else if (kind == 1) {
-        n = lsnPlyPack(c.device, d_v, nv, nt > 0 ? d_t : nullptr, nt, c.d_wire.p, bound, l.stream);
-    } else {
-        n = lsnPlyPackNormals(c.device, d_v, c.d_nm.p, nv, nt > 0 ? d_t : nullptr, nt, c.d_wire.p, bound, l.stream);
+        return home(lsnTransferPack(c.xfer, d_v, nv, nt > 0 ? d_t : nullptr, nt, c.d_wire.p, bound, l.stream), out, out_cap);
     }
-    if (n < 0) return -1;
-    if (n > out_cap) {
-        (void)hipStreamSynchronize(l.stream);
-        lsn::set_error("lsnLastMesh*: the result is %lld bytes, the buffer holds %lld", n, out_cap);
-        return -1;
+    // the binary PLY file image of it, with the normals of c.d_nm if asked
+    long long ply(long long bound, bool with_normals, unsigned char *out, long long out_cap)
+    {
+        const int *tri = nt > 0 ? d_t : nullptr;
+        return home(with_normals ? lsnPlyPackNormals(c.device, d_v, c.d_nm.p, nv, tri, nt, c.d_wire.p, bound, l.stream)
+                                 : lsnPlyPack(c.device, d_v, nv, tri, nt, c.d_wire.p, bound, l.stream),
+                    out, out_cap);
     }
-    LSN_HIP(hipMemcpyAsync(out, c.d_wire.p, (size_t)n, hipMemcpyDeviceToHost, l.stream));
-    LSN_HIP(hipStreamSynchronize(l.stream));
-    return n;
-}
+    long long home(long long n, unsigned char *out, long long out_cap)
+    {
+        if (n < 0) return -1;
+        if (n > out_cap) {
+            (void)hipStreamSynchronize(l.stream);
+            lsn::set_error("lsnLastMesh*: the result is %lld bytes, the buffer holds %lld", n, out_cap);
+            return -1;
+        }
+        LSN_HIP(hipMemcpyAsync(out, c.d_wire.p, (size_t)n, hipMemcpyDeviceToHost, l.stream));
+        LSN_HIP(hipStreamSynchronize(l.stream));
+        return n;
+    }
+};
 }  // namespace
 
+// out == NULL: the length (an upper bound where the level of detail runs), before anything touches the device.
 extern "C" long long lsnLastMeshTransferFrame(unsigned char *out, long long out_cap)
 {
     return lsn::guarded("lsnLastMeshTransferFrame", -1LL, [&]() -> long long {
         lsn::clear_error();
-        Ctx &c = ctx();
-        Lane *l = t_last_lane ? t_last_lane : c.last_lane.load();   // this thread's own last mesh call, else the process's
-        if (!l) l = &c.merge;
-        std::lock_guard<std::mutex> g(l->mu);
-        return last_mesh_bytes(c, *l, 0, nullptr, out, out_cap);
+        LastMesh m;
+        if (m.resident()) return -1;
+        const long long bound = lsnTransferFrameBound(m.nv, m.nt);
+        if (!out) return bound;
+        if (m.open(bound)) return -1;
+        return m.frame(bound, out, out_cap);
     });
 }
 
@@ -632,24 +672,27 @@ extern "C" long long lsnLastMeshPly(unsigned char *out, long long out_cap)
 {
     return lsn::guarded("lsnLastMeshPly", -1LL, [&]() -> long long {
         lsn::clear_error();
-        Ctx &c = ctx();
-        Lane *l = t_last_lane ? t_last_lane : c.last_lane.load();   // this thread's own last mesh call, else the process's
-        if (!l) l = &c.merge;
-        std::lock_guard<std::mutex> g(l->mu);
-        return last_mesh_bytes(c, *l, 1, nullptr, out, out_cap);
+        LastMesh m;
+        if (m.resident()) return -1;
+        const long long bound = lsnPlyBinaryBytes(m.nv, m.nt);
+        if (!out) return bound;
+        if (m.open(bound)) return -1;
+        return m.ply(bound, false, out, out_cap);
     });
 }
 
-// The same two through the level-of-detail stage (simplify.hip) with cell size `cell`; out == NULL: the length for the unsimplified mesh.
+// The same two through the level of detail (simplify.hip) with cell size `cell`; out == NULL: the length of the unsimplified mesh, an
+// upper bound (fewer vertices and triangles are never longer, except that a mesh that loses every triangle leaves as points).
 extern "C" long long lsnLastMeshTransferFrameLod(float cell, unsigned char *out, long long out_cap)
 {
     return lsn::guarded("lsnLastMeshTransferFrameLod", -1LL, [&]() -> long long {
         lsn::clear_error();
-        Ctx &c = ctx();
-        Lane *l = t_last_lane ? t_last_lane : c.last_lane.load();   // this thread's own last mesh call, else the process's
-        if (!l) l = &c.merge;
-        std::lock_guard<std::mutex> g(l->mu);
-        return last_mesh_bytes(c, *l, 0, &cell, out, out_cap);
+        LastMesh m;
+        if (m.resident()) return -1;
+        const long long bound = std::max(lsnTransferFrameBound(m.nv, m.nt), lsnTransferFrameBound(m.nv, 0));
+        if (!out) return bound;
+        if (m.open(bound) || m.lod("lsnLastMeshTransferFrameLod", cell)) return -1;
+        return m.frame(bound, out, out_cap);
     });
 }
 
@@ -657,11 +700,12 @@ extern "C" long long lsnLastMeshPlyLod(float cell, unsigned char *out, long long
 {
     return lsn::guarded("lsnLastMeshPlyLod", -1LL, [&]() -> long long {
         lsn::clear_error();
-        Ctx &c = ctx();
-        Lane *l = t_last_lane ? t_last_lane : c.last_lane.load();   // this thread's own last mesh call, else the process's
-        if (!l) l = &c.merge;
-        std::lock_guard<std::mutex> g(l->mu);
-        return last_mesh_bytes(c, *l, 1, &cell, out, out_cap);
+        LastMesh m;
+        if (m.resident()) return -1;
+        const long long bound = lsnPlyBinaryBytes(m.nv, m.nt);
+        if (!out) return bound;
+        if (m.open(bound) || m.lod("lsnLastMeshPlyLod", cell)) return -1;
+        return m.ply(bound, false, out, out_cap);
     });
 }
 
@@ -670,16 +714,20 @@ extern "C" long long lsnLastMeshPlyNormals(float cell, unsigned char *out, long 
 {
     return lsn::guarded("lsnLastMeshPlyNormals", -1LL, [&]() -> long long {
         lsn::clear_error();
-        Ctx &c = ctx();
-        Lane *l = t_last_lane ? t_last_lane : c.last_lane.load();   // this thread's own last mesh call, else the process's
-        if (!l) l = &c.merge;
-        std::lock_guard<std::mutex> g(l->mu);
-        return last_mesh_bytes(c, *l, 2, &cell, out, out_cap);
+        LastMesh m;
+        if (m.resident()) return -1;
+        if (m.nt <= 0) {
+            lsn::set_error("lsnLastMeshPlyNormals: the resident mesh has no triangles (the normals of a bare point cloud are not defined)");
+            return -1;
+        }
+        const long long bound = lsnPlyNormalsBytes(m.nv, m.nt);
+        if (!out) return bound;
+        if (m.open(bound) || (cell > 0.0f && m.lod("lsnLastMeshPlyNormals", cell)) || m.normals("lsnLastMeshPlyNormals")) return -1;
+        return m.ply(bound, true, out, out_cap);
     });
 }
 
-// One view of the calling thread's last mesh (render.hip) into host arrays: the mesh is one tick of one "sensor" whose offset rows are its
-// two counts.
+// One view of that mesh (render.hip) into host arrays.
 extern "C" long long lsnLastMeshRenderView(const float *intr7, const float *wt12, int width, int height, int points_only, unsigned char *depth_out,
                                            unsigned char *colors_out)
 {
@@ -689,32 +737,8 @@ extern "C" long long lsnLastMeshRenderView(const float *intr7, const float *wt12
             lsn::set_error("lsnLastMeshRenderView: null argument");
             return -1;
         }
-        Ctx &c = ctx();
-        Lane *l = t_last_lane ? t_last_lane : c.last_lane.load();   // this thread's own last mesh call, else the process's
-        if (!l) l = &c.merge;
-        std::lock_guard<std::mutex> g(l->mu);
-        if (ensure_ready(c)) return -1;
-        if (l->last_nv < 0) {
-            lsn::set_error("lsnLastMesh*: no mesh is resident (call generateMeshFromDepthMaps / generateVerticesFromDepthMap first)");
-            return -1;
-        }
-        if (materialize(*l)) return -1;
-        const int nv = l->last_nv, nt = l->last_nt;
-        const bool points = points_only != 0 || nt <= 0;
-        std::lock_guard<std::mutex> wg(c.wire_mu);
-        LSN_HIP(hipSetDevice(l->device));
-        const size_t npix = (size_t)(width > 0 ? width : 0) * (size_t)(height > 0 ? height : 0);
-        if (c.d_rv_off.reserve(sizeof(int) * 4) || c.d_rv_img.reserve(5 * npix + 16)) return -1;
-        c.rv_rows[0] = 0; c.rv_rows[1] = nv; c.rv_rows[2] = 0; c.rv_rows[3] = nt;   // {first vertex, nVertices}, {first triangle, nTriangles}
-        LSN_HIP(hipMemcpyAsync(c.d_rv_off.p, c.rv_rows, sizeof(c.rv_rows), hipMemcpyHostToDevice, l->stream));
-        unsigned char *d_depth = c.d_rv_img.as<unsigned char>(), *d_col = d_depth + 2 * npix;
-        if (lsn::render_views(c.rv, "lsnLastMeshRenderView", 1, 1, nv, nt, 1, intr7, wt12, width, height, l->d_out.p, c.d_rv_off.as<int>(),
-                              points ? nullptr : l->d_tri.p, points ? nullptr : c.d_rv_off.as<int>() + 2, d_depth, d_col, l->stream))
-            return -1;
-        LSN_HIP(hipMemcpyAsync(depth_out, d_depth, 2 * npix, hipMemcpyDeviceToHost, l->stream));
-        LSN_HIP(hipMemcpyAsync(colors_out, d_col, 3 * npix, hipMemcpyDeviceToHost, l->stream));
-        int n_pixels = 0;
-        if (lsn::render_counts(c.rv, "lsnLastMeshRenderView", 0, 0, nullptr, nullptr, &n_pixels, l->stream)) return -1;   // synchronises
-        return n_pixels;
+        LastMesh m;
+        if (m.resident() || m.open()) return -1;
+        return m.render("lsnLastMeshRenderView", intr7, wt12, width, height, points_only != 0, depth_out, colors_out);
     });
 }

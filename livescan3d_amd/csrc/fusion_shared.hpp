@@ -613,11 +613,9 @@ struct LsnFusion {
     int fl_tiles_per_tick = 0;
     int fl_last = 0;                     // what the last call was: 0 = none yet, 1 = a copy (neighbourhood <= 0), 2 = the filter
     hipStream_t fl_stream = nullptr;     // ... and its stream
-    // render view (render.hip), allocated on its first call: keys, projections, work list, counters
+    // the three stages on the merged mesh (render.hip, simplify.hip, normals.hip): each one's scratch, allocated on its first call
     lsn::RenderScratch rv;
-    // mesh level of detail (simplify.hip), allocated on its first call: hash table, remap, tile counts, counters
     lsn::SimplifyScratch sp;
-    // vertex normals (normals.hip), allocated on its first call: the integer sums, counters
     lsn::NormalsScratch nm;
     bool thr_valid = false;
     bool thr_enabled = true;             // $LSN_NO_THRESHOLDS=1 keeps the arithmetic count pass (ablation / tests)

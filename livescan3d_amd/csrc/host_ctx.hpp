@@ -157,14 +157,14 @@ struct Ctx {
     LsnTransfer *xfer = nullptr;
     int xfer_v = 0, xfer_t = 0;
     lsn::DevBuf d_wire;
-    lsn::RenderScratch rv;    // lsnLastMeshRenderView (under wire_mu too): the renderer's scratch, the mesh's two counts as offset rows, the image
-    lsn::DevBuf d_rv_off, d_rv_img;
-    int rv_rows[4] = {0, 0, 0, 0};
-    lsn::SimplifyScratch sp;  // lsnLastMesh*Lod (under wire_mu too): the simplifier's scratch, the simplified mesh, the offset rows in and out
-    lsn::DevBuf d_lod_v, d_lod_t, d_lod_off;
-    int lod_rows[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    lsn::NormalsScratch nm;   // lsnLastMeshPlyNormals (under wire_mu too): the normals stage's scratch and the normals of the mesh it packs
-    lsn::DevBuf d_nm;
+    // the steps of lsnLastMesh* (abi.hip LastMesh; under wire_mu too): the mesh's two counts as offset rows {0, nVertices}, {0, nTriangles}
+    // and behind them the rows the level of detail writes; the stages' scratch; the simplified mesh, its normals, the rendered image
+    lsn::DevBuf d_mesh_rows;
+    int mesh_rows[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    lsn::RenderScratch rv;
+    lsn::SimplifyScratch sp;
+    lsn::NormalsScratch nm;
+    lsn::DevBuf d_lod_v, d_lod_t, d_nm, d_rv_img;
     bool warned_flags = false;
 };
 

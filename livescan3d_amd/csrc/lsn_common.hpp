@@ -135,20 +135,42 @@ int outlier_filter(LsnFusion *p, int k, float max_dist, const void *d_depth, con
 // place; neighbourhood <= 0 copies).  Takes the plan's mutex.
 int flying_pixels(LsnFusion *p, int neighbourhood, int threshold, const void *d_depth_in, void *d_depth_out, hipStream_t s);
 
+// A batch of meshes in lsnFusionRunMesh's layout, as the three stages on the merged mesh read it (render.hip, simplify.hip, normals.hip;
+// what they share is mesh_batch.hip's).  The stages' device structs embed it; it is built from a plan (plan_batch, mesh_batch.hip) or
+// from a lane's last mesh (LastMesh::batch, abi.hip).
+struct MeshBatch {
+    const uint4 *verts;              // [n_ticks][tick_vert]
+    const int *voff;                 // [n_ticks][n + 1]
+    const int *tri;                  // [n_ticks][tick_tri][3], null: points only
+    const int *toff;                 // [n_ticks][n + 1]
+    long long tick_vert, tick_tri;   // vertices / triangles per tick: the strides, and what a tick's counts are clipped to
+    int n_ticks, n;                  // ticks; sensors per offset row
+};
+
+// The counters behind a stage's diagnostics: four ints per slot (a tick; a (tick, view) of the render stage) and the shape of the last
+// call, which a call forgets when it begins and remembers when everything is queued -- a failed call leaves "nothing yet".
+struct StageCounters {
+    DevBuf buf;
+    int ticks = 0, per_tick = 0;     // the shape of the last call (0: none yet)
+    int begin(size_t reserve_slots, size_t slots, hipStream_t s);   // reserve, clear `slots` on `s`, forget the last shape
+    void finish(int n_ticks, int n_per_tick = 1) { ticks = n_ticks; per_tick = n_per_tick; }
+    // slot (tick, sub) of the last call into c; synchronises `s`.  No call yet: "who: nothing_yet"; no such slot: what out_of_range() says.
+    template <class F>
+    int read(const char *who, const char *nothing_yet, int tick, int sub, int c[4], hipStream_t s, F &&out_of_range) const;
+};
+
 // The render stage (render.hip): what one renderer keeps between calls -- the per-pixel keys [n_ticks][n_views][w * h] u64, one view's
 // projected vertices [n_ticks][vertices per tick] and work list [n_ticks][triangles per tick] (the views of a call take turns on them;
 // mesh mode only), the counters behind lsnFusionRenderDiagnostics.  Reserved by the first call, grown by a call that needs more.
 struct RenderScratch {
-    DevBuf key, proj, list, cnt;
+    DevBuf key, proj, list;
+    StageCounters cnt;                // per (tick, view)
     bool keys_clean = false;          // every key is "none": the resolve passes of the last call were all queued
-    int last_ticks = 0, last_views = 0;   // the shape of the last render (0: none yet)
 };
-// lsnFusionRenderViews on any batch of clouds in lsnFusionRunMesh's layout (n sensors per offset row, tick_vert vertices and tick_tri
-// triangles per tick), and the counters of one (tick, view) of the last call with `rs` (synchronises `s`).  The caller holds the lock that
-// guards `rs` and has made its device current; `who` names the export in messages.
-int render_views(RenderScratch &rs, const char *who, int n_ticks, int n, long long tick_vert, long long tick_tri, int n_views,
-                 const float *intr_params, const float *wtransform_params, int width, int height, const void *d_vertices, const int *d_offsets,
-                 const void *d_triangles, const int *d_tri_offsets, void *d_depth_out, void *d_colors_out, hipStream_t s);
+// Each stage on a batch, and the counters of one slot of the last call with its scratch (synchronises `s`).  The caller holds the lock
+// that guards the scratch and has made its device current; `who` names the export in messages.
+int render_views(RenderScratch &rs, const char *who, const MeshBatch &m, int n_views, const float *intr_params, const float *wtransform_params,
+                 int width, int height, void *d_depth_out, void *d_colors_out, hipStream_t s);
 int render_counts(RenderScratch &rs, const char *who, int tick, int view, int *n_drawn, int *n_large, int *n_pixels, hipStream_t s);
 
 // Mesh level of detail (simplify.hip): what one simplifier keeps between calls -- the hash table [n_ticks][slots] of u64 keys and, behind
@@ -156,30 +178,22 @@ int render_counts(RenderScratch &rs, const char *who, int tick, int view, int *n
 // the per-256 counts of kept vertices and triangles, the counters behind lsnFusionSimplifyDiagnostics.  Reserved by the first call, grown
 // by a call that needs more; cell <= 0 never reserves the table.
 struct SimplifyScratch {
-    DevBuf table, rep, newidx, tiles, cnt;
-    int last_ticks = 0;   // the ticks of the last call (0: none yet)
+    DevBuf table, rep, newidx, tiles;
+    StageCounters cnt;                // per tick
 };
-// lsnFusionSimplify on any batch of clouds in lsnFusionRunMesh's layout (n sensors per offset row, tick_vert vertices and tick_tri
-// triangles per tick), and the counters of one tick of the last call with `ss` (synchronises `s`).  The caller holds the lock that guards
-// `ss` and has made its device current; `who` names the export in messages.
-int simplify(SimplifyScratch &ss, const char *who, int n_ticks, int n, long long tick_vert, long long tick_tri, float cell, const void *d_vertices,
-             const int *d_offsets, const void *d_triangles, const int *d_tri_offsets, void *d_vertices_out, int *d_offsets_out,
-             void *d_triangles_out, int *d_tri_offsets_out, int *d_remap_out, hipStream_t s);
+int simplify(SimplifyScratch &ss, const char *who, const MeshBatch &m, float cell, void *d_vertices_out, int *d_offsets_out, void *d_triangles_out,
+             int *d_tri_offsets_out, int *d_remap_out, hipStream_t s);
 int simplify_counts(SimplifyScratch &ss, const char *who, int tick, int *n_cells, int *n_unclustered, int *n_dropped_triangles, hipStream_t s);
 
 // Vertex normals (normals.hip): what one stage keeps between calls -- the sums, three planes [n_ticks][3][vertices per tick] of i64 (24 B
-// per vertex; the counted vertices are cleared by every call), and the counters behind lsnFusionNormalsDiagnostics, 16 B per tick.
-// Reserved by the first call, grown by a call that needs more.
+// per vertex; the counted vertices are cleared by every call), and the counters behind lsnFusionNormalsDiagnostics.  Reserved by the
+// first call, grown by a call that needs more.
 struct NormalsScratch {
-    DevBuf acc, cnt;
-    int last_ticks = 0;   // the ticks of the last call (0: none yet)
+    DevBuf acc;
+    StageCounters cnt;                // per tick
 };
-// lsnFusionNormals on any batch of meshes in lsnFusionRunMesh's layout (n sensors per offset row, tick_vert vertices and tick_tri
-// triangles per tick; d_normals_out: tick_vert x 3 floats per tick), and the counters of one tick of the last call with `ns`
-// (synchronises `s`).  The caller holds the lock that guards `ns` and has made its device current; `who` names the export in messages;
-// prof (nullable): the plan whose lsnFusionProfile brackets the face pass.
-int normals(NormalsScratch &ns, const char *who, int n_ticks, int n, long long tick_vert, long long tick_tri, const void *d_vertices,
-            const int *d_offsets, const void *d_triangles, const int *d_tri_offsets, void *d_normals_out, LsnFusion *prof, hipStream_t s);
+// d_normals_out: tick_vert x 3 floats per tick; prof (nullable): the plan whose lsnFusionProfile brackets the face pass.
+int normals(NormalsScratch &ns, const char *who, const MeshBatch &m, void *d_normals_out, LsnFusion *prof, hipStream_t s);
 int normals_counts(NormalsScratch &ns, const char *who, int tick, int *n_used, int *n_skipped, int *n_zero_normals, hipStream_t s);
 
 // The refine pass (icp.hip) on ONE tick's merged cloud, resident on `device` and final: vertices -> packed points -> Gauss-Seidel loop.

@@ -611,6 +611,8 @@ int lsn::run_triangles_write(LsnFusion *p, const void *d_depth, void *d_triangle
 #include "merge.hip"
 // The outlier filter (lsnSetOutlierFilter):
 #include "outlier.hip"
+// What the three stages on the merged mesh share (the batch they read, their counters, the form of their plan exports):
+#include "mesh_batch.hip"
 // Render view (lsnFusionRenderViews): the merged mesh drawn from virtual cameras, with the merge's projection and coverage.
 #include "render.hip"
 // Mesh level of detail (lsnFusionSimplify): vertex clustering of the merged mesh, in front of the packers and the renderer.

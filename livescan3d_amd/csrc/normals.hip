@@ -18,7 +18,7 @@
 //      the zero normals are counted, one add per wave.
 //
 // No kernel waits for another workgroup; every loop is bounded by a clipped count.  Plain vector stores and HIP atomics only.
-// Compiled as part of mesh.hip's translation unit (after simplify.hip, whose sp_count it uses).
+// Compiled as part of mesh.hip's translation unit (after mesh_batch.hip, whose batch, counters and export form the three stages share).
 #include "fusion_shared.hpp"
 
 namespace {
@@ -29,28 +29,23 @@ constexpr float kNmLim = 4096.0f;                // a face component at or above
 constexpr float kNmScale = 1099511627776.0f;     // 2^40: the sums count 2^-40 m^2
 
 struct NmArgs {
-    const uint4 *verts;            // [n_ticks][tick_vert]
-    const int *voff;               // [n_ticks][n + 1]
-    const int *tri;                // [n_ticks][tick_tri][3]
-    const int *toff;               // [n_ticks][n + 1]
+    lsn::MeshBatch m;              // the input
     float *out;                    // [n_ticks][tick_vert][3]
     unsigned long long *acc;       // [n_ticks][3][tick_vert]: the sums' bits (two's complement)
     int *cnt;                      // [n_ticks][4]: used, skipped, zero normals, unused
-    int n;
-    long long tick_vert, tick_tri;
 };
 
 // ---- 0. clear -----------------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(kNmThreads) void nm_clear_kernel(NmArgs a)
 {
     const int tick = blockIdx.y;
-    const int nv = sp_count(a.voff, tick, a.n, a.tick_vert);
+    const int nv = mesh_count(a.m.voff, tick, a.m.n, a.m.tick_vert);
     const int g = blockIdx.x * blockDim.x + threadIdx.x;
     if (g >= nv) return;
-    unsigned long long *acc = a.acc + 3 * tick * a.tick_vert;
+    unsigned long long *acc = a.acc + 3 * tick * a.m.tick_vert;
     acc[g] = 0;
-    acc[a.tick_vert + g] = 0;
-    acc[2 * a.tick_vert + g] = 0;
+    acc[a.m.tick_vert + g] = 0;
+    acc[2 * a.m.tick_vert + g] = 0;
 }
 
 // ---- 1. faces -----------------------------------------------------------------------------------------------------------------------
@@ -67,10 +62,10 @@ __device__ __forceinline__ void nm_add(unsigned long long *acc, int i0, int i1, 
 __global__ __launch_bounds__(kNmThreads) void nm_face_kernel(NmArgs a)
 {
     const int tick = blockIdx.y;
-    const int nv = sp_count(a.voff, tick, a.n, a.tick_vert), nt = sp_count(a.toff, tick, a.n, a.tick_tri);
-    const uint4 *verts = a.verts + tick * a.tick_vert;
-    const int *tri = a.tri + 3 * (tick * a.tick_tri);
-    unsigned long long *acc = a.acc + 3 * tick * a.tick_vert;
+    const int nv = mesh_count(a.m.voff, tick, a.m.n, a.m.tick_vert), nt = mesh_count(a.m.toff, tick, a.m.n, a.m.tick_tri);
+    const uint4 *verts = a.m.verts + tick * a.m.tick_vert;
+    const int *tri = a.m.tri + 3 * (tick * a.m.tick_tri);
+    unsigned long long *acc = a.acc + 3 * tick * a.m.tick_vert;
     const int lane = threadIdx.x & 63;
     const int stride = gridDim.x * kNmThreads;                // <= kNmMaxBlocks x 256; nt <= 2^31 / 3: base + stride stays an int
     int used = 0, skipped = 0;
@@ -91,8 +86,8 @@ __global__ __launch_bounds__(kNmThreads) void nm_face_kernel(NmArgs a)
                 if (fabsf(fx) < kNmLim && fabsf(fy) < kNmLim && fabsf(fz) < kNmLim) {   // NaN and +-inf fail
                     ok = true;
                     nm_add(acc, i0, i1, i2, fx);
-                    nm_add(acc + a.tick_vert, i0, i1, i2, fy);
-                    nm_add(acc + 2 * a.tick_vert, i0, i1, i2, fz);
+                    nm_add(acc + a.m.tick_vert, i0, i1, i2, fy);
+                    nm_add(acc + 2 * a.m.tick_vert, i0, i1, i2, fz);
                 }
             }
         }
@@ -109,12 +104,12 @@ __global__ __launch_bounds__(kNmThreads) void nm_face_kernel(NmArgs a)
 __global__ __launch_bounds__(kNmThreads) void nm_finish_kernel(NmArgs a)
 {
     const int tick = blockIdx.y;
-    const int nv = sp_count(a.voff, tick, a.n, a.tick_vert);
+    const int nv = mesh_count(a.m.voff, tick, a.m.n, a.m.tick_vert);
     const int g = blockIdx.x * blockDim.x + threadIdx.x;
     bool zero = false;
     if (g < nv) {
-        const unsigned long long *acc = a.acc + 3 * tick * a.tick_vert;
-        const long long sx = (long long)acc[g], sy = (long long)acc[a.tick_vert + g], sz = (long long)acc[2 * a.tick_vert + g];
+        const unsigned long long *acc = a.acc + 3 * tick * a.m.tick_vert;
+        const long long sx = (long long)acc[g], sy = (long long)acc[a.m.tick_vert + g], sz = (long long)acc[2 * a.m.tick_vert + g];
         zero = (sx | sy | sz) == 0;
         float nx = 0.0f, ny = 0.0f, nz = 0.0f;
         if (!zero) {
@@ -124,7 +119,7 @@ __global__ __launch_bounds__(kNmThreads) void nm_finish_kernel(NmArgs a)
             ny = y / len;
             nz = z / len;
         }
-        float *o = a.out + 3 * (tick * a.tick_vert + g);
+        float *o = a.out + 3 * (tick * a.m.tick_vert + g);
         o[0] = nx;
         o[1] = ny;
         o[2] = nz;
@@ -137,53 +132,30 @@ __global__ __launch_bounds__(kNmThreads) void nm_finish_kernel(NmArgs a)
 
 namespace lsn {
 
-// The stage on any batch of meshes in lsnFusionRunMesh's layout (n_ticks ticks of tick_vert vertices / tick_tri triangles, offset rows of
-// n + 1 ints; d_normals_out: tick_vert x 3 floats per tick), with `ns` as its scratch; the caller holds whatever lock guards `ns` and has
-// made the device current.  prof (nullable): a plan whose profiling (lsnFusionProfile) then brackets the face pass.
-int normals(NormalsScratch &ns, const char *who, int n_ticks, int n, long long tick_vert, long long tick_tri, const void *d_vertices,
-            const int *d_offsets, const void *d_triangles, const int *d_tri_offsets, void *d_normals_out, LsnFusion *prof, hipStream_t s)
+// The stage on a batch, with `ns` as its scratch.  prof (nullable): a plan whose profiling (lsnFusionProfile) then brackets the face pass.
+int normals(NormalsScratch &ns, const char *who, const MeshBatch &m, void *d_normals_out, LsnFusion *prof, hipStream_t s)
 {
-    if (!d_vertices || !d_offsets || !d_tri_offsets || !d_normals_out) {
+    if (!m.verts || !m.voff || !m.toff || !d_normals_out) {
         lsn::set_error("%s: null argument", who);
         return -1;
     }
-    if (!d_triangles) {
+    if (!m.tri) {
         lsn::set_error("%s: null argument (d_triangles: the normals of a bare point cloud are not defined)", who);
         return -1;
     }
-    if (n_ticks < 1 || n < 0 || tick_vert < 0 || tick_tri < 0 || tick_vert > 0x3FFFFFFFll || tick_tri > 0x7FFFFFFFll / 3) {
-        lsn::set_error("%s: bad batch", who);
-        return -1;
-    }
-    // out of place: the output may not overlap an input
-    const size_t T = (size_t)n_ticks, row = sizeof(int) * (size_t)(n + 1) * T, out_bytes = 12 * (size_t)tick_vert * T;
-    struct Range { const void *p; size_t bytes; const char *name; };
-    const Range in[4] = {{d_vertices, 16 * (size_t)tick_vert * T, "d_vertices"}, {d_offsets, row, "d_offsets"},
-                         {d_triangles, 12 * (size_t)tick_tri * T, "d_triangles"}, {d_tri_offsets, row, "d_tri_offsets"}};
-    for (const Range &i : in) {
-        const uintptr_t x = (uintptr_t)i.p, y = (uintptr_t)d_normals_out;
-        if (x < y + out_bytes && y < x + i.bytes) {
-            lsn::set_error("%s: d_normals_out overlaps %s (the stage runs out of place)", who, i.name);
-            return -1;
-        }
-    }
-    ns.last_ticks = 0;
-    if (ns.acc.reserve(24 * T * (size_t)std::max(tick_vert, 1LL)) || ns.cnt.reserve(sizeof(int) * 4 * T)) return -1;
-    LSN_HIP(hipMemsetAsync(ns.cnt.p, 0, sizeof(int) * 4 * T, s));
+    if (check_batch(who, m)) return -1;
+    const long long tick_vert = m.tick_vert, tick_tri = m.tick_tri;
+    const size_t T = (size_t)m.n_ticks;
+    if (check_out_of_place(who, m, {{d_normals_out, 12 * (size_t)tick_vert * T, "d_normals_out"}}, "the stage runs out of place")) return -1;
+    if (ns.cnt.begin(T, T, s) || ns.acc.reserve(24 * T * (size_t)std::max(tick_vert, 1LL))) return -1;
     NmArgs a;
-    a.verts = static_cast<const uint4 *>(d_vertices);
-    a.voff = d_offsets;
-    a.tri = static_cast<const int *>(d_triangles);
-    a.toff = d_tri_offsets;
+    a.m = m;
     a.out = static_cast<float *>(d_normals_out);
     a.acc = ns.acc.as<unsigned long long>();
-    a.cnt = ns.cnt.as<int>();
-    a.n = n;
-    a.tick_vert = tick_vert;
-    a.tick_tri = tick_tri;
+    a.cnt = ns.cnt.buf.as<int>();
     const int nvb = (int)std::max<long long>(1, (tick_vert + kNmThreads - 1) / kNmThreads);
     const int ntb = (int)std::min<long long>(kNmMaxBlocks, std::max<long long>(1, (tick_tri + kNmThreads - 1) / kNmThreads));
-    const dim3 vgrid(nvb, n_ticks), tgrid(ntb, n_ticks), block(kNmThreads);
+    const dim3 vgrid(nvb, m.n_ticks), tgrid(ntb, m.n_ticks), block(kNmThreads);
     hipEvent_t e0 = nullptr, e1 = nullptr;
     if (prof && timed_launch(prof)) {
         if (next_event_pair(prof, e0, e1)) return -1;
@@ -195,24 +167,17 @@ int normals(NormalsScratch &ns, const char *who, int n_ticks, int n, long long t
     if (e1) LSN_HIP(hipEventRecord(e1, s));
     hipLaunchKernelGGL(nm_finish_kernel, vgrid, block, 0, s, a);
     LSN_HIP(hipGetLastError());
-    ns.last_ticks = n_ticks;
+    ns.cnt.finish(m.n_ticks);
     return 0;
 }
 
 // {used triangles, skipped triangles, zero normals} of one tick of the last call with `ns`; synchronises `s`.
 int normals_counts(NormalsScratch &ns, const char *who, int tick, int *n_used, int *n_skipped, int *n_zero_normals, hipStream_t s)
 {
-    if (ns.last_ticks <= 0) {
-        lsn::set_error("%s: no normals have been computed yet", who);
-        return -1;
-    }
-    if (tick < 0 || tick >= ns.last_ticks) {
-        lsn::set_error("%s: the last call had %d ticks (asked for tick %d)", who, ns.last_ticks, tick);
-        return -1;
-    }
     int c[4] = {0, 0, 0, 0};
-    LSN_HIP(hipMemcpyAsync(c, ns.cnt.as<int>() + 4 * (size_t)tick, sizeof(c), hipMemcpyDeviceToHost, s));
-    LSN_HIP(hipStreamSynchronize(s));
+    if (ns.cnt.read(who, "no normals have been computed yet", tick, 0, c, s,
+                    [&] { lsn::set_error("%s: the last call had %d ticks (asked for tick %d)", who, ns.cnt.ticks, tick); }))
+        return -1;
     if (n_used) *n_used = c[0];
     if (n_skipped) *n_skipped = c[1];
     if (n_zero_normals) *n_zero_normals = c[2];
@@ -224,29 +189,15 @@ int normals_counts(NormalsScratch &ns, const char *who, int tick, int *n_used, i
 extern "C" int lsnFusionNormals(LsnFusion *p, const void *d_vertices, const int *d_offsets, const void *d_triangles, const int *d_tri_offsets,
                                 void *d_normals_out, void *stream)
 {
-    return lsn::guarded("lsnFusionNormals", -1, [&]() {
-        lsn::clear_error();
-        if (!p) {
-            lsn::set_error("lsnFusionNormals: null argument");
-            return -1;
-        }
-        std::lock_guard<std::mutex> g(p->mu);
-        LSN_HIP(hipSetDevice(p->device));
-        return lsn::normals(p->nm, "lsnFusionNormals", p->n_ticks, p->n_maps, p->cap, 2 * p->cap, d_vertices, d_offsets, d_triangles, d_tri_offsets,
-                            d_normals_out, p, lsn::as_stream(stream));
+    return plan_export("lsnFusionNormals", p, [&] {
+        return lsn::normals(p->nm, "lsnFusionNormals", plan_batch(p, d_vertices, d_offsets, d_triangles, d_tri_offsets), d_normals_out, p,
+                            lsn::as_stream(stream));
     });
 }
 
 extern "C" int lsnFusionNormalsDiagnostics(LsnFusion *p, int tick, int *n_used, int *n_skipped, int *n_zero_normals, void *stream)
 {
-    return lsn::guarded("lsnFusionNormalsDiagnostics", -1, [&]() {
-        lsn::clear_error();
-        if (!p) {
-            lsn::set_error("lsnFusionNormalsDiagnostics: null argument");
-            return -1;
-        }
-        std::lock_guard<std::mutex> g(p->mu);
-        LSN_HIP(hipSetDevice(p->device));
+    return plan_export("lsnFusionNormalsDiagnostics", p, [&] {
         return lsn::normals_counts(p->nm, "lsnFusionNormalsDiagnostics", tick, n_used, n_skipped, n_zero_normals, lsn::as_stream(stream));
     });
 }

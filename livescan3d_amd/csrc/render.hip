@@ -18,7 +18,7 @@
 //      colour out, the key back to "none".
 //
 // Every loop is bounded by the view size or by a count that an earlier kernel of the stream left; no kernel waits for another workgroup.
-// Compiled as part of mesh.hip's translation unit (after cloud_index.hip and merge.hip, whose project and cvt_u16_x64 it uses).
+// Compiled as part of mesh.hip's translation unit (after cloud_index.hip, merge.hip and mesh_batch.hip: project, cvt_u16_x64, the batch).
 #include "fusion_shared.hpp"
 
 namespace {
@@ -36,24 +36,15 @@ constexpr unsigned long long kRvNone = ~0ull;
 
 struct RvArgs {
     SensorParams view;             // the view's camera, packed like a sensor's
-    const uint4 *verts;            // [n_ticks][tick_vert]
-    const int *voff;               // [n_ticks][n + 1]
-    const int *tri;                // [n_ticks][tick_tri][3], null in points mode
-    const int *toff;               // [n_ticks][n + 1]
+    lsn::MeshBatch m;              // what is drawn; m.tri null in points mode
     int2 *proj;                    // [n_ticks][tick_vert]: {x | y << 16, d} in this view, d = 0: not drawable
     unsigned long long *key;       // [n_ticks][n_views][w * h]: min (val << 32 | primitive), kRvNone = nothing drawn
     int *list;                     // [n_ticks][tick_tri]: the triangles of large boxes
     int *cnt;                      // [n_ticks][n_views][4]: listed triangles, primitives drawn, pixels with depth != 0
     unsigned short *depth_out;     // [n_ticks][n_views][h][w]
     unsigned char *color_out;      // [n_ticks][n_views][h][w][3]
-    int n, n_views, view_index, w, h;
-    long long tick_vert, tick_tri;
+    int n_views, view_index, w, h;
 };
-
-__device__ __forceinline__ int rv_count(const int *off, int tick, int n, long long cap)
-{
-    return max(0, (int)min((long long)off[tick * (n + 1) + n], cap));
-}
 
 __device__ __forceinline__ long long rv_slot(const RvArgs &a, int tick) { return (long long)tick * a.n_views + a.view_index; }
 
@@ -115,18 +106,18 @@ template <bool POINTS>
 __global__ __launch_bounds__(256) void rv_project_kernel(RvArgs a)
 {
     const int tick = blockIdx.y;
-    const int nv = rv_count(a.voff, tick, a.n, a.tick_vert);
+    const int nv = mesh_count(a.m.voff, tick, a.m.n, a.m.tick_vert);
     const int g = blockIdx.x * blockDim.x + threadIdx.x;
     bool ok = false;
     if (g < nv) {
-        const uint4 v = a.verts[tick * a.tick_vert + g];
+        const uint4 v = a.m.verts[tick * a.m.tick_vert + g];
         int x, y, d;
         project(a.view, __uint_as_float(v.y), __uint_as_float(v.z), __uint_as_float(v.w), x, y, d);
         ok = x >= 0 && x < a.w && y >= 0 && y < a.h && d != 0;
         if (POINTS) {
             if (ok) atomicMin(&a.key[rv_slot(a, tick) * a.w * a.h + (long long)y * a.w + x], ((unsigned long long)(unsigned int)d << 32) | (unsigned int)g);
         } else {
-            a.proj[tick * a.tick_vert + g] = ok ? make_int2(x | (y << 16), d) : make_int2(0, 0);
+            a.proj[tick * a.m.tick_vert + g] = ok ? make_int2(x | (y << 16), d) : make_int2(0, 0);
         }
     }
     if (POINTS) {   // primitives drawn: one add per wave
@@ -139,11 +130,11 @@ __global__ __launch_bounds__(256) void rv_project_kernel(RvArgs a)
 __global__ __launch_bounds__(256) void rv_raster_kernel(RvArgs a)
 {
     const int tick = blockIdx.y;
-    const int nv = rv_count(a.voff, tick, a.n, a.tick_vert), nt = rv_count(a.toff, tick, a.n, a.tick_tri);
-    const int *tri = a.tri + 3 * tick * a.tick_tri;
-    const int2 *proj = a.proj + tick * a.tick_vert;
+    const int nv = mesh_count(a.m.voff, tick, a.m.n, a.m.tick_vert), nt = mesh_count(a.m.toff, tick, a.m.n, a.m.tick_tri);
+    const int *tri = a.m.tri + 3 * tick * a.m.tick_tri;
+    const int2 *proj = a.proj + tick * a.m.tick_vert;
     unsigned long long *key = a.key + rv_slot(a, tick) * a.w * a.h;
-    int *list = a.list + tick * a.tick_tri;
+    int *list = a.list + tick * a.m.tick_tri;
     int *cnt = a.cnt + rv_slot(a, tick) * 4;
     const int lane = threadIdx.x & 63;
     int drawn = 0;
@@ -185,11 +176,11 @@ __global__ __launch_bounds__(256) void rv_large_kernel(RvArgs a)
 {
     const int tick = blockIdx.y;
     const int *cnt = a.cnt + rv_slot(a, tick) * 4;
-    const int n_list = min(cnt[0], (int)a.tick_tri);   // left by rv_raster_kernel, a launch earlier
-    const int *tri = a.tri + 3 * tick * a.tick_tri;
-    const int2 *proj = a.proj + tick * a.tick_vert;
+    const int n_list = min(cnt[0], (int)a.m.tick_tri);   // left by rv_raster_kernel, a launch earlier
+    const int *tri = a.m.tri + 3 * tick * a.m.tick_tri;
+    const int2 *proj = a.proj + tick * a.m.tick_vert;
     unsigned long long *key = a.key + rv_slot(a, tick) * a.w * a.h;
-    const int *list = a.list + tick * a.tick_tri;
+    const int *list = a.list + tick * a.m.tick_tri;
     const int lane = threadIdx.x & 63, waves = (int)(gridDim.x * blockDim.x) >> 6;
     for (int i = (int)(blockIdx.x * blockDim.x + threadIdx.x) >> 6; i < n_list; i += waves) {
         const int t = list[i];
@@ -217,15 +208,15 @@ __global__ __launch_bounds__(256) void rv_resolve_kernel(RvArgs a)
         unsigned int d = 0, r = 0, g = 0, b = 0;
         if (k != kRvNone) {
             const int t = (int)(unsigned int)k;
-            const uint4 *verts = a.verts + tick * a.tick_vert;
+            const uint4 *verts = a.m.verts + tick * a.m.tick_vert;
             d = (unsigned int)(k >> 32);
             if (POINTS) {
                 const unsigned int c = verts[t].x;
                 r = c & 0xFFu; g = (c >> 8) & 0xFFu; b = (c >> 16) & 0xFFu;
             } else {
-                const int *tr = a.tri + 3 * (tick * a.tick_tri + t);
+                const int *tr = a.m.tri + 3 * (tick * a.m.tick_tri + t);
                 const int i1 = tr[0], i2 = tr[1], i3 = tr[2];
-                const int2 *proj = a.proj + tick * a.tick_vert;
+                const int2 *proj = a.proj + tick * a.m.tick_vert;
                 RvTri s;
                 float w1 = 0.0f, w2 = 0.0f, w3 = 0.0f;
                 unsigned int val;
@@ -253,13 +244,11 @@ __global__ __launch_bounds__(256) void rv_resolve_kernel(RvArgs a)
 
 namespace lsn {
 
-// The stage on any batch of clouds in lsnFusionRunMesh's layout (n_ticks ticks of tick_vert vertices / tick_tri triangles, offset rows
-// of n + 1 ints), with `rs` as its scratch; the caller holds whatever lock guards `rs` and has made `device` current.
-int render_views(RenderScratch &rs, const char *who, int n_ticks, int n, long long tick_vert, long long tick_tri, int n_views,
-                 const float *intr_params, const float *wtransform_params, int width, int height, const void *d_vertices, const int *d_offsets,
-                 const void *d_triangles, const int *d_tri_offsets, void *d_depth_out, void *d_colors_out, hipStream_t s)
+// The stage on a batch, with `rs` as its scratch; the caller holds whatever lock guards `rs` and has made its device current.
+int render_views(RenderScratch &rs, const char *who, const MeshBatch &m, int n_views, const float *intr_params, const float *wtransform_params,
+                 int width, int height, void *d_depth_out, void *d_colors_out, hipStream_t s)
 {
-    if (!intr_params || !wtransform_params || !d_vertices || !d_offsets || !d_depth_out || !d_colors_out || (d_triangles && !d_tri_offsets)) {
+    if (!intr_params || !wtransform_params || !m.verts || !m.voff || !d_depth_out || !d_colors_out || (m.tri && !m.toff)) {
         lsn::set_error("%s: null argument", who);
         return -1;
     }
@@ -271,15 +260,13 @@ int render_views(RenderScratch &rs, const char *who, int n_ticks, int n, long lo
         lsn::set_error("%s: a view is 1x1 to %dx%d pixels (got %dx%d)", who, kRvMaxSide, kRvMaxSide, width, height);
         return -1;
     }
-    if (n_ticks < 1 || n < 0 || tick_vert < 0 || tick_tri < 0) {
-        lsn::set_error("%s: bad batch", who);
-        return -1;
-    }
-    const bool points = d_triangles == nullptr;
+    if (check_batch(who, m)) return -1;
+    const bool points = m.tri == nullptr;
+    const int n_ticks = m.n_ticks;
     const size_t npix = (size_t)width * height, slots = (size_t)n_ticks * n_views;
-    if (rs.cnt.reserve(sizeof(int) * 4 * (size_t)n_ticks * kRvMaxViews) ||
-        (!points && (rs.proj.reserve(sizeof(int2) * (size_t)n_ticks * (size_t)std::max(tick_vert, 1LL)) ||
-                     rs.list.reserve(sizeof(int) * (size_t)n_ticks * (size_t)std::max(tick_tri, 1LL)))))
+    if (rs.cnt.begin((size_t)n_ticks * kRvMaxViews, slots, s) ||
+        (!points && (rs.proj.reserve(sizeof(int2) * (size_t)n_ticks * (size_t)std::max(m.tick_vert, 1LL)) ||
+                     rs.list.reserve(sizeof(int) * (size_t)n_ticks * (size_t)std::max(m.tick_tri, 1LL)))))
         return -1;
     // the keys last, and their flag right behind them: a call that fails further down must not leave a fresh block marked clean
     const size_t key_bytes_before = rs.key.bytes;
@@ -288,27 +275,19 @@ int render_views(RenderScratch &rs, const char *who, int n_ticks, int n, long lo
     if (key_rc) return -1;
     if (!rs.keys_clean) LSN_HIP(hipMemsetAsync(rs.key.p, 0xFF, rs.key.bytes, s));
     rs.keys_clean = false;   // until every resolve pass of this call is queued: they leave the keys at "none"
-    rs.last_ticks = rs.last_views = 0;
-    LSN_HIP(hipMemsetAsync(rs.cnt.p, 0, sizeof(int) * 4 * slots, s));
     RvArgs a;
-    a.verts = static_cast<const uint4 *>(d_vertices);
-    a.voff = d_offsets;
-    a.tri = static_cast<const int *>(d_triangles);
-    a.toff = d_tri_offsets;
+    a.m = m;
     a.proj = rs.proj.as<int2>();
     a.key = rs.key.as<unsigned long long>();
     a.list = rs.list.as<int>();
-    a.cnt = rs.cnt.as<int>();
+    a.cnt = rs.cnt.buf.as<int>();
     a.depth_out = static_cast<unsigned short *>(d_depth_out);
     a.color_out = static_cast<unsigned char *>(d_colors_out);
-    a.n = n;
     a.n_views = n_views;
     a.w = width;
     a.h = height;
-    a.tick_vert = tick_vert;
-    a.tick_tri = tick_tri;
-    const unsigned int vblocks = (unsigned int)((tick_vert + 255) / 256), pblocks = (unsigned int)((npix + 255) / 256);
-    const unsigned int tblocks = (unsigned int)std::min<long long>(kRvBlocks, (tick_tri + 255) / 256);
+    const unsigned int vblocks = (unsigned int)((m.tick_vert + 255) / 256), pblocks = (unsigned int)((npix + 255) / 256);
+    const unsigned int tblocks = (unsigned int)std::min<long long>(kRvBlocks, (m.tick_tri + 255) / 256);
     for (int v = 0; v < n_views; v++) {
         pack_sensor_params(intr_params + 7 * v, wtransform_params + 12 * v, a.view);
         a.view_index = v;
@@ -327,25 +306,18 @@ int render_views(RenderScratch &rs, const char *who, int n_ticks, int n, long lo
     }
     LSN_HIP(hipGetLastError());
     rs.keys_clean = true;
-    rs.last_ticks = n_ticks;
-    rs.last_views = n_views;
+    rs.cnt.finish(n_ticks, n_views);
     return 0;
 }
 
 // {primitives drawn, listed triangles, pixels with depth != 0} of (tick, view) of the last render with `rs`; synchronises `s`.
 int render_counts(RenderScratch &rs, const char *who, int tick, int view, int *n_drawn, int *n_large, int *n_pixels, hipStream_t s)
 {
-    if (rs.last_ticks <= 0) {
-        lsn::set_error("%s: nothing has been rendered yet", who);
-        return -1;
-    }
-    if (tick < 0 || tick >= rs.last_ticks || view < 0 || view >= rs.last_views) {
-        lsn::set_error("%s: the last render had %d ticks and %d views (asked for tick %d, view %d)", who, rs.last_ticks, rs.last_views, tick, view);
-        return -1;
-    }
     int c[4] = {0, 0, 0, 0};
-    LSN_HIP(hipMemcpyAsync(c, rs.cnt.as<int>() + 4 * ((size_t)tick * rs.last_views + view), sizeof(c), hipMemcpyDeviceToHost, s));
-    LSN_HIP(hipStreamSynchronize(s));
+    if (rs.cnt.read(who, "nothing has been rendered yet", tick, view, c, s, [&] {
+            lsn::set_error("%s: the last render had %d ticks and %d views (asked for tick %d, view %d)", who, rs.cnt.ticks, rs.cnt.per_tick, tick, view);
+        }))
+        return -1;
     if (n_large) *n_large = c[0];
     if (n_drawn) *n_drawn = c[1];
     if (n_pixels) *n_pixels = c[2];
@@ -358,30 +330,15 @@ extern "C" int lsnFusionRenderViews(LsnFusion *p, int n_views, const float *intr
                                     const void *d_vertices, const int *d_offsets, const void *d_triangles, const int *d_tri_offsets,
                                     void *d_depth_out, void *d_colors_out, void *stream)
 {
-    return lsn::guarded("lsnFusionRenderViews", -1, [&]() {
-        lsn::clear_error();
-        if (!p) {
-            lsn::set_error("lsnFusionRenderViews: null argument");
-            return -1;
-        }
-        std::lock_guard<std::mutex> g(p->mu);
-        LSN_HIP(hipSetDevice(p->device));
-        return lsn::render_views(p->rv, "lsnFusionRenderViews", p->n_ticks, p->n_maps, p->cap, 2 * p->cap, n_views, intr_params, wtransform_params,
-                                 width, height, d_vertices, d_offsets, d_triangles, d_tri_offsets, d_depth_out, d_colors_out,
-                                 lsn::as_stream(stream));
+    return plan_export("lsnFusionRenderViews", p, [&] {
+        return lsn::render_views(p->rv, "lsnFusionRenderViews", plan_batch(p, d_vertices, d_offsets, d_triangles, d_tri_offsets), n_views, intr_params,
+                                 wtransform_params, width, height, d_depth_out, d_colors_out, lsn::as_stream(stream));
     });
 }
 
 extern "C" int lsnFusionRenderDiagnostics(LsnFusion *p, int tick, int view, int *n_drawn, int *n_large, int *n_pixels, void *stream)
 {
-    return lsn::guarded("lsnFusionRenderDiagnostics", -1, [&]() {
-        lsn::clear_error();
-        if (!p) {
-            lsn::set_error("lsnFusionRenderDiagnostics: null argument");
-            return -1;
-        }
-        std::lock_guard<std::mutex> g(p->mu);
-        LSN_HIP(hipSetDevice(p->device));
+    return plan_export("lsnFusionRenderDiagnostics", p, [&] {
         return lsn::render_counts(p->rv, "lsnFusionRenderDiagnostics", tick, view, n_drawn, n_large, n_pixels, lsn::as_stream(stream));
     });
 }

@@ -23,7 +23,7 @@
 //
 // cell <= 0 or NaN: the same launches with every vertex and every triangle kept and the offset rows copied as they are.
 // No kernel waits for another workgroup; every loop is bounded by a size the host passes.  Plain vector stores and HIP atomics only.
-// Compiled as part of mesh.hip's translation unit (after cloud_index.hip, whose ct_block_scan_kernel it launches).
+// Compiled as part of mesh.hip's translation unit (after cloud_index.hip and mesh_batch.hip: ct_block_scan_kernel, the batch).
 #include "fusion_shared.hpp"
 
 namespace {
@@ -32,6 +32,7 @@ constexpr int kSpThreads = 256;
 constexpr unsigned long long kSpEmpty = ~0ull;   // no key: keys have 63 bits
 constexpr float kSpLim = 1048576.0f;             // 2^20
 
+// (restates the fields of lsn::MeshBatch: embedding it moves the kernel arguments and sp_write_kernel from 16 to 14 VGPRs)
 struct SpArgs {
     const uint4 *verts;            // [n_ticks][tick_vert]
     const int *voff;               // [n_ticks][n + 1]
@@ -50,11 +51,6 @@ struct SpArgs {
     unsigned int mask;             // slots - 1
     long long tick_vert, tick_tri;
 };
-
-__device__ __forceinline__ int sp_count(const int *off, int tick, int n, long long cap)
-{
-    return max(0, (int)min((long long)off[tick * (n + 1) + n], cap));
-}
 
 // One axis: false when it is out of range; else its 21 bits.
 __device__ __forceinline__ bool sp_axis(float c, float inv, unsigned long long &bits)
@@ -92,7 +88,7 @@ __device__ __forceinline__ int sp_block_rank(bool flag, int *s_wave, int &total)
 __global__ __launch_bounds__(kSpThreads) void sp_insert_kernel(SpArgs a)
 {
     const int tick = blockIdx.y;
-    const int nv = sp_count(a.voff, tick, a.n, a.tick_vert);
+    const int nv = mesh_count(a.voff, tick, a.n, a.tick_vert);
     const int g = blockIdx.x * blockDim.x + threadIdx.x;
     bool loose = false;
     if (g < nv) {
@@ -125,7 +121,7 @@ __global__ __launch_bounds__(kSpThreads) void sp_rep_kernel(SpArgs a)
 {
     __shared__ int s_wave[kSpThreads / 64];
     const int tick = blockIdx.y;
-    const int nv = sp_count(a.voff, tick, a.n, a.tick_vert);
+    const int nv = mesh_count(a.voff, tick, a.n, a.tick_vert);
     const int g = blockIdx.x * blockDim.x + threadIdx.x;
     bool kept = false;
     if (g < nv) {
@@ -148,7 +144,7 @@ __global__ __launch_bounds__(kSpThreads) void sp_write_kernel(SpArgs a)
 {
     __shared__ int s_wave[kSpThreads / 64];
     const int tick = blockIdx.y;
-    const int nv = sp_count(a.voff, tick, a.n, a.tick_vert);
+    const int nv = mesh_count(a.voff, tick, a.n, a.tick_vert);
     const int g = blockIdx.x * blockDim.x + threadIdx.x;
     const bool kept = g < nv && a.rep[tick * a.tick_vert + g] == g;
     int total;
@@ -162,7 +158,7 @@ __global__ __launch_bounds__(kSpThreads) void sp_write_kernel(SpArgs a)
 __global__ __launch_bounds__(kSpThreads) void sp_remap_kernel(SpArgs a)
 {
     const int tick = blockIdx.y;
-    const int nv = sp_count(a.voff, tick, a.n, a.tick_vert);
+    const int nv = mesh_count(a.voff, tick, a.n, a.tick_vert);
     const int g = blockIdx.x * blockDim.x + threadIdx.x;
     if (g >= nv) return;
     int *rep = a.rep + tick * a.tick_vert;
@@ -189,7 +185,7 @@ __global__ __launch_bounds__(kSpThreads) void sp_tri_kernel(SpArgs a)
 {
     __shared__ int s_wave[kSpThreads / 64];
     const int tick = blockIdx.y;
-    const int nv = sp_count(a.voff, tick, a.n, a.tick_vert), nt = sp_count(a.toff, tick, a.n, a.tick_tri);
+    const int nv = mesh_count(a.voff, tick, a.n, a.tick_vert), nt = mesh_count(a.toff, tick, a.n, a.tick_tri);
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
     int i1 = 0, i2 = 0, i3 = 0;
     const bool kept = t < nt && sp_triangle(a, tick, t, nv, i1, i2, i3);
@@ -210,8 +206,8 @@ __global__ __launch_bounds__(kSpThreads) void sp_offsets_kernel(SpArgs a)
 {
     __shared__ int s_wave[kSpThreads / 64];
     const int tick = blockIdx.y, i = blockIdx.x;
-    const int nv = sp_count(a.voff, tick, a.n, a.tick_vert);
-    const int count = TRI ? sp_count(a.toff, tick, a.n, a.tick_tri) : nv;
+    const int nv = mesh_count(a.voff, tick, a.n, a.tick_vert);
+    const int count = TRI ? mesh_count(a.toff, tick, a.n, a.tick_tri) : nv;
     const int *tile = TRI ? a.ttile + tick * (a.ntb + 1) : a.vtile + tick * (a.nvb + 1);
     const int nb = TRI ? a.ntb : a.nvb;
     const int in = (TRI ? a.toff : a.voff)[tick * (a.n + 1) + i];
@@ -243,56 +239,41 @@ __global__ __launch_bounds__(kSpThreads) void sp_offsets_kernel(SpArgs a)
 
 namespace lsn {
 
-// The stage on any batch of clouds in lsnFusionRunMesh's layout (n_ticks ticks of tick_vert vertices / tick_tri triangles, offset rows
-// of n + 1 ints; d_remap_out: tick_vert ints per tick), with `ss` as its scratch; the caller holds whatever lock guards `ss` and has made
-// the device current.
-int simplify(SimplifyScratch &ss, const char *who, int n_ticks, int n, long long tick_vert, long long tick_tri, float cell, const void *d_vertices,
-             const int *d_offsets, const void *d_triangles, const int *d_tri_offsets, void *d_vertices_out, int *d_offsets_out,
-             void *d_triangles_out, int *d_tri_offsets_out, int *d_remap_out, hipStream_t s)
+// The stage on a batch (d_remap_out: tick_vert ints per tick), with `ss` as its scratch: lsn_common.hpp says what the caller holds.
+int simplify(SimplifyScratch &ss, const char *who, const MeshBatch &m, float cell, void *d_vertices_out, int *d_offsets_out, void *d_triangles_out,
+             int *d_tri_offsets_out, int *d_remap_out, hipStream_t s)
 {
-    const bool points = d_triangles == nullptr;
-    if (!d_vertices || !d_offsets || !d_vertices_out || !d_offsets_out || (!points && (!d_tri_offsets || !d_triangles_out || !d_tri_offsets_out))) {
+    const bool points = m.tri == nullptr;
+    if (!m.verts || !m.voff || !d_vertices_out || !d_offsets_out || (!points && (!m.toff || !d_triangles_out || !d_tri_offsets_out))) {
         lsn::set_error("%s: null argument", who);
         return -1;
     }
-    if (n_ticks < 1 || n < 0 || tick_vert < 0 || tick_tri < 0 || tick_vert > 0x3FFFFFFFll || tick_tri > 0x7FFFFFFFll / 3) {
-        lsn::set_error("%s: bad batch", who);
-        return -1;
-    }
-    // out of place: no output may overlap an input
+    if (check_batch(who, m)) return -1;
+    const int n_ticks = m.n_ticks, n = m.n;
+    const long long tick_vert = m.tick_vert, tick_tri = m.tick_tri;
     const size_t T = (size_t)n_ticks, row = sizeof(int) * (size_t)(n + 1) * T;
-    struct Range { const void *p; size_t bytes; const char *name; };
-    const Range in[4] = {{d_vertices, 16 * (size_t)tick_vert * T, "d_vertices"}, {d_offsets, row, "d_offsets"},
-                         {d_triangles, 12 * (size_t)tick_tri * T, "d_triangles"}, {points ? nullptr : d_tri_offsets, row, "d_tri_offsets"}};
-    const Range out[5] = {{d_vertices_out, 16 * (size_t)tick_vert * T, "d_vertices_out"}, {d_offsets_out, row, "d_offsets_out"},
-                          {points ? nullptr : d_triangles_out, 12 * (size_t)tick_tri * T, "d_triangles_out"},
-                          {points ? nullptr : d_tri_offsets_out, row, "d_tri_offsets_out"}, {d_remap_out, 4 * (size_t)tick_vert * T, "d_remap_out"}};
-    for (const Range &o : out)
-        for (const Range &i : in) {
-            const uintptr_t x = (uintptr_t)i.p, y = (uintptr_t)o.p;
-            if (i.p && o.p && x < y + o.bytes && y < x + i.bytes) {
-                lsn::set_error("%s: %s overlaps %s (the stage reads the whole input while it writes: it runs out of place)", who, o.name, i.name);
-                return -1;
-            }
-        }
+    if (check_out_of_place(who, m,
+                           {{d_vertices_out, 16 * (size_t)tick_vert * T, "d_vertices_out"}, {d_offsets_out, row, "d_offsets_out"},
+                            {points ? nullptr : d_triangles_out, 12 * (size_t)tick_tri * T, "d_triangles_out"},
+                            {points ? nullptr : d_tri_offsets_out, row, "d_tri_offsets_out"}, {d_remap_out, 4 * (size_t)tick_vert * T, "d_remap_out"}},
+                           "the stage reads the whole input while it writes: it runs out of place"))
+        return -1;
     const bool identity = !(cell > 0.0f);   // <= 0 or NaN: off
     size_t slots = 1;
     while (slots < 2 * (size_t)tick_vert) slots <<= 1;
     const int nvb = (int)std::max<long long>(1, (tick_vert + kSpThreads - 1) / kSpThreads), ntb = (int)std::max<long long>(1, (tick_tri + kSpThreads - 1) / kSpThreads);
     const size_t tile_ints = T * ((size_t)nvb + 1 + (points ? 0 : (size_t)ntb + 1));
-    ss.last_ticks = 0;
-    if (ss.rep.reserve(sizeof(int) * T * (size_t)std::max(tick_vert, 1LL)) || ss.newidx.reserve(sizeof(int) * T * (size_t)std::max(tick_vert, 1LL)) ||
-        ss.tiles.reserve(sizeof(int) * tile_ints) || ss.cnt.reserve(sizeof(int) * 4 * T) || (!identity && ss.table.reserve(12 * slots * T)))
+    if (ss.cnt.begin(T, T, s) || ss.rep.reserve(sizeof(int) * T * (size_t)std::max(tick_vert, 1LL)) ||
+        ss.newidx.reserve(sizeof(int) * T * (size_t)std::max(tick_vert, 1LL)) || ss.tiles.reserve(sizeof(int) * tile_ints) || (!identity && ss.table.reserve(12 * slots * T)))
         return -1;
     // the table: every key "none", every value above any index
     if (!identity) LSN_HIP(hipMemsetAsync(ss.table.p, 0xFF, 12 * slots * T, s));
     LSN_HIP(hipMemsetAsync(ss.tiles.p, 0, sizeof(int) * tile_ints, s));
-    LSN_HIP(hipMemsetAsync(ss.cnt.p, 0, sizeof(int) * 4 * T, s));
     SpArgs a;
-    a.verts = static_cast<const uint4 *>(d_vertices);
-    a.voff = d_offsets;
-    a.tri = static_cast<const int *>(d_triangles);
-    a.toff = d_tri_offsets;
+    a.verts = m.verts;
+    a.voff = m.voff;
+    a.tri = m.tri;
+    a.toff = m.toff;
     a.verts_out = static_cast<uint4 *>(d_vertices_out);
     a.voff_out = d_offsets_out;
     a.tri_out = static_cast<int *>(d_triangles_out);
@@ -304,7 +285,7 @@ int simplify(SimplifyScratch &ss, const char *who, int n_ticks, int n, long long
     a.newidx = ss.newidx.as<int>();
     a.vtile = ss.tiles.as<int>();
     a.ttile = a.vtile + T * ((size_t)nvb + 1);
-    a.cnt = ss.cnt.as<int>();
+    a.cnt = ss.cnt.buf.as<int>();
     a.inv = identity ? 0.0f : 1.0f / cell;
     a.n = n;
     a.identity = identity ? 1 : 0;
@@ -327,24 +308,17 @@ int simplify(SimplifyScratch &ss, const char *who, int n_ticks, int n, long long
         hipLaunchKernelGGL(sp_offsets_kernel<true>, ogrid, block, 0, s, a);
     }
     LSN_HIP(hipGetLastError());
-    ss.last_ticks = n_ticks;
+    ss.cnt.finish(n_ticks);
     return 0;
 }
 
 // {occupied cells = vertices out, unclustered vertices, dropped triangles} of one tick of the last call with `ss`; synchronises `s`.
 int simplify_counts(SimplifyScratch &ss, const char *who, int tick, int *n_cells, int *n_unclustered, int *n_dropped_triangles, hipStream_t s)
 {
-    if (ss.last_ticks <= 0) {
-        lsn::set_error("%s: nothing has been simplified yet", who);
-        return -1;
-    }
-    if (tick < 0 || tick >= ss.last_ticks) {
-        lsn::set_error("%s: the last call had %d ticks (asked for tick %d)", who, ss.last_ticks, tick);
-        return -1;
-    }
     int c[4] = {0, 0, 0, 0};
-    LSN_HIP(hipMemcpyAsync(c, ss.cnt.as<int>() + 4 * (size_t)tick, sizeof(c), hipMemcpyDeviceToHost, s));
-    LSN_HIP(hipStreamSynchronize(s));
+    if (ss.cnt.read(who, "nothing has been simplified yet", tick, 0, c, s,
+                    [&] { lsn::set_error("%s: the last call had %d ticks (asked for tick %d)", who, ss.cnt.ticks, tick); }))
+        return -1;
     if (n_unclustered) *n_unclustered = c[0];
     if (n_cells) *n_cells = c[1];
     if (n_dropped_triangles) *n_dropped_triangles = c[3] - c[2];
@@ -357,29 +331,15 @@ extern "C" int lsnFusionSimplify(LsnFusion *p, float cell, const void *d_vertice
                                  const int *d_tri_offsets, void *d_vertices_out, int *d_offsets_out, void *d_triangles_out, int *d_tri_offsets_out,
                                  int *d_remap_out, void *stream)
 {
-    return lsn::guarded("lsnFusionSimplify", -1, [&]() {
-        lsn::clear_error();
-        if (!p) {
-            lsn::set_error("lsnFusionSimplify: null argument");
-            return -1;
-        }
-        std::lock_guard<std::mutex> g(p->mu);
-        LSN_HIP(hipSetDevice(p->device));
-        return lsn::simplify(p->sp, "lsnFusionSimplify", p->n_ticks, p->n_maps, p->cap, 2 * p->cap, cell, d_vertices, d_offsets, d_triangles,
-                             d_tri_offsets, d_vertices_out, d_offsets_out, d_triangles_out, d_tri_offsets_out, d_remap_out, lsn::as_stream(stream));
+    return plan_export("lsnFusionSimplify", p, [&] {
+        return lsn::simplify(p->sp, "lsnFusionSimplify", plan_batch(p, d_vertices, d_offsets, d_triangles, d_tri_offsets), cell, d_vertices_out,
+                             d_offsets_out, d_triangles_out, d_tri_offsets_out, d_remap_out, lsn::as_stream(stream));
     });
 }
 
 extern "C" int lsnFusionSimplifyDiagnostics(LsnFusion *p, int tick, int *n_cells, int *n_unclustered, int *n_dropped_triangles, void *stream)
 {
-    return lsn::guarded("lsnFusionSimplifyDiagnostics", -1, [&]() {
-        lsn::clear_error();
-        if (!p) {
-            lsn::set_error("lsnFusionSimplifyDiagnostics: null argument");
-            return -1;
-        }
-        std::lock_guard<std::mutex> g(p->mu);
-        LSN_HIP(hipSetDevice(p->device));
+    return plan_export("lsnFusionSimplifyDiagnostics", p, [&] {
         return lsn::simplify_counts(p->sp, "lsnFusionSimplifyDiagnostics", tick, n_cells, n_unclustered, n_dropped_triangles, lsn::as_stream(stream));
     });
 }

@@ -2,7 +2,7 @@
 //   1. every export with NULL pointers and zero sizes; random rigs of sensors of different sizes through every host export, the caller's
 //      arrays exactly as long as needed; the inbound formats (frame messages, recordings) valid, truncated, with flipped bits and lying headers;
 //   2. the call mix of LiveScanServer from four threads at once (MainWindowForm.cs:238,304: updateWorker's merge calls, refineWorker's
-//      single-sensor calls + ICP, plus the radial export and the last-mesh formats), every result checked against what the runtime
+//      single-sensor calls + ICP, plus the radial export and all six last-mesh formats), every result checked against what the runtime
 //      double's kernels "compute" (every non-zero depth pixel survives, one triangle per vertex);
 //   3. the pool of pinned mesh blocks must be empty at the end.
 // $LSN_HOST_DEVICES (read by the library) switches the merge calls to the sharded flow; $LSN_TEST_FAIL_ALLOC / $LSN_TEST_THROW make
@@ -113,6 +113,12 @@ bool failed_call(const Mesh &m)   // a call that a fault hook hit: empty mesh + 
     return g_faults && m.nVertices == 0 && lsnGetLastError(msg, sizeof(msg)) > 0;
 }
 
+bool mesh_gone()   // a last-mesh call that found nothing: the radial thread's calls reuse the merge lane's buffers, which forgets its mesh
+{
+    char msg[256];
+    return lsnGetLastError(msg, sizeof(msg)) > 0 && strstr(msg, "no mesh is resident");
+}
+
 void check_mesh(const Mesh &m, int want_v, bool triangles, const char *what)
 {
     if (failed_call(m)) return;
@@ -144,6 +150,25 @@ void merge_thread(int iters)
             std::vector<unsigned char> frame((size_t)bound);
             (void)lsnLastMeshTransferFrame(frame.data(), bound);
         }
+        // the other outbound formats of that mesh, one after the other on the steps they share (the offset rows, the stages' scratch, the
+        // packers' buffer).  The level of detail, the normals and the renderer are not emulated: their counts read back as 0 and the packers
+        // see an empty mesh, so what runs here is the steps' host side -- reserves, the rows' copies, the order of the locks
+        auto packed = [](const char *what, long long need, auto &&call) {
+            if (need <= 0) return;
+            std::vector<unsigned char> out((size_t)need);
+            const long long n = call(out.data(), need);
+            CHECK(g_faults || (n >= 0 && n <= need) || mesh_gone(), "%s: %lld bytes of at most %lld", what, n, need);
+        };
+        packed("lsnLastMeshPly", lsnLastMeshPly(nullptr, 0), [](unsigned char *o, long long n) { return lsnLastMeshPly(o, n); });
+        packed("lsnLastMeshPlyNormals", lsnLastMeshPlyNormals(0.05f, nullptr, 0), [](unsigned char *o, long long n) { return lsnLastMeshPlyNormals(0.05f, o, n); });
+        {
+            std::vector<unsigned char> view_d(2 * 64 * 48), view_c(3 * 64 * 48);
+            const long long px = lsnLastMeshRenderView(small.intr.data(), small.wt.data(), 64, 48, it & 1, view_d.data(), view_c.data());
+            CHECK(g_faults || px == 0 || mesh_gone(), "lsnLastMeshRenderView: %lld pixels", px);
+        }
+        packed("lsnLastMeshTransferFrameLod", lsnLastMeshTransferFrameLod(0.2f, nullptr, 0), [](unsigned char *o, long long n) { return lsnLastMeshTransferFrameLod(0.2f, o, n); });
+        packed("lsnLastMeshPlyNormals, no level of detail", lsnLastMeshPlyNormals(0.0f, nullptr, 0), [](unsigned char *o, long long n) { return lsnLastMeshPlyNormals(0.0f, o, n); });
+        packed("lsnLastMeshPlyLod", lsnLastMeshPlyLod(0.05f, nullptr, 0), [](unsigned char *o, long long n) { return lsnLastMeshPlyLod(0.05f, o, n); });
         release(m);
         // the same rig with bcolor_transfer: the flow that keeps the whole cloud in HBM, and the colour transfer's scratch on the plan (its
         // kernels are no-ops on the double and it only changes colour bytes on a device, so the same mesh is expected)
@@ -219,6 +244,10 @@ void null_sweep()
     CHECK(ICP(nullptr, nullptr, 5, 5, nullptr, nullptr, 0) == 1.0f, "ICP(null, 5)");
     (void)lsnLastMeshTransferFrame(nullptr, 0);
     (void)lsnLastMeshPly(nullptr, 0);
+    (void)lsnLastMeshTransferFrameLod(0.05f, nullptr, 0);
+    (void)lsnLastMeshPlyLod(0.05f, nullptr, 0);
+    (void)lsnLastMeshPlyNormals(0.05f, nullptr, 0);
+    CHECK(lsnLastMeshRenderView(nullptr, nullptr, 0, 0, 0, nullptr, nullptr) == -1, "lsnLastMeshRenderView(null)");
     char buf[64];
     CHECK(lsnHostScheduleDescribe(0, nullptr, nullptr, 0, 0, 0, 0, buf, sizeof(buf)) == -1, "schedule(null)");
     CHECK(lsnHostShardDescribe(0, 0, nullptr, buf, sizeof(buf)) == -1, "shards(0)");

@@ -11,9 +11,9 @@ import numpy as np
 import pytest
 
 from livescan3d_amd import native, synth
-from tests import color_cases, merge_cases
+from tests import color_cases, merge_cases, normals_ref, render_ref, simplify_ref
 from tests.normals_cases import PREFILL, Clouds, check_device, cloud, tick, wrap_mesh
-from tests.support import ROOT, Guarded, child
+from tests.support import ROOT, Guarded, child, export
 
 pytestmark = pytest.mark.gpu
 
@@ -282,6 +282,45 @@ def test_last_mesh_ply_normals(gpu):
     parts = head.split(" ", 3)
     assert parts[0] == "RESULT" and parts[1] == "1" * 9 and parts[2] == "11087", line
     assert "no mesh is resident" in parts[3] and "no triangles" in tail, line
+
+
+def test_last_mesh_exports_one_after_the_other(gpu, orc):
+    """The six lsnLastMesh* exports on ONE resident mesh (the 3 x 96x80 ring), in an order in which each finds the offset rows, the stages'
+    scratch and the packers' buffer as another left them, then in the reverse order: every result is what the export gives alone -- the
+    restatements of the level of detail, the normals and the renderer, the oracle's packers for the frame and the plain PLY."""
+    rig = color_cases.ring(3, sizes=[(96, 80)] * 3)
+    v, t, err = export(rig)
+    assert err == "" and len(v) == 11087 and len(t) > 0
+    intr, view = rig.intr[:7], render_ref.ring_views(rig)[1]
+
+    def lod(cell):
+        r = simplify_ref.simplify(v, [0, len(v)], t, [0, len(t)], cell)
+        return r["vertices"], r["triangles"]
+
+    def with_normals(mv, mt):
+        return ply_with_normals(mv, normals_ref.normals(mv, [0, len(mv)], mt, [0, len(mt)])["normals"], mt)
+
+    def view_of(points):
+        wd, wc, info = render_ref.render(v, None if points else t, intr, view, 96, 80)
+        assert info["pixels"] > 0
+        return wd, wc, info["pixels"]
+
+    steps = [("ply_normals(0.05)", lambda: native.last_mesh_ply_normals(0.05), with_normals(*lod(0.05))),
+             ("render_view, mesh", lambda: native.last_mesh_render_view(intr, view, 96, 80), view_of(False)),
+             ("transfer_frame_lod(0.2)", lambda: native.last_mesh_transfer_frame_lod(0.2), orc.transfer_frame(*lod(0.2))),
+             ("ply", native.last_mesh_ply, orc.ply_binary(v, t)),
+             ("render_view, points", lambda: native.last_mesh_render_view(intr, view, 96, 80, points_only=True), view_of(True)),
+             ("ply_normals(0.0)", lambda: native.last_mesh_ply_normals(0.0), with_normals(v, t)),
+             ("ply_lod(0.05)", lambda: native.last_mesh_ply_lod(0.05), orc.ply_binary(*lod(0.05))),
+             ("transfer_frame", native.last_mesh_transfer_frame, orc.transfer_frame(v, t))]
+    assert len(lod(0.05)[0]) == 5040 and len(lod(0.2)[0]) < 5040          # the two cells give two meshes
+    for order in (steps, steps[::-1]):
+        for what, call, want in order:
+            got = call()
+            if isinstance(want, bytes):
+                assert got == want, what
+            else:
+                assert np.array_equal(got[0], want[0]) and np.array_equal(got[1], want[1]) and got[2] == want[2], what
 
 
 def test_stream_example_writes_a_ply_with_normals(gpu, tmp_path):
