@@ -192,23 +192,7 @@ __global__ __launch_bounds__(1024) void ct_block_scan_kernel(int *blk, int nblk)
 {
     __shared__ int s_wave[16];
     int *b = blk + (long long)blockIdx.x * nblk;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int carry = 0;
-    for (int c0 = 0; c0 < nblk; c0 += 1024) {
-        const int i = c0 + threadIdx.x;
-        const int v = i < nblk ? b[i] : 0;
-        const int incl = wave_inclusive_scan(v, lane);
-        if (lane == 63) s_wave[wave] = incl;
-        __syncthreads();
-        int pre = carry, tot = 0;
-        for (int w = 0; w < 16; w++) {
-            pre += w < wave ? s_wave[w] : 0;
-            tot += s_wave[w];
-        }
-        if (i < nblk) b[i] = pre + incl - v;
-        carry += tot;
-        __syncthreads();
-    }
+    block_scan_array_excl<int, 1024>(b, 1, b, nblk, s_wave);
 }
 
 }  // namespace

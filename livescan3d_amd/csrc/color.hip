@@ -201,11 +201,8 @@ __global__ __launch_bounds__(kSampleThreads) void ct_sample_kernel(CtArgs a)
         }
         return;
     }
-    if (lane == 0) s_wave[wave][0] = __popcll(m);
-    __syncthreads();
-    int r = a.blk[slot * a.nblk + blockIdx.x];
-    for (int w = 0; w < wave; w++) r += s_wave[w][0];
-    r += __builtin_amdgcn_mbcnt_hi((unsigned int)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned int)m, 0));
+    int total;
+    const int r = a.blk[slot * a.nblk + blockIdx.x] + block_rank<kSampleThreads / 64>(take, s_wave[0], total);
     if (take) a.samples[slot * a.nblk * kSampleThreads + r] = make_uint2(ci, cj);
 }
 

@@ -155,26 +155,9 @@ struct ReconArgs {
 __global__ __launch_bounds__(kThreads) void tick_base_kernel(const int *shard_off /* [n_shards][n_ticks][mps + 1] */, int n_ticks, int mps,
                                                              int *tick_base /* [n_shards][n_ticks] */)
 {
-    __shared__ int s_wave[4];
-    __shared__ int s_carry;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    __shared__ int s_wave[kThreads / 64];
     const int *off = shard_off + (long long)blockIdx.x * n_ticks * (mps + 1);
-    int *out = tick_base + (long long)blockIdx.x * n_ticks;
-    if (threadIdx.x == 0) s_carry = 0;
-    __syncthreads();
-    for (int c0 = 0; c0 < n_ticks; c0 += kThreads) {
-        const int i = c0 + threadIdx.x;
-        const int v = i < n_ticks ? off[(long long)i * (mps + 1) + mps] : 0;
-        const int incl = wave_inclusive_scan(v, lane);
-        if (lane == 63) s_wave[wave] = incl;
-        __syncthreads();
-        int pre = s_carry;
-        for (int w = 0; w < wave; w++) pre += s_wave[w];
-        if (i < n_ticks) out[i] = pre + incl - v;
-        __syncthreads();
-        if (threadIdx.x == kThreads - 1) s_carry = pre + incl;
-        __syncthreads();
-    }
+    block_scan_array_excl<int, kThreads>(off + mps, mps + 1, tick_base + (long long)blockIdx.x * n_ticks, n_ticks, s_wave);
 }
 
 // `a` describes the WHOLE rig (all sensors, their parameters, a.out = the merged cloud).

@@ -4,6 +4,7 @@
 #pragma once
 
 #include "lsn_common.hpp"
+#include "wave_ops.hpp"
 
 #include <cstdint>
 #include <mutex>
@@ -177,16 +178,6 @@ __device__ __forceinline__ bool inside_box(float ox, float oy, float oz, const F
     return !rejected;
 }
 
-__device__ __forceinline__ int wave_inclusive_scan(int v, int lane)
-{
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        int n = __shfl_up(v, off, 64);
-        if (lane >= off) v += n;
-    }
-    return v;
-}
-
 // Number of survivors among the lower lanes of the wave, and in the whole wave, straight from the keep predicates'
 // lane masks: v_mbcnt per mask for the lanes below, s_bcnt1 (SALU) for the total -- no shuffles, no per-lane counters.
 __device__ __forceinline__ void rank_from_masks(const bool (&keep)[kPxPerLane], int &below, int &wave_total)
@@ -199,13 +190,6 @@ __device__ __forceinline__ void rank_from_masks(const bool (&keep)[kPxPerLane], 
         below = __builtin_amdgcn_mbcnt_hi((unsigned int)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned int)m, below));
         wave_total += __popcll(m);
     }
-}
-
-__device__ __forceinline__ int wave_sum(int v)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
 }
 
 // ---- one tile: where it is, its inputs, its arithmetic --------------------------------------------------------
@@ -495,7 +479,7 @@ __device__ __forceinline__ void scan_tick(int *tc, int tiles_per_tick, const Fra
             v[k] = t;
             t += x;
         }
-        const int incl = wave_inclusive_scan(t, lane);
+        const int incl = wave_scan_incl(t, lane);
         if (lane == 63) s_wave[wave] = incl;
         __syncthreads();
         int pre = carry, round_tot = 0;

@@ -34,6 +34,7 @@
 //     kernel of the next iteration's NN step (one separate pass after the last iteration).
 // This file is compiled with -ffp-contract=off.
 #include "lsn_common.hpp"
+#include "wave_ops.hpp"
 
 #include <algorithm>
 #include <cstdint>
@@ -50,6 +51,8 @@ constexpr int kScanItems = 16;        // cells per thread in the scan kernels
 constexpr int kScanBlock = kThreads * kScanItems;  // 4096
 constexpr int kSuper = 16;            // cells per super-block edge
 constexpr int kMaxSupers = kMaxCells / (kSuper * kSuper * kSuper);  // 1024
+static_assert(kMaxCells % kScanBlock == 0, "the int4 scans take whole scan blocks");
+static_assert(kSuper * kSuper * kSuper == kScanBlock, "a scan block is one super-block's cells: it lies inside the grid or outside it");
 constexpr int kMaxBlocks3 = kMaxCells / 64;                          // 4^3-cell blocks
 constexpr int kChunk = 256;            // points per scan item (4 LDS batches of 64)
 constexpr int kSeedBlocks = 4;        // blocks nearest to a query patch that are scanned first when it has no candidates yet
@@ -94,27 +97,6 @@ __device__ __forceinline__ float dist2(float qx, float qy, float qz, float px, f
     return d0 * d0 + d1 * d1 + d2 * d2;  // (d0*d0 + d1*d1) + d2*d2, contraction is off
 }
 
-__device__ __forceinline__ double wave_sum_d(double v)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-
-__device__ __forceinline__ float wave_min_f(float v)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v = fminf(v, __shfl_xor(v, off, 64));
-    return v;
-}
-
-__device__ __forceinline__ float wave_max_f(float v)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, 64));
-    return v;
-}
-
 // Sums NV doubles per thread over the workgroup (4 waves) into out[] (valid in every thread).
 template <int NV>
 __device__ __forceinline__ void block_sum_d(double (&v)[NV], double *lds /* [4*NV] */)
@@ -122,7 +104,7 @@ __device__ __forceinline__ void block_sum_d(double (&v)[NV], double *lds /* [4*N
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll
     for (int i = 0; i < NV; i++) {
-        double s = wave_sum_d(v[i]);
+        double s = wave_sum(v[i]);
         if (lane == 0) lds[wave * NV + i] = s;
     }
     __syncthreads();
@@ -215,7 +197,7 @@ __global__ __launch_bounds__(kThreads) void bbox_partial_kernel(const float *pts
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll
     for (int c = 0; c < 3; c++) {
-        float a = wave_min_f(mn[c]), b = wave_max_f(mx[c]);
+        float a = wave_min(mn[c]), b = wave_max(mx[c]);
         if (lane == 0) {
             lds[wave * 6 + c] = a;
             lds[wave * 6 + 3 + c] = b;
@@ -238,8 +220,8 @@ __global__ __launch_bounds__(64) void grid_setup_kernel(const float *part, int n
             mx[c] = fmaxf(mx[c], part[b * 6 + 3 + c]);
         }
     for (int c = 0; c < 3; c++) {
-        mn[c] = wave_min_f(mn[c]);
-        mx[c] = wave_max_f(mx[c]);
+        mn[c] = wave_min(mn[c]);
+        mx[c] = wave_max(mx[c]);
     }
     if (threadIdx.x != 0) return;
     float ext[3];
@@ -322,8 +304,7 @@ __global__ __launch_bounds__(kThreads) void scan_block_sums_kernel(const int *cn
             s += (a.x + a.y) + (a.z + a.w);
         }
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
+    s = wave_sum(s);
     if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = s;
     __syncthreads();
     if (threadIdx.x == 0) block_sums[blockIdx.x] = lds[0] + lds[1] + lds[2] + lds[3];
@@ -331,19 +312,8 @@ __global__ __launch_bounds__(kThreads) void scan_block_sums_kernel(const int *cn
 
 __global__ __launch_bounds__(1024) void scan_top_kernel(int *block_sums, int n_blocks)
 {
-    // n_blocks <= 1024: one element per thread, Hillis-Steele in LDS
-    __shared__ int lds[1024];
-    int v = threadIdx.x < n_blocks ? block_sums[threadIdx.x] : 0;
-    lds[threadIdx.x] = v;
-    __syncthreads();
-    for (int off = 1; off < 1024; off <<= 1) {
-        int t = threadIdx.x >= off ? lds[threadIdx.x - off] : 0;
-        __syncthreads();
-        lds[threadIdx.x] += t;
-        __syncthreads();
-    }
-    if (threadIdx.x < n_blocks) block_sums[threadIdx.x] = lds[threadIdx.x] - v;  // exclusive
-    if (threadIdx.x == n_blocks - 1) block_sums[n_blocks] = lds[threadIdx.x];     // grand total for the tail block
+    __shared__ int s_wave[16];
+    block_scan_array_excl<int, 1024>(block_sums, 1, block_sums, n_blocks, s_wave, block_sums + n_blocks);   // [n_blocks]: the grand total, for the tail block
 }
 
 __global__ __launch_bounds__(kThreads) void scan_finish_kernel(const int *cnt, const GridParams *gp, const int *block_sums,
@@ -367,18 +337,7 @@ __global__ __launch_bounds__(kThreads) void scan_finish_kernel(const int *cnt, c
             s += (a.x + a.y) + (a.z + a.w);
         }
     }
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int incl = s;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        int t = __shfl_up(incl, off, 64);
-        if (lane >= off) incl += t;
-    }
-    if (lane == 63) lds[wave] = incl;
-    __syncthreads();
-    int pre = block_sums[blockIdx.x];
-    for (int w = 0; w < wave; w++) pre += lds[w];
-    int run = pre + incl - s;
+    int run = block_sums[blockIdx.x] + block_scan_incl<int, kThreads / 64>(s, lds) - s;
     int4 *o4 = reinterpret_cast<int4 *>(cell_start + base);
 #pragma unroll
     for (int k = 0; k < kScanItems / 4; k++) {
@@ -450,8 +409,8 @@ __global__ __launch_bounds__(kThreads) void block_box_kernel(const GridParams *g
                 bx.lx = fminf(bx.lx, p.x); bx.ly = fminf(bx.ly, p.y); bx.lz = fminf(bx.lz, p.z);
                 bx.hx = fmaxf(bx.hx, p.x); bx.hy = fmaxf(bx.hy, p.y); bx.hz = fmaxf(bx.hz, p.z);
             }
-            bx.lx = wave_min_f(bx.lx); bx.ly = wave_min_f(bx.ly); bx.lz = wave_min_f(bx.lz);
-            bx.hx = wave_max_f(bx.hx); bx.hy = wave_max_f(bx.hy); bx.hz = wave_max_f(bx.hz);
+            bx.lx = wave_min(bx.lx); bx.ly = wave_min(bx.ly); bx.lz = wave_min(bx.lz);
+            bx.hx = wave_max(bx.hx); bx.hy = wave_max(bx.hy); bx.hz = wave_max(bx.hz);
         }
         // the point range rides in the two spare words: one 32-byte load per block in the query kernel
         bx.pad0 = __int_as_float(s);
@@ -467,8 +426,8 @@ __global__ __launch_bounds__(64) void super_box_kernel(const GridParams *gp, con
     if (s >= gp->ncells / 4096) return;
     const Box b = boxes[s * 64 + threadIdx.x];
     Box r;
-    r.lx = wave_min_f(b.lx); r.ly = wave_min_f(b.ly); r.lz = wave_min_f(b.lz);
-    r.hx = wave_max_f(b.hx); r.hy = wave_max_f(b.hy); r.hz = wave_max_f(b.hz);
+    r.lx = wave_min(b.lx); r.ly = wave_min(b.ly); r.lz = wave_min(b.lz);
+    r.hx = wave_max(b.hx); r.hy = wave_max(b.hy); r.hz = wave_max(b.hz);
     r.pad0 = r.pad1 = 0;
     if (threadIdx.x == 0) supers[s] = r;
 }
@@ -649,23 +608,12 @@ __device__ __forceinline__ int key_index(unsigned long long key) { return (int)(
 
 __device__ __forceinline__ bool finite3(float x, float y, float z) { return fabsf(x) < INFINITY && fabsf(y) < INFINITY && fabsf(z) < INFINITY; }
 
-__device__ __forceinline__ int wave_excl_scan_i(int v, int lane)
-{
-    int incl = v;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const int t = __shfl_up(incl, off, 64);
-        if (lane >= off) incl += t;
-    }
-    return incl - v;
-}
-
 // Appends the point range [js, je) of every lane with `take` set to list B as (group, range) items of <= item_points points.
 // `spread` picks the segment: a heavy group's ranges are spread over the segments by its super-blocks.
 __device__ __forceinline__ void emit_ranges(const NnWork &wk, int *bank, int which, int g, int spread, bool take, int js, int je, int lane)
 {
     const int n_items = take ? (je - js + wk.item_points - 1) / wk.item_points : 0;
-    const int before = wave_excl_scan_i(n_items, lane);
+    const int before = wave_scan_incl(n_items, lane) - n_items;
     const int total = __shfl(before + n_items, 63, 64);
     if (total == 0) return;  // wave-uniform
     const int seg = spread & (kSegs - 1);
@@ -690,8 +638,8 @@ __device__ void wave_search(const GridParams *__restrict__ gp, const float4 *__r
                             int &best_i)
 {
     if (!__ballot(part)) return;
-    const float wlx = wave_min_f(part ? qx : INFINITY), wly = wave_min_f(part ? qy : INFINITY), wlz = wave_min_f(part ? qz : INFINITY);
-    const float whx = wave_max_f(part ? qx : -INFINITY), why = wave_max_f(part ? qy : -INFINITY), whz = wave_max_f(part ? qz : -INFINITY);
+    const float wlx = wave_min(part ? qx : INFINITY), wly = wave_min(part ? qy : INFINITY), wlz = wave_min(part ? qz : INFINITY);
+    const float whx = wave_max(part ? qx : -INFINITY), why = wave_max(part ? qy : -INFINITY), whz = wave_max(part ? qz : -INFINITY);
     const int n_supers = gp->ncells / 4096;
     int seed_super = -1;
     unsigned long long seed_done = 0;
@@ -709,14 +657,14 @@ __device__ void wave_search(const GridParams *__restrict__ gp, const float4 *__r
                 }
             }
         }
-        const float wm = wave_min_f(m_best);
+        const float wm = wave_min(m_best);
         if (wm < INFINITY) {
             const int src_lane = __ffsll((long long)__ballot(m_best == wm)) - 1;
             seed_super = __shfl(s_best, src_lane, 64);
             const Box bb = boxes[seed_super * 64 + lane];
             float mb = boxbox_min_dist2(wlx, wly, wlz, whx, why, whz, bb);
             for (int t = 0; t < kSeedBlocks; t++) {
-                const float wmb = wave_min_f(mb);
+                const float wmb = wave_min(mb);
                 if (!(wmb < INFINITY)) break;
                 const int b = __ffsll((long long)__ballot(mb == wmb)) - 1;
                 const int js = __builtin_amdgcn_readlane(__float_as_int(bb.pad0), b), je = __builtin_amdgcn_readlane(__float_as_int(bb.pad1), b);
@@ -727,7 +675,7 @@ __device__ void wave_search(const GridParams *__restrict__ gp, const float4 *__r
         }
     }
     float bound = part ? best : -1.0f;  // a lane outside the search never opens a box
-    float rmax = wave_max_f(bound);
+    float rmax = wave_max(bound);
     for (int c0 = 0; c0 < n_supers; c0 += 64) {
         const int sl = c0 + lane;
         float m = INFINITY;
@@ -756,7 +704,7 @@ __device__ void wave_search(const GridParams *__restrict__ gp, const float4 *__r
                 scan_points(sorted, js, je, st, lane, qx, qy, qz, best, best_i);
                 bound = part ? best : -1.0f;
             }
-            rmax = wave_max_f(bound);
+            rmax = wave_max(bound);
             open &= __ballot(m <= rmax);  // super-blocks of this chunk that the tighter bounds rule out need not be opened
         }
     }
@@ -937,8 +885,8 @@ __device__ __forceinline__ void emit_seed_blocks(const GridParams *__restrict__ 
                                                  const NnWork &wk, int bank, int g, int lane, bool need, float qx, float qy, float qz)
 {
     if (!__ballot(need)) return;
-    const float wlx = wave_min_f(need ? qx : INFINITY), wly = wave_min_f(need ? qy : INFINITY), wlz = wave_min_f(need ? qz : INFINITY);
-    const float whx = wave_max_f(need ? qx : -INFINITY), why = wave_max_f(need ? qy : -INFINITY), whz = wave_max_f(need ? qz : -INFINITY);
+    const float wlx = wave_min(need ? qx : INFINITY), wly = wave_min(need ? qy : INFINITY), wlz = wave_min(need ? qz : INFINITY);
+    const float whx = wave_max(need ? qx : -INFINITY), why = wave_max(need ? qy : -INFINITY), whz = wave_max(need ? qz : -INFINITY);
     const int n_supers = gp->ncells / 4096;
     float m_best = INFINITY;
     int s_best = 0;
@@ -952,14 +900,14 @@ __device__ __forceinline__ void emit_seed_blocks(const GridParams *__restrict__ 
             }
         }
     }
-    const float wm = wave_min_f(m_best);
+    const float wm = wave_min(m_best);
     if (!(wm < INFINITY)) return;  // no target point with comparable coordinates at all
     const int seed_super = __shfl(s_best, __ffsll((long long)__ballot(m_best == wm)) - 1, 64);
     const Box bb = boxes[seed_super * 64 + lane];
     float mb = boxbox_min_dist2(wlx, wly, wlz, whx, why, whz, bb);
     unsigned long long chosen = 0;
     for (int t = 0; t < kSeedBlocks; t++) {
-        const float wmb = wave_min_f(mb);
+        const float wmb = wave_min(mb);
         if (!(wmb < INFINITY)) break;
         const int b = __ffsll((long long)__ballot(mb == wmb)) - 1;
         chosen |= 1ull << b;
@@ -1111,9 +1059,9 @@ __global__ __launch_bounds__(kCullThreads) __attribute__((amdgpu_waves_per_eu(7,
     if (wave == 0 && seed_targets && g * 64 + lane < n2) best_key[g * 64 + lane] = sh.key[lane];
     const bool search = me.w >= 0.0f;   // (a bound is a squared distance or +inf)
     GroupInfo gi;
-    gi.wlx = wave_min_f(search ? me.x : INFINITY); gi.wly = wave_min_f(search ? me.y : INFINITY); gi.wlz = wave_min_f(search ? me.z : INFINITY);
-    gi.whx = wave_max_f(search ? me.x : -INFINITY); gi.why = wave_max_f(search ? me.y : -INFINITY); gi.whz = wave_max_f(search ? me.z : -INFINITY);
-    gi.rmax = wave_max_f(me.w);
+    gi.wlx = wave_min(search ? me.x : INFINITY); gi.wly = wave_min(search ? me.y : INFINITY); gi.wlz = wave_min(search ? me.z : INFINITY);
+    gi.whx = wave_max(search ? me.x : -INFINITY); gi.why = wave_max(search ? me.y : -INFINITY); gi.whz = wave_max(search ? me.z : -INFINITY);
+    gi.rmax = wave_max(me.w);
     gi.pad = 0;
     gi.resolved = __ballot(sh.flag[lane] != 0);
     if (threadIdx.x == 0) groups[g] = gi;

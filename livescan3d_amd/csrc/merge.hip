@@ -23,8 +23,9 @@
 //   3. mesh.hip's triangle passes on the final maps, into the caller's triangle buffers (generateTriangles + formMesh's rebase).
 //
 // Defined here where the reference is not: float -> unsigned short as x64 code converts (cvttss2si, then the low 16
-// bits); every sensor must have the same size (the reference strides an overlay with the base's width); no debug images or timings.
-// Compiled as part of mesh.hip's translation unit (after cloud_index.hip, whose project / cvt_i32_x64 and cloud index it uses).
+// bits: cvt_u16_x64, raster.hip); every sensor must have the same size (the reference strides an overlay with the base's width); no debug images or timings.
+// Compiled as part of mesh.hip's translation unit (after cloud_index.hip, whose project / cvt_i32_x64 and cloud index it uses, and
+// raster.hip, whose cvt_u16_x64).
 #include "fusion_shared.hpp"
 
 namespace {
@@ -55,14 +56,6 @@ struct MgArgs {
     int n;
     long long tick_pix, tick_vert, tick_tri;
 };
-
-// (unsigned short)v of a float as x64 code computes it: cvttss2si (truncation; INT_MIN for NaN and anything out of int32), then the
-// low 16 bits.  gfx950's v_cvt_u32_f32 / v_cvt_i32_f32 saturate instead.
-__device__ __forceinline__ unsigned int cvt_u16_x64(float v)
-{
-    const int i = (v >= -2147483648.0f && v < 2147483648.0f) ? (int)v : (int)0x80000000u;
-    return (unsigned int)i & 0xFFFFu;
-}
 
 // ---- 1. reprojection (:749-782) ------------------------------------------------------------------------------------------------
 // PASS 0: per-vertex confidence, clear point_assigned, claim the pixel (the largest vertex index = the last in the loop of :768);
@@ -111,7 +104,9 @@ __global__ __launch_bounds__(256) void mg_project_kernel(MgArgs a, int b)
 }
 
 // ---- 2c. drawTriangle (:598-706) -----------------------------------------------------------------------------------------------
-// One lane per triangle, its bounding box walked as the reference walks it.  PASS 0: atomicMax of the index over the covered pixels of
+// One lane per triangle, its bounding box walked as the reference walks it.  The set-up and the per-pixel value are raster.hip's
+// tri_setup / tri_value written out in place, with the row's two terms hoisted: calling them cost this kernel 0.4 % of the merge's time
+// (17 more VGPRs, the row terms recomputed per covered pixel), so it keeps its own copy -- a change to either is made in both.  PASS 0: atomicMax of the index over the covered pixels of
 // val 0; PASS 1 (after PASS 0 everywhere): 64-bit atomicMin of (val << 32 | index) over the covered pixels whose Z is below the index.
 template <int PASS>
 __global__ __launch_bounds__(256) void mg_raster_kernel(MgArgs a, int b)

@@ -334,7 +334,7 @@ __global__ __launch_bounds__(kThreads, MODE == 0 ? kTriMinWaves : 1) void tri_ke
 
     // ---- ranks ---------------------------------------------------------------------------------------------------
     const int cnt = __popc(code);
-    const int incl = wave_inclusive_scan(cnt, lane);
+    const int incl = wave_scan_incl(cnt, lane);
     if (lane == 63) s_wave_tot[wave] = incl;
     int base = 0;
     if (MODE == 1) base = a.tile_counts[blockIdx.x];
@@ -607,13 +607,15 @@ int lsn::run_triangles_write(LsnFusion *p, const void *d_depth, void *d_triangle
 #include "cloud_index.hip"
 // The colour transfer of the merge call (bcolor_transfer):
 #include "color.hip"
+// drawTriangle as render view draws it, and the float -> u16 conversion it shares with the overlay merge:
+#include "raster.hip"
 // The overlay merge (bgenerate_triangles): it re-runs these triangle passes on its reprojected maps.
 #include "merge.hip"
 // The outlier filter (lsnSetOutlierFilter):
 #include "outlier.hip"
 // What the three stages on the merged mesh share (the batch they read, their counters, the form of their plan exports):
 #include "mesh_batch.hip"
-// Render view (lsnFusionRenderViews): the merged mesh drawn from virtual cameras, with the merge's projection and coverage.
+// Render view (lsnFusionRenderViews): the merged mesh drawn from virtual cameras, with the merge's projection and drawTriangle.
 #include "render.hip"
 // Mesh level of detail (lsnFusionSimplify): vertex clustering of the merged mesh, in front of the packers and the renderer.
 #include "simplify.hip"

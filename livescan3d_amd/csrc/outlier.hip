@@ -150,12 +150,7 @@ __global__ __launch_bounds__(kOlThreads) void ol_box_kernel(OlArgs a)
     int *bx = a.box + ((long long)tick * n) * 6;
 #pragma unroll
     for (int q = 0; q < 3; q++) {
-        int lo = same ? ol_ord(c[q]) : 0x7FFFFFFF, hi = same ? ol_ord(c[q]) : (int)0x80000000u;
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            lo = min(lo, __shfl_xor(lo, o, 64));
-            hi = max(hi, __shfl_xor(hi, o, 64));
-        }
+        const int lo = wave_min(same ? ol_ord(c[q]) : 0x7FFFFFFF), hi = wave_max(same ? ol_ord(c[q]) : (int)0x80000000u);
         if ((threadIdx.x & 63) == 0 && lo <= hi) {
             atomicMin(&bx[s0 * 6 + q], lo);
             atomicMax(&bx[s0 * 6 + 3 + q], hi);
@@ -229,21 +224,13 @@ __global__ __launch_bounds__(kOlThreads) void ol_chunk_kernel(int *bucket, int *
         v[q] = t;
         t += x;
     }
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int incl = wave_inclusive_scan(t, lane);
-    if (lane == 63) s_wave[wave] = incl;
-    __syncthreads();
-    int pre = 0, tot = 0;
-#pragma unroll
-    for (int w = 0; w < kOlThreads / 64; w++) {
-        pre += w < wave ? s_wave[w] : 0;
-        tot += s_wave[w];
-    }
+    int tot;
+    const int incl = block_scan_incl<int, kOlThreads / 64>(t, s_wave, &tot);
     if (PASS == 0) {
         if (threadIdx.x == 0) chunk[(long long)tick * nchunk + c] = tot;
         return;
     }
-    pre += chunk[(long long)tick * nchunk + c] + incl - t;
+    const int pre = chunk[(long long)tick * nchunk + c] + incl - t;
 #pragma unroll
     for (int q = 0; q < 8; q++)
         if (i0 + q < nb) b[i0 + q] = pre + v[q];

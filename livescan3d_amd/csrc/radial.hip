@@ -582,7 +582,7 @@ constexpr int kDx[8] = {-1, 0, 1, -1, 1, -1, 0, 1}, kDy[8] = {-1, -1, -1, 0, 0, 
 __device__ __forceinline__ int wave_reserve(int *counter, int mine)
 {
     const int lane = threadIdx.x & 63;
-    const int incl = wave_inclusive_scan(mine, lane);
+    const int incl = wave_scan_incl(mine, lane);
     const int total = __shfl(incl, 63, 64);
     int base = 0;
     if (total > 0) {

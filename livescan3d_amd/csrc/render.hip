@@ -3,9 +3,9 @@
 //
 // The reference shows the merged mesh in an OpenGL window (LiveScanServer's OpenGLWindow); this device has no rasteriser and no display,
 // so the stage is DEFINED here, from pieces that are pinned to the reference: pointProjection with the view's inverted pose (project,
-// cloud_index.hip) and drawTriangle's fill rule, barycentric weights and depth value (src/NativeUtils/depthprocessing.cpp:598-706, as
-// mg_raster_kernel of merge.hip evaluates them).  What is new: a plain z-buffer -- per pixel the candidate of smallest (val, primitive
-// index) wins, candidates of val 0 are skipped -- and the winner's colour, interpolated with the same weights.  No clipping: a triangle
+// cloud_index.hip) and drawTriangle's fill rule, barycentric weights and depth value (src/NativeUtils/depthprocessing.cpp:598-706:
+// raster.hip, the arithmetic mg_raster_kernel of merge.hip has in its loop).  What is new: a plain z-buffer -- per pixel the candidate of smallest
+// (val, primitive index) wins, candidates of val 0 are skipped -- and the winner's colour, interpolated with the same weights.  No clipping: a triangle
 // with a vertex outside the image, behind the camera or closer than 1 mm is dropped.  Per view, over every tick of the batch:
 //
 //   1. projection (rv_project_kernel): every vertex into the view; mesh mode keeps {x | y << 16, d} (d = 0: not drawable), points mode
@@ -14,11 +14,11 @@
 //      a larger one goes to the tick's work list (one returning atomic per wave, plain stores), which rv_large_kernel then draws with one
 //      wave per triangle, lanes striding the box.  Both do a 64-bit atomicMin of (val << 32 | triangle) on the pixel's key: the image
 //      does not depend on the order of the launches' lanes or of the list.
-//   3. resolve (rv_resolve_kernel): per pixel the winner's weights again (rv_pixel, the function the raster passes called), depth and
+//   3. resolve (rv_resolve_kernel): per pixel the winner's weights again (tri_value, the function the raster passes called), depth and
 //      colour out, the key back to "none".
 //
 // Every loop is bounded by the view size or by a count that an earlier kernel of the stream left; no kernel waits for another workgroup.
-// Compiled as part of mesh.hip's translation unit (after cloud_index.hip, merge.hip and mesh_batch.hip: project, cvt_u16_x64, the batch).
+// Compiled as part of mesh.hip's translation unit (after cloud_index.hip, raster.hip and mesh_batch.hip: project, drawTriangle, the batch).
 #include "fusion_shared.hpp"
 
 namespace {
@@ -48,57 +48,13 @@ struct RvArgs {
 
 __device__ __forceinline__ long long rv_slot(const RvArgs &a, int tick) { return (long long)tick * a.n_views + a.view_index; }
 
-// What drawTriangle derives before its loops (:602-666), for one triangle of projected vertices.
-struct RvTri {
-    int C1, C2, C3, DX12, DX23, DX31, DY12, DY23, DY31;
-    int minx, maxx, miny, maxy, x3, y3;
-    float fden, y23, x32, y31, x13, fd1, fd2, fd3;
-};
-
-// false: nothing is drawn (a vertex that is not drawable, or den == 0)
-__device__ __forceinline__ bool rv_setup(const int2 p1, const int2 p2, const int2 p3, RvTri &s)
-{
-    if (p1.y == 0 || p2.y == 0 || p3.y == 0) return false;
-    const int x1 = p1.x & 0xFFFF, y1 = p1.x >> 16, x2 = p2.x & 0xFFFF, y2 = p2.x >> 16, x3 = p3.x & 0xFFFF, y3 = p3.x >> 16;
-    const int X1 = 16 * x1, X2 = 16 * x2, X3 = 16 * x3, Y1 = 16 * y1, Y2 = 16 * y2, Y3 = 16 * y3;   // :602-609
-    s.DX12 = X1 - X2; s.DX23 = X2 - X3; s.DX31 = X3 - X1;
-    s.DY12 = Y1 - Y2; s.DY23 = Y2 - Y3; s.DY31 = Y3 - Y1;
-    s.minx = (min(min(X1, X2), X3) + 0xF) >> 4; s.maxx = (max(max(X1, X2), X3) + 0xF) >> 4;   // :629-632, half-open
-    s.miny = (min(min(Y1, Y2), Y3) + 0xF) >> 4; s.maxy = (max(max(Y1, Y2), Y3) + 0xF) >> 4;
-    s.C1 = s.DY12 * X1 - s.DX12 * Y1; s.C2 = s.DY23 * X2 - s.DX23 * Y2; s.C3 = s.DY31 * X3 - s.DX31 * Y3;   // :639-641
-    if (s.DY12 < 0 || (s.DY12 == 0 && s.DX12 > 0)) s.C1++;   // fill convention (:644-646)
-    if (s.DY23 < 0 || (s.DY23 == 0 && s.DX23 > 0)) s.C2++;
-    if (s.DY31 < 0 || (s.DY31 == 0 && s.DX31 > 0)) s.C3++;
-    const int den = (y2 - y3) * (x1 - x3) + (x3 - x2) * (y1 - y3);   // :656, :660
-    if (den == 0) return false;                                      // :662-663
-    s.fden = (float)den; s.y23 = (float)(y2 - y3); s.x32 = (float)(x3 - x2); s.y31 = (float)(y3 - y1); s.x13 = (float)(x1 - x3);
-    s.fd1 = (float)p1.y; s.fd2 = (float)p2.y; s.fd3 = (float)p3.y;
-    s.x3 = x3; s.y3 = y3;
-    return true;
-}
-
-// Pixel (x, y) of the triangle's box: whether it is covered (the half-space values of :648-650, :697-703 in closed form -- the same
-// int32 numbers the reference reaches by stepping), its weights and its depth value (:671-682, the reference's operation order).
-__device__ __forceinline__ bool rv_pixel(const RvTri &s, int x, int y, float &w1, float &w2, float &w3, unsigned int &val)
-{
-    const int CX1 = s.C1 + s.DX12 * (y << 4) - s.DY12 * (x << 4);
-    const int CX2 = s.C2 + s.DX23 * (y << 4) - s.DY23 * (x << 4);
-    const int CX3 = s.C3 + s.DX31 * (y << 4) - s.DY31 * (x << 4);
-    if (!(CX1 >= 0 && CX2 >= 0 && CX3 >= 0)) return false;
-    const float term21 = __fmul_rn(s.x32, (float)(y - s.y3)), term22 = __fmul_rn(s.x13, (float)(y - s.y3));
-    w1 = __fdiv_rn(__fadd_rn(__fmul_rn(s.y23, (float)(x - s.x3)), term21), s.fden);
-    w2 = __fdiv_rn(__fadd_rn(__fmul_rn(s.y31, (float)(x - s.x3)), term22), s.fden);
-    w3 = __fsub_rn(__fsub_rn(1.0f, w1), w2);
-    val = cvt_u16_x64(__fadd_rn(__fadd_rn(__fmul_rn(s.fd1, w1), __fmul_rn(s.fd2, w2)), __fmul_rn(s.fd3, w3)));
-    return true;
-}
-
 // The candidate of pixel (x, y), if the triangle covers it with a val other than 0.
-__device__ __forceinline__ void rv_draw(const RvTri &s, int x, int y, int t, unsigned long long *key, int w)
+__device__ __forceinline__ void rv_draw(const TriSetup &s, int x, int y, int t, unsigned long long *key, int w)
 {
+    if (!tri_covers(s, x, y)) return;
     float w1, w2, w3;
-    unsigned int val;
-    if (rv_pixel(s, x, y, w1, w2, w3, val) && val != 0) atomicMin(&key[(long long)y * w + x], ((unsigned long long)val << 32) | (unsigned int)t);
+    const unsigned int val = tri_value(s, x, y, w1, w2, w3);
+    if (val != 0) atomicMin(&key[(long long)y * w + x], ((unsigned long long)val << 32) | (unsigned int)t);
 }
 
 // ---- 1. projection ----------------------------------------------------------------------------------------------------------------
@@ -143,13 +99,13 @@ __global__ __launch_bounds__(256) void rv_raster_kernel(RvArgs a)
     for (int t0 = blockIdx.x * blockDim.x + (threadIdx.x & ~63); t0 < nt; t0 += stride) {
         const int t = t0 + lane;
         bool large = false;
-        RvTri s;
+        TriSetup s;
         if (t < nt) {
             const int i1 = tri[3 * t], i2 = tri[3 * t + 1], i3 = tri[3 * t + 2];
             if ((unsigned int)i1 < (unsigned int)nv && (unsigned int)i2 < (unsigned int)nv && (unsigned int)i3 < (unsigned int)nv) {
                 const int2 p1 = proj[i1], p2 = proj[i2], p3 = proj[i3];
                 drawn += p1.y != 0 && p2.y != 0 && p3.y != 0;
-                if (rv_setup(p1, p2, p3, s)) {
+                if (tri_setup(p1, p2, p3, s)) {
                     if ((s.maxx - s.minx) * (s.maxy - s.miny) > kRvSmallBox) {
                         large = true;
                     } else {
@@ -184,8 +140,8 @@ __global__ __launch_bounds__(256) void rv_large_kernel(RvArgs a)
     const int lane = threadIdx.x & 63, waves = (int)(gridDim.x * blockDim.x) >> 6;
     for (int i = (int)(blockIdx.x * blockDim.x + threadIdx.x) >> 6; i < n_list; i += waves) {
         const int t = list[i];
-        RvTri s;
-        if (!rv_setup(proj[tri[3 * t]], proj[tri[3 * t + 1]], proj[tri[3 * t + 2]], s)) continue;   // (listed: it was drawable)
+        TriSetup s;
+        if (!tri_setup(proj[tri[3 * t]], proj[tri[3 * t + 1]], proj[tri[3 * t + 2]], s)) continue;   // (listed: it was drawable)
         const int bw = s.maxx - s.minx, npx = bw * (s.maxy - s.miny);   // <= 1024 * 1024
         for (int j = lane; j < npx; j += 64) {
             const int r = j / bw;
@@ -217,10 +173,9 @@ __global__ __launch_bounds__(256) void rv_resolve_kernel(RvArgs a)
                 const int *tr = a.m.tri + 3 * (tick * a.m.tick_tri + t);
                 const int i1 = tr[0], i2 = tr[1], i3 = tr[2];
                 const int2 *proj = a.proj + tick * a.m.tick_vert;
-                RvTri s;
+                TriSetup s;
                 float w1 = 0.0f, w2 = 0.0f, w3 = 0.0f;
-                unsigned int val;
-                if (rv_setup(proj[i1], proj[i2], proj[i3], s)) (void)rv_pixel(s, i % a.w, i / a.w, w1, w2, w3, val);
+                if (tri_setup(proj[i1], proj[i2], proj[i3], s) && tri_covers(s, i % a.w, i / a.w)) (void)tri_value(s, i % a.w, i / a.w, w1, w2, w3);
                 const unsigned int c1 = verts[i1].x, c2 = verts[i2].x, c3 = verts[i3].x;
                 auto mix = [&](int sh) -> unsigned int {
                     const float f1 = (float)((c1 >> sh) & 0xFFu), f2 = (float)((c2 >> sh) & 0xFFu), f3 = (float)((c3 >> sh) & 0xFFu);

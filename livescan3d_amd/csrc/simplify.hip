@@ -67,23 +67,6 @@ __device__ __forceinline__ unsigned int sp_hash(unsigned long long key)
     return (unsigned int)(key >> 32) ^ (unsigned int)key;
 }
 
-// Exclusive rank of `flag` among the workgroup's lanes (kSpThreads = 4 waves), and their total.
-__device__ __forceinline__ int sp_block_rank(bool flag, int *s_wave, int &total)
-{
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const unsigned long long m = __ballot(flag);
-    if (lane == 0) s_wave[wave] = __popcll(m);
-    __syncthreads();
-    int rank = __popcll(m & ((1ull << lane) - 1ull));
-    total = 0;
-#pragma unroll
-    for (int w = 0; w < kSpThreads / 64; w++) {
-        rank += w < wave ? s_wave[w] : 0;
-        total += s_wave[w];
-    }
-    return rank;
-}
-
 // ---- 1. insert ----------------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(kSpThreads) void sp_insert_kernel(SpArgs a)
 {
@@ -135,7 +118,7 @@ __global__ __launch_bounds__(kSpThreads) void sp_rep_kernel(SpArgs a)
         kept = r == g;
     }
     int total;
-    (void)sp_block_rank(kept, s_wave, total);
+    (void)block_rank<kSpThreads / 64>(kept, s_wave, total);
     if (threadIdx.x == 0) a.vtile[tick * (a.nvb + 1) + blockIdx.x] = total;
 }
 
@@ -148,7 +131,7 @@ __global__ __launch_bounds__(kSpThreads) void sp_write_kernel(SpArgs a)
     const int g = blockIdx.x * blockDim.x + threadIdx.x;
     const bool kept = g < nv && a.rep[tick * a.tick_vert + g] == g;
     int total;
-    const int rank = a.vtile[tick * (a.nvb + 1) + blockIdx.x] + sp_block_rank(kept, s_wave, total);
+    const int rank = a.vtile[tick * (a.nvb + 1) + blockIdx.x] + block_rank<kSpThreads / 64>(kept, s_wave, total);
     if (kept) {   // rank < kept vertices of the tick <= nv
         a.verts_out[tick * a.tick_vert + rank] = a.verts[tick * a.tick_vert + g];
         a.newidx[tick * a.tick_vert + g] = rank;
@@ -190,7 +173,7 @@ __global__ __launch_bounds__(kSpThreads) void sp_tri_kernel(SpArgs a)
     int i1 = 0, i2 = 0, i3 = 0;
     const bool kept = t < nt && sp_triangle(a, tick, t, nv, i1, i2, i3);
     int total;
-    const int rank = sp_block_rank(kept, s_wave, total);
+    const int rank = block_rank<kSpThreads / 64>(kept, s_wave, total);
     if (!WRITE) {
         if (threadIdx.x == 0) a.ttile[tick * (a.ntb + 1) + blockIdx.x] = total;
     } else if (kept) {   // prefix + rank < surviving triangles of the tick <= nt
@@ -224,7 +207,7 @@ __global__ __launch_bounds__(kSpThreads) void sp_offsets_kernel(SpArgs a)
         }
     }
     int total;
-    (void)sp_block_rank(kept, s_wave, total);
+    (void)block_rank<kSpThreads / 64>(kept, s_wave, total);
     if (threadIdx.x == 0) {
         const int below = tile[b] + total;
         (TRI ? a.toff_out : a.voff_out)[tick * (a.n + 1) + i] = a.identity ? in : below;

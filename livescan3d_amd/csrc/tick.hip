@@ -138,11 +138,11 @@ extern "C" int lsnTickRun(LsnTick *t, const void *d_depth_in, const void *d_colo
             lsn::set_error("lsnTickRun: null argument");
             return -1;
         }
-        if (t->intr.empty()) {
+        std::lock_guard<std::mutex> g(t->mu);
+        if (t->intr.empty()) {   // (under the lock: lsnTickSetParams assigns the vector under it)
             lsn::set_error("lsnTickRun: lsnTickSetParams has not been called");
             return -1;
         }
-        std::lock_guard<std::mutex> g(t->mu);
         LSN_HIP(hipSetDevice(t->device));
         hipStream_t s = lsn::as_stream(stream);
         const bool filter = t->fp_neighbourhood >= 1;
@@ -178,7 +178,7 @@ extern "C" int lsnTickRun(LsnTick *t, const void *d_depth_in, const void *d_colo
         t->plan[0]->after_band = nullptr;
         char err_a[lsn::kErrorLen];
         snprintf(err_a, sizeof(err_a), "%s", lsn::error_buffer());   // (every export clears the channel on entry: the second half's calls would wipe the first half's text)
-        (void)hipStreamWaitEvent(t->side, t->ev_band, 0);   // (a closing route without a band kernel records nothing new: no wait, the halves start together)
+        if (hipStreamWaitEvent(t->side, t->ev_band, 0) != hipSuccess) (void)hipGetLastError();   // (a closing route without a band kernel records nothing new: no wait, the halves start together)
         const int rc_b = part(1, t->side);
         if (rc_a) lsn::set_error("%s", err_a);
         // (the join is enqueued whatever happened: nothing of a failed half may still be running unobserved when the caller's stream goes on)

@@ -15,6 +15,7 @@
 // the chunk --, a block-sum + last-block scan finds the triangle that closes the chunk, and the new indices are the ranks of
 // the winners.  Only the chunk boundaries are found one after the other (the boundary of chunk c+1 depends on chunk c).
 #include "lsn_common.hpp"
+#include "wave_ops.hpp"
 
 #include <dlfcn.h>
 
@@ -112,24 +113,6 @@ __device__ __forceinline__ void stores_acknowledged()
     __builtin_amdgcn_s_waitcnt(0);
 }
 
-// inclusive scan over the block's 256 threads (4 waves)
-__device__ __forceinline__ int block_inclusive_scan(int v, int *s_wave /* 4 ints */)
-{
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int x = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int y = __shfl_up(x, d, 64);
-        if (lane >= d) x += y;
-    }
-    if (lane == 63) s_wave[wave] = x;
-    __syncthreads();
-    int add = 0;
-    for (int w2 = 0; w2 < wave; w2++) add += s_wave[w2];
-    __syncthreads();
-    return x + add;
-}
-
 // ---- pass 2: vertices first used per block; the last block to arrive finds where the chunk closes --------------------------
 __global__ __launch_bounds__(kTriPerBlock) void chunk_count_kernel(ChunkState *st, const int *__restrict__ tri, int nT, int nV,
                                                                      const unsigned long long *tag, int *bsum, int *boff)
@@ -141,7 +124,7 @@ __global__ __launch_bounds__(kTriPerBlock) void chunk_count_kernel(ChunkState *s
     const int win = st->win_tri, c = st->c;
     const int k = win + blockIdx.x * kTriPerBlock + threadIdx.x;
     const int cnt = k < nT ? __popc(triangle_new_mask(tri, k, nV, c, tag)) : 0;
-    const int incl = block_inclusive_scan(cnt, s_wave);
+    const int incl = block_scan_incl<int, 4>(cnt, s_wave);
     if (threadIdx.x == kTriPerBlock - 1) {
         __hip_atomic_store(&bsum[blockIdx.x], incl, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         stores_acknowledged();
@@ -158,7 +141,7 @@ __global__ __launch_bounds__(kTriPerBlock) void chunk_count_kernel(ChunkState *s
     for (int b0 = 0; b0 < nb; b0 += kTriPerBlock) {
         const int b = b0 + threadIdx.x;
         const int v = b < nb ? __hip_atomic_load(&bsum[b], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0;
-        const int inc = block_inclusive_scan(v, s_wave) + running;
+        const int inc = block_scan_incl<int, 4>(v, s_wave) + running;
         if (b < nb) {
             boff[b] = inc - v;
             if (inc >= kChunkLimit && inc - v < kChunkLimit) { s_found_block = b; s_found_off = inc - v; }   // unique: inc is monotone
@@ -173,7 +156,7 @@ __global__ __launch_bounds__(kTriPerBlock) void chunk_count_kernel(ChunkState *s
         // the triangle inside block fb at which the count reaches the limit: the chunk closes at its last index (:239)
         const int kk = win + fb * kTriPerBlock + threadIdx.x;
         const int c2 = kk < nT ? __popc(triangle_new_mask(tri, kk, nV, c, tag)) : 0;
-        const int inc2 = block_inclusive_scan(c2, s_wave) + s_found_off;
+        const int inc2 = block_scan_incl<int, 4>(c2, s_wave) + s_found_off;
         if (inc2 >= kChunkLimit && inc2 - c2 < kChunkLimit) {
             st->e_tri = kk;
             st->closes = 1;
@@ -201,7 +184,7 @@ __global__ __launch_bounds__(kTriPerBlock) void chunk_emit_kernel(ChunkState *st
     const int k = win + blockIdx.x * kTriPerBlock + threadIdx.x;
     const int m = (k <= e && k < nT) ? triangle_new_mask(tri, k, nV, c, tag) : 0;
     const int cnt = __popc(m);
-    int li = block_inclusive_scan(cnt, s_wave) - cnt + boff[blockIdx.x];
+    int li = block_scan_incl<int, 4>(cnt, s_wave) - cnt + boff[blockIdx.x];
 #pragma unroll
     for (int j = 0; j < 3; j++) {
         if (m & (1 << j)) {
@@ -294,8 +277,7 @@ __global__ __launch_bounds__(kUsesThreads) void link_uses_kernel(const int *__re
     }
     if (bad) atomicOr(&st->bad, 1);
     for (int i = tid; i < kUsesWindow; i += kUsesThreads) s_cnt[i] = 0;
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) vmin = min(vmin, __shfl_xor(vmin, d, 64));
+    vmin = wave_min(vmin);
     if ((tid & 63) == 0) s_min[tid >> 6] = vmin;
     __syncthreads();
     vmin = s_min[0];
@@ -384,24 +366,6 @@ __global__ __launch_bounds__(256) void link_pack_kernel(const unsigned *__restri
 }
 
 // ---- prefix sums over a few million elements: block totals, one workgroup over the totals, blocks again ----
-template <typename T>
-__device__ __forceinline__ T block_scan_incl(T v, T *s_wave /* 4 */)
-{
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    T x = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const T y = __shfl_up(x, d, 64);
-        if (lane >= d) x += y;
-    }
-    if (lane == 63) s_wave[wave] = x;
-    __syncthreads();
-    T add = 0;
-    for (int w2 = 0; w2 < wave; w2++) add += s_wave[w2];
-    __syncthreads();
-    return x + add;
-}
-
 // eight consecutive elements of a thread (the arrays are 32-byte aligned and padded to a multiple of eight)
 template <typename T>
 __device__ __forceinline__ void load8(const T *in, long long base, long long n, T (&v)[8])
@@ -444,7 +408,7 @@ __global__ __launch_bounds__(256) void scan_totals_kernel(const T *__restrict__ 
     load8(in, base, n, v);
 #pragma unroll
     for (int k = 0; k < 8; k++) sum += v[k];
-    const T incl = block_scan_incl(sum, s_wave);
+    const T incl = block_scan_incl<T, 4>(sum, s_wave);
     if (threadIdx.x == 255) totals[blockIdx.x] = incl;
 }
 
@@ -452,28 +416,7 @@ template <typename T>
 __global__ __launch_bounds__(1024) void scan_top_kernel(T *totals, int nb)   // totals -> exclusive prefixes, in place
 {
     __shared__ T s_wave[16];
-    __shared__ T s_carry;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (threadIdx.x == 0) s_carry = 0;
-    __syncthreads();
-    for (int b0 = 0; b0 < nb; b0 += 1024) {
-        const int b = b0 + threadIdx.x;
-        const T v = b < nb ? totals[b] : T(0);
-        T x = v;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const T y = __shfl_up(x, d, 64);
-            if (lane >= d) x += y;
-        }
-        if (lane == 63) s_wave[wave] = x;
-        __syncthreads();
-        T add = s_carry;
-        for (int w2 = 0; w2 < wave; w2++) add += s_wave[w2];
-        if (b < nb) totals[b] = x + add - v;
-        __syncthreads();
-        if (threadIdx.x == 1023) s_carry = x + add;
-        __syncthreads();
-    }
+    block_scan_array_excl<T, 1024>(totals, 1, totals, nb, s_wave);
 }
 
 template <typename T>
@@ -485,7 +428,7 @@ __global__ __launch_bounds__(256) void scan_apply_kernel(T *data /* in place, in
     load8(data, base, n, v);
 #pragma unroll
     for (int k = 0; k < 8; k++) sum += v[k];
-    T run = block_scan_incl(sum, s_wave) - sum + totals[blockIdx.x];
+    T run = block_scan_incl<T, 4>(sum, s_wave) - sum + totals[blockIdx.x];
 #pragma unroll
     for (int k = 0; k < 8; k++) {
         run += v[k];
@@ -632,7 +575,7 @@ __global__ __launch_bounds__(256) void rank_totals_kernel(const unsigned *__rest
     opening_flags(prev, base, n_pos, s_start, nc, flag);
 #pragma unroll
     for (int k = 0; k < 8; k++) sum += flag[k];
-    const int incl = block_scan_incl(sum, s_wave);
+    const int incl = block_scan_incl<int, 4>(sum, s_wave);
     if (threadIdx.x == 255) totals[blockIdx.x] = incl;
 }
 
@@ -649,7 +592,7 @@ __global__ __launch_bounds__(256) void rank_apply_kernel(const unsigned *__restr
     opening_flags(prev, base, n_pos, s_start, nc, flag);
 #pragma unroll
     for (int k = 0; k < 8; k++) sum += flag[k];
-    int run = block_scan_incl(sum, s_wave) - sum + totals[blockIdx.x];
+    int run = block_scan_incl<int, 4>(sum, s_wave) - sum + totals[blockIdx.x];
 #pragma unroll
     for (int k = 0; k < 8; k++) {
         const int f = flag[k];

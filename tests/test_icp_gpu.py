@@ -65,6 +65,37 @@ def test_nn_matches_oracle_bitexact(gpu, orc, mode):
         assert np.array_equal(got_i, want_i), f"case {k}: indices differ at {np.flatnonzero(got_i != want_i)[:5]}"
 
 
+def _grid_cells(targets):
+    """The cells of the grid the library lays over `targets` (grid_setup_kernel of icp.hip, its f32 arithmetic restated): the cell edge is
+    twice the spacing of a surface-like cloud, within [L / 512, L / 4], and every axis is rounded up to whole super-blocks of 16 cells."""
+    f = np.float32
+    ext = (targets.max(0) - targets.min(0)).astype(f)
+    L = ext.max()
+    area = f(ext[0] * ext[1]) + f(ext[1] * ext[2]) + f(ext[0] * ext[2])
+    hh = f(2) * np.sqrt(f(max(area, f(1e-12)) / f(len(targets))), dtype=f)
+    hh = min(max(hh, f(L / f(512))), f(L / f(4)))
+    ns = [int(min(np.floor(f(f(e / hh) / f(16))) + f(1), f(4096))) for e in ext]
+    assert all(f(n * 16) * hh > e * f(1.001) for n, e in zip(ns, ext))          # the first edge fits: the set-up loop ends at once
+    return ns[0] * ns[1] * ns[2] * 4096
+
+
+@pytest.mark.parametrize("box,n,cells", [((1.0, 1.0, 1.0), 400, 4096), ((1.0, 0.1, 0.1), 400, 2 * 4096), ((1.0, 0.1, 0.1), 300, 2 * 4096),
+                                         ((1.0, 1.0, 0.05), 3000, 4 * 4096)])
+def test_nn_grids_of_one_two_and_four_scan_blocks(gpu, orc, box, n, cells):
+    """The cell starts are summed 4096 cells per workgroup; one workgroup sums the workgroups' totals and leaves the grand total behind
+    them, which becomes cell_start[ncells].  A grid of exactly one scan block, two and four, a few hundred points each: the last cell's
+    points are found only when that total is right."""
+    rng = np.random.default_rng(n)
+    t = (rng.uniform(0, 1, size=(n, 3)) * box).astype(np.float32)
+    t[0], t[1] = 0, box                                                          # the box's corners: the extents are exactly `box`
+    q = (rng.uniform(-0.1, 1.1, size=(257, 3)) * box).astype(np.float32)
+    q[:8] = np.asarray(box, np.float32) * rng.uniform(0.97, 1.0, size=(8, 3)).astype(np.float32)   # queries in the last cells
+    assert _grid_cells(t) == cells
+    want_i, want_d = orc.nn(t, q, mode="brute", n_threads=8)
+    got_i, got_d = _gpu_nn(t, q, native.NN_GRID)
+    assert np.array_equal(got_d.view(np.uint32), want_d.view(np.uint32)) and np.array_equal(got_i, want_i)
+
+
 GOLDEN_NN = sorted(glob.glob(os.path.join(os.path.dirname(__file__), "golden", "nn_*.npz")))
 
 

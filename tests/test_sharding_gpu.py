@@ -153,6 +153,40 @@ def test_survivor_exchange_kernels_on_one_gpu(gpu, S, G, w, h):
         assert torch.equal(merged2[k, :n], want_v[k, :n]), f"run layout, tick {k}"
 
 
+@pytest.mark.parametrize("T", [255, 256, 257, 513])
+def test_tick_bases_over_more_ticks_than_one_workgroup(gpu, T):
+    """The ticks' starts in the back-to-back layout are the exclusive prefix sums of the ticks' survivor counts (np.cumsum).  One
+    workgroup of 256 threads carries the sum from round to round: 255 / 256 ticks end inside / with the first round, 257 starts a second
+    with one tick, 513 a third.  2 sensors of 16 x 8 pixels, a few of which the crop box drops in every tick."""
+    sys.path.insert(0, ROOT)
+    import numpy as np
+    import torch
+    from livescan3d_amd import synth
+    from livescan3d_amd.fusion import DeviceFusion
+    S, w, h = 2, 16, 8
+    P = w * h
+    depth, rgb = synth.noise_frames_torch(torch.device("cuda", 0), 3, T, S, w, h)
+    depth, rgb = depth.view(T, S * P).contiguous(), rgb.view(T, S * P * 3).contiguous()
+    intr = np.concatenate([synth.kinect_intrinsics(w, h)] * S)
+    wt = np.concatenate([synth.pack_pose(*synth.ring_pose(s, S)) for s in range(S)])
+    local = DeviceFusion(T, [w] * S, [h] * S)
+    local.set_params(intr, wt, synth.CROP_BOUNDS)
+    cap = S * P
+    mask = torch.zeros((T, cap // 8), dtype=torch.uint8, device="cuda")
+    dc = torch.zeros((T * cap,), dtype=torch.int16, device="cuda")
+    cc = torch.zeros((T * cap, 3), dtype=torch.uint8, device="cuda")
+    tp = torch.zeros((T, local.plan.tiles_per_tick), dtype=torch.int32, device="cuda")
+    off = torch.zeros((T, S + 1), dtype=torch.int32, device="cuda")
+    tb = torch.full((T + 1,), -7, dtype=torch.int32, device="cuda")
+    local.plan.pack_survivors_run(depth.data_ptr(), rgb.data_ptr(), mask.data_ptr(), dc.data_ptr(), cc.data_ptr(), tp.data_ptr(), off.data_ptr(),
+                                  tb.data_ptr(), int(torch.cuda.current_stream().cuda_stream))
+    torch.cuda.synchronize()
+    tot = off[:, S].cpu().numpy().astype(np.int64)
+    assert tot.min() >= 0 and 0 < tot.sum() and len(set(tot.tolist())) > 1          # the counts differ from tick to tick
+    assert tb[:T].cpu().numpy().tolist() == np.concatenate([[0], np.cumsum(tot)[:-1]]).tolist()
+    assert int(tb[T]) == -7                                                         # nothing behind the last tick's start
+
+
 def _survivor_worker(rank, port, out):
     sys.path.insert(0, ROOT)
     import numpy as np

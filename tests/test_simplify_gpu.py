@@ -63,6 +63,21 @@ def test_full_table_probe_chains(gpu):
     c.close()
 
 
+def test_more_tiles_than_one_scan_round(gpu):
+    """The kept vertices and triangles are counted per tile of 256 and one workgroup turns a tick's counts into prefixes, 1024 a round
+    with the sum carried along.  1026 vertex tiles and as many triangle tiles, nearly every vertex alone in its cell: the second round's
+    tiles have something to add to and the kept vertices themselves fill more than 1024 tiles.  One sensor of 513 x 513, the smallest
+    square capacity above 1024 tiles."""
+    import torch
+    nv = 263000                                               # of the 263169 the sensor holds: 1028 tiles
+    rng = np.random.default_rng(3)
+    fan = (np.arange(nv - 2, dtype=np.int32)[:, None] + np.arange(3, dtype=np.int32)[None, :])
+    c = Clouds(torch, [(simplify_ref.cloud(rng.uniform(-2.0, 2.0, (nv, 3))), [0, nv], fan, [0, nv - 2])], sizes=((513, 513),))
+    _, refs = c.check(0.01)                                   # 400^3 cells: some 540 vertices share one (nv^2 / 2 / 400^3)
+    assert refs[0]["cells"] > 1024 * 256 and len(refs[0]["triangles"]) > nv - 2 - 3 * 2000
+    c.close()
+
+
 @pytest.fixture(scope="module")
 def ring_fusion(gpu):
     from livescan3d_amd.fusion import DeviceFusion

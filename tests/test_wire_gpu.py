@@ -78,6 +78,27 @@ def test_mesh_stream_matches_oracle(gpu, orc, w, h):
         assert _ply(v, tri, mis) == orc.ply_binary(v, tri)
 
 
+@pytest.mark.parametrize("nt", [682, 683, 2047, 2048, 2049, 4096, 4097])
+def test_triangle_counts_around_the_prefix_sums_blocks(gpu, orc, nt):
+    """The all-chunks-at-once path sums 2048 elements per workgroup, over the triangles and over their 3 nt index positions: one workgroup's
+    worth of positions is 682 2/3 triangles, of triangles 2048; 4096 / 4097 end the second workgroup / start a third."""
+    v, grid = _grid(np.random.default_rng(7), 60, 40)
+    assert len(grid) >= nt
+    assert _pack(v, grid[:nt]) == orc.transfer_frame(v, grid[:nt]) and _pack.last_path == 1
+
+
+def test_more_workgroup_totals_than_one_round(gpu, orc):
+    """2 * 1025 * 1024 triangles are 1025 workgroups of 2048: the one workgroup that turns their totals into prefixes takes 1024 a round
+    and carries the sum into a second (the positions' totals, three times as many, take four rounds)."""
+    w, h = 1026, 1025
+    ids = np.arange(w * h, dtype=np.int32).reshape(h, w)
+    p, u, ur, r = ids[1:, :-1], ids[:-1, :-1], ids[:-1, 1:], ids[1:, 1:]
+    tri = np.stack([np.stack([r, u, p], -1), np.stack([r, ur, u], -1)], 2).reshape(-1, 3)
+    assert len(tri) == 1025 * 2048
+    v = _cloud(np.random.default_rng(8), w * h)
+    assert _pack(v, tri) == orc.transfer_frame(v, tri) and _pack.last_path == 1
+
+
 def test_chunk_that_spans_several_windows_and_reuse(gpu, orc):
     """Triangles that keep re-using a small vertex set never fill a chunk: the chunk must carry over many search windows
     (one window = 196608 triangles), then a grid part closes chunks normally; one packer serves several calls."""
