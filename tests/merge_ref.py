@@ -19,10 +19,20 @@ own drawTriangle through tests/golden/overlay_merge_ref.npz).
 
 Pinned as a whole: tests/golden/export_ref.npz / export_ref_digests.json hold the reference's own
 generateMeshFromDepthMaps(bgenerate_triangles = true), alone and after colour transfer, on wall, twins, ring and edge rigs
-(tests/golden/make_export_golden.py); tests/test_export_pin.py holds overlay_merge() to them.
+(tests/golden/make_export_golden.py); tests/test_export_pin.py holds overlay_merge() to them.  tests/golden/merge_boundary_ref.npz
+holds the same call on the boundary rigs of tests/merge_boundary_cases.py -- 1 mm depths, unequal intrinsics, zero writers, colliding
+reprojections (tests/golden/make_merge_boundary_golden.py); tests/test_merge_boundary_ref.py holds overlay_merge() to it.
 
 Defined where the reference is not: float -> unsigned short is x64's (cvttss2si to int32, INT_MIN for NaN and
-out of range, then the low 16 bits); every sensor must have the same size (mixed sizes are not in the export fixtures)."""
+out of range, then the low 16 bits); every sensor must have the same size (mixed sizes are not in the export fixtures).
+
+Two keyword arguments serve tests/test_merge_boundary_ref.py (defaults: neither; the restatement is then what it always was):
+  trace=   a dict (records are appended to trace[kind]) or a callable trace(kind, record); kinds "reproject" (per sensor), "map" (per
+           (base, overlay): the projection and the triangles of mapDepthMap), "draw" (per drawTriangle pass: the triangles, their tags
+           and the per-pixel class, CLASSES) and "overlay" (per (base, overlay): the base depth before the mask, the mapped depth and
+           tag, the raw and the eroded mask); a record names its place by "s" (sensor) or "b" and "o" (base, overlay);
+  rules=   names out of RULES: each flips ONE decision of the restatement (a mutant), so that a test can show that a rig's output
+           depends on that decision."""
 import numpy as np
 
 from tests import color_ref
@@ -31,6 +41,54 @@ DEPTH_THRESHOLD = 20   # :934
 CONF_THRESHOLD = 5     # :1007
 INT_MIN = -2 ** 31
 f32 = np.float32
+
+# the per-pixel classes of a draw (trace kind "draw", key "classes"); Z = the last covering triangle whose val is 0
+NEVER, ONE_WRITER, SEVERAL_NONE_ZERO, ZERO_THEN_LATER, SMALLER_DISCARDED, ZERO_ONLY = range(6)
+CLASSES = ("never covered", "one writer", "several writers, none zero", "zero writer followed by a later writer",
+           "earlier smaller val discarded by a zero writer", "zero writers only")
+# ZERO_THEN_LATER:   a writer behind Z decides the pixel (the kernel's t > zmax filter lets it through, zmax must be reset afterwards)
+# SMALLER_DISCARDED: as ZERO_THEN_LATER, and a writer before Z had a non-zero val below the winner's (the plain minimum would keep it)
+# ZERO_ONLY:         nothing behind Z: depth 0 with Z's tag (the resolve kernel's "key is none" branch)
+
+RULES = {
+    "depth_threshold_19": "|base - mapped| < 19 for < 20 (:934)",
+    "depth_threshold_21": "|base - mapped| < 21 for < 20 (:934)",
+    "conf_threshold_4": "tag > 4 for > 5 (:1007)",
+    "conf_threshold_6": "tag > 6 for > 5 (:1007)",
+    "zero_writers_ignored": "drawTriangle as the plain minimum of (val, index) (:684 without d == 0)",
+    "k_ge_z": "the writers k >= Z compete, not k > Z: Z's own 0 wins",
+    "nonzero_minimum": "every writer with a non-zero val competes, those before Z too: the smallest non-zero (val, index)",
+    "drop_lt_0": "mapDepthMap drops x < 0 / y < 0 for x < 1 / y < 1 (:867)",
+    "drop_gt_wh": "mapDepthMap drops x > w / y > h for x >= w / y >= h (:867)",
+    "reproject_d0_test": "a d == 0 test added to projectVerticesIntoDepthMap (:773)",
+    "first_vertex_wins": "the first vertex on a pixel keeps it in projectVerticesIntoDepthMap (:768-778)",
+    "den0_drawn": "triangles with den == 0 drawn: the NaN / inf weights convert to val 0 (:662)",
+    "one_erosion": "morphologyErode once (:1023-1024)",
+    "overlays_decreasing": "the overlays of a base visited in decreasing order (:1276-1283)",
+    "one_dropped_vertex_drawn": "a triangle with exactly one dropped vertex drawn with that vertex at (0, 0, 0) (:885)",
+}
+
+# Mutants that rules= accepts as well, but that no rig can kill through generateMeshFromDepthMaps (tests/merge_boundary_cases.py says why):
+# they are not part of the decisiveness table.
+UNDECIDED_RULES = {
+    "border_cleared": "morphologyErode clears the border rows and columns",
+    "assigned_ignored": "mapDepthMap projects assigned vertices too (:860)",
+}
+
+
+def _emit(trace, kind, **record):
+    if trace is None:
+        return
+    if callable(trace):
+        trace(kind, record)
+    else:
+        trace.setdefault(kind, []).append(record)
+
+
+def _rules(rules):
+    rules = frozenset(rules or ())
+    assert rules <= set(RULES) | set(UNDECIDED_RULES), sorted(rules - set(RULES) - set(UNDECIDED_RULES))
+    return rules
 
 
 def cvt_u16_x64(v):
@@ -67,11 +125,11 @@ def triangle_setup(x1, y1, d1, x2, y2, d2, x3, y3, d3):
     return s
 
 
-def triangle_pixels(s):
+def triangle_pixels(s, rules=frozenset()):
     """Every (triangle, pixel) the loops of :668-705 visit that passes the edge test, with its val.  Returns (k, x, y, val)."""
     bw = np.maximum(s["maxx"] - s["minx"], 0)
     bh = np.maximum(s["maxy"] - s["miny"], 0)
-    cnt = np.where(s["den"] != 0, bw * bh, 0)                                            # den == 0: no pixel (:662-663)
+    cnt = np.where((s["den"] != 0) | ("den0_drawn" in rules), bw * bh, 0)                # den == 0: no pixel (:662-663)
     k = np.repeat(np.arange(len(cnt)), cnt)
     j = np.arange(int(cnt.sum())) - np.repeat(np.cumsum(cnt) - cnt, cnt)
     bwk = bw[k]
@@ -85,29 +143,51 @@ def triangle_pixels(s):
     fden = s["den"][k].astype(f32)
     dx3, dy3 = (px - s["x3"][k]).astype(f32), (py - s["y3"][k]).astype(f32)
     term21, term22 = s["x32"][k] * dy3, s["x13"][k] * dy3                              # :671-672
-    w1 = (s["y23"][k] * dx3 + term21) / fden                                            # :677
-    w2 = (s["y31"][k] * dx3 + term22) / fden                                            # :678
-    w3 = f32(1.0) - w1 - w2                                                             # :679
-    fd1, fd2, fd3 = (f[k] for f in s["fd"])
-    val = cvt_u16_x64(fd1 * w1 + fd2 * w2 + fd3 * w3)                                   # :682
+    with np.errstate(all="ignore"):                                                     # (den == 0 only under the den0_drawn rule)
+        w1 = (s["y23"][k] * dx3 + term21) / fden                                        # :677
+        w2 = (s["y31"][k] * dx3 + term22) / fden                                        # :678
+        w3 = f32(1.0) - w1 - w2                                                         # :679
+        fd1, fd2, fd3 = (f[k] for f in s["fd"])
+        val = cvt_u16_x64(fd1 * w1 + fd2 * w2 + fd3 * w3)                               # :682
     return k, px, py, val
 
 
-def draw(tris, tags, w, h):
+def pixel_classes(k, p, val, npix):
+    """The class (CLASSES) of every pixel of a draw from its writers: triangle k writes val at pixel p."""
+    big = np.iinfo(np.int64).max
+    cover = np.bincount(p, minlength=npix)
+    z = np.full(npix, -1, dtype=np.int64)
+    np.maximum.at(z, p[val == 0], k[val == 0])
+    after = k > z[p]
+    win = np.full(npix, big, dtype=np.int64)
+    np.minimum.at(win, p[after], val[after])
+    before = (k < z[p]) & (val != 0)
+    low = np.full(npix, big, dtype=np.int64)
+    np.minimum.at(low, p[before], val[before])
+    cls = np.select([cover == 0, (z >= 0) & (win == big), (z >= 0) & (low < win), z >= 0, cover == 1],
+                    [NEVER, ZERO_ONLY, SMALLER_DISCARDED, ZERO_THEN_LATER, ONE_WRITER], SEVERAL_NONE_ZERO)
+    return cls
+
+
+def draw(tris, tags, w, h, trace=None, rules=None, **where):
     """drawTriangle (:598-706) of tris (m, 9) int {x1,y1,d1,x2,y2,d2,x3,y3,d3}, in order, into a zeroed (h, w) map, tags int (m,):
-    the closed form of the sequential loop.  Returns (depth u16 (h, w), tag u16 (h, w))."""
+    the closed form of the sequential loop.  Returns (depth u16 (h, w), tag u16 (h, w)).  `where` goes into the trace record."""
+    rules = _rules(rules)
     tris = np.asarray(tris, dtype=np.int64).reshape(-1, 9)
     tags = np.asarray(tags, dtype=np.int64)
     depth = np.zeros(h * w, dtype=np.int64)
     tag = np.zeros(h * w, dtype=np.int64)
     if len(tris) == 0:
+        _emit(trace, "draw", tris=tris, tags=tags, w=w, h=h, classes=np.zeros((h, w), dtype=np.int64), **where)
         return depth.reshape(h, w).astype(np.uint16), tag.reshape(h, w).astype(np.uint16)
-    k, px, py, val = triangle_pixels(triangle_setup(*tris.T))
+    k, px, py, val = triangle_pixels(triangle_setup(*tris.T), rules)
     p = py * w + px
+    if trace is not None:
+        _emit(trace, "draw", tris=tris, tags=tags, w=w, h=h, classes=pixel_classes(k, p, val, h * w).reshape(h, w), **where)
     z = np.full(h * w, -1, dtype=np.int64)
-    zero = val == 0
+    zero = (val == 0) & ("zero_writers_ignored" not in rules)
     np.maximum.at(z, p[zero], k[zero])                                                  # the last val-0 writer
-    after = k > z[p]
+    after = (k >= z[p]) if "k_ge_z" in rules else (val != 0) if "nonzero_minimum" in rules else (k > z[p])
     key = np.full(h * w, np.iinfo(np.int64).max, dtype=np.int64)
     np.minimum.at(key, p[after], (val[after] << 32) | k[after])                         # smallest (val, index) behind it
     won = key != np.iinfo(np.int64).max
@@ -187,63 +267,88 @@ def _sensors(rig, orc):
     return out
 
 
-def reproject(st):
+def reproject(st, trace=None, rules=None, **where):
     """projectVerticesIntoDepthMap (:749-782) with the sensor's own inverted pose, includeAssigned = false, nothing assigned yet."""
+    rules = _rules(rules)
     s = st.s
     x, y, d = color_ref.project(s.verts["X"], s.verts["Y"], s.verts["Z"], s.intr, s.wt)
     inb = (x >= 0) & (x < s.w) & (y >= 0) & (y < s.h)                                  # :773-774 (no d == 0 test)
+    if "reproject_d0_test" in rules:
+        inb &= d != 0
     pix = (y * s.w + x)[inb]
     idx = np.flatnonzero(inb)
-    np.maximum.at(st.d2v, pix, idx)                                                     # the last vertex wins (:768-778)
+    if "first_vertex_wins" in rules:
+        first = np.full(len(st.d2v), len(x), dtype=np.int64)
+        np.minimum.at(first, pix, idx)
+        st.d2v[first < len(x)] = first[first < len(x)]
+    else:
+        np.maximum.at(st.d2v, pix, idx)                                                 # the last vertex wins (:768-778)
     hit = st.d2v >= 0
     st.depth[hit] = d[st.d2v[hit]]
+    _emit(trace, "reproject", x=x, y=y, d=d, inb=inb, v2p=s.v2p, w=s.w, h=s.h, **where)
 
 
-def map_depth_map(ov, base, orc):
+def map_depth_map(ov, base, orc, trace=None, rules=None, **where):
     """mapDepthMap (:840-901) of overlay state `ov` into the camera of `base`.  Returns (mapped depth, tag) (h, w)."""
+    rules = _rules(rules)
     s, b = ov.s, base.s
     w, h = b.w, b.h
     tris = orc.generate_triangles(ov.depth.reshape(h, w).astype(np.uint16), ov.d2v.astype(np.int32))   # :844-845 (b's w, h)
     x, y, d = color_ref.project(s.verts["X"], s.verts["Y"], s.verts["Z"], b.intr, b.wt)                   # :851 inv, :866
-    ok = ~ov.assigned & ~((x < 1) | (x >= w) | (y < 1) | (y >= h) | (d == 0))                            # :860-861, :867-868
+    low = 0 if "drop_lt_0" in rules else 1
+    out = ((x > w) | (y > h)) if "drop_gt_wh" in rules else ((x >= w) | (y >= h))
+    free = np.ones_like(ov.assigned) if "assigned_ignored" in rules else ~ov.assigned
+    ok = free & ~((x < low) | (y < low) | out | (d == 0))                                               # :860-861, :867-868
     ds, xs, ys = np.where(ok, d, 0), np.where(ok, x, 0), np.where(ok, y, 0)
     conf = np.where(ok, s.conf[s.v2p].astype(np.int64), 0)                                             # :874
-    if len(tris) == 0:
-        return draw(np.zeros((0, 9)), np.zeros(0), w, h)
+    tris = np.asarray(tris, dtype=np.int64).reshape(-1, 3)
     i1, i2, i3 = tris[:, 0], tris[:, 1], tris[:, 2]
-    keep = (ds[i1] != 0) & (ds[i2] != 0) & (ds[i3] != 0)                                # :885-886
+    dropped = (ds[i1] == 0).astype(np.int64) + (ds[i2] == 0) + (ds[i3] == 0)
+    keep = dropped <= (1 if "one_dropped_vertex_drawn" in rules else 0)                 # :885-886
+    _emit(trace, "map", x=x, y=y, d=d, assigned=ov.assigned.copy(), ok=ok, tris=tris, dropped=dropped, w=w, h=h, **where)
     i1, i2, i3 = i1[keep], i2[keep], i3[keep]
     tags = cvt_u16_x64((conf[i1] + conf[i2] + conf[i3]).astype(f32) / f32(3.0))         # :889
     t9 = np.stack([xs[i1], ys[i1], ds[i1], xs[i2], ys[i2], ds[i2], xs[i3], ys[i3], ds[i3]], axis=1)
-    return draw(t9, tags, w, h)
+    return draw(t9, tags, w, h, trace, rules, **where)
 
 
-def assign_overlay(base, ov, orc):
+def assign_overlay(base, ov, orc, trace=None, rules=None, **where):
     """assignDepthMapOverlay (:932-1099) of overlay `ov` onto `base`: mask, two erosions, zero + assign."""
-    mapped, tag = map_depth_map(ov, base, orc)
+    rules = _rules(rules)
+    mapped, tag = map_depth_map(ov, base, orc, trace, rules, **where)
     mapped, tag = mapped.ravel().astype(np.int64), tag.ravel().astype(np.int64)
     b = base.s
-    mask = (base.depth != 0) & (np.abs(base.depth - mapped) < DEPTH_THRESHOLD) & (tag > CONF_THRESHOLD)   # :989-1020
-    mask = erode(erode(mask.reshape(b.h, b.w))).ravel()                                                # :1023-1024
+    dthr = 19 if "depth_threshold_19" in rules else 21 if "depth_threshold_21" in rules else DEPTH_THRESHOLD
+    cthr = 4 if "conf_threshold_4" in rules else 6 if "conf_threshold_6" in rules else CONF_THRESHOLD
+    raw = (base.depth != 0) & (np.abs(base.depth - mapped) < dthr) & (tag > cthr)                       # :989-1020
+    mask = raw.reshape(b.h, b.w)
+    for _ in range(1 if "one_erosion" in rules else 2):                                                 # :1023-1024
+        mask = erode(mask)
+        if "border_cleared" in rules:
+            mask[[0, -1], :] = False
+            mask[:, [0, -1]] = False
+    mask = mask.ravel()
+    _emit(trace, "overlay", base_depth=base.depth.copy(), mapped=mapped, tag=tag, mask_raw=raw, mask_eroded=mask.copy(), w=b.w, h=b.h, **where)
     base.depth[mask] = 0                                                                               # :1026-1032
     base.assigned[base.d2v[mask]] = True
 
 
-def overlay_merge(rig, orc):
+def overlay_merge(rig, orc, trace=None, rules=None):
     """generateMeshFromDepthMaps(..., bgenerate_triangles = true)'s triangles for a synth.Rig of equal-sized sensors.
     Returns (triangles int32 (m, 3), {"reprojected": u16 per tick pixel, "merged": u16 per tick pixel, "assigned": u8 per vertex,
     "offsets": vertex offsets [n+1]})."""
     sensors = _sensors(rig, orc)
     assert all(s.w == sensors[0].w and s.h == sensors[0].h for s in sensors), "the merge needs equal sensor sizes"
+    rules = _rules(rules)
     st = [_State(s) for s in sensors]
-    for x in st:
-        reproject(x)
+    for k, x in enumerate(st):
+        reproject(x, trace, rules, s=k)
     reprojected = np.concatenate([x.depth for x in st]).astype(np.uint16)
     n = len(st)
     for b in range(n):                                                                   # :1250
-        for o in range(n):                                                               # :1276-1283
+        for o in (range(n - 1, -1, -1) if "overlays_decreasing" in rules else range(n)):   # :1276-1283
             if o != b:
-                assign_overlay(st[b], st[o], orc)
+                assign_overlay(st[b], st[o], orc, trace, rules, b=b, o=o)
     off = np.concatenate([[0], np.cumsum([len(s.verts) for s in sensors])]).astype(np.int64)
     tris = [orc.generate_triangles(x.depth.reshape(x.s.h, x.s.w).astype(np.uint16), x.d2v.astype(np.int32), int(off[k]))
             for k, x in enumerate(st)]                                                   # :1659-1691, formMesh :1611-1627

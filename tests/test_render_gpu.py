@@ -9,61 +9,11 @@ import pytest
 
 from livescan3d_amd import native
 from tests import color_cases, merge_cases, render_ref
-from tests.support import ROOT, Guarded, child, export
+from tests.support import ROOT, Clouds, Guarded, child, export
 
 pytestmark = pytest.mark.gpu
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "overlay_merge_ref.npz")
-PREFILL = 249   # -7 as a byte: what DeviceFusion prefills its tables with
-
-
-class Clouds:
-    """A plan of one `size` sensor per tick with hand-made clouds uploaded as its ticks: clouds[k] = (vertices, triangles or None)."""
-
-    def __init__(self, torch, clouds, size=(64, 48)):
-        self.torch, self.clouds, self.T = torch, clouds, len(clouds)
-        self.plan = native.FusionPlan(0, self.T, [size[0]], [size[1]])
-        cap = self.cap = self.plan.capacity
-        v = np.zeros((self.T, cap, 16), np.uint8)
-        t = np.full((self.T, 2 * cap, 3), -3, np.int32)     # what lies behind a tick's triangles is never read
-        off, toff = np.zeros((self.T, 2), np.int32), np.zeros((self.T, 2), np.int32)
-        for k, (cv, ct) in enumerate(clouds):
-            assert len(cv) <= cap and (ct is None or len(ct) <= 2 * cap)
-            v[k, :len(cv)] = np.frombuffer(cv.tobytes(), np.uint8).reshape(-1, 16)
-            off[k, 1] = len(cv)
-            if ct is not None:
-                t[k, :len(ct)] = ct
-                toff[k, 1] = len(ct)
-        self.v, self.t, self.off, self.toff = (torch.from_numpy(a).cuda() for a in (v, t, off, toff))
-
-    def render(self, intr, wt, w, h, points=False):
-        """-> (depth u16 [T, V, h, w], rgb u8 [T, V, h, w, 3]) between guard bands, prefilled."""
-        V = np.asarray(intr).size // 7
-        gd, gc = Guarded(self.torch, self.T * V * w * h * 2, "cuda"), Guarded(self.torch, self.T * V * w * h * 3, "cuda")
-        gd.body().fill_(PREFILL)
-        gc.body().fill_(PREFILL)
-        self.plan.render_views(intr, wt, w, h, self.v.data_ptr(), self.off.data_ptr(), 0 if points else self.t.data_ptr(),
-                               0 if points else self.toff.data_ptr(), gd.ptr, gc.ptr)
-        self.torch.cuda.synchronize()
-        assert gd.intact() and gc.intact()
-        return (gd.body().cpu().numpy().view(np.uint16).reshape(self.T, V, h, w), gc.body().cpu().numpy().reshape(self.T, V, h, w, 3))
-
-    def check(self, intr, wt, w, h, points=False):
-        depth, rgb = self.render(intr, wt, w, h, points)
-        intr, wt = np.asarray(intr, np.float32).reshape(-1, 7), np.asarray(wt, np.float32).reshape(-1, 12)
-        diags = []
-        for k, (cv, ct) in enumerate(self.clouds):
-            for q in range(len(intr)):
-                wd, wc, info = render_ref.render(cv, None if points else (np.zeros((0, 3), np.int32) if ct is None else ct), intr[q], wt[q], w, h)
-                assert np.array_equal(depth[k, q], wd), (k, q, int((depth[k, q] != wd).sum()))
-                assert np.array_equal(rgb[k, q], wc), (k, q, int((rgb[k, q] != wc).any(axis=-1).sum()))
-                d = self.plan.render_diagnostics(k, q)
-                assert d["drawn"] == info["drawn"] and d["pixels"] == info["pixels"], (k, q, d, info)
-                diags.append(d)
-        return depth, rgb, diags
-
-    def close(self):
-        self.plan.close()
 
 
 def _golden_clouds():
