@@ -37,6 +37,30 @@ def numpy_create_vertices(depth, rgb, intr, wt, bounds):
     return out
 
 
+def np_warp_target(w, h, intr):
+    """The warp target of every pixel of a w x h frame (depthprocessing.cpp:205-213: u, v, r, d, (int)), vectorised in float32 with one
+    rounding per operation and the cvttss2si rule of py_radial's f2i.  Returns int64 (h * w): the destination pixel x_corr + y_corr * w of
+    source pixel x + y * w, -1 where the target lies outside the frame.  It does not depend on the depth values."""
+    f = np.float32
+    cx, cy, fx, fy, r2, r4, r6 = [f(v) for v in intr]
+    y, x = np.meshgrid(np.arange(h), np.arange(w), indexing="ij")
+    with np.errstate(all="ignore"):
+        u = (x.astype(f) - cx) / fx
+        v = (y.astype(f) - cy) / fy
+        r = u * u + v * v
+        d = f(1) - r2 * r - r4 * r * r - r6 * r * r * r
+        xf = u * d * fx + cx
+        yf = v * d * fy + cy
+
+        def f2i(a):
+            ok = (a > f(-2147483904.0)) & (a < f(2147483648.0))     # NaN / out of range: cvttss2si -> INT_MIN
+            return np.where(ok, np.trunc(np.where(ok, a, f(0))).astype(np.int64), -2147483648)
+
+        xc, yc = f2i(xf), f2i(yf)
+    inside = (xc >= 0) & (xc < w) & (yc >= 0) & (yc < h)
+    return np.where(inside, xc + yc * w, -1).ravel()
+
+
 def py_radial(depth2d, rgb3, intr):
     f = np.float32
     h, w = depth2d.shape
