@@ -53,25 +53,6 @@ struct PackArgs {
                               // all ticks back to back, ONE contiguous run per shard: what the RCCL all-gather sends as it is
 };
 
-// Aligned copy of n bytes that sit in LDS at lds[lead ..), lead = (address of dst) mod 16, to dst: the 16-byte chunks that lie
-// wholly inside the range go out as one store each, the (< 16-byte) pieces at either end element by element (ELEM bytes each) --
-// the neighbouring tiles own the rest of those chunks.
-template <int ELEM, typename T>
-__device__ __forceinline__ void store_run(T *dst, const T *lds, int lead, int n)
-{
-    static_assert(sizeof(T) == ELEM, "element size");
-    const int end = lead + n;                        // in bytes, relative to the aligned start of the first chunk
-    const int c0 = lead ? 1 : 0, c1 = end >> 4;       // chunks [c0, c1) are whole
-    uint4 *g16 = reinterpret_cast<uint4 *>(reinterpret_cast<unsigned char *>(dst) - lead);
-    const uint4 *l16 = reinterpret_cast<const uint4 *>(lds);
-    for (int j = c0 + (int)threadIdx.x; j < c1; j += kThreads) g16[j] = l16[j];
-    const int head = lead ? min(n, 16 - lead) : 0;   // bytes before the first whole chunk
-    const int tail0 = max(head, 16 * c1 - lead);     // first byte after the last whole chunk
-    const int t = (int)threadIdx.x * ELEM;
-    if (t < head) dst[threadIdx.x] = lds[lead / ELEM + threadIdx.x];
-    if (tail0 + t < n) dst[tail0 / ELEM + threadIdx.x] = lds[(lead + tail0) / ELEM + threadIdx.x];
-}
-
 // The survivors of a tile are staged in LDS in rank order and leave as 16-byte stores (the first version had every lane store
 // its own short run: 32 one- and two-byte stores per lane, 0.32 ms per 64 ticks x 8 sensors against 0.14 at the copy rate).
 __global__ __launch_bounds__(kThreads) void pack_kernel(const FuseArgs a, const PackArgs pk)

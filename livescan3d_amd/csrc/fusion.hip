@@ -761,7 +761,7 @@ extern "C" void lsnFusionDestroy(LsnFusion *p)
             (void)hipEventDestroy(e.first);
             (void)hipEventDestroy(e.second);
         }
-        if (p->radial_done) (void)hipEventDestroy(p->radial_done);
+        p->rd.destroy_event();
         if (p->side) {
             (void)hipStreamSynchronize(p->side);
             (void)hipStreamDestroy(p->side);

@@ -445,6 +445,26 @@ __device__ __forceinline__ void stage_and_store(uint4 *stage, const bool (&keep)
     }
 }
 
+// Aligned copy of n bytes that sit in LDS at lds[lead ..), lead = (address of dst) mod 16, to dst: the 16-byte chunks that lie
+// wholly inside the range go out as one store each, the (< 16-byte) pieces at either end element by element (ELEM bytes each) --
+// the neighbouring tiles own the rest of those chunks.  Every thread of a kThreads workgroup calls it.  (exchange.hip: pack_kernel's survivor
+// streams; radial.hip: radial_gather_pack_kernel's tile.)
+template <int ELEM, typename T>
+__device__ __forceinline__ void store_run(T *dst, const T *lds, int lead, int n)
+{
+    static_assert(sizeof(T) == ELEM, "element size");
+    const int end = lead + n;                        // in bytes, relative to the aligned start of the first chunk
+    const int c0 = lead ? 1 : 0, c1 = end >> 4;       // chunks [c0, c1) are whole
+    uint4 *g16 = reinterpret_cast<uint4 *>(reinterpret_cast<unsigned char *>(dst) - lead);
+    const uint4 *l16 = reinterpret_cast<const uint4 *>(lds);
+    for (int j = c0 + (int)threadIdx.x; j < c1; j += kThreads) g16[j] = l16[j];
+    const int head = lead ? min(n, 16 - lead) : 0;   // bytes before the first whole chunk
+    const int tail0 = max(head, 16 * c1 - lead);     // first byte after the last whole chunk
+    const int t = (int)threadIdx.x * ELEM;
+    if (t < head) dst[threadIdx.x] = lds[lead / ELEM + threadIdx.x];
+    if (tail0 + t < n) dst[tail0 / ELEM + threadIdx.x] = lds[(lead + tail0) / ELEM + threadIdx.x];
+}
+
 // Mode 0, between the count and the write launch: one workgroup per tick turns that tick's tile counts into exclusive
 // prefixes in place and fills the per-sensor offset table (offsets[tick][f] = first vertex of sensor f, [n_frames] = total).
 // 1024 threads x 8 consecutive counts each: a tick of up to 8192 tiles (16 x 1024x1024) is ONE round -- two 16-byte loads, a serial
@@ -543,19 +563,7 @@ struct LsnFusion {
     lsn::DevBuf xtab, ytab;
     lsn::DevBuf pixmap, pm_first, pm_mask, tri_counts, tri_codes;  // triangulation scratch, allocated on first use
     bool pixmap_compact = false;     // which form of the pixel -> vertex map the last run wrote
-    lsn::DevBuf winner, map_copy, colors_copy, radial;  // radial-correction scratch, allocated on first use
-    lsn::DevBuf cand;                                   // [pixels per tick][4] warp candidates of the current intrinsics
-    lsn::DevBuf ctab;                                   // [pixels per tick] their compact form (one dword per destination)
-    lsn::DevBuf bands, holes, work, work2, work_cnt;    // hole closing: band list, hole bitmap, per-frame work lists (two, used in turn) and their counters
-    int band_rows = 0, bands_per_tick = 0;              // what `bands` was built for
-    hipStream_t work_cnt_stream = nullptr;              // the stream of the last radial call ...
-    hipEvent_t radial_done = nullptr;                   // ... and the end of its chain: a call on another stream waits for it (radial.hip radial_correct)
-    bool radial_chain_open = false;                     // radial_done has been recorded at least once
-    hipEvent_t after_band = nullptr;                    // not owned: recorded behind the band kernel of a radial call (set by lsnTickRun around its calls)
-    bool work_cnt_clean = false;                        // the closing chain of the last call was enqueued to its end (it leaves work_cnt zeroed)
-    bool band_attr_set = false;
-    std::vector<float> radial_intr;                     // the intrinsics `cand` was built for
-    bool cand_valid = false, cand_overflow = false;
+    lsn::RadialScratch rd;           // the radial correction (radial.hip), allocated on first use
     // pipelined mode: the count + scan of call k+1 run on a side stream while the write kernel of call k is still busy
     bool pipelined = false;
     hipStream_t side = nullptr;

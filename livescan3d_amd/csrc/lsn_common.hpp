@@ -9,6 +9,7 @@
 #include <exception>
 #include <new>
 #include <string>
+#include <vector>
 
 #include "../../include/NativeUtils.h"
 
@@ -195,6 +196,41 @@ struct NormalsScratch {
 // d_normals_out: tick_vert x 3 floats per tick; prof (nullable): the plan whose lsnFusionProfile brackets the face pass.
 int normals(NormalsScratch &ns, const char *who, const MeshBatch &m, void *d_normals_out, LsnFusion *prof, hipStream_t s);
 int normals_counts(NormalsScratch &ns, const char *who, int tick, int *n_used, int *n_skipped, int *n_zero_normals, hipStream_t s);
+
+// The radial correction (radial.hip): what one plan keeps between calls -- the sensors' parameters, the warp tables of the current
+// calibration ([pixels per tick][4] candidates and their compact form, one dword per destination) with the intrinsics they were built for,
+// the scratch maps and the winner array of the routes that warp through memory, and the hole closing's band list, hole bitmap, two
+// work lists (used in turn) and their counters.  All of it is shared by every call on the plan: calls on one stream are ordered by
+// the stream, and an event recorded behind every chain orders a call on another stream behind the chain before it.  Reserved by the
+// first call that needs each piece, grown by a call that needs more.
+struct RadialScratch {
+    DevBuf params, cand, ctab;
+    std::vector<float> intr;          // the intrinsics `cand` / `ctab` were built for
+    bool tables_valid = false, overflow = false;   // overflow: a destination has more than four sources, the calls take the atomicMax warp
+    DevBuf winner, map_copy, colors_copy;
+    DevBuf bands, holes, work, work2, work_cnt;
+    int band_rows = 0, bands_per_tick = 0;         // what `bands` was built for
+    bool work_cnt_clean = false;      // the closing chain of the last call was enqueued to its end (it leaves work_cnt zeroed)
+    bool band_attr_set = false;
+    hipEvent_t after_band = nullptr;  // not owned: recorded behind the band kernel of a call (set by lsnTickRun around its calls)
+    hipStream_t stream = nullptr;     // the stream of the last call ...
+    hipEvent_t done = nullptr;        // ... and the end of its chain
+    bool chain_open = false;          // `done` has been recorded at least once
+    // Work on `s` that clears, refills or reads the scratch first waits for the previous chain's end if that was enqueued on another stream.
+    int wait_for_chain(hipStream_t s)
+    {
+        if (chain_open && stream != s) LSN_HIP(hipStreamWaitEvent(s, done, 0));
+        return 0;
+    }
+    // `s` now holds the last chain (also one that failed half-way: whatever it did enqueue is what the next stream has to wait for).
+    void chain_ends_on(hipStream_t s)
+    {
+        if (hipEventRecord(done, s) == hipSuccess) chain_open = true;
+        else (void)hipGetLastError();
+        stream = s;
+    }
+    void destroy_event() { if (done) (void)hipEventDestroy(done); }   // lsnFusionDestroy, with the plan's device current
+};
 
 // The refine pass (icp.hip) on ONE tick's merged cloud, resident on `device` and final: vertices -> packed points -> Gauss-Seidel loop.
 // offsets: the tick's n_sensors + 1 row on the HOST; Rt: n_sensors x 12 floats, receives {Rs[i][9], Ts[i][3]}; h_clouds (host) / d_clouds

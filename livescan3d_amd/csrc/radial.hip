@@ -1,19 +1,28 @@
 // radial.hip -- depthMapAndColorSetRadialCorrection: forward warp + raster-order hole closing, lsnFusionRadialCorrect.
-// Shares the plan of fusion.hip (fusion_shared.hpp).
+// Shares the plan of fusion.hip (fusion_shared.hpp); its state on the plan is lsn::RadialScratch (lsn_common.hpp).
 #include "fusion_shared.hpp"
 
 namespace {
 
 // ---- radial correction (the step before the fusion path on every tick) ---------------------------------------------
 //
-// Replaces depthMapAndColorRadialCorrection (src/NativeUtils/depthprocessing.cpp:191-261) and its export (:1794-1815):
-//   1. forward warp of every valid pixel to (x_corr, y_corr); the reference's raster-order loop lets the LAST source
-//      pixel win a collision -> atomicMax of the source index per destination, then a gather;
-//   2. hole closing, which the reference does IN PLACE in raster order: a pixel filled earlier in the pass is seen by
-//      its right / lower neighbours.  Those dependencies (left, up-left, up, up-right) are honoured exactly by a skewed
-//      wavefront: one thread per row, row y runs two columns behind row y-1, one workgroup barrier per step.
-// All arithmetic in the reference's order (contraction off); (int) follows the x86-64 cvttss2si the reference is built
-// with: NaN / out-of-range -> INT_MIN, which then fails the >= 0 test.
+// Replaces depthMapAndColorRadialCorrection (src/NativeUtils/depthprocessing.cpp:191-261) and its export (:1794-1815): a forward warp
+// of every valid pixel to (x_corr, y_corr), where the reference's raster-order loop lets the LAST source pixel win a collision
+// (:200-218), then hole closing IN PLACE in raster order (:223-256): a pixel filled earlier in the pass is seen by its right / lower
+// neighbours.  All arithmetic in the reference's order (contraction off); (int) follows the x86-64 cvttss2si the reference is built
+// with: NaN / out-of-range -> INT_MIN, which then fails the >= 0 test.  The file, top to bottom:
+//   * per calibration (build_warp_table): radial_cand_fill / sort / pack_kernel -- every destination's (at most four) sources, then the
+//     compact one-dword table the ticks read;
+//   * the warp of a tick: gather_batch, table -> candidates' depths -> the winner's colour, inside the band kernel (out of place) or
+//     radial_gather_pack_kernel (in place: to the scratch maps first).  OVERFLOW FALLBACK: a calibration with more than four sources on
+//     one destination, or LSN_RADIAL_FORCE_ATOMIC=1, takes radial_warp_kernel + radial_gather_kernel (atomicMax of the source index,
+//     then a gather) to the scratch maps instead;
+//   * the closing, two passes (close_two_pass): radial_band_kernel closes every band of rows against the un-closed map and lists the holes
+//     behind a fill; close_fix_round_kernel (two grid-wide rounds, batches of at most 128 frames) and close_fix_kernel (one workgroup per
+//     frame: rounds in LDS, full sweeps when a round list outgrows it -- LSN_RADIAL_TINY_LISTS=1 forces them) re-evaluate those until
+//     nothing changes.  LSN_RADIAL_BAND_ROWS sets the band height.  ABLATION: LSN_RADIAL_CLOSE=wavefront closes the scratch maps with
+//     radial_close_kernel, the ordered skewed wavefront of round 1, instead (close_wavefront);
+//   * the host side: radial_correct and its pieces, the exports.
 
 struct RadialParams { float cx, cy, fx, fy, r2, r4, r6, pad; };
 
@@ -22,32 +31,76 @@ __device__ __forceinline__ int f2i_x86(float v)
     return (v > -2147483904.0f && v < 2147483648.0f) ? (int)v : (int)0x80000000;
 }
 
+// 0x00BBGGRR as the three bytes of a pixel, and back
+__device__ __forceinline__ void put_rgb(unsigned char *c3, unsigned int v)
+{
+    c3[0] = (unsigned char)v;
+    c3[1] = (unsigned char)(v >> 8);
+    c3[2] = (unsigned char)(v >> 16);
+}
+__device__ __forceinline__ unsigned int get_rgb(const unsigned char *c3)
+{
+    return (unsigned int)c3[0] | ((unsigned int)c3[1] << 8) | ((unsigned int)c3[2] << 16);
+}
+
+// the warp target of pixel (x, y) (:204-212): its destination pixel in the frame, or -1
+__device__ __forceinline__ long long warp_target(const RadialParams &P, const FrameDesc &fd, int x, int y)
+{
+    const float u = ((float)x - P.cx) / P.fx;                              // :204
+    const float v = ((float)y - P.cy) / P.fy;                              // :205
+    const float r = u * u + v * v;                                         // :206
+    const float d = 1 - P.r2 * r - P.r4 * r * r - P.r6 * r * r * r;        // :207
+    const int x_corr = f2i_x86(u * d * P.fx + P.cx);                       // :209
+    const int y_corr = f2i_x86(v * d * P.fy + P.cy);                       // :210
+    if (x_corr >= 0 && y_corr >= 0 && x_corr < fd.w && y_corr < fd.h) return x_corr + (long long)y_corr * fd.w;   // :212
+    return -1;
+}
+
+// The tile of kTile pixels a workgroup of the tile kernels works on: its frame, the frame's first pixel in the batch, the tile's first
+// pixel inside the frame.  (Not fusion_shared.hpp's Tile / locate: that resolves FuseArgs' input pointers and unprojection tables.)
+struct RadialTile {
+    int frame, p0;
+    long long fb;
+    FrameDesc fd;
+};
+__device__ __forceinline__ RadialTile tile_at(const FrameDesc *frames, const TileDesc *tiles, int tick, int tile, long long tick_pix_stride)
+{
+    RadialTile t;
+    t.frame = tiles[tile].frame;
+    t.fd = frames[t.frame];
+    t.fb = tick * tick_pix_stride + t.fd.depth_off;
+    t.p0 = (tile - t.fd.tile_start) * kTile;
+    return t;
+}
+// ... of a launch over a batch: blockIdx.x = tick * tiles_per_tick + tile
+__device__ __forceinline__ RadialTile batch_tile(const FrameDesc *frames, const TileDesc *tiles, int tiles_per_tick, long long tick_pix_stride)
+{
+    const int tick = blockIdx.x / tiles_per_tick;
+    return tile_at(frames, tiles, tick, blockIdx.x - tick * tiles_per_tick, tick_pix_stride);
+}
+// f(p) for the tile's pixels p of the frame, consecutive lanes -> consecutive pixels
+template <class F>
+__device__ __forceinline__ void for_tile_pixels(const RadialTile &t, F f)
+{
+    for (int i = threadIdx.x; i < kTile; i += kThreads) {
+        const int p = t.p0 + i;
+        if (p >= t.fd.npix) break;
+        f(p);
+    }
+}
+
 __global__ __launch_bounds__(kThreads) void radial_warp_kernel(const FrameDesc *frames, const TileDesc *tiles, const RadialParams *rp,
                                                                const unsigned short *depth, unsigned int *winner, int tiles_per_tick,
                                                                long long tick_pix_stride)
 {
-    const int tick = blockIdx.x / tiles_per_tick;
-    const int tile = blockIdx.x - tick * tiles_per_tick;
-    const TileDesc td = tiles[tile];
-    const FrameDesc fd = frames[td.frame];
-    const RadialParams P = rp[td.frame];
-    const unsigned short *dep = depth + tick * tick_pix_stride + fd.depth_off;
-    unsigned int *win = winner + tick * tick_pix_stride + fd.depth_off;
-    const int p0 = (tile - fd.tile_start) * kTile;
-    for (int i = threadIdx.x; i < kTile; i += kThreads) {  // consecutive lanes -> consecutive pixels
-        const int p = p0 + i;
-        if (p >= fd.npix) break;
-        if (dep[p] == 0) continue;                                             // :202-203
-        const int y = p / fd.w, x = p - y * fd.w;
-        const float u = ((float)x - P.cx) / P.fx;                              // :204
-        const float v = ((float)y - P.cy) / P.fy;                              // :205
-        const float r = u * u + v * v;                                         // :206
-        const float d = 1 - P.r2 * r - P.r4 * r * r - P.r6 * r * r * r;        // :207
-        const int x_corr = f2i_x86(u * d * P.fx + P.cx);                       // :209
-        const int y_corr = f2i_x86(v * d * P.fy + P.cy);                       // :210
-        if (x_corr >= 0 && y_corr >= 0 && x_corr < fd.w && y_corr < fd.h)      // :212
-            atomicMax(&win[x_corr + (long long)y_corr * fd.w], (unsigned int)p + 1u);  // later source pixel wins (:214-215)
-    }
+    const RadialTile t = batch_tile(frames, tiles, tiles_per_tick, tick_pix_stride);
+    const RadialParams P = rp[t.frame];
+    for_tile_pixels(t, [&](int p) {
+        if (depth[t.fb + p] == 0) return;                                      // :202-203
+        const int y = p / t.fd.w, x = p - y * t.fd.w;
+        const long long dst = warp_target(P, t.fd, x, y);
+        if (dst >= 0) atomicMax(&winner[t.fb + dst], (unsigned int)p + 1u);    // later source pixel wins (:214-215)
+    });
 }
 
 __global__ __launch_bounds__(kThreads) void radial_gather_kernel(const FrameDesc *frames, const TileDesc *tiles, const unsigned short *depth,
@@ -55,28 +108,13 @@ __global__ __launch_bounds__(kThreads) void radial_gather_kernel(const FrameDesc
                                                                  unsigned short *map_copy, unsigned char *colors_copy, int tiles_per_tick,
                                                                  long long tick_pix_stride)
 {
-    const int tick = blockIdx.x / tiles_per_tick;
-    const int tile = blockIdx.x - tick * tiles_per_tick;
-    const TileDesc td = tiles[tile];
-    const FrameDesc fd = frames[td.frame];
-    const long long fb = tick * tick_pix_stride + fd.depth_off;
-    const int p0 = (tile - fd.tile_start) * kTile;
-    for (int i = threadIdx.x; i < kTile; i += kThreads) {
-        const int p = p0 + i;
-        if (p >= fd.npix) break;
-        const unsigned int wsrc = winner[fb + p];
-        unsigned short d = 0;
-        unsigned char c0 = 0, c1 = 0, c2 = 0;
-        if (wsrc) {
-            const long long s = fb + (long long)(wsrc - 1u);
-            d = depth[s];
-            c0 = rgb[3 * s]; c1 = rgb[3 * s + 1]; c2 = rgb[3 * s + 2];
-        }
-        map_copy[fb + p] = d;
-        colors_copy[3 * (fb + p)] = c0;
-        colors_copy[3 * (fb + p) + 1] = c1;
-        colors_copy[3 * (fb + p) + 2] = c2;
-    }
+    const RadialTile t = batch_tile(frames, tiles, tiles_per_tick, tick_pix_stride);
+    for_tile_pixels(t, [&](int p) {
+        const unsigned int wsrc = winner[t.fb + p];
+        const long long s = t.fb + (long long)(wsrc - 1u);
+        map_copy[t.fb + p] = wsrc ? depth[s] : (unsigned short)0;
+        put_rgb(colors_copy + 3 * (t.fb + p), wsrc ? get_rgb(rgb + 3 * s) : 0u);
+    });
 }
 
 // The warp target of a pixel depends on the intrinsics only, not on the depth values: per calibration, every destination
@@ -87,28 +125,17 @@ __global__ __launch_bounds__(kThreads) void radial_gather_kernel(const FrameDesc
 __global__ __launch_bounds__(kThreads) void radial_cand_fill_kernel(const FrameDesc *frames, const TileDesc *tiles, const RadialParams *rp,
                                                                     unsigned int *count, unsigned int *cand, int *overflow)
 {
-    const int tile = blockIdx.x;
-    const TileDesc td = tiles[tile];
-    const FrameDesc fd = frames[td.frame];
-    const RadialParams P = rp[td.frame];
-    const int p0 = (tile - fd.tile_start) * kTile;
-    for (int i = threadIdx.x; i < kTile; i += kThreads) {
-        const int p = p0 + i;
-        if (p >= fd.npix) break;
-        const int y = p / fd.w, x = p - y * fd.w;
-        const float u = ((float)x - P.cx) / P.fx;                              // :204
-        const float v = ((float)y - P.cy) / P.fy;                              // :205
-        const float r = u * u + v * v;                                         // :206
-        const float d = 1 - P.r2 * r - P.r4 * r * r - P.r6 * r * r * r;        // :207
-        const int x_corr = f2i_x86(u * d * P.fx + P.cx);                       // :209
-        const int y_corr = f2i_x86(v * d * P.fy + P.cy);                       // :210
-        if (x_corr >= 0 && y_corr >= 0 && x_corr < fd.w && y_corr < fd.h) {    // :212
-            const long long dst = fd.depth_off + x_corr + (long long)y_corr * fd.w;
-            const unsigned int slot = atomicAdd(&count[dst], 1u);
-            if (slot < 4) cand[4 * dst + slot] = (unsigned int)p + 1u;
-            else atomicOr(overflow, 1);
-        }
-    }
+    const RadialTile t = tile_at(frames, tiles, 0, blockIdx.x, 0);   // one tick's tiles
+    const RadialParams P = rp[t.frame];
+    for_tile_pixels(t, [&](int p) {
+        const int y = p / t.fd.w, x = p - y * t.fd.w;
+        const long long q = warp_target(P, t.fd, x, y);
+        if (q < 0) return;
+        const long long dst = t.fb + q;
+        const unsigned int slot = atomicAdd(&count[dst], 1u);
+        if (slot < 4) cand[4 * dst + slot] = (unsigned int)p + 1u;
+        else atomicOr(overflow, 1);
+    });
 }
 
 __global__ __launch_bounds__(kThreads) void radial_cand_sort_kernel(uint4 *cand, long long n)
@@ -120,24 +147,6 @@ __global__ __launch_bounds__(kThreads) void radial_cand_sort_kernel(uint4 *cand,
     auto cswap = [](unsigned int &a, unsigned int &b) { const unsigned int hi = max(a, b), lo = min(a, b); a = hi; b = lo; };
     cswap(c.x, c.y); cswap(c.z, c.w); cswap(c.x, c.z); cswap(c.y, c.w); cswap(c.y, c.z);
     cand[i] = c;
-}
-
-// Aligned copy of n bytes that sit in LDS at lds[lead ..), lead = (address of dst) mod 16, to dst: whole 16-byte chunks as one store
-// each, the ragged ends element by element (the twin of store_run in exchange.hip).
-template <int ELEM, typename T>
-__device__ __forceinline__ void store_tile_run(T *dst, const T *lds, int lead, int n)
-{
-    static_assert(sizeof(T) == ELEM, "element size");
-    const int end = lead + n;
-    const int c0 = lead ? 1 : 0, c1 = end >> 4;
-    uint4 *g16 = reinterpret_cast<uint4 *>(reinterpret_cast<unsigned char *>(dst) - lead);
-    const uint4 *l16 = reinterpret_cast<const uint4 *>(lds);
-    for (int j = c0 + (int)threadIdx.x; j < c1; j += kThreads) g16[j] = l16[j];
-    const int head = lead ? min(n, 16 - lead) : 0;
-    const int tail0 = max(head, 16 * c1 - lead);
-    const int t = (int)threadIdx.x * ELEM;
-    if (t < head) dst[threadIdx.x] = lds[lead / ELEM + threadIdx.x];
-    if (tail0 + t < n) dst[tail0 / ELEM + threadIdx.x] = lds[(lead + tail0) / ELEM + threadIdx.x];
 }
 
 // ---- the compact warp table ------------------------------------------------------------------------------------------------
@@ -154,14 +163,9 @@ constexpr unsigned int kWide = 0xFFFFFFFFu;
 __global__ __launch_bounds__(kThreads) void radial_cand_pack_kernel(const FrameDesc *frames, const TileDesc *tiles, const uint4 *cand,
                                                                     unsigned int *ctab)
 {
-    const int tile = blockIdx.x;
-    const TileDesc td = tiles[tile];
-    const FrameDesc fd = frames[td.frame];
-    const int p0 = (tile - fd.tile_start) * kTile;
-    for (int i = threadIdx.x; i < kTile; i += kThreads) {
-        const int p = p0 + i;
-        if (p >= fd.npix) break;
-        const uint4 c = cand[fd.depth_off + p];
+    const RadialTile t = tile_at(frames, tiles, 0, blockIdx.x, 0);   // one tick's tiles
+    for_tile_pixels(t, [&](int p) {
+        const uint4 c = cand[t.fb + p];
         auto enc = [&](unsigned int src, unsigned int &code) {
             code = 0;
             if (!src) return true;
@@ -172,8 +176,8 @@ __global__ __launch_bounds__(kThreads) void radial_cand_pack_kernel(const FrameD
         };
         unsigned int c0, c1;
         const bool ok0 = enc(c.x, c0), ok1 = enc(c.y, c1);
-        ctab[fd.depth_off + p] = (ok0 && ok1 && c.z == 0) ? (c0 | (c1 << 16)) : kWide;
-    }
+        ctab[t.fb + p] = (ok0 && ok1 && c.z == 0) ? (c0 | (c1 << 16)) : kWide;
+    });
 }
 
 typedef unsigned int u32_ua __attribute__((aligned(1)));
@@ -263,8 +267,7 @@ __device__ __forceinline__ void gather_batch(const WarpSrc &S, long long fb, lon
 // test inside colour() cost radial_band_kernel 30 %: 456 -> 590 us per 512 frames).
 __device__ __forceinline__ unsigned int one_pixel_colour(const WarpSrc &S, long long fb, unsigned int depth)
 {
-    const unsigned char *px = S.rgb + 3 * fb;
-    return depth ? ((unsigned int)px[0] | ((unsigned int)px[1] << 8) | ((unsigned int)px[2] << 16)) : 0u;
+    return depth ? get_rgb(S.rgb + 3 * fb) : 0u;
 }
 
 // The warp alone, to the un-closed scratch maps (the in-place entry point: the closing then reads those).
@@ -272,12 +275,10 @@ __global__ __launch_bounds__(kThreads) void radial_gather_pack_kernel(const Fram
                                                                       const WarpSrc S, unsigned short *__restrict__ map_copy,
                                                                       unsigned char *__restrict__ colors_copy, int tiles_per_tick, long long tick_pix_stride)
 {
-    const int tick = blockIdx.x / tiles_per_tick;
-    const int tile = blockIdx.x - tick * tiles_per_tick;
-    const TileDesc td = tiles[tile];
-    const FrameDesc fd = frames[td.frame];
-    const long long fb = tick * tick_pix_stride + fd.depth_off;
-    const int p0 = (tile - fd.tile_start) * kTile;
+    const RadialTile t = batch_tile(frames, tiles, tiles_per_tick, tick_pix_stride);
+    const FrameDesc &fd = t.fd;
+    const long long fb = t.fb;
+    const int p0 = t.p0;
     // the tile's results are staged in LDS and leave as 16-byte stores
     __shared__ alignas(16) unsigned short s_d[kTile + 8];
     __shared__ alignas(16) unsigned char s_c[3 * kTile + 16];
@@ -300,23 +301,59 @@ __global__ __launch_bounds__(kThreads) void radial_gather_pack_kernel(const Fram
             if (!in[k]) continue;
             const int i = i0 + k * kThreads;
             s_d[lead_d / 2 + i] = (unsigned short)d[k];
-            unsigned char *c3 = s_c + lead_c + 3 * i;
-            c3[0] = (unsigned char)c[k];
-            c3[1] = (unsigned char)(c[k] >> 8);
-            c3[2] = (unsigned char)(c[k] >> 16);
+            put_rgb(s_c + lead_c + 3 * i, c[k]);
         }
     }
     if (fd.npix == 1 && threadIdx.x == 0) {
         const unsigned int c1 = one_pixel_colour(S, fb, s_d[lead_d / 2]);
-        unsigned char *c3 = s_c + lead_c;
-        c3[0] = (unsigned char)c1;
-        c3[1] = (unsigned char)(c1 >> 8);
-        c3[2] = (unsigned char)(c1 >> 16);
+        put_rgb(s_c + lead_c, c1);
     }
     __syncthreads();
     const int n_px = min(kTile, fd.npix - p0);
-    store_tile_run<2>(gd, s_d, lead_d, 2 * n_px);
-    store_tile_run<1>(gc, s_c, lead_c, 3 * n_px);
+    store_run<2>(gd, s_d, lead_d, 2 * n_px);
+    store_run<1>(gc, s_c, lead_c, 3 * n_px);
+}
+
+// ---- the closing arithmetic of one hole (:241-256), shared by every closing kernel below ------------------------------------------------
+//
+// the acceptance chain of :241-248, branch-free: lane-mask logic and selects instead of eight nested branches
+__device__ __forceinline__ void accept_chain(const int (&nb)[8], int &n, int &sum, unsigned int &accepted)
+{
+    n = 0;
+    sum = 0;
+    accepted = 0;
+    int prev_val = -1;
+#pragma unroll
+    for (int i = 0; i < 8; i++) {
+        const bool ok = (nb[i] > 0) & ((prev_val == -1) | (abs(nb[i] - prev_val) < 30));  // :241
+        prev_val = ok ? nb[i] : prev_val;
+        n += ok ? 1 : 0;
+        sum += ok ? nb[i] : 0;
+        accepted |= (ok ? 1u : 0u) << i;
+    }
+}
+
+// v / n for n = 5..8 and v < 2^20: a float reciprocal and one correction step divide exactly
+__device__ __forceinline__ unsigned int div_small(int v, int n)
+{
+    const float rn = 1.0f / (float)n;
+    int q = (int)((float)v * rn);
+    const int r = v - q * n;
+    q += r >= n ? 1 : 0;
+    q -= r < 0 ? 1 : 0;
+    return (unsigned int)q;
+}
+
+// the average colour of the accepted neighbours (:244-246, :252-255) as 0x00BBGGRR; nc[i] = neighbour i's packed colour
+__device__ __forceinline__ unsigned int average_colour(const unsigned int (&nc)[8], unsigned int accepted, int n)
+{
+    int sR = 0, sG = 0, sB = 0;
+#pragma unroll
+    for (int i = 0; i < 8; i++) {
+        const unsigned int c = (accepted >> i) & 1u ? nc[i] : 0u;
+        sR += c & 0xFF; sG += (c >> 8) & 0xFF; sB += (c >> 16) & 0xFF;
+    }
+    return div_small(sR, n) | (div_small(sG, n) << 8) | (div_small(sB, n) << 16);
 }
 
 // One workgroup per sensor-frame, one thread per row (bands of blockDim rows when h is larger).  At step t the thread of
@@ -364,7 +401,7 @@ __device__ __forceinline__ void ring_load_chunk(const unsigned short *map, const
         if (row_ok && c0 >= 0 && c0 < w) {
             const long long p = (long long)row * w + c0;
             dv = map[p];
-            cv = col[3 * p] | (col[3 * p + 1] << 8) | (col[3 * p + 2] << 16);
+            cv = get_rgb(col + 3 * p);
         }
         if (j & 1) reg.d[j >> 1] |= dv << 16;
         else reg.d[j >> 1] = dv;
@@ -469,43 +506,17 @@ __global__ __launch_bounds__(768) void radial_close_kernel(const FrameDesc *fram
             if (y < h - 1 && x >= 1 && x < w - 1 && d_mine[x & (kRing - 1)] == 0) {        // :229-234
                 const int xm = (x - 1) & (kRing - 1), x0 = x & (kRing - 1), xp = (x + 1) & (kRing - 1);
                 const int nb[8] = {d_up[xm], d_up[x0], d_up[xp], d_mine[xm], d_mine[xp], d_below[xm], d_below[x0], d_below[xp]};
-                // the acceptance chain of :241-248, branch-free: lane-mask logic and selects instead of eight nested branches
-                int n = 0, sum = 0, prev_val = -1;
-                unsigned int accepted = 0;
-#pragma unroll
-                for (int i = 0; i < 8; i++) {
-                    const bool ok = (nb[i] > 0) & ((prev_val == -1) | (abs(nb[i] - prev_val) < 30));  // :241
-                    prev_val = ok ? nb[i] : prev_val;
-                    n += ok ? 1 : 0;
-                    sum += ok ? nb[i] : 0;
-                    accepted |= (ok ? 1u : 0u) << i;
-                }
+                int n, sum;
+                unsigned int accepted;
+                accept_chain(nb, n, sum, accepted);
                 if (n > 4) {                                                                // :250-256
                     const unsigned int nc[8] = {c_up[xm], c_up[x0], c_up[xp], c_mine[xm], c_mine[xp], c_below[xm], c_below[x0], c_below[xp]};
-                    int sR = 0, sG = 0, sB = 0;
-#pragma unroll
-                    for (int i = 0; i < 8; i++) {
-                        const unsigned int c = (accepted >> i) & 1u ? nc[i] : 0u;
-                        sR += c & 0xFF; sG += (c >> 8) & 0xFF; sB += (c >> 16) & 0xFF;
-                    }
-                    // n is 5..8 and the sums stay below 2^20: a float reciprocal and one correction step divide exactly
-                    const float rn = 1.0f / (float)n;
-                    auto div_n = [&](int v) {
-                        int q = (int)((float)v * rn);
-                        const int r = v - q * n;
-                        q += r >= n ? 1 : 0;
-                        q -= r < 0 ? 1 : 0;
-                        return (unsigned int)q;
-                    };
-                    const unsigned int fd_ = div_n(sum);
-                    const unsigned int fR = div_n(sR), fG = div_n(sG), fB = div_n(sB);
+                    const unsigned int fd_ = div_small(sum, n), rgb = average_colour(nc, accepted, n);
                     d_mine[x0] = (unsigned short)fd_;
-                    c_mine[x0] = fR | (fG << 8) | (fB << 16);
+                    c_mine[x0] = rgb;
                     const long long pos = x + (long long)y * w;
                     map[pos] = (unsigned short)fd_;
-                    col[pos * 3] = (unsigned char)fR;
-                    col[pos * 3 + 1] = (unsigned char)fG;
-                    col[pos * 3 + 2] = (unsigned char)fB;
+                    put_rgb(col + pos * 3, rgb);
                 }
             }
             // Step barrier on LDS traffic only: a plain __syncthreads() would also wait for the chunk prefetches and
@@ -537,46 +548,39 @@ __global__ __launch_bounds__(768) void radial_close_kernel(const FrameDesc *fram
 //      sequential loop reaches, whatever the order inside a round.  A round list that outgrows LDS switches the frame to full sweeps
 //      over all its holes until nothing changes: the same fixed point, no list.
 // The colour of a hole is zero in the un-closed map (map_copy / colors_copy start zeroed, :193-194, and only valid pixels are warped).
-__device__ __forceinline__ void accept_chain(const int (&nb)[8], int &n, int &sum, unsigned int &accepted)
-{
-    n = 0;
-    sum = 0;
-    accepted = 0;
-    int prev_val = -1;
-#pragma unroll
-    for (int i = 0; i < 8; i++) {
-        const bool ok = (nb[i] > 0) & ((prev_val == -1) | (abs(nb[i] - prev_val) < 30));  // :241
-        prev_val = ok ? nb[i] : prev_val;
-        n += ok ? 1 : 0;
-        sum += ok ? nb[i] : 0;
-        accepted |= (ok ? 1u : 0u) << i;
-    }
-}
-
-// v / n for n = 5..8 and v < 2^20: a float reciprocal and one correction step divide exactly
-__device__ __forceinline__ unsigned int div_small(int v, int n)
-{
-    const float rn = 1.0f / (float)n;
-    int q = (int)((float)v * rn);
-    const int r = v - q * n;
-    q += r >= n ? 1 : 0;
-    q -= r < 0 ? 1 : 0;
-    return (unsigned int)q;
-}
-
-// the average colour of the accepted neighbours (:244-246, :252-255) as 0x00BBGGRR; nc[i] = neighbour i's packed colour
-__device__ __forceinline__ unsigned int average_colour(const unsigned int (&nc)[8], unsigned int accepted, int n)
-{
-    int sR = 0, sG = 0, sB = 0;
-#pragma unroll
-    for (int i = 0; i < 8; i++) {
-        const unsigned int c = (accepted >> i) & 1u ? nc[i] : 0u;
-        sR += c & 0xFF; sG += (c >> 8) & 0xFF; sB += (c >> 16) & 0xFF;
-    }
-    return div_small(sR, n) | (div_small(sG, n) << 8) | (div_small(sB, n) << 16);
-}
-
 constexpr int kDx[8] = {-1, 0, 1, -1, 1, -1, 0, 1}, kDy[8] = {-1, -1, -1, 0, 0, 1, 1, 1};   // the neighbour order of :225
+
+// (x, y) of pixel p of a w-wide frame: p / w by a float multiply and an exact +-1 correction
+__device__ __forceinline__ void xy_of(int p, int w, float inv_w, int &x, int &y)
+{
+    y = (int)((float)p * inv_w);
+    x = p - y * w;
+    if (x < 0) { y--; x += w; }
+    if (x >= w) { y++; x -= w; }
+}
+
+// The hole successors of a pixel (x, y) whose value changed -- right, down-left, down, down-right; bit s = neighbour 4 + s -- that have to be
+// looked at again: the ones that are holes and interior pixels (:223-224).
+__device__ __forceinline__ unsigned int successor_mask(bool hole_r, bool hole_dl, bool hole_d, bool hole_dr, int x, int y, int w, int h)
+{
+    const bool below = y + 1 < h - 1;
+    return ((hole_r && x + 1 < w - 1) ? 1u : 0u) | ((hole_dl && x - 1 >= 1 && below) ? 2u : 0u) | ((hole_d && below) ? 4u : 0u) |
+           ((hole_dr && x + 1 < w - 1 && below) ? 8u : 0u);
+}
+
+// put(slot, pixel) for every hole successor of (x, y) that succ names (bit s = neighbour 4 + s), from `slot` on
+template <class Put>
+__device__ __forceinline__ void list_successors(unsigned int succ, int slot, int x, int y, int w, Put put)
+{
+#pragma unroll
+    for (int sidx = 0; sidx < 4; sidx++) {
+        if ((succ >> sidx) & 1u) {
+            const int j = 4 + sidx;   // neighbours 4..7 are the successors
+            put(slot, (unsigned int)((y + kDy[j]) * w + x + kDx[j]));
+            slot++;
+        }
+    }
+}
 
 // Appends the wave's entries to a list: one atomicAdd per wave.  `mine` = this lane's count; returns its first slot.
 __device__ __forceinline__ int wave_reserve(int *counter, int mine)
@@ -600,17 +604,22 @@ struct BandDesc { int frame, y0; };
 // first bit of frame f in a tick's hole bitmap: 64-bit aligned, frames never share a word
 __device__ __forceinline__ long long hole_base_bit(const FrameDesc &fd, int f) { return ((fd.depth_off + 63) & ~63ll) + 64ll * f; }
 
-struct BandArgs {
+struct CloseArgs {                   // what both closing passes work on
     const FrameDesc *frames;
-    const BandDesc *bands;           // the bands of one tick
-    WarpSrc src;
     unsigned short *out_d;           // the closed maps
     unsigned char *out_c;
     unsigned char *holes;            // [n_ticks][holes_tick_bytes] one bit per pixel: a hole of the un-closed map
-    unsigned int *work;              // [n_ticks][2 * pixels per tick]: frame f's list starts at 2 * depth_off, 2 * npix entries
-    int *work_cnt;                   // [n_ticks * n_frames] x kCntStride
-    int bands_per_tick, n_frames, rows;
+    unsigned int *work;              // [n_ticks][2 * pixels per tick]: frame f's list starts at 2 * depth_off, 2 * npix entries (the band kernel
+                                     // fills it, the second pass starts from it)
+    int *work_cnt;                   // [3][n_ticks * n_frames] x kCntStride: band kernel -> first grid-wide round -> second -> per-frame kernel
+    int n_frames;
     long long tick_pix_stride, holes_tick_bytes;
+};
+
+struct BandArgs : CloseArgs {
+    const BandDesc *bands;           // the bands of one tick
+    WarpSrc src;
+    int bands_per_tick, rows;
 };
 
 constexpr int kBandList = 8192;   // most candidates one pass over the band's rows lists (16-bit local pixel indices); taller / wider bands go in chunks of rows
@@ -631,6 +640,8 @@ __host__ __device__ inline int band_lds_bytes(int rows, int w)
 }
 
 // copies n bytes from LDS to global memory; (lds offset from the 16-byte aligned LDS base) = (global address) modulo 16
+// (store_run of fusion_shared.hpp for kBandThreads threads and byte-sized ends, taking the lead from dst: called through store_run the
+// band kernels come out 17 address instructions longer)
 __device__ __forceinline__ void store_band_run(unsigned char *dst, const unsigned char *lds, int n)
 {
     const int lead = (int)(reinterpret_cast<uintptr_t>(dst) & 15);
@@ -700,18 +711,12 @@ __global__ __launch_bounds__(kBandThreads) void radial_band_kernel(const BandArg
                 if (!in[k]) continue;
                 const int i = i0 + k * kBandThreads;
                 s_d[i] = (unsigned short)d[k];
-                unsigned char *c3 = s_c + 3 * i;
-                c3[0] = (unsigned char)c[k];
-                c3[1] = (unsigned char)(c[k] >> 8);
-                c3[2] = (unsigned char)(c[k] >> 16);
+                put_rgb(s_c + 3 * i, c[k]);
             }
         }
         if (fd.npix == 1 && tid == 0) {   // local pixel `lo` is the frame's only pixel, and this thread stored it
             const unsigned int c1 = one_pixel_colour(a.src, fb, s_d[lo]);
-            unsigned char *c3 = s_c + 3 * lo;
-            c3[0] = (unsigned char)c1;
-            c3[1] = (unsigned char)(c1 >> 8);
-            c3[2] = (unsigned char)(c1 >> 16);
+            put_rgb(s_c + 3 * lo, c1);
         }
     } else if (VEC) {
         const unsigned short *sd = a.src.depth + fb + pl0;
@@ -728,9 +733,7 @@ __global__ __launch_bounds__(kBandThreads) void radial_band_kernel(const BandArg
         const unsigned char *sc = a.src.rgb + 3 * (fb + pl0);
         for (int i = lo + tid; i < hi; i += kBandThreads) {
             s_d[i] = sd[i];
-            s_c[3 * i] = sc[3 * i];
-            s_c[3 * i + 1] = sc[3 * i + 1];
-            s_c[3 * i + 2] = sc[3 * i + 2];
+            put_rgb(s_c + 3 * i, get_rgb(sc + 3 * i));
         }
     }
     __syncthreads();
@@ -838,36 +841,22 @@ __global__ __launch_bounds__(kBandThreads) void radial_band_kernel(const BandArg
                 if (n > 4) {                                                                       // :250-256
                     unsigned int nc[8];
 #pragma unroll
-                    for (int j = 0; j < 8; j++) {
+                    for (int j = 0; j < 8; j++) {   // (spelled out: through get_rgb the compiler packs the bytes otherwise -- 32 VALU and 2 VGPRs fewer)
                         const unsigned char *c3 = s_c + 3 * (q + kDy[j] * w + kDx[j]);
                         nc[j] = (accepted >> j) & 1u ? ((unsigned int)c3[0] | ((unsigned int)c3[1] << 8) | ((unsigned int)c3[2] << 16)) : 0u;
                     }
                     const unsigned int rgb = average_colour(nc, accepted, n);
                     const long long pos = fb + pl0 + q;
                     a.out_d[pos] = (unsigned short)div_small(sum, n);
-                    a.out_c[3 * pos] = (unsigned char)rgb;
-                    a.out_c[3 * pos + 1] = (unsigned char)(rgb >> 8);
-                    a.out_c[3 * pos + 2] = (unsigned char)(rgb >> 16);
-                    int yl = (int)((float)q * fd.inv_w);
-                    x = q - yl * w;
-                    if (x < 0) { yl--; x += w; }
-                    if (x >= w) { yl++; x -= w; }
-                    y = y0 - 1 + yl;
-                    // its hole successors now depend on the order: onto the frame's list (interior pixels only, :223-224)
-                    const bool below = y + 1 < h - 1;
-                    succ = ((nb[4] == 0 && x + 1 < w - 1) ? 1u : 0u) | ((nb[5] == 0 && x - 1 >= 1 && below) ? 2u : 0u) |
-                           ((nb[6] == 0 && below) ? 4u : 0u) | ((nb[7] == 0 && x + 1 < w - 1 && below) ? 8u : 0u);
+                    put_rgb(a.out_c + 3 * pos, rgb);
+                    xy_of(q, w, fd.inv_w, x, y);
+                    y += y0 - 1;
+                    succ = successor_mask(nb[4] == 0, nb[5] == 0, nb[6] == 0, nb[7] == 0, x, y, w, h);   // they now depend on the order: onto the frame's list
                 }
             }
-            int slot = wave_reserve(work_cnt, __popc(succ));
-#pragma unroll
-            for (int sidx = 0; sidx < 4; sidx++) {
-                if ((succ >> sidx) & 1u) {
-                    const int j = 4 + sidx;   // neighbours 4..7 are the successors
-                    if (slot < 2 * fd.npix) work[slot] = (unsigned int)((y + kDy[j]) * w + x + kDx[j]);   // (a frame lists < 24/13 npix entries)
-                    slot++;
-                }
-            }
+            list_successors(succ, wave_reserve(work_cnt, __popc(succ)), x, y, w, [&](int slot, unsigned int q) {
+                if (slot < 2 * fd.npix) work[slot] = q;   // (a frame lists < 24/13 npix entries)
+            });
         }
     }
 }
@@ -875,16 +864,9 @@ __global__ __launch_bounds__(kBandThreads) void radial_band_kernel(const BandArg
 constexpr int kFixThreads = 256;   // measured on 512 scene frames: 1024 threads 377 us, 512: 274, 256: 245 -- the rounds are short, idle waves only add barrier time
 constexpr int kFixList = 8192;   // entries per round list (LDS, two lists: 64 KB)
 
-struct FixArgs {
-    const FrameDesc *frames;
-    unsigned short *out_d;
-    unsigned char *out_c;
-    const unsigned char *holes;
-    const unsigned int *work;        // the list the per-frame kernel starts from: 2 * npix entries per frame at 2 * (first pixel of the frame)
-    int *work_cnt;                   // [3][n_ticks * n_frames] x kCntStride: band kernel -> first grid-wide round -> second -> per-frame kernel
-    int n_frames, list_cap;          // list_cap: entries a round list may hold (kFixList; the tests shrink it to force the sweeps)
+struct FixArgs : CloseArgs {
+    int list_cap;                    // entries a round list may hold (kFixList; the tests shrink it to force the sweeps)
     int n_tf, cnt_index;             // cnt_index: which of the three counter arrays the per-frame kernel starts from
-    long long tick_pix_stride, holes_tick_bytes;
 };
 
 // Re-evaluates hole p of a frame (out_d / out_c / holes point at the frame, bit0 = its first bit in `holes`): predecessors as they
@@ -893,10 +875,7 @@ struct FixArgs {
 __device__ __forceinline__ bool fix_pixel(unsigned short *out_d, unsigned char *out_c, const unsigned char *holes, long long bit0, int p, int w, int h,
                                           float inv_w, unsigned int &succ, int &x, int &y)
 {
-    y = (int)((float)p * inv_w);
-    x = p - y * w;
-    if (x < 0) { y--; x += w; }
-    if (x >= w) { y++; x -= w; }
+    xy_of(p, w, inv_w, x, y);
     // three rows of three pixels: depths as dword + word, colours as 8 + 1 bytes (nothing is read outside the nine pixels)
     unsigned int dv[3][3], cv[3][3];
 #pragma unroll
@@ -930,12 +909,8 @@ __device__ __forceinline__ bool fix_pixel(unsigned short *out_d, unsigned char *
     succ = 0;
     if (nd == od && nrgb == orgb) return false;
     out_d[p] = (unsigned short)nd;
-    out_c[3 * (long long)p] = (unsigned char)nrgb;
-    out_c[3 * (long long)p + 1] = (unsigned char)(nrgb >> 8);
-    out_c[3 * (long long)p + 2] = (unsigned char)(nrgb >> 16);
-    const bool below = y + 1 < h - 1;
-    succ = ((h1 && x + 1 < w - 1) ? 1u : 0u) | (((h2 & 1u) && x - 1 >= 1 && below) ? 2u : 0u) | (((h2 & 2u) && below) ? 4u : 0u) |
-           (((h2 & 4u) && x + 1 < w - 1 && below) ? 8u : 0u);
+    put_rgb(out_c + 3 * (long long)p, nrgb);
+    succ = successor_mask(h1, h2 & 1u, h2 & 2u, h2 & 4u, x, y, w, h);
     return true;
 }
 
@@ -973,15 +948,9 @@ __global__ __launch_bounds__(kThreads) void close_fix_round_kernel(const FixArgs
         unsigned int succ = 0;
         int x = 0, y = 0;
         if (i < n_in) fix_pixel(out_d, out_c, holes, bit0, (int)lin[i], w, h, fd.inv_w, succ, x, y);
-        int slot = wave_reserve(cnt_out + kCntStride * tf, __popc(succ));
-#pragma unroll
-        for (int sidx = 0; sidx < 4; sidx++) {
-            if ((succ >> sidx) & 1u) {
-                const int k = 4 + sidx;
-                if (slot < out_cap) lout[slot] = (unsigned int)((y + kDy[k]) * w + x + kDx[k]);
-                slot++;
-            }
-        }
+        list_successors(succ, wave_reserve(cnt_out + kCntStride * tf, __popc(succ)), x, y, w, [&](int slot, unsigned int q) {
+            if (slot < out_cap) lout[slot] = q;
+        });
     }
 }
 
@@ -1024,16 +993,10 @@ __global__ __launch_bounds__(kFixThreads) void close_fix_kernel(const FixArgs a)
             unsigned int succ = 0;
             int x = 0, y = 0;
             if (i < n_items) fix_pixel(out_d, out_c, holes, bit0, (int)(round == 0 ? glist[i] : lists[cur][i]), w, h, fd.inv_w, succ, x, y);
-            int slot = wave_reserve(&s_n[1 - cur], __popc(succ));
-#pragma unroll
-            for (int sidx = 0; sidx < 4; sidx++) {
-                if ((succ >> sidx) & 1u) {
-                    const int k = 4 + sidx;
-                    if (slot < a.list_cap) lists[1 - cur][slot] = (unsigned int)((y + kDy[k]) * w + x + kDx[k]);
-                    else s_flag = 1;
-                    slot++;
-                }
-            }
+            list_successors(succ, wave_reserve(&s_n[1 - cur], __popc(succ)), x, y, w, [&](int slot, unsigned int q) {
+                if (slot < a.list_cap) lists[1 - cur][slot] = q;
+                else s_flag = 1;
+            });
         }
         __threadfence_block();
         __syncthreads();   // this round's writes are in place before the next round reads them
@@ -1053,12 +1016,7 @@ __global__ __launch_bounds__(kFixThreads) void close_fix_kernel(const FixArgs a)
             const long long b = bit0 + p;
             if (!((holes[b >> 3] >> (b & 7)) & 1u)) continue;
             int x, y;
-            {
-                y = (int)((float)p * fd.inv_w);
-                x = p - y * w;
-                if (x < 0) { y--; x += w; }
-                if (x >= w) { y++; x -= w; }
-            }
+            xy_of(p, w, fd.inv_w, x, y);
             if (x < 1 || x >= w - 1) continue;
             unsigned int succ;
             changed |= fix_pixel(out_d, out_c, holes, bit0, p, w, h, fd.inv_w, succ, x, y);
@@ -1070,147 +1028,141 @@ __global__ __launch_bounds__(kFixThreads) void close_fix_kernel(const FixArgs a)
     }
 }
 
-// The bands of one tick for `rows` rows per band; returns their number.
-static int make_bands(const LsnFusion *p, int rows, std::vector<BandDesc> &bands)
+// ---- host side --------------------------------------------------------------------------------------------------------------
+
+using lsn::RadialScratch;
+
+// Both maps in place or both out of place; out of place, no output range may overlap an input range in part.
+int check_buffers(const LsnFusion *p, const void *d_depth_in, const void *d_colors_in, const void *d_depth, const void *d_colors, bool &in_place)
 {
-    bands.clear();
-    for (int f = 0; f < p->n_maps; f++)
-        for (int y0 = 0; y0 < p->h[f]; y0 += rows) bands.push_back(BandDesc{f, y0});
-    return (int)bands.size();
-}
-
-}  // namespace
-
-static int radial_correct_on(LsnFusion *p, const float *intr_params, const void *d_depth_in, const void *d_colors_in, void *d_depth, void *d_colors,
-                             hipStream_t s);
-
-// The plan's radial scratch -- warp tables, band list, hole bitmap, work lists and their counters -- is shared by all calls on the plan: a
-// call on ANOTHER stream than the previous one's first waits for that chain's end (an event recorded behind every chain), so that nothing
-// of it is still counting, listing or reading when this call clears and refills the scratch.  Calls on one stream are ordered by the stream.
-static int radial_correct(LsnFusion *p, const float *intr_params, const void *d_depth_in, const void *d_colors_in, void *d_depth, void *d_colors,
-                          hipStream_t s)
-{
-    LSN_HIP(hipSetDevice(p->device));
-    if (!p->radial_done) LSN_HIP(hipEventCreateWithFlags(&p->radial_done, hipEventDisableTiming));
-    if (p->radial_chain_open && p->work_cnt_stream != s) LSN_HIP(hipStreamWaitEvent(s, p->radial_done, 0));
-    const int rc = radial_correct_on(p, intr_params, d_depth_in, d_colors_in, d_depth, d_colors, s);
-    // (also behind a call that failed half-way: whatever it did enqueue is what the next stream has to wait for)
-    if (hipEventRecord(p->radial_done, s) == hipSuccess) p->radial_chain_open = true;
-    else (void)hipGetLastError();
-    p->work_cnt_stream = s;
-    return rc;
-}
-
-static int radial_correct_on(LsnFusion *p, const float *intr_params, const void *d_depth_in, const void *d_colors_in, void *d_depth, void *d_colors,
-                             hipStream_t s)
-{
-    const bool in_place = d_depth_in == d_depth && d_colors_in == d_colors;
-    if (!in_place && (d_depth_in == d_depth || d_colors_in == d_colors)) {
+    in_place = d_depth_in == d_depth && d_colors_in == d_colors;
+    if (in_place) return 0;
+    if (d_depth_in == d_depth || d_colors_in == d_colors) {
         lsn::set_error("lsnFusionRadialCorrectTo: depth and colours must both be in place or both out of place");
         return -1;
     }
+    // out of place the bands warp straight from the input (no scratch copy): an output range that overlaps an input range in part
+    // would be overwritten by one band while another still reads it as a warp source
     const size_t npix = (size_t)p->cap * p->n_ticks;
-    if (!in_place) {
-        // out of place the bands warp straight from the input (no scratch copy): an output range that overlaps an input range in part
-        // would be overwritten by one band while another still reads it as a warp source
-        auto overlap = [](const void *a, size_t na, const void *b, size_t nb) {
-            const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-            return x < y + nb && y < x + na;
-        };
-        if (overlap(d_depth_in, 2 * npix, d_depth, 2 * npix) || overlap(d_colors_in, 3 * npix, d_colors, 3 * npix) ||
-            overlap(d_depth_in, 2 * npix, d_colors, 3 * npix) || overlap(d_colors_in, 3 * npix, d_depth, 2 * npix)) {
-            lsn::set_error("lsnFusionRadialCorrectTo: the output buffers overlap the input buffers in part (pass the same pointers for an in-place correction)");
-            return -1;
-        }
+    auto overlap = [](const void *a, size_t na, const void *b, size_t nb) {
+        const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+        return x < y + nb && y < x + na;
+    };
+    if (overlap(d_depth_in, 2 * npix, d_depth, 2 * npix) || overlap(d_colors_in, 3 * npix, d_colors, 3 * npix) ||
+        overlap(d_depth_in, 2 * npix, d_colors, 3 * npix) || overlap(d_colors_in, 3 * npix, d_depth, 2 * npix)) {
+        lsn::set_error("lsnFusionRadialCorrectTo: the output buffers overlap the input buffers in part (pass the same pointers for an in-place correction)");
+        return -1;
     }
-    if (p->radial.reserve(sizeof(RadialParams) * p->n_maps)) return -1;
+    return 0;
+}
+
+// The warp candidates of this calibration (one tick's worth of pixels), then their compact form; nothing to do while the intrinsics are
+// the ones the tables were built for.
+int build_warp_table(LsnFusion *p, const float *intr_params, hipStream_t s)
+{
+    RadialScratch &r = p->rd;
+    const bool same_intr = r.tables_valid && r.intr.size() == 7 * (size_t)p->n_maps &&
+                           memcmp(r.intr.data(), intr_params, sizeof(float) * 7 * p->n_maps) == 0;
+    if (same_intr) return 0;
+    if (r.params.reserve(sizeof(RadialParams) * p->n_maps)) return -1;
     std::vector<RadialParams> rp(p->n_maps);
     for (int i = 0; i < p->n_maps; i++) {
         const float *ip = intr_params + 7 * i;  // IntrinsicCameraParameters(float*), include/NativeUtils/depthprocessing.h:96-97
         rp[i] = RadialParams{ip[0], ip[1], ip[2], ip[3], ip[4], ip[5], ip[6], 0.0f};
     }
-    const int grid = p->tiles_per_tick * p->n_ticks;
-    const bool same_intr = p->cand_valid && p->radial_intr.size() == 7 * (size_t)p->n_maps &&
-                           memcmp(p->radial_intr.data(), intr_params, sizeof(float) * 7 * p->n_maps) == 0;
-    if (!same_intr) {
-        LSN_HIP(hipMemcpyAsync(p->radial.p, rp.data(), sizeof(RadialParams) * p->n_maps, hipMemcpyHostToDevice, s));
-        LSN_HIP(hipStreamSynchronize(s));  // rp is a local
-        // the warp candidates of this calibration (one tick's worth of pixels), then their compact form
-        if (p->cand.reserve(16 * (size_t)p->cap) || p->ctab.reserve(4 * (size_t)p->cap + 16)) return -1;
-        unsigned int *count = p->ctab.as<unsigned int>();   // the per-destination counters of the fill pass live where the compact table will
-        LSN_HIP(hipMemsetAsync(count, 0, 4 * (size_t)p->cap, s));
-        LSN_HIP(hipMemsetAsync(p->cand.p, 0, 16 * (size_t)p->cap, s));
-        LSN_HIP(hipMemsetAsync(p->misc.as<char>() + 64, 0, sizeof(int), s));
-        int *overflow = reinterpret_cast<int *>(p->misc.as<char>() + 64);
-        hipLaunchKernelGGL(radial_cand_fill_kernel, dim3(p->tiles_per_tick), dim3(kThreads), 0, s, p->frames.as<FrameDesc>(),
-                           p->tile_frame.as<TileDesc>(), p->radial.as<RadialParams>(), count, p->cand.as<unsigned int>(), overflow);
-        hipLaunchKernelGGL(radial_cand_sort_kernel, dim3((unsigned)((p->cap + kThreads - 1) / kThreads)), dim3(kThreads), 0, s, p->cand.as<uint4>(),
-                           p->cap);
-        hipLaunchKernelGGL(radial_cand_pack_kernel, dim3(p->tiles_per_tick), dim3(kThreads), 0, s, p->frames.as<FrameDesc>(),
-                           p->tile_frame.as<TileDesc>(), (const uint4 *)p->cand.as<uint4>(), p->ctab.as<unsigned int>());
-        int ov = 0;
-        LSN_HIP(hipMemcpyAsync(&ov, overflow, sizeof(int), hipMemcpyDeviceToHost, s));
-        LSN_HIP(hipStreamSynchronize(s));
-        p->cand_overflow = ov != 0;
-        p->radial_intr.assign(intr_params, intr_params + 7 * (size_t)p->n_maps);
-        p->cand_valid = true;
+    LSN_HIP(hipMemcpyAsync(r.params.p, rp.data(), sizeof(RadialParams) * p->n_maps, hipMemcpyHostToDevice, s));
+    LSN_HIP(hipStreamSynchronize(s));  // rp is a local
+    if (r.cand.reserve(16 * (size_t)p->cap) || r.ctab.reserve(4 * (size_t)p->cap + 16)) return -1;
+    unsigned int *count = r.ctab.as<unsigned int>();   // the per-destination counters of the fill pass live where the compact table will
+    int *overflow = reinterpret_cast<int *>(p->misc.as<char>() + 64);
+    LSN_HIP(hipMemsetAsync(count, 0, 4 * (size_t)p->cap, s));
+    LSN_HIP(hipMemsetAsync(r.cand.p, 0, 16 * (size_t)p->cap, s));
+    LSN_HIP(hipMemsetAsync(overflow, 0, sizeof(int), s));
+    const FrameDesc *frames = p->frames.as<FrameDesc>();
+    const TileDesc *tiles = p->tile_frame.as<TileDesc>();
+    hipLaunchKernelGGL(radial_cand_fill_kernel, dim3(p->tiles_per_tick), dim3(kThreads), 0, s, frames, tiles, r.params.as<RadialParams>(), count,
+                       r.cand.as<unsigned int>(), overflow);
+    hipLaunchKernelGGL(radial_cand_sort_kernel, dim3((unsigned)((p->cap + kThreads - 1) / kThreads)), dim3(kThreads), 0, s, r.cand.as<uint4>(), p->cap);
+    hipLaunchKernelGGL(radial_cand_pack_kernel, dim3(p->tiles_per_tick), dim3(kThreads), 0, s, frames, tiles, (const uint4 *)r.cand.as<uint4>(),
+                       r.ctab.as<unsigned int>());
+    int ov = 0;
+    LSN_HIP(hipMemcpyAsync(&ov, overflow, sizeof(int), hipMemcpyDeviceToHost, s));
+    LSN_HIP(hipStreamSynchronize(s));
+    r.overflow = ov != 0;
+    r.intr.assign(intr_params, intr_params + 7 * (size_t)p->n_maps);
+    r.tables_valid = true;
+    return 0;
+}
+
+struct RadialSwitches {
+    bool force_atomic;   // LSN_RADIAL_FORCE_ATOMIC=1 (tests): take the atomicMax path even when the table did not overflow
+    bool wavefront;      // LSN_RADIAL_CLOSE=wavefront: the ablation
+    bool tiny_lists;     // LSN_RADIAL_TINY_LISTS=1 (tests): force the sweeps of the second pass
+    int band_rows;       // LSN_RADIAL_BAND_ROWS (tuning): rows per band, 0 = not set
+};
+RadialSwitches read_switches()   // (on every call: the tests switch them inside one process)
+{
+    auto on = [](const char *name) { const char *v = getenv(name); return v && atoi(v) != 0; };
+    const char *close_env = getenv("LSN_RADIAL_CLOSE"), *rows_env = getenv("LSN_RADIAL_BAND_ROWS");
+    return RadialSwitches{on("LSN_RADIAL_FORCE_ATOMIC"), close_env && !strcmp(close_env, "wavefront"), on("LSN_RADIAL_TINY_LISTS"),
+                          rows_env ? atoi(rows_env) : 0};
+}
+
+// The un-closed maps of the batch into the scratch maps, which src names on return: from the tables, or by atomicMax + gather.
+int warp_to_scratch(LsnFusion *p, bool atomic_warp, WarpSrc &src, hipStream_t s)
+{
+    RadialScratch &r = p->rd;
+    const size_t npix = (size_t)p->cap * p->n_ticks;
+    const dim3 grid(p->tiles_per_tick * p->n_ticks);
+    const FrameDesc *frames = p->frames.as<FrameDesc>();
+    const TileDesc *tiles = p->tile_frame.as<TileDesc>();
+    if (r.map_copy.reserve(2 * npix + 16) || r.colors_copy.reserve(3 * npix + 16)) return -1;
+    unsigned short *map_copy = r.map_copy.as<unsigned short>();
+    unsigned char *colors_copy = r.colors_copy.as<unsigned char>();
+    if (!atomic_warp) {
+        hipLaunchKernelGGL(radial_gather_pack_kernel, grid, dim3(kThreads), 0, s, frames, tiles, src, map_copy, colors_copy, p->tiles_per_tick, p->cap);
+    } else {
+        if (r.winner.reserve(4 * npix)) return -1;
+        LSN_HIP(hipMemsetAsync(r.winner.p, 0, 4 * npix, s));
+        hipLaunchKernelGGL(radial_warp_kernel, grid, dim3(kThreads), 0, s, frames, tiles, r.params.as<RadialParams>(), src.depth,
+                           r.winner.as<unsigned int>(), p->tiles_per_tick, p->cap);
+        hipLaunchKernelGGL(radial_gather_kernel, grid, dim3(kThreads), 0, s, frames, tiles, src.depth, src.rgb,
+                           (const unsigned int *)r.winner.as<unsigned int>(), map_copy, colors_copy, p->tiles_per_tick, p->cap);
     }
-    // (read on every call: the tests switch them inside one process)
-    const char *force = getenv("LSN_RADIAL_FORCE_ATOMIC");  // tests: take the atomicMax path even when the table did not overflow
-    const char *close_env = getenv("LSN_RADIAL_CLOSE"), *tiny_env = getenv("LSN_RADIAL_TINY_LISTS");
-    const bool atomic_warp = p->cand_overflow || (force && atoi(force) != 0);
-    const bool wavefront = close_env && !strcmp(close_env, "wavefront");
-    const bool tiny_lists = tiny_env && atoi(tiny_env) != 0;   // tests: force the sweeps of the second pass
-    const bool vec_ptrs = ((uintptr_t)d_depth & 15) == 0 && ((uintptr_t)d_colors & 7) == 0 && ((uintptr_t)d_depth_in & 15) == 0 &&
-                          ((uintptr_t)d_colors_in & 7) == 0 && (p->cap % 8) == 0;
-    const bool vec = p->vec_ok && vec_ptrs;
-    WarpSrc src;
-    src.depth = static_cast<const unsigned short *>(d_depth_in);
-    src.rgb = static_cast<const unsigned char *>(d_colors_in);
-    src.ctab = p->ctab.as<unsigned int>();
-    src.cand = p->cand.as<uint4>();
-    src.last_px = (long long)npix - 1;
-    // The un-closed maps go through memory when the closing cannot warp by itself: in place (a band would overwrite another band's
-    // sources), after the atomicMax warp, and for the wavefront kernel.
-    const bool scratch = in_place || atomic_warp || wavefront;
-    if (scratch) {
-        if (p->map_copy.reserve(2 * npix + 16) || p->colors_copy.reserve(3 * npix + 16)) return -1;
-        if (!atomic_warp) {
-            hipLaunchKernelGGL(radial_gather_pack_kernel, dim3(grid), dim3(kThreads), 0, s, p->frames.as<FrameDesc>(), p->tile_frame.as<TileDesc>(), src,
-                               p->map_copy.as<unsigned short>(), p->colors_copy.as<unsigned char>(), p->tiles_per_tick, p->cap);
-        } else {
-            if (p->winner.reserve(4 * npix)) return -1;
-            LSN_HIP(hipMemsetAsync(p->winner.p, 0, 4 * npix, s));
-            hipLaunchKernelGGL(radial_warp_kernel, dim3(grid), dim3(kThreads), 0, s, p->frames.as<FrameDesc>(), p->tile_frame.as<TileDesc>(),
-                               p->radial.as<RadialParams>(), src.depth, p->winner.as<unsigned int>(), p->tiles_per_tick, p->cap);
-            hipLaunchKernelGGL(radial_gather_kernel, dim3(grid), dim3(kThreads), 0, s, p->frames.as<FrameDesc>(), p->tile_frame.as<TileDesc>(),
-                               src.depth, src.rgb, (const unsigned int *)p->winner.as<unsigned int>(), p->map_copy.as<unsigned short>(),
-                               p->colors_copy.as<unsigned char>(), p->tiles_per_tick, p->cap);
-        }
-        src.depth = p->map_copy.as<unsigned short>();
-        src.rgb = p->colors_copy.as<unsigned char>();
-    }
+    src.depth = map_copy;
+    src.rgb = colors_copy;
+    return 0;
+}
+
+// The ablation: radial_close_kernel closes the scratch maps in place, then they replace the outputs (:259-260).
+int close_wavefront(LsnFusion *p, void *d_depth, void *d_colors, hipStream_t s)
+{
+    const size_t npix = (size_t)p->cap * p->n_ticks;
     const int n_tf = p->n_maps * p->n_ticks;
-    if (wavefront) {
-        int max_h = 1;
-        for (int v : p->h) max_h = v > max_h ? v : max_h;
-        int rows = max_h - 2 < 64 ? 64 : ((max_h - 2 + 63) / 64) * 64;
-        if (rows > 768) rows = 768;  // (rows + 2) x 32 columns x 6 B of LDS rings must fit in 160 KB
-        // One band per frame is the shortest chain of steps, but (rows + 2) x 192 B of LDS per workgroup then allows a single
-        // frame per CU.  With more frames than CUs, 256-row bands (49.5 KB: three frames per CU) win.
-        if ((long long)n_tf > 256 && rows > 256) rows = 256;
-        const size_t ring_bytes = (sizeof(unsigned int) + sizeof(unsigned short)) * kRing * (rows + 2);
-        hipLaunchKernelGGL(radial_close_kernel, dim3((unsigned)n_tf), dim3(rows), ring_bytes, s, p->frames.as<FrameDesc>(), p->n_maps,
-                           p->map_copy.as<unsigned short>(), p->colors_copy.as<unsigned char>(), p->cap);
-        LSN_HIP(hipGetLastError());
-        // :259-260 the corrected maps replace the inputs
-        LSN_HIP(hipMemcpyAsync(d_depth, p->map_copy.p, 2 * npix, hipMemcpyDeviceToDevice, s));
-        LSN_HIP(hipMemcpyAsync(d_colors, p->colors_copy.p, 3 * npix, hipMemcpyDeviceToDevice, s));
-        return 0;
-    }
-    // bands: as many rows as fit the LDS budget of two workgroups per CU for the widest frame
-    int max_w = 1, max_h = 1;
-    for (int i = 0; i < p->n_maps; i++) { max_w = std::max(max_w, p->w[i]); max_h = std::max(max_h, p->h[i]); }
+    int max_h = 1;
+    for (int v : p->h) max_h = v > max_h ? v : max_h;
+    int rows = max_h - 2 < 64 ? 64 : ((max_h - 2 + 63) / 64) * 64;
+    if (rows > 768) rows = 768;  // (rows + 2) x 32 columns x 6 B of LDS rings must fit in 160 KB
+    // One band per frame is the shortest chain of steps, but (rows + 2) x 192 B of LDS per workgroup then allows a single
+    // frame per CU.  With more frames than CUs, 256-row bands (49.5 KB: three frames per CU) win.
+    if ((long long)n_tf > 256 && rows > 256) rows = 256;
+    const size_t ring_bytes = (sizeof(unsigned int) + sizeof(unsigned short)) * kRing * (rows + 2);
+    hipLaunchKernelGGL(radial_close_kernel, dim3((unsigned)n_tf), dim3(rows), ring_bytes, s, p->frames.as<FrameDesc>(), p->n_maps,
+                       p->rd.map_copy.as<unsigned short>(), p->rd.colors_copy.as<unsigned char>(), p->cap);
+    LSN_HIP(hipGetLastError());
+    LSN_HIP(hipMemcpyAsync(d_depth, p->rd.map_copy.p, 2 * npix, hipMemcpyDeviceToDevice, s));
+    LSN_HIP(hipMemcpyAsync(d_colors, p->rd.colors_copy.p, 3 * npix, hipMemcpyDeviceToDevice, s));
+    return 0;
+}
+
+// The four forms of the band kernel: [GATHER][VEC].
+using BandKernel = void (*)(const BandArgs);
+constexpr BandKernel kBandKernels[2][2] = {{radial_band_kernel<false, false>, radial_band_kernel<false, true>},
+                                           {radial_band_kernel<true, false>, radial_band_kernel<true, true>}};
+
+// Rows per band: as many as fit the LDS budget of two workgroups per CU for the widest frame (or what the switch asks for); 0: no band fits.
+int band_rows_for(int max_w, int max_h, int asked)
+{
     // 256 threads on 6 rows of a 512-wide frame: 27 KB, six workgroups of four waves per CU.  Round 6 (512 scene frames, radial_band_kernel
     // alone, profiles/r06_ab_band.txt): 512 threads x 12 rows (rounds 3-5: three workgroups of eight waves) 462-467 us, 256 x 6 417-419,
     // 256 x 4 426, 256 x 7 432, 256 x 5 470, 256 x 8 489, 256 x 12 551, 128 x 4 496, 1024 x 12 718 -- the same 24 waves per CU, but six
@@ -1220,100 +1172,129 @@ static int radial_correct_on(LsnFusion *p, const float *intr_params, const void 
     // correction: 5 rows (the 52 KB budget of rounds 3-5) 1.31 ms, 2 / 3 / 4 rows 1.22-1.25, 6 rows 1.26, 8 rows 1.46.
     int rows = 6;
     while (rows > 2 && band_lds_bytes(rows, max_w) > 32 * 1024) rows--;
-    if (const char *env = getenv("LSN_RADIAL_BAND_ROWS")) {  // tuning
-        const int v = atoi(env);
-        if (v >= 1 && band_lds_bytes(v, max_w) <= 160 * 1024) rows = v;
-    }
+    if (asked >= 1 && band_lds_bytes(asked, max_w) <= 160 * 1024) rows = asked;
     if (rows > max_h) rows = max_h;
-    if (band_lds_bytes(rows, max_w) > 160 * 1024 || (long long)(rows + 2) * max_w > 65535) {
+    return band_lds_bytes(rows, max_w) > 160 * 1024 || (long long)(rows + 2) * max_w > 65535 ? 0 : rows;
+}
+
+// The default closing: the band kernel (gather: it warps by itself from src; else src names the un-closed scratch maps), the grid-wide
+// rounds for a small batch, the per-frame kernel.
+int close_two_pass(LsnFusion *p, const WarpSrc &src, bool gather, bool vec, const RadialSwitches &sw, void *d_depth, void *d_colors, hipStream_t s)
+{
+    RadialScratch &r = p->rd;
+    const size_t npix = (size_t)p->cap * p->n_ticks;
+    const int n_tf = p->n_maps * p->n_ticks;
+    int max_w = 1, max_h = 1;
+    for (int i = 0; i < p->n_maps; i++) { max_w = std::max(max_w, p->w[i]); max_h = std::max(max_h, p->h[i]); }
+    const int rows = band_rows_for(max_w, max_h, sw.band_rows);
+    if (!rows) {
         lsn::set_error("lsnFusionRadialCorrect: a frame of width %d does not fit the closing kernel's LDS band", max_w);
         return -1;
     }
-    if (p->band_rows != rows) {
+    if (r.band_rows != rows) {   // the bands of one tick
         std::vector<BandDesc> bands;
-        p->bands_per_tick = make_bands(p, rows, bands);
-        if (p->bands.reserve(sizeof(BandDesc) * bands.size())) return -1;
-        LSN_HIP(hipMemcpyAsync(p->bands.p, bands.data(), sizeof(BandDesc) * bands.size(), hipMemcpyHostToDevice, s));
+        for (int f = 0; f < p->n_maps; f++)
+            for (int y0 = 0; y0 < p->h[f]; y0 += rows) bands.push_back(BandDesc{f, y0});
+        r.bands_per_tick = (int)bands.size();
+        if (r.bands.reserve(sizeof(BandDesc) * bands.size())) return -1;
+        LSN_HIP(hipMemcpyAsync(r.bands.p, bands.data(), sizeof(BandDesc) * bands.size(), hipMemcpyHostToDevice, s));
         LSN_HIP(hipStreamSynchronize(s));  // bands is a local
-        p->band_rows = rows;
+        r.band_rows = rows;
     }
     const long long holes_tick_bytes = (((p->cap + 64ll * (p->n_maps + 1)) / 8) + 31) & ~15ll;
     const size_t cnt_bytes = 3 * sizeof(int) * kCntStride * (size_t)n_tf;
-    if (p->holes.reserve((size_t)holes_tick_bytes * p->n_ticks + 64) || p->work.reserve(8 * npix + 64) || p->work2.reserve(4 * npix + 64)) return -1;
+    if (r.holes.reserve((size_t)holes_tick_bytes * p->n_ticks + 64) || r.work.reserve(8 * npix + 64) || r.work2.reserve(4 * npix + 64)) return -1;
     // The second pass leaves every counter cleared -- when it has run to its end.  A call that failed between the band kernel and the
     // per-frame kernel (a launch error), or one that took another closing route after the band kernel, leaves counts behind: the
     // counters are cleared here unless the previous chain is known to have been enqueued completely.
-    if (p->work_cnt.bytes < cnt_bytes) {
-        if (p->work_cnt.reserve(cnt_bytes)) return -1;
-        p->work_cnt_clean = false;
+    if (r.work_cnt.bytes < cnt_bytes) {
+        if (r.work_cnt.reserve(cnt_bytes)) return -1;
+        r.work_cnt_clean = false;
     }
-    // (a call on another stream than the previous one's has waited for that chain's end: radial_correct)
-    if (!p->work_cnt_clean) LSN_HIP(hipMemsetAsync(p->work_cnt.p, 0, p->work_cnt.bytes, s));
-    p->work_cnt_clean = false;
-    if (!vec) LSN_HIP(hipMemsetAsync(p->holes.p, 0, (size_t)holes_tick_bytes * p->n_ticks, s));   // the pixel-by-pixel pass only sets bits
-    BandArgs ba;
-    ba.frames = p->frames.as<FrameDesc>();
-    ba.bands = p->bands.as<BandDesc>();
-    ba.src = src;
-    ba.out_d = static_cast<unsigned short *>(d_depth);
-    ba.out_c = static_cast<unsigned char *>(d_colors);
-    ba.holes = p->holes.as<unsigned char>();
-    ba.work = p->work.as<unsigned int>();
-    ba.work_cnt = p->work_cnt.as<int>();
-    ba.bands_per_tick = p->bands_per_tick;
-    ba.n_frames = p->n_maps;
-    ba.rows = rows;
-    ba.tick_pix_stride = p->cap;
-    ba.holes_tick_bytes = holes_tick_bytes;
-    const size_t lds = (size_t)band_lds_bytes(rows, max_w);
-    const dim3 bgrid((unsigned)((long long)p->bands_per_tick * p->n_ticks));
-    if (!p->band_attr_set) {
+    // (a call on another stream than the previous one's has waited for that chain's end: radial_export)
+    if (!r.work_cnt_clean) LSN_HIP(hipMemsetAsync(r.work_cnt.p, 0, r.work_cnt.bytes, s));
+    r.work_cnt_clean = false;
+    if (!vec) LSN_HIP(hipMemsetAsync(r.holes.p, 0, (size_t)holes_tick_bytes * p->n_ticks, s));   // the pixel-by-pixel pass only sets bits
+    const CloseArgs ca{p->frames.as<FrameDesc>(), static_cast<unsigned short *>(d_depth), static_cast<unsigned char *>(d_colors),
+                       r.holes.as<unsigned char>(), r.work.as<unsigned int>(), r.work_cnt.as<int>(), p->n_maps, p->cap, holes_tick_bytes};
+    const BandArgs ba{ca, r.bands.as<BandDesc>(), src, r.bands_per_tick, rows};
+    if (!r.band_attr_set) {
         // more than 64 KB of dynamic LDS has to be asked for, once per kernel
-        LSN_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&radial_band_kernel<true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        LSN_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&radial_band_kernel<true, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        LSN_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&radial_band_kernel<false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        LSN_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&radial_band_kernel<false, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        p->band_attr_set = true;
+        for (const auto &pair : kBandKernels)
+            for (const BandKernel k : pair) LSN_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        r.band_attr_set = true;
     }
-    if (!scratch) {
-        if (vec) hipLaunchKernelGGL((radial_band_kernel<true, true>), bgrid, dim3(kBandThreads), lds, s, ba);
-        else     hipLaunchKernelGGL((radial_band_kernel<true, false>), bgrid, dim3(kBandThreads), lds, s, ba);
-    } else {
-        if (vec) hipLaunchKernelGGL((radial_band_kernel<false, true>), bgrid, dim3(kBandThreads), lds, s, ba);
-        else     hipLaunchKernelGGL((radial_band_kernel<false, false>), bgrid, dim3(kBandThreads), lds, s, ba);
-    }
+    hipLaunchKernelGGL(kBandKernels[gather][vec], dim3((unsigned)((long long)r.bands_per_tick * p->n_ticks)), dim3(kBandThreads),
+                       (size_t)band_lds_bytes(rows, max_w), s, ba);
     // (tick.hip: the other half of a tick batch starts its own band kernel here, beside this half's closing rounds)
-    if (p->after_band) LSN_HIP(hipEventRecord(p->after_band, s));
-    FixArgs fa;
-    fa.frames = ba.frames;
-    fa.out_d = ba.out_d;
-    fa.out_c = ba.out_c;
-    fa.holes = ba.holes;
-    fa.work = ba.work;
-    fa.work_cnt = ba.work_cnt;
-    fa.n_frames = p->n_maps;
-    fa.list_cap = tiny_lists ? 8 : kFixList;
-    fa.n_tf = n_tf;
-    fa.tick_pix_stride = p->cap;
-    fa.holes_tick_bytes = holes_tick_bytes;
+    if (r.after_band) LSN_HIP(hipEventRecord(r.after_band, s));
+    FixArgs fa{ca, sw.tiny_lists ? 8 : kFixList, n_tf, 0};
     // A few frames (a live tick): the first two rounds -- thousands of pixels per frame -- over all frames at once, the tail one workgroup
     // per frame (8 frames: 130 -> 102 us).  A large batch is bound by the scattered lines those rounds touch, not by their latency, and
     // the two extra launches only cost (512 frames: 242 -> 305 us): there the per-frame kernel does it all.
-    fa.cnt_index = 0;
     if (n_tf <= 128) {
         fa.cnt_index = 2;
-        int *c0 = ba.work_cnt, *c1 = c0 + (size_t)kCntStride * n_tf, *c2 = c1 + (size_t)kCntStride * n_tf;
+        int *c0 = ca.work_cnt, *c1 = c0 + (size_t)kCntStride * n_tf, *c2 = c1 + (size_t)kCntStride * n_tf;
         const int bpf = 12;
         const dim3 rgrid((unsigned)((long long)n_tf * bpf));
-        hipLaunchKernelGGL(close_fix_round_kernel, rgrid, dim3(kThreads), 0, s, fa, (const unsigned int *)p->work.as<unsigned int>(), (const int *)c0, 2, 2, 1,
-                           p->work2.as<unsigned int>(), c1, 1, 1, tiny_lists ? (1 << 30) : 1, bpf);
-        hipLaunchKernelGGL(close_fix_round_kernel, rgrid, dim3(kThreads), 0, s, fa, (const unsigned int *)p->work2.as<unsigned int>(), (const int *)c1, 1, 1,
-                           tiny_lists ? (1 << 30) : 1, p->work.as<unsigned int>(), c2, 2, 2, 1, bpf);
+        const int cap2 = sw.tiny_lists ? (1 << 30) : 1;   // work2 holds npix entries per frame: 1 / cap2 of them may be listed
+        hipLaunchKernelGGL(close_fix_round_kernel, rgrid, dim3(kThreads), 0, s, fa, (const unsigned int *)ca.work, (const int *)c0, 2, 2, 1,
+                           r.work2.as<unsigned int>(), c1, 1, 1, cap2, bpf);
+        hipLaunchKernelGGL(close_fix_round_kernel, rgrid, dim3(kThreads), 0, s, fa, (const unsigned int *)r.work2.as<unsigned int>(), (const int *)c1, 1, 1,
+                           cap2, ca.work, c2, 2, 2, 1, bpf);
     }
     hipLaunchKernelGGL(close_fix_kernel, dim3((unsigned)n_tf), dim3(kFixThreads), 0, s, fa);
     LSN_HIP(hipGetLastError());
-    p->work_cnt_clean = true;
+    r.work_cnt_clean = true;
     return 0;
+}
+
+}  // namespace
+
+// One correction of the batch on stream s: the route is chosen here.  The un-closed maps go through memory when the closing cannot warp by
+// itself: in place (a band would overwrite another band's sources), after the atomicMax warp, and for the wavefront kernel.
+static int radial_correct(LsnFusion *p, const float *intr_params, const void *d_depth_in, const void *d_colors_in, void *d_depth, void *d_colors,
+                          hipStream_t s)
+{
+    bool in_place;
+    if (check_buffers(p, d_depth_in, d_colors_in, d_depth, d_colors, in_place) || build_warp_table(p, intr_params, s)) return -1;
+    const RadialSwitches sw = read_switches();
+    const bool atomic_warp = p->rd.overflow || sw.force_atomic;
+    const bool vec_ptrs = ((uintptr_t)d_depth & 15) == 0 && ((uintptr_t)d_colors & 7) == 0 && ((uintptr_t)d_depth_in & 15) == 0 &&
+                          ((uintptr_t)d_colors_in & 7) == 0 && (p->cap % 8) == 0;
+    const bool vec = p->vec_ok && vec_ptrs;
+    WarpSrc src;
+    src.depth = static_cast<const unsigned short *>(d_depth_in);
+    src.rgb = static_cast<const unsigned char *>(d_colors_in);
+    src.ctab = p->rd.ctab.as<unsigned int>();
+    src.cand = p->rd.cand.as<uint4>();
+    src.last_px = (long long)p->cap * p->n_ticks - 1;
+    const bool scratch = in_place || atomic_warp || sw.wavefront;
+    if (scratch && warp_to_scratch(p, atomic_warp, src, s)) return -1;
+    if (sw.wavefront) return close_wavefront(p, d_depth, d_colors, s);
+    return close_two_pass(p, src, !scratch, vec, sw, d_depth, d_colors, s);
+}
+
+// The two exports' body.  The plan's radial scratch is shared by all calls on the plan: a call on ANOTHER stream than the previous one's
+// first waits for that chain's end, so that nothing of it is still counting, listing or reading when this call clears and refills the scratch.
+static int radial_export(const char *who, LsnFusion *p, const float *intr_params, const void *d_depth_in, const void *d_colors_in, void *d_depth,
+                         void *d_colors, void *stream)
+{
+    return lsn::guarded(who, -1, [&]() {
+        lsn::clear_error();
+        if (!p || !intr_params || !d_depth_in || !d_colors_in || !d_depth || !d_colors) {
+            lsn::set_error("%s: null argument", who);
+            return -1;
+        }
+        std::lock_guard<std::mutex> g(p->mu);
+        hipStream_t s = lsn::as_stream(stream);
+        LSN_HIP(hipSetDevice(p->device));
+        if (!p->rd.done) LSN_HIP(hipEventCreateWithFlags(&p->rd.done, hipEventDisableTiming));
+        if (p->rd.wait_for_chain(s)) return -1;
+        const int rc = radial_correct(p, intr_params, d_depth_in, d_colors_in, d_depth, d_colors, s);
+        p->rd.chain_ends_on(s);
+        return rc;
+    });
 }
 
 // Test hook: how many of the closing chain's work counters are not zero once `stream` has drained.  The chain leaves them all cleared when
@@ -1326,9 +1307,9 @@ extern "C" int lsnFusionRadialCountersLeft(LsnFusion *p, void *stream)
         std::lock_guard<std::mutex> g(p->mu);
         LSN_HIP(hipSetDevice(p->device));
         LSN_HIP(hipStreamSynchronize(lsn::as_stream(stream)));
-        if (!p->work_cnt.p || p->work_cnt.bytes == 0) return 0;
-        std::vector<int> host(p->work_cnt.bytes / sizeof(int));
-        LSN_HIP(hipMemcpy(host.data(), p->work_cnt.p, host.size() * sizeof(int), hipMemcpyDeviceToHost));
+        if (!p->rd.work_cnt.p || p->rd.work_cnt.bytes == 0) return 0;
+        std::vector<int> host(p->rd.work_cnt.bytes / sizeof(int));
+        LSN_HIP(hipMemcpy(host.data(), p->rd.work_cnt.p, host.size() * sizeof(int), hipMemcpyDeviceToHost));
         int left = 0;
         for (int v : host) left += v != 0;
         return left;
@@ -1337,29 +1318,13 @@ extern "C" int lsnFusionRadialCountersLeft(LsnFusion *p, void *stream)
 
 extern "C" int lsnFusionRadialCorrect(LsnFusion *p, const float *intr_params, void *d_depth, void *d_colors, void *stream)
 {
-    return lsn::guarded("lsnFusionRadialCorrect", -1, [&]() {
-        lsn::clear_error();
-        if (!p || !intr_params || !d_depth || !d_colors) {
-            lsn::set_error("lsnFusionRadialCorrect: null argument");
-            return -1;
-        }
-        std::lock_guard<std::mutex> g(p->mu);
-        return radial_correct(p, intr_params, d_depth, d_colors, d_depth, d_colors, lsn::as_stream(stream));
-    });
+    return radial_export("lsnFusionRadialCorrect", p, intr_params, d_depth, d_colors, d_depth, d_colors, stream);
 }
 
 extern "C" int lsnFusionRadialCorrectTo(LsnFusion *p, const float *intr_params, const void *d_depth_in, const void *d_colors_in, void *d_depth_out,
                                         void *d_colors_out, void *stream)
 {
-    return lsn::guarded("lsnFusionRadialCorrectTo", -1, [&]() {
-        lsn::clear_error();
-        if (!p || !intr_params || !d_depth_in || !d_colors_in || !d_depth_out || !d_colors_out) {
-            lsn::set_error("lsnFusionRadialCorrectTo: null argument");
-            return -1;
-        }
-        std::lock_guard<std::mutex> g(p->mu);
-        return radial_correct(p, intr_params, d_depth_in, d_colors_in, d_depth_out, d_colors_out, lsn::as_stream(stream));
-    });
+    return radial_export("lsnFusionRadialCorrectTo", p, intr_params, d_depth_in, d_colors_in, d_depth_out, d_colors_out, stream);
 }
 
 // The flying-pixel filter, the per-sensor depth stage in front of this one, is compiled as part of this translation unit.

@@ -157,8 +157,7 @@ extern "C" int lsnTickRun(LsnTick *t, const void *d_depth_in, const void *d_colo
                 unsigned char *dfl = t->d_filtered.as<unsigned char>() + 2 * px * t0;
                 // the scratch is shared by all runs of the tick object: a run on another stream than the previous one's waits until that
                 // run's correction has read it (the event radial.hip records behind every chain)
-                LsnFusion *pl = t->plan[k];
-                if (pl->radial_chain_open && pl->work_cnt_stream != st) LSN_HIP(hipStreamWaitEvent(st, pl->radial_done, 0));
+                if (t->plan[k]->rd.wait_for_chain(st)) return -1;
                 if (lsn::flying_pixels(t->plan[k], t->fp_neighbourhood, t->fp_threshold, din, dfl, st)) return -1;
                 din = dfl;
             }
@@ -173,9 +172,9 @@ extern "C" int lsnTickRun(LsnTick *t, const void *d_depth_in, const void *d_colo
         // continues behind both halves.
         LSN_HIP(hipEventRecord(t->ev_fork, s));
         LSN_HIP(hipStreamWaitEvent(t->side, t->ev_fork, 0));
-        t->plan[0]->after_band = t->ev_band;
+        t->plan[0]->rd.after_band = t->ev_band;
         const int rc_a = part(0, s);
-        t->plan[0]->after_band = nullptr;
+        t->plan[0]->rd.after_band = nullptr;
         char err_a[lsn::kErrorLen];
         snprintf(err_a, sizeof(err_a), "%s", lsn::error_buffer());   // (every export clears the channel on entry: the second half's calls would wipe the first half's text)
         if (hipStreamWaitEvent(t->side, t->ev_band, 0) != hipSuccess) (void)hipGetLastError();   // (a closing route without a band kernel records nothing new: no wait, the halves start together)

@@ -144,7 +144,7 @@ OFFSETS = rc.ALIGN_OFFSETS
 @pytest.mark.parametrize("name", ["align_vec", "align_ragged"])
 def test_every_pointer_offset_in_place_and_out_of_place(gpu, orc, name):
     """A vec-capable rig handed over at pointers that are not 16-byte (depth) / 8-byte (colour) aligned takes the narrow kernels, and
-    the lead handling of store_band_run / store_tile_run then writes the first bytes of every row run one by one: 54 of the 56 offset
+    the lead handling of store_band_run / store_run then writes the first bytes of every row run one by one: 54 of the 56 offset
     pairs.  Every depth offset with every colour offset in place; out of place the input at one pair of offsets and the output at
     another, independently.  Held: the result and the bytes around it.  Not held, because no output shows it: WHICH kernels ran (with
     vec_ptrs disabled gfx950 completes the wide kernels' misaligned accesses with the same bytes; EXPERIMENTS.md)."""
