@@ -157,6 +157,13 @@ void deleteMesh(Mesh *mesh);
  * Returns 1.0f like the reference. */
 float ICP(Point3f *verts1, Point3f *verts2, int nVerts1, int nVerts2, float *R, float *t, int maxIter);
 
+/* ICP's flow on host arrays with the point-to-plane residual (an extension the reference has no counterpart of; the step is
+ * lsnIcpRunPlane's, part 2): normals1 = the target's normals, nVerts1 x 3 floats at the target's own index, read only and used as given.
+ * The same context, lock, stream and $LSN_NN as ICP; the result equals lsnIcpRunPlane's on the same data bit for bit.  Returns 0 -- also
+ * for maxIter <= 0, which does nothing --, or -1 with lsnGetLastError set: a null argument, an empty cloud, no device, a failed copy.  On -1
+ * verts2, R and t are untouched. */
+int lsnIcpPointToPlane(Point3f *verts1, Point3f *normals1, Point3f *verts2, int nVerts1, int nVerts2, float *R, float *t, int maxIter);
+
 /* ---------------------------------------------------------------------------------------------------------
  * Part 2 -- device-resident API (extension; every pointer named d_* is HIP device memory)
  * ------------------------------------------------------------------------------------------------------- */
@@ -544,6 +551,19 @@ void lsnIcpDestroy(LsnIcp *icp);
 int lsnIcpRun(LsnIcp *icp, const float *d_verts1, int n1, float *d_verts2, int n2, float *d_R, float *d_t,
               int maxIter, int nn_mode, void *stream);
 
+/* lsnIcpRun with the point-to-plane residual: DEFINED by this project, not copied -- the reference has point-to-point ICP only; the
+ * definition is tests/icp_plane_ref.py.  d_normals1: n1*3 floats, the target's normals at the target's own index, used
+ * as given (never renormalised).  Per iteration the exact NN, the one-to-one matching, the statistics and the 2.5 sigma rejection are
+ * lsnIcpRun's, bit for bit; a kept match takes part when its target normal is finite and (nx nx + ny ny) + nz nz > 0 in f32 (lsnFusionNormals
+ * writes (0, 0, 0) for a vertex of no used triangle: those matches drop out).  The usable matches' residuals r = (b - a) . n with
+ * J = [b x n, n] are summed in double into the 6x6 normal equations, solved by pseudo-inverse over the eigen-decomposition -- a mode whose
+ * eigenvalue is <= 2^-20 of the largest is unconstrained and gets zero step (a single wall leaves three) --, and the step becomes a motion
+ * (T, Rn) in f32 that moves the cloud and updates d_R / d_t exactly as lsnIcpRun's does.  No usable match: no motion.  Everything else as
+ * lsnIcpRun: both nn_modes, asynchronous on `stream`, $LSN_ICP_NEAR; lsnIcpTrace's record carries the usable count where the kept count
+ * goes.  A run's bits repeat.  Returns 0, -1 on error. */
+int lsnIcpRunPlane(LsnIcp *icp, const float *d_verts1, const float *d_normals1, int n1, float *d_verts2, int n2, float *d_R,
+                   float *d_t, int maxIter, int nn_mode, void *stream);
+
 /* The NN step alone (parity tests, ablation): d_idx n2 ints, d_dist2 n2 floats. */
 int lsnIcpNearest(LsnIcp *icp, const float *d_verts1, int n1, const float *d_verts2, int n2, int *d_idx,
                   float *d_dist2, int nn_mode, void *stream);
@@ -574,6 +594,17 @@ int lsnRefine(int device, int n_sensors, float *const *clouds, const int *counts
 int lsnRefineVertices(int device, int n_sensors, const void *d_vertices, const int *d_offsets, int n_refine_iters, int n_icp_iters,
                       float *world_R, float *world_t, float *camera_R, float *camera_t, float *Rs_out, float *Ts_out, float *d_clouds_out,
                       void *stream);
+
+/* lsnRefineVertices with the point-to-plane residual (lsnIcpRunPlane's step in every ICP call of the Gauss-Seidel loop).  d_normals: ONE
+ * tick of lsnFusionNormals' output -- 12 bytes per vertex at the vertex's own index, so for tick k of a plan d_normals_out + k * capacity * 12
+ * bytes --, read only and final like d_vertices.  "All other sensors" is concatenated for the normals as for the points (two more
+ * device-to-device copies per step); after sensor i's call its current normals are recomputed as n0_i R_i in f32 from the tick's ORIGINAL
+ * normals and the sensor's accumulated pose -- never chained from the step before.  The seeds between passes, the kept device state
+ * (lsnRefineRelease frees and reports the three normals buffers with the rest: 36 bytes per point more, less 12 per point of the smallest
+ * cloud), the "nothing to refine" rules and every other argument: as lsnRefineVertices.  Returns 0, -1 on error. */
+int lsnRefineVerticesPlane(int device, int n_sensors, const void *d_vertices, const float *d_normals, const int *d_offsets,
+                           int n_refine_iters, int n_icp_iters, float *world_R, float *world_t, float *camera_R, float *camera_t,
+                           float *Rs_out, float *Ts_out, float *d_clouds_out, void *stream);
 
 /* Host-only (no device needed): the pose composition at the end of refineWorker_DoWork (MainWindowForm.cs:382-410) in f32, the C# loops
  * as written -- including their in-place update of worldTransforms[i].R while later rows still read it.  Rs (n x 9) / Ts (n x 3) are the

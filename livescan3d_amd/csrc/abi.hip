@@ -467,6 +467,63 @@ extern "C" void deleteMesh(Mesh *mesh)
     });
 }
 
+// ICP's flow on host arrays, for either residual: the context's workspace, lock, stream and device buffers, pinned scratch for the way
+// home, the caller's buffers untouched unless everything worked.  normals1 (nullable): the target's normals -- the point-to-plane step.
+// 0, or -1 (the message is set wherever the failure has one).
+static int icp_on_host_arrays(const char *who, Point3f *verts1, Point3f *normals1, Point3f *verts2, int nVerts1, int nVerts2, float *R, float *t, int maxIter)
+{
+    Ctx &c = ctx();
+    std::lock_guard<std::mutex> g(c.icp_mu);   // not c.mu: merge calls go on while a refine call runs
+    if (ensure_ready(c)) return -1;
+    if (!c.icp || nVerts1 > c.icp_n1 || nVerts2 > c.icp_n2) {
+        if (c.icp) lsnIcpDestroy(c.icp);
+        c.icp_n1 = nVerts1 > c.icp_n1 ? nVerts1 : c.icp_n1;
+        c.icp_n2 = nVerts2 > c.icp_n2 ? nVerts2 : c.icp_n2;
+        c.icp = lsnIcpCreate(c.device, c.icp_n1, c.icp_n2);
+        if (!c.icp) {
+            c.icp_n1 = c.icp_n2 = 0;
+            return -1;
+        }
+    }
+    const size_t v1_bytes = sizeof(float) * 3 * (size_t)nVerts1;
+    if (c.d_v1.reserve(v1_bytes) || c.d_v2.reserve(sizeof(float) * 3 * (size_t)nVerts2) || c.d_Rt.reserve(64) || (normals1 && c.d_n1.reserve(v1_bytes)))
+        return -1;
+    const char *env = getenv("LSN_NN");
+    const int nn_mode = (env && strcmp(env, "brute") == 0) ? 0 : 1;
+    if (hipMemcpyAsync(c.d_v1.p, verts1, v1_bytes, hipMemcpyHostToDevice, c.icp_stream) != hipSuccess ||
+        (normals1 && hipMemcpyAsync(c.d_n1.p, normals1, v1_bytes, hipMemcpyHostToDevice, c.icp_stream) != hipSuccess) ||
+        hipMemcpyAsync(c.d_v2.p, verts2, sizeof(float) * 3 * (size_t)nVerts2, hipMemcpyHostToDevice, c.icp_stream) != hipSuccess ||
+        hipMemcpyAsync(c.d_Rt.p, R, sizeof(float) * 9, hipMemcpyHostToDevice, c.icp_stream) != hipSuccess ||
+        hipMemcpyAsync(c.d_Rt.as<float>() + 9, t, sizeof(float) * 3, hipMemcpyHostToDevice, c.icp_stream) != hipSuccess) {
+        lsn::set_error("%s: upload failed: %s", who, hipGetErrorString(hipGetLastError()));
+        return -1;
+    }
+    const int rc = normals1 ? lsnIcpRunPlane(c.icp, c.d_v1.as<float>(), c.d_n1.as<float>(), nVerts1, c.d_v2.as<float>(), nVerts2, c.d_Rt.as<float>(),
+                                             c.d_Rt.as<float>() + 9, maxIter, nn_mode, c.icp_stream)
+                            : lsnIcpRun(c.icp, c.d_v1.as<float>(), nVerts1, c.d_v2.as<float>(), nVerts2, c.d_Rt.as<float>(), c.d_Rt.as<float>() + 9, maxIter,
+                                        nn_mode, c.icp_stream);
+    if (rc) return -1;
+    // results go to a scratch first so that the caller's buffers stay untouched when anything fails: a pinned block of the pool
+    // (recycled call after call; the download runs as DMA into it)
+    const size_t v2_bytes = sizeof(float) * 3 * (size_t)nVerts2;
+    float *v2 = static_cast<float *>(pinned_get(c, v2_bytes + sizeof(float) * 12));
+    if (!v2) return -1;
+    float *Rt = v2 + (size_t)nVerts2 * 3;
+    if (hipMemcpyAsync(v2, c.d_v2.p, v2_bytes, hipMemcpyDeviceToHost, c.icp_stream) != hipSuccess ||
+        hipMemcpyAsync(Rt, c.d_Rt.p, sizeof(float) * 12, hipMemcpyDeviceToHost, c.icp_stream) != hipSuccess ||
+        hipStreamSynchronize(c.icp_stream) != hipSuccess) {
+        lsn::set_error("%s: download failed: %s", who, hipGetErrorString(hipGetLastError()));
+        (void)hipStreamSynchronize(c.icp_stream);
+        pinned_put(c, v2);
+        return -1;
+    }
+    memcpy(verts2, v2, v2_bytes);
+    memcpy(R, Rt, sizeof(float) * 9);
+    memcpy(t, Rt + 9, sizeof(float) * 3);
+    pinned_put(c, v2);
+    return 0;
+}
+
 extern "C" float ICP(Point3f *verts1, Point3f *verts2, int nVerts1, int nVerts2, float *R, float *t, int maxIter)
 {
     return lsn::guarded("ICP", 1.0f, [&]() {
@@ -477,53 +534,21 @@ extern "C" float ICP(Point3f *verts1, Point3f *verts2, int nVerts1, int nVerts2,
             if (nVerts1 <= 0 || nVerts2 <= 0) lsn::set_error("ICP: empty cloud (nVerts1=%d nVerts2=%d)", nVerts1, nVerts2);
             return error;
         }
-        Ctx &c = ctx();
-        std::lock_guard<std::mutex> g(c.icp_mu);   // not c.mu: merge calls go on while a refine call runs
-        if (ensure_ready(c)) return error;
-        if (!c.icp || nVerts1 > c.icp_n1 || nVerts2 > c.icp_n2) {
-            if (c.icp) lsnIcpDestroy(c.icp);
-            c.icp_n1 = nVerts1 > c.icp_n1 ? nVerts1 : c.icp_n1;
-            c.icp_n2 = nVerts2 > c.icp_n2 ? nVerts2 : c.icp_n2;
-            c.icp = lsnIcpCreate(c.device, c.icp_n1, c.icp_n2);
-            if (!c.icp) {
-                c.icp_n1 = c.icp_n2 = 0;
-                return error;
-            }
-        }
-        if (c.d_v1.reserve(sizeof(float) * 3 * (size_t)nVerts1) || c.d_v2.reserve(sizeof(float) * 3 * (size_t)nVerts2) || c.d_Rt.reserve(64))
-            return error;
-        const char *env = getenv("LSN_NN");
-        const int nn_mode = (env && strcmp(env, "brute") == 0) ? 0 : 1;
-        auto fail = [&]() { return error; };
-        if (hipMemcpyAsync(c.d_v1.p, verts1, sizeof(float) * 3 * (size_t)nVerts1, hipMemcpyHostToDevice, c.icp_stream) != hipSuccess ||
-            hipMemcpyAsync(c.d_v2.p, verts2, sizeof(float) * 3 * (size_t)nVerts2, hipMemcpyHostToDevice, c.icp_stream) != hipSuccess ||
-            hipMemcpyAsync(c.d_Rt.p, R, sizeof(float) * 9, hipMemcpyHostToDevice, c.icp_stream) != hipSuccess ||
-            hipMemcpyAsync(c.d_Rt.as<float>() + 9, t, sizeof(float) * 3, hipMemcpyHostToDevice, c.icp_stream) != hipSuccess) {
-            lsn::set_error("ICP: upload failed: %s", hipGetErrorString(hipGetLastError()));
-            return fail();
-        }
-        if (lsnIcpRun(c.icp, c.d_v1.as<float>(), nVerts1, c.d_v2.as<float>(), nVerts2, c.d_Rt.as<float>(), c.d_Rt.as<float>() + 9, maxIter,
-                      nn_mode, c.icp_stream))
-            return fail();
-        // results go to a scratch first so that the caller's buffers stay untouched when anything fails: a pinned block of the pool
-        // (recycled call after call; the download runs as DMA into it)
-        const size_t v2_bytes = sizeof(float) * 3 * (size_t)nVerts2;
-        float *v2 = static_cast<float *>(pinned_get(c, v2_bytes + sizeof(float) * 12));
-        if (!v2) return fail();
-        float *Rt = v2 + (size_t)nVerts2 * 3;
-        if (hipMemcpyAsync(v2, c.d_v2.p, v2_bytes, hipMemcpyDeviceToHost, c.icp_stream) != hipSuccess ||
-            hipMemcpyAsync(Rt, c.d_Rt.p, sizeof(float) * 12, hipMemcpyDeviceToHost, c.icp_stream) != hipSuccess ||
-            hipStreamSynchronize(c.icp_stream) != hipSuccess) {
-            lsn::set_error("ICP: download failed: %s", hipGetErrorString(hipGetLastError()));
-            (void)hipStreamSynchronize(c.icp_stream);
-            pinned_put(c, v2);
-            return fail();
-        }
-        memcpy(verts2, v2, v2_bytes);
-        memcpy(R, Rt, sizeof(float) * 9);
-        memcpy(t, Rt + 9, sizeof(float) * 3);
-        pinned_put(c, v2);
+        (void)icp_on_host_arrays("ICP", verts1, nullptr, verts2, nVerts1, nVerts2, R, t, maxIter);
         return error;
+    });
+}
+
+extern "C" int lsnIcpPointToPlane(Point3f *verts1, Point3f *normals1, Point3f *verts2, int nVerts1, int nVerts2, float *R, float *t, int maxIter)
+{
+    return lsn::guarded("lsnIcpPointToPlane", -1, [&]() {
+        lsn::clear_error();
+        if (!verts1 || !normals1 || !verts2 || !R || !t || nVerts1 <= 0 || nVerts2 <= 0) {
+            lsn::set_error("lsnIcpPointToPlane: null argument or empty cloud (nVerts1=%d nVerts2=%d)", nVerts1, nVerts2);
+            return -1;
+        }
+        if (maxIter <= 0) return 0;   // nothing to do: the caller's arrays stay as they are
+        return icp_on_host_arrays("lsnIcpPointToPlane", verts1, normals1, verts2, nVerts1, nVerts2, R, t, maxIter);
     });
 }
 

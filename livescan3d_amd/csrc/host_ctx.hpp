@@ -147,7 +147,7 @@ struct Ctx {
     int host_path = 0;        // $LSN_HOST_PATH: 0 = by call (default), 1 = "direct" (kernel stores) always, 2 = "grouped" (copy engine) always
     int group_override = 0;   // $LSN_HOST_GROUP: sensors per group (0 = by size)
     hipStream_t icp_stream = nullptr;
-    lsn::DevBuf d_v1, d_v2, d_Rt;
+    lsn::DevBuf d_v1, d_v2, d_Rt, d_n1;   // d_n1: the target's normals (lsnIcpPointToPlane)
     LsnIcp *icp = nullptr;
     int icp_n1 = 0, icp_n2 = 0;
     // pinned host blocks handed out as Mesh::vertices, recycled by deleteMesh

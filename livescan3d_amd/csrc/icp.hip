@@ -32,6 +32,10 @@
 //     of the SVD algorithm up to rounding), then the same f32 products, det test and updates as icp.cpp:155-168.
 //   * apply -- the translate+rotate of the source cloud in the reference's f32 operation order rides in the first
 //     kernel of the next iteration's NN step (one separate pass after the last iteration).
+//   * point-to-plane step (lsnIcpRunPlane; no counterpart in the reference, defined in tests/icp_plane_ref.py) -- the same NN, matching,
+//     statistics and rejection; then the 6x6 normal equations of r = (b - a) . n over the kept matches with a usable target normal, summed
+//     in double like the Kabsch sums, an eigen-solve by cyclic Jacobi in the single-thread kernel with the weakly determined modes left
+//     alone, and the same apply and pose update (accum_plane_kernel, solve_plane_kernel).
 // This file is compiled with -ffp-contract=off.
 #include "lsn_common.hpp"
 #include "wave_ops.hpp"
@@ -1358,17 +1362,13 @@ __global__ __launch_bounds__(kThreads) void stats_kernel(const int *idx, const f
     }
 }
 
-// pass 2: mean and standard deviation of the matches' squared distances (GetStandardDeviation, icp.cpp:34-54: the mean is
-// rounded to f32, the deviations are taken from that f32 mean, the sum is kept in a float and divided by the count),
-// reject d > 2.5*std (icp.cpp:56-73), accumulate count, sum m1, sum m2, sum m2 m1^T over the kept matches.
-// sum (d - mean)^2 = sum d^2 - 2 mean sum d + m mean^2 is evaluated in double from pass 1's three sums (mean = the f32
-// value): one pass over the matches instead of two; the cancellation costs ~1e-15 relative, far below the f32 result.
-__global__ __launch_bounds__(kThreads) void accum_kernel(const float *verts1, const float *verts2, const int *idx, const float *dist,
-                                                         const unsigned long long *keys, int n2, const double *part1, int n_part1,
-                                                         double *part /* [blocks][16] */, IcpState *st)
+// The front half of pass 2, shared by both residuals: mean and standard deviation of the matches' squared distances from pass 1's partials
+// (GetStandardDeviation, icp.cpp:34-54: the mean is rounded to f32, the deviations are taken from that f32 mean, the sum is kept in a
+// float and divided by the count) and the rejection threshold 2.5*std (icp.cpp:56-73), in every thread; the first thread of the launch
+// leaves them in st.  sum (d - mean)^2 = sum d^2 - 2 mean sum d + m mean^2 is evaluated in double from pass 1's three sums (mean = the
+// f32 value): one pass over the matches instead of two; the cancellation costs ~1e-15 relative, far below the f32 result.
+__device__ __forceinline__ float rejection_threshold(const double *part1, int n_part1, int n2, IcpState *st, double *red /* [kThreads + 4] */)
 {
-    __shared__ double lds[4 * 16];
-    __shared__ double red[kThreads + 4];
     double s1[4];
     reduce_partials<4, 4>(part1, n_part1, s1, red);
     const float mean = (float)(s1[1] / s1[0]);
@@ -1385,6 +1385,17 @@ __global__ __launch_bounds__(kThreads) void accum_kernel(const float *verts1, co
         st->thresh = thresh;
         st->near_next = 2.0 * s1[3] >= (double)n2;
     }
+    return thresh;
+}
+
+// pass 2 of the point-to-point step: reject d > 2.5*std, accumulate count, sum m1, sum m2, sum m2 m1^T over the kept matches.
+__global__ __launch_bounds__(kThreads) void accum_kernel(const float *verts1, const float *verts2, const int *idx, const float *dist,
+                                                         const unsigned long long *keys, int n2, const double *part1, int n_part1,
+                                                         double *part /* [blocks][16] */, IcpState *st)
+{
+    __shared__ double lds[4 * 16];
+    __shared__ double red[kThreads + 4];
+    const float thresh = rejection_threshold(part1, n_part1, n2, st, red);
     double v[16];
 #pragma unroll
     for (int k = 0; k < 16; k++) v[k] = 0;
@@ -1409,6 +1420,56 @@ __global__ __launch_bounds__(kThreads) void accum_kernel(const float *verts1, co
         for (int k = 0; k < 16; k++)
             if (threadIdx.x == k) out = v[k];
         part[blockIdx.x * 16 + threadIdx.x] = out;
+    }
+}
+
+// pass 2 of the point-to-plane step (lsnIcpRunPlane; defined in tests/icp_plane_ref.py): accum_kernel's front half
+// (rejection_threshold: the same mean, sigma and threshold from pass 1's partials, the same bits in st), then, over the kept matches whose
+// target normal is usable (finite, (nx nx + ny ny) + nz nz > 0 in f32), the 28 sums of the 6x6 normal equations: the count, the 21
+// distinct sums of A = sum J J^T (row-major upper triangle) and the 6 of g = sum J r, with r = (b - a) . n and J = [b x n, n] in
+// double.  A product of two f32 values is exact in double, so every term has one value in any IEEE double arithmetic; the sums are
+// reduced without atomics in a fixed order: a run's bits repeat.  The partials' stride is kPlaneStride (reduce_partials takes a
+// power of two); the four spare components are written as zero.
+constexpr int kPlaneSums = 28, kPlaneStride = 32;
+__global__ __launch_bounds__(kThreads) void accum_plane_kernel(const float *verts1, const float *normals1, const float *verts2, const int *idx,
+                                                               const float *dist, const unsigned long long *keys, int n2, const double *part1,
+                                                               int n_part1, double *part /* [blocks][kPlaneStride] */, IcpState *st)
+{
+    __shared__ double lds[4 * kPlaneSums];
+    __shared__ double red[kThreads + 4];
+    const float thresh = rejection_threshold(part1, n_part1, n2, st, red);
+    double v[kPlaneSums];
+#pragma unroll
+    for (int k = 0; k < kPlaneSums; k++) v[k] = 0;
+    for (int i = blockIdx.x * kThreads + threadIdx.x; i < n2; i += gridDim.x * kThreads) {
+        if (!is_winner(keys, idx, i)) continue;
+        if (dist[i] > thresh) continue;
+        const int k = idx[i];
+        const float nx = normals1[3 * (size_t)k], ny = normals1[3 * (size_t)k + 1], nz = normals1[3 * (size_t)k + 2];
+        if (!finite3(nx, ny, nz) || !(nx * nx + ny * ny + nz * nz > 0.0f)) continue;   // (nx nx + ny ny) + nz nz, contraction is off
+        const double a0 = verts1[3 * (size_t)k], a1 = verts1[3 * (size_t)k + 1], a2 = verts1[3 * (size_t)k + 2];
+        const double b0 = verts2[3 * (size_t)i], b1 = verts2[3 * (size_t)i + 1], b2 = verts2[3 * (size_t)i + 2];
+        const double n0 = nx, n1 = ny, n2d = nz;
+        const double d0 = b0 - a0, d1 = b1 - a1, d2 = b2 - a2;
+        const double r = (d0 * n0 + d1 * n1) + d2 * n2d;
+        const double J[6] = {b1 * n2d - b2 * n1, b2 * n0 - b0 * n2d, b0 * n1 - b1 * n0, n0, n1, n2d};
+        v[0] += 1.0;
+        int c = 1;
+#pragma unroll
+        for (int p = 0; p < 6; p++)
+#pragma unroll
+            for (int q = p; q < 6; q++) v[c++] += J[p] * J[q];
+#pragma unroll
+        for (int p = 0; p < 6; p++) v[22 + p] += J[p] * r;
+    }
+    block_sum_d<kPlaneSums>(v, lds);
+    if (threadIdx.x < kPlaneStride) {
+        // v[] is valid in every thread; thread k stores component k
+        double out = 0;
+#pragma unroll
+        for (int k = 0; k < kPlaneSums; k++)
+            if (threadIdx.x == k) out = v[k];
+        part[blockIdx.x * kPlaneStride + threadIdx.x] = out;
     }
 }
 
@@ -1498,6 +1559,33 @@ __device__ void svd3(const double A[9], double U[9], double w[3], double V[9], c
     }
 }
 
+// What a step's solve ends with, whichever residual it minimised (icp.cpp:167-168): with mk > 0 the pose update matT += tempT * matR.t()
+// (R before the update), matR = matR * tempR in f32; then the motion for the next launch's apply and the trace record.
+__device__ __forceinline__ void commit_step(const float (&T)[3], const float (&Rn)[9], int mk, float *R, float *t, IcpState *st, float *trace, int iter)
+{
+    st->mk = mk;
+    if (mk > 0) {
+        float add[3];
+        for (int c = 0; c < 3; c++) add[c] = T[0] * R[3 * c] + T[1] * R[3 * c + 1] + T[2] * R[3 * c + 2];
+        for (int c = 0; c < 3; c++) t[c] += add[c];
+        float Rnew[9];
+        for (int r = 0; r < 3; r++)
+            for (int c = 0; c < 3; c++) Rnew[3 * r + c] = R[3 * r] * Rn[c] + R[3 * r + 1] * Rn[3 + c] + R[3 * r + 2] * Rn[6 + c];
+        for (int k = 0; k < 9; k++) R[k] = Rnew[k];
+    }
+    for (int c = 0; c < 3; c++) st->T[c] = T[c];
+    for (int k = 0; k < 9; k++) st->Rn[k] = Rn[k];
+    if (trace) {
+        float *tr = trace + 16 * iter;
+        tr[0] = (float)st->m;
+        tr[1] = (float)mk;
+        tr[2] = st->mean;
+        tr[3] = st->stddev;
+        for (int c = 0; c < 3; c++) tr[4 + c] = T[c];
+        for (int k = 0; k < 9; k++) tr[7 + k] = Rn[k];
+    }
+}
+
 // icp.cpp:141 (T), :152-163 (M, SVD, tempR), :167-168 (t, R update).  One workgroup; thread 0 does the 3x3 work.
 __global__ __launch_bounds__(kThreads) void solve_kernel(const double *part3, int n_part3, float *R, float *t, IcpState *st, float *trace,
                                                          int iter)
@@ -1507,7 +1595,6 @@ __global__ __launch_bounds__(kThreads) void solve_kernel(const double *part3, in
     reduce_partials<16, 16>(part3, n_part3, s, red);
     if (threadIdx.x != 0) return;
     const int mk = (int)s[0];
-    st->mk = mk;
     float T[3] = {0, 0, 0};
     float Rn[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
     if (mk > 0) {
@@ -1536,26 +1623,117 @@ __global__ __launch_bounds__(kThreads) void solve_kernel(const double *part3, in
             for (int r = 0; r < 3; r++)
                 for (int c = 0; c < 3; c++) Rn[3 * r + c] = Uf[3 * r] * Vtf[c] + Uf[3 * r + 1] * Vtf[3 + c] + Uf[3 * r + 2] * Vtf[6 + c];
         }
-        // matT += tempT * matR.t() (R before the update), matR = matR * tempR
-        float add[3];
-        for (int c = 0; c < 3; c++) add[c] = T[0] * R[3 * c] + T[1] * R[3 * c + 1] + T[2] * R[3 * c + 2];
-        for (int c = 0; c < 3; c++) t[c] += add[c];
-        float Rnew[9];
-        for (int r = 0; r < 3; r++)
-            for (int c = 0; c < 3; c++) Rnew[3 * r + c] = R[3 * r] * Rn[c] + R[3 * r + 1] * Rn[3 + c] + R[3 * r + 2] * Rn[6 + c];
-        for (int k = 0; k < 9; k++) R[k] = Rnew[k];
     }
-    for (int c = 0; c < 3; c++) st->T[c] = T[c];
-    for (int k = 0; k < 9; k++) st->Rn[k] = Rn[k];
-    if (trace) {
-        float *tr = trace + 16 * iter;
-        tr[0] = (float)st->m;
-        tr[1] = (float)mk;
-        tr[2] = st->mean;
-        tr[3] = st->stddev;
-        for (int c = 0; c < 3; c++) tr[4 + c] = T[c];
-        for (int k = 0; k < 9; k++) tr[7 + k] = Rn[k];
+    commit_step(T, Rn, mk, R, t, st, trace, iter);
+}
+
+// A (6x6 symmetric, both halves filled) = V diag(a_ii) V^T on return, by cyclic Jacobi rotations in double; the eigenvectors are V's columns.
+// Every index is a compile-time constant once the pair loops are unrolled, so a and V live in registers (no scratch).  A pair is passed
+// over when its off-diagonal element is below 1e-16 of the geometric mean of its diagonal elements, or below 2^-70 of A's trace: the
+// second floor ends the sweeps on the exact zero modes of a singular A (a wall, two walls), whose diagonal elements are rounding noise,
+// and sits far below the 2^-20 lambda_max cutoff the eigenvalues are compared with.
+__device__ __forceinline__ void eig6(double (&a)[6][6], double (&V)[6][6])
+{
+#pragma unroll
+    for (int i = 0; i < 6; i++)
+#pragma unroll
+        for (int j = 0; j < 6; j++) V[i][j] = i == j ? 1.0 : 0.0;
+    const double floor_abs = 0x1p-70 * (((a[0][0] + a[1][1]) + (a[2][2] + a[3][3])) + (a[4][4] + a[5][5]));
+    for (int sweep = 0; sweep < 30; sweep++) {
+        int rotations = 0;
+#pragma unroll
+        for (int p = 0; p < 5; p++)
+#pragma unroll
+            for (int q = p + 1; q < 6; q++) {
+                const double apq = a[p][q];
+                if (fabs(apq) <= floor_abs || apq * apq <= 1e-32 * fabs(a[p][p] * a[q][q])) continue;
+                rotations++;
+                // tan of the rotation as in svd3: one division and one square root
+                const double ba = a[q][q] - a[p][p];
+                const double tt = ((ba >= 0) == (apq >= 0) ? 2.0 : -2.0) * fabs(apq) / (fabs(ba) + sqrt(ba * ba + 4.0 * apq * apq));
+                const double cs = rsqrt(1.0 + tt * tt), sn = cs * tt;
+                a[p][p] -= tt * apq;
+                a[q][q] += tt * apq;
+                a[p][q] = a[q][p] = 0.0;
+#pragma unroll
+                for (int k = 0; k < 6; k++) {
+                    if (k != p && k != q) {
+                        const double akp = a[k][p], akq = a[k][q];
+                        a[k][p] = a[p][k] = cs * akp - sn * akq;
+                        a[k][q] = a[q][k] = sn * akp + cs * akq;
+                    }
+                    const double vp = V[k][p], vq = V[k][q];
+                    V[k][p] = cs * vp - sn * vq;
+                    V[k][q] = sn * vp + cs * vq;
+                }
+            }
+        if (rotations == 0) break;
     }
+}
+
+// The point-to-plane solve (tests/icp_plane_ref.py steps 4-6): A x = -g by pseudo-inverse over A's eigen-decomposition -- a mode whose
+// eigenvalue is <= 2^-20 lambda_max is unconstrained and gets zero step --, x = (omega, tau), Rinc = exp([omega]x) by Rodrigues in double
+// (series for sin th / th and (1 - cos th) / th^2 below th = 2^-10), Rn = Rinc^T and T = Rinc^T tau rounded once to f32, and solve_kernel's
+// pose update.  One workgroup; thread 0 does the 6x6 work.
+__global__ __launch_bounds__(kThreads) void solve_plane_kernel(const double *part3, int n_part3, float *R, float *t, IcpState *st, float *trace,
+                                                               int iter)
+{
+    __shared__ double red[kThreads + kPlaneStride];
+    double s[kPlaneSums];
+    reduce_partials<kPlaneSums, kPlaneStride>(part3, n_part3, s, red);
+    if (threadIdx.x != 0) return;
+    const int mk = (int)s[0];
+    float T[3] = {0, 0, 0};
+    float Rn[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
+    if (mk > 0) {
+        double a[6][6], V[6][6];
+        {
+            int c = 1;
+#pragma unroll
+            for (int p = 0; p < 6; p++)
+#pragma unroll
+                for (int q = p; q < 6; q++) a[p][q] = a[q][p] = s[c++];
+        }
+        eig6(a, V);
+        double lmax = a[0][0];
+#pragma unroll
+        for (int i = 1; i < 6; i++) lmax = a[i][i] > lmax ? a[i][i] : lmax;
+        if (lmax > 0.0) {
+            double x[6] = {0, 0, 0, 0, 0, 0};
+#pragma unroll
+            for (int i = 0; i < 6; i++) {
+                if (!(a[i][i] > 0x1p-20 * lmax)) continue;
+                double c = 0;
+#pragma unroll
+                for (int k = 0; k < 6; k++) c += V[k][i] * s[22 + k];
+                c = -c / a[i][i];
+#pragma unroll
+                for (int k = 0; k < 6; k++) x[k] += V[k][i] * c;
+            }
+            const double t2 = (x[0] * x[0] + x[1] * x[1]) + x[2] * x[2];
+            const double th = sqrt(t2);
+            double sc, cc;
+            if (th < 0x1p-10) {
+                sc = 1.0 - t2 / 6.0 * (1.0 - t2 / 20.0 * (1.0 - t2 / 42.0));
+                cc = 0.5 - t2 / 24.0 * (1.0 - t2 / 30.0 * (1.0 - t2 / 56.0));
+            } else {
+                sc = sin(th) / th;
+                cc = (1.0 - cos(th)) / t2;
+            }
+            // Rinc = I + sc K + cc K^2, K = [omega]x, K^2 = omega omega^T - |omega|^2 I
+            double Ri[9];
+            for (int r = 0; r < 3; r++)
+                for (int c = 0; c < 3; c++) Ri[3 * r + c] = cc * (x[r] * x[c] - (r == c ? t2 : 0.0)) + (r == c ? 1.0 : 0.0);
+            Ri[1] -= sc * x[2]; Ri[2] += sc * x[1];
+            Ri[3] += sc * x[2]; Ri[5] -= sc * x[0];
+            Ri[6] -= sc * x[1]; Ri[7] += sc * x[0];
+            for (int r = 0; r < 3; r++) {
+                T[r] = (float)((Ri[r] * x[3] + Ri[3 + r] * x[4]) + Ri[6 + r] * x[5]);   // T = Rinc^T tau
+                for (int c = 0; c < 3; c++) Rn[3 * r + c] = (float)Ri[3 * c + r];        // Rn = Rinc^T
+            }
+        }
+    }
+    commit_step(T, Rn, mk, R, t, st, trace, iter);
 }
 
 // icp.cpp:143-146 + :165: v = (v + T) * Rn, row vectors, f32, one rounding per operation.  Thread j moves query j of the
@@ -1581,6 +1759,19 @@ __global__ __launch_bounds__(kThreads) void apply_kernel(float4 *src, float *ver
     verts2[o] = q.x;
     verts2[o + 1] = q.y;
     verts2[o + 2] = q.z;
+}
+
+// out = n0 R for row vectors in f32, in apply_kernel's association (x r0 + y r3) + z r6: a sensor's current normals from its ORIGINAL ones
+// and its accumulated pose (the point-to-plane refine pass: never chained from the previous step's normals).
+__global__ __launch_bounds__(kThreads) void rotate_normals_kernel(const float *__restrict__ n0, const float *__restrict__ R, float *__restrict__ out, int n)
+{
+    const int j = blockIdx.x * kThreads + threadIdx.x;
+    if (j >= n) return;
+    const float r0 = R[0], r1 = R[1], r2 = R[2], r3 = R[3], r4 = R[4], r5 = R[5], r6 = R[6], r7 = R[7], r8 = R[8];
+    const float x = n0[3 * (size_t)j], y = n0[3 * (size_t)j + 1], z = n0[3 * (size_t)j + 2];
+    out[3 * (size_t)j] = x * r0 + y * r3 + z * r6;
+    out[3 * (size_t)j + 1] = x * r1 + y * r4 + z * r7;
+    out[3 * (size_t)j + 2] = x * r2 + y * r5 + z * r8;
 }
 
 // What lsnIcpRun clears before its first iteration.
@@ -1694,7 +1885,7 @@ extern "C" LsnIcp * lsnIcpCreate(int device, int max_n1, int max_n2)
             bad |= w->list_b.reserve(sizeof(int4) * (size_t)w->seg_b * kSegs) != 0;
         }
         bad |= w->part1.reserve(sizeof(double) * 4 * kMaxBlocks) != 0;
-        bad |= w->part3.reserve(sizeof(double) * 16 * kMaxBlocks) != 0;
+        bad |= w->part3.reserve(sizeof(double) * kPlaneStride * kMaxBlocks) != 0;   // 16 per slot (point-to-point) or kPlaneStride (point-to-plane)
         bad |= w->state.reserve(sizeof(IcpState)) != 0;
         bad |= w->trace.reserve(sizeof(float) * 16 * kTraceCap) != 0;
         if (bad) {
@@ -1925,13 +2116,15 @@ extern "C" int lsnIcpNearest(LsnIcp *w, const float *d_verts1, int n1, const flo
 // d_seeds (nullable, lsnRefine): n2 target indices by the queries' original index -- any index < n1 is a valid seed (a real point bounds the
 // search; the result never depends on it), good ones make the first step as cheap as the later ones.
 // The body of lsnIcpRun under a name of its own: lsnRefine (below) calls it too, with seeds, inside a guarded entry it makes itself.
-static int icp_run(LsnIcp *w, const float *d_verts1, int n1, float *d_verts2, int n2, float *d_R, float *d_t, int maxIter, int nn_mode,
-                   void *stream, const int *d_seeds = nullptr)
+// d_normals1 (nullable): n1 x 3 floats, the target's normals at the target's index -- non-null selects the point-to-plane step
+// (accum_plane_kernel / solve_plane_kernel in place of accum_kernel / solve_kernel); null is the point-to-point path, launch for launch.
+static int icp_run(const char *who, LsnIcp *w, const float *d_verts1, const float *d_normals1, int n1, float *d_verts2, int n2, float *d_R, float *d_t,
+                   int maxIter, int nn_mode, void *stream, const int *d_seeds = nullptr)
 {
     lsn::clear_error();
-    if (check_sizes(w, n1, n2, "lsnIcpRun")) return -1;
+    if (check_sizes(w, n1, n2, who)) return -1;
     if (!d_verts1 || !d_verts2 || !d_R || !d_t) {
-        lsn::set_error("lsnIcpRun: null argument");
+        lsn::set_error("%s: null argument", who);
         return -1;
     }
     std::lock_guard<std::mutex> g(w->mu);
@@ -1966,10 +2159,16 @@ static int icp_run(LsnIcp *w, const float *d_verts1, int n1, float *d_verts2, in
         mark(w, 1, s);
         hipLaunchKernelGGL(stats_kernel, dim3(nb), dim3(kThreads), 0, s, w->idx.as<int>(), w->dist.as<float>(), keys, n2,
                            nn_mode != 0 ? (const GridParams *)w->tgt.gp.as<GridParams>() : (const GridParams *)nullptr, w->part1.as<double>());
-        hipLaunchKernelGGL(accum_kernel, dim3(nb), dim3(kThreads), 0, s, d_verts1, (const float *)d_verts2, w->idx.as<int>(),
-                           w->dist.as<float>(), keys, n2, w->part1.as<double>(), nb, w->part3.as<double>(), st);
-        hipLaunchKernelGGL(solve_kernel, dim3(1), dim3(kThreads), 0, s, w->part3.as<double>(), nb, d_R, d_t, st,
-                           iter < kTraceCap ? w->trace.as<float>() : (float *)nullptr, iter);
+        float *trace = iter < kTraceCap ? w->trace.as<float>() : (float *)nullptr;
+        if (d_normals1) {
+            hipLaunchKernelGGL(accum_plane_kernel, dim3(nb), dim3(kThreads), 0, s, d_verts1, d_normals1, (const float *)d_verts2, w->idx.as<int>(),
+                               w->dist.as<float>(), keys, n2, w->part1.as<double>(), nb, w->part3.as<double>(), st);
+            hipLaunchKernelGGL(solve_plane_kernel, dim3(1), dim3(kThreads), 0, s, w->part3.as<double>(), nb, d_R, d_t, st, trace, iter);
+        } else {
+            hipLaunchKernelGGL(accum_kernel, dim3(nb), dim3(kThreads), 0, s, d_verts1, (const float *)d_verts2, w->idx.as<int>(),
+                               w->dist.as<float>(), keys, n2, w->part1.as<double>(), nb, w->part3.as<double>(), st);
+            hipLaunchKernelGGL(solve_kernel, dim3(1), dim3(kThreads), 0, s, w->part3.as<double>(), nb, d_R, d_t, st, trace, iter);
+        }
         mark(w, 2, s);
     }
     hipLaunchKernelGGL(apply_kernel, dim3(blocks_for(n2)), dim3(kThreads), 0, s, w->src.sorted.as<float4>(), d_verts2, n2, (const IcpState *)st,
@@ -1982,7 +2181,20 @@ static int icp_run(LsnIcp *w, const float *d_verts1, int n1, float *d_verts2, in
 extern "C" int lsnIcpRun(LsnIcp *w, const float *d_verts1, int n1, float *d_verts2, int n2, float *d_R, float *d_t, int maxIter,
                          int nn_mode, void *stream)
 {
-    return lsn::guarded("lsnIcpRun", -1, [&]() { return icp_run(w, d_verts1, n1, d_verts2, n2, d_R, d_t, maxIter, nn_mode, stream); });
+    return lsn::guarded("lsnIcpRun", -1, [&]() { return icp_run("lsnIcpRun", w, d_verts1, nullptr, n1, d_verts2, n2, d_R, d_t, maxIter, nn_mode, stream); });
+}
+
+extern "C" int lsnIcpRunPlane(LsnIcp *w, const float *d_verts1, const float *d_normals1, int n1, float *d_verts2, int n2, float *d_R, float *d_t,
+                              int maxIter, int nn_mode, void *stream)
+{
+    return lsn::guarded("lsnIcpRunPlane", -1, [&]() {
+        if (!d_normals1) {
+            lsn::clear_error();
+            lsn::set_error("lsnIcpRunPlane: null argument");
+            return -1;
+        }
+        return icp_run("lsnIcpRunPlane", w, d_verts1, d_normals1, n1, d_verts2, n2, d_R, d_t, maxIter, nn_mode, stream);
+    });
 }
 
 // How many queries of the last voxel-grid NN step the near path settled (diagnostic: synchronises `stream`, reads the groups' masks back).
@@ -2028,7 +2240,14 @@ struct RefineState {   // what a refine pass keeps on the device between calls
     LsnIcp *ws = nullptr;
     hipStream_t s = nullptr;
     lsn::DevBuf d_all, d_others, d_Rt, d_seeds;
-    long long bytes() const { return (long long)(d_all.bytes + d_others.bytes + d_Rt.bytes + d_seeds.bytes + (ws ? ws->bytes() : 0)); }
+    // the point-to-plane pass only (lsnRefineVerticesPlane): the normals twin of d_all / d_others, and the tick's original normals every
+    // sensor's current ones are recomputed from
+    lsn::DevBuf d_nrm, d_nrm_others, d_nrm0;
+    long long bytes() const
+    {
+        return (long long)(d_all.bytes + d_others.bytes + d_Rt.bytes + d_seeds.bytes + d_nrm.bytes + d_nrm_others.bytes + d_nrm0.bytes +
+                           (ws ? ws->bytes() : 0));
+    }
     void drop()
     {
         if (device >= 0) (void)hipSetDevice(device);
@@ -2037,6 +2256,7 @@ struct RefineState {   // what a refine pass keeps on the device between calls
         if (s) (void)hipStreamDestroy(s);
         s = nullptr;
         d_all.release(); d_others.release(); d_Rt.release(); d_seeds.release();
+        d_nrm.release(); d_nrm_others.release(); d_nrm0.release();
     }
     ~RefineState() { drop(); }
 };
@@ -2064,9 +2284,12 @@ static RefineState &refine_state(int device)
 
 // The Gauss-Seidel loop (:347-376) on clouds that are resident: rs.d_all holds every sensor's current cloud, sensor i's counts[i] points at
 // 3 * off[i] floats, and rs.d_Rt its accumulated pose {R[9], t[3]} at 12 * i.  Everything is queued on rs.s; nothing is waited for.
+// plane: the point-to-plane pass -- rs.d_nrm holds every sensor's current normals like rs.d_all its points, "all other sensors" is
+// concatenated for both, and after sensor i's call its normals are recomputed as n0_i R_i from the original ones (rs.d_nrm0) and the
+// accumulated pose.
 // 0, or non-zero with the message set or a HIP error pending.
 static int refine_gauss_seidel(const char *who, RefineState &rs, int n_sensors, const int *counts, const long long *off, int n_refine_iters,
-                               int n_icp_iters)
+                               int n_icp_iters, bool plane)
 {
     hipStream_t s = rs.s;
     LsnIcp *ws = rs.ws;
@@ -2082,16 +2305,26 @@ static int refine_gauss_seidel(const char *who, RefineState &rs, int n_sensors, 
             if (!rc && off[i + 1] < total)
                 rc = hipMemcpyAsync(d_others.as<float>() + 3 * off[i], d_all.as<float>() + 3 * off[i + 1], sizeof(float) * 3 * (size_t)(total - off[i + 1]),
                                     hipMemcpyDeviceToDevice, s) != hipSuccess;
+            if (!rc && plane && off[i] > 0)
+                rc = hipMemcpyAsync(rs.d_nrm_others.as<float>(), rs.d_nrm.as<float>(), sizeof(float) * 3 * (size_t)off[i], hipMemcpyDeviceToDevice, s) != hipSuccess;
+            if (!rc && plane && off[i + 1] < total)
+                rc = hipMemcpyAsync(rs.d_nrm_others.as<float>() + 3 * off[i], rs.d_nrm.as<float>() + 3 * off[i + 1],
+                                    sizeof(float) * 3 * (size_t)(total - off[i + 1]), hipMemcpyDeviceToDevice, s) != hipSuccess;
             // From the second pass on the first NN step of a call is seeded with the neighbours the sensor's call of the previous pass ended
             // with ("all other sensors" is the same concatenation in every pass, so the indices still name real points; the others have moved a
             // little, which only makes the seeds a little less tight): ~65 us instead of ~150 for that step, same result (14.23-14.38 ->
             // 13.98-14.07 ms per call, same digest).
             if (!rc)
                 rc = lsn::guarded(who, -1, [&]() {
-                    return icp_run(ws, d_others.as<float>(), (int)pos, d_all.as<float>() + 3 * off[i], counts[i], d_Rt.as<float>() + 12 * i,
-                                   d_Rt.as<float>() + 12 * i + 9, n_icp_iters, 1, s,
-                                   it > 0 ? d_seeds.as<int>() + off[i] : (const int *)nullptr);     // :370
+                    return icp_run(plane ? "lsnIcpRunPlane" : "lsnIcpRun", ws, d_others.as<float>(), plane ? rs.d_nrm_others.as<float>() : (const float *)nullptr,
+                                   (int)pos, d_all.as<float>() + 3 * off[i], counts[i], d_Rt.as<float>() + 12 * i, d_Rt.as<float>() + 12 * i + 9,
+                                   n_icp_iters, 1, s, it > 0 ? d_seeds.as<int>() + off[i] : (const int *)nullptr);     // :370
                 });
+            if (!rc && plane) {
+                hipLaunchKernelGGL(rotate_normals_kernel, dim3(blocks_for(counts[i])), dim3(kThreads), 0, s, (const float *)rs.d_nrm0.as<float>() + 3 * off[i],
+                                   (const float *)d_Rt.as<float>() + 12 * i, rs.d_nrm.as<float>() + 3 * off[i], counts[i]);
+                rc = hipGetLastError() != hipSuccess;
+            }
             if (!rc && it + 1 < n_refine_iters)
                 rc = hipMemcpyAsync(d_seeds.as<int>() + off[i], ws->idx.p, sizeof(int) * (size_t)counts[i], hipMemcpyDeviceToDevice, s) != hipSuccess;
         }
@@ -2122,9 +2355,10 @@ struct RefineShape {
 // One pass on `device`, on the device's kept state: fill(rs, off) queues on rs.s whatever brings the clouds into rs.d_all; the Gauss-Seidel
 // loop runs if the shape is runnable; drain(rs) queues the copies that take the clouds wherever the caller wants them; Rt (n_sensors x 12,
 // handed in as {I, 0}) receives the accumulated poses.  Complete on return.  -1: the message is set and nothing of the pass is kept.
+// d_normals (device, nullable): shape.total x 3 floats, the clouds' normals in d_all's order, final -- the pass is the point-to-plane one.
 template <class Fill, class Drain>
 static int refine_pass(const char *who, int device, int n_sensors, const int *counts, const RefineShape &shape, int n_refine_iters, int n_icp_iters,
-                       float *Rt, Fill &&fill, Drain &&drain)
+                       float *Rt, const float *d_normals, Fill &&fill, Drain &&drain)
 {
     const long long total = shape.total;
     const size_t rt_bytes = sizeof(float) * 12 * (size_t)n_sensors;
@@ -2149,12 +2383,18 @@ static int refine_pass(const char *who, int device, int n_sensors, const int *co
     if (!rc && shape.runnable)
         rc = rs->d_others.reserve(sizeof(float) * 3 * (size_t)(total - shape.min_n)) || rs->d_Rt.reserve(rt_bytes) ||
              rs->d_seeds.reserve(sizeof(int) * (size_t)total);
+    if (!rc && shape.runnable && d_normals)
+        rc = rs->d_nrm.reserve(sizeof(float) * 3 * (size_t)total) || rs->d_nrm0.reserve(sizeof(float) * 3 * (size_t)total) ||
+             rs->d_nrm_others.reserve(sizeof(float) * 3 * (size_t)(total - shape.min_n));
     // (allocated before anything is queued: once a copy into host memory is in flight nothing below may throw before the synchronise)
     std::vector<float> Rt_back(shape.runnable ? 12 * (size_t)n_sensors : 0);
     if (!rc) rc = fill(*rs, shape.off.data());
     if (!rc && shape.runnable) {
         rc = hipMemcpyAsync(rs->d_Rt.p, Rt, rt_bytes, hipMemcpyHostToDevice, s) != hipSuccess;
-        if (!rc) rc = refine_gauss_seidel(who, *rs, n_sensors, counts, shape.off.data(), n_refine_iters, n_icp_iters);
+        if (!rc && d_normals)
+            rc = hipMemcpyAsync(rs->d_nrm0.p, d_normals, sizeof(float) * 3 * (size_t)total, hipMemcpyDeviceToDevice, s) != hipSuccess ||
+                 hipMemcpyAsync(rs->d_nrm.p, d_normals, sizeof(float) * 3 * (size_t)total, hipMemcpyDeviceToDevice, s) != hipSuccess;
+        if (!rc) rc = refine_gauss_seidel(who, *rs, n_sensors, counts, shape.off.data(), n_refine_iters, n_icp_iters, d_normals != nullptr);
     }
     // results land in scratch first: the caller's arrays are only touched when everything worked
     if (!rc) rc = drain(*rs);
@@ -2254,7 +2494,7 @@ extern "C" int lsnRefine(int device, int n_sensors, float *const *clouds, const 
         if (shape.runnable) {
             std::vector<float> back((size_t)shape.total * 3);   // before the pass: nothing may throw between the queued download and its synchronise
             const int rc = refine_pass(
-                "lsnRefine", device, n_sensors, counts, shape, n_refine_iters, n_icp_iters, Rt.data(),
+                "lsnRefine", device, n_sensors, counts, shape, n_refine_iters, n_icp_iters, Rt.data(), nullptr,
                 [&](RefineState &rs, const long long *off) -> int {
                     int bad = 0;
                     for (int i = 0; i < n_sensors && !bad; i++)
@@ -2277,7 +2517,7 @@ extern "C" int lsnRefine(int device, int n_sensors, float *const *clouds, const 
 // (device, nullable) each receive offsets[n_sensors] - offsets[0] points, sensor blocks in sensor order.  offsets: the tick's row on the
 // HOST.  Rt: n_sensors x 12, receives {Rs[i], Ts[i]} ({I, 0} when the shape is not runnable: then the clouds leave as they came).
 int lsn::refine_cloud(const char *who, int device, int n_sensors, const void *d_vertices, const int *offsets, int n_refine_iters, int n_icp_iters,
-                      float *Rt, float *h_clouds, float *d_clouds)
+                      float *Rt, float *h_clouds, float *d_clouds, const float *d_normals)
 {
     std::vector<int> counts((size_t)n_sensors);
     bool bad = offsets[0] < 0;
@@ -2294,7 +2534,7 @@ int lsn::refine_cloud(const char *who, int device, int n_sensors, const void *d_
     identity_poses(poses, n_sensors);
     const size_t cloud_bytes = sizeof(float) * 3 * (size_t)shape.total;
     const int rc = refine_pass(
-        who, device, n_sensors, counts.data(), shape, n_refine_iters, n_icp_iters, poses.data(),
+        who, device, n_sensors, counts.data(), shape, n_refine_iters, n_icp_iters, poses.data(), d_normals ? d_normals + 3 * (size_t)offsets[0] : nullptr,
         [&](RefineState &rs, const long long *) -> int {
             return xyz_of_vertices(static_cast<const char *>(d_vertices) + (size_t)offsets[0] * sizeof(VertexC4ubV3f), rs.d_all.as<float>(), (int)shape.total, rs.s);
         },
@@ -2327,6 +2567,30 @@ extern "C" int lsnRefineVertices(int device, int n_sensors, const void *d_vertic
         LSN_HIP(hipStreamSynchronize(lsn::as_stream(stream)));
         std::vector<float> Rt((size_t)n_sensors * 12);
         if (lsn::refine_cloud("lsnRefineVertices", device, n_sensors, d_vertices, offsets.data(), n_refine_iters, n_icp_iters, Rt.data(), nullptr, d_clouds_out))
+            return -1;
+        lsn::refine_compose(n_sensors, Rt.data(), world_R, world_t, camera_R, camera_t, Rs_out, Ts_out);
+        return 0;
+    });
+}
+
+extern "C" int lsnRefineVerticesPlane(int device, int n_sensors, const void *d_vertices, const float *d_normals, const int *d_offsets, int n_refine_iters,
+                                      int n_icp_iters, float *world_R, float *world_t, float *camera_R, float *camera_t, float *Rs_out, float *Ts_out,
+                                      float *d_clouds_out, void *stream)
+{
+    return lsn::guarded("lsnRefineVerticesPlane", -1, [&]() {
+        lsn::clear_error();
+        if (n_sensors <= 0 || !d_vertices || !d_normals || !d_offsets || (reinterpret_cast<uintptr_t>(d_vertices) & 15) != 0) {
+            lsn::set_error("lsnRefineVerticesPlane: bad arguments");
+            return -1;
+        }
+        LSN_HIP(hipSetDevice(device));
+        // behind everything queued on the caller's stream: once the row is here, the cloud and the normals it describes are final
+        std::vector<int> offsets((size_t)n_sensors + 1);
+        LSN_HIP(hipMemcpyAsync(offsets.data(), d_offsets, sizeof(int) * offsets.size(), hipMemcpyDeviceToHost, lsn::as_stream(stream)));
+        LSN_HIP(hipStreamSynchronize(lsn::as_stream(stream)));
+        std::vector<float> Rt((size_t)n_sensors * 12);
+        if (lsn::refine_cloud("lsnRefineVerticesPlane", device, n_sensors, d_vertices, offsets.data(), n_refine_iters, n_icp_iters, Rt.data(), nullptr,
+                              d_clouds_out, d_normals))
             return -1;
         lsn::refine_compose(n_sensors, Rt.data(), world_R, world_t, camera_R, camera_t, Rs_out, Ts_out);
         return 0;

@@ -234,10 +234,12 @@ struct RadialScratch {
 
 // The refine pass (icp.hip) on ONE tick's merged cloud, resident on `device` and final: vertices -> packed points -> Gauss-Seidel loop.
 // offsets: the tick's n_sensors + 1 row on the HOST; Rt: n_sensors x 12 floats, receives {Rs[i][9], Ts[i][3]}; h_clouds (host) / d_clouds
-// (device), both nullable, receive the refined points.  Complete on return.  refine_compose: the pose composition of the reference's refine
-// worker for those poses (world and camera pairs nullable), and the poses themselves into Rs_out / Ts_out (nullable).
+// (device), both nullable, receive the refined points.  d_normals (device, nullable): the tick's vertex normals, 3 floats per vertex at the
+// vertex's own index and final -- the pass then minimises the point-to-plane residual (lsnRefineVerticesPlane).  Complete on return.
+// refine_compose: the pose composition of the reference's refine worker for those poses (world and camera pairs nullable), and the poses
+// themselves into Rs_out / Ts_out (nullable).
 int refine_cloud(const char *who, int device, int n_sensors, const void *d_vertices, const int *offsets, int n_refine_iters, int n_icp_iters,
-                 float *Rt, float *h_clouds, float *d_clouds);
+                 float *Rt, float *h_clouds, float *d_clouds, const float *d_normals = nullptr);
 void refine_compose(int n, const float *Rt, float *world_R, float *world_t, float *camera_R, float *camera_t, float *Rs_out, float *Ts_out);
 
 // The survivor exchange's two ends with the back-to-back stream layout (exchange.hip; see their definitions).

@@ -154,6 +154,16 @@ class DeviceFusion:
                                       n_refine_iters, n_icp_iters, world_R, world_t, camera_R, camera_t,
                                       None if clouds_out is None else clouds_out.data_ptr(), _stream_handle(stream))
 
+    def refine_plane(self, tick, normals=None, n_refine_iters=2, n_icp_iters=10, world_R=None, world_t=None, camera_R=None, camera_t=None,
+                     clouds_out=None, stream=None):
+        """refine() with the point-to-plane residual (native.refine_vertices_plane).  normals: what normals() returned for the batch as it
+        is now (float32 [T, capacity, 3]); None: the tensor normals() last returned."""
+        normals = self._normals if normals is None else normals
+        assert normals is not None, "refine_plane needs the ticks' normals: call normals() first"
+        return native.refine_vertices_plane(self.device.index, self.n_maps, self.vertices[tick].data_ptr(), normals[tick].data_ptr(),
+                                            self.offsets[tick].data_ptr(), n_refine_iters, n_icp_iters, world_R, world_t, camera_R, camera_t,
+                                            None if clouds_out is None else clouds_out.data_ptr(), _stream_handle(stream))
+
     # ---- host views (each synchronises the device first) ----
 
     def host_offsets(self):

@@ -49,6 +49,7 @@ _PROTOTYPES = {
     "createMesh": (_mesh, []),
     "deleteMesh": (None, [_mesh]),
     "ICP": (_f, [_vp, _vp, _i, _i, _vp, _vp, _i]),
+    "lsnIcpPointToPlane": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _i]),
     "lsnGetLastError": (_i, [_s, _i]),
     "lsnDeviceCount": (_i, []),
     "lsnCorrectAndGenerateMesh": (None, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _mesh, _f, _f, _f, _f, _f, _f, _i]),
@@ -123,6 +124,7 @@ _PROTOTYPES = {
     "lsnIcpCreate": (_vp, [_i, _i, _i]),
     "lsnIcpDestroy": (None, [_vp]),
     "lsnIcpRun": (_i, [_vp, _vp, _i, _vp, _i, _vp, _vp, _i, _i, _vp]),
+    "lsnIcpRunPlane": (_i, [_vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _i, _i, _vp]),
     "lsnIcpNearest": (_i, [_vp, _vp, _i, _vp, _i, _vp, _vp, _i, _vp]),
     "lsnIcpTrace": (_i, [_vp, _vp, _i, _vp]),
     "lsnIcpSetProfiling": (_i, [_vp, _i]),
@@ -130,6 +132,7 @@ _PROTOTYPES = {
     "lsnIcpNearResolved": (_i, [_vp, _vp]),
     "lsnRefine": (_i, [_i, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp]),
     "lsnRefineVertices": (_i, [_i, _i, _vp, _vp, _i, _i] + [_vp] * 8),
+    "lsnRefineVerticesPlane": (_i, [_i, _i, _vp, _vp, _vp, _i, _i] + [_vp] * 8),
     "lsnRefineComposePoses": (_i, [_i] + [_vp] * 6),
     "lsnRefineRelease": (_ll, [_i]),
     "lsnTickCreate": (_vp, [_i, _i, _i, _vp, _vp]),
@@ -437,6 +440,20 @@ def icp(verts1, verts2, R=None, t=None, max_iter=10):
     return v2, R.reshape(3, 3), t
 
 
+def icp_point_to_plane(verts1, normals1, verts2, R=None, t=None, max_iter=10):
+    """lsnIcpPointToPlane: ICP's flow on host arrays with the point-to-plane residual (normals1: the target's normals, [n1, 3]).
+    Returns (verts2_out, R_out[3,3], t_out[3]); inputs are not modified."""
+    require_gpu()
+    v1 = _as(verts1, np.float32).reshape(-1, 3)
+    n1 = _as(normals1, np.float32).reshape(-1, 3)
+    assert n1.shape == v1.shape, (n1.shape, v1.shape)
+    v2 = _as(verts2, np.float32).reshape(-1, 3).copy()
+    R = np.eye(3, dtype=np.float32).ravel() if R is None else _as(R, np.float32).ravel().copy()
+    t = np.zeros(3, dtype=np.float32) if t is None else _as(t, np.float32).ravel().copy()
+    _check(lib().lsnIcpPointToPlane(_ptr(v1), _ptr(n1), _ptr(v2), len(v1), len(v2), _ptr(R), _ptr(t), int(max_iter)), "lsnIcpPointToPlane")
+    return v2, R.reshape(3, 3), t
+
+
 def refine(clouds, world_R, world_t, n_refine_iters=2, n_icp_iters=10, device=0):
     """refineWorker_DoWork (MainWindowForm.cs:330-410) through lsnRefine.  clouds: list of [n_i, 3] float arrays.
     Returns (clouds_out, world_R [n,3,3], world_t [n,3], Rs [n,3,3], Ts [n,3]); inputs are not modified."""
@@ -517,6 +534,19 @@ def refine_vertices(device, n_sensors, d_vertices, d_offsets, n_refine_iters=2, 
     Rs, Ts = np.zeros(9 * n, dtype=np.float32), np.zeros(3 * n, dtype=np.float32)
     _check(lib().lsnRefineVertices(int(device), n, d_vertices, d_offsets, int(n_refine_iters), int(n_icp_iters), _opt(wR), _opt(wt), _opt(cR),
                                    _opt(ct), _ptr(Rs), _ptr(Ts), d_clouds_out, stream), "lsnRefineVertices")
+    return _shaped(wR, -1, 3, 3), _shaped(wt, -1, 3), _shaped(cR, -1, 3, 3), _shaped(ct, -1, 3), Rs.reshape(-1, 3, 3), Ts.reshape(-1, 3)
+
+
+def refine_vertices_plane(device, n_sensors, d_vertices, d_normals, d_offsets, n_refine_iters=2, n_icp_iters=10, world_R=None, world_t=None,
+                          camera_R=None, camera_t=None, d_clouds_out=None, stream=0):
+    """lsnRefineVerticesPlane: refine_vertices with the point-to-plane residual; d_normals: the tick's vertex normals (one tick of
+    lsnFusionNormals' output, a device pointer as an integer).  Returns what refine_vertices returns."""
+    n = int(n_sensors)
+    wR, wt = _pose_pair(world_R, world_t, n)
+    cR, ct = _pose_pair(camera_R, camera_t, n)
+    Rs, Ts = np.zeros(9 * n, dtype=np.float32), np.zeros(3 * n, dtype=np.float32)
+    _check(lib().lsnRefineVerticesPlane(int(device), n, d_vertices, d_normals, d_offsets, int(n_refine_iters), int(n_icp_iters), _opt(wR), _opt(wt),
+                                        _opt(cR), _opt(ct), _ptr(Rs), _ptr(Ts), d_clouds_out, stream), "lsnRefineVerticesPlane")
     return _shaped(wR, -1, 3, 3), _shaped(wt, -1, 3), _shaped(cR, -1, 3, 3), _shaped(ct, -1, 3), Rs.reshape(-1, 3, 3), Ts.reshape(-1, 3)
 
 
@@ -879,6 +909,11 @@ class IcpWorkspace(_Handle):
     def run(self, d_verts1, n1, d_verts2, n2, d_R, d_t, max_iter=10, nn_mode=NN_GRID, stream=0):
         _check(lib().lsnIcpRun(self._h, d_verts1, int(n1), d_verts2, int(n2), d_R, d_t, int(max_iter), int(nn_mode), stream),
                "lsnIcpRun")
+
+    def run_plane(self, d_verts1, d_normals1, n1, d_verts2, n2, d_R, d_t, max_iter=10, nn_mode=NN_GRID, stream=0):
+        """lsnIcpRunPlane: run() with the point-to-plane residual; d_normals1: the target's normals, n1 x 3 floats on the device."""
+        _check(lib().lsnIcpRunPlane(self._h, d_verts1, d_normals1, int(n1), d_verts2, int(n2), d_R, d_t, int(max_iter), int(nn_mode), stream),
+               "lsnIcpRunPlane")
 
     def nearest(self, d_verts1, n1, d_verts2, n2, d_idx, d_dist2, nn_mode=NN_GRID, stream=0):
         _check(lib().lsnIcpNearest(self._h, d_verts1, int(n1), d_verts2, int(n2), d_idx, d_dist2, int(nn_mode), stream),

@@ -11,7 +11,13 @@
               library, `pairs` times each; reports both medians, each side's run-to-run spread (max - min of the children's medians), the
               baseline's parts, and whether the refined clouds have the same digest on both sides.
 
+  --plane     both refine passes on the SAME resident tick (DeviceFusion: run_mesh -> normals): lsnRefineVertices (point-to-point) and
+              lsnRefineVerticesPlane (point-to-plane), alternating; ms per call and per ICP iteration (a call is refine_iters x S ICP
+              runs of icp_iters iterations, with its copies and the one synchronise), each with its spread, and how far each pass moved
+              the clouds.
+
     python tools/refine_path.py --baseline [repeats] [S w h] [refine_iters icp_iters]
+    python tools/refine_path.py --plane [repeats] [S w h] [refine_iters icp_iters]
     python tools/refine_path.py --onecall [repeats] [S w h] [refine_iters icp_iters]
     python tools/refine_path.py --ab path/to/parent/libNativeUtils.so [pairs] [repeats]
 
@@ -117,6 +123,40 @@ def onecall(repeats, S, w, h, iters):
     print(json.dumps(res))
 
 
+def plane(repeats, S, w, h, iters):
+    import torch
+    from livescan3d_amd.fusion import DeviceFusion
+    rig = _rig(S, w, h)
+    with DeviceFusion.from_rigs([rig]) as fus:
+        fus.run_mesh()
+        normals = fus.normals()
+        torch.cuda.synchronize()
+        total = int(fus.host_offsets()[0, -1])
+        before = fus.vertices[0, :total].view(torch.float32)[:, 1:4].cpu().numpy()
+        out = torch.zeros((total, 3), dtype=torch.float32, device=fus.device)
+        passes = {"point_to_point": lambda: fus.refine(0, *iters, clouds_out=out),
+                  "point_to_plane": lambda: fus.refine_plane(0, normals, *iters, clouds_out=out)}
+        times, moved, digests = {k: [] for k in passes}, {}, {}
+        for rep in range(repeats + 1):
+            for key, call in passes.items():
+                t0 = time.perf_counter()
+                call()
+                dt = time.perf_counter() - t0
+                if rep == 0:
+                    after = out.cpu().numpy()
+                    moved[key], digests[key] = float(np.abs(after - before).max()), synth.digest(after)
+                else:
+                    times[key].append(1e3 * dt)
+        res = {"mode": "plane", "rig": [S, w, h], "iters": list(iters), "repeats": repeats, "points": total,
+               "zero_normals": fus.plan.normals_diagnostics(0)["zero_normals"]}
+        n_iterations = iters[0] * S * iters[1]
+        for key in passes:
+            st = _stats(times[key])
+            res[key] = dict(st, per_iteration_ms=round(st["median_ms"] / n_iterations, 5), moved_max_m=round(moved[key], 6), digest=digests[key])
+        res["kept_bytes"] = native.refine_release(0)
+    print(json.dumps(res))
+
+
 def ab(parent_lib, pairs, repeats):
     runs = {"baseline": [], "onecall": []}
     for i in range(pairs):
@@ -156,7 +196,8 @@ def main():
     repeats = int(args[0]) if args else 5
     S, w, h = (int(x) for x in args[1:4]) if len(args) >= 4 else (8, 512, 424)
     iters = (int(args[4]), int(args[5])) if len(args) >= 6 else (2, 10)
-    return (baseline if "--baseline" in sys.argv else onecall)(repeats, S, w, h, iters)
+    mode = plane if "--plane" in sys.argv else (baseline if "--baseline" in sys.argv else onecall)
+    return mode(repeats, S, w, h, iters)
 
 
 if __name__ == "__main__":
