@@ -8,9 +8,11 @@
 //             (Utils.saveToPly, LiveScanServer/Utils.cs:222-262) = lsnLastMeshPly, written to --ply.  With --lod CELL both go
 //             through the level-of-detail stage first (vertex clustering on a grid of CELL metres: lsnLastMeshTransferFrameLod,
 //             lsnLastMeshPlyLod); without it the output is what it always was.  With --normals the PLY carries vertex normals
-//             (nx, ny, nz between z and red; lsnLastMeshPlyNormals, which takes --lod's CELL as its own argument).
+//             (nx, ny, nz between z and red; lsnLastMeshPlyNormals, which takes --lod's CELL as its own argument).  With
+//             --min-fragment N both go through the fragment filter first (connected components of fewer than N vertices dropped:
+//             lsnLastMeshTransferFrameFragments, lsnLastMeshPlyFragments, which take CELL and the normals switch as arguments).
 //
-//   stream --calib calib.bin [--bounds 6 floats] [--lod CELL] [--normals] [--frames-out f.bin] [--ply mesh.ply] rec0.bin rec1.bin ...
+//   stream --calib calib.bin [--bounds 6 floats] [--min-fragment N] [--lod CELL] [--normals] [--frames-out f.bin] [--ply mesh.ply] rec0.bin rec1.bin ...
 //   calib.bin: per sensor 7 f32 intrinsics + 12 f32 pose (the arrays KinectServer passes, KinectServer.cs:470-490)
 //
 // Build: make -C examples stream   (links -lNativeUtils only)
@@ -47,20 +49,22 @@ int main(int argc, char **argv)
 {
     float b[6] = {-5, -5, -5, 5, 5, 5};   // KinectSettings.cs:54-60
     const char *calib = nullptr, *frames_out = nullptr, *ply = nullptr;
-    bool lod = false, normals = false;
+    bool lod = false, normals = false, fragments = false;
     float cell = 0.0f;
+    int min_fragment = 0;
     std::vector<const char *> recs;
     for (int i = 1; i < argc; i++) {
         if (!strcmp(argv[i], "--calib") && i + 1 < argc) calib = argv[++i];
         else if (!strcmp(argv[i], "--frames-out") && i + 1 < argc) frames_out = argv[++i];
         else if (!strcmp(argv[i], "--ply") && i + 1 < argc) ply = argv[++i];
         else if (!strcmp(argv[i], "--lod") && i + 1 < argc) { lod = true; cell = (float)atof(argv[++i]); }
+        else if (!strcmp(argv[i], "--min-fragment") && i + 1 < argc) { fragments = true; min_fragment = atoi(argv[++i]); }
         else if (!strcmp(argv[i], "--normals")) normals = true;
         else if (!strcmp(argv[i], "--bounds") && i + 6 < argc) { for (int k = 0; k < 6; k++) b[k] = (float)atof(argv[++i]); }
         else recs.push_back(argv[i]);
     }
     const int n = (int)recs.size();
-    if (!calib || n == 0) { fprintf(stderr, "usage: %s --calib calib.bin [--bounds 6 floats] [--lod CELL] [--normals] [--frames-out f.bin] [--ply mesh.ply] rec0.bin ...\n", argv[0]); return 2; }
+    if (!calib || n == 0) { fprintf(stderr, "usage: %s --calib calib.bin [--bounds 6 floats] [--min-fragment N] [--lod CELL] [--normals] [--frames-out f.bin] [--ply mesh.ply] rec0.bin ...\n", argv[0]); return 2; }
     std::vector<unsigned char> cal;
     if (!read_all(calib, cal) || cal.size() != (size_t)n * 19 * 4) { fprintf(stderr, "calib: expected %d x 19 floats\n", n); return 1; }
     std::vector<float> intr(7 * (size_t)n), wt(12 * (size_t)n);
@@ -108,21 +112,30 @@ int main(int argc, char **argv)
         const int nv = mesh.nVertices, nt = mesh.nTriangles;
         deleteMesh(&mesh);
         if (nv == 0) { char e[8]; if (lsnGetLastError(e, sizeof e) > 0) return fail("generateMeshFromDepthMaps"); }
-        const long long bound = lod ? lsnLastMeshTransferFrameLod(cell, nullptr, 0) : lsnLastMeshTransferFrame(nullptr, 0);   // (Lod: an upper bound)
+        const long long bound = fragments ? lsnLastMeshTransferFrameFragments(min_fragment, cell, nullptr, 0)   // (Fragments, Lod: an upper bound)
+                                : lod     ? lsnLastMeshTransferFrameLod(cell, nullptr, 0)
+                                          : lsnLastMeshTransferFrame(nullptr, 0);
         if (bound < 0) return fail("lsnLastMeshTransferFrame");
         wire.resize((size_t)bound);
-        const long long len = lod ? lsnLastMeshTransferFrameLod(cell, wire.data(), bound) : lsnLastMeshTransferFrame(wire.data(), bound);
-        if (len < 0) return fail("lsnLastMeshTransferFrame");
+        const long long len = fragments ? lsnLastMeshTransferFrameFragments(min_fragment, cell, wire.data(), bound)
+                              : lod     ? lsnLastMeshTransferFrameLod(cell, wire.data(), bound)
+                                        : lsnLastMeshTransferFrame(wire.data(), bound);
+        if (len < 0) return fail(fragments ? "lsnLastMeshTransferFrameFragments" : "lsnLastMeshTransferFrame");
         if (fo) fwrite(wire.data(), 1, (size_t)len, fo);
         sent += len;
         printf("tick %d: %d vertices, %d triangles -> %lld bytes on the wire\n", ticks, nv, nt, len);
     }
     if (fo) fclose(fo);
     if (ply && ticks > 0) {
-        long long need = normals ? lsnLastMeshPlyNormals(cell, nullptr, 0) : lod ? lsnLastMeshPlyLod(cell, nullptr, 0) : lsnLastMeshPly(nullptr, 0);
-        if (need < 0) return fail(normals ? "lsnLastMeshPlyNormals" : "lsnLastMeshPly");
+        long long need = fragments ? lsnLastMeshPlyFragments(min_fragment, cell, normals, nullptr, 0)
+                         : normals ? lsnLastMeshPlyNormals(cell, nullptr, 0)
+                         : lod     ? lsnLastMeshPlyLod(cell, nullptr, 0)
+                                   : lsnLastMeshPly(nullptr, 0);
+        if (need < 0) return fail(fragments ? "lsnLastMeshPlyFragments" : normals ? "lsnLastMeshPlyNormals" : "lsnLastMeshPly");
         wire.resize((size_t)need);
-        if (normals) {
+        if (fragments) {
+            if ((need = lsnLastMeshPlyFragments(min_fragment, cell, normals, wire.data(), need)) < 0) return fail("lsnLastMeshPlyFragments");
+        } else if (normals) {
             if ((need = lsnLastMeshPlyNormals(cell, wire.data(), need)) < 0) return fail("lsnLastMeshPlyNormals");
         } else if (lod) {
             if ((need = lsnLastMeshPlyLod(cell, wire.data(), need)) < 0) return fail("lsnLastMeshPlyLod");

@@ -376,6 +376,42 @@ int lsnFusionSimplify(LsnFusion *plan, float cell, const void *d_vertices, const
                       int *d_remap_out, void *stream);
 int lsnFusionSimplifyDiagnostics(LsnFusion *plan, int tick, int *n_cells, int *n_unclustered, int *n_dropped_triangles, void *stream);
 
+/* Fragment filter: the small connected components of the merged mesh of every tick (what lsnFusionRunMesh or any stage above left in
+ * d_vertices / d_offsets / d_triangles / d_tri_offsets, read only) are dropped, in front of the packers, the renderer, the level of detail
+ * and the normals.  The reference has no such step: the stage is defined here (tests/fragments_ref.py restates it).
+ * Only minima and integer counts: the bytes do not depend on the order in which the device takes the triangles.  Per tick, on its own:
+ * Counts: nVertices = d_offsets[n_maps] clipped to [0, lsnFusionTickCapacity()], nTriangles = d_tri_offsets[n_maps] clipped to [0,
+ * lsnFusionTickTriangleCapacity()].
+ * Graph: a triangle is VALID iff its three indices are in [0, nVertices), compared unsigned.  A valid triangle (i0, i1, i2) joins i0-i1
+ * and i1-i2 (i0-i2 follows).  A repeated index is fine: (2, 2, 3) joins 2 and 3, (4, 4, 4) joins nothing.  An invalid triangle joins
+ * nothing.  Positions play no part.
+ * Label: label[v] = the LOWEST vertex index of v's connected component; a vertex of no valid triangle is a component of one, label[v] = v.
+ * Size: the size of a component is the number of vertices that carry its label.
+ * Kept: a vertex is kept iff size[label[v]] >= min_vertices.
+ * Vertices out: the kept vertices in ascending input index with their own 16 bytes; d_offsets_out[i] = the kept vertices of input index
+ * below d_offsets[i], i = 0..n_maps; d_remap_out[j] (nullable) = the output index of a kept vertex, -1 for a removed one; d_labels_out[j]
+ * (nullable) = the label, an input index, for every j < nVertices (both lsnFusionTickCapacity() ints per tick).
+ * Triangles out: a valid triangle whose component is kept is remapped (its three vertices share one fate) and stays in its input order,
+ * degenerate ones too; invalid triangles and triangles of removed components are dropped; d_tri_offsets_out[i] = the survivors of input
+ * position below d_tri_offsets[i].
+ * Off: min_vertices <= 1 copies the counted vertices, the counted triangles (invalid ones too) and both offset rows as they are; the
+ * remap is the identity, the labels are NOT written, all four diagnostics are 0.
+ * Refused, with a message and no output touched: a null argument; d_triangles == NULL (the components of a bare point cloud are not
+ * defined here); an output that overlaps an input.
+ * Idempotent: the output filtered again with the same min_vertices is the same bytes.
+ * Outputs have lsnFusionRunMesh's layouts and per-tick strides; nothing behind a tick's new counts is written.  Asynchronous on `stream`;
+ * returns 0, -1 with a message.
+ * Scratch, the plan's own, reserved by the first call, grown when a later call needs more, freed with the plan (a plan that never
+ * filters has none): 12 bytes x lsnFusionTickCapacity() per tick (parent / label, size, output index; 4 of them while min_vertices <= 1),
+ * 4 bytes per 256 vertices and per 256 triangles, 16 bytes of counters per tick: 8 x 512x424 sensors, one tick = 20.8 + 0.1 MB.
+ * lsnFusionFragmentsDiagnostics (synchronises `stream`): for one tick of the plan's last call the components, the removed components,
+ * the removed vertices and the dropped triangles (in minus out); any pointer may be NULL.  Returns 0, -1 on error or before any call. */
+int lsnFusionFragments(LsnFusion *plan, int min_vertices, const void *d_vertices, const int *d_offsets, const void *d_triangles,
+                       const int *d_tri_offsets, void *d_vertices_out, int *d_offsets_out, void *d_triangles_out, int *d_tri_offsets_out,
+                       int *d_remap_out, int *d_labels_out, void *stream);
+int lsnFusionFragmentsDiagnostics(LsnFusion *plan, int tick, int *n_components, int *n_removed_components, int *n_removed_vertices,
+                                  int *n_dropped_triangles, void *stream);
+
 /* Vertex normals of the merged mesh of every tick (what lsnFusionRunMesh and the stages above -- overlay merge, outlier filter, level of
  * detail -- left in d_vertices / d_offsets / d_triangles / d_tri_offsets, read only): area weighted, bit-exact whatever order the device
  * takes the triangles in.  The reference computes no normals: the stage is defined here (tests/normals_ref.py
@@ -737,6 +773,14 @@ long long lsnLastMeshPlyLod(float cell, unsigned char *out, long long out_cap);
  * from there.  out == NULL: the length for the unsimplified mesh, an upper bound.  A mesh without triangles: -1 with a message.  The
  * resident mesh is not changed. */
 long long lsnLastMeshPlyNormals(float cell, unsigned char *out, long long out_cap);
+/* The outbound formats through the fragment filter: the same mesh goes through lsnFusionFragments' stage with `min_vertices`, then through
+ * the level-of-detail stage if cell > 0, then (with_normals != 0) through lsnFusionNormals' stage, each on what the step before left, as
+ * one tick of one sensor, in HBM, and is packed from there.  out == NULL: the length for the unfiltered mesh, an upper bound.
+ * min_vertices <= 1 together with cell <= 0 (or NaN): byte for byte what the plain calls return.  A mesh that loses everything leaves as
+ * the packers' bytes for (0, 0).  A resident mesh without triangles: -1 with a message when min_vertices > 1 or with_normals != 0.  The
+ * resident mesh is not changed. */
+long long lsnLastMeshTransferFrameFragments(int min_vertices, float cell, unsigned char *out, long long out_cap);
+long long lsnLastMeshPlyFragments(int min_vertices, float cell, int with_normals, unsigned char *out, long long out_cap);
 
 /* Inbound (host-side parsing, no device work): the client's frame message -- LiveScanClient::SerializeFrame
  * (src/LiveScanClient/liveScanClient.cpp:185-290) as KinectSocket.ReceiveFrame reads it

@@ -557,8 +557,8 @@ extern "C" int lsnIcpPointToPlane(Point3f *verts1, Point3f *normals1, Point3f *v
 namespace {
 // The exports below as steps on the mesh the calling thread's last mesh call left: the lane is picked and locked here; `resident` says
 // whether there is a mesh (from then on nv / nt are its counts, and a call that only asks for a length is answered); `open` puts it into
-// HBM and makes it a batch of one tick of one "sensor" whose offset rows are its two counts; `lod` and `normals` run their stage on what
-// the step before left, `render`, `frame` and `ply` bring the result home.  Locks: the lane's, then c.wire_mu from `open` on.
+// HBM and makes it a batch of one tick of one "sensor" whose offset rows are its two counts; `fragments`, `lod` and `normals` run their
+// stage on what the step before left, `render`, `frame` and `ply` bring the result home.  Locks: the lane's, then c.wire_mu from `open` on.
 struct LastMesh {
     Ctx &c;
     Lane &l;
@@ -609,7 +609,8 @@ struct LastMesh {
     int lod(const char *who, float cell)
     {
         if (nv <= 0) return 0;
-        if (c.d_lod_v.reserve(16 * (size_t)nv) || c.d_lod_t.reserve(12 * (size_t)(nt > 0 ? nt : 1))) return -1;
+        // (the batch's strides, which the stage's overlap test measures with: the fragment filter may have left fewer than nv0 / nt0)
+        if (c.d_lod_v.reserve(16 * (size_t)nv0) || c.d_lod_t.reserve(12 * (size_t)(nt0 > 0 ? nt0 : 1))) return -1;
         int *out_rows = c.d_mesh_rows.as<int>() + 4;
         if (lsn::simplify(c.sp, who, batch(), cell, c.d_lod_v.p, out_rows, c.d_lod_t.p, out_rows + 2, nullptr, l.stream)) return -1;
         LSN_HIP(hipMemcpyAsync(c.mesh_rows + 4, out_rows, 4 * sizeof(int), hipMemcpyDeviceToHost, l.stream));
@@ -618,6 +619,23 @@ struct LastMesh {
         if (nt > 0) nt = c.mesh_rows[7];
         d_v = c.d_lod_v.p;
         d_t = c.d_lod_t.as<int>();
+        d_rows = out_rows;
+        return 0;
+    }
+    // the fragment filter (fragments.hip), in HBM, in front of `lod`: the later steps see the filtered mesh and the rows the stage wrote.
+    // min_vertices <= 1 is the stage's "off", a copy: the mesh stays where it is.
+    int fragments(const char *who, int min_vertices)
+    {
+        if (min_vertices <= 1 || nv <= 0) return 0;
+        if (c.d_frag_v.reserve(16 * (size_t)nv) || c.d_frag_t.reserve(12 * (size_t)(nt > 0 ? nt : 1))) return -1;
+        int *out_rows = c.d_mesh_rows.as<int>() + 8;
+        if (lsn::fragments(c.fr, who, batch(), min_vertices, c.d_frag_v.p, out_rows, c.d_frag_t.p, out_rows + 2, nullptr, nullptr, l.stream)) return -1;
+        LSN_HIP(hipMemcpyAsync(c.mesh_rows + 8, out_rows, 4 * sizeof(int), hipMemcpyDeviceToHost, l.stream));
+        LSN_HIP(hipStreamSynchronize(l.stream));
+        nv = c.mesh_rows[9];
+        nt = c.mesh_rows[11];
+        d_v = c.d_frag_v.p;
+        d_t = c.d_frag_t.as<int>();
         d_rows = out_rows;
         return 0;
     }
@@ -749,6 +767,44 @@ extern "C" long long lsnLastMeshPlyNormals(float cell, unsigned char *out, long 
         if (!out) return bound;
         if (m.open(bound) || (cell > 0.0f && m.lod("lsnLastMeshPlyNormals", cell)) || m.normals("lsnLastMeshPlyNormals")) return -1;
         return m.ply(bound, true, out, out_cap);
+    });
+}
+
+// The outbound formats through the fragment filter (fragments.hip) with `min_vertices`, then the level of detail if cell > 0, then the
+// normals if asked: open, fragments, lod, normals, pack.  out == NULL: the length of the unfiltered mesh, an upper bound.  min_vertices
+// <= 1 with cell <= 0: the plain exports' bytes.  A resident mesh without triangles is refused when min_vertices > 1 (fragments.hip
+// defines no components for a bare point cloud), and always with normals.
+extern "C" long long lsnLastMeshTransferFrameFragments(int min_vertices, float cell, unsigned char *out, long long out_cap)
+{
+    return lsn::guarded("lsnLastMeshTransferFrameFragments", -1LL, [&]() -> long long {
+        lsn::clear_error();
+        LastMesh m;
+        if (m.resident()) return -1;
+        const long long bound = std::max(lsnTransferFrameBound(m.nv, m.nt), lsnTransferFrameBound(m.nv, 0));
+        if (!out) return bound;
+        if (m.open(bound) || m.fragments("lsnLastMeshTransferFrameFragments", min_vertices) ||
+            (cell > 0.0f && m.lod("lsnLastMeshTransferFrameFragments", cell)))
+            return -1;
+        return m.frame(bound, out, out_cap);
+    });
+}
+
+extern "C" long long lsnLastMeshPlyFragments(int min_vertices, float cell, int with_normals, unsigned char *out, long long out_cap)
+{
+    return lsn::guarded("lsnLastMeshPlyFragments", -1LL, [&]() -> long long {
+        lsn::clear_error();
+        LastMesh m;
+        if (m.resident()) return -1;
+        if (with_normals && m.nt <= 0) {
+            lsn::set_error("lsnLastMeshPlyFragments: the resident mesh has no triangles (the normals of a bare point cloud are not defined)");
+            return -1;
+        }
+        const long long bound = with_normals ? lsnPlyNormalsBytes(m.nv, m.nt) : lsnPlyBinaryBytes(m.nv, m.nt);
+        if (!out) return bound;
+        if (m.open(bound) || m.fragments("lsnLastMeshPlyFragments", min_vertices) || (cell > 0.0f && m.lod("lsnLastMeshPlyFragments", cell)) ||
+            (with_normals && m.normals("lsnLastMeshPlyFragments")))
+            return -1;
+        return m.ply(bound, with_normals != 0, out, out_cap);
     });
 }
 

@@ -608,6 +608,7 @@ struct LsnFusion {
     // the three stages on the merged mesh (render.hip, simplify.hip, normals.hip): each one's scratch, allocated on its first call
     lsn::RenderScratch rv;
     lsn::SimplifyScratch sp;
+    lsn::FragmentsScratch fr;            // (fragments.hip: the fourth stage on the merged mesh)
     lsn::NormalsScratch nm;
     bool thr_valid = false;
     bool thr_enabled = true;             // $LSN_NO_THRESHOLDS=1 keeps the arithmetic count pass (ablation / tests)

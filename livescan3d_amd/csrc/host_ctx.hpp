@@ -158,13 +158,15 @@ struct Ctx {
     int xfer_v = 0, xfer_t = 0;
     lsn::DevBuf d_wire;
     // the steps of lsnLastMesh* (abi.hip LastMesh; under wire_mu too): the mesh's two counts as offset rows {0, nVertices}, {0, nTriangles}
-    // and behind them the rows the level of detail writes; the stages' scratch; the simplified mesh, its normals, the rendered image
+    // and behind them the rows the level of detail writes, then the rows the fragment filter writes; the stages' scratch; the simplified
+    // mesh, the filtered mesh, the normals, the rendered image
     lsn::DevBuf d_mesh_rows;
-    int mesh_rows[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    int mesh_rows[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     lsn::RenderScratch rv;
     lsn::SimplifyScratch sp;
+    lsn::FragmentsScratch fr;
     lsn::NormalsScratch nm;
-    lsn::DevBuf d_lod_v, d_lod_t, d_nm, d_rv_img;
+    lsn::DevBuf d_lod_v, d_lod_t, d_frag_v, d_frag_t, d_nm, d_rv_img;
     bool warned_flags = false;
 };
 

@@ -186,6 +186,20 @@ int simplify(SimplifyScratch &ss, const char *who, const MeshBatch &m, float cel
              int *d_tri_offsets_out, int *d_remap_out, hipStream_t s);
 int simplify_counts(SimplifyScratch &ss, const char *who, int tick, int *n_cells, int *n_unclustered, int *n_dropped_triangles, hipStream_t s);
 
+// The fragment filter (fragments.hip): what one filter keeps between calls -- the parent / label array, the sizes (at the label's index)
+// and the output index, each [n_ticks][vertices per tick] ints, the per-256 counts of kept vertices and triangles, the counters behind
+// lsnFusionFragmentsDiagnostics.  Reserved by the first call, grown by a call that needs more; min_vertices <= 1 reserves neither the
+// parents nor the sizes.
+struct FragmentsScratch {
+    DevBuf parent, size, newidx, tiles;
+    StageCounters cnt;                // per tick
+};
+// d_remap_out, d_labels_out: nullable; a batch without triangles is refused.
+int fragments(FragmentsScratch &fs, const char *who, const MeshBatch &m, int min_vertices, void *d_vertices_out, int *d_offsets_out,
+              void *d_triangles_out, int *d_tri_offsets_out, int *d_remap_out, int *d_labels_out, hipStream_t s);
+int fragments_counts(FragmentsScratch &fs, const char *who, int tick, int *n_components, int *n_removed_components, int *n_removed_vertices,
+                     int *n_dropped_triangles, hipStream_t s);
+
 // Vertex normals (normals.hip): what one stage keeps between calls -- the sums, three planes [n_ticks][3][vertices per tick] of i64 (24 B
 // per vertex; the counted vertices are cleared by every call), and the counters behind lsnFusionNormalsDiagnostics.  Reserved by the
 // first call, grown by a call that needs more.

@@ -619,5 +619,7 @@ int lsn::run_triangles_write(LsnFusion *p, const void *d_depth, void *d_triangle
 #include "render.hip"
 // Mesh level of detail (lsnFusionSimplify): vertex clustering of the merged mesh, in front of the packers and the renderer.
 #include "simplify.hip"
+// The fragment filter (lsnFusionFragments): the small connected components of the merged mesh dropped, in front of the same consumers.
+#include "fragments.hip"
 // Vertex normals (lsnFusionNormals): area-weighted, summed as 64-bit integers, of the mesh as any of the stages above left it.
 #include "normals.hip"

@@ -1,6 +1,7 @@
 // mesh_batch.hip -- what the three stages on the merged mesh (render.hip, simplify.hip, normals.hip) share: the batch they read
 // (lsn::MeshBatch) with its clipped counts, its check and the out-of-place test, the counters behind their diagnostics
-// (lsn::StageCounters), the form of their six plan exports.  A stage checks null arguments, its own limits, the batch, the overlap.
+// (lsn::StageCounters), the form of their plan exports, and the ordered compaction of triangles and offset rows that simplify.hip and
+// fragments.hip share (compact_tri_kernel, compact_offsets_kernel).  A stage checks null arguments, its own limits, the batch, the overlap.
 // Compiled as part of mesh.hip's translation unit (the include at its end, ahead of the three stages), not on its own.
 #include "fusion_shared.hpp"
 
@@ -61,6 +62,67 @@ int plan_export(const char *name, LsnFusion *p, F &&body)
         LSN_HIP(hipSetDevice(p->device));
         return body();
     });
+}
+
+// ---- the ordered compaction of a tick's triangles and of its two offset rows, shared by the stages that drop vertices (simplify.hip,
+// fragments.hip).  A stage's argument block A has voff / tri / toff / tri_out / voff_out / toff_out, vtile / ttile ([n_ticks][nvb + 1],
+// [n_ticks][ntb + 1]: kept per 256, then their exclusive prefixes with the total last), n, identity, nvb, ntb, tick_vert, tick_tri, and
+// the stage says what is kept through three functions found by their argument:
+//   bool compact_triangle(const A &, tick, t, nv, i1, i2, i3)   the triangle at position t < nt through the remap; false: dropped
+//   bool compact_vertex_kept(const A &, tick, e)                vertex e < nv leaves
+//   void compact_totals(const A &, tick, tri, count, kept)      entry n of a row (tri: the triangles') is written: the stage's counters
+constexpr int kCompactThreads = 256;
+
+template <class A, int WRITE>
+__global__ __launch_bounds__(kCompactThreads) void compact_tri_kernel(A a)
+{
+    __shared__ int s_wave[kCompactThreads / 64];
+    const int tick = blockIdx.y;
+    const int nv = mesh_count(a.voff, tick, a.n, a.tick_vert), nt = mesh_count(a.toff, tick, a.n, a.tick_tri);
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    int i1 = 0, i2 = 0, i3 = 0;
+    const bool kept = t < nt && compact_triangle(a, tick, t, nv, i1, i2, i3);
+    int total;
+    const int rank = block_rank<kCompactThreads / 64>(kept, s_wave, total);
+    if (!WRITE) {
+        if (threadIdx.x == 0) a.ttile[tick * (a.ntb + 1) + blockIdx.x] = total;
+    } else if (kept) {   // prefix + rank < surviving triangles of the tick <= nt
+        int *o = a.tri_out + 3 * (tick * a.tick_tri + a.ttile[tick * (a.ntb + 1) + blockIdx.x] + rank);
+        o[0] = i1; o[1] = i2; o[2] = i3;
+    }
+}
+
+// The offset rows, one workgroup per (entry, tick): out[i] = the kept elements below in[i] -- the prefix of in[i]'s tile plus the kept
+// ones of that tile in front of it.
+template <class A, bool TRI>
+__global__ __launch_bounds__(kCompactThreads) void compact_offsets_kernel(A a)
+{
+    __shared__ int s_wave[kCompactThreads / 64];
+    const int tick = blockIdx.y, i = blockIdx.x;
+    const int nv = mesh_count(a.voff, tick, a.n, a.tick_vert);
+    const int count = TRI ? mesh_count(a.toff, tick, a.n, a.tick_tri) : nv;
+    const int *tile = TRI ? a.ttile + tick * (a.ntb + 1) : a.vtile + tick * (a.nvb + 1);
+    const int nb = TRI ? a.ntb : a.nvb;
+    const int in = (TRI ? a.toff : a.voff)[tick * (a.n + 1) + i];
+    const int j = min(max(in, 0), count);
+    const int b = min(j / kCompactThreads, nb);      // tile[nb] is the total; j == count may lie there
+    const int e = b * kCompactThreads + threadIdx.x;
+    bool kept = false;
+    if (e < j) {
+        if (TRI) {
+            int i1, i2, i3;
+            kept = compact_triangle(a, tick, e, nv, i1, i2, i3);
+        } else {
+            kept = compact_vertex_kept(a, tick, e);
+        }
+    }
+    int total;
+    (void)block_rank<kCompactThreads / 64>(kept, s_wave, total);
+    if (threadIdx.x == 0) {
+        const int below = tile[b] + total;
+        (TRI ? a.toff_out : a.voff_out)[tick * (a.n + 1) + i] = a.identity ? in : below;
+        if (i == a.n) compact_totals(a, tick, TRI, count, tile[nb]);
+    }
 }
 
 }  // namespace

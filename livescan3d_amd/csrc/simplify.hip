@@ -17,9 +17,10 @@
 //   3. ordered compaction in the project's multi-launch form: the per-tile counts of 2, their exclusive scan (ct_block_scan_kernel, one
 //      workgroup per tick), then
 //   4. write (sp_write_kernel): the kept vertices, 16 bytes per lane, to tile prefix + rank inside the tile, which also goes into `newidx`;
-//      sp_offsets_kernel<false> counts the kept vertices below every entry of the offset row; sp_remap_kernel (a launch behind the write)
-//      turns rep into remap = newidx[rep].
-//   5. triangles: sp_tri_kernel<0> (remap, flag, count per tile), the scan, sp_tri_kernel<1> (write), sp_offsets_kernel<true>.
+//      compact_offsets_kernel<.., false> counts the kept vertices below every entry of the offset row; sp_remap_kernel (a launch behind
+//      the write) turns rep into remap = newidx[rep].
+//   5. triangles: compact_tri_kernel<.., 0> (remap, flag, count per tile), the scan, compact_tri_kernel<.., 1> (write),
+//      compact_offsets_kernel<.., true> -- the two kernels are mesh_batch.hip's, shared with fragments.hip.
 //
 // cell <= 0 or NaN: the same launches with every vertex and every triangle kept and the offset rows copied as they are.
 // No kernel waits for another workgroup; every loop is bounded by a size the host passes.  Plain vector stores and HIP atomics only.
@@ -163,59 +164,14 @@ __device__ __forceinline__ bool sp_triangle(const SpArgs &a, int tick, int t, in
     return i1 != i2 && i2 != i3 && i1 != i3;
 }
 
-template <int WRITE>
-__global__ __launch_bounds__(kSpThreads) void sp_tri_kernel(SpArgs a)
+// What compact_tri_kernel / compact_offsets_kernel (mesh_batch.hip) ask of the stage.
+__device__ __forceinline__ bool compact_triangle(const SpArgs &a, int tick, int t, int nv, int &i1, int &i2, int &i3) { return sp_triangle(a, tick, t, nv, i1, i2, i3); }
+// (queued in front of sp_remap_kernel: rep still names representatives)
+__device__ __forceinline__ bool compact_vertex_kept(const SpArgs &a, int tick, int e) { return a.rep[tick * a.tick_vert + e] == e; }
+__device__ __forceinline__ void compact_totals(const SpArgs &a, int tick, bool tri, int count, int kept)
 {
-    __shared__ int s_wave[kSpThreads / 64];
-    const int tick = blockIdx.y;
-    const int nv = mesh_count(a.voff, tick, a.n, a.tick_vert), nt = mesh_count(a.toff, tick, a.n, a.tick_tri);
-    const int t = blockIdx.x * blockDim.x + threadIdx.x;
-    int i1 = 0, i2 = 0, i3 = 0;
-    const bool kept = t < nt && sp_triangle(a, tick, t, nv, i1, i2, i3);
-    int total;
-    const int rank = block_rank<kSpThreads / 64>(kept, s_wave, total);
-    if (!WRITE) {
-        if (threadIdx.x == 0) a.ttile[tick * (a.ntb + 1) + blockIdx.x] = total;
-    } else if (kept) {   // prefix + rank < surviving triangles of the tick <= nt
-        int *o = a.tri_out + 3 * (tick * a.tick_tri + a.ttile[tick * (a.ntb + 1) + blockIdx.x] + rank);
-        o[0] = i1; o[1] = i2; o[2] = i3;
-    }
-}
-
-// ---- the offset rows: one workgroup per (entry, tick) -------------------------------------------------------------------------------
-// out[i] = the kept elements below in[i]: the prefix of in[i]'s tile plus the kept ones of that tile in front of it.
-template <bool TRI>
-__global__ __launch_bounds__(kSpThreads) void sp_offsets_kernel(SpArgs a)
-{
-    __shared__ int s_wave[kSpThreads / 64];
-    const int tick = blockIdx.y, i = blockIdx.x;
-    const int nv = mesh_count(a.voff, tick, a.n, a.tick_vert);
-    const int count = TRI ? mesh_count(a.toff, tick, a.n, a.tick_tri) : nv;
-    const int *tile = TRI ? a.ttile + tick * (a.ntb + 1) : a.vtile + tick * (a.nvb + 1);
-    const int nb = TRI ? a.ntb : a.nvb;
-    const int in = (TRI ? a.toff : a.voff)[tick * (a.n + 1) + i];
-    const int j = min(max(in, 0), count);
-    const int b = min(j / kSpThreads, nb);      // tile[nb] is the total; j == count may lie there
-    const int e = b * kSpThreads + threadIdx.x;
-    bool kept = false;
-    if (e < j) {
-        if (TRI) {
-            int i1, i2, i3;
-            kept = sp_triangle(a, tick, e, nv, i1, i2, i3);
-        } else {
-            kept = a.rep[tick * a.tick_vert + e] == e;   // queued in front of sp_remap_kernel: rep still names representatives
-        }
-    }
-    int total;
-    (void)block_rank<kSpThreads / 64>(kept, s_wave, total);
-    if (threadIdx.x == 0) {
-        const int below = tile[b] + total;
-        (TRI ? a.toff_out : a.voff_out)[tick * (a.n + 1) + i] = a.identity ? in : below;
-        if (i == a.n) {
-            a.cnt[tick * 4 + (TRI ? 2 : 1)] = tile[nb];
-            if (TRI) a.cnt[tick * 4 + 3] = count;
-        }
-    }
+    a.cnt[tick * 4 + (tri ? 2 : 1)] = kept;
+    if (tri) a.cnt[tick * 4 + 3] = count;
 }
 
 }  // namespace
@@ -282,13 +238,13 @@ int simplify(SimplifyScratch &ss, const char *who, const MeshBatch &m, float cel
     hipLaunchKernelGGL(sp_rep_kernel, vgrid, block, 0, s, a);
     hipLaunchKernelGGL(ct_block_scan_kernel, dim3(n_ticks), dim3(1024), 0, s, a.vtile, nvb + 1);
     hipLaunchKernelGGL(sp_write_kernel, vgrid, block, 0, s, a);
-    hipLaunchKernelGGL(sp_offsets_kernel<false>, ogrid, block, 0, s, a);
+    hipLaunchKernelGGL((compact_offsets_kernel<SpArgs, false>), ogrid, block, 0, s, a);
     hipLaunchKernelGGL(sp_remap_kernel, vgrid, block, 0, s, a);
     if (!points) {
-        hipLaunchKernelGGL(sp_tri_kernel<0>, tgrid, block, 0, s, a);
+        hipLaunchKernelGGL((compact_tri_kernel<SpArgs, 0>), tgrid, block, 0, s, a);
         hipLaunchKernelGGL(ct_block_scan_kernel, dim3(n_ticks), dim3(1024), 0, s, a.ttile, ntb + 1);
-        hipLaunchKernelGGL(sp_tri_kernel<1>, tgrid, block, 0, s, a);
-        hipLaunchKernelGGL(sp_offsets_kernel<true>, ogrid, block, 0, s, a);
+        hipLaunchKernelGGL((compact_tri_kernel<SpArgs, 1>), tgrid, block, 0, s, a);
+        hipLaunchKernelGGL((compact_offsets_kernel<SpArgs, true>), ogrid, block, 0, s, a);
     }
     LSN_HIP(hipGetLastError());
     ss.cnt.finish(n_ticks);

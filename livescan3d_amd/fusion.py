@@ -135,6 +135,21 @@ class DeviceFusion:
                            _stream_handle(stream))
         return vertices, offsets, triangles, tri_offsets, remap
 
+    def fragments(self, min_vertices, stream=None):
+        """Fragment filter: the connected components of fewer than `min_vertices` vertices of the ticks' meshes dropped.  Returns fresh
+        tensors (vertices uint8 [T, capacity, 16], offsets int32 [T, N+1], triangles int32 [T, 2*capacity, 3], tri_offsets, remap int32
+        [T, capacity], labels int32 [T, capacity]); the offset tables are prefilled with SENTINEL."""
+        vertices = torch.zeros_like(self.vertices)
+        offsets = torch.full_like(self.offsets, SENTINEL)
+        triangles = torch.zeros_like(self.triangles)
+        tri_offsets = torch.full_like(self.tri_offsets, SENTINEL)
+        remap = torch.zeros((self.n_ticks, self.capacity), dtype=torch.int32, device=self.device)
+        labels = torch.zeros((self.n_ticks, self.capacity), dtype=torch.int32, device=self.device)
+        self.plan.fragments(min_vertices, self.vertices.data_ptr(), self.offsets.data_ptr(), self.triangles.data_ptr(),
+                            self.tri_offsets.data_ptr(), vertices.data_ptr(), offsets.data_ptr(), triangles.data_ptr(), tri_offsets.data_ptr(),
+                            remap.data_ptr(), labels.data_ptr(), _stream_handle(stream))
+        return vertices, offsets, triangles, tri_offsets, remap, labels
+
     def normals(self, vertices=None, offsets=None, triangles=None, tri_offsets=None, stream=None):
         """Vertex normals of the ticks' meshes -- the batch's own, or the four tensors handed in (simplify()'s first four outputs, say).
         Returns float32 [T, capacity, 3], the batch's own tensor (allocated by the first call with every byte SENTINEL % 256, written again

@@ -95,6 +95,8 @@ _PROTOTYPES = {
     "lsnFusionRenderDiagnostics": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp]),
     "lsnFusionSimplify": (_i, [_vp, _f] + [_vp] * 10),
     "lsnFusionSimplifyDiagnostics": (_i, [_vp, _i, _vp, _vp, _vp, _vp]),
+    "lsnFusionFragments": (_i, [_vp, _i] + [_vp] * 11),
+    "lsnFusionFragmentsDiagnostics": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp]),
     "lsnFusionNormals": (_i, [_vp] * 7),
     "lsnFusionNormalsDiagnostics": (_i, [_vp, _i, _vp, _vp, _vp, _vp]),
     "lsnFusionTilesPerTick": (_i, [_vp]),
@@ -159,6 +161,8 @@ _PROTOTYPES = {
     "lsnLastMeshTransferFrameLod": (_ll, [_f, _vp, _ll]),
     "lsnLastMeshPlyLod": (_ll, [_f, _vp, _ll]),
     "lsnLastMeshPlyNormals": (_ll, [_f, _vp, _ll]),
+    "lsnLastMeshTransferFrameFragments": (_ll, [_i, _f, _vp, _ll]),
+    "lsnLastMeshPlyFragments": (_ll, [_i, _f, _i, _vp, _ll]),
     "lsnZstdAvailable": (_i, []),
     "lsnFrameParseHeader": (_i, [_vp, C.POINTER(FrameInfo)]),
     "lsnFrameDecode": (_ll, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _i, C.POINTER(_i)]),
@@ -731,6 +735,23 @@ class FusionPlan(_Handle):
                "lsnFusionSimplifyDiagnostics")
         return {"cells": c.value, "unclustered": u.value, "dropped_triangles": d.value}
 
+    def fragments(self, min_vertices, d_vertices, d_offsets, d_triangles, d_tri_offsets, d_vertices_out, d_offsets_out, d_triangles_out,
+                  d_tri_offsets_out, d_remap_out=0, d_labels_out=0, stream=0):
+        """Fragment filter: the connected components of fewer than `min_vertices` vertices of every tick's merged mesh dropped, into the
+        out buffers (run_mesh's layouts; d_remap_out, d_labels_out: capacity ints per tick, optional).  Out of place; min_vertices <= 1
+        copies; a mesh without triangles (d_triangles 0) is refused."""
+        _check(lib().lsnFusionFragments(self._h, int(min_vertices), d_vertices, d_offsets, d_triangles or None, d_tri_offsets or None,
+                                        d_vertices_out or None, d_offsets_out or None, d_triangles_out or None, d_tri_offsets_out or None,
+                                        d_remap_out or None, d_labels_out or None, stream or None), "lsnFusionFragments")
+
+    def fragments_diagnostics(self, tick=0, stream=0):
+        """The last fragments() of one tick: {"components", "removed_components", "removed_vertices", "dropped_triangles": triangles in
+        minus triangles out}; all 0 after min_vertices <= 1."""
+        c, r, v, d = C.c_int(0), C.c_int(0), C.c_int(0), C.c_int(0)
+        _check(lib().lsnFusionFragmentsDiagnostics(self._h, int(tick), C.byref(c), C.byref(r), C.byref(v), C.byref(d), stream or None),
+               "lsnFusionFragmentsDiagnostics")
+        return {"components": c.value, "removed_components": r.value, "removed_vertices": v.value, "dropped_triangles": d.value}
+
     def normals(self, d_vertices, d_offsets, d_triangles, d_tri_offsets, d_normals_out, stream=0):
         """Vertex normals of every tick's merged mesh (run_mesh's layouts) into d_normals_out, float32 [n_ticks, capacity, 3]: area
         weighted, summed as 64-bit integers, so bit-exact in any order.  Out of place; a mesh without triangles (d_triangles 0) is refused."""
@@ -1022,6 +1043,20 @@ def last_mesh_ply_normals(cell=0.0):
     (<= 0: as it is).  A mesh without triangles is an error."""
     fn = lib().lsnLastMeshPlyNormals
     return _last_mesh(lambda out, cap: fn(float(cell), out, cap), "lsnLastMeshPlyNormals")
+
+
+def last_mesh_transfer_frame_fragments(min_vertices, cell=0.0):
+    """lsnLastMeshTransferFrameFragments: the SendFrame stream of that mesh after the fragment filter with `min_vertices` (<= 1: off), then
+    vertex clustering with cell size `cell` (<= 0: off)."""
+    fn = lib().lsnLastMeshTransferFrameFragments
+    return _last_mesh(lambda out, cap: fn(int(min_vertices), float(cell), out, cap), "lsnLastMeshTransferFrameFragments")
+
+
+def last_mesh_ply_fragments(min_vertices, cell=0.0, with_normals=False):
+    """lsnLastMeshPlyFragments: the binary PLY file image of that mesh after the fragment filter with `min_vertices` (<= 1: off), then
+    vertex clustering with cell size `cell` (<= 0: off), with vertex normals if asked."""
+    fn = lib().lsnLastMeshPlyFragments
+    return _last_mesh(lambda out, cap: fn(int(min_vertices), float(cell), 1 if with_normals else 0, out, cap), "lsnLastMeshPlyFragments")
 
 
 def last_mesh_render_view(intr7, wt12, width, height, points_only=False):
