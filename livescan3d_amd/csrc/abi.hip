@@ -385,7 +385,7 @@ extern "C" void depthMapAndColorSetRadialCorrection(int n_maps, unsigned char *d
 
 // LiveScanServer's "Refine calibration" as one call: the frames go up once, the clouds never leave the device.  The fusion runs on the
 // single-sensor lane -- the refine worker's lane, so the update worker's merge calls go on beside it -- and on that lane's device alone,
-// whatever $LSN_HOST_DEVICES says; the pass itself is icp.hip's (lsn::refine_cloud).  Every result is computed into scratch first: a call
+// whatever $LSN_HOST_DEVICES says; the pass itself is refine.hip's (lsn::refine_cloud).  Every result is computed into scratch first: a call
 // that fails has touched none of the caller's arrays.
 extern "C" int lsnRefineFromDepthMaps(int n_maps, unsigned char *depth_maps, unsigned char *depth_colors, int *widths, int *heights,
                                       float *intr_params, float *wtransform_params, float minX, float minY, float minZ, float maxX, float maxY,

@@ -35,7 +35,7 @@
 //      at most 1 -- parent[v] is the root, the label.  The bound is the capacity's logarithm, stated by the host; the mesh's depth (a chain
 //      hooked in descending order is nVertices deep) bounds nothing here.
 //   4. sizes (fr_size_kernel): one integer atomicAdd on size[label] per RUN of equal labels inside a wave (the run's head finds its
-//      length in the ballot of the heads), as icp.hip counts its cells -- on a surface nearly every lane of a wave has the same label.
+//      length in the ballot of the heads), as icp_grid.hip counts its cells -- on a surface nearly every lane of a wave has the same label.
 //      The lanes that are their own label are the tick's components.
 //   5. ordered compaction in the project's multi-launch form, as simplify.hip does it: fr_keep_kernel (kept = size[label] >=
 //      min_vertices, kept per 256), ct_block_scan_kernel, fr_write_kernel (vertices, remap, labels), compact_offsets_kernel<.., false>,

@@ -246,7 +246,7 @@ struct RadialScratch {
     void destroy_event() { if (done) (void)hipEventDestroy(done); }   // lsnFusionDestroy, with the plan's device current
 };
 
-// The refine pass (icp.hip) on ONE tick's merged cloud, resident on `device` and final: vertices -> packed points -> Gauss-Seidel loop.
+// The refine pass (refine.hip) on ONE tick's merged cloud, resident on `device` and final: vertices -> packed points -> Gauss-Seidel loop.
 // offsets: the tick's n_sensors + 1 row on the HOST; Rt: n_sensors x 12 floats, receives {Rs[i][9], Ts[i][3]}; h_clouds (host) / d_clouds
 // (device), both nullable, receive the refined points.  d_normals (device, nullable): the tick's vertex normals, 3 floats per vertex at the
 // vertex's own index and final -- the pass then minimises the point-to-plane residual (lsnRefineVerticesPlane).  Complete on return.

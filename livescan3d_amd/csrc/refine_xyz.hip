@@ -1,5 +1,5 @@
 // refine_xyz.hip -- a merged cloud's vertices as the packed XYZ points the refine pass works on.  Compiled as part of icp.hip's translation
-// unit (see where icp.hip includes it, in front of the refine pass).
+// unit (refine.hip includes it, in front of the refine pass).
 //
 // refineWorker_DoWork strips X, Y, Z out of every sensor's VertexC4ubV3f list on the host (LiveScanServer/MainWindowForm.cs:318-327) before
 // the Gauss-Seidel loop.  A tick's merged cloud lies in HBM in sensor order then raster order, so ONE launch over [0, nVertices) leaves every

@@ -66,7 +66,7 @@ def test_nn_matches_oracle_bitexact(gpu, orc, mode):
 
 
 def _grid_cells(targets):
-    """The cells of the grid the library lays over `targets` (grid_setup_kernel of icp.hip, its f32 arithmetic restated): the cell edge is
+    """The cells of the grid the library lays over `targets` (grid_setup_kernel of icp_grid.hip, its f32 arithmetic restated): the cell edge is
     twice the spacing of a surface-like cloud, within [L / 512, L / 4], and every axis is rounded up to whole super-blocks of 16 cells."""
     f = np.float32
     ext = (targets.max(0) - targets.min(0)).astype(f)
@@ -178,7 +178,7 @@ def _near_cases(orc):
 
 
 def test_near_path_gives_the_group_searchs_bits(gpu, orc, monkeypatch):
-    """The near path (a query with a small bound walks the grid cells around it, icp.hip near_search) against the same step with
+    """The near path (a query with a small bound walks the grid cells around it, the NEAR PATH of icp_nn.hip) against the same step with
     the path off ($LSN_ICP_NEAR=0: every query through the box hierarchy), against the brute force and against the oracle:
     indices and squared distances bit for bit -- and the path did settle queries in every case (lsnIcpNearResolved)."""
     import torch
@@ -242,6 +242,42 @@ def test_icp_runs_identically_with_and_without_the_near_path(gpu, orc, monkeypat
     for near in ("2", "1"):
         for k in range(3):
             assert np.array_equal(outs[near][k].view(np.uint32), outs["0"][k].view(np.uint32)), (near, k)
+
+
+def test_icp_run_through_the_complete_walk_gives_the_same_bits(gpu, orc, monkeypatch):
+    """A whole lsnIcpRun whose every NN step -- the unseeded first and the seeded ones -- overflows its work lists and runs the complete
+    walk (wave_search), against the same run with lists of the normal size, with the near path off and on (the default): the moved
+    cloud, R, t and every iteration's trace bit-identical.  $LSN_ICP_TINY_LISTS=1 (read when a workspace is created) makes a list
+    segment hold two items.  With the near path off overflow is certain at >= 12288 queries = 192 query groups: every group emits at
+    least one item into segment (g mod 64), in the seed round as in the cull -- a seed or a previous neighbour is a real point, so the
+    super-block that holds it lies within the group's largest bound -- and three groups share each of the 64 segments: every segment
+    overflows."""
+    import torch
+    clouds = _scene_clouds(orc, 3, 256, 212)
+    tgt, src = np.concatenate(clouds[1:]), clouds[0]
+    assert len(src) >= 12288
+    for near in ("0", None):
+        if near is None:
+            monkeypatch.delenv("LSN_ICP_NEAR", raising=False)
+        else:
+            monkeypatch.setenv("LSN_ICP_NEAR", near)
+        outs = {}
+        for tiny in (True, False):
+            if tiny:
+                monkeypatch.setenv("LSN_ICP_TINY_LISTS", "1")
+            else:
+                monkeypatch.delenv("LSN_ICP_TINY_LISTS", raising=False)
+            v1 = torch.from_numpy(tgt).cuda(); v2 = torch.from_numpy(src.copy()).cuda()
+            Rt = torch.tensor([1, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0], dtype=torch.float32, device="cuda")
+            ws = native.IcpWorkspace(0, len(tgt), len(src))
+            st = int(torch.cuda.current_stream().cuda_stream)
+            ws.run(v1.data_ptr(), len(tgt), v2.data_ptr(), len(src), Rt.data_ptr(), Rt.data_ptr() + 36, 4, native.NN_GRID, st)
+            outs[tiny] = (v2.cpu().numpy(), Rt.cpu().numpy(), ws.trace(4, st))
+            ws.close()
+        assert np.abs(outs[False][0] - src).max() > 1e-4, near          # the run did move the cloud
+        for k in range(3):
+            assert np.array_equal(outs[True][k].view(np.uint32), outs[False][k].view(np.uint32)), (near, k)
+    monkeypatch.delenv("LSN_ICP_NEAR", raising=False)
 
 
 def test_nn_non_finite_points_do_not_derail_the_search(gpu, orc):
