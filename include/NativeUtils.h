@@ -464,6 +464,52 @@ int lsnFusionFlyingPixels(LsnFusion *plan, int neighbourhood, int threshold, con
 int lsnFusionFlyingDiagnostics(LsnFusion *plan, int tick, int *removed_per_sensor, void *stream);
 int lsnSetFlyingPixelFilter(int neighbourhood, int threshold, int *prev_neighbourhood, int *prev_threshold);
 
+/* Depth smoothing: an integer bilateral filter on all n_ticks x n_maps raw depth maps of the plan, between the flying-pixel filter and the
+ * radial correction.  The reference has no such step; the stage is DEFINED here, tests/depth_smooth_ref.py restates this text in numpy and
+ * the kernels are held to the restatement bit for bit.
+ * One u16 map D of w x h (millimetres, 0 = no sample).  Inputs: a radius r in {1, 2, 3}; a spatial table ws[(2r+1)^2], row-major over
+ * (dy, dx); a range table wr[n_range], indexed by |delta| in millimetres; both tables unsigned short with every entry <= 4095;
+ * 1 <= n_range <= 1024, ws[centre] >= 1 and wr[0] >= 1.
+ * Per pixel, with c = D[y][x]:  c == 0 gives out = 0 (holes are not filled: that is the closing's job).  Otherwise every window position
+ * (dy, dx), |dy|, |dx| <= r, centre included, contributes iff its pixel lies inside the frame, its value v != 0, and a = |v - c| < n_range.
+ * A contributing position has the weight wt = ws[dy+r][dx+r] * wr[a] (below 2^24).  W = sum of wt (at least 1: the centre contributes
+ * ws[centre] * wr[0]; below 2^30).  S = sum of wt * (v - c), signed, |S| < 2^40: 64 bits.  out = c + floor((2 S + W) / (2 W)), the
+ * division being mathematical floor division: an exact half rounds towards +infinity.  The result is a rounded weighted mean of non-zero
+ * samples: it lies in [1, 65535], and |out - c| < n_range.
+ * Across the map: every pixel, borders included, is treated this way (out-of-frame positions simply do not contribute); every decision
+ * reads the unmodified map, so the pass runs out of place; everything is an integer, so the order of the sums cannot matter.  The filter
+ * is not idempotent: a tick applies it exactly once.
+ * lsnDepthSmoothGaussian (host only, needs no device): Gaussian tables, all arithmetic in double:
+ * ws[dy][dx] = rint(4095 exp(-(dx^2 + dy^2) / (2 ss ss))) with ss = (double) sigma_s into spatial_out ((2 radius + 1)^2 entries),
+ * wr[k] = rint(4095 exp(-k^2 / (2 sr sr))) into range_out; n_range, the return value, is the number of leading non-zero entries, at most
+ * min(range_cap, 1024) -- nothing behind them is written.  Refused with a message (-1): a radius outside 1..3, a sigma that is not finite
+ * and positive, a null pointer, range_cap < 1.  (Two exp implementations may differ in the last bit, so an entry may differ by one unit
+ * from another library's: that is why the kernels take tables, not sigmas.)
+ * lsnFusionSetDepthSmooth: the plan's setting.  radius <= 0: off (the default; the table pointers are ignored).  Otherwise the tables are
+ * validated as above -- refused with a message (-1), they leave the plan's previous setting in place -- and kept by the plan: both
+ * tables are uploaded into a buffer of the plan's once per new setting (setting the same tables again costs nothing; replacing them waits
+ * for the device).
+ * lsnFusionDepthSmooth: d_depth_in into d_depth_out ([n_ticks][pixels per tick] u16, as lsnFusionRun's input) on every tick and sensor of
+ * the plan; off: a device-to-device copy.  Out of place: a d_depth_out that overlaps d_depth_in (equal pointers included) is refused with
+ * nothing written; a null argument is refused.  Asynchronous on `stream`; returns 0, -1 on error.  The plan's list of 128 x 16 tiles
+ * (shared with the flying-pixel filter) and two words per tile of every tick are reserved by the first filtering call and freed with
+ * the plan.
+ * lsnFusionDepthSmoothDiagnostics (synchronises `stream`): for tick `tick` of the plan's last call, per sensor the pixels with out != in
+ * (n_maps ints) and the sum of |out - in| (n_maps long longs); either may be NULL; all 0 after a call with the filter off.  Returns the
+ * total of changed pixels, -1 on error or before any call.
+ * lsnSetDepthSmooth: the process-wide switch of the stage in the exports that START AT RAW FRAMES, depthMapAndColorSetRadialCorrection and
+ * lsnCorrectAndGenerateMesh: they smooth every sensor's map between the flying-pixel filter (if that is on) and the correction, on every
+ * device of $LSN_HOST_DEVICES, with the Gaussian tables of (radius, sigma_s, sigma_r), and what they write back is the smoothed, corrected
+ * maps.  generateMeshFromDepthMaps and generateVerticesFromDepthMap never smooth (they run on maps the radial export has already
+ * returned), nor does lsnRefineFromDepthMaps.  radius <= 0: off.  A triple lsnDepthSmoothGaussian refuses is refused here (-1, the
+ * setting stays).  Initially $LSN_DEPTH_SMOOTH="radius,sigma_s,sigma_r" (e.g. "2,1.5,12"; unset, malformed or refused: off); every call
+ * reads the current value.  The previous triple goes to prev_* (each may be NULL); returns 0. */
+int lsnDepthSmoothGaussian(int radius, float sigma_s, float sigma_r, unsigned short *spatial_out, unsigned short *range_out, int range_cap);
+int lsnFusionSetDepthSmooth(LsnFusion *plan, int radius, const unsigned short *spatial, const unsigned short *range, int n_range);
+int lsnFusionDepthSmooth(LsnFusion *plan, const void *d_depth_in, void *d_depth_out, void *stream);
+int lsnFusionDepthSmoothDiagnostics(LsnFusion *plan, int tick, int *changed_per_sensor, long long *abs_change_per_sensor, void *stream);
+int lsnSetDepthSmooth(int radius, float sigma_s, float sigma_r, int *prev_radius, float *prev_sigma_s, float *prev_sigma_r);
+
 /* Radial correction of n_ticks x n_maps frames in place in HBM (same layouts as lsnFusionRun's inputs);
  * intr_params: host, 7 floats per sensor {cx,cy,fx,fy,r2,r4,r6}. */
 int lsnFusionRadialCorrect(LsnFusion *plan, const float *intr_params, void *d_depth_maps, void *d_depth_colors, void *stream);
@@ -694,6 +740,12 @@ int lsnTickParts(const LsnTick *tick);   /* 1 or 2 */
  * pass through scratch of the tick object (2 bytes per pixel per tick), reserved by the first lsnTickRun that filters: a tick object
  * that never filters allocates nothing for it.  neighbourhood <= 0: off (the default).  Returns 0, -1 on error. */
 int lsnTickSetFlyingPixels(LsnTick *tick, int neighbourhood, int threshold);
+/* Depth smoothing (lsnFusionDepthSmooth, with the Gaussian tables of lsnDepthSmoothGaussian) as a stage of the tick: lsnTickRun then runs
+ * flying pixels (if set) -> depth smoothing -> radial correction -> vertices -> triangles on each half, on that half's plan and stream.
+ * d_depth_in stays untouched; the smoothed maps pass through scratch of the tick object (2 bytes per pixel per tick) that only a
+ * smoothing run reserves.  radius <= 0: off (the default).  Returns 0; -1 with a message where lsnDepthSmoothGaussian refuses the triple,
+ * which leaves the previous setting in place. */
+int lsnTickSetDepthSmooth(LsnTick *tick, int radius, float sigma_s, float sigma_r);
 int lsnTickRun(LsnTick *tick, const void *d_depth_in, const void *d_colors_in, void *d_depth_corrected, void *d_colors_corrected,
                void *d_vertices, int *d_offsets, void *d_triangles, int *d_tri_offsets, void *stream);
 

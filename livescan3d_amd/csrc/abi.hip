@@ -216,6 +216,55 @@ static PairSetting<int, int> &flying_setting()
     return *s;
 }
 
+// The depth smoothing of the same two exports, between that filter and the correction (lsnSetDepthSmooth): (radius, sigma_s, sigma_r) and the
+// Gaussian tables built from them, which a call takes with it (null: off).  generateMeshFromDepthMaps, generateVerticesFromDepthMap and
+// lsnRefineFromDepthMaps never read it -- the first two for the flying pixels' reason: the filter is not idempotent either.
+namespace {
+struct SmoothSetting {
+    std::mutex mu;
+    std::shared_ptr<const lsn::DepthSmoothTables> tables;   // null: off
+    float sigma_s = 0.0f, sigma_r = 0.0f;                   // what an "off" setting was given, so that the previous triple goes back as it came
+    int radius = 0;
+    SmoothSetting()
+    {
+        const char *e = getenv("LSN_DEPTH_SMOOTH");
+        if (!e || !*e) return;
+        int r = 0, used = 0;
+        float ss = 0.0f, sr = 0.0f;
+        if (sscanf(e, " %d , %f , %f %n", &r, &ss, &sr, &used) == 3 && e[used] == '\0' && set(r, ss, sr) == 0) return;
+        fprintf(stderr, "[NativeUtils] $LSN_DEPTH_SMOOTH=\"%s\" is not \"radius,sigma_s,sigma_r\" with a radius of at most 3 and positive sigmas "
+                        "(e.g. \"2,1.5,12\"): depth smoothing stays off\n", e);
+    }
+    // the new triple; refused (-1, lsnDepthSmoothGaussian's message) it leaves the setting as it was
+    int set(int r, float ss, float sr)
+    {
+        std::shared_ptr<const lsn::DepthSmoothTables> fresh;
+        if (r >= 1) {
+            auto t = std::make_shared<lsn::DepthSmoothTables>();
+            if (lsn::depth_smooth_gaussian(r, ss, sr, *t)) return -1;
+            fresh = t;
+        }
+        std::lock_guard<std::mutex> g(mu);
+        tables = fresh;
+        radius = r;
+        sigma_s = ss;
+        sigma_r = sr;
+        return 0;
+    }
+    std::shared_ptr<const lsn::DepthSmoothTables> current()
+    {
+        std::lock_guard<std::mutex> g(mu);
+        return tables;
+    }
+};
+}  // namespace
+
+static SmoothSetting &smooth_setting()
+{
+    static auto *s = new SmoothSetting();   // never destroyed, like the pairs above
+    return *s;
+}
+
 // What the three mesh exports share: `call` as `name` filled it (everything but the outlier filter's setting, which is read here) runs on
 // lane `l` of the context.  0: *out_mesh is the call's mesh; -1: the call was refused or failed, *out_mesh (if there is one) is empty and,
 // unless the caller merely passed no sensors, the message is set.
@@ -284,6 +333,27 @@ extern "C" int lsnSetFlyingPixelFilter(int neighbourhood, int threshold, int *pr
 {
     return lsn::guarded("lsnSetFlyingPixelFilter", -1, [&]() {
         flying_setting().exchange(neighbourhood, threshold, prev_neighbourhood, prev_threshold);
+        return 0;
+    });
+}
+
+extern "C" int lsnSetDepthSmooth(int radius, float sigma_s, float sigma_r, int *prev_radius, float *prev_sigma_s, float *prev_sigma_r)
+{
+    return lsn::guarded("lsnSetDepthSmooth", -1, [&]() {
+        lsn::clear_error();
+        SmoothSetting &s = smooth_setting();
+        int r0;
+        float ss0, sr0;
+        {
+            std::lock_guard<std::mutex> g(s.mu);
+            r0 = s.radius;
+            ss0 = s.sigma_s;
+            sr0 = s.sigma_r;
+        }
+        if (s.set(radius, sigma_s, sigma_r)) return -1;
+        if (prev_radius) *prev_radius = r0;
+        if (prev_sigma_s) *prev_sigma_s = ss0;
+        if (prev_sigma_r) *prev_sigma_r = sr0;
         return 0;
     });
 }
@@ -358,6 +428,7 @@ extern "C" void lsnCorrectAndGenerateMesh(int n_maps, unsigned char *depth_maps,
         call.back_d = write_back_corrected ? depth_maps : nullptr;
         call.back_c = write_back_corrected ? depth_colors : nullptr;
         flying_setting().current(call.fp_neighbourhood, call.fp_threshold);
+        call.smooth = smooth_setting().current();
         (void)mesh_export("lsnCorrectAndGenerateMesh", ctx().merge, call, out_mesh);
         return true;
     });
@@ -379,7 +450,8 @@ extern "C" void depthMapAndColorSetRadialCorrection(int n_maps, unsigned char *d
         if (ensure_ready(c)) return;
         int fp_n = 0, fp_t = 0;
         flying_setting().current(fp_n, fp_t);
-        radial_host(c, l, n_maps, depth_maps, depth_colors, widths, heights, intr_params, fp_n, fp_t);
+        const std::shared_ptr<const lsn::DepthSmoothTables> smooth = smooth_setting().current();
+        radial_host(c, l, n_maps, depth_maps, depth_colors, widths, heights, intr_params, fp_n, fp_t, smooth.get());
     });
 }
 

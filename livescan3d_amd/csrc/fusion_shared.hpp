@@ -605,6 +605,14 @@ struct LsnFusion {
     int fl_tiles_per_tick = 0;
     int fl_last = 0;                     // what the last call was: 0 = none yet, 1 = a copy (neighbourhood <= 0), 2 = the filter
     hipStream_t fl_stream = nullptr;     // ... and its stream
+    // depth smoothing (depth_smooth.hip): the setting of lsnFusionSetDepthSmooth (radius 0: off) -- one device table, the range table
+    // zero-padded to the 1032 entries the kernel stages and the spatial table behind it (ds_table_host: what it holds) -- and, allocated
+    // by the first filtering call, two words per 128 x 16 tile of every tick (the tile list is fl_tiles)
+    int ds_radius = 0, ds_n_range = 0;
+    std::vector<unsigned short> ds_table_host;
+    lsn::DevBuf ds_table, ds_counts;
+    int ds_last = 0;                     // what the last call was: 0 = none yet, 1 = a copy (off), 2 = the filter
+    hipStream_t ds_stream = nullptr;     // ... and its stream
     // the three stages on the merged mesh (render.hip, simplify.hip, normals.hip): each one's scratch, allocated on its first call
     lsn::RenderScratch rv;
     lsn::SimplifyScratch sp;

@@ -10,6 +10,7 @@
 #include <condition_variable>
 #include <cstdlib>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <new>
 #include <thread>
@@ -53,6 +54,7 @@ struct Lane {
     lsn::DevBuf d_depth, d_colors, d_depth2, d_colors2, d_out, d_off, d_tri, d_tri_off;
     lsn::DevBuf d_masked;     // a call with the outlier filter on: its depth maps with the removed vertices' pixels at 0 (allocated by the first such call)
     lsn::DevBuf d_flying;     // a call with the flying-pixel filter on: its raw depth maps filtered, what the radial correction then reads (allocated by the first such call)
+    lsn::DevBuf d_smooth;     // a call with depth smoothing on: its (filtered) depth maps smoothed, what the radial correction then reads (allocated by the first such call)
     // the lane's plans: key = n sensors, first sensor, widths..., heights...  Owned by the lane and only touched under its lock, so a
     // plan never runs on two lanes' streams at once and an eviction cannot pull a plan from under the other lane's call
     std::map<std::vector<int>, LsnFusion *> plans;
@@ -202,15 +204,24 @@ struct MeshCall {
     float outlier_max_dist = 0.0f;           //     and outlier_max_dist > 0
     int fp_neighbourhood = 0, fp_threshold = 0;   // the flying-pixel filter (flying.hip, lsnSetFlyingPixelFilter) in front of the radial correction
                                                   //     of a call that starts with it (`radial`): it runs when flying_on(fp_neighbourhood)
+    std::shared_ptr<const lsn::DepthSmoothTables> smooth;   // depth smoothing (depth_smooth.hip, lsnSetDepthSmooth) between that filter and the
+                                                            //     correction of such a call: it runs when smooth_on(smooth.get())
 };
 
 // The one place that decides whether a call filters flying pixels: a neighbourhood of at least one pixel (0 and below mean off).
 inline bool flying_on(int neighbourhood) { return neighbourhood >= 1; }
+// ... and whether it smooths the depth maps: the export found the process-wide switch on and handed its tables over.
+inline bool smooth_on(const lsn::DepthSmoothTables *smooth) { return smooth != nullptr && smooth->radius >= 1; }
+// Depth smoothing of one plan's maps inside a flow: the plan takes the call's tables (nothing to do when it has them), then `in` into `out`.
+inline int smooth_maps(LsnFusion *plan, const lsn::DepthSmoothTables &t, const void *in, void *out, hipStream_t s)
+{
+    return lsn::set_depth_smooth(plan, "lsnSetDepthSmooth", t.radius, t.spatial, t.range, t.n_range) || lsn::depth_smooth(plan, in, out, s) ? -1 : 0;
+}
 
 // The calls.  The lane's lock is held by the caller; `out` is left untouched on failure (the export then returns an empty mesh).
 int fuse_host(Ctx &c, Lane &l, const MeshCall &call, Mesh *out);
 void radial_host(Ctx &c, Lane &l, int n_maps, unsigned char *depth_maps, unsigned char *depth_colors, const int *widths, const int *heights,
-                 const float *intr_params, int fp_neighbourhood = 0, int fp_threshold = 0);
+                 const float *intr_params, int fp_neighbourhood = 0, int fp_threshold = 0, const lsn::DepthSmoothTables *smooth = nullptr);
 // The fusion of a call whose cloud stays on the device: vertices only (with the outlier filter if the call has it on) into l.d_out, final on
 // return, the tick's offset row (call.count + 1 ints) into `offsets`.  No mesh: the lane is left without a last one.
 int fuse_resident(Ctx &c, Lane &l, const MeshCall &call, int *offsets);

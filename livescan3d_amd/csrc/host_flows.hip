@@ -465,6 +465,7 @@ struct HostCall {
             return -1;
         if (radial && (l.d_depth2.reserve(dbytes + 16) || l.d_colors2.reserve(cbytes + 16))) return -1;
         if (radial && flying_on(call.fp_neighbourhood) && l.d_flying.reserve(dbytes + 16)) return -1;
+        if (radial && smooth_on(call.smooth.get()) && l.d_smooth.reserve(dbytes + 16)) return -1;
         if (in_hbm && (l.d_out.reserve((size_t)cap * 16) || (with_triangles && l.d_tri.reserve((size_t)cap * 2 * 12)))) return -1;
         back = radial && call.back_d && call.back_c;
         // the mesh's host blocks, sized for the most the frames can give (recycled through the pool: the same blocks tick after tick);
@@ -508,6 +509,10 @@ struct HostCall {
                 if (call.radial && flying_on(call.fp_neighbourhood)) {
                     if (lsn::flying_pixels(g.radial_plan, call.fp_neighbourhood, call.fp_threshold, raw_d, l.d_flying.as<char>() + g.d_off, l.stream)) return -1;
                     raw_d = l.d_flying.as<char>() + g.d_off;
+                }
+                if (call.radial && smooth_on(call.smooth.get())) {   // ... and smoothed into d_smooth behind that
+                    if (smooth_maps(g.radial_plan, *call.smooth, raw_d, l.d_smooth.as<char>() + g.d_off, l.stream)) return -1;
+                    raw_d = l.d_smooth.as<char>() + g.d_off;
                 }
                 if (call.radial && lsnFusionRadialCorrectTo(g.radial_plan, call.intr + 7 * g.first, raw_d, l.d_colors.as<char>() + g.c_off,
                                                        l.d_depth2.as<char>() + g.d_off, l.d_colors2.as<char>() + g.c_off, l.stream))
@@ -854,6 +859,10 @@ int shard_part(ShardedCall &sc, int d)
     // correction then reads
     const bool flying = call.radial && flying_on(call.fp_neighbourhood);
     if (flying && l.d_flying.reserve(dbytes + 16)) return -1;
+    // ... and depth smoothing behind it, into d_smooth: raw() names the maps the correction reads once the stages in front of it are queued
+    const bool smooth = call.radial && smooth_on(call.smooth.get());
+    if (smooth && l.d_smooth.reserve(dbytes + 16)) return -1;
+    auto raw = [&]() -> const void * { return smooth ? l.d_smooth.p : flying ? l.d_flying.p : l.d_depth.p; };
     if (sc.only_radial) {
         // the radial export alone: this block up over this device's link, corrected out of place, home again (both ways pageable copies
         // that keep this thread -- which is why every device has one)
@@ -861,7 +870,8 @@ int shard_part(ShardedCall &sc, int d)
         LSN_HIP(hipMemcpyWithStream(l.d_depth.p, call.depth_maps + d_src, dbytes, hipMemcpyHostToDevice, l.up));
         LSN_HIP(hipMemcpyWithStream(l.d_colors.p, call.depth_colors + c_src, cbytes, hipMemcpyHostToDevice, l.up));
         if (flying && lsn::flying_pixels(plan, call.fp_neighbourhood, call.fp_threshold, l.d_depth.p, l.d_flying.p, l.stream)) return -1;
-        if (lsnFusionRadialCorrectTo(plan, call.intr + 7 * f0, flying ? l.d_flying.p : l.d_depth.p, l.d_colors.p, l.d_depth2.p, l.d_colors2.p, l.stream)) return -1;
+        if (smooth && smooth_maps(plan, *call.smooth, flying ? l.d_flying.p : l.d_depth.p, l.d_smooth.p, l.stream)) return -1;
+        if (lsnFusionRadialCorrectTo(plan, call.intr + 7 * f0, raw(), l.d_colors.p, l.d_depth2.p, l.d_colors2.p, l.stream)) return -1;
         LSN_HIP(hipStreamSynchronize(l.stream));
         LSN_HIP(hipMemcpyWithStream(call.back_d + d_src, l.d_depth2.p, dbytes, hipMemcpyDeviceToHost, l.back));
         LSN_HIP(hipMemcpyWithStream(call.back_c + c_src, l.d_colors2.p, cbytes, hipMemcpyDeviceToHost, l.back));
@@ -884,7 +894,8 @@ int shard_part(ShardedCall &sc, int d)
     LSN_HIP(hipMemcpyWithStream(l.d_colors.p, call.depth_colors + c_src, cbytes, hipMemcpyHostToDevice, l.up));
     if (call.radial) {
         if (flying && lsn::flying_pixels(plan, call.fp_neighbourhood, call.fp_threshold, l.d_depth.p, l.d_flying.p, l.stream)) return -1;
-        if (lsnFusionRadialCorrectTo(plan, call.intr + 7 * f0, flying ? l.d_flying.p : l.d_depth.p, l.d_colors.p, l.d_depth2.p, l.d_colors2.p, l.stream)) return -1;
+        if (smooth && smooth_maps(plan, *call.smooth, flying ? l.d_flying.p : l.d_depth.p, l.d_smooth.p, l.stream)) return -1;
+        if (lsnFusionRadialCorrectTo(plan, call.intr + 7 * f0, raw(), l.d_colors.p, l.d_depth2.p, l.d_colors2.p, l.stream)) return -1;
         LSN_HIP(hipEventRecord(ev_corrected, l.stream));
         if (lsn::run_count(plan, run_d, run_c, l.d_off.as<int>(), l.h_off, ev_counted, l.stream)) return -1;
     }
@@ -1011,7 +1022,7 @@ int run_parts(Ctx &c, ShardedCall &sc)
 // depthMapAndColorSetRadialCorrection over the devices of $LSN_HOST_DEVICES: every device corrects its block of sensors and writes it back
 // into the caller's arrays.  The merge lane's lock is held.
 int radial_sharded(Ctx &c, Lane &ml, int n_maps, unsigned char *depth_maps, unsigned char *depth_colors, const int *widths, const int *heights,
-                   const float *intr, int fp_neighbourhood, int fp_threshold)
+                   const float *intr, int fp_neighbourhood, int fp_threshold, const lsn::DepthSmoothTables *smooth)
 {
     ml.forget_last();
     MeshCall call;
@@ -1026,6 +1037,7 @@ int radial_sharded(Ctx &c, Lane &ml, int n_maps, unsigned char *depth_maps, unsi
     call.back_c = depth_colors;
     call.fp_neighbourhood = fp_neighbourhood;
     call.fp_threshold = fp_threshold;
+    if (smooth_on(smooth)) call.smooth = std::make_shared<const lsn::DepthSmoothTables>(*smooth);
     ShardedCall sc(c, call);
     sc.only_radial = true;
     plan_shards(n_maps, (int)c.shards.size(), sc.first, sc.D);
@@ -1168,10 +1180,10 @@ int fuse_host(Ctx &c, Lane &l, const MeshCall &call, Mesh *out)
 
 // depthMapAndColorSetRadialCorrection on the lane (one device) or over the devices of $LSN_HOST_DEVICES.  The lane's lock is held.
 void radial_host(Ctx &c, Lane &l, int n_maps, unsigned char *depth_maps, unsigned char *depth_colors, const int *widths, const int *heights,
-                 const float *intr_params, int fp_neighbourhood, int fp_threshold)
+                 const float *intr_params, int fp_neighbourhood, int fp_threshold, const lsn::DepthSmoothTables *smooth_tables)
 {
     if (c.shards.size() >= 2 && n_maps >= 2) {
-        (void)radial_sharded(c, l, n_maps, depth_maps, depth_colors, widths, heights, intr_params, fp_neighbourhood, fp_threshold);
+        (void)radial_sharded(c, l, n_maps, depth_maps, depth_colors, widths, heights, intr_params, fp_neighbourhood, fp_threshold, smooth_tables);
         return;
     }
     const bool flying = flying_on(fp_neighbourhood);   // every group's raw maps are filtered into d_flying, which its correction reads
@@ -1188,6 +1200,8 @@ void radial_host(Ctx &c, Lane &l, int n_maps, unsigned char *depth_maps, unsigne
     }
     if (l.d_depth.reserve(dbytes + 16) || l.d_colors.reserve(cbytes + 16) || l.d_depth2.reserve(dbytes + 16) || l.d_colors2.reserve(cbytes + 16)) return;
     if (flying && l.d_flying.reserve(dbytes + 16)) return;
+    const bool smooth = smooth_on(smooth_tables);      // ... and smoothed into d_smooth behind that
+    if (smooth && l.d_smooth.reserve(dbytes + 16)) return;
     // Both directions are pageable copies that keep the thread; what overlaps is the correction itself (~100 us per group, latency
     // bound) with the next group's upload and the previous group's way home.  Out of place on the device (the warped, un-closed
     // maps stay in LDS); a group's slice of the caller's arrays is overwritten once ITS kernels have run -- a call that fails
@@ -1216,6 +1230,10 @@ void radial_host(Ctx &c, Lane &l, int n_maps, unsigned char *depth_maps, unsigne
             if (flying) {
                 ok = lsn::flying_pixels(q.radial_plan, fp_neighbourhood, fp_threshold, raw_d, l.d_flying.as<char>() + q.d_off, l.stream) == 0;
                 raw_d = l.d_flying.as<char>() + q.d_off;
+            }
+            if (ok && smooth) {
+                ok = smooth_maps(q.radial_plan, *smooth_tables, raw_d, l.d_smooth.as<char>() + q.d_off, l.stream) == 0;
+                raw_d = l.d_smooth.as<char>() + q.d_off;
             }
             ok = ok && lsnFusionRadialCorrectTo(q.radial_plan, intr_params + 7 * q.first, raw_d, l.d_colors.as<char>() + q.c_off,
                                           l.d_depth2.as<char>() + q.d_off, l.d_colors2.as<char>() + q.c_off, l.stream) == 0 &&

@@ -136,6 +136,19 @@ int outlier_filter(LsnFusion *p, int k, float max_dist, const void *d_depth, con
 // place; neighbourhood <= 0 copies).  Takes the plan's mutex.
 int flying_pixels(LsnFusion *p, int neighbourhood, int threshold, const void *d_depth_in, void *d_depth_out, hipStream_t s);
 
+// Depth smoothing (depth_smooth.hip).  One setting as the process-wide switch and the tick hold it: the Gaussian tables of
+// lsnDepthSmoothGaussian for (radius, sigma_s, sigma_r).  set_depth_smooth is lsnFusionSetDepthSmooth under the name `who` (a setting the
+// plan already has costs nothing), depth_smooth is lsnFusionDepthSmooth on a stream; both take the plan's mutex.
+struct DepthSmoothTables {
+    int radius = 0, n_range = 0;
+    unsigned short spatial[49] = {};
+    unsigned short range[1024] = {};
+};
+int set_depth_smooth(LsnFusion *p, const char *who, int radius, const unsigned short *spatial, const unsigned short *range, int n_range);
+int depth_smooth(LsnFusion *p, const void *d_depth_in, void *d_depth_out, hipStream_t s);
+// The tables of (radius, sigma_s, sigma_r) into `t`; -1 with lsnDepthSmoothGaussian's message where it refuses them.
+int depth_smooth_gaussian(int radius, float sigma_s, float sigma_r, DepthSmoothTables &t);
+
 // A batch of meshes in lsnFusionRunMesh's layout, as the three stages on the merged mesh read it (render.hip, simplify.hip, normals.hip;
 // what they share is mesh_batch.hip's).  The stages' device structs embed it; it is built from a plan (plan_batch, mesh_batch.hip) or
 // from a lane's last mesh (LastMesh::batch, abi.hip).

@@ -1329,3 +1329,5 @@ extern "C" int lsnFusionRadialCorrectTo(LsnFusion *p, const float *intr_params, 
 
 // The flying-pixel filter, the per-sensor depth stage in front of this one, is compiled as part of this translation unit.
 #include "flying.hip"
+// ... and so is depth smoothing, the stage between the two (it shares the filter's tile list).
+#include "depth_smooth.hip"

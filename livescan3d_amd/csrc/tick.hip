@@ -23,6 +23,8 @@ struct LsnTick {
     std::vector<float> intr;             // the radial correction's intrinsics (lsnTickSetParams)
     int fp_neighbourhood = 0, fp_threshold = 0;   // the flying-pixel filter in front of the correction (lsnTickSetFlyingPixels; <= 0: off)
     lsn::DevBuf d_filtered;              // ... and its output, [n_ticks][pixels per tick] u16: reserved by the first run that filters
+    int ds_radius = 0;                   // depth smoothing between the filter and the correction (lsnTickSetDepthSmooth; <= 0: off; the plans hold the tables)
+    lsn::DevBuf d_smoothed;              // ... and its output, laid out like d_filtered: reserved by the first run that smooths
     hipStream_t side = nullptr;
     hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_band = nullptr;
     std::mutex mu;
@@ -129,6 +131,24 @@ extern "C" int lsnTickSetFlyingPixels(LsnTick *t, int neighbourhood, int thresho
     });
 }
 
+extern "C" int lsnTickSetDepthSmooth(LsnTick *t, int radius, float sigma_s, float sigma_r)
+{
+    return lsn::guarded("lsnTickSetDepthSmooth", -1, [&]() {
+        lsn::clear_error();
+        if (!t) {
+            lsn::set_error("lsnTickSetDepthSmooth: null argument");
+            return -1;
+        }
+        lsn::DepthSmoothTables tab;
+        if (radius >= 1 && lsn::depth_smooth_gaussian(radius, sigma_s, sigma_r, tab)) return -1;   // refused: the previous setting stays
+        std::lock_guard<std::mutex> g(t->mu);
+        for (int k = 0; k < t->parts; k++)
+            if (lsn::set_depth_smooth(t->plan[k], "lsnTickSetDepthSmooth", radius, tab.spatial, tab.range, tab.n_range)) return -1;
+        t->ds_radius = radius >= 1 ? radius : 0;
+        return 0;
+    });
+}
+
 extern "C" int lsnTickRun(LsnTick *t, const void *d_depth_in, const void *d_colors_in, void *d_depth_corr, void *d_colors_corr, void *d_vertices,
                           int *d_offsets, void *d_triangles, int *d_tri_offsets, void *stream)
 {
@@ -147,6 +167,8 @@ extern "C" int lsnTickRun(LsnTick *t, const void *d_depth_in, const void *d_colo
         hipStream_t s = lsn::as_stream(stream);
         const bool filter = t->fp_neighbourhood >= 1;
         if (filter && t->d_filtered.reserve(2 * (size_t)t->cap * t->n_ticks + 16)) return -1;
+        const bool smooth = t->ds_radius >= 1;
+        if (smooth && t->d_smoothed.reserve(2 * (size_t)t->cap * t->n_ticks + 16)) return -1;
         // part k's slices of the caller's arrays: [tick][pixels], [tick][pixels][3], [tick][capacity] vertices, [tick][n_maps + 1], ...
         auto part = [&](int k, hipStream_t st) -> int {
             const size_t t0 = (size_t)t->first[k];
@@ -160,6 +182,12 @@ extern "C" int lsnTickRun(LsnTick *t, const void *d_depth_in, const void *d_colo
                 if (t->plan[k]->rd.wait_for_chain(st)) return -1;
                 if (lsn::flying_pixels(t->plan[k], t->fp_neighbourhood, t->fp_threshold, din, dfl, st)) return -1;
                 din = dfl;
+            }
+            if (smooth) {   // (filter ->) smoothing -> correction, through scratch of its own under the same rule
+                unsigned char *dsm = t->d_smoothed.as<unsigned char>() + 2 * px * t0;
+                if (t->plan[k]->rd.wait_for_chain(st)) return -1;
+                if (lsn::depth_smooth(t->plan[k], din, dsm, st)) return -1;
+                din = dsm;
             }
             if (lsnFusionRadialCorrectTo(t->plan[k], t->intr.data(), din, cin, dco, cco, st)) return -1;
             return lsnFusionRunMesh(t->plan[k], dco, cco, static_cast<unsigned char *>(d_vertices) + 16 * px * t0, d_offsets + nm * t0,

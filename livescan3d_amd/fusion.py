@@ -109,6 +109,10 @@ class DeviceFusion:
     def flying_pixels(self, neighbourhood, threshold, depth_out, depth=None, stream=None):
         self.plan.flying_pixels(neighbourhood, threshold, self._in(depth)[0], depth_out.data_ptr(), _stream_handle(stream))
 
+    def depth_smooth(self, depth_out, depth=None, stream=None):
+        """Depth smoothing with the tables of plan.set_depth_smooth(), out of place into depth_out."""
+        self.plan.depth_smooth(self._in(depth)[0], depth_out.data_ptr(), _stream_handle(stream))
+
     def render_views(self, intr, wt, width, height, points=False, stream=None):
         """The ticks' meshes (points: their vertices alone) drawn from the virtual cameras intr / wt (7 / 12 floats per view), each
         width x height.  Returns (depth int16-bit-pattern [T, V, h, w], rgb uint8 [T, V, h, w, 3]), both prefilled with SENTINEL."""

@@ -62,6 +62,8 @@ _PROTOTYPES = {
     "lsnSetOverlayMerge": (_i, [_i]),
     "lsnSetOutlierFilter": (_i, [_i, _f, _vp, _vp]),
     "lsnSetFlyingPixelFilter": (_i, [_i, _i, _vp, _vp]),
+    "lsnSetDepthSmooth": (_i, [_i, _f, _f, _vp, _vp, _vp]),
+    "lsnDepthSmoothGaussian": (_i, [_i, _f, _f, _vp, _vp, _i]),
     # part 2: the device-resident API
     "lsnFusionCreate": (_vp, [_i, _i, _i, _vp, _vp]),
     "lsnFusionDestroy": (None, [_vp]),
@@ -91,6 +93,9 @@ _PROTOTYPES = {
     "lsnFusionOutlierDiagnostics": (_i, [_vp, _i, _vp, _vp, _vp, _vp]),
     "lsnFusionFlyingPixels": (_i, [_vp, _i, _i, _vp, _vp, _vp]),
     "lsnFusionFlyingDiagnostics": (_i, [_vp, _i, _vp, _vp]),
+    "lsnFusionSetDepthSmooth": (_i, [_vp, _i, _vp, _vp, _i]),
+    "lsnFusionDepthSmooth": (_i, [_vp] * 4),
+    "lsnFusionDepthSmoothDiagnostics": (_i, [_vp, _i, _vp, _vp, _vp]),
     "lsnFusionRenderViews": (_i, [_vp, _i, _vp, _vp, _i, _i] + [_vp] * 7),
     "lsnFusionRenderDiagnostics": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp]),
     "lsnFusionSimplify": (_i, [_vp, _f] + [_vp] * 10),
@@ -141,6 +146,7 @@ _PROTOTYPES = {
     "lsnTickDestroy": (None, [_vp]),
     "lsnTickSetParams": (_i, [_vp] * 5),
     "lsnTickSetFlyingPixels": (_i, [_vp, _i, _i]),
+    "lsnTickSetDepthSmooth": (_i, [_vp, _i, _f, _f]),
     "lsnTickCapacity": (_ll, [_vp]),
     "lsnTickTriangleCapacity": (_ll, [_vp]),
     "lsnTickParts": (_i, [_vp]),
@@ -287,6 +293,25 @@ def set_flying_pixel_filter(neighbourhood, threshold):
     return pn.value, pt.value
 
 
+def depth_smooth_gaussian(radius, sigma_s, sigma_r, range_cap=1024):
+    """lsnDepthSmoothGaussian (needs no GPU): the Gaussian tables of depth smoothing for (radius, sigma_s, sigma_r).  Returns (spatial
+    uint16 [2r+1, 2r+1], range uint16 [n_range]); n_range is at most min(range_cap, 1024)."""
+    side = 2 * int(radius) + 1 if 1 <= int(radius) <= 3 else 1
+    ws = np.zeros(side * side, dtype=np.uint16)
+    wr = np.zeros(max(min(int(range_cap), 1024), 1), dtype=np.uint16)
+    n = _nonneg(lib().lsnDepthSmoothGaussian(int(radius), float(sigma_s), float(sigma_r), _ptr(ws), _ptr(wr), int(range_cap)), "lsnDepthSmoothGaussian")
+    return ws.reshape(side, side), wr[:n].copy()
+
+
+def set_depth_smooth(radius, sigma_s=0.0, sigma_r=0.0):
+    """lsnSetDepthSmooth: the process-wide (radius, sigma_s, sigma_r) of depth smoothing in the exports that start with the radial correction
+    (radial_correction, correct_and_generate_mesh), between the flying-pixel filter and the correction; radius <= 0: off.  Returns the
+    previous triple."""
+    pr, ps, pq = C.c_int(0), C.c_float(0), C.c_float(0)
+    _check(lib().lsnSetDepthSmooth(int(radius), float(sigma_s), float(sigma_r), C.byref(pr), C.byref(ps), C.byref(pq)), "lsnSetDepthSmooth")
+    return pr.value, ps.value, pq.value
+
+
 class _Scoped:
     """Sets a process-wide setting for the body of a with-statement: setter(*setting) returns the previous one, which goes back in on the
     way out (None: leaves the setting as it is)."""
@@ -385,12 +410,14 @@ def host_schedule(widths, heights, first=0, count=None, radial=False, sensors_pe
     return g, buf.value.decode()
 
 
-def radial_correction(depth_maps, depth_colors, widths, heights, intr, flying_pixels=None):
+def radial_correction(depth_maps, depth_colors, widths, heights, intr, flying_pixels=None, depth_smooth=None):
     """KinectServer.CorrectRadialDistortionsForDepthMaps (KinectServer.cs:518-525): returns corrected copies
     (depth as a uint8 view of the u16 maps, colours); the export itself works in place on the arrays it is given.
     flying_pixels: None leaves the process-wide flying-pixel filter (lsnSetFlyingPixelFilter) as it is; (neighbourhood, threshold) sets
-    it for this call alone (the maps are filtered, then corrected)."""
-    with _Scoped(set_flying_pixel_filter, flying_pixels):
+    it for this call alone (the maps are filtered, then corrected).
+    depth_smooth: None leaves the process-wide depth smoothing (lsnSetDepthSmooth) as it is; (radius, sigma_s, sigma_r) sets it for this
+    call alone (the maps are filtered if that is on, smoothed, then corrected)."""
+    with _Scoped(set_flying_pixel_filter, flying_pixels), _Scoped(set_depth_smooth, depth_smooth):
         require_gpu()
         n, dm, dc, widths, heights, intr, _, _ = _host_args(depth_maps, depth_colors, widths, heights, intr, copy=True)
         lib().depthMapAndColorSetRadialCorrection(n, _ptr(dm), _ptr(dc), _ptr(widths), _ptr(heights), _ptr(intr))
@@ -401,12 +428,12 @@ def radial_correction(depth_maps, depth_colors, widths, heights, intr, flying_pi
 
 
 def correct_and_generate_mesh(depth_maps, depth_colors, widths, heights, intr, wt, bounds, write_back=True, outlier_filter=None,
-                              flying_pixels=None):
+                              flying_pixels=None, depth_smooth=None):
     """One call per tick (extension): radial correction + merge call with a single upload.  Returns (vertices, triangles,
     corrected depth as uint8, corrected colours); with write_back=False the last two are the untouched inputs.
     outlier_filter: as for generate_mesh_from_depth_maps (the corrected maps written back are the unmasked ones).
-    flying_pixels: as for radial_correction (the corrected maps written back are the filtered, corrected ones)."""
-    with _Scoped(set_flying_pixel_filter, flying_pixels), _Scoped(set_outlier_filter, outlier_filter):
+    flying_pixels / depth_smooth: as for radial_correction (the corrected maps written back are the filtered, smoothed, corrected ones)."""
+    with _Scoped(set_flying_pixel_filter, flying_pixels), _Scoped(set_depth_smooth, depth_smooth), _Scoped(set_outlier_filter, outlier_filter):
         require_gpu()
         n, dm, dc, widths, heights, intr, wt, b = _host_args(depth_maps, depth_colors, widths, heights, intr, wt, bounds, copy=True)
         mesh = Mesh()
@@ -699,6 +726,28 @@ class FusionPlan(_Handle):
         k = _nonneg(lib().lsnFusionFlyingDiagnostics(self._h, int(tick), _ptr(rps), stream or None), "lsnFusionFlyingDiagnostics")
         return rps[:self.n_maps].copy(), k
 
+    def set_depth_smooth(self, radius, spatial=None, range_table=None):
+        """The plan's depth smoothing (lsnFusionSetDepthSmooth): radius 1..3 with a spatial table of (2 radius + 1)^2 and a range table of
+        1..1024 uint16 entries <= 4095 (e.g. depth_smooth_gaussian's); radius <= 0: off.  A refused setting leaves the previous one."""
+        ws = _as(np.zeros(1) if spatial is None else spatial, np.uint16).ravel()
+        wr = _as(np.zeros(1) if range_table is None else range_table, np.uint16).ravel()
+        if int(radius) >= 1 and ws.size != (2 * int(radius) + 1) ** 2:
+            raise NativeUtilsError(f"set_depth_smooth: the spatial table of radius {radius} has {(2 * int(radius) + 1) ** 2} entries, not {ws.size}")
+        _check(lib().lsnFusionSetDepthSmooth(self._h, int(radius), _ptr(ws), _ptr(wr), int(wr.size)), "lsnFusionSetDepthSmooth")
+
+    def depth_smooth(self, d_depth_in, d_depth_out, stream=0):
+        """Depth smoothing on every map of the plan with the tables of set_depth_smooth(), d_depth_in into d_depth_out (out of place:
+        overlapping buffers are refused; off copies).  Run radial_correct_to() / run() on d_depth_out next."""
+        _check(lib().lsnFusionDepthSmooth(self._h, d_depth_in, d_depth_out, stream or None), "lsnFusionDepthSmooth")
+
+    def depth_smooth_diagnostics(self, tick=0, stream=0):
+        """What the last depth_smooth() did in one tick: (pixels with out != in per sensor int32[n], sum of |out - in| per sensor int64[n],
+        the total of changed pixels)."""
+        ch = np.zeros(max(self.n_maps, 1), dtype=np.int32)
+        mv = np.zeros(max(self.n_maps, 1), dtype=np.int64)
+        k = _nonneg(lib().lsnFusionDepthSmoothDiagnostics(self._h, int(tick), _ptr(ch), _ptr(mv), stream or None), "lsnFusionDepthSmoothDiagnostics")
+        return ch[:self.n_maps].copy(), mv[:self.n_maps].copy(), k
+
     def render_views(self, intr, wt, width, height, d_vertices, d_offsets, d_triangles, d_tri_offsets, d_depth_out, d_colors_out, stream=0):
         """Render view: every tick's merged mesh (d_triangles None / 0: its vertices as points) drawn from the virtual cameras of intr
         (7 floats per view) / wt (12 per view), each width x height, into d_depth_out [n_ticks][n_views][h][w] u16 and d_colors_out
@@ -912,6 +961,11 @@ class TickPipeline(_Handle):
         """The flying-pixel filter as the first stage of run() (neighbourhood <= 0: off): filter -> radial correction -> vertices ->
         triangles; d_depth_corr then receives the filtered and corrected maps."""
         _check(lib().lsnTickSetFlyingPixels(self._h, int(neighbourhood), int(threshold)), "lsnTickSetFlyingPixels")
+
+    def set_depth_smooth(self, radius, sigma_s=0.0, sigma_r=0.0):
+        """Depth smoothing with the Gaussian tables of (radius, sigma_s, sigma_r) as a stage of run() (radius <= 0: off): flying pixels
+        (if set) -> depth smoothing -> radial correction -> vertices -> triangles."""
+        _check(lib().lsnTickSetDepthSmooth(self._h, int(radius), float(sigma_s), float(sigma_r)), "lsnTickSetDepthSmooth")
 
     def run(self, d_depth_in, d_colors_in, d_depth_corr, d_colors_corr, d_vertices, d_offsets, d_triangles, d_tri_offsets, stream=0):
         _check(lib().lsnTickRun(self._h, d_depth_in, d_colors_in, d_depth_corr, d_colors_corr, d_vertices, d_offsets, d_triangles, d_tri_offsets, stream),
