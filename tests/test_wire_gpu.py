@@ -49,7 +49,7 @@ def _ply(v, tri, misalign=0):
     return out[misalign:misalign + n].cpu().numpy().tobytes()
 
 
-@pytest.mark.parametrize("n", [1, 5, 1023, 1025, 64997, 64998, 2 * 64997 + 17])
+@pytest.mark.parametrize("n", [1, 2, 5, 1023, 1024, 1025, 1026, 64997, 64998, 2 * 64997 + 17])
 def test_vertices_only_stream(gpu, orc, n):
     v = _cloud(np.random.default_rng(n), n)
     none = np.zeros((0, 3), np.int32)
@@ -78,10 +78,11 @@ def test_mesh_stream_matches_oracle(gpu, orc, w, h):
         assert _ply(v, tri, mis) == orc.ply_binary(v, tri)
 
 
-@pytest.mark.parametrize("nt", [682, 683, 2047, 2048, 2049, 4096, 4097])
+@pytest.mark.parametrize("nt", [682, 683, 1023, 1024, 1025, 2047, 2048, 2049, 4096, 4097])
 def test_triangle_counts_around_the_prefix_sums_blocks(gpu, orc, nt):
     """The all-chunks-at-once path sums 2048 elements per workgroup, over the triangles and over their 3 nt index positions: one workgroup's
-    worth of positions is 682 2/3 triangles, of triangles 2048; 4096 / 4097 end the second workgroup / start a third."""
+    worth of positions is 682 2/3 triangles, of triangles 2048; 4096 / 4097 end the second workgroup / start a third.  1023 / 1024 / 1025:
+    one block of the stream's triangle section is 1024 triangles."""
     v, grid = _grid(np.random.default_rng(7), 60, 40)
     assert len(grid) >= nt
     assert _pack(v, grid[:nt]) == orc.transfer_frame(v, grid[:nt]) and _pack.last_path == 1
@@ -151,6 +152,79 @@ def test_which_path_forms_the_chunks(gpu, orc):
     t0 = int(np.frombuffer(want, "<i4", 4 + 2 * n_chunks)[3 + n_chunks]) + 1     # triangles of the first chunk (its count is one short, :244)
     for nt in (t0 - 1, t0, t0 + 1, 21665, 21666):
         assert _pack(v, grid[:nt]) == orc.transfer_frame(v, grid[:nt]) and _pack.last_path == 1, nt
+
+
+def test_the_walk_at_a_small_shape(gpu, orc):
+    """The 40 x 30 grid with a 17th use of one vertex takes the chunk-after-chunk walk (2) and gives the reference's bytes; with 16 uses
+    the same handle takes the all-chunks-at-once path (1) again, with the bytes of a fresh handle."""
+    v, grid = _grid(np.random.default_rng(40 * 30), 40, 30)
+    hub = int(grid[100, 0])
+    uses = int((grid == hub).sum())
+    assert uses <= 6
+    far = grid[(grid != hub).all(1)][-40:]
+
+    def fan(extra):
+        t = far[:extra].copy()
+        t[:, 0] = hub
+        return np.concatenate([grid[:110], t, grid[110:]])
+
+    packer = native.TransferPacker(0, len(v), len(grid) + 40)
+    tri = fan(17 - uses)
+    assert int((tri == hub).sum()) == 17
+    assert _pack(v, tri, packer) == orc.transfer_frame(v, tri) and _pack.last_path == 2
+    tri = fan(16 - uses)
+    assert int((tri == hub).sum()) == 16
+    got = _pack(v, tri, packer)
+    assert _pack.last_path == 1
+    assert got == _pack(v, tri) == orc.transfer_frame(v, tri) and _pack.last_path == 1
+
+
+PLY_SIZES = (1, 2, 3, 4, 1023, 1024, 1025, 1026)
+
+
+@pytest.mark.parametrize("normals", [False, True])
+def test_ply_records_at_every_count_and_alignment(gpu, orc, normals):
+    """lsnPlyPack / lsnPlyPackNormals pack four records per lane and 1024 per block: every count mod 4, exactly one block and one record
+    into the next, of vertices and of faces, at each of the four alignments of the output, between guard bytes."""
+    import torch
+    from tests.support import Guarded
+    from tests.test_normals_gpu import ply_with_normals
+    rng = np.random.default_rng(1026)
+    v = _cloud(rng, 1026)
+    nrm = rng.normal(size=(1026, 3)).astype(np.float32)
+    dn = torch.from_numpy(nrm).cuda()
+    for i, nv in enumerate(PLY_SIZES):
+        nt = PLY_SIZES[(i + 3) % len(PLY_SIZES)]
+        tri = rng.integers(0, nv, size=(nt, 3)).astype(np.int32)
+        dv, dt = _device(v[:nv], tri)
+        want = ply_with_normals(v[:nv], nrm[:nv], tri) if normals else orc.ply_binary(v[:nv], tri)
+        need = native.ply_normals_bytes(nv, nt) if normals else native.ply_binary_bytes(nv, nt)
+        assert need == len(want)
+        for shift in range(4):
+            buf = Guarded(torch, need + shift, "cuda")
+            if normals:
+                n = native.ply_pack_normals(0, dv.data_ptr(), dn.data_ptr(), nv, dt.data_ptr(), nt, buf.ptr + shift, need)
+            else:
+                n = native.ply_pack(0, dv.data_ptr(), nv, dt.data_ptr(), nt, buf.ptr + shift, need)
+            torch.cuda.synchronize()
+            assert n == need and buf.intact() and (buf.body()[:shift] == 0xA5).all()
+            assert buf.body()[shift:].cpu().numpy().tobytes() == want, (nv, nt, shift)
+
+
+# lsnTransferFrameBound of the build before the stream's size and the chunk bound were each written once
+FRAME_BOUNDS = {(0, 0): 28, (1, 0): 43, (64997, 0): 974991, (64998, 0): 975006, (100, 21665): 1234933, (100, 21666): 1234998}
+
+
+@pytest.mark.parametrize("nv,nt", sorted(FRAME_BOUNDS))
+def test_frame_bound_holds_the_stream_and_keeps_its_value(gpu, orc, nv, nt):
+    """Either side of a vertex chunk's 64997 vertices and of 3 nt = 64997 index positions: the bound is what it was, and the packed
+    stream (the reference's bytes) fits it."""
+    rng = np.random.default_rng(nv + nt)
+    v = _cloud(rng, nv)
+    tri = rng.integers(0, max(nv, 1), size=(nt, 3)).astype(np.int32)
+    assert native.transfer_frame_bound(nv, nt) == FRAME_BOUNDS[nv, nt]
+    got = _pack(v, tri)
+    assert got == orc.transfer_frame(v, tri) and len(got) <= FRAME_BOUNDS[nv, nt]
 
 
 @pytest.mark.parametrize("seed", range(12))
