@@ -11,8 +11,10 @@
 //             (nx, ny, nz between z and red; lsnLastMeshPlyNormals, which takes --lod's CELL as its own argument).  With
 //             --min-fragment N both go through the fragment filter first (connected components of fewer than N vertices dropped:
 //             lsnLastMeshTransferFrameFragments, lsnLastMeshPlyFragments, which take CELL and the normals switch as arguments).
+//             With --smooth ITERATIONS,LAMBDA,MU both get Taubin smoothing behind those two stages and in front of the normals,
+//             open vertices pinned (lsnLastMeshTransferFrameSmooth, lsnLastMeshPlySmooth, which take all of the above as arguments).
 //
-//   stream --calib calib.bin [--bounds 6 floats] [--min-fragment N] [--lod CELL] [--normals] [--frames-out f.bin] [--ply mesh.ply] rec0.bin rec1.bin ...
+//   stream --calib calib.bin [--bounds 6 floats] [--min-fragment N] [--lod CELL] [--smooth I,L,M] [--normals] [--frames-out f.bin] [--ply mesh.ply] rec0.bin rec1.bin ...
 //   calib.bin: per sensor 7 f32 intrinsics + 12 f32 pose (the arrays KinectServer passes, KinectServer.cs:470-490)
 //
 // Build: make -C examples stream   (links -lNativeUtils only)
@@ -51,7 +53,8 @@ int main(int argc, char **argv)
     const char *calib = nullptr, *frames_out = nullptr, *ply = nullptr;
     bool lod = false, normals = false, fragments = false;
     float cell = 0.0f;
-    int min_fragment = 0;
+    int min_fragment = 0, iterations = 0;
+    float lambda = 0.5f, mu = -0.53f;
     std::vector<const char *> recs;
     for (int i = 1; i < argc; i++) {
         if (!strcmp(argv[i], "--calib") && i + 1 < argc) calib = argv[++i];
@@ -59,12 +62,15 @@ int main(int argc, char **argv)
         else if (!strcmp(argv[i], "--ply") && i + 1 < argc) ply = argv[++i];
         else if (!strcmp(argv[i], "--lod") && i + 1 < argc) { lod = true; cell = (float)atof(argv[++i]); }
         else if (!strcmp(argv[i], "--min-fragment") && i + 1 < argc) { fragments = true; min_fragment = atoi(argv[++i]); }
+        else if (!strcmp(argv[i], "--smooth") && i + 1 < argc) {
+            if (sscanf(argv[++i], "%d,%f,%f", &iterations, &lambda, &mu) != 3 || iterations <= 0) { fprintf(stderr, "--smooth: expected ITERATIONS,LAMBDA,MU, e.g. 10,0.5,-0.53\n"); return 2; }
+        }
         else if (!strcmp(argv[i], "--normals")) normals = true;
         else if (!strcmp(argv[i], "--bounds") && i + 6 < argc) { for (int k = 0; k < 6; k++) b[k] = (float)atof(argv[++i]); }
         else recs.push_back(argv[i]);
     }
     const int n = (int)recs.size();
-    if (!calib || n == 0) { fprintf(stderr, "usage: %s --calib calib.bin [--bounds 6 floats] [--min-fragment N] [--lod CELL] [--normals] [--frames-out f.bin] [--ply mesh.ply] rec0.bin ...\n", argv[0]); return 2; }
+    if (!calib || n == 0) { fprintf(stderr, "usage: %s --calib calib.bin [--bounds 6 floats] [--min-fragment N] [--lod CELL] [--smooth I,L,M] [--normals] [--frames-out f.bin] [--ply mesh.ply] rec0.bin ...\n", argv[0]); return 2; }
     std::vector<unsigned char> cal;
     if (!read_all(calib, cal) || cal.size() != (size_t)n * 19 * 4) { fprintf(stderr, "calib: expected %d x 19 floats\n", n); return 1; }
     std::vector<float> intr(7 * (size_t)n), wt(12 * (size_t)n);
@@ -112,28 +118,35 @@ int main(int argc, char **argv)
         const int nv = mesh.nVertices, nt = mesh.nTriangles;
         deleteMesh(&mesh);
         if (nv == 0) { char e[8]; if (lsnGetLastError(e, sizeof e) > 0) return fail("generateMeshFromDepthMaps"); }
-        const long long bound = fragments ? lsnLastMeshTransferFrameFragments(min_fragment, cell, nullptr, 0)   // (Fragments, Lod: an upper bound)
-                                : lod     ? lsnLastMeshTransferFrameLod(cell, nullptr, 0)
-                                          : lsnLastMeshTransferFrame(nullptr, 0);
+        const bool smooth = iterations > 0;
+        const long long bound = smooth      ? lsnLastMeshTransferFrameSmooth(min_fragment, cell, iterations, lambda, mu, 1, nullptr, 0)
+                                : fragments ? lsnLastMeshTransferFrameFragments(min_fragment, cell, nullptr, 0)   // (Smooth, Fragments, Lod: an upper bound)
+                                : lod       ? lsnLastMeshTransferFrameLod(cell, nullptr, 0)
+                                            : lsnLastMeshTransferFrame(nullptr, 0);
         if (bound < 0) return fail("lsnLastMeshTransferFrame");
         wire.resize((size_t)bound);
-        const long long len = fragments ? lsnLastMeshTransferFrameFragments(min_fragment, cell, wire.data(), bound)
-                              : lod     ? lsnLastMeshTransferFrameLod(cell, wire.data(), bound)
-                                        : lsnLastMeshTransferFrame(wire.data(), bound);
-        if (len < 0) return fail(fragments ? "lsnLastMeshTransferFrameFragments" : "lsnLastMeshTransferFrame");
+        const long long len = smooth      ? lsnLastMeshTransferFrameSmooth(min_fragment, cell, iterations, lambda, mu, 1, wire.data(), bound)
+                              : fragments ? lsnLastMeshTransferFrameFragments(min_fragment, cell, wire.data(), bound)
+                              : lod       ? lsnLastMeshTransferFrameLod(cell, wire.data(), bound)
+                                          : lsnLastMeshTransferFrame(wire.data(), bound);
+        if (len < 0) return fail(smooth ? "lsnLastMeshTransferFrameSmooth" : fragments ? "lsnLastMeshTransferFrameFragments" : "lsnLastMeshTransferFrame");
         if (fo) fwrite(wire.data(), 1, (size_t)len, fo);
         sent += len;
         printf("tick %d: %d vertices, %d triangles -> %lld bytes on the wire\n", ticks, nv, nt, len);
     }
     if (fo) fclose(fo);
     if (ply && ticks > 0) {
-        long long need = fragments ? lsnLastMeshPlyFragments(min_fragment, cell, normals, nullptr, 0)
-                         : normals ? lsnLastMeshPlyNormals(cell, nullptr, 0)
-                         : lod     ? lsnLastMeshPlyLod(cell, nullptr, 0)
-                                   : lsnLastMeshPly(nullptr, 0);
-        if (need < 0) return fail(fragments ? "lsnLastMeshPlyFragments" : normals ? "lsnLastMeshPlyNormals" : "lsnLastMeshPly");
+        const bool smooth = iterations > 0;
+        long long need = smooth      ? lsnLastMeshPlySmooth(min_fragment, cell, iterations, lambda, mu, 1, normals, nullptr, 0)
+                         : fragments ? lsnLastMeshPlyFragments(min_fragment, cell, normals, nullptr, 0)
+                         : normals   ? lsnLastMeshPlyNormals(cell, nullptr, 0)
+                         : lod       ? lsnLastMeshPlyLod(cell, nullptr, 0)
+                                     : lsnLastMeshPly(nullptr, 0);
+        if (need < 0) return fail(smooth ? "lsnLastMeshPlySmooth" : fragments ? "lsnLastMeshPlyFragments" : normals ? "lsnLastMeshPlyNormals" : "lsnLastMeshPly");
         wire.resize((size_t)need);
-        if (fragments) {
+        if (smooth) {
+            if ((need = lsnLastMeshPlySmooth(min_fragment, cell, iterations, lambda, mu, 1, normals, wire.data(), need)) < 0) return fail("lsnLastMeshPlySmooth");
+        } else if (fragments) {
             if ((need = lsnLastMeshPlyFragments(min_fragment, cell, normals, wire.data(), need)) < 0) return fail("lsnLastMeshPlyFragments");
         } else if (normals) {
             if ((need = lsnLastMeshPlyNormals(cell, wire.data(), need)) < 0) return fail("lsnLastMeshPlyNormals");

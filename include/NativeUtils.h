@@ -442,6 +442,49 @@ int lsnFusionNormals(LsnFusion *plan, const void *d_vertices, const int *d_offse
                      void *d_normals_out, void *stream);
 int lsnFusionNormalsDiagnostics(LsnFusion *plan, int tick, int *n_used, int *n_skipped, int *n_zero_normals, void *stream);
 
+/* Mesh smoothing: Taubin's lambda|mu filter on the merged mesh of every tick (what lsnFusionRunMesh or any stage above left in d_vertices
+ * / d_offsets / d_triangles / d_tri_offsets, read only), bit-exact whatever order the device takes the triangles in.  The reference moves
+ * no vertex: the stage is defined here (tests/smooth_ref.py restates it).  Per tick, on its own: nVertices =
+ * d_offsets[n_maps] clipped to [0, lsnFusionTickCapacity()], nTriangles = d_tri_offsets[n_maps] clipped to [0,
+ * lsnFusionTickTriangleCapacity()].  Vertices are the 16-byte records {colour, x, y, z}.
+ * ONE PASS with factor f goes from positions P to positions P', both float, and reads only P (Jacobi, never half-updated positions).
+ * Used triangle: a triangle is USED iff it has three indices in [0, nVertices), the indices are pairwise distinct, and all nine
+ * coordinates of its corners in P satisfy fabsf(c) < 4096.0f, which NaN and +-inf fail.  Anything else contributes nothing and is counted
+ * as skipped.
+ * Fixed point: q(c) = (int64) trunc(c * 2^32).  The float multiply by a power of two is exact, the product is below 2^44, and truncation
+ * is toward zero.  Anything below 2^-32 m becomes 0, so denormal flushing cannot matter.
+ * Sums: a used triangle (i0, i1, i2) adds the positions of a corner's two other corners to that corner.  For corner a with other corners
+ * b, c and each component: S[a] += q(P[b]) + q(P[c]), and N[a] += 2.  S is three signed 64-bit sums per vertex, two's complement with
+ * wrap-around; N is a 32-bit count.  An edge shared by two triangles therefore weighs twice and a border edge once: that is part of the
+ * definition, there is no de-duplication.  Only integer adds enter, so the bytes cannot depend on the order of the atomics.
+ * New position: if N[a] == 0, or the vertex is pinned (below), then P'[a] = P[a] bit for bit.  Otherwise, per component: m = (float)
+ * (((double) S / (double) N) * 2^-32) -- one round-to-nearest-even conversion of S to double, one correctly rounded double division, an
+ * exact scaling, one rounding to float -- then d = m - p and p' = p + f * d in float, every operation rounded on its own, nothing fused.
+ * The colour word is carried over.
+ * OPEN VERTICES are found once per call from the indices alone; coordinates play no part.  For every triangle that is in range and
+ * pairwise distinct, and every corner a with next corner n and previous corner p in the triangle's own order: H[a] += mix(n) - mix(p),
+ * as unsigned 64-bit with wrap.  mix is the splitmix64 finaliser of the index: add 0x9E3779B97F4A7C15; x ^= x >> 30, then multiply by
+ * 0xBF58476D1CE4E5B9; x ^= x >> 27, then multiply by 0x94D049BB133111EB; x ^= x >> 31.  A vertex with at least one such triangle is OPEN
+ * iff H[a] != 0: the multiset of its "next" neighbours differs from that of its "previous" neighbours, some incident edge is not matched
+ * by its opposite.  With pin_boundary != 0, open vertices are pinned in every pass.
+ * THE FILTER: iterations in [1, 64], lambda in (0, 1], mu in [-1, 0].  Each iteration is one pass with lambda, then one with mu; with
+ * mu == 0 the second pass is left out, which gives plain Laplacian smoothing.  Usual values: 10, 0.5, -0.53.
+ * Refused, with a message and no output touched: a null argument; NaN or a value out of range; d_triangles == NULL; an output that
+ * overlaps an input.
+ * d_vertices_out: [n_ticks][lsnFusionTickCapacity()] 16-byte records; only the first nVertices of each tick are written.  Offsets and
+ * triangles are unchanged, so the caller hands the input's own rows to whatever follows.  Asynchronous on `stream`; returns 0, -1 with
+ * a message.
+ * Scratch, the plan's own, reserved by the first call, grown when a later call needs more, freed with the plan (a plan that never
+ * smooths has none), per vertex and tick: 24 bytes of sums (three planes [n_ticks][3][lsnFusionTickCapacity()] of int64), 4 of count, 8
+ * of H, 1 of flag and 16 of the vertex buffer the passes take turns on with d_vertices_out (none for a call of one pass): 8 x 512x424
+ * sensors, one tick = 92.0 MB; and 16 bytes of counters per tick.
+ * lsnFusionSmoothDiagnostics (synchronises `stream`): for one tick of the plan's last call the used and the skipped triangles of the
+ * last pass, the pinned vertices (0 with pin_boundary == 0) and the vertices with N == 0 in the last pass; any pointer may be NULL.
+ * Returns 0, -1 on error or before any call. */
+int lsnFusionSmooth(LsnFusion *plan, int iterations, float lambda, float mu, int pin_boundary, const void *d_vertices, const int *d_offsets,
+                    const void *d_triangles, const int *d_tri_offsets, void *d_vertices_out, void *stream);
+int lsnFusionSmoothDiagnostics(LsnFusion *plan, int tick, int *n_used, int *n_skipped, int *n_pinned, int *n_isolated, void *stream);
+
 /* Flying-pixel filter (LiveScanClient's KinectCapture::filterFlyingPixels, src/LiveScanClient/kinectCapture.cpp:132-174, with the server's
  * bFilterFlyingPixels / nFPNeighbourhoodSize / nFPThreshold, LiveScanServer/KinectSettings.cs:34-37) on all n_ticks x n_maps depth maps of
  * the plan, in front of the radial correction: a pixel with `neighbourhood` <= x < w - neighbourhood and the same for y (value 0 included)
@@ -833,6 +876,15 @@ long long lsnLastMeshPlyNormals(float cell, unsigned char *out, long long out_ca
  * resident mesh is not changed. */
 long long lsnLastMeshTransferFrameFragments(int min_vertices, float cell, unsigned char *out, long long out_cap);
 long long lsnLastMeshPlyFragments(int min_vertices, float cell, int with_normals, unsigned char *out, long long out_cap);
+/* The same two with mesh smoothing: open, fragments if min_vertices > 1, level of detail if cell > 0, lsnFusionSmooth's stage with
+ * (iterations, lambda, mu, pin_boundary), normals if asked, pack -- each on what the one before left, as one tick of one sensor, in
+ * HBM.  iterations <= 0: byte for byte what the Fragments calls return.  out == NULL: the same upper bound as theirs (the stage moves
+ * vertices and drops none).  With iterations > 0: -1 with a message for a resident mesh without triangles and for what lsnFusionSmooth
+ * refuses.  The resident mesh is not changed. */
+long long lsnLastMeshPlySmooth(int min_vertices, float cell, int iterations, float lambda, float mu, int pin_boundary, int with_normals,
+                               unsigned char *out, long long out_cap);
+long long lsnLastMeshTransferFrameSmooth(int min_vertices, float cell, int iterations, float lambda, float mu, int pin_boundary,
+                                         unsigned char *out, long long out_cap);
 
 /* Inbound (host-side parsing, no device work): the client's frame message -- LiveScanClient::SerializeFrame
  * (src/LiveScanClient/liveScanClient.cpp:185-290) as KinectSocket.ReceiveFrame reads it

@@ -629,8 +629,9 @@ extern "C" int lsnIcpPointToPlane(Point3f *verts1, Point3f *normals1, Point3f *v
 namespace {
 // The exports below as steps on the mesh the calling thread's last mesh call left: the lane is picked and locked here; `resident` says
 // whether there is a mesh (from then on nv / nt are its counts, and a call that only asks for a length is answered); `open` puts it into
-// HBM and makes it a batch of one tick of one "sensor" whose offset rows are its two counts; `fragments`, `lod` and `normals` run their
-// stage on what the step before left, `render`, `frame` and `ply` bring the result home.  Locks: the lane's, then c.wire_mu from `open` on.
+// HBM and makes it a batch of one tick of one "sensor" whose offset rows are its two counts; `fragments`, `lod`, `smooth` and `normals`
+// run their stage on what the step before left, `render`, `frame` and `ply` bring the result home.  Locks: the lane's, then c.wire_mu
+// from `open` on.
 struct LastMesh {
     Ctx &c;
     Lane &l;
@@ -709,6 +710,14 @@ struct LastMesh {
         d_v = c.d_frag_v.p;
         d_t = c.d_frag_t.as<int>();
         d_rows = out_rows;
+        return 0;
+    }
+    // Taubin smoothing (smooth.hip), in HBM, behind `lod`: the later steps see the moved vertices; the rows and the triangles stay
+    int smooth(const char *who, int iterations, float lambda, float mu, int pin_boundary)
+    {
+        if (c.d_sm_v.reserve(16 * (size_t)(nv0 > 0 ? nv0 : 1))) return -1;
+        if (lsn::smooth(c.sm, who, batch(), iterations, lambda, mu, pin_boundary, c.d_sm_v.p, l.stream)) return -1;
+        d_v = c.d_sm_v.p;
         return 0;
     }
     // the vertex normals (normals.hip) of that mesh into c.d_nm
@@ -875,6 +884,52 @@ extern "C" long long lsnLastMeshPlyFragments(int min_vertices, float cell, int w
         if (!out) return bound;
         if (m.open(bound) || m.fragments("lsnLastMeshPlyFragments", min_vertices) || (cell > 0.0f && m.lod("lsnLastMeshPlyFragments", cell)) ||
             (with_normals && m.normals("lsnLastMeshPlyFragments")))
+            return -1;
+        return m.ply(bound, with_normals != 0, out, out_cap);
+    });
+}
+
+// The same two with Taubin smoothing (smooth.hip) between the level of detail and the normals: open, fragments, lod, smooth, normals,
+// pack.  iterations <= 0: the Fragments exports' bytes; out == NULL: their bound (the stage moves vertices and drops none).  With
+// iterations > 0 a resident mesh without triangles is refused, and so is what lsnFusionSmooth refuses.
+extern "C" long long lsnLastMeshTransferFrameSmooth(int min_vertices, float cell, int iterations, float lambda, float mu, int pin_boundary,
+                                                    unsigned char *out, long long out_cap)
+{
+    return lsn::guarded("lsnLastMeshTransferFrameSmooth", -1LL, [&]() -> long long {
+        lsn::clear_error();
+        LastMesh m;
+        if (m.resident()) return -1;
+        if (iterations > 0 && m.nt <= 0) {
+            lsn::set_error("lsnLastMeshTransferFrameSmooth: the resident mesh has no triangles (a bare point cloud has no neighbours to smooth with)");
+            return -1;
+        }
+        const long long bound = std::max(lsnTransferFrameBound(m.nv, m.nt), lsnTransferFrameBound(m.nv, 0));
+        if (!out) return bound;
+        if (m.open(bound) || m.fragments("lsnLastMeshTransferFrameSmooth", min_vertices) ||
+            (cell > 0.0f && m.lod("lsnLastMeshTransferFrameSmooth", cell)) ||
+            (iterations > 0 && m.smooth("lsnLastMeshTransferFrameSmooth", iterations, lambda, mu, pin_boundary)))
+            return -1;
+        return m.frame(bound, out, out_cap);
+    });
+}
+
+extern "C" long long lsnLastMeshPlySmooth(int min_vertices, float cell, int iterations, float lambda, float mu, int pin_boundary, int with_normals,
+                                          unsigned char *out, long long out_cap)
+{
+    return lsn::guarded("lsnLastMeshPlySmooth", -1LL, [&]() -> long long {
+        lsn::clear_error();
+        LastMesh m;
+        if (m.resident()) return -1;
+        if ((with_normals || iterations > 0) && m.nt <= 0) {
+            lsn::set_error("lsnLastMeshPlySmooth: the resident mesh has no triangles (%s)", with_normals ? "the normals of a bare point cloud are not defined"
+                                                                                                      : "a bare point cloud has no neighbours to smooth with");
+            return -1;
+        }
+        const long long bound = with_normals ? lsnPlyNormalsBytes(m.nv, m.nt) : lsnPlyBinaryBytes(m.nv, m.nt);
+        if (!out) return bound;
+        if (m.open(bound) || m.fragments("lsnLastMeshPlySmooth", min_vertices) || (cell > 0.0f && m.lod("lsnLastMeshPlySmooth", cell)) ||
+            (iterations > 0 && m.smooth("lsnLastMeshPlySmooth", iterations, lambda, mu, pin_boundary)) ||
+            (with_normals && m.normals("lsnLastMeshPlySmooth")))
             return -1;
         return m.ply(bound, with_normals != 0, out, out_cap);
     });

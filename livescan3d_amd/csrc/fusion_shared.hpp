@@ -618,6 +618,7 @@ struct LsnFusion {
     lsn::SimplifyScratch sp;
     lsn::FragmentsScratch fr;            // (fragments.hip: the fourth stage on the merged mesh)
     lsn::NormalsScratch nm;
+    lsn::SmoothScratch sm;               // (smooth.hip: the stage that moves vertices)
     bool thr_valid = false;
     bool thr_enabled = true;             // $LSN_NO_THRESHOLDS=1 keeps the arithmetic count pass (ablation / tests)
     bool one_tick_single_pass = false;   // a one-tick plan of <= 2048 tiles takes the single pass (fuse_kernel<4>) instead of count -> scan -> write; $LSN_ONE_TICK_SINGLE_PASS=0 / 1 forces

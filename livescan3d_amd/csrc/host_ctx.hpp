@@ -168,7 +168,8 @@ struct Ctx {
     lsn::SimplifyScratch sp;
     lsn::FragmentsScratch fr;
     lsn::NormalsScratch nm;
-    lsn::DevBuf d_lod_v, d_lod_t, d_frag_v, d_frag_t, d_nm, d_rv_img;
+    lsn::SmoothScratch sm;
+    lsn::DevBuf d_lod_v, d_lod_t, d_frag_v, d_frag_t, d_sm_v, d_nm, d_rv_img;
     bool warned_flags = false;
 };
 

@@ -224,6 +224,20 @@ struct NormalsScratch {
 int normals(NormalsScratch &ns, const char *who, const MeshBatch &m, void *d_normals_out, LsnFusion *prof, hipStream_t s);
 int normals_counts(NormalsScratch &ns, const char *who, int tick, int *n_used, int *n_skipped, int *n_zero_normals, hipStream_t s);
 
+// Mesh smoothing (smooth.hip): what one stage keeps between calls -- the sums, three planes [n_ticks][3][vertices per tick] of i64, the
+// counts N (u32), the open-vertex hashes H (u64) and the pinned flags (a byte), each [n_ticks][vertices per tick], the vertex buffer the
+// passes take turns on with the output (16 B per vertex; a call of one pass needs none), and the counters behind
+// lsnFusionSmoothDiagnostics: 53 B per vertex.  Reserved by the first call, grown by a call that needs more; the counted vertices are
+// cleared by every call.
+struct SmoothScratch {
+    DevBuf acc, num, hash, flag, verts;
+    StageCounters cnt;                // per tick
+};
+// d_vertices_out: tick_vert 16-byte records per tick; refuses iterations outside [1, 64], lambda outside (0, 1], mu outside [-1, 0].
+int smooth(SmoothScratch &ss, const char *who, const MeshBatch &m, int iterations, float lambda, float mu, int pin_boundary, void *d_vertices_out,
+           hipStream_t s);
+int smooth_counts(SmoothScratch &ss, const char *who, int tick, int *n_used, int *n_skipped, int *n_pinned, int *n_isolated, hipStream_t s);
+
 // The radial correction (radial.hip): what one plan keeps between calls -- the sensors' parameters, the warp tables of the current
 // calibration ([pixels per tick][4] candidates and their compact form, one dword per destination) with the intrinsics they were built for,
 // the scratch maps and the winner array of the routes that warp through memory, and the hole closing's band list, hole bitmap, two

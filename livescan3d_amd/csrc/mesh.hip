@@ -623,3 +623,5 @@ int lsn::run_triangles_write(LsnFusion *p, const void *d_depth, void *d_triangle
 #include "fragments.hip"
 // Vertex normals (lsnFusionNormals): area-weighted, summed as 64-bit integers, of the mesh as any of the stages above left it.
 #include "normals.hip"
+// Mesh smoothing (lsnFusionSmooth): Taubin lambda|mu passes over the same mesh, the neighbour sums as 64-bit integers, in front of the normals.
+#include "smooth.hip"

@@ -37,7 +37,7 @@ class DeviceFusion:
         # (not cleared here: the benchmark and the drivers construct their plans this way; from_rigs() clears them)
         self.vertices = torch.empty((n_ticks, self.capacity, 16), dtype=torch.uint8, device=self.device)
         self.offsets = torch.full((n_ticks, self.n_maps + 1), SENTINEL, dtype=torch.int32, device=self.device)
-        self.depth = self.rgb = self.intr = self._triangles = self._tri_offsets = self._normals = None
+        self.depth = self.rgb = self.intr = self._triangles = self._tri_offsets = self._normals = self._smoothed = None
 
     @classmethod
     def from_rigs(cls, rigs, n_ticks=None, device=None, mode=0):
@@ -164,6 +164,19 @@ class DeviceFusion:
                           (self.triangles if triangles is None else triangles).data_ptr(),
                           (self.tri_offsets if tri_offsets is None else tri_offsets).data_ptr(), self._normals.data_ptr(), _stream_handle(stream))
         return self._normals
+
+    def smooth(self, iterations, lam, mu, pin_boundary=True, vertices=None, offsets=None, triangles=None, tri_offsets=None, stream=None):
+        """Taubin lambda|mu smoothing of the ticks' meshes -- the batch's own, or the four tensors handed in (fragments()'s first four
+        outputs, say).  Returns uint8 [T, capacity, 16], the batch's own tensor (allocated by the first call with every byte SENTINEL %
+        256, written again by every call): the first nVertices records of a tick are its moved vertices, nothing behind them is written;
+        offsets and triangles stay the input's."""
+        if self._smoothed is None:
+            self._smoothed = torch.full((self.n_ticks, self.capacity, 16), SENTINEL % 256, dtype=torch.uint8, device=self.device)
+        self.plan.smooth(iterations, lam, mu, pin_boundary, (self.vertices if vertices is None else vertices).data_ptr(),
+                         (self.offsets if offsets is None else offsets).data_ptr(),
+                         (self.triangles if triangles is None else triangles).data_ptr(),
+                         (self.tri_offsets if tri_offsets is None else tri_offsets).data_ptr(), self._smoothed.data_ptr(), _stream_handle(stream))
+        return self._smoothed
 
     def refine(self, tick, n_refine_iters=2, n_icp_iters=10, world_R=None, world_t=None, camera_R=None, camera_t=None, clouds_out=None,
                stream=None):

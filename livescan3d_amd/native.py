@@ -104,6 +104,8 @@ _PROTOTYPES = {
     "lsnFusionFragmentsDiagnostics": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp]),
     "lsnFusionNormals": (_i, [_vp] * 7),
     "lsnFusionNormalsDiagnostics": (_i, [_vp, _i, _vp, _vp, _vp, _vp]),
+    "lsnFusionSmooth": (_i, [_vp, _i, _f, _f, _i] + [_vp] * 6),
+    "lsnFusionSmoothDiagnostics": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp]),
     "lsnFusionTilesPerTick": (_i, [_vp]),
     "lsnFusionPackSurvivors": (_i, [_vp] * 9),
     "lsnFusionReconstruct": (_i, [_vp, _i, _i, _vp, _vp, _vp, _ll, _vp, _vp, _vp, _vp, _vp]),
@@ -169,6 +171,8 @@ _PROTOTYPES = {
     "lsnLastMeshPlyNormals": (_ll, [_f, _vp, _ll]),
     "lsnLastMeshTransferFrameFragments": (_ll, [_i, _f, _vp, _ll]),
     "lsnLastMeshPlyFragments": (_ll, [_i, _f, _i, _vp, _ll]),
+    "lsnLastMeshPlySmooth": (_ll, [_i, _f, _i, _f, _f, _i, _i, _vp, _ll]),
+    "lsnLastMeshTransferFrameSmooth": (_ll, [_i, _f, _i, _f, _f, _i, _vp, _ll]),
     "lsnZstdAvailable": (_i, []),
     "lsnFrameParseHeader": (_i, [_vp, C.POINTER(FrameInfo)]),
     "lsnFrameDecode": (_ll, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _i, C.POINTER(_i)]),
@@ -815,6 +819,21 @@ class FusionPlan(_Handle):
                "lsnFusionNormalsDiagnostics")
         return {"used": u.value, "skipped": k.value, "zero_normals": z.value}
 
+    def smooth(self, iterations, lam, mu, pin_boundary, d_vertices, d_offsets, d_triangles, d_tri_offsets, d_vertices_out, stream=0):
+        """Taubin lambda|mu smoothing of every tick's merged mesh (run_mesh's layouts) into d_vertices_out, uint8 [n_ticks, capacity, 16]:
+        `iterations` times a pass with `lam` and one with `mu` (0: plain Laplacian), open vertices pinned if asked; offsets and triangles
+        stay the input's.  Out of place, asynchronous; DESIGN.md section 21."""
+        _check(lib().lsnFusionSmooth(self._h, int(iterations), float(lam), float(mu), 1 if pin_boundary else 0, d_vertices, d_offsets,
+                                     d_triangles or None, d_tri_offsets or None, d_vertices_out, stream or None), "lsnFusionSmooth")
+
+    def smooth_diagnostics(self, tick=0, stream=0):
+        """The last smooth() of one tick: {"used", "skipped": triangles of the last pass that entered the sums / did not, "pinned": open
+        vertices held in place, "isolated": vertices without a used triangle in the last pass}."""
+        u, k, p, z = C.c_int(0), C.c_int(0), C.c_int(0), C.c_int(0)
+        _check(lib().lsnFusionSmoothDiagnostics(self._h, int(tick), C.byref(u), C.byref(k), C.byref(p), C.byref(z), stream or None),
+               "lsnFusionSmoothDiagnostics")
+        return {"used": u.value, "skipped": k.value, "pinned": p.value, "isolated": z.value}
+
     def thresholds(self, capacity=None, stream=0, copy=True):
         """Builds the per-pixel depth thresholds now.  Returns (table uint32[capacity] or None, build_ms); table is None when
         the plan does not use thresholds ($LSN_NO_THRESHOLDS=1)."""
@@ -1111,6 +1130,22 @@ def last_mesh_ply_fragments(min_vertices, cell=0.0, with_normals=False):
     vertex clustering with cell size `cell` (<= 0: off), with vertex normals if asked."""
     fn = lib().lsnLastMeshPlyFragments
     return _last_mesh(lambda out, cap: fn(int(min_vertices), float(cell), 1 if with_normals else 0, out, cap), "lsnLastMeshPlyFragments")
+
+
+def last_mesh_ply_smooth(min_vertices=0, cell=0.0, iterations=10, lam=0.5, mu=-0.53, pin_boundary=True, with_normals=False):
+    """lsnLastMeshPlySmooth: last_mesh_ply_fragments with Taubin smoothing (iterations <= 0: off) between the level of detail and the
+    normals."""
+    fn = lib().lsnLastMeshPlySmooth
+    return _last_mesh(lambda out, cap: fn(int(min_vertices), float(cell), int(iterations), float(lam), float(mu), 1 if pin_boundary else 0,
+                                          1 if with_normals else 0, out, cap), "lsnLastMeshPlySmooth")
+
+
+def last_mesh_transfer_frame_smooth(min_vertices=0, cell=0.0, iterations=10, lam=0.5, mu=-0.53, pin_boundary=True):
+    """lsnLastMeshTransferFrameSmooth: last_mesh_transfer_frame_fragments with Taubin smoothing (iterations <= 0: off) behind the level
+    of detail."""
+    fn = lib().lsnLastMeshTransferFrameSmooth
+    return _last_mesh(lambda out, cap: fn(int(min_vertices), float(cell), int(iterations), float(lam), float(mu), 1 if pin_boundary else 0,
+                                          out, cap), "lsnLastMeshTransferFrameSmooth")
 
 
 def last_mesh_render_view(intr7, wt12, width, height, points_only=False):
