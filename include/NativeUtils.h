@@ -553,6 +553,60 @@ int lsnFusionDepthSmooth(LsnFusion *plan, const void *d_depth_in, void *d_depth_
 int lsnFusionDepthSmoothDiagnostics(LsnFusion *plan, int tick, int *changed_per_sensor, long long *abs_change_per_sensor, void *stream);
 int lsnSetDepthSmooth(int radius, float sigma_s, float sigma_r, int *prev_radius, float *prev_sigma_s, float *prev_sigma_r);
 
+/* The temporal depth filter: a range-gated recursive mean ACROSS TICKS on the raw depth maps, in front of the flying-pixel filter (order:
+ * temporal -> flying pixels -> depth smoothing -> radial correction).  It removes what no single-frame stage can: per-pixel noise that is
+ * independent from tick to tick (shimmer) and pixels that drop out for a tick or two (flicker holes).  The reference has no such step; the
+ * stage is DEFINED here, tests/temporal_ref.py restates this text in numpy int64 and the kernel is held to the restatement bit for bit, in
+ * maps and in state.  Integers only.
+ * Inputs: per tick one u16 map D (millimetres, 0 = no sample) per sensor.
+ * Parameters: alpha_q in 1..256, the weight of the new sample in 1/256; delta in 1..4095 mm, the gate; persist in 0..255, how many
+ * consecutive ticks a missing sample is served from history.
+ * State: one u32 word per pixel, F | miss << 24.  F is the filtered depth in 1/256 mm; it lies in 256 .. 65535 * 256 (below 2^24), and
+ * F == 0 means no history.  miss counts the consecutive ticks served from history.  The word 0 is "no history": a zeroed buffer is a reset.
+ * Per pixel and tick, with sample c:
+ *   1. Blend: c != 0, F != 0 and |256 c - F| <= 256 delta.  F' = F + floor((alpha_q (256 c - F) + 128) / 256), mathematical floor (the
+ *      product stays below 2^29: 32 bits are enough); miss' = 0; out = floor((F' + 128) / 256).
+ *   2. Restart: c != 0 otherwise (no history, or the gate failed because of motion or an edge).  F' = 256 c, miss' = 0, out = c.
+ *   3. Fill: c == 0, F != 0 and miss < persist.  F' = F, miss' = miss + 1, out = floor((F + 128) / 256).
+ *   4. Expire or empty: c == 0 otherwise.  The state word becomes 0 and out = 0.
+ * Consequences: F' of a blend lies between F and 256 c; out lies in [1, 65535] wherever something is served; alpha_q = 256 with
+ * persist = 0 is the identity on the maps; the pass is pointwise, so it may run in place; ticks are sequential per pixel, so a call of n
+ * ticks equals n calls of one tick, byte for byte, in maps and in state.  Lag is by design: a surface that moves by less than delta per
+ * tick keeps being blended and lags behind itself (by up to (256 - alpha_q) / alpha_q steps); one that moves further restarts.
+ * Because the stage runs on the raw samples in front of the flying-pixel filter, a pixel that filter removes is never filled back in, and a
+ * pixel served from history still passes that filter.
+ * lsnFusionSetTemporal: the plan's setting.  alpha_q <= 0: off (the default).  Out-of-range values are refused with a message (-1) and the
+ * previous setting stays in force.  Changing the setting keeps the history.
+ * lsnFusionTemporal: d_depth_in into d_depth_out ([n_ticks][pixels per tick] u16) on all ticks and sensors of the plan, in tick order; the
+ * plan's history advances by n_ticks.  Off: a device-to-device copy (nothing when in place), the history untouched.  d_depth_out ==
+ * d_depth_in is allowed; any other overlap is refused with nothing written.  Asynchronous on `stream`; a call on another stream than the
+ * previous call's first waits for that one.  The first filtering call reserves the history (4 bytes per pixel of ONE tick, zeroed) and four
+ * count words per 128 x 16 tile of every tick; a plan that never filters allocates nothing.
+ * lsnFusionTemporalReset: zeroes the history (asynchronous on `stream`).
+ * lsnFusionTemporalStateRead / lsnFusionTemporalStateWrite (both synchronise `stream`): the history as [pixels per tick] u32 in the layout
+ * of one tick's depth maps, to / from host memory -- a checkpoint of the history (before any filtering call: all 0).  Write refuses (-1,
+ * the history stays) a word whose F is outside {0} and 256 .. 65535 * 256, or whose F is 0 and miss is not.
+ * lsnFusionTemporalDiagnostics (synchronises `stream`): for tick `tick` of the plan's last call, per sensor (n_maps ints each, any pointer
+ * may be NULL) the pixels blended, restarted although they had history, filled from history, and expired; all 0 after a call with the
+ * stage off.  Returns 0, -1 on error or before any call.
+ * lsnSetTemporalFilter: the process-wide switch of the stage in the exports that START AT RAW FRAMES, depthMapAndColorSetRadialCorrection
+ * and lsnCorrectAndGenerateMesh: each such call is ONE tick, and what it writes back is the temporally filtered (then flying-filtered,
+ * smoothed) and corrected maps.  The history lives with the calling lane (on every device of $LSN_HOST_DEVICES: of that device's block),
+ * one word per pixel at the sensor's offset in the caller's arrays, whatever the grouping or host path; it is keyed by the rig (sensor
+ * count, widths, heights): a call with another rig, or lsnResetTemporalFilter, starts from no history.  generateMeshFromDepthMaps,
+ * generateVerticesFromDepthMap and lsnRefineFromDepthMaps never run the stage.  alpha_q <= 0: off.  Out-of-range values are refused (-1,
+ * the setting stays).  Initially $LSN_TEMPORAL_FILTER="alpha_q,delta,persist" (e.g. "64,20,2"; unset, malformed or refused: off, a
+ * refused value with a message on stderr); every call reads the current value.  The previous triple goes to prev_* (each may be NULL);
+ * returns 0. */
+int lsnFusionSetTemporal(LsnFusion *plan, int alpha_q, int delta, int persist);
+int lsnFusionTemporal(LsnFusion *plan, const void *d_depth_in, void *d_depth_out, void *stream);
+int lsnFusionTemporalReset(LsnFusion *plan, void *stream);
+int lsnFusionTemporalStateRead(LsnFusion *plan, unsigned int *h_state, void *stream);
+int lsnFusionTemporalStateWrite(LsnFusion *plan, const unsigned int *h_state, void *stream);
+int lsnFusionTemporalDiagnostics(LsnFusion *plan, int tick, int *blended, int *restarted, int *filled, int *expired, void *stream);
+int lsnSetTemporalFilter(int alpha_q, int delta, int persist, int *prev_alpha_q, int *prev_delta, int *prev_persist);
+int lsnResetTemporalFilter(void);
+
 /* Radial correction of n_ticks x n_maps frames in place in HBM (same layouts as lsnFusionRun's inputs);
  * intr_params: host, 7 floats per sensor {cx,cy,fx,fy,r2,r4,r6}. */
 int lsnFusionRadialCorrect(LsnFusion *plan, const float *intr_params, void *d_depth_maps, void *d_depth_colors, void *stream);
@@ -789,6 +843,14 @@ int lsnTickSetFlyingPixels(LsnTick *tick, int neighbourhood, int threshold);
  * smoothing run reserves.  radius <= 0: off (the default).  Returns 0; -1 with a message where lsnDepthSmoothGaussian refuses the triple,
  * which leaves the previous setting in place. */
 int lsnTickSetDepthSmooth(LsnTick *tick, int radius, float sigma_s, float sigma_r);
+/* The temporal depth filter (lsnFusionTemporal) as the tick's first stage: lsnTickRun then runs temporal -> flying pixels (if set) -> depth
+ * smoothing (if set) -> radial correction -> vertices -> triangles.  The tick object owns ONE history, which continues from run to run,
+ * and the pass runs once over the whole batch in tick order on the caller's stream, in front of the fork of a two-part tick, into scratch
+ * of the tick object (2 bytes per pixel per tick; history and scratch are reserved by the first run that filters); d_depth_in stays
+ * untouched.  alpha_q <= 0: off (the default); out-of-range values are refused (-1) and leave the previous setting; changing the setting
+ * keeps the history.  lsnTickTemporalReset zeroes the history (asynchronous on `stream`). */
+int lsnTickSetTemporal(LsnTick *tick, int alpha_q, int delta, int persist);
+int lsnTickTemporalReset(LsnTick *tick, void *stream);
 int lsnTickRun(LsnTick *tick, const void *d_depth_in, const void *d_colors_in, void *d_depth_corrected, void *d_colors_corrected,
                void *d_vertices, int *d_offsets, void *d_triangles, int *d_tri_offsets, void *stream);
 

@@ -265,6 +265,66 @@ static SmoothSetting &smooth_setting()
     return *s;
 }
 
+// The temporal depth filter of the same two exports, in front of the flying-pixel filter (lsnSetTemporalFilter): (alpha_q, delta, persist),
+// and the generation lsnResetTemporalFilter advances -- a lane whose history is of an older generation starts from none.  The other
+// exports never read it, for the flying pixels' reason: there the stage would run twice per tick.
+namespace {
+struct TemporalSwitch {
+    std::mutex mu;
+    lsn::TemporalSetting setting;
+    int alpha_q = 0, delta = 0, persist = 0;   // what an "off" setting was given, so that the previous triple goes back as it came
+    unsigned long long gen = 1;
+    std::vector<int> rig;                      // the rig of the last filtering call: sensor count, widths, heights
+    TemporalSwitch()
+    {
+        const char *e = getenv("LSN_TEMPORAL_FILTER");
+        if (!e || !*e) return;
+        int a = 0, d = 0, p = 0, used = 0;
+        if (sscanf(e, " %d , %d , %d %n", &a, &d, &p, &used) == 3 && e[used] == '\0') {
+            if (set(a, d, p) == 0) return;
+            fprintf(stderr, "[NativeUtils] $LSN_TEMPORAL_FILTER=\"%s\": %s: the temporal filter stays off\n", e, lsn::error_buffer());
+            lsn::clear_error();
+            return;
+        }
+        fprintf(stderr, "[NativeUtils] $LSN_TEMPORAL_FILTER=\"%s\" is not \"alpha_q,delta,persist\" (e.g. \"64,20,2\"): the temporal filter stays off\n", e);
+    }
+    // the new triple; refused (-1, with the message) it leaves the setting as it was
+    int set(int a, int d, int p)
+    {
+        if (lsn::temporal_setting_ok("lsnSetTemporalFilter", a, d, p)) return -1;
+        std::lock_guard<std::mutex> g(mu);
+        setting = a >= 1 ? lsn::TemporalSetting{a, d, p} : lsn::TemporalSetting{};
+        alpha_q = a;
+        delta = d;
+        persist = p;
+        return 0;
+    }
+    // what a call of this rig takes with it; a filtering call of another rig than the last one's starts a generation of its own, so that
+    // every lane -- the shards' too, which only ever see their blocks -- starts it from no history
+    void current(lsn::TemporalSetting &ts, unsigned long long &generation, int n_maps, const int *widths, const int *heights)
+    {
+        std::lock_guard<std::mutex> g(mu);
+        ts = setting;
+        if (ts.on() && n_maps > 0 && widths && heights) {
+            std::vector<int> now(1, n_maps);
+            now.insert(now.end(), widths, widths + n_maps);
+            now.insert(now.end(), heights, heights + n_maps);
+            if (now != rig) {
+                rig.swap(now);
+                gen++;
+            }
+        }
+        generation = gen;
+    }
+};
+}  // namespace
+
+static TemporalSwitch &temporal_switch()
+{
+    static auto *s = new TemporalSwitch();   // never destroyed, like the pairs above
+    return *s;
+}
+
 // What the three mesh exports share: `call` as `name` filled it (everything but the outlier filter's setting, which is read here) runs on
 // lane `l` of the context.  0: *out_mesh is the call's mesh; -1: the call was refused or failed, *out_mesh (if there is one) is empty and,
 // unless the caller merely passed no sensors, the message is set.
@@ -358,6 +418,37 @@ extern "C" int lsnSetDepthSmooth(int radius, float sigma_s, float sigma_r, int *
     });
 }
 
+extern "C" int lsnSetTemporalFilter(int alpha_q, int delta, int persist, int *prev_alpha_q, int *prev_delta, int *prev_persist)
+{
+    return lsn::guarded("lsnSetTemporalFilter", -1, [&]() {
+        lsn::clear_error();
+        TemporalSwitch &s = temporal_switch();
+        int a0, d0, p0;
+        {
+            std::lock_guard<std::mutex> g(s.mu);
+            a0 = s.alpha_q;
+            d0 = s.delta;
+            p0 = s.persist;
+        }
+        if (s.set(alpha_q, delta, persist)) return -1;
+        if (prev_alpha_q) *prev_alpha_q = a0;
+        if (prev_delta) *prev_delta = d0;
+        if (prev_persist) *prev_persist = p0;
+        return 0;
+    });
+}
+
+extern "C" int lsnResetTemporalFilter(void)
+{
+    return lsn::guarded("lsnResetTemporalFilter", -1, [&]() {
+        lsn::clear_error();
+        TemporalSwitch &s = temporal_switch();
+        std::lock_guard<std::mutex> g(s.mu);
+        s.gen++;   // every lane finds its history stale at its next filtering call
+        return 0;
+    });
+}
+
 extern "C" void generateMeshFromDepthMaps(int n_maps, unsigned char *depth_maps, unsigned char *depth_colors, int *widths, int *heights,
                                           float *intr_params, float *wtransform_params, Mesh *out_mesh, bool bcolor_transfer, float minX,
                                           float minY, float minZ, float maxX, float maxY, float maxZ, bool bgenerate_triangles)
@@ -429,6 +520,7 @@ extern "C" void lsnCorrectAndGenerateMesh(int n_maps, unsigned char *depth_maps,
         call.back_c = write_back_corrected ? depth_colors : nullptr;
         flying_setting().current(call.fp_neighbourhood, call.fp_threshold);
         call.smooth = smooth_setting().current();
+        temporal_switch().current(call.temporal, call.temporal_gen, n_maps, widths, heights);
         (void)mesh_export("lsnCorrectAndGenerateMesh", ctx().merge, call, out_mesh);
         return true;
     });
@@ -451,7 +543,10 @@ extern "C" void depthMapAndColorSetRadialCorrection(int n_maps, unsigned char *d
         int fp_n = 0, fp_t = 0;
         flying_setting().current(fp_n, fp_t);
         const std::shared_ptr<const lsn::DepthSmoothTables> smooth = smooth_setting().current();
-        radial_host(c, l, n_maps, depth_maps, depth_colors, widths, heights, intr_params, fp_n, fp_t, smooth.get());
+        lsn::TemporalSetting temporal;
+        unsigned long long temporal_gen = 0;
+        temporal_switch().current(temporal, temporal_gen, n_maps, widths, heights);
+        radial_host(c, l, n_maps, depth_maps, depth_colors, widths, heights, intr_params, fp_n, fp_t, smooth.get(), temporal, temporal_gen);
     });
 }
 

@@ -613,6 +613,12 @@ struct LsnFusion {
     lsn::DevBuf ds_table, ds_counts;
     int ds_last = 0;                     // what the last call was: 0 = none yet, 1 = a copy (off), 2 = the filter
     hipStream_t ds_stream = nullptr;     // ... and its stream
+    // temporal depth filter (temporal.hip): the setting of lsnFusionSetTemporal (off by default) and, allocated by the first filtering call
+    // (or lsnFusionTemporalStateWrite), the history -- one word per pixel of one tick -- and four words per 128 x 16 tile of every tick
+    lsn::TemporalSetting tp_setting;
+    lsn::DevBuf tp_state, tp_counts;
+    int tp_last = 0;                     // what the last call was: 0 = none yet, 1 = a copy (off), 2 = the filter
+    hipStream_t tp_stream = nullptr;     // ... and its stream
     // the three stages on the merged mesh (render.hip, simplify.hip, normals.hip): each one's scratch, allocated on its first call
     lsn::RenderScratch rv;
     lsn::SimplifyScratch sp;

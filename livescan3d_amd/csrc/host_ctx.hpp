@@ -55,6 +55,29 @@ struct Lane {
     lsn::DevBuf d_masked;     // a call with the outlier filter on: its depth maps with the removed vertices' pixels at 0 (allocated by the first such call)
     lsn::DevBuf d_flying;     // a call with the flying-pixel filter on: its raw depth maps filtered, what the radial correction then reads (allocated by the first such call)
     lsn::DevBuf d_smooth;     // a call with depth smoothing on: its (filtered) depth maps smoothed, what the radial correction then reads (allocated by the first such call)
+    // the temporal depth filter (temporal.hip, lsnSetTemporalFilter) of the calls that start at raw frames: its output, what the stages behind
+    // it then read; the history of the rig the lane sees call after call, one word per pixel at the sensor's offset in the call's arrays
+    // (so neither grouping nor the host path changes which word a pixel owns); the branch counts of the last launch.  The history is keyed
+    // by the rig (sensor count, widths, heights) and the reset generation: temporal_history() zeroes it when either changed.  All
+    // allocated by the first such call.
+    lsn::DevBuf d_temporal, tp_state, tp_counts;
+    std::vector<int> tp_rig;
+    unsigned long long tp_gen = 0;
+    int temporal_history(const int *widths, const int *heights, int count, unsigned long long gen)
+    {
+        std::vector<int> rig(1, count);
+        rig.insert(rig.end(), widths, widths + count);
+        rig.insert(rig.end(), heights, heights + count);
+        size_t pixels = 0;
+        for (int i = 0; i < count; i++) pixels += (size_t)widths[i] * heights[i];
+        if (tp_state.p && rig == tp_rig && gen == tp_gen) return 0;
+        const bool grown = !tp_state.p || tp_state.bytes < 4 * pixels;
+        if (lsn::temporal_state_reserve(tp_state, pixels, stream)) return -1;   // (a new buffer comes zeroed)
+        if (!grown) LSN_HIP(hipMemsetAsync(tp_state.p, 0, 4 * pixels, stream));
+        tp_rig.swap(rig);
+        tp_gen = gen;
+        return 0;
+    }
     // the lane's plans: key = n sensors, first sensor, widths..., heights...  Owned by the lane and only touched under its lock, so a
     // plan never runs on two lanes' streams at once and an eviction cannot pull a plan from under the other lane's call
     std::map<std::vector<int>, LsnFusion *> plans;
@@ -207,8 +230,18 @@ struct MeshCall {
                                                   //     of a call that starts with it (`radial`): it runs when flying_on(fp_neighbourhood)
     std::shared_ptr<const lsn::DepthSmoothTables> smooth;   // depth smoothing (depth_smooth.hip, lsnSetDepthSmooth) between that filter and the
                                                             //     correction of such a call: it runs when smooth_on(smooth.get())
+    lsn::TemporalSetting temporal;           // the temporal depth filter (temporal.hip, lsnSetTemporalFilter) in front of all of them in such a
+    unsigned long long temporal_gen = 0;     //     call: it runs when temporal_on(temporal); the generation of lsnResetTemporalFilter
 };
 
+// The one place that decides whether a call runs the temporal depth filter: the export found the process-wide switch on.
+inline bool temporal_on(const lsn::TemporalSetting &ts) { return ts.on(); }
+// The temporal filter of one plan's maps inside a flow, as ONE tick: `off` is where the plan's first sensor starts in the call's arrays
+// (bytes of u16 maps), which is where its words start in the lane's history; lane.d_temporal at `off` receives the filtered maps.
+inline int temporal_maps(Lane &l, LsnFusion *plan, const lsn::TemporalSetting &ts, size_t off, const void *in, hipStream_t s)
+{
+    return lsn::temporal(plan, ts, in, l.d_temporal.as<char>() + off, l.tp_state.as<unsigned int>() + off / 2, l.tp_counts, 1, s);
+}
 // The one place that decides whether a call filters flying pixels: a neighbourhood of at least one pixel (0 and below mean off).
 inline bool flying_on(int neighbourhood) { return neighbourhood >= 1; }
 // ... and whether it smooths the depth maps: the export found the process-wide switch on and handed its tables over.
@@ -222,7 +255,8 @@ inline int smooth_maps(LsnFusion *plan, const lsn::DepthSmoothTables &t, const v
 // The calls.  The lane's lock is held by the caller; `out` is left untouched on failure (the export then returns an empty mesh).
 int fuse_host(Ctx &c, Lane &l, const MeshCall &call, Mesh *out);
 void radial_host(Ctx &c, Lane &l, int n_maps, unsigned char *depth_maps, unsigned char *depth_colors, const int *widths, const int *heights,
-                 const float *intr_params, int fp_neighbourhood = 0, int fp_threshold = 0, const lsn::DepthSmoothTables *smooth = nullptr);
+                 const float *intr_params, int fp_neighbourhood = 0, int fp_threshold = 0, const lsn::DepthSmoothTables *smooth = nullptr,
+                 const lsn::TemporalSetting &temporal = lsn::TemporalSetting(), unsigned long long temporal_gen = 0);
 // The fusion of a call whose cloud stays on the device: vertices only (with the outlier filter if the call has it on) into l.d_out, final on
 // return, the tick's offset row (call.count + 1 ints) into `offsets`.  No mesh: the lane is left without a last one.
 int fuse_resident(Ctx &c, Lane &l, const MeshCall &call, int *offsets);

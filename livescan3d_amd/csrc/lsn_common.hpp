@@ -149,6 +149,21 @@ int depth_smooth(LsnFusion *p, const void *d_depth_in, void *d_depth_out, hipStr
 // The tables of (radius, sigma_s, sigma_r) into `t`; -1 with lsnDepthSmoothGaussian's message where it refuses them.
 int depth_smooth_gaussian(int radius, float sigma_s, float sigma_r, DepthSmoothTables &t);
 
+// The temporal depth filter (temporal.hip), the stage in front of the flying-pixel filter.  One setting as the plans, the tick and the
+// process-wide switch hold it (alpha_q <= 0: off).  temporal is lsnFusionTemporal with an explicit history and tick count, on a stream: the
+// history belongs to whoever sees the same rig tick after tick (a plan, a tick object, a lane of the host exports), not to the plan whose
+// frame and tile tables the pass reads.  It takes the plan's mutex.
+struct TemporalSetting {
+    int alpha_q = 0, delta = 0, persist = 0;
+    bool on() const { return alpha_q >= 1; }
+};
+int temporal_setting_ok(const char *who, int alpha_q, int delta, int persist);
+int temporal_state_ok(const char *who, const unsigned int *h_state, size_t pixels);
+int temporal_state_reserve(DevBuf &state, size_t pixels, hipStream_t s);
+int temporal(LsnFusion *p, const TemporalSetting &ts, const void *d_depth_in, void *d_depth_out, unsigned int *d_state, DevBuf &counts, int n_ticks,
+             hipStream_t s);
+int temporal_counts(LsnFusion *p, const DevBuf &counts, int tick, int *per_frame4);
+
 // A batch of meshes in lsnFusionRunMesh's layout, as the three stages on the merged mesh read it (render.hip, simplify.hip, normals.hip;
 // what they share is mesh_batch.hip's).  The stages' device structs embed it; it is built from a plan (plan_batch, mesh_batch.hip) or
 // from a lane's last mesh (LastMesh::batch, abi.hip).

@@ -1331,3 +1331,5 @@ extern "C" int lsnFusionRadialCorrectTo(LsnFusion *p, const float *intr_params, 
 #include "flying.hip"
 // ... and so is depth smoothing, the stage between the two (it shares the filter's tile list).
 #include "depth_smooth.hip"
+// ... and the temporal depth filter, the stage in front of all three (it shares the tile list too).
+#include "temporal.hip"

@@ -25,6 +25,11 @@ struct LsnTick {
     lsn::DevBuf d_filtered;              // ... and its output, [n_ticks][pixels per tick] u16: reserved by the first run that filters
     int ds_radius = 0;                   // depth smoothing between the filter and the correction (lsnTickSetDepthSmooth; <= 0: off; the plans hold the tables)
     lsn::DevBuf d_smoothed;              // ... and its output, laid out like d_filtered: reserved by the first run that smooths
+    lsn::TemporalSetting tp;             // the temporal depth filter in front of all of them (lsnTickSetTemporal; off by default)
+    lsn::DevBuf tp_state, tp_counts;     // ... its history (one word per pixel of one tick) and branch counts,
+    lsn::DevBuf d_temporal;              // ... and its output, laid out like d_filtered: all reserved by the first run that filters
+    hipStream_t tp_stream = nullptr;     // the stream of the last run that filtered (the history is handed from run to run)
+    bool tp_ran = false;
     hipStream_t side = nullptr;
     hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_band = nullptr;
     std::mutex mu;
@@ -149,6 +154,39 @@ extern "C" int lsnTickSetDepthSmooth(LsnTick *t, int radius, float sigma_s, floa
     });
 }
 
+extern "C" int lsnTickSetTemporal(LsnTick *t, int alpha_q, int delta, int persist)
+{
+    return lsn::guarded("lsnTickSetTemporal", -1, [&]() {
+        lsn::clear_error();
+        if (!t) {
+            lsn::set_error("lsnTickSetTemporal: null argument");
+            return -1;
+        }
+        if (lsn::temporal_setting_ok("lsnTickSetTemporal", alpha_q, delta, persist)) return -1;   // refused: the previous setting stays
+        std::lock_guard<std::mutex> g(t->mu);
+        t->tp = alpha_q >= 1 ? lsn::TemporalSetting{alpha_q, delta, persist} : lsn::TemporalSetting{};
+        return 0;
+    });
+}
+
+extern "C" int lsnTickTemporalReset(LsnTick *t, void *stream)
+{
+    return lsn::guarded("lsnTickTemporalReset", -1, [&]() {
+        lsn::clear_error();
+        if (!t) {
+            lsn::set_error("lsnTickTemporalReset: null argument");
+            return -1;
+        }
+        std::lock_guard<std::mutex> g(t->mu);
+        if (!t->tp_state.p) return 0;   // no history yet
+        LSN_HIP(hipSetDevice(t->device));
+        hipStream_t s = lsn::as_stream(stream);
+        if (t->tp_ran && t->tp_stream != s) LSN_HIP(hipStreamSynchronize(t->tp_stream));
+        LSN_HIP(hipMemsetAsync(t->tp_state.p, 0, 4 * (size_t)t->cap, s));
+        return 0;
+    });
+}
+
 extern "C" int lsnTickRun(LsnTick *t, const void *d_depth_in, const void *d_colors_in, void *d_depth_corr, void *d_colors_corr, void *d_vertices,
                           int *d_offsets, void *d_triangles, int *d_tri_offsets, void *stream)
 {
@@ -169,6 +207,19 @@ extern "C" int lsnTickRun(LsnTick *t, const void *d_depth_in, const void *d_colo
         if (filter && t->d_filtered.reserve(2 * (size_t)t->cap * t->n_ticks + 16)) return -1;
         const bool smooth = t->ds_radius >= 1;
         if (smooth && t->d_smoothed.reserve(2 * (size_t)t->cap * t->n_ticks + 16)) return -1;
+        // the temporal filter runs once over the whole batch, in tick order, on the caller's stream in front of the fork: the halves share the
+        // rig, so plan 0's frame and tile tables serve all ticks, and one history sees them in order.  The halves then start from d_temporal
+        // at their own offsets.  (The scratch follows d_filtered's rule below: a run on another stream waits for the previous run's chains.)
+        if (t->tp.on()) {
+            if (t->d_temporal.reserve(2 * (size_t)t->cap * t->n_ticks + 16) || lsn::temporal_state_reserve(t->tp_state, (size_t)t->cap, s)) return -1;
+            if (t->tp_ran && t->tp_stream != s) LSN_HIP(hipStreamSynchronize(t->tp_stream));
+            for (int k = 0; k < t->parts; k++)
+                if (t->plan[k]->rd.wait_for_chain(s)) return -1;
+            if (lsn::temporal(t->plan[0], t->tp, d_depth_in, t->d_temporal.p, t->tp_state.as<unsigned int>(), t->tp_counts, t->n_ticks, s)) return -1;
+            t->tp_stream = s;
+            t->tp_ran = true;
+            d_depth_in = t->d_temporal.p;
+        }
         // part k's slices of the caller's arrays: [tick][pixels], [tick][pixels][3], [tick][capacity] vertices, [tick][n_maps + 1], ...
         auto part = [&](int k, hipStream_t st) -> int {
             const size_t t0 = (size_t)t->first[k];

@@ -113,6 +113,26 @@ class DeviceFusion:
         """Depth smoothing with the tables of plan.set_depth_smooth(), out of place into depth_out."""
         self.plan.depth_smooth(self._in(depth)[0], depth_out.data_ptr(), _stream_handle(stream))
 
+    def set_temporal(self, alpha_q, delta=0, persist=0):
+        self.plan.set_temporal(alpha_q, delta, persist)
+
+    def temporal(self, depth_out, depth=None, stream=None):
+        """The temporal depth filter with the setting of set_temporal() on the batch's ticks in order, into depth_out (which may be the
+        input itself: in place); the plan's history advances by the batch's ticks."""
+        self.plan.temporal(self._in(depth)[0], depth_out.data_ptr(), _stream_handle(stream))
+
+    def temporal_reset(self, stream=None):
+        self.plan.temporal_reset(_stream_handle(stream))
+
+    def temporal_state(self, stream=None):
+        return self.plan.temporal_state(_stream_handle(stream))
+
+    def set_temporal_state(self, state, stream=None):
+        self.plan.set_temporal_state(state, _stream_handle(stream))
+
+    def temporal_diagnostics(self, tick=0, stream=None):
+        return self.plan.temporal_diagnostics(tick, _stream_handle(stream))
+
     def render_views(self, intr, wt, width, height, points=False, stream=None):
         """The ticks' meshes (points: their vertices alone) drawn from the virtual cameras intr / wt (7 / 12 floats per view), each
         width x height.  Returns (depth int16-bit-pattern [T, V, h, w], rgb uint8 [T, V, h, w, 3]), both prefilled with SENTINEL."""

@@ -64,6 +64,8 @@ _PROTOTYPES = {
     "lsnSetFlyingPixelFilter": (_i, [_i, _i, _vp, _vp]),
     "lsnSetDepthSmooth": (_i, [_i, _f, _f, _vp, _vp, _vp]),
     "lsnDepthSmoothGaussian": (_i, [_i, _f, _f, _vp, _vp, _i]),
+    "lsnSetTemporalFilter": (_i, [_i, _i, _i, _vp, _vp, _vp]),
+    "lsnResetTemporalFilter": (_i, []),
     # part 2: the device-resident API
     "lsnFusionCreate": (_vp, [_i, _i, _i, _vp, _vp]),
     "lsnFusionDestroy": (None, [_vp]),
@@ -96,6 +98,12 @@ _PROTOTYPES = {
     "lsnFusionSetDepthSmooth": (_i, [_vp, _i, _vp, _vp, _i]),
     "lsnFusionDepthSmooth": (_i, [_vp] * 4),
     "lsnFusionDepthSmoothDiagnostics": (_i, [_vp, _i, _vp, _vp, _vp]),
+    "lsnFusionSetTemporal": (_i, [_vp, _i, _i, _i]),
+    "lsnFusionTemporal": (_i, [_vp] * 4),
+    "lsnFusionTemporalReset": (_i, [_vp, _vp]),
+    "lsnFusionTemporalStateRead": (_i, [_vp] * 3),
+    "lsnFusionTemporalStateWrite": (_i, [_vp] * 3),
+    "lsnFusionTemporalDiagnostics": (_i, [_vp, _i] + [_vp] * 5),
     "lsnFusionRenderViews": (_i, [_vp, _i, _vp, _vp, _i, _i] + [_vp] * 7),
     "lsnFusionRenderDiagnostics": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp]),
     "lsnFusionSimplify": (_i, [_vp, _f] + [_vp] * 10),
@@ -149,6 +157,8 @@ _PROTOTYPES = {
     "lsnTickSetParams": (_i, [_vp] * 5),
     "lsnTickSetFlyingPixels": (_i, [_vp, _i, _i]),
     "lsnTickSetDepthSmooth": (_i, [_vp, _i, _f, _f]),
+    "lsnTickSetTemporal": (_i, [_vp, _i, _i, _i]),
+    "lsnTickTemporalReset": (_i, [_vp, _vp]),
     "lsnTickCapacity": (_ll, [_vp]),
     "lsnTickTriangleCapacity": (_ll, [_vp]),
     "lsnTickParts": (_i, [_vp]),
@@ -316,6 +326,20 @@ def set_depth_smooth(radius, sigma_s=0.0, sigma_r=0.0):
     return pr.value, ps.value, pq.value
 
 
+def set_temporal_filter(alpha_q, delta=0, persist=0):
+    """lsnSetTemporalFilter: the process-wide (alpha_q, delta, persist) of the temporal depth filter in the exports that start at raw frames
+    (radial_correction, correct_and_generate_mesh), in front of the flying-pixel filter; each such call is one tick; alpha_q <= 0: off.
+    Returns the previous triple."""
+    pa, pd, pp = C.c_int(0), C.c_int(0), C.c_int(0)
+    _check(lib().lsnSetTemporalFilter(int(alpha_q), int(delta), int(persist), C.byref(pa), C.byref(pd), C.byref(pp)), "lsnSetTemporalFilter")
+    return pa.value, pd.value, pp.value
+
+
+def reset_temporal_filter():
+    """lsnResetTemporalFilter: the exports' next filtering call starts from no history."""
+    _check(lib().lsnResetTemporalFilter(), "lsnResetTemporalFilter")
+
+
 class _Scoped:
     """Sets a process-wide setting for the body of a with-statement: setter(*setting) returns the previous one, which goes back in on the
     way out (None: leaves the setting as it is)."""
@@ -414,14 +438,16 @@ def host_schedule(widths, heights, first=0, count=None, radial=False, sensors_pe
     return g, buf.value.decode()
 
 
-def radial_correction(depth_maps, depth_colors, widths, heights, intr, flying_pixels=None, depth_smooth=None):
+def radial_correction(depth_maps, depth_colors, widths, heights, intr, flying_pixels=None, depth_smooth=None, temporal_filter=None):
     """KinectServer.CorrectRadialDistortionsForDepthMaps (KinectServer.cs:518-525): returns corrected copies
     (depth as a uint8 view of the u16 maps, colours); the export itself works in place on the arrays it is given.
     flying_pixels: None leaves the process-wide flying-pixel filter (lsnSetFlyingPixelFilter) as it is; (neighbourhood, threshold) sets
     it for this call alone (the maps are filtered, then corrected).
     depth_smooth: None leaves the process-wide depth smoothing (lsnSetDepthSmooth) as it is; (radius, sigma_s, sigma_r) sets it for this
-    call alone (the maps are filtered if that is on, smoothed, then corrected)."""
-    with _Scoped(set_flying_pixel_filter, flying_pixels), _Scoped(set_depth_smooth, depth_smooth):
+    call alone (the maps are filtered if that is on, smoothed, then corrected).
+    temporal_filter: None leaves the process-wide temporal depth filter (lsnSetTemporalFilter) as it is; (alpha_q, delta, persist) sets it
+    for this call alone (one tick of the history the library keeps for the rig; it runs in front of the other two)."""
+    with _Scoped(set_temporal_filter, temporal_filter), _Scoped(set_flying_pixel_filter, flying_pixels), _Scoped(set_depth_smooth, depth_smooth):
         require_gpu()
         n, dm, dc, widths, heights, intr, _, _ = _host_args(depth_maps, depth_colors, widths, heights, intr, copy=True)
         lib().depthMapAndColorSetRadialCorrection(n, _ptr(dm), _ptr(dc), _ptr(widths), _ptr(heights), _ptr(intr))
@@ -432,12 +458,13 @@ def radial_correction(depth_maps, depth_colors, widths, heights, intr, flying_pi
 
 
 def correct_and_generate_mesh(depth_maps, depth_colors, widths, heights, intr, wt, bounds, write_back=True, outlier_filter=None,
-                              flying_pixels=None, depth_smooth=None):
+                              flying_pixels=None, depth_smooth=None, temporal_filter=None):
     """One call per tick (extension): radial correction + merge call with a single upload.  Returns (vertices, triangles,
     corrected depth as uint8, corrected colours); with write_back=False the last two are the untouched inputs.
     outlier_filter: as for generate_mesh_from_depth_maps (the corrected maps written back are the unmasked ones).
-    flying_pixels / depth_smooth: as for radial_correction (the corrected maps written back are the filtered, smoothed, corrected ones)."""
-    with _Scoped(set_flying_pixel_filter, flying_pixels), _Scoped(set_depth_smooth, depth_smooth), _Scoped(set_outlier_filter, outlier_filter):
+    flying_pixels / depth_smooth / temporal_filter: as for radial_correction (the corrected maps written back are the filtered, smoothed,
+    corrected ones)."""
+    with _Scoped(set_temporal_filter, temporal_filter), _Scoped(set_flying_pixel_filter, flying_pixels), _Scoped(set_depth_smooth, depth_smooth), _Scoped(set_outlier_filter, outlier_filter):
         require_gpu()
         n, dm, dc, widths, heights, intr, wt, b = _host_args(depth_maps, depth_colors, widths, heights, intr, wt, bounds, copy=True)
         mesh = Mesh()
@@ -752,6 +779,37 @@ class FusionPlan(_Handle):
         k = _nonneg(lib().lsnFusionDepthSmoothDiagnostics(self._h, int(tick), _ptr(ch), _ptr(mv), stream or None), "lsnFusionDepthSmoothDiagnostics")
         return ch[:self.n_maps].copy(), mv[:self.n_maps].copy(), k
 
+    def set_temporal(self, alpha_q, delta=0, persist=0):
+        """The plan's temporal depth filter (lsnFusionSetTemporal): alpha_q 1..256, delta 1..4095 mm, persist 0..255; alpha_q <= 0: off.  A
+        refused setting leaves the previous one; changing the setting keeps the history."""
+        _check(lib().lsnFusionSetTemporal(self._h, int(alpha_q), int(delta), int(persist)), "lsnFusionSetTemporal")
+
+    def temporal(self, d_depth_in, d_depth_out, stream=0):
+        """The temporal filter on every tick of the plan in order, d_depth_in into d_depth_out (the same pointer: in place; any other overlap
+        is refused; off copies); the plan's history advances by n_ticks.  Run flying_pixels() / radial_correct_to() on d_depth_out next."""
+        _check(lib().lsnFusionTemporal(self._h, d_depth_in, d_depth_out, stream or None), "lsnFusionTemporal")
+
+    def temporal_reset(self, stream=0):
+        _check(lib().lsnFusionTemporalReset(self._h, stream or None), "lsnFusionTemporalReset")
+
+    def temporal_state(self, stream=0):
+        """The history: uint32 [pixels per tick] (F | miss << 24) in the layout of one tick's depth maps."""
+        st = np.zeros(max(self.capacity, 1), dtype=np.uint32)
+        _check(lib().lsnFusionTemporalStateRead(self._h, _ptr(st), stream or None), "lsnFusionTemporalStateRead")
+        return st[:self.capacity]
+
+    def set_temporal_state(self, state, stream=0):
+        st = _as(state, np.uint32).ravel()
+        if st.size != self.capacity:
+            raise NativeUtilsError(f"set_temporal_state: the history has {self.capacity} words, not {st.size}")
+        _check(lib().lsnFusionTemporalStateWrite(self._h, _ptr(st), stream or None), "lsnFusionTemporalStateWrite")
+
+    def temporal_diagnostics(self, tick=0, stream=0):
+        """What the last temporal() did in one tick: int32 [n, 4] per sensor -- blended, restarted with history, filled, expired."""
+        c = [np.zeros(max(self.n_maps, 1), dtype=np.int32) for _ in range(4)]
+        _check(lib().lsnFusionTemporalDiagnostics(self._h, int(tick), *[_ptr(x) for x in c], stream or None), "lsnFusionTemporalDiagnostics")
+        return np.stack(c, axis=1)[:self.n_maps]
+
     def render_views(self, intr, wt, width, height, d_vertices, d_offsets, d_triangles, d_tri_offsets, d_depth_out, d_colors_out, stream=0):
         """Render view: every tick's merged mesh (d_triangles None / 0: its vertices as points) drawn from the virtual cameras of intr
         (7 floats per view) / wt (12 per view), each width x height, into d_depth_out [n_ticks][n_views][h][w] u16 and d_colors_out
@@ -985,6 +1043,14 @@ class TickPipeline(_Handle):
         """Depth smoothing with the Gaussian tables of (radius, sigma_s, sigma_r) as a stage of run() (radius <= 0: off): flying pixels
         (if set) -> depth smoothing -> radial correction -> vertices -> triangles."""
         _check(lib().lsnTickSetDepthSmooth(self._h, int(radius), float(sigma_s), float(sigma_r)), "lsnTickSetDepthSmooth")
+
+    def set_temporal(self, alpha_q, delta=0, persist=0):
+        """The temporal depth filter as the first stage of run() (alpha_q <= 0: off): temporal -> flying pixels (if set) -> depth smoothing (if
+        set) -> radial correction -> vertices -> triangles.  The tick object's one history continues from run to run."""
+        _check(lib().lsnTickSetTemporal(self._h, int(alpha_q), int(delta), int(persist)), "lsnTickSetTemporal")
+
+    def temporal_reset(self, stream=0):
+        _check(lib().lsnTickTemporalReset(self._h, stream or None), "lsnTickTemporalReset")
 
     def run(self, d_depth_in, d_colors_in, d_depth_corr, d_colors_corr, d_vertices, d_offsets, d_triangles, d_tri_offsets, stream=0):
         _check(lib().lsnTickRun(self._h, d_depth_in, d_colors_in, d_depth_corr, d_colors_corr, d_vertices, d_offsets, d_triangles, d_tri_offsets, stream),
