@@ -36,7 +36,7 @@
 // Files: fusion_shared.hpp holds the building blocks every translation unit of the plan uses (geometry structs, the
 // per-pixel arithmetic, tile loading, ranking, LDS staging, scan_kernel, the LsnFusion plan object); this file holds the
 // count / write / streamed / look-back kernels, the per-pixel depth thresholds and the plan's entry points; mesh.hip the
-// triangulation, radial.hip the radial correction, exchange.hip the multi-GPU exchange step.
+// triangulation, radial.hip the radial correction, exchange.hip the kernels of the multi-GPU exchange step, shard.hip (in its translation unit) the step itself.
 
 
 #include "fusion_shared.hpp"

@@ -301,9 +301,15 @@ void refine_compose(int n, const float *Rt, float *world_R, float *world_t, floa
 // The survivor exchange's two ends with the back-to-back stream layout (exchange.hip; see their definitions).
 int pack_survivors(LsnFusion *p, const void *d_depth, const void *d_colors, void *d_mask, void *d_depth_c, void *d_rgb_c, int *d_tile_prefix,
                    int *d_offsets, int *d_tick_base, void *stream);
+// The ticks one reconstruct call covers (lsnShardStep's pipelined form cuts a step into chunks; everybody else takes the default, all of
+// them): [tick0, tick0 + n_ticks), n_ticks <= 0 = up to the plan's last; only a step's first chunk fills the tick bases.
+struct ReconChunk {
+    int tick0 = 0, n_ticks = 0;
+    bool fill_tick_base = true;
+};
 int reconstruct(LsnFusion *all, int n_shards, int maps_per_shard, const void *d_masks, const void *d_depth_c, const void *d_rgb_c, long long slab,
                 const int *d_tile_prefix, const int *d_shard_offsets, void *d_merged, int *d_merged_offsets, int *d_tick_base, void *stream,
-                int tick0 = 0, int n_chunk_ticks = 0, bool fill_tick_base = true);
+                ReconChunk chunk = ReconChunk());
 
 // lsnMergeShards, optionally for shards laid out [n_ticks][n_shards][shard_cap] (per-tick all-gathers).
 int merge_shards(int device, int n_shards, int n_ticks, int maps_per_shard, const void *d_shards, long long shard_cap, const int *d_shard_offsets,

@@ -303,6 +303,33 @@ void null_sweep()
     free(heap);
 }
 
+// The exports of the multi-GPU exchange step (exchange.hip, shard.hip) with NULL handles and arguments: each must refuse with its failure
+// value -- and a message, where it sets one -- before it touches RCCL.  (lsnShardRcclPath and lsnShardRanksSeen load RCCL before they look
+// at their arguments: they are not called, no real RCCL is mapped into a sanitizer process.)
+void exchange_null_sweep()
+{
+    auto refused = [](bool failed, const char *what) {
+        char msg[256] = "";
+        CHECK(failed && lsnGetLastError(msg, sizeof(msg)) > 0, "%s: %s", what, failed ? "no message" : "did not fail");
+    };
+    refused(lsnFusionPackSurvivors(nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr) == -1, "lsnFusionPackSurvivors(null)");
+    refused(lsnFusionPackSurvivorsRun(nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr) == -1,
+            "lsnFusionPackSurvivorsRun(null)");
+    refused(lsnFusionReconstruct(nullptr, 0, 0, nullptr, nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr) == -1, "lsnFusionReconstruct(null)");
+    refused(lsnFusionReconstructRun(nullptr, 0, 0, nullptr, nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr) == -1,
+            "lsnFusionReconstructRun(null)");
+    refused(lsnMergeShards(0, 0, 0, 0, nullptr, 0, nullptr, nullptr, 0, nullptr, nullptr) == -1, "lsnMergeShards(0)");
+    CHECK(lsnShardUniqueId(nullptr) == -1, "lsnShardUniqueId(null)");
+    refused(lsnShardPrepare(0, 0, 0, 0, 0, nullptr, nullptr) == nullptr, "lsnShardPrepare(world 0)");
+    refused(lsnShardConnect(nullptr, nullptr) == -1, "lsnShardConnect(null)");
+    refused(lsnShardCreate(0, 0, 1, nullptr, 1, 1, nullptr, nullptr) == nullptr, "lsnShardCreate(null id)");
+    refused(lsnShardSetParams(nullptr, nullptr, nullptr, nullptr, nullptr) == -1, "lsnShardSetParams(null)");
+    refused(lsnShardStep(nullptr, nullptr, nullptr, nullptr, nullptr, nullptr) == -1, "lsnShardStep(null)");
+    lsnShardDestroy(nullptr);
+    CHECK(lsnShardPlan(nullptr, 0) == nullptr && lsnShardPlan(nullptr, 1) == nullptr, "lsnShardPlan(null)");
+    CHECK(lsnShardMergedCapacity(nullptr) == 0 && lsnShardLastBytesSent(nullptr) == 0 && lsnFusionTilesPerTick(nullptr) == 0, "lsnShard getters(null)");
+}
+
 }  // namespace
 
 // Random rigs of 1-8 sensors of different sizes (1 x 1 up to ~0.9 MB of colours each: below and above the size at which the upload
@@ -507,6 +534,7 @@ int main(int argc, char **argv)
 {
     const int iters = argc > 1 ? atoi(argv[1]) : 4;
     null_sweep();
+    exchange_null_sweep();
     ragged_rigs(3 * iters);
     parser_fuzz(20 * iters);
     {

@@ -1,4 +1,4 @@
-// fake_rccl.cpp -- TEST DOUBLE, not a product path.  The nccl* entry points lsnShard* binds (exchange.hip: struct Rccl),
+// fake_rccl.cpp -- TEST DOUBLE, not a product path.  The nccl* entry points lsnShard* binds (shard.hip: struct Rccl),
 // implemented for ranks that are processes on ONE host sharing ONE GPU: every all-gather is staged through a POSIX
 // shared-memory segment (device -> shm slot of the rank, barrier, every slot -> device).  RCCL refuses two ranks on one
 // device, so this is the only way the world > 1 code of lsnShardStep (rank offsets, the grouped collectives, the chunked

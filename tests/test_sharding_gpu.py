@@ -233,6 +233,30 @@ def test_rccl_survivor_exchange_world1(gpu, tmp_path):
     assert open(out).read() == "ok"
 
 
+def _expected_bytes_sent(counts, T, mpr, cap, tiles_loc, chunks, padded, vertex):
+    """What lsnShardLastBytesSent must report after a step: the bytes ONE rank puts into the step's all-gathers.  counts[q][k]: rank q's
+    survivors (or vertices) in tick k; cap: pixels per tick of one rank's block.  Always the offset tables (4 bytes x T x (mpr + 1)).
+    Survivors: the tile prefixes, one mask bit per pixel and 5 bytes per entry of the streams, which are cut to the largest rank total
+    rounded up to 8 entries -- per chunk of ceil(T / C) ticks when the streams travel in C chunks (C clamped to 1..min(16, T)), the whole
+    capacity when padded (chunks are ignored then).  Vertices: 16 bytes x T slabs of the largest (rank, tick) count, or of cap when padded."""
+    off = 4 * T * (mpr + 1)
+    if vertex:
+        slab = cap if padded else max(1, max(max(row) for row in counts))
+        return off + 16 * T * slab
+    if padded:
+        slab = T * cap
+    else:
+        C = max(1, min(chunks, 16, T))
+        per = -(-T // C)
+        slab = 0
+        for c in range(C):
+            t0, t1 = c * per, min(T, (c + 1) * per)
+            if t0 >= t1:
+                break
+            slab += (max(1, max(sum(row[t0:t1]) for row in counts)) + 7) & ~7
+    return off + 4 * T * tiles_loc + T * cap // 8 + 5 * slab
+
+
 def _shard_worker(rank, padded, chunks, out):
     sys.path.insert(0, ROOT)
     if padded:
@@ -266,9 +290,9 @@ def _shard_worker(rank, padded, chunks, out):
     want_v, want_o = whole.run(depth, rgb)
     torch.cuda.synchronize()
     ok = ok and bool(torch.equal(moff, want_o))
-    sent = sf.shard.last_bytes_sent()
-    full = T * S * w * h * 5
-    ok = ok and (sent > full if padded else sent < 0.8 * full)      # compact: survivors only; padded: whole capacity, no host read
+    counts = [[int(want_o[k, -1]) for k in range(T)]]               # one rank: its tick totals are the step's own
+    want_sent = _expected_bytes_sent(counts, T, S, S * w * h, sf.shard.plan(whole=False).tiles_per_tick, chunks, padded, False)
+    ok = ok and sf.shard.last_bytes_sent() == want_sent
     sf.close()
     with open(out, "w") as f:
         f.write("ok" if ok else "mismatch")
@@ -324,8 +348,8 @@ def _shard_worker_ragged(rank, padded, out):
             n = int(oh[k, -1])
             ok = ok and n == len(want) and list(np.diff(oh[k])) == list(counts) and merged[k, :n].cpu().numpy().tobytes() == want.tobytes()
     cap = sum(w * h for w, h in sizes)
-    sent = sf.shard.last_bytes_sent()
-    ok = ok and (sent >= T * cap * 16 if padded else 0 < sent < T * cap * 16)
+    counts = [[int(oh[k, -1]) for k in range(T)]]
+    ok = ok and sf.shard.last_bytes_sent() == _expected_bytes_sent(counts, T, len(sizes), cap, None, 1, padded, True)
     sf.close()
     with open(out, "w") as f:
         f.write("ok" if ok else "mismatch")
@@ -392,8 +416,12 @@ def _shard_worker_multi(rank, world, port, sizes, chunks, padded, out):
         for k in range(T):
             n = int(want_o[k, -1])
             ok = ok and n > 0 and bool(torch.equal(merged[k, :n], want_v[k, :n]))
-    sent = sf.shard.last_bytes_sent()
-    ok = ok and sent > 0
+    # rank q's count in tick k, from the single-plan offsets at the block boundaries; the library's own rule for the exchange's mode
+    oh = want_o.cpu().numpy()
+    counts = [[int(oh[k, (q + 1) * mpr] - oh[k, q * mpr]) for k in range(T)] for q in range(world)]
+    vertex = not all(sz == sizes[0] and sz[0] % 8 == 0 for sz in sizes)
+    want_sent = _expected_bytes_sent(counts, T, mpr, p1 - p0, sf.shard.plan(whole=False).tiles_per_tick, chunks, padded, vertex)
+    ok = ok and sf.shard.last_bytes_sent() == want_sent
     if rank == 0:
         # ... and straight against the CPU oracle, not only against the single-plan HIP fusion: the merged cloud a rank ends up with
         # is the oracle's merge of ALL sensors, byte for byte
