@@ -4,9 +4,11 @@
 // MainWindowForm.cs:364-370) and reads host memory back (Marshal.Copy, KinectServer.cs:383), so these entry points
 // add the H2D / D2H hops around the same kernels bench.py drives directly on HBM-resident data.  How a call runs -- the
 // upload schedule, kernels storing into the pinned mesh blocks, the copy-engine flow, the call sharded over devices -- is
-// host_flows.hip; the context it runs on (lanes, pinned pool, devices) host_ctx.hpp.  This file: argument checks, locks, the
-// exception trampoline, and the exports that need no flow (error channel, device helpers, createMesh / deleteMesh, ICP, the
-// outbound formats of the last mesh).
+// host_flows.hip; the context it runs on (lanes, pinned pool, devices) and the records a call carries host_ctx.hpp.  This file: argument
+// checks, locks, the exception trampoline, the process-wide switches of the exports' opt-in stages (the outlier filter, the overlay merge;
+// the temporal filter, the flying-pixel filter and depth smoothing in front of the radial correction, which current_stages() hands to a
+// call) with their setters, and the exports that need no flow (error channel, device helpers, createMesh / deleteMesh, ICP, the outbound
+// formats of the last mesh).
 #include "host_ctx.hpp"
 
 using namespace lsn::host;
@@ -231,20 +233,24 @@ struct SmoothSetting {
         if (!e || !*e) return;
         int r = 0, used = 0;
         float ss = 0.0f, sr = 0.0f;
-        if (sscanf(e, " %d , %f , %f %n", &r, &ss, &sr, &used) == 3 && e[used] == '\0' && set(r, ss, sr) == 0) return;
+        if (sscanf(e, " %d , %f , %f %n", &r, &ss, &sr, &used) == 3 && e[used] == '\0' && exchange(r, ss, sr, nullptr, nullptr, nullptr) == 0) return;
         fprintf(stderr, "[NativeUtils] $LSN_DEPTH_SMOOTH=\"%s\" is not \"radius,sigma_s,sigma_r\" with a radius of at most 3 and positive sigmas "
                         "(e.g. \"2,1.5,12\"): depth smoothing stays off\n", e);
     }
-    // the new triple; refused (-1, lsnDepthSmoothGaussian's message) it leaves the setting as it was
-    int set(int r, float ss, float sr)
+    // lsnSetDepthSmooth: the new triple in, the previous one to prev_* (any may be null), under one acquisition of the lock; refused (-1,
+    // lsnDepthSmoothGaussian's message) it leaves the setting and prev_* as they were
+    int exchange(int r, float ss, float sr, int *prev_r, float *prev_ss, float *prev_sr)
     {
         std::shared_ptr<const lsn::DepthSmoothTables> fresh;
-        if (r >= 1) {
+        if (r >= 1) {   // (the tables depend on the arguments alone: built, and refused, in front of the lock)
             auto t = std::make_shared<lsn::DepthSmoothTables>();
             if (lsn::depth_smooth_gaussian(r, ss, sr, *t)) return -1;
             fresh = t;
         }
         std::lock_guard<std::mutex> g(mu);
+        if (prev_r) *prev_r = radius;
+        if (prev_ss) *prev_ss = sigma_s;
+        if (prev_sr) *prev_sr = sigma_r;
         tables = fresh;
         radius = r;
         sigma_s = ss;
@@ -281,18 +287,22 @@ struct TemporalSwitch {
         if (!e || !*e) return;
         int a = 0, d = 0, p = 0, used = 0;
         if (sscanf(e, " %d , %d , %d %n", &a, &d, &p, &used) == 3 && e[used] == '\0') {
-            if (set(a, d, p) == 0) return;
+            if (exchange(a, d, p, nullptr, nullptr, nullptr) == 0) return;
             fprintf(stderr, "[NativeUtils] $LSN_TEMPORAL_FILTER=\"%s\": %s: the temporal filter stays off\n", e, lsn::error_buffer());
             lsn::clear_error();
             return;
         }
         fprintf(stderr, "[NativeUtils] $LSN_TEMPORAL_FILTER=\"%s\" is not \"alpha_q,delta,persist\" (e.g. \"64,20,2\"): the temporal filter stays off\n", e);
     }
-    // the new triple; refused (-1, with the message) it leaves the setting as it was
-    int set(int a, int d, int p)
+    // lsnSetTemporalFilter: the new triple in, the previous one to prev_* (any may be null), under one acquisition of the lock; refused (-1,
+    // with the message) it leaves the setting and prev_* as they were
+    int exchange(int a, int d, int p, int *prev_a, int *prev_d, int *prev_p)
     {
         if (lsn::temporal_setting_ok("lsnSetTemporalFilter", a, d, p)) return -1;
         std::lock_guard<std::mutex> g(mu);
+        if (prev_a) *prev_a = alpha_q;
+        if (prev_d) *prev_d = delta;
+        if (prev_p) *prev_p = persist;
         setting = a >= 1 ? lsn::TemporalSetting{a, d, p} : lsn::TemporalSetting{};
         alpha_q = a;
         delta = d;
@@ -323,6 +333,16 @@ static TemporalSwitch &temporal_switch()
 {
     static auto *s = new TemporalSwitch();   // never destroyed, like the pairs above
     return *s;
+}
+
+// The stages in front of the radial correction that a call of this rig takes with it: the three switches as they stand when it is called.
+static DepthStages current_stages(int n_maps, const int *widths, const int *heights)
+{
+    DepthStages st;
+    flying_setting().current(st.fp_neighbourhood, st.fp_threshold);
+    st.smooth = smooth_setting().current();
+    temporal_switch().current(st.temporal, st.temporal_gen, n_maps, widths, heights);
+    return st;
 }
 
 // What the three mesh exports share: `call` as `name` filled it (everything but the outlier filter's setting, which is read here) runs on
@@ -401,20 +421,7 @@ extern "C" int lsnSetDepthSmooth(int radius, float sigma_s, float sigma_r, int *
 {
     return lsn::guarded("lsnSetDepthSmooth", -1, [&]() {
         lsn::clear_error();
-        SmoothSetting &s = smooth_setting();
-        int r0;
-        float ss0, sr0;
-        {
-            std::lock_guard<std::mutex> g(s.mu);
-            r0 = s.radius;
-            ss0 = s.sigma_s;
-            sr0 = s.sigma_r;
-        }
-        if (s.set(radius, sigma_s, sigma_r)) return -1;
-        if (prev_radius) *prev_radius = r0;
-        if (prev_sigma_s) *prev_sigma_s = ss0;
-        if (prev_sigma_r) *prev_sigma_r = sr0;
-        return 0;
+        return smooth_setting().exchange(radius, sigma_s, sigma_r, prev_radius, prev_sigma_s, prev_sigma_r);
     });
 }
 
@@ -422,19 +429,7 @@ extern "C" int lsnSetTemporalFilter(int alpha_q, int delta, int persist, int *pr
 {
     return lsn::guarded("lsnSetTemporalFilter", -1, [&]() {
         lsn::clear_error();
-        TemporalSwitch &s = temporal_switch();
-        int a0, d0, p0;
-        {
-            std::lock_guard<std::mutex> g(s.mu);
-            a0 = s.alpha_q;
-            d0 = s.delta;
-            p0 = s.persist;
-        }
-        if (s.set(alpha_q, delta, persist)) return -1;
-        if (prev_alpha_q) *prev_alpha_q = a0;
-        if (prev_delta) *prev_delta = d0;
-        if (prev_persist) *prev_persist = p0;
-        return 0;
+        return temporal_switch().exchange(alpha_q, delta, persist, prev_alpha_q, prev_delta, prev_persist);
     });
 }
 
@@ -518,9 +513,7 @@ extern "C" void lsnCorrectAndGenerateMesh(int n_maps, unsigned char *depth_maps,
         call.radial = true;
         call.back_d = write_back_corrected ? depth_maps : nullptr;
         call.back_c = write_back_corrected ? depth_colors : nullptr;
-        flying_setting().current(call.fp_neighbourhood, call.fp_threshold);
-        call.smooth = smooth_setting().current();
-        temporal_switch().current(call.temporal, call.temporal_gen, n_maps, widths, heights);
+        call.stages = current_stages(n_maps, widths, heights);
         (void)mesh_export("lsnCorrectAndGenerateMesh", ctx().merge, call, out_mesh);
         return true;
     });
@@ -540,13 +533,7 @@ extern "C" void depthMapAndColorSetRadialCorrection(int n_maps, unsigned char *d
         Lane &l = c.merge;
         std::lock_guard<std::mutex> g(l.mu);
         if (ensure_ready(c)) return;
-        int fp_n = 0, fp_t = 0;
-        flying_setting().current(fp_n, fp_t);
-        const std::shared_ptr<const lsn::DepthSmoothTables> smooth = smooth_setting().current();
-        lsn::TemporalSetting temporal;
-        unsigned long long temporal_gen = 0;
-        temporal_switch().current(temporal, temporal_gen, n_maps, widths, heights);
-        radial_host(c, l, n_maps, depth_maps, depth_colors, widths, heights, intr_params, fp_n, fp_t, smooth.get(), temporal, temporal_gen);
+        radial_host(c, l, n_maps, depth_maps, depth_colors, widths, heights, intr_params, current_stages(n_maps, widths, heights));
     });
 }
 
@@ -576,7 +563,7 @@ extern "C" int lsnRefineFromDepthMaps(int n_maps, unsigned char *depth_maps, uns
         call.bounds6 = b;
         call.count = n_maps;
         call.radial = correct_radial != 0;
-        if (call.radial) flying_setting().current(call.fp_neighbourhood, call.fp_threshold);
+        if (call.radial) flying_setting().current(call.stages.fp_neighbourhood, call.stages.fp_threshold);
         outlier_setting().current(call.outlier_k, call.outlier_max_dist);
         Ctx &c = ctx();
         Lane &l = c.single;

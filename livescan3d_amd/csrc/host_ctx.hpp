@@ -1,6 +1,8 @@
 // host_ctx.hpp -- the process-wide context behind the reference's exports on HOST arrays: lanes (streams, device buffers, plan tables), the
-// pool of pinned mesh blocks, the devices of $LSN_HOST_DEVICES with their worker threads -- and the entry points of the three call flows
-// that run on it (host_flows.hip; the design notes are at the top of that file).  abi.hip holds the exports themselves.
+// pool of pinned mesh blocks, the devices of $LSN_HOST_DEVICES with their worker threads -- the record of the opt-in stages in front of
+// the radial correction that a call carries (DepthStages) with the lane's side of them (DepthChain), the record of a mesh call (MeshCall)
+// -- and the entry points of the three call flows that run on it (host_flows.hip; the design notes are at the top of that file).
+// abi.hip holds the exports themselves.
 #pragma once
 
 #include "lsn_common.hpp"
@@ -40,6 +42,78 @@ constexpr int kMaxGroups = 16;
 
 struct Ctx;
 
+// The opt-in stages on a call's raw u16 depth maps, in front of its radial correction, in the order they run: the temporal depth filter
+// (temporal.hip, lsnSetTemporalFilter) with the generation of lsnResetTemporalFilter, the flying-pixel filter (flying.hip,
+// lsnSetFlyingPixelFilter), depth smoothing (depth_smooth.hip, lsnSetDepthSmooth; the Gaussian tables, null: off).  The export fills it from
+// the process-wide switches (abi.hip); this is the one place that says when a stage runs.
+struct DepthStages {
+    lsn::TemporalSetting temporal;
+    unsigned long long temporal_gen = 0;
+    int fp_neighbourhood = 0, fp_threshold = 0;
+    std::shared_ptr<const lsn::DepthSmoothTables> smooth;
+    bool temporal_on() const { return temporal.on(); }
+    bool flying_on() const { return lsn::flying_on(fp_neighbourhood); }
+    bool smooth_on() const { return smooth != nullptr && lsn::smooth_on(smooth->radius); }
+};
+
+// A lane's side of those stages: each stage's output, laid out like the lane's d_depth, which the next stage or the correction reads; the
+// temporal filter's history of the rig the lane sees call after call, one word per pixel at the sensor's offset in the call's arrays (so
+// neither grouping nor the host path changes which word a pixel owns), keyed by the rig (sensor count, widths, heights) and the reset
+// generation; the branch counts of its last launch.  All allocated by the first call that runs the stage.
+struct DepthChain {
+    lsn::DevBuf d_temporal, d_flying, d_smooth, tp_state, tp_counts;
+    std::vector<int> tp_rig;
+    unsigned long long tp_gen = 0;
+    // the history up to date for a call of this rig and generation: zeroed when either changed
+    int history(const int *widths, const int *heights, int count, unsigned long long gen, hipStream_t s)
+    {
+        std::vector<int> rig(1, count);
+        rig.insert(rig.end(), widths, widths + count);
+        rig.insert(rig.end(), heights, heights + count);
+        size_t pixels = 0;
+        for (int i = 0; i < count; i++) pixels += (size_t)widths[i] * heights[i];
+        if (tp_state.p && rig == tp_rig && gen == tp_gen) return 0;
+        const bool grown = !tp_state.p || tp_state.bytes < 4 * pixels;
+        if (lsn::temporal_state_reserve(tp_state, pixels, s)) return -1;   // (a new buffer comes zeroed)
+        if (!grown) LSN_HIP(hipMemsetAsync(tp_state.p, 0, 4 * pixels, s));
+        tp_rig.swap(rig);
+        tp_gen = gen;
+        return 0;
+    }
+    // What the stages that are on need for a call whose depth block has `dbytes` bytes and whose sensors are widths / heights [0, count).
+    int reserve(const DepthStages &st, size_t dbytes, const int *widths, const int *heights, int count, hipStream_t s)
+    {
+        if (st.temporal_on() && (d_temporal.reserve(dbytes + 16) || history(widths, heights, count, st.temporal_gen, s))) return -1;
+        if (st.flying_on() && d_flying.reserve(dbytes + 16)) return -1;
+        if (st.smooth_on() && d_smooth.reserve(dbytes + 16)) return -1;
+        return 0;
+    }
+    // Queues the stages that are on for one plan's maps, which start `off` bytes into the lane's depth block `d_depth` (and so into every
+    // buffer here; the history word of a pixel is off / 2), the temporal filter as ONE tick.  Returns the maps the correction must read --
+    // d_depth + off itself when nothing is on -- or null with the message set.
+    const void *run(LsnFusion *plan, const DepthStages &st, const lsn::DevBuf &d_depth, size_t off, hipStream_t s)
+    {
+        const char *in = d_depth.as<char>() + off;
+        if (st.temporal_on()) {
+            char *out = d_temporal.as<char>() + off;
+            if (lsn::temporal(plan, st.temporal, in, out, tp_state.as<unsigned int>() + off / 2, tp_counts, 1, s)) return nullptr;
+            in = out;
+        }
+        if (st.flying_on()) {
+            char *out = d_flying.as<char>() + off;
+            if (lsn::flying_pixels(plan, st.fp_neighbourhood, st.fp_threshold, in, out, s)) return nullptr;
+            in = out;
+        }
+        if (st.smooth_on()) {   // the plan takes the call's tables first (nothing to do when it has them)
+            const lsn::DepthSmoothTables &t = *st.smooth;
+            char *out = d_smooth.as<char>() + off;
+            if (lsn::set_depth_smooth(plan, "lsnSetDepthSmooth", t.radius, t.spatial, t.range, t.n_range) || lsn::depth_smooth(plan, in, out, s)) return nullptr;
+            in = out;
+        }
+        return in;
+    }
+};
+
 // What one call in flight needs: streams, events, device buffers, plans.  LiveScanServer runs its merge calls (updateWorker: radial
 // correction, generateMeshFromDepthMaps) and its refine calls (refineWorker: generateVerticesFromDepthMap per sensor, then ICP) on two
 // threads (MainWindowForm.cs:238,304); each of the three families has its own lane, so they only meet at the pool of pinned blocks.
@@ -53,31 +127,7 @@ struct Lane {
     int h_off_cap = 0;
     lsn::DevBuf d_depth, d_colors, d_depth2, d_colors2, d_out, d_off, d_tri, d_tri_off;
     lsn::DevBuf d_masked;     // a call with the outlier filter on: its depth maps with the removed vertices' pixels at 0 (allocated by the first such call)
-    lsn::DevBuf d_flying;     // a call with the flying-pixel filter on: its raw depth maps filtered, what the radial correction then reads (allocated by the first such call)
-    lsn::DevBuf d_smooth;     // a call with depth smoothing on: its (filtered) depth maps smoothed, what the radial correction then reads (allocated by the first such call)
-    // the temporal depth filter (temporal.hip, lsnSetTemporalFilter) of the calls that start at raw frames: its output, what the stages behind
-    // it then read; the history of the rig the lane sees call after call, one word per pixel at the sensor's offset in the call's arrays
-    // (so neither grouping nor the host path changes which word a pixel owns); the branch counts of the last launch.  The history is keyed
-    // by the rig (sensor count, widths, heights) and the reset generation: temporal_history() zeroes it when either changed.  All
-    // allocated by the first such call.
-    lsn::DevBuf d_temporal, tp_state, tp_counts;
-    std::vector<int> tp_rig;
-    unsigned long long tp_gen = 0;
-    int temporal_history(const int *widths, const int *heights, int count, unsigned long long gen)
-    {
-        std::vector<int> rig(1, count);
-        rig.insert(rig.end(), widths, widths + count);
-        rig.insert(rig.end(), heights, heights + count);
-        size_t pixels = 0;
-        for (int i = 0; i < count; i++) pixels += (size_t)widths[i] * heights[i];
-        if (tp_state.p && rig == tp_rig && gen == tp_gen) return 0;
-        const bool grown = !tp_state.p || tp_state.bytes < 4 * pixels;
-        if (lsn::temporal_state_reserve(tp_state, pixels, stream)) return -1;   // (a new buffer comes zeroed)
-        if (!grown) LSN_HIP(hipMemsetAsync(tp_state.p, 0, 4 * pixels, stream));
-        tp_rig.swap(rig);
-        tp_gen = gen;
-        return 0;
-    }
+    DepthChain pre;           // a call that starts at raw frames with stages in front of the correction: their scratch and history
     // the lane's plans: key = n sensors, first sensor, widths..., heights...  Owned by the lane and only touched under its lock, so a
     // plan never runs on two lanes' streams at once and an eviction cannot pull a plan from under the other lane's call
     std::map<std::vector<int>, LsnFusion *> plans;
@@ -226,37 +276,13 @@ struct MeshCall {
     bool color_transfer = false, overlay_merge = false;   // the stages on the fused cloud (color.hip, merge.hip) ...
     int outlier_k = 0;                       // ... and the outlier filter (outlier.hip, lsnSetOutlierFilter): it runs when outlier_k > 0
     float outlier_max_dist = 0.0f;           //     and outlier_max_dist > 0
-    int fp_neighbourhood = 0, fp_threshold = 0;   // the flying-pixel filter (flying.hip, lsnSetFlyingPixelFilter) in front of the radial correction
-                                                  //     of a call that starts with it (`radial`): it runs when flying_on(fp_neighbourhood)
-    std::shared_ptr<const lsn::DepthSmoothTables> smooth;   // depth smoothing (depth_smooth.hip, lsnSetDepthSmooth) between that filter and the
-                                                            //     correction of such a call: it runs when smooth_on(smooth.get())
-    lsn::TemporalSetting temporal;           // the temporal depth filter (temporal.hip, lsnSetTemporalFilter) in front of all of them in such a
-    unsigned long long temporal_gen = 0;     //     call: it runs when temporal_on(temporal); the generation of lsnResetTemporalFilter
+    DepthStages stages;                      // the stages in front of the radial correction of a call that starts with it (`radial`)
 };
-
-// The one place that decides whether a call runs the temporal depth filter: the export found the process-wide switch on.
-inline bool temporal_on(const lsn::TemporalSetting &ts) { return ts.on(); }
-// The temporal filter of one plan's maps inside a flow, as ONE tick: `off` is where the plan's first sensor starts in the call's arrays
-// (bytes of u16 maps), which is where its words start in the lane's history; lane.d_temporal at `off` receives the filtered maps.
-inline int temporal_maps(Lane &l, LsnFusion *plan, const lsn::TemporalSetting &ts, size_t off, const void *in, hipStream_t s)
-{
-    return lsn::temporal(plan, ts, in, l.d_temporal.as<char>() + off, l.tp_state.as<unsigned int>() + off / 2, l.tp_counts, 1, s);
-}
-// The one place that decides whether a call filters flying pixels: a neighbourhood of at least one pixel (0 and below mean off).
-inline bool flying_on(int neighbourhood) { return neighbourhood >= 1; }
-// ... and whether it smooths the depth maps: the export found the process-wide switch on and handed its tables over.
-inline bool smooth_on(const lsn::DepthSmoothTables *smooth) { return smooth != nullptr && smooth->radius >= 1; }
-// Depth smoothing of one plan's maps inside a flow: the plan takes the call's tables (nothing to do when it has them), then `in` into `out`.
-inline int smooth_maps(LsnFusion *plan, const lsn::DepthSmoothTables &t, const void *in, void *out, hipStream_t s)
-{
-    return lsn::set_depth_smooth(plan, "lsnSetDepthSmooth", t.radius, t.spatial, t.range, t.n_range) || lsn::depth_smooth(plan, in, out, s) ? -1 : 0;
-}
 
 // The calls.  The lane's lock is held by the caller; `out` is left untouched on failure (the export then returns an empty mesh).
 int fuse_host(Ctx &c, Lane &l, const MeshCall &call, Mesh *out);
 void radial_host(Ctx &c, Lane &l, int n_maps, unsigned char *depth_maps, unsigned char *depth_colors, const int *widths, const int *heights,
-                 const float *intr_params, int fp_neighbourhood = 0, int fp_threshold = 0, const lsn::DepthSmoothTables *smooth = nullptr,
-                 const lsn::TemporalSetting &temporal = lsn::TemporalSetting(), unsigned long long temporal_gen = 0);
+                 const float *intr_params, const DepthStages &stages);
 // The fusion of a call whose cloud stays on the device: vertices only (with the outlier filter if the call has it on) into l.d_out, final on
 // return, the tick's offset row (call.count + 1 ints) into `offsets`.  No mesh: the lane is left without a last one.
 int fuse_resident(Ctx &c, Lane &l, const MeshCall &call, int *offsets);

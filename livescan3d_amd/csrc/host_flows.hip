@@ -464,11 +464,7 @@ struct HostCall {
             l.d_tri_off.reserve(sizeof(int) * (size_t)(count + 1)) || ensure_tables(l, count + 2 + extra_tab))
             return -1;
         if (radial && (l.d_depth2.reserve(dbytes + 16) || l.d_colors2.reserve(cbytes + 16))) return -1;
-        if (radial && temporal_on(call.temporal) &&
-            (l.d_temporal.reserve(dbytes + 16) || l.temporal_history(call.widths + call.first, call.heights + call.first, count, call.temporal_gen)))
-            return -1;
-        if (radial && flying_on(call.fp_neighbourhood) && l.d_flying.reserve(dbytes + 16)) return -1;
-        if (radial && smooth_on(call.smooth.get()) && l.d_smooth.reserve(dbytes + 16)) return -1;
+        if (radial && l.pre.reserve(call.stages, dbytes, call.widths + call.first, call.heights + call.first, count, l.stream)) return -1;
         if (in_hbm && (l.d_out.reserve((size_t)cap * 16) || (with_triangles && l.d_tri.reserve((size_t)cap * 2 * 12)))) return -1;
         back = radial && call.back_d && call.back_c;
         // the mesh's host blocks, sized for the most the frames can give (recycled through the pool: the same blocks tick after tick);
@@ -506,24 +502,14 @@ struct HostCall {
             tr.mark(cp.colours ? "upC" : "upD");
             for (; next_group < G && l.groups[next_group].ready_after == (int)i + 1; next_group++) {
                 const Group &g = l.groups[next_group];
-                // out of place: raw frames in d_depth / d_colors, corrected ones in the second pair, which the launches read; with the
-                // flying-pixel filter on, the group's raw maps are filtered into d_flying first and the correction reads those
-                const char *raw_d = l.d_depth.as<char>() + g.d_off;
-                if (call.radial && temporal_on(call.temporal)) {   // the temporal filter in front of all of them, into d_temporal
-                    if (temporal_maps(l, g.radial_plan, call.temporal, g.d_off, raw_d, l.stream)) return -1;
-                    raw_d = l.d_temporal.as<char>() + g.d_off;
+                // out of place: raw frames in d_depth / d_colors, corrected ones in the second pair, which the launches read; the
+                // correction reads what the call's stages in front of it made of the group's raw maps
+                if (call.radial) {
+                    const void *raw_d = l.pre.run(g.radial_plan, call.stages, l.d_depth, g.d_off, l.stream);
+                    if (!raw_d || lsnFusionRadialCorrectTo(g.radial_plan, call.intr + 7 * g.first, raw_d, l.d_colors.as<char>() + g.c_off,
+                                                           l.d_depth2.as<char>() + g.d_off, l.d_colors2.as<char>() + g.c_off, l.stream))
+                        return -1;
                 }
-                if (call.radial && flying_on(call.fp_neighbourhood)) {
-                    if (lsn::flying_pixels(g.radial_plan, call.fp_neighbourhood, call.fp_threshold, raw_d, l.d_flying.as<char>() + g.d_off, l.stream)) return -1;
-                    raw_d = l.d_flying.as<char>() + g.d_off;
-                }
-                if (call.radial && smooth_on(call.smooth.get())) {   // ... and smoothed into d_smooth behind that
-                    if (smooth_maps(g.radial_plan, *call.smooth, raw_d, l.d_smooth.as<char>() + g.d_off, l.stream)) return -1;
-                    raw_d = l.d_smooth.as<char>() + g.d_off;
-                }
-                if (call.radial && lsnFusionRadialCorrectTo(g.radial_plan, call.intr + 7 * g.first, raw_d, l.d_colors.as<char>() + g.c_off,
-                                                       l.d_depth2.as<char>() + g.d_off, l.d_colors2.as<char>() + g.c_off, l.stream))
-                    return -1;
                 if (on_group(next_group, g)) return -1;
                 tr.mark("launch");
             }
@@ -862,28 +848,17 @@ int shard_part(ShardedCall &sc, int d)
     l.groups.clear();
     LsnFusion *plan = get_plan(c, l, call.widths, call.heights, f0, n);
     if (!plan) return -1;
-    // the flying-pixel filter of a call that starts with the correction: this device filters its own block into d_flying, which the
-    // correction then reads
-    const bool flying = call.radial && flying_on(call.fp_neighbourhood);
-    if (flying && l.d_flying.reserve(dbytes + 16)) return -1;
-    // ... and the temporal filter in front of it, into d_temporal: this device's lane keeps the history of its own block
-    const bool temporal = call.radial && temporal_on(call.temporal);
-    if (temporal && (l.d_temporal.reserve(dbytes + 16) || l.temporal_history(call.widths + f0, call.heights + f0, n, call.temporal_gen))) return -1;
-    auto first_d = [&]() -> const void * { return temporal ? l.d_temporal.p : l.d_depth.p; };   // what the first stage behind it reads
-    // ... and depth smoothing behind it, into d_smooth: raw() names the maps the correction reads once the stages in front of it are queued
-    const bool smooth = call.radial && smooth_on(call.smooth.get());
-    if (smooth && l.d_smooth.reserve(dbytes + 16)) return -1;
-    auto raw = [&]() -> const void * { return smooth ? l.d_smooth.p : flying ? l.d_flying.p : first_d(); };
+    // the stages in front of the correction of a call that starts with it: this device runs them on its own block, and its lane keeps the
+    // temporal filter's history of that block
+    if (call.radial && l.pre.reserve(call.stages, dbytes, call.widths + f0, call.heights + f0, n, l.stream)) return -1;
     if (sc.only_radial) {
         // the radial export alone: this block up over this device's link, corrected out of place, home again (both ways pageable copies
         // that keep this thread -- which is why every device has one)
         if (l.d_depth.reserve(dbytes + 16) || l.d_colors.reserve(cbytes + 16) || l.d_depth2.reserve(dbytes + 16) || l.d_colors2.reserve(cbytes + 16)) return -1;
         LSN_HIP(hipMemcpyWithStream(l.d_depth.p, call.depth_maps + d_src, dbytes, hipMemcpyHostToDevice, l.up));
         LSN_HIP(hipMemcpyWithStream(l.d_colors.p, call.depth_colors + c_src, cbytes, hipMemcpyHostToDevice, l.up));
-        if (temporal && temporal_maps(l, plan, call.temporal, 0, l.d_depth.p, l.stream)) return -1;
-        if (flying && lsn::flying_pixels(plan, call.fp_neighbourhood, call.fp_threshold, first_d(), l.d_flying.p, l.stream)) return -1;
-        if (smooth && smooth_maps(plan, *call.smooth, flying ? l.d_flying.p : first_d(), l.d_smooth.p, l.stream)) return -1;
-        if (lsnFusionRadialCorrectTo(plan, call.intr + 7 * f0, raw(), l.d_colors.p, l.d_depth2.p, l.d_colors2.p, l.stream)) return -1;
+        const void *raw_d = l.pre.run(plan, call.stages, l.d_depth, 0, l.stream);
+        if (!raw_d || lsnFusionRadialCorrectTo(plan, call.intr + 7 * f0, raw_d, l.d_colors.p, l.d_depth2.p, l.d_colors2.p, l.stream)) return -1;
         LSN_HIP(hipStreamSynchronize(l.stream));
         LSN_HIP(hipMemcpyWithStream(call.back_d + d_src, l.d_depth2.p, dbytes, hipMemcpyDeviceToHost, l.back));
         LSN_HIP(hipMemcpyWithStream(call.back_c + c_src, l.d_colors2.p, cbytes, hipMemcpyDeviceToHost, l.back));
@@ -905,10 +880,8 @@ int shard_part(ShardedCall &sc, int d)
     if (!call.radial && lsn::run_count(plan, run_d, run_c, l.d_off.as<int>(), l.h_off, ev_counted, l.stream)) return -1;
     LSN_HIP(hipMemcpyWithStream(l.d_colors.p, call.depth_colors + c_src, cbytes, hipMemcpyHostToDevice, l.up));
     if (call.radial) {
-        if (temporal && temporal_maps(l, plan, call.temporal, 0, l.d_depth.p, l.stream)) return -1;
-        if (flying && lsn::flying_pixels(plan, call.fp_neighbourhood, call.fp_threshold, first_d(), l.d_flying.p, l.stream)) return -1;
-        if (smooth && smooth_maps(plan, *call.smooth, flying ? l.d_flying.p : first_d(), l.d_smooth.p, l.stream)) return -1;
-        if (lsnFusionRadialCorrectTo(plan, call.intr + 7 * f0, raw(), l.d_colors.p, l.d_depth2.p, l.d_colors2.p, l.stream)) return -1;
+        const void *raw_d = l.pre.run(plan, call.stages, l.d_depth, 0, l.stream);
+        if (!raw_d || lsnFusionRadialCorrectTo(plan, call.intr + 7 * f0, raw_d, l.d_colors.p, l.d_depth2.p, l.d_colors2.p, l.stream)) return -1;
         LSN_HIP(hipEventRecord(ev_corrected, l.stream));
         if (lsn::run_count(plan, run_d, run_c, l.d_off.as<int>(), l.h_off, ev_counted, l.stream)) return -1;
     }
@@ -1035,8 +1008,7 @@ int run_parts(Ctx &c, ShardedCall &sc)
 // depthMapAndColorSetRadialCorrection over the devices of $LSN_HOST_DEVICES: every device corrects its block of sensors and writes it back
 // into the caller's arrays.  The merge lane's lock is held.
 int radial_sharded(Ctx &c, Lane &ml, int n_maps, unsigned char *depth_maps, unsigned char *depth_colors, const int *widths, const int *heights,
-                   const float *intr, int fp_neighbourhood, int fp_threshold, const lsn::DepthSmoothTables *smooth,
-                   const lsn::TemporalSetting &temporal, unsigned long long temporal_gen)
+                   const float *intr, const DepthStages &stages)
 {
     ml.forget_last();
     MeshCall call;
@@ -1049,11 +1021,7 @@ int radial_sharded(Ctx &c, Lane &ml, int n_maps, unsigned char *depth_maps, unsi
     call.radial = true;
     call.back_d = depth_maps;
     call.back_c = depth_colors;
-    call.fp_neighbourhood = fp_neighbourhood;
-    call.fp_threshold = fp_threshold;
-    if (smooth_on(smooth)) call.smooth = std::make_shared<const lsn::DepthSmoothTables>(*smooth);
-    call.temporal = temporal;
-    call.temporal_gen = temporal_gen;
+    call.stages = stages;
     ShardedCall sc(c, call);
     sc.only_radial = true;
     plan_shards(n_maps, (int)c.shards.size(), sc.first, sc.D);
@@ -1196,15 +1164,12 @@ int fuse_host(Ctx &c, Lane &l, const MeshCall &call, Mesh *out)
 
 // depthMapAndColorSetRadialCorrection on the lane (one device) or over the devices of $LSN_HOST_DEVICES.  The lane's lock is held.
 void radial_host(Ctx &c, Lane &l, int n_maps, unsigned char *depth_maps, unsigned char *depth_colors, const int *widths, const int *heights,
-                 const float *intr_params, int fp_neighbourhood, int fp_threshold, const lsn::DepthSmoothTables *smooth_tables,
-                 const lsn::TemporalSetting &temporal_setting, unsigned long long temporal_gen)
+                 const float *intr_params, const DepthStages &stages)
 {
     if (c.shards.size() >= 2 && n_maps >= 2) {
-        (void)radial_sharded(c, l, n_maps, depth_maps, depth_colors, widths, heights, intr_params, fp_neighbourhood, fp_threshold, smooth_tables, temporal_setting,
-                             temporal_gen);
+        (void)radial_sharded(c, l, n_maps, depth_maps, depth_colors, widths, heights, intr_params, stages);
         return;
     }
-    const bool flying = flying_on(fp_neighbourhood);   // every group's raw maps are filtered into d_flying, which its correction reads
     l.last_nv = -1;   // the lane's buffers are about to be reused
     l.last_plan = nullptr;
     l.groups.clear();
@@ -1217,11 +1182,7 @@ void radial_host(Ctx &c, Lane &l, int n_maps, unsigned char *depth_maps, unsigne
         cbytes += q.cbytes;
     }
     if (l.d_depth.reserve(dbytes + 16) || l.d_colors.reserve(cbytes + 16) || l.d_depth2.reserve(dbytes + 16) || l.d_colors2.reserve(cbytes + 16)) return;
-    if (flying && l.d_flying.reserve(dbytes + 16)) return;
-    const bool temporal = temporal_on(temporal_setting);   // ... the temporal filter in front of it, into d_temporal (each call is one tick)
-    if (temporal && (l.d_temporal.reserve(dbytes + 16) || l.temporal_history(widths, heights, n_maps, temporal_gen))) return;
-    const bool smooth = smooth_on(smooth_tables);      // ... and smoothed into d_smooth behind that
-    if (smooth && l.d_smooth.reserve(dbytes + 16)) return;
+    if (l.pre.reserve(stages, dbytes, widths, heights, n_maps, l.stream)) return;   // the stages in front of every group's correction (each call is one tick)
     // Both directions are pageable copies that keep the thread; what overlaps is the correction itself (~100 us per group, latency
     // bound) with the next group's upload and the previous group's way home.  Out of place on the device (the warped, un-closed
     // maps stay in LDS); a group's slice of the caller's arrays is overwritten once ITS kernels have run -- a call that fails
@@ -1246,21 +1207,9 @@ void radial_host(Ctx &c, Lane &l, int n_maps, unsigned char *depth_maps, unsigne
         }
         for (; ok && next_group < G && l.groups[next_group].ready_after == (int)i + 1; next_group++) {
             const Group &q = l.groups[next_group];
-            const char *raw_d = l.d_depth.as<char>() + q.d_off;
-            if (temporal) {
-                ok = temporal_maps(l, q.radial_plan, temporal_setting, q.d_off, raw_d, l.stream) == 0;
-                raw_d = l.d_temporal.as<char>() + q.d_off;
-            }
-            if (ok && flying) {
-                ok = lsn::flying_pixels(q.radial_plan, fp_neighbourhood, fp_threshold, raw_d, l.d_flying.as<char>() + q.d_off, l.stream) == 0;
-                raw_d = l.d_flying.as<char>() + q.d_off;
-            }
-            if (ok && smooth) {
-                ok = smooth_maps(q.radial_plan, *smooth_tables, raw_d, l.d_smooth.as<char>() + q.d_off, l.stream) == 0;
-                raw_d = l.d_smooth.as<char>() + q.d_off;
-            }
-            ok = ok && lsnFusionRadialCorrectTo(q.radial_plan, intr_params + 7 * q.first, raw_d, l.d_colors.as<char>() + q.c_off,
-                                          l.d_depth2.as<char>() + q.d_off, l.d_colors2.as<char>() + q.c_off, l.stream) == 0 &&
+            const void *raw_d = l.pre.run(q.radial_plan, stages, l.d_depth, q.d_off, l.stream);
+            ok = raw_d && lsnFusionRadialCorrectTo(q.radial_plan, intr_params + 7 * q.first, raw_d, l.d_colors.as<char>() + q.c_off,
+                                                   l.d_depth2.as<char>() + q.d_off, l.d_colors2.as<char>() + q.c_off, l.stream) == 0 &&
                  hipEventRecord(l.ev_group[next_group], l.stream) == hipSuccess;
             // the group before goes home while this one is being corrected -- but never before every upload run it shares with a later
             // group has been read (a depth run may cover sensors of the next group: write_back_runs only takes runs that END in k)

@@ -164,6 +164,12 @@ int temporal(LsnFusion *p, const TemporalSetting &ts, const void *d_depth_in, vo
              hipStream_t s);
 int temporal_counts(LsnFusion *p, const DevBuf &counts, int tick, int *per_frame4);
 
+// What "on" means for the two stages behind it, for everybody who chains them in front of the correction (the host exports' DepthStages,
+// host_ctx.hpp; the tick object, tick.hip): a neighbourhood / a radius of at least one pixel; 0 and below mean off.  The temporal filter's is
+// TemporalSetting::on().
+inline bool flying_on(int neighbourhood) { return neighbourhood >= 1; }
+inline bool smooth_on(int radius) { return radius >= 1; }
+
 // A batch of meshes in lsnFusionRunMesh's layout, as the three stages on the merged mesh read it (render.hip, simplify.hip, normals.hip;
 // what they share is mesh_batch.hip's).  The stages' device structs embed it; it is built from a plan (plan_batch, mesh_batch.hip) or
 // from a lane's last mesh (LastMesh::batch, abi.hip).

@@ -203,9 +203,9 @@ extern "C" int lsnTickRun(LsnTick *t, const void *d_depth_in, const void *d_colo
         }
         LSN_HIP(hipSetDevice(t->device));
         hipStream_t s = lsn::as_stream(stream);
-        const bool filter = t->fp_neighbourhood >= 1;
+        const bool filter = lsn::flying_on(t->fp_neighbourhood);
         if (filter && t->d_filtered.reserve(2 * (size_t)t->cap * t->n_ticks + 16)) return -1;
-        const bool smooth = t->ds_radius >= 1;
+        const bool smooth = lsn::smooth_on(t->ds_radius);
         if (smooth && t->d_smoothed.reserve(2 * (size_t)t->cap * t->n_ticks + 16)) return -1;
         // the temporal filter runs once over the whole batch, in tick order, on the caller's stream in front of the fork: the halves share the
         // rig, so plan 0's frame and tile tables serve all ticks, and one history sees them in order.  The halves then start from d_temporal

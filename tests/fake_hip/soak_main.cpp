@@ -4,7 +4,8 @@
 //   2. the call mix of LiveScanServer from four threads at once (MainWindowForm.cs:238,304: updateWorker's merge calls, refineWorker's
 //      single-sensor calls + ICP, plus the radial export and all six last-mesh formats), every result checked against what the runtime
 //      double's kernels "compute" (every non-zero depth pixel survives, one triangle per vertex);
-//   3. the pool of pinned mesh blocks must be empty at the end.
+//   3. the setters of two process-wide switches from four threads at once: every "previous" value handed back is one that was stored;
+//   4. the pool of pinned mesh blocks must be empty at the end.
 // $LSN_HOST_DEVICES (read by the library) switches the merge calls to the sharded flow; $LSN_TEST_FAIL_ALLOC / $LSN_TEST_THROW make
 // single calls fail, which must leave empty meshes and still an empty pool.  Exit code 0 = all checks held (the sanitizer adds its own).
 #include "../../include/NativeUtils.h"
@@ -220,6 +221,59 @@ void icp_thread(int iters)
         const float r = ICP(a.data(), b.data(), n1, n2, R, t, 3);
         CHECK(r == 1.0f, "ICP returned %f", r);
     }
+}
+
+// lsnSetTemporalFilter and lsnSetDepthSmooth, two threads each, every thread alternating between two triples and putting back what it was
+// handed.  A setter exchanges under one acquisition of its switch's lock, so whatever it hands back -- the raw numbers of an "off"
+// request included -- is a triple some call stored: one of `known` (the initial value first, which main reads before the threads start).
+// (A guard, not a reproduction: two setters that were handed the same previous value still hand back known ones.)
+template <class B>
+struct Triple {
+    int a;
+    B b, c;
+    bool operator==(const Triple &o) const { return a == o.a && b == o.b && c == o.c; }
+};
+
+template <class B>
+void setter_thread(int (*set)(int, B, B, int *, B *, B *), const char *what, const Triple<B> *known, int first, int rounds)
+{
+    for (int r = 0; r < rounds; r++) {
+        const Triple<B> &mine = known[1 + ((first + r) & 1)];
+        Triple<B> prev = {-12345, (B)-1, (B)-1};
+        if (set(mine.a, mine.b, mine.c, &prev.a, &prev.b, &prev.c)) {   // refused: only a fault hook can do that, and prev stays untouched
+            CHECK(g_faults && prev.a == -12345, "%s refused a valid triple", what);
+            continue;
+        }
+        CHECK(prev == known[0] || prev == known[1] || prev == known[2], "%s handed back (%d, %g, %g), which nobody stored", what, prev.a, (double)prev.b, (double)prev.c);
+        CHECK(set(prev.a, prev.b, prev.c, nullptr, nullptr, nullptr) == 0 || g_faults, "%s refused the triple it had handed back", what);
+    }
+}
+
+// Behind the call mix, not beside it: the switches are process-wide, and calls that found them on or off by chance would pass a number of
+// allocation fault points that depends on the scheduling.  The initial values are put back at the end.
+void setter_race(int rounds)
+{
+    Triple<int> tp[3] = {{0, 0, 0}, {64, 20, 2}, {128, 30, 1}};
+    Triple<float> ds[3] = {{0, 0.0f, 0.0f}, {1, 1.0f, 10.0f}, {2, 1.5f, 12.0f}};
+    const bool read = lsnSetTemporalFilter(tp[1].a, tp[1].b, tp[1].c, &tp[0].a, &tp[0].b, &tp[0].c) == 0 &&
+                      lsnSetTemporalFilter(tp[0].a, tp[0].b, tp[0].c, nullptr, nullptr, nullptr) == 0 &&
+                      lsnSetDepthSmooth(ds[1].a, ds[1].b, ds[1].c, &ds[0].a, &ds[0].b, &ds[0].c) == 0 &&
+                      lsnSetDepthSmooth(ds[0].a, ds[0].b, ds[0].c, nullptr, nullptr, nullptr) == 0;
+    CHECK(read || g_faults, "the switches' initial values");
+    if (!read) return;
+    std::vector<std::thread> th;
+    for (int k = 0; k < 2; k++) {
+        th.emplace_back(setter_thread<int>, lsnSetTemporalFilter, "lsnSetTemporalFilter", tp, k, rounds);
+        th.emplace_back(setter_thread<float>, lsnSetDepthSmooth, "lsnSetDepthSmooth", ds, k, rounds);
+    }
+    for (auto &t : th) t.join();
+    // each switch holds one of the values that were set; then the initial ones again
+    Triple<int> t_end = {-1, -1, -1};
+    Triple<float> d_end = {-1, -1.0f, -1.0f};
+    const bool put = lsnSetTemporalFilter(tp[0].a, tp[0].b, tp[0].c, &t_end.a, &t_end.b, &t_end.c) == 0 &&
+                     lsnSetDepthSmooth(ds[0].a, ds[0].b, ds[0].c, &d_end.a, &d_end.b, &d_end.c) == 0;
+    CHECK(g_faults || (put && (t_end == tp[0] || t_end == tp[1] || t_end == tp[2]) && (d_end == ds[0] || d_end == ds[1] || d_end == ds[2])),
+          "the switches ended at (%d, %d, %d) and (%d, %g, %g)", t_end.a, t_end.b, t_end.c, d_end.a, (double)d_end.b, (double)d_end.c);
 }
 
 void null_sweep()
@@ -551,6 +605,7 @@ int main(int argc, char **argv)
         th.emplace_back(icp_thread, iters);
         for (auto &t : th) t.join();
     }
+    setter_race(200 * iters);
     int live = -1, pooled = -1;
     long long bytes = -1;
     CHECK(lsnHostPoolStats(&live, &pooled, &bytes) == 0, "lsnHostPoolStats");

@@ -13,7 +13,7 @@ import numpy as np
 import pytest
 
 from livescan3d_amd import native
-from tests import color_cases, flying_ref, temporal_ref as ref
+from tests import color_cases, depth_smooth_ref, flying_ref, temporal_ref as ref
 from tests.support import child
 
 pytestmark = pytest.mark.gpu
@@ -165,22 +165,33 @@ def _H(*a):
     return hashlib.sha256(b"".join(np.ascontiguousarray(x).tobytes() for x in a)).hexdigest()
 
 
-@pytest.mark.parametrize("flow", [{}, {"LSN_HOST_GROUP": "1"}, {"LSN_HOST_DEVICES": "0,0"}], ids=["default", "group1", "shard2"])
-def test_host_exports_keep_one_history_per_rig(gpu, orc, flow):
-    """$LSN_TEMPORAL_FILTER with $LSN_FLYING_PIXELS in a child process per flow: the restatement, tests/flying_ref.py, then the oracle."""
-    rigs = frames(3, (96, 80))
+FLOWS = [{}, {"LSN_HOST_GROUP": "1"}, {"LSN_HOST_DEVICES": "0,0"}]
 
-    def tick(r, state):
-        """One call: (state', corrected depth, corrected colours, the maps in front of the correction)."""
-        dm, state, = ref.run_packed(r.depth_maps, state, *SETTING)
+
+@pytest.mark.parametrize("flow,smooth", [(f, False) for f in FLOWS] + [(f, True) for f in FLOWS],
+                         ids=["default", "group1", "shard2", "default-smooth", "group1-smooth", "shard2-smooth"])
+def test_host_exports_keep_one_history_per_rig(gpu, orc, flow, smooth):
+    """$LSN_TEMPORAL_FILTER with $LSN_FLYING_PIXELS -- and, in the second stage set, $LSN_DEPTH_SMOOTH: all three stages -- in a child
+    process per flow: the restatement, tests/flying_ref.py, (tests/depth_smooth_ref.py with the library's own tables,) then the oracle."""
+    rigs = frames(3, (96, 80))
+    tables = native.depth_smooth_gaussian(*SMOOTH) if smooth else None
+
+    def behind(dm, r, smoothed):
+        """The stages behind the temporal filter, then the correction: (corrected depth, corrected colours)."""
         dm, _ = flying_ref.filter_packed(dm, r.widths, r.heights, *FLYING)
+        if smoothed:
+            dm, changed, _ = depth_smooth_ref.smooth_packed(dm, r.widths, r.heights, SMOOTH[0], *tables)
+            assert (changed > 0).all()
         cd, cc = orc.radial_correction(dm, r.depth_colors, r.widths, r.heights, r.intr)
-        return state, np.asarray(cd).view(np.uint8).ravel(), np.asarray(cc).ravel()
+        return np.asarray(cd).view(np.uint8).ravel(), np.asarray(cc).ravel()
+
+    def tick(r, state, smoothed=smooth):
+        """One call: (state', corrected depth, corrected colours)."""
+        dm, state, = ref.run_packed(r.depth_maps, state, *SETTING)
+        return (state,) + behind(dm, r, smoothed)
 
     def off(r):
-        dm, _ = flying_ref.filter_packed(r.depth_maps, r.widths, r.heights, *FLYING)
-        cd, cc = orc.radial_correction(dm, r.depth_colors, r.widths, r.heights, r.intr)
-        return _H(np.asarray(cd).view(np.uint8).ravel(), np.asarray(cc).ravel())
+        return _H(*behind(r.depth_maps, r, smooth))
 
     want, s = [], None
     for r in rigs:                                                    # three consecutive calls
@@ -191,6 +202,8 @@ def test_host_exports_keep_one_history_per_rig(gpu, orc, flow):
     assert (br == ref.FILL).sum() > 100 and (br == ref.BLEND).sum() > 1000
     assert want[2] != _H(*tick(rigs[2], None)[1:]) and want[1] != off(rigs[1]) and want[0] == off(rigs[0])     # (a first tick is the identity)
     s0, cd, cc = tick(rigs[0], None)
+    if smooth:                                                        # smoothing did something: tick 1 differs from the unsmoothed one
+        assert want[1] != _H(*tick(rigs[1], s0, smoothed=False)[1:])
     want.append(_H(cd, cc))                                           # fresh after the changed rig
     assert want[3] == want[0]
     s1, cd, cc = tick(rigs[1], s0)
@@ -206,7 +219,7 @@ def test_host_exports_keep_one_history_per_rig(gpu, orc, flow):
     mv, _, mt = orc.generate_mesh(r.depth_maps, r.depth_colors, r.widths, r.heights, r.intr, r.wt, r.bounds)
     want.append(_H(mv, np.asarray(mt, np.int32)))
     want.append(off(rigs[0]) + "(64,20,2)")
-    env = dict(flow, LSN_TEMPORAL_FILTER="64,20,2", LSN_FLYING_PIXELS="1,20")
+    env = dict(flow, LSN_TEMPORAL_FILTER="64,20,2", LSN_FLYING_PIXELS="1,20", **({"LSN_DEPTH_SMOOTH": "1,1.0,10"} if smooth else {}))
     got = child(CHILD, env, drop=DROP, timeout=600)[0].split()
     assert got == want, [i for i, (a, b) in enumerate(zip(got, want)) if a != b]
 
