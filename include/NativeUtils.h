@@ -607,6 +607,65 @@ int lsnFusionTemporalDiagnostics(LsnFusion *plan, int tick, int *blended, int *r
 int lsnSetTemporalFilter(int alpha_q, int delta, int persist, int *prev_alpha_q, int *prev_delta, int *prev_persist);
 int lsnResetTemporalFilter(void);
 
+/* Background subtraction: a learned per-pixel depth model of the EMPTY scene, what matches it dropped, the small blobs that survive dropped
+ * too -- "keep the subject, drop the room", which the axis-aligned crop box cannot do (the floor under the feet, a wall behind a shoulder,
+ * furniture inside the box).  It sits behind the temporal depth filter and in front of the flying-pixel filter (order: temporal ->
+ * background -> flying pixels -> depth smoothing -> radial correction): it sees the temporal stage's output (the raw maps when that stage is
+ * off) both when it learns and when it classifies, and the flying-pixel filter then cleans the silhouette the subtraction creates.  The
+ * reference has no such step; the stage is DEFINED here, tests/background_ref.py restates this text in numpy and the kernels are held to the
+ * restatement bit for bit, in maps, model and diagnostics.  Integers only.
+ * Inputs: per tick one u16 map (millimetres, 0 = no sample) per sensor.
+ * Parameters: margin in 1..4095 mm (<= 0: off); rel_q in 0..255, the part of the threshold that grows with depth, in 1/1024; min_pixels in
+ * 0..2^24 (<= 1: no blob pass).
+ * Model: one u16 per pixel of ONE tick, lo: the smallest non-zero sample seen while learning; 0 means none seen.  The model is itself a
+ * depth map: every u16 map is a valid model, and a zeroed buffer is "nothing learned".
+ *   1. Learn, per pixel and tick with sample c.  c != 0: lo' = (lo == 0) ? c : min(lo, c).  c == 0: unchanged.  Learning is therefore
+ *      order-independent, and a call of n ticks equals n calls of one tick.  A learning pass writes no maps.
+ *   2. Classify, per pixel and tick.  thr = margin + floor(lo * rel_q / 1024) (the product stays below 2^24).  c != 0 and lo == 0: UNKNOWN,
+ *      kept.  c != 0, lo != 0 and c + thr < lo (strict <, int arithmetic): FOREGROUND, kept.  Otherwise out = 0.  m is the kept mask.  The
+ *      model is never changed by classification.
+ *   3. Blobs, only when min_pixels >= 2.  Two kept pixels of the same frame and tick are joined when they are 4-neighbours (connectivity
+ *      is the mask alone: no depth gate -- out of scope).  label[p] is the lowest raster index y * w + x in p's component, size its pixel
+ *      count.  A kept pixel survives iff size[label] >= min_pixels, else out = 0.  Only minima and integer counts enter, so the bytes do not
+ *      depend on the order of the device's atomics.
+ *   4. Diagnostics, per (tick, frame), six ints: foreground kept by classification, unknown kept by classification, samples removed as
+ *      background, components, components removed, pixels removed by the blob pass (the last three are 0 when no blob pass ran).
+ * The stage is pointwise plus per-frame, so out == in is allowed; any other overlap is refused with nothing written.
+ * lsnFusionSetBackground: the plan's setting.  margin <= 0: off (the default).  Out-of-range values are refused with a message (-1) and the
+ * previous setting stays in force.  Changing the setting keeps the model.
+ * lsnFusionBackgroundLearn: folds all ticks of d_depth ([n_ticks][pixels per tick] u16) into the plan's model, which is reserved (2 bytes per
+ * pixel of ONE tick, zeroed) on first use; it needs no setting.  Asynchronous on `stream`.
+ * lsnFusionBackground: d_depth_in into d_depth_out on all ticks and sensors of the plan against the plan's model (never learned: every
+ * sample is unknown and kept).  Off: a device-to-device copy (nothing when in place), the model untouched.  Asynchronous on `stream`; a call
+ * on another stream than the previous call's that touched the model first waits for that one.  The first call with the stage on reserves six
+ * count words per 128 x 16 tile of every tick; the first with min_pixels >= 2 reserves the blob pass's scratch, 8 bytes per pixel of
+ * min(n_ticks, 16) ticks (the pass labels 16 ticks at a time).  A plan that never runs the stage allocates nothing.
+ * lsnFusionBackgroundReset: zeroes the model (asynchronous on `stream`).
+ * lsnFusionBackgroundModelRead / lsnFusionBackgroundModelWrite (both synchronise `stream`): the model as [pixels per tick] u16 in the layout
+ * of one tick's depth maps, to / from host memory (before any learning: all 0).  Write accepts any map.
+ * lsnFusionBackgroundDiagnostics (synchronises `stream`): for tick `tick` of the plan's last lsnFusionBackground, per sensor (n_maps ints
+ * each, any pointer may be NULL) the six counts of 4.; all 0 after a call with the stage off.  Returns 0, -1 on error or before any call.
+ * lsnSetBackground: the process-wide switch of the stage in the exports that START AT RAW FRAMES, depthMapAndColorSetRadialCorrection and
+ * lsnCorrectAndGenerateMesh: each such call is ONE tick.  The model lives with the calling lane (on every device of $LSN_HOST_DEVICES: of
+ * that device's block), one value per pixel at the sensor's offset in the caller's arrays, whatever the grouping or host path; it is keyed
+ * by the rig (sensor count, widths, heights) and a generation.  lsnLearnBackground(n_calls) advances the generation.  When the rig or the
+ * generation changes, the lane zeroes its model and its next n_calls calls (the last value requested; 0 if none was) are LEARNING calls: a
+ * learning call folds its maps into the model, passes them through unchanged and runs no blob pass; the calls behind them subtract.
+ * generateMeshFromDepthMaps, generateVerticesFromDepthMap and lsnRefineFromDepthMaps never run the stage.  margin <= 0: off.  Out-of-range
+ * values are refused (-1, the setting stays).  Initially $LSN_BACKGROUND="margin,rel_q,min_pixels[,learn_calls]" (e.g. "40,8,64,30"; unset,
+ * malformed or refused: off, a refused value with a message on stderr); every call reads the current value.  The previous triple goes to
+ * prev_* (each may be NULL); returns 0.  lsnLearnBackground returns 0, -1 for a negative n_calls. */
+int lsnFusionSetBackground(LsnFusion *plan, int margin, int rel_q, int min_pixels);
+int lsnFusionBackgroundLearn(LsnFusion *plan, const void *d_depth, void *stream);
+int lsnFusionBackground(LsnFusion *plan, const void *d_depth_in, void *d_depth_out, void *stream);
+int lsnFusionBackgroundReset(LsnFusion *plan, void *stream);
+int lsnFusionBackgroundModelRead(LsnFusion *plan, unsigned short *h_model, void *stream);
+int lsnFusionBackgroundModelWrite(LsnFusion *plan, const unsigned short *h_model, void *stream);
+int lsnFusionBackgroundDiagnostics(LsnFusion *plan, int tick, int *foreground, int *unknown, int *background, int *components,
+                                   int *components_removed, int *pixels_removed, void *stream);
+int lsnSetBackground(int margin, int rel_q, int min_pixels, int *prev_margin, int *prev_rel_q, int *prev_min_pixels);
+int lsnLearnBackground(int n_calls);
+
 /* Radial correction of n_ticks x n_maps frames in place in HBM (same layouts as lsnFusionRun's inputs);
  * intr_params: host, 7 floats per sensor {cx,cy,fx,fy,r2,r4,r6}. */
 int lsnFusionRadialCorrect(LsnFusion *plan, const float *intr_params, void *d_depth_maps, void *d_depth_colors, void *stream);
@@ -851,6 +910,16 @@ int lsnTickSetDepthSmooth(LsnTick *tick, int radius, float sigma_s, float sigma_
  * keeps the history.  lsnTickTemporalReset zeroes the history (asynchronous on `stream`). */
 int lsnTickSetTemporal(LsnTick *tick, int alpha_q, int delta, int persist);
 int lsnTickTemporalReset(LsnTick *tick, void *stream);
+/* Background subtraction (lsnFusionBackground) as the tick's second stage: lsnTickRun then runs temporal (if set) -> background -> flying
+ * pixels (if set) -> depth smoothing (if set) -> radial correction -> vertices -> triangles.  The tick object owns ONE model and a scratch
+ * of the batch's size; the pass runs once over the whole batch on the caller's stream in front of the fork of a two-part tick, right behind
+ * the temporal pass, whose output it reads; d_depth_in stays untouched.  margin <= 0: off (the default); out-of-range values are refused
+ * (-1) and leave the previous setting; changing the setting keeps the model.  lsnTickBackgroundLearn folds every tick of d_depth_in -- as
+ * the temporal stage serves it, when that is set, whose history advances -- into the model (reserved on first use) and runs nothing else;
+ * lsnTickBackgroundReset zeroes the model.  Both are asynchronous on `stream`. */
+int lsnTickSetBackground(LsnTick *tick, int margin, int rel_q, int min_pixels);
+int lsnTickBackgroundLearn(LsnTick *tick, const void *d_depth_in, void *stream);
+int lsnTickBackgroundReset(LsnTick *tick, void *stream);
 int lsnTickRun(LsnTick *tick, const void *d_depth_in, const void *d_colors_in, void *d_depth_corrected, void *d_colors_corrected,
                void *d_vertices, int *d_offsets, void *d_triangles, int *d_tri_offsets, void *stream);
 

@@ -6,7 +6,7 @@
 // upload schedule, kernels storing into the pinned mesh blocks, the copy-engine flow, the call sharded over devices -- is
 // host_flows.hip; the context it runs on (lanes, pinned pool, devices) and the records a call carries host_ctx.hpp.  This file: argument
 // checks, locks, the exception trampoline, the process-wide switches of the exports' opt-in stages (the outlier filter, the overlay merge;
-// the temporal filter, the flying-pixel filter and depth smoothing in front of the radial correction, which current_stages() hands to a
+// the temporal filter, background subtraction, the flying-pixel filter and depth smoothing in front of the radial correction, which current_stages() hands to a
 // call) with their setters, and the exports that need no flow (error channel, device helpers, createMesh / deleteMesh, ICP, the outbound
 // formats of the last mesh).
 #include "host_ctx.hpp"
@@ -335,13 +335,84 @@ static TemporalSwitch &temporal_switch()
     return *s;
 }
 
-// The stages in front of the radial correction that a call of this rig takes with it: the three switches as they stand when it is called.
+// Background subtraction of the same two exports, behind the temporal filter (lsnSetBackground): (margin, rel_q, min_pixels), the generation
+// lsnLearnBackground advances and the learning calls it asked for -- a lane whose model is of an older generation zeroes it and learns for
+// that many calls before it subtracts.  The other exports never read it, for the flying pixels' reason.
+namespace {
+struct BackgroundSwitch {
+    std::mutex mu;
+    lsn::BackgroundSetting setting;
+    int margin = 0, rel_q = 0, min_pixels = 0;   // what an "off" setting was given, so that the previous triple goes back as it came
+    int learn_calls = 0;                         // the last value lsnLearnBackground (or the environment) requested
+    unsigned long long gen = 1;
+    std::vector<int> rig;                        // the rig of the last call with the stage on: sensor count, widths, heights
+    BackgroundSwitch()
+    {
+        const char *e = getenv("LSN_BACKGROUND");
+        if (!e || !*e) return;
+        int m = 0, q = 0, p = 0, n = 0, used = 0;
+        const int got = sscanf(e, " %d , %d , %d %n, %d %n", &m, &q, &p, &used, &n, &used);
+        if ((got == 3 || got == 4) && e[used] == '\0' && n >= 0) {
+            if (exchange(m, q, p, nullptr, nullptr, nullptr) == 0) {
+                learn_calls = n;
+                return;
+            }
+            fprintf(stderr, "[NativeUtils] $LSN_BACKGROUND=\"%s\": %s: background subtraction stays off\n", e, lsn::error_buffer());
+            lsn::clear_error();
+            return;
+        }
+        fprintf(stderr, "[NativeUtils] $LSN_BACKGROUND=\"%s\" is not \"margin,rel_q,min_pixels[,learn_calls]\" (e.g. \"40,8,64,30\"): background subtraction stays off\n", e);
+    }
+    // lsnSetBackground: the new triple in, the previous one to prev_* (any may be null), under one acquisition of the lock; refused (-1, with
+    // the message) it leaves the setting and prev_* as they were
+    int exchange(int m, int q, int p, int *prev_m, int *prev_q, int *prev_p)
+    {
+        if (lsn::background_setting_ok("lsnSetBackground", m, q, p)) return -1;
+        std::lock_guard<std::mutex> g(mu);
+        if (prev_m) *prev_m = margin;
+        if (prev_q) *prev_q = rel_q;
+        if (prev_p) *prev_p = min_pixels;
+        setting = m >= 1 ? lsn::BackgroundSetting{m, q, p} : lsn::BackgroundSetting{};
+        margin = m;
+        rel_q = q;
+        min_pixels = p;
+        return 0;
+    }
+    // what a call of this rig takes with it; a call of another rig than the last one's starts a generation of its own, so that every lane --
+    // the shards' too, which only ever see their blocks -- zeroes its model and learns again
+    void current(DepthStages &st, int n_maps, const int *widths, const int *heights)
+    {
+        std::lock_guard<std::mutex> g(mu);
+        st.background = setting;
+        if (setting.on() && n_maps > 0 && widths && heights) {
+            std::vector<int> now(1, n_maps);
+            now.insert(now.end(), widths, widths + n_maps);
+            now.insert(now.end(), heights, heights + n_maps);
+            if (now != rig) {
+                rig.swap(now);
+                gen++;
+            }
+        }
+        st.background_gen = gen;
+        st.background_learn = learn_calls;
+    }
+};
+}  // namespace
+
+static BackgroundSwitch &background_switch()
+{
+    static auto *s = new BackgroundSwitch();   // never destroyed, like the pairs above
+    return *s;
+}
+
+// The stages in front of the radial correction that a call of this rig takes with it: the four switches as they stand when it is called.
 static DepthStages current_stages(int n_maps, const int *widths, const int *heights)
 {
     DepthStages st;
     flying_setting().current(st.fp_neighbourhood, st.fp_threshold);
     st.smooth = smooth_setting().current();
     temporal_switch().current(st.temporal, st.temporal_gen, n_maps, widths, heights);
+    background_switch().current(st, n_maps, widths, heights);
     return st;
 }
 
@@ -440,6 +511,30 @@ extern "C" int lsnResetTemporalFilter(void)
         TemporalSwitch &s = temporal_switch();
         std::lock_guard<std::mutex> g(s.mu);
         s.gen++;   // every lane finds its history stale at its next filtering call
+        return 0;
+    });
+}
+
+extern "C" int lsnSetBackground(int margin, int rel_q, int min_pixels, int *prev_margin, int *prev_rel_q, int *prev_min_pixels)
+{
+    return lsn::guarded("lsnSetBackground", -1, [&]() {
+        lsn::clear_error();
+        return background_switch().exchange(margin, rel_q, min_pixels, prev_margin, prev_rel_q, prev_min_pixels);
+    });
+}
+
+extern "C" int lsnLearnBackground(int n_calls)
+{
+    return lsn::guarded("lsnLearnBackground", -1, [&]() {
+        lsn::clear_error();
+        if (n_calls < 0) {
+            lsn::set_error("lsnLearnBackground: n_calls %d is negative", n_calls);
+            return -1;
+        }
+        BackgroundSwitch &s = background_switch();
+        std::lock_guard<std::mutex> g(s.mu);
+        s.learn_calls = n_calls;
+        s.gen++;   // every lane finds its model stale at its next call with the stage on
         return 0;
     });
 }

@@ -619,6 +619,13 @@ struct LsnFusion {
     lsn::DevBuf tp_state, tp_counts;
     int tp_last = 0;                     // what the last call was: 0 = none yet, 1 = a copy (off), 2 = the filter
     hipStream_t tp_stream = nullptr;     // ... and its stream
+    // background subtraction (background.hip): the setting of lsnFusionSetBackground (off by default) and, allocated by the first call that
+    // needs them, the model -- one u16 per pixel of one tick --, six words per 128 x 16 tile of every tick and the blob pass's scratch
+    lsn::BackgroundSetting bg_setting;
+    lsn::DevBuf bg_model, bg_counts, bg_blob;
+    int bg_last = 0;                     // what the last lsnFusionBackground was: 0 = none yet, 1 = a copy (off), 2 = the stage
+    bool bg_busy = false;                // a call has touched the model on ...
+    hipStream_t bg_stream = nullptr;     // ... this stream (the model is handed from call to call)
     // the three stages on the merged mesh (render.hip, simplify.hip, normals.hip): each one's scratch, allocated on its first call
     lsn::RenderScratch rv;
     lsn::SimplifyScratch sp;

@@ -43,12 +43,17 @@ constexpr int kMaxGroups = 16;
 struct Ctx;
 
 // The opt-in stages on a call's raw u16 depth maps, in front of its radial correction, in the order they run: the temporal depth filter
-// (temporal.hip, lsnSetTemporalFilter) with the generation of lsnResetTemporalFilter, the flying-pixel filter (flying.hip,
+// (temporal.hip, lsnSetTemporalFilter) with the generation of lsnResetTemporalFilter, background subtraction (background.hip,
+// lsnSetBackground) with the generation of lsnLearnBackground and the learning calls it asked for, the flying-pixel filter (flying.hip,
 // lsnSetFlyingPixelFilter), depth smoothing (depth_smooth.hip, lsnSetDepthSmooth; the Gaussian tables, null: off).  The export fills it from
 // the process-wide switches (abi.hip); this is the one place that says when a stage runs.
 struct DepthStages {
     lsn::TemporalSetting temporal;
     unsigned long long temporal_gen = 0;
+    lsn::BackgroundSetting background;
+    unsigned long long background_gen = 0;
+    int background_learn = 0;        // the learning calls a lane runs when it starts a generation
+    bool background_on() const { return background.on(); }
     int fp_neighbourhood = 0, fp_threshold = 0;
     std::shared_ptr<const lsn::DepthSmoothTables> smooth;
     bool temporal_on() const { return temporal.on(); }
@@ -59,11 +64,32 @@ struct DepthStages {
 // A lane's side of those stages: each stage's output, laid out like the lane's d_depth, which the next stage or the correction reads; the
 // temporal filter's history of the rig the lane sees call after call, one word per pixel at the sensor's offset in the call's arrays (so
 // neither grouping nor the host path changes which word a pixel owns), keyed by the rig (sensor count, widths, heights) and the reset
-// generation; the branch counts of its last launch.  All allocated by the first call that runs the stage.
+// generation; the branch counts of its last launch.  Background subtraction's model lives the same way, one u16 per pixel, keyed by the rig
+// and lsnLearnBackground's generation, with the learning calls the lane still owes, the blob pass's scratch and the stage's counts.  All
+// allocated by the first call that runs the stage.
 struct DepthChain {
-    lsn::DevBuf d_temporal, d_flying, d_smooth, tp_state, tp_counts;
-    std::vector<int> tp_rig;
-    unsigned long long tp_gen = 0;
+    lsn::DevBuf d_temporal, d_background, d_flying, d_smooth, tp_state, tp_counts, bg_model, bg_blob, bg_counts;
+    std::vector<int> tp_rig, bg_rig;
+    unsigned long long tp_gen = 0, bg_gen = 0;
+    int bg_learn_left = 0;           // learning calls still to come
+    bool bg_learning = false;        // ... and whether the call in progress is one (decided once per call, in reserve())
+    // the model up to date for a call of this rig and generation: zeroed, with `learn_calls` learning calls ahead, when either changed
+    int model(const int *widths, const int *heights, int count, unsigned long long gen, int learn_calls, hipStream_t s)
+    {
+        std::vector<int> rig(1, count);
+        rig.insert(rig.end(), widths, widths + count);
+        rig.insert(rig.end(), heights, heights + count);
+        size_t pixels = 0;
+        for (int i = 0; i < count; i++) pixels += (size_t)widths[i] * heights[i];
+        if (bg_model.p && rig == bg_rig && gen == bg_gen) return 0;
+        const bool grown = !bg_model.p || bg_model.bytes < 2 * pixels + 16;
+        if (lsn::background_model_reserve(bg_model, pixels, s)) return -1;   // (a new buffer comes zeroed)
+        if (!grown) LSN_HIP(hipMemsetAsync(bg_model.p, 0, 2 * pixels, s));
+        bg_rig.swap(rig);
+        bg_gen = gen;
+        bg_learn_left = learn_calls;
+        return 0;
+    }
     // the history up to date for a call of this rig and generation: zeroed when either changed
     int history(const int *widths, const int *heights, int count, unsigned long long gen, hipStream_t s)
     {
@@ -84,13 +110,18 @@ struct DepthChain {
     int reserve(const DepthStages &st, size_t dbytes, const int *widths, const int *heights, int count, hipStream_t s)
     {
         if (st.temporal_on() && (d_temporal.reserve(dbytes + 16) || history(widths, heights, count, st.temporal_gen, s))) return -1;
+        if (st.background_on()) {   // a call is one tick and counts once, whichever groups the host path cuts it into
+            if (d_background.reserve(dbytes + 16) || model(widths, heights, count, st.background_gen, st.background_learn, s)) return -1;
+            bg_learning = bg_learn_left > 0;
+            if (bg_learning) bg_learn_left--;
+        }
         if (st.flying_on() && d_flying.reserve(dbytes + 16)) return -1;
         if (st.smooth_on() && d_smooth.reserve(dbytes + 16)) return -1;
         return 0;
     }
     // Queues the stages that are on for one plan's maps, which start `off` bytes into the lane's depth block `d_depth` (and so into every
-    // buffer here; the history word of a pixel is off / 2), the temporal filter as ONE tick.  Returns the maps the correction must read --
-    // d_depth + off itself when nothing is on -- or null with the message set.
+    // buffer here; the history word and the model value of a pixel are at off / 2), the temporal filter and the subtraction as ONE tick.
+    // Returns the maps the correction must read -- d_depth + off itself when nothing is on -- or null with the message set.
     const void *run(LsnFusion *plan, const DepthStages &st, const lsn::DevBuf &d_depth, size_t off, hipStream_t s)
     {
         const char *in = d_depth.as<char>() + off;
@@ -98,6 +129,16 @@ struct DepthChain {
             char *out = d_temporal.as<char>() + off;
             if (lsn::temporal(plan, st.temporal, in, out, tp_state.as<unsigned int>() + off / 2, tp_counts, 1, s)) return nullptr;
             in = out;
+        }
+        if (st.background_on()) {   // a learning call folds its maps into the model and passes them on as they are
+            unsigned short *model = bg_model.as<unsigned short>() + off / 2;
+            char *out = d_background.as<char>() + off;
+            if (bg_learning) {
+                if (lsn::background_learn(plan, in, model, 1, s)) return nullptr;
+            } else {
+                if (lsn::background(plan, st.background, in, out, model, bg_counts, bg_blob, 1, s)) return nullptr;
+                in = out;
+            }
         }
         if (st.flying_on()) {
             char *out = d_flying.as<char>() + off;

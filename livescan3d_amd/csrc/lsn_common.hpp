@@ -164,6 +164,23 @@ int temporal(LsnFusion *p, const TemporalSetting &ts, const void *d_depth_in, vo
              hipStream_t s);
 int temporal_counts(LsnFusion *p, const DevBuf &counts, int tick, int *per_frame4);
 
+// Background subtraction (background.hip), the stage between the temporal filter and the flying-pixel filter.  One setting as the plans, the
+// tick and the process-wide switch hold it (margin <= 0: off; min_pixels <= 1: no blob pass).  background_learn and background are
+// lsnFusionBackgroundLearn and lsnFusionBackground with an explicit model and tick count, on a stream: the model belongs to whoever sees the
+// same rig tick after tick (a plan, a tick object, a lane of the host exports), not to the plan whose frame and tile tables the passes read.
+// Both take the plan's mutex.
+struct BackgroundSetting {
+    int margin = 0, rel_q = 0, min_pixels = 0;
+    bool on() const { return margin >= 1; }
+    bool blobs() const { return min_pixels >= 2; }
+};
+int background_setting_ok(const char *who, int margin, int rel_q, int min_pixels);
+int background_model_reserve(DevBuf &model, size_t pixels, hipStream_t s);
+int background_learn(LsnFusion *p, const void *d_depth, unsigned short *d_model, int n_ticks, hipStream_t s);
+int background(LsnFusion *p, const BackgroundSetting &bs, const void *d_depth_in, void *d_depth_out, const unsigned short *d_model, DevBuf &counts,
+               DevBuf &blob, int n_ticks, hipStream_t s);
+int background_counts(LsnFusion *p, const DevBuf &counts, int tick, int *per_frame6);
+
 // What "on" means for the two stages behind it, for everybody who chains them in front of the correction (the host exports' DepthStages,
 // host_ctx.hpp; the tick object, tick.hip): a neighbourhood / a radius of at least one pixel; 0 and below mean off.  The temporal filter's is
 // TemporalSetting::on().

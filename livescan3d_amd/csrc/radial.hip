@@ -1333,3 +1333,5 @@ extern "C" int lsnFusionRadialCorrectTo(LsnFusion *p, const float *intr_params, 
 #include "depth_smooth.hip"
 // ... and the temporal depth filter, the stage in front of all three (it shares the tile list too).
 #include "temporal.hip"
+// ... and background subtraction, the stage between the temporal filter and the flying-pixel filter (the same tile list).
+#include "background.hip"

@@ -30,6 +30,11 @@ struct LsnTick {
     lsn::DevBuf d_temporal;              // ... and its output, laid out like d_filtered: all reserved by the first run that filters
     hipStream_t tp_stream = nullptr;     // the stream of the last run that filtered (the history is handed from run to run)
     bool tp_ran = false;
+    lsn::BackgroundSetting bg;           // background subtraction behind the temporal filter (lsnTickSetBackground; off by default)
+    lsn::DevBuf bg_model, bg_counts, bg_blob;   // ... its model (one u16 per pixel of one tick), counts and blob scratch,
+    lsn::DevBuf d_background;            // ... and its output, laid out like d_filtered: each reserved by the first run that needs it
+    hipStream_t bg_stream = nullptr;     // the stream of the last run that touched the model (it is handed from run to run)
+    bool bg_ran = false;
     hipStream_t side = nullptr;
     hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_band = nullptr;
     std::mutex mu;
@@ -187,6 +192,82 @@ extern "C" int lsnTickTemporalReset(LsnTick *t, void *stream)
     });
 }
 
+extern "C" int lsnTickSetBackground(LsnTick *t, int margin, int rel_q, int min_pixels)
+{
+    return lsn::guarded("lsnTickSetBackground", -1, [&]() {
+        lsn::clear_error();
+        if (!t) {
+            lsn::set_error("lsnTickSetBackground: null argument");
+            return -1;
+        }
+        if (lsn::background_setting_ok("lsnTickSetBackground", margin, rel_q, min_pixels)) return -1;   // refused: the previous setting stays
+        std::lock_guard<std::mutex> g(t->mu);
+        t->bg = margin >= 1 ? lsn::BackgroundSetting{margin, rel_q, min_pixels} : lsn::BackgroundSetting{};
+        return 0;
+    });
+}
+
+// The temporal pass of a run or a learning call (t->mu held): the whole batch once, in tick order, on the caller's stream, plan 0's frame and
+// tile tables serving all ticks and one history seeing them in order; d_depth_in becomes its output.  Off: nothing.
+static int tick_temporal(LsnTick *t, const void *&d_depth_in, hipStream_t s)
+{
+    if (!t->tp.on()) return 0;
+    if (t->d_temporal.reserve(2 * (size_t)t->cap * t->n_ticks + 16) || lsn::temporal_state_reserve(t->tp_state, (size_t)t->cap, s)) return -1;
+    if (t->tp_ran && t->tp_stream != s) LSN_HIP(hipStreamSynchronize(t->tp_stream));
+    for (int k = 0; k < t->parts; k++)
+        if (t->plan[k]->rd.wait_for_chain(s)) return -1;
+    if (lsn::temporal(t->plan[0], t->tp, d_depth_in, t->d_temporal.p, t->tp_state.as<unsigned int>(), t->tp_counts, t->n_ticks, s)) return -1;
+    t->tp_stream = s;
+    t->tp_ran = true;
+    d_depth_in = t->d_temporal.p;
+    return 0;
+}
+
+// The tick's model ready for a call on stream s (t->mu held): reserved if asked for, handed over from the last call's stream.
+static int tick_model(LsnTick *t, bool reserve, hipStream_t s)
+{
+    if (reserve && lsn::background_model_reserve(t->bg_model, (size_t)t->cap, s)) return -1;
+    if (t->bg_ran && t->bg_stream != s) LSN_HIP(hipStreamSynchronize(t->bg_stream));
+    t->bg_stream = s;
+    t->bg_ran = true;
+    return 0;
+}
+
+extern "C" int lsnTickBackgroundLearn(LsnTick *t, const void *d_depth_in, void *stream)
+{
+    return lsn::guarded("lsnTickBackgroundLearn", -1, [&]() {
+        lsn::clear_error();
+        if (!t || !d_depth_in) {
+            lsn::set_error("lsnTickBackgroundLearn: null argument");
+            return -1;
+        }
+        std::lock_guard<std::mutex> g(t->mu);
+        LSN_HIP(hipSetDevice(t->device));
+        hipStream_t s = lsn::as_stream(stream);
+        // the stage learns what it will classify: the temporal stage's output when that is set
+        if (tick_temporal(t, d_depth_in, s) || tick_model(t, true, s)) return -1;
+        return lsn::background_learn(t->plan[0], d_depth_in, t->bg_model.as<unsigned short>(), t->n_ticks, s);
+    });
+}
+
+extern "C" int lsnTickBackgroundReset(LsnTick *t, void *stream)
+{
+    return lsn::guarded("lsnTickBackgroundReset", -1, [&]() {
+        lsn::clear_error();
+        if (!t) {
+            lsn::set_error("lsnTickBackgroundReset: null argument");
+            return -1;
+        }
+        std::lock_guard<std::mutex> g(t->mu);
+        if (!t->bg_model.p) return 0;   // nothing learned yet
+        LSN_HIP(hipSetDevice(t->device));
+        hipStream_t s = lsn::as_stream(stream);
+        if (tick_model(t, false, s)) return -1;
+        LSN_HIP(hipMemsetAsync(t->bg_model.p, 0, 2 * (size_t)t->cap, s));
+        return 0;
+    });
+}
+
 extern "C" int lsnTickRun(LsnTick *t, const void *d_depth_in, const void *d_colors_in, void *d_depth_corr, void *d_colors_corr, void *d_vertices,
                           int *d_offsets, void *d_triangles, int *d_tri_offsets, void *stream)
 {
@@ -210,15 +291,14 @@ extern "C" int lsnTickRun(LsnTick *t, const void *d_depth_in, const void *d_colo
         // the temporal filter runs once over the whole batch, in tick order, on the caller's stream in front of the fork: the halves share the
         // rig, so plan 0's frame and tile tables serve all ticks, and one history sees them in order.  The halves then start from d_temporal
         // at their own offsets.  (The scratch follows d_filtered's rule below: a run on another stream waits for the previous run's chains.)
-        if (t->tp.on()) {
-            if (t->d_temporal.reserve(2 * (size_t)t->cap * t->n_ticks + 16) || lsn::temporal_state_reserve(t->tp_state, (size_t)t->cap, s)) return -1;
-            if (t->tp_ran && t->tp_stream != s) LSN_HIP(hipStreamSynchronize(t->tp_stream));
+        if (tick_temporal(t, d_depth_in, s)) return -1;
+        // background subtraction follows right behind it under the same rules, from the temporal pass's output into scratch of its own
+        if (t->bg.on()) {
+            if (t->d_background.reserve(2 * (size_t)t->cap * t->n_ticks + 16) || tick_model(t, true, s)) return -1;
             for (int k = 0; k < t->parts; k++)
                 if (t->plan[k]->rd.wait_for_chain(s)) return -1;
-            if (lsn::temporal(t->plan[0], t->tp, d_depth_in, t->d_temporal.p, t->tp_state.as<unsigned int>(), t->tp_counts, t->n_ticks, s)) return -1;
-            t->tp_stream = s;
-            t->tp_ran = true;
-            d_depth_in = t->d_temporal.p;
+            if (lsn::background(t->plan[0], t->bg, d_depth_in, t->d_background.p, t->bg_model.as<unsigned short>(), t->bg_counts, t->bg_blob, t->n_ticks, s)) return -1;
+            d_depth_in = t->d_background.p;
         }
         // part k's slices of the caller's arrays: [tick][pixels], [tick][pixels][3], [tick][capacity] vertices, [tick][n_maps + 1], ...
         auto part = [&](int k, hipStream_t st) -> int {

@@ -133,6 +133,30 @@ class DeviceFusion:
     def temporal_diagnostics(self, tick=0, stream=None):
         return self.plan.temporal_diagnostics(tick, _stream_handle(stream))
 
+    def set_background(self, margin, rel_q=0, min_pixels=0):
+        self.plan.set_background(margin, rel_q, min_pixels)
+
+    def background_learn(self, depth=None, stream=None):
+        """Folds the batch's ticks into the plan's background model."""
+        self.plan.background_learn(self._in(depth)[0], _stream_handle(stream))
+
+    def background(self, depth_out, depth=None, stream=None):
+        """Background subtraction with the setting of set_background() against the plan's model, into depth_out (which may be the input
+        itself: in place)."""
+        self.plan.background(self._in(depth)[0], depth_out.data_ptr(), _stream_handle(stream))
+
+    def background_reset(self, stream=None):
+        self.plan.background_reset(_stream_handle(stream))
+
+    def background_model(self, stream=None):
+        return self.plan.background_model(_stream_handle(stream))
+
+    def set_background_model(self, model, stream=None):
+        self.plan.set_background_model(model, _stream_handle(stream))
+
+    def background_diagnostics(self, tick=0, stream=None):
+        return self.plan.background_diagnostics(tick, _stream_handle(stream))
+
     def render_views(self, intr, wt, width, height, points=False, stream=None):
         """The ticks' meshes (points: their vertices alone) drawn from the virtual cameras intr / wt (7 / 12 floats per view), each
         width x height.  Returns (depth int16-bit-pattern [T, V, h, w], rgb uint8 [T, V, h, w, 3]), both prefilled with SENTINEL."""

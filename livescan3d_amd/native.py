@@ -66,6 +66,8 @@ _PROTOTYPES = {
     "lsnDepthSmoothGaussian": (_i, [_i, _f, _f, _vp, _vp, _i]),
     "lsnSetTemporalFilter": (_i, [_i, _i, _i, _vp, _vp, _vp]),
     "lsnResetTemporalFilter": (_i, []),
+    "lsnSetBackground": (_i, [_i, _i, _i, _vp, _vp, _vp]),
+    "lsnLearnBackground": (_i, [_i]),
     # part 2: the device-resident API
     "lsnFusionCreate": (_vp, [_i, _i, _i, _vp, _vp]),
     "lsnFusionDestroy": (None, [_vp]),
@@ -104,6 +106,13 @@ _PROTOTYPES = {
     "lsnFusionTemporalStateRead": (_i, [_vp] * 3),
     "lsnFusionTemporalStateWrite": (_i, [_vp] * 3),
     "lsnFusionTemporalDiagnostics": (_i, [_vp, _i] + [_vp] * 5),
+    "lsnFusionSetBackground": (_i, [_vp, _i, _i, _i]),
+    "lsnFusionBackgroundLearn": (_i, [_vp] * 3),
+    "lsnFusionBackground": (_i, [_vp] * 4),
+    "lsnFusionBackgroundReset": (_i, [_vp, _vp]),
+    "lsnFusionBackgroundModelRead": (_i, [_vp] * 3),
+    "lsnFusionBackgroundModelWrite": (_i, [_vp] * 3),
+    "lsnFusionBackgroundDiagnostics": (_i, [_vp, _i] + [_vp] * 7),
     "lsnFusionRenderViews": (_i, [_vp, _i, _vp, _vp, _i, _i] + [_vp] * 7),
     "lsnFusionRenderDiagnostics": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp]),
     "lsnFusionSimplify": (_i, [_vp, _f] + [_vp] * 10),
@@ -159,6 +168,9 @@ _PROTOTYPES = {
     "lsnTickSetDepthSmooth": (_i, [_vp, _i, _f, _f]),
     "lsnTickSetTemporal": (_i, [_vp, _i, _i, _i]),
     "lsnTickTemporalReset": (_i, [_vp, _vp]),
+    "lsnTickSetBackground": (_i, [_vp, _i, _i, _i]),
+    "lsnTickBackgroundLearn": (_i, [_vp] * 3),
+    "lsnTickBackgroundReset": (_i, [_vp, _vp]),
     "lsnTickCapacity": (_ll, [_vp]),
     "lsnTickTriangleCapacity": (_ll, [_vp]),
     "lsnTickParts": (_i, [_vp]),
@@ -340,6 +352,20 @@ def reset_temporal_filter():
     _check(lib().lsnResetTemporalFilter(), "lsnResetTemporalFilter")
 
 
+def set_background(margin, rel_q=0, min_pixels=0):
+    """lsnSetBackground: the process-wide (margin, rel_q, min_pixels) of background subtraction in the exports that start at raw frames
+    (radial_correction, correct_and_generate_mesh), behind the temporal filter; each such call is one tick; margin <= 0: off.  Returns the
+    previous triple."""
+    pm, pq, pp = C.c_int(0), C.c_int(0), C.c_int(0)
+    _check(lib().lsnSetBackground(int(margin), int(rel_q), int(min_pixels), C.byref(pm), C.byref(pq), C.byref(pp)), "lsnSetBackground")
+    return pm.value, pq.value, pp.value
+
+
+def learn_background(n_calls):
+    """lsnLearnBackground: every lane zeroes its model at its next call with the stage on and learns for n_calls calls before it subtracts."""
+    _check(lib().lsnLearnBackground(int(n_calls)), "lsnLearnBackground")
+
+
 class _Scoped:
     """Sets a process-wide setting for the body of a with-statement: setter(*setting) returns the previous one, which goes back in on the
     way out (None: leaves the setting as it is)."""
@@ -438,7 +464,7 @@ def host_schedule(widths, heights, first=0, count=None, radial=False, sensors_pe
     return g, buf.value.decode()
 
 
-def radial_correction(depth_maps, depth_colors, widths, heights, intr, flying_pixels=None, depth_smooth=None, temporal_filter=None):
+def radial_correction(depth_maps, depth_colors, widths, heights, intr, flying_pixels=None, depth_smooth=None, temporal_filter=None, background=None):
     """KinectServer.CorrectRadialDistortionsForDepthMaps (KinectServer.cs:518-525): returns corrected copies
     (depth as a uint8 view of the u16 maps, colours); the export itself works in place on the arrays it is given.
     flying_pixels: None leaves the process-wide flying-pixel filter (lsnSetFlyingPixelFilter) as it is; (neighbourhood, threshold) sets
@@ -446,8 +472,10 @@ def radial_correction(depth_maps, depth_colors, widths, heights, intr, flying_pi
     depth_smooth: None leaves the process-wide depth smoothing (lsnSetDepthSmooth) as it is; (radius, sigma_s, sigma_r) sets it for this
     call alone (the maps are filtered if that is on, smoothed, then corrected).
     temporal_filter: None leaves the process-wide temporal depth filter (lsnSetTemporalFilter) as it is; (alpha_q, delta, persist) sets it
-    for this call alone (one tick of the history the library keeps for the rig; it runs in front of the other two)."""
-    with _Scoped(set_temporal_filter, temporal_filter), _Scoped(set_flying_pixel_filter, flying_pixels), _Scoped(set_depth_smooth, depth_smooth):
+    for this call alone (one tick of the history the library keeps for the rig; it runs in front of the other two).
+    background: None leaves the process-wide background subtraction (lsnSetBackground) as it is; (margin, rel_q, min_pixels) sets it for this
+    call alone (one tick against -- or, while the lane learns, into -- the model the library keeps for the rig; it runs behind the temporal filter)."""
+    with _Scoped(set_temporal_filter, temporal_filter), _Scoped(set_background, background), _Scoped(set_flying_pixel_filter, flying_pixels), _Scoped(set_depth_smooth, depth_smooth):
         require_gpu()
         n, dm, dc, widths, heights, intr, _, _ = _host_args(depth_maps, depth_colors, widths, heights, intr, copy=True)
         lib().depthMapAndColorSetRadialCorrection(n, _ptr(dm), _ptr(dc), _ptr(widths), _ptr(heights), _ptr(intr))
@@ -458,13 +486,13 @@ def radial_correction(depth_maps, depth_colors, widths, heights, intr, flying_pi
 
 
 def correct_and_generate_mesh(depth_maps, depth_colors, widths, heights, intr, wt, bounds, write_back=True, outlier_filter=None,
-                              flying_pixels=None, depth_smooth=None, temporal_filter=None):
+                              flying_pixels=None, depth_smooth=None, temporal_filter=None, background=None):
     """One call per tick (extension): radial correction + merge call with a single upload.  Returns (vertices, triangles,
     corrected depth as uint8, corrected colours); with write_back=False the last two are the untouched inputs.
     outlier_filter: as for generate_mesh_from_depth_maps (the corrected maps written back are the unmasked ones).
-    flying_pixels / depth_smooth / temporal_filter: as for radial_correction (the corrected maps written back are the filtered, smoothed,
-    corrected ones)."""
-    with _Scoped(set_temporal_filter, temporal_filter), _Scoped(set_flying_pixel_filter, flying_pixels), _Scoped(set_depth_smooth, depth_smooth), _Scoped(set_outlier_filter, outlier_filter):
+    flying_pixels / depth_smooth / temporal_filter / background: as for radial_correction (the corrected maps written back are the filtered,
+    subtracted, smoothed, corrected ones)."""
+    with _Scoped(set_temporal_filter, temporal_filter), _Scoped(set_background, background), _Scoped(set_flying_pixel_filter, flying_pixels), _Scoped(set_depth_smooth, depth_smooth), _Scoped(set_outlier_filter, outlier_filter):
         require_gpu()
         n, dm, dc, widths, heights, intr, wt, b = _host_args(depth_maps, depth_colors, widths, heights, intr, wt, bounds, copy=True)
         mesh = Mesh()
@@ -810,6 +838,42 @@ class FusionPlan(_Handle):
         _check(lib().lsnFusionTemporalDiagnostics(self._h, int(tick), *[_ptr(x) for x in c], stream or None), "lsnFusionTemporalDiagnostics")
         return np.stack(c, axis=1)[:self.n_maps]
 
+    def set_background(self, margin, rel_q=0, min_pixels=0):
+        """The plan's background subtraction (lsnFusionSetBackground): margin 1..4095 mm, rel_q 0..255 (1/1024), min_pixels 0..2^24 (<= 1: no
+        blob pass); margin <= 0: off.  A refused setting leaves the previous one; changing the setting keeps the model."""
+        _check(lib().lsnFusionSetBackground(self._h, int(margin), int(rel_q), int(min_pixels)), "lsnFusionSetBackground")
+
+    def background_learn(self, d_depth, stream=0):
+        """Folds every tick of d_depth into the plan's model (the smallest non-zero sample per pixel); writes no maps."""
+        _check(lib().lsnFusionBackgroundLearn(self._h, d_depth, stream or None), "lsnFusionBackgroundLearn")
+
+    def background(self, d_depth_in, d_depth_out, stream=0):
+        """Background subtraction on every tick of the plan, d_depth_in into d_depth_out (the same pointer: in place; any other overlap is
+        refused; off copies); the model is only read.  Run flying_pixels() / radial_correct_to() on d_depth_out next."""
+        _check(lib().lsnFusionBackground(self._h, d_depth_in, d_depth_out, stream or None), "lsnFusionBackground")
+
+    def background_reset(self, stream=0):
+        _check(lib().lsnFusionBackgroundReset(self._h, stream or None), "lsnFusionBackgroundReset")
+
+    def background_model(self, stream=0):
+        """The model: uint16 [pixels per tick] in the layout of one tick's depth maps (0: nothing learned)."""
+        m = np.zeros(max(self.capacity, 1), dtype=np.uint16)
+        _check(lib().lsnFusionBackgroundModelRead(self._h, _ptr(m), stream or None), "lsnFusionBackgroundModelRead")
+        return m[:self.capacity]
+
+    def set_background_model(self, model, stream=0):
+        m = _as(model, np.uint16).ravel()
+        if m.size != self.capacity:
+            raise NativeUtilsError(f"set_background_model: the model has {self.capacity} values, not {m.size}")
+        _check(lib().lsnFusionBackgroundModelWrite(self._h, _ptr(m), stream or None), "lsnFusionBackgroundModelWrite")
+
+    def background_diagnostics(self, tick=0, stream=0):
+        """What the last background() did in one tick: int32 [n, 6] per sensor -- foreground kept, unknown kept, background removed,
+        components, components removed, pixels removed by the blob pass."""
+        c = [np.zeros(max(self.n_maps, 1), dtype=np.int32) for _ in range(6)]
+        _check(lib().lsnFusionBackgroundDiagnostics(self._h, int(tick), *[_ptr(x) for x in c], stream or None), "lsnFusionBackgroundDiagnostics")
+        return np.stack(c, axis=1)[:self.n_maps]
+
     def render_views(self, intr, wt, width, height, d_vertices, d_offsets, d_triangles, d_tri_offsets, d_depth_out, d_colors_out, stream=0):
         """Render view: every tick's merged mesh (d_triangles None / 0: its vertices as points) drawn from the virtual cameras of intr
         (7 floats per view) / wt (12 per view), each width x height, into d_depth_out [n_ticks][n_views][h][w] u16 and d_colors_out
@@ -1051,6 +1115,17 @@ class TickPipeline(_Handle):
 
     def temporal_reset(self, stream=0):
         _check(lib().lsnTickTemporalReset(self._h, stream or None), "lsnTickTemporalReset")
+
+    def set_background(self, margin, rel_q=0, min_pixels=0):
+        """Background subtraction as the stage of run() behind the temporal filter (margin <= 0: off).  The tick object owns one model."""
+        _check(lib().lsnTickSetBackground(self._h, int(margin), int(rel_q), int(min_pixels)), "lsnTickSetBackground")
+
+    def background_learn(self, d_depth_in, stream=0):
+        """Folds the batch at d_depth_in (through the temporal filter, if that is set) into the tick object's model; runs nothing else."""
+        _check(lib().lsnTickBackgroundLearn(self._h, d_depth_in, stream or None), "lsnTickBackgroundLearn")
+
+    def background_reset(self, stream=0):
+        _check(lib().lsnTickBackgroundReset(self._h, stream or None), "lsnTickBackgroundReset")
 
     def run(self, d_depth_in, d_colors_in, d_depth_corr, d_colors_corr, d_vertices, d_offsets, d_triangles, d_tri_offsets, stream=0):
         _check(lib().lsnTickRun(self._h, d_depth_in, d_colors_in, d_depth_corr, d_colors_corr, d_vertices, d_offsets, d_triangles, d_tri_offsets, stream),

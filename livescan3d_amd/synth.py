@@ -127,10 +127,11 @@ def _ray_box(o, d, lo, hi):
     return np.where(hit, tmin, np.inf)
 
 
-def scene_frame(seed, tick, sensor, n_sensors, w=512, h=424, radius=2.0):
+def scene_frame(seed, tick, sensor, n_sensors, w=512, h=424, radius=2.0, subjects=True):
     """Ray-cast (float64) of a fixed scene from ring sensor `sensor`: sphere r=0.5 at the origin, floor y=-0.6
     (disc r=2.5), an off-centre box that breaks the symmetries.  depth = round(1000 z) +-2 mm hash jitter,
-    clamped to [500,4500], 2 % dropout.  Returns (depth u16 [h,w], rgb u8 [h,w,3])."""
+    clamped to [500,4500], 2 % dropout.  subjects=False: the empty room, the floor alone (what background subtraction
+    learns from).  Returns (depth u16 [h,w], rgb u8 [h,w,3])."""
     intr = kinect_intrinsics(w, h).astype(np.float64)
     cx, cy, fx, fy = intr[:4]
     R, t = ring_pose(sensor, n_sensors, radius)
@@ -154,6 +155,8 @@ def scene_frame(seed, tick, sensor, n_sensors, w=512, h=424, radius=2.0):
     # box
     tb = _ray_box(o, d, np.array([0.25, -0.6, -0.55]), np.array([0.65, 0.15, -0.15]))
     tb2 = _ray_box(o, d, np.array([-0.8, -0.6, 0.3]), np.array([-0.5, 0.4, 0.5]))
+    if not subjects:
+        ts = tb = tb2 = np.full_like(tf, np.inf)
     z = np.minimum(np.minimum(ts, tf), np.minimum(tb, tb2))
     which = np.argmin(np.stack([ts, tf, tb, tb2], axis=-1), axis=-1)
 
