@@ -34,9 +34,12 @@ def threshold(max_dist):
         return np.float32(np.float32(max_dist) * np.float32(max_dist))
 
 
-def k_distance(pts, k):
+def k_distance(pts, k, rules=None, pool=None):
     """KNNeighbors' kDistance (filter.cpp:19-34): the k-th smallest squared distance of every point to the cloud, chunked brute force;
-    FLT_MAX for every point of a cloud of fewer than k points (KNNResultSet::init writes dists[k-1], nothing overwrites it)."""
+    FLT_MAX for every point of a cloud of fewer than k points (KNNResultSet::init writes dists[k-1], nothing overwrites it).
+    rules (names of RULES) / pool: a neighbouring wrong rule instead (wrong_k_distance below); without them, exactly the above."""
+    if rules or pool is not None:
+        return wrong_k_distance(pts, k, rules, pool)
     pts = xyz(pts)
     n = len(pts)
     out = np.full(n, FLT_MAX, dtype=np.float32)
@@ -78,9 +81,12 @@ def neighbour_counts(pts, thr, idx=None):
     return out
 
 
-def keep_mask(pts, k, max_dist, brute_limit=8000):
+def keep_mask(pts, k, max_dist, brute_limit=8000, rules=None, pool=None):
     """The points filter() keeps (filter.cpp:40-58): kDistance > distThreshold removes.  Small clouds: the order statistic itself; larger
-    ones: its count form, #{d^2 <= thr} >= k (the same set: the k-th smallest is > thr iff fewer than k are <= thr)."""
+    ones: its count form, #{d^2 <= thr} >= k (the same set: the k-th smallest is > thr iff fewer than k are <= thr).
+    rules (names of RULES) / pool: a neighbouring wrong rule instead (wrong_keep_mask below); without them, exactly the above."""
+    if rules or pool is not None:
+        return wrong_keep_mask(pts, k, max_dist, rules, pool)
     pts = xyz(pts)
     n = len(pts)
     if k <= 0 or max_dist <= 0 or n == 0:   # :40-41 (a NaN maxDist passes this test)
@@ -93,6 +99,109 @@ def keep_mask(pts, k, max_dist, brute_limit=8000):
     if np.isnan(thr):
         return np.ones(n, dtype=bool)
     return neighbour_counts(pts, thr) >= k
+
+
+# ---- neighbouring wrong rules (tests/test_outlier_boundary_ref.py: every one of them is told apart from the filter by a named case) ----
+
+RULES = {
+    "lt_thr": "a neighbour needs d^2 < thr, not <=",
+    "self_not_counted": "the point itself is no neighbour of its own",
+    "duplicates_once": "points at one position count once",
+    "thr_not_squared": "thr = maxDist",
+    "thr_double": "thr = maxDist^2 kept in double",
+    "d2_double": "d^2: float differences, squared and summed in double",
+    "d2_right_to_left": "d^2 = d0*d0 + (d1*d1 + d2*d2)",
+    "d2_fma": "d^2 = fma(d2, d2, d0*d0 + d1*d1)",
+    "k_plus_1": "k + 1 neighbours asked for",
+    "small_le_k": "a block of n <= k points is a small block",
+    "small_removed": "a small block is always removed",
+    "small_kept": "a small block is always kept",
+    "scope_tick": "neighbours from every sensor of the tick",
+    "scope_batch": "neighbours from every sensor of every tick of the batch",
+}
+
+
+def _wrong_dist2(q, p, rules):
+    d0 = q[:, None, 0] - p[None, :, 0]
+    d1 = q[:, None, 1] - p[None, :, 1]
+    d2 = q[:, None, 2] - p[None, :, 2]
+    if "d2_double" in rules:
+        d0, d1, d2 = d0.astype(np.float64), d1.astype(np.float64), d2.astype(np.float64)
+        return d0 * d0 + d1 * d1 + d2 * d2
+    if "d2_right_to_left" in rules:
+        return d0 * d0 + (d1 * d1 + d2 * d2)
+    if "d2_fma" in rules:   # the product of two floats is exact in double; the sum is rounded to double and then to float
+        return (d2.astype(np.float64) * d2.astype(np.float64) + (d0 * d0 + d1 * d1).astype(np.float64)).astype(np.float32)
+    return d0 * d0 + d1 * d1 + d2 * d2
+
+
+def wrong_k_distance(pts, k, rules=None, pool=None):
+    """k_distance under the rules of `rules`; pool = (points, first): the neighbours come from `points`, of which pts is the slice that
+    starts at `first` (the scope rules, filter_batch below).  float64 under d2_double."""
+    rules = set(rules or ())
+    assert rules <= set(RULES), rules - set(RULES)
+    pts = xyz(pts)
+    cloud, first = (pts, 0) if pool is None else (xyz(pool[0]), int(pool[1]))
+    n = len(pts)
+    k = k + 1 if "k_plus_1" in rules else k
+    out = np.full(n, FLT_MAX, dtype=np.float64 if "d2_double" in rules else np.float32)
+    if n == 0 or (n <= k if "small_le_k" in rules else n < k):
+        return out
+    d = _wrong_dist2(pts, cloud, rules).astype(out.dtype)
+    big = np.asarray(np.inf, dtype=out.dtype)
+    if "duplicates_once" in rules:
+        _, firsts = np.unique(cloud, axis=0, return_index=True)
+        gone = np.ones(len(cloud), bool)
+        gone[firsts] = False
+        d[:, gone] = big
+    if "self_not_counted" in rules:
+        d[np.arange(n), first + np.arange(n)] = big
+    if d.shape[1] < k:
+        return out
+    kd = np.partition(d, k - 1, axis=1)[:, k - 1]
+    return np.where(np.isinf(kd) & ~np.isinf(out), out, kd).astype(out.dtype)   # fewer than k candidates left: init's FLT_MAX
+
+
+def wrong_keep_mask(pts, k, max_dist, rules=None, pool=None):
+    rules = set(rules or ())
+    assert rules <= set(RULES), rules - set(RULES)
+    pts = xyz(pts)
+    n = len(pts)
+    if k <= 0 or max_dist <= 0 or n == 0:
+        return np.ones(n, dtype=bool)
+    thr = threshold(max_dist)
+    if "thr_not_squared" in rules:
+        thr = np.float32(max_dist)
+    if "thr_double" in rules:
+        thr = np.float64(np.float32(max_dist)) ** 2
+    kk = k + 1 if "k_plus_1" in rules else k
+    if n <= kk if "small_le_k" in rules else n < kk:
+        if "small_removed" in rules or "small_kept" in rules:
+            return np.full(n, "small_kept" in rules)
+    kd = wrong_k_distance(pts, k, rules, pool)
+    return kd < thr if "lt_thr" in rules else ~(kd > thr)
+
+
+def filter_batch(ticks, k, max_dist, rules=None, brute_limit=8000):
+    """ticks[t][s]: the (n, 3) block of sensor s in tick t.  The keep mask of every block: every block on its own (keep_mask), unless
+    `rules` says otherwise."""
+    rules = set(rules or ())
+    out = []
+    everything = [b for tick in ticks for b in tick]
+    for t, tick in enumerate(ticks):
+        row = []
+        for s, b in enumerate(tick):
+            pool = None
+            if "scope_batch" in rules:
+                before = sum(len(x) for tk in ticks[:t] for x in tk) + sum(len(x) for x in tick[:s])
+                pool = (np.concatenate([xyz(x) for x in everything]), before)
+            elif "scope_tick" in rules:
+                pool = (np.concatenate([xyz(x) for x in tick]), sum(len(x) for x in tick[:s]))
+            only_scope = rules <= {"scope_tick", "scope_batch"}
+            row.append(keep_mask(b, k, max_dist, brute_limit) if not rules else
+                       keep_mask(b, k, max_dist, rules=rules - {"scope_tick", "scope_batch"} if not only_scope else None, pool=pool))
+        out.append(row)
+    return out
 
 
 def filter(vertices, colors, k, max_dist):
