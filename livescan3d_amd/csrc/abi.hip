@@ -271,51 +271,72 @@ static SmoothSetting &smooth_setting()
     return *s;
 }
 
-// The temporal depth filter of the same two exports, in front of the flying-pixel filter (lsnSetTemporalFilter): (alpha_q, delta, persist),
-// and the generation lsnResetTemporalFilter advances -- a lane whose history is of an older generation starts from none.  The other
-// exports never read it, for the flying pixels' reason: there the stage would run twice per tick.
+// The process-wide switch of a stage with state, for the same two exports: the triple as the stage holds it and as it was given, the
+// generation its reset export advances, the rig of the last call with the stage on.  A lane whose state is of an older generation starts
+// from none; a call of another rig than the last one's starts a generation of its own, so that every lane -- the shards' too, which only
+// ever see their blocks -- does.  The other exports never read the switches, for the flying pixels' reason: there the stage would run
+// twice per tick.
+//   the temporal depth filter, in front of the flying-pixel filter: lsnSetTemporalFilter (alpha_q, delta, persist), lsnResetTemporalFilter;
+//   background subtraction, behind the temporal filter: lsnSetBackground (margin, rel_q, min_pixels), lsnLearnBackground, which also sets
+//   the learning calls a lane runs on a zeroed model before it subtracts ($LSN_BACKGROUND's optional fourth field).
 namespace {
-struct TemporalSwitch {
+template <class Setting>
+struct StageSwitch {
     std::mutex mu;
-    lsn::TemporalSetting setting;
-    int alpha_q = 0, delta = 0, persist = 0;   // what an "off" setting was given, so that the previous triple goes back as it came
+    Setting setting;
+    int given[3] = {0, 0, 0};        // what an "off" setting was given, so that the previous triple goes back as it came
+    int learn_calls = 0;             // the last value lsnLearnBackground (or the environment) requested
     unsigned long long gen = 1;
-    std::vector<int> rig;                      // the rig of the last filtering call: sensor count, widths, heights
-    TemporalSwitch()
+    std::vector<int> rig;            // sensor count, widths, heights
+    int (*const ok)(const char *, int, int, int);
+    const char *const who;           // the set export, for the validator's message
+    // env: the variable; usage: its form with an example; what: the stage, for "... stays off"; fourth: a learn_calls field is admitted
+    StageSwitch(int (*validator)(const char *, int, int, int), const char *set_export, const char *env, const char *usage, const char *what, bool fourth)
+        : ok(validator), who(set_export)
     {
-        const char *e = getenv("LSN_TEMPORAL_FILTER");
+        const char *e = getenv(env);
         if (!e || !*e) return;
-        int a = 0, d = 0, p = 0, used = 0;
-        if (sscanf(e, " %d , %d , %d %n", &a, &d, &p, &used) == 3 && e[used] == '\0') {
-            if (exchange(a, d, p, nullptr, nullptr, nullptr) == 0) return;
-            fprintf(stderr, "[NativeUtils] $LSN_TEMPORAL_FILTER=\"%s\": %s: the temporal filter stays off\n", e, lsn::error_buffer());
+        int a = 0, b = 0, c = 0, n = 0, used = 0;
+        const int got = sscanf(e, " %d , %d , %d %n, %d %n", &a, &b, &c, &used, &n, &used);
+        if ((got == 3 || (fourth && got == 4)) && e[used] == '\0' && n >= 0) {
+            if (exchange(a, b, c, nullptr, nullptr, nullptr) == 0) {
+                learn_calls = n;
+                return;
+            }
+            fprintf(stderr, "[NativeUtils] $%s=\"%s\": %s: %s stays off\n", env, e, lsn::error_buffer(), what);
             lsn::clear_error();
             return;
         }
-        fprintf(stderr, "[NativeUtils] $LSN_TEMPORAL_FILTER=\"%s\" is not \"alpha_q,delta,persist\" (e.g. \"64,20,2\"): the temporal filter stays off\n", e);
+        fprintf(stderr, "[NativeUtils] $%s=\"%s\" is not %s: %s stays off\n", env, e, usage, what);
     }
-    // lsnSetTemporalFilter: the new triple in, the previous one to prev_* (any may be null), under one acquisition of the lock; refused (-1,
-    // with the message) it leaves the setting and prev_* as they were
-    int exchange(int a, int d, int p, int *prev_a, int *prev_d, int *prev_p)
+    // the set export: the new triple in, the previous one to prev_* (any may be null), under one acquisition of the lock; refused (-1, with
+    // the message) it leaves the setting and prev_* as they were
+    int exchange(int a, int b, int c, int *prev_a, int *prev_b, int *prev_c)
     {
-        if (lsn::temporal_setting_ok("lsnSetTemporalFilter", a, d, p)) return -1;
+        if (ok(who, a, b, c)) return -1;
         std::lock_guard<std::mutex> g(mu);
-        if (prev_a) *prev_a = alpha_q;
-        if (prev_d) *prev_d = delta;
-        if (prev_p) *prev_p = persist;
-        setting = a >= 1 ? lsn::TemporalSetting{a, d, p} : lsn::TemporalSetting{};
-        alpha_q = a;
-        delta = d;
-        persist = p;
+        if (prev_a) *prev_a = given[0];
+        if (prev_b) *prev_b = given[1];
+        if (prev_c) *prev_c = given[2];
+        setting = a >= 1 ? Setting{a, b, c} : Setting{};
+        given[0] = a;
+        given[1] = b;
+        given[2] = c;
         return 0;
     }
-    // what a call of this rig takes with it; a filtering call of another rig than the last one's starts a generation of its own, so that
-    // every lane -- the shards' too, which only ever see their blocks -- starts it from no history
-    void current(lsn::TemporalSetting &ts, unsigned long long &generation, int n_maps, const int *widths, const int *heights)
+    // the reset export: every lane finds its state stale at its next call with the stage on
+    void advance(int learn)
     {
         std::lock_guard<std::mutex> g(mu);
-        ts = setting;
-        if (ts.on() && n_maps > 0 && widths && heights) {
+        learn_calls = learn;
+        gen++;
+    }
+    // what a call of this rig takes with it
+    void current(Setting &st, unsigned long long &generation, int &learn, int n_maps, const int *widths, const int *heights)
+    {
+        std::lock_guard<std::mutex> g(mu);
+        st = setting;
+        if (st.on() && n_maps > 0 && widths && heights) {
             std::vector<int> now(1, n_maps);
             now.insert(now.end(), widths, widths + n_maps);
             now.insert(now.end(), heights, heights + n_maps);
@@ -325,83 +346,23 @@ struct TemporalSwitch {
             }
         }
         generation = gen;
+        learn = learn_calls;
     }
 };
 }  // namespace
 
-static TemporalSwitch &temporal_switch()
+static StageSwitch<lsn::TemporalSetting> &temporal_switch()
 {
-    static auto *s = new TemporalSwitch();   // never destroyed, like the pairs above
+    static auto *s = new StageSwitch<lsn::TemporalSetting>(   // never destroyed, like the pairs above
+        lsn::temporal_setting_ok, "lsnSetTemporalFilter", "LSN_TEMPORAL_FILTER", "\"alpha_q,delta,persist\" (e.g. \"64,20,2\")", "the temporal filter", false);
     return *s;
 }
 
-// Background subtraction of the same two exports, behind the temporal filter (lsnSetBackground): (margin, rel_q, min_pixels), the generation
-// lsnLearnBackground advances and the learning calls it asked for -- a lane whose model is of an older generation zeroes it and learns for
-// that many calls before it subtracts.  The other exports never read it, for the flying pixels' reason.
-namespace {
-struct BackgroundSwitch {
-    std::mutex mu;
-    lsn::BackgroundSetting setting;
-    int margin = 0, rel_q = 0, min_pixels = 0;   // what an "off" setting was given, so that the previous triple goes back as it came
-    int learn_calls = 0;                         // the last value lsnLearnBackground (or the environment) requested
-    unsigned long long gen = 1;
-    std::vector<int> rig;                        // the rig of the last call with the stage on: sensor count, widths, heights
-    BackgroundSwitch()
-    {
-        const char *e = getenv("LSN_BACKGROUND");
-        if (!e || !*e) return;
-        int m = 0, q = 0, p = 0, n = 0, used = 0;
-        const int got = sscanf(e, " %d , %d , %d %n, %d %n", &m, &q, &p, &used, &n, &used);
-        if ((got == 3 || got == 4) && e[used] == '\0' && n >= 0) {
-            if (exchange(m, q, p, nullptr, nullptr, nullptr) == 0) {
-                learn_calls = n;
-                return;
-            }
-            fprintf(stderr, "[NativeUtils] $LSN_BACKGROUND=\"%s\": %s: background subtraction stays off\n", e, lsn::error_buffer());
-            lsn::clear_error();
-            return;
-        }
-        fprintf(stderr, "[NativeUtils] $LSN_BACKGROUND=\"%s\" is not \"margin,rel_q,min_pixels[,learn_calls]\" (e.g. \"40,8,64,30\"): background subtraction stays off\n", e);
-    }
-    // lsnSetBackground: the new triple in, the previous one to prev_* (any may be null), under one acquisition of the lock; refused (-1, with
-    // the message) it leaves the setting and prev_* as they were
-    int exchange(int m, int q, int p, int *prev_m, int *prev_q, int *prev_p)
-    {
-        if (lsn::background_setting_ok("lsnSetBackground", m, q, p)) return -1;
-        std::lock_guard<std::mutex> g(mu);
-        if (prev_m) *prev_m = margin;
-        if (prev_q) *prev_q = rel_q;
-        if (prev_p) *prev_p = min_pixels;
-        setting = m >= 1 ? lsn::BackgroundSetting{m, q, p} : lsn::BackgroundSetting{};
-        margin = m;
-        rel_q = q;
-        min_pixels = p;
-        return 0;
-    }
-    // what a call of this rig takes with it; a call of another rig than the last one's starts a generation of its own, so that every lane --
-    // the shards' too, which only ever see their blocks -- zeroes its model and learns again
-    void current(DepthStages &st, int n_maps, const int *widths, const int *heights)
-    {
-        std::lock_guard<std::mutex> g(mu);
-        st.background = setting;
-        if (setting.on() && n_maps > 0 && widths && heights) {
-            std::vector<int> now(1, n_maps);
-            now.insert(now.end(), widths, widths + n_maps);
-            now.insert(now.end(), heights, heights + n_maps);
-            if (now != rig) {
-                rig.swap(now);
-                gen++;
-            }
-        }
-        st.background_gen = gen;
-        st.background_learn = learn_calls;
-    }
-};
-}  // namespace
-
-static BackgroundSwitch &background_switch()
+static StageSwitch<lsn::BackgroundSetting> &background_switch()
 {
-    static auto *s = new BackgroundSwitch();   // never destroyed, like the pairs above
+    static auto *s = new StageSwitch<lsn::BackgroundSetting>(   // never destroyed, like the pairs above
+        lsn::background_setting_ok, "lsnSetBackground", "LSN_BACKGROUND", "\"margin,rel_q,min_pixels[,learn_calls]\" (e.g. \"40,8,64,30\")",
+        "background subtraction", true);
     return *s;
 }
 
@@ -411,8 +372,9 @@ static DepthStages current_stages(int n_maps, const int *widths, const int *heig
     DepthStages st;
     flying_setting().current(st.fp_neighbourhood, st.fp_threshold);
     st.smooth = smooth_setting().current();
-    temporal_switch().current(st.temporal, st.temporal_gen, n_maps, widths, heights);
-    background_switch().current(st, n_maps, widths, heights);
+    int no_learning = 0;
+    temporal_switch().current(st.temporal, st.temporal_gen, no_learning, n_maps, widths, heights);
+    background_switch().current(st.background, st.background_gen, st.background_learn, n_maps, widths, heights);
     return st;
 }
 
@@ -508,9 +470,7 @@ extern "C" int lsnResetTemporalFilter(void)
 {
     return lsn::guarded("lsnResetTemporalFilter", -1, [&]() {
         lsn::clear_error();
-        TemporalSwitch &s = temporal_switch();
-        std::lock_guard<std::mutex> g(s.mu);
-        s.gen++;   // every lane finds its history stale at its next filtering call
+        temporal_switch().advance(0);   // every lane finds its history stale at its next filtering call
         return 0;
     });
 }
@@ -531,10 +491,7 @@ extern "C" int lsnLearnBackground(int n_calls)
             lsn::set_error("lsnLearnBackground: n_calls %d is negative", n_calls);
             return -1;
         }
-        BackgroundSwitch &s = background_switch();
-        std::lock_guard<std::mutex> g(s.mu);
-        s.learn_calls = n_calls;
-        s.gen++;   // every lane finds its model stale at its next call with the stage on
+        background_switch().advance(n_calls);   // every lane finds its model stale at its next call with the stage on
         return 0;
     });
 }

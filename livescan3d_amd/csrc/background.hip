@@ -12,25 +12,22 @@
 //             index, size = its pixel count; a kept pixel survives iff size[label] >= min_pixels.
 // Only minima and integer counts: the bytes do not depend on the order in which the device takes the pixels.
 //
-// Shape.  Every kernel takes 128 x 16 tiles of flying.hip's list with 256 lanes, one lane 8 consecutive pixels of a row (one 16-byte load
-// or store where VEC holds: widths that are multiples of 8, aligned buffers; else element-wise).
+// Shape.  Every kernel takes 128 x 16 tiles of flying.hip's list with tile_lane.hpp's lane: 8 consecutive pixels of a row.
 //   learn (bg_learn_kernel): temporal_kernel's shape.  One launch per call whatever its ticks, tiles_per_tick workgroups; a lane keeps its 8
 //     model values in registers as lo - 1 mod 2^16 (0 becomes 65535, "none seen" is the largest value: the rule is one unsigned minimum),
 //     keeps the loads of kBgAhead ticks in flight ahead of the minimum and stores the model once.
-//   classify (bg_classify_kernel): one launch over tiles x ticks.  The three counts (foreground, unknown, background) are packed per lane,
-//     summed per wave (wave_ops.hpp) and stored as plain words per (tick, tile) with three zeros behind them.  min_pixels <= 1: that is
+//   classify (bg_classify_kernel): one launch over tiles x ticks.  The three counts (foreground, unknown, background) are packed per lane
+//     and stored as plain words per (tick, tile) (tile_lane.hpp's tile count) with three zeros behind them.  min_pixels <= 1: that is
 //     the whole stage -- no scratch, no further launch.
 //   blobs, on the classified maps (non-zero = kept), kBgBlobTicks ticks at a time to bound the scratch (a `parent` and a `size` int per
 //     pixel of that many ticks); an index is the pixel's position in its tick, frame offset + y w + x, so a frame's order is its raster order:
 //     1. bg_local_kernel: a tile is labelled inside LDS.  The pixels start as row runs (each kept pixel points at the first pixel of its
 //        run in the tile's row, found from the lanes' masks with a ballot), then one union per run of vertically adjacent kept pairs, by
-//        the lock-free union below on the LDS words; parent[p] = the index of the tile-local root (p itself where p is not kept),
+//        union_find.hpp's lock-free union on the LDS words; parent[p] = the index of the tile-local root (p itself where p is not kept),
 //        size[p] = 0 -- for the lanes that hold a kept pixel; the others' words are neither written nor ever read.
 //     2. bg_border_kernel: one lane per pixel of a tile's top row and left column joins it with its kept neighbour across the tile's edge
-//        (one union per run of kept pairs along the edge).
-//        This is fragments.hip's union (its header comment gives the reasons; bg_find / bg_unite restate fr_find / fr_unite): every hook is
-//        a returning atomicCAS that puts the HIGHER root under the LOWER, so parent[v] <= v always holds and a tree's root is its lowest
-//        index; the walks are plain loads, which may be old and still name a vertex of the right tree.
+//        (one union per run of kept pairs along the edge), by the same union on the global words: parent[v] <= v always holds and a
+//        tree's root is its lowest index.
 //     3. bg_size_kernel: the flatten and the sizes in ONE launch.  Every kept pixel walks to its root -- the forest no longer changes, a
 //        walk only falls in index, and a pixel's parent is its tile's root, so the walk is the chain of hooked roots alone -- and stores
 //        it over its own word (a concurrent walk through that word reads the old parent or the root: an ancestor either way).  A launch
@@ -41,12 +38,13 @@
 //        pixels go out as the (tick, tile)'s last three plain count words.
 // No kernel waits for another workgroup; every loop is bounded by a size the host passes or by an index that only falls.  Plain vector
 // stores and HIP atomics only.
+#include "union_find.hpp"
+
 namespace {
 
 constexpr int kBgAhead = 8;        // ticks whose loads a learning lane keeps in flight
 constexpr int kBgBlobTicks = 16;   // ticks the blob pass labels at a time: its scratch is 8 bytes per pixel of that many ticks
 constexpr int kBgTilePixels = kFlyW * kFlyH;
-static_assert(kFlyW == 128 && kFlyThreads * 8 == kBgTilePixels, "a tile-local index is lane * 8 + j = row * 128 + column");
 
 typedef unsigned short bg_u16x8 __attribute__((ext_vector_type(8)));
 
@@ -64,101 +62,22 @@ struct BgArgs {
     long long tick_stride;          // u16 elements
 };
 
-// A lane's 8 pixels at p, two a word; pixels beyond the row's end read as 0.
-template <bool VEC>
-__device__ __forceinline__ uint4 bg_load8(const unsigned short *p, int x, int w)
-{
-    if (VEC) return *reinterpret_cast<const uint4 *>(p);           // w % 8 == 0: a whole chunk
-    unsigned int e[8];
-#pragma unroll
-    for (int j = 0; j < 8; j++) e[j] = x + j < w ? p[j] : 0u;
-    return make_uint4(e[0] | (e[1] << 16), e[2] | (e[3] << 16), e[4] | (e[5] << 16), e[6] | (e[7] << 16));
-}
-
-template <bool VEC>
-__device__ __forceinline__ void bg_store8(unsigned short *p, int x, int w, const unsigned int (&o)[8])
-{
-    if (VEC) {
-        *reinterpret_cast<uint4 *>(p) = make_uint4(o[0] | (o[1] << 16), o[2] | (o[3] << 16), o[4] | (o[5] << 16), o[6] | (o[7] << 16));
-    } else {
-#pragma unroll
-        for (int j = 0; j < 8; j++)
-            if (x + j < w) p[j] = (unsigned short)o[j];
-    }
-}
-
-template <bool VEC>
-__device__ __forceinline__ void bg_load8i(const int *p, int x, int w, int (&v)[8])
-{
-    if (VEC) {
-        const int4 a = reinterpret_cast<const int4 *>(p)[0], b = reinterpret_cast<const int4 *>(p)[1];
-        v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w;
-        v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
-    } else {
-#pragma unroll
-        for (int j = 0; j < 8; j++) v[j] = x + j < w ? p[j] : 0;
-    }
-}
-
-template <bool VEC>
-__device__ __forceinline__ void bg_store8i(int *p, int x, int w, const int (&v)[8])
-{
-    if (VEC) {
-        reinterpret_cast<int4 *>(p)[0] = make_int4(v[0], v[1], v[2], v[3]);
-        reinterpret_cast<int4 *>(p)[1] = make_int4(v[4], v[5], v[6], v[7]);
-    } else {
-#pragma unroll
-        for (int j = 0; j < 8; j++)
-            if (x + j < w) p[j] = v[j];
-    }
-}
-
-__device__ __forceinline__ void bg_unpack(const uint4 v, unsigned int (&c)[8])
-{
-    const unsigned int d[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-    for (int j = 0; j < 8; j++) c[j] = (j & 1) ? d[j >> 1] >> 16 : d[j >> 1] & 0xFFFFu;
-}
-
-// What every kernel here knows of its lane: the tile, the frame, the lane's first pixel and whether it lies in the frame.
-struct BgLane {
-    int w, h, x, y;
-    bool live;
-    long long frame_off, pix;       // the frame's first pixel and the lane's, inside a tick
-};
-
-__device__ __forceinline__ BgLane bg_lane(const BgArgs &a, int tile, TileDesc &td)
-{
-    td = a.tiles[tile];
-    const FrameDesc fd = a.frames[td.frame];
-    BgLane l;
-    l.w = fd.w;
-    l.h = fd.h;
-    l.y = td.y0 + ((int)threadIdx.x >> 4);
-    l.x = td.x0 + ((int)threadIdx.x & 15) * 8;
-    l.live = l.y < l.h && l.x < l.w;
-    l.frame_off = fd.depth_off;
-    l.pix = l.live ? fd.depth_off + (long long)l.y * l.w + l.x : 0;
-    return l;
-}
-
 // ---- learn ----------------------------------------------------------------------------------------------------------------------------
 template <bool VEC>
 __global__ __launch_bounds__(kFlyThreads) void bg_learn_kernel(const BgArgs a)
 {
-    TileDesc td;
-    const BgLane l = bg_lane(a, blockIdx.x, td);
+    const TileLane l = tile_lane(a.frames, a.tiles[blockIdx.x]);
     if (!l.live) return;                                           // (no wave operation below)
     const int n = a.n_ticks;
     auto load = [&](int t) -> bg_u16x8 {
-        return __builtin_bit_cast(bg_u16x8, bg_load8<VEC>(a.in + (long long)t * a.tick_stride + l.pix, l.x, l.w));
+        return __builtin_bit_cast(bg_u16x8, load8<VEC>(a.in + (long long)t * a.tick_stride + l.pix, l.x, l.w));
     };
     bg_u16x8 ahead[kBgAhead];
 #pragma unroll
     for (int k = 0; k < kBgAhead; k++) ahead[k] = k < n ? load(k) : (bg_u16x8)(0);
     // lo - 1 mod 2^16: "none seen" (0) is the largest value and a missing sample (0) never lowers the minimum
     const bg_u16x8 one = (bg_u16x8)(1);
-    bg_u16x8 acc = __builtin_bit_cast(bg_u16x8, bg_load8<VEC>(a.model + l.pix, l.x, l.w)) - one;
+    bg_u16x8 acc = __builtin_bit_cast(bg_u16x8, load8<VEC>(a.model + l.pix, l.x, l.w)) - one;
     for (int base = 0; base < n; base += kBgAhead) {
 #pragma unroll
         for (int k = 0; k < kBgAhead; k++) {
@@ -170,25 +89,24 @@ __global__ __launch_bounds__(kFlyThreads) void bg_learn_kernel(const BgArgs a)
         }
     }
     unsigned int o[8];
-    bg_unpack(__builtin_bit_cast(uint4, (bg_u16x8)(acc + one)), o);
-    bg_store8<VEC>(a.model + l.pix, l.x, l.w, o);
+    unpack8(__builtin_bit_cast(uint4, (bg_u16x8)(acc + one)), o);
+    store8<VEC>(a.model + l.pix, l.x, l.w, o);
 }
 
 // ---- classify -------------------------------------------------------------------------------------------------------------------------
 template <bool VEC>
 __global__ __launch_bounds__(kFlyThreads) void bg_classify_kernel(const BgArgs a)
 {
-    __shared__ unsigned int s_cnt[kFlyThreads / 64][2];
+    __shared__ TileCount s_cnt;
     const int tid = threadIdx.x;
     const int tick = blockIdx.x / a.tiles_per_tick;
     const int tile = blockIdx.x - tick * a.tiles_per_tick;
-    TileDesc td;
-    const BgLane l = bg_lane(a, tile, td);
+    const TileLane l = tile_lane(a.frames, a.tiles[tile]);
     unsigned int lo_w = 0, hi_w = 0;                               // foreground | unknown << 16, background
     if (l.live) {
         unsigned int c[8], lo[8], o[8];
-        bg_unpack(bg_load8<VEC>(a.in + (long long)tick * a.tick_stride + l.pix, l.x, l.w), c);
-        bg_unpack(bg_load8<VEC>(a.model + l.pix, l.x, l.w), lo);
+        unpack8(load8<VEC>(a.in + (long long)tick * a.tick_stride + l.pix, l.x, l.w), c);
+        unpack8(load8<VEC>(a.model + l.pix, l.x, l.w), lo);
 #pragma unroll
         for (int j = 0; j < 8; j++) {
             const int thr = a.margin + (int)((lo[j] * (unsigned int)a.rel_q) >> 10);   // the product stays below 2^24
@@ -199,53 +117,13 @@ __global__ __launch_bounds__(kFlyThreads) void bg_classify_kernel(const BgArgs a
             lo_w += fore ? 1u : unknown ? 0x10000u : 0u;
             hi_w += (sample && !unknown && !fore) ? 1u : 0u;
         }
-        bg_store8<VEC>(a.out + (long long)tick * a.tick_stride + l.pix, l.x, l.w, o);
+        store8<VEC>(a.out + (long long)tick * a.tick_stride + l.pix, l.x, l.w, o);
     }
-    // a lane adds at most 8 to a field, a wave 512, the tile 2048: 16 bits hold it
-    lo_w = wave_sum(lo_w);
-    hi_w = wave_sum(hi_w);
-    if ((tid & 63) == 0) {
-        s_cnt[tid >> 6][0] = lo_w;
-        s_cnt[tid >> 6][1] = hi_w;
-    }
+    tile_count_put(s_cnt, lo_w, hi_w);
     __syncthreads();
     if (tid < 6) {
-        int total = 0;
-        if (tid < 3) {
-#pragma unroll
-            for (int wv = 0; wv < kFlyThreads / 64; wv++) {
-                const unsigned int word = s_cnt[wv][tid >> 1];
-                total += (int)(tid == 1 ? word >> 16 : word & 0xFFFFu);
-            }
-        }
+        const int total = tid < 3 ? tile_count_get(s_cnt, tid) : 0;
         a.counts[(long long)blockIdx.x * 6 + tid] = total;         // (the blob pass's three words start at 0)
-    }
-}
-
-// ---- blobs: the union (fragments.hip's fr_find / fr_unite restated; that file's header comment says why the plain loads are enough) -----
-// A vertex of x's tree that was a root when it was read.
-__device__ __forceinline__ int bg_find(const int *parent, int x)
-{
-    int p = parent[x];
-    while (p != x) {                                     // p < x: at most x rounds
-        x = p;
-        p = parent[x];
-    }
-    return x;
-}
-
-// Joins the trees of a and b; returns the root the union ended on (the lower one).
-__device__ __forceinline__ int bg_unite(int *parent, int a, int b)
-{
-    for (;;) {                                           // a + b falls with every failed round
-        a = bg_find(parent, a);
-        b = bg_find(parent, b);
-        if (a == b) return a;
-        const int hi = max(a, b), lo = min(a, b);
-        const int was = atomicCAS(&parent[hi], hi, lo);
-        if (was == hi) return lo;
-        a = was;                                         // < hi: hi had been hooked already
-        b = lo;
     }
 }
 
@@ -258,12 +136,12 @@ __global__ __launch_bounds__(kFlyThreads) void bg_local_kernel(const BgArgs a)
     const int tid = threadIdx.x;
     const int slot = blockIdx.x / a.tiles_per_tick;
     const int tile = blockIdx.x - slot * a.tiles_per_tick;
-    TileDesc td;
-    const BgLane l = bg_lane(a, tile, td);
+    const TileDesc td = a.tiles[tile];
+    const TileLane l = tile_lane(a.frames, td);
     unsigned int mask = 0;
     if (l.live) {
         unsigned int c[8];
-        bg_unpack(bg_load8<VEC>(a.out + (long long)(a.tick0 + slot) * a.tick_stride + l.pix, l.x, l.w), c);
+        unpack8(load8<VEC>(a.out + (long long)(a.tick0 + slot) * a.tick_stride + l.pix, l.x, l.w), c);
 #pragma unroll
         for (int j = 0; j < 8; j++) mask |= c[j] != 0 ? 1u << j : 0u;
     }
@@ -299,7 +177,7 @@ __global__ __launch_bounds__(kFlyThreads) void bg_local_kernel(const BgArgs a)
         while (heads) {                                            // at most 4 rounds
             const int j = __ffs((int)heads) - 1;
             heads &= heads - 1;
-            (void)bg_unite(s_par, tid * 8 + j, tid * 8 + j + kFlyW);
+            (void)uf_unite(s_par, tid * 8 + j, tid * 8 + j + kFlyW);
         }
     }
     __syncthreads();
@@ -307,14 +185,14 @@ __global__ __launch_bounds__(kFlyThreads) void bg_local_kernel(const BgArgs a)
     int par[8], zero[8];
 #pragma unroll
     for (int j = 0; j < 8; j++) {
-        const int r = bg_find(s_par, tid * 8 + j);                 // (a pixel that is not kept is its own root)
+        const int r = uf_find(s_par, tid * 8 + j);                 // (a pixel that is not kept is its own root)
         // the root's position in the tick: the tile's first pixel + its row and column inside the tile
         par[j] = (int)(l.frame_off + (long long)(td.y0 + (r >> 7)) * l.w + td.x0 + (r & (kFlyW - 1)));
         zero[j] = 0;
     }
     const long long at = (long long)slot * a.tick_stride + l.pix;
-    bg_store8i<VEC>(a.parent + at, l.x, l.w, par);
-    bg_store8i<VEC>(a.size + at, l.x, l.w, zero);
+    store8<VEC>(a.parent + at, l.x, l.w, par);
+    store8<VEC>(a.size + at, l.x, l.w, zero);
 }
 
 // ---- blobs 2: across the tiles' edges -------------------------------------------------------------------------------------------------
@@ -336,7 +214,7 @@ __global__ __launch_bounds__(kFlyThreads) void bg_border_kernel(const BgArgs a)
     // has joined it with this pair on either side of the edge
     const long long back = top ? 1 : fd.w;
     if ((top ? x > td.x0 : y > td.y0) && map[p - back] != 0 && map[q - back] != 0) return;
-    (void)bg_unite(a.parent + (long long)slot * a.tick_stride, (int)q, (int)p);
+    (void)uf_unite(a.parent + (long long)slot * a.tick_stride, (int)q, (int)p);
 }
 
 // ---- blobs 3: the labels and the sizes --------------------------------------------------------------------------------------------------
@@ -346,18 +224,17 @@ __global__ __launch_bounds__(kFlyThreads) void bg_size_kernel(const BgArgs a)
     const int lane = threadIdx.x & 63;
     const int slot = blockIdx.x / a.tiles_per_tick;
     const int tile = blockIdx.x - slot * a.tiles_per_tick;
-    TileDesc td;
-    const BgLane l = bg_lane(a, tile, td);
+    const TileLane l = tile_lane(a.frames, a.tiles[tile]);
     int *parent = a.parent + (long long)slot * a.tick_stride, *size = a.size + (long long)slot * a.tick_stride;
     int label = -1, n = 0;                                         // the lane's last run of equal labels (-1: no kept pixel)
     if (l.live) {
         unsigned int c[8];
         int par[8];
-        bg_unpack(bg_load8<VEC>(a.out + (long long)(a.tick0 + slot) * a.tick_stride + l.pix, l.x, l.w), c);
+        unpack8(load8<VEC>(a.out + (long long)(a.tick0 + slot) * a.tick_stride + l.pix, l.x, l.w), c);
         bool any = false;
 #pragma unroll
         for (int j = 0; j < 8; j++) any |= c[j] != 0;
-        if (any) bg_load8i<VEC>(parent + l.pix, l.x, l.w, par);   // (bg_local_kernel wrote the words of the lanes with a kept pixel)
+        if (any) load8<VEC>(parent + l.pix, l.x, l.w, par);   // (bg_local_kernel wrote the words of the lanes with a kept pixel)
         int from = -1;                                             // the parent the label was found from
 #pragma unroll
         for (int j = 0; j < 8; j++) {
@@ -365,7 +242,7 @@ __global__ __launch_bounds__(kFlyThreads) void bg_size_kernel(const BgArgs a)
             int lab = label;
             if (par[j] != from || label < 0) {
                 from = par[j];
-                lab = bg_find(parent, from);
+                lab = uf_find(parent, from);
             }
             par[j] = lab;
             if (lab != label) {
@@ -375,7 +252,7 @@ __global__ __launch_bounds__(kFlyThreads) void bg_size_kernel(const BgArgs a)
             }
             n++;
         }
-        if (any) bg_store8i<VEC>(parent + l.pix, l.x, l.w, par);
+        if (any) store8<VEC>(parent + l.pix, l.x, l.w, par);
     }
     // the lanes' last runs: one atomicAdd per run of lanes with equal labels
     const int incl = wave_scan_incl(n, lane);
@@ -392,24 +269,23 @@ __global__ __launch_bounds__(kFlyThreads) void bg_size_kernel(const BgArgs a)
 template <bool VEC>
 __global__ __launch_bounds__(kFlyThreads) void bg_apply_kernel(const BgArgs a)
 {
-    __shared__ unsigned int s_cnt[kFlyThreads / 64][2];
+    __shared__ TileCount s_cnt;
     const int tid = threadIdx.x;
     const int slot = blockIdx.x / a.tiles_per_tick;
     const int tile = blockIdx.x - slot * a.tiles_per_tick;
     const int tick = a.tick0 + slot;
-    TileDesc td;
-    const BgLane l = bg_lane(a, tile, td);
+    const TileLane l = tile_lane(a.frames, a.tiles[tile]);
     const int *parent = a.parent + (long long)slot * a.tick_stride, *size = a.size + (long long)slot * a.tick_stride;
     unsigned int lo_w = 0, hi_w = 0;                               // components | removed components << 16, removed pixels
     if (l.live) {
         unsigned int c[8];
         int par[8];
         unsigned short *map = a.out + (long long)tick * a.tick_stride + l.pix;
-        bg_unpack(bg_load8<VEC>(map, l.x, l.w), c);
+        unpack8(load8<VEC>(map, l.x, l.w), c);
         bool any = false;
 #pragma unroll
         for (int j = 0; j < 8; j++) any |= c[j] != 0;
-        if (any) bg_load8i<VEC>(parent + l.pix, l.x, l.w, par);
+        if (any) load8<VEC>(parent + l.pix, l.x, l.w, par);
         int label = -1;
         bool stays = false, changed = false;
 #pragma unroll
@@ -427,24 +303,11 @@ __global__ __launch_bounds__(kFlyThreads) void bg_apply_kernel(const BgArgs a)
                 changed = true;
             }
         }
-        if (changed) bg_store8<VEC>(map, l.x, l.w, c);             // (the classified map is in place already)
+        if (changed) store8<VEC>(map, l.x, l.w, c);             // (the classified map is in place already)
     }
-    lo_w = wave_sum(lo_w);
-    hi_w = wave_sum(hi_w);
-    if ((tid & 63) == 0) {
-        s_cnt[tid >> 6][0] = lo_w;
-        s_cnt[tid >> 6][1] = hi_w;
-    }
+    tile_count_put(s_cnt, lo_w, hi_w);
     __syncthreads();
-    if (tid < 3) {
-        int total = 0;
-#pragma unroll
-        for (int wv = 0; wv < kFlyThreads / 64; wv++) {
-            const unsigned int word = s_cnt[wv][tid >> 1];
-            total += (int)(tid == 1 ? word >> 16 : word & 0xFFFFu);
-        }
-        a.counts[((long long)tick * a.tiles_per_tick + tile) * 6 + 3 + tid] = total;
-    }
+    if (tid < 3) a.counts[((long long)tick * a.tiles_per_tick + tile) * 6 + 3 + tid] = tile_count_get(s_cnt, tid);
 }
 
 // what the learning pass and the stage share: the plan's tables, the maps, the model
@@ -489,16 +352,6 @@ int lsn::background_setting_ok(const char *who, int margin, int rel_q, int min_p
     return 0;
 }
 
-// A model of `pixels` values at "nothing learned", reserved on first use (grow-only: a larger one starts empty too).
-int lsn::background_model_reserve(lsn::DevBuf &model, size_t pixels, hipStream_t s)
-{
-    if (2 * pixels + 16 <= model.bytes && model.p) return 0;
-    if (model.reserve(2 * pixels + 16)) return -1;
-    LSN_HIP(hipMemsetAsync(model.p, 0, model.bytes, s));
-    LSN_HIP(hipStreamSynchronize(s));   // (once per buffer: whichever stream comes next finds the zeros)
-    return 0;
-}
-
 // The learning pass for the library's own flows (takes the plan's mutex): `n_ticks` ticks in the plan's frame layout folded into d_model.
 int lsn::background_learn(LsnFusion *p, const void *d_depth, unsigned short *d_model, int n_ticks, hipStream_t s)
 {
@@ -524,17 +377,8 @@ int lsn::background(LsnFusion *p, const BackgroundSetting &bs, const void *d_dep
                     lsn::DevBuf &counts, lsn::DevBuf &blob, int n_ticks, hipStream_t s)
 {
     std::lock_guard<std::mutex> g(p->mu);
-    LSN_HIP(hipSetDevice(p->device));
-    const size_t bytes = 2 * (size_t)p->cap * (size_t)n_ticks;
-    const uintptr_t x = (uintptr_t)d_depth_in, y = (uintptr_t)d_depth_out;
-    if (x != y && x < y + bytes && y < x + bytes) {
-        lsn::set_error("lsnFusionBackground: the output maps overlap the input maps (the pass runs in place or on disjoint buffers)");
-        return -1;
-    }
-    if (!bs.on()) {
-        if (x != y) LSN_HIP(hipMemcpyAsync(d_depth_out, d_depth_in, bytes, hipMemcpyDeviceToDevice, s));
-        return 0;
-    }
+    const int run = stage_preamble(p, "lsnFusionBackground", bs.on(), d_depth_in, d_depth_out, n_ticks, s);
+    if (run <= 0) return run;
     if (background_setting_ok("lsnFusionBackground", bs.margin, bs.rel_q, bs.min_pixels) || n_ticks < 1 || !d_model) {
         if (!lsn::has_error()) lsn::set_error("lsnFusionBackground: bad arguments");
         return -1;
@@ -570,28 +414,6 @@ int lsn::background(LsnFusion *p, const BackgroundSetting &bs, const void *d_dep
     return 0;
 }
 
-// The sums of the six counts of tick `tick` per frame of the plan (p->mu held or the plan otherwise quiet): counts as lsn::background left them.
-int lsn::background_counts(LsnFusion *p, const lsn::DevBuf &counts, int tick, int *per_frame6)
-{
-    std::vector<int> words(6 * (size_t)p->fl_tiles_per_tick);
-    LSN_HIP(hipMemcpy(words.data(), counts.as<int>() + words.size() * (size_t)tick, sizeof(int) * words.size(), hipMemcpyDeviceToHost));
-    for (int i = 0; i < 6 * p->n_maps; i++) per_frame6[i] = 0;
-    for (size_t t = 0; t < (size_t)p->fl_tiles_per_tick; t++)
-        for (int f = 0; f < 6; f++) per_frame6[6 * p->fl_tile_frame[t] + f] += words[6 * t + f];
-    return 0;
-}
-
-namespace {
-// The plan's model ready for a call on stream s (p->mu held): reserved if asked for, and handed over from the last call's stream.
-int bg_model(LsnFusion *p, bool reserve, hipStream_t s)
-{
-    LSN_HIP(hipSetDevice(p->device));
-    if (reserve && lsn::background_model_reserve(p->bg_model, (size_t)p->cap, s)) return -1;
-    if (p->bg_busy && p->bg_stream != s) LSN_HIP(hipStreamSynchronize(p->bg_stream));
-    return 0;
-}
-}  // namespace
-
 extern "C" int lsnFusionSetBackground(LsnFusion *p, int margin, int rel_q, int min_pixels)
 {
     return lsn::guarded("lsnFusionSetBackground", -1, [&]() {
@@ -618,13 +440,10 @@ extern "C" int lsnFusionBackgroundLearn(LsnFusion *p, const void *d_depth, void 
         hipStream_t s = lsn::as_stream(stream);
         {
             std::lock_guard<std::mutex> g(p->mu);
-            if (bg_model(p, true, s)) return -1;
+            LSN_HIP(hipSetDevice(p->device));
+            if (p->bg.reserve((size_t)p->cap, s) || p->bg.hand_over(s)) return -1;
         }
-        if (lsn::background_learn(p, d_depth, p->bg_model.as<unsigned short>(), p->n_ticks, s)) return -1;
-        std::lock_guard<std::mutex> g(p->mu);
-        p->bg_busy = true;
-        p->bg_stream = s;
-        return 0;
+        return lsn::background_learn(p, d_depth, p->bg.state.as<unsigned short>(), p->n_ticks, s);
     });
 }
 
@@ -641,16 +460,16 @@ extern "C" int lsnFusionBackground(LsnFusion *p, const void *d_depth_in, void *d
         {
             std::lock_guard<std::mutex> g(p->mu);
             bs = p->bg_setting;
-            // the first call with the stage on reserves the model (nothing learned: every sample is unknown and kept)
-            if (bs.on() && bg_model(p, true, s)) return -1;
+            // the first call with the stage on reserves the model (nothing learned: every sample is unknown and kept); a copy leaves the
+            // model and its stream as they are
+            if (bs.on()) {
+                LSN_HIP(hipSetDevice(p->device));
+                if (p->bg.reserve((size_t)p->cap, s) || p->bg.hand_over(s)) return -1;
+            }
         }
-        if (lsn::background(p, bs, d_depth_in, d_depth_out, p->bg_model.as<unsigned short>(), p->bg_counts, p->bg_blob, p->n_ticks, s)) return -1;
+        if (lsn::background(p, bs, d_depth_in, d_depth_out, p->bg.state.as<unsigned short>(), p->bg.counts, p->bg_blob, p->n_ticks, s)) return -1;
         std::lock_guard<std::mutex> g(p->mu);
         p->bg_last = bs.on() ? 2 : 1;
-        if (bs.on()) {   // (a copy leaves the model and its stream as they are)
-            p->bg_busy = true;
-            p->bg_stream = s;
-        }
         return 0;
     });
 }
@@ -664,13 +483,8 @@ extern "C" int lsnFusionBackgroundReset(LsnFusion *p, void *stream)
             return -1;
         }
         std::lock_guard<std::mutex> g(p->mu);
-        if (!p->bg_model.p) return 0;   // nothing learned yet
-        hipStream_t s = lsn::as_stream(stream);
-        if (bg_model(p, false, s)) return -1;
-        LSN_HIP(hipMemsetAsync(p->bg_model.p, 0, 2 * (size_t)p->cap, s));
-        p->bg_busy = true;
-        p->bg_stream = s;
-        return 0;
+        LSN_HIP(hipSetDevice(p->device));
+        return p->bg.reset((size_t)p->cap, lsn::as_stream(stream));
     });
 }
 
@@ -683,15 +497,8 @@ extern "C" int lsnFusionBackgroundModelRead(LsnFusion *p, unsigned short *h_mode
             return -1;
         }
         std::lock_guard<std::mutex> g(p->mu);
-        if (!p->bg_model.p) {   // nothing learned yet
-            std::fill(h_model, h_model + (size_t)p->cap, (unsigned short)0);
-            return 0;
-        }
-        hipStream_t s = lsn::as_stream(stream);
-        if (bg_model(p, false, s)) return -1;
-        LSN_HIP(hipMemcpyAsync(h_model, p->bg_model.p, 2 * (size_t)p->cap, hipMemcpyDeviceToHost, s));
-        LSN_HIP(hipStreamSynchronize(s));
-        return 0;
+        LSN_HIP(hipSetDevice(p->device));
+        return p->bg.read(h_model, (size_t)p->cap, lsn::as_stream(stream));
     });
 }
 
@@ -704,11 +511,8 @@ extern "C" int lsnFusionBackgroundModelWrite(LsnFusion *p, const unsigned short 
             return -1;
         }
         std::lock_guard<std::mutex> g(p->mu);
-        hipStream_t s = lsn::as_stream(stream);
-        if (bg_model(p, true, s)) return -1;
-        LSN_HIP(hipMemcpyAsync(p->bg_model.p, h_model, 2 * (size_t)p->cap, hipMemcpyHostToDevice, s));
-        LSN_HIP(hipStreamSynchronize(s));   // (the caller's array is free again on return)
-        return 0;
+        LSN_HIP(hipSetDevice(p->device));
+        return p->bg.write(h_model, (size_t)p->cap, lsn::as_stream(stream));
     });
 }
 
@@ -726,17 +530,7 @@ extern "C" int lsnFusionBackgroundDiagnostics(LsnFusion *p, int tick, int *foreg
             lsn::set_error("lsnFusionBackgroundDiagnostics: the plan has not run the stage");
             return -1;
         }
-        LSN_HIP(hipSetDevice(p->device));
-        std::vector<int> per(6 * (size_t)p->n_maps, 0);
-        if (p->bg_last == 2) {
-            LSN_HIP(hipStreamSynchronize(lsn::as_stream(stream)));
-            if (p->bg_stream != lsn::as_stream(stream)) LSN_HIP(hipStreamSynchronize(p->bg_stream));
-            if (lsn::background_counts(p, p->bg_counts, tick, per.data())) return -1;
-        }
         int *const dst[6] = {foreground, unknown, background, components, components_removed, pixels_removed};
-        for (int f = 0; f < p->n_maps; f++)
-            for (int k = 0; k < 6; k++)
-                if (dst[k]) dst[k][f] = per[6 * f + k];
-        return 0;
+        return stage_diagnostics(p, p->bg_last == 2, p->bg, tick, 6, dst, lsn::as_stream(stream));
     });
 }

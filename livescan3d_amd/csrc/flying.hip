@@ -257,11 +257,9 @@ extern "C" int lsnFusionFlyingDiagnostics(LsnFusion *p, int tick, int *removed_p
         LSN_HIP(hipSetDevice(p->device));
         std::vector<int> per(p->n_maps, 0);
         if (p->fl_last == 2) {
-            std::vector<int> counts((size_t)p->fl_tiles_per_tick);
             LSN_HIP(hipStreamSynchronize(lsn::as_stream(stream)));
             if (p->fl_stream != lsn::as_stream(stream)) LSN_HIP(hipStreamSynchronize(p->fl_stream));
-            LSN_HIP(hipMemcpy(counts.data(), p->fl_counts.as<int>() + (size_t)tick * p->fl_tiles_per_tick, sizeof(int) * counts.size(), hipMemcpyDeviceToHost));
-            for (size_t t = 0; t < counts.size(); t++) per[p->fl_tile_frame[t]] += counts[t];
+            if (lsn::stage_counts(p, p->fl_counts, tick, 1, per.data())) return -1;
         }
         long long total = 0;
         for (int f = 0; f < p->n_maps; f++) {

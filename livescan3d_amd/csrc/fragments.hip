@@ -9,25 +9,14 @@
 // Per call, over every tick of the batch (grid y = tick):
 //
 //   1. init (fr_init_kernel): parent[v] = v, size[v] = 0 for the tick's counted vertices.
-//   2. union (fr_union_kernel): one lane per triangle, two unions.  A union finds an ancestor of either end and hooks the HIGHER under
-//      the LOWER, so parent[v] <= v holds at every moment and a tree's root is its lowest index.  How parent[] is touched:
-//        - every hook is a returning atomicCAS(&parent[hi], hi, lo): it succeeds only while hi is still a root (a root is hooked once; a
-//          vertex that is no root never becomes one again).  When it fails it returns what parent[hi] holds, strictly below hi, and the
-//          lane goes on from there: the sum of the two indices a union holds falls with every failed round, so a union ends after at
-//          most i0 + i1 rounds and no lane ever waits for another;
-//        - the walks read parent[] with PLAIN loads.  Within a launch a plain load may be old (L1 is per CU, L2 per XCD), and the design
-//          is correct when every one of them is: an old value of parent[x] is x itself or an earlier parent, in both cases a vertex of
-//          x's own tree with an index <= x, so a walk always ends on a vertex of the right component; that it is (still) a root is
-//          decided by the CAS alone, which answers with the word as it is, and hooking under a vertex that has stopped being a root
-//          still joins the two trees and keeps parent[hi] < hi.  (Agent-scope atomic loads, which go past both caches, were measured:
-//          the call on the 8 x 512x424 scene tick took 2.7 ms with them against 2.0 ms -- fewer failed rounds do not pay for their
-//          latency);
-//        - paths are shortened inside the launch only by a no-return atomicMin(&parent[v], r) on the triangle's own three vertices, r
-//          the root the lane's last union ended on: r lies in v's tree and below v, so parent[v] <= v and "parent[v] is in v's tree"
-//          both survive, in any interleaving with the hooks (a hook writes only roots, and a vertex with a lower vertex in its tree is
-//          none).  Halving the path on every step of a walk, by atomicMin or by a store, was measured and is slower (1.2 - 2.0 ms
-//          for the call against 1.0 ms): the walks are a chain of dependent loads, and the extra traffic costs more than the shorter paths save.
-//      A walk goes down in index with every step: at most x steps from x.
+//   2. union (fr_union_kernel): one lane per triangle, two unions by union_find.hpp's lock-free union (its header says how parent[] is
+//      touched and why plain loads suffice): the HIGHER root is hooked under the LOWER, so parent[v] <= v holds at every moment and a
+//      tree's root is its lowest index.  Paths are shortened inside the launch only by a no-return atomicMin(&parent[v], r) on the
+//      triangle's own three vertices, r the root the lane's last union ended on: r lies in v's tree and below v, so parent[v] <= v and
+//      "parent[v] is in v's tree" both survive, in any interleaving with the hooks (a hook writes only roots, and a vertex with a lower
+//      vertex in its tree is none).  Halving the path on every step of a walk, by atomicMin or by a store, was measured and is slower
+//      (1.2 - 2.0 ms for the call against 1.0 ms): the walks are a chain of dependent loads, and the extra traffic costs more than the
+//      shorter paths save.
 //   3. flatten (fr_jump_kernel), ceil(log2(vertices per tick)) launches: parent[v] = parent[parent[v]], one step per lane per launch, plain
 //      loads and one plain store of the lane's own word.  A launch sees at least what the launch before wrote; what it sees of its own
 //      launch is an ancestor further up.  Every hop of the new forest covers two hops of the old one (or ends on the root), so a launch
@@ -48,6 +37,7 @@
 // HIP atomics only.  Compiled as part of mesh.hip's translation unit (after cloud_index.hip and mesh_batch.hip: ct_block_scan_kernel, the
 // batch), behind simplify.hip.
 #include "fusion_shared.hpp"
+#include "union_find.hpp"
 
 namespace {
 
@@ -68,32 +58,6 @@ struct FrArgs {
     int n, identity, nvb, ntb, min_vertices;
     long long tick_vert, tick_tri;
 };
-
-// A vertex of x's tree that was a root when it was read (plain loads: the file's header says why they may be old).
-__device__ __forceinline__ int fr_find(const int *parent, int x)
-{
-    int p = parent[x];
-    while (p != x) {                                     // p < x: at most x rounds
-        x = p;
-        p = parent[x];
-    }
-    return x;
-}
-
-// Joins the trees of a and b; returns the root the union ended on (the lower one).
-__device__ __forceinline__ int fr_unite(int *parent, int a, int b)
-{
-    for (;;) {                                           // a + b falls with every failed round
-        a = fr_find(parent, a);
-        b = fr_find(parent, b);
-        if (a == b) return a;
-        const int hi = max(a, b), lo = min(a, b);
-        const int was = atomicCAS(&parent[hi], hi, lo);
-        if (was == hi) return lo;
-        a = was;                                         // < hi: hi had been hooked already
-        b = lo;
-    }
-}
 
 // ---- 1. init ------------------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(kFrThreads) void fr_init_kernel(FrArgs a)
@@ -117,7 +81,7 @@ __global__ __launch_bounds__(kFrThreads) void fr_union_kernel(FrArgs a)
     const int i0 = tr[0], i1 = tr[1], i2 = tr[2];
     if (!((unsigned int)i0 < (unsigned int)nv && (unsigned int)i1 < (unsigned int)nv && (unsigned int)i2 < (unsigned int)nv)) return;
     int *parent = a.parent + tick * a.tick_vert;
-    const int r = fr_unite(parent, fr_unite(parent, i0, i1), i2);   // (the first union's root stands for i1: one walk less)
+    const int r = uf_unite(parent, uf_unite(parent, i0, i1), i2);   // (the first union's root stands for i1: one walk less)
     if (r < i0) atomicMin(&parent[i0], r);                          // no return; r lies in the three vertices' tree, below them
     if (r < i1) atomicMin(&parent[i1], r);
     if (r < i2) atomicMin(&parent[i2], r);

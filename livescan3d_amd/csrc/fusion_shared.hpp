@@ -613,19 +613,17 @@ struct LsnFusion {
     lsn::DevBuf ds_table, ds_counts;
     int ds_last = 0;                     // what the last call was: 0 = none yet, 1 = a copy (off), 2 = the filter
     hipStream_t ds_stream = nullptr;     // ... and its stream
-    // temporal depth filter (temporal.hip): the setting of lsnFusionSetTemporal (off by default) and, allocated by the first filtering call
-    // (or lsnFusionTemporalStateWrite), the history -- one word per pixel of one tick -- and four words per 128 x 16 tile of every tick
+    // the two stages with state (lsn::StageState, lsn_common.hpp), each with its setting (off by default), its record -- allocated by the
+    // first call that needs it -- and what its last call was: 0 = none yet, 1 = a copy (off), 2 = the stage.  The temporal depth filter
+    // (temporal.hip): the history, one word per pixel of one tick, four count words per 128 x 16 tile of every tick.  Background
+    // subtraction (background.hip): the model, one u16 per pixel of one tick, six count words, and the blob pass's scratch.
     lsn::TemporalSetting tp_setting;
-    lsn::DevBuf tp_state, tp_counts;
-    int tp_last = 0;                     // what the last call was: 0 = none yet, 1 = a copy (off), 2 = the filter
-    hipStream_t tp_stream = nullptr;     // ... and its stream
-    // background subtraction (background.hip): the setting of lsnFusionSetBackground (off by default) and, allocated by the first call that
-    // needs them, the model -- one u16 per pixel of one tick --, six words per 128 x 16 tile of every tick and the blob pass's scratch
+    lsn::StageState tp{4, 0};
+    int tp_last = 0;
     lsn::BackgroundSetting bg_setting;
-    lsn::DevBuf bg_model, bg_counts, bg_blob;
-    int bg_last = 0;                     // what the last lsnFusionBackground was: 0 = none yet, 1 = a copy (off), 2 = the stage
-    bool bg_busy = false;                // a call has touched the model on ...
-    hipStream_t bg_stream = nullptr;     // ... this stream (the model is handed from call to call)
+    lsn::StageState bg{2, 16};
+    lsn::DevBuf bg_blob;
+    int bg_last = 0;
     // the three stages on the merged mesh (render.hip, simplify.hip, normals.hip): each one's scratch, allocated on its first call
     lsn::RenderScratch rv;
     lsn::SimplifyScratch sp;

@@ -61,57 +61,51 @@ struct DepthStages {
     bool smooth_on() const { return smooth != nullptr && lsn::smooth_on(smooth->radius); }
 };
 
-// A lane's side of those stages: each stage's output, laid out like the lane's d_depth, which the next stage or the correction reads; the
-// temporal filter's history of the rig the lane sees call after call, one word per pixel at the sensor's offset in the call's arrays (so
-// neither grouping nor the host path changes which word a pixel owns), keyed by the rig (sensor count, widths, heights) and the reset
-// generation; the branch counts of its last launch.  Background subtraction's model lives the same way, one u16 per pixel, keyed by the rig
-// and lsnLearnBackground's generation, with the learning calls the lane still owes, the blob pass's scratch and the stage's counts.  All
+// A lane's side of those stages: each stage's output, laid out like the lane's d_depth, which the next stage or the correction reads; and
+// for the two stages with state their record (lsn::StageState) for the rig the lane sees call after call -- the temporal filter's history,
+// one word per pixel at the sensor's offset in the call's arrays (so neither grouping nor the host path changes which word a pixel owns),
+// and background subtraction's model, one u16 per pixel -- keyed by the rig (sensor count, widths, heights) and the generation of
+// lsnResetTemporalFilter / lsnLearnBackground; for the model also the learning calls the lane still owes, and the blob pass's scratch.  All
 // allocated by the first call that runs the stage.
 struct DepthChain {
-    lsn::DevBuf d_temporal, d_background, d_flying, d_smooth, tp_state, tp_counts, bg_model, bg_blob, bg_counts;
-    std::vector<int> tp_rig, bg_rig;
-    unsigned long long tp_gen = 0, bg_gen = 0;
+    lsn::DevBuf d_temporal, d_background, d_flying, d_smooth, bg_blob;
+    struct Keyed {
+        lsn::StageState st;
+        std::vector<int> rig;
+        unsigned long long gen = 0;
+        Keyed(size_t px_bytes, size_t pad) : st(px_bytes, pad) {}
+    };
+    Keyed tp{4, 0}, bg{2, 16};
     int bg_learn_left = 0;           // learning calls still to come
     bool bg_learning = false;        // ... and whether the call in progress is one (decided once per call, in reserve())
-    // the model up to date for a call of this rig and generation: zeroed, with `learn_calls` learning calls ahead, when either changed
-    int model(const int *widths, const int *heights, int count, unsigned long long gen, int learn_calls, hipStream_t s)
+    // the state up to date for a call of this rig and generation: zeroed when either changed (`fresh`)
+    static int keyed(Keyed &k, const std::vector<int> &rig, size_t pixels, unsigned long long gen, hipStream_t s, bool &fresh)
     {
-        std::vector<int> rig(1, count);
-        rig.insert(rig.end(), widths, widths + count);
-        rig.insert(rig.end(), heights, heights + count);
-        size_t pixels = 0;
-        for (int i = 0; i < count; i++) pixels += (size_t)widths[i] * heights[i];
-        if (bg_model.p && rig == bg_rig && gen == bg_gen) return 0;
-        const bool grown = !bg_model.p || bg_model.bytes < 2 * pixels + 16;
-        if (lsn::background_model_reserve(bg_model, pixels, s)) return -1;   // (a new buffer comes zeroed)
-        if (!grown) LSN_HIP(hipMemsetAsync(bg_model.p, 0, 2 * pixels, s));
-        bg_rig.swap(rig);
-        bg_gen = gen;
-        bg_learn_left = learn_calls;
-        return 0;
-    }
-    // the history up to date for a call of this rig and generation: zeroed when either changed
-    int history(const int *widths, const int *heights, int count, unsigned long long gen, hipStream_t s)
-    {
-        std::vector<int> rig(1, count);
-        rig.insert(rig.end(), widths, widths + count);
-        rig.insert(rig.end(), heights, heights + count);
-        size_t pixels = 0;
-        for (int i = 0; i < count; i++) pixels += (size_t)widths[i] * heights[i];
-        if (tp_state.p && rig == tp_rig && gen == tp_gen) return 0;
-        const bool grown = !tp_state.p || tp_state.bytes < 4 * pixels;
-        if (lsn::temporal_state_reserve(tp_state, pixels, s)) return -1;   // (a new buffer comes zeroed)
-        if (!grown) LSN_HIP(hipMemsetAsync(tp_state.p, 0, 4 * pixels, s));
-        tp_rig.swap(rig);
-        tp_gen = gen;
+        fresh = !(k.st.state.p && rig == k.rig && gen == k.gen);
+        if (!fresh) return 0;
+        const bool grown = !k.st.state.p || k.st.state.bytes < k.st.px_bytes * pixels + k.st.pad;
+        if (k.st.reserve(pixels, s)) return -1;   // (a new buffer comes zeroed)
+        if (!grown && k.st.reset(pixels, s)) return -1;
+        k.rig = rig;
+        k.gen = gen;
         return 0;
     }
     // What the stages that are on need for a call whose depth block has `dbytes` bytes and whose sensors are widths / heights [0, count).
     int reserve(const DepthStages &st, size_t dbytes, const int *widths, const int *heights, int count, hipStream_t s)
     {
-        if (st.temporal_on() && (d_temporal.reserve(dbytes + 16) || history(widths, heights, count, st.temporal_gen, s))) return -1;
+        std::vector<int> rig;
+        size_t pixels = 0;
+        if (st.temporal_on() || st.background_on()) {
+            rig.assign(1, count);
+            rig.insert(rig.end(), widths, widths + count);
+            rig.insert(rig.end(), heights, heights + count);
+            for (int i = 0; i < count; i++) pixels += (size_t)widths[i] * heights[i];
+        }
+        bool fresh = false;
+        if (st.temporal_on() && (d_temporal.reserve(dbytes + 16) || keyed(tp, rig, pixels, st.temporal_gen, s, fresh))) return -1;
         if (st.background_on()) {   // a call is one tick and counts once, whichever groups the host path cuts it into
-            if (d_background.reserve(dbytes + 16) || model(widths, heights, count, st.background_gen, st.background_learn, s)) return -1;
+            if (d_background.reserve(dbytes + 16) || keyed(bg, rig, pixels, st.background_gen, s, fresh)) return -1;
+            if (fresh) bg_learn_left = st.background_learn;   // a new model has that many learning calls ahead
             bg_learning = bg_learn_left > 0;
             if (bg_learning) bg_learn_left--;
         }
@@ -127,16 +121,16 @@ struct DepthChain {
         const char *in = d_depth.as<char>() + off;
         if (st.temporal_on()) {
             char *out = d_temporal.as<char>() + off;
-            if (lsn::temporal(plan, st.temporal, in, out, tp_state.as<unsigned int>() + off / 2, tp_counts, 1, s)) return nullptr;
+            if (lsn::temporal(plan, st.temporal, in, out, tp.st.state.as<unsigned int>() + off / 2, tp.st.counts, 1, s)) return nullptr;
             in = out;
         }
         if (st.background_on()) {   // a learning call folds its maps into the model and passes them on as they are
-            unsigned short *model = bg_model.as<unsigned short>() + off / 2;
+            unsigned short *model = bg.st.state.as<unsigned short>() + off / 2;
             char *out = d_background.as<char>() + off;
             if (bg_learning) {
                 if (lsn::background_learn(plan, in, model, 1, s)) return nullptr;
             } else {
-                if (lsn::background(plan, st.background, in, out, model, bg_counts, bg_blob, 1, s)) return nullptr;
+                if (lsn::background(plan, st.background, in, out, model, bg.st.counts, bg_blob, 1, s)) return nullptr;
                 in = out;
             }
         }

@@ -97,6 +97,62 @@ struct DevBuf {
 
 inline hipStream_t as_stream(void *s) { return static_cast<hipStream_t>(s); }
 
+// What a stage keeps that carries per-pixel state from call to call (the temporal filter's history, temporal.hip: 4 bytes a pixel, no pad;
+// background subtraction's model, background.hip: 2 bytes a pixel and 16 behind them): the state of ONE tick's pixels, the count words of
+// the last call, and the stream that touched the state last.  One rule for every owner (a plan, a tick object, a lane of the host
+// exports): whatever touches the state first calls hand_over(s), which waits for the previous stream's work when that is another one and
+// records `s`.  The owner holds the lock that guards the record and has made its device current.
+struct StageState {
+    const size_t px_bytes, pad;
+    DevBuf state, counts;
+    hipStream_t stream = nullptr;    // the stream that touched the state last ...
+    bool busy = false;               // ... once something has
+    StageState(size_t bytes_per_pixel, size_t tail_pad) : px_bytes(bytes_per_pixel), pad(tail_pad) {}
+    // room for `pixels`, all zero ("no history" / "nothing learned") on first use and when it grows (grow-only: a larger one starts empty too)
+    int reserve(size_t pixels, hipStream_t s)
+    {
+        if (px_bytes * pixels + pad <= state.bytes && state.p) return 0;
+        if (state.reserve(px_bytes * pixels + pad)) return -1;
+        LSN_HIP(hipMemsetAsync(state.p, 0, state.bytes, s));
+        LSN_HIP(hipStreamSynchronize(s));   // (once per buffer: whichever stream comes next finds the zeros)
+        return 0;
+    }
+    int hand_over(hipStream_t s)
+    {
+        if (busy && stream != s) LSN_HIP(hipStreamSynchronize(stream));
+        stream = s;
+        busy = true;
+        return 0;
+    }
+    // back to all zero, queued on `s`; nothing reserved yet: nothing to do
+    int reset(size_t pixels, hipStream_t s)
+    {
+        if (!state.p) return 0;
+        if (hand_over(s)) return -1;
+        LSN_HIP(hipMemsetAsync(state.p, 0, px_bytes * pixels, s));
+        return 0;
+    }
+    // the state of `pixels` pixels into / from a host array, complete on return; nothing reserved yet reads as zeros, a write reserves
+    int read(void *host, size_t pixels, hipStream_t s)
+    {
+        if (!state.p) {
+            memset(host, 0, px_bytes * pixels);
+            return 0;
+        }
+        if (hand_over(s)) return -1;
+        LSN_HIP(hipMemcpyAsync(host, state.p, px_bytes * pixels, hipMemcpyDeviceToHost, s));
+        LSN_HIP(hipStreamSynchronize(s));
+        return 0;
+    }
+    int write(const void *host, size_t pixels, hipStream_t s)
+    {
+        if (reserve(pixels, s) || hand_over(s)) return -1;
+        LSN_HIP(hipMemcpyAsync(state.p, host, px_bytes * pixels, hipMemcpyHostToDevice, s));
+        LSN_HIP(hipStreamSynchronize(s));   // (the caller's array is free again on return)
+        return 0;
+    }
+};
+
 // lsnFusionRun on a stream, for the library's own flows (takes the plan's mutex; leaves the error text as it is unless it fails).
 int run_vertices(LsnFusion *p, const void *d_depth, const void *d_colors, void *d_vertices, int *d_offsets, hipStream_t s);
 // The same with the mutex already held; with_pixmap also fills the pixel -> vertex map the triangulation reads, which the caller has
@@ -159,10 +215,8 @@ struct TemporalSetting {
 };
 int temporal_setting_ok(const char *who, int alpha_q, int delta, int persist);
 int temporal_state_ok(const char *who, const unsigned int *h_state, size_t pixels);
-int temporal_state_reserve(DevBuf &state, size_t pixels, hipStream_t s);
 int temporal(LsnFusion *p, const TemporalSetting &ts, const void *d_depth_in, void *d_depth_out, unsigned int *d_state, DevBuf &counts, int n_ticks,
              hipStream_t s);
-int temporal_counts(LsnFusion *p, const DevBuf &counts, int tick, int *per_frame4);
 
 // Background subtraction (background.hip), the stage between the temporal filter and the flying-pixel filter.  One setting as the plans, the
 // tick and the process-wide switch hold it (margin <= 0: off; min_pixels <= 1: no blob pass).  background_learn and background are
@@ -175,11 +229,16 @@ struct BackgroundSetting {
     bool blobs() const { return min_pixels >= 2; }
 };
 int background_setting_ok(const char *who, int margin, int rel_q, int min_pixels);
-int background_model_reserve(DevBuf &model, size_t pixels, hipStream_t s);
 int background_learn(LsnFusion *p, const void *d_depth, unsigned short *d_model, int n_ticks, hipStream_t s);
 int background(LsnFusion *p, const BackgroundSetting &bs, const void *d_depth_in, void *d_depth_out, const unsigned short *d_model, DevBuf &counts,
                DevBuf &blob, int n_ticks, hipStream_t s);
-int background_counts(LsnFusion *p, const DevBuf &counts, int tick, int *per_frame6);
+
+// What the two stages' calls open with (the caller holds the plan's mutex): the plan's device, the rule "in place or on disjoint buffers"
+// with the stage's export `who` in the message, and a stage that is off, which copies.  1: the stage runs; 0: off, the call is done; -1: refused.
+int stage_preamble(LsnFusion *p, const char *who, bool on, const void *d_depth_in, void *d_depth_out, int n_ticks, hipStream_t s);
+// The count words of tick `tick`, `n_fields` plain words per 128 x 16 tile as a stage's kernels left them in `counts`, summed per frame of
+// the plan into per_frame[n_maps][n_fields] (p->mu held or the plan otherwise quiet).
+int stage_counts(LsnFusion *p, const DevBuf &counts, int tick, int n_fields, int *per_frame);
 
 // What "on" means for the two stages behind it, for everybody who chains them in front of the correction (the host exports' DepthStages,
 // host_ctx.hpp; the tick object, tick.hip): a neighbourhood / a radius of at least one pixel; 0 and below mean off.  The temporal filter's is

@@ -1331,7 +1331,9 @@ extern "C" int lsnFusionRadialCorrectTo(LsnFusion *p, const float *intr_params, 
 #include "flying.hip"
 // ... and so is depth smoothing, the stage between the two (it shares the filter's tile list).
 #include "depth_smooth.hip"
-// ... and the temporal depth filter, the stage in front of all three (it shares the tile list too).
+// ... and the temporal depth filter, the stage in front of all three (it shares the tile list too), behind the 8-pixel lane and the packed
+// tile count that it and background subtraction share.
+#include "tile_lane.hpp"
 #include "temporal.hip"
 // ... and background subtraction, the stage between the temporal filter and the flying-pixel filter (the same tile list).
 #include "background.hip"

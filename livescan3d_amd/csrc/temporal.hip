@@ -12,13 +12,13 @@
 //   expire / empty  c == 0 otherwise:                   the word becomes 0, out = 0
 // Everything is an integer in 32 bits (the blend's product stays below 2^29); the pass is pointwise, so it may run in place.
 //
-// Shape: one launch per call, whatever its ticks.  One workgroup of 256 lanes takes one 128 x 16 tile of flying.hip's list, one lane 8
-// consecutive pixels of a row; the lane loads its 8 state words, walks the call's ticks in order with the state in registers and stores
+// Shape: one launch per call, whatever its ticks.  One workgroup takes one 128 x 16 tile of flying.hip's list with tile_lane.hpp's lane (8
+// consecutive pixels of a row); the lane loads its 8 state words, walks the call's ticks in order with the state in registers and stores
 // the state once at the end: 4 B per pixel and tick, 8 B per pixel and call.  The grid is only tiles_per_tick workgroups, so the tick loop
 // hides the latency itself: the samples do not depend on the state, and each lane keeps the loads of kTempAhead ticks in flight ahead of
 // the arithmetic (8 x 16 B x 256 lanes = 32 KiB per workgroup).  No LDS staging of pixels, no atomics: the branch counts of a tick
-// (blended, restarted with history, filled, expired) are packed into two words per lane, summed per wave, and go out as four plain words
-// per (tick, tile) once per kTempAhead ticks; lsnFusionTemporalDiagnostics adds them up per sensor on the host.
+// (blended, restarted with history, filled, expired) are tile_lane.hpp's packed tile count, four plain words per (tick, tile) once per
+// kTempAhead ticks.  The history, its count words and the stream hand-over are a lsn::StageState (lsn_common.hpp) in whoever owns them.
 namespace {
 
 constexpr int kTempAhead = 8;   // ticks whose loads a lane keeps in flight
@@ -56,31 +56,15 @@ __device__ __forceinline__ unsigned int temporal_pixel(unsigned int c, unsigned 
 template <bool VEC>
 __global__ __launch_bounds__(kFlyThreads) void temporal_kernel(const TemporalArgs a)
 {
-    __shared__ unsigned int s_cnt[2][kTempAhead][kFlyThreads / 64][2];
+    __shared__ TileCount s_cnt[2][kTempAhead];
     const int tid = threadIdx.x;
-    const TileDesc td = a.tiles[blockIdx.x];
-    const FrameDesc fd = a.frames[td.frame];
-    const int w = fd.w, h = fd.h;
-    const int ry = tid >> 4, cx = tid & 15;
-    const int y = td.y0 + ry, x = td.x0 + cx * 8;
-    const bool live = y < h && x < w;                          // (a lane outside the frame walks the loop for the wave sums and touches no memory)
-    const long long pix = live ? fd.depth_off + (long long)y * w + x : 0;
+    const TileLane l = tile_lane(a.frames, a.tiles[blockIdx.x]);   // (a lane outside the frame walks the loop for the wave sums and touches no memory)
     const int n = a.n_ticks;
 
-    // the lane's chunk of tick t, packed two pixels a word; pixels beyond the row's end read as 0 and are never stored
+    // the lane's chunk of tick t
     auto load = [&](int t) -> uint4 {
         uint4 v = make_uint4(0, 0, 0, 0);
-        if (live) {
-            const unsigned short *p = a.in + (long long)t * a.tick_stride + pix;
-            if (VEC) {
-                v = *reinterpret_cast<const uint4 *>(p);       // w % 8 == 0: a whole chunk
-            } else {
-                unsigned int e[8];
-#pragma unroll
-                for (int j = 0; j < 8; j++) e[j] = x + j < w ? p[j] : 0u;
-                v = make_uint4(e[0] | (e[1] << 16), e[2] | (e[3] << 16), e[4] | (e[5] << 16), e[6] | (e[7] << 16));
-            }
-        }
+        if (l.live) load8<VEC>(v, a.in + (long long)t * a.tick_stride + l.pix, l.x, l.w);
         return v;
     };
 
@@ -91,17 +75,7 @@ __global__ __launch_bounds__(kFlyThreads) void temporal_kernel(const TemporalArg
     unsigned int st[8];
 #pragma unroll
     for (int j = 0; j < 8; j++) st[j] = 0;
-    if (live) {
-        const unsigned int *sp = a.state + pix;
-        if (VEC) {
-            const uint4 s0 = reinterpret_cast<const uint4 *>(sp)[0], s1 = reinterpret_cast<const uint4 *>(sp)[1];
-            st[0] = s0.x; st[1] = s0.y; st[2] = s0.z; st[3] = s0.w;
-            st[4] = s1.x; st[5] = s1.y; st[6] = s1.z; st[7] = s1.w;
-        } else {
-#pragma unroll
-            for (int j = 0; j < 8; j++) st[j] = x + j < w ? sp[j] : 0u;
-        }
-    }
+    if (l.live) load8<VEC>(a.state + l.pix, l.x, l.w, st);
 
     int par = 0;
     for (int base = 0; base < n; base += kTempAhead, par ^= 1) {
@@ -111,58 +85,22 @@ __global__ __launch_bounds__(kFlyThreads) void temporal_kernel(const TemporalArg
             if (t >= n) break;                                 // uniform
             const uint4 cur = ahead[k];
             if (t + kTempAhead < n) ahead[k] = load(t + kTempAhead);
-            const unsigned int cd[4] = {cur.x, cur.y, cur.z, cur.w};
-            unsigned int o[8], lo = 0, hi = 0;
+            unsigned int c[8], o[8], lo = 0, hi = 0;
+            unpack8(cur, c);
 #pragma unroll
-            for (int j = 0; j < 8; j++) {
-                const unsigned int c = (j & 1) ? cd[j >> 1] >> 16 : cd[j >> 1] & 0xFFFFu;
-                o[j] = temporal_pixel(c, st[j], a.alpha_q, a.gate, a.persist, lo, hi);
-            }
-            if (live) {
-                unsigned short *dp = a.out + (long long)t * a.tick_stride + pix;
-                if (VEC) {
-                    *reinterpret_cast<uint4 *>(dp) = make_uint4(o[0] | (o[1] << 16), o[2] | (o[3] << 16), o[4] | (o[5] << 16), o[6] | (o[7] << 16));
-                } else {
-#pragma unroll
-                    for (int j = 0; j < 8; j++)
-                        if (x + j < w) dp[j] = (unsigned short)o[j];
-                }
-            }
-            // a lane adds at most 8 to a field, a wave 512, the tile 2048: 16 bits hold it
-            lo = wave_sum(lo);
-            hi = wave_sum(hi);
-            if ((tid & 63) == 0) {
-                s_cnt[par][k][tid >> 6][0] = lo;
-                s_cnt[par][k][tid >> 6][1] = hi;
-            }
+            for (int j = 0; j < 8; j++) o[j] = temporal_pixel(c[j], st[j], a.alpha_q, a.gate, a.persist, lo, hi);
+            if (l.live) store8<VEC>(a.out + (long long)t * a.tick_stride + l.pix, l.x, l.w, o);
+            tile_count_put(s_cnt[par][k], lo, hi);
         }
         // these ticks' four words per tile: one barrier per kTempAhead ticks (the other half of s_cnt is the next round's)
         __syncthreads();
         if (tid < kTempAhead * 4) {
             const int k = tid >> 2, f = tid & 3, t = base + k;
-            if (t < n) {
-                int total = 0;
-#pragma unroll
-                for (int wv = 0; wv < kFlyThreads / 64; wv++) {
-                    const unsigned int word = s_cnt[par][k][wv][f >> 1];
-                    total += (int)((f & 1) ? word >> 16 : word & 0xFFFFu);
-                }
-                a.counts[((long long)t * a.tiles_per_tick + blockIdx.x) * 4 + f] = total;
-            }
+            if (t < n) a.counts[((long long)t * a.tiles_per_tick + blockIdx.x) * 4 + f] = tile_count_get(s_cnt[par][k], f);
         }
     }
 
-    if (live) {
-        unsigned int *sp = a.state + pix;
-        if (VEC) {
-            reinterpret_cast<uint4 *>(sp)[0] = make_uint4(st[0], st[1], st[2], st[3]);
-            reinterpret_cast<uint4 *>(sp)[1] = make_uint4(st[4], st[5], st[6], st[7]);
-        } else {
-#pragma unroll
-            for (int j = 0; j < 8; j++)
-                if (x + j < w) sp[j] = st[j];
-        }
-    }
+    if (l.live) store8<VEC>(a.state + l.pix, l.x, l.w, st);
 }
 
 }  // namespace
@@ -199,17 +137,8 @@ int lsn::temporal(LsnFusion *p, const TemporalSetting &ts, const void *d_depth_i
                   int n_ticks, hipStream_t s)
 {
     std::lock_guard<std::mutex> g(p->mu);
-    LSN_HIP(hipSetDevice(p->device));
-    const size_t bytes = 2 * (size_t)p->cap * (size_t)n_ticks;
-    const uintptr_t x = (uintptr_t)d_depth_in, y = (uintptr_t)d_depth_out;
-    if (x != y && x < y + bytes && y < x + bytes) {
-        lsn::set_error("lsnFusionTemporal: the output maps overlap the input maps (the pass runs in place or on disjoint buffers)");
-        return -1;
-    }
-    if (!ts.on()) {
-        if (x != y) LSN_HIP(hipMemcpyAsync(d_depth_out, d_depth_in, bytes, hipMemcpyDeviceToDevice, s));
-        return 0;
-    }
+    const int run = stage_preamble(p, "lsnFusionTemporal", ts.on(), d_depth_in, d_depth_out, n_ticks, s);
+    if (run <= 0) return run;
     if (temporal_setting_ok("lsnFusionTemporal", ts.alpha_q, ts.delta, ts.persist) || n_ticks < 1 || !d_state) {
         if (!lsn::has_error()) lsn::set_error("lsnFusionTemporal: bad arguments");
         return -1;
@@ -228,31 +157,11 @@ int lsn::temporal(LsnFusion *p, const TemporalSetting &ts, const void *d_depth_i
     a.gate = 256 * ts.delta;
     a.persist = ts.persist;
     a.tick_stride = p->tick_depth_elems;
+    const uintptr_t x = (uintptr_t)d_depth_in, y = (uintptr_t)d_depth_out;
     const bool vec = p->vec_ok && (x & 15) == 0 && (y & 15) == 0 && ((uintptr_t)d_state & 15) == 0 && (p->tick_depth_elems % 8) == 0;
     if (vec) hipLaunchKernelGGL((temporal_kernel<true>), dim3((unsigned)p->fl_tiles_per_tick), dim3(kFlyThreads), 0, s, a);
     else hipLaunchKernelGGL((temporal_kernel<false>), dim3((unsigned)p->fl_tiles_per_tick), dim3(kFlyThreads), 0, s, a);
     LSN_HIP(hipGetLastError());
-    return 0;
-}
-
-// A history of `pixels` words at no history, reserved on first use (grow-only: a larger one starts empty too).
-int lsn::temporal_state_reserve(lsn::DevBuf &state, size_t pixels, hipStream_t s)
-{
-    if (4 * pixels <= state.bytes && state.p) return 0;
-    if (state.reserve(4 * pixels)) return -1;
-    LSN_HIP(hipMemsetAsync(state.p, 0, state.bytes, s));
-    LSN_HIP(hipStreamSynchronize(s));   // (once per buffer: whichever stream comes next finds the zeros)
-    return 0;
-}
-
-// The sums of the four counts of tick `tick` per frame of the plan (p->mu held or the plan otherwise quiet): counts as lsn::temporal left them.
-int lsn::temporal_counts(LsnFusion *p, const lsn::DevBuf &counts, int tick, int *per_frame4)
-{
-    std::vector<int> words(4 * (size_t)p->fl_tiles_per_tick);
-    LSN_HIP(hipMemcpy(words.data(), counts.as<int>() + words.size() * (size_t)tick, sizeof(int) * words.size(), hipMemcpyDeviceToHost));
-    for (int i = 0; i < 4 * p->n_maps; i++) per_frame4[i] = 0;
-    for (size_t t = 0; t < (size_t)p->fl_tiles_per_tick; t++)
-        for (int f = 0; f < 4; f++) per_frame4[4 * p->fl_tile_frame[t] + f] += words[4 * t + f];
     return 0;
 }
 
@@ -285,15 +194,13 @@ extern "C" int lsnFusionTemporal(LsnFusion *p, const void *d_depth_in, void *d_d
             std::lock_guard<std::mutex> g(p->mu);
             LSN_HIP(hipSetDevice(p->device));
             ts = p->tp_setting;
-            // the first filtering call reserves the history; a plan that never filters allocates nothing
-            if (ts.on() && lsn::temporal_state_reserve(p->tp_state, (size_t)p->cap, s)) return -1;
-            // a call on another stream than the last one's starts behind it: the history is handed from call to call
-            if (ts.on() && p->tp_last == 2 && p->tp_stream != s) LSN_HIP(hipStreamSynchronize(p->tp_stream));
+            // the first filtering call reserves the history (a plan that never filters allocates nothing); a call on another stream than the
+            // last one's starts behind it
+            if (ts.on() && (p->tp.reserve((size_t)p->cap, s) || p->tp.hand_over(s))) return -1;
         }
-        if (lsn::temporal(p, ts, d_depth_in, d_depth_out, p->tp_state.as<unsigned int>(), p->tp_counts, p->n_ticks, s)) return -1;
+        if (lsn::temporal(p, ts, d_depth_in, d_depth_out, p->tp.state.as<unsigned int>(), p->tp.counts, p->n_ticks, s)) return -1;
         std::lock_guard<std::mutex> g(p->mu);
         p->tp_last = ts.on() ? 2 : 1;
-        p->tp_stream = s;
         return 0;
     });
 }
@@ -307,12 +214,8 @@ extern "C" int lsnFusionTemporalReset(LsnFusion *p, void *stream)
             return -1;
         }
         std::lock_guard<std::mutex> g(p->mu);
-        if (!p->tp_state.p) return 0;   // no history yet
         LSN_HIP(hipSetDevice(p->device));
-        hipStream_t s = lsn::as_stream(stream);
-        if (p->tp_last == 2 && p->tp_stream != s) LSN_HIP(hipStreamSynchronize(p->tp_stream));
-        LSN_HIP(hipMemsetAsync(p->tp_state.p, 0, 4 * (size_t)p->cap, s));
-        return 0;
+        return p->tp.reset((size_t)p->cap, lsn::as_stream(stream));
     });
 }
 
@@ -325,16 +228,8 @@ extern "C" int lsnFusionTemporalStateRead(LsnFusion *p, unsigned int *h_state, v
             return -1;
         }
         std::lock_guard<std::mutex> g(p->mu);
-        if (!p->tp_state.p) {   // no history yet
-            std::fill(h_state, h_state + (size_t)p->cap, 0u);
-            return 0;
-        }
         LSN_HIP(hipSetDevice(p->device));
-        hipStream_t s = lsn::as_stream(stream);
-        if (p->tp_last == 2 && p->tp_stream != s) LSN_HIP(hipStreamSynchronize(p->tp_stream));
-        LSN_HIP(hipMemcpyAsync(h_state, p->tp_state.p, 4 * (size_t)p->cap, hipMemcpyDeviceToHost, s));
-        LSN_HIP(hipStreamSynchronize(s));
-        return 0;
+        return p->tp.read(h_state, (size_t)p->cap, lsn::as_stream(stream));
     });
 }
 
@@ -349,12 +244,7 @@ extern "C" int lsnFusionTemporalStateWrite(LsnFusion *p, const unsigned int *h_s
         if (lsn::temporal_state_ok("lsnFusionTemporalStateWrite", h_state, (size_t)p->cap)) return -1;   // refused: the history stays
         std::lock_guard<std::mutex> g(p->mu);
         LSN_HIP(hipSetDevice(p->device));
-        hipStream_t s = lsn::as_stream(stream);
-        if (lsn::temporal_state_reserve(p->tp_state, (size_t)p->cap, s)) return -1;
-        if (p->tp_last == 2 && p->tp_stream != s) LSN_HIP(hipStreamSynchronize(p->tp_stream));
-        LSN_HIP(hipMemcpyAsync(p->tp_state.p, h_state, 4 * (size_t)p->cap, hipMemcpyHostToDevice, s));
-        LSN_HIP(hipStreamSynchronize(s));   // (the caller's array is free again on return)
-        return 0;
+        return p->tp.write(h_state, (size_t)p->cap, lsn::as_stream(stream));
     });
 }
 
@@ -371,19 +261,7 @@ extern "C" int lsnFusionTemporalDiagnostics(LsnFusion *p, int tick, int *blended
             lsn::set_error("lsnFusionTemporalDiagnostics: the plan has not run the filter");
             return -1;
         }
-        LSN_HIP(hipSetDevice(p->device));
-        std::vector<int> per(4 * (size_t)p->n_maps, 0);
-        if (p->tp_last == 2) {
-            LSN_HIP(hipStreamSynchronize(lsn::as_stream(stream)));
-            if (p->tp_stream != lsn::as_stream(stream)) LSN_HIP(hipStreamSynchronize(p->tp_stream));
-            if (lsn::temporal_counts(p, p->tp_counts, tick, per.data())) return -1;
-        }
-        for (int f = 0; f < p->n_maps; f++) {
-            if (blended) blended[f] = per[4 * f];
-            if (restarted) restarted[f] = per[4 * f + 1];
-            if (filled) filled[f] = per[4 * f + 2];
-            if (expired) expired[f] = per[4 * f + 3];
-        }
-        return 0;
+        int *const dst[4] = {blended, restarted, filled, expired};
+        return stage_diagnostics(p, p->tp_last == 2, p->tp, tick, 4, dst, lsn::as_stream(stream));
     });
 }

@@ -25,16 +25,15 @@ struct LsnTick {
     lsn::DevBuf d_filtered;              // ... and its output, [n_ticks][pixels per tick] u16: reserved by the first run that filters
     int ds_radius = 0;                   // depth smoothing between the filter and the correction (lsnTickSetDepthSmooth; <= 0: off; the plans hold the tables)
     lsn::DevBuf d_smoothed;              // ... and its output, laid out like d_filtered: reserved by the first run that smooths
-    lsn::TemporalSetting tp;             // the temporal depth filter in front of all of them (lsnTickSetTemporal; off by default)
-    lsn::DevBuf tp_state, tp_counts;     // ... its history (one word per pixel of one tick) and branch counts,
-    lsn::DevBuf d_temporal;              // ... and its output, laid out like d_filtered: all reserved by the first run that filters
-    hipStream_t tp_stream = nullptr;     // the stream of the last run that filtered (the history is handed from run to run)
-    bool tp_ran = false;
-    lsn::BackgroundSetting bg;           // background subtraction behind the temporal filter (lsnTickSetBackground; off by default)
-    lsn::DevBuf bg_model, bg_counts, bg_blob;   // ... its model (one u16 per pixel of one tick), counts and blob scratch,
-    lsn::DevBuf d_background;            // ... and its output, laid out like d_filtered: each reserved by the first run that needs it
-    hipStream_t bg_stream = nullptr;     // the stream of the last run that touched the model (it is handed from run to run)
-    bool bg_ran = false;
+    // the two stages with state in front of all of them, each with its setting (lsnTickSetTemporal, lsnTickSetBackground; off by default),
+    // its record (lsn::StageState: the history, one word per pixel of one tick, and the model, one u16; handed from run to run) and its
+    // output, laid out like d_filtered -- all reserved by the first run that needs them: the temporal depth filter, then background subtraction
+    lsn::TemporalSetting tp_setting;
+    lsn::StageState tp{4, 0};
+    lsn::DevBuf d_temporal;
+    lsn::BackgroundSetting bg_setting;
+    lsn::StageState bg{2, 16};
+    lsn::DevBuf bg_blob, d_background;
     hipStream_t side = nullptr;
     hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_band = nullptr;
     std::mutex mu;
@@ -169,7 +168,7 @@ extern "C" int lsnTickSetTemporal(LsnTick *t, int alpha_q, int delta, int persis
         }
         if (lsn::temporal_setting_ok("lsnTickSetTemporal", alpha_q, delta, persist)) return -1;   // refused: the previous setting stays
         std::lock_guard<std::mutex> g(t->mu);
-        t->tp = alpha_q >= 1 ? lsn::TemporalSetting{alpha_q, delta, persist} : lsn::TemporalSetting{};
+        t->tp_setting = alpha_q >= 1 ? lsn::TemporalSetting{alpha_q, delta, persist} : lsn::TemporalSetting{};
         return 0;
     });
 }
@@ -183,12 +182,8 @@ extern "C" int lsnTickTemporalReset(LsnTick *t, void *stream)
             return -1;
         }
         std::lock_guard<std::mutex> g(t->mu);
-        if (!t->tp_state.p) return 0;   // no history yet
         LSN_HIP(hipSetDevice(t->device));
-        hipStream_t s = lsn::as_stream(stream);
-        if (t->tp_ran && t->tp_stream != s) LSN_HIP(hipStreamSynchronize(t->tp_stream));
-        LSN_HIP(hipMemsetAsync(t->tp_state.p, 0, 4 * (size_t)t->cap, s));
-        return 0;
+        return t->tp.reset((size_t)t->cap, lsn::as_stream(stream));
     });
 }
 
@@ -202,7 +197,7 @@ extern "C" int lsnTickSetBackground(LsnTick *t, int margin, int rel_q, int min_p
         }
         if (lsn::background_setting_ok("lsnTickSetBackground", margin, rel_q, min_pixels)) return -1;   // refused: the previous setting stays
         std::lock_guard<std::mutex> g(t->mu);
-        t->bg = margin >= 1 ? lsn::BackgroundSetting{margin, rel_q, min_pixels} : lsn::BackgroundSetting{};
+        t->bg_setting = margin >= 1 ? lsn::BackgroundSetting{margin, rel_q, min_pixels} : lsn::BackgroundSetting{};
         return 0;
     });
 }
@@ -211,25 +206,12 @@ extern "C" int lsnTickSetBackground(LsnTick *t, int margin, int rel_q, int min_p
 // tile tables serving all ticks and one history seeing them in order; d_depth_in becomes its output.  Off: nothing.
 static int tick_temporal(LsnTick *t, const void *&d_depth_in, hipStream_t s)
 {
-    if (!t->tp.on()) return 0;
-    if (t->d_temporal.reserve(2 * (size_t)t->cap * t->n_ticks + 16) || lsn::temporal_state_reserve(t->tp_state, (size_t)t->cap, s)) return -1;
-    if (t->tp_ran && t->tp_stream != s) LSN_HIP(hipStreamSynchronize(t->tp_stream));
+    if (!t->tp_setting.on()) return 0;
+    if (t->d_temporal.reserve(2 * (size_t)t->cap * t->n_ticks + 16) || t->tp.reserve((size_t)t->cap, s) || t->tp.hand_over(s)) return -1;
     for (int k = 0; k < t->parts; k++)
         if (t->plan[k]->rd.wait_for_chain(s)) return -1;
-    if (lsn::temporal(t->plan[0], t->tp, d_depth_in, t->d_temporal.p, t->tp_state.as<unsigned int>(), t->tp_counts, t->n_ticks, s)) return -1;
-    t->tp_stream = s;
-    t->tp_ran = true;
+    if (lsn::temporal(t->plan[0], t->tp_setting, d_depth_in, t->d_temporal.p, t->tp.state.as<unsigned int>(), t->tp.counts, t->n_ticks, s)) return -1;
     d_depth_in = t->d_temporal.p;
-    return 0;
-}
-
-// The tick's model ready for a call on stream s (t->mu held): reserved if asked for, handed over from the last call's stream.
-static int tick_model(LsnTick *t, bool reserve, hipStream_t s)
-{
-    if (reserve && lsn::background_model_reserve(t->bg_model, (size_t)t->cap, s)) return -1;
-    if (t->bg_ran && t->bg_stream != s) LSN_HIP(hipStreamSynchronize(t->bg_stream));
-    t->bg_stream = s;
-    t->bg_ran = true;
     return 0;
 }
 
@@ -245,8 +227,8 @@ extern "C" int lsnTickBackgroundLearn(LsnTick *t, const void *d_depth_in, void *
         LSN_HIP(hipSetDevice(t->device));
         hipStream_t s = lsn::as_stream(stream);
         // the stage learns what it will classify: the temporal stage's output when that is set
-        if (tick_temporal(t, d_depth_in, s) || tick_model(t, true, s)) return -1;
-        return lsn::background_learn(t->plan[0], d_depth_in, t->bg_model.as<unsigned short>(), t->n_ticks, s);
+        if (tick_temporal(t, d_depth_in, s) || t->bg.reserve((size_t)t->cap, s) || t->bg.hand_over(s)) return -1;
+        return lsn::background_learn(t->plan[0], d_depth_in, t->bg.state.as<unsigned short>(), t->n_ticks, s);
     });
 }
 
@@ -259,12 +241,8 @@ extern "C" int lsnTickBackgroundReset(LsnTick *t, void *stream)
             return -1;
         }
         std::lock_guard<std::mutex> g(t->mu);
-        if (!t->bg_model.p) return 0;   // nothing learned yet
         LSN_HIP(hipSetDevice(t->device));
-        hipStream_t s = lsn::as_stream(stream);
-        if (tick_model(t, false, s)) return -1;
-        LSN_HIP(hipMemsetAsync(t->bg_model.p, 0, 2 * (size_t)t->cap, s));
-        return 0;
+        return t->bg.reset((size_t)t->cap, lsn::as_stream(stream));
     });
 }
 
@@ -293,11 +271,11 @@ extern "C" int lsnTickRun(LsnTick *t, const void *d_depth_in, const void *d_colo
         // at their own offsets.  (The scratch follows d_filtered's rule below: a run on another stream waits for the previous run's chains.)
         if (tick_temporal(t, d_depth_in, s)) return -1;
         // background subtraction follows right behind it under the same rules, from the temporal pass's output into scratch of its own
-        if (t->bg.on()) {
-            if (t->d_background.reserve(2 * (size_t)t->cap * t->n_ticks + 16) || tick_model(t, true, s)) return -1;
+        if (t->bg_setting.on()) {
+            if (t->d_background.reserve(2 * (size_t)t->cap * t->n_ticks + 16) || t->bg.reserve((size_t)t->cap, s) || t->bg.hand_over(s)) return -1;
             for (int k = 0; k < t->parts; k++)
                 if (t->plan[k]->rd.wait_for_chain(s)) return -1;
-            if (lsn::background(t->plan[0], t->bg, d_depth_in, t->d_background.p, t->bg_model.as<unsigned short>(), t->bg_counts, t->bg_blob, t->n_ticks, s)) return -1;
+            if (lsn::background(t->plan[0], t->bg_setting, d_depth_in, t->d_background.p, t->bg.state.as<unsigned short>(), t->bg.counts, t->bg_blob, t->n_ticks, s)) return -1;
             d_depth_in = t->d_background.p;
         }
         // part k's slices of the caller's arrays: [tick][pixels], [tick][pixels][3], [tick][capacity] vertices, [tick][n_maps + 1], ...

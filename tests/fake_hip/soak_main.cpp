@@ -5,7 +5,9 @@
 //      single-sensor calls + ICP, plus the radial export and all six last-mesh formats), every result checked against what the runtime
 //      double's kernels "compute" (every non-zero depth pixel survives, one triangle per vertex);
 //   3. the setters of two process-wide switches from four threads at once: every "previous" value handed back is one that was stored;
-//   4. the pool of pinned mesh blocks must be empty at the end.
+//   4. the device-resident forms of the two depth stages with state (temporal filter, background subtraction) on a plan and on a tick
+//      object: set, learn, run, reset, state / model read and write, diagnostics, on two streams, the tick object from two threads;
+//   5. the pool of pinned mesh blocks must be empty at the end.
 // $LSN_HOST_DEVICES (read by the library) switches the merge calls to the sharded flow; $LSN_TEST_FAIL_ALLOC / $LSN_TEST_THROW make
 // single calls fail, which must leave empty meshes and still an empty pool.  Exit code 0 = all checks held (the sanitizer adds its own).
 #include "../../include/NativeUtils.h"
@@ -584,11 +586,171 @@ void fusion_forms(int T, const int *w, const int *h)
     lsnFusionDestroy(p);
 }
 
+// The device-resident forms of the two stages with state (temporal.hip, background.hip) on the double: each export once with NULL
+// arguments; then on a plan and on a tick object set, learn, run, reset, state / model read and write and diagnostics, on two streams, the
+// tick object from two threads at once.  The stages' kernels are launch stubs there, so a state that was written reads back as it was and
+// every count is 0: what is checked is what the host side reserves, copies and hands over from stream to stream, and that a call a fault
+// hook hits fails with -1 and leaves everything usable.
+void stateful_stages()
+{
+    auto refused = [](int rc, const char *what) { CHECK(rc == -1, "%s: returned %d", what, rc); };
+    auto works = [](int rc, const char *what) {
+        char why[256] = "";
+        if (rc) (void)lsnGetLastError(why, sizeof(why));
+        CHECK(g_faults || rc == 0, "%s: %s", what, why);
+        return rc == 0;
+    };
+    unsigned int word = 0;
+    unsigned short value = 0;
+    int cnt = 0;
+    refused(lsnFusionSetTemporal(nullptr, 64, 20, 2), "lsnFusionSetTemporal(null)");
+    refused(lsnFusionTemporal(nullptr, nullptr, nullptr, nullptr), "lsnFusionTemporal(null)");
+    refused(lsnFusionTemporalReset(nullptr, nullptr), "lsnFusionTemporalReset(null)");
+    refused(lsnFusionTemporalStateRead(nullptr, &word, nullptr), "lsnFusionTemporalStateRead(null)");
+    refused(lsnFusionTemporalStateWrite(nullptr, &word, nullptr), "lsnFusionTemporalStateWrite(null)");
+    refused(lsnFusionTemporalDiagnostics(nullptr, 0, &cnt, &cnt, &cnt, &cnt, nullptr), "lsnFusionTemporalDiagnostics(null)");
+    refused(lsnFusionSetBackground(nullptr, 40, 8, 64), "lsnFusionSetBackground(null)");
+    refused(lsnFusionBackgroundLearn(nullptr, nullptr, nullptr), "lsnFusionBackgroundLearn(null)");
+    refused(lsnFusionBackground(nullptr, nullptr, nullptr, nullptr), "lsnFusionBackground(null)");
+    refused(lsnFusionBackgroundReset(nullptr, nullptr), "lsnFusionBackgroundReset(null)");
+    refused(lsnFusionBackgroundModelRead(nullptr, &value, nullptr), "lsnFusionBackgroundModelRead(null)");
+    refused(lsnFusionBackgroundModelWrite(nullptr, &value, nullptr), "lsnFusionBackgroundModelWrite(null)");
+    refused(lsnFusionBackgroundDiagnostics(nullptr, 0, &cnt, &cnt, &cnt, &cnt, &cnt, &cnt, nullptr), "lsnFusionBackgroundDiagnostics(null)");
+    refused(lsnTickSetTemporal(nullptr, 64, 20, 2), "lsnTickSetTemporal(null)");
+    refused(lsnTickTemporalReset(nullptr, nullptr), "lsnTickTemporalReset(null)");
+    refused(lsnTickSetBackground(nullptr, 40, 8, 64), "lsnTickSetBackground(null)");
+    refused(lsnTickBackgroundLearn(nullptr, nullptr, nullptr), "lsnTickBackgroundLearn(null)");
+    refused(lsnTickBackgroundReset(nullptr, nullptr), "lsnTickBackgroundReset(null)");
+
+    const int n = 2, w[2] = {136, 128}, h[2] = {40, 16};   // a tile edge in x and in y, one width that is no multiple of 128
+    void *s1 = lsnStreamCreate(0), *s2 = lsnStreamCreate(0);
+    CHECK(g_faults || (s1 && s2), "lsnStreamCreate");
+    // ---- a plan ----
+    const int T = 3;
+    LsnFusion *p = s1 && s2 ? lsnFusionCreate(0, T, n, w, h) : nullptr;
+    CHECK(g_faults || p != nullptr, "stateful stages: lsnFusionCreate");
+    if (p) {
+        const long long cap = lsnFusionTickCapacity(p);
+        void *d_in = nullptr, *d_out = nullptr;
+        const bool bufs = fakeDevMalloc(&d_in, 2 * cap * T + 16) == 0 && fakeDevMalloc(&d_out, 2 * cap * T) == 0;
+        CHECK(g_faults || bufs, "stateful stages: device buffers");
+        std::vector<unsigned int> st((size_t)cap), st2((size_t)cap, 7u);
+        std::vector<unsigned short> md((size_t)cap), md2((size_t)cap, 7);
+        std::vector<int> c(6 * n, -1);
+        auto counts_zero = [&](int fields, const char *what) {
+            for (int i = 0; i < fields * n; i++) CHECK(c[i] == 0, "%s: count %d is %d", what, i, c[i]);
+        };
+        for (size_t i = 0; i < st.size(); i++) st[i] = i % 5 == 0 ? 0u : (unsigned int)(256 * (500 + i % 3000)) | (unsigned int)(i % 3) << 24;
+        for (size_t i = 0; i < md.size(); i++) md[i] = (unsigned short)(i % 7 == 0 ? 0 : 400 + i % 5000);
+        // the temporal filter
+        if (!g_faults) refused(lsnFusionTemporalDiagnostics(p, 0, c.data(), c.data() + n, c.data() + 2 * n, c.data() + 3 * n, s1), "lsnFusionTemporalDiagnostics before a call");
+        if (works(lsnFusionTemporalStateRead(p, st2.data(), s1), "lsnFusionTemporalStateRead before a history"))
+            for (unsigned int v : st2) CHECK(v == 0, "no history read as %u", v);
+        works(lsnFusionTemporalReset(p, s2), "lsnFusionTemporalReset before a history");
+        refused(lsnFusionSetTemporal(p, 300, 20, 2), "lsnFusionSetTemporal(300)");
+        works(lsnFusionSetTemporal(p, 64, 20, 2), "lsnFusionSetTemporal");
+        if (bufs) {
+            works(lsnFusionTemporal(p, d_in, d_out, s1), "lsnFusionTemporal");
+            works(lsnFusionTemporal(p, d_in, d_in, s2), "lsnFusionTemporal in place, on the other stream");
+            refused(lsnFusionTemporal(p, d_in, static_cast<char *>(d_in) + 16, s1), "lsnFusionTemporal on overlapping maps");
+            if (works(lsnFusionTemporalDiagnostics(p, T - 1, c.data(), c.data() + n, c.data() + 2 * n, c.data() + 3 * n, s1), "lsnFusionTemporalDiagnostics"))
+                counts_zero(4, "lsnFusionTemporalDiagnostics");
+        }
+        st2[3] = 5u << 24;   // a miss count without history
+        refused(lsnFusionTemporalStateWrite(p, st2.data(), s2), "lsnFusionTemporalStateWrite of a word that is no state");
+        if (works(lsnFusionTemporalStateWrite(p, st.data(), s2), "lsnFusionTemporalStateWrite") &&
+            works(lsnFusionTemporalStateRead(p, st2.data(), s1), "lsnFusionTemporalStateRead"))
+            CHECK(st2 == st, "the history read back differs from what was written");
+        if (works(lsnFusionTemporalReset(p, s2), "lsnFusionTemporalReset") && bufs && works(lsnFusionTemporal(p, d_in, d_out, s1), "lsnFusionTemporal behind a reset") &&
+            works(lsnFusionTemporalStateRead(p, st2.data(), nullptr), "lsnFusionTemporalStateRead behind a reset"))
+            for (unsigned int v : st2) CHECK(v == 0, "a reset history read as %u", v);
+        works(lsnFusionSetTemporal(p, 0, 0, 0), "lsnFusionSetTemporal(off)");
+        if (bufs && works(lsnFusionTemporal(p, d_in, d_out, s1), "lsnFusionTemporal, off") &&
+            works(lsnFusionTemporalDiagnostics(p, 0, c.data(), nullptr, nullptr, c.data() + 3 * n, s2), "lsnFusionTemporalDiagnostics behind a copy"))
+            CHECK(c[0] == 0 && c[3 * n] == 0, "lsnFusionTemporalDiagnostics behind a copy");
+        // background subtraction
+        if (!g_faults) refused(lsnFusionBackgroundDiagnostics(p, 0, c.data(), nullptr, nullptr, nullptr, nullptr, nullptr, s1), "lsnFusionBackgroundDiagnostics before a call");
+        if (works(lsnFusionBackgroundModelRead(p, md2.data(), s1), "lsnFusionBackgroundModelRead before a model"))
+            for (unsigned short v : md2) CHECK(v == 0, "no model read as %u", v);
+        works(lsnFusionBackgroundReset(p, s2), "lsnFusionBackgroundReset before a model");
+        refused(lsnFusionSetBackground(p, 5000, 0, 0), "lsnFusionSetBackground(5000)");
+        works(lsnFusionSetBackground(p, 40, 8, 64), "lsnFusionSetBackground");
+        if (bufs) {
+            works(lsnFusionBackgroundLearn(p, d_in, s1), "lsnFusionBackgroundLearn");
+            works(lsnFusionBackground(p, d_in, d_out, s2), "lsnFusionBackground, on the other stream");
+            works(lsnFusionBackground(p, d_in, d_in, s1), "lsnFusionBackground in place");
+            refused(lsnFusionBackground(p, d_in, static_cast<char *>(d_in) + 16, s1), "lsnFusionBackground on overlapping maps");
+            if (works(lsnFusionBackgroundDiagnostics(p, T - 1, c.data(), c.data() + n, c.data() + 2 * n, c.data() + 3 * n, c.data() + 4 * n, c.data() + 5 * n, s2),
+                      "lsnFusionBackgroundDiagnostics"))
+                counts_zero(6, "lsnFusionBackgroundDiagnostics");
+        }
+        if (works(lsnFusionBackgroundModelWrite(p, md.data(), s2), "lsnFusionBackgroundModelWrite") &&
+            works(lsnFusionBackgroundModelRead(p, md2.data(), s1), "lsnFusionBackgroundModelRead"))
+            CHECK(md2 == md, "the model read back differs from what was written");
+        if (works(lsnFusionBackgroundReset(p, s2), "lsnFusionBackgroundReset") && bufs && works(lsnFusionBackground(p, d_in, d_out, s1), "lsnFusionBackground behind a reset") &&
+            works(lsnFusionBackgroundModelRead(p, md2.data(), nullptr), "lsnFusionBackgroundModelRead behind a reset"))
+            for (unsigned short v : md2) CHECK(v == 0, "a reset model read as %u", v);
+        works(lsnFusionSetBackground(p, 0, 0, 0), "lsnFusionSetBackground(off)");
+        if (bufs) works(lsnFusionBackground(p, d_in, d_out, s1), "lsnFusionBackground, off");
+        (void)fakeDevFree(d_in);
+        (void)fakeDevFree(d_out);
+        lsnFusionDestroy(p);
+    }
+    // ---- a tick object, two threads, each on its own stream ----
+    const int TT = 9;
+    LsnTick *tk = s1 && s2 ? lsnTickCreate(0, TT, n, w, h) : nullptr;
+    CHECK(g_faults || tk != nullptr, "stateful stages: lsnTickCreate");
+    if (tk) {
+        const long long cap = lsnTickCapacity(tk), tcap = lsnTickTriangleCapacity(tk);
+        float intr[14], wt[24], bounds[6] = {-2, -2, -2, 2, 2, 2};
+        for (int i = 0; i < n; i++) {
+            const float k[7] = {w[i] / 2.0f, h[i] / 2.0f, 365.0f * w[i] / 512.0f, 365.0f * w[i] / 512.0f, 0.09f, -0.05f, 0.01f};
+            memcpy(intr + 7 * i, k, sizeof(k));
+            const float q[12] = {0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0, 1};
+            memcpy(wt + 12 * i, q, sizeof(q));
+        }
+        void *d_in = nullptr, *c_in = nullptr, *d_co = nullptr, *c_co = nullptr, *v = nullptr, *tr = nullptr;
+        int *o = nullptr, *to = nullptr;
+        const bool bufs = fakeDevMalloc(&d_in, 2 * cap * TT) == 0 && fakeDevMalloc(&c_in, 3 * cap * TT) == 0 && fakeDevMalloc(&d_co, 2 * cap * TT) == 0 &&
+                          fakeDevMalloc(&c_co, 3 * cap * TT) == 0 && fakeDevMalloc(&v, 16 * cap * TT) == 0 && fakeDevMalloc(&tr, 12 * tcap * TT) == 0 &&
+                          fakeDevMalloc((void **)&o, sizeof(int) * (n + 1) * TT) == 0 && fakeDevMalloc((void **)&to, sizeof(int) * (n + 1) * TT) == 0;
+        CHECK(g_faults || bufs, "stateful stages: device buffers for the tick object");
+        const bool set = works(lsnTickSetParams(tk, intr, wt, bounds, nullptr), "lsnTickSetParams");
+        refused(lsnTickSetTemporal(tk, 64, 5000, 2), "lsnTickSetTemporal(delta 5000)");
+        refused(lsnTickSetBackground(tk, 40, 300, 64), "lsnTickSetBackground(rel_q 300)");
+        works(lsnTickTemporalReset(tk, s1), "lsnTickTemporalReset before a history");
+        works(lsnTickBackgroundReset(tk, s2), "lsnTickBackgroundReset before a model");
+        works(lsnTickSetTemporal(tk, 64, 20, 2), "lsnTickSetTemporal");
+        works(lsnTickSetBackground(tk, 40, 8, 64), "lsnTickSetBackground");
+        if (bufs && set) {
+            auto worker = [&](void *s) {   // (the tick object's lock orders the calls; the runs write the shared outputs under it)
+                for (int rep = 0; rep < 3; rep++) {
+                    works(lsnTickBackgroundLearn(tk, d_in, s), "lsnTickBackgroundLearn");
+                    works(lsnTickRun(tk, d_in, c_in, d_co, c_co, v, o, tr, to, s), "lsnTickRun with both stages");
+                    works(lsnTickTemporalReset(tk, s), "lsnTickTemporalReset");
+                    works(lsnTickBackgroundReset(tk, s), "lsnTickBackgroundReset");
+                    works(lsnTickRun(tk, d_in, c_in, d_co, c_co, v, o, tr, to, s), "lsnTickRun behind the resets");
+                }
+            };
+            std::thread a(worker, s1), b(worker, s2);
+            a.join();
+            b.join();
+        }
+        works(lsnTickSetTemporal(tk, 0, 0, 0), "lsnTickSetTemporal(off)");
+        works(lsnTickSetBackground(tk, 0, 0, 0), "lsnTickSetBackground(off)");
+        for (void *q : {d_in, c_in, d_co, c_co, v, tr, (void *)o, (void *)to}) (void)fakeDevFree(q);
+        lsnTickDestroy(tk);
+    }
+    if (s1) (void)lsnStreamDestroy(0, s1);
+    if (s2) (void)lsnStreamDestroy(0, s2);
+}
+
 int main(int argc, char **argv)
 {
     const int iters = argc > 1 ? atoi(argv[1]) : 4;
     null_sweep();
     exchange_null_sweep();
+    stateful_stages();
     ragged_rigs(3 * iters);
     parser_fuzz(20 * iters);
     {
