@@ -270,6 +270,33 @@ int lsnFusionColorTransfer(LsnFusion *plan, const void *d_depth_maps, void *d_ve
 int lsnFusionColorDiagnostics(LsnFusion *plan, int tick, unsigned char *confidence, int *coverage, int *pairs, double *transforms,
                               void *stream);
 
+/* Colour blending across views, in place on the output of lsnFusionRun / lsnFusionRunMesh (behind lsnFusionColorTransfer when both run):
+ * d_depth_maps the depth maps that call read, d_vertices / d_offsets what it wrote; every tick on its own, asynchronous on `stream`.
+ * Not in the reference: defined.  The colour of a vertex of sensor j becomes, per channel, floor((sum w c +
+ * floor(W / 2)) / W) over its own term -- w the confidence level of its pixel (1 .. 20: lsnFusionColorDiagnostics' maps), c its colour --
+ * and one term per other sensor i in which it projects (the colour transfer's projection) onto a pixel (x, y) of i's frame with
+ * projected depth d1 != 0, depth_i[y, x] = d2 > 0, |d1 - d2| < depth_tol (mm), a vertex of i at that pixel and confidence
+ * w = conf_i[y, x] >= min_confidence: that confidence, that vertex's colour.  Every term reads the colours as they were when the call
+ * started (the call snapshots them), so the result depends on no order.  A vertex without a partner keeps its bytes; A, X, Y, Z, the
+ * offsets and the triangles never change.  depth_tol <= 0 or min_confidence > 20: off, nothing is touched; min_confidence < 1 is read
+ * as 1; a plan of one sensor: nothing to do.  At most 32 sensors; mixed frame sizes are allowed.  Returns 0, -1 on error.
+ * The blend rebuilds the index the plan's stages share (colour transfer, overlay merge, outlier filter): what their diagnostics keep in
+ * that index -- the confidence maps, nVertices -- is valid only until it runs, as it is between any two of them.
+ * lsnFusionColorBlendDiagnostics (synchronises `stream`): for tick `tick` of the last blend, per sensor (n_maps entries each) the
+ * vertices that had at least one partner, the partner terms they summed and the sum over R, G, B of |new - old|; any pointer may be
+ * NULL.  Returns the tick's number of blended vertices, -1 on error.  (The counters are the blend's own: they stay until the next one; a
+ * call that is off leaves zeros.)
+ * lsnSetColorBlend: the process-wide switch of the blend in generateMeshFromDepthMaps and lsnCorrectAndGenerateMesh (every host flow;
+ * with $LSN_HOST_DEVICES the call runs on the first device alone, like a call with colour transfer): behind the colour transfer when
+ * bcolor_transfer is set, in front of the overlay merge.  generateVerticesFromDepthMap never blends (one sensor).  Initially
+ * $LSN_COLOR_BLEND="depth_tol,min_confidence" (e.g. "20,5"; unset or malformed: off); every call reads the current value.  The previous
+ * pair goes to prev_depth_tol / prev_min_confidence (either may be NULL); returns 0. */
+int lsnFusionColorBlend(LsnFusion *plan, int depth_tol, int min_confidence, const void *d_depth_maps, void *d_vertices, const int *d_offsets,
+                        void *stream);
+int lsnFusionColorBlendDiagnostics(LsnFusion *plan, int tick, int *blended_per_sensor, long long *partners_per_sensor,
+                                   long long *abs_change_per_sensor, void *stream);
+int lsnSetColorBlend(int depth_tol, int min_confidence, int *prev_depth_tol, int *prev_min_confidence);
+
 /* Cross-view overlay merge (generateMeshFromDepthMaps' bgenerate_triangles stage) on the output of lsnFusionRun / lsnFusionRunMesh:
  * d_depth_maps the raw depth maps that call read (for the confidence maps), d_vertices / d_offsets what it wrote (read only); every tick
  * on its own, asynchronous on `stream`.  Rewrites d_triangles / d_tri_offsets in lsnFusionRunMesh's layout and capacity: the triangles

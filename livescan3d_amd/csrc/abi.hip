@@ -5,7 +5,7 @@
 // add the H2D / D2H hops around the same kernels bench.py drives directly on HBM-resident data.  How a call runs -- the
 // upload schedule, kernels storing into the pinned mesh blocks, the copy-engine flow, the call sharded over devices -- is
 // host_flows.hip; the context it runs on (lanes, pinned pool, devices) and the records a call carries host_ctx.hpp.  This file: argument
-// checks, locks, the exception trampoline, the process-wide switches of the exports' opt-in stages (the outlier filter, the overlay merge;
+// checks, locks, the exception trampoline, the process-wide switches of the exports' opt-in stages (the outlier filter, the overlay merge, the colour blend;
 // the temporal filter, background subtraction, the flying-pixel filter and depth smoothing in front of the radial correction, which current_stages() hands to a
 // call) with their setters, and the exports that need no flow (error channel, device helpers, createMesh / deleteMesh, ICP, the outbound
 // formats of the last mesh).
@@ -206,6 +206,16 @@ static PairSetting<int, float> &outlier_setting()
     return *s;
 }
 
+// (depth_tol, min_confidence) of the exports' colour blend (lsnSetColorBlend): generateMeshFromDepthMaps and lsnCorrectAndGenerateMesh read
+// it, generateVerticesFromDepthMap never does (one sensor has no partner)
+static PairSetting<int, int> &blend_setting()
+{
+    static auto *s = new PairSetting<int, int>(
+        "LSN_COLOR_BLEND", " %d , %d %n",
+        "[NativeUtils] $LSN_COLOR_BLEND=\"%s\" is not \"depth_tol,min_confidence\" (e.g. \"20,5\"): the colour blend stays off\n");
+    return *s;
+}
+
 // (neighbourhood, threshold) of the flying-pixel filter of the exports that start at raw frames, i.e. with the radial correction:
 // depthMapAndColorSetRadialCorrection and lsnCorrectAndGenerateMesh (lsnSetFlyingPixelFilter).  generateMeshFromDepthMaps and
 // generateVerticesFromDepthMap never read it: LiveScanServer calls them on the maps the radial export has just returned
@@ -378,7 +388,7 @@ static DepthStages current_stages(int n_maps, const int *widths, const int *heig
     return st;
 }
 
-// What the three mesh exports share: `call` as `name` filled it (everything but the outlier filter's setting, which is read here) runs on
+// What the three mesh exports share: `call` as `name` filled it (everything but the outlier filter's and the colour blend's settings, which are read here) runs on
 // lane `l` of the context.  0: *out_mesh is the call's mesh; -1: the call was refused or failed, *out_mesh (if there is one) is empty and,
 // unless the caller merely passed no sensors, the message is set.
 static int mesh_export(const char *name, Lane &l, MeshCall &call, Mesh *out_mesh)
@@ -392,6 +402,7 @@ static int mesh_export(const char *name, Lane &l, MeshCall &call, Mesh *out_mesh
         return -1;
     }
     outlier_setting().current(call.outlier_k, call.outlier_max_dist);
+    blend_setting().current(call.blend_tol, call.blend_min_conf);   // (MeshCall::blends(): never on one sensor)
     Ctx &c = ctx();
     if (ensure_ready(c) || fuse_host(c, l, call, out_mesh)) {
         empty_mesh(out_mesh);
@@ -438,6 +449,14 @@ extern "C" int lsnSetOutlierFilter(int k, float max_dist, int *prev_k, float *pr
 {
     return lsn::guarded("lsnSetOutlierFilter", -1, [&]() {
         outlier_setting().exchange(k, max_dist, prev_k, prev_max_dist);
+        return 0;
+    });
+}
+
+extern "C" int lsnSetColorBlend(int depth_tol, int min_confidence, int *prev_depth_tol, int *prev_min_confidence)
+{
+    return lsn::guarded("lsnSetColorBlend", -1, [&]() {
+        blend_setting().exchange(depth_tol, min_confidence, prev_depth_tol, prev_min_confidence);
         return 0;
     });
 }

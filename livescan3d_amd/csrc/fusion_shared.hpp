@@ -586,6 +586,10 @@ struct LsnFusion {
     lsn::DevBuf ct_cov, ct_pairs, ct_blk, ct_stats, ct_samples, ct_xform;
     bool ct_ready = false;
     int ct_nblk = 0;                     // sample blocks per pair (the largest sensor's pixels / 256)
+    // colour blend (color_blend.hip), allocated on first use: the colour dword of every vertex as the call found it, and the counters of
+    // the last call, three 64-bit words per (tick, sensor)
+    lsn::DevBuf cb_snap, cb_diag;
+    bool cb_ready = false;
     // overlay merge (merge.hip), allocated on its first call: intermediate triangle offsets, the reprojected maps (as first built / as
     // modified) and their pixel -> vertex maps, point_assigned, per-vertex confidence and projection, raster scratch, mapped depth / tag
     // maps, eroded mask

@@ -311,7 +311,10 @@ struct MeshCall {
     bool color_transfer = false, overlay_merge = false;   // the stages on the fused cloud (color.hip, merge.hip) ...
     int outlier_k = 0;                       // ... and the outlier filter (outlier.hip, lsnSetOutlierFilter): it runs when outlier_k > 0
     float outlier_max_dist = 0.0f;           //     and outlier_max_dist > 0
+    int blend_tol = 0, blend_min_conf = 0;   // ... and the colour blend (color_blend.hip, lsnSetColorBlend) behind the colour transfer
     DepthStages stages;                      // the stages in front of the radial correction of a call that starts with it (`radial`)
+    // the blend runs for depth_tol > 0 and min_confidence <= 20, on more than one sensor (color_blend.hip: everything else changes nothing)
+    bool blends() const { return blend_tol > 0 && blend_min_conf <= 20 && count > 1; }
 };
 
 // The calls.  The lane's lock is held by the caller; `out` is left untouched on failure (the export then returns an empty mesh).

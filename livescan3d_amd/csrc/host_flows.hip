@@ -524,6 +524,19 @@ struct HostCall {
                                call.with_triangles, l.h_off, group_end_mirror, host_out, l.stream);
     }
 
+    // The corrected maps of every group into the caller's arrays, if the call asks for them and they have not gone yet (flow 2b: the
+    // whole cloud is in HBM first, so they go in one piece).  drained: the kernels' stream has been synchronised behind the corrections.
+    int write_back_all(bool drained = false)
+    {
+        if (!back) return 0;
+        if (!drained) LSN_HIP(hipStreamSynchronize(l.stream));   // every group's corrected maps are final
+        for (size_t k = 0; k < G; k++)
+            if (write_back_runs(l, k, call.back_d, call.back_c)) return -1;
+        LSN_HIP(hipStreamSynchronize(l.back));
+        back = false;
+        return 0;
+    }
+
     // The outlier filter on the tick's cloud in l.d_out, behind the groups' launches: the cloud is filtered per sensor where it lies
     // (outlier.hip), the removed vertices' pixels become depth 0 in a copy of the maps, and the groups fuse again from that copy, which
     // every later launch of the call reads.  The corrected maps a call writes back are the unmasked ones: they go home first.
@@ -534,13 +547,7 @@ struct HostCall {
         if (l.d_masked.reserve(dbytes + 16) ||
             lsn::outlier_filter(plan, call.outlier_k, call.outlier_max_dist, run_d, l.d_out.p, l.d_off.as<int>(), l.d_masked.p, l.stream))
             return -1;
-        if (back) {
-            LSN_HIP(hipStreamSynchronize(l.stream));   // every group's corrected maps are final
-            for (size_t k = 0; k < G; k++)
-                if (write_back_runs(l, k, call.back_d, call.back_c)) return -1;
-            LSN_HIP(hipStreamSynchronize(l.back));
-            back = false;
-        }
+        if (write_back_all()) return -1;
         run_d = l.d_masked.as<char>();
         for (size_t k = 0; k < G; k++)
             if (fuse_group(k, l.groups[k], l.d_out.p, nullptr, false)) return -1;
@@ -707,9 +714,10 @@ int fuse_host_grouped(HostCall &h, Mesh *out)
     return 0;
 }
 
-// Flow 2b: colour transfer (bcolor_transfer = true) and / or the overlay merge (bgenerate_triangles = true with the merge switched on).
-// Both cross sensors, so the whole merged cloud has to be in HBM before any of it can go home: the groups fuse into d_out as in flow 2,
-// then the correction runs in place (color.hip), the merge rebuilds the triangles (merge.hip), and the mesh leaves in one copy.  Without
+// Flow 2b: colour transfer (bcolor_transfer = true), the colour blend (lsnSetColorBlend) and / or the overlay merge (bgenerate_triangles =
+// true with the merge switched on).  All cross sensors, so the whole merged cloud has to be in HBM before any of it can go home: the groups
+// fuse into d_out as in flow 2, then the correction runs in place (color.hip), the blend in place on its output (color_blend.hip), the
+// merge rebuilds the triangles (merge.hip), and the mesh leaves in one copy.  Without
 // the merge the triangles do not depend on the colours; they are built as in flow 2.  The merge reads the positions alone, so the two
 // commute.
 // With the outlier filter on (`filter`: fuse_host decides) the cloud is filtered first (HostCall::outlier_pass): everything after -- triangles,
@@ -725,6 +733,7 @@ int fuse_host_color(HostCall &h, Mesh *out, bool filter)
     if (call.with_triangles && !call.overlay_merge && lsn::run_triangles(h.plan, h.run_d, l.d_tri.p, l.d_tri_off.as<int>(), l.h_toff, false, l.stream))
         return -1;
     if (call.color_transfer && lsn::color_transfer(h.plan, h.run_d, l.d_out.p, l.d_off.as<int>(), l.stream)) return -1;
+    if (call.blends() && lsn::color_blend(h.plan, call.blend_tol, call.blend_min_conf, h.run_d, l.d_out.p, l.d_off.as<int>(), l.stream)) return -1;
     if (call.with_triangles && call.overlay_merge) {
         if (lsn::overlay_merge(h.plan, h.run_d, l.d_out.p, l.d_off.as<int>(), l.d_tri.p, l.d_tri_off.as<int>(), l.stream)) return -1;
         LSN_HIP(hipMemcpyAsync(l.h_toff, l.d_tri_off.as<int>(), sizeof(int) * (size_t)(count + 1), hipMemcpyDeviceToHost, l.stream));
@@ -739,6 +748,9 @@ int fuse_host_color(HostCall &h, Mesh *out, bool filter)
     if (nt > 0 && !(h.host_tri = pinned_get(h.c, (size_t)nt * 12))) return -1;
     LSN_HIP(hipMemcpyAsync(h.host, l.d_out.p, (size_t)nv * 16, hipMemcpyDeviceToHost, l.stream));
     if (nt > 0) LSN_HIP(hipMemcpyAsync(h.host_tri, l.d_tri.p, (size_t)nt * 12, hipMemcpyDeviceToHost, l.stream));
+    // the corrected maps of a call that starts with the correction go home behind every stage's launch, beside the mesh's download (a
+    // call with the filter has sent them already: the unmasked ones)
+    if (h.write_back_all(true)) return -1;
     LSN_HIP(hipStreamSynchronize(l.stream));
     h.tr.mark("down");
     h.commit(out, nv, nt, true);
@@ -1151,10 +1163,10 @@ int fuse_host(Ctx &c, Lane &l, const MeshCall &call, Mesh *out)
     // the outlier filter runs for k > 0 and max_dist > 0; k <= 0, max_dist <= 0 and a NaN max_dist change nothing (outlier.hip), so
     // those calls take the flows of a call without it
     const bool filter = call.outlier_k > 0 && call.outlier_max_dist > 0.0f;
-    const bool whole_cloud = call.color_transfer || call.overlay_merge || filter;
+    const bool whole_cloud = call.color_transfer || call.overlay_merge || filter || call.blends();
     // a merge call on a context with several devices ($LSN_HOST_DEVICES), more than one sensor: one sensor block per device and link --
-    // except with colour transfer, the overlay merge or the outlier filter, which need the whole cloud in HBM: that call runs on the first
-    // device alone (flow 2b)
+    // except with colour transfer, the colour blend, the overlay merge or the outlier filter, which need the whole cloud in HBM (the blend
+    // reads every other sensor's maps for every vertex): that call runs on the first device alone (flow 2b)
     if (&l == &c.merge && c.shards.size() >= 2 && call.count >= 2 && call.first == 0 && !whole_cloud) return fuse_host_sharded(c, l, call, out);
     HostCall h(c, l, call);
     if (whole_cloud) return fuse_host_color(h, out, filter);

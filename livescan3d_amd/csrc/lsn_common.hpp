@@ -181,6 +181,9 @@ int run_triangles_write(LsnFusion *p, const void *d_depth, void *d_triangles, in
 
 // lsnFusionColorTransfer on a stream (color.hip): colour transfer in place on the cloud lsnFusionRun* wrote from d_depth.
 int color_transfer(LsnFusion *p, const void *d_depth, void *d_vertices, const int *d_offsets, hipStream_t s);
+// lsnFusionColorBlend on a stream (color_blend.hip): the confidence-weighted blend across views in place on the same cloud, behind the
+// colour transfer when both run.  Takes the plan's mutex.
+int color_blend(LsnFusion *p, int depth_tol, int min_confidence, const void *d_depth, void *d_vertices, const int *d_offsets, hipStream_t s);
 // lsnFusionOverlayMerge on a stream (merge.hip): rewrites the triangles of the cloud lsnFusionRun* wrote from d_depth.
 int overlay_merge(LsnFusion *p, const void *d_depth, const void *d_vertices, const int *d_offsets, void *d_triangles, int *d_tri_offsets,
                   hipStream_t s);

@@ -615,6 +615,9 @@ int lsn::run_triangles_write(LsnFusion *p, const void *d_depth, void *d_triangle
 #include "outlier.hip"
 // What the three stages on the merged mesh share (the batch they read, their counters, the form of their plan exports):
 #include "mesh_batch.hip"
+// Colour blending across views (lsnFusionColorBlend, lsnSetColorBlend): the confidence-weighted feathering behind the colour transfer;
+// it uses the cloud index and the projection above, and the plan exports' form.
+#include "color_blend.hip"
 // Render view (lsnFusionRenderViews): the merged mesh drawn from virtual cameras, with the merge's projection and drawTriangle.
 #include "render.hip"
 // Mesh level of detail (lsnFusionSimplify): vertex clustering of the merged mesh, in front of the packers and the renderer.

@@ -98,6 +98,14 @@ class DeviceFusion:
     def color_transfer(self, depth=None, stream=None):
         self.plan.color_transfer(self._in(depth)[0], self.vertices.data_ptr(), self.offsets.data_ptr(), _stream_handle(stream))
 
+    def color_blend(self, depth_tol, min_confidence, depth=None, stream=None):
+        """Colour blending across views in place on the batch's vertices (behind color_transfer() when both run)."""
+        self.plan.color_blend(depth_tol, min_confidence, self._in(depth)[0], self.vertices.data_ptr(), self.offsets.data_ptr(),
+                              _stream_handle(stream))
+
+    def color_blend_diagnostics(self, tick=0, stream=None):
+        return self.plan.color_blend_diagnostics(tick, _stream_handle(stream))
+
     def overlay_merge(self, depth=None, stream=None):
         self.plan.overlay_merge(self._in(depth)[0], self.vertices.data_ptr(), self.offsets.data_ptr(), self.triangles.data_ptr(),
                                 self.tri_offsets.data_ptr(), _stream_handle(stream))

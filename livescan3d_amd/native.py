@@ -61,6 +61,7 @@ _PROTOTYPES = {
     "lsnHostPoolStats": (_i, [_vp, _vp, _vp]),
     "lsnSetOverlayMerge": (_i, [_i]),
     "lsnSetOutlierFilter": (_i, [_i, _f, _vp, _vp]),
+    "lsnSetColorBlend": (_i, [_i, _i, _vp, _vp]),
     "lsnSetFlyingPixelFilter": (_i, [_i, _i, _vp, _vp]),
     "lsnSetDepthSmooth": (_i, [_i, _f, _f, _vp, _vp, _vp]),
     "lsnDepthSmoothGaussian": (_i, [_i, _f, _f, _vp, _vp, _i]),
@@ -91,6 +92,8 @@ _PROTOTYPES = {
     "lsnMergeShards": (_i, [_i, _i, _i, _i, _vp, _ll, _vp, _vp, _ll, _vp, _vp]),
     "lsnFusionColorTransfer": (_i, [_vp] * 5),
     "lsnFusionColorDiagnostics": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp]),
+    "lsnFusionColorBlend": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp]),
+    "lsnFusionColorBlendDiagnostics": (_i, [_vp, _i, _vp, _vp, _vp, _vp]),
     "lsnFusionOverlayMerge": (_i, [_vp] * 7),
     "lsnFusionOverlayDiagnostics": (_i, [_vp, _i, _vp, _vp, _vp, _vp]),
     "lsnFusionOutlierFilter": (_i, [_vp, _i, _f, _vp, _vp, _vp, _vp, _vp]),
@@ -311,6 +314,14 @@ def set_outlier_filter(k, max_dist):
     return pk.value, pd.value
 
 
+def set_color_blend(depth_tol, min_confidence):
+    """lsnSetColorBlend: the process-wide (depth_tol, min_confidence) of the colour blend in generate_mesh_from_depth_maps and
+    correct_and_generate_mesh (depth_tol <= 0 or min_confidence > 20: off).  Returns the previous pair."""
+    pt, pc = C.c_int(0), C.c_int(0)
+    _check(lib().lsnSetColorBlend(int(depth_tol), int(min_confidence), C.byref(pt), C.byref(pc)), "lsnSetColorBlend")
+    return pt.value, pc.value
+
+
 def set_flying_pixel_filter(neighbourhood, threshold):
     """lsnSetFlyingPixelFilter: the process-wide (neighbourhood, threshold) of the flying-pixel filter in the exports that start with the
     radial correction (radial_correction, correct_and_generate_mesh); neighbourhood <= 0: off.  Returns the previous pair."""
@@ -410,11 +421,12 @@ def _raise_if_empty(mesh):
 
 
 def generate_mesh_from_depth_maps(depth_maps, depth_colors, widths, heights, intr, wt, bounds,
-                                  color_transfer=False, generate_triangles=False, overlay_merge=None, outlier_filter=None):
+                                  color_transfer=False, generate_triangles=False, overlay_merge=None, outlier_filter=None, color_blend=None):
     """KinectServer.GenerateMesh (KinectServer.cs:354-374).  Returns (vertices[VERTEX_DTYPE], triangles int32).
     overlay_merge: None leaves the process-wide switch (lsnSetOverlayMerge) as it is; True / False sets it for this call alone.
-    outlier_filter: None leaves the process-wide outlier filter (lsnSetOutlierFilter) as it is; (k, max_dist) sets it for this call alone."""
-    with _Scoped(set_outlier_filter, outlier_filter), \
+    outlier_filter: None leaves the process-wide outlier filter (lsnSetOutlierFilter) as it is; (k, max_dist) sets it for this call alone.
+    color_blend: None leaves the process-wide colour blend (lsnSetColorBlend) as it is; (depth_tol, min_confidence) sets it for this call alone."""
+    with _Scoped(set_outlier_filter, outlier_filter), _Scoped(set_color_blend, color_blend), \
             _Scoped(lambda on: (set_overlay_merge(on),), None if overlay_merge is None else (overlay_merge,)):
         require_gpu()
         n, dm, dc, widths, heights, intr, wt, b = _host_args(depth_maps, depth_colors, widths, heights, intr, wt, bounds)
@@ -486,13 +498,13 @@ def radial_correction(depth_maps, depth_colors, widths, heights, intr, flying_pi
 
 
 def correct_and_generate_mesh(depth_maps, depth_colors, widths, heights, intr, wt, bounds, write_back=True, outlier_filter=None,
-                              flying_pixels=None, depth_smooth=None, temporal_filter=None, background=None):
+                              flying_pixels=None, depth_smooth=None, temporal_filter=None, background=None, color_blend=None):
     """One call per tick (extension): radial correction + merge call with a single upload.  Returns (vertices, triangles,
     corrected depth as uint8, corrected colours); with write_back=False the last two are the untouched inputs.
-    outlier_filter: as for generate_mesh_from_depth_maps (the corrected maps written back are the unmasked ones).
+    outlier_filter / color_blend: as for generate_mesh_from_depth_maps (the corrected maps written back are the unmasked ones).
     flying_pixels / depth_smooth / temporal_filter / background: as for radial_correction (the corrected maps written back are the filtered,
     subtracted, smoothed, corrected ones)."""
-    with _Scoped(set_temporal_filter, temporal_filter), _Scoped(set_background, background), _Scoped(set_flying_pixel_filter, flying_pixels), _Scoped(set_depth_smooth, depth_smooth), _Scoped(set_outlier_filter, outlier_filter):
+    with _Scoped(set_temporal_filter, temporal_filter), _Scoped(set_background, background), _Scoped(set_flying_pixel_filter, flying_pixels), _Scoped(set_depth_smooth, depth_smooth), _Scoped(set_outlier_filter, outlier_filter), _Scoped(set_color_blend, color_blend):
         require_gpu()
         n, dm, dc, widths, heights, intr, wt, b = _host_args(depth_maps, depth_colors, widths, heights, intr, wt, bounds, copy=True)
         mesh = Mesh()
@@ -739,6 +751,21 @@ class FusionPlan(_Handle):
         k = _nonneg(lib().lsnFusionColorDiagnostics(self._h, int(tick), _ptr(conf), _ptr(cov), _ptr(pairs), _ptr(xf), stream or None), "lsnFusionColorDiagnostics")
         return {"confidence": conf[:self.pixels_per_tick], "coverage": cov,
                 "pairs": [(int(pairs[2 * q]), int(pairs[2 * q + 1])) for q in range(k)], "transforms": xf[:k].copy()}
+
+    def color_blend(self, depth_tol, min_confidence, d_depth, d_vertices, d_offsets, stream=0):
+        """Colour blending across views in place on the clouds run() / run_mesh() wrote from d_depth (behind color_transfer() when both
+        run); every tick on its own.  depth_tol <= 0 or min_confidence > 20: off."""
+        _check(lib().lsnFusionColorBlend(self._h, int(depth_tol), int(min_confidence), d_depth, d_vertices, d_offsets, stream or None),
+               "lsnFusionColorBlend")
+
+    def color_blend_diagnostics(self, tick=0, stream=0):
+        """What the last color_blend() did to one tick, per sensor: {"blended": int32[n] (vertices with at least one partner), "partners":
+        int64[n] (partner terms), "abs_change": int64[n] (sum over R, G, B of |new - old|), "n_blended": int}."""
+        n = self.n_maps
+        blended, partners, change = np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.int64), np.zeros(n, dtype=np.int64)
+        k = _nonneg(lib().lsnFusionColorBlendDiagnostics(self._h, int(tick), _ptr(blended), _ptr(partners), _ptr(change), stream or None),
+                    "lsnFusionColorBlendDiagnostics")
+        return {"blended": blended, "partners": partners, "abs_change": change, "n_blended": k}
 
     def overlay_merge(self, d_depth, d_vertices, d_offsets, d_triangles, d_tri_offsets, stream=0):
         """Overlay merge (bgenerate_triangles) on the clouds run() / run_mesh() wrote from d_depth: rewrites the triangles and their
