@@ -53,13 +53,18 @@ def walk(s):
 
 def project_view(verts, intr7, wt12, w, h):
     """(x, y, d, drawable) of every vertex in the view."""
-    x, y, d = color_ref.project(verts["X"], verts["Y"], verts["Z"], intr7, wt12)
+    with np.errstate(invalid="ignore"):      # (a NaN or an inf in a vertex: the conversion gives INT_MIN)
+        x, y, d = color_ref.project(verts["X"], verts["Y"], verts["Z"], intr7, wt12)
     return x, y, d, (x >= 0) & (x < w) & (y >= 0) & (y < h) & (d != 0)
 
 
-def render(verts, tris, intr7, wt12, w, h, labels=None):
+def render(verts, tris, intr7, wt12, w, h, labels=None, terms=None):
     """One view of one tick.  verts: VERTEX_DTYPE; tris: (m, 3) vertex indices, or None for points; labels: the triangles' indices
-    (default 0 .. m-1: their positions).  Returns (depth u16 (h, w), rgb u8 (h, w, 3), {"drawn", "pixels", "boxes"})."""
+    (default 0 .. m-1: their positions).  Returns (depth u16 (h, w), rgb u8 (h, w, 3), {"drawn", "pixels", "boxes"}).
+    terms: a list that receives one record of the intermediate values (what the witnesses of tests/test_render_boundary_ref.py read):
+    x, y, d, ok per vertex; in mesh mode keep per triangle, den per kept triangle, every candidate (ck its triangle, cx, cy, cval,
+    cw1, cw2, cw3; val 0 included), and per winning pixel wp (y * w + x), wk (its triangle) and v (the three float32 colour sums, the
+    0.5 not yet added)."""
     assert 1 <= w <= MAX_SIDE and 1 <= h <= MAX_SIDE
     nv = len(verts)
     x, y, d, ok = project_view(verts, intr7, wt12, w, h)
@@ -69,6 +74,7 @@ def render(verts, tris, intr7, wt12, w, h, labels=None):
     depth = np.zeros(w * h, dtype=np.uint16)
     rgb = np.zeros((w * h, 3), dtype=np.uint8)
     info = {"drawn": 0, "pixels": 0, "boxes": np.zeros(0, np.int64)}
+    rec = {"x": x, "y": y, "d": d, "ok": ok}
     if tris is None:
         g = np.flatnonzero(ok)
         p = y[g] * w + x[g]
@@ -85,11 +91,14 @@ def render(verts, tris, intr7, wt12, w, h, labels=None):
         keep[inr] = np.all(ok[tris[inr]], axis=1)
         t, lab = tris[keep], labels[keep]
         info["drawn"] = int(keep.sum())
+        rec.update(keep=keep, den=np.zeros(0, np.int64), wp=np.zeros(0, np.int64), wk=np.zeros(0, np.int64), v=np.zeros((0, 3), f32),
+                   **{c: np.zeros(0, np.int64) for c in ("ck", "cx", "cy", "cval")}, **{c: np.zeros(0, f32) for c in ("cw1", "cw2", "cw3")})
         if len(t):
             i1, i2, i3 = t[:, 0], t[:, 1], t[:, 2]
             s = merge_ref.triangle_setup(x[i1], y[i1], d[i1], x[i2], y[i2], d[i2], x[i3], y[i3], d[i3])
             info["boxes"] = np.where(s["den"] != 0, (s["maxx"] - s["minx"]) * (s["maxy"] - s["miny"]), 0)
             k, px, py, val, w1, w2, w3 = walk(s)
+            rec.update(den=s["den"], ck=lab[k], cx=px, cy=py, cval=val, cw1=w1, cw2=w2, cw3=w3)
             seen = val != 0                                                              # candidates of val 0 are skipped
             k, px, py, val, w1, w2, w3 = (a[seen] for a in (k, px, py, val, w1, w2, w3))
             p = py * w + px
@@ -100,10 +109,14 @@ def render(verts, tris, intr7, wt12, w, h, labels=None):
             assert len(np.unique(p)) == len(p)
             depth[p] = key[p] >> 32
             c1, c2, c3 = col[i1[k]], col[i2[k]], col[i3[k]]
-            v = ((c1 * w1[:, None] + c2 * w2[:, None]) + c3 * w3[:, None]) + f32(0.5)
+            v0 = (c1 * w1[:, None] + c2 * w2[:, None]) + c3 * w3[:, None]
+            v = v0 + f32(0.5)
             assert v.dtype == f32
             rgb[p] = np.clip(np.trunc(v), 0, 255).astype(np.uint8)
+            rec.update(wp=p, wk=lab[k], v=v0)
     info["pixels"] = int((depth != 0).sum())
+    if terms is not None:
+        terms.append(rec)
     return depth.reshape(h, w), rgb.reshape(h, w, 3), info
 
 

@@ -95,13 +95,14 @@ CLOUDS_PREFILL = 249   # -7 as a byte: what DeviceFusion prefills its tables wit
 
 
 class Clouds:
-    """A plan of one `size` sensor per tick with hand-made clouds uploaded as its ticks: clouds[k] = (vertices, triangles or None)."""
+    """A plan of one `size` sensor per tick with hand-made clouds uploaded as its ticks: clouds[k] = (vertices, triangles or None).
+    vertex_fill: the byte that lies behind every tick's vertices (never read)."""
 
-    def __init__(self, torch, clouds, size=(64, 48)):
+    def __init__(self, torch, clouds, size=(64, 48), vertex_fill=0):
         self.torch, self.clouds, self.T = torch, clouds, len(clouds)
         self.plan = native.FusionPlan(0, self.T, [size[0]], [size[1]])
         cap = self.cap = self.plan.capacity
-        v = np.zeros((self.T, cap, 16), np.uint8)
+        v = np.full((self.T, cap, 16), vertex_fill, np.uint8)
         t = np.full((self.T, 2 * cap, 3), -3, np.int32)     # what lies behind a tick's triangles is never read
         off, toff = np.zeros((self.T, 2), np.int32), np.zeros((self.T, 2), np.int32)
         for k, (cv, ct) in enumerate(clouds):
@@ -125,13 +126,18 @@ class Clouds:
         assert gd.intact() and gc.intact()
         return (gd.body().cpu().numpy().view(np.uint16).reshape(self.T, V, h, w), gc.body().cpu().numpy().reshape(self.T, V, h, w, 3))
 
-    def check(self, intr, wt, w, h, points=False):
+    def check(self, intr, wt, w, h, points=False, refs=None):
+        """Renders and compares with render_ref.render, tick by tick and view by view (every view its own 7 + 12 floats).  refs: a list of
+        the restatement's (depth, rgb, info) in that order, computed elsewhere."""
         depth, rgb = self.render(intr, wt, w, h, points)
         intr, wt = np.asarray(intr, np.float32).reshape(-1, 7), np.asarray(wt, np.float32).reshape(-1, 12)
         diags = []
         for k, (cv, ct) in enumerate(self.clouds):
             for q in range(len(intr)):
-                wd, wc, info = render_ref.render(cv, None if points else (np.zeros((0, 3), np.int32) if ct is None else ct), intr[q], wt[q], w, h)
+                if refs is not None:
+                    wd, wc, info = refs[len(diags)]
+                else:
+                    wd, wc, info = render_ref.render(cv, None if points else (np.zeros((0, 3), np.int32) if ct is None else ct), intr[q], wt[q], w, h)
                 assert np.array_equal(depth[k, q], wd), (k, q, int((depth[k, q] != wd).sum()))
                 assert np.array_equal(rgb[k, q], wc), (k, q, int((rgb[k, q] != wc).any(axis=-1).sum()))
                 d = self.plan.render_diagnostics(k, q)
